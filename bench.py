@@ -11,7 +11,12 @@ all-gather of the output tiles the north star names).  Weak scaling: every rank 
 tiles.  Rank 0 prints ONE JSON line.  Weights: seeded synthetic RealESRGAN_x4plus shapes (no
 checkpoints offline), broadcast from rank 0 over RCCL.
 
-Behind the headline and OUTSIDE its timed region the same line carries:
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.  `--dump-outputs DIR`
+writes what the last timed step computed (rank 0's view: the output tiles, or the gathered tiles for N > 1) as float32 .npy
+files: `sr_tile0.npy` (the first whole output tile) and `sr_sample.npy` (a fixed, seeded sample of every output byte).
+
+With `--full`, behind the headline and OUTSIDE its timed region the same line carries `roofline` (per-kernel figures from a
+second, separate pass of the K steps, and the clock held during the timed one) and:
   N > 1:  `aoi_strong_scaling` -- BASELINE configs[2]: one 4096x4096 AOI sharded over the N ranks (strong scaling), host image
           out on rank 0 (s2sr.dist.enhance_distributed), in both flavours: plain, and with the reference's default
           enhance_crops=True post-process (main.py:204,227);
@@ -467,14 +472,20 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--group", type=int, default=int(os.environ.get("S2SR_GROUP", "0")))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the fp8 / AOI / single-tile-latency legs behind the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / per-kernel stats pass, secondary legs, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float32, a seeded sample of the output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the fp8 / AOI / single-tile-latency legs behind the headline")
     ap.add_argument("--precision", choices=["hp", "fast", "fp8"], default="hp",
                     help="hp: split-operand head/tail convs, <=1e-4 of the fp32 reference (meets the north star's 1e-3); "
                          "fast: plain fp16 operands everywhere, 2e-3; fp8: BASELINE configs[4] -- the 345 RDB convs on e4m3 "
                          "operands (block-scaled fp8 MFMA), measured max-abs 4.1e-3")
     ap.add_argument("--enhance-crops", action="store_true", help="also run the CLAHE/unsharp/vegetation pass")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -567,8 +578,7 @@ def main():
     def timed(e, steps, warmup, sample_clock):
         """W warm-up steps (the second sighting of a (group, buffers) pair captures its hipGraph), then exactly K steps on the
         product's launch path (hipGraph replay of each group, no events inside) bracketed by barrier + synchronize on both
-        sides; then a second, separate pass of the same K steps with a hipEvent pair around every 7th launch of each kernel
-        family (direct launches: events cannot sit inside a graph) for the per-kernel figures -- `value` never comes from it."""
+        sides."""
         for _ in range(max(warmup, 2 * nbuf)):
             step(e)
         torch.cuda.synchronize()
@@ -592,6 +602,11 @@ def main():
             t = torch.tensor([dt], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+        return dt, g0, g1, clocks
+
+    def stats_pass(e, steps):
+        """A second, separate pass of the same K steps with a hipEvent pair around every 7th launch of each kernel family
+        (direct launches: events cannot sit inside a graph) for the per-kernel figures -- `value` never comes from it."""
         e.set_profiling(PROF_EVERY)
         e.reset_kernel_stats()
         torch.cuda.synchronize()
@@ -603,9 +618,24 @@ def main():
         stats = e.kernel_stats()
         e.set_profiling(0)
         barrier()
-        return dt, dt_prof, stats, g0, g1, clocks
+        return dt_prof, stats
 
-    dt, dt_prof, stats, g0, g1, clocks = timed(eng, a.steps, a.warmup, rank == 0)
+    def dump_outputs(out_dir: str, out: torch.Tensor):
+        """What the caller of the timed path receives from its last step: the first whole tile, and a seeded sample of 4M of
+        every output byte (the same positions in every run with the same arguments), both as float32."""
+        d = Path(out_dir)
+        d.mkdir(parents=True, exist_ok=True)
+        np.save(d / "sr_tile0.npy", out[0].cpu().numpy().astype(np.float32))
+        flat = out.reshape(-1)
+        idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=min(flat.numel(), 4_000_000)))
+        np.save(d / "sr_sample.npy", flat[torch.from_numpy(idx).to(dev)].cpu().numpy().astype(np.float32))
+
+    dt, g0, g1, clocks = timed(eng, a.steps, a.warmup, a.full and rank == 0)
+    if a.dump_outputs and rank == 0:
+        last = (step_no[0] - 1) % nbuf
+        dump_outputs(a.dump_outputs, gs[last] if dist is not None else (y2s[last] if a.enhance_crops else ys[last]))
+    if a.full:
+        dt_prof, stats = stats_pass(eng, a.steps)
 
     if rank == 0:
         ms = dt / a.steps * 1e3
@@ -629,8 +659,9 @@ def main():
                        "precision": PRECISION_TEXT[a.precision],
                        "rccl_ranks_seen": dist.get_world_size() if dist is not None else 1,
                        "collective_backend": backend if dist is not None else None},
-            "roofline": roofline_block(stats, a.precision, a.group, B, dt_prof, a.steps, g0, g1),
         }
+        if a.full:
+            line["roofline"] = roofline_block(stats, a.precision, a.group, B, dt_prof, a.steps, g0, g1)
         if clocks:   # what the cap leaves: the same dense peak at the clock the part actually held
             pk = PEAK * clocks["sclk_mhz"] / 2400.0
             line["roofline"]["held_clock"] = dict(clocks, peak_at_clock=round(pk, 1),
@@ -647,7 +678,7 @@ def main():
     # the image; windows in contiguous blocks per rank, each block in chunks; chunk k's outputs are gathered to rank 0 on a
     # communication stream under chunk k+1's compute, stitched band by band and landed in a page-locked host image
     # (s2sr.dist.enhance_distributed).  Timed: host image in -> host image out on rank 0, barrier to barrier, max over ranks.
-    if dist is not None and not a.no_secondary:
+    if dist is not None and a.full and not a.no_secondary:
         try:
             from s2sr.dist import NativeBackend, enhance_distributed
             be = NativeBackend(eng, local)
@@ -688,11 +719,12 @@ def main():
                 line["aoi_strong_scaling"] = {"error": f"{type(e).__name__}: {e}", "n_gpus": world}
 
     # ---- behind the headline, same process, one GPU only: the fp8 line, the paths /api/wow really takes, one tile's latency
-    if world == 1 and not a.no_secondary:
+    if world == 1 and a.full and not a.no_secondary:
         sec = {}
         if a.precision != "fp8":
             e8 = make_engine("fp8")
-            dt8, dtp8, st8, h0, h1, _ = timed(e8, a.steps, a.warmup, False)
+            dt8, h0, h1, _ = timed(e8, a.steps, a.warmup, False)
+            dtp8, st8 = stats_pass(e8, a.steps)
             v8 = B * a.steps / dt8 * 16 * TILE * TILE / 1e6
             sec["fp8"] = {"value": round(v8, 2), "unit": "SR-MP/s", "ms_per_step": round(dt8 / a.steps * 1e3, 3), "dtype": "f8e4m3",
                           "tolerance": "max-abs 4.1e-3 (noise goldens) / 5.4e-3 (the reference's real image) vs the fp32 reference (tests/test_gpu_net.py test_fp8_mode_*, test_real_image_golden): OUTSIDE the 1e-3 "
@@ -864,7 +896,7 @@ def main():
         if rank == 0:
             line["secondary"] = sec
     if rank == 0:
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(tiles_np)
         print(json.dumps(line), flush=True)
     barrier()

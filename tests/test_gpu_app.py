@@ -373,7 +373,8 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     s.close()
     env = dict(os.environ, S2SR_BENCH_SAME_DEVICE="1", S2SR_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", S2SR_BENCH_AOI="1024")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(port), str(repo / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4"],
+                        "--master-port", str(port), str(repo / "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4",
+                        "--full"],
                        capture_output=True, text=True, env=env, timeout=600, cwd=str(repo))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -388,6 +389,37 @@ def test_bench_two_ranks_rehearsal(tmp_path):
     assert "blocks of 8 per rank" in ao["workload"]
     # ... and in the flavour the reference requests by default (enhance_crops=True: band histograms, LUTs, finish in row bands)
     assert ao["enhance_crops"]["value"] > 0 and ao["enhance_crops"]["seconds"] > 0
+
+
+def test_bench_plain_run_dumps_the_last_steps_outputs(tmp_path):
+    """A plain bench.py run prints the headline line alone (no stats pass, no legs behind it), times exactly --steps steps, and
+    --dump-outputs writes what its last step computed: the first whole SR tile and the seeded sample of every output byte, both
+    float32, equal to the engine's own output on the same seeded tiles and weights."""
+    import subprocess
+    import sys
+    from pathlib import Path
+    from s2sr.synth import synthetic_tiles
+    repo = Path(__file__).resolve().parent.parent
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, str(repo / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=str(repo))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f16" and d["higher_is_better"] is True
+    assert not {"roofline", "secondary", "cpu_baseline"} & set(d)
+    tile0 = np.load(out_dir / "sr_tile0.npy")
+    sample = np.load(out_dir / "sr_sample.npy")
+    assert tile0.dtype == sample.dtype == np.float32 and tile0.shape == (1024, 1024, 3) and sample.shape == (4_000_000,)
+    assert tile0.nbytes + sample.nbytes <= 64 << 20
+    e = native.Engine(num_block=23, device=0, precision=native.PREC_F16_HP)
+    e.load_state_dict(synthetic_state_dict(23, seed=0))
+    want = e.forward_batch_u8(synthetic_tiles(4, 256, seed=1234)).copy()
+    e.close()
+    assert np.array_equal(tile0, want[0].astype(np.float32))
+    idx = np.sort(np.random.default_rng(0).integers(0, want.size, size=4_000_000))
+    assert np.array_equal(sample, want.reshape(-1)[idx].astype(np.float32))
 
 
 def test_job_result_beyond_2_gib(monkeypatch, tmp_path):

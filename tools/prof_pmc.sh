@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for mode in hp fp8; do
   echo "[prof] kernel trace of bench.py --precision $mode"
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$mode -- python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-secondary --precision $mode > $OUT/trace_$mode.log 2>&1
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$mode -- python3 $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-secondary --precision $mode > $OUT/trace_$mode.log 2>&1
   echo "[prof] trace $mode rc=$?"
 done
 for mode in hp fp8; do

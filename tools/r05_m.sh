@@ -3,7 +3,7 @@
 R=$PWD; OUT=$R/gpurun_out/${1:-r05_m}; mkdir -p $OUT
 for cfg in "16 32" "10 30" "12 36" "14 28" "20 40" "24 48" "16 32"; do
   set -- $cfg
-  timeout -k 10 200 python3 bench.py --steps 10 --warmup 3 --no-secondary --no-cpu-baseline --group $1 --batch $2 > $OUT/bench_g$1.json 2> $OUT/bench_g$1.err
+  timeout -k 10 200 python3 bench.py --full --steps 10 --warmup 3 --no-secondary --no-cpu-baseline --group $1 --batch $2 > $OUT/bench_g$1.json 2> $OUT/bench_g$1.err
   python3 - $OUT/bench_g$1.json $1 $2 <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
