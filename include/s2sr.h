@@ -297,8 +297,10 @@ uint8_t s2sr_debug_f32_to_e4m3(float v);
 size_t s2sr_debug_pack_f8_bytes(int32_t cin, int32_t cout);
 int  s2sr_debug_pack_f8(const float* w, int32_t cin, int32_t cout, uint8_t* out, int32_t* wscale);
 
-/* test hook: one 3x3 conv layer on NCHW fp32 host tensors through the production kernel
- * (upsample != 0 -> nearest-2x on load).  act: 0 none, 1 LeakyReLU(0.2). */
+/* test hook: one 3x3 conv layer on NCHW fp32 host tensors through the generic fp16 form of conv3x3.hip (the EPI_DEBUG
+ * instantiations: plain fp16 operands, no split-operand stages, no sub-pixel or whole-patch forms, none of the head / tail
+ * epilogues -- no launch of the net runs this form; s2sr_debug_forward_taps checks what does).
+ * upsample != 0 -> nearest-2x on load.  act: 0 none, 1 LeakyReLU(0.2). */
 int  s2sr_debug_conv(s2sr_handle* h, const float* x, int32_t N, int32_t Cin, int32_t H, int32_t W,
                      const float* weight, const float* bias, int32_t Cout, int32_t upsample,
                      int32_t act, float* y);
@@ -358,6 +360,38 @@ typedef struct s2sr_debug_trunk_args {
     float* y_aux;           /* kinds 4-5: [N,64,H,W], may be NULL */
 } s2sr_debug_trunk_args;
 int  s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a);
+
+/* test hook: ONE batch through the production forward (the launch schedule of s2sr_forward_batch_u8 / s2sr_forward_f32, with the
+ * handle's weights and switches; run eagerly, never from a captured graph), then every tensor the six head / tail convs read or
+ * write, decoded on the host to fp32 over the PADDED extent [n, C, Hp, Wp] of the launch images (halo and round-up slack
+ * included).  Input: `tiles` [B, th, tw, 3] u8, or `x` [B, 3, th, tw] fp32 in [0, 1] (exactly one of them); `job_windows`
+ * (>= B, 0 = B) sizes the window mosaic as s2sr_forward_part_u8_dev does.  A batch that needs more than one launch group or more
+ * than one mosaic segment is refused (S2SR_E_INVALID); after the call the workspace holds exactly this batch.
+ * The geometry fields are always filled; the batch runs only when at least one buffer is given.  Buffers (NULL: skip):
+ *   tap[S2SR_TAP_P0]       16 ch  the packed input (fp16)
+ *   tap[S2SR_TAP_F]        64 ch  conv_first's fp32 output (the global skip)
+ *   tap[S2SR_TAP_TRUNK_HI] 64 ch  the trunk output conv_body reads: fp16 hi
+ *   tap[S2SR_TAP_TRUNK_LO] 64 ch  ... its lo as stored: fp16, or e4m3(lo * 2^trunk_lo_exp) (the value lo is returned)
+ *   tap[S2SR_TAP_T8]      128 ch  conv_body's e4m3 operand planes: ch 0-63 the lo8 bytes' values * 2^-11, ch 64-127 the hi8 values
+ *   tap[S2SR_TAP_U0 + k]   64 ch  conv_body (k 0), up1, up2, hr outputs: fp16 hi (U1 at 2x, U2 and U3 at 4x)
+ *   tap[S2SR_TAP_U0LO + k] 128 ch their e4m3 planes as T8 (split-operand tail only; hi8 planes that are not written read as 0)
+ *   out_f32 [B, 3, 4th, 4tw], out_u8 [B, 4th, 4tw, 3]: the outputs of the same run.
+ * `avail` bit t: tap t exists in this mode. */
+enum { S2SR_TAP_P0 = 0, S2SR_TAP_F, S2SR_TAP_TRUNK_HI, S2SR_TAP_TRUNK_LO, S2SR_TAP_T8, S2SR_TAP_U0, S2SR_TAP_U1, S2SR_TAP_U2,
+       S2SR_TAP_U3, S2SR_TAP_U0LO, S2SR_TAP_U1LO, S2SR_TAP_U2LO, S2SR_TAP_U3LO, S2SR_TAP_COUNT };
+typedef struct s2sr_debug_taps {
+    int32_t n;                          /* out: launch images */
+    int32_t H[3], W[3], Hp[3], Wp[3];   /* out: per scale 1x / 2x / 4x: live extent of a launch image, padded plane dims */
+    int32_t mos_kx, mos_ky, mos_wh, mos_ww, mos_count;   /* out: window mosaic of the launch (all 0: one window per image) */
+    int32_t trunk_lo_exp;               /* out: -1 trunk lo stored as fp16, else as e4m3 at 2^trunk_lo_exp */
+    int32_t avail;                      /* out: bit t = tap t exists */
+    int32_t reserved[4];
+    float* tap[S2SR_TAP_COUNT];         /* in */
+    float* out_f32;                     /* in */
+    uint8_t* out_u8;                    /* in */
+} s2sr_debug_taps;
+int  s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw,
+                             int32_t job_windows, s2sr_debug_taps* t);
 
 /* diagnostic: time one RDB-shaped conv (cin in {64,96,128,160,192}; cout 32 -> conv1..4 form,
  * cout 64 -> conv5 form) over N images of HxW, `iters` launches; avg_us = mean launch time from

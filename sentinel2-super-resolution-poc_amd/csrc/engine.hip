@@ -187,6 +187,9 @@ struct s2sr_handle {
     std::vector<GraphEntry> graphs;
     uint64_t graph_clock = 0;
     int64_t graph_replays = 0, graph_captures = 0;
+    // where the last run_net left the trunk output conv_body reads (it differs between the w4, fp8 and 8-wave paths);
+    // read by s2sr_debug_forward_taps only
+    struct TrunkRec { const char* hi = nullptr; uint64_t hi_img = 0; const char* lo = nullptr; uint64_t lo_img = 0; int lo_exp = -1; } trunk_rec;
 };
 
 namespace {
@@ -616,6 +619,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
             }
         trunk_hi = w.D[cur]; trunk_hi_img = 12 * w.blk1; trunk_lo = w.T;
     }
+    h->trunk_rec = {trunk_hi, trunk_hi_img, trunk_lo, (uint64_t)(trunk_lo_exp >= 0 ? 2 : 4) * w.blk1, trunk_lo_exp};
     const bool hp = w.hp;   // split-operand head/tail: inputs as (hi, lo) pairs, outputs write both halves
     {   // conv_body + global skip; its input is the trunk: hi = x, lo = trunk lo (all zero in fp8 mode: the trunk is fp16 there)
         ConvParams p = b;
@@ -2745,6 +2749,123 @@ int s2sr_debug_bench_conv(s2sr_handle* h, int32_t N, int32_t H, int32_t W, int32
     }
     hipEventDestroy(e0); hipEventDestroy(e1);
     dev_free(D0); dev_free(D1); dev_free(T); dev_free(Rr); dev_free(d_w); dev_free(d_b);
+    return S2SR_OK;
+}
+
+// The tail's per-layer parity hook: one batch through forward_dev -> run_net as production runs it (eagerly: graphs off for the
+// call), then the tensors of the six head / tail convs copied out of the workspace and decoded on the host.
+int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, int32_t job_windows,
+                            s2sr_debug_taps* t) {
+    if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    const int job = job_windows > B ? job_windows : B;
+    // the plan forward_dev follows (s2sr_forward_part_u8_dev: the job's mosaic), and the one segment this batch must be
+    Mosaic plan = tiles ? pick_mosaic(h, job, th, tw) : Mosaic();
+    const int per = plan.on() ? plan.kx * plan.ky : 1;
+    int skx = plan.kx, sky = plan.ky;
+    if (plan.on()) {
+        if (B / per && B % per) return fail(h, S2SR_E_INVALID, "batch spans two mosaic segments (full mosaics and a remainder)");
+        if (B < per) mosaic_remainder(B, plan.kx, plan.ky, &skx, &sky);
+    }
+    const int sper = plan.on() ? skx * sky : 1;
+    const int NI = (B + sper - 1) / sper;
+    const int IH = plan.on() ? plan.ky * (th + 1) - 1 : th, IW = plan.on() ? plan.kx * (tw + 1) - 1 : tw;
+    const int SH = plan.on() ? sky * (th + 1) - 1 : th, SW = plan.on() ? skx * (tw + 1) - 1 : tw;
+    if (NI > group_size(h, (job + per - 1) / per, IH, IW)) return fail(h, S2SR_E_INVALID, "batch needs more than one launch group");
+    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;
+    const bool hp = h->cfg.precision == S2SR_PREC_F16_HP || (fp8 && h->fp8_hp_tail);
+    t->n = NI;
+    for (int k = 0; k < 3; ++k) {
+        const int s = k == 0 ? 1 : 2 * k;
+        t->H[k] = s * SH; t->W[k] = s * SW; t->Hp[k] = padded(s * IH); t->Wp[k] = padded(s * IW);
+    }
+    t->mos_kx = plan.on() ? skx : 0; t->mos_ky = plan.on() ? sky : 0; t->mos_wh = plan.on() ? th : 0; t->mos_ww = plan.on() ? tw : 0;
+    t->mos_count = plan.on() ? B : 0;
+    t->trunk_lo_exp = fp8 ? -1 : (h->trunk_w4 ? h->lo_exp : -1);
+    t->avail = 0;
+    for (int k = 0; k < S2SR_TAP_COUNT; ++k)
+        if (hp || (k != S2SR_TAP_T8 && k < S2SR_TAP_U0LO)) t->avail |= 1 << k;
+    bool any = t->out_f32 || t->out_u8;
+    for (int k = 0; k < S2SR_TAP_COUNT; ++k) any = any || t->tap[k];
+    if (!any) return S2SR_OK;
+    // ---- the run, on buffers of its own
+    const size_t ib = tiles ? (size_t)B * th * tw * 3 : (size_t)B * 3 * th * tw * 4, opx = (size_t)B * 16 * th * tw;
+    DevBuf d_in, d_o8, d_o32;
+    HIPCHK(h, dev_malloc(&d_in.p, ib));
+    HIPCHK(h, dev_malloc(&d_o8.p, opx * 3));
+    HIPCHK(h, dev_malloc(&d_o32.p, opx * 3 * 4));
+    HIPCHK(h, hipMemcpyAsync(d_in.p, tiles ? (const void*)tiles : (const void*)x, ib, hipMemcpyHostToDevice, st));
+    const bool graphs = h->graphs_on;
+    h->graphs_on = false;
+    int rc = forward_dev(h, st, tiles ? (const uint8_t*)d_in.p : nullptr, tiles ? nullptr : (const float*)d_in.p, B, th, tw,
+                         t->out_u8 ? (uint8_t*)d_o8.p : nullptr, t->out_f32 ? (float*)d_o32.p : nullptr, plan.on() ? &plan : nullptr);
+    h->graphs_on = graphs;
+    if (rc) return rc;
+    HIPCHK(h, hipStreamSynchronize(st));
+    const Workspace& w = h->ws;
+    if (w.G < NI) return fail(h, S2SR_E_INVALID, "workspace fell back to a smaller launch group: the batch ran in two");
+    if (t->out_u8) HIPCHK(h, copy_blocking(h, t->out_u8, d_o8.p, opx * 3, hipMemcpyDeviceToHost));
+    if (t->out_f32) HIPCHK(h, copy_blocking(h, t->out_f32, d_o32.p, opx * 3 * 4, hipMemcpyDeviceToHost));
+    // ---- decoders: n images of `nb` planes of 32 B per pixel at `img` bytes apart -> [n][channels][Hp][Wp] fp32
+    std::vector<uint8_t> buf;
+    auto fetch = [&](const char* src, uint64_t img, int nb, size_t blk) -> int {
+        buf.resize((size_t)NI * nb * blk);
+        for (int i = 0; i < NI; ++i) HIPCHK(h, copy_blocking(h, buf.data() + (size_t)i * nb * blk, src + (size_t)i * img, (size_t)nb * blk, hipMemcpyDeviceToHost));
+        return S2SR_OK;
+    };
+    auto f16_planes = [&](float* dst, const char* src, uint64_t img, int nb, int k) -> int {   // fp16 blocked-16
+        const size_t blk = (k == 0 ? w.blk1 : k == 1 ? w.blk2 : w.blk4), np = blk / 32;
+        if (int r = fetch(src, img, nb, blk)) return r;
+        const hf16* v = (const hf16*)buf.data();
+        for (int i = 0; i < NI; ++i)
+            for (int b = 0; b < nb; ++b)
+                for (size_t q = 0; q < np; ++q)
+                    for (int c = 0; c < 16; ++c)
+                        dst[(((size_t)i * nb * 16 + b * 16 + c) * np) + q] = (float)v[(((size_t)i * nb + b) * np + q) * 16 + c];
+        return S2SR_OK;
+    };
+    auto e4m3_planes = [&](float* dst, const char* src, uint64_t img, int nb, int k, const float* scale /*[nb]*/) -> int {   // 32 ch per plane
+        const size_t blk = (k == 0 ? w.blk1 : k == 1 ? w.blk2 : w.blk4), np = blk / 32;
+        if (int r = fetch(src, img, nb, blk)) return r;
+        for (int i = 0; i < NI; ++i)
+            for (int b = 0; b < nb; ++b)
+                for (size_t q = 0; q < np; ++q)
+                    for (int c = 0; c < 32; ++c)
+                        dst[(((size_t)i * nb * 32 + b * 32 + c) * np) + q] = e4m3_to_f32(buf[(((size_t)i * nb + b) * np + q) * 32 + c]) * scale[b];
+        return S2SR_OK;
+    };
+    const float s_lo4[4] = {1.0f / 2048.0f, 1.0f / 2048.0f, 1.0f, 1.0f};
+    const int nb1 = 1;
+    if (t->tap[S2SR_TAP_P0] && (rc = f16_planes(t->tap[S2SR_TAP_P0], w.P0, w.blk1, nb1, 0))) return rc;
+    if (t->tap[S2SR_TAP_F]) {   // fp32 blocked-8: [n][8][Hp][Wp][8]
+        const size_t np = w.blk1 / 32;
+        if ((rc = fetch((const char*)w.F, 8 * w.blk1, 8, w.blk1))) return rc;
+        const float* v = (const float*)buf.data();
+        for (int i = 0; i < NI; ++i)
+            for (int b = 0; b < 8; ++b)
+                for (size_t q = 0; q < np; ++q)
+                    for (int c = 0; c < 8; ++c) t->tap[S2SR_TAP_F][(((size_t)i * 64 + b * 8 + c) * np) + q] = v[(((size_t)i * 8 + b) * np + q) * 8 + c];
+    }
+    const auto& tr = h->trunk_rec;
+    if (t->tap[S2SR_TAP_TRUNK_HI] && (rc = f16_planes(t->tap[S2SR_TAP_TRUNK_HI], tr.hi, tr.hi_img, 4, 0))) return rc;
+    if (t->tap[S2SR_TAP_TRUNK_LO]) {
+        if (tr.lo_exp >= 0) {
+            const float s = ldexpf(1.0f, -tr.lo_exp), sc[2] = {s, s};
+            if ((rc = e4m3_planes(t->tap[S2SR_TAP_TRUNK_LO], tr.lo, tr.lo_img, 2, 0, sc))) return rc;
+        } else if ((rc = f16_planes(t->tap[S2SR_TAP_TRUNK_LO], tr.lo, tr.lo_img, 4, 0))) return rc;
+    }
+    if (hp && t->tap[S2SR_TAP_T8] && (rc = e4m3_planes(t->tap[S2SR_TAP_T8], w.T8, 4 * w.blk1, 4, 0, s_lo4))) return rc;
+    const char* U[4] = {w.U0, w.U1, w.U2, w.U3};
+    const char* UL[4] = {w.U0lo, w.U1lo, w.U2lo, w.U3lo};
+    const int Uk[4] = {0, 1, 2, 2};
+    const size_t Ublk[4] = {w.blk1, w.blk2, w.blk4, w.blk4};
+    for (int u = 0; u < 4; ++u) {
+        if (t->tap[S2SR_TAP_U0 + u] && (rc = f16_planes(t->tap[S2SR_TAP_U0 + u], U[u], 4 * Ublk[u], 4, Uk[u]))) return rc;
+        if (hp && t->tap[S2SR_TAP_U0LO + u] && (rc = e4m3_planes(t->tap[S2SR_TAP_U0LO + u], UL[u], 4 * Ublk[u], 4, Uk[u], s_lo4))) return rc;
+    }
     return S2SR_OK;
 }
 

@@ -52,6 +52,18 @@ class DebugTrunkArgs(C.Structure):
                [(n, C.c_void_p) for n in ("x", "weight", "bias", "lo", "skip", "y", "y_aux")]
 
 
+TAP_NAMES = ("P0", "F", "TRUNK_HI", "TRUNK_LO", "T8", "U0", "U1", "U2", "U3", "U0LO", "U1LO", "U2LO", "U3LO")   # S2SR_TAP_*
+# channels and scale (0: 1x, 1: 2x, 2: 4x) of each tap
+TAP_SHAPE = {"P0": (16, 0), "F": (64, 0), "TRUNK_HI": (64, 0), "TRUNK_LO": (64, 0), "T8": (128, 0), "U0": (64, 0), "U1": (64, 1),
+             "U2": (64, 2), "U3": (64, 2), "U0LO": (128, 0), "U1LO": (128, 1), "U2LO": (128, 2), "U3LO": (128, 2)}
+
+
+class DebugTaps(C.Structure):
+    _fields_ = [("n", C.c_int32)] + [(n, C.c_int32 * 3) for n in ("H", "W", "Hp", "Wp")] + \
+               [(n, C.c_int32) for n in ("mos_kx", "mos_ky", "mos_wh", "mos_ww", "mos_count", "trunk_lo_exp", "avail")] + \
+               [("reserved", C.c_int32 * 4), ("tap", C.c_void_p * len(TAP_NAMES)), ("out_f32", C.c_void_p), ("out_u8", C.c_void_p)]
+
+
 class KStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double)]
@@ -135,6 +147,7 @@ _PROTOS = {
     "s2sr_debug_plan_chunks": (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "s2sr_debug_get_config": (C.c_int, [C.c_void_p, C.POINTER(DebugConfig)]),
     "s2sr_debug_conv_trunk": (C.c_int, [C.c_void_p, C.POINTER(DebugTrunkArgs)]),
+    "s2sr_debug_forward_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(DebugTaps)]),
     "s2sr_debug_mfma_ceiling": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_float)]),
     "s2sr_debug_bench_conv": (C.c_int, [C.c_void_p] + [C.c_int32] * 6 + [C.POINTER(C.c_float), C.c_void_p, C.c_int32]),
@@ -758,8 +771,41 @@ def _debug_conv_trunk(self, kind, x, weight, bias, lo=None, skip=None, form=0):
     return y if aux is None else (y, aux)
 
 
+def _debug_forward_taps(self, tiles=None, x=None, job_windows=0):
+    """One batch through the production forward, eagerly, then every tensor the head / tail convs read or write
+    (include/s2sr.h: s2sr_debug_forward_taps).  Pass u8 `tiles` [B, th, tw, 3] or fp32 `x` [B, 3, th, tw].
+    Returns (geometry dict, {tap name: fp32 [n, C, Hp, Wp]} of the taps this mode has, out_f32 [B, 3, 4th, 4tw], out_u8 [B, 4th, 4tw, 3])."""
+    assert (tiles is None) != (x is None)
+    if tiles is not None:
+        tiles = np.ascontiguousarray(tiles, np.uint8)
+        B, th, tw, c = tiles.shape
+        assert c == 3
+    else:
+        x = np.ascontiguousarray(x, np.float32)
+        B, c, th, tw = x.shape
+        assert c == 3
+    t = DebugTaps()
+    call = lambda: self._check(self._lib.s2sr_debug_forward_taps(self._h, None if tiles is None else _ptr(tiles), None if x is None else _ptr(x),
+                                                                 B, th, tw, int(job_windows), C.byref(t)), "s2sr_debug_forward_taps")
+    call()                                  # geometry only
+    geo = {"n": t.n, "H": list(t.H), "W": list(t.W), "Hp": list(t.Hp), "Wp": list(t.Wp), "mos_kx": t.mos_kx, "mos_ky": t.mos_ky,
+           "mos_wh": t.mos_wh, "mos_ww": t.mos_ww, "mos_count": t.mos_count, "trunk_lo_exp": t.trunk_lo_exp}
+    taps = {}
+    for i, name in enumerate(TAP_NAMES):
+        if t.avail >> i & 1:
+            ch, k = TAP_SHAPE[name]
+            taps[name] = np.zeros((t.n, ch, t.Hp[k], t.Wp[k]), np.float32)
+            t.tap[i] = taps[name].ctypes.data
+    out_f32 = np.zeros((B, 3, 4 * th, 4 * tw), np.float32)
+    out_u8 = np.zeros((B, 4 * th, 4 * tw, 3), np.uint8)
+    t.out_f32, t.out_u8 = out_f32.ctypes.data, out_u8.ctypes.data
+    call()
+    return geo, taps, out_f32, out_u8
+
+
 Engine.debug_config = _debug_config
 Engine.debug_conv_trunk = _debug_conv_trunk
+Engine.debug_forward_taps = _debug_forward_taps
 
 
 def _bench_conv(self, N, H, W, cin, cout, iters=20, trace_wgs=0):

@@ -1,5 +1,7 @@
-"""GPU parity of the conv kernel (through the C ABI test hook s2sr_debug_conv) against a
-plain torch fp32 conv of the same op.  Operands are pre-rounded to fp16 so that the only
+"""GPU parity of the generic fp16 form of conv3x3.hip (the EPI_DEBUG instantiations behind the C ABI test hook
+s2sr_debug_conv) against a plain torch fp32 conv of the same op.  No launch of the net runs this form: the head / tail
+convs as the net runs them (split operands, sub-pixel and whole-patch forms, their epilogues) are checked in situ by
+test_gpu_tail.py, the trunk kernels by test_gpu_trunk.py.  Operands are pre-rounded to fp16 so that the only
 difference left is fp32 accumulation order: tolerance 2e-4 * sum|a*b| scale."""
 import numpy as np
 import pytest
