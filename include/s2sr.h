@@ -393,6 +393,46 @@ typedef struct s2sr_debug_taps {
 int  s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw,
                              int32_t job_windows, s2sr_debug_taps* t);
 
+/* The trunk kernel instantiation one RDB conv launch took (launch_conv_trunk / launch_conv_trunk_f8 report it).
+ * kernel: 1 conv_trunk_f16, 2 conv_trunk_f8, 3 the row-Winograd form (conv_wino.hip; no further fields), 0 nothing recorded.
+ * rows: patch rows (the patch is rows x 32 pixels); ring: slab ring depth; full: the FULL template argument (0 generic px_live
+ * test, 1 whole patches, 2 mosaics of 276-pixel windows, 3 the extent test alone); pl: planes per pipeline stage; prod: a
+ * load-only wave; wgl: weights from global memory; loe: the lo-encoding form of conv5; wv: MFMA waves; npl: fp8 weights
+ * resident in LDS (planes; 0 = streamed); epi: the epilogue (0 conv1-4 LeakyReLU, 1 conv5 of rdb1 / rdb2, 2 conv5 of rdb3 with the
+ * RRDB skip). */
+typedef struct s2sr_debug_trunk_form {
+    int32_t kernel, ct, rows, ring, full, pl, prod, wgl, loe, wv, npl, epi;
+} s2sr_debug_trunk_form;
+
+/* test hook: ONE batch through the production forward, exactly as s2sr_debug_forward_taps runs it (same input rules, same
+ * refusals, graphs off, buffers of its own; also refused while s2sr_calibrate_fp8 runs and on the 8-wave trunk, S2SR_TRUNK=0),
+ * with the trunk fields of the RDBs [first, first + count) (global RDB index: 3 * block + rdb, < 3 * num_block) copied out at
+ * every RDB boundary and decoded to fp32 over the PADDED extent [n, C, Hp, Wp] (halo and round-up slack included):
+ *   x_hi   [count + 1][n][64][Hp][Wp]  the trunk x at boundary j (the input of RDB first + j): fp16 hi (fp8 path: the fp16 Xh)
+ *   x_lo   [count + 1][n][64][Hp][Wp]  fp16 path: its lo as stored, e4m3 planes at 2^lo_exp (the value lo is returned);
+ *                                      fp8 path: the e4m3 x planes of D8 at 2^x_exp (the value x is returned)
+ *   growth [count][n][128][Hp][Wp]     x1..x4 of each RDB: fp16, or (fp8 path) e4m3 planes at 2^g_exp (value returned)
+ *   skip_hi, skip_lo [count][n][64][Hp][Wp]  the RRDB skip a rdb3 reads (its RRDB's input: fp16 hi, or Xh; lo as x_lo, fp16
+ *                                      path only); left untouched for rdb1 / rdb2
+ *   entry_lo [n][64][Hp][Wp]           first == 0, fp16 path: conv_first's fp16 lo (T) that xh_to_fp8 turns into boundary 0's lo
+ *   form   [count][5]                  the instantiation conv1..conv5 of each RDB ran on
+ *   out_f32 / out_u8                   the outputs of the same run, as s2sr_debug_forward_taps.
+ * The geometry fields are always filled; the batch runs only when at least one buffer is given. */
+typedef struct s2sr_debug_trunk_fields {
+    int32_t first, count;               /* in */
+    int32_t n, H, W, Hp, Wp;            /* out: launch images, live extent of one, padded plane dims */
+    int32_t mos_kx, mos_ky, mos_wh, mos_ww, mos_count;   /* out: window mosaic of the launch (all 0: one window per image) */
+    int32_t fp8;                        /* out: 1 = the fp8 trunk path, 0 = the fp16 one */
+    int32_t lo_exp, x_exp, g_exp;       /* out: the scales of the path (-1 where the path has none) */
+    int32_t reserved[4];
+    float *x_hi, *x_lo, *growth, *skip_hi, *skip_lo, *entry_lo;   /* in (NULL: skip) */
+    s2sr_debug_trunk_form* form;        /* in */
+    float* out_f32;                     /* in */
+    uint8_t* out_u8;                    /* in */
+} s2sr_debug_trunk_fields;
+int  s2sr_debug_trunk_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw,
+                           int32_t job_windows, s2sr_debug_trunk_fields* t);
+
 /* diagnostic: time one RDB-shaped conv (cin in {64,96,128,160,192}; cout 32 -> conv1..4 form,
  * cout 64 -> conv5 form) over N images of HxW, `iters` launches; avg_us = mean launch time from
  * HIP events.  If trace != NULL, one extra launch of the stamped diagnostic build fills

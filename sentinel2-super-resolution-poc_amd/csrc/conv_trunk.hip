@@ -939,7 +939,7 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
 }
 
 template <int CT, int NP, int R, int EPI, bool TRACE, int PROD = 0, int FULL = 0, int WGL = 0, int LOE = S2SR_F16_LOENC, int PL = 1>
-hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st) {
+hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_form* form = nullptr) {
     using G = TG<CT, NP, R, WGL, PL>;
     constexpr bool kNoLdsBias = (EPI == EPI_LRELU) && S2SR_F16_BIASC && S2SR_F16_EARLYBIAS;    // bias as the C operand: no LDS copy
     constexpr int LDSB = kNoLdsBias ? G::RING_BYTES : G::LDS_BYTES;
@@ -983,6 +983,7 @@ hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st) {
     const int ntiles = q.tilesX * q.tilesY * p.N;
     int grid = ncu & ~7;
     if (ntiles < grid) grid = (ntiles + 7) & ~7;
+    if (form) *form = s2sr_debug_trunk_form{1, CT, G::TH, R, FULL, PL, PROD, WGL, LOE, 4, 0, EPI};
     hipLaunchKernelGGL(kern, dim3(grid), dim3(PROD ? 320 : 256), LDSB, st, q);
     return hipGetLastError();
 }
@@ -1605,7 +1606,7 @@ __global__ void __launch_bounds__((WV + PROD) * 64, PROD ? 1 : WV / 4) conv_trun
 }
 
 template <int CT, int NP, int RS, int EPI, int WV = 4, int NPL = 0, int PROD = 0>
-hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st) {
+hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_form* form = nullptr) {
     using G = TG8<CT, NP, RS, WV, NPL>;
     static_assert(G::LDS_BYTES <= 160 * 1024, "LDS rings do not fit");
     static_assert(G::NW >= 0 && G::NW < 64, "vmcnt field is 6 bits");
@@ -1644,6 +1645,7 @@ hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st) {
     const int ntiles = q.tilesX * q.tilesY * p.N;
     int grid = ncu & ~7;
     if (ntiles < grid) grid = (ntiles + 7) & ~7;
+    if (form) *form = s2sr_debug_trunk_form{2, CT, G::TH, RS, 0, 2, PROD, 0, 0, WV, NPL, EPI};
     hipLaunchKernelGGL(kern, dim3(grid), dim3((WV + PROD) * 64), G::LDS_BYTES, st, q);
     return hipGetLastError();
 }
@@ -1652,27 +1654,27 @@ hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st) {
 
 // ct = 1: conv1..4 (EPI_LRELU); ct = 2: conv5 (EPI_RDB5 / EPI_RDB5_RRDB).  Returns hipErrorNotSupported for
 // anything else.
-hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, bool trace, int force_form) {
+hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, bool trace, int force_form, s2sr_debug_trunk_form* form) {
 #if !S2SR_EXPERIMENTAL
     if (trace || force_form == 4 || (p.f16_form & 1)) return hipErrorNotSupported;     // stamped builds, loader-wave form: experimental library only
 #endif
     if (ct == 1 && epi == EPI_LRELU) {
-        if (force_form == 1) return launch_trunk_t<1, 4, 5, EPI_LRELU, false>(p, st);      // per-layer parity hook: name the patch form
-        if (force_form == 2) return launch_trunk_t<1, 8, 3, EPI_LRELU, false>(p, st);
+        if (force_form == 1) return launch_trunk_t<1, 4, 5, EPI_LRELU, false>(p, st, form);      // per-layer parity hook: name the patch form
+        if (force_form == 2) return launch_trunk_t<1, 8, 3, EPI_LRELU, false>(p, st, form);
 #if S2SR_EXPERIMENTAL
-        if (force_form == 4) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 1>(p, st);
+        if (force_form == 4) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 1>(p, st, form);
 #endif
-        if (force_form == 5) return launch_trunk_t<1, 2, 7, EPI_LRELU, false>(p, st);
-        if (force_form == 6) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 1>(p, st);    // whole-patch forms (invalid-value on ragged sizes / mosaics)
-        if (force_form == 7) return launch_trunk_t<1, 4, 5, EPI_LRELU, false, 0, 1>(p, st);
-        if (force_form == 8) return launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 1>(p, st);
+        if (force_form == 5) return launch_trunk_t<1, 2, 7, EPI_LRELU, false>(p, st, form);
+        if (force_form == 6) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 1>(p, st, form);    // whole-patch forms (invalid-value on ragged sizes / mosaics)
+        if (force_form == 7) return launch_trunk_t<1, 4, 5, EPI_LRELU, false, 0, 1>(p, st, form);
+        if (force_form == 8) return launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 1>(p, st, form);
 #if S2SR_EXPERIMENTAL
-        if (force_form == 11) return launch_trunk_t<1, 16, 2, EPI_LRELU, false, 0, 1>(p, st);   // whole 64x32 patches
+        if (force_form == 11) return launch_trunk_t<1, 16, 2, EPI_LRELU, false, 0, 1>(p, st, form);   // whole 64x32 patches
 #else
         if (force_form == 11) return hipErrorNotSupported;
 #endif
 #if S2SR_EXPERIMENTAL
-        if (force_form == 9) return launch_trunk_t<1, 8, 4, EPI_LRELU, false, 0, 1, 1>(p, st);   // whole 32x32 patches, weights from global memory (WGL)
+        if (force_form == 9) return launch_trunk_t<1, 8, 4, EPI_LRELU, false, 0, 1, 1>(p, st, form);   // whole 32x32 patches, weights from global memory (WGL)
 #else
         if (force_form == 9) return hipErrorNotSupported;
 #endif
@@ -1685,38 +1687,38 @@ hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t s
         const bool full = !trace && p.mos_py == 0 && p.H % 32 == 0 && p.W % 32 == 0 && !(p.f16_form & 4);   // whole patches only (f16_form bit 2: diagnostic off switch)
         const bool plain = !trace && p.mos_py == 0 && !(p.f16_form & 4);                                  // ragged, but no mosaic: the extent test alone
 #if S2SR_EXPERIMENTAL
-        if (n32 < 96 && trace) return launch_trunk_t<1, 2, 7, EPI_LRELU, true>(p, st);               // launch anatomy of the single-tile form
+        if (n32 < 96 && trace) return launch_trunk_t<1, 2, 7, EPI_LRELU, true>(p, st, form);               // launch anatomy of the single-tile form
 #endif
-        if (force_form == 10) return launch_trunk_t<1, 2, 3, EPI_LRELU, false, 0, 3, 0, S2SR_F16_LOENC, 2>(p, st);   // 8x32 patches, two planes per stage
+        if (force_form == 10) return launch_trunk_t<1, 2, 3, EPI_LRELU, false, 0, 3, 0, S2SR_F16_LOENC, 2>(p, st, form);   // 8x32 patches, two planes per stage
         if (n32 < 96 && !trace && !(p.f16_form & 2)) {
 #if S2SR_EXPERIMENTAL
-            if (full && (p.f16_form & 8)) return launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 1, 1>(p, st);   // r04 probe: single-tile form with the weights from global memory
+            if (full && (p.f16_form & 8)) return launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 1, 1>(p, st, form);   // r04 probe: single-tile form with the weights from global memory
 #endif
-            if (S2SR_SMALL_PL == 2 && full) return launch_trunk_t<1, 2, 3, EPI_LRELU, false, 0, 1, 0, S2SR_F16_LOENC, 2>(p, st);
-            if (S2SR_SMALL_PL == 2 && plain) return launch_trunk_t<1, 2, 3, EPI_LRELU, false, 0, 3, 0, S2SR_F16_LOENC, 2>(p, st);
-            return full ? launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 1>(p, st)
-                        : plain ? launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 3>(p, st) : launch_trunk_t<1, 2, 7, EPI_LRELU, false>(p, st);
+            if (S2SR_SMALL_PL == 2 && full) return launch_trunk_t<1, 2, 3, EPI_LRELU, false, 0, 1, 0, S2SR_F16_LOENC, 2>(p, st, form);
+            if (S2SR_SMALL_PL == 2 && plain) return launch_trunk_t<1, 2, 3, EPI_LRELU, false, 0, 3, 0, S2SR_F16_LOENC, 2>(p, st, form);
+            return full ? launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 1>(p, st, form)
+                        : plain ? launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 3>(p, st, form) : launch_trunk_t<1, 2, 7, EPI_LRELU, false>(p, st, form);
         }
         if (n32 < 192 && !trace)
-            return full ? launch_trunk_t<1, 4, 5, EPI_LRELU, false, 0, 1>(p, st)
-                        : plain ? launch_trunk_t<1, 4, 5, EPI_LRELU, false, 0, 3>(p, st) : launch_trunk_t<1, 4, 5, EPI_LRELU, false>(p, st);
+            return full ? launch_trunk_t<1, 4, 5, EPI_LRELU, false, 0, 1>(p, st, form)
+                        : plain ? launch_trunk_t<1, 4, 5, EPI_LRELU, false, 0, 3>(p, st, form) : launch_trunk_t<1, 4, 5, EPI_LRELU, false>(p, st, form);
 #if S2SR_EXPERIMENTAL
-        if (!trace && (p.f16_form & 1)) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 1>(p, st);     // S2SR_F16_LOADER=1: loader-wave form
+        if (!trace && (p.f16_form & 1)) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 1>(p, st, form);     // S2SR_F16_LOADER=1: loader-wave form
 #endif
 #if S2SR_EXPERIMENTAL
-        if (full && (p.f16_form & 8)) return launch_trunk_t<1, 8, 4, EPI_LRELU, false, 0, 1, 1>(p, st);   // r04 A/B: weights from global memory, 4-deep slab ring
+        if (full && (p.f16_form & 8)) return launch_trunk_t<1, 8, 4, EPI_LRELU, false, 0, 1, 1>(p, st, form);   // r04 A/B: weights from global memory, 4-deep slab ring
 #endif
 #if S2SR_EXPERIMENTAL
-        if (full && (p.f16_form & 16) && p.H % 64 == 0) return launch_trunk_t<1, 16, 2, EPI_LRELU, false, 0, 1>(p, st);   // 64x32 patches, double-buffered ring (r04 A/B: 5 % slower)
+        if (full && (p.f16_form & 16) && p.H % 64 == 0) return launch_trunk_t<1, 16, 2, EPI_LRELU, false, 0, 1>(p, st, form);   // 64x32 patches, double-buffered ring (r04 A/B: 5 % slower)
 #endif
-        if (full) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 1>(p, st);
-        if (plain && !(p.f16_form & 1)) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 3>(p, st);
+        if (full) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 1>(p, st, form);
+        if (plain && !(p.f16_form & 1)) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 3>(p, st, form);
         if (!trace && !(p.f16_form & 4) && p.mos_py == 277 && p.mos_ry == 276 && p.mos_px == 277 && p.mos_rx == 276)
-            return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 2>(p, st);                             // mosaics of 276-pixel windows (tile 256, pad 10)
+            return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 2>(p, st, form);                             // mosaics of 276-pixel windows (tile 256, pad 10)
 #if S2SR_EXPERIMENTAL
-        if (trace) return launch_trunk_t<1, 8, 3, EPI_LRELU, true>(p, st);
+        if (trace) return launch_trunk_t<1, 8, 3, EPI_LRELU, true>(p, st, form);
 #endif
-        return launch_trunk_t<1, 8, 3, EPI_LRELU, false>(p, st);
+        return launch_trunk_t<1, 8, 3, EPI_LRELU, false>(p, st, form);
     }
     // conv5: 16x32 patches (4 rows per wave, 4-deep ring); single tiles take 8x32 patches (2 rows per wave, 5-deep ring): one
     // 256x256 tile is 128 patches of 16x32 -- half the CUs idle through twelve MFMA-bound stages (r04 kernel trace: 24 us per
@@ -1727,20 +1729,20 @@ hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t s
         const bool small = force_form == 5 || (force_form == 0 && n16 < 192 && !(p.f16_form & 2));
 #if S2SR_EXPERIMENTAL
         if (force_form == 2)      // 16x32 patches with the LONG form of the lo encoding
-            return epi == EPI_RDB5 ? launch_trunk_t<2, 4, 4, EPI_RDB5, false, 0, 0, 0, 0>(p, st) : launch_trunk_t<2, 4, 4, EPI_RDB5_RRDB, false, 0, 0, 0, 0>(p, st);
+            return epi == EPI_RDB5 ? launch_trunk_t<2, 4, 4, EPI_RDB5, false, 0, 0, 0, 0>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5_RRDB, false, 0, 0, 0, 0>(p, st, form);
 #else
         if (force_form == 2) return hipErrorNotSupported;
 #endif
         if (force_form == 10 || (small && force_form == 0 && !trace && S2SR_SMALL_PL == 2))      // 8x32 patches, two planes per stage, double-buffered
-            return epi == EPI_RDB5 ? launch_trunk_t<2, 2, 2, EPI_RDB5, false, 0, 0, 0, S2SR_F16_LOENC, 2>(p, st)
-                                   : launch_trunk_t<2, 2, 2, EPI_RDB5_RRDB, false, 0, 0, 0, S2SR_F16_LOENC, 2>(p, st);
+            return epi == EPI_RDB5 ? launch_trunk_t<2, 2, 2, EPI_RDB5, false, 0, 0, 0, S2SR_F16_LOENC, 2>(p, st, form)
+                                   : launch_trunk_t<2, 2, 2, EPI_RDB5_RRDB, false, 0, 0, 0, S2SR_F16_LOENC, 2>(p, st, form);
         if (epi == EPI_RDB5) {
 #if S2SR_EXPERIMENTAL
-            if (trace) return small ? launch_trunk_t<2, 2, 5, EPI_RDB5, true>(p, st) : launch_trunk_t<2, 4, 4, EPI_RDB5, true>(p, st);
+            if (trace) return small ? launch_trunk_t<2, 2, 5, EPI_RDB5, true>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5, true>(p, st, form);
 #endif
-            return small ? launch_trunk_t<2, 2, 5, EPI_RDB5, false>(p, st) : launch_trunk_t<2, 4, 4, EPI_RDB5, false>(p, st);
+            return small ? launch_trunk_t<2, 2, 5, EPI_RDB5, false>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5, false>(p, st, form);
         }
-        return small ? launch_trunk_t<2, 2, 5, EPI_RDB5_RRDB, false>(p, st) : launch_trunk_t<2, 4, 4, EPI_RDB5_RRDB, false>(p, st);
+        return small ? launch_trunk_t<2, 2, 5, EPI_RDB5_RRDB, false>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5_RRDB, false>(p, st, form);
     }
     return hipErrorNotSupported;
 }
@@ -1789,7 +1791,7 @@ void pack_conv_weights_f8(const float* w, int cin, int cout, void* dst_host, int
                         }
 }
 
-hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_t st) {
+hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_t st, s2sr_debug_trunk_form* form) {
     if (ct == 1 && epi == EPI_LRELU) {
         // kernel forms, all bit-identical in their results (tests/test_gpu_net.py); p.f8_form comes from the environment at s2sr_create:
         // weights (S2SR_FP8_WSTREAM): 0 (default) conv1-3 keep theirs resident in LDS (<= 4 planes incl. a phantom, next to the 6-slot
@@ -1801,18 +1803,18 @@ hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_
 #if S2SR_EXPERIMENTAL
         const bool w8 = (p.f8_form & 8) != 0, loader = (p.f8_form & 1) == 0;
         const int stream_w = (p.f8_form >> 1) & 3;
-        if (w8) return launch_trunk8_t<1, 2, 6, EPI_LRELU, 8>(p, st);
+        if (w8) return launch_trunk8_t<1, 2, 6, EPI_LRELU, 8>(p, st, form);
         if (!loader) {
-            if (stream_w == 1 || (stream_w == 0 && p.nstage > 4)) return launch_trunk8_t<1, 4, 6, EPI_LRELU>(p, st);
-            return p.nstage <= 4 ? launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 4>(p, st) : launch_trunk8_t<1, 4, 4, EPI_LRELU, 4, 6>(p, st);
+            if (stream_w == 1 || (stream_w == 0 && p.nstage > 4)) return launch_trunk8_t<1, 4, 6, EPI_LRELU>(p, st, form);
+            return p.nstage <= 4 ? launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 4>(p, st, form) : launch_trunk8_t<1, 4, 4, EPI_LRELU, 4, 6>(p, st, form);
         }
 #else
         if (p.f8_form != 0) return hipErrorNotSupported;      // the other conv1-4 forms: experimental library only
 #endif
-        return p.nstage <= 4 ? launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 4, 1>(p, st) : launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 0, 1>(p, st);
+        return p.nstage <= 4 ? launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 4, 1>(p, st, form) : launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 0, 1>(p, st, form);
     }
-    if (ct == 2 && epi == EPI_RDB5) return launch_trunk8_t<2, 4, 4, EPI_RDB5>(p, st);
-    if (ct == 2 && epi == EPI_RDB5_RRDB) return launch_trunk8_t<2, 4, 4, EPI_RDB5_RRDB>(p, st);
+    if (ct == 2 && epi == EPI_RDB5) return launch_trunk8_t<2, 4, 4, EPI_RDB5>(p, st, form);
+    if (ct == 2 && epi == EPI_RDB5_RRDB) return launch_trunk8_t<2, 4, 4, EPI_RDB5_RRDB>(p, st, form);
     return hipErrorNotSupported;
 }
 }  // namespace s2sr

@@ -106,6 +106,15 @@ struct GraphEntry {
     uint64_t last_use = 0;
 };
 
+// s2sr_debug_trunk_taps while its batch runs: the RDB range whose fields run_net copies out (trunk_tap) and where the form
+// records of the range's conv launches go
+struct TrunkTap {
+    int first = 0, count = 0;
+    s2sr_debug_trunk_fields* t = nullptr;
+    s2sr_debug_trunk_form spare[5];     // the records of RDBs outside the range
+    s2sr_debug_trunk_form* forms(int g) { return t->form && g >= first && g < first + count ? t->form + 5 * (g - first) : spare; }
+};
+
 }  // namespace
 
 struct s2sr_handle {
@@ -190,6 +199,7 @@ struct s2sr_handle {
     // where the last run_net left the trunk output conv_body reads (it differs between the w4, fp8 and 8-wave paths);
     // read by s2sr_debug_forward_taps only
     struct TrunkRec { const char* hi = nullptr; uint64_t hi_img = 0; const char* lo = nullptr; uint64_t lo_img = 0; int lo_exp = -1; } trunk_rec;
+    TrunkTap* ttap = nullptr;     // s2sr_debug_trunk_taps' batch is running (run_net taps the trunk at its RDB boundaries); null otherwise
 };
 
 namespace {
@@ -303,6 +313,50 @@ hipError_t copy_blocking(s2sr_handle* h, void* dst, const void* src, size_t byte
 hipError_t fill_blocking(s2sr_handle* h, void* dst, int value, size_t bytes) {
     hipError_t e = hipMemsetAsync(dst, value, bytes, h->stream);
     return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
+}
+
+// ---- the test hooks' decoders (s2sr_debug_forward_taps, s2sr_debug_trunk_taps)
+float e4m3_to_f32(uint8_t b) {   // OCP e4m3fn: bias 7, subnormals, 0x7f / 0xff = NaN
+    const int e = (b >> 3) & 15, m = b & 7;
+    float v = e == 0 ? ldexpf((float)m, -9) : ldexpf((float)(8 + m), e - 10);
+    if ((b & 0x7f) == 0x7f) v = NAN;
+    return (b & 0x80) ? -v : v;
+}
+typedef _Float16 hf16;
+struct DevBuf {   // frees on scope exit: the hooks have many early returns
+    void* p = nullptr;
+    ~DevBuf() { if (p) dev_free(p); }
+};
+// n images of `nb` planes of `blk` bytes (32 B per pixel) at `img` bytes apart -> buf (blocking, on the handle's stream)
+int fetch_planes(s2sr_handle* h, std::vector<uint8_t>& buf, const char* src, uint64_t img, int n, int nb, size_t blk) {
+    buf.resize((size_t)n * nb * blk);
+    for (int i = 0; i < n; ++i) HIPCHK(h, copy_blocking(h, buf.data() + (size_t)i * nb * blk, src + (size_t)i * img, (size_t)nb * blk, hipMemcpyDeviceToHost));
+    return S2SR_OK;
+}
+// fp16 blocked-16: 16 channels per plane -> dst [n][16 nb][Hp][Wp]
+int decode_f16_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img, int n, int nb, size_t blk) {
+    std::vector<uint8_t> buf;
+    if (int r = fetch_planes(h, buf, src, img, n, nb, blk)) return r;
+    const size_t np = blk / 32;
+    const hf16* v = (const hf16*)buf.data();
+    for (int i = 0; i < n; ++i)
+        for (int b = 0; b < nb; ++b)
+            for (size_t q = 0; q < np; ++q)
+                for (int c = 0; c < 16; ++c)
+                    dst[(((size_t)i * nb * 16 + b * 16 + c) * np) + q] = (float)v[(((size_t)i * nb + b) * np + q) * 16 + c];
+    return S2SR_OK;
+}
+// e4m3 planes of 32 channels, plane b's values times scale[b] -> dst [n][32 nb][Hp][Wp]
+int decode_e4m3_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img, int n, int nb, size_t blk, const float* scale) {
+    std::vector<uint8_t> buf;
+    if (int r = fetch_planes(h, buf, src, img, n, nb, blk)) return r;
+    const size_t np = blk / 32;
+    for (int i = 0; i < n; ++i)
+        for (int b = 0; b < nb; ++b)
+            for (size_t q = 0; q < np; ++q)
+                for (int c = 0; c < 32; ++c)
+                    dst[(((size_t)i * nb * 32 + b * 32 + c) * np) + q] = e4m3_to_f32(buf[(((size_t)i * nb + b) * np + q) * 32 + c]) * scale[b];
+    return S2SR_OK;
 }
 
 int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mos_px = 0) {
@@ -435,7 +489,7 @@ int collect_events(s2sr_handle* h) {
 
 // one conv launch
 int run_conv(s2sr_handle* h, hipStream_t st, int fam, const ConvW& cw, ConvParams p, int epi, bool up,
-             bool lo_out = false) {
+             bool lo_out = false, s2sr_debug_trunk_form* form = nullptr) {   // form: where the RDB convs record their kernel form
     p.wpack = cw.d_wpack;
     p.bias = cw.d_bias;
     p.nstage = cw.nstage;
@@ -461,13 +515,15 @@ int run_conv(s2sr_handle* h, hipStream_t st, int fam, const ConvW& cw, ConvParam
     if (epi == EPI_FIRST) bytes += px * 64 * 10.0;        // lo + R + F
     if (epi == EPI_BODY) bytes += px * 64 * 4.0;
     Scope sc(h, st, fam, flops, bytes);
+    if (form) *form = s2sr_debug_trunk_form{};
     if (cw.wino) {
         HIPCHK(h, launch_conv_trunk_wino(p, st));
+        if (form) { form->kernel = 3; form->epi = epi; }
         return S2SR_OK;
     }
     if (h->trunk_w4 && (fam == F_RDB14 || fam == F_RDB5) && !up && !lo_out && !cw.f8) {
         p.f16_form = (h->f16_loader ? 1 : 0) | (h->small8 ? 0 : 2) | (h->f16_full ? 0 : 4) | (h->f16_wgl ? 8 : 0) | (h->f16_p64 ? 16 : 0);
-        const hipError_t e = launch_conv_trunk(p, cw.ct, epi, st);
+        const hipError_t e = launch_conv_trunk(p, cw.ct, epi, st, false, 0, form);
         if (e == hipSuccess) return S2SR_OK;
         if (e != hipErrorNotSupported) HIPCHK(h, e);
     }
@@ -493,6 +549,42 @@ int run_up_subpixel(s2sr_handle* h, hipStream_t st, const ConvW& cw, ConvParams 
         // (r03 counted the split-operand figure for the plain fp16 form too: 8.2 TB/s "algorithmic" in the fp8 leg)
         Scope sc(h, st, F_UP, 2.0 * 9.0 * cw.cin * cw.cout * 2.0 * px, px * (cw.f8 ? 768.0 : 384.0));
         HIPCHK(h, launch_conv_phase(p, k, st, cw.f8));
+    }
+    return S2SR_OK;
+}
+
+// s2sr_debug_trunk_taps: the trunk fields at the boundary in front of global RDB g (g = 3 num_block: behind the last one), called
+// by run_net before RDB g's first launch.  What RDB g - 1 wrote (the trunk x, its growth planes) is still in place then, and so
+// is the RRDB skip a rdb3 is about to read.  Blocking copies: the hook's batch runs eagerly.
+int trunk_tap(s2sr_handle* h, hipStream_t st, int g) {
+    const TrunkTap& tt = *h->ttap;
+    s2sr_debug_trunk_fields* t = tt.t;
+    const Workspace& w = h->ws;
+    const int n = t->n, j = g - tt.first;
+    if (j < 0 || j > tt.count) return S2SR_OK;
+    if (w.Hp != t->Hp || w.Wp != t->Wp) return fail(h, S2SR_E_INVALID, "trunk taps: the workspace planes differ from the planned ones");
+    HIPCHK(h, hipStreamSynchronize(st));
+    const size_t f64 = (size_t)n * 64 * w.Hp * w.Wp;   // floats of one 64-channel field
+    const int r = g % 3;
+    int rc;
+    if (w.fp8) {
+        const float sx = ldexpf(1.0f, -h->fp8_x_exp), sg = ldexpf(1.0f, -h->fp8_g_exp), scx[2] = {sx, sx}, scg[4] = {sg, sg, sg, sg};
+        if (t->x_hi && (rc = decode_f16_planes(h, t->x_hi + j * f64, w.Xh[r], 4 * w.blk1, n, 4, w.blk1))) return rc;
+        if (t->x_lo && (rc = decode_e4m3_planes(h, t->x_lo + j * f64, w.D8[g & 1], 6 * w.blk1, n, 2, w.blk1, scx))) return rc;
+        if (j > 0 && t->growth && (rc = decode_e4m3_planes(h, t->growth + (j - 1) * 2 * f64, w.D8[(g - 1) & 1] + 2 * w.blk1, 6 * w.blk1, n, 4, w.blk1, scg)))
+            return rc;
+        if (j < tt.count && r == 2 && t->skip_hi && (rc = decode_f16_planes(h, t->skip_hi + j * f64, w.Xh[0], 4 * w.blk1, n, 4, w.blk1))) return rc;
+    } else {
+        const float sl = ldexpf(1.0f, -h->lo_exp), scl[2] = {sl, sl};
+        if (t->x_hi && (rc = decode_f16_planes(h, t->x_hi + j * f64, w.D[r], 12 * w.blk1, n, 4, w.blk1))) return rc;
+        if (t->x_lo && (rc = decode_e4m3_planes(h, t->x_lo + j * f64, w.Tr[r], 2 * w.blk1, n, 2, w.blk1, scl))) return rc;
+        if (j > 0 && t->growth && (rc = decode_f16_planes(h, t->growth + (j - 1) * 2 * f64, w.D[(g + 2) % 3] + 4 * w.blk1, 12 * w.blk1, n, 8, w.blk1)))
+            return rc;
+        if (j < tt.count && r == 2) {
+            if (t->skip_hi && (rc = decode_f16_planes(h, t->skip_hi + j * f64, w.D[0], 12 * w.blk1, n, 4, w.blk1))) return rc;
+            if (t->skip_lo && (rc = decode_e4m3_planes(h, t->skip_lo + j * f64, w.Tr[0], 2 * w.blk1, n, 2, w.blk1, scl))) return rc;
+        }
+        if (g == 0 && t->entry_lo && (rc = decode_f16_planes(h, t->entry_lo, w.T, 4 * w.blk1, n, 4, w.blk1))) return rc;
     }
     return S2SR_OK;
 }
@@ -540,6 +632,11 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         }
         for (int blk = 0; blk < nb; ++blk)
             for (int r = 0; r < 3; ++r) {
+                s2sr_debug_trunk_form* fo = nullptr;             // s2sr_debug_trunk_taps only
+                if (h->ttap) {
+                    if ((rc = trunk_tap(h, st, 3 * blk + r))) return rc;
+                    fo = h->ttap->forms(3 * blk + r);
+                }
                 span_begin(h, st, F_RDB14);                      // conv1..4 of this RDB: one sample
                 for (int k = 1; k <= 5; ++k) {
                     if (k == 5) span_end(h, st);
@@ -562,7 +659,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
                         if (r == 2) { p.xh_skip = w.Xh[0]; epi = EPI_RDB5_RRDB; bytes += px * 128.0; }
                     }
                     Scope sc(h, st, k < 5 ? F_RDB14 : F_RDB5, 2.0 * 9.0 * cw.cin * cw.cout * px, bytes);
-                    HIPCHK(h, launch_conv_trunk_f8(p, cw.ct, epi, st));
+                    HIPCHK(h, launch_conv_trunk_f8(p, cw.ct, epi, st, fo ? fo + (k - 1) : nullptr));
                 }
                 if (h->d_calib) {   // s2sr_calibrate_fp8: ranges of this RDB's growth planes and of the trunk it produced
                     HIPCHK(h, launch_absmax_e4m3(w.D8[cur] + 2 * w.blk1, (size_t)4 * w.blk1, ge, h->d_calib + 1, st));
@@ -572,6 +669,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
                 }
                 cur ^= 1;
             }
+        if (h->ttap && (rc = trunk_tap(h, st, 3 * nb))) return rc;
         trunk_hi = w.Xh[0]; trunk_hi_img = 4 * w.blk1; trunk_lo = w.Tz;
     } else if (h->trunk_w4) {
         // one-wave-per-SIMD trunk kernel: rdb r of every RRDB reads D[r] / Tr[r] and writes the next trunk (x, lo) into
@@ -586,12 +684,17 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         for (int blk = 0; blk < nb; ++blk)
             for (int r = 0; r < 3; ++r) {
                 const int nx = (r + 1) % 3;
+                s2sr_debug_trunk_form* fo = nullptr;             // s2sr_debug_trunk_taps only
+                if (h->ttap) {
+                    if ((rc = trunk_tap(h, st, 3 * blk + r))) return rc;
+                    fo = h->ttap->forms(3 * blk + r);
+                }
                 span_begin(h, st, F_RDB14);                      // conv1..4 of this RDB: one sample
                 for (int k = 1; k <= 4; ++k) {
                     ConvParams p = b;
                     p.src = w.D[r]; p.src_img = 12 * w.blk1;
                     p.dst = w.D[r] + (size_t)(4 + 2 * (k - 1)) * w.blk1; p.dst_img = 12 * w.blk1;
-                    if ((rc = run_conv(h, st, F_RDB14, h->convs[ci++], p, EPI_LRELU, false))) { span_end(h, st); return rc; }
+                    if ((rc = run_conv(h, st, F_RDB14, h->convs[ci++], p, EPI_LRELU, false, false, fo ? fo + (k - 1) : nullptr))) { span_end(h, st); return rc; }
                 }
                 span_end(h, st);
                 ConvParams p = b;
@@ -599,8 +702,9 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
                 p.dst = w.D[nx]; p.dst_img = 12 * w.blk1;
                 p.xh_in = w.Tr[r]; p.T = w.Tr[nx]; p.lo_exp = h->lo_exp;
                 if (r == 2) { p.xh_skip = w.D[0]; p.xh_img = 12 * w.blk1; p.lo_skip = w.Tr[0]; }
-                if ((rc = run_conv(h, st, F_RDB5, h->convs[ci++], p, r == 2 ? EPI_RDB5_RRDB : EPI_RDB5, false))) return rc;
+                if ((rc = run_conv(h, st, F_RDB5, h->convs[ci++], p, r == 2 ? EPI_RDB5_RRDB : EPI_RDB5, false, false, fo ? fo + 4 : nullptr))) return rc;
             }
+        if (h->ttap && (rc = trunk_tap(h, st, 3 * nb))) return rc;
         trunk_hi = w.D[0]; trunk_hi_img = 12 * w.blk1; trunk_lo = w.Tr[0]; trunk_lo_exp = h->lo_exp;
     } else {
         for (int blk = 0; blk < nb; ++blk)
@@ -2458,20 +2562,6 @@ int s2sr_debug_get_config(s2sr_handle* h, s2sr_debug_config* out) {
     return S2SR_OK;
 }
 
-namespace {
-float e4m3_to_f32(uint8_t b) {   // OCP e4m3fn: bias 7, subnormals, 0x7f / 0xff = NaN
-    const int e = (b >> 3) & 15, m = b & 7;
-    float v = e == 0 ? ldexpf((float)m, -9) : ldexpf((float)(8 + m), e - 10);
-    if ((b & 0x7f) == 0x7f) v = NAN;
-    return (b & 0x80) ? -v : v;
-}
-typedef _Float16 hf16;
-struct DevBuf {   // frees on scope exit: the hook has many early returns
-    void* p = nullptr;
-    ~DevBuf() { if (p) dev_free(p); }
-};
-}  // namespace
-
 // One RDB-shaped conv through conv_trunk_f16 / conv_trunk_f8.  Host-side packing and decoding (a test hook: clarity over
 // speed); the weights go through the production device packers (pack.hip).
 int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
@@ -2752,18 +2842,16 @@ int s2sr_debug_bench_conv(s2sr_handle* h, int32_t N, int32_t H, int32_t W, int32
     return S2SR_OK;
 }
 
-// The tail's per-layer parity hook: one batch through forward_dev -> run_net as production runs it (eagerly: graphs off for the
-// call), then the tensors of the six head / tail convs copied out of the workspace and decoded on the host.
-int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, int32_t job_windows,
-                            s2sr_debug_taps* t) {
-    if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
+namespace {
+// The launch plan a tap hook's batch gets from forward_dev (s2sr_forward_part_u8_dev: the job's mosaic) and the one launch group /
+// mosaic segment it must be.
+struct TapPlan {
+    Mosaic plan;
+    int NI = 0, skx = 0, sky = 0, SH = 0, SW = 0, IH = 0, IW = 0;
+};
+int tap_plan(s2sr_handle* h, bool u8, int32_t B, int32_t th, int32_t tw, int32_t job_windows, TapPlan* tp) {
     const int job = job_windows > B ? job_windows : B;
-    // the plan forward_dev follows (s2sr_forward_part_u8_dev: the job's mosaic), and the one segment this batch must be
-    Mosaic plan = tiles ? pick_mosaic(h, job, th, tw) : Mosaic();
+    Mosaic plan = u8 ? pick_mosaic(h, job, th, tw) : Mosaic();
     const int per = plan.on() ? plan.kx * plan.ky : 1;
     int skx = plan.kx, sky = plan.ky;
     if (plan.on()) {
@@ -2771,27 +2859,17 @@ int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x
         if (B < per) mosaic_remainder(B, plan.kx, plan.ky, &skx, &sky);
     }
     const int sper = plan.on() ? skx * sky : 1;
-    const int NI = (B + sper - 1) / sper;
-    const int IH = plan.on() ? plan.ky * (th + 1) - 1 : th, IW = plan.on() ? plan.kx * (tw + 1) - 1 : tw;
-    const int SH = plan.on() ? sky * (th + 1) - 1 : th, SW = plan.on() ? skx * (tw + 1) - 1 : tw;
-    if (NI > group_size(h, (job + per - 1) / per, IH, IW)) return fail(h, S2SR_E_INVALID, "batch needs more than one launch group");
-    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;
-    const bool hp = h->cfg.precision == S2SR_PREC_F16_HP || (fp8 && h->fp8_hp_tail);
-    t->n = NI;
-    for (int k = 0; k < 3; ++k) {
-        const int s = k == 0 ? 1 : 2 * k;
-        t->H[k] = s * SH; t->W[k] = s * SW; t->Hp[k] = padded(s * IH); t->Wp[k] = padded(s * IW);
-    }
-    t->mos_kx = plan.on() ? skx : 0; t->mos_ky = plan.on() ? sky : 0; t->mos_wh = plan.on() ? th : 0; t->mos_ww = plan.on() ? tw : 0;
-    t->mos_count = plan.on() ? B : 0;
-    t->trunk_lo_exp = fp8 ? -1 : (h->trunk_w4 ? h->lo_exp : -1);
-    t->avail = 0;
-    for (int k = 0; k < S2SR_TAP_COUNT; ++k)
-        if (hp || (k != S2SR_TAP_T8 && k < S2SR_TAP_U0LO)) t->avail |= 1 << k;
-    bool any = t->out_f32 || t->out_u8;
-    for (int k = 0; k < S2SR_TAP_COUNT; ++k) any = any || t->tap[k];
-    if (!any) return S2SR_OK;
-    // ---- the run, on buffers of its own
+    tp->plan = plan; tp->skx = skx; tp->sky = sky;
+    tp->NI = (B + sper - 1) / sper;
+    tp->IH = plan.on() ? plan.ky * (th + 1) - 1 : th; tp->IW = plan.on() ? plan.kx * (tw + 1) - 1 : tw;
+    tp->SH = plan.on() ? sky * (th + 1) - 1 : th; tp->SW = plan.on() ? skx * (tw + 1) - 1 : tw;
+    if (tp->NI > group_size(h, (job + per - 1) / per, tp->IH, tp->IW)) return fail(h, S2SR_E_INVALID, "batch needs more than one launch group");
+    return S2SR_OK;
+}
+// ... and the run: forward_dev -> run_net eagerly (graphs off for the call) on buffers of its own, outputs copied back
+int tap_forward(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, const TapPlan& tp,
+                uint8_t* out_u8, float* out_f32) {
+    hipStream_t st = h->stream;
     const size_t ib = tiles ? (size_t)B * th * tw * 3 : (size_t)B * 3 * th * tw * 4, opx = (size_t)B * 16 * th * tw;
     DevBuf d_in, d_o8, d_o32;
     HIPCHK(h, dev_malloc(&d_in.p, ib));
@@ -2800,49 +2878,63 @@ int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x
     HIPCHK(h, hipMemcpyAsync(d_in.p, tiles ? (const void*)tiles : (const void*)x, ib, hipMemcpyHostToDevice, st));
     const bool graphs = h->graphs_on;
     h->graphs_on = false;
+    Mosaic plan = tp.plan;
     int rc = forward_dev(h, st, tiles ? (const uint8_t*)d_in.p : nullptr, tiles ? nullptr : (const float*)d_in.p, B, th, tw,
-                         t->out_u8 ? (uint8_t*)d_o8.p : nullptr, t->out_f32 ? (float*)d_o32.p : nullptr, plan.on() ? &plan : nullptr);
+                         out_u8 ? (uint8_t*)d_o8.p : nullptr, out_f32 ? (float*)d_o32.p : nullptr, plan.on() ? &plan : nullptr);
     h->graphs_on = graphs;
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(st));
+    if (h->ws.G < tp.NI) return fail(h, S2SR_E_INVALID, "workspace fell back to a smaller launch group: the batch ran in two");
+    if (out_u8) HIPCHK(h, copy_blocking(h, out_u8, d_o8.p, opx * 3, hipMemcpyDeviceToHost));
+    if (out_f32) HIPCHK(h, copy_blocking(h, out_f32, d_o32.p, opx * 3 * 4, hipMemcpyDeviceToHost));
+    return S2SR_OK;
+}
+}  // namespace
+
+// The tail's per-layer parity hook: one batch through forward_dev -> run_net as production runs it (eagerly: graphs off for the
+// call), then the tensors of the six head / tail convs copied out of the workspace and decoded on the host.
+int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, int32_t job_windows,
+                            s2sr_debug_taps* t) {
+    if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    TapPlan tp;
+    int rc = tap_plan(h, tiles != nullptr, B, th, tw, job_windows, &tp);
+    if (rc) return rc;
+    const int NI = tp.NI;
+    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;
+    const bool hp = h->cfg.precision == S2SR_PREC_F16_HP || (fp8 && h->fp8_hp_tail);
+    t->n = NI;
+    for (int k = 0; k < 3; ++k) {
+        const int s = k == 0 ? 1 : 2 * k;
+        t->H[k] = s * tp.SH; t->W[k] = s * tp.SW; t->Hp[k] = padded(s * tp.IH); t->Wp[k] = padded(s * tp.IW);
+    }
+    const bool mos = tp.plan.on();
+    t->mos_kx = mos ? tp.skx : 0; t->mos_ky = mos ? tp.sky : 0; t->mos_wh = mos ? th : 0; t->mos_ww = mos ? tw : 0;
+    t->mos_count = mos ? B : 0;
+    t->trunk_lo_exp = fp8 ? -1 : (h->trunk_w4 ? h->lo_exp : -1);
+    t->avail = 0;
+    for (int k = 0; k < S2SR_TAP_COUNT; ++k)
+        if (hp || (k != S2SR_TAP_T8 && k < S2SR_TAP_U0LO)) t->avail |= 1 << k;
+    bool any = t->out_f32 || t->out_u8;
+    for (int k = 0; k < S2SR_TAP_COUNT; ++k) any = any || t->tap[k];
+    if (!any) return S2SR_OK;
+    if ((rc = tap_forward(h, tiles, x, B, th, tw, tp, t->out_u8, t->out_f32))) return rc;
     const Workspace& w = h->ws;
-    if (w.G < NI) return fail(h, S2SR_E_INVALID, "workspace fell back to a smaller launch group: the batch ran in two");
-    if (t->out_u8) HIPCHK(h, copy_blocking(h, t->out_u8, d_o8.p, opx * 3, hipMemcpyDeviceToHost));
-    if (t->out_f32) HIPCHK(h, copy_blocking(h, t->out_f32, d_o32.p, opx * 3 * 4, hipMemcpyDeviceToHost));
-    // ---- decoders: n images of `nb` planes of 32 B per pixel at `img` bytes apart -> [n][channels][Hp][Wp] fp32
+    // ---- decoders: NI images of `nb` planes of 32 B per pixel at `img` bytes apart -> [n][channels][Hp][Wp] fp32
     std::vector<uint8_t> buf;
-    auto fetch = [&](const char* src, uint64_t img, int nb, size_t blk) -> int {
-        buf.resize((size_t)NI * nb * blk);
-        for (int i = 0; i < NI; ++i) HIPCHK(h, copy_blocking(h, buf.data() + (size_t)i * nb * blk, src + (size_t)i * img, (size_t)nb * blk, hipMemcpyDeviceToHost));
-        return S2SR_OK;
-    };
-    auto f16_planes = [&](float* dst, const char* src, uint64_t img, int nb, int k) -> int {   // fp16 blocked-16
-        const size_t blk = (k == 0 ? w.blk1 : k == 1 ? w.blk2 : w.blk4), np = blk / 32;
-        if (int r = fetch(src, img, nb, blk)) return r;
-        const hf16* v = (const hf16*)buf.data();
-        for (int i = 0; i < NI; ++i)
-            for (int b = 0; b < nb; ++b)
-                for (size_t q = 0; q < np; ++q)
-                    for (int c = 0; c < 16; ++c)
-                        dst[(((size_t)i * nb * 16 + b * 16 + c) * np) + q] = (float)v[(((size_t)i * nb + b) * np + q) * 16 + c];
-        return S2SR_OK;
-    };
-    auto e4m3_planes = [&](float* dst, const char* src, uint64_t img, int nb, int k, const float* scale /*[nb]*/) -> int {   // 32 ch per plane
-        const size_t blk = (k == 0 ? w.blk1 : k == 1 ? w.blk2 : w.blk4), np = blk / 32;
-        if (int r = fetch(src, img, nb, blk)) return r;
-        for (int i = 0; i < NI; ++i)
-            for (int b = 0; b < nb; ++b)
-                for (size_t q = 0; q < np; ++q)
-                    for (int c = 0; c < 32; ++c)
-                        dst[(((size_t)i * nb * 32 + b * 32 + c) * np) + q] = e4m3_to_f32(buf[(((size_t)i * nb + b) * np + q) * 32 + c]) * scale[b];
-        return S2SR_OK;
+    auto blk_at = [&](int k) { return k == 0 ? w.blk1 : k == 1 ? w.blk2 : w.blk4; };
+    auto f16_planes = [&](float* dst, const char* src, uint64_t img, int nb, int k) { return decode_f16_planes(h, dst, src, img, NI, nb, blk_at(k)); };
+    auto e4m3_planes = [&](float* dst, const char* src, uint64_t img, int nb, int k, const float* scale /*[nb]*/) {   // 32 ch per plane
+        return decode_e4m3_planes(h, dst, src, img, NI, nb, blk_at(k), scale);
     };
     const float s_lo4[4] = {1.0f / 2048.0f, 1.0f / 2048.0f, 1.0f, 1.0f};
     const int nb1 = 1;
     if (t->tap[S2SR_TAP_P0] && (rc = f16_planes(t->tap[S2SR_TAP_P0], w.P0, w.blk1, nb1, 0))) return rc;
     if (t->tap[S2SR_TAP_F]) {   // fp32 blocked-8: [n][8][Hp][Wp][8]
         const size_t np = w.blk1 / 32;
-        if ((rc = fetch((const char*)w.F, 8 * w.blk1, 8, w.blk1))) return rc;
+        if ((rc = fetch_planes(h, buf, (const char*)w.F, 8 * w.blk1, NI, 8, w.blk1))) return rc;
         const float* v = (const float*)buf.data();
         for (int i = 0; i < NI; ++i)
             for (int b = 0; b < 8; ++b)
@@ -2867,6 +2959,40 @@ int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x
         if (hp && t->tap[S2SR_TAP_U0LO + u] && (rc = e4m3_planes(t->tap[S2SR_TAP_U0LO + u], UL[u], 4 * Ublk[u], 4, Uk[u], s_lo4))) return rc;
     }
     return S2SR_OK;
+}
+
+// The trunk's per-RDB parity hook: the batch of s2sr_debug_forward_taps, with run_net copying the trunk fields of the RDBs
+// [first, first + count) out at every RDB boundary (trunk_tap) and the conv launches recording their kernel forms.
+int s2sr_debug_trunk_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, int32_t job_windows,
+                          s2sr_debug_trunk_fields* t) {
+    if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
+    if (t->first < 0 || t->count < 1 || t->first + t->count > 3 * h->cfg.num_block)
+        return fail(h, S2SR_E_INVALID, "RDB range outside [0, 3 * num_block)");
+    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;
+    if (!fp8 && !h->trunk_w4) return fail(h, S2SR_E_INVALID, "trunk taps: the 8-wave trunk (S2SR_TRUNK=0) is not tapped");
+    if (h->d_calib) return fail(h, S2SR_E_INVALID, "trunk taps: the handle is calibrating");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    TapPlan tp;
+    int rc = tap_plan(h, tiles != nullptr, B, th, tw, job_windows, &tp);
+    if (rc) return rc;
+    const bool mos = tp.plan.on();
+    t->n = tp.NI; t->H = tp.SH; t->W = tp.SW; t->Hp = padded(tp.IH); t->Wp = padded(tp.IW);
+    t->mos_kx = mos ? tp.skx : 0; t->mos_ky = mos ? tp.sky : 0; t->mos_wh = mos ? th : 0; t->mos_ww = mos ? tw : 0;
+    t->mos_count = mos ? B : 0;
+    t->fp8 = fp8 ? 1 : 0;
+    t->lo_exp = fp8 ? -1 : h->lo_exp;
+    t->x_exp = fp8 ? h->fp8_x_exp : -1;
+    t->g_exp = fp8 ? h->fp8_g_exp : -1;
+    if (!(t->x_hi || t->x_lo || t->growth || t->skip_hi || t->skip_lo || t->entry_lo || t->form || t->out_f32 || t->out_u8)) return S2SR_OK;
+    if (t->form) memset(t->form, 0, sizeof(*t->form) * 5 * (size_t)t->count);
+    TrunkTap tt;
+    tt.first = t->first; tt.count = t->count; tt.t = t;
+    h->ttap = &tt;
+    rc = tap_forward(h, tiles, x, B, th, tw, tp, t->out_u8, t->out_f32);
+    h->ttap = nullptr;
+    return rc;
 }
 
 }  // extern "C"

@@ -180,14 +180,16 @@ hipError_t launch_conv_trace(const ConvParams& p, int ct, hipStream_t st);   // 
 // EPI_RDB5_RRDB (conv5).  hipErrorNotSupported = not a trunk form / launch too small: use launch_conv.
 // force_form (conv1-4 only; the per-layer parity hook): 0 = by launch size, 1 = 16x32 patches / 5-deep ring, 2 = 32x32 patches / 3-deep ring,
 // 4 = loader wave, 5 = 8x32 patches, 6 / 7 / 8 = the whole-patch (FULL) forms of 2 / 1 / 5
-hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, bool trace = false, int force_form = 0);
+// form (optional): the instantiation the launch took (s2sr_debug_trunk_taps' form record), written when the launch was issued
+hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, bool trace = false, int force_form = 0,
+                             s2sr_debug_trunk_form* form = nullptr);
 // fp16 RDB conv1..4 in the row-Winograd F(2,3) form (conv_wino.hip): weights transformed over dy (4 x 3 fragments per 16-channel
 // stage instead of 3 x 3), inputs transformed over 4 consecutive slab rows in registers, 12 MFMAs per 2 output rows instead of 18
 hipError_t launch_conv_trunk_wino(const ConvParams& p, hipStream_t st);
 size_t conv_wpack_bytes_wino(int cin, int cout);
 hipError_t launch_pack_trunk_wino(const float* d_w, int cin, int cout, void* d_out, hipStream_t st);
 // the same convs on e4m3 operands, block-scaled fp8 MFMA (K = 64 = two planes per instruction)
-hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_t st);
+hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_t st, s2sr_debug_trunk_form* form = nullptr);
 // per-plane weight stages for conv_trunk_f8: [plane][tap][ct][16-B half][cout row 0..31][16 channel bytes] e4m3 of
 // w * 2^k_co, planes padded to an even count with a zero plane; wscale_out[co] = 127 - k_co
 size_t conv_wpack_bytes_f8(int cin, int cout);

@@ -64,6 +64,19 @@ class DebugTaps(C.Structure):
                [("reserved", C.c_int32 * 4), ("tap", C.c_void_p * len(TAP_NAMES)), ("out_f32", C.c_void_p), ("out_u8", C.c_void_p)]
 
 
+TRUNK_FORM_FIELDS = ("kernel", "ct", "rows", "ring", "full", "pl", "prod", "wgl", "loe", "wv", "npl", "epi")   # s2sr_debug_trunk_form
+
+
+class DebugTrunkForm(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in TRUNK_FORM_FIELDS]
+
+
+class DebugTrunkFields(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("first", "count", "n", "H", "W", "Hp", "Wp", "mos_kx", "mos_ky", "mos_wh", "mos_ww",
+                                         "mos_count", "fp8", "lo_exp", "x_exp", "g_exp")] + [("reserved", C.c_int32 * 4)] + \
+               [(n, C.c_void_p) for n in ("x_hi", "x_lo", "growth", "skip_hi", "skip_lo", "entry_lo", "form", "out_f32", "out_u8")]
+
+
 class KStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_int64), ("total_ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double)]
@@ -148,6 +161,7 @@ _PROTOS = {
     "s2sr_debug_get_config": (C.c_int, [C.c_void_p, C.POINTER(DebugConfig)]),
     "s2sr_debug_conv_trunk": (C.c_int, [C.c_void_p, C.POINTER(DebugTrunkArgs)]),
     "s2sr_debug_forward_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(DebugTaps)]),
+    "s2sr_debug_trunk_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(DebugTrunkFields)]),
     "s2sr_debug_mfma_ceiling": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_float)]),
     "s2sr_debug_bench_conv": (C.c_int, [C.c_void_p] + [C.c_int32] * 6 + [C.POINTER(C.c_float), C.c_void_p, C.c_int32]),
@@ -803,7 +817,46 @@ def _debug_forward_taps(self, tiles=None, x=None, job_windows=0):
     return geo, taps, out_f32, out_u8
 
 
+def _debug_trunk_taps(self, first, count, tiles=None, x=None, job_windows=0):
+    """One batch through the production forward, eagerly, with the trunk fields of the RDBs [first, first + count) copied out at
+    every RDB boundary (include/s2sr.h: s2sr_debug_trunk_taps).  Input as debug_forward_taps.
+    Returns (geometry dict, fields, forms, out_f32 [B, 3, 4th, 4tw], out_u8 [B, 4th, 4tw, 3]).  fields (fp32, padded extent):
+    x_hi / x_lo [count + 1, n, 64, Hp, Wp], growth [count, n, 128, Hp, Wp], skip_hi / skip_lo [count, n, 64, Hp, Wp] (zero
+    where the RDB is no rdb3), entry_lo [n, 64, Hp, Wp] (first == 0, fp16 path; else zero).  forms: [count][5] dicts of
+    TRUNK_FORM_FIELDS, conv1..conv5 of each RDB."""
+    assert (tiles is None) != (x is None)
+    if tiles is not None:
+        tiles = np.ascontiguousarray(tiles, np.uint8)
+        B, th, tw, c = tiles.shape
+    else:
+        x = np.ascontiguousarray(x, np.float32)
+        B, c, th, tw = x.shape
+    assert c == 3
+    t = DebugTrunkFields()
+    t.first, t.count = int(first), int(count)
+    call = lambda: self._check(self._lib.s2sr_debug_trunk_taps(self._h, None if tiles is None else _ptr(tiles), None if x is None else _ptr(x),
+                                                               B, th, tw, int(job_windows), C.byref(t)), "s2sr_debug_trunk_taps")
+    call()                                  # geometry only
+    geo = {k: getattr(t, k) for k in ("n", "H", "W", "Hp", "Wp", "mos_kx", "mos_ky", "mos_wh", "mos_ww", "mos_count", "fp8",
+                                       "lo_exp", "x_exp", "g_exp")}
+    n, Hp, Wp = t.n, t.Hp, t.Wp
+    fields = {"x_hi": np.zeros((count + 1, n, 64, Hp, Wp), np.float32), "x_lo": np.zeros((count + 1, n, 64, Hp, Wp), np.float32),
+              "growth": np.zeros((count, n, 128, Hp, Wp), np.float32), "skip_hi": np.zeros((count, n, 64, Hp, Wp), np.float32),
+              "skip_lo": np.zeros((count, n, 64, Hp, Wp), np.float32), "entry_lo": np.zeros((n, 64, Hp, Wp), np.float32)}
+    for k, a in fields.items():
+        setattr(t, k, a.ctypes.data)
+    forms = (DebugTrunkForm * (5 * count))()
+    t.form = C.addressof(forms)
+    out_f32 = np.zeros((B, 3, 4 * th, 4 * tw), np.float32)
+    out_u8 = np.zeros((B, 4 * th, 4 * tw, 3), np.uint8)
+    t.out_f32, t.out_u8 = out_f32.ctypes.data, out_u8.ctypes.data
+    call()
+    fl = [[{k: getattr(forms[5 * i + c5], k) for k in TRUNK_FORM_FIELDS} for c5 in range(5)] for i in range(count)]
+    return geo, fields, fl, out_f32, out_u8
+
+
 Engine.debug_config = _debug_config
+Engine.debug_trunk_taps = _debug_trunk_taps
 Engine.debug_conv_trunk = _debug_conv_trunk
 Engine.debug_forward_taps = _debug_forward_taps
 
