@@ -310,14 +310,14 @@ int  s2sr_debug_conv(s2sr_handle* h, const float* x, int32_t N, int32_t Cin, int
 typedef struct s2sr_debug_config {
     int32_t precision;      /* S2SR_PREC_* */
     int32_t group;          /* cfg.group as given (0 = default) */
-    int32_t trunk_w4;       /* 1: RDB convs on the one-wave-per-SIMD kernels (conv_trunk.hip); 0: 8-wave kernel (S2SR_TRUNK=0) */
+    int32_t trunk_w4;       /* always 1: RDB convs on the one-wave-per-SIMD kernels (conv_trunk.hip) */
     int32_t lo_exp;         /* trunk lo half as e4m3(lo * 2^lo_exp) (S2SR_LO_EXP) */
-    int32_t fp8_form;       /* conv_trunk_f8 conv1-4 form bits: 1 no loader wave, 2/4 weight placement, 8 two waves per SIMD */
+    int32_t fp8_form;       /* always 0 (conv_trunk_f8 conv1-4 runs in its one, loader-wave form) */
     int32_t fp8_x_exp, fp8_g_exp;   /* fp8 trunk activation scales (S2SR_FP8_XEXP / _GEXP or s2sr_calibrate_fp8) */
     int32_t fp8_hp_tail;    /* S2SR_FP8_TAIL=hp */
     int32_t graphs_on;      /* S2SR_GRAPH */
-    int32_t trunk_wino;     /* 1: fp16 RDB conv1-4 in the row-Winograd F(2,3) form (S2SR_WINO) */
-    int32_t reserved[6];    /* [0]: window mosaics on (S2SR_MOSAIC); [1]: fp16 conv1-4 loader-wave form (S2SR_F16_LOADER); [2]: conv_last folded 6-stage form (S2SR_LAST_FOLD); [3]: 4-wave tail convs (S2SR_TAIL_W4); [4]: whole-patch fp16 conv1-4 forms allowed (S2SR_F16_FULL); [5]: workspace allocations since s2sr_create */
+    int32_t trunk_wino;     /* always 0 (the row-Winograd form was removed) */
+    int32_t reserved[6];    /* [0]: window mosaics on (S2SR_MOSAIC); [1]: always 0; [2]: conv_last folded 6-stage form (S2SR_LAST_FOLD); [3]: always 0; [4]: whole-patch fp16 conv1-4 forms allowed (S2SR_F16_FULL); [5]: workspace allocations since s2sr_create */
 } s2sr_debug_config;
 int  s2sr_debug_get_config(s2sr_handle* h, s2sr_debug_config* out);
 
@@ -345,9 +345,9 @@ int  s2sr_debug_plan_chunks(int32_t units, int32_t u_max, int32_t unit_windows, 
  * x is rounded to the operand format on the way in (fp16, or e4m3 at the handle's scales), so callers pass representable
  * values; `lo` ([N,64,H,W], kinds 1-2, may be NULL) is stored as e4m3(lo * 2^lo_exp); `skip` ([N,64,H,W]) as the
  * (fp16 hi, e4m3 lo) pair (kind 2) or fp16 (kind 5).  form: kind 0: 0 auto, 1 = 16x32 patches, 2 = 32x32 patches,
- * 3 = row-Winograd F(2,3), 4 = 32x32 patches with the load-only fifth wave, 5 = 8x32 patches (single tiles), 10 = 8x32 patches with two
- * planes per pipeline stage; kinds 1-2: 0 auto, 1 = 16x32 patches, 5 = 8x32 patches, 10 = 8x32 patches with two planes per stage; kind 3:
- * the fp8_form bits.  (3, 4, 9 and the long lo-encoding form 2 of kinds 1-2: experimental library only.) */
+ * 5 = 8x32 patches (single tiles), 6 / 7 / 8 = the whole-patch forms of 2 / 1 / 5, 10 = 8x32 patches with two planes per pipeline
+ * stage; kinds 1-2: 0 auto, 1 = 16x32 patches, 5 = 8x32 patches, 10 = 8x32 patches with two planes per stage; kind 3: 0.  The removed
+ * forms (kind 0: 3, 4, 9, 11; kinds 1-2: 2; kind 3: anything but 0) are refused (S2SR_E_HIP, not supported). */
 typedef struct s2sr_debug_trunk_args {
     int32_t kind, form;
     int32_t N, Cin, H, W;
@@ -394,10 +394,10 @@ int  s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* 
                              int32_t job_windows, s2sr_debug_taps* t);
 
 /* The trunk kernel instantiation one RDB conv launch took (launch_conv_trunk / launch_conv_trunk_f8 report it).
- * kernel: 1 conv_trunk_f16, 2 conv_trunk_f8, 3 the row-Winograd form (conv_wino.hip; no further fields), 0 nothing recorded.
+ * kernel: 1 conv_trunk_f16, 2 conv_trunk_f8, 0 nothing recorded.
  * rows: patch rows (the patch is rows x 32 pixels); ring: slab ring depth; full: the FULL template argument (0 generic px_live
  * test, 1 whole patches, 2 mosaics of 276-pixel windows, 3 the extent test alone); pl: planes per pipeline stage; prod: a
- * load-only wave; wgl: weights from global memory; loe: the lo-encoding form of conv5; wv: MFMA waves; npl: fp8 weights
+ * load-only wave (conv_trunk_f8 conv1-4); wgl: always 0; loe: 1, conv5's short lo encoding; wv: MFMA waves (4); npl: fp8 weights
  * resident in LDS (planes; 0 = streamed); epi: the epilogue (0 conv1-4 LeakyReLU, 1 conv5 of rdb1 / rdb2, 2 conv5 of rdb3 with the
  * RRDB skip). */
 typedef struct s2sr_debug_trunk_form {
@@ -405,7 +405,7 @@ typedef struct s2sr_debug_trunk_form {
 } s2sr_debug_trunk_form;
 
 /* test hook: ONE batch through the production forward, exactly as s2sr_debug_forward_taps runs it (same input rules, same
- * refusals, graphs off, buffers of its own; also refused while s2sr_calibrate_fp8 runs and on the 8-wave trunk, S2SR_TRUNK=0),
+ * refusals, graphs off, buffers of its own; also refused while s2sr_calibrate_fp8 runs),
  * with the trunk fields of the RDBs [first, first + count) (global RDB index: 3 * block + rdb, < 3 * num_block) copied out at
  * every RDB boundary and decoded to fp32 over the PADDED extent [n, C, Hp, Wp] (halo and round-up slack included):
  *   x_hi   [count + 1][n][64][Hp][Wp]  the trunk x at boundary j (the input of RDB first + j): fp16 hi (fp8 path: the fp16 Xh)

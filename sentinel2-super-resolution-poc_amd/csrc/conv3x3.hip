@@ -6,8 +6,8 @@
 //   v_mfma_f32_32x32x16_f16:  A = weights  (lane = cout + 32*(k/8)),
 //                             B = activations (lane = pixel + 32*(k/8)),
 //                             D: lane = pixel column, 16 registers = 16 couts
-//   so a lane ends up owning 16 output channels of ONE pixel: bias, LeakyReLU, the x0.2
-//   residual adds of RDB / RRDB and the stores are lane-local; one v_permlane32_swap per
+//   so a lane ends up owning 16 output channels of ONE pixel: bias, LeakyReLU, the residual
+//   adds and the stores are lane-local; one v_permlane32_swap per
 //   dword pairs the two half-waves into 16-byte stores.
 //
 // Schedule (measured choices, see DESIGN.md "kernel history"):
@@ -87,9 +87,9 @@ __device__ __forceinline__ const char* uniform_ptr(const char* q) {
 // LDS-DMA, 16 B per lane: LDS[lds_addr + lane*16] <- global[base + voff].  M0 is written in the
 // statement that uses it (hipcc keeps nothing live in M0 across statements in this kernel: no
 // other LDS-DMA, GWS, sendmsg or movrel user), one wait state between the M0 write and the DMA.
-// FORCE_UNIFORM re-derives base / lds_addr through v_readfirstlane: only the stamped diagnostic
-// build needs it (its divergent stamp branches make hipcc keep these uniform values in VGPRs,
-// which an "s" operand cannot take); s_nop 4 then covers the VALU-written SGPRs.
+// FORCE_UNIFORM (the EPI_DEBUG forms) re-derives base / lds_addr through v_readfirstlane, for when
+// hipcc keeps these uniform values in VGPRs, which an "s" operand cannot take; s_nop 4 then covers
+// the VALU-written SGPRs.
 template <bool FORCE_UNIFORM>
 __device__ __forceinline__ void glds16(const char* base, uint32_t voff, uint32_t lds_addr) {
     if (FORCE_UNIFORM) {
@@ -103,36 +103,7 @@ __device__ __forceinline__ void glds16(const char* base, uint32_t voff, uint32_t
     }
 }
 
-// 16-B global load hidden from hipcc's waitcnt bookkeeping; valid only after an explicit
-// s_waitcnt vmcnt(0) (asm) that the caller places before the first use.
-// The destination is an ACCUMULATION register ("a"; gfx90a+ vector-memory instructions may target
-// AGPRs): the compiler does not know the value is still in flight, so whatever it does with the
-// register before the wait must be nothing.  With "=v" and more than 256 live registers (the one-wave-
-// per-SIMD forms) hipcc parked freshly "loaded" VGPRs in AGPRs right behind the asm statement -- it
-// copied bytes that had not arrived, handed the VGPR to someone else (an address), and the load then
-// landed on top of it: the memory fault of r01's 4-wave variant.  asm_land() after the wait ties the
-// value to a statement behind the wait, so every consumer (and every copy to a VGPR) comes after it.
-__device__ __forceinline__ f32x4 asm_load16(const float* addr) {
-    f32x4 r;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(r) : "v"(addr) : "memory");
-    return r;
-}
-template <typename T>
-__device__ __forceinline__ void asm_land(T& r) { asm volatile("" : "+a"(r)); }
-
 // LeakyReLU(0.2): max(v, 0.2v) is the same value for every finite v and one VALU op shorter
-__device__ __forceinline__ u32x2 asm_load8(const char* addr) {
-    u32x2 r;
-    asm volatile("global_load_dwordx2 %0, %1, off" : "=a"(r) : "v"(addr) : "memory");
-    return r;
-}
-__device__ __forceinline__ f32x4 half4_to_float(u32x2 h) {
-    const f16x4 v = __builtin_bit_cast(f16x4, h);
-    f32x4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = (float)v[i];
-    return o;
-}
 __device__ __forceinline__ float lrelu(float v) { return fmaxf(v, __fmul_rn(v, 0.2f)); }
 
 // Epilogue stores are unconditional (lanes outside the image write to a trash line), so their
@@ -141,8 +112,6 @@ __device__ __forceinline__ float lrelu(float v) { return fmaxf(v, __fmul_rn(v, 0
 template <int EPI, int CT, int NP, int HPO>
 struct EpiStores {
     static constexpr int value = (EPI == EPI_LRELU || EPI == EPI_BODY) ? CT * (HPO == 1 ? 4 : HPO == 2 ? 3 : 2) * NP
-                                 : (EPI == EPI_RDB5)                   ? CT * 4 * NP
-                                 : (EPI == EPI_RDB5_RRDB)              ? CT * 8 * NP
                                  : (EPI == EPI_FIRST)                  ? CT * 12 * NP
                                                                        : -1;   // LAST / DEBUG: data-dependent, stay conservative
 };
@@ -168,19 +137,6 @@ __device__ __forceinline__ void wait_vm_barrier() {
 #ifndef S2SR_DIAG_F8
 #define S2SR_DIAG_F8 0   // timing diagnostics of the split-operand (F8) schedule: 1 no LDS-DMA, 2 no MFMA, 4 no epilogue, 8 epilogue without its stores
 #endif
-#define S2SR_STAMP(k)                                                              \
-    do {                                                                           \
-        if (TRACE && p.trace && !(p.dbg & 4) && tid == 0 && (k) < 20)              \
-            p.trace[(size_t)blockIdx.x * 24 + (k)] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-// dbg & 4: per-wave anatomy of steady-state stage 5 instead (tools/trace_waves.py): slot 0 = leaves the
-// barrier before stage 5, slot 2 = has issued its last MFMA of stage 5, slot 1 = leaves the barrier before stage 6
-#define S2SR_WSTAMP(slot)                                                                                 \
-    do {                                                                                                  \
-        if (TRACE && p.trace && (p.dbg & 4) && lane == 0)                                                 \
-            p.trace[(size_t)blockIdx.x * 24 + (slot) * 8 + wave] = __builtin_amdgcn_s_memtime();          \
-    } while (0)
-
 // F8 (split-operand consumers, S2SR_PREC_F16_HP): a patch is 8 stages -- 4 fp16 blocks of x_hi
 // against w_hi, then 4 fp8 (e4m3) planes of 32 channels: [x_lo*2^11 | x_hi] against
 // [w_hi | w_lo*2^11], two planes per v_mfma_scale_f32_32x32x64_f8f6f4 (lanes 0-31 take their 32 K
@@ -202,8 +158,8 @@ __device__ __forceinline__ void wait_vm_barrier() {
 // tensor) and stores to (2y+py, 2x+q).
 // FULL: the launch has no ragged edge and no mosaic separators (whole patches only: H % TH == 0, W % 32 == 0, mos_py == 0): the
 // epilogue carries no px_live arithmetic and no trash-line selects (split-operand producers: conv_up -3.7 %, conv_hr -2.6 %).
-template <int CT, int NP, int WAVES, int EPI, bool UP, int R, bool TRACE = false, int HPO = 0, int OCC = 1, bool F8 = false,
-          int PH = -1, bool FULL = false>
+template <int CT, int NP, int WAVES, int EPI, bool UP, int R, int HPO = 0, int OCC = 1, bool F8 = false, int PH = -1,
+          bool FULL = false>
 __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const ConvParams p) {
     using G = Geom<WAVES, NP, CT, R, (PH >= 0 ? 4 : 9)>;
     static_assert(!F8 || R == 4, "the fp8 pair schedule is written for a 4-slot ring");
@@ -219,11 +175,6 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int pcol = lane & 31, hh = lane >> 5;
-    S2SR_STAMP(0);
-    if (TRACE && p.trace && !(p.dbg & 4) && tid == 0) {
-        p.trace[(size_t)blockIdx.x * 24 + 20] = __builtin_amdgcn_s_memrealtime();
-        p.trace[(size_t)blockIdx.x * 24 + 22] = __builtin_amdgcn_s_memtime();
-    }
 
     // ---- my patches.  Round `it` of the grid covers tiles [it*nwg, (it+1)*nwg); inside a round
     // the workgroups that share an XCD (same blockIdx % 8) take one contiguous run of tiles, so
@@ -295,18 +246,6 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
         }
     const uint32_t aaddr = G::PLANE + lane * 16;
 
-    // conv5 forms: the trunk is carried as an fp16 pair (hi = the x the convs read, lo = what fp16
-    // lost), t = hi + lo.  hi of this patch's own pixels is picked out of the slab planes while
-    // the first four stages (the 64 channels of x) are in LDS -- it never comes from HBM again.
-    constexpr bool kTrunk = (EPI == EPI_RDB5 || EPI == EPI_RDB5_RRDB);
-    u32x2 hi_cap[4][NP][2];
-    uint32_t caddr[NP];
-#pragma unroll
-    for (int np = 0; np < NP; ++np) {
-        const int q = (wave * NP + np + 1) * G::SW + pcol + 1;
-        caddr[np] = (uint32_t)(q * 32 + 16 * ((q >> 3) & 1) + 8 * hh);   // half 0; half 1 is at ^16
-    }
-
     char* const trash = p.trash + (size_t)(tid & 255) * 16;   // where out-of-image lanes park their stores
 
     f32x16 acc[CT][NP];
@@ -330,14 +269,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
     // n_issue (workgroup-uniform; 0/1, the F8 schedule also 2): stages whose DMA is issued from
     // inside this stage, into LDS slots sl_off / sl_off1
     constexpr int MAXI = F8 ? 2 : 1;
-    auto stage_body = [&](const char* buf, int n_issue, uint32_t sl_off, uint32_t sl_off1, int r, bool capture) __attribute__((always_inline)) {
-        if (kTrunk && r < 4 && capture) {
-#pragma unroll
-            for (int np = 0; np < NP; ++np) {
-                hi_cap[r < 4 ? r : 0][np][0] = *(const u32x2*)(buf + caddr[np]);
-                hi_cap[r < 4 ? r : 0][np][1] = *(const u32x2*)(buf + (caddr[np] ^ 16));
-            }
-        }
+    auto stage_body = [&](const char* buf, int n_issue, uint32_t sl_off, uint32_t sl_off1) __attribute__((always_inline)) {
         const char* sbv[MAXI] = {nullptr};
         const char* wbv[MAXI] = {nullptr};
         const uint32_t slv[2] = {sl_off, sl_off1};
@@ -385,11 +317,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
                 int j = wave + sl * WAVES;
                 if (j > G::NSTI - 1) j = G::NSTI - 1;   // padding slot: same piece again
                 const uint32_t dst = lds0 + slv[w] + (uint32_t)j * 1024;
-                uint32_t vo = loff[sl];
-                const char* bp = j < G::PI ? sbv[w] : wbv[w];
-                if (TRACE && (((p.dbg & 1) && j >= G::PI) || ((p.dbg & 2) && j < G::PI))) { vo = lane * 16; bp = (const char*)p.wpack; }
-                if (TRACE && (p.dbg & 8)) continue;   // ablation: no DMA instruction at all
-                glds16<(TRACE || EPI == EPI_DEBUG)>(bp, vo, dst);
+                glds16<EPI == EPI_DEBUG>(j < G::PI ? sbv[w] : wbv[w], loff[sl], dst);
             }
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
@@ -399,15 +327,6 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
                 for (int ct = 0; ct < CT; ++ct)
                     acc[ct][np] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[dy * 3 + dx][ct], b[step % (D + 1)], acc[ct][np], 0, 0, 0);
             }
-        }
-        // one wave per SIMD (512 registers): the accumulators live in AGPRs.  Left alone, hipcc moves every
-        // finished accumulator to VGPRs and back once per stage (~7 v_accvgpr moves per MFMA) because the
-        // epilogue behind the loop wants them in VGPRs; this pins them where the MFMAs want them.
-        if (WAVES == 4) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int np = 0; np < NP; ++np) asm volatile("" : "+a"(acc[ct][np]));
         }
     };
 
@@ -440,7 +359,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
             if (w >= n_issue) continue;
             int j = wave + sl * WAVES;
             if (j > G::NSTI - 1) j = G::NSTI - 1;
-            glds16<(TRACE || EPI == EPI_DEBUG)>(j < G::PI ? sbv[w] : wbv[w], loff[sl], lds0 + slv[w] + (uint32_t)j * 1024);
+            glds16<EPI == EPI_DEBUG>(j < G::PI ? sbv[w] : wbv[w], loff[sl], lds0 + slv[w] + (uint32_t)j * 1024);
         }
     };
     // hipcc sinks the (side-effect free) MFMAs of a finished column below the next wait/barrier and keeps
@@ -450,10 +369,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-            for (int np = 0; np < NP; ++np) {
-                if (WAVES == 4) asm volatile("" : "+a"(acc[ct][np]));   // one wave per SIMD: the accumulators live in AGPRs (see stage_body)
-                else asm volatile("" : "+v"(acc[ct][np]));
-            }
+            for (int np = 0; np < NP; ++np) asm volatile("" : "+v"(acc[ct][np]));
     };
     auto stage16_dx = [&](const char* buf, int n_issue, uint32_t sl_off, uint32_t sl_off1) __attribute__((always_inline)) {
         plan_dma(n_issue, sl_off, sl_off1);
@@ -584,39 +500,8 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
         }
         const size_t tn = (size_t)n * 8 * oblk;   // image offset inside an fp32 skip tensor (R, F), bytes
         const size_t ln = (size_t)n * 4 * oblk;   // image offset inside the fp16 lo tensor, bytes
-        // residual operands: one burst of independent loads (padded tensors make every address
-        // valid, so they are unconditional); asm loads + one explicit wait, see asm_load16.
-        u32x2 lo_old[CT][NP][4];
-        f32x4 res1[CT][NP][4];
-        f32x4 res0[CT][NP][4];   // EPI_BODY only
-        auto load_res = [&](int np) __attribute__((always_inline)) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    lo_old[ct][np][g] = asm_load8((const char*)p.T + ln + (size_t)(ct * 2 + (g >> 1)) * oblk + opix[np] * 32 +
-                                                  (g & 1) * 16 + hh * 8);
-                    if (EPI == EPI_RDB5_RRDB)
-                        res1[ct][np][g] = asm_load16((const float*)((const char*)p.R + tn + (size_t)(ct * 4 + g) * oblk + opix[np] * 32 + hh * 16));
-                }
-        };
-        auto land_res = [&](int np) __attribute__((always_inline)) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    asm_land(lo_old[ct][np][g]);
-                    if (EPI == EPI_RDB5_RRDB) asm_land(res1[ct][np][g]);
-                }
-        };
-        if (EPI == EPI_RDB5) {
-#pragma unroll
-            for (int np = 0; np < NP; ++np) load_res(np);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int np = 0; np < NP; ++np) land_res(np);
-            __builtin_amdgcn_sched_barrier(0);
-        } else if (EPI == EPI_BODY) {
+        f32x4 res0[CT][NP][4];   // EPI_BODY only: the global skip
+        if (EPI == EPI_BODY) {
 #pragma unroll
             for (int np = 0; np < NP; ++np)
 #pragma unroll
@@ -628,18 +513,12 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
 #pragma unroll
         for (int np = 0; np < NP; ++np) {
             const int y = y0 + wave * NP + np;
-            if (EPI == EPI_RDB5_RRDB) {
-                load_res(np);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                land_res(np);
-                __builtin_amdgcn_sched_barrier(0);
-            }
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
                 const int rc = ct % CTR;                                   // real cout tile
                 const size_t qoff = PH >= 0 ? (size_t)(ct / CTR) * 32 : 0;   // sub-pixel form: the pixel to the right
                 u32x2 hpk[4];   // fp16 x4 per g (hi / plain output)
-                u32x2 lpk[4];   // fp16 x4 per g (lo), trunk forms and conv_first
+                u32x2 lpk[4];   // fp16 x4 per g (lo), conv_first
                 uint32_t lo8[4], hi8[4];   // e4m3 x4 per g (HPO): channels 8g+4hh .. +3 of fp8 plane ct
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
@@ -652,17 +531,6 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
                     if (EPI == EPI_LRELU) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) v[i] = lrelu(v[i]);
-                    } else if (kTrunk) {
-                        // t = hi + lo (exact in fp32); hi was captured from LDS: block ct*2 + (g>>1), half g&1
-                        const f32x4 th = half4_to_float(hi_cap[(ct * 2 + (g >> 1)) & 3][np][g & 1]);
-                        const f32x4 tl = half4_to_float(lo_old[ct][np][g]);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const float t = __fadd_rn(th[i], tl[i]);
-                            v[i] = __fadd_rn(__fmul_rn(v[i], 0.2f), t);
-                            if (EPI == EPI_RDB5_RRDB) v[i] = __fadd_rn(__fmul_rn(v[i], 0.2f), res1[ct][np][g][i]);
-                        }
-                        if (EPI == EPI_RDB5_RRDB) *(f32x4*)(ok[np] ? (char*)p.R + to : trash) = v;
                     } else if (EPI == EPI_FIRST) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) v[i] = __fadd_rn(__fmul_rn(v[i], p.in_scale), p.bias[cb + i]);
@@ -741,7 +609,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
 #pragma unroll
                         for (int i = 0; i < 4; ++i) hv[i] = (f16)v[i];
                         hpk[g] = __builtin_bit_cast(u32x2, hv);
-                        if (kTrunk || EPI == EPI_FIRST) {
+                        if (EPI == EPI_FIRST) {
                             f16x4 lv;
 #pragma unroll
                             for (int i = 0; i < 4; ++i) lv[i] = (f16)__fsub_rn(v[i], (float)hv[i]);
@@ -801,7 +669,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
                         o[0] = r0[0]; o[1] = r1[0]; o[2] = r0[1]; o[3] = r1[1];
                         if ((S2SR_DIAG_F8 & 8) && F8) asm volatile("" ::"v"(o));   // timing diagnostic: the epilogue's arithmetic without its stores
                         else *(u32x4*)(ok[np] ? p.dst + (size_t)n * p.dst_img + (size_t)(rc * 2 + bk) * oblk + opix[np] * 32 + qoff + hh * 16 : trash) = o;
-                        if (kTrunk || EPI == EPI_FIRST) {
+                        if (EPI == EPI_FIRST) {
                             u32x2 llo = lpk[2 * bk], lhi = lpk[2 * bk + 1];
                             const auto q0 = __builtin_amdgcn_permlane32_swap(llo[0], lhi[0], false, false);
                             const auto q1 = __builtin_amdgcn_permlane32_swap(llo[1], lhi[1], false, false);
@@ -810,7 +678,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
                             *(u32x4*)(ok[np] ? (char*)p.T + ln + (size_t)(ct * 2 + bk) * oblk + opix[np] * 32 + hh * 16 : trash) = ol;
                         }
                     }
-                    if (HPO && !kTrunk && EPI != EPI_FIRST) {
+                    if (HPO && EPI != EPI_FIRST) {
                         // the lane holds dwords 2g+hh of the pixel's 32 plane bytes; after the swaps
                         // lanes 0-31 hold dwords 0-3, lanes 32-63 dwords 4-7: one 16-B store each
 #pragma unroll
@@ -841,14 +709,13 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
                 for (int sl = 0; sl < G::PW; ++sl) {
                     int j = wave + sl * WAVES;
                     if (j > G::NSTI - 1) j = G::NSTI - 1;
-                    glds16<(TRACE || EPI == EPI_DEBUG)>(j < G::PI ? sb : wb, loff[sl], lds0 + (uint32_t)(r * G::STAGE_BYTES) + (uint32_t)j * 1024);
+                    glds16<EPI == EPI_DEBUG>(j < G::PI ? sb : wb, loff[sl], lds0 + (uint32_t)(r * G::STAGE_BYTES) + (uint32_t)j * 1024);
                 }
             }
         }
     }
     __syncthreads();   // bias visible in LDS
     init_acc();
-    S2SR_STAMP(1);
 
     int k = 0, it_c = 0, st_c = 0;
     bool after_epi = false;
@@ -960,16 +827,10 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
                     wait_vm_barrier<0>();
                 }
                 after_epi = false;
-                S2SR_STAMP(2 + 2 * k);
-                if (k == 5) S2SR_WSTAMP(0);
-                if (k == 6) S2SR_WSTAMP(1);
                 if constexpr (PH >= 0)
                     stage16_dx(smem + r * G::STAGE_BYTES, (k + (R - 1) < S) ? 1 : 0, (uint32_t)(((r + R - 1) % R) * G::STAGE_BYTES), 0u);
                 else
-                    stage_body(smem + r * G::STAGE_BYTES, (k + (R - 1) < S) ? 1 : 0, (uint32_t)(((r + R - 1) % R) * G::STAGE_BYTES), 0u, r,
-                               st_c == r);   // NS % R == 0 for the trunk forms: stages 0..3 of a patch sit in slots 0..3
-                S2SR_STAMP(3 + 2 * k);
-                if (k == 5) S2SR_WSTAMP(2);
+                    stage_body(smem + r * G::STAGE_BYTES, (k + (R - 1) < S) ? 1 : 0, (uint32_t)(((r + R - 1) % R) * G::STAGE_BYTES), 0u);
                 if (++st_c == NS) {
                     epilogue(it_c);
                     init_acc();
@@ -981,23 +842,19 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
             }
         }
     }
-    if (TRACE && p.trace && !(p.dbg & 4) && tid == 0) {
-        p.trace[(size_t)blockIdx.x * 24 + 21] = __builtin_amdgcn_s_memrealtime();
-        p.trace[(size_t)blockIdx.x * 24 + 23] = __builtin_amdgcn_s_memtime();
-    }
 }
 
 // ------------------------------------------------------------------------------------------
 // launch
 // ------------------------------------------------------------------------------------------
-template <int CT, int EPI, bool UP, int WAVES, int NP, int R, bool TRACE = false, int HPO = 0, int OCC = 1, bool F8 = false,
-          int PH = -1, bool FULL = false>
+template <int CT, int EPI, bool UP, int WAVES, int NP, int R, int HPO = 0, int OCC = 1, bool F8 = false, int PH = -1,
+          bool FULL = false>
 static hipError_t launch_t(const ConvParams& p, hipStream_t st) {
     using G = Geom<WAVES, NP, CT, R, (PH >= 0 ? 4 : 9)>;
     if (FULL && (p.mos_py != 0 || p.H % G::TH != 0 || p.W % G::TW != 0)) return hipErrorInvalidValue;
     static_assert(G::LDS_BYTES * OCC <= 160 * 1024, "LDS ring does not fit");
     static_assert(G::PW*(R - 2) < 64, "vmcnt field is 6 bits");
-    auto kern = conv3x3_f16<CT, NP, WAVES, EPI, UP, R, TRACE, HPO, OCC, F8, PH, FULL>;
+    auto kern = conv3x3_f16<CT, NP, WAVES, EPI, UP, R, HPO, OCC, F8, PH, FULL>;
     if (F8 && (p.nstage != ((EPI == EPI_LAST && HPO == 3) ? 6 : 8) || ((EPI == EPI_LAST && HPO == 3) && !p.fold_lo) || p.seg_len != 4 || !p.src_lo))
         return hipErrorInvalidValue;   // 4 fp16 blocks + 4 fp8 planes (conv_last folded: + 2)
     if (PH >= 0 && !F8 && p.nstage != 4) return hipErrorInvalidValue;
@@ -1023,8 +880,6 @@ static hipError_t launch_t(const ConvParams& p, hipStream_t st) {
         }
         ncu = ncu_dev[dev];
     }
-    if ((EPI == EPI_RDB5 || EPI == EPI_RDB5_RRDB) && (p.nstage % R != 0 || p.nstage < 4))
-        return hipErrorInvalidValue;   // the trunk forms pick x out of ring slots 0..3 (see hi_cap)
     ConvParams q = p;
     if (q.seg_len <= 0) { q.seg_len = q.nstage; q.seg_lo_mask = 0; }
     if (!q.src_lo) { q.src_lo = q.src; q.lo_img = q.src_img; }
@@ -1043,84 +898,41 @@ static hipError_t launch_t(const ConvParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-// S2SR_W4=1: the RDB convs as 4-wave workgroups, one wave per SIMD with the 512-register budget
-// (8 / 4 rows per wave), instead of 8 waves x 4 / 2 rows
-#if S2SR_EXPERIMENTAL
-static bool use_w4() {
-    static const bool v = [] { const char* e = getenv("S2SR_W4"); return e && atoi(e) != 0; }();
-    return v;
-}
-#endif
-
+// the generic form: 8 waves x 2 rows (16x32 patches)
 template <int CT, int EPI, bool UP>
 static hipError_t launch_w(const ConvParams& p, hipStream_t st) {
-    constexpr int R = (CT == 1) ? 5 : 4;
-#if !S2SR_EXPERIMENTAL
-    // the RDB convs run on conv_trunk.hip; their 8-wave / 4-wave forms here (r01's trunk, S2SR_TRUNK=0 / S2SR_W4=1) and the
-    // upsample-on-load up-convs (S2SR_NO_SUBPIXEL) are in the experimental library only
-    if constexpr (!UP && ((CT == 1 && EPI == EPI_LRELU) || (CT == 2 && (EPI == EPI_RDB5 || EPI == EPI_RDB5_RRDB)))) return hipErrorNotSupported;
-    else if constexpr (UP && EPI != EPI_DEBUG) return hipErrorNotSupported;
-    else return launch_t<CT, EPI, UP, 8, 2, R>(p, st);
-#else
-    if constexpr (!UP && ((CT == 1 && EPI == EPI_LRELU) || (CT == 2 && (EPI == EPI_RDB5 || EPI == EPI_RDB5_RRDB)))) {
-        if (use_w4()) {
-            if constexpr (CT == 1) {
-                const long n32 = (long)((p.W + 31) / 32) * ((p.H + 31) / 32) * p.N;
-                if (n32 >= 192) return launch_t<1, EPI_LRELU, false, 4, 8, 3>(p, st);
-                return launch_t<1, EPI_LRELU, false, 4, 4, 5>(p, st);
-            } else {
-                return launch_t<2, EPI, false, 4, 4, 4>(p, st);
-            }
-        }
-    }
-    if (CT == 1 && EPI == EPI_LRELU && !UP) {
-        // the 32-cout RDB convs: 32x32 patch (4 rows per wave), 3-deep ring -- unless that leaves most
-        // CUs without a patch (single tiles): then the 16x32 patch spreads the image over twice as
-        // many workgroups
-        const long n32 = (long)((p.W + 31) / 32) * ((p.H + 31) / 32) * p.N;
-        if (n32 >= 192) return launch_t<1, EPI_LRELU, false, 8, 4, 3>(p, st);
-    }
-    return launch_t<CT, EPI, UP, 8, 2, R>(p, st);
-#endif
+    return launch_t<CT, EPI, UP, 8, 2, (CT == 1) ? 5 : 4>(p, st);
 }
 
 hipError_t launch_conv(const ConvParams& p, int ct, int epi, bool up, bool lo_out, hipStream_t st, bool f8_in) {
     if (f8_in) {   // split-operand mode: fp16 main term + fp8 correction planes in; lo_out: fp8 planes out as well
-#if S2SR_EXPERIMENTAL
-        if (p.tail_form & 1) {   // one wave per SIMD: 4 waves x 4 rows, the same 16x32 patch and ring
-            if (ct == 2 && lo_out && epi == EPI_LRELU && !up) return launch_t<2, EPI_LRELU, false, 4, 4, 4, false, 1, 1, true>(p, st);
-            if (ct == 1 && !lo_out && epi == EPI_LAST && !up && p.nstage == 6 && p.fold_lo) return launch_t<1, EPI_LAST, false, 4, 4, 4, false, 3, 1, true>(p, st);
-        }
-#endif
         const bool full = p.mos_py == 0 && p.H % 16 == 0 && p.W % 32 == 0 && !(p.tail_form & 8);   // whole 16x32 patches (bit 3: diagnostic off switch)
         if (ct == 2 && lo_out && epi == EPI_LRELU && !up && (p.tail_form & 2))   // conv_hr in front of a folded conv_last: no hi8 planes out
-            return full ? launch_t<2, EPI_LRELU, false, 8, 2, 4, false, 2, 1, true, -1, true>(p, st)
-                        : launch_t<2, EPI_LRELU, false, 8, 2, 4, false, 2, 1, true>(p, st);
-        if (ct == 2 && lo_out && epi == EPI_BODY && !up && full) return launch_t<2, EPI_BODY, false, 8, 2, 4, false, 1, 1, true, -1, true>(p, st);
+            return full ? launch_t<2, EPI_LRELU, false, 8, 2, 4, 2, 1, true, -1, true>(p, st)
+                        : launch_t<2, EPI_LRELU, false, 8, 2, 4, 2, 1, true>(p, st);
+        if (ct == 2 && lo_out && epi == EPI_BODY && !up && full) return launch_t<2, EPI_BODY, false, 8, 2, 4, 1, 1, true, -1, true>(p, st);
         if (ct == 2 && lo_out) {
-#if S2SR_EXPERIMENTAL
-            if (epi == EPI_LRELU && up) return launch_t<2, EPI_LRELU, true, 8, 2, 4, false, 1, 1, true>(p, st);
-#endif
-            if (epi == EPI_LRELU && !up) return launch_t<2, EPI_LRELU, false, 8, 2, 4, false, 1, 1, true>(p, st);
-            if (epi == EPI_BODY && !up) return launch_t<2, EPI_BODY, false, 8, 2, 4, false, 1, 1, true>(p, st);
+            if (epi == EPI_LRELU && !up) return launch_t<2, EPI_LRELU, false, 8, 2, 4, 1, 1, true>(p, st);
+            if (epi == EPI_BODY && !up) return launch_t<2, EPI_BODY, false, 8, 2, 4, 1, 1, true>(p, st);
         }
         if (ct == 1 && !lo_out && epi == EPI_LAST && !up) {
             if (p.nstage == 6 && p.fold_lo)
-                return full ? launch_t<1, EPI_LAST, false, 8, 2, 4, false, 3, 1, true, -1, true>(p, st)
-                            : launch_t<1, EPI_LAST, false, 8, 2, 4, false, 3, 1, true>(p, st);
-            return launch_t<1, EPI_LAST, false, 8, 2, 4, false, 0, 1, true>(p, st);
+                return full ? launch_t<1, EPI_LAST, false, 8, 2, 4, 3, 1, true, -1, true>(p, st)
+                            : launch_t<1, EPI_LAST, false, 8, 2, 4, 3, 1, true>(p, st);
+            return launch_t<1, EPI_LAST, false, 8, 2, 4, 0, 1, true>(p, st);
         }
         return hipErrorInvalidValue;
     }
     if (lo_out) return hipErrorInvalidValue;
+    // the RDB convs run on conv_trunk.hip, the up-convs in sub-pixel form (launch_conv_phase)
+    if ((ct == 1 && epi == EPI_LRELU && !up) || (ct == 2 && epi == EPI_LRELU && up) ||
+        (ct == 2 && (epi == EPI_RDB5 || epi == EPI_RDB5_RRDB) && !up))
+        return hipErrorNotSupported;
     if (ct == 1) {
-        if (epi == EPI_LRELU && !up) return launch_w<1, EPI_LRELU, false>(p, st);
         if (epi == EPI_LAST && !up) return launch_w<1, EPI_LAST, false>(p, st);
         if (epi == EPI_DEBUG) return up ? launch_w<1, EPI_DEBUG, true>(p, st) : launch_w<1, EPI_DEBUG, false>(p, st);
     } else if (ct == 2) {
-        if (epi == EPI_LRELU) return up ? launch_w<2, EPI_LRELU, true>(p, st) : launch_w<2, EPI_LRELU, false>(p, st);
-        if (epi == EPI_RDB5 && !up) return launch_w<2, EPI_RDB5, false>(p, st);
-        if (epi == EPI_RDB5_RRDB && !up) return launch_w<2, EPI_RDB5_RRDB, false>(p, st);
+        if (epi == EPI_LRELU) return launch_w<2, EPI_LRELU, false>(p, st);
         if (epi == EPI_FIRST && !up) return launch_w<2, EPI_FIRST, false>(p, st);
         if (epi == EPI_BODY && !up) return launch_w<2, EPI_BODY, false>(p, st);
         if (epi == EPI_DEBUG) return up ? launch_w<2, EPI_DEBUG, true>(p, st) : launch_w<2, EPI_DEBUG, false>(p, st);
@@ -1131,36 +943,19 @@ hipError_t launch_conv(const ConvParams& p, int ct, int epi, bool up, bool lo_ou
 // one ROW parity of a split-operand up-conv in sub-pixel form (both column parities inside the launch;
 // p.H, p.W = source dims, p.Hp, p.Wp = 2x tensor)
 hipError_t launch_conv_phase(const ConvParams& p, int py, hipStream_t st, bool f8) {
-#if S2SR_EXPERIMENTAL
-    if (f8 && (p.tail_form & 1)) {   // one wave per SIMD: 4 waves x 2 source rows
-        if (py == 0) return launch_t<4, EPI_LRELU, false, 4, 2, 4, false, 1, 1, true, 0>(p, st);
-        if (py == 1) return launch_t<4, EPI_LRELU, false, 4, 2, 4, false, 1, 1, true, 1>(p, st);
-    }
-#endif
     if (f8 && p.mos_py == 0 && p.H % 8 == 0 && p.W % 32 == 0 && !(p.tail_form & 8)) {   // whole 8x32 source patches
-        if (py == 0) return launch_t<4, EPI_LRELU, false, 8, 1, 4, false, 1, 1, true, 0, true>(p, st);
-        if (py == 1) return launch_t<4, EPI_LRELU, false, 8, 1, 4, false, 1, 1, true, 1, true>(p, st);
+        if (py == 0) return launch_t<4, EPI_LRELU, false, 8, 1, 4, 1, 1, true, 0, true>(p, st);
+        if (py == 1) return launch_t<4, EPI_LRELU, false, 8, 1, 4, 1, 1, true, 1, true>(p, st);
     }
     if (f8) {
-        if (py == 0) return launch_t<4, EPI_LRELU, false, 8, 1, 4, false, 1, 1, true, 0>(p, st);
-        if (py == 1) return launch_t<4, EPI_LRELU, false, 8, 1, 4, false, 1, 1, true, 1>(p, st);
+        if (py == 0) return launch_t<4, EPI_LRELU, false, 8, 1, 4, 1, 1, true, 0>(p, st);
+        if (py == 1) return launch_t<4, EPI_LRELU, false, 8, 1, 4, 1, 1, true, 1>(p, st);
     } else {   // plain fp16 mode: the same four fp16 stages, no correction planes in or out
-        if (py == 0) return launch_t<4, EPI_LRELU, false, 8, 2, 4, false, 0, 1, false, 0>(p, st);
-        if (py == 1) return launch_t<4, EPI_LRELU, false, 8, 2, 4, false, 0, 1, false, 1>(p, st);
+        if (py == 0) return launch_t<4, EPI_LRELU, false, 8, 2, 4, 0, 1, false, 0>(p, st);
+        if (py == 1) return launch_t<4, EPI_LRELU, false, 8, 2, 4, 0, 1, false, 1>(p, st);
     }
     return hipErrorInvalidValue;
 }
-
-#if S2SR_EXPERIMENTAL
-hipError_t launch_conv_trace(const ConvParams& p, int ct, hipStream_t st) {
-    if (use_w4()) {
-        if (ct == 1) return launch_t<1, EPI_LRELU, false, 4, 8, 3, true>(p, st);
-        return launch_t<2, EPI_RDB5, false, 4, 4, 4, true>(p, st);
-    }
-    if (ct == 1) return launch_t<1, EPI_LRELU, false, 8, 4, 3, true>(p, st);
-    return launch_t<2, EPI_RDB5, false, 8, 2, 4, true>(p, st);
-}
-#endif
 
 // ------------------------------------------------------------------------------------------
 // host-side weight repack.  Layout: [stage = cin/16][tap][ct][lane 0..63][j 0..7] fp16 with
@@ -1252,11 +1047,6 @@ static void pack_f8hp_taps(const float* w, int cin, int cout, int taps, void* ds
                         *d16++ = o;
                     }
     uint8_t* d = (uint8_t*)d16;
-#if S2SR_EXPERIMENTAL
-    static const bool diag_no_wlo = [] { const char* e = getenv("S2SR_DIAG_NO_WLO"); return e && atoi(e) != 0; }();   // numerics diagnostic
-#else
-    const bool diag_no_wlo = false;
-#endif
     for (int part = 0; part < (fold ? 1 : 2); ++part)                   // 0: w_hi (meets x_lo), 1: w_lo * 2^11 (meets x_hi)
         for (int pl = 0; pl < 2; ++pl)
             for (int t = 0; t < taps; ++t)
@@ -1269,7 +1059,7 @@ static void pack_f8hp_taps(const float* w, int cin, int cout, int taps, void* ds
                                 if (co < cout && ci < cin) {
                                     const float x = w[((size_t)co * cin + ci) * taps + t];
                                     const float hi = (float)(f16)x;
-                                    v = part == 0 ? hi : (diag_no_wlo ? 0.0f : (x - hi) * 2048.0f);
+                                    v = part == 0 ? hi : (x - hi) * 2048.0f;
                                 }
                                 *d++ = f32_to_e4m3(v);
                             }

@@ -88,22 +88,18 @@ typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-// WGL (r04 A/B; measured 3.4 % SLOWER, profiles/r04_trunk_ab.txt: experimental library only): the weights do NOT travel through the LDS-DMA ring.  Every wave fetches the 9 * CT A
-// fragments of the NEXT stage with global_load_dwordx4 straight into AGPRs (two register sets, ping-pong; the accumulators of
-// the conv1-4 forms live in architectural VGPRs, so the AGPRs are free), one stage ahead.  A stage in LDS is then the slab plane
-// alone: 20 % fewer LDS-DMA bytes and instructions, 23 % fewer LDS reads, and room for one more ring slot.
 // PL (r04, the single-tile forms): planes per pipeline stage.  A stage of an 8x32 patch is 0.7 us for 0.28 us of MFMA work -- its
 // barrier, its LDS round trips and its DMA issue are per-stage costs (profiles/r04_latency_anatomy.txt) -- so the small forms take
 // TWO 16-channel planes (and their two weight blocks) per stage: half the barriers per patch, the same MFMAs in the same order.
-template <int CT_, int NP_, int R_, int WGL_ = 0, int PL_ = 1>
+template <int CT_, int NP_, int R_, int PL_ = 1>
 struct TG {
-    static constexpr int CT = CT_, NP = NP_, R = R_, WAVES = 4, WGL = WGL_, PL = PL_;
+    static constexpr int CT = CT_, NP = NP_, R = R_, WAVES = 4, PL = PL_;
     static constexpr int TH = WAVES * NP, TW = 32, SW = TW + 2, SH = TH + 2, SPX = SH * SW;
     static constexpr int ROWB = SW * 32;                       // bytes of one slab row
     static constexpr int PLANE = ((SPX * 32 + 1023) / 1024) * 1024;
     static constexpr int PI1 = PLANE / 1024, PI = PL * PI1;    // slab DMA pieces per plane / per stage
     static constexpr int WI1 = 9 * CT, WI = PL * WI1;          // weight pieces (KiB) per plane / per stage
-    static constexpr int NSTI = PI + (WGL ? 0 : WI);
+    static constexpr int NSTI = PI + WI;
     static constexpr int WOFF = PL * PLANE;                    // the stage's weight blocks sit behind its slab planes
     static constexpr int PW = (NSTI + WAVES - 1) / WAVES;      // LDS-DMA instructions per wave and stage
     static constexpr int STAGE_BYTES = NSTI * 1024;
@@ -112,39 +108,23 @@ struct TG {
     static constexpr int LDS_BYTES = BIAS_OFF + CT * 128;
     static constexpr int T = 3 * (NP + 2);                     // B fragments (steps) per plane
     static constexpr int TS = PL * T;                          // ... per stage
-    // steps over which a stage's DMA instructions are spread.  Deeper rings issue them up to the barrier step (the awaited stage was
-    // issued stages ago); a DOUBLE buffer of big stages (the 64x32 form) awaits the very stage it is issuing: its pieces go out in the first third
-    static constexpr int ISS = (R_ == 2 && NP_ > 8) ? 12 : TS - 3;     // (12 steps for 20 pieces: two per step at most)
-    static constexpr int PV = PW + (WGL ? WI : 0);             // vector-memory instructions per wave and stage (WGL: + the A-fragment loads)
-    // ... that may stay in flight at a barrier.  WGL: the A fragments of the next stage were requested at the start of this one
-    // and must have landed: only this stage's own DMA pieces, issued behind them, may still fly
-    static constexpr int NW = WGL ? PW : PV * (R - 2);
-    static constexpr int NW0 = WGL ? PW * (R - 2) : NW;        // the prologue's wait: stage 0 (and its A fragments, requested first) landed
+    static constexpr int ISS = TS - 3;                         // steps over which a stage's DMA instructions are spread (up to the barrier step)
+    static constexpr int NW = PW * (R - 2);                    // vector-memory instructions per wave that may stay in flight at a barrier
     static_assert((NP + 2) % 2 == 0, "the 6-deep B ring needs T % 6 == 0");
     static constexpr int AK = (3 * CT + NP + 1) / (NP + 2);    // A fragments fetched per step: the 3 * CT of the next kernel column must fit the NP + 2 steps of this one
     static_assert(3 * CT <= AK * (NP + 2), "the A fragments of a kernel column must fit its steps");
-    static_assert(ISS <= TS - 3 && PW <= 2 * ISS, "DMA slots must fit in front of the barrier step");
-    static_assert(PL == 1 || WGL == 0, "");
+    static_assert(PW <= 2 * ISS, "DMA slots must fit in front of the barrier step");
 };
 
-// LDS-DMA, 16 B per lane (conv3x3.hip glds16).  FORCE_UNIFORM: the stamped diagnostic build's divergent stamp
-// branches make hipcc keep the uniform base / LDS address in VGPRs; re-derive them through v_readfirstlane.
-template <bool FORCE_UNIFORM>
+// LDS-DMA, 16 B per lane (conv3x3.hip glds16)
 __device__ __forceinline__ void glds16(const char* base, uint32_t voff, uint32_t lds_addr) {
-    if (FORCE_UNIFORM) {
-        const uint64_t v = (uint64_t)base;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-        base = (const char*)(((uint64_t)hi << 32) | lo);
-        lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_addr) : "memory");
-    } else {
-        // the slot offset also feeds VALU address arithmetic, and hipcc then keeps it in a VGPR, which an "s"
-        // operand does not legalise: pin it to an SGPR (folds away when it already is one)
-        lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_addr) : "memory");
-    }
+    // the slot offset also feeds VALU address arithmetic, and hipcc then keeps it in a VGPR, which an "s"
+    // operand does not legalise: pin it to an SGPR (folds away when it already is one)
+    lds_addr = __builtin_amdgcn_readfirstlane(lds_addr);
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(base), "s"(lds_addr) : "memory");
 }
-// hidden global loads into AGPRs + landing tie: see conv3x3.hip (asm_load16)
+// hidden global loads into AGPRs + landing tie: the destination is an AGPR because hipcc does not know the value is still in
+// flight (with "=v" it parked such VGPRs in AGPRs and reused them -- r01's fault); asm_land() behind the wait ties every consumer to it
 __device__ __forceinline__ f32x4 asm_load16(const char* addr) {
     f32x4 r;
     asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(r) : "v"(addr) : "memory");
@@ -201,14 +181,6 @@ __device__ __forceinline__ void mfma_first_v(f32x16& acc, const f16x8& a, const 
 __device__ __forceinline__ void mfma_first_bias_v(f32x16& acc, const f16x8& a, const f16x8& b, const f32x16& bias) {
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(acc) : "v"(a), "v"(b), "v"(bias));
 }
-// ... and with the A operand in AGPRs (WGL: the weights are loaded there straight from global memory; gfx90a+ MFMAs take A / B
-// from either file)
-__device__ __forceinline__ void mfma_acc_va(f32x16& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(a), "v"(b));
-}
-__device__ __forceinline__ void mfma_first_bias_va(f32x16& acc, const f16x8& a, const f16x8& b, const f32x16& bias) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(acc) : "a"(a), "v"(b), "v"(bias));
-}
 template <typename T>
 __device__ __forceinline__ void asm_land_v(T& r) { asm volatile("" : "+v"(r)); }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -236,26 +208,17 @@ struct TrunkStores {   // epilogue stores per wave (all unconditional, see conv3
     static constexpr int value = (EPI == EPI_LRELU) ? CT * 2 * NP : CT * 3 * NP;     // conv5: two fp16 blocks of x + one e4m3 plane of lo per 32 couts
 };
 
-// PROD = 1 (conv1-4 form only: its 208 registers fit two waves on a SIMD): a FIFTH wave issues every LDS-DMA instruction of the
-// workgroup and nothing else, as in conv_trunk_f8.  An LDS-DMA instruction holds its wave's issue port for ~60 cycles (12 per
-// stage and wave: a quarter of a stage with the matrix pipe starving behind an in-order wave); a wave that only loads can sit
-// in that stall for free.  One barrier per stage for everybody: the loader arrives when the NEXT stage has landed.
 // FULL: the launch has no ragged edge and no mosaic separators (H % TH == 0, W % 32 == 0, mos_py == 0 -- the 256x256 tile
 // batches): every pixel of every patch is live, so the epilogue carries no px_live arithmetic, no trash-line selects and none
 // of the SGPR spills they cost (conv1-4, 32x32 form: 2544 -> 1880 instructions, 142 -> 6 v_readlane; 71.1 -> 68.8 us per launch).
 // FULL == 3: ragged launches without mosaics (any image that is no multiple of the patch): the extent test alone.
 // FULL == 2: mosaics of the reference's default windows (256 + 2 x 10 = 276 pixels, period 277, at the trunk's scale): the separator
 // test on compile-time constants -- the 8 scalars of the runtime geometry are what pushes the generic form over its SGPR budget.
-// LOE: conv5's lo encoding in its short form (the shipped one) or its long form (experimental library: the byte-identity test
-// of the two, tests/test_gpu_trunk.py::test_f16_conv5_lo_encoding_forms_agree).
-template <int CT, int NP, int R, int EPI, bool TRACE, int PROD = 0, int FULL = 0, int WGL = 0, int LOE = S2SR_F16_LOENC, int PL = 1>
-__global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const ConvParams p) {
-    using G = TG<CT, NP, R, WGL, PL>;
-    static_assert(PL == 1 || (!TRACE && PROD == 0), "two-plane stages: plain forms only");
-    static_assert(WGL == 0 || (EPI == EPI_LRELU && !TRACE && PROD == 0), "weights-from-global form: conv1-4 only");
+template <int CT, int NP, int R, int EPI, int FULL = 0, int PL = 1>
+__global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
+    using G = TG<CT, NP, R, PL>;
     constexpr bool kTrunk = (EPI == EPI_RDB5 || EPI == EPI_RDB5_RRDB);
     static_assert(EPI == EPI_LRELU || kTrunk, "trunk kernel: conv1-4 (LRELU) and conv5 (RDB5 / RDB5_RRDB) only");
-    static_assert(PROD == 0 || (EPI == EPI_LRELU && !TRACE), "loader wave: conv1-4 form only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x;
@@ -271,27 +234,12 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
     const int my_tiles = (ntiles - slot_in_round + nwg - 1) / nwg;
     if (my_tiles <= 0) return;                                   // workgroup-uniform
     const int NS = p.nstage / PL;                                // stages per patch (of PL planes each)
-    // dbg bit 5 (32): launch anatomy of a small launch (tools/launch_anatomy.py), wave 0 lane 0: [0] entry (s_memrealtime), [1] entry,
-    // [2] prologue DMA issued, [3] first barrier passed (stage 0 landed), [4] last stage of the last patch done, [5] its epilogue's
-    // stores issued, [6] exit after vmcnt(0) (all s_memtime), [7] exit (s_memrealtime)
-    const bool kAnat = TRACE && p.trace && (p.dbg & 32) && tid == 0;
-    if (kAnat) {
-        p.trace[(size_t)blockIdx.x * 24 + 0] = __builtin_amdgcn_s_memrealtime();
-        p.trace[(size_t)blockIdx.x * 24 + 1] = __builtin_amdgcn_s_memtime();
-    }
-    if (TRACE && p.trace && !(p.dbg & 52) && tid == 0) {         // whole-kernel clock stamps (tools/trunk_anatomy.py)
-        p.trace[(size_t)blockIdx.x * 24 + 20] = __builtin_amdgcn_s_memrealtime();
-        p.trace[(size_t)blockIdx.x * 24 + 22] = __builtin_amdgcn_s_memtime();
-    }
     const uint32_t sblk = (uint32_t)p.sHp * p.sWp * 32;
     const size_t oblk = (size_t)p.Hp * p.Wp * 32;
 
     constexpr bool kBiasC = (EPI == EPI_LRELU) && S2SR_F16_BIASC;
-    constexpr bool kAccV = (EPI == EPI_LRELU) && S2SR_F16_ACCV && !TRACE;
-    // rows whose accumulators live in architectural VGPRs (the rest in AGPRs): all of them up to 8 rows per wave; the 16-row form
-    // (64x32 patches) splits 8 + 8 -- 256 accumulator registers do not fit one file next to the fragments
-    constexpr int NPV = kAccV ? (NP > 8 ? 8 : NP) : 0;
-    constexpr bool kSplit = NPV > 0 && NPV < NP;
+    constexpr bool kAccV = (EPI == EPI_LRELU) && S2SR_F16_ACCV;
+    static_assert(NP <= 8, "accumulators of at most 8 rows per wave fit one register file next to the fragments");
 
     // ---- per-lane global offsets of this wave's PW DMA pieces (patch independent)
     uint32_t loff[G::PW];
@@ -336,54 +284,14 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
     auto dma_piece = [&](int sl, uint32_t slot_off) __attribute__((always_inline)) {
         int j = wave + sl * 4;
         if (j > G::NSTI - 1) j = G::NSTI - 1;
-        if (TRACE && (p.dbg & 8)) return;                         // ablation (results wrong): no DMA instruction at all
-        glds16<TRACE>(j < G::PI ? sb_i : wb_i, loff[sl], lds0 + slot_off + (uint32_t)j * 1024);
+        glds16(j < G::PI ? sb_i : wb_i, loff[sl], lds0 + slot_off + (uint32_t)j * 1024);
     };
-
-    // ---- the loader wave (PROD): the whole workgroup's DMA schedule                          [role-branch]
-    // (tests/test_abi_cpu.py moves the block between the [hidden-bias-requests] markers up to this line in a scratch copy -- r04's
-    // faulting placement -- and expects tools/check_asm_loads.py --cfg to report it)
-    if (PROD && wave == 4) {
-        uint32_t loffP[G::PI];                                   // my 16 bytes of slab piece j
-#pragma unroll
-        for (int j = 0; j < G::PI; ++j) {
-            const int i = j * 64 + lane;
-            int q = i >> 1;
-            if (q >= G::SPX) q = 0;
-            const int ry = q / G::SW, rx = q - ry * G::SW;
-            const int h2 = (i & 1) ^ ((rx >> 3) & 1);
-            loffP[j] = (uint32_t)((ry * p.sWp + rx) * 32 + h2 * 16);
-        }
-        auto issue_stage = [&](uint32_t slot_off) __attribute__((always_inline)) {   // the stage under the cursor -> ring slot
-            cursor_next();
-#pragma unroll
-            for (int j = 0; j < G::PI; ++j) glds16<false>(sb_i, loffP[j], lds0 + slot_off + (uint32_t)j * 1024);
-#pragma unroll
-            for (int j = 0; j < G::WI; ++j) glds16<false>(wb_i, (uint32_t)(j * 1024 + lane * 16), lds0 + slot_off + (uint32_t)(G::PI + j) * 1024);
-        };
-        constexpr int NLAND = PROD ? G::NSTI * (R - 2) : 0;      // pieces that may still be in flight when the awaited stage has landed
-        static_assert(NLAND < 64, "vmcnt field is 6 bits");
-#pragma unroll
-        for (int r = 0; r < R - 1; ++r) issue_stage((uint32_t)(r * G::STAGE_BYTES));
-        asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(NLAND) : "memory");          // stage 0 has landed
-        const int total = my_tiles * NS;
-        uint32_t slot = 0;
-        for (int k = 0; k < total; ++k) {
-            // stage k + R - 1 goes where stage k - 1 was: the barrier of stage k - 1 (passed) released that slot
-            issue_stage(slot == 0 ? (uint32_t)(G::RING_BYTES - G::STAGE_BYTES) : slot - G::STAGE_BYTES);
-            asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(NLAND) : "memory");      // stage k + 1 has landed: the barrier inside stage k
-            slot = (slot + G::STAGE_BYTES == (uint32_t)G::RING_BYTES) ? 0u : slot + G::STAGE_BYTES;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        return;
-    }
 
     // The bias is REQUESTED here and consumed behind the first wait of the ring (r04 launch anatomy: as plain C++ the two
     // dependent round trips -- bias to LDS, bias to the C operand -- sat in front of the first DMA instruction: 1.5 of the
     // 2 us prologue of a 7-8 us single-tile launch).  Inline asm: the compiler's own wait would drain the ring.
-    // BEHIND the loader wave's branch: a hidden load whose destination is dead on some path lands in registers the compiler has
-    // handed to something else there (the loader's DMA offsets: a memory fault, r04).
-    // [hidden-bias-requests begin]
+    // (A hidden load whose destination is dead on some path lands in registers the compiler has handed to something else there:
+    // in front of a loader wave's role branch, its DMA offsets -- a memory fault, r04.  tools/check_asm_loads.py --cfg.)
     constexpr bool kEarly = S2SR_F16_EARLYBIAS != 0;
     uint32_t bias_l = 0;
     if (!kEarly && tid < CT * 32) ((float*)(smem + G::BIAS_OFF))[tid] = p.bias[tid];
@@ -398,7 +306,6 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
                 bq[kBiasC ? ct : 0][g] = kAccV ? asm_load16v(a) : asm_load16(a);
             }
     }
-    // [hidden-bias-requests end]
 
     // ---- fragment addresses inside a slot: per-lane base + immediate
     uint32_t bbase[3];
@@ -418,7 +325,6 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
     // conv1-4: the bias rides in as the C operand of each accumulator's first MFMA (16 AGPRs per cout tile, loaded once);
     // conv5 keeps adding it in the epilogue (its AGPRs are spoken for by the residual operands)
     f32x16 bacc[kBiasC ? CT : 1];
-    f32x16 bacc_a[(kBiasC && kSplit) ? CT : 1];                  // ... and its AGPR copy for the rows that accumulate there (C and D share a file)
     if (!kEarly && kBiasC) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
@@ -434,36 +340,20 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
     }
     f16x8 acol[3][3][CT];     // A fragments: [kernel column dx][kernel row dy][cout tile]
     f16x8 breg[6];            // B fragments of steps t, t+1, t+2, t+3 (ring indexed by step % 6)
-    // WGL: the A fragments of two stages in AGPRs, [set][tap * CT + ct]; set = stage parity inside the patch (NS is even)
-    f16x8 aw[WGL ? 2 : 1][WGL ? 9 * CT : 1];
-    const char* const wlane = (const char*)p.wpack + (size_t)lane * 16;
-    auto issue_a = [&](auto set_tag, int st) __attribute__((always_inline)) {     // stage st of a patch -> register set
-        constexpr int SET = decltype(set_tag)::value;
-        if constexpr (WGL != 0) {
-            const char* a = wlane + (size_t)st * (G::WI * 1024);
-#pragma unroll
-            for (int f = 0; f < 9 * CT; ++f)
-                aw[SET][f] = __builtin_bit_cast(f16x8, asm_load16(a + (size_t)f * 1024));     // (through the helper: an asm operand that names a captured array inside a generic lambda does not compile)
-        }
-    };
 
     // ---- prologue: R-1 stages in flight, then the first fragments of stage 0
     // (r04, measured and dropped -- tools/ab_latency.sh, profiles/r04_latency_anatomy.txt: issuing exactly as many stage loads
     // as a workgroup runs stages, instead of letting the cursor park on the last stage and re-load it R-1 times, with waits that
     // count the loads really younger: one tile 4.00 -> 4.20 ms, 64x64 2.83 -> 3.10 ms, the 32-tile step 82.2 -> 83.7 ms.  The
     // redundant loads cost nothing measurable; the run-time wait selection and its scalar state do.)
-    if (WGL) issue_a(std::integral_constant<int, 0>{}, 0);          // the first stage's weights, in front of everything
 #pragma unroll
-    for (int r = 0; r < (PROD ? 0 : R - 1); ++r) {
+    for (int r = 0; r < R - 1; ++r) {
         cursor_next();
 #pragma unroll
         for (int sl = 0; sl < G::PW; ++sl) dma_piece(sl, (uint32_t)(r * G::STAGE_BYTES));
     }
     uint32_t cur_off = 0;                                         // LDS offset of the slot of the stage being computed
-    if (kAnat) p.trace[(size_t)blockIdx.x * 24 + 2] = __builtin_amdgcn_s_memtime();
-    if (PROD) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   // the loader waited for the data (vmcnt: my bias request)
-    else wait_release_barrier<G::NW0>();                          // stage 0 has landed
-    if (kAnat) p.trace[(size_t)blockIdx.x * 24 + 3] = __builtin_amdgcn_s_memtime();
+    wait_release_barrier<G::NW>();                                // stage 0 has landed
     // the bias requests are older than every DMA instruction: they have landed too.  conv5 reads it from LDS in its epilogue
     // (every stage barrier lies in between), conv1-4 feed it to the first MFMA of each accumulator as C.
     if (kEarly && !kBiasC) {
@@ -482,25 +372,17 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
             }
             if (kAccV) asm volatile("" : "+v"(bacc[kBiasC ? ct : 0]));
             else asm volatile("" : "+a"(bacc[kBiasC ? ct : 0]));
-            if (kSplit) {
-                bacc_a[kSplit ? ct : 0] = bacc[kBiasC ? ct : 0];
-                asm volatile("" : "+a"(bacc_a[kSplit ? ct : 0]));
-            }
         }
     }
     {
         const char* sb = smem;
-        if (!WGL) {
 #pragma unroll
-            for (int dy = 0; dy < 3; ++dy)
+        for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
-                for (int ct = 0; ct < CT; ++ct) acol[0][dy][ct] = *(const f16x8*)(sb + abase + ((dy * 3) * CT + ct) * 1024);
-        }
+            for (int ct = 0; ct < CT; ++ct) acol[0][dy][ct] = *(const f16x8*)(sb + abase + ((dy * 3) * CT + ct) * 1024);
 #pragma unroll
         for (int v = 0; v < 3; ++v) breg[v] = *(const f16x8*)(sb + bbase[0] + v * G::ROWB);
     }
-
-    int kglob = 0;   // TRACE only
 
     // conv5: the trunk-lo operands of the patch's own pixels are requested at the START of the patch's last stage, straight
     // into AGPRs, and arrive under its MFMAs instead of stalling the epilogue for an HBM round trip
@@ -542,17 +424,14 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
 
     // One stage.  FIRST: first stage of a patch (accumulators start from C = 0; the barrier inside it may also
     // leave the previous patch's epilogue stores in flight).  CAP >= 0: capture x block CAP for the trunk epilogue.
-    auto stage = [&](auto first_tag, auto cap_tag, bool first_patch, auto set_tag, int st_next) __attribute__((always_inline)) {
+    auto stage = [&](auto first_tag, auto cap_tag, bool first_patch) __attribute__((always_inline)) {
         constexpr bool FIRST = decltype(first_tag)::value;
         constexpr int CAP = decltype(cap_tag)::value;
-        constexpr int SET = decltype(set_tag)::value;             // WGL: the register set this stage's A fragments sit in
-        static_assert(!WGL || (kAccV && kBiasC), "WGL: accumulators in VGPRs, bias as C");
-        if (WGL) issue_a(std::integral_constant<int, SET ^ 1>{}, st_next);     // the next stage's, one stage ahead (other set)
         const uint32_t next_off = (cur_off + G::STAGE_BYTES == (uint32_t)G::RING_BYTES) ? 0u : cur_off + G::STAGE_BYTES;
         const uint32_t dma_off = (cur_off == 0) ? (uint32_t)(G::RING_BYTES - G::STAGE_BYTES) : cur_off - G::STAGE_BYTES;
         const char* sb = smem + cur_off;
         const char* sn = smem + next_off;
-        if (!PROD) cursor_next();                                 // the stage R-1 ahead: its DMA rides on this stage
+        cursor_next();                                            // the stage R-1 ahead: its DMA rides on this stage
 #pragma unroll
         for (int pl = 0; pl < PL; ++pl) {                         // the stage's planes, one after the other; the barrier sits in the last
         const bool last = pl == PL - 1;
@@ -567,25 +446,12 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
             if (last && t == G::T - 3) {
                 // next stage landed + this slot released; everything below reads the NEXT slot
                 constexpr int NST = TrunkStores<EPI, CT, NP>::value;
-                // (WGL: the A fragments requested at the top of this stage are YOUNGER than the previous epilogue's stores and must
-                // have landed: no allowance for the stores)
                 // (R == 2, a double buffer: the awaited stage's DMA pieces are issued in THIS stage, behind the previous epilogue's
                 // stores -- an allowance for the stores would leave that many of the awaited pieces in flight: r04, found by
                 // test_window_mosaics_give_the_same_bytes on the two-plane conv5 form with several patches per workgroup)
-                constexpr int NEPI = (WGL || R == 2) ? G::NW : ((G::NW + NST < 63) ? G::NW + NST : 63);
-                if (PROD) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // my only vector-memory traffic are stores
-                else if (FIRST && !first_patch) wait_release_barrier<NEPI>();
+                constexpr int NEPI = (R == 2) ? G::NW : ((G::NW + NST < 63) ? G::NW + NST : 63);
+                if (FIRST && !first_patch) wait_release_barrier<NEPI>();
                 else wait_release_barrier<G::NW>();
-                if (TRACE && p.trace && (p.dbg & 4) && lane == 0) {
-                    if (kglob == 4) p.trace[(size_t)blockIdx.x * 24 + 0 * 8 + wave] = __builtin_amdgcn_s_memtime();
-                    if (kglob == 5) p.trace[(size_t)blockIdx.x * 24 + 1 * 8 + wave] = __builtin_amdgcn_s_memtime();
-                }
-                if (TRACE && p.trace && (p.dbg & 16) && lane == 0) {   // patch-boundary anatomy (tools/trace_boundary.py)
-                    if (kglob == 2 * NS - 2) p.trace[(size_t)blockIdx.x * 24 + 20 + wave] = __builtin_amdgcn_s_memtime();   // barrier of patch 1's last-but-one stage
-                    if (kglob == 2 * NS - 1) p.trace[(size_t)blockIdx.x * 24 + 4 + wave] = __builtin_amdgcn_s_memtime();    // ... of its last stage
-                    if (kglob == 2 * NS) p.trace[(size_t)blockIdx.x * 24 + 16 + wave] = __builtin_amdgcn_s_memtime();       // ... of patch 2's first stage
-                    if (kglob == 2 * NS + 1) p.trace[(size_t)blockIdx.x * 24 + 12 + wave] = __builtin_amdgcn_s_memtime();   // ... of its second stage
-                }
             }
             // B fragment of step t+3
             {
@@ -594,7 +460,7 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
                 else breg[u % 6] = *(const f16x8*)(nbp + bbase[0] + (u - G::T) * G::ROWB);
             }
             // A fragments: the next kernel column's, one per step; behind the barrier the next stage's column 0
-            if (dx < 2 && !WGL) {
+            if (dx < 2) {
 #pragma unroll
                 for (int k = 0; k < G::AK; ++k) {             // AK = 1 in every form but the 8x32-patch conv5 (6 fragments, 4 steps)
                     const int f = s * G::AK + k;
@@ -604,7 +470,7 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
                     }
                 }
             }
-            if (t >= G::T - 3 && !WGL) {
+            if (t >= G::T - 3) {
                 const int dy = t - (G::T - 3);
 #pragma unroll
                 for (int ct = 0; ct < CT; ++ct) acol[0][dy][ct] = *(const f16x8*)(nap + ((dy * 3) * CT + ct) * 1024);
@@ -619,7 +485,7 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
             // LDS-DMA of the stage R-1 ahead, spread over the steps in front of the barrier
 #pragma unroll
             for (int sl = 0; sl < G::PW; ++sl)
-                if ((sl * G::ISS) / G::PW == pl * G::T + t && !PROD) dma_piece(sl, dma_off);
+                if ((sl * G::ISS) / G::PW == pl * G::T + t) dma_piece(sl, dma_off);
 #pragma unroll
             for (int dy = 0; dy < 3; ++dy) {
                 const int np = s - dy;
@@ -643,17 +509,6 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
                         continue;
                     }
 #endif
-                    if (WGL) {
-                        const f16x8& af = aw[WGL ? SET : 0][WGL ? (dy * 3 + dx) * CT + ct : 0];
-                        if (FIRST && pl == 0 && dx == 0 && dy == 0) mfma_first_bias_va(acc[ct][np], af, breg[t % 6], bacc[kBiasC ? ct : 0]);
-                        else mfma_acc_va(acc[ct][np], af, breg[t % 6]);
-                        continue;
-                    }
-                    if (kAccV && np >= NPV) {                     // the 16-row form's upper rows: AGPR accumulators, AGPR bias
-                        if (FIRST && pl == 0 && dx == 0 && dy == 0) mfma_first_bias(acc[ct][np], acol[dx][dy][ct], breg[t % 6], bacc_a[kSplit ? ct : 0]);
-                        else mfma_acc(acc[ct][np], acol[dx][dy][ct], breg[t % 6]);
-                        continue;
-                    }
                     if (kAccV) {
                         if (FIRST && pl == 0 && dx == 0 && dy == 0) {
                             if (kBiasC) mfma_first_bias_v(acc[ct][np], acol[dx][dy][ct], breg[t % 6], bacc[kBiasC ? ct : 0]);
@@ -670,9 +525,6 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
             __builtin_amdgcn_sched_barrier(0);
         }
         }
-        if (TRACE && p.trace && (p.dbg & 4) && lane == 0 && kglob == 5)
-            p.trace[(size_t)blockIdx.x * 24 + 2 * 8 + wave] = __builtin_amdgcn_s_memtime();
-        if (TRACE) ++kglob;
         cur_off = next_off;
     };
 
@@ -680,7 +532,6 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
     auto epilogue = [&](int it) __attribute__((always_inline)) {
         // the MFMA results must have left the matrix pipe before the VALU reads them; hipcc does not know these
         // asm statements are MFMAs, so the wait states are spelled out (16-pass MFMA: 18 needed)
-        if (TRACE && p.trace && (p.dbg & 16) && lane == 0 && it == 1) p.trace[(size_t)blockIdx.x * 24 + 0 + wave] = __builtin_amdgcn_s_memtime();
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
         // ... and tied to the data: every accumulator passes through an empty "+a" statement BEHIND the nops, so no read of
         // it (hipcc hoisted 16-17 v_accvgpr_read above the nops before this; tools/check_asm_loads.py now counts the wait
@@ -689,7 +540,7 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int np = 0; np < NP; ++np) {
-                if (kAccV && np < NPV) asm_land_v(acc[ct][np]);
+                if (kAccV) asm_land_v(acc[ct][np]);
                 else asm_land(acc[ct][np]);
             }
         const int tile = it * nwg + slot_in_round;
@@ -699,7 +550,7 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
         const int y0 = ty * G::TH, x0 = tx * G::TW;
         const int x = x0 + pcol;
         f32x16 bv[CT];
-        if constexpr (!(kBiasC && S2SR_F16_EARLYBIAS)) {          // (bias as the MFMA's C operand: nothing in LDS, the 64x32 form has no room for it)
+        if constexpr (!(kBiasC && S2SR_F16_EARLYBIAS)) {          // (bias as the MFMA's C operand: nothing in LDS)
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -735,7 +586,7 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
         const size_t sn = (size_t)n * p.xh_img;   // image offset inside the skip-hi tensor, bytes
         if (kTrunk) {
             // the prefetched trunk lo: only the last stage's DMA instructions are younger
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::PV) : "memory");
+            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::PW) : "memory");
 #pragma unroll
             for (int np = 0; np < NP; ++np)
 #pragma unroll
@@ -826,11 +677,12 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
                     if (kTrunk) {
                         // lo = v - fp16(v), kept as e4m3(lo * 2^lo_exp): 4 significant bits of it are what the 1e-3 needs
                         // (measured: max-abs 8.8e-5 .. 1.85e-4 against 7.0e-5 .. 1.8e-4 with an fp16 lo, 2.2e-3 .. 3.4e-3 without one)
-                        // Two forms with the same bytes (test_f16_conv5_lo_encoding_forms_agree, experimental library, stress weights).
+                        // Two forms with the same bytes (S2SR_F16_LOENC; the short one ships, checked against tests/trunk_model.py's restatement
+                        // on stress operands by test_f16_conv5_lo_encoding_on_stress_operands).
                         // (r02 tried another short form -- fma(fp16(v), -2^lo_exp, v * 2^lo_exp) as one asm v_fma_mix_f32 -- that measured
                         // 1.4e-3 instead of 1.3e-4 inside this kernel although it was bit-identical in isolation; never explained, and
                         // not this form: here the fma computes v - fp16(v), exact in fp32, and the scale rides in the conversion.)
-                        if constexpr (LOE != 0) {
+                        if constexpr (S2SR_F16_LOENC != 0) {
                         // r03: 2.5 instead of 4.5 instructions per value (the conv5 epilogue was 1/3 lo encoding): v - fp16(v) in ONE
                         // v_fma_mix_f32 that reads the packed half in place (exact: the difference of a float and its own fp16 rounding),
                         // the clamp on the unscaled value, and the 2^lo_exp inside v_cvt_scalef32_pk_fp8_f32 (it divides by the power
@@ -885,72 +737,49 @@ __global__ void __launch_bounds__(PROD ? 320 : 256, 1) conv_trunk_f16(const Conv
     };
 
     using std::integral_constant;
+    constexpr integral_constant<bool, true> kFirst{};
+    constexpr integral_constant<bool, false> kNext{};
+    constexpr integral_constant<int, -1> kNoCap{};
     for (int it = 0; it < my_tiles; ++it) {
         const bool first_patch = it == 0;
-        if (TRACE && p.trace && (p.dbg & 16) && lane == 0 && it == 2) p.trace[(size_t)blockIdx.x * 24 + 8 + wave] = __builtin_amdgcn_s_memtime();   // epilogue of patch 1 left
         if (kTrunk && PL == 2) {   // two planes per stage: stages 0 and 1 are the 64 channels of x (NS >= 3, host)
-            constexpr integral_constant<int, 0> S0{};
-            stage(integral_constant<bool, true>{}, integral_constant<int, 0>{}, first_patch, S0, 0);
-            stage(integral_constant<bool, false>{}, integral_constant<int, 2>{}, false, S0, 0);
-            for (int st = 2; st < NS - 1; ++st) stage(integral_constant<bool, false>{}, integral_constant<int, -1>{}, false, S0, 0);
+            stage(kFirst, integral_constant<int, 0>{}, first_patch);
+            stage(kNext, integral_constant<int, 2>{}, false);
+            for (int st = 2; st < NS - 1; ++st) stage(kNext, kNoCap, false);
             prefetch_lo(it);
-            stage(integral_constant<bool, false>{}, integral_constant<int, -1>{}, false, S0, 0);
+            stage(kNext, kNoCap, false);
         } else if (kTrunk) {   // NS >= 4 (host): stages 0..3 are the 64 channels of x
-            constexpr integral_constant<int, 0> S0{};
-            stage(integral_constant<bool, true>{}, integral_constant<int, 0>{}, first_patch, S0, 0);
+            stage(kFirst, integral_constant<int, 0>{}, first_patch);
             if constexpr (PL == 1) {
-            stage(integral_constant<bool, false>{}, integral_constant<int, 1>{}, false, S0, 0);
-            stage(integral_constant<bool, false>{}, integral_constant<int, 2>{}, false, S0, 0);
-            stage(integral_constant<bool, false>{}, integral_constant<int, 3>{}, false, S0, 0);
+            stage(kNext, integral_constant<int, 1>{}, false);
+            stage(kNext, integral_constant<int, 2>{}, false);
+            stage(kNext, integral_constant<int, 3>{}, false);
             }
-            for (int st = 4; st < NS - 1; ++st) stage(integral_constant<bool, false>{}, integral_constant<int, -1>{}, false, S0, 0);
+            for (int st = 4; st < NS - 1; ++st) stage(kNext, kNoCap, false);
             prefetch_lo(it);                                      // NS >= 5 (host): the last stage is peeled, the loads ride on it
-            stage(integral_constant<bool, false>{}, integral_constant<int, -1>{}, false, S0, 0);
-        } else if (WGL) {
-            // the register set is the stage's parity inside the patch (NS is even: every patch starts on set 0)
-            constexpr integral_constant<int, 0> S0{};
-            constexpr integral_constant<int, 1> S1{};
-            constexpr integral_constant<int, -1> NC{};
-            stage(integral_constant<bool, true>{}, NC, first_patch, S0, 1);
-            stage(integral_constant<bool, false>{}, NC, false, S1, 2 == NS ? 0 : 2);
-            for (int st = 2; st < NS; st += 2) {
-                stage(integral_constant<bool, false>{}, NC, false, S0, st + 1);
-                stage(integral_constant<bool, false>{}, NC, false, S1, st + 2 == NS ? 0 : st + 2);
-            }
+            stage(kNext, kNoCap, false);
         } else {
-            constexpr integral_constant<int, 0> S0{};
-            stage(integral_constant<bool, true>{}, integral_constant<int, -1>{}, first_patch, S0, 0);
-            for (int st = 1; st < NS; ++st) stage(integral_constant<bool, false>{}, integral_constant<int, -1>{}, false, S0, 0);
+            stage(kFirst, kNoCap, first_patch);
+            for (int st = 1; st < NS; ++st) stage(kNext, kNoCap, false);
         }
-        if (kAnat && it == my_tiles - 1) p.trace[(size_t)blockIdx.x * 24 + 4] = __builtin_amdgcn_s_memtime();
         epilogue(it);
-        if (kAnat && it == my_tiles - 1) p.trace[(size_t)blockIdx.x * 24 + 5] = __builtin_amdgcn_s_memtime();
     }
     // nothing may still be on its way into this workgroup's LDS when it ends
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (kAnat) {
-        p.trace[(size_t)blockIdx.x * 24 + 6] = __builtin_amdgcn_s_memtime();
-        p.trace[(size_t)blockIdx.x * 24 + 7] = __builtin_amdgcn_s_memrealtime();
-    }
-    if (TRACE && p.trace && !(p.dbg & 52) && tid == 0) {
-        p.trace[(size_t)blockIdx.x * 24 + 21] = __builtin_amdgcn_s_memrealtime();
-        p.trace[(size_t)blockIdx.x * 24 + 23] = __builtin_amdgcn_s_memtime();
-    }
 }
 
-template <int CT, int NP, int R, int EPI, bool TRACE, int PROD = 0, int FULL = 0, int WGL = 0, int LOE = S2SR_F16_LOENC, int PL = 1>
+template <int CT, int NP, int R, int EPI, int FULL = 0, int PL = 1>
 hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_form* form = nullptr) {
-    using G = TG<CT, NP, R, WGL, PL>;
+    using G = TG<CT, NP, R, PL>;
     constexpr bool kNoLdsBias = (EPI == EPI_LRELU) && S2SR_F16_BIASC && S2SR_F16_EARLYBIAS;    // bias as the C operand: no LDS copy
     constexpr int LDSB = kNoLdsBias ? G::RING_BYTES : G::LDS_BYTES;
     static_assert(LDSB <= 160 * 1024, "LDS ring does not fit");
     static_assert(G::NW < 64, "vmcnt field is 6 bits");
     if (FULL == 1 && (p.mos_py != 0 || p.H % G::TH != 0 || p.W % 32 != 0)) return hipErrorInvalidValue;
-    if (WGL && (p.nstage & 1)) return hipErrorInvalidValue;       // the A-fragment register sets alternate with the stage's parity
     if (p.nstage % PL != 0) return hipErrorInvalidValue;          // whole stages of PL planes
     if (FULL == 3 && p.mos_py != 0) return hipErrorInvalidValue;
     if (FULL == 2 && (p.mos_py != 277 || p.mos_ry != 276 || p.mos_px != 277 || p.mos_rx != 276)) return hipErrorInvalidValue;
-    auto kern = conv_trunk_f16<CT, NP, R, EPI, TRACE, PROD, FULL, WGL, LOE, PL>;
+    auto kern = conv_trunk_f16<CT, NP, R, EPI, FULL, PL>;
     static std::mutex attr_mu;
     static bool attr_set[64] = {false};
     static int ncu_dev[64] = {0};
@@ -983,8 +812,8 @@ hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_
     const int ntiles = q.tilesX * q.tilesY * p.N;
     int grid = ncu & ~7;
     if (ntiles < grid) grid = (ntiles + 7) & ~7;
-    if (form) *form = s2sr_debug_trunk_form{1, CT, G::TH, R, FULL, PL, PROD, WGL, LOE, 4, 0, EPI};
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(PROD ? 320 : 256), LDSB, st, q);
+    if (form) *form = s2sr_debug_trunk_form{1, CT, G::TH, R, FULL, PL, 0, 0, S2SR_F16_LOENC, 4, 0, EPI};
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDSB, st, q);
     return hipGetLastError();
 }
 
@@ -1020,9 +849,9 @@ __device__ __forceinline__ void mfma8_first_bias(f32x16& acc, const v8i& a, cons
     asm volatile("v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %5, %3, %4 op_sel_hi:[0,0,0]" : "=&a"(acc) : "v"(a), "v"(b), "v"(sa), "v"(sb), "a"(bias));
 }
 
-template <int CT_, int NP_, int RS_, int WV_ = 4, int NPL_ = 0>
+template <int CT_, int NP_, int RS_, int NPL_ = 0>
 struct TG8 {
-    static constexpr int CT = CT_, NP = NP_, RS = RS_, WAVES = WV_;
+    static constexpr int CT = CT_, NP = NP_, RS = RS_, WAVES = 4;
     // NPL > 0: ALL of the conv's weight planes (up to NPL, 9*CT KiB each) are loaded into LDS once per workgroup and stay:
     // no weight DMA in the loop (+1 % on conv1-3, see launch_conv_trunk_f8).
     static constexpr int NPL = NPL_;
@@ -1050,19 +879,19 @@ struct TG8 {
     static_assert(3 * CT <= NP + 2, "one A fragment per step must cover a kernel column");
 };
 
-// WV = 4: one wave per SIMD (512 registers).  WV = 8 (conv1-4 form): two waves per SIMD with 256 registers each -- the fp8
-// form is bound by ONE wave's issue port (PMC: 47 % of wave cycles issuing, 35 % MFMA busy), which a second wave doubles.
-// PROD = 1 (conv1-4 form, WV = 4): a FIFTH wave issues every LDS-DMA of the workgroup and nothing else.  With the MFMAs
+// WV = 4 compute waves, one per SIMD (512 registers).
+// PROD = 1 (conv1-4 form): a FIFTH wave issues every LDS-DMA of the workgroup and nothing else.  With the MFMAs
 // compiled out (S2SR_DIAG_NOMFMA) these kernels still take 73 % of their time: they run against the memory system, whose
 // back-pressure stalls a DMA instruction at issue -- and, the wave being in-order, every MFMA behind it.  A wave that only
 // loads can sit in that stall for free; the four compute waves then only ever wait at the step barrier for data.
 // (Two waves share one SIMD: 256 registers per wave, which the conv1-4 form fits; conv5 and the fp16 kernels do not.)
-template <int CT, int NP, int RS, int EPI, int WV = 4, int NPL = 0, int PROD = 0>
-__global__ void __launch_bounds__((WV + PROD) * 64, PROD ? 1 : WV / 4) conv_trunk_f8(const ConvParams p) {
-    using G = TG8<CT, NP, RS, WV, NPL>;
+template <int CT, int NP, int RS, int EPI, int NPL = 0, int PROD = 0>
+__global__ void __launch_bounds__((4 + PROD) * 64, 1) conv_trunk_f8(const ConvParams p) {
+    using G = TG8<CT, NP, RS, NPL>;
+    constexpr int WV = G::WAVES;
     constexpr bool kTrunk = (EPI == EPI_RDB5 || EPI == EPI_RDB5_RRDB);
     static_assert((EPI == EPI_LRELU && CT == 1) || (kTrunk && CT == 2), "conv1-4: 32 couts; conv5: 64 couts");
-    static_assert(PROD == 0 || (PROD == 1 && WV == 4 && !kTrunk), "loader wave: conv1-4 form only");
+    static_assert(PROD == 0 || (PROD == 1 && !kTrunk), "loader wave: conv1-4 form only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x;
@@ -1154,12 +983,12 @@ __global__ void __launch_bounds__((WV + PROD) * 64, PROD ? 1 : WV / 4) conv_trun
         if (G::CTMAP) {
             const bool second = sl >= G::PWP;
             const int k = second ? sl - G::PWP : sl;
-            glds16<false>(second ? sB : sA, (second && ph_slab) ? 0u : loffS[k], (second ? mB : mA) + (uint32_t)k * (WV * 1024));
+            glds16(second ? sB : sA, (second && ph_slab) ? 0u : loffS[k], (second ? mB : mA) + (uint32_t)k * (WV * 1024));
         } else {
             const int i = wave + sl * WV;                                // wave-uniform
             const bool second = i >= G::PI;
             const int jj = second ? i - G::PI : i;
-            glds16<false>(second ? sB : sA, (second && ph_slab) ? 0u : loffS[sl],
+            glds16(second ? sB : sA, (second && ph_slab) ? 0u : loffS[sl],
                           (second ? mB : mA) + (uint32_t)(jj - wave) * 1024);
         }
     };
@@ -1168,10 +997,13 @@ __global__ void __launch_bounds__((WV + PROD) * 64, PROD ? 1 : WV / 4) conv_trun
         const bool over = (sl * WV + WV - 1 > 2 * G::WI - 1) && (wave + sl * WV > 2 * G::WI - 1);
         const uint32_t back = over ? (uint32_t)(wave + sl * WV - (2 * G::WI - 1)) * 1024 : 0u;
         const bool zero = ph_wts && (sl * WV >= G::WI || (sl * WV + WV - 1 >= G::WI && wave + sl * WV >= G::WI));   // piece of the phantom's zero block
-        glds16<false>(wS, zero ? (uint32_t)(G::WI * 1024) : lane16w + (uint32_t)sl * (WV * 1024) - back, mW + (uint32_t)sl * (WV * 1024) - back);
+        glds16(wS, zero ? (uint32_t)(G::WI * 1024) : lane16w + (uint32_t)sl * (WV * 1024) - back, mW + (uint32_t)sl * (WV * 1024) - back);
     };
 
-    // ---- the loader wave (PROD): the whole workgroup's DMA schedule, one barrier per pair-step like everybody else
+    // ---- the loader wave (PROD): the whole workgroup's DMA schedule, one barrier per pair-step like everybody else   [role-branch]
+    // (No hidden load may be issued in front of this branch: on the loader's side its destination is dead, and the compiler
+    // hands those registers to the DMA offsets -- r04's memory fault.  tests/test_abi_cpu.py plants such a request here in a
+    // scratch copy and expects tools/check_asm_loads.py --cfg to report it.)
     if (PROD && wave == WV) {
         uint32_t loffP[G::PI];                                   // my 16 bytes of piece jj of a plane
 #pragma unroll
@@ -1189,22 +1021,22 @@ __global__ void __launch_bounds__((WV + PROD) * 64, PROD ? 1 : WV / 4) conv_trun
             if (s1 == (uint32_t)RS) s1 = 0;
             const uint32_t tA = lds0 + slot0 * G::PLANE, tB = lds0 + s1 * G::PLANE;
 #pragma unroll
-            for (int jj = 0; jj < G::PI; ++jj) glds16<false>(sA, loffP[jj], tA + (uint32_t)jj * 1024);
+            for (int jj = 0; jj < G::PI; ++jj) glds16(sA, loffP[jj], tA + (uint32_t)jj * 1024);
 #pragma unroll
-            for (int jj = 0; jj < G::PI; ++jj) glds16<false>(sB, ph_slab ? 0u : loffP[jj], tB + (uint32_t)jj * 1024);
+            for (int jj = 0; jj < G::PI; ++jj) glds16(sB, ph_slab ? 0u : loffP[jj], tB + (uint32_t)jj * 1024);
         };
         auto issue_wts = [&](uint32_t wslot) __attribute__((always_inline)) {       // the pair under the weight cursor -> weight slot wslot
             wts_next();
             const uint32_t tW = lds0 + G::WOFF + wslot * G::WBYTES;
 #pragma unroll
             for (int i = 0; i < 2 * G::WI; ++i)
-                glds16<false>(wS, (ph_wts && i >= G::WI) ? (uint32_t)(G::WI * 1024) : (uint32_t)lane * 16 + (uint32_t)i * 1024, tW + (uint32_t)i * 1024);
+                glds16(wS, (ph_wts && i >= G::WI) ? (uint32_t)(G::WI * 1024) : (uint32_t)lane * 16 + (uint32_t)i * 1024, tW + (uint32_t)i * 1024);
         };
         issue_slabs(0);
         if (G::WRES) {
             const int npieces = p.nstage * G::WI;
             for (int i = 0; i < npieces; ++i)
-                glds16<false>((const char*)p.wpack, (uint32_t)lane * 16 + (uint32_t)i * 1024, lds0 + G::WOFF + (uint32_t)i * 1024);
+                glds16((const char*)p.wpack, (uint32_t)lane * 16 + (uint32_t)i * 1024, lds0 + G::WOFF + (uint32_t)i * 1024);
         } else {
             issue_wts(0);
             issue_wts(1);
@@ -1284,7 +1116,7 @@ __global__ void __launch_bounds__((WV + PROD) * 64, PROD ? 1 : WV / 4) conv_trun
             for (int k = 0; k * WV < npieces; ++k) {
                 int i = wave + k * WV;
                 if (i > npieces - 1) i = npieces - 1;
-                glds16<false>((const char*)p.wpack, (uint32_t)lane * 16 + (uint32_t)i * 1024, lds0 + G::WOFF + (uint32_t)i * 1024);
+                glds16((const char*)p.wpack, (uint32_t)lane * 16 + (uint32_t)i * 1024, lds0 + G::WOFF + (uint32_t)i * 1024);
             }
         } else {
             wts_next();               // weights of pair-steps 0 and 1
@@ -1605,12 +1437,12 @@ __global__ void __launch_bounds__((WV + PROD) * 64, PROD ? 1 : WV / 4) conv_trun
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-template <int CT, int NP, int RS, int EPI, int WV = 4, int NPL = 0, int PROD = 0>
+template <int CT, int NP, int RS, int EPI, int NPL = 0, int PROD = 0>
 hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_form* form = nullptr) {
-    using G = TG8<CT, NP, RS, WV, NPL>;
+    using G = TG8<CT, NP, RS, NPL>;
     static_assert(G::LDS_BYTES <= 160 * 1024, "LDS rings do not fit");
     static_assert(G::NW >= 0 && G::NW < 64, "vmcnt field is 6 bits");
-    auto kern = conv_trunk_f8<CT, NP, RS, EPI, WV, NPL, PROD>;
+    auto kern = conv_trunk_f8<CT, NP, RS, EPI, NPL, PROD>;
     if (NPL > 0 && p.nstage > NPL) return hipErrorInvalidValue;   // resident weights: the conv's planes must fit the LDS block
     static std::mutex attr_mu;
     static bool attr_set[64] = {false};
@@ -1645,8 +1477,8 @@ hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk
     const int ntiles = q.tilesX * q.tilesY * p.N;
     int grid = ncu & ~7;
     if (ntiles < grid) grid = (ntiles + 7) & ~7;
-    if (form) *form = s2sr_debug_trunk_form{2, CT, G::TH, RS, 0, 2, PROD, 0, 0, WV, NPL, EPI};
-    hipLaunchKernelGGL(kern, dim3(grid), dim3((WV + PROD) * 64), G::LDS_BYTES, st, q);
+    if (form) *form = s2sr_debug_trunk_form{2, CT, G::TH, RS, 0, 2, PROD, 0, 0, G::WAVES, NPL, EPI};
+    hipLaunchKernelGGL(kern, dim3(grid), dim3((G::WAVES + PROD) * 64), G::LDS_BYTES, st, q);
     return hipGetLastError();
 }
 
@@ -1654,95 +1486,53 @@ hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk
 
 // ct = 1: conv1..4 (EPI_LRELU); ct = 2: conv5 (EPI_RDB5 / EPI_RDB5_RRDB).  Returns hipErrorNotSupported for
 // anything else.
-hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, bool trace, int force_form, s2sr_debug_trunk_form* form) {
-#if !S2SR_EXPERIMENTAL
-    if (trace || force_form == 4 || (p.f16_form & 1)) return hipErrorNotSupported;     // stamped builds, loader-wave form: experimental library only
-#endif
+hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, int force_form, s2sr_debug_trunk_form* form) {
+    if (force_form == 4) return hipErrorNotSupported;        // the loader wave: the forms the measurements buried are refused
     if (ct == 1 && epi == EPI_LRELU) {
-        if (force_form == 1) return launch_trunk_t<1, 4, 5, EPI_LRELU, false>(p, st, form);      // per-layer parity hook: name the patch form
-        if (force_form == 2) return launch_trunk_t<1, 8, 3, EPI_LRELU, false>(p, st, form);
-#if S2SR_EXPERIMENTAL
-        if (force_form == 4) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 1>(p, st, form);
-#endif
-        if (force_form == 5) return launch_trunk_t<1, 2, 7, EPI_LRELU, false>(p, st, form);
-        if (force_form == 6) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 1>(p, st, form);    // whole-patch forms (invalid-value on ragged sizes / mosaics)
-        if (force_form == 7) return launch_trunk_t<1, 4, 5, EPI_LRELU, false, 0, 1>(p, st, form);
-        if (force_form == 8) return launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 1>(p, st, form);
-#if S2SR_EXPERIMENTAL
-        if (force_form == 11) return launch_trunk_t<1, 16, 2, EPI_LRELU, false, 0, 1>(p, st, form);   // whole 64x32 patches
-#else
-        if (force_form == 11) return hipErrorNotSupported;
-#endif
-#if S2SR_EXPERIMENTAL
-        if (force_form == 9) return launch_trunk_t<1, 8, 4, EPI_LRELU, false, 0, 1, 1>(p, st, form);   // whole 32x32 patches, weights from global memory (WGL)
-#else
-        if (force_form == 9) return hipErrorNotSupported;
-#endif
+        if (force_form == 1) return launch_trunk_t<1, 4, 5, EPI_LRELU>(p, st, form);      // per-layer parity hook: name the patch form
+        if (force_form == 2) return launch_trunk_t<1, 8, 3, EPI_LRELU>(p, st, form);
+        if (force_form == 5) return launch_trunk_t<1, 2, 7, EPI_LRELU>(p, st, form);
+        if (force_form == 6) return launch_trunk_t<1, 8, 3, EPI_LRELU, 1>(p, st, form);    // whole-patch forms (invalid-value on ragged sizes / mosaics)
+        if (force_form == 7) return launch_trunk_t<1, 4, 5, EPI_LRELU, 1>(p, st, form);
+        if (force_form == 8) return launch_trunk_t<1, 2, 7, EPI_LRELU, 1>(p, st, form);
+        if (force_form == 10) return launch_trunk_t<1, 2, 3, EPI_LRELU, 3, 2>(p, st, form);   // 8x32 patches, two planes per stage
+        if (force_form == 3 || force_form == 9 || force_form == 11) return hipErrorNotSupported;   // Winograd, weights from global, 64x32
         // 32x32 patches (8 rows per wave, 3-deep ring) unless that leaves most CUs without a patch (single tiles):
         // then 16x32 patches (4 rows per wave, 5-deep ring) spread the image over twice as many workgroups.  Both
         // forms accumulate in the same order, so the result does not depend on the choice.
         const long n32 = (long)((p.W + 31) / 32) * ((p.H + 31) / 32) * p.N;
         // ... and 8x32 patches (2 rows per wave, 7-deep ring) for a single tile: 256 patches for 256 CUs instead of 128 (one 256x256 tile
         // is launch-bound: 351 dependent launches; S2SR_SMALL8=0 keeps the 16x32 form)
-        const bool full = !trace && p.mos_py == 0 && p.H % 32 == 0 && p.W % 32 == 0 && !(p.f16_form & 4);   // whole patches only (f16_form bit 2: diagnostic off switch)
-        const bool plain = !trace && p.mos_py == 0 && !(p.f16_form & 4);                                  // ragged, but no mosaic: the extent test alone
-#if S2SR_EXPERIMENTAL
-        if (n32 < 96 && trace) return launch_trunk_t<1, 2, 7, EPI_LRELU, true>(p, st, form);               // launch anatomy of the single-tile form
-#endif
-        if (force_form == 10) return launch_trunk_t<1, 2, 3, EPI_LRELU, false, 0, 3, 0, S2SR_F16_LOENC, 2>(p, st, form);   // 8x32 patches, two planes per stage
-        if (n32 < 96 && !trace && !(p.f16_form & 2)) {
-#if S2SR_EXPERIMENTAL
-            if (full && (p.f16_form & 8)) return launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 1, 1>(p, st, form);   // r04 probe: single-tile form with the weights from global memory
-#endif
-            if (S2SR_SMALL_PL == 2 && full) return launch_trunk_t<1, 2, 3, EPI_LRELU, false, 0, 1, 0, S2SR_F16_LOENC, 2>(p, st, form);
-            if (S2SR_SMALL_PL == 2 && plain) return launch_trunk_t<1, 2, 3, EPI_LRELU, false, 0, 3, 0, S2SR_F16_LOENC, 2>(p, st, form);
-            return full ? launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 1>(p, st, form)
-                        : plain ? launch_trunk_t<1, 2, 7, EPI_LRELU, false, 0, 3>(p, st, form) : launch_trunk_t<1, 2, 7, EPI_LRELU, false>(p, st, form);
+        const bool full = p.mos_py == 0 && p.H % 32 == 0 && p.W % 32 == 0 && !(p.f16_form & 4);   // whole patches only (f16_form bit 2: diagnostic off switch)
+        const bool plain = p.mos_py == 0 && !(p.f16_form & 4);                                  // ragged, but no mosaic: the extent test alone
+        if (n32 < 96 && !(p.f16_form & 2)) {
+            if (S2SR_SMALL_PL == 2 && full) return launch_trunk_t<1, 2, 3, EPI_LRELU, 1, 2>(p, st, form);
+            if (S2SR_SMALL_PL == 2 && plain) return launch_trunk_t<1, 2, 3, EPI_LRELU, 3, 2>(p, st, form);
+            return full ? launch_trunk_t<1, 2, 7, EPI_LRELU, 1>(p, st, form)
+                        : plain ? launch_trunk_t<1, 2, 7, EPI_LRELU, 3>(p, st, form) : launch_trunk_t<1, 2, 7, EPI_LRELU>(p, st, form);
         }
-        if (n32 < 192 && !trace)
-            return full ? launch_trunk_t<1, 4, 5, EPI_LRELU, false, 0, 1>(p, st, form)
-                        : plain ? launch_trunk_t<1, 4, 5, EPI_LRELU, false, 0, 3>(p, st, form) : launch_trunk_t<1, 4, 5, EPI_LRELU, false>(p, st, form);
-#if S2SR_EXPERIMENTAL
-        if (!trace && (p.f16_form & 1)) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 1>(p, st, form);     // S2SR_F16_LOADER=1: loader-wave form
-#endif
-#if S2SR_EXPERIMENTAL
-        if (full && (p.f16_form & 8)) return launch_trunk_t<1, 8, 4, EPI_LRELU, false, 0, 1, 1>(p, st, form);   // r04 A/B: weights from global memory, 4-deep slab ring
-#endif
-#if S2SR_EXPERIMENTAL
-        if (full && (p.f16_form & 16) && p.H % 64 == 0) return launch_trunk_t<1, 16, 2, EPI_LRELU, false, 0, 1>(p, st, form);   // 64x32 patches, double-buffered ring (r04 A/B: 5 % slower)
-#endif
-        if (full) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 1>(p, st, form);
-        if (plain && !(p.f16_form & 1)) return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 3>(p, st, form);
-        if (!trace && !(p.f16_form & 4) && p.mos_py == 277 && p.mos_ry == 276 && p.mos_px == 277 && p.mos_rx == 276)
-            return launch_trunk_t<1, 8, 3, EPI_LRELU, false, 0, 2>(p, st, form);                             // mosaics of 276-pixel windows (tile 256, pad 10)
-#if S2SR_EXPERIMENTAL
-        if (trace) return launch_trunk_t<1, 8, 3, EPI_LRELU, true>(p, st, form);
-#endif
-        return launch_trunk_t<1, 8, 3, EPI_LRELU, false>(p, st, form);
+        if (n32 < 192)
+            return full ? launch_trunk_t<1, 4, 5, EPI_LRELU, 1>(p, st, form)
+                        : plain ? launch_trunk_t<1, 4, 5, EPI_LRELU, 3>(p, st, form) : launch_trunk_t<1, 4, 5, EPI_LRELU>(p, st, form);
+        if (full) return launch_trunk_t<1, 8, 3, EPI_LRELU, 1>(p, st, form);
+        if (plain) return launch_trunk_t<1, 8, 3, EPI_LRELU, 3>(p, st, form);
+        if (!(p.f16_form & 4) && p.mos_py == 277 && p.mos_ry == 276 && p.mos_px == 277 && p.mos_rx == 276)
+            return launch_trunk_t<1, 8, 3, EPI_LRELU, 2>(p, st, form);                             // mosaics of 276-pixel windows (tile 256, pad 10)
+        return launch_trunk_t<1, 8, 3, EPI_LRELU>(p, st, form);
     }
     // conv5: 16x32 patches (4 rows per wave, 4-deep ring); single tiles take 8x32 patches (2 rows per wave, 5-deep ring): one
     // 256x256 tile is 128 patches of 16x32 -- half the CUs idle through twelve MFMA-bound stages (r04 kernel trace: 24 us per
     // conv5 launch, 69 of them = 37 % of one tile's latency) -- and 256 of 8x32.  Same accumulation order, same bytes.
     // force_form 1 / 5: name the patch form (per-layer parity hook).
     if (ct == 2 && (epi == EPI_RDB5 || epi == EPI_RDB5_RRDB)) {
+        if (force_form == 2) return hipErrorNotSupported;
         const long n16 = (long)((p.W + 31) / 32) * ((p.H + 15) / 16) * p.N;
         const bool small = force_form == 5 || (force_form == 0 && n16 < 192 && !(p.f16_form & 2));
-#if S2SR_EXPERIMENTAL
-        if (force_form == 2)      // 16x32 patches with the LONG form of the lo encoding
-            return epi == EPI_RDB5 ? launch_trunk_t<2, 4, 4, EPI_RDB5, false, 0, 0, 0, 0>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5_RRDB, false, 0, 0, 0, 0>(p, st, form);
-#else
-        if (force_form == 2) return hipErrorNotSupported;
-#endif
-        if (force_form == 10 || (small && force_form == 0 && !trace && S2SR_SMALL_PL == 2))      // 8x32 patches, two planes per stage, double-buffered
-            return epi == EPI_RDB5 ? launch_trunk_t<2, 2, 2, EPI_RDB5, false, 0, 0, 0, S2SR_F16_LOENC, 2>(p, st, form)
-                                   : launch_trunk_t<2, 2, 2, EPI_RDB5_RRDB, false, 0, 0, 0, S2SR_F16_LOENC, 2>(p, st, form);
-        if (epi == EPI_RDB5) {
-#if S2SR_EXPERIMENTAL
-            if (trace) return small ? launch_trunk_t<2, 2, 5, EPI_RDB5, true>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5, true>(p, st, form);
-#endif
-            return small ? launch_trunk_t<2, 2, 5, EPI_RDB5, false>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5, false>(p, st, form);
-        }
-        return small ? launch_trunk_t<2, 2, 5, EPI_RDB5_RRDB, false>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5_RRDB, false>(p, st, form);
+        if (force_form == 10 || (small && force_form == 0 && S2SR_SMALL_PL == 2))      // 8x32 patches, two planes per stage, double-buffered
+            return epi == EPI_RDB5 ? launch_trunk_t<2, 2, 2, EPI_RDB5, 0, 2>(p, st, form)
+                                   : launch_trunk_t<2, 2, 2, EPI_RDB5_RRDB, 0, 2>(p, st, form);
+        if (epi == EPI_RDB5) return small ? launch_trunk_t<2, 2, 5, EPI_RDB5>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5>(p, st, form);
+        return small ? launch_trunk_t<2, 2, 5, EPI_RDB5_RRDB>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5_RRDB>(p, st, form);
     }
     return hipErrorNotSupported;
 }
@@ -1793,25 +1583,10 @@ void pack_conv_weights_f8(const float* w, int cin, int cout, void* dst_host, int
 
 hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_t st, s2sr_debug_trunk_form* form) {
     if (ct == 1 && epi == EPI_LRELU) {
-        // kernel forms, all bit-identical in their results (tests/test_gpu_net.py); p.f8_form comes from the environment at s2sr_create:
-        // weights (S2SR_FP8_WSTREAM): 0 (default) conv1-3 keep theirs resident in LDS (<= 4 planes incl. a phantom, next to the 6-slot
-        // slab ring), conv4 streams them (6 planes would cost two slab slots); 1 all stream; 2 all resident (conv4 on a 4-slot ring).
-        // Measured on one box, conv1-4 per 5 steps: 108.7 / 109.8 / 111.9 ms -- +1 %, nothing like the -18 % a "no weight DMA"
-        // diagnostic suggested (that one read zeros as weights, and an MFMA fed zeros draws less power: the chip clocked higher).
-        // The loader-wave form (conv_trunk_f8 PROD) is the default: 77.5 against 79.8 us per conv1-4 launch of 32 tiles on one box,
-        // A/B/A/B (+3 %; the no-MFMA floor of either form is 58 us).  S2SR_FP8_LOADER=0 selects the four-wave forms below.
-#if S2SR_EXPERIMENTAL
-        const bool w8 = (p.f8_form & 8) != 0, loader = (p.f8_form & 1) == 0;
-        const int stream_w = (p.f8_form >> 1) & 3;
-        if (w8) return launch_trunk8_t<1, 2, 6, EPI_LRELU, 8>(p, st, form);
-        if (!loader) {
-            if (stream_w == 1 || (stream_w == 0 && p.nstage > 4)) return launch_trunk8_t<1, 4, 6, EPI_LRELU>(p, st, form);
-            return p.nstage <= 4 ? launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 4>(p, st, form) : launch_trunk8_t<1, 4, 4, EPI_LRELU, 4, 6>(p, st, form);
-        }
-#else
-        if (p.f8_form != 0) return hipErrorNotSupported;      // the other conv1-4 forms: experimental library only
-#endif
-        return p.nstage <= 4 ? launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 4, 1>(p, st, form) : launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 0, 1>(p, st, form);
+        // The loader-wave form (conv_trunk_f8 PROD): conv1-3 keep their weights resident in LDS (<= 4 planes incl. a phantom, next
+        // to the 6-slot slab ring), conv4 streams them (6 planes would cost two slab slots).  The other forms the measurements buried
+        // (DESIGN section 9): four waves without the loader (-3 %), all weights streamed or all resident (+-1 %), two waves per SIMD.
+        return p.nstage <= 4 ? launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 1>(p, st, form) : launch_trunk8_t<1, 4, 6, EPI_LRELU, 0, 1>(p, st, form);
     }
     if (ct == 2 && epi == EPI_RDB5) return launch_trunk8_t<2, 4, 4, EPI_RDB5>(p, st, form);
     if (ct == 2 && epi == EPI_RDB5_RRDB) return launch_trunk8_t<2, 4, 4, EPI_RDB5_RRDB>(p, st, form);

@@ -40,7 +40,6 @@ struct ConvW {
     bool f8trunk = false;
     int32_t* d_wscale = nullptr;
     bool pooled = false;                // d_wpack / d_wscale point into the handle's pools
-    bool wino = false;                  // fp16 RDB conv1-4 packed for the row-Winograd form (conv_wino.hip: 12 U fragments per stage)
 };
 
 // kernel families for the HIP-event statistics
@@ -157,24 +156,16 @@ struct s2sr_handle {
     float* d_calib = nullptr;     // fp8 calibration: [0] max |x| of the trunk, [1] max |x_k| of the growth planes (device)
     bool fp8_hp_tail = false;     // S2SR_PREC_FP8: the six head / tail convs in plain fp16 (their ~2e-3 is below the trunk's e4m3
                                   // error) unless S2SR_FP8_TAIL=hp asks for the split-operand forms
-    int fp8_form = 0;             // ConvParams::f8_form (S2SR_FP8_LOADER / S2SR_FP8_WSTREAM / S2SR_FP8_W8)
     int lo_exp = 12;              // fp16 modes, one-wave-per-SIMD trunk: the trunk's lo half as e4m3(lo * 2^lo_exp): exact to 4 bits for
                                   // |x| < 2^(20 - lo_exp) = 256, clamped beyond (S2SR_LO_EXP)
     int fp8_x_exp = 3, fp8_g_exp = 5;   // S2SR_PREC_FP8 activation scales 2^e of the x / growth planes (S2SR_FP8_XEXP, S2SR_FP8_GEXP); calibrated
                                         // on the synthetic set: profiles/r02_fp8_scale_sweep.txt (|x| up to 56, |x_k| up to 14 before clipping)
     int fp8_x_exp0 = 3, fp8_g_exp0 = 5; // ... as s2sr_create left them: every weight load starts from these again (a calibration belongs to the weights it saw)
-    int trunk_wino = 0;           // fp16 modes: RDB conv1-4 in the row-Winograd F(2,3) form (conv_wino.hip); S2SR_WINO=1: all four, 2: conv2-4 only (Cin >= 96)
-    bool trunk_w4 = true;         // RRDB trunk convs on the one-wave-per-SIMD kernel (conv_trunk.hip); S2SR_TRUNK=0: the 8-wave kernel
     bool graphs_on = true;        // S2SR_GRAPH=0 turns it off
     int64_t ws_allocs = 0;        // workspace (re)allocations since s2sr_create (s2sr_debug_get_config reserved[5])
-    bool tail_w4 = false;         // S2SR_TAIL_W4=1: split-operand tail convs (up1, up2, hr, last) as 4 waves x twice the rows (one wave per SIMD)
     bool last_fold = true;        // S2SR_LAST_FOLD=0: conv_last (hp) reads all four e4m3 planes (8 stages) instead of folding w_lo into idle couts
     bool f16_full = true;         // S2SR_F16_FULL=0: fp16 conv1-4 never take the whole-patch form (no px_live arithmetic in the epilogue) on 32-multiple launches
     bool small8 = true;           // S2SR_SMALL8=0: single tiles keep the 16x32-patch form of fp16 conv1-4 (default: 8x32 patches, 256 per 256x256 tile)
-    bool f16_loader = false;      // S2SR_F16_LOADER=1: fp16 conv1-4 (32x32-patch form) with a fifth, load-only wave (conv_trunk_f16 PROD)
-    bool no_subpixel = false;     // experimental build, S2SR_NO_SUBPIXEL: up-convs in the upsample-on-load 3x3 form instead of the sub-pixel form
-    bool f16_p64 = false;         // S2SR_F16_P64=1 (r04 A/B): fp16 conv1-4 of whole-patch launches on 64x32 patches with a double-buffered ring
-    bool f16_wgl = false;         // S2SR_F16_WGL=1 (r04 A/B): fp16 conv1-4 of whole-patch launches fetch their weights from global memory into AGPRs (conv_trunk_f16 WGL)
     bool mosaic_on = true;        // S2SR_MOSAIC=0: windows that are no multiple of the 32-pixel patch travel one per image (ConvParams::mos_*)
     // paste maps of the window plan last stitched through s2sr_stitch_rows_u8_dev (row map, column map), kept on the device:
     // an AOI is stitched band by band, the maps are uploaded once per (H, W, tile, pad)
@@ -496,7 +487,7 @@ int run_conv(s2sr_handle* h, hipStream_t st, int fam, const ConvW& cw, ConvParam
     p.seg_len = cw.seg_len;
     p.seg_lo_mask = cw.seg_lo_mask;
     p.fold_lo = cw.fold ? 1 : 0;
-    p.tail_form = (h->tail_w4 ? 1 : 0) | (h->f16_full ? 0 : 8);
+    p.tail_form = h->f16_full ? 0 : 8;
     // conv_hr: a folded conv_last (the last conv) reads x_lo planes only, so the e4m3(x_hi) planes need not be written
     if (fam == F_HR && lo_out && !h->convs.empty() && h->convs.back().f8 && h->convs.back().fold) p.tail_form |= 2;
     p.trash = h->d_trash;
@@ -509,23 +500,17 @@ int run_conv(s2sr_handle* h, hipStream_t st, int fam, const ConvW& cw, ConvParam
     // two x_lo planes only) and write (4 planes; 2 when the consumer is a folded conv_last)
     if (cw.f8) bytes += px * (up ? 0.25 : 1.0) * (cw.fold ? 64.0 : 128.0);
     if (lo_out) bytes += px * ((p.tail_form & 2) ? 64.0 : 128.0);
-    const bool lo8 = h->trunk_w4;                          // one-wave-per-SIMD trunk: lo as e4m3 planes (1 B per channel), else fp16
-    if (epi == EPI_RDB5) bytes += px * 64 * (lo8 ? 2.0 : 4.0);          // lo: read + write
-    if (epi == EPI_RDB5_RRDB) bytes += px * 64 * (p.xh_skip ? (lo8 ? 5.0 : 8.0) : 12.0);    // lo r/w + RRDB skip: (fp16 hi, lo) pair read (trunk kernel) or fp32 R r/w
+    // the trunk's lo half travels as e4m3 planes (1 B per channel)
+    if (epi == EPI_RDB5) bytes += px * 64 * 2.0;                        // lo: read + write
+    if (epi == EPI_RDB5_RRDB) bytes += px * 64 * (p.xh_skip ? 5.0 : 12.0);    // lo r/w + RRDB skip: (fp16 hi, e4m3 lo) pair read, or fp32 R r/w
     if (epi == EPI_FIRST) bytes += px * 64 * 10.0;        // lo + R + F
     if (epi == EPI_BODY) bytes += px * 64 * 4.0;
     Scope sc(h, st, fam, flops, bytes);
     if (form) *form = s2sr_debug_trunk_form{};
-    if (cw.wino) {
-        HIPCHK(h, launch_conv_trunk_wino(p, st));
-        if (form) { form->kernel = 3; form->epi = epi; }
+    if ((fam == F_RDB14 || fam == F_RDB5) && !up && !lo_out && !cw.f8) {   // the RRDB trunk: conv_trunk.hip
+        p.f16_form = (h->small8 ? 0 : 2) | (h->f16_full ? 0 : 4);
+        HIPCHK(h, launch_conv_trunk(p, cw.ct, epi, st, 0, form));
         return S2SR_OK;
-    }
-    if (h->trunk_w4 && (fam == F_RDB14 || fam == F_RDB5) && !up && !lo_out && !cw.f8) {
-        p.f16_form = (h->f16_loader ? 1 : 0) | (h->small8 ? 0 : 2) | (h->f16_full ? 0 : 4) | (h->f16_wgl ? 8 : 0) | (h->f16_p64 ? 16 : 0);
-        const hipError_t e = launch_conv_trunk(p, cw.ct, epi, st, false, 0, form);
-        if (e == hipSuccess) return S2SR_OK;
-        if (e != hipErrorNotSupported) HIPCHK(h, e);
     }
     HIPCHK(h, launch_conv(p, cw.ct, epi, up, lo_out, st, cw.f8));
     return S2SR_OK;
@@ -538,7 +523,7 @@ int run_up_subpixel(s2sr_handle* h, hipStream_t st, const ConvW& cw, ConvParams 
                     int oHp, int oWp) {
     p.N = n; p.H = Hs; p.W = Ws; p.sHp = sHp; p.sWp = sWp; p.Hp = oHp; p.Wp = oWp;
     p.bias = cw.d_bias; p.nstage = cw.f8 ? 8 : 4; p.seg_len = 4; p.seg_lo_mask = cw.f8 ? 0x2 : 0x0; p.fold_lo = 0;
-    p.tail_form = (h->tail_w4 ? 1 : 0) | (h->f16_full ? 0 : 8);
+    p.tail_form = h->f16_full ? 0 : 8;
     p.trash = h->d_trash;
     const double px = (double)n * Hs * Ws;
     for (int k = 0; k < 2; ++k) {
@@ -645,7 +630,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
                     p.src = w.D8[cur]; p.src_img = 6 * w.blk1;
                     p.wpack = cw.d_wpack; p.bias = cw.d_bias; p.wscale = cw.d_wscale;
                     p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.trash = h->d_trash;
-                    p.x_exp = xe; p.g_exp = ge; p.xh_img = 4 * w.blk1; p.f8_form = h->fp8_form;
+                    p.x_exp = xe; p.g_exp = ge; p.xh_img = 4 * w.blk1;
                     int epi = EPI_LRELU;
                     double bytes = px * (32.0 * cw.seg_len);                     // algorithmic: every input byte once
                     if (k < 5) {
@@ -671,7 +656,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
             }
         if (h->ttap && (rc = trunk_tap(h, st, 3 * nb))) return rc;
         trunk_hi = w.Xh[0]; trunk_hi_img = 4 * w.blk1; trunk_lo = w.Tz;
-    } else if (h->trunk_w4) {
+    } else {
         // one-wave-per-SIMD trunk kernel: rdb r of every RRDB reads D[r] / Tr[r] and writes the next trunk (x, lo) into
         // D[(r+1)%3] / Tr[(r+1)%3]; rdb3's conv5 takes the RRDB skip from (D[0] x blocks, Tr[0]) -- still the RRDB's
         // input -- and overwrites exactly those pixels (same lane reads, then writes; nobody else touches D[0] then)
@@ -706,22 +691,6 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
             }
         if (h->ttap && (rc = trunk_tap(h, st, 3 * nb))) return rc;
         trunk_hi = w.D[0]; trunk_hi_img = 12 * w.blk1; trunk_lo = w.Tr[0]; trunk_lo_exp = h->lo_exp;
-    } else {
-        for (int blk = 0; blk < nb; ++blk)
-            for (int r = 0; r < 3; ++r) {
-                for (int k = 1; k <= 4; ++k) {
-                    ConvParams p = b;
-                    p.src = w.D[cur]; p.src_img = 12 * w.blk1;
-                    p.dst = w.D[cur] + (size_t)(4 + 2 * (k - 1)) * w.blk1; p.dst_img = 12 * w.blk1;
-                    if ((rc = run_conv(h, st, F_RDB14, h->convs[ci++], p, EPI_LRELU, false))) return rc;
-                }
-                ConvParams p = b;
-                p.src = w.D[cur]; p.src_img = 12 * w.blk1;
-                p.dst = w.D[cur ^ 1]; p.dst_img = 12 * w.blk1;
-                if ((rc = run_conv(h, st, F_RDB5, h->convs[ci++], p, r == 2 ? EPI_RDB5_RRDB : EPI_RDB5, false))) return rc;
-                cur ^= 1;
-            }
-        trunk_hi = w.D[cur]; trunk_hi_img = 12 * w.blk1; trunk_lo = w.T;
     }
     h->trunk_rec = {trunk_hi, trunk_hi_img, trunk_lo, (uint64_t)(trunk_lo_exp >= 0 ? 2 : 4) * w.blk1, trunk_lo_exp};
     const bool hp = w.hp;   // split-operand head/tail: inputs as (hi, lo) pairs, outputs write both halves
@@ -740,20 +709,16 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         p.N = n; p.H = 2 * H; p.W = 2 * W; p.Hp = w.Hp2; p.Wp = w.Wp2; p.sHp = w.Hp; p.sWp = w.Wp;
         p.src = w.U0; p.src_img = 4 * w.blk1; p.dst = w.U1; p.dst_img = 4 * w.blk2;
         if (hp) { p.src_lo = w.U0lo; p.lo_img = 4 * w.blk1; p.T = w.U1lo; }
-        mosaic_at(p, h->convs[ci].d_wphase[0] ? 1 : 2);          // sub-pixel form: the epilogue walks SOURCE pixels
-        if (h->convs[ci].d_wphase[0]) {
-            if ((rc = run_up_subpixel(h, st, h->convs[ci++], p, n, H, W, w.Hp, w.Wp, w.Hp2, w.Wp2))) return rc;
-        } else if ((rc = run_conv(h, st, F_UP, h->convs[ci++], p, EPI_LRELU, true, hp))) return rc;
+        mosaic_at(p, 1);                                         // sub-pixel form: the epilogue walks SOURCE pixels
+        if ((rc = run_up_subpixel(h, st, h->convs[ci++], p, n, H, W, w.Hp, w.Wp, w.Hp2, w.Wp2))) return rc;
     }
     {   // conv_up2 on nearest-2x
         ConvParams p{};
         p.N = n; p.H = 4 * H; p.W = 4 * W; p.Hp = w.Hp4; p.Wp = w.Wp4; p.sHp = w.Hp2; p.sWp = w.Wp2;
         p.src = w.U1; p.src_img = 4 * w.blk2; p.dst = w.U2; p.dst_img = 4 * w.blk4;
         if (hp) { p.src_lo = w.U1lo; p.lo_img = 4 * w.blk2; p.T = w.U2lo; }
-        mosaic_at(p, h->convs[ci].d_wphase[0] ? 2 : 4);
-        if (h->convs[ci].d_wphase[0]) {
-            if ((rc = run_up_subpixel(h, st, h->convs[ci++], p, n, 2 * H, 2 * W, w.Hp2, w.Wp2, w.Hp4, w.Wp4))) return rc;
-        } else if ((rc = run_conv(h, st, F_UP, h->convs[ci++], p, EPI_LRELU, true, hp))) return rc;
+        mosaic_at(p, 2);
+        if ((rc = run_up_subpixel(h, st, h->convs[ci++], p, n, 2 * H, 2 * W, w.Hp2, w.Wp2, w.Hp4, w.Wp4))) return rc;
     }
     ConvParams hr{};
     hr.N = n; hr.H = 4 * H; hr.W = 4 * W; hr.Hp = w.Hp4; hr.Wp = w.Wp4; hr.sHp = w.Hp4; hr.sWp = w.Wp4;
@@ -961,17 +926,6 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
     return S2SR_OK;
 }
 
-#if !S2SR_EXPERIMENTAL
-}  // namespace
-// the experimental kernel families are not in this library (s2sr_internal.h): their entry points answer "not supported"
-namespace s2sr {
-hipError_t launch_conv_trunk_wino(const ConvParams&, hipStream_t) { return hipErrorNotSupported; }
-size_t conv_wpack_bytes_wino(int cin, int cout) { return conv_wpack_bytes(cin, cout); }
-hipError_t launch_pack_trunk_wino(const float*, int, int, void*, hipStream_t) { return hipErrorNotSupported; }
-hipError_t launch_conv_trace(const ConvParams&, int, hipStream_t) { return hipErrorNotSupported; }
-}  // namespace s2sr
-namespace {
-#endif
 }  // namespace
 
 // ==========================================================================================
@@ -980,11 +934,7 @@ namespace {
 extern "C" {
 
 const char* s2sr_version(void) {
-#if S2SR_EXPERIMENTAL
-    return "s2sr 0.4 (gfx950, fp16-MFMA implicit-GEMM conv) +experimental";
-#else
     return "s2sr 0.4 (gfx950, fp16-MFMA implicit-GEMM conv)";
-#endif
 }
 
 int s2sr_device_count(void) {
@@ -1038,19 +988,6 @@ int s2sr_create(const s2sr_config* cfg, s2sr_handle** out) {
     if (const char* g = getenv("S2SR_LAST_FOLD")) h->last_fold = atoi(g) != 0;
     if (const char* g = getenv("S2SR_D2H_STAGED")) h->d2h_staged_on = atoi(g) != 0;
     if (const char* g = getenv("S2SR_FP8_TAIL")) h->fp8_hp_tail = strcmp(g, "hp") == 0;
-#if S2SR_EXPERIMENTAL
-    if (const char* g = getenv("S2SR_F16_WGL")) h->f16_wgl = atoi(g) != 0;
-    if (const char* g = getenv("S2SR_F16_P64")) h->f16_p64 = atoi(g) != 0;
-    // kernel forms the measurements buried: only in the experimental build (s2sr_internal.h)
-    if (const char* g = getenv("S2SR_TRUNK")) h->trunk_w4 = atoi(g) != 0;
-    if (const char* g = getenv("S2SR_F16_LOADER")) h->f16_loader = atoi(g) != 0;
-    if (const char* g = getenv("S2SR_TAIL_W4")) h->tail_w4 = atoi(g) != 0;
-    if (const char* g = getenv("S2SR_FP8_LOADER")) h->fp8_form |= atoi(g) != 0 ? 0 : 1;
-    if (const char* g = getenv("S2SR_FP8_WSTREAM")) h->fp8_form |= (atoi(g) & 3) << 1;
-    if (const char* g = getenv("S2SR_FP8_W8")) h->fp8_form |= atoi(g) != 0 ? 8 : 0;
-    if (const char* g = getenv("S2SR_WINO")) h->trunk_wino = atoi(g) == 2 ? 2 : (atoi(g) != 0 ? 1 : 0);
-    h->no_subpixel = getenv("S2SR_NO_SUBPIXEL") != nullptr;
-#endif
     if (const char* g = getenv("S2SR_LO_EXP")) {
         const int v = atoi(g);
         if (v >= 6 && v <= 18) h->lo_exp = v;
@@ -1128,9 +1065,7 @@ static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_flo
         const bool trunk = i >= 1 && i + 5 < nconv;
         if (trunk) {
             poff[i] = pool_bytes;
-            const bool wino = !fp8 && h->trunk_wino && h->trunk_w4 && specs[i].cout == 32 && (h->trunk_wino == 1 || specs[i].cin >= 96);
-            pool_bytes += align256(fp8 ? conv_wpack_bytes_f8(specs[i].cin, specs[i].cout)
-                                       : wino ? conv_wpack_bytes_wino(specs[i].cin, specs[i].cout) : conv_wpack_bytes(specs[i].cin, specs[i].cout));
+            pool_bytes += align256(fp8 ? conv_wpack_bytes_f8(specs[i].cin, specs[i].cout) : conv_wpack_bytes(specs[i].cin, specs[i].cout));
         }
     }
     HIPCHK(h, dev_malloc(&h->pool_w, pool_bytes ? pool_bytes : 256));
@@ -1182,9 +1117,6 @@ static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_flo
                 cw.seg_lo_mask = 0;
                 cw.d_wscale = h->pool_s + idx * 64;
                 HIPCHK(h, launch_pack_trunk_f8(d_blob + woff[idx], s.cin, s.cout, cw.d_wpack, cw.d_wscale, st));
-            } else if (h->trunk_wino && h->trunk_w4 && s.cout == 32 && (h->trunk_wino == 1 || s.cin >= 96)) {
-                cw.wino = true;
-                HIPCHK(h, launch_pack_trunk_wino(d_blob + woff[idx], s.cin, s.cout, cw.d_wpack, st));
             } else {
                 HIPCHK(h, launch_pack_trunk_f16(d_blob + woff[idx], s.cin, s.cout, cw.d_wpack, st));
             }
@@ -1198,7 +1130,7 @@ static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_flo
             tmp.resize(wb);
             if (f8) pack_conv_weights_f8hp(pw, s.cin, s.cout, tmp.data(), last_fold);
             else pack_conv_weights(pw, s.cin, s.cout, nseg, tmp.data(), fold);
-            if (s.cin == 64 && s.cout == 64 && (idx + 4 == nconv || idx + 3 == nconv) && !h->no_subpixel) {   // conv_up1, conv_up2
+            if (s.cin == 64 && s.cout == 64 && (idx + 4 == nconv || idx + 3 == nconv)) {   // conv_up1, conv_up2: sub-pixel form
                 const size_t pb = conv_wpack_bytes_phase(s.cin, s.cout);
                 std::vector<char> ph(pb);
                 for (int k = 0; k < 2; ++k) {
@@ -2555,10 +2487,10 @@ int s2sr_debug_get_config(s2sr_handle* h, s2sr_debug_config* out) {
     if (!h || !out) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     memset(out, 0, sizeof *out);
-    out->precision = h->cfg.precision; out->group = h->cfg.group; out->trunk_w4 = h->trunk_w4 ? 1 : 0; out->lo_exp = h->lo_exp;
-    out->fp8_form = h->fp8_form; out->fp8_x_exp = h->fp8_x_exp; out->fp8_g_exp = h->fp8_g_exp; out->fp8_hp_tail = h->fp8_hp_tail ? 1 : 0;
-    out->graphs_on = h->graphs_on ? 1 : 0; out->trunk_wino = h->trunk_wino; out->reserved[0] = h->mosaic_on ? 1 : 0; out->reserved[1] = h->f16_loader ? 1 : 0; out->reserved[2] = h->last_fold ? 1 : 0; out->reserved[3] = h->tail_w4 ? 1 : 0; out->reserved[4] = h->f16_full ? 1 : 0; out->reserved[5] = (int32_t)h->ws_allocs;
-    out->trunk_wino |= h->f16_wgl ? 0x100 : 0;      // (bit 8 of trunk_wino: the WGL A/B switch took)
+    // trunk_w4 always 1; trunk_wino, fp8_form, reserved[1] and reserved[3] always 0 (the forms they named were removed)
+    out->precision = h->cfg.precision; out->group = h->cfg.group; out->trunk_w4 = 1; out->lo_exp = h->lo_exp;
+    out->fp8_x_exp = h->fp8_x_exp; out->fp8_g_exp = h->fp8_g_exp; out->fp8_hp_tail = h->fp8_hp_tail ? 1 : 0;
+    out->graphs_on = h->graphs_on ? 1 : 0; out->reserved[0] = h->mosaic_on ? 1 : 0; out->reserved[2] = h->last_fold ? 1 : 0; out->reserved[4] = h->f16_full ? 1 : 0; out->reserved[5] = (int32_t)h->ws_allocs;
     return S2SR_OK;
 }
 
@@ -2583,15 +2515,13 @@ int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
     const size_t wn = (size_t)Cout * Cin * 9;
     HIPCHK(h, dev_malloc(&d_w32.p, wn * 4));
     HIPCHK(h, hipMemcpyAsync(d_w32.p, a->weight, wn * 4, hipMemcpyHostToDevice, st));
-    const bool wino = kind == 0 && a->form == 3;
-    HIPCHK(h, dev_malloc(&d_wp.p, f8 ? conv_wpack_bytes_f8(Cin, Cout) : wino ? conv_wpack_bytes_wino(Cin, Cout) : conv_wpack_bytes(Cin, Cout)));
+    HIPCHK(h, dev_malloc(&d_wp.p, f8 ? conv_wpack_bytes_f8(Cin, Cout) : conv_wpack_bytes(Cin, Cout)));
     HIPCHK(h, dev_malloc(&d_b.p, 64 * 4));
     HIPCHK(h, dev_malloc(&d_ws.p, 64 * 4));
     float bb[64] = {0};
     memcpy(bb, a->bias, Cout * sizeof(float));
     HIPCHK(h, hipMemcpyAsync(d_b.p, bb, sizeof bb, hipMemcpyHostToDevice, st));
     if (f8) HIPCHK(h, launch_pack_trunk_f8((const float*)d_w32.p, Cin, Cout, d_wp.p, (int32_t*)d_ws.p, st));
-    else if (wino) HIPCHK(h, launch_pack_trunk_wino((const float*)d_w32.p, Cin, Cout, d_wp.p, st));
     else HIPCHK(h, launch_pack_trunk_f16((const float*)d_w32.p, Cin, Cout, d_wp.p, st));
     // ---- activations: the dense tensor D (12 fp16 blocks per image, or 6 e4m3 planes), packed on the host
     const int xe = h->fp8_x_exp, ge = h->fp8_g_exp, le = h->lo_exp;
@@ -2659,13 +2589,11 @@ int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
                 p.xh_skip = (const char*)d_Sk.p; p.xh_img = 4 * blk; p.lo_skip = (const char*)d_SkLo.p;
             }
         }
-        hipError_t e;
-        if (wino) e = launch_conv_trunk_wino(p, st);
-        else e = launch_conv_trunk(p, Cout / 32, epi, st, false, a->form);
+        const hipError_t e = launch_conv_trunk(p, Cout / 32, epi, st, a->form);
         if (e != hipSuccess) return fail(h, S2SR_E_HIP, std::string("launch_conv_trunk: ") + hipGetErrorString(e));
     } else {
         p.seg_len = Cin / 32; p.nstage = (p.seg_len + 1) & ~1; p.wscale = (const int32_t*)d_ws.p;
-        p.x_exp = xe; p.g_exp = ge; p.f8_form = kind == 3 ? a->form : 0; p.xh_img = 4 * blk;
+        p.x_exp = xe; p.g_exp = ge; p.xh_img = 4 * blk;
         if (!c5) {
             p.dst = (char*)d_D.p + (size_t)(Cin / 32) * blk; p.dst_img = dimg;
         } else {
@@ -2694,7 +2622,8 @@ int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
                 p.xh_skip = (const char*)d_Sk.p;
             }
         }
-        const hipError_t e = launch_conv_trunk_f8(p, Cout / 32, epi, st);
+        // conv1-4: the loader-wave form is the only one (the others the measurements buried are refused)
+        const hipError_t e = (kind == 3 && a->form != 0) ? hipErrorNotSupported : launch_conv_trunk_f8(p, Cout / 32, epi, st);
         if (e != hipSuccess) return fail(h, S2SR_E_HIP, std::string("launch_conv_trunk_f8: ") + hipGetErrorString(e));
     }
     HIPCHK(h, hipStreamSynchronize(st));
@@ -2752,23 +2681,20 @@ int s2sr_debug_bench_conv(s2sr_handle* h, int32_t N, int32_t H, int32_t W, int32
     if (!h || !avg_us || N <= 0 || H <= 0 || W <= 0 || iters <= 0 || cin < 16 || cin > 192 || cin % 16 ||
         (cout != 32 && cout != 64))
         return S2SR_E_INVALID;
+    if (trace && trace_wgs > 0) return fail(h, S2SR_E_INVALID, "stamped kernel builds are not part of this library");
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
     const int Hp = padded(H), Wp = padded(W);
     const size_t blk = (size_t)Hp * Wp * 32;
-    char *D0 = nullptr, *D1 = nullptr, *d_w = nullptr;
-    char* T = nullptr;
-    float *Rr = nullptr, *d_b = nullptr;
-    unsigned long long* d_tr = nullptr;
-    const bool wino = h->trunk_wino && h->trunk_w4 && cout == 32;
-    const size_t wb = wino ? conv_wpack_bytes_wino(cin, cout) : conv_wpack_bytes(cin, cout), db = (size_t)N * 12 * blk;
-    HIPCHK(h, dev_malloc(&D0, db));
-    HIPCHK(h, dev_malloc(&D1, db));
-    HIPCHK(h, dev_malloc(&T, (size_t)N * 4 * blk));
-    HIPCHK(h, dev_malloc(&Rr, (size_t)N * 8 * blk));
-    HIPCHK(h, dev_malloc(&d_w, wb));
-    HIPCHK(h, dev_malloc(&d_b, 256));
+    const size_t wb = conv_wpack_bytes(cin, cout), db = (size_t)N * 12 * blk;
+    DevBuf D0, D1, T, Rr, d_w, d_b;
+    HIPCHK(h, dev_malloc(&D0.p, db));
+    HIPCHK(h, dev_malloc(&D1.p, db));
+    HIPCHK(h, dev_malloc(&T.p, (size_t)N * 4 * blk));
+    HIPCHK(h, dev_malloc(&Rr.p, (size_t)N * 8 * blk));
+    HIPCHK(h, dev_malloc(&d_w.p, wb));
+    HIPCHK(h, dev_malloc(&d_b.p, 256));
     // pseudo-random fp16 bit patterns (finite, |v| < 2)
     std::vector<unsigned char> pat(db > wb ? db : wb);
     unsigned s = 12345u;
@@ -2777,68 +2703,34 @@ int s2sr_debug_bench_conv(s2sr_handle* h, int32_t N, int32_t H, int32_t W, int32
         pat[i] = (unsigned char)(s >> 24);
         pat[i + 1] = (unsigned char)(((s >> 16) & 0x80) | 0x30 | ((s >> 8) & 0x0b));
     }
-    HIPCHK(h, hipMemcpy(D0, pat.data(), db, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemcpy(d_w, pat.data(), wb, hipMemcpyHostToDevice));
-    HIPCHK(h, hipMemset(D1, 0, db));
-    HIPCHK(h, hipMemset(T, 0, (size_t)N * 4 * blk));
-    HIPCHK(h, hipMemset(Rr, 0, (size_t)N * 8 * blk));
-    HIPCHK(h, hipMemset(d_b, 0, 256));
+    HIPCHK(h, copy_blocking(h, D0.p, pat.data(), db, hipMemcpyHostToDevice));
+    HIPCHK(h, copy_blocking(h, d_w.p, pat.data(), wb, hipMemcpyHostToDevice));
+    HIPCHK(h, fill_blocking(h, D1.p, 0, db));
+    HIPCHK(h, fill_blocking(h, T.p, 0, (size_t)N * 4 * blk));
+    HIPCHK(h, fill_blocking(h, Rr.p, 0, (size_t)N * 8 * blk));
+    HIPCHK(h, fill_blocking(h, d_b.p, 0, 256));
     ConvParams p{};
-    p.src = D0; p.src_img = 12 * blk; p.nstage = cin / 16;
-    p.wpack = d_w; p.bias = d_b; p.N = N; p.H = H; p.W = W; p.Hp = Hp; p.Wp = Wp; p.sHp = Hp; p.sWp = Wp;
-    p.T = T; p.R = Rr; p.F = Rr; p.trash = h->d_trash;
-    p.xh_in = T; p.lo_exp = h->lo_exp;   // conv_trunk_f16: trunk lo coming in (here read and written in place: timing only)
-#if S2SR_EXPERIMENTAL
-    p.dbg = getenv("S2SR_DBG") ? atoi(getenv("S2SR_DBG")) : 0;
-#else
-    if (trace && trace_wgs > 0) return fail(h, S2SR_E_INVALID, "stamped kernel builds are in the experimental library only (make EXP=1, S2SR_LIB=.../libs2sr_exp.so)");
-#endif
-    int epi;
-    if (cout == 32) { p.dst = D1; p.dst_img = 12 * blk; epi = EPI_LRELU; }
-    else { p.dst = D1; p.dst_img = 12 * blk; epi = EPI_RDB5; }
-    const int ct = cout / 32;
+    p.src = (const char*)D0.p; p.src_img = 12 * blk; p.nstage = cin / 16;
+    p.wpack = d_w.p; p.bias = (const float*)d_b.p; p.N = N; p.H = H; p.W = W; p.Hp = Hp; p.Wp = Wp; p.sHp = Hp; p.sWp = Wp;
+    p.T = (char*)T.p; p.R = (float*)Rr.p; p.F = (float*)Rr.p; p.trash = h->d_trash;
+    p.xh_in = (const char*)T.p; p.lo_exp = h->lo_exp;   // conv_trunk_f16: trunk lo coming in (here read and written in place: timing only)
+    p.dst = (char*)D1.p; p.dst_img = 12 * blk;
+    p.f16_form = (h->small8 ? 0 : 2) | (h->f16_full ? 0 : 4);
+    const int epi = cout == 32 ? EPI_LRELU : EPI_RDB5, ct = cout / 32;
     hipEvent_t e0, e1;
     HIPCHK(h, hipEventCreate(&e0));
-    HIPCHK(h, hipEventCreate(&e1));
-#if S2SR_EXPERIMENTAL
-    const bool timed_trace = trace && trace_wgs > 0 && getenv("S2SR_TRACE_TIMED");   // time the TRACE build (ablations)
-#else
-    const bool timed_trace = false;
-#endif
-    if (timed_trace) {
-        HIPCHK(h, dev_malloc(&d_tr, (size_t)256 * 24 * 8));
-        p.trace = d_tr;
-    }
-    auto launch_one = [&](bool tr) -> hipError_t {
-        if (wino) return launch_conv_trunk_wino(p, st);           // stamps whenever p.trace is set
-        p.f16_form = (h->f16_loader ? 1 : 0) | (h->small8 ? 0 : 2) | (h->f16_full ? 0 : 4);
-        if (h->trunk_w4) {
-            const hipError_t e = launch_conv_trunk(p, ct, epi, st, tr);
-            if (e != hipErrorNotSupported) return e;
-        }
-        return tr ? launch_conv_trace(p, ct, st) : launch_conv(p, ct, epi, false, false, st);
-    };
-    for (int i = 0; i < 3; ++i) HIPCHK(h, launch_one(false));
-    HIPCHK(h, hipEventRecord(e0, st));
-    for (int i = 0; i < iters; ++i) HIPCHK(h, launch_one(timed_trace));
-    HIPCHK(h, hipEventRecord(e1, st));
-    HIPCHK(h, hipStreamSynchronize(st));
+    if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); return fail(h, S2SR_E_HIP, "hipEventCreate failed"); }
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = launch_conv_trunk(p, ct, epi, st);
+    if (e == hipSuccess) e = hipEventRecord(e0, st);
+    for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_conv_trunk(p, ct, epi, st);
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
     float ms = 0;
-    HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.0f / iters;
-    if (trace && trace_wgs > 0) {
-        const int nwg = 256;
-        if (!d_tr) HIPCHK(h, dev_malloc(&d_tr, (size_t)nwg * 24 * 8));
-        HIPCHK(h, hipMemset(d_tr, 0, (size_t)nwg * 24 * 8));
-        p.trace = d_tr;
-        HIPCHK(h, launch_one(true));
-        HIPCHK(h, hipStreamSynchronize(st));
-        const int nw = trace_wgs < nwg ? trace_wgs : nwg;
-        HIPCHK(h, hipMemcpy(trace, d_tr, (size_t)nw * 24 * 8, hipMemcpyDeviceToHost));
-        dev_free(d_tr);
-    }
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
     hipEventDestroy(e0); hipEventDestroy(e1);
-    dev_free(D0); dev_free(D1); dev_free(T); dev_free(Rr); dev_free(d_w); dev_free(d_b);
+    HIPCHK(h, e);
+    *avg_us = ms * 1000.0f / iters;
     return S2SR_OK;
 }
 
@@ -2913,7 +2805,7 @@ int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x
     const bool mos = tp.plan.on();
     t->mos_kx = mos ? tp.skx : 0; t->mos_ky = mos ? tp.sky : 0; t->mos_wh = mos ? th : 0; t->mos_ww = mos ? tw : 0;
     t->mos_count = mos ? B : 0;
-    t->trunk_lo_exp = fp8 ? -1 : (h->trunk_w4 ? h->lo_exp : -1);
+    t->trunk_lo_exp = fp8 ? -1 : h->lo_exp;
     t->avail = 0;
     for (int k = 0; k < S2SR_TAP_COUNT; ++k)
         if (hp || (k != S2SR_TAP_T8 && k < S2SR_TAP_U0LO)) t->avail |= 1 << k;
@@ -2971,7 +2863,6 @@ int s2sr_debug_trunk_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, 
     if (t->first < 0 || t->count < 1 || t->first + t->count > 3 * h->cfg.num_block)
         return fail(h, S2SR_E_INVALID, "RDB range outside [0, 3 * num_block)");
     const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;
-    if (!fp8 && !h->trunk_w4) return fail(h, S2SR_E_INVALID, "trunk taps: the 8-wave trunk (S2SR_TRUNK=0) is not tapped");
     if (h->d_calib) return fail(h, S2SR_E_INVALID, "trunk taps: the handle is calibrating");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     TapPlan tp;

@@ -10,14 +10,9 @@
 
 #include "../../include/s2sr.h"
 
-// Kernel families and forms that the measurements buried (profiles/r0x_*) are compiled only with -DS2SR_EXPERIMENTAL=1
-// (`make EXP=1` -> csrc/libs2sr_exp.so, selected with S2SR_LIB=...): the row-Winograd trunk form (conv_wino.hip, +-0..+1.5 % in
-// the net), the fp16 loader-wave form (+-0), the one-wave-per-SIMD tail convs (10-15 % slower), the 8-wave RDB path (r01's
-// kernel), the non-default fp8 conv1-4 forms, the upsample-on-load up-convs, and every stamped (TRACE) build.  The default
-// library answers requests for them with hipErrorNotSupported and ignores their environment switches.
-#ifndef S2SR_EXPERIMENTAL
-#define S2SR_EXPERIMENTAL 0
-#endif
+// The library carries only the kernel forms that run.  The ones the measurements buried (the row-Winograd trunk form, the fp16
+// loader-wave form, the one-wave-per-SIMD tail convs, the 8-wave RDB path, the non-default fp8 conv1-4 forms, the upsample-on-load
+// up-convs, every stamped build) are recorded in DESIGN.md section 9 and profiles/; their code is in git history.
 
 namespace s2sr {
 
@@ -117,11 +112,10 @@ struct ConvParams {
     uint64_t xh_img;         // bytes between images of the three
     const int32_t* wscale;   // [64] E8M0 bytes 127 - k_co of the per-output-channel weight scales 2^k_co
     int32_t x_exp, g_exp;    // activation scales: x planes hold e4m3(x * 2^x_exp), growth planes e4m3(x_k * 2^g_exp)
-    int32_t f8_form;         // conv_trunk_f8 conv1-4 kernel form (diagnostics): bit 0 no loader wave, bits 1-2 weight placement (0 default, 1 all
-                             // streamed, 2 all resident), bit 3 two waves per SIMD -- from S2SR_FP8_LOADER / _WSTREAM / _W8 at s2sr_create
-    int32_t f16_form;        // conv_trunk_f16 conv1-4 kernel form: bit 0 = 32x32 patches with the load-only fifth wave (S2SR_F16_LOADER), bit 1 = single
-                             // tiles keep the 16x32-patch form instead of 8x32 (S2SR_SMALL8=0)
-    int32_t tail_form;       // split-operand head/tail convs (conv3x3.hip F8 schedule): bit 0 = one wave per SIMD (4 waves, twice the rows per wave; S2SR_TAIL_W4), bit 1 = this conv's consumer reads no e4m3(x_hi) planes (conv_hr before a folded conv_last): do not write them, bit 3 = never the whole-patch (FULL) forms (S2SR_F16_FULL=0)
+    int32_t f8_form;         // unused (kept so that every kernel argument stays at its offset)
+    int32_t f16_form;        // conv_trunk_f16 conv1-4 kernel form: bit 1 = single tiles keep the 16x32-patch form instead of 8x32 (S2SR_SMALL8=0),
+                             // bit 2 = never the whole-patch (FULL) forms (S2SR_F16_FULL=0); bits 0, 3, 4 unused
+    int32_t tail_form;       // split-operand head/tail convs (conv3x3.hip F8 schedule): bit 1 = this conv's consumer reads no e4m3(x_hi) planes (conv_hr before a folded conv_last): do not write them, bit 3 = never the whole-patch (FULL) forms (S2SR_F16_FULL=0); bit 0 unused
     int32_t lo_exp;          // conv_trunk_f16 conv5: the trunk's lo half is stored as e4m3(lo * 2^lo_exp) planes (xh_in, T, lo_skip)
     // Window mosaics (the AOI path, engine.hip forward_dev): equal-size windows of `_tile_process` (cnn_super_resolution.py:249-257) laid
     // out on a grid inside ONE image with a single zero row / column between neighbours -- the conv zero padding of both, at
@@ -133,9 +127,8 @@ struct ConvParams {
     int32_t mos_kx, mos_ky, mos_count;   // EPI_LAST: grid of a mosaic and the number of windows in this launch: window t = (n * ky + wy) * kx + wx
                                          // is written as image t of [count, ry, rx]; slots past the count are not written
     char* trash;             // >= 4 KiB scratch: out-of-image lanes park their (unconditional) stores here
-    unsigned long long* trace;   // diagnostic build only: s_memtime stamps, 24 per workgroup
-    int32_t dbg;                 // diagnostic only (timing ablations, results wrong): 1 weights DMA from one fixed piece,
-                                 // 2 slab DMA from one fixed piece, 4 per-wave stamps, 8 no DMA instructions in the loop
+    unsigned long long* trace;   // unused (kept so that every kernel argument stays at its offset)
+    int32_t dbg;                 // unused (ditto)
 };
 
 // is output pixel (y, x) of this launch one the reference writes (inside the image, and not a mosaic separator)?
@@ -175,19 +168,13 @@ __device__ __forceinline__ bool px_live(const ConvParams& p, const PatchLive& L,
 
 // conv kernel (conv3x3.hip).  ct = ceil(Cout/32) in {1,2}.
 hipError_t launch_conv(const ConvParams& p, int ct, int epi, bool upsample, bool lo_out, hipStream_t st, bool f8_in = false);
-hipError_t launch_conv_trace(const ConvParams& p, int ct, hipStream_t st);   // stamped diagnostic build
 // the RRDB trunk convs as one-wave-per-SIMD workgroups (conv_trunk.hip): ct 1 + EPI_LRELU (conv1..4), ct 2 + EPI_RDB5 /
 // EPI_RDB5_RRDB (conv5).  hipErrorNotSupported = not a trunk form / launch too small: use launch_conv.
-// force_form (conv1-4 only; the per-layer parity hook): 0 = by launch size, 1 = 16x32 patches / 5-deep ring, 2 = 32x32 patches / 3-deep ring,
-// 4 = loader wave, 5 = 8x32 patches, 6 / 7 / 8 = the whole-patch (FULL) forms of 2 / 1 / 5
+// force_form (the per-layer parity hook): 0 = by launch size; conv1-4: 1 = 16x32 patches / 5-deep ring, 2 = 32x32 patches / 3-deep ring,
+// 5 = 8x32 patches, 6 / 7 / 8 = the whole-patch (FULL) forms of 2 / 1 / 5, 10 = 8x32 patches with two planes per stage; conv5: 1, 5, 10.
+// The removed forms 3, 4, 9, 11 (and conv5's 2) answer hipErrorNotSupported.
 // form (optional): the instantiation the launch took (s2sr_debug_trunk_taps' form record), written when the launch was issued
-hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, bool trace = false, int force_form = 0,
-                             s2sr_debug_trunk_form* form = nullptr);
-// fp16 RDB conv1..4 in the row-Winograd F(2,3) form (conv_wino.hip): weights transformed over dy (4 x 3 fragments per 16-channel
-// stage instead of 3 x 3), inputs transformed over 4 consecutive slab rows in registers, 12 MFMAs per 2 output rows instead of 18
-hipError_t launch_conv_trunk_wino(const ConvParams& p, hipStream_t st);
-size_t conv_wpack_bytes_wino(int cin, int cout);
-hipError_t launch_pack_trunk_wino(const float* d_w, int cin, int cout, void* d_out, hipStream_t st);
+hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, int force_form = 0, s2sr_debug_trunk_form* form = nullptr);
 // the same convs on e4m3 operands, block-scaled fp8 MFMA (K = 64 = two planes per instruction)
 hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_t st, s2sr_debug_trunk_form* form = nullptr);
 // per-plane weight stages for conv_trunk_f8: [plane][tap][ct][16-B half][cout row 0..31][16 channel bytes] e4m3 of

@@ -143,25 +143,25 @@ def test_hidden_asm_loads_are_not_touched_before_their_wait(tmp_path):
     if not Path(hipcc).exists():
         pytest.skip("no hipcc")
     csrc = REPO / "sentinel2-super-resolution-poc_amd" / "csrc"
-    for src in ("conv_trunk.hip", "conv3x3.hip"):        # the shipped kernels (conv_wino.hip is in the experimental library only: tools/check_exp.sh)
+    for src in ("conv_trunk.hip", "conv3x3.hip"):
         asm = tmp_path / (src + ".s")
         subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-S",
                         "--cuda-device-only", str(csrc / src), "-o", str(asm)], check=True, stderr=subprocess.DEVNULL)
         # --cfg: + the control-flow rule (every path from a hidden load to its first vmcnt wait; test below)
         r = subprocess.run([sys.executable, str(REPO / "tools" / "check_asm_loads.py"), "--cfg", str(asm)], capture_output=True, text=True)
         assert r.returncode == 0 and "0 hazard(s)" in r.stdout, r.stdout[-2000:]
-        if src == "conv_trunk.hip":      # the check has something to check (conv3x3.hip's hidden loads sat in the RDB epilogues: experimental library now)
+        if src == "conv_trunk.hip":      # the check has something to check (conv3x3.hip has no hidden loads left)
             assert asm.read_text().count("global_load_dwordx2 a[") + asm.read_text().count("global_load_dwordx4 a[") > 0
 
 
-def test_hidden_asm_loads_on_side_paths_r04_fault_is_caught(tmp_path):
-    """The guard for r04's GPU fault (profiles/r04_latency_anatomy.txt section 3: inline-asm bias requests issued in front of the
+def test_hidden_asm_load_before_fp8_loader_branch_is_caught(tmp_path):
+    """The guard for r04's GPU fault (profiles/r04_latency_anatomy.txt section 3: inline-asm bias requests issued in front of a
     loader wave's role branch; on the loader's side their destination registers were dead, the compiler handed them to DMA
     offsets, the landing loads overwrote those -- an aborted GPU test).  tools/check_asm_loads.py --cfg follows every path of the
     control-flow graph from each hidden load to the first vmcnt wait on that path and reports any touch of the destination on the
-    way; no counting, hence no false positives from infeasible paths.  Shown here to (a) pass on the experimental build of
-    conv_trunk.hip at HEAD (the loader-wave form exists only there) and (b) FIRE on r04's placement, rebuilt in a scratch copy by
-    moving the marked request block back in front of the role branch."""
+    way; no counting, hence no false positives from infeasible paths.  Shown here to (a) pass on conv_trunk.hip as it is and (b)
+    FIRE on r04's placement, rebuilt in a scratch copy in the shipped loader-wave form (conv_trunk_f8's conv1-4 kernels): a hidden
+    request planted in front of the marked role branch and consumed on the compute side behind a vmcnt wait."""
     import os
     import shutil
     import subprocess
@@ -176,17 +176,20 @@ def test_hidden_asm_loads_on_side_paths_r04_fault_is_caught(tmp_path):
     shutil.copy(REPO / "include" / "s2sr.h", tmp_path / "include" / "s2sr.h")
     shutil.copy(csrc / "s2sr_internal.h", work / "s2sr_internal.h")
     src = (csrc / "conv_trunk.hip").read_text()
-    b0, b1 = "    // [hidden-bias-requests begin]", "    // [hidden-bias-requests end]\n"
-    role = "    // ---- the loader wave (PROD): the whole workgroup's DMA schedule                          [role-branch]"
-    assert src.count(b0) == 1 and src.count(b1) == 1 and src.count(role) == 1 and src.index(role) < src.index(b0)
-    block = src[src.index(b0):src.index(b1) + len(b1)]
-    rest = src.replace(block, "")
-    old = rest[:rest.index(role)] + block + rest[rest.index(role):]
+    role = "    // ---- the loader wave (PROD): the whole workgroup's DMA schedule, one barrier per pair-step like everybody else   [role-branch]"
+    compute = "    // ---- fragment addresses: per-lane base + immediate.  b0 / b1 = logical 16-B halves 0 / 1 of pixel (row, pcol + dx)"
+    assert src.count(role) == 1 and src.count(compute) == 1 and src.index(role) < src.index(compute)
+    request = ("    // [hidden-request begin]\n"
+               "    const f32x4 probe = asm_load16v((const char*)(p.bias + (tid & 31)));\n"
+               "    // [hidden-request end]\n")
+    land = ("    asm volatile(\"s_waitcnt vmcnt(0)\" ::: \"memory\");\n"
+            "    asm volatile(\"\" ::\"v\"(probe));\n")
+    old = src.replace(role, request + role).replace(compute, land + compute)
 
     def hazards(text, name):
         (work / "conv_trunk.hip").write_text(text)
         asm = tmp_path / (name + ".s")
-        subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-DS2SR_EXPERIMENTAL=1", "-S",
+        subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-S",
                         "--cuda-device-only", str(work / "conv_trunk.hip"), "-o", str(asm)], check=True, stderr=subprocess.DEVNULL)
         r = subprocess.run([sys.executable, str(REPO / "tools" / "check_asm_loads.py"), "--cfg", str(asm)], capture_output=True, text=True)
         return r.returncode, r.stdout
@@ -194,10 +197,11 @@ def test_hidden_asm_loads_on_side_paths_r04_fault_is_caught(tmp_path):
     rc, out = hazards(src, "head")
     assert rc == 0 and "0 hazard(s)" in out, out[-2000:]
     rc, out = hazards(old, "r04_placement")
+    print(out[-3000:])
     assert rc == 1 and "with no vmcnt wait in between" in out, out[-2000:]
-    # ... in the loader-wave form (template argument PROD = 1: conv_trunk_f16<1, 8, 3, 0, false, 1, ...>), nowhere else
+    # ... in the loader-wave form (conv_trunk_f8<1, 4, 6, EPI_LRELU, NPL, PROD = 1>), nowhere else
     lines = [l for l in out.splitlines() if "touches" in l]
-    assert lines and all("conv_trunk_f16ILi1ELi8ELi3ELi0ELb0ELi1E" in l for l in lines), out[-2000:]
+    assert lines and all(re.search(r"conv_trunk_f8ILi1ELi4ELi6ELi0ELi[04]ELi1EE", l) for l in lines), out[-2000:]
 
 
 def test_enhance_chunk_plan_properties():

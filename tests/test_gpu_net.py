@@ -477,13 +477,12 @@ def _fresh(monkeypatch, nb, precision, env, **kw):
     return e
 
 
-def test_trunk_lo_as_e4m3_scale_choices(monkeypatch, golden_dir):
+def test_trunk_lo_e4m3_scale_choices_and_ignored_switches(monkeypatch, golden_dir):
     """The trunk's lo half travels as e4m3(lo * 2^lo_exp) planes (conv_trunk_f16 conv5; S2SR_LO_EXP, default 12).  e4m3's own
     exponent covers the range, so the choice of scale only moves where very small / very large |x| lose bits: the HP
     test bound (3e-4) holds for 2^9 .. 2^14; 2^16 clamps lo wherever |x| >= 16 and measures 3.4e-4 (inside the north star's
-    1e-3, outside this file's bound -- r02 claimed it inside from a test that compared one cached handle with itself);
-    the 8-wave path (fp16 lo, S2SR_TRUNK=0) stays the tighter reference.  Fresh handles per setting; the five
-    configurations must actually differ."""
+    1e-3, outside this file's bound -- r02 claimed it inside from a test that compared one cached handle with itself).
+    Fresh handles per setting; the four configurations must actually differ."""
     g = np.load(golden_dir / "g4_full_nets.npz")
     HP = native.PREC_F16_HP
     outs = {}
@@ -493,21 +492,14 @@ def test_trunk_lo_as_e4m3_scale_choices(monkeypatch, golden_dir):
         assert cfg["lo_exp"] == lo_exp and cfg["trunk_w4"] == 1, cfg
         outs[lo_exp] = e.forward_f32(g["x"])
         e.close()
-    if native.experimental():       # the 8-wave path (r01's kernel) is in the experimental library only
-        e = _fresh(monkeypatch, 23, HP, {"S2SR_TRUNK": "0"})
-        assert e.debug_config()["trunk_w4"] == 0
-        outs["w8"] = e.forward_f32(g["x"])
-        e.close()
-    else:                            # the shipped library ignores the switch
-        e = _fresh(monkeypatch, 23, HP, {"S2SR_TRUNK": "0", "S2SR_WINO": "1", "S2SR_TAIL_W4": "1", "S2SR_F16_LOADER": "1"})
-        cfg = e.debug_config()
-        assert cfg["trunk_w4"] == 1 and cfg["trunk_wino"] == 0 and cfg["tail_w4"] == 0 and cfg["f16_loader"] == 0, cfg
-        e.close()
+    # the switches of the removed forms are not read
+    e = _fresh(monkeypatch, 23, HP, {"S2SR_TRUNK": "0", "S2SR_WINO": "1", "S2SR_TAIL_W4": "1", "S2SR_F16_LOADER": "1"})
+    cfg = e.debug_config()
+    assert cfg["trunk_w4"] == 1 and cfg["trunk_wino"] == 0 and cfg["tail_w4"] == 0 and cfg["f16_loader"] == 0, cfg
+    e.close()
     errs = {k: float(np.abs(v - g["y_b23"]).max()) for k, v in outs.items()}
-    print("trunk lo as e4m3 * 2^k / fp16 lo on the 8-wave path: max-abs err " + ", ".join(f"{k}: {v:.3e}" for k, v in errs.items()))
+    print("trunk lo as e4m3 * 2^k: max-abs err " + ", ".join(f"{k}: {v:.3e}" for k, v in errs.items()))
     assert all(v <= TOL_HP for k, v in errs.items() if k != 16) and errs[16] <= 1e-3, errs
-    if "w8" in errs:
-        assert errs["w8"] <= 1.5 * errs[12]
     # different arithmetic must give different bytes (r02's version of this test compared one cached handle with itself)
     keys = list(outs)
     for i in range(len(keys)):
@@ -516,40 +508,6 @@ def test_trunk_lo_as_e4m3_scale_choices(monkeypatch, golden_dir):
     # the default handle is lo_exp 12 on the one-wave-per-SIMD kernels
     monkeypatch.delenv("S2SR_TRUNK", raising=False)
     assert np.array_equal(engine(23, HP).forward_f32(g["x"]), outs[12])
-
-
-@pytest.mark.experimental
-def test_row_winograd_trunk_goldens(monkeypatch, golden_dir):
-    """S2SR_WINO=1: RDB conv1-4 in the row-Winograd F(2,3) form (conv_wino.hip).  Its transformed operands are rounded to
-    fp16 once more than the direct form's; the HP bound must hold all the same (CPU emulation: tools/emulate_r03.py), on the
-    goldens incl. the stress weights, on a full tile against the oracle, and a tile must give the same bytes alone (16x32
-    patch form) and inside a batch (32x32 form)."""
-    g3 = np.load(golden_dir / "g3_small_nets.npz")
-    g4 = np.load(golden_dir / "g4_full_nets.npz")
-    HP = native.PREC_F16_HP
-    for nb, g, key, kw in ((2, g3, "y_b2", {}), (6, g4, "y_b6", {}), (23, g4, "y_b23", {}), (23, g4, "y_b23_gain1", {"body_gain": 1.0})):
-        e = _fresh(monkeypatch, nb, HP, {"S2SR_WINO": "1"}, **kw)
-        assert e.debug_config()["trunk_wino"] == 1
-        err = float(np.abs(e.forward_f32(g["x"]) - g[key]).max())
-        e0 = _fresh(monkeypatch, nb, HP, {}, **kw)           # the direct form, on a handle created WITHOUT the switch
-        d = float(np.abs(e.forward_f32(g["x"]) - e0.forward_f32(g["x"])).max())
-        e0.close()
-        e.close()
-        print(f"row-Winograd trunk, {nb} blocks {kw}: max-abs err {err:.3e} (vs the direct form's output: {d:.3e})")
-        assert err <= TOL_HP and d > 0, (nb, err)
-    from s2sr.synth import synthetic_tiles
-    tiles = synthetic_tiles(8, 256, seed=21)
-    e = _fresh(monkeypatch, 23, HP, {"S2SR_WINO": "1"})
-    y = e.forward_batch_u8(tiles)                       # 512 patches of 32x32: the 32x32 form
-    assert np.array_equal(e.forward_batch_u8(tiles[3:4])[0], y[3])   # 64 patches: the 16x32 form
-    torch.set_num_threads(min(32, torch.get_num_threads() or 8))
-    q_ref, f_ref = ref.enhance(tiles[0], ref.to_torch_sd(synthetic_state_dict(23, seed=0)), 23, return_float=True)
-    f = e.enhance_f32(tiles[0])
-    err = float(np.abs(f - f_ref).max())
-    dq = np.abs(y[0].astype(np.int16) - q_ref.astype(np.int16))
-    print(f"row-Winograd trunk, 256x256 tile vs the oracle: float max-abs {err:.3e}, u8 identical {np.mean(dq == 0):.4f}")
-    assert err <= TOL_HP and dq.max() <= 1 and np.mean(dq == 0) > 0.99
-    e.close()
 
 
 @pytest.mark.parametrize("prec", [native.PREC_F16_HP, native.PREC_F16, native.PREC_FP8])
@@ -606,24 +564,6 @@ def test_conv_last_folded_and_eight_stage_forms(monkeypatch, golden_dir):
     print(f"u8 outputs, folded vs 8-stage: {int((d != 0).sum())} of {d.size} differ, max {int(d.max())}")
     assert d.max() <= 1 and (d != 0).mean() < 1e-3
 
-
-@pytest.mark.experimental
-def test_tail_convs_one_wave_per_simd_form_gives_the_same_bytes(monkeypatch, golden_dir):
-    """S2SR_TAIL_W4 picks the 4-wave instantiations of the split-operand tail convs (conv_up1 / conv_up2 sub-pixel forms, conv_hr,
-    conv_last; conv3x3.hip F8 schedule with WAVES = 4 and twice the rows per wave).  Same patch, same ring, same accumulation
-    order per pixel: the float outputs are bit-identical to the 8-wave forms on ragged windows and on the goldens."""
-    g4 = np.load(golden_dir / "g4_full_nets.npz")
-    rng = np.random.default_rng(78)
-    xs = [rng.random((2, 3, 37, 53), dtype=np.float32), rng.random((1, 3, 64, 96), dtype=np.float32), g4["x"]]
-    outs = {}
-    for w4 in ("0", "1"):
-        e = _fresh(monkeypatch, 6, native.PREC_F16_HP, {"S2SR_TAIL_W4": w4})
-        assert e.debug_config()["tail_w4"] == int(w4)
-        outs[w4] = [e.forward_f32(x) for x in xs]
-        e.close()
-    for a, b in zip(outs["0"], outs["1"]):
-        assert np.array_equal(a, b), float(np.abs(a - b).max())
-    assert float(np.abs(outs["1"][2] - g4["y_b6"]).max()) <= TOL_HP
 
 
 def test_staged_device_to_host_bands_give_the_same_image(monkeypatch):
@@ -713,49 +653,6 @@ def test_whole_patch_conv_forms_change_no_byte(monkeypatch):
             e.close()
         for a, b in zip(outs["1"], outs["0"]):
             assert np.array_equal(a, b)
-
-
-@pytest.mark.experimental
-def test_eight_wave_rdb_path_goldens(monkeypatch, golden_dir):
-    """S2SR_TRUNK=0 keeps the RDB convs on the 8-wave kernel (conv3x3.hip EPI_RDB5 / EPI_RDB5_RRDB epilogues, fp16 lo,
-    3-buffer workspace): the g3 / g4 / g5 goldens in HP and fast mode through a handle created with the switch set."""
-    g3 = np.load(golden_dir / "g3_small_nets.npz")
-    g4 = np.load(golden_dir / "g4_full_nets.npz")
-    for prec, tol in ((native.PREC_F16_HP, TOL_HP), (native.PREC_F16, TOL_F16)):
-        for nb, g, key in ((2, g3, "y_b2"), (6, g4, "y_b6"), (23, g4, "y_b23")):
-            e = _fresh(monkeypatch, nb, prec, {"S2SR_TRUNK": "0"})
-            assert e.debug_config()["trunk_w4"] == 0
-            err = float(np.abs(e.forward_f32(g["x"]) - g[key]).max())
-            e.close()
-            print(f"8-wave RDB path, precision {prec}, {nb} blocks: max-abs err {err:.3e}")
-            assert err <= tol, (prec, nb, err)
-
-
-@pytest.mark.experimental
-def test_subpixel_and_upsample_on_load_forms_agree(monkeypatch):
-    """The up-convs run in sub-pixel form (2x2 taps on the source image); S2SR_NO_SUBPIXEL=1 keeps the
-    3x3-on-upsampled loader form.  Both must match the oracle, and each other to fp32-rounding level."""
-    nb = 2
-    sd = synthetic_state_dict(nb, seed=4)
-    tsd = ref.to_torch_sd(sd)
-    img = np.random.default_rng(77).integers(0, 256, size=(37, 53, 3), dtype=np.uint8)
-    _, f_ref = ref.enhance(img, tsd, nb, return_float=True)
-    for prec, tol in ((native.PREC_F16_HP, TOL_HP), (native.PREC_F16, TOL_F16)):
-        outs = []
-        for flag in ("0", "1"):
-            if flag == "1":
-                monkeypatch.setenv("S2SR_NO_SUBPIXEL", "1")
-            else:
-                monkeypatch.delenv("S2SR_NO_SUBPIXEL", raising=False)
-            e = native.Engine(num_block=nb, precision=prec)
-            e.load_state_dict(sd)
-            outs.append(e.enhance_f32(img))
-            e.close()
-            assert np.abs(outs[-1] - f_ref).max() <= tol, (prec, flag)
-        d = np.abs(outs[0] - outs[1]).max()
-        print(f"precision {prec}: sub-pixel vs upsample-on-load max diff {d:.2e}")
-        assert d <= (5e-5 if prec == native.PREC_F16_HP else 2e-3)
-    monkeypatch.delenv("S2SR_NO_SUBPIXEL", raising=False)
 
 
 def _oracle_enhance_memo(img, sd, nb, tile, pad):
@@ -939,27 +836,6 @@ def test_fp8_mode_full_tile_and_batch_properties():
         img = np.random.default_rng(H).integers(0, 256, size=(H, W, 3), dtype=np.uint8)
         a, b = e.enhance_f32(img), hp.enhance_f32(img)
         assert a.shape == (4 * H, 4 * W, 3) and np.isfinite(a).all() and np.abs(a - b).max() <= TOL_FP8_23, (H, W)
-
-
-@pytest.mark.parametrize("env,form", [({"S2SR_FP8_LOADER": "0"}, 1), ({"S2SR_FP8_LOADER": "0", "S2SR_FP8_WSTREAM": "1"}, 3),
-                                      ({"S2SR_FP8_LOADER": "0", "S2SR_FP8_WSTREAM": "2"}, 5), ({"S2SR_FP8_W8": "1"}, 8)])
-@pytest.mark.experimental
-def test_fp8_conv14_kernel_forms_agree_bit_for_bit(monkeypatch, env, form):
-    """The fp8 conv1-4 kernel comes in several forms (a fifth load-only wave or not, weights streamed or resident in LDS,
-    one or two waves per SIMD).  They accumulate the same products in the same order, so whichever form the environment
-    selects must give the same bytes as the default -- through a FRESH handle whose config shows the form was taken
-    (per layer: tests/test_gpu_trunk.py::test_f8_conv14_forms_agree_bit_for_bit)."""
-    from s2sr.synth import synthetic_tiles
-    tiles = synthetic_tiles(3, 96, seed=5)
-    e0 = _fresh(monkeypatch, 6, native.PREC_FP8, {})
-    assert e0.debug_config()["fp8_form"] == 0
-    y0 = e0.forward_batch_u8(tiles)
-    e0.close()
-    e1 = _fresh(monkeypatch, 6, native.PREC_FP8, env)
-    assert e1.debug_config()["fp8_form"] == form, e1.debug_config()
-    y1 = e1.forward_batch_u8(tiles)
-    e1.close()
-    assert np.array_equal(y0, y1), env
 
 
 def test_fp8_calibration_sets_scales_from_data(golden_dir):

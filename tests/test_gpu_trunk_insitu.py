@@ -336,32 +336,6 @@ def test_trunk_fp8_calibrated(monkeypatch):
     _run(monkeypatch, FP8, {}, "ragged_2x37x53", calibrate=True)
 
 
-# ---- experimental forms --------------------------------------------------------------------------------------------------
-@pytest.mark.experimental
-def test_trunk_taps_refuse_the_8_wave_trunk(monkeypatch):
-    e, _ = _engine(monkeypatch, HP, {"S2SR_TRUNK": "0"}, 1, 0.3)
-    try:
-        args, _ = _inputs("tiny_1x16x32")
-        with pytest.raises(native.S2srError):
-            e.debug_trunk_taps(0, 3, **args)
-    finally:
-        e.close()
-
-
-@pytest.mark.experimental
-@pytest.mark.parametrize("env", [{"S2SR_WINO": "1"}, {"S2SR_F16_LOADER": "1"}], ids=["wino", "f16_loader"])
-def test_trunk_hp_experimental_forms(monkeypatch, env):
-    _run(monkeypatch, HP, env, "r32_2x300x330", first=2, count=1, wino="S2SR_WINO" in env)
-
-
-@pytest.mark.experimental
-@pytest.mark.parametrize("env", [{"S2SR_FP8_LOADER": "0"}, {"S2SR_FP8_LOADER": "0", "S2SR_FP8_WSTREAM": "1"},
-                                 {"S2SR_FP8_LOADER": "0", "S2SR_FP8_WSTREAM": "2"}, {"S2SR_FP8_W8": "1"}],
-                         ids=["fourwave", "wstream", "wresident", "w8"])
-def test_trunk_fp8_experimental_forms(monkeypatch, env):
-    _run(monkeypatch, FP8, env, "ragged_2x37x53")
-
-
 def test_trunk_forms_cover_the_dispatcher():
     """run last in this module: the union of the recorded forms holds every instantiation the shipped dispatcher picks"""
     if not _SEEN_FORMS:

@@ -9,7 +9,7 @@ set -e
 C=sentinel2-super-resolution-poc_amd/csrc
 make -C $C > /dev/null
 mkdir -p $C/diag
-FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-result -Wno-unused-value -ffp-contract=off -DS2SR_EXPERIMENTAL=0"
+FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -Wno-unused-result -Wno-unused-value -ffp-contract=off"
 OBJS="engine.o conv_trunk.o pack.o postprocess.o hostcodec.o tiles.o"
 build() {  # name, define
   /opt/rocm/bin/hipcc $FLAGS $2 -c $C/conv3x3.hip -o $C/diag/conv3x3_$1.o

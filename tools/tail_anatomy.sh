@@ -4,9 +4,7 @@
 #   -DS2SR_DIAG_F8=1 no LDS-DMA, =2 no MFMA (fragment reads kept), =4 no epilogue, =8 epilogue without its stores.
 # Results of those builds are garbage; only time counts.  profiles/r03_tail_anatomy.txt holds the r03 table.
 D=sentinel2-super-resolution-poc_amd/csrc
-for w4 in 0 1; do
-  for lib in libs2sr.so diag/libs2sr_f8diag1.so diag/libs2sr_f8diag2.so diag/libs2sr_f8diag4.so diag/libs2sr_f8diag8.so; do
-    echo "=== $lib  S2SR_TAIL_W4=$w4"
-    S2SR_LIB=$PWD/$D/$lib S2SR_TAIL_W4=$w4 python tools/quick_bench.py --batch 256 --hp 1 --steps 2 | grep -E "SR-MP|conv_last|conv_hr|conv_up|conv_body"
-  done
+for lib in libs2sr.so diag/libs2sr_f8diag1.so diag/libs2sr_f8diag2.so diag/libs2sr_f8diag4.so diag/libs2sr_f8diag8.so; do
+  echo "=== $lib"
+  S2SR_LIB=$PWD/$D/$lib python tools/quick_bench.py --batch 256 --hp 1 --steps 2 | grep -E "SR-MP|conv_last|conv_hr|conv_up|conv_body"
 done
