@@ -1,5 +1,5 @@
 /*
- * s2sr.h -- C ABI of libs2sr.so, the MI355X (gfx950) Real-ESRGAN x4 inference path.
+ * s2sr.h -- C ABI of libs2sr.so, the MI355X (gfx950) Real-ESRGAN x4 (and x2plus) inference path.
  *
  * The reference (fieldin/sentinel2-super-resolution-poc) has no FFI layer: its seam is the
  * Python class `RealESRGAN` (server/app/cnn_super_resolution.py:161-280) plus the free
@@ -56,7 +56,13 @@ typedef struct s2sr_config {
     int32_t num_block;   /* 23 (realesrgan_x4) or 6 (realesrgan_anime), cnn_super_resolution.py:28-45 */
     int32_t num_feat;    /* must be 64 */
     int32_t num_grow;    /* must be 32 */
-    int32_t scale;       /* must be 4 (the only scale in the reference's MODELS table) */
+    int32_t scale;       /* 4, or 2 = RealESRGAN_x2plus: F.pixel_unshuffle(x, 2), a 12-channel conv_first, then the x4 body and
+                          * tail on the half-resolution grid (basicsr RRDBNet(num_in_ch=3, scale=2)); output 2H x 2W.  Scale 2
+                          * network-level entries (forward_batch_u8, forward_f32, calibrate_fp8, forward_part_u8_dev, the debug
+                          * hooks) take even th, tw (S2SR_E_INVALID otherwise); the image entries (enhance_*, tile_process, cut /
+                          * stitch) take any H, W >= 2 and an even tile, reflect-pad an odd H or W by one row / column at the
+                          * bottom / right (RealESRGANer's mod-2 rule), plan the windows on the padded image at scale 2 and crop
+                          * the output to 2H x 2W. */
     int32_t precision;   /* S2SR_PREC_* */
     int32_t device;      /* HIP device ordinal */
     int32_t group;       /* images pushed through the trunk together (0 = default) */
@@ -110,7 +116,11 @@ int  s2sr_host_free(void* p);
  * registration order (conv_first, body.{b}.rdb{1..3}.conv{1..5}, conv_body, conv_up1,
  * conv_up2, conv_hr, conv_last): weight[Cout][Cin][3][3] then bias[Cout], fp32. */
 int  s2sr_load_weights(s2sr_handle* h, const float* blob, size_t n_floats);
+/* floats of the blob of a scale-4 net (conv_first 3 -> 64) */
 size_t s2sr_expected_blob_floats(int32_t num_block);
+/* ... of a net of `scale` 4 or 2 (scale 2: conv_first 12 -> 64, 5184 floats more); 0 for any other scale.  A blob of the other
+ * scale is S2SR_E_BADBLOB in s2sr_load_weights. */
+size_t s2sr_expected_blob_floats_scale(int32_t num_block, int32_t scale);
 /* same blob, DEVICE-resident (e.g. the receive buffer of the RCCL weight broadcast); `stream`
  * is the stream the blob was produced on (a hipStream_t; NULL = default stream).  Returns when loaded.  The RDB convs are
  * repacked on the device; only the six head/tail convs' weights (0.9 MB) pass through host memory. */
@@ -129,18 +139,20 @@ int  s2sr_plan_tiles(int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t sc
                      s2sr_window* out, int32_t cap, int32_t* n);
 
 /* replaces RRDBNet.forward + the u8 quantisation of enhance() on a batch of equal-size tiles
- * (cnn_super_resolution.py:140-158,220-222,231-232): [B,h,w,3] u8 -> [B,4h,4w,3] u8. */
+ * (cnn_super_resolution.py:140-158,220-222,231-232): [B,h,w,3] u8 -> [B,S h,S w,3] u8, S = s2sr_config.scale (scale 2: even h,
+ * w).  Every output shape below that says 4 is S on a scale-2 handle. */
 int  s2sr_forward_batch_u8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int32_t th, int32_t tw,
                            uint8_t* out);
 /* same with device-resident input/output, asynchronous on `stream` (a hipStream_t; NULL = the
  * default stream, ordered with the caller's other default-stream work) */
 int  s2sr_forward_batch_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int32_t th, int32_t tw,
                                void* d_out, void* stream);
-/* unquantised net output for parity tests: x [N,3,H,W] fp32 in [0,1] -> y [N,3,4H,4W] fp32 */
+/* unquantised net output for parity tests: x [N,3,H,W] fp32 in [0,1] -> y [N,3,4H,4W] fp32 (scale 2: even H, W -> [N,3,2H,2W]) */
 int  s2sr_forward_f32(s2sr_handle* h, const float* x, int32_t N, int32_t H, int32_t W, float* y);
 
 /* replaces RealESRGAN.enhance incl. the whole/tiled switch and _tile_process
- * (cnn_super_resolution.py:217-280): HxWx3 u8 -> 4Hx4Wx3 u8, channel order as given. */
+ * (cnn_super_resolution.py:217-280): HxWx3 u8 -> 4Hx4Wx3 u8, channel order as given.  Scale 2: -> 2Hx2Wx3, H, W >= 2, even
+ * tile; the whole / tiled switch compares the padded size (s2sr_config.scale). */
 int  s2sr_enhance_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W,
                      int32_t tile, int32_t pad, uint8_t* out);
 /* The device work of one /api/wow or /api/sr job in ONE call (apply_wow_sr, wow_sr.py:85-110; apply_farm_sr, farm_sr.py:156-178):
@@ -161,7 +173,8 @@ int  s2sr_tile_process_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_
 /* Multi-GPU building blocks of _tile_process (cnn_super_resolution.py:244-278), device-resident:
  * cut windows [first, first+count) of the plan into d_tiles [count, wh, ww, 3] (wh/ww = the
  * plan's common window size), and paste ALL T windows' outputs d_tiles [T, 4wh, 4ww, 3] into
- * d_out [4H, 4W, 3] with the reference's crop + overwrite order.  Between the two a rank runs
+ * d_out [4H, 4W, 3] with the reference's crop + overwrite order.  Scale 2: the plan of the padded image at scale 2 (odd H or W:
+ * the cut reads the reflect row / column by index), [T, 2wh, 2ww, 3] into [2H, 2W, 3].  Between the two a rank runs
  * s2sr_forward_batch_u8_dev on its share and the ranks all-gather (RCCL) the outputs. */
 int  s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_t W, int32_t tile, int32_t pad,
                              int32_t first, int32_t count, void* d_tiles, void* stream);
@@ -376,7 +389,9 @@ int  s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a);
  *   tap[S2SR_TAP_U0 + k]   64 ch  conv_body (k 0), up1, up2, hr outputs: fp16 hi (U1 at 2x, U2 and U3 at 4x)
  *   tap[S2SR_TAP_U0LO + k] 128 ch their e4m3 planes as T8 (split-operand tail only; hi8 planes that are not written read as 0)
  *   out_f32 [B, 3, 4th, 4tw], out_u8 [B, 4th, 4tw, 3]: the outputs of the same run.
- * `avail` bit t: tap t exists in this mode. */
+ * `avail` bit t: tap t exists in this mode.
+ * Scale 2: th, tw even; every tap is on the th/2 x tw/2 trunk grid (P0 = the unshuffled input, channels 12-15 zero), mos_wh /
+ * mos_ww are trunk sizes, and the outputs are [B, 3, 2th, 2tw] / [B, 2th, 2tw, 3]. */
 enum { S2SR_TAP_P0 = 0, S2SR_TAP_F, S2SR_TAP_TRUNK_HI, S2SR_TAP_TRUNK_LO, S2SR_TAP_T8, S2SR_TAP_U0, S2SR_TAP_U1, S2SR_TAP_U2,
        S2SR_TAP_U3, S2SR_TAP_U0LO, S2SR_TAP_U1LO, S2SR_TAP_U2LO, S2SR_TAP_U3LO, S2SR_TAP_COUNT };
 typedef struct s2sr_debug_taps {
@@ -430,6 +445,7 @@ typedef struct s2sr_debug_trunk_fields {
     float* out_f32;                     /* in */
     uint8_t* out_u8;                    /* in */
 } s2sr_debug_trunk_fields;
+/* (scale-4 handles only: S2SR_E_INVALID on a scale-2 handle, whose trunk is the same schedule on the half grid) */
 int  s2sr_debug_trunk_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw,
                            int32_t job_windows, s2sr_debug_trunk_fields* t);
 

@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from s2sr import native
-from s2sr.weights import MODEL_TABLE, conv_specs, flatten_state_dict, select_params
+from s2sr.weights import MODEL_TABLE, conv_specs, first_conv_cin, flatten_state_dict, select_params
 
 # Model table -- keys and fields as in the reference (:28-45)
 MODELS = {
@@ -43,6 +43,22 @@ MODELS = {
     },
 }
 
+# Models beyond the reference's table, resolved by name after MODELS (download_weights, RealESRGAN(model_name=...)).  MODELS stays
+# the reference's, so RealESRGAN(scale=2) still looks up "realesrgan_x2" and fails as the reference does; a deployment serves
+# x2plus by naming it.
+EXTRA_MODELS = {
+    "realesrgan_x2plus": {
+        "url": "https://github.com/xinntao/Real-ESRGAN/releases/download/v0.2.1/RealESRGAN_x2plus.pth",
+        "description": "Quick upscaling (less hallucination, 2x upscale)",
+        **MODEL_TABLE["realesrgan_x2plus"],
+    },
+}
+
+
+def model_config(model_name: str) -> Optional[dict]:
+    """The table entry of `model_name`: MODELS first, then EXTRA_MODELS; None when neither has it."""
+    return MODELS.get(model_name) or EXTRA_MODELS.get(model_name)
+
 
 def get_model_dir() -> Path:
     """`server/models` next to the app package, or $S2SR_MODEL_DIR (reference :48-52)."""
@@ -52,18 +68,19 @@ def get_model_dir() -> Path:
 
 
 def download_weights(model_name: str) -> Path:
-    """Path of `<model_name>.pth`; ValueError for unknown names (reference :55-70)."""
-    if model_name not in MODELS:
+    """Path of `<model_name>.pth`; ValueError for unknown names (reference :55-70).  Names resolve in MODELS, then EXTRA_MODELS."""
+    config = model_config(model_name)
+    if config is None:
         raise ValueError(f"Unknown model: {model_name}")
     path = get_model_dir() / f"{model_name}.pth"
     if not path.exists():
         if os.environ.get("S2SR_ALLOW_DOWNLOAD") == "1":
             print(f"Downloading {model_name} weights...")
-            urllib.request.urlretrieve(MODELS[model_name]["url"], path)
+            urllib.request.urlretrieve(config["url"], path)
         else:
             raise FileNotFoundError(
                 f"{path} not found and network download is disabled (set S2SR_ALLOW_DOWNLOAD=1 to fetch "
-                f"{MODELS[model_name]['url']}, or place the file there)")
+                f"{config['url']}, or place the file there)")
     return path
 
 
@@ -83,16 +100,20 @@ def _attach(root: nn.Module, dotted: str, leaf: nn.Module) -> None:
 
 class RRDBNet(nn.Module):
     """Shape-compatible with the reference RRDBNet (:110-158): `load_state_dict(strict=True)`
-    accepts RealESRGAN_x4plus / anime_6B checkpoints.  `forward` runs on the GPU engine."""
+    accepts RealESRGAN_x4plus / anime_6B checkpoints.  `forward` runs on the GPU engine.
+
+    num_in_ch=12 (with scale=4, the reference class's own spelling of it) holds RealESRGAN_x2plus: that checkpoint is
+    RRDBNet(num_in_ch=12, scale=4) applied to pixel_unshuffle(x, 2).  Its `forward` takes the [N,3,H,W] image (the unshuffle
+    runs on the device) and returns [N,3,2H,2W]; `scale` is then 2.  The reference's one-upsample scale=2 branch stays refused."""
 
     def __init__(self, num_in_ch=3, num_out_ch=3, num_feat=64, num_block=23, num_grow_ch=32, scale=4):
         super().__init__()
-        if (num_in_ch, num_out_ch, num_feat, num_grow_ch, scale) != (3, 3, 64, 32, 4):
-            raise ValueError("the native path is built for num_in_ch=3, num_out_ch=3, num_feat=64, "
-                             "num_grow_ch=32, scale=4 (the only shapes in MODELS)")
-        self.scale = scale
+        if num_in_ch not in (3, 12) or (num_out_ch, num_feat, num_grow_ch, scale) != (3, 64, 32, 4):
+            raise ValueError("the native path is built for num_in_ch=3 (or 12: RealESRGAN_x2plus), num_out_ch=3, num_feat=64, "
+                             "num_grow_ch=32, scale=4 (the shapes in MODELS and EXTRA_MODELS)")
+        self.scale = 2 if num_in_ch == 12 else 4
         self.num_block = num_block
-        for name, cin, cout, _ in conv_specs(num_block):
+        for name, cin, cout, _ in conv_specs(num_block, num_in_ch=num_in_ch):
             _attach(self, name, nn.Conv2d(cin, cout, 3, 1, 1))
         self._engine: Optional[native.Engine] = None
         self._engine_key = None
@@ -117,13 +138,13 @@ class RRDBNet(nn.Module):
         if self._engine is not None and self._engine_key is not None and self._engine_key[1:] == (device_index, ver, prec):
             return self._engine
         fp = self._fingerprint()
-        self._engine = _engine_for(self.state_dict(), self.num_block, device_index, fp)
+        self._engine = _engine_for(self.state_dict(), self.num_block, device_index, fp, self.scale)
         self._engine_key = (fp, device_index, ver, prec)
         return self._engine
 
     @torch.no_grad()
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        """[N,3,H,W] float in [0,1] -> [N,3,4H,4W] float32 (unclamped), computed on the GPU."""
+        """[N,3,H,W] float in [0,1] -> [N,3,sH,sW] float32 (unclamped, s = self.scale), computed on the GPU."""
         dev = x.device
         idx = dev.index if dev.type == "cuda" and dev.index is not None else 0
         y = self.engine(idx).forward_f32(x.detach().float().cpu().numpy())
@@ -136,10 +157,10 @@ _LOADED_MODELS: Dict[tuple, "RRDBNet"] = {}      # checkpoint file identity -> l
 _MODELS_LOCK = threading.Lock()
 
 
-def _engine_for(state_dict, num_block: int, device_index: int, fingerprint: str) -> native.Engine:
-    """One native handle per (weights, GPU), shared by every RealESRGAN object of the process."""
+def _engine_for(state_dict, num_block: int, device_index: int, fingerprint: str, scale: int = 4) -> native.Engine:
+    """One native handle per (weights, scale, GPU), shared by every RealESRGAN object of the process."""
     with _ENGINES_LOCK:
-        key = (fingerprint, device_index, _precision_override() or os.environ.get("S2SR_PRECISION", "hp"))
+        key = (fingerprint, device_index, _precision_override() or os.environ.get("S2SR_PRECISION", "hp"), scale)
         eng = _ENGINES.get(key)
         if eng is None:
             # S2SR_PRECISION=fast trades the <=1e-4 parity of the default for ~14 % more throughput; =fp8 runs the RDB
@@ -147,8 +168,8 @@ def _engine_for(state_dict, num_block: int, device_index: int, fingerprint: str)
             prec = {"fast": native.PREC_F16, "fp8": native.PREC_FP8}.get(_precision_override() or
                                                                           os.environ.get("S2SR_PRECISION", "hp"), native.PREC_F16_HP)
             eng = native.Engine(num_block=num_block, device=device_index, precision=prec,
-                                group=int(os.environ.get("S2SR_GROUP", "0")))
-            eng.load_blob(flatten_state_dict(state_dict, num_block))
+                                group=int(os.environ.get("S2SR_GROUP", "0")), scale=scale)
+            eng.load_blob(flatten_state_dict(state_dict, num_block, scale=scale))
             if prec == native.PREC_FP8 and not (os.environ.get("S2SR_FP8_XEXP") or os.environ.get("S2SR_FP8_GEXP")):
                 # activation scales of the fp8 trunk from data: a few imagery-like tiles through THIS checkpoint
                 from s2sr.synth import synthetic_tiles
@@ -226,9 +247,9 @@ class RealESRGAN:
 
         if model_name is None:
             model_name = f"realesrgan_x{scale}"
-        if model_name not in MODELS:
+        config = model_config(model_name)
+        if config is None:
             raise ValueError(f"Unknown model: {model_name}. Available: {list(MODELS.keys())}")
-        config = MODELS[model_name]
         self.scale = config["scale"]
         self.model_name = model_name
 
@@ -239,14 +260,15 @@ class RealESRGAN:
         if state_dict is None:
             weights_path = Path(download_weights(model_name))
             st = weights_path.stat()
-            cache_key = (str(weights_path.resolve()), st.st_mtime_ns, st.st_size, config["blocks"])
+            cache_key = (str(weights_path.resolve()), st.st_mtime_ns, st.st_size, config["blocks"], config["scale"])
             with _MODELS_LOCK:
                 self.model = _LOADED_MODELS.get(cache_key)
         else:
             self.model = None
         if self.model is None:
-            self.model = RRDBNet(num_in_ch=3, num_out_ch=3, num_feat=config["channels"],
-                                 num_block=config["blocks"], num_grow_ch=32, scale=self.scale)
+            # RealESRGAN_x2plus: the reference class's RRDBNet(num_in_ch=12, scale=4) on the unshuffled image
+            self.model = RRDBNet(num_in_ch=first_conv_cin(self.scale), num_out_ch=3, num_feat=config["channels"],
+                                 num_block=config["blocks"], num_grow_ch=32, scale=4)
             if state_dict is None:
                 state_dict = select_params(torch.load(weights_path, map_location="cpu"))
             state_dict = {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in state_dict.items()}
@@ -261,7 +283,8 @@ class RealESRGAN:
         print(f"   Loaded {model_name} (x{self.scale})")
 
     def enhance(self, img: np.ndarray) -> np.ndarray:
-        """HxWx3 uint8 (channel order as given) -> 4Hx4Wx3 uint8.
+        """HxWx3 uint8 (channel order as given) -> 4Hx4Wx3 uint8 (self.scale x: 2Hx2Wx3 for realesrgan_x2plus, whose odd
+        sizes are reflect-padded by one row / column and cropped back, RealESRGANer's mod-2 rule).
 
         Whole-image forward when h*w <= tile_size^2*4, otherwise the reference's window plan
         (tile_size + 2*tile_pad windows, halo crop, later windows overwrite) -- both inside
@@ -285,7 +308,7 @@ class RealESRGAN:
         return self._engine.enhance_job_u8(rgb, post, tile=self.tile_size, pad=self.tile_pad)
 
     def _tile_process(self, img: torch.Tensor) -> torch.Tensor:
-        """[1,3,H,W] float in [0,1] -> [1,3,4H,4W] float32 through the tiled path (:236-280)."""
+        """[1,3,H,W] float in [0,1] -> [1,3,sH,sW] float32 (s = self.scale) through the tiled path (:236-280)."""
         u8 = (img[0].permute(1, 2, 0).cpu().numpy() * 255.0).round().clip(0, 255).astype(np.uint8)
         out = self._engine.tile_process_f32(u8, tile=self.tile_size, pad=self.tile_pad)
         return torch.from_numpy(out).permute(2, 0, 1).unsqueeze(0)

@@ -41,7 +41,8 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
     from s2sr import rasterio_lite as rio
 
     model_display = {"realesrgan_x4": "Real-ESRGAN x4",
-                     "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)"}.get(model, model)
+                     "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)",
+                     "realesrgan_x2plus": "Real-ESRGAN x2plus (5 m)"}.get(model, model)
     print(f"\nWOW Super-Resolution ({model_display} + Enhanced)\n   Input: {input_path}")
     input_path = Path(input_path)
     img, georef = rio.read_rgb_u8(input_path)           # u8 RGB (min-max normalised if >255, :67-73)

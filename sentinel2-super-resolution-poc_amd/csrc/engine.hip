@@ -96,6 +96,7 @@ struct Mosaic {
 
 struct GraphEntry {
     int n = 0, th = 0, tw = 0;
+    int sh = 0, sw = 0;              // input rows / columns as stored (forward_dev src_h / src_w)
     int mos_kx = 0, mos_ky = 0, mos_count = 0;
     const void *in_u8 = nullptr, *in_f32 = nullptr;
     void *out_u8 = nullptr, *out_f32 = nullptr;
@@ -118,6 +119,9 @@ struct TrunkTap {
 
 struct s2sr_handle {
     s2sr_config cfg{};
+    // RealESRGAN_x2plus (cfg.scale 2) runs pixel_unshuffle(x, 2) and then the x4 net on the half grid.  Every entry takes input
+    // sizes: the trunk (workspace, mosaic, launch groups, graphs) is input / unshuffle(), the output input * cfg.scale.
+    int unshuffle() const { return cfg.scale == 2 ? 2 : 1; }
     hipStream_t stream = nullptr;
     std::mutex mu;
     std::string err;
@@ -215,9 +219,9 @@ struct ConvSpec {
     int cin, cout;
 };
 
-std::vector<ConvSpec> conv_specs(int num_block) {
+std::vector<ConvSpec> conv_specs(int num_block, int scale) {
     std::vector<ConvSpec> v;
-    v.push_back({3, 64});
+    v.push_back({scale == 2 ? 12 : 3, 64});   // conv_first; scale 2 reads the 12 channels of pixel_unshuffle(x, 2)
     for (int b = 0; b < num_block; ++b)
         for (int r = 0; r < 3; ++r)
             for (int k = 1; k <= 5; ++k) v.push_back({64 + (k - 1) * 32, k < 5 ? 32 : 64});
@@ -776,7 +780,8 @@ static long mosaic_patches(int B, int th, int tw, int kx, int ky) {   // patches
     return a;
 }
 static Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw);
-Mosaic pick_mosaic(const s2sr_handle* h, int B, int th, int tw) { return pick_mosaic_cfg(h->mosaic_on, B, th, tw); }
+// th x tw: input windows; the mosaic is laid out on the trunk grid (its wh x ww are trunk sizes)
+Mosaic pick_mosaic(const s2sr_handle* h, int B, int th, int tw) { return pick_mosaic_cfg(h->mosaic_on, B, th / h->unshuffle(), tw / h->unshuffle()); }
 // pure host arithmetic (s2sr_debug_pick_mosaic exposes it to the CPU tests)
 static Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw) {
     Mosaic m;
@@ -812,29 +817,39 @@ static Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw) {
     return m;
 }
 
-// [B,th,tw,3] u8 (device) -> u8 [B,4th,4tw,3] and/or f32 [B,3,4th,4tw] (device)
+// [B,th,tw,3] u8 (device) -> u8 [B,S th,S tw,3] and/or f32 [B,3,S th,S tw] (device), S = cfg.scale.  At scale 2 th and tw are even
+// and the net runs on the th/2 x tw/2 trunk grid.  `src_h` x `src_w` (0: th x tw): the rows / columns the single input image holds
+// when it is one short of th / tw (scale 2, odd image: the packer reads the reflect row / column by index).
 // `plan`: the mosaic chosen for the whole job this call is a part of (a chunk of an AOI, a group of a batch) -- its geometry
 // sizes the workspace, so every part of the job runs in the same planes (r03 ADVICE: re-picking the mosaic from each chunk's own
 // window count gave a short last chunk another image height, and with it a workspace reallocation, a device synchronise and
 // dropped graphs inside the chunk loop, on every call).  nullptr: choose from B.
 int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const float* d_x_f32, int B, int th, int tw,
-                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan = nullptr) {
+                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan = nullptr, int src_h = 0, int src_w = 0) {
     if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
     if (B <= 0 || th <= 0 || tw <= 0) return fail(h, S2SR_E_INVALID, "bad batch/tile dims");
+    const int u = h->unshuffle();
+    if (th % u || tw % u) {
+        char b[200];
+        snprintf(b, sizeof b, "tiles of %d x %d: a scale-2 handle (pixel_unshuffle by 2) needs even tile sizes", th, tw);
+        return fail(h, S2SR_E_INVALID, b);
+    }
+    const int sh = src_h ? src_h : th, sw = src_w ? src_w : tw;     // input rows / columns as stored
+    const int TH = th / u, TW = tw / u;                            // the trunk grid: what the schedule, workspace and graphs see
     // u8 tiles may travel as window mosaics; "images" below are then mosaics of per = kx*ky windows
     const Mosaic mo = !d_tiles ? Mosaic() : (plan ? *plan : pick_mosaic(h, B, th, tw));
     const int per = mo.on() ? mo.kx * mo.ky : 1;
-    const int IH = mo.on() ? mo.ky * (th + 1) - 1 : th, IW = mo.on() ? mo.kx * (tw + 1) - 1 : tw;   // the plan's image: the workspace geometry
+    const int IH = mo.on() ? mo.ky * (TH + 1) - 1 : TH, IW = mo.on() ? mo.kx * (TW + 1) - 1 : TW;   // the plan's image: the workspace geometry
     const int NIplan = ((plan && plan->count > B ? plan->count : B) + per - 1) / per;
     int G = group_size(h, NIplan, IH, IW);
-    int rc = ensure_workspace(h, G, IH, IW, mo.on() ? th + 1 : 0, mo.on() ? tw + 1 : 0);
+    int rc = ensure_workspace(h, G, IH, IW, mo.on() ? TH + 1 : 0, mo.on() ? TW + 1 : 0);
     while (rc == S2SR_E_CAPACITY && G > 1) {          // the card is shared: fall back to smaller launch groups rather than fail the job
         G = (G + 1) / 2;
-        rc = ensure_workspace(h, G, IH, IW, mo.on() ? th + 1 : 0, mo.on() ? tw + 1 : 0);
+        rc = ensure_workspace(h, G, IH, IW, mo.on() ? TH + 1 : 0, mo.on() ? TW + 1 : 0);
     }
     if (rc) return rc;
     Workspace& w = h->ws;
-    const size_t opx = (size_t)16 * th * tw;
+    const size_t opx = (size_t)16 * TH * TW;          // output pixels per tile: the x4 tail on the trunk grid
     // segments of equal image geometry: the full mosaics, then the remainder as one smaller mosaic
     struct Seg { int t0, nwin, kx, ky; };
     Seg segs[2];
@@ -849,12 +864,12 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
     const Seg& sg = segs[si];
     const int sper = sg.kx * sg.ky;
     const int NI = (sg.nwin + sper - 1) / sper;                                // images of this segment
-    const int SH = mo.on() ? sg.ky * (th + 1) - 1 : th, SW = mo.on() ? sg.kx * (tw + 1) - 1 : tw;
+    const int SH = mo.on() ? sg.ky * (TH + 1) - 1 : TH, SW = mo.on() ? sg.kx * (TW + 1) - 1 : TW;
     for (int g0 = 0; g0 < NI; g0 += G) {
         const int n = (NI - g0 < G) ? (NI - g0) : G;
         const int t0 = sg.t0 + g0 * sper;                                     // first window / tile of this group
         const int nt = (sg.t0 + sg.nwin - t0 < n * sper) ? (sg.t0 + sg.nwin - t0) : n * sper;   // windows / tiles in it
-        const uint8_t* in8 = d_tiles ? d_tiles + (size_t)t0 * th * tw * 3 : nullptr;
+        const uint8_t* in8 = d_tiles ? d_tiles + (size_t)t0 * sh * sw * 3 : nullptr;
         const float* in32 = d_tiles ? nullptr : d_x_f32 + (size_t)t0 * 3 * th * tw;
         float* o32 = d_out_f32 ? d_out_f32 + (size_t)t0 * 3 * opx : nullptr;
         uint8_t* o8 = d_out_u8 ? d_out_u8 + (size_t)t0 * 3 * opx : nullptr;
@@ -862,8 +877,12 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
         mg.kx = sg.kx; mg.ky = sg.ky; mg.count = nt;
         auto enqueue = [&]() -> int {
             {
-                Scope sc(h, st, F_PACK, 0.0, (double)nt * th * tw * (3.0 + 8.0));
-                if (in8 && mo.on()) HIPCHK(h, launch_pack_u8_mosaic(in8, nt, th, tw, sg.kx, sg.ky, w.P0, w.Hp, w.Wp, st));
+                Scope sc(h, st, F_PACK, 0.0, (double)nt * th * tw * (3.0 + 8.0));   // (scale 2: 32 B per trunk pixel = 8 per input pixel)
+                if (u == 2) {      // pixel_unshuffle(x, 2) folded into the packers
+                    if (in8 && mo.on()) HIPCHK(h, launch_pack_u8_unshuffle_mosaic(in8, nt, TH, TW, sg.kx, sg.ky, w.P0, w.Hp, w.Wp, st));
+                    else if (in8) HIPCHK(h, launch_pack_u8_unshuffle(in8, n, sh, sw, TH, TW, w.P0, w.Hp, w.Wp, st));
+                    else HIPCHK(h, launch_pack_f32_nchw_unshuffle(in32, n, TH, TW, 255.0f, w.P0, w.Hp, w.Wp, st));
+                } else if (in8 && mo.on()) HIPCHK(h, launch_pack_u8_mosaic(in8, nt, th, tw, sg.kx, sg.ky, w.P0, w.Hp, w.Wp, st));
                 else if (in8) HIPCHK(h, launch_pack_u8(in8, n, th, tw, w.P0, w.Hp, w.Wp, st));
                 else HIPCHK(h, launch_pack_f32_nchw(in32, n, 3, th, tw, 255.0f, w.P0, 1, w.Hp, w.Wp, st));
             }
@@ -873,7 +892,7 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
         GraphEntry* ge = nullptr;
         if (h->graphs_on && h->prof <= 0 && st != nullptr) {
             for (GraphEntry& g : h->graphs)
-                if (g.n == n && g.th == th && g.tw == tw && g.in_u8 == in8 && g.in_f32 == in32 && g.out_u8 == o8 &&
+                if (g.n == n && g.th == th && g.tw == tw && g.sh == sh && g.sw == sw && g.in_u8 == in8 && g.in_f32 == in32 && g.out_u8 == o8 &&
                     g.out_f32 == o32 && g.st == st && g.mos_kx == (mo.on() ? sg.kx : 0) && g.mos_ky == (mo.on() ? sg.ky : 0) &&
                     g.mos_count == (mo.on() ? nt : 0)) { ge = &g; break; }
             if (!ge) {   // first sighting: remember it, launch directly (also warms the per-kernel attributes)
@@ -885,7 +904,7 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
                     h->graphs.erase(h->graphs.begin() + victim);
                 }
                 GraphEntry g;
-                g.n = n; g.th = th; g.tw = tw; g.in_u8 = in8; g.in_f32 = in32; g.out_u8 = o8; g.out_f32 = o32; g.st = st;
+                g.n = n; g.th = th; g.tw = tw; g.sh = sh; g.sw = sw; g.in_u8 = in8; g.in_f32 = in32; g.out_u8 = o8; g.out_f32 = o32; g.st = st;
                 g.mos_kx = mo.on() ? sg.kx : 0; g.mos_ky = mo.on() ? sg.ky : 0; g.mos_count = mo.on() ? nt : 0;
                 g.last_use = ++h->graph_clock;
                 h->graphs.push_back(g);
@@ -943,19 +962,22 @@ int s2sr_device_count(void) {
     return n;
 }
 
-size_t s2sr_expected_blob_floats(int32_t num_block) {
+size_t s2sr_expected_blob_floats_scale(int32_t num_block, int32_t scale) {
+    if (scale != 2 && scale != 4) return 0;
     size_t n = 0;
-    for (const ConvSpec& s : conv_specs(num_block)) n += (size_t)s.cin * s.cout * 9 + s.cout;
+    for (const ConvSpec& s : conv_specs(num_block, scale)) n += (size_t)s.cin * s.cout * 9 + s.cout;
     return n;
 }
+
+size_t s2sr_expected_blob_floats(int32_t num_block) { return s2sr_expected_blob_floats_scale(num_block, 4); }
 
 const char* s2sr_last_error(const s2sr_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 int s2sr_create(const s2sr_config* cfg, s2sr_handle** out) {
     if (!cfg || !out) return fail(nullptr, S2SR_E_INVALID, "null argument");
     *out = nullptr;
-    if (cfg->num_block <= 0 || cfg->num_feat != 64 || cfg->num_grow != 32 || cfg->scale != 4)
-        return fail(nullptr, S2SR_E_INVALID, "unsupported net shape (need num_feat=64, num_grow=32, scale=4)");
+    if (cfg->num_block <= 0 || cfg->num_feat != 64 || cfg->num_grow != 32 || (cfg->scale != 4 && cfg->scale != 2))
+        return fail(nullptr, S2SR_E_INVALID, "unsupported net shape (need num_feat=64, num_grow=32, scale=4 or 2)");
     if (cfg->precision != S2SR_PREC_F16 && cfg->precision != S2SR_PREC_F16_HP && cfg->precision != S2SR_PREC_FP8)
         return fail(nullptr, S2SR_E_INVALID, "unknown precision");
     int ndev = 0;
@@ -1039,11 +1061,11 @@ void s2sr_destroy(s2sr_handle* h) {
 // are repacked by device kernels straight from it (pack.hip), every bias is gathered on the device; only the six head/tail
 // convs (0.9 MB of the 67 MB) come back to the host, because their split-operand / sub-pixel packers are host code.
 static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_floats, hipStream_t st) {
-    const std::vector<ConvSpec> specs = conv_specs(h->cfg.num_block);
-    const size_t want = s2sr_expected_blob_floats(h->cfg.num_block);
+    const std::vector<ConvSpec> specs = conv_specs(h->cfg.num_block, h->cfg.scale);
+    const size_t want = s2sr_expected_blob_floats_scale(h->cfg.num_block, h->cfg.scale);
     if (n_floats != want) {
         char b[160];
-        snprintf(b, sizeof b, "weight blob has %zu floats, a %d-block net needs %zu", n_floats, h->cfg.num_block, want);
+        snprintf(b, sizeof b, "weight blob has %zu floats, a %d-block scale-%d net needs %zu", n_floats, h->cfg.num_block, h->cfg.scale, want);
         return fail(h, S2SR_E_BADBLOB, b);
     }
     HIPCHK(h, dev_sync());
@@ -1153,7 +1175,7 @@ int s2sr_load_weights(s2sr_handle* h, const float* blob, size_t n_floats) {
     if (!h || !blob) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (n_floats != s2sr_expected_blob_floats(h->cfg.num_block)) return load_weights_locked(h, nullptr, n_floats, h->stream);   // -> BADBLOB text
+    if (n_floats != s2sr_expected_blob_floats_scale(h->cfg.num_block, h->cfg.scale)) return load_weights_locked(h, nullptr, n_floats, h->stream);   // -> BADBLOB text
     float* d_blob = nullptr;
     HIPCHK(h, dev_malloc(&d_blob, n_floats * sizeof(float)));
     hipError_t e = hipMemcpyAsync(d_blob, blob, n_floats * sizeof(float), hipMemcpyHostToDevice, h->stream);
@@ -1298,7 +1320,8 @@ static int forward_batch_u8_once(s2sr_handle* h, const uint8_t* tiles, int32_t B
     if (!h || !tiles || !out) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t ib = (size_t)B * th * tw * 3, ob = ib * 16;
+    const int S = h->cfg.scale, u = h->unshuffle();
+    const size_t ib = (size_t)B * th * tw * 3, ob = ib * S * S;
     int rc = ensure_scratch(h, 0, ib);
     if (rc) return rc;
     rc = ensure_scratch(h, 1, ob);
@@ -1309,8 +1332,8 @@ static int forward_batch_u8_once(s2sr_handle* h, const uint8_t* tiles, int32_t B
     // one mosaic plan for the whole batch (ragged tiles): every group runs in the same workspace geometry
     const Mosaic mo = pick_mosaic(h, B, th, tw);
     const int per = mo.on() ? mo.kx * mo.ky : 1;
-    const int G = (mo.on() ? group_size(h, (B + per - 1) / per, mo.ky * (th + 1) - 1, mo.kx * (tw + 1) - 1) : group_size(h, B, th, tw)) * per;
-    const size_t tin = (size_t)th * tw * 3, tout = tin * 16;
+    const int G = (mo.on() ? group_size(h, (B + per - 1) / per, mo.ky * (mo.wh + 1) - 1, mo.kx * (mo.ww + 1) - 1) : group_size(h, B, th / u, tw / u)) * per;
+    const size_t tin = (size_t)th * tw * 3, tout = tin * S * S;
     const int ngroups = (B + G - 1) / G;
     while ((int)h->group_done.size() < ngroups) {
         hipEvent_t e;
@@ -1342,7 +1365,7 @@ static int forward_f32_once(s2sr_handle* h, const float* x, int32_t N, int32_t H
     if (!h || !x || !y) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t ib = (size_t)N * 3 * H * W * 4, ob = ib * 16;
+    const size_t ib = (size_t)N * 3 * H * W * 4, ob = ib * h->cfg.scale * h->cfg.scale;
     int rc = ensure_scratch(h, 0, ib);
     if (rc) return rc;
     rc = ensure_scratch(h, 1, ob);
@@ -1441,6 +1464,18 @@ static int pp_band_hist_locked(s2sr_handle* h, const void* d_img, int y0, int y1
 static int pp_band_lut_locked(s2sr_handle* h, hipStream_t st);
 static int pp_band_rows_locked(s2sr_handle* h, const void* d_img, int y0, int y1, void* d_out, hipStream_t st);
 
+// The image a tile plan is made for.  Scale 2: H x W reflect-padded by one row / column at the bottom / right to even sizes
+// (RealESRGANer's mod-2 rule; the pad is read by index, see pack.hip), and an even tile, so that every window of the padded image
+// has even origin and extent.
+static int plan_dims(s2sr_handle* h, int H, int W, int tile, int* PH, int* PW) {
+    *PH = H; *PW = W;
+    if (h->unshuffle() == 1) return S2SR_OK;
+    if (H < 2 || W < 2) return fail(h, S2SR_E_INVALID, "scale 2 needs an image of at least 2 x 2 (the mod-2 reflect pad)");
+    if (tile % 2) return fail(h, S2SR_E_INVALID, "scale 2 needs an even tile: every window of the padded image must have even origin and size");
+    *PH = H + (H & 1); *PW = W + (W & 1);
+    return S2SR_OK;
+}
+
 // job_rgb: the caller's image is RGB and wants RGB back -- R and B are swapped on the device in front of and behind the net (the
 // reference's cvtColor pair, wow_sr.py:85,103).  prm: the crop-visibility post-process (wow_sr.py:187-209) on the stitched RGB
 // image, on the device, before the one copy out (it is image-global: no band leaves before the whole mosaic is done).
@@ -1451,20 +1486,26 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
-    const int scale = 4, OH = H * scale, OW = W * scale;
+    int rc, PH, PW;
+    if ((rc = plan_dims(h, H, W, tile, &PH, &PW))) return rc;
+    // scale 2, odd H or W: everything below runs on the padded PH x PW image; the output is cropped to OH x OW by the stitch maps
+    const bool reflect = PH != H || PW != W;
+    const int scale = h->cfg.scale, u = h->unshuffle(), OH = H * scale, OW = W * scale, OHp = PH * scale, OWp = PW * scale;
     const size_t ib = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
-    int rc;
     if ((rc = ensure_scratch(h, 0, ib))) return rc;
     if ((rc = ensure_scratch(h, 1, opx * (out_f32 ? 4 : 1)))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, ib, hipMemcpyHostToDevice, st));
     if (job_rgb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[0], (size_t)H * W, (uint8_t*)h->d_scratch[0], st));
     const bool whole_finish = job_rgb || prm != nullptr;      // the image leaves in one piece, behind the device-side finish
-    const bool tiled = force_tiled || (long long)H * W > (long long)tile * tile * 4;   // strict '>' (:226)
+    const bool tiled = force_tiled || (long long)PH * PW > (long long)tile * tile * 4;   // strict '>' (:226)
     if (!tiled) {
-        if (out_f32) {
-            // net output is NCHW; enhance() returns HWC -> stitch with an identity map
-            if ((rc = ensure_scratch(h, 2, opx * 4))) return rc;
-            rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[0], nullptr, 1, H, W, nullptr, (float*)h->d_scratch[2]);
+        if (out_f32 || reflect) {
+            // net output is NCHW (f32; enhance() returns HWC) or the padded image's (u8, odd scale-2 image) -> stitch with an
+            // identity map, cropped to OH x OW
+            const size_t opxp = (size_t)OHp * OWp * 3;
+            if ((rc = ensure_scratch(h, 2, opxp * (out_f32 ? 4 : 1)))) return rc;
+            rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[0], nullptr, 1, PH, PW, out_f32 ? nullptr : (uint8_t*)h->d_scratch[2],
+                             out_f32 ? (float*)h->d_scratch[2] : nullptr, nullptr, H, W);
             if (rc) return rc;
             std::vector<int32_t> rm(2 * OH), cm(2 * OW);
             for (int i = 0; i < OH; ++i) { rm[2 * i] = 0; rm[2 * i + 1] = i; }
@@ -1475,20 +1516,21 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
             HIPCHK(h, hipMemcpyAsync(d_rm, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, st));
             HIPCHK(h, hipMemcpyAsync(d_cm, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
             HIPCHK(h, hipStreamSynchronize(st));   // rm/cm are stack-owned host buffers
-            HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[2], 1, OH, OW, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
+            if (out_f32) HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
+            else HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
         } else {
             rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[0], nullptr, 1, H, W, (uint8_t*)h->d_scratch[1], nullptr);
             if (rc) return rc;
         }
     } else {
         int T = 0;
-        s2sr_plan_tiles(H, W, tile, pad, scale, nullptr, 0, &T);
+        s2sr_plan_tiles(PH, PW, tile, pad, scale, nullptr, 0, &T);
         std::vector<s2sr_window> wins(T);
-        s2sr_plan_tiles(H, W, tile, pad, scale, wins.data(), T, &T);
-        const int pnx = (W + tile - 1) / tile, pny = (H + tile - 1) / tile;      // the reference's plan
+        s2sr_plan_tiles(PH, PW, tile, pad, scale, wins.data(), T, &T);
+        const int pnx = (PW + tile - 1) / tile, pny = (PH + tile - 1) / tile;    // the reference's plan
         const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;   // all windows share one shape
         std::vector<int32_t> rm, cm;
-        build_stitch_maps(wins, pnx, pny, OH, OW, rm, cm);
+        build_stitch_maps(wins, pnx, pny, OHp, OWp, rm, cm);                    // (the stitches read the first OH x OW of them)
         // When a dimension ends within 2*pad of a tile multiple, the last two window rows (columns)
         // of the plan are the same rectangle: the reference runs the net on both (only the paste
         // ranges differ).  Identical inputs give identical outputs, so each distinct rectangle is
@@ -1516,7 +1558,7 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
                 const int t = y * nx + x;
                 rects[4 * t] = rows_y1[y]; rects[4 * t + 1] = rows_y1[y] + wh; rects[4 * t + 2] = cols_x1[x]; rects[4 * t + 3] = cols_x1[x] + ww;
             }
-        const size_t tin = (size_t)T * wh * ww * 3, tout = tin * 16;
+        const size_t tin = (size_t)T * wh * ww * 3, tout = tin * scale * scale;
         if ((rc = ensure_scratch(h, 2, tin))) return rc;
         if ((rc = ensure_scratch(h, 4, tout * (out_f32 ? 4 : 1)))) return rc;
         if ((rc = ensure_scratch(h, 3, (rects.size() + rm.size() + cm.size()) * 4))) return rc;
@@ -1527,7 +1569,8 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
         HIPCHK(h, hipMemcpyAsync(d_rm, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHK(h, hipMemcpyAsync(d_cm, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
         HIPCHK(h, hipStreamSynchronize(st));
-        HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
+        if (reflect) HIPCHK(h, launch_gather_windows_reflect((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
+        else HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
         // Chunks of whole window rows.  An output row is final once the last window row that pastes into it is done (the row
         // map is monotone), so each chunk is followed by the stitch of its band of final rows, and the band's device-to-host
         // copy runs on the copy stream under the next chunk's compute.  A chunk holds whole launch groups: for windows that
@@ -1545,16 +1588,16 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
         const Mosaic mo = pick_mosaic(h, T, wh, ww);   // ONE plan for the job: every chunk runs in its workspace geometry
         {
             const int per = mo.on() ? mo.kx * mo.ky : 1;
-            const int gw = (mo.on() ? group_size(h, (T + per - 1) / per, mo.ky * (wh + 1) - 1, mo.kx * (ww + 1) - 1)
-                                    : group_size(h, T, wh, ww)) * per;                  // windows per launch group
+            const int gw = (mo.on() ? group_size(h, (T + per - 1) / per, mo.ky * (mo.wh + 1) - 1, mo.kx * (mo.ww + 1) - 1)
+                                    : group_size(h, T, wh / u, ww / u)) * per;          // windows per launch group
             const int r_min = (per + nx - 1) / nx;                                      // rows that fill a mosaic
             const int units = (ny + r_min - 1) / r_min;                                 // ... and how many such row units the image has
             int u_max = gw / nx / r_min;                                                // units per chunk the workspace allows
             if (u_max < 1) u_max = 1;
             int ncu = 256;
             (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-            const long pimg = mo.on() ? (long)((mo.ky * (wh + 1) - 1 + 31) / 32) * ((mo.kx * (ww + 1) - 1 + 31) / 32)
-                                      : (long)((wh + 31) / 32) * ((ww + 31) / 32);      // 32 x 32 patches per launch image
+            const long pimg = mo.on() ? (long)((mo.ky * (mo.wh + 1) - 1 + 31) / 32) * ((mo.kx * (mo.ww + 1) - 1 + 31) / 32)
+                                      : (long)((wh / u + 31) / 32) * ((ww / u + 31) / 32);   // 32 x 32 patches per launch image
             std::vector<int> sizes;                                                     // in units, front to back
             plan_chunk_sizes(units, u_max, r_min * nx, per, pimg, ncu, sizes);
             int r = 0;
@@ -1569,7 +1612,7 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
             // finishes the image in row bands, each followed by its copy out: what is exposed behind the last window is one band's
             // kernels plus the PCIe time of the image (the r04 form waited for the whole mosaic, swapped, post-processed and only
             // then started the one copy).
-            const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * 16;
+            const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;
             const size_t row_b = (size_t)OW * 3;
             int fin_rows = 0, nfin = 0;          // finishing bands of the post-process: ~48 MB each, whole 32-row tile rows
             if (prm) {
@@ -1595,7 +1638,7 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
                 if (r1 < ny)
                     for (ye = yb; ye < OH && rm[2 * ye] < r1; ++ye) {}
                 if (ye > yb) {
-                    HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * 4, ww * 4, d_rm + 2 * yb, d_cm, ye - yb, OW,
+                    HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW,
                                                d_img_out + (size_t)yb * row_b, st));
                     if (prm) {
                         if ((rc = pp_band_hist_locked(h, d_img_out, yb, ye, st))) return rc;
@@ -1651,8 +1694,8 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
         rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[2], nullptr, T, wh, ww, out_f32 ? nullptr : (uint8_t*)h->d_scratch[4],
                          out_f32 ? (float*)h->d_scratch[4] : nullptr);
         if (rc) return rc;
-        if (out_f32) HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[4], nx, wh * 4, ww * 4, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
-        else HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * 4, ww * 4, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
+        if (out_f32) HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
+        else HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
     }
     const uint8_t* d_final = (const uint8_t*)h->d_scratch[1];
     if (whole_finish) {
@@ -1697,39 +1740,46 @@ int s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
-    int T = 0;
-    s2sr_plan_tiles(H, W, tile, pad, 4, nullptr, 0, &T);
+    int T = 0, PH, PW;
+    int rc = plan_dims(h, H, W, tile, &PH, &PW);
+    if (rc) return rc;
+    s2sr_plan_tiles(PH, PW, tile, pad, h->cfg.scale, nullptr, 0, &T);
     if (first + count > T) return fail(h, S2SR_E_INVALID, "window range exceeds the plan");
     std::vector<s2sr_window> wins(T);
-    s2sr_plan_tiles(H, W, tile, pad, 4, wins.data(), T, &T);
+    s2sr_plan_tiles(PH, PW, tile, pad, h->cfg.scale, wins.data(), T, &T);
     const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;
     std::vector<int32_t> rects(4 * (size_t)count);
     for (int t = 0; t < count; ++t) {
         const s2sr_window& w = wins[first + t];
         rects[4 * t] = w.y1; rects[4 * t + 1] = w.y2; rects[4 * t + 2] = w.x1; rects[4 * t + 3] = w.x2;
     }
-    int rc = ensure_scratch(h, 3, rects.size() * 4);
+    rc = ensure_scratch(h, 3, rects.size() * 4);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_scratch[3], rects.data(), rects.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, launch_gather_windows((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, (uint8_t*)d_tiles, st));
+    if (PH != H || PW != W)
+        HIPCHK(h, launch_gather_windows_reflect((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, (uint8_t*)d_tiles, st));
+    else HIPCHK(h, launch_gather_windows((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, (uint8_t*)d_tiles, st));
     return S2SR_OK;
 }
 
 int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t oy0, int32_t oy1,
                             void* d_out, void* stream) {
-    if (!h || !d_tiles || !d_out || H <= 0 || W <= 0 || tile <= 0 || pad < 0 || oy0 < 0 || oy1 > 4 * H || oy0 > oy1) return S2SR_E_INVALID;
+    if (!h || !d_tiles || !d_out || H <= 0 || W <= 0 || tile <= 0 || pad < 0 || oy0 < 0 || oy1 > h->cfg.scale * H || oy0 > oy1) return S2SR_E_INVALID;
     if (oy0 == oy1) return S2SR_OK;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
-    int T = 0;
-    s2sr_plan_tiles(H, W, tile, pad, 4, nullptr, 0, &T);
+    const int S = h->cfg.scale;
+    int T = 0, PH, PW;
+    int rc = plan_dims(h, H, W, tile, &PH, &PW);
+    if (rc) return rc;
+    s2sr_plan_tiles(PH, PW, tile, pad, S, nullptr, 0, &T);
     std::vector<s2sr_window> wins(T);
-    s2sr_plan_tiles(H, W, tile, pad, 4, wins.data(), T, &T);
-    const int nx = (W + tile - 1) / tile, ny = (H + tile - 1) / tile;
+    s2sr_plan_tiles(PH, PW, tile, pad, S, wins.data(), T, &T);
+    const int nx = (PW + tile - 1) / tile, ny = (PH + tile - 1) / tile;
     const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;
-    const size_t nrm = 2 * (size_t)(4 * H), ncm = 2 * (size_t)(4 * W);
+    const size_t nrm = 2 * (size_t)(S * PH), ncm = 2 * (size_t)(S * PW);   // maps of the padded image; the stitch reads S H x S W
     // the plan's paste maps: from the handle's LRU of map sets, or built and uploaded now.  A NEW set costs an allocation and a
     // blocking upload on the handle's own stream -- nothing the caller has queued on ITS stream is waited for (r04: any key change
     // synchronised the device under the process-wide gate, so the first band's stitch drained every compute chunk already queued
@@ -1758,7 +1808,7 @@ int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int3
             ms->cap = (nrm + ncm) * 4;
         }
         std::vector<int32_t> rm, cm;
-        build_stitch_maps(wins, nx, ny, 4 * H, 4 * W, rm, cm);
+        build_stitch_maps(wins, nx, ny, S * PH, S * PW, rm, cm);
         HIPCHK(h, copy_blocking(h, ms->d, rm.data(), nrm * 4, hipMemcpyHostToDevice));
         HIPCHK(h, copy_blocking(h, ms->d + nrm, cm.data(), ncm * 4, hipMemcpyHostToDevice));
         for (int i = 0; i < 4; ++i) ms->key[i] = key[i];
@@ -1766,14 +1816,15 @@ int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int3
     ms->last_use = ++h->stitch_clock;
     const int32_t* d_rm = ms->d;
     const int32_t* d_cm = d_rm + nrm;
-    HIPCHK(h, launch_stitch_u8((const uint8_t*)d_tiles, nx, wh * 4, ww * 4, d_rm + 2 * (size_t)oy0, d_cm, oy1 - oy0, 4 * W,
-                               (uint8_t*)d_out + (size_t)oy0 * 4 * W * 3, st));
+    HIPCHK(h, launch_stitch_u8((const uint8_t*)d_tiles, nx, wh * S, ww * S, d_rm + 2 * (size_t)oy0, d_cm, oy1 - oy0, S * W,
+                               (uint8_t*)d_out + (size_t)oy0 * S * W * 3, st));
     return S2SR_OK;
 }
 
 int s2sr_stitch_windows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int32_t W, int32_t tile, int32_t pad,
                                void* d_out, void* stream) {
-    return s2sr_stitch_rows_u8_dev(h, d_tiles, H, W, tile, pad, 0, 4 * H, d_out, stream);
+    if (!h) return S2SR_E_INVALID;
+    return s2sr_stitch_rows_u8_dev(h, d_tiles, H, W, tile, pad, 0, h->cfg.scale * H, d_out, stream);
 }
 
 // Device -> host for callers that hold device buffers (s2sr/dist.py's consuming rank): `bytes` from d_src into dst once
@@ -2287,7 +2338,7 @@ int s2sr_calibrate_fp8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int32_t 
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->cfg.precision != S2SR_PREC_FP8) return fail(h, S2SR_E_INVALID, "s2sr_calibrate_fp8 needs a handle created with S2SR_PREC_FP8");
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t ib = (size_t)B * th * tw * 3, ob = ib * 16;
+    const size_t ib = (size_t)B * th * tw * 3, ob = ib * h->cfg.scale * h->cfg.scale;
     int rc = ensure_scratch(h, 0, ib);
     if (rc) return rc;
     if ((rc = ensure_scratch(h, 1, ob))) return rc;
@@ -2743,7 +2794,10 @@ struct TapPlan {
 };
 int tap_plan(s2sr_handle* h, bool u8, int32_t B, int32_t th, int32_t tw, int32_t job_windows, TapPlan* tp) {
     const int job = job_windows > B ? job_windows : B;
-    Mosaic plan = u8 ? pick_mosaic(h, job, th, tw) : Mosaic();
+    const int u = h->unshuffle();
+    if (th % u || tw % u) return fail(h, S2SR_E_INVALID, "a scale-2 handle (pixel_unshuffle by 2) needs even tile sizes");
+    th /= u; tw /= u;                                   // the trunk grid from here on
+    Mosaic plan = u8 ? pick_mosaic_cfg(h->mosaic_on, job, th, tw) : Mosaic();
     const int per = plan.on() ? plan.kx * plan.ky : 1;
     int skx = plan.kx, sky = plan.ky;
     if (plan.on()) {
@@ -2762,7 +2816,7 @@ int tap_plan(s2sr_handle* h, bool u8, int32_t B, int32_t th, int32_t tw, int32_t
 int tap_forward(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, const TapPlan& tp,
                 uint8_t* out_u8, float* out_f32) {
     hipStream_t st = h->stream;
-    const size_t ib = tiles ? (size_t)B * th * tw * 3 : (size_t)B * 3 * th * tw * 4, opx = (size_t)B * 16 * th * tw;
+    const size_t ib = tiles ? (size_t)B * th * tw * 3 : (size_t)B * 3 * th * tw * 4, opx = (size_t)B * h->cfg.scale * h->cfg.scale * th * tw;
     DevBuf d_in, d_o8, d_o32;
     HIPCHK(h, dev_malloc(&d_in.p, ib));
     HIPCHK(h, dev_malloc(&d_o8.p, opx * 3));
@@ -2803,7 +2857,7 @@ int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x
         t->H[k] = s * tp.SH; t->W[k] = s * tp.SW; t->Hp[k] = padded(s * tp.IH); t->Wp[k] = padded(s * tp.IW);
     }
     const bool mos = tp.plan.on();
-    t->mos_kx = mos ? tp.skx : 0; t->mos_ky = mos ? tp.sky : 0; t->mos_wh = mos ? th : 0; t->mos_ww = mos ? tw : 0;
+    t->mos_kx = mos ? tp.skx : 0; t->mos_ky = mos ? tp.sky : 0; t->mos_wh = mos ? tp.plan.wh : 0; t->mos_ww = mos ? tp.plan.ww : 0;
     t->mos_count = mos ? B : 0;
     t->trunk_lo_exp = fp8 ? -1 : h->lo_exp;
     t->avail = 0;
@@ -2860,6 +2914,7 @@ int s2sr_debug_trunk_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, 
     if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
+    if (h->cfg.scale != 4) return fail(h, S2SR_E_INVALID, "trunk taps: scale-4 handles only (the scale-2 trunk is the same schedule on the half grid)");
     if (t->first < 0 || t->count < 1 || t->first + t->count > 3 * h->cfg.num_block)
         return fail(h, S2SR_E_INVALID, "RDB range outside [0, 3 * num_block)");
     const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;

@@ -89,6 +89,119 @@ hipError_t launch_pack_f32_nchw(const float* d_x, int N, int C, int H, int W, fl
     return hipGetLastError();
 }
 
+// RealESRGAN_x2plus (s2sr_config.scale 2): F.pixel_unshuffle(x, 2) in front of conv_first.  Twins of the three packers above:
+// the input at full resolution, the blocked-16 plane at half resolution (the trunk grid h x w).  Channel c*4 + i*2 + j of trunk
+// pixel (y, x) is input channel c at (2y+i, 2x+j) (torch's order), as the exact integers 0..255.  One thread per trunk pixel,
+// consecutive lanes along a trunk row; all 16 channels (12..15 zero) leave as two 16-byte stores.
+typedef f16 f16x8 __attribute__((ext_vector_type(8)));
+
+__device__ inline void store_unshuffled(char* dst, const float (&v)[12]) {
+    f16x8 a, b;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) a[k] = (f16)v[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { b[k] = (f16)v[8 + k]; b[4 + k] = (f16)0.f; }
+    *(f16x8*)dst = a;
+    *(f16x8*)(dst + 16) = b;
+}
+
+// [N,H,W,3] u8, H x W as stored: H is 2h or, for an odd image, 2h - 1.  A row / column 2y+i that is not stored is the one-pixel
+// reflect pad of RealESRGANer's mod-2 rule (torch 'reflect': row H reads row H - 2), read by index -- there is no padded copy.
+__global__ void pack_u8_unshuffle_kernel(const uint8_t* __restrict__ in, int N, int H, int W, int h, int w, char* __restrict__ blk,
+                                         int Hp, int Wp) {
+    const size_t total = (size_t)N * h * w;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % w);
+        const size_t r = i / w;
+        const int y = (int)(r % h);
+        const int n = (int)(r / h);
+        const uint8_t* img = in + (size_t)n * H * W * 3;
+        float v[12];
+#pragma unroll
+        for (int di = 0; di < 2; ++di) {
+            const int sy0 = 2 * y + di, sy = sy0 < H ? sy0 : 2 * H - 2 - sy0;
+#pragma unroll
+            for (int dj = 0; dj < 2; ++dj) {
+                const int sx0 = 2 * x + dj, sx = sx0 < W ? sx0 : 2 * W - 2 - sx0;
+                const uint8_t* s = img + ((size_t)sy * W + sx) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c * 4 + di * 2 + dj] = (float)s[c];
+            }
+        }
+        store_unshuffled(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32, v);
+    }
+}
+
+hipError_t launch_pack_u8_unshuffle(const uint8_t* d_img, int N, int H, int W, int h, int w, char* blk, int Hp, int Wp, hipStream_t st) {
+    const size_t total = (size_t)N * h * w;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(pack_u8_unshuffle_kernel, dim3(grid), dim3(256), 0, st, d_img, N, H, W, h, w, blk, Hp, Wp);
+    return hipGetLastError();
+}
+
+// B windows of 2h x 2w u8 -> kx x ky windows of h x w per mosaic image (the geometry of pack_u8_mosaic_kernel on the trunk grid)
+__global__ void pack_u8_unshuffle_mosaic_kernel(const uint8_t* __restrict__ in, int B, int h, int w, int kx, int ky,
+                                                char* __restrict__ blk, int Hp, int Wp) {
+    const size_t total = (size_t)B * h * w;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int lx = (int)(i % w);
+        const size_t r = i / w;
+        const int ly = (int)(r % h);
+        const int t = (int)(r / h);
+        const int n = t / (kx * ky), slot = t - n * (kx * ky);
+        const int wy = slot / kx, wx = slot - wy * kx;
+        const int y = wy * (h + 1) + ly, x = wx * (w + 1) + lx;
+        const uint8_t* img = in + (size_t)t * (4 * h) * w * 3;
+        float v[12];
+#pragma unroll
+        for (int di = 0; di < 2; ++di)
+#pragma unroll
+            for (int dj = 0; dj < 2; ++dj) {
+                const uint8_t* s = img + ((size_t)(2 * ly + di) * (2 * w) + 2 * lx + dj) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c * 4 + di * 2 + dj] = (float)s[c];
+            }
+        store_unshuffled(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32, v);
+    }
+}
+
+hipError_t launch_pack_u8_unshuffle_mosaic(const uint8_t* d_tiles, int B, int h, int w, int kx, int ky, char* blk, int Hp, int Wp,
+                                           hipStream_t st) {
+    const size_t total = (size_t)B * h * w;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(pack_u8_unshuffle_mosaic_kernel, dim3(grid), dim3(256), 0, st, d_tiles, B, h, w, kx, ky, blk, Hp, Wp);
+    return hipGetLastError();
+}
+
+// [N,3,2h,2w] fp32 -> the plane of the h x w grid, values x * scale (255: the f32 entries feed [0,1] floats)
+__global__ void pack_f32_nchw_unshuffle_kernel(const float* __restrict__ x, int N, int h, int w, float scale, char* __restrict__ blk,
+                                               int Hp, int Wp) {
+    const size_t total = (size_t)N * h * w;
+    const size_t plane = (size_t)(2 * h) * (2 * w);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int xx = (int)(i % w);
+        const size_t r = i / w;
+        const int y = (int)(r % h);
+        const int n = (int)(r / h);
+        float v[12];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int di = 0; di < 2; ++di)
+#pragma unroll
+                for (int dj = 0; dj < 2; ++dj)
+                    v[c * 4 + di * 2 + dj] = x[((size_t)n * 3 + c) * plane + (size_t)(2 * y + di) * (2 * w) + 2 * xx + dj] * scale;
+        store_unshuffled(blk + (((size_t)n * Hp + y + 1) * Wp + xx + 1) * 32, v);
+    }
+}
+
+hipError_t launch_pack_f32_nchw_unshuffle(const float* d_x, int N, int h, int w, float scale, char* blk, int Hp, int Wp, hipStream_t st) {
+    const size_t total = (size_t)N * h * w;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(pack_f32_nchw_unshuffle_kernel, dim3(grid), dim3(256), 0, st, d_x, N, h, w, scale, blk, Hp, Wp);
+    return hipGetLastError();
+}
+
 // conv_body's correction operands (S2SR_PREC_F16_HP): the trunk arrives as an fp16 pair (hi = dense
 // blocks 0..3, lo = the trunk-lo tensor); the split-operand kernel wants e4m3 planes of 32 channels
 // [lo*2^11 plane 0, plane 1, hi plane 0, plane 1] in the same padded geometry (halo pixels are zero
@@ -359,6 +472,32 @@ hipError_t launch_gather_windows(const uint8_t* d_img, int H, int W, const int32
     const size_t total = (size_t)T * wh * ww * 3;
     const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
     hipLaunchKernelGGL(gather_windows_kernel, dim3(grid), dim3(256), 0, st, d_img, H, W, d_rects, T, wh, ww, d_tiles);
+    return hipGetLastError();
+}
+
+// Scale 2 with an odd H or W: the windows are planned on the reflect-padded image (one row / column more); that row / column is
+// read by index (row H = row H - 2, as torch's 'reflect').
+__global__ void gather_windows_reflect_kernel(const uint8_t* __restrict__ img, int H, int W, const int32_t* __restrict__ rects,
+                                              int T, int wh, int ww, uint8_t* __restrict__ tiles) {
+    const size_t total = (size_t)T * wh * ww * 3;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % 3);
+        size_t r = i / 3;
+        const int x = (int)(r % ww);
+        r /= ww;
+        const int y = (int)(r % wh);
+        const int t = (int)(r / wh);
+        const int sy0 = rects[t * 4 + 0] + y, sx0 = rects[t * 4 + 2] + x;
+        const int sy = sy0 < H ? sy0 : 2 * H - 2 - sy0, sx = sx0 < W ? sx0 : 2 * W - 2 - sx0;
+        tiles[i] = img[((size_t)sy * W + sx) * 3 + c];
+    }
+}
+
+hipError_t launch_gather_windows_reflect(const uint8_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
+                                         uint8_t* d_tiles, hipStream_t st) {
+    const size_t total = (size_t)T * wh * ww * 3;
+    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+    hipLaunchKernelGGL(gather_windows_reflect_kernel, dim3(grid), dim3(256), 0, st, d_img, H, W, d_rects, T, wh, ww, d_tiles);
     return hipGetLastError();
 }
 

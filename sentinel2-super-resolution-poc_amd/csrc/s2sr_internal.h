@@ -248,11 +248,21 @@ hipError_t launch_pack_u8(const uint8_t* d_tiles, int N, int H, int W, char* blk
 hipError_t launch_pack_u8_mosaic(const uint8_t* d_tiles, int B, int h, int w, int kx, int ky, char* blk, int Hp, int Wp, hipStream_t st);
 hipError_t launch_pack_f32_nchw(const float* d_x, int N, int C, int H, int W, float scale, char* blk, int NB,
                                 int Hp, int Wp, hipStream_t st);
+// scale 2 (RealESRGAN_x2plus): the same three with pixel_unshuffle(x, 2) -- full-resolution input, plane of the h x w trunk grid,
+// channels 0..11 in torch's order, 12..15 zero.  pack_u8_unshuffle: images of H x W as stored (H = 2h, or 2h - 1 with the reflect
+// row read by index; likewise W); the mosaic form takes windows of 2h x 2w; the f32 form [N,3,2h,2w]
+hipError_t launch_pack_u8_unshuffle(const uint8_t* d_img, int N, int H, int W, int h, int w, char* blk, int Hp, int Wp, hipStream_t st);
+hipError_t launch_pack_u8_unshuffle_mosaic(const uint8_t* d_tiles, int B, int h, int w, int kx, int ky, char* blk, int Hp, int Wp,
+                                           hipStream_t st);
+hipError_t launch_pack_f32_nchw_unshuffle(const float* d_x, int N, int h, int w, float scale, char* blk, int Hp, int Wp, hipStream_t st);
 hipError_t launch_trunk_to_fp8(const char* hi, size_t hi_img, const char* lo, size_t lo_img, int lo_e4m3_exp, int N, int Hp, int Wp, char* out,
                                hipStream_t st);
 hipError_t launch_swap_rb_u8(const uint8_t* d_in, size_t npx, uint8_t* d_out, hipStream_t st);
 hipError_t launch_gather_windows(const uint8_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
                                  uint8_t* d_tiles, hipStream_t st);
+// ... windows of the reflect-padded image (scale 2, odd H or W): row H reads row H - 2, column W column W - 2
+hipError_t launch_gather_windows_reflect(const uint8_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
+                                         uint8_t* d_tiles, hipStream_t st);
 hipError_t launch_stitch_u8(const uint8_t* d_tiles, int tilesX, int oth, int otw, const int32_t* d_rowmap,
                             const int32_t* d_colmap, int OH, int OW, uint8_t* d_out, hipStream_t st);
 hipError_t launch_stitch_f32(const float* d_tiles /*[T,3,oth,otw]*/, int tilesX, int oth, int otw, const int32_t* d_rowmap,

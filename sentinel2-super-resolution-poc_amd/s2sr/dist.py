@@ -87,6 +87,7 @@ class BackendBase:
     `stitch` (and `postprocess`); the rest have defaults in terms of those, which the CPU stand-in of the tests uses
     and `NativeBackend` replaces with calls that neither allocate nor copy more than they must."""
     device = torch.device("cpu")
+    scale = 4          # output / input size of the backend's net; enhance_distributed runs scale 4 only
 
     # -- streams (no-ops on the CPU) ---------------------------------------------------------
     def comm_stream(self):
@@ -147,6 +148,7 @@ class NativeBackend(BackendBase):
 
     def __init__(self, engine: native.Engine, device_index: int):
         self.engine = engine
+        self.scale = engine.scale
         self.device = torch.device("cuda", device_index)
         self._comm = None
 
@@ -287,7 +289,11 @@ def enhance_distributed(backend, img: np.ndarray, tile: int = 256, pad: int = 10
     channel order as a flag.  CLAHE's 8x8 grid is image-global (wow_sr.py:191-192), so the post-process cannot run per window: on
     the consuming rank(s) every stitched band is counted into the histograms as it completes (communication stream, under the
     remaining compute), the LUTs are built behind the last band, and the mosaic is finished and copied out in row bands.
-    stats: optional dict that receives the chunk plan and band count of this call."""
+    stats: optional dict that receives the chunk plan and band count of this call.
+    Scale 4 only: a backend of another scale (RealESRGAN_x2plus) raises ValueError -- run it on one GPU (RealESRGAN.enhance)."""
+    if backend.scale != 4:
+        raise ValueError(f"enhance_distributed runs scale-4 nets only; this backend's scale is {backend.scale} "
+                         "(RealESRGAN_x2plus runs on one GPU)")
     world, rank = dist.get_world_size(), dist.get_rank()
     H, W, _ = img.shape
     dev = backend.device

@@ -106,6 +106,7 @@ _PROTOS = {
     "s2sr_host_free": (C.c_int, [C.c_void_p]),
     "s2sr_load_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "s2sr_expected_blob_floats": (C.c_size_t, [C.c_int32]),
+    "s2sr_expected_blob_floats_scale": (C.c_size_t, [C.c_int32, C.c_int32]),
     "s2sr_load_weights_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "s2sr_calibrate_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32)]),
@@ -451,12 +452,14 @@ pinned_pool = _PinnedPool()
 class Engine:
     """One native handle == one GPU.  Thread-safe (the library serialises calls per handle)."""
 
-    def __init__(self, num_block: int = 23, precision: int = PREC_F16, device: int = 0, group: int = 0):
+    def __init__(self, num_block: int = 23, precision: int = PREC_F16, device: int = 0, group: int = 0, scale: int = 4):
+        """scale 4, or 2 = RealESRGAN_x2plus (include/s2sr.h s2sr_config.scale): every output is `scale` x the input."""
         self._lib = load_library()
         self._h = C.c_void_p()
         self.num_block = num_block
         self.precision, self.group = precision, group
-        cfg = _Config(num_block, 64, 32, 4, precision, device, group, 0)
+        self.scale = int(scale)
+        cfg = _Config(num_block, 64, 32, self.scale, precision, device, group, 0)
         rc = self._lib.s2sr_create(C.byref(cfg), C.byref(self._h))
         if rc:
             msg = self._lib.s2sr_last_error(None)
@@ -495,7 +498,7 @@ class Engine:
 
     def load_state_dict(self, sd):
         from .weights import flatten_state_dict
-        self.load_blob(flatten_state_dict(sd, self.num_block))
+        self.load_blob(flatten_state_dict(sd, self.num_block, scale=self.scale))
 
     def calibrate_fp8(self, tiles: np.ndarray, headroom: float = 2.0) -> tuple:
         """PREC_FP8 engines: set the trunk's activation scales from representative tiles -> (x_exp, g_exp)."""
@@ -511,7 +514,8 @@ class Engine:
         tiles = np.ascontiguousarray(tiles, dtype=np.uint8)
         B, h, w, c = tiles.shape
         assert c == 3
-        out = pinned_pool.empty((B, 4 * h, 4 * w, 3), np.uint8)
+        S = self.scale
+        out = pinned_pool.empty((B, S * h, S * w, 3), np.uint8)
         self._check(self._lib.s2sr_forward_batch_u8(self._h, _ptr(tiles), B, h, w, _ptr(out)), "s2sr_forward_batch_u8")
         return out
 
@@ -524,7 +528,7 @@ class Engine:
         x = np.ascontiguousarray(x, dtype=np.float32)
         N, c, H, W = x.shape
         assert c == 3
-        y = np.empty((N, 3, 4 * H, 4 * W), dtype=np.float32)
+        y = np.empty((N, 3, self.scale * H, self.scale * W), dtype=np.float32)
         self._check(self._lib.s2sr_forward_f32(self._h, _ptr(x), N, H, W, _ptr(y)), "s2sr_forward_f32")
         return y
 
@@ -532,7 +536,7 @@ class Engine:
         img = np.ascontiguousarray(img, dtype=np.uint8)
         H, W, c = img.shape
         assert c == 3
-        out = pinned_pool.empty((4 * H, 4 * W, 3), np.uint8)
+        out = pinned_pool.empty((self.scale * H, self.scale * W, 3), np.uint8)
         self._check(self._lib.s2sr_enhance_u8(self._h, _ptr(img), H, W, tile, pad, _ptr(out)), "s2sr_enhance_u8")
         return out
 
@@ -541,7 +545,7 @@ class Engine:
         rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
         H, W, c = rgb.shape
         assert c == 3
-        out = pinned_pool.empty((4 * H, 4 * W, 3), np.uint8)
+        out = pinned_pool.empty((self.scale * H, self.scale * W, 3), np.uint8)
         self._check(self._lib.s2sr_enhance_job_u8(self._h, _ptr(rgb), H, W, tile, pad, C.byref(prm) if prm is not None else None, _ptr(out)),
                     "s2sr_enhance_job_u8")
         return out
@@ -549,14 +553,14 @@ class Engine:
     def enhance_f32(self, img: np.ndarray, tile: int = 256, pad: int = 10) -> np.ndarray:
         img = np.ascontiguousarray(img, dtype=np.uint8)
         H, W, c = img.shape
-        out = np.empty((4 * H, 4 * W, 3), dtype=np.float32)
+        out = np.empty((self.scale * H, self.scale * W, 3), dtype=np.float32)
         self._check(self._lib.s2sr_enhance_f32(self._h, _ptr(img), H, W, tile, pad, _ptr(out)), "s2sr_enhance_f32")
         return out
 
     def tile_process_f32(self, img: np.ndarray, tile: int = 256, pad: int = 10) -> np.ndarray:
         img = np.ascontiguousarray(img, dtype=np.uint8)
         H, W, c = img.shape
-        out = np.empty((4 * H, 4 * W, 3), dtype=np.float32)
+        out = np.empty((self.scale * H, self.scale * W, 3), dtype=np.float32)
         self._check(self._lib.s2sr_tile_process_f32(self._h, _ptr(img), H, W, tile, pad, _ptr(out)),
                     "s2sr_tile_process_f32")
         return out
@@ -572,7 +576,7 @@ class Engine:
                     "s2sr_stitch_windows_u8_dev")
 
     def stitch_rows_u8_dev(self, d_tiles: int, H: int, W: int, tile: int, pad: int, oy0: int, oy1: int, d_out: int, stream: int = 0):
-        """Output rows [oy0, oy1) of the paste; d_out is the whole [4H,4W,3] image."""
+        """Output rows [oy0, oy1) of the paste; d_out is the whole [S H, S W, 3] image (S = self.scale)."""
         self._check(self._lib.s2sr_stitch_rows_u8_dev(self._h, d_tiles, H, W, tile, pad, oy0, oy1, d_out, C.c_void_p(stream)),
                     "s2sr_stitch_rows_u8_dev")
 
@@ -804,8 +808,9 @@ def _debug_forward_taps(self, tiles=None, x=None, job_windows=0):
             ch, k = TAP_SHAPE[name]
             taps[name] = np.zeros((t.n, ch, t.Hp[k], t.Wp[k]), np.float32)
             t.tap[i] = taps[name].ctypes.data
-    out_f32 = np.zeros((B, 3, 4 * th, 4 * tw), np.float32)
-    out_u8 = np.zeros((B, 4 * th, 4 * tw, 3), np.uint8)
+    S = self.scale
+    out_f32 = np.zeros((B, 3, S * th, S * tw), np.float32)
+    out_u8 = np.zeros((B, S * th, S * tw, 3), np.uint8)
     t.out_f32, t.out_u8 = out_f32.ctypes.data, out_u8.ctypes.data
     call()
     return geo, taps, out_f32, out_u8

@@ -29,7 +29,17 @@ NUM_GROW = 32
 MODEL_TABLE = {
     "realesrgan_x4": {"scale": 4, "channels": 64, "blocks": 23, "num_in_ch": 3},
     "realesrgan_anime": {"scale": 4, "channels": 64, "blocks": 6, "num_in_ch": 3},
+    # RealESRGAN_x2plus: basicsr RRDBNet(num_in_ch=3, scale=2) = pixel_unshuffle(x, 2), a 12-channel conv_first, then the x4 body
+    # and tail on the half grid.  Not in the drop-in's MODELS (the reference's table); app.cnn_super_resolution.EXTRA_MODELS
+    "realesrgan_x2plus": {"scale": 2, "channels": 64, "blocks": 23, "num_in_ch": 3},
 }
+
+
+def first_conv_cin(scale: int) -> int:
+    """Input channels of conv_first: 3, or 12 at scale 2 (the channels of pixel_unshuffle(x, 2))."""
+    if scale not in (2, 4):
+        raise ValueError(f"scale {scale}: the native path runs scale 4 and RealESRGAN_x2plus (scale 2)")
+    return 12 if scale == 2 else 3
 
 
 def conv_specs(num_block: int, num_feat: int = NUM_FEAT, num_grow: int = NUM_GROW,
@@ -54,8 +64,8 @@ def conv_specs(num_block: int, num_feat: int = NUM_FEAT, num_grow: int = NUM_GRO
     return specs
 
 
-def num_params(num_block: int) -> int:
-    return sum(ci * co * 9 + co for _, ci, co, _ in conv_specs(num_block))
+def num_params(num_block: int, scale: int = 4) -> int:
+    return sum(ci * co * 9 + co for _, ci, co, _ in conv_specs(num_block, num_in_ch=first_conv_cin(scale)))
 
 
 # ----------------------------------------------------------------------------------------
@@ -84,7 +94,7 @@ def _uniform(seed: int, start: int, count: int) -> np.ndarray:
 
 
 def synthetic_state_dict(num_block: int = 23, seed: int = 0, body_gain: float = 0.3,
-                         other_gain: float = 1.0, bias_amp: float = 0.01
+                         other_gain: float = 1.0, bias_amp: float = 0.01, scale: int = 4
                          ) -> "OrderedDict[str, np.ndarray]":
     """Seeded weights with RealESRGAN shapes (numpy fp32, state-dict key order).
 
@@ -92,10 +102,11 @@ def synthetic_state_dict(num_block: int = 23, seed: int = 0, body_gain: float = 
     (0.3 -- mirrors ESRGAN's scaled-down residual-branch init), the rest `other_gain`;
     biases ~ U(-bias_amp, bias_amp).  One contiguous counter stream, tensors consumed in
     `conv_specs` order (weight then bias), so any prefix of the net is reproducible.
+    scale=2: RealESRGAN_x2plus shapes (conv_first.weight [64, 12, 3, 3]; the stream runs on from there).
     """
     sd: "OrderedDict[str, np.ndarray]" = OrderedDict()
     pos = 0
-    for name, cin, cout, is_body in conv_specs(num_block):
+    for name, cin, cout, is_body in conv_specs(num_block, num_in_ch=first_conv_cin(scale)):
         a = (body_gain if is_body else other_gain) * np.sqrt(1.0 / (9.0 * cin))
         n_w = cout * cin * 9
         sd[name + ".weight"] = (_uniform(seed, pos, n_w) * a).astype(np.float32).reshape(cout, cin, 3, 3)
@@ -120,15 +131,24 @@ def select_params(obj):
     return obj
 
 
-def flatten_state_dict(sd: Dict[str, "np.ndarray"], num_block: int | None = None) -> np.ndarray:
+def infer_scale(sd) -> int:
+    """2 when conv_first reads 12 channels (RealESRGAN_x2plus), else 4."""
+    w = sd.get("conv_first.weight")
+    return 2 if w is not None and len(w.shape) == 4 and w.shape[1] == 12 else 4
+
+
+def flatten_state_dict(sd: Dict[str, "np.ndarray"], num_block: int | None = None, scale: int | None = None) -> np.ndarray:
     """State-dict (numpy arrays or torch tensors) -> the flat fp32 blob of the C ABI.
 
     Raises KeyError / ValueError on missing, unexpected or mis-shaped tensors -- the same
     failures `load_state_dict(strict=True)` reports (reference cnn_super_resolution.py:211).
+    `scale` (None: from conv_first's shape) picks the layout: 2 = RealESRGAN_x2plus (conv_first 12 -> 64).
     """
     if num_block is None:
         num_block = infer_num_block(sd.keys())
-    specs = conv_specs(num_block)
+    if scale is None:
+        scale = infer_scale(sd)
+    specs = conv_specs(num_block, num_in_ch=first_conv_cin(scale))
     expected = {p + s for p, _, _, _ in specs for s in (".weight", ".bias")}
     missing = sorted(expected - set(sd.keys()))
     unexpected = sorted(set(sd.keys()) - expected)
