@@ -1,5 +1,5 @@
 /*
- * s2sr.h -- C ABI of libs2sr.so, the MI355X (gfx950) Real-ESRGAN x4 (and x2plus) inference path.
+ * s2sr.h -- C ABI of libs2sr.so, the MI355X (gfx950) Real-ESRGAN x4 (and x2plus, and SRVGGNetCompact x4) inference path.
  *
  * The reference (fieldin/sentinel2-super-resolution-poc) has no FFI layer: its seam is the
  * Python class `RealESRGAN` (server/app/cnn_super_resolution.py:161-280) plus the free
@@ -47,6 +47,16 @@ extern "C" {
                             * BASELINE.json configs[4] (the /api/sr variant).  NOT within the 1e-3 tolerance: e4m3 keeps
                             * 3 mantissa bits; measured max-abs in tests/test_gpu_net.py (test_fp8_mode_*)             */
 
+/* network family (s2sr_config.arch) */
+#define S2SR_ARCH_RRDB    0   /* RRDBNet: realesrgan_x4, realesrgan_anime, RealESRGAN_x2plus */
+#define S2SR_ARCH_COMPACT 1   /* SRVGGNetCompact(num_feat=64, num_conv, upscale=4, act_type="prelu"): realesr-general-x4v3,
+                               * realesr-general-wdn-x4v3 (num_conv 32), realesr-animevideov3 (16):
+                               *   h = PReLU(conv3x3(x, 3->64)); num_conv x h = PReLU(conv3x3(h, 64->64)); y = conv3x3(h, 64->48);
+                               *   out = pixel_shuffle(y, 4) + nearest_upsample(x, 4)
+                               * Arithmetic: fp16 operands, fp32 accumulate, fp16 activations between layers, fp32 bias / slope /
+                               * base add.  S2SR_PREC_F16 and S2SR_PREC_F16_HP run this SAME arithmetic on this arch (there is no
+                               * split-operand form of it); S2SR_PREC_FP8 is S2SR_E_INVALID (s2sr_create, s2sr_calibrate_fp8). */
+
 typedef struct s2sr_handle s2sr_handle;
 
 /* Mirrors the constructor arguments of the reference net
@@ -66,7 +76,9 @@ typedef struct s2sr_config {
     int32_t precision;   /* S2SR_PREC_* */
     int32_t device;      /* HIP device ordinal */
     int32_t group;       /* images pushed through the trunk together (0 = default) */
-    int32_t reserved;
+    int32_t arch;        /* S2SR_ARCH_* (the field was `reserved`: callers that zeroed it get S2SR_ARCH_RRDB; any other value is
+                          * S2SR_E_INVALID).  S2SR_ARCH_COMPACT: num_block carries num_conv (16 or 32), num_feat 64, num_grow is
+                          * ignored, scale 4 only. */
 } s2sr_config;
 
 /* One window of RealESRGAN._tile_process (cnn_super_resolution.py:244-278). */
@@ -121,6 +133,12 @@ size_t s2sr_expected_blob_floats(int32_t num_block);
 /* ... of a net of `scale` 4 or 2 (scale 2: conv_first 12 -> 64, 5184 floats more); 0 for any other scale.  A blob of the other
  * scale is S2SR_E_BADBLOB in s2sr_load_weights. */
 size_t s2sr_expected_blob_floats_scale(int32_t num_block, int32_t scale);
+/* ... of the net a config describes, either arch; 0 for a config s2sr_create would refuse for its shape.  S2SR_ARCH_COMPACT: the
+ * blob is the state dict's flat `body` list in order, fp32 -- body.0.weight [64][3][3][3], body.0.bias [64], body.1.weight (64
+ * PReLU slopes), then conv weight / bias / slopes alternating, last body.{2 num_conv + 2}.weight [48][64][3][3] and .bias [48]
+ * (1,213,296 floats at num_conv 32).  The blob stays in state-dict order: the row permutation of the last conv that the
+ * pixel-shuffle epilogue wants is a property of the packed weights only. */
+size_t s2sr_expected_blob_floats_cfg(const s2sr_config* cfg);
 /* same blob, DEVICE-resident (e.g. the receive buffer of the RCCL weight broadcast); `stream`
  * is the stream the blob was produced on (a hipStream_t; NULL = default stream).  Returns when loaded.  The RDB convs are
  * repacked on the device; only the six head/tail convs' weights (0.9 MB) pass through host memory. */
@@ -479,6 +497,27 @@ int  s2sr_debug_mfma_ceiling(s2sr_handle* h, int32_t mode, int32_t stages, int32
  * *timeouts: dependency waits that ran into their bound (must be 0 for the timing to mean anything). */
 int  s2sr_debug_rdb_persistent(s2sr_handle* h, int32_t variant, int32_t grid, int32_t P, int32_t rdbs, int32_t launches, double* flop_per_launch,
                                float* ms_total, int32_t* timeouts, int32_t* mismatches);
+
+/* test hook (S2SR_ARCH_COMPACT handles only; the RRDB-only hooks above -- s2sr_debug_conv_trunk, s2sr_debug_forward_taps,
+ * s2sr_debug_trunk_taps, s2sr_debug_rdb_persistent -- answer S2SR_E_INVALID on such a handle): ONE batch through the production
+ * forward exactly as s2sr_debug_forward_taps runs it (same input rules and refusals, graphs off), with the fp16 activation
+ * copied out after the layers of the caller's choice and decoded to fp32 over the PADDED extent [n, 64, Hp, Wp] of the launch
+ * images.  Layer 0 is the first conv (after its PReLU), layer k in 1..num_conv body conv k (after its PReLU).  The geometry
+ * fields are always filled; the batch runs only when at least one buffer is given. */
+#define S2SR_COMPACT_TAPS_MAX 8
+typedef struct s2sr_debug_compact_fields {
+    int32_t nlayers;                        /* in: entries of layers / act in use (<= S2SR_COMPACT_TAPS_MAX) */
+    int32_t layers[S2SR_COMPACT_TAPS_MAX];  /* in: ascending, each in [0, num_conv] */
+    int32_t n, H, W, Hp, Wp;                /* out: launch images, live extent of one, padded plane dims */
+    int32_t mos_kx, mos_ky, mos_wh, mos_ww, mos_count;   /* out: window mosaic of the launch (all 0: one window per image) */
+    int32_t reserved[4];
+    float* act[S2SR_COMPACT_TAPS_MAX];      /* in (NULL: skip): [n][64][Hp][Wp] */
+    float* p0;                              /* in (NULL: skip): the packed input, [n][16][Hp][Wp] (channels 0..2 = exact 0..255) */
+    float* out_f32;                         /* in: [B, 3, 4th, 4tw] */
+    uint8_t* out_u8;                        /* in: [B, 4th, 4tw, 3] */
+} s2sr_debug_compact_fields;
+int  s2sr_debug_compact_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw,
+                             int32_t job_windows, s2sr_debug_compact_fields* t);
 
 #ifdef __cplusplus
 }

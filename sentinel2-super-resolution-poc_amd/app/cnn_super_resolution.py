@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 from s2sr import native
-from s2sr.weights import MODEL_TABLE, conv_specs, first_conv_cin, flatten_state_dict, select_params
+from s2sr.weights import MODEL_TABLE, compact_specs, conv_specs, dni, first_conv_cin, flatten_state_dict, select_params
 
 # Model table -- keys and fields as in the reference (:28-45)
 MODELS = {
@@ -52,7 +52,25 @@ EXTRA_MODELS = {
         "description": "Quick upscaling (less hallucination, 2x upscale)",
         **MODEL_TABLE["realesrgan_x2plus"],
     },
+    # SRVGGNetCompact ("arch": "compact"): Real-ESRGAN's small x4 models, 2.42 MFLOP per input pixel against RRDBNet-23's 35.8.
+    # realesr_general_x4v3 takes RealESRGAN(denoise_strength=s): dni(x4v3, wdn_x4v3, s), upstream's interpolation.
+    "realesr_general_x4v3": {
+        "url": "https://github.com/xinntao/Real-ESRGAN/releases/download/v0.2.5.0/realesr-general-x4v3.pth",
+        "description": "General scenes, small and fast (SRVGGNetCompact, 1.2 M parameters)",
+        **MODEL_TABLE["realesr_general_x4v3"],
+    },
+    "realesr_general_wdn_x4v3": {
+        "url": "https://github.com/xinntao/Real-ESRGAN/releases/download/v0.2.5.0/realesr-general-wdn-x4v3.pth",
+        "description": "General scenes, small and fast, with denoising (the other end of denoise_strength)",
+        **MODEL_TABLE["realesr_general_wdn_x4v3"],
+    },
+    "realesr_animevideov3": {
+        "url": "https://github.com/xinntao/Real-ESRGAN/releases/download/v0.2.5.0/realesr-animevideov3.pth",
+        "description": "Anime video, smallest (SRVGGNetCompact, 16 convs)",
+        **MODEL_TABLE["realesr_animevideov3"],
+    },
 }
+DNI_MODEL, DNI_WDN_MODEL = "realesr_general_x4v3", "realesr_general_wdn_x4v3"
 
 
 def model_config(model_name: str) -> Optional[dict]:
@@ -112,6 +130,7 @@ class RRDBNet(nn.Module):
             raise ValueError("the native path is built for num_in_ch=3 (or 12: RealESRGAN_x2plus), num_out_ch=3, num_feat=64, "
                              "num_grow_ch=32, scale=4 (the shapes in MODELS and EXTRA_MODELS)")
         self.scale = 2 if num_in_ch == 12 else 4
+        self.arch = "rrdb"
         self.num_block = num_block
         for name, cin, cout, _ in conv_specs(num_block, num_in_ch=num_in_ch):
             _attach(self, name, nn.Conv2d(cin, cout, 3, 1, 1))
@@ -138,7 +157,7 @@ class RRDBNet(nn.Module):
         if self._engine is not None and self._engine_key is not None and self._engine_key[1:] == (device_index, ver, prec):
             return self._engine
         fp = self._fingerprint()
-        self._engine = _engine_for(self.state_dict(), self.num_block, device_index, fp, self.scale)
+        self._engine = _engine_for(self.state_dict(), self.num_block, device_index, fp, self.scale, self.arch)
         self._engine_key = (fp, device_index, ver, prec)
         return self._engine
 
@@ -151,26 +170,56 @@ class RRDBNet(nn.Module):
         return torch.from_numpy(y).to(dev)
 
 
+class SRVGGNetCompact(nn.Module):
+    """Shape-compatible with Real-ESRGAN's SRVGGNetCompact(num_in_ch=3, num_out_ch=3, num_feat=64, num_conv, upscale=4,
+    act_type="prelu"): a flat `body` ModuleList of conv / PReLU(64) alternating and the last conv, so
+    `load_state_dict(strict=True)` accepts realesr-general-x4v3 / -wdn-x4v3 / realesr-animevideov3 checkpoints.  It holds
+    weights only; `forward` runs on the GPU engine (pixel-shuffle and the nearest-x4 base add are in the last conv's stores)."""
+
+    def __init__(self, num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=32, upscale=4, act_type="prelu"):
+        super().__init__()
+        if (num_in_ch, num_out_ch, num_feat, upscale, act_type) != (3, 3, 64, 4, "prelu") or num_conv not in (16, 32):
+            raise ValueError("the native path is built for SRVGGNetCompact(num_in_ch=3, num_out_ch=3, num_feat=64, num_conv in "
+                             "{16, 32}, upscale=4, act_type='prelu')")
+        self.scale = 4
+        self.arch = "compact"
+        self.num_block = num_conv          # what native.Engine carries in num_block
+        self.body = nn.ModuleList()
+        for key, shape in compact_specs(num_conv):
+            if key.endswith(".bias"):
+                continue
+            self.body.append(nn.Conv2d(shape[1], shape[0], 3, 1, 1) if len(shape) == 4 else nn.PReLU(num_parameters=shape[0]))
+        self._engine: Optional[native.Engine] = None
+        self._engine_key = None
+
+    _fingerprint = RRDBNet._fingerprint
+    _version = RRDBNet._version
+    engine = RRDBNet.engine
+    forward = RRDBNet.forward
+
+
 _ENGINES: Dict[Tuple[str, int], native.Engine] = {}
 _ENGINES_LOCK = threading.Lock()
 _LOADED_MODELS: Dict[tuple, "RRDBNet"] = {}      # checkpoint file identity -> loaded parameter shell
 _MODELS_LOCK = threading.Lock()
 
 
-def _engine_for(state_dict, num_block: int, device_index: int, fingerprint: str, scale: int = 4) -> native.Engine:
+def _engine_for(state_dict, num_block: int, device_index: int, fingerprint: str, scale: int = 4, arch: str = "rrdb") -> native.Engine:
     """One native handle per (weights, scale, GPU), shared by every RealESRGAN object of the process."""
     with _ENGINES_LOCK:
-        key = (fingerprint, device_index, _precision_override() or os.environ.get("S2SR_PRECISION", "hp"), scale)
+        key = (fingerprint, device_index, _precision_override() or os.environ.get("S2SR_PRECISION", "hp"), scale, arch)
         eng = _ENGINES.get(key)
         if eng is None:
             # S2SR_PRECISION=fast trades the <=1e-4 parity of the default for ~14 % more throughput; =fp8 runs the RDB
             # trunk on e4m3 operands (BASELINE configs[4], ~1.5x, max-abs ~5e-3: outside the 1e-3 tolerance)
             prec = {"fast": native.PREC_F16, "fp8": native.PREC_FP8}.get(_precision_override() or
                                                                           os.environ.get("S2SR_PRECISION", "hp"), native.PREC_F16_HP)
+            if arch == "compact" and prec == native.PREC_FP8:
+                prec = native.PREC_F16      # the compact arch has one arithmetic (fp16 operands, fp32 accumulate); no fp8 form of it
             eng = native.Engine(num_block=num_block, device=device_index, precision=prec,
-                                group=int(os.environ.get("S2SR_GROUP", "0")), scale=scale)
-            eng.load_blob(flatten_state_dict(state_dict, num_block, scale=scale))
-            if prec == native.PREC_FP8 and not (os.environ.get("S2SR_FP8_XEXP") or os.environ.get("S2SR_FP8_GEXP")):
+                                group=int(os.environ.get("S2SR_GROUP", "0")), scale=scale, arch=arch)
+            eng.load_blob(flatten_state_dict(state_dict, num_block, scale=scale, arch=arch))
+            if arch == "rrdb" and prec == native.PREC_FP8 and not (os.environ.get("S2SR_FP8_XEXP") or os.environ.get("S2SR_FP8_GEXP")):
                 # activation scales of the fp8 trunk from data: a few imagery-like tiles through THIS checkpoint
                 from s2sr.synth import synthetic_tiles
                 eng.calibrate_fp8(synthetic_tiles(4, 64, seed=0), headroom=2.0)
@@ -239,7 +288,9 @@ class RealESRGAN:
     """Real-ESRGAN inference wrapper with the reference's interface (:161-280)."""
 
     def __init__(self, scale: int = 4, device: str = None, tile_size: int = 256, model_name: str = None,
-                 state_dict=None):
+                 state_dict=None, denoise_strength: Optional[float] = None):
+        """denoise_strength (realesr_general_x4v3 only, upstream's knob): s in [0, 1] loads realesr_general_x4v3.pth and
+        realesr_general_wdn_x4v3.pth and runs dni(x4v3, wdn, s) = s * x4v3 + (1 - s) * wdn: 1 = no denoising, 0 = the wdn model."""
         self.tile_size = tile_size
         self.tile_pad = 10
         self.device = _resolve_device(device)
@@ -252,6 +303,15 @@ class RealESRGAN:
             raise ValueError(f"Unknown model: {model_name}. Available: {list(MODELS.keys())}")
         self.scale = config["scale"]
         self.model_name = model_name
+        compact = config.get("arch") == "compact"
+        if denoise_strength is not None:
+            if model_name != DNI_MODEL:
+                raise ValueError(f"denoise_strength belongs to {DNI_MODEL} (interpolated with {DNI_WDN_MODEL}), not to {model_name}")
+            if not (0.0 <= float(denoise_strength) <= 1.0):
+                raise ValueError(f"denoise_strength {denoise_strength} outside [0, 1]")
+            if state_dict is not None:
+                raise ValueError("denoise_strength interpolates the two checkpoint files; it cannot be combined with state_dict=")
+        self.denoise_strength = None if denoise_strength is None else float(denoise_strength)
 
         # The reference builds the net and reads the 64 MB checkpoint in every job
         # (wow_sr.py:93-97, :164-215).  Here a checkpoint file that has not changed on disk
@@ -260,17 +320,27 @@ class RealESRGAN:
         if state_dict is None:
             weights_path = Path(download_weights(model_name))
             st = weights_path.stat()
-            cache_key = (str(weights_path.resolve()), st.st_mtime_ns, st.st_size, config["blocks"], config["scale"])
+            cache_key = (str(weights_path.resolve()), st.st_mtime_ns, st.st_size, config.get("blocks", config.get("num_conv")), config["scale"])
+            if self.denoise_strength is not None:
+                wdn_path = Path(download_weights(DNI_WDN_MODEL))
+                st2 = wdn_path.stat()
+                cache_key += (str(wdn_path.resolve()), st2.st_mtime_ns, st2.st_size, self.denoise_strength)
             with _MODELS_LOCK:
                 self.model = _LOADED_MODELS.get(cache_key)
         else:
             self.model = None
         if self.model is None:
             # RealESRGAN_x2plus: the reference class's RRDBNet(num_in_ch=12, scale=4) on the unshuffled image
-            self.model = RRDBNet(num_in_ch=first_conv_cin(self.scale), num_out_ch=3, num_feat=config["channels"],
-                                 num_block=config["blocks"], num_grow_ch=32, scale=4)
+            if compact:
+                self.model = SRVGGNetCompact(num_in_ch=3, num_out_ch=3, num_feat=config["channels"], num_conv=config["num_conv"],
+                                             upscale=config["scale"], act_type="prelu")
+            else:
+                self.model = RRDBNet(num_in_ch=first_conv_cin(self.scale), num_out_ch=3, num_feat=config["channels"],
+                                     num_block=config["blocks"], num_grow_ch=32, scale=4)
             if state_dict is None:
                 state_dict = select_params(torch.load(weights_path, map_location="cpu"))
+                if self.denoise_strength is not None:
+                    state_dict = dni(state_dict, select_params(torch.load(wdn_path, map_location="cpu")), self.denoise_strength)
             state_dict = {k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v) for k, v in state_dict.items()}
             self.model.load_state_dict(state_dict, strict=True)
             self.model.eval()

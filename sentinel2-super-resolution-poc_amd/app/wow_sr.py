@@ -42,7 +42,10 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
 
     model_display = {"realesrgan_x4": "Real-ESRGAN x4",
                      "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)",
-                     "realesrgan_x2plus": "Real-ESRGAN x2plus (5 m)"}.get(model, model)
+                     "realesrgan_x2plus": "Real-ESRGAN x2plus (5 m)",
+                     "realesr_general_x4v3": "Real-ESRGAN general-x4v3 (compact)",
+                     "realesr_general_wdn_x4v3": "Real-ESRGAN general-wdn-x4v3 (compact, denoising)",
+                     "realesr_animevideov3": "Real-ESRGAN animevideov3 (compact)"}.get(model, model)
     print(f"\nWOW Super-Resolution ({model_display} + Enhanced)\n   Input: {input_path}")
     input_path = Path(input_path)
     img, georef = rio.read_rgb_u8(input_path)           # u8 RGB (min-max normalised if >255, :67-73)

@@ -111,7 +111,7 @@ __device__ __forceinline__ float lrelu(float v) { return fmaxf(v, __fmul_rn(v, 0
 // them exactly: the ring keeps its R-2 stages in flight across patch boundaries.
 template <int EPI, int CT, int NP, int HPO>
 struct EpiStores {
-    static constexpr int value = (EPI == EPI_LRELU || EPI == EPI_BODY) ? CT * (HPO == 1 ? 4 : HPO == 2 ? 3 : 2) * NP
+    static constexpr int value = (EPI == EPI_LRELU || EPI == EPI_BODY || EPI == EPI_PRELU) ? CT * (HPO == 1 ? 4 : HPO == 2 ? 3 : 2) * NP
                                  : (EPI == EPI_FIRST)                  ? CT * 12 * NP
                                                                        : -1;   // LAST / DEBUG: data-dependent, stay conservative
 };
@@ -189,7 +189,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
     const uint32_t sblk = (uint32_t)p.sHp * p.sWp * 32;              // bytes between source blocks
     const size_t oblk = (size_t)p.Hp * p.Wp * 32;                    // bytes between output blocks
 
-    if (tid < CT * 32) ((float*)(smem + G::BIAS_OFF))[tid] = (EPI == EPI_FIRST) ? 0.f : p.bias[tid % (CTR * 32)];
+    if (tid < CT * 32) ((float*)(smem + G::BIAS_OFF))[tid] = (EPI == EPI_FIRST || EPI == EPI_CFIRST) ? 0.f : p.bias[tid % (CTR * 32)];
 
     // ---- per-lane source offsets of this wave's PW DMA slots (patch independent)
     uint32_t loff[G::PW];
@@ -247,6 +247,22 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
     const uint32_t aaddr = G::PLANE + lane * 16;
 
     char* const trash = p.trash + (size_t)(tid & 255) * 16;   // where out-of-image lanes park their stores
+
+    // PReLU epilogues (SRVGGNetCompact): the slopes of this lane's 16 output channels per cout tile -- they depend on the
+    // half-wave only -- are fetched once, ahead of the ring loop (a load inside it would drain the ring, see the header);
+    // the first conv's bias likewise (it is added after the 1/255 scale, so it cannot ride in the accumulator)
+    float slp[CT][16], fbias[CT][16];
+    if (EPI == EPI_PRELU || EPI == EPI_CFIRST) {
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    slp[ct][4 * g + i] = p.slope[ct * 32 + 8 * g + 4 * hh + i];
+                    if (EPI == EPI_CFIRST) fbias[ct][4 * g + i] = p.bias[ct * 32 + 8 * g + 4 * hh + i];
+                }
+    }
 
     f32x16 acc[CT][NP];
     auto init_acc = [&]() __attribute__((always_inline)) {
@@ -513,8 +529,54 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
 #pragma unroll
         for (int np = 0; np < NP; ++np) {
             const int y = y0 + wave * NP + np;
+            float base3[3] = {0.f, 0.f, 0.f};
+            if (EPI == EPI_CLAST) {
+                // nearest-x4 of the input is "this LR pixel's colour under all 16 sub-pixels": read from the packed input (exact
+                // 0..255 in fp16), scaled in fp32 as the first conv scales it
+                const f16x4 bx = *(const f16x4*)(p.src_lo + (size_t)n * p.lo_img + opix[np] * 32);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) base3[c] = __fmul_rn((float)bx[c], p.in_scale);
+            }
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) {
+                if (EPI == EPI_CLAST) {
+                    // pixel-shuffle tail.  The host put the 48 output channels in rows such that this lane's accumulators of tile
+                    // ct are [colour c][dx] (register 4c + dx) of HR row 4y + dy, dy = 2 hh + ct, columns 4x .. 4x+3 -- per colour
+                    // 16 contiguous fp32 bytes (a half-wave: 512), per row 12 contiguous u8 bytes (a half-wave: 384)
+                    size_t oimg = (size_t)n;
+                    int oy = y, ox = x, oH = p.H, oW = p.W;
+                    bool live = ok[np];
+                    if (p.mos_py) {
+                        const int wy = y / p.mos_py, wx = x / p.mos_px;
+                        const int t = (n * p.mos_ky + wy) * p.mos_kx + wx;
+                        live = live && t < p.mos_count;
+                        oimg = (size_t)t; oy = y - wy * p.mos_py; ox = x - wx * p.mos_px; oH = p.mos_ry; oW = p.mos_rx;
+                    }
+                    const size_t H4 = (size_t)oH * 4, W4 = (size_t)oW * 4;
+                    const size_t hy = (size_t)oy * 4 + (size_t)(2 * hh + ct), hx = (size_t)ox * 4;
+                    uint32_t w3[3] = {0u, 0u, 0u};
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        f32x4 o;
+#pragma unroll
+                        for (int dx = 0; dx < 4; ++dx) {
+                            o[dx] = __fadd_rn(acc[ct][np][4 * c + dx], base3[c]);
+                            // (out*255).clip(0,255).astype(uint8): truncation, as EPI_LAST
+                            const float q = fminf(fmaxf(__fmul_rn(o[dx], 255.0f), 0.f), 255.f);
+                            const int k = dx * 3 + c;
+                            w3[k >> 2] |= (uint32_t)(int)q << (8 * (k & 3));
+                        }
+                        if (p.out_f32) *(f32x4*)(live ? (char*)(p.out_f32 + ((oimg * 3 + c) * H4 + hy) * W4 + hx) : trash) = o;
+                    }
+                    if (p.out_u8) {
+                        typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
+                        typedef u32x3 u32x3a __attribute__((aligned(4)));
+                        u32x3 pk;
+                        pk[0] = w3[0]; pk[1] = w3[1]; pk[2] = w3[2];
+                        *(u32x3a*)(live ? (char*)(p.out_u8 + ((oimg * H4 + hy) * W4 + hx) * 3) : trash) = pk;
+                    }
+                    continue;
+                }
                 const int rc = ct % CTR;                                   // real cout tile
                 const size_t qoff = PH >= 0 ? (size_t)(ct / CTR) * 32 : 0;   // sub-pixel form: the pixel to the right
                 u32x2 hpk[4];   // fp16 x4 per g (hi / plain output)
@@ -539,6 +601,15 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
                     } else if (EPI == EPI_BODY) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) v[i] = __fadd_rn(res0[ct][np][g][i], v[i]);
+                    } else if (EPI == EPI_PRELU) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) v[i] = v[i] >= 0.f ? v[i] : __fmul_rn(slp[ct][4 * g + i], v[i]);
+                    } else if (EPI == EPI_CFIRST) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const float u = __fadd_rn(__fmul_rn(v[i], p.in_scale), fbias[ct][4 * g + i]);
+                            v[i] = u >= 0.f ? u : __fmul_rn(slp[ct][4 * g + i], u);
+                        }
                     }
                     if (EPI == EPI_LAST || EPI == EPI_DEBUG) {
                         // where the pixel goes: image n of [N, H, W], or -- window mosaic -- window (n*ky + wy)*kx + wx of [count, ry, rx]
@@ -935,6 +1006,10 @@ hipError_t launch_conv(const ConvParams& p, int ct, int epi, bool up, bool lo_ou
         if (epi == EPI_LRELU) return launch_w<2, EPI_LRELU, false>(p, st);
         if (epi == EPI_FIRST && !up) return launch_w<2, EPI_FIRST, false>(p, st);
         if (epi == EPI_BODY && !up) return launch_w<2, EPI_BODY, false>(p, st);
+        // SRVGGNetCompact: the same 8-wave, 16x32-patch form with the PReLU / pixel-shuffle epilogues
+        if (epi == EPI_PRELU && !up && p.slope) return launch_w<2, EPI_PRELU, false>(p, st);
+        if (epi == EPI_CFIRST && !up && p.slope) return launch_w<2, EPI_CFIRST, false>(p, st);
+        if (epi == EPI_CLAST && !up && p.src_lo) return launch_w<2, EPI_CLAST, false>(p, st);
         if (epi == EPI_DEBUG) return up ? launch_w<2, EPI_DEBUG, true>(p, st) : launch_w<2, EPI_DEBUG, false>(p, st);
     }
     return hipErrorInvalidValue;
@@ -1006,6 +1081,12 @@ void pack_conv_weights(const float* w, int cin, int cout, int nseg, void* dst_ho
                             *d++ = lo ? (f16)(v - (float)hi) : hi;
                         }
     }
+}
+
+int compact_last_row_channel(int row) {
+    const int ct = row >> 5, r = row & 31, g = r >> 3, hh = (r >> 2) & 1, i = r & 3;   // row r of tile ct = accumulator 4g + i of half-wave hh
+    if (g == 3) return -1;
+    return g * 16 + (2 * hh + ct) * 4 + i;     // pixel_shuffle(., 4): channel c*16 + dy*4 + dx, c = g, dy = 2 hh + ct, dx = i
 }
 
 uint8_t f32_to_e4m3(float f) {

@@ -40,12 +40,14 @@ struct ConvW {
     bool f8trunk = false;
     int32_t* d_wscale = nullptr;
     bool pooled = false;                // d_wpack / d_wscale point into the handle's pools
+    float* d_slope = nullptr;           // SRVGGNetCompact: the 64 PReLU slopes behind this conv (in pool_b, next to the bias)
 };
 
 // kernel families for the HIP-event statistics
-enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_COUNT };
+enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_COUNT };
 const char* kFamName[F_COUNT] = {"pack_u8",   "conv_first", "rdb_conv1-4", "rdb_conv5",   "conv_body",
-                                 "conv_up",   "conv_hr",    "conv_last",   "postprocess", "misc"};
+                                 "conv_up",   "conv_hr",    "conv_last",   "postprocess", "misc",
+                                 "compact_first", "compact_body", "compact_last"};
 
 struct Workspace {
     int G = 0, H = 0, W = 0;   // capacity (images) and logical LR dims
@@ -108,6 +110,11 @@ struct GraphEntry {
 
 // s2sr_debug_trunk_taps while its batch runs: the RDB range whose fields run_net copies out (trunk_tap) and where the form
 // records of the range's conv launches go
+// s2sr_debug_compact_taps while its batch runs: run_net_compact copies the chosen layers' activations out
+struct CompactTap {
+    s2sr_debug_compact_fields* t = nullptr;
+};
+
 struct TrunkTap {
     int first = 0, count = 0;
     s2sr_debug_trunk_fields* t = nullptr;
@@ -122,6 +129,7 @@ struct s2sr_handle {
     // RealESRGAN_x2plus (cfg.scale 2) runs pixel_unshuffle(x, 2) and then the x4 net on the half grid.  Every entry takes input
     // sizes: the trunk (workspace, mosaic, launch groups, graphs) is input / unshuffle(), the output input * cfg.scale.
     int unshuffle() const { return cfg.scale == 2 ? 2 : 1; }
+    bool compact() const { return cfg.arch == S2SR_ARCH_COMPACT; }   // SRVGGNetCompact: cfg.num_block carries num_conv
     hipStream_t stream = nullptr;
     std::mutex mu;
     std::string err;
@@ -195,6 +203,7 @@ struct s2sr_handle {
     // read by s2sr_debug_forward_taps only
     struct TrunkRec { const char* hi = nullptr; uint64_t hi_img = 0; const char* lo = nullptr; uint64_t lo_img = 0; int lo_exp = -1; } trunk_rec;
     TrunkTap* ttap = nullptr;     // s2sr_debug_trunk_taps' batch is running (run_net taps the trunk at its RDB boundaries); null otherwise
+    CompactTap* ctap = nullptr;   // s2sr_debug_compact_taps' batch is running
 };
 
 namespace {
@@ -231,6 +240,14 @@ std::vector<ConvSpec> conv_specs(int num_block, int scale) {
     v.push_back({64, 64});   // conv_hr
     v.push_back({64, 3});    // conv_last
     return v;
+}
+
+// SRVGGNetCompact(num_feat 64, num_conv, upscale 4): floats of its flat `body` list (conv weight, conv bias, 64 slopes, ...)
+size_t compact_blob_floats(int num_conv) {
+    return (size_t)(3 * 64 * 9 + 64 + 64) + (size_t)num_conv * (64 * 64 * 9 + 64 + 64) + (size_t)(64 * 48 * 9 + 48);
+}
+size_t handle_blob_floats(const s2sr_handle* h) {
+    return h->compact() ? compact_blob_floats(h->cfg.num_block) : s2sr_expected_blob_floats_scale(h->cfg.num_block, h->cfg.scale);
 }
 
 void free_weights(s2sr_handle* h) {
@@ -369,6 +386,26 @@ int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mo
     }
     w.G = G; w.H = H; w.W = W; w.hp = hp; w.fp8 = fp8; w.mos_py = mos_py; w.mos_px = mos_px;
     w.Hp = padded(H); w.Wp = padded(W);
+    if (h->compact()) {
+        // SRVGGNetCompact: the packed input (1 block) and two 64-channel fp16 tensors (D[0], D[1]: 4 blocks each) that the
+        // layers ping-pong between -- 288 B per padded LR pixel; everything stays at input resolution
+        w.blk1 = (size_t)w.Hp * w.Wp * 32;
+        const size_t g = (size_t)G, bP0 = align256(g * w.blk1), bA = align256(g * 4 * w.blk1);
+        w.bytes = bP0 + 2 * bA;
+        const hipError_t em = dev_malloc(&w.base, w.bytes);
+        if (em != hipSuccess) {
+            (void)hipGetLastError();
+            const size_t want = w.bytes;
+            w = Workspace();
+            char b[200];
+            snprintf(b, sizeof b, "workspace of %.1f GB for %d images of %dx%d: %s", (double)want / 1e9, G, H, W, hipGetErrorString(em));
+            return fail(h, em == hipErrorOutOfMemory ? S2SR_E_CAPACITY : S2SR_E_HIP, b);
+        }
+        HIPCHK(h, fill_blocking(h, w.base, 0, w.bytes));   // the zero halos
+        ++h->ws_allocs;
+        w.P0 = w.base; w.D[0] = w.base + bP0; w.D[1] = w.base + bP0 + bA;
+        return S2SR_OK;
+    }
     w.Hp2 = padded(2 * H); w.Wp2 = padded(2 * W);
     w.Hp4 = padded(4 * H); w.Wp4 = padded(4 * W);
     w.blk1 = (size_t)w.Hp * w.Wp * 32; w.blk2 = (size_t)w.Hp2 * w.Wp2 * 32; w.blk4 = (size_t)w.Hp4 * w.Wp4 * 32;
@@ -583,7 +620,65 @@ int trunk_tap(s2sr_handle* h, hipStream_t st, int g) {
 // (:85-91, :103-107).  The torch.cat of the dense block is "the first k blocks of D[cur]",
 // never a copy; conv5 writes the next x into the other dense tensor because neighbouring
 // workgroups still read this one's x as halo.
+// SRVGGNetCompact: first conv, num_conv PReLU convs ping-ponging between D[0] and D[1], the last conv with the pixel-shuffle
+// tail.  Every launch works at input resolution (the x4 happens in the last conv's stores), on the 8-wave form of conv3x3.hip.
+int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f32, uint8_t* d_out_u8, const Mosaic& mo) {
+    Workspace& w = h->ws;
+    const int nc = h->cfg.num_block;
+    if ((int)h->convs.size() != nc + 2) return fail(h, S2SR_E_NOWEIGHTS, "compact weights are not loaded");
+    ConvParams b{};
+    b.N = n; b.H = H; b.W = W; b.Hp = w.Hp; b.Wp = w.Wp; b.sHp = w.Hp; b.sWp = w.Wp;
+    b.trash = h->d_trash; b.in_scale = 1.0f / 255.0f;
+    if (mo.on()) {
+        b.mos_py = mo.wh + 1; b.mos_ry = mo.wh; b.mos_px = mo.ww + 1; b.mos_rx = mo.ww;
+        b.mos_my = (uint32_t)(0x100000000ull / (uint32_t)b.mos_py) + 1u; b.mos_mx = (uint32_t)(0x100000000ull / (uint32_t)b.mos_px) + 1u;
+        b.mos_kx = mo.kx; b.mos_ky = mo.ky; b.mos_count = mo.count;
+    }
+    const double px = (double)n * H * W;
+    auto tap = [&](int layer, const char* act) -> int {       // s2sr_debug_compact_taps only
+        if (!h->ctap) return S2SR_OK;
+        s2sr_debug_compact_fields* t = h->ctap->t;
+        for (int k = 0; k < t->nlayers; ++k)
+            if (t->layers[k] == layer && t->act[k]) {
+                if (w.Hp != t->Hp || w.Wp != t->Wp) return fail(h, S2SR_E_INVALID, "compact taps: the workspace planes differ from the planned ones");
+                HIPCHK(h, hipStreamSynchronize(st));
+                if (int r = decode_f16_planes(h, t->act[k], act, 4 * w.blk1, n, 4, w.blk1)) return r;
+            }
+        return S2SR_OK;
+    };
+    auto launch = [&](int fam, const ConvW& cw, ConvParams p, int epi, double bytes) -> int {
+        p.wpack = cw.d_wpack; p.bias = cw.d_bias; p.slope = cw.d_slope; p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.seg_lo_mask = 0;
+        Scope sc(h, st, fam, 2.0 * 9.0 * cw.cin * cw.cout * px, bytes);
+        HIPCHK(h, launch_conv(p, cw.ct, epi, false, false, st, false));
+        return S2SR_OK;
+    };
+    int rc, cur = 0;
+    {   // first conv 3 -> 64 on the exact 0..255 input, x 1/255 in the epilogue
+        ConvParams p = b;
+        p.src = w.P0; p.src_img = w.blk1; p.dst = w.D[0]; p.dst_img = 4 * w.blk1;
+        if ((rc = launch(F_CFIRST, h->convs[0], p, EPI_CFIRST, px * (32.0 + 128.0)))) return rc;
+        if ((rc = tap(0, w.D[0]))) return rc;
+    }
+    for (int k = 1; k <= nc; ++k) {
+        ConvParams p = b;
+        p.src = w.D[cur]; p.src_img = 4 * w.blk1; p.dst = w.D[cur ^ 1]; p.dst_img = 4 * w.blk1;
+        if ((rc = launch(F_CBODY, h->convs[k], p, EPI_PRELU, px * 256.0))) return rc;   // 128 B read + 128 B written per pixel
+        cur ^= 1;
+        if ((rc = tap(k, w.D[cur]))) return rc;
+    }
+    {   // last conv 64 -> 48, pixel_shuffle(4) + nearest-x4 of the input in its stores
+        ConvParams p = b;
+        p.src = w.D[cur]; p.src_img = 4 * w.blk1;
+        p.src_lo = w.P0; p.lo_img = w.blk1;               // the base: this LR pixel's own colour (ConvParams::slope's note)
+        p.out_f32 = d_out_f32; p.out_u8 = d_out_u8; p.cout = 3;
+        const double ob = px * 48.0 * ((d_out_u8 ? 1.0 : 0.0) + (d_out_f32 ? 4.0 : 0.0));
+        if ((rc = launch(F_CLAST, h->convs[nc + 1], p, EPI_CLAST, px * (128.0 + 32.0) + ob))) return rc;
+    }
+    return S2SR_OK;
+}
+
 int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f32, uint8_t* d_out_u8, const Mosaic& mo = Mosaic()) {
+    if (h->compact()) return run_net_compact(h, st, n, H, W, d_out_f32, d_out_u8, mo);
     Workspace& w = h->ws;
     const int nb = h->cfg.num_block;
     // window mosaic: every launch gets the separator geometry at the scale of the coordinates its epilogue works in
@@ -742,10 +837,20 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
     return S2SR_OK;
 }
 
+constexpr int kCompactGroup = 16;
 int group_size(const s2sr_handle* h, int B, int H, int W) {
     // default group: 16 images per launch sequence; the fp8 trunk's launches are half as long, so it takes 32 (measured:
     // 50.5 vs 51.9 ms per 32-tile step; the fp16 modes gain nothing from 32)
     int g = h->cfg.group > 0 ? h->cfg.group : (h->cfg.precision == S2SR_PREC_FP8 ? 32 : 16);
+    if (h->compact()) {
+        // SRVGGNetCompact: 288 B per padded LR pixel.  Default group: kCompactGroup, from the sweep of tools/bench_compact.py
+        // (profiles/compact_group_sweep.txt)
+        if (h->cfg.group <= 0) g = kCompactGroup;
+        const double per_c = (double)padded(H) * padded(W) * 288.0;
+        while (g > 1 && per_c * g > 96.0 * 1024 * 1024 * 1024) --g;
+        if (g > B) g = B;
+        return g < 1 ? 1 : g;
+    }
     // keep the workspace within a third of the 288 GB: bytes per LR pixel 32 + 3*384 (dense) + 128 + 3*128 (lo) + 2*256
     // (fp32 skips) + 2*128 (hp planes); 2x and 4x tensors with their correction planes
     const double per_img = (double)padded(H) * padded(W) * 2500.0 + (double)padded(2 * H) * padded(2 * W) * 256.0 +
@@ -971,12 +1076,25 @@ size_t s2sr_expected_blob_floats_scale(int32_t num_block, int32_t scale) {
 
 size_t s2sr_expected_blob_floats(int32_t num_block) { return s2sr_expected_blob_floats_scale(num_block, 4); }
 
+size_t s2sr_expected_blob_floats_cfg(const s2sr_config* cfg) {
+    if (!cfg) return 0;
+    if (cfg->arch == S2SR_ARCH_COMPACT)
+        return ((cfg->num_block == 16 || cfg->num_block == 32) && cfg->num_feat == 64 && cfg->scale == 4) ? compact_blob_floats(cfg->num_block) : 0;
+    if (cfg->arch != S2SR_ARCH_RRDB || cfg->num_block <= 0 || cfg->num_feat != 64 || cfg->num_grow != 32) return 0;
+    return s2sr_expected_blob_floats_scale(cfg->num_block, cfg->scale);
+}
+
 const char* s2sr_last_error(const s2sr_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 int s2sr_create(const s2sr_config* cfg, s2sr_handle** out) {
     if (!cfg || !out) return fail(nullptr, S2SR_E_INVALID, "null argument");
     *out = nullptr;
-    if (cfg->num_block <= 0 || cfg->num_feat != 64 || cfg->num_grow != 32 || (cfg->scale != 4 && cfg->scale != 2))
+    if (cfg->arch != S2SR_ARCH_RRDB && cfg->arch != S2SR_ARCH_COMPACT) return fail(nullptr, S2SR_E_INVALID, "unknown arch (S2SR_ARCH_RRDB or S2SR_ARCH_COMPACT)");
+    if (cfg->arch == S2SR_ARCH_COMPACT) {
+        if ((cfg->num_block != 16 && cfg->num_block != 32) || cfg->num_feat != 64 || cfg->scale != 4)
+            return fail(nullptr, S2SR_E_INVALID, "unsupported compact net shape (need num_conv = num_block in {16, 32}, num_feat=64, scale=4)");
+        if (cfg->precision == S2SR_PREC_FP8) return fail(nullptr, S2SR_E_INVALID, "the compact arch has no fp8 mode");
+    } else if (cfg->num_block <= 0 || cfg->num_feat != 64 || cfg->num_grow != 32 || (cfg->scale != 4 && cfg->scale != 2))
         return fail(nullptr, S2SR_E_INVALID, "unsupported net shape (need num_feat=64, num_grow=32, scale=4 or 2)");
     if (cfg->precision != S2SR_PREC_F16 && cfg->precision != S2SR_PREC_F16_HP && cfg->precision != S2SR_PREC_FP8)
         return fail(nullptr, S2SR_E_INVALID, "unknown precision");
@@ -1060,7 +1178,68 @@ void s2sr_destroy(s2sr_handle* h) {
 // Weights in, by either door.  `d_blob` is the fp32 blob ON THE DEVICE (the host entry uploads it first): the 345 RDB convs
 // are repacked by device kernels straight from it (pack.hip), every bias is gathered on the device; only the six head/tail
 // convs (0.9 MB of the 67 MB) come back to the host, because their split-operand / sub-pixel packers are host code.
+// SRVGGNetCompact: 1.2 M parameters -- the blob comes to the host whole and every conv goes through pack_conv_weights (plain
+// fp16, one segment).  The last conv's 48 output channels are placed in the rows the pixel-shuffle epilogue wants
+// (compact_last_row_channel); bias and slopes stay fp32.
+static int load_weights_compact(s2sr_handle* h, const float* d_blob, size_t n_floats, hipStream_t st) {
+    const int nc = h->cfg.num_block;
+    const size_t want = compact_blob_floats(nc);
+    if (n_floats != want) {
+        char b[160];
+        snprintf(b, sizeof b, "weight blob has %zu floats, a compact net of %d convs needs %zu", n_floats, nc, want);
+        return fail(h, S2SR_E_BADBLOB, b);
+    }
+    HIPCHK(h, dev_sync());
+    drop_graphs(h);
+    free_weights(h);
+    h->has_weights = false;
+    std::vector<float> blob(n_floats);
+    HIPCHK(h, hipMemcpyAsync(blob.data(), d_blob, n_floats * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    const int nconv = nc + 2;
+    std::vector<float> pb((size_t)nconv * 128, 0.f);     // per conv: [64 bias | 64 slopes]
+    HIPCHK(h, dev_malloc(&h->pool_b, pb.size() * sizeof(float)));
+    std::vector<char> tmp;
+    std::vector<float> wperm((size_t)64 * 64 * 9);
+    size_t off = 0;
+    for (int idx = 0; idx < nconv; ++idx) {
+        const int cin = idx == 0 ? 3 : 64, cout = idx == nconv - 1 ? 48 : 64;
+        const float* wsrc = blob.data() + off; off += (size_t)cin * cout * 9;
+        const float* bsrc = blob.data() + off; off += cout;
+        float* bias = pb.data() + (size_t)idx * 128;
+        ConvW cw;
+        cw.cin = cin; cw.cout = cout; cw.ct = 2; cw.seg_len = (cin + 15) / 16; cw.nstage = cw.seg_len; cw.seg_lo_mask = 0;
+        const float* pw = wsrc;
+        if (idx == nconv - 1) {     // rows in the epilogue's order, idle rows zero
+            std::fill(wperm.begin(), wperm.end(), 0.f);
+            for (int row = 0; row < 64; ++row) {
+                const int ch = compact_last_row_channel(row);
+                if (ch < 0) continue;
+                memcpy(&wperm[(size_t)row * 64 * 9], wsrc + (size_t)ch * 64 * 9, sizeof(float) * 64 * 9);
+                bias[row] = bsrc[ch];
+            }
+            pw = wperm.data();
+        } else {
+            memcpy(bias, bsrc, sizeof(float) * 64);
+            memcpy(bias + 64, blob.data() + off, sizeof(float) * 64);   // the PReLU behind this conv
+            off += 64;
+        }
+        const size_t wb = conv_wpack_bytes(cin, 64);
+        tmp.resize(wb);
+        pack_conv_weights(pw, cin, 64, 1, tmp.data(), false);
+        HIPCHK(h, dev_malloc(&cw.d_wpack, wb));
+        HIPCHK(h, copy_blocking(h, cw.d_wpack, tmp.data(), wb, hipMemcpyHostToDevice));
+        cw.d_bias = h->pool_b + (size_t)idx * 128;
+        cw.d_slope = h->pool_b + (size_t)idx * 128 + 64;
+        h->convs.push_back(cw);
+    }
+    HIPCHK(h, copy_blocking(h, h->pool_b, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
+    h->has_weights = true;
+    return S2SR_OK;
+}
+
 static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_floats, hipStream_t st) {
+    if (h->compact()) return load_weights_compact(h, d_blob, n_floats, st);
     const std::vector<ConvSpec> specs = conv_specs(h->cfg.num_block, h->cfg.scale);
     const size_t want = s2sr_expected_blob_floats_scale(h->cfg.num_block, h->cfg.scale);
     if (n_floats != want) {
@@ -1175,7 +1354,7 @@ int s2sr_load_weights(s2sr_handle* h, const float* blob, size_t n_floats) {
     if (!h || !blob) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (n_floats != s2sr_expected_blob_floats_scale(h->cfg.num_block, h->cfg.scale)) return load_weights_locked(h, nullptr, n_floats, h->stream);   // -> BADBLOB text
+    if (n_floats != handle_blob_floats(h)) return load_weights_locked(h, nullptr, n_floats, h->stream);   // -> BADBLOB text
     float* d_blob = nullptr;
     HIPCHK(h, dev_malloc(&d_blob, n_floats * sizeof(float)));
     hipError_t e = hipMemcpyAsync(d_blob, blob, n_floats * sizeof(float), hipMemcpyHostToDevice, h->stream);
@@ -2489,6 +2668,7 @@ int s2sr_debug_rdb_persistent(s2sr_handle* h, int32_t variant, int32_t grid, int
                               float* ms_total, int32_t* timeouts, int32_t* mismatches) {
     if (!h || variant < 0 || variant > 5 || grid < 2 || P < 2 || P > 4 || rdbs < 1 || rdbs > 4000 || launches < 1 || !ms_total) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
+    if (h->compact()) return fail(h, S2SR_E_INVALID, "s2sr_debug_rdb_persistent: RRDB handles only");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
@@ -2549,6 +2729,7 @@ int s2sr_debug_get_config(s2sr_handle* h, s2sr_debug_config* out) {
 // speed); the weights go through the production device packers (pack.hip).
 int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
     if (!h || !a || !a->x || !a->weight || !a->bias || !a->y) return S2SR_E_INVALID;
+    if (h->compact()) return S2SR_E_INVALID;     // RRDB handles only
     const int kind = a->kind, N = a->N, Cin = a->Cin, H = a->H, W = a->W;
     if (kind < 0 || kind > 5 || N <= 0 || H <= 0 || W <= 0) return S2SR_E_INVALID;
     const bool f8 = kind >= 3, c5 = (kind % 3) != 0, rr = (kind % 3) == 2;
@@ -2843,6 +3024,7 @@ int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x
                             s2sr_debug_taps* t) {
     if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
+    if (h->compact()) return fail(h, S2SR_E_INVALID, "s2sr_debug_forward_taps: RRDB handles only (compact: s2sr_debug_compact_taps)");
     if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     TapPlan tp;
@@ -2913,6 +3095,7 @@ int s2sr_debug_trunk_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, 
                           s2sr_debug_trunk_fields* t) {
     if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
+    if (h->compact()) return fail(h, S2SR_E_INVALID, "s2sr_debug_trunk_taps: RRDB handles only (compact: s2sr_debug_compact_taps)");
     if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
     if (h->cfg.scale != 4) return fail(h, S2SR_E_INVALID, "trunk taps: scale-4 handles only (the scale-2 trunk is the same schedule on the half grid)");
     if (t->first < 0 || t->count < 1 || t->first + t->count > 3 * h->cfg.num_block)
@@ -2939,6 +3122,39 @@ int s2sr_debug_trunk_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, 
     rc = tap_forward(h, tiles, x, B, th, tw, tp, t->out_u8, t->out_f32);
     h->ttap = nullptr;
     return rc;
+}
+
+// SRVGGNetCompact's per-layer parity hook: the batch of s2sr_debug_forward_taps, with run_net_compact copying the chosen layers'
+// fp16 activations out right behind their launches.
+int s2sr_debug_compact_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, int32_t job_windows,
+                            s2sr_debug_compact_fields* t) {
+    if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->compact()) return fail(h, S2SR_E_INVALID, "s2sr_debug_compact_taps: compact handles only");
+    if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
+    if (t->nlayers < 0 || t->nlayers > S2SR_COMPACT_TAPS_MAX) return fail(h, S2SR_E_INVALID, "too many layers");
+    for (int k = 0; k < t->nlayers; ++k)
+        if (t->layers[k] < 0 || t->layers[k] > h->cfg.num_block || (k > 0 && t->layers[k] <= t->layers[k - 1]))
+            return fail(h, S2SR_E_INVALID, "layers must ascend inside [0, num_conv]");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    TapPlan tp;
+    int rc = tap_plan(h, tiles != nullptr, B, th, tw, job_windows, &tp);
+    if (rc) return rc;
+    const bool mos = tp.plan.on();
+    t->n = tp.NI; t->H = tp.SH; t->W = tp.SW; t->Hp = padded(tp.IH); t->Wp = padded(tp.IW);
+    t->mos_kx = mos ? tp.skx : 0; t->mos_ky = mos ? tp.sky : 0; t->mos_wh = mos ? th : 0; t->mos_ww = mos ? tw : 0;
+    t->mos_count = mos ? B : 0;
+    bool any = t->out_f32 || t->out_u8 || t->p0;
+    for (int k = 0; k < t->nlayers; ++k) any = any || t->act[k];
+    if (!any) return S2SR_OK;
+    CompactTap ct;
+    ct.t = t;
+    h->ctap = &ct;
+    rc = tap_forward(h, tiles, x, B, th, tw, tp, t->out_u8, t->out_f32);
+    h->ctap = nullptr;
+    if (rc) return rc;
+    if (t->p0 && (rc = decode_f16_planes(h, t->p0, h->ws.P0, h->ws.blk1, tp.NI, 1, h->ws.blk1))) return rc;
+    return S2SR_OK;
 }
 
 }  // extern "C"

@@ -67,6 +67,10 @@ enum Epilogue : int {
     EPI_BODY = 4,       // v = F + acc                     -> fp16               (conv_body + trunk skip)
     EPI_LAST = 5,       // out fp32 NCHW and/or u8 NHWC (x255, clip, truncate)   (conv_last)
     EPI_DEBUG = 6,      // out fp32 NCHW, all Cout, optional lrelu               (s2sr_debug_conv)
+    // SRVGGNetCompact (S2SR_ARCH_COMPACT): per-channel PReLU, pixel-shuffle tail
+    EPI_PRELU = 7,      // y = prelu(acc, slope[c])        -> fp16 blocks        (compact body convs)
+    EPI_CFIRST = 8,     // y = prelu(acc*in_scale + bias)  -> fp16 blocks        (compact first conv; no lo / R / F)
+    EPI_CLAST = 9,      // pixel_shuffle(acc, 4) + x/255 -> fp32 NCHW and/or u8 NHWC at 4x (compact last conv, rows permuted on the host)
 };
 
 struct ConvParams {
@@ -127,8 +131,12 @@ struct ConvParams {
     int32_t mos_kx, mos_ky, mos_count;   // EPI_LAST: grid of a mosaic and the number of windows in this launch: window t = (n * ky + wy) * kx + wx
                                          // is written as image t of [count, ry, rx]; slots past the count are not written
     char* trash;             // >= 4 KiB scratch: out-of-image lanes park their (unconditional) stores here
-    unsigned long long* trace;   // unused (kept so that every kernel argument stays at its offset)
-    int32_t dbg;                 // unused (ditto)
+    const float* slope;      // EPI_PRELU / EPI_CFIRST (SRVGGNetCompact): [64] fp32 PReLU slopes, one per output channel, next to `bias`.
+                             // (Takes the slot of the retired `trace` pointer, so the struct keeps its size and every kernel
+                             // argument its offset: the RRDB kernels compile to the parent's instructions.)
+                             // EPI_CLAST takes the packed input (fp16 blocked-16, one block: channels 0..2 = the pixel's exact 0..255
+                             // values, for the nearest-x4 base) as src_lo / lo_img: the loader never reads src_lo of a plain conv
+    int32_t dbg;                 // unused (kept so that every kernel argument stays at its offset)
 };
 
 // is output pixel (y, x) of this launch one the reference writes (inside the image, and not a mosaic separator)?
@@ -195,6 +203,10 @@ size_t conv_wpack_bytes(int cin, int cout);
 // output channels gets x*w_hi and x*w_lo from one pass over x (conv_last in hp mode: 2 segments, x_hi and x_lo)
 void pack_conv_weights(const float* w, int cin, int cout, int nseg, void* dst_host, bool fold = false);
 size_t conv_wpack_bytes_seg(int cin, int cout, int nseg);
+// SRVGGNetCompact's last conv (64 -> 48 = 3 colours x 4 x 4 sub-pixels): which state-dict output channel sits in row
+// `row` (0..63) of the packed weights / bias, -1 = an idle (zero) row.  Chosen so that a lane's 16 accumulators of cout tile ct
+// are [colour 0..2][dx 0..3] of HR row dy = 2 * half-wave + ct (EPI_CLAST): 12 contiguous u8 / 3 x 16 contiguous fp32 bytes.
+int compact_last_row_channel(int row);
 // split-operand convs with fp8 correction terms (cin == 64): 4 fp16 stages [w_hi] + 4 e4m3 stages
 // [w_hi ch 0-31][w_hi ch 32-63][w_lo*2^11 ch 0-31][w_lo*2^11 ch 32-63]; an fp8 stage fragment is
 // [tap][ct][16-B half][cout row 0..31][16 channel bytes].  Same size as nseg = 2.

@@ -294,6 +294,9 @@ def enhance_distributed(backend, img: np.ndarray, tile: int = 256, pad: int = 10
     if backend.scale != 4:
         raise ValueError(f"enhance_distributed runs scale-4 nets only; this backend's scale is {backend.scale} "
                          "(RealESRGAN_x2plus runs on one GPU)")
+    if getattr(getattr(backend, "engine", None), "arch", "rrdb") != "rrdb":
+        raise ValueError("enhance_distributed runs RRDBNet engines only; the compact arch (realesr-general-x4v3 and kin) is not "
+                         "sharded -- run it on one GPU (RealESRGAN.enhance)")
     world, rank = dist.get_world_size(), dist.get_rank()
     H, W, _ = img.shape
     dev = backend.device

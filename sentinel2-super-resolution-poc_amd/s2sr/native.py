@@ -28,7 +28,7 @@ class S2srError(RuntimeError):
 
 class _Config(C.Structure):
     _fields_ = [("num_block", C.c_int32), ("num_feat", C.c_int32), ("num_grow", C.c_int32), ("scale", C.c_int32),
-                ("precision", C.c_int32), ("device", C.c_int32), ("group", C.c_int32), ("reserved", C.c_int32)]
+                ("precision", C.c_int32), ("device", C.c_int32), ("group", C.c_int32), ("arch", C.c_int32)]
 
 
 class Window(C.Structure):
@@ -94,6 +94,19 @@ def pp_farm() -> PPParams:
 PP_ORDER_BGR, PP_ORDER_SWAP_OUT = 1, 2      # s2sr_pp_band_begin_dev `order` bits
 
 
+COMPACT_TAPS_MAX = 8
+COMPACT_GROUP = 16          # engine.hip kCompactGroup (the sweep of tools/bench_compact.py)
+ARCH_RRDB, ARCH_COMPACT = 0, 1
+_ARCH = {"rrdb": ARCH_RRDB, "compact": ARCH_COMPACT}
+
+
+class DebugCompactFields(C.Structure):     # s2sr_debug_compact_fields
+    _fields_ = [("nlayers", C.c_int32), ("layers", C.c_int32 * COMPACT_TAPS_MAX)] + \
+               [(n, C.c_int32) for n in ("n", "H", "W", "Hp", "Wp", "mos_kx", "mos_ky", "mos_wh", "mos_ww", "mos_count")] + \
+               [("reserved", C.c_int32 * 4), ("act", C.c_void_p * COMPACT_TAPS_MAX), ("p0", C.c_void_p), ("out_f32", C.c_void_p),
+                ("out_u8", C.c_void_p)]
+
+
 _lib = None
 
 _PROTOS = {
@@ -107,6 +120,7 @@ _PROTOS = {
     "s2sr_load_weights": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "s2sr_expected_blob_floats": (C.c_size_t, [C.c_int32]),
     "s2sr_expected_blob_floats_scale": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "s2sr_expected_blob_floats_cfg": (C.c_size_t, [C.POINTER(_Config)]),
     "s2sr_load_weights_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "s2sr_calibrate_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_int32),
                                      C.POINTER(C.c_int32)]),
@@ -163,6 +177,7 @@ _PROTOS = {
     "s2sr_debug_conv_trunk": (C.c_int, [C.c_void_p, C.POINTER(DebugTrunkArgs)]),
     "s2sr_debug_forward_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(DebugTaps)]),
     "s2sr_debug_trunk_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(DebugTrunkFields)]),
+    "s2sr_debug_compact_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(DebugCompactFields)]),
     "s2sr_debug_mfma_ceiling": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                           C.POINTER(C.c_float)]),
     "s2sr_debug_bench_conv": (C.c_int, [C.c_void_p] + [C.c_int32] * 6 + [C.POINTER(C.c_float), C.c_void_p, C.c_int32]),
@@ -452,14 +467,20 @@ pinned_pool = _PinnedPool()
 class Engine:
     """One native handle == one GPU.  Thread-safe (the library serialises calls per handle)."""
 
-    def __init__(self, num_block: int = 23, precision: int = PREC_F16, device: int = 0, group: int = 0, scale: int = 4):
-        """scale 4, or 2 = RealESRGAN_x2plus (include/s2sr.h s2sr_config.scale): every output is `scale` x the input."""
+    def __init__(self, num_block: int = 23, precision: int = PREC_F16, device: int = 0, group: int = 0, scale: int = 4,
+                 arch: str = "rrdb"):
+        """scale 4, or 2 = RealESRGAN_x2plus (include/s2sr.h s2sr_config.scale): every output is `scale` x the input.
+        arch "compact" = SRVGGNetCompact (realesr-general-x4v3 and kin): `num_block` carries num_conv (16 or 32), scale 4 only;
+        PREC_F16 and PREC_F16_HP run the same arithmetic there, PREC_FP8 is refused."""
         self._lib = load_library()
         self._h = C.c_void_p()
+        if arch not in _ARCH:
+            raise ValueError(f"arch {arch!r}: 'rrdb' or 'compact'")
+        self.arch = arch
         self.num_block = num_block
         self.precision, self.group = precision, group
         self.scale = int(scale)
-        cfg = _Config(num_block, 64, 32, self.scale, precision, device, group, 0)
+        cfg = _Config(num_block, 64, 32, self.scale, precision, device, group, _ARCH[arch])
         rc = self._lib.s2sr_create(C.byref(cfg), C.byref(self._h))
         if rc:
             msg = self._lib.s2sr_last_error(None)
@@ -467,6 +488,8 @@ class Engine:
 
     def group_images(self) -> int:
         """Images per launch group (engine.hip group_size: 16, 32 for the fp8 trunk, or what the constructor was given)."""
+        if self.group <= 0 and self.arch == "compact":
+            return COMPACT_GROUP
         return self.group if self.group > 0 else (32 if self.precision == PREC_FP8 else 16)
 
     # -- plumbing ---------------------------------------------------------------------------
@@ -497,8 +520,11 @@ class Engine:
                     "s2sr_load_weights_dev")
 
     def load_state_dict(self, sd):
-        from .weights import flatten_state_dict
-        self.load_blob(flatten_state_dict(sd, self.num_block, scale=self.scale))
+        from .weights import flatten_state_dict, infer_arch
+        arch = infer_arch(sd.keys())[0]
+        if arch != self.arch:
+            raise ValueError(f"state dict is a {arch} net, this engine was created with arch={self.arch!r}")
+        self.load_blob(flatten_state_dict(sd, self.num_block, scale=self.scale, arch=arch))
 
     def calibrate_fp8(self, tiles: np.ndarray, headroom: float = 2.0) -> tuple:
         """PREC_FP8 engines: set the trunk's activation scales from representative tiles -> (x_exp, g_exp)."""
@@ -854,6 +880,44 @@ def _debug_trunk_taps(self, first, count, tiles=None, x=None, job_windows=0):
     return geo, fields, fl, out_f32, out_u8
 
 
+def _debug_compact_taps(self, layers, tiles=None, x=None, job_windows=0):
+    """Compact engines: one batch through the production forward, eagerly, with the fp16 activation copied out behind each layer
+    of `layers` (ascending; 0 = the first conv, k = body conv k; include/s2sr.h: s2sr_debug_compact_taps).  Input as
+    debug_forward_taps.  Returns (geometry dict, {layer: [n, 64, Hp, Wp] fp32}, p0 [n, 16, Hp, Wp], out_f32, out_u8)."""
+    assert (tiles is None) != (x is None)
+    if tiles is not None:
+        tiles = np.ascontiguousarray(tiles, np.uint8)
+        B, th, tw, c = tiles.shape
+    else:
+        x = np.ascontiguousarray(x, np.float32)
+        B, c, th, tw = x.shape
+    assert c == 3
+    layers = [int(v) for v in layers]
+    t = DebugCompactFields()
+    t.nlayers = len(layers)
+    for k, v in enumerate(layers):
+        t.layers[k] = v
+    call = lambda: self._check(self._lib.s2sr_debug_compact_taps(self._h, None if tiles is None else _ptr(tiles), None if x is None else _ptr(x),
+                                                                 B, th, tw, int(job_windows), C.byref(t)), "s2sr_debug_compact_taps")
+    call()                                  # geometry only
+    geo = {k: getattr(t, k) for k in ("n", "H", "W", "Hp", "Wp", "mos_kx", "mos_ky", "mos_wh", "mos_ww", "mos_count")}
+    acts = {v: np.zeros((t.n, 64, t.Hp, t.Wp), np.float32) for v in layers}
+    for k, v in enumerate(layers):
+        t.act[k] = acts[v].ctypes.data
+    p0 = np.zeros((t.n, 16, t.Hp, t.Wp), np.float32)
+    out_f32 = np.zeros((B, 3, 4 * th, 4 * tw), np.float32)
+    out_u8 = np.zeros((B, 4 * th, 4 * tw, 3), np.uint8)
+    t.p0, t.out_f32, t.out_u8 = p0.ctypes.data, out_f32.ctypes.data, out_u8.ctypes.data
+    call()
+    return geo, acts, p0, out_f32, out_u8
+
+
+def expected_blob_floats_cfg(num_block: int, scale: int = 4, arch: str = "rrdb") -> int:
+    cfg = _Config(num_block, 64, 32, scale, PREC_F16, 0, 0, _ARCH[arch])
+    return int(load_library().s2sr_expected_blob_floats_cfg(C.byref(cfg)))
+
+
+Engine.debug_compact_taps = _debug_compact_taps
 Engine.debug_config = _debug_config
 Engine.debug_trunk_taps = _debug_trunk_taps
 Engine.debug_conv_trunk = _debug_conv_trunk
