@@ -165,7 +165,11 @@ int  s2sr_forward_batch_u8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int3
  * default stream, ordered with the caller's other default-stream work) */
 int  s2sr_forward_batch_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int32_t th, int32_t tw,
                                void* d_out, void* stream);
-/* unquantised net output for parity tests: x [N,3,H,W] fp32 in [0,1] -> y [N,3,4H,4W] fp32 (scale 2: even H, W -> [N,3,2H,2W]) */
+/* unquantised net output for parity tests: x [N,3,H,W] fp32 in [0,1] -> y [N,3,4H,4W] fp32 (scale 2: even H, W -> [N,3,2H,2W]).
+ * The entry quantises its input to fp16(fp32(255 x)): exact for x = u / 255 (what the u8 entries feed), up to 0.0625 / 255 = 2.5e-4
+ * off for other x above 0.5.  SRVGGNetCompact adds that input to its output (the nearest-x4 base); measured on uniform random
+ * floats against a float64 net fed the same floats: 5.0e-4 max-abs at num_conv 16, 3.4e-4 at 32 (fed the quantised input: 3.1e-4 /
+ * 1.3e-4); tests/test_gpu_compact_insitu.py holds both to 1e-3. */
 int  s2sr_forward_f32(s2sr_handle* h, const float* x, int32_t N, int32_t H, int32_t W, float* y);
 
 /* replaces RealESRGAN.enhance incl. the whole/tiled switch and _tile_process

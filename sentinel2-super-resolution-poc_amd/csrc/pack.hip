@@ -77,7 +77,13 @@ __global__ void pack_f32_nchw_kernel(const float* __restrict__ x, int N, int C, 
         const int c = (int)(r % C);
         const int n = (int)(r / C);
         f16* d = (f16*)(blk + ((((size_t)n * NB + (c >> 4)) * Hp + y + 1) * Wp + xx + 1) * 32) + (c & 15);
-        *d = (f16)(x[i] * scale);
+        // fp16(fp32(x * scale)): the product rounded to fp32, then to fp16, as pack_f32_nchw_unshuffle_kernel's v_mul_f32 +
+        // v_cvt_pk_f16_f32 do.  Left to itself the compiler selects one v_fma_mixlo_f16 for (f16)(x[i] * scale) (__fmul_rn does
+        // not stop it), which rounds the exact product once: an fp16 ulp apart wherever the fp32 product lands on an fp16 tie
+        // (x = 0.21868873f: 55.78125 against 55.75).  The empty asm keeps the fp32 product in a register.
+        float v = x[i] * scale;
+        asm volatile("" : "+v"(v));
+        *d = (f16)v;
     }
 }
 

@@ -1,8 +1,10 @@
 """SRVGGNetCompact (s2sr_config.arch = S2SR_ARCH_COMPACT: realesr-general-x4v3, -wdn-x4v3, realesr-animevideov3) on the MI355X,
 through the C ABI.  Checked against the float64 CPU checker tests/compact_model.py (pinned by tests/golden/g10_compact.npz):
-network parity at the project's 1e-3, every layer in situ against the checker fed with the device's own previous activation
-(bound: tests/tail_model.py Layer.result), the pixel-shuffle tail exactly, the u8 paths, byte identities across the run-time
-switches, the schedule, the error codes, and the drop-in.
+network parity at the project's 1e-3, layers 0, 1, 16, num_conv and the last conv in situ on two batches against the checker fed
+with the device's own previous activation (the judge of tests/compact_insitu.py; bound: tests/tail_model.py Layer.result), the
+pixel-shuffle tail exactly, the u8 paths, byte identities across the run-time switches, the schedule, the error codes, and the
+drop-in.  Every layer of both depths, the shape classes (mosaics with dead slots, AOI windows, whole tiles, degenerate sizes, the
+fp32 entry off the u8 grid), out_u8 byte for byte, workspace reuse and guard bytes: tests/test_gpu_compact_insitu.py.
 
 Measured (MI355X, seeded weights, u8 / 255 inputs): network max-abs error against float64 3.6e-4 at num_conv 16, 1.5e-4 at
 num_conv 32 (the CPU emulation of the same formats on the golden: 2.8e-4 / 1.2e-4); u8 off by one level at 0.5 % of the values
@@ -15,8 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+import compact_insitu as ci
 import compact_model as cm
-import tail_model as tm
 from s2sr import native
 from s2sr import rasterio_lite as rio
 from s2sr import weights as W
@@ -95,70 +97,23 @@ def test_forward_f32_vs_checker(nc, shape):
 
 
 # ---- 2. in situ per layer ------------------------------------------------------------------------------------------------
-def _live_mask(geo, B, th, tw, shape):
-    live = np.zeros((geo["n"], 1) + shape, bool)
-    kx, ky = (geo["mos_kx"], geo["mos_ky"]) if geo["mos_kx"] else (1, 1)
-    for t in range(B):
-        i, slot = divmod(t, kx * ky)
-        wy, wx = divmod(slot, kx)
-        live[i, 0, wy * (th + 1):wy * (th + 1) + th, wx * (tw + 1):wx * (tw + 1) + tw] = True
-    return live
-
-
-def _insitu_tiles(seed, B, th, tw):
-    """Noise tiles plus one smooth tile (ramps, a checkerboard channel, flat dark / bright corners) and one posterised tile."""
-    t = _u8(seed, B, th, tw, 3)
-    yy, xx = np.mgrid[0:th, 0:tw]
-    g = np.stack([xx * 255 // (tw - 1), yy * 255 // (th - 1), ((xx + yy) % 2) * 255], -1).astype(np.uint8)
-    g[: th // 4, : tw // 4] = 0
-    g[-(th // 4):, -(tw // 4):] = 255
-    t[1] = g
-    if B > 2:
-        t[2] = (t[2] // 64) * 85
-    return t
-
-
-def _insitu_sd(nc):
-    """The per-layer tests judge one layer at a time on the device's own operands, so they need no net-level stability; they do
-    need both signs in every channel at every depth.  With the golden's weights (biases of 0.05, body gain 0.90) the signal 32
-    layers deep is smaller than some channels' bias and 7 of the 64 pre-activation channels stay positive on any input (CPU,
-    float32).  Same generator, zero-mean rows, biases of 0.01, body gain 1.0: every channel of layers 0, 1, 16 and num_conv goes
-    negative (asserted below)."""
-    return W.synthetic_compact_state_dict(nc, seed=0, zero_mean=True, bias_amp=0.01, body_gain=1.0)
-
-
 @pytest.mark.parametrize("nc,B,th,tw", [(32, 2, 40, 56), (16, 5, 37, 45)])
 def test_layers_in_situ(nc, B, th, tw, monkeypatch):
     """The activation after the first conv and after body convs 1, 16 and num_conv, each against the checker's arithmetic on the
     DEVICE's own previous activation (so one layer is what is judged).  Bound per element: tail_model.Layer.result (stages x taps
     fp32 accumulator roundings of half an ulp of the running sum, two ulps for the epilogue) through the PReLU (slopes below 1
-    do not widen it), then half an fp16 quantum for the store."""
-    sd = _insitu_sd(nc)
+    do not widen it), then half an fp16 quantum for the store.  The arithmetic lives in tests/compact_insitu.py (judge), which
+    judges the last conv, out_u8, p0 and the zeros outside the live pixels of the same run as well; all layers and the other
+    shape classes: tests/test_gpu_compact_insitu.py."""
+    sd = ci.insitu_sd(nc)
     e = _fresh(monkeypatch, nc, {}, sd=sd)
-    tiles = _insitu_tiles(nc + B, B, th, tw)
+    tiles = ci.insitu_tiles(nc + B, B, th, tw)
     want = sorted({0, 1, 15, 16, nc - 1, nc})
-    geo, acts, p0, out_f32, _ = e.debug_compact_taps(want, tiles=tiles)
-    live = _live_mask(geo, B, th, tw, (geo["Hp"] - 2, geo["Wp"] - 2))
-    assert np.array_equal(p0[:, :3, 1:-1, 1:-1][np.broadcast_to(live, (geo["n"], 3) + live.shape[2:])].reshape(-1),
-                          p0[:, :3, 1:-1, 1:-1][np.broadcast_to(live, (geo["n"], 3) + live.shape[2:])].round().reshape(-1))
-    for layer in (0, 1, 16, nc):
-        w = sd[f"body.{2 * layer}.weight"]
-        b, slope = sd[f"body.{2 * layer}.bias"], sd[f"body.{2 * layer + 1}.weight"].astype(np.float64).reshape(1, -1, 1, 1)
-        if layer == 0:
-            L = tm.model_first(p0, w, False)
-            m, _, tol = L.result(b, scale=1.0 / 255.0)
-        else:
-            m, _, tol = tm.model_plain64("3x3", acts[layer - 1].astype(np.float64), w).result(b)
-        L4 = np.broadcast_to(live, m.shape)
-        neg = (m < 0) & L4
-        assert neg.any(axis=(0, 2, 3)).all(), f"layer {layer}: a channel without negative pre-activations (PReLU untested)"
-        v = np.where(m >= 0, m, slope * m)
-        tol = tol + tm.U32 * np.abs(v)                          # the slope multiply
-        got = acts[layer][:, :, 1:-1, 1:-1].astype(np.float64)
-        ratio = np.abs(got - v) / (tol + tm.f16_quantum(v) / 2)
-        print(f"num_conv {nc} layer {layer}: worst {float(ratio[L4].max()):.3f} x bound, {int(neg.sum())} negative pre-activations")
-        assert (ratio[L4] <= 1).all(), f"layer {layer}: off the model by {float(ratio[L4].max()):.3g} x bound"
-        assert not acts[layer][:, :, 1:-1, 1:-1][~L4].any(), f"layer {layer}: stores outside the live pixels"
+    geo, acts, p0, out_f32, out_u8 = e.debug_compact_taps(want, tiles=tiles)
+    rep = ci.judge(geo, acts, p0, out_f32, out_u8, sd, B, th, tw, tiles=tiles)      # need_negative: every channel, every judged layer
+    print(rep.text(f"num_conv {nc} {B}x{th}x{tw}"))
+    assert set(rep.judged) == {0, 1, 16, nc, nc + 1}
+    assert not rep.fails, rep.message()
     # the hook's outputs are production's
     assert np.array_equal(out_f32, e.forward_f32((tiles.astype(np.float32) / 255.0).transpose(0, 3, 1, 2)))
     e.close()
