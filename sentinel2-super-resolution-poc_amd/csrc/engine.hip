@@ -1,228 +1,30 @@
-// libs2sr engine: handle, weights, workspace planes and the layer schedule of
-// RRDBNet.forward / RealESRGAN.enhance (reference server/app/cnn_super_resolution.py:140-158,
-// 217-280) on top of the conv kernel in conv_mfma.hip.  This file is the C ABI of
-// include/s2sr.h.  There is no CPU fallback anywhere in this library.
+// libs2sr engine core: handle, weights, workspace planes, profiling events, the hipGraph cache and the layer schedule of
+// RRDBNet.forward / RealESRGAN.enhance (reference server/app/cnn_super_resolution.py:140-158, 217-280) on top of the conv kernels
+// in conv3x3.hip and conv_trunk.hip.  With engine_aoi.hip (whole images), engine_tiles.hip (the XYZ pyramid) and engine_debug.hip
+// (test and diagnostic hooks) this is the C ABI of include/s2sr.h.  There is no CPU fallback anywhere in this library.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <atomic>
-#include <chrono>
 #include <mutex>
 #include <string>
 #include <vector>
 
-#include "png_internal.h"
-#include "s2sr_internal.h"
+#include "engine_internal.h"
 
 using namespace s2sr;
+using namespace s2sr::engine;
 
 std::recursive_mutex& s2sr::device_gate() {      // see s2sr_internal.h
     static std::recursive_mutex m;
     return m;
 }
 
+// ---- local to this file: weight bookkeeping, the workspace planner, event statistics and the layer schedule
 namespace {
 
 thread_local std::string g_create_error;
-
-struct ConvW {
-    int cin = 0, cout = 0, nstage = 0, ct = 0;
-    int seg_len = 0, seg_lo_mask = 0;   // split-operand convs (precision S2SR_PREC_F16_HP), see ConvParams
-    bool fold = false;                  // conv_last in hp mode: w_lo folded into idle couts (pack_conv_weights)
-    bool f8 = false;                    // hp mode, cin 64: fp16 main term + e4m3 correction planes (pack_conv_weights_f8hp)
-    void* d_wphase[2] = {nullptr, nullptr};   // hp up-convs: the 2x2 sub-pixel kernels per output row parity (pack_conv_weights_phase_f8hp)
-    void* d_wpack = nullptr;
-    float* d_bias = nullptr;
-    // fp8 trunk mode (S2SR_PREC_FP8), the 345 RDB convs: e4m3 weight planes (pack_conv_weights_f8; nstage = planes padded
-    // to even, seg_len = real planes) + per-output-channel E8M0 scale bytes
-    bool f8trunk = false;
-    int32_t* d_wscale = nullptr;
-    bool pooled = false;                // d_wpack / d_wscale point into the handle's pools
-    float* d_slope = nullptr;           // SRVGGNetCompact: the 64 PReLU slopes behind this conv (in pool_b, next to the bias)
-};
-
-// kernel families for the HIP-event statistics
-enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_COUNT };
-const char* kFamName[F_COUNT] = {"pack_u8",   "conv_first", "rdb_conv1-4", "rdb_conv5",   "conv_body",
-                                 "conv_up",   "conv_hr",    "conv_last",   "postprocess", "misc",
-                                 "compact_first", "compact_body", "compact_last"};
-
-struct Workspace {
-    int G = 0, H = 0, W = 0;   // capacity (images) and logical LR dims
-    char* base = nullptr;
-    size_t bytes = 0;
-    // LR tensors (blocked-16 fp16 / blocked-8 fp32, see s2sr_internal.h)
-    char *P0 = nullptr;                  // input, 1 block
-    char *D[3] = {nullptr, nullptr, nullptr};   // dense-block tensors, 12 blocks: [x(4) | x1 | x2 | x3 | x4]; three of them rotate
-                                         // through an RRDB (rdb k reads D[k], writes the next x into D[(k+1)%3]), so the
-                                         // RRDB's input D[0] is still there when rdb3's conv5 needs it as the skip
-    char *U0 = nullptr;                  // 4 blocks
-    char *T = nullptr;                   // trunk lo as fp16 (4 blocks): conv_first writes it, conv_body's packer reads it (8-wave path: every conv5 too)
-    char *Tr[3] = {nullptr, nullptr, nullptr};  // one-wave-per-SIMD path: trunk lo of D[0..2] as e4m3(lo * 2^lo_exp), 2 planes of 32 channels
-    float *R = nullptr, *F = nullptr;    // fp32 RRDB skip / global skip (8 blocks of 8)
-    // 2x and 4x tensors, 4 blocks each
-    char *U1 = nullptr, *U2 = nullptr, *U3 = nullptr;
-    // split-operand mode only: e4m3 correction planes of U0..U3 and of the trunk, 4 planes of 32 B per
-    // pixel each ([lo*2^11 p0, p1, hi p0, p1]) -- the size of a 4-block fp16 tensor
-    char *U0lo = nullptr, *U1lo = nullptr, *U2lo = nullptr, *U3lo = nullptr, *T8 = nullptr;
-    // fp8 trunk mode only: the dense-block tensors as e4m3 planes of 32 channels [x(2) | x1 | x2 | x3 | x4], the trunk x in
-    // fp16 (three rotating buffers: an RRDB's input stays readable until its last conv5 has used it as the skip), and
-    // an all-zero "trunk lo" for conv_body's split-operand path
-    char *D8[2] = {nullptr, nullptr};
-    char *Xh[3] = {nullptr, nullptr, nullptr};
-    char *Tz = nullptr;
-    bool hp = false, fp8 = false;
-    int mos_py = 0, mos_px = 0;          // separator periods of the window mosaic these planes were zeroed for (0: plain images)
-    int Hp = 0, Wp = 0, Hp2 = 0, Wp2 = 0, Hp4 = 0, Wp4 = 0;
-    size_t blk1 = 0, blk2 = 0, blk4 = 0;   // bytes of one block plane at 1x / 2x / 4x
-};
-
-struct EvRec {
-    int fam;
-    hipEvent_t e0, e1;
-    double flops, bytes;
-    int n = 1;           // launches between the two events (a span of consecutive launches of one family)
-};
-
-// One captured group (pack + the whole layer schedule) for fixed shapes and buffers.  A net is
-// 351 dependent launches; small groups are launch-bound (~15 us per launch against a few us of
-// work), so the second time the same (shape, buffers) group shows up it is captured into a
-// hipGraph and replayed from then on.
-// Window mosaic geometry of one forward (see ConvParams::mos_*): kx x ky windows of wh x ww per image, `count` windows in all.
-struct Mosaic {
-    int kx = 1, ky = 1, wh = 0, ww = 0, count = 0;
-    bool on() const { return wh > 0; }
-};
-
-struct GraphEntry {
-    int n = 0, th = 0, tw = 0;
-    int sh = 0, sw = 0;              // input rows / columns as stored (forward_dev src_h / src_w)
-    int mos_kx = 0, mos_ky = 0, mos_count = 0;
-    const void *in_u8 = nullptr, *in_f32 = nullptr;
-    void *out_u8 = nullptr, *out_f32 = nullptr;
-    hipStream_t st = nullptr;
-    hipGraphExec_t exec = nullptr;   // null until captured
-    bool refused = false;            // capture failed once: stay on direct launches
-    uint64_t last_use = 0;
-};
-
-// s2sr_debug_trunk_taps while its batch runs: the RDB range whose fields run_net copies out (trunk_tap) and where the form
-// records of the range's conv launches go
-// s2sr_debug_compact_taps while its batch runs: run_net_compact copies the chosen layers' activations out
-struct CompactTap {
-    s2sr_debug_compact_fields* t = nullptr;
-};
-
-struct TrunkTap {
-    int first = 0, count = 0;
-    s2sr_debug_trunk_fields* t = nullptr;
-    s2sr_debug_trunk_form spare[5];     // the records of RDBs outside the range
-    s2sr_debug_trunk_form* forms(int g) { return t->form && g >= first && g < first + count ? t->form + 5 * (g - first) : spare; }
-};
-
-}  // namespace
-
-struct s2sr_handle {
-    s2sr_config cfg{};
-    // RealESRGAN_x2plus (cfg.scale 2) runs pixel_unshuffle(x, 2) and then the x4 net on the half grid.  Every entry takes input
-    // sizes: the trunk (workspace, mosaic, launch groups, graphs) is input / unshuffle(), the output input * cfg.scale.
-    int unshuffle() const { return cfg.scale == 2 ? 2 : 1; }
-    bool compact() const { return cfg.arch == S2SR_ARCH_COMPACT; }   // SRVGGNetCompact: cfg.num_block carries num_conv
-    hipStream_t stream = nullptr;
-    std::mutex mu;
-    std::string err;
-    std::vector<ConvW> convs;
-    // the packed weights of the 345 RDB convs, their fp8 scales and every conv's bias live in three pooled allocations
-    // (ConvW pointers point into them); only the six head/tail convs own separate buffers (pooled == false)
-    char* pool_w = nullptr;
-    int32_t* pool_s = nullptr;
-    float* pool_b = nullptr;
-    bool has_weights = false;
-    char* d_trash = nullptr;      // parking area for out-of-image epilogue stores
-    Workspace ws;
-    // scratch device buffers (grown on demand)
-    void* d_scratch[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[6] = {0, 0, 0, 0, 0, 0};
-    int capture_failures = 0;            // captures voided by a device-wide call of another runtime user; 3 -> graphs off
-    int tiles_slot = -1;                 // scratch slot that still holds the tile level the last pyramid call produced (-1: none)
-    int tiles_nx = 0, tiles_ny = 0;
-    int warp_slot = -1, warp_h = 0, warp_w = 0;   // ... and the RGBA raster the last warp produced (s2sr_tiles_base_u8 with rgba == NULL)
-    // profiling
-    int prof = 0;                 // 0 off, N>=1: bracket every N-th launch of each family with events
-    bool span_on = false;         // a sampled span of consecutive launches of ONE family is open (span_begin / span_end): its launches
-    EvRec span;                   // add their work to it instead of recording events of their own.  Two marker packets between two
-    int64_t span_count = 0;       // kernels cost ~2 us of a 70-us launch (r03: 71.6 us by events against 69.0 by rocprofv3); one pair around
-                                  // the four conv1-4 launches of an RDB spreads that over four
-    int64_t fam_count[16] = {0};
-    std::vector<EvRec> evs;
-    std::vector<hipEvent_t> ev_pool;
-    s2sr_kstat stats[F_COUNT];
-    hipStream_t copy_stream = nullptr;          // device-to-host copies behind the compute stream
-    std::vector<hipEvent_t> group_done;
-    void* stage_buf[2] = {nullptr, nullptr};    // pinned staging slices of the device-to-host path (d2h_staged)
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    bool d2h_staged_on = true;                  // S2SR_D2H_STAGED=0: hipMemcpyAsync straight into the caller's (pageable) buffer
-    // hipGraph replay of repeated groups
-    float* d_calib = nullptr;     // fp8 calibration: [0] max |x| of the trunk, [1] max |x_k| of the growth planes (device)
-    bool fp8_hp_tail = false;     // S2SR_PREC_FP8: the six head / tail convs in plain fp16 (their ~2e-3 is below the trunk's e4m3
-                                  // error) unless S2SR_FP8_TAIL=hp asks for the split-operand forms
-    int lo_exp = 12;              // fp16 modes, one-wave-per-SIMD trunk: the trunk's lo half as e4m3(lo * 2^lo_exp): exact to 4 bits for
-                                  // |x| < 2^(20 - lo_exp) = 256, clamped beyond (S2SR_LO_EXP)
-    int fp8_x_exp = 3, fp8_g_exp = 5;   // S2SR_PREC_FP8 activation scales 2^e of the x / growth planes (S2SR_FP8_XEXP, S2SR_FP8_GEXP); calibrated
-                                        // on the synthetic set: profiles/r02_fp8_scale_sweep.txt (|x| up to 56, |x_k| up to 14 before clipping)
-    int fp8_x_exp0 = 3, fp8_g_exp0 = 5; // ... as s2sr_create left them: every weight load starts from these again (a calibration belongs to the weights it saw)
-    bool graphs_on = true;        // S2SR_GRAPH=0 turns it off
-    int64_t ws_allocs = 0;        // workspace (re)allocations since s2sr_create (s2sr_debug_get_config reserved[5])
-    bool last_fold = true;        // S2SR_LAST_FOLD=0: conv_last (hp) reads all four e4m3 planes (8 stages) instead of folding w_lo into idle couts
-    bool f16_full = true;         // S2SR_F16_FULL=0: fp16 conv1-4 never take the whole-patch form (no px_live arithmetic in the epilogue) on 32-multiple launches
-    bool small8 = true;           // S2SR_SMALL8=0: single tiles keep the 16x32-patch form of fp16 conv1-4 (default: 8x32 patches, 256 per 256x256 tile)
-    bool mosaic_on = true;        // S2SR_MOSAIC=0: windows that are no multiple of the 32-pixel patch travel one per image (ConvParams::mos_*)
-    // paste maps of the window plan last stitched through s2sr_stitch_rows_u8_dev (row map, column map), kept on the device:
-    // an AOI is stitched band by band, the maps are uploaded once per (H, W, tile, pad)
-    // (a small LRU of map sets: a service that alternates AOI sizes neither re-uploads nor synchronises the device per job)
-    struct StitchMaps { int key[4] = {0, 0, 0, 0}; int32_t* d = nullptr; size_t cap = 0; uint64_t last_use = 0; };
-    StitchMaps stitch_sets[4];
-    uint64_t stitch_clock = 0;
-    hipEvent_t host_copy_ev = nullptr;          // s2sr_copy_to_host: orders the copy stream behind the caller's stream
-    void* host_arena = nullptr;                 // page-locked host block of the tile-PNG stage (stats back, plan up): grown on demand, kept
-    size_t host_arena_bytes = 0;
-    // the banded post-process in progress on this handle (s2sr_pp_band_*_dev, enhance_impl): geometry, channel order, how far the
-    // CLAHE'd rows and the finished rows reach
-    struct PPBand {
-        bool open = false, lut = false;
-        int H = 0, W = 0, bgr = 0, swap_out = 0, radius = 0;
-        int applied_end = 0, rows_end = 0;
-        s2sr_pp_params prm{};
-    } ppb;
-    std::vector<GraphEntry> graphs;
-    uint64_t graph_clock = 0;
-    int64_t graph_replays = 0, graph_captures = 0;
-    // where the last run_net left the trunk output conv_body reads (it differs between the w4, fp8 and 8-wave paths);
-    // read by s2sr_debug_forward_taps only
-    struct TrunkRec { const char* hi = nullptr; uint64_t hi_img = 0; const char* lo = nullptr; uint64_t lo_img = 0; int lo_exp = -1; } trunk_rec;
-    TrunkTap* ttap = nullptr;     // s2sr_debug_trunk_taps' batch is running (run_net taps the trunk at its RDB boundaries); null otherwise
-    CompactTap* ctap = nullptr;   // s2sr_debug_compact_taps' batch is running
-};
-
-namespace {
-
-int fail(s2sr_handle* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    else g_create_error = msg;
-    return code;
-}
-
-#define HIPCHK(h, expr)                                                                        \
-    do {                                                                                       \
-        hipError_t e__ = (expr);                                                               \
-        if (e__ != hipSuccess) {                                                               \
-            char b__[512];                                                                     \
-            snprintf(b__, sizeof b__, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return fail(h, S2SR_E_HIP, b__);                                                   \
-        }                                                                                      \
-    } while (0)
 
 struct ConvSpec {
     int cin, cout;
@@ -269,107 +71,7 @@ void drop_graphs(s2sr_handle* h) {   // buffers or weights moved: every captured
     h->graphs.clear();
 }
 
-// A capture that another user of the runtime voided (their hipDeviceSynchronize / hipFree while this handle captured: the device
-// gate only covers this library) leaves the stream in the "invalidated" state for good -- hipStreamEndCapture reports the error
-// but every later operation on the stream still fails.  The host-facing calls that run on the handle's own stream check for that
-// after a failure, replace the stream and run again (inputs are untouched, outputs are rewritten); after three such captures
-// the handle stops capturing.  Callers that pass their own stream (the *_dev calls) get the error.
-bool recover_stream(s2sr_handle* h) {
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (hipSetDevice(h->cfg.device) != hipSuccess) return false;
-    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
-    const hipError_t e = hipStreamIsCapturing(h->stream, &status);
-    (void)hipGetLastError();
-    if (e == hipSuccess && status == hipStreamCaptureStatusNone) return false;       // the failure was something else
-    hipStream_t fresh = nullptr;
-    if (hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking) != hipSuccess) return false;
-    hipStreamDestroy(h->stream);
-    (void)hipGetLastError();
-    h->stream = fresh;
-    drop_graphs(h);
-    if (++h->capture_failures >= 3) h->graphs_on = false;
-    return true;
-}
-#define RUN_WITH_STREAM_RECOVERY(h, call)            \
-    do {                                             \
-        int rc_ = (call);                            \
-        if (rc_ != S2SR_OK && (h) && recover_stream(h)) rc_ = (call); \
-        return rc_;                                  \
-    } while (0)
-
-int ensure_scratch(s2sr_handle* h, int slot, size_t bytes) {
-    h->tiles_slot = -1;                  // whoever asks for scratch is about to overwrite it; the pyramid calls set it again
-    h->warp_slot = -1;
-    if (h->scratch_bytes[slot] >= bytes) return S2SR_OK;
-    if (h->d_scratch[slot]) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        drop_graphs(h);
-        HIPCHK(h, dev_free(h->d_scratch[slot]));
-        h->d_scratch[slot] = nullptr;
-        h->scratch_bytes[slot] = 0;
-    }
-    HIPCHK(h, dev_malloc(&h->d_scratch[slot], bytes));
-    h->scratch_bytes[slot] = bytes;
-    return S2SR_OK;
-}
-
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// Blocking copies / fills go through one of the handle's own (non-blocking) streams, never the legacy stream: the runtime refuses
-// any legacy-stream operation (hipMemcpy, hipMemset) while ANY stream of the process captures a graph, and it also invalidates
-// that capture -- two handles on two threads (the x4 and the anime engine under Starlette's pool) hit exactly that in the r04 soak.
-hipError_t copy_blocking(s2sr_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
-    hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, h->stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
-}
-hipError_t fill_blocking(s2sr_handle* h, void* dst, int value, size_t bytes) {
-    hipError_t e = hipMemsetAsync(dst, value, bytes, h->stream);
-    return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
-}
-
-// ---- the test hooks' decoders (s2sr_debug_forward_taps, s2sr_debug_trunk_taps)
-float e4m3_to_f32(uint8_t b) {   // OCP e4m3fn: bias 7, subnormals, 0x7f / 0xff = NaN
-    const int e = (b >> 3) & 15, m = b & 7;
-    float v = e == 0 ? ldexpf((float)m, -9) : ldexpf((float)(8 + m), e - 10);
-    if ((b & 0x7f) == 0x7f) v = NAN;
-    return (b & 0x80) ? -v : v;
-}
-typedef _Float16 hf16;
-struct DevBuf {   // frees on scope exit: the hooks have many early returns
-    void* p = nullptr;
-    ~DevBuf() { if (p) dev_free(p); }
-};
-// n images of `nb` planes of `blk` bytes (32 B per pixel) at `img` bytes apart -> buf (blocking, on the handle's stream)
-int fetch_planes(s2sr_handle* h, std::vector<uint8_t>& buf, const char* src, uint64_t img, int n, int nb, size_t blk) {
-    buf.resize((size_t)n * nb * blk);
-    for (int i = 0; i < n; ++i) HIPCHK(h, copy_blocking(h, buf.data() + (size_t)i * nb * blk, src + (size_t)i * img, (size_t)nb * blk, hipMemcpyDeviceToHost));
-    return S2SR_OK;
-}
-// fp16 blocked-16: 16 channels per plane -> dst [n][16 nb][Hp][Wp]
-int decode_f16_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img, int n, int nb, size_t blk) {
-    std::vector<uint8_t> buf;
-    if (int r = fetch_planes(h, buf, src, img, n, nb, blk)) return r;
-    const size_t np = blk / 32;
-    const hf16* v = (const hf16*)buf.data();
-    for (int i = 0; i < n; ++i)
-        for (int b = 0; b < nb; ++b)
-            for (size_t q = 0; q < np; ++q)
-                for (int c = 0; c < 16; ++c)
-                    dst[(((size_t)i * nb * 16 + b * 16 + c) * np) + q] = (float)v[(((size_t)i * nb + b) * np + q) * 16 + c];
-    return S2SR_OK;
-}
-// e4m3 planes of 32 channels, plane b's values times scale[b] -> dst [n][32 nb][Hp][Wp]
-int decode_e4m3_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img, int n, int nb, size_t blk, const float* scale) {
-    std::vector<uint8_t> buf;
-    if (int r = fetch_planes(h, buf, src, img, n, nb, blk)) return r;
-    const size_t np = blk / 32;
-    for (int i = 0; i < n; ++i)
-        for (int b = 0; b < nb; ++b)
-            for (size_t q = 0; q < np; ++q)
-                for (int c = 0; c < 32; ++c)
-                    dst[(((size_t)i * nb * 32 + b * 32 + c) * np) + q] = e4m3_to_f32(buf[(((size_t)i * nb + b) * np + q) * 32 + c]) * scale[b];
-    return S2SR_OK;
-}
 
 int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mos_px = 0) {
     Workspace& w = h->ws;
@@ -386,23 +88,26 @@ int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mo
     }
     w.G = G; w.H = H; w.W = W; w.hp = hp; w.fp8 = fp8; w.mos_py = mos_py; w.mos_px = mos_px;
     w.Hp = padded(H); w.Wp = padded(W);
+    auto alloc_zeroed = [&](size_t bytes) -> int {    // both layouts: one allocation, zeroed
+        const hipError_t em = dev_malloc(&w.base, bytes);
+        if (em != hipSuccess) {                       // leave a clean "no workspace" state: the caller may retry with a smaller group
+            (void)hipGetLastError();
+            w = Workspace();
+            char b[200];
+            snprintf(b, sizeof b, "workspace of %.1f GB for %d images of %dx%d: %s", (double)bytes / 1e9, G, H, W, hipGetErrorString(em));
+            return fail(h, em == hipErrorOutOfMemory ? S2SR_E_CAPACITY : S2SR_E_HIP, b);
+        }
+        w.bytes = bytes;
+        HIPCHK(h, fill_blocking(h, w.base, 0, w.bytes));   // the zero halos
+        ++h->ws_allocs;
+        return S2SR_OK;
+    };
     if (h->compact()) {
         // SRVGGNetCompact: the packed input (1 block) and two 64-channel fp16 tensors (D[0], D[1]: 4 blocks each) that the
         // layers ping-pong between -- 288 B per padded LR pixel; everything stays at input resolution
         w.blk1 = (size_t)w.Hp * w.Wp * 32;
         const size_t g = (size_t)G, bP0 = align256(g * w.blk1), bA = align256(g * 4 * w.blk1);
-        w.bytes = bP0 + 2 * bA;
-        const hipError_t em = dev_malloc(&w.base, w.bytes);
-        if (em != hipSuccess) {
-            (void)hipGetLastError();
-            const size_t want = w.bytes;
-            w = Workspace();
-            char b[200];
-            snprintf(b, sizeof b, "workspace of %.1f GB for %d images of %dx%d: %s", (double)want / 1e9, G, H, W, hipGetErrorString(em));
-            return fail(h, em == hipErrorOutOfMemory ? S2SR_E_CAPACITY : S2SR_E_HIP, b);
-        }
-        HIPCHK(h, fill_blocking(h, w.base, 0, w.bytes));   // the zero halos
-        ++h->ws_allocs;
+        if (int rc = alloc_zeroed(bP0 + 2 * bA)) return rc;
         w.P0 = w.base; w.D[0] = w.base + bP0; w.D[1] = w.base + bP0 + bA;
         return S2SR_OK;
     }
@@ -430,19 +135,7 @@ int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mo
         for (int i = 0; i < 3; ++i) oXh[i] = take(g * 4 * w.blk1);
         oTz = take(g * 4 * w.blk1);
     }
-    w.bytes = off;
-    {
-        const hipError_t em = dev_malloc(&w.base, w.bytes);
-        if (em != hipSuccess) {                       // leave a clean "no workspace" state: the caller may retry with a smaller group
-            (void)hipGetLastError();
-            w = Workspace();
-            char b[200];
-            snprintf(b, sizeof b, "workspace of %.1f GB for %d images of %dx%d: %s", (double)off / 1e9, G, H, W, hipGetErrorString(em));
-            return fail(h, em == hipErrorOutOfMemory ? S2SR_E_CAPACITY : S2SR_E_HIP, b);
-        }
-    }
-    HIPCHK(h, fill_blocking(h, w.base, 0, w.bytes));   // the zero halos
-    ++h->ws_allocs;
+    if (int rc = alloc_zeroed(off)) return rc;
     w.P0 = w.base + oP0; w.D[0] = w.base + oD0; w.D[1] = w.base + oD1; w.D[2] = w.base + oD2; w.U0 = w.base + oU0;
     w.T = w.base + oT; w.Tr[0] = w.base + oT0; w.Tr[1] = w.base + oT1; w.Tr[2] = w.base + oT2; w.R = (float*)(w.base + oR); w.F = (float*)(w.base + oF);
     w.U1 = w.base + oU1; w.U2 = w.base + oU2; w.U3 = w.base + oU3;
@@ -454,38 +147,6 @@ int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mo
     }
     return S2SR_OK;
 }
-
-hipEvent_t get_event(s2sr_handle* h) {
-    if (!h->ev_pool.empty()) {
-        hipEvent_t e = h->ev_pool.back();
-        h->ev_pool.pop_back();
-        return e;
-    }
-    hipEvent_t e;
-    hipEventCreate(&e);
-    return e;
-}
-
-struct Scope {   // brackets one launch with events when profiling is on
-    s2sr_handle* h;
-    hipStream_t st;
-    EvRec r;
-    bool on;
-    Scope(s2sr_handle* h_, hipStream_t st_, int fam, double flops, double bytes) : h(h_), st(st_), on(false) {
-        if (h->prof <= 0) return;
-        if (h->span_on && h->span.fam == fam) { h->span.flops += flops; h->span.bytes += bytes; h->span.n += 1; return; }
-        on = (h->fam_count[fam]++ % h->prof) == 0;
-        if (!on) return;
-        r.fam = fam; r.flops = flops; r.bytes = bytes;
-        r.e0 = get_event(h); r.e1 = get_event(h);
-        hipEventRecord(r.e0, st);
-    }
-    ~Scope() {
-        if (!on) return;
-        hipEventRecord(r.e1, st);
-        h->evs.push_back(r);
-    }
-};
 
 // a span: one event pair around the next launches of `fam` (every prof-th span is sampled, the others record nothing at all)
 void span_begin(s2sr_handle* h, hipStream_t st, int fam) {
@@ -517,6 +178,14 @@ int collect_events(s2sr_handle* h) {
     }
     h->evs.clear();
     return S2SR_OK;
+}
+
+// window mosaic: every launch gets the separator geometry at the scale of the coordinates its epilogue works in
+void mosaic_at(ConvParams& q, const Mosaic& mo, int scale) {
+    if (!mo.on()) return;
+    q.mos_py = (mo.wh + 1) * scale; q.mos_ry = mo.wh * scale; q.mos_px = (mo.ww + 1) * scale; q.mos_rx = mo.ww * scale;
+    q.mos_my = (uint32_t)(0x100000000ull / (uint32_t)q.mos_py) + 1u; q.mos_mx = (uint32_t)(0x100000000ull / (uint32_t)q.mos_px) + 1u;
+    q.mos_kx = mo.kx; q.mos_ky = mo.ky; q.mos_count = mo.count;
 }
 
 // one conv launch
@@ -615,11 +284,6 @@ int trunk_tap(s2sr_handle* h, hipStream_t st, int g) {
     return S2SR_OK;
 }
 
-// The layer schedule for `n` images already packed into ws.P0.  Exactly the op order of
-// RRDBNet.forward (cnn_super_resolution.py:140-158) with ResidualDenseBlock / RRDB inlined
-// (:85-91, :103-107).  The torch.cat of the dense block is "the first k blocks of D[cur]",
-// never a copy; conv5 writes the next x into the other dense tensor because neighbouring
-// workgroups still read this one's x as halo.
 // SRVGGNetCompact: first conv, num_conv PReLU convs ping-ponging between D[0] and D[1], the last conv with the pixel-shuffle
 // tail.  Every launch works at input resolution (the x4 happens in the last conv's stores), on the 8-wave form of conv3x3.hip.
 int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f32, uint8_t* d_out_u8, const Mosaic& mo) {
@@ -629,11 +293,7 @@ int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* 
     ConvParams b{};
     b.N = n; b.H = H; b.W = W; b.Hp = w.Hp; b.Wp = w.Wp; b.sHp = w.Hp; b.sWp = w.Wp;
     b.trash = h->d_trash; b.in_scale = 1.0f / 255.0f;
-    if (mo.on()) {
-        b.mos_py = mo.wh + 1; b.mos_ry = mo.wh; b.mos_px = mo.ww + 1; b.mos_rx = mo.ww;
-        b.mos_my = (uint32_t)(0x100000000ull / (uint32_t)b.mos_py) + 1u; b.mos_mx = (uint32_t)(0x100000000ull / (uint32_t)b.mos_px) + 1u;
-        b.mos_kx = mo.kx; b.mos_ky = mo.ky; b.mos_count = mo.count;
-    }
+    mosaic_at(b, mo, 1);
     const double px = (double)n * H * W;
     auto tap = [&](int layer, const char* act) -> int {       // s2sr_debug_compact_taps only
         if (!h->ctap) return S2SR_OK;
@@ -677,21 +337,19 @@ int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* 
     return S2SR_OK;
 }
 
+// The layer schedule for `n` images already packed into ws.P0.  Exactly the op order of
+// RRDBNet.forward (cnn_super_resolution.py:140-158) with ResidualDenseBlock / RRDB inlined
+// (:85-91, :103-107).  The torch.cat of the dense block is "the first k blocks of D[cur]",
+// never a copy; conv5 writes the next x into the other dense tensor because neighbouring
+// workgroups still read this one's x as halo.
 int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f32, uint8_t* d_out_u8, const Mosaic& mo = Mosaic()) {
     if (h->compact()) return run_net_compact(h, st, n, H, W, d_out_f32, d_out_u8, mo);
     Workspace& w = h->ws;
     const int nb = h->cfg.num_block;
-    // window mosaic: every launch gets the separator geometry at the scale of the coordinates its epilogue works in
-    auto mosaic_at = [&](ConvParams& q, int scale) {
-        if (!mo.on()) return;
-        q.mos_py = (mo.wh + 1) * scale; q.mos_ry = mo.wh * scale; q.mos_px = (mo.ww + 1) * scale; q.mos_rx = mo.ww * scale;
-        q.mos_my = (uint32_t)(0x100000000ull / (uint32_t)q.mos_py) + 1u; q.mos_mx = (uint32_t)(0x100000000ull / (uint32_t)q.mos_px) + 1u;
-        q.mos_kx = mo.kx; q.mos_ky = mo.ky; q.mos_count = mo.count;
-    };
     ConvParams b{};
     b.N = n; b.H = H; b.W = W; b.Hp = w.Hp; b.Wp = w.Wp; b.sHp = w.Hp; b.sWp = w.Wp;
     b.T = w.T; b.R = w.R; b.F = w.F;
-    mosaic_at(b, 1);
+    mosaic_at(b, mo, 1);
     int ci = 0, rc;
     const bool fp8 = w.fp8;
     {   // conv_first: 3 -> 64 (input = one 16-channel block)
@@ -808,7 +466,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         p.N = n; p.H = 2 * H; p.W = 2 * W; p.Hp = w.Hp2; p.Wp = w.Wp2; p.sHp = w.Hp; p.sWp = w.Wp;
         p.src = w.U0; p.src_img = 4 * w.blk1; p.dst = w.U1; p.dst_img = 4 * w.blk2;
         if (hp) { p.src_lo = w.U0lo; p.lo_img = 4 * w.blk1; p.T = w.U1lo; }
-        mosaic_at(p, 1);                                         // sub-pixel form: the epilogue walks SOURCE pixels
+        mosaic_at(p, mo, 1);                                         // sub-pixel form: the epilogue walks SOURCE pixels
         if ((rc = run_up_subpixel(h, st, h->convs[ci++], p, n, H, W, w.Hp, w.Wp, w.Hp2, w.Wp2))) return rc;
     }
     {   // conv_up2 on nearest-2x
@@ -816,12 +474,12 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         p.N = n; p.H = 4 * H; p.W = 4 * W; p.Hp = w.Hp4; p.Wp = w.Wp4; p.sHp = w.Hp2; p.sWp = w.Wp2;
         p.src = w.U1; p.src_img = 4 * w.blk2; p.dst = w.U2; p.dst_img = 4 * w.blk4;
         if (hp) { p.src_lo = w.U1lo; p.lo_img = 4 * w.blk2; p.T = w.U2lo; }
-        mosaic_at(p, 2);
+        mosaic_at(p, mo, 2);
         if ((rc = run_up_subpixel(h, st, h->convs[ci++], p, n, 2 * H, 2 * W, w.Hp2, w.Wp2, w.Hp4, w.Wp4))) return rc;
     }
     ConvParams hr{};
     hr.N = n; hr.H = 4 * H; hr.W = 4 * W; hr.Hp = w.Hp4; hr.Wp = w.Wp4; hr.sHp = w.Hp4; hr.sWp = w.Wp4;
-    mosaic_at(hr, 4);
+    mosaic_at(hr, mo, 4);
     {
         ConvParams p = hr;
         p.src = w.U2; p.src_img = 4 * w.blk4; p.dst = w.U3; p.dst_img = 4 * w.blk4;
@@ -835,6 +493,117 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         if ((rc = run_conv(h, st, F_LAST, h->convs[ci++], p, EPI_LAST, false))) return rc;
     }
     return S2SR_OK;
+}
+
+}  // namespace
+
+// ---- what the other engine files use too (declared in engine_internal.h)
+namespace s2sr::engine {
+
+int fail(s2sr_handle* h, int code, const std::string& msg) {
+    if (h) h->err = msg;
+    else g_create_error = msg;
+    return code;
+}
+
+// A capture that another user of the runtime voided (their hipDeviceSynchronize / hipFree while this handle captured: the device
+// gate only covers this library) leaves the stream in the "invalidated" state for good -- hipStreamEndCapture reports the error
+// but every later operation on the stream still fails.  The host-facing calls that run on the handle's own stream check for that
+// after a failure, replace the stream and run again (inputs are untouched, outputs are rewritten); after three such captures
+// the handle stops capturing.  Callers that pass their own stream (the *_dev calls) get the error.
+bool recover_stream(s2sr_handle* h) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (hipSetDevice(h->cfg.device) != hipSuccess) return false;
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    const hipError_t e = hipStreamIsCapturing(h->stream, &status);
+    (void)hipGetLastError();
+    if (e == hipSuccess && status == hipStreamCaptureStatusNone) return false;       // the failure was something else
+    hipStream_t fresh = nullptr;
+    if (hipStreamCreateWithFlags(&fresh, hipStreamNonBlocking) != hipSuccess) return false;
+    hipStreamDestroy(h->stream);
+    (void)hipGetLastError();
+    h->stream = fresh;
+    drop_graphs(h);
+    if (++h->capture_failures >= 3) h->graphs_on = false;
+    return true;
+}
+
+int ensure_scratch(s2sr_handle* h, int slot, size_t bytes) {
+    h->tiles_slot = -1;                  // whoever asks for scratch is about to overwrite it; the pyramid calls set it again
+    h->warp_slot = -1;
+    if (h->scratch_bytes[slot] >= bytes) return S2SR_OK;
+    if (h->d_scratch[slot]) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        drop_graphs(h);
+        HIPCHK(h, dev_free(h->d_scratch[slot]));
+        h->d_scratch[slot] = nullptr;
+        h->scratch_bytes[slot] = 0;
+    }
+    HIPCHK(h, dev_malloc(&h->d_scratch[slot], bytes));
+    h->scratch_bytes[slot] = bytes;
+    return S2SR_OK;
+}
+
+// Blocking copies / fills go through one of the handle's own (non-blocking) streams, never the legacy stream: the runtime refuses
+// any legacy-stream operation (hipMemcpy, hipMemset) while ANY stream of the process captures a graph, and it also invalidates
+// that capture -- two handles on two threads (the x4 and the anime engine under Starlette's pool) hit exactly that in the r04 soak.
+hipError_t copy_blocking(s2sr_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, h->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
+}
+hipError_t fill_blocking(s2sr_handle* h, void* dst, int value, size_t bytes) {
+    hipError_t e = hipMemsetAsync(dst, value, bytes, h->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
+}
+
+// ---- the test hooks' decoders (s2sr_debug_forward_taps, s2sr_debug_trunk_taps)
+float e4m3_to_f32(uint8_t b) {   // OCP e4m3fn: bias 7, subnormals, 0x7f / 0xff = NaN
+    const int e = (b >> 3) & 15, m = b & 7;
+    float v = e == 0 ? ldexpf((float)m, -9) : ldexpf((float)(8 + m), e - 10);
+    if ((b & 0x7f) == 0x7f) v = NAN;
+    return (b & 0x80) ? -v : v;
+}
+// n images of `nb` planes of `blk` bytes (32 B per pixel) at `img` bytes apart -> buf (blocking, on the handle's stream)
+int fetch_planes(s2sr_handle* h, std::vector<uint8_t>& buf, const char* src, uint64_t img, int n, int nb, size_t blk) {
+    buf.resize((size_t)n * nb * blk);
+    for (int i = 0; i < n; ++i) HIPCHK(h, copy_blocking(h, buf.data() + (size_t)i * nb * blk, src + (size_t)i * img, (size_t)nb * blk, hipMemcpyDeviceToHost));
+    return S2SR_OK;
+}
+// fp16 blocked-16: 16 channels per plane -> dst [n][16 nb][Hp][Wp]
+int decode_f16_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img, int n, int nb, size_t blk) {
+    std::vector<uint8_t> buf;
+    if (int r = fetch_planes(h, buf, src, img, n, nb, blk)) return r;
+    const size_t np = blk / 32;
+    const hf16* v = (const hf16*)buf.data();
+    for (int i = 0; i < n; ++i)
+        for (int b = 0; b < nb; ++b)
+            for (size_t q = 0; q < np; ++q)
+                for (int c = 0; c < 16; ++c)
+                    dst[(((size_t)i * nb * 16 + b * 16 + c) * np) + q] = (float)v[(((size_t)i * nb + b) * np + q) * 16 + c];
+    return S2SR_OK;
+}
+// e4m3 planes of 32 channels, plane b's values times scale[b] -> dst [n][32 nb][Hp][Wp]
+int decode_e4m3_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img, int n, int nb, size_t blk, const float* scale) {
+    std::vector<uint8_t> buf;
+    if (int r = fetch_planes(h, buf, src, img, n, nb, blk)) return r;
+    const size_t np = blk / 32;
+    for (int i = 0; i < n; ++i)
+        for (int b = 0; b < nb; ++b)
+            for (size_t q = 0; q < np; ++q)
+                for (int c = 0; c < 32; ++c)
+                    dst[(((size_t)i * nb * 32 + b * 32 + c) * np) + q] = e4m3_to_f32(buf[(((size_t)i * nb + b) * np + q) * 32 + c]) * scale[b];
+    return S2SR_OK;
+}
+
+hipEvent_t get_event(s2sr_handle* h) {
+    if (!h->ev_pool.empty()) {
+        hipEvent_t e = h->ev_pool.back();
+        h->ev_pool.pop_back();
+        return e;
+    }
+    hipEvent_t e;
+    hipEventCreate(&e);
+    return e;
 }
 
 constexpr int kCompactGroup = 16;
@@ -870,7 +639,7 @@ int group_size(const s2sr_handle* h, int B, int H, int W) {
 // full one: its first row / column past the end is a separator position of the full geometry, which no launch ever stores to.
 // The choice is made on what is LAUNCHED (r03 ADVICE: dividing the mosaic's area by kx * ky assumes every mosaic is full, and a
 // partly filled one costs as much as a full one -- 17 windows of 276 as two 4 x 4 mosaics launched 78 % more patches than 17 plain images).
-static void mosaic_remainder(int rem, int kx, int ky, int* rkx, int* rky) {
+void mosaic_remainder(int rem, int kx, int ky, int* rkx, int* rky) {
     *rky = (rem + kx - 1) / kx;
     if (*rky > ky) *rky = ky;
     *rkx = (*rky == 1) ? rem : kx;
@@ -878,17 +647,14 @@ static void mosaic_remainder(int rem, int kx, int ky, int* rkx, int* rky) {
 static long mosaic_area(int th, int tw, int kx, int ky) {   // 32 x 32 patches of one kx x ky mosaic image
     return (long)(roundup32(ky * (th + 1) - 1) / 32) * (roundup32(kx * (tw + 1) - 1) / 32);
 }
-static long mosaic_patches(int B, int th, int tw, int kx, int ky) {   // patches launched for B windows
+long mosaic_patches(int B, int th, int tw, int kx, int ky) {   // patches launched for B windows
     const int per = kx * ky, full = B / per, rem = B % per;
     long a = (long)full * mosaic_area(th, tw, kx, ky);
     if (rem) { int rkx, rky; mosaic_remainder(rem, kx, ky, &rkx, &rky); a += mosaic_area(th, tw, rkx, rky); }
     return a;
 }
-static Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw);
-// th x tw: input windows; the mosaic is laid out on the trunk grid (its wh x ww are trunk sizes)
-Mosaic pick_mosaic(const s2sr_handle* h, int B, int th, int tw) { return pick_mosaic_cfg(h->mosaic_on, B, th / h->unshuffle(), tw / h->unshuffle()); }
 // pure host arithmetic (s2sr_debug_pick_mosaic exposes it to the CPU tests)
-static Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw) {
+Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw) {
     Mosaic m;
     if (!mosaic_on || B < 2) return m;
     const long plain = (long)B * (roundup32(th) / 32) * (roundup32(tw) / 32);
@@ -921,6 +687,8 @@ static Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw) {
     m.kx = bkx; m.ky = bky; m.wh = th; m.ww = tw; m.count = B;
     return m;
 }
+// th x tw: input windows; the mosaic is laid out on the trunk grid (its wh x ww are trunk sizes)
+Mosaic pick_mosaic(const s2sr_handle* h, int B, int th, int tw) { return pick_mosaic_cfg(h->mosaic_on, B, th / h->unshuffle(), tw / h->unshuffle()); }
 
 // [B,th,tw,3] u8 (device) -> u8 [B,S th,S tw,3] and/or f32 [B,3,S th,S tw] (device), S = cfg.scale.  At scale 2 th and tw are even
 // and the net runs on the th/2 x tw/2 trunk grid.  `src_h` x `src_w` (0: th x tw): the rows / columns the single input image holds
@@ -930,7 +698,7 @@ static Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw) {
 // window count gave a short last chunk another image height, and with it a workspace reallocation, a device synchronise and
 // dropped graphs inside the chunk loop, on every call).  nullptr: choose from B.
 int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const float* d_x_f32, int B, int th, int tw,
-                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan = nullptr, int src_h = 0, int src_w = 0) {
+                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan, int src_h, int src_w) {
     if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
     if (B <= 0 || th <= 0 || tw <= 0) return fail(h, S2SR_E_INVALID, "bad batch/tile dims");
     const int u = h->unshuffle();
@@ -996,10 +764,9 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
         // the legacy null stream cannot be captured; profiling wants its events between launches
         GraphEntry* ge = nullptr;
         if (h->graphs_on && h->prof <= 0 && st != nullptr) {
+            const GraphKey key{n, th, tw, sh, sw, mo.on() ? sg.kx : 0, mo.on() ? sg.ky : 0, mo.on() ? nt : 0, in8, in32, o8, o32, st};
             for (GraphEntry& g : h->graphs)
-                if (g.n == n && g.th == th && g.tw == tw && g.sh == sh && g.sw == sw && g.in_u8 == in8 && g.in_f32 == in32 && g.out_u8 == o8 &&
-                    g.out_f32 == o32 && g.st == st && g.mos_kx == (mo.on() ? sg.kx : 0) && g.mos_ky == (mo.on() ? sg.ky : 0) &&
-                    g.mos_count == (mo.on() ? nt : 0)) { ge = &g; break; }
+                if (g.key == key) { ge = &g; break; }
             if (!ge) {   // first sighting: remember it, launch directly (also warms the per-kernel attributes)
                 if (h->graphs.size() >= 24) {
                     size_t victim = 0;
@@ -1009,8 +776,7 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
                     h->graphs.erase(h->graphs.begin() + victim);
                 }
                 GraphEntry g;
-                g.n = n; g.th = th; g.tw = tw; g.sh = sh; g.sw = sw; g.in_u8 = in8; g.in_f32 = in32; g.out_u8 = o8; g.out_f32 = o32; g.st = st;
-                g.mos_kx = mo.on() ? sg.kx : 0; g.mos_ky = mo.on() ? sg.ky : 0; g.mos_count = mo.on() ? nt : 0;
+                g.key = key;
                 g.last_use = ++h->graph_clock;
                 h->graphs.push_back(g);
                 ge = nullptr;
@@ -1050,7 +816,7 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
     return S2SR_OK;
 }
 
-}  // namespace
+}  // namespace s2sr::engine
 
 // ==========================================================================================
 // C ABI
@@ -1175,9 +941,6 @@ void s2sr_destroy(s2sr_handle* h) {
     delete h;
 }
 
-// Weights in, by either door.  `d_blob` is the fp32 blob ON THE DEVICE (the host entry uploads it first): the 345 RDB convs
-// are repacked by device kernels straight from it (pack.hip), every bias is gathered on the device; only the six head/tail
-// convs (0.9 MB of the 67 MB) come back to the host, because their split-operand / sub-pixel packers are host code.
 // SRVGGNetCompact: 1.2 M parameters -- the blob comes to the host whole and every conv goes through pack_conv_weights (plain
 // fp16, one segment).  The last conv's 48 output channels are placed in the rows the pixel-shuffle epilogue wants
 // (compact_last_row_channel); bias and slopes stay fp32.
@@ -1238,6 +1001,9 @@ static int load_weights_compact(s2sr_handle* h, const float* d_blob, size_t n_fl
     return S2SR_OK;
 }
 
+// Weights in, by either door.  `d_blob` is the fp32 blob ON THE DEVICE (the host entry uploads it first): the 345 RDB convs
+// are repacked by device kernels straight from it (pack.hip), every bias is gathered on the device; only the six head/tail
+// convs (0.9 MB of the 67 MB) come back to the host, because their split-operand / sub-pixel packers are host code.
 static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_floats, hipStream_t st) {
     if (h->compact()) return load_weights_compact(h, d_blob, n_floats, st);
     const std::vector<ConvSpec> specs = conv_specs(h->cfg.num_block, h->cfg.scale);
@@ -1378,35 +1144,6 @@ int s2sr_load_weights_dev(s2sr_handle* h, const void* d_blob, size_t n_floats, v
     return load_weights_locked(h, (const float*)d_blob, n_floats, h->stream);
 }
 
-int s2sr_plan_tiles(int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t scale, s2sr_window* out, int32_t cap,
-                    int32_t* n) {
-    if (H <= 0 || W <= 0 || tile <= 0 || pad < 0 || scale <= 0 || !n) return S2SR_E_INVALID;
-    const int nx = (W + tile - 1) / tile, ny = (H + tile - 1) / tile;
-    *n = nx * ny;
-    if (!out) return S2SR_OK;
-    if (cap < nx * ny) return S2SR_E_CAPACITY;
-    const int win = tile + 2 * pad, op = pad * scale;
-    for (int y = 0; y < ny; ++y)
-        for (int x = 0; x < nx; ++x) {
-            s2sr_window& w = out[y * nx + x];
-            // far edge first, then pull the near edge in so the window keeps its full extent
-            w.x2 = (x * tile + win < W) ? x * tile + win : W;
-            w.y2 = (y * tile + win < H) ? y * tile + win : H;
-            w.x1 = (w.x2 - win > 0) ? w.x2 - win : 0;
-            w.y1 = (w.y2 - win > 0) ? w.y2 - win : 0;
-            // the halo is dropped on every side that has a neighbouring tile INDEX
-            w.crop_left = x > 0 ? op : 0;
-            w.crop_top = y > 0 ? op : 0;
-            w.crop_right = x < nx - 1 ? op : 0;
-            w.crop_bottom = y < ny - 1 ? op : 0;
-            w.ox1 = w.x1 * scale + w.crop_left;
-            w.oy1 = w.y1 * scale + w.crop_top;
-            w.ox2 = w.x2 * scale - w.crop_right;
-            w.oy2 = w.y2 * scale - w.crop_bottom;
-        }
-    return S2SR_OK;
-}
-
 int s2sr_forward_batch_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int32_t th, int32_t tw, void* d_out,
                               void* stream) {
     if (!h || !d_tiles || !d_out) return S2SR_E_INVALID;
@@ -1425,54 +1162,6 @@ int s2sr_forward_part_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const Mosaic mo = pick_mosaic(h, job_windows, th, tw);
     return forward_dev(h, (hipStream_t)stream, (const uint8_t*)d_tiles, nullptr, B, th, tw, (uint8_t*)d_out, nullptr, mo.on() ? &mo : nullptr);
-}
-
-// Device -> caller's host buffer, `bytes` from `src`, ordered behind everything already on the copy stream; returns when the
-// bytes are in `dst`.  The caller's buffer is ordinary pageable memory (a numpy array): handed to hipMemcpyAsync directly, the
-// runtime moves it with copy KERNELS through its own staging at ~6 GB/s, and those kernels take CUs from the persistent conv
-// workgroups of the chunk computing meanwhile (4096 x 4096 AOI: +20 ms of compute under 130 ms of copies).  Here: two pinned
-// 32-MB slices filled by the DMA engines (pinned destination), emptied by this thread's memcpy while the next slice flies.
-static constexpr size_t kStageBytes = 32u << 20;
-// `exposed`: nothing computes under this copy (the last band, or the only one): below 128 MB the runtime's own path is then as
-// fast or faster (50 MB: 58.1 vs 60.3 ms per 1024 x 1024 call), and there are no conv workgroups for its copy kernels to displace.
-static bool is_pinned_host(const void* p) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-        (void)hipGetLastError();   // an ordinary malloc'd pointer is "invalid value" to the runtime: not an error of ours
-        return false;
-    }
-    return a.type == hipMemoryTypeHost;
-}
-
-static int d2h_staged(s2sr_handle* h, uint8_t* dst, const uint8_t* src, size_t bytes, bool exposed) {
-    if (is_pinned_host(dst)) {   // s2sr_host_alloc'd (or registered) destination: one DMA, nothing for this thread to copy
-        HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->copy_stream));
-        HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-        return S2SR_OK;
-    }
-    if (!h->d2h_staged_on || bytes < (exposed ? (128u << 20) : (24u << 20))) {
-        HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->copy_stream));
-        HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-        return S2SR_OK;
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (!h->stage_buf[i]) HIPCHK(h, host_malloc(&h->stage_buf[i], kStageBytes, hipHostMallocDefault));
-        if (!h->stage_ev[i]) HIPCHK(h, hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming));
-    }
-    const size_t nsl = (bytes + kStageBytes - 1) / kStageBytes;
-    auto len = [&](size_t k) { return k + 1 < nsl ? kStageBytes : bytes - k * kStageBytes; };
-    for (size_t k = 0; k < nsl + 2; ++k) {
-        const int i = (int)(k & 1);
-        if (k >= 2) {   // slice k-2 sits in buffer i
-            HIPCHK(h, hipEventSynchronize(h->stage_ev[i]));
-            memcpy(dst + (k - 2) * kStageBytes, h->stage_buf[i], len(k - 2));
-        }
-        if (k < nsl) {
-            HIPCHK(h, hipMemcpyAsync(h->stage_buf[i], src + k * kStageBytes, len(k), hipMemcpyDeviceToHost, h->copy_stream));
-            HIPCHK(h, hipEventRecord(h->stage_ev[i], h->copy_stream));
-        }
-    }
-    return S2SR_OK;
 }
 
 int s2sr_host_alloc(size_t bytes, void** out) {
@@ -1559,908 +1248,6 @@ static int forward_f32_once(s2sr_handle* h, const float* x, int32_t N, int32_t H
 
 int s2sr_forward_f32(s2sr_handle* h, const float* x, int32_t N, int32_t H, int32_t W, float* y) {
     RUN_WITH_STREAM_RECOVERY(h, forward_f32_once(h, x, N, H, W, y));
-}
-
-// host-side maps of the paste rule; shared by enhance and the multi-GPU stitch
-static void build_stitch_maps(const std::vector<s2sr_window>& wins, int nx, int ny, int OH, int OW,
-                              std::vector<int32_t>& rm, std::vector<int32_t>& cm) {
-    rm.assign(2 * (size_t)OH, -1);
-    cm.assign(2 * (size_t)OW, -1);
-    // last window in loop order wins (:278): ascending index, later entries overwrite the map
-    for (int y = 0; y < ny; ++y) {
-        const s2sr_window& w = wins[(size_t)y * nx];
-        for (int oy = w.oy1; oy < w.oy2; ++oy) { rm[2 * oy] = y; rm[2 * oy + 1] = oy - w.oy1 + w.crop_top; }
-    }
-    for (int x = 0; x < nx; ++x) {
-        const s2sr_window& w = wins[x];
-        for (int ox = w.ox1; ox < w.ox2; ++ox) { cm[2 * ox] = x; cm[2 * ox + 1] = ox - w.ox1 + w.crop_left; }
-    }
-}
-
-// RealESRGAN.enhance (cnn_super_resolution.py:217-234) incl. _tile_process (:236-280)
-// Chunk sizes of a tiled enhance(), front to back, in row units (pure host arithmetic; s2sr_debug_plan_chunks exposes it to the
-// CPU tests).  `unit_windows` windows per row unit, `per` windows per launch image (a mosaic; 1 without), `pimg` 32 x 32 patches per
-// launch image, `ncu` persistent workgroups.  The tail (last, middle) is searched for the fewest trunk-conv rounds plus the
-// exposed copy of the last band; what is left goes in front in pieces of at most u_max units.
-static void plan_chunk_sizes(int units, int u_max, long unit_windows, int per, long pimg, int ncu, std::vector<int>& sizes) {
-    sizes.clear();
-    if (units <= 0) return;
-    if (u_max < 1) u_max = 1;
-    if (per < 1) per = 1;
-    if (ncu < 1) ncu = 1;
-    auto rounds = [&](int u) -> double {                                        // trunk-conv rounds of a chunk of u units
-        const long imgs = ((long)u * unit_windows + per - 1) / per;
-        return (double)((imgs * pimg + ncu - 1) / ncu);
-    };
-    const double copy_per_unit = (double)unit_windows * pimg / per / ncu / 6.0;  // exposed copy of one unit, in rounds
-    int best_last = 1, best_mid = 0;
-    double best = 1e300;
-    for (int last = 1; last <= 3 && last <= units; ++last)
-        for (int mid = 0; mid <= 12 && last + mid <= units; ++mid) {
-            if (mid > u_max || last > u_max || mid > 5 * last) continue;         // a band's copy must fit under the next chunk's compute (~6x)
-            const int front = units - last - mid;
-            if (front > 0 && mid == 0 && front > 5 * last) continue;            // a big chunk straight in front of the last one
-            if (front > 0 && mid > 0 && front > 6 * mid && front <= u_max) continue;
-            double c = rounds(last) + (mid ? rounds(mid) : 0.0) + last * copy_per_unit;
-            for (int left = front; left > 0;) { const int u = left < u_max ? left : u_max; c += rounds(u); left -= u; }
-            if (c < best - 1e-9) { best = c; best_last = last; best_mid = mid; }
-        }
-    for (int left = units - best_last - best_mid; left > 0;) { const int u = left < u_max ? left : u_max; sizes.push_back(u); left -= u; }
-    if (best_mid) sizes.push_back(best_mid);
-    sizes.push_back(best_last);
-}
-
-int s2sr_debug_pick_mosaic(int32_t B, int32_t th, int32_t tw, int32_t* kx, int32_t* ky) {
-    if (!kx || !ky || B < 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
-    const Mosaic m = pick_mosaic_cfg(true, B, th, tw);
-    *kx = m.on() ? m.kx : 1; *ky = m.on() ? m.ky : 1;
-    return S2SR_OK;
-}
-
-int s2sr_debug_mosaic_patches(int32_t B, int32_t th, int32_t tw, int64_t* launched, int64_t* plain) {
-    if (!launched || !plain || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
-    const Mosaic m = pick_mosaic_cfg(true, B, th, tw);
-    *plain = (int64_t)B * (roundup32(th) / 32) * (roundup32(tw) / 32);
-    *launched = m.on() ? (int64_t)mosaic_patches(B, th, tw, m.kx, m.ky) : *plain;
-    return S2SR_OK;
-}
-
-int s2sr_debug_plan_chunks(int32_t units, int32_t u_max, int32_t unit_windows, int32_t per, int32_t pimg, int32_t ncu, int32_t* sizes,
-                           int32_t cap, int32_t* n) {
-    if (!n || units < 0 || cap < 0 || (cap > 0 && !sizes)) return S2SR_E_INVALID;
-    std::vector<int> v;
-    plan_chunk_sizes(units, u_max, unit_windows, per, pimg, ncu, v);
-    *n = (int32_t)v.size();
-    if ((int)v.size() > cap) return cap == 0 ? S2SR_OK : S2SR_E_CAPACITY;
-    for (size_t i = 0; i < v.size(); ++i) sizes[i] = v[i];
-    return S2SR_OK;
-}
-
-static int postprocess_dev_locked(s2sr_handle* h, const void* d_rgb, int32_t B, int32_t H, int32_t W, const s2sr_pp_params* prm,
-                                  void* d_out, hipStream_t st);
-static int pp_band_begin_locked(s2sr_handle* h, int H, int W, const s2sr_pp_params* prm, int order, hipStream_t st);
-static int pp_band_hist_locked(s2sr_handle* h, const void* d_img, int y0, int y1, hipStream_t st);
-static int pp_band_lut_locked(s2sr_handle* h, hipStream_t st);
-static int pp_band_rows_locked(s2sr_handle* h, const void* d_img, int y0, int y1, void* d_out, hipStream_t st);
-
-// The image a tile plan is made for.  Scale 2: H x W reflect-padded by one row / column at the bottom / right to even sizes
-// (RealESRGANer's mod-2 rule; the pad is read by index, see pack.hip), and an even tile, so that every window of the padded image
-// has even origin and extent.
-static int plan_dims(s2sr_handle* h, int H, int W, int tile, int* PH, int* PW) {
-    *PH = H; *PW = W;
-    if (h->unshuffle() == 1) return S2SR_OK;
-    if (H < 2 || W < 2) return fail(h, S2SR_E_INVALID, "scale 2 needs an image of at least 2 x 2 (the mod-2 reflect pad)");
-    if (tile % 2) return fail(h, S2SR_E_INVALID, "scale 2 needs an even tile: every window of the padded image must have even origin and size");
-    *PH = H + (H & 1); *PW = W + (W & 1);
-    return S2SR_OK;
-}
-
-// job_rgb: the caller's image is RGB and wants RGB back -- R and B are swapped on the device in front of and behind the net (the
-// reference's cvtColor pair, wow_sr.py:85,103).  prm: the crop-visibility post-process (wow_sr.py:187-209) on the stitched RGB
-// image, on the device, before the one copy out (it is image-global: no band leaves before the whole mosaic is done).
-static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int tile, int pad, uint8_t* out_u8,
-                        float* out_f32, bool force_tiled = false, bool job_rgb = false, const s2sr_pp_params* prm = nullptr) {
-    if (!h || !img || (!out_u8 && !out_f32) || H <= 0 || W <= 0 || tile <= 0 || pad < 0) return S2SR_E_INVALID;
-    if ((job_rgb || prm) && !out_u8) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    int rc, PH, PW;
-    if ((rc = plan_dims(h, H, W, tile, &PH, &PW))) return rc;
-    // scale 2, odd H or W: everything below runs on the padded PH x PW image; the output is cropped to OH x OW by the stitch maps
-    const bool reflect = PH != H || PW != W;
-    const int scale = h->cfg.scale, u = h->unshuffle(), OH = H * scale, OW = W * scale, OHp = PH * scale, OWp = PW * scale;
-    const size_t ib = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
-    if ((rc = ensure_scratch(h, 0, ib))) return rc;
-    if ((rc = ensure_scratch(h, 1, opx * (out_f32 ? 4 : 1)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, ib, hipMemcpyHostToDevice, st));
-    if (job_rgb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[0], (size_t)H * W, (uint8_t*)h->d_scratch[0], st));
-    const bool whole_finish = job_rgb || prm != nullptr;      // the image leaves in one piece, behind the device-side finish
-    const bool tiled = force_tiled || (long long)PH * PW > (long long)tile * tile * 4;   // strict '>' (:226)
-    if (!tiled) {
-        if (out_f32 || reflect) {
-            // net output is NCHW (f32; enhance() returns HWC) or the padded image's (u8, odd scale-2 image) -> stitch with an
-            // identity map, cropped to OH x OW
-            const size_t opxp = (size_t)OHp * OWp * 3;
-            if ((rc = ensure_scratch(h, 2, opxp * (out_f32 ? 4 : 1)))) return rc;
-            rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[0], nullptr, 1, PH, PW, out_f32 ? nullptr : (uint8_t*)h->d_scratch[2],
-                             out_f32 ? (float*)h->d_scratch[2] : nullptr, nullptr, H, W);
-            if (rc) return rc;
-            std::vector<int32_t> rm(2 * OH), cm(2 * OW);
-            for (int i = 0; i < OH; ++i) { rm[2 * i] = 0; rm[2 * i + 1] = i; }
-            for (int i = 0; i < OW; ++i) { cm[2 * i] = 0; cm[2 * i + 1] = i; }
-            if ((rc = ensure_scratch(h, 3, (rm.size() + cm.size()) * 4))) return rc;
-            int32_t* d_rm = (int32_t*)h->d_scratch[3];
-            int32_t* d_cm = d_rm + rm.size();
-            HIPCHK(h, hipMemcpyAsync(d_rm, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(d_cm, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipStreamSynchronize(st));   // rm/cm are stack-owned host buffers
-            if (out_f32) HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
-            else HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
-        } else {
-            rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[0], nullptr, 1, H, W, (uint8_t*)h->d_scratch[1], nullptr);
-            if (rc) return rc;
-        }
-    } else {
-        int T = 0;
-        s2sr_plan_tiles(PH, PW, tile, pad, scale, nullptr, 0, &T);
-        std::vector<s2sr_window> wins(T);
-        s2sr_plan_tiles(PH, PW, tile, pad, scale, wins.data(), T, &T);
-        const int pnx = (PW + tile - 1) / tile, pny = (PH + tile - 1) / tile;    // the reference's plan
-        const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;   // all windows share one shape
-        std::vector<int32_t> rm, cm;
-        build_stitch_maps(wins, pnx, pny, OHp, OWp, rm, cm);                    // (the stitches read the first OH x OW of them)
-        // When a dimension ends within 2*pad of a tile multiple, the last two window rows (columns)
-        // of the plan are the same rectangle: the reference runs the net on both (only the paste
-        // ranges differ).  Identical inputs give identical outputs, so each distinct rectangle is
-        // forwarded once and the paste maps point at it.
-        std::vector<int> uy(pny), ux(pnx), rows_y1, cols_x1;
-        for (int y = 0; y < pny; ++y) {
-            const int y1 = wins[(size_t)y * pnx].y1;
-            if (rows_y1.empty() || rows_y1.back() != y1) rows_y1.push_back(y1);
-            uy[y] = (int)rows_y1.size() - 1;
-        }
-        for (int x = 0; x < pnx; ++x) {
-            const int x1 = wins[x].x1;
-            if (cols_x1.empty() || cols_x1.back() != x1) cols_x1.push_back(x1);
-            ux[x] = (int)cols_x1.size() - 1;
-        }
-        for (size_t i = 0; i < rm.size(); i += 2)
-            if (rm[i] >= 0) rm[i] = uy[rm[i]];
-        for (size_t i = 0; i < cm.size(); i += 2)
-            if (cm[i] >= 0) cm[i] = ux[cm[i]];
-        const int nx = (int)cols_x1.size(), ny = (int)rows_y1.size();
-        T = nx * ny;
-        std::vector<int32_t> rects(4 * (size_t)T);
-        for (int y = 0; y < ny; ++y)
-            for (int x = 0; x < nx; ++x) {
-                const int t = y * nx + x;
-                rects[4 * t] = rows_y1[y]; rects[4 * t + 1] = rows_y1[y] + wh; rects[4 * t + 2] = cols_x1[x]; rects[4 * t + 3] = cols_x1[x] + ww;
-            }
-        const size_t tin = (size_t)T * wh * ww * 3, tout = tin * scale * scale;
-        if ((rc = ensure_scratch(h, 2, tin))) return rc;
-        if ((rc = ensure_scratch(h, 4, tout * (out_f32 ? 4 : 1)))) return rc;
-        if ((rc = ensure_scratch(h, 3, (rects.size() + rm.size() + cm.size()) * 4))) return rc;
-        int32_t* d_rects = (int32_t*)h->d_scratch[3];
-        int32_t* d_rm = d_rects + rects.size();
-        int32_t* d_cm = d_rm + rm.size();
-        HIPCHK(h, hipMemcpyAsync(d_rects, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(d_rm, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(d_cm, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipStreamSynchronize(st));
-        if (reflect) HIPCHK(h, launch_gather_windows_reflect((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
-        else HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
-        // Chunks of whole window rows.  An output row is final once the last window row that pastes into it is done (the row
-        // map is monotone), so each chunk is followed by the stitch of its band of final rows, and the band's device-to-host
-        // copy runs on the copy stream under the next chunk's compute.  A chunk holds whole launch groups: for windows that
-        // travel as mosaics (forward_dev) rows in multiples of what fills a mosaic, and as many mosaics as the workspace
-        // allows -- the patch count of a launch must be large against the 256 workgroups (one 4 x 4 mosaic of 276-pixel
-        // windows is 1225 patches = 4.8 per CU, five rounds for 4.8 rounds of work; five mosaics are 23.9 -> 24).
-        // Chunk sizes.  The device-to-host copy of a chunk's band hides under the NEXT chunk's compute and only the last band's
-        // copy is exposed, so chunks shrink towards the end (a row of 276-pixel windows computes ~6x longer than its 13 MB band
-        // takes to reach pageable host memory; a chunk may be up to 5x its successor).  What a small chunk costs is the rounding
-        // of its patch count to whole rounds of the persistent workgroups in the trunk convs (32 x 32 patches; a 4 x 4 mosaic
-        // of 276-pixel windows = 1225 patches = 4.8 rounds of 256: 1, 2, 3, 4 mosaics lose 4.3 %, 5 or 10 lose 0.3 %).  The
-        // tail (last, middle) is searched over small sizes for the fewest rounds + exposed copy; the rest goes in front in
-        // workspace-sized pieces.  4096 x 4096 at 256/10: 16 rows of 16 windows -> 10 + 5 + 1.
-        std::vector<int> chunk_r0;   // first window row of each chunk, plus ny at the end
-        const Mosaic mo = pick_mosaic(h, T, wh, ww);   // ONE plan for the job: every chunk runs in its workspace geometry
-        {
-            const int per = mo.on() ? mo.kx * mo.ky : 1;
-            const int gw = (mo.on() ? group_size(h, (T + per - 1) / per, mo.ky * (mo.wh + 1) - 1, mo.kx * (mo.ww + 1) - 1)
-                                    : group_size(h, T, wh / u, ww / u)) * per;          // windows per launch group
-            const int r_min = (per + nx - 1) / nx;                                      // rows that fill a mosaic
-            const int units = (ny + r_min - 1) / r_min;                                 // ... and how many such row units the image has
-            int u_max = gw / nx / r_min;                                                // units per chunk the workspace allows
-            if (u_max < 1) u_max = 1;
-            int ncu = 256;
-            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-            const long pimg = mo.on() ? (long)((mo.ky * (mo.wh + 1) - 1 + 31) / 32) * ((mo.kx * (mo.ww + 1) - 1 + 31) / 32)
-                                      : (long)((wh / u + 31) / 32) * ((ww / u + 31) / 32);   // 32 x 32 patches per launch image
-            std::vector<int> sizes;                                                     // in units, front to back
-            plan_chunk_sizes(units, u_max, r_min * nx, per, pimg, ncu, sizes);
-            int r = 0;
-            for (int u : sizes) { chunk_r0.push_back(r); r += u * r_min; }
-            chunk_r0.push_back(ny);
-        }
-        const int nchunks = (int)chunk_r0.size() - 1;
-        if (!out_f32 && nchunks > 1) {
-            // A job (job_rgb / prm) takes the same route: the channel swap behind the net is applied to every band as it is stitched;
-            // the post-process -- image-global through CLAHE's grid (wow_sr.py:191-192) -- counts every band into the histograms as
-            // it is stitched (under the compute of the chunks still to come), builds the LUTs behind the last band and then
-            // finishes the image in row bands, each followed by its copy out: what is exposed behind the last window is one band's
-            // kernels plus the PCIe time of the image (the r04 form waited for the whole mosaic, swapped, post-processed and only
-            // then started the one copy).
-            const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;
-            const size_t row_b = (size_t)OW * 3;
-            int fin_rows = 0, nfin = 0;          // finishing bands of the post-process: ~48 MB each, whole 32-row tile rows
-            if (prm) {
-                fin_rows = (int)(((size_t)48 << 20) / row_b) & ~31;
-                if (fin_rows < 64) fin_rows = 64;
-                nfin = (OH + fin_rows - 1) / fin_rows;
-                if ((rc = pp_band_begin_locked(h, OH, OW, prm, job_rgb ? 3 : 0, st))) return rc;   // (allocates: before anything is enqueued)
-            }
-            while ((int)h->group_done.size() < nchunks + nfin) {
-                hipEvent_t e;
-                HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                h->group_done.push_back(e);
-            }
-            uint8_t* d_img_out = (uint8_t*)h->d_scratch[1];
-            int yb = 0, prev_yb = 0, prev_ye = 0;
-            for (int c = 0; c < nchunks; ++c) {
-                const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1] < ny ? chunk_r0[c + 1] : ny;
-                const int t0 = r0 * nx, n = (r1 - r0) * nx;
-                rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[2] + t0 * win_in, nullptr, n, wh, ww,
-                                 (uint8_t*)h->d_scratch[4] + t0 * win_out, nullptr, mo.on() ? &mo : nullptr);
-                if (rc) return rc;
-                int ye = OH;
-                if (r1 < ny)
-                    for (ye = yb; ye < OH && rm[2 * ye] < r1; ++ye) {}
-                if (ye > yb) {
-                    HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW,
-                                               d_img_out + (size_t)yb * row_b, st));
-                    if (prm) {
-                        if ((rc = pp_band_hist_locked(h, d_img_out, yb, ye, st))) return rc;
-                    } else if (job_rgb) {
-                        HIPCHK(h, launch_swap_rb_u8(d_img_out + (size_t)yb * row_b, (size_t)(ye - yb) * OW, d_img_out + (size_t)yb * row_b, st));
-                    }
-                }
-                HIPCHK(h, hipEventRecord(h->group_done[c], st));
-                if (!prm && c > 0 && prev_ye > prev_yb) {
-                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[c - 1], 0));
-                    if ((rc = d2h_staged(h, out_u8 + (size_t)prev_yb * row_b, d_img_out + (size_t)prev_yb * row_b,
-                                         (size_t)(prev_ye - prev_yb) * row_b, false))) return rc;
-                }
-                prev_yb = yb; prev_ye = ye; yb = ye;
-            }
-            if (!prm) {
-                if (prev_ye > prev_yb) {
-                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
-                    if ((rc = d2h_staged(h, out_u8 + (size_t)prev_yb * row_b, d_img_out + (size_t)prev_yb * row_b,
-                                         (size_t)(prev_ye - prev_yb) * row_b, true))) return rc;
-                }
-            } else {
-                // LUTs, then every finishing band's kernels (in place: a band's rows are rewritten only after the apply pass, which
-                // runs R rows ahead, has read them), an event behind each; the copies follow band by band on the copy stream
-                const bool timing = getenv("S2SR_JOB_TIMING") != nullptr;     // diagnostic: stage times of the finish on stderr
-                auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-                double t_enq = now(), t_compute = 0, t_first = 0;
-                if ((rc = pp_band_lut_locked(h, st))) return rc;
-                for (int b = 0; b < nfin; ++b) {
-                    const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
-                    if ((rc = pp_band_rows_locked(h, d_img_out, y0, y1, d_img_out, st))) return rc;
-                    HIPCHK(h, hipEventRecord(h->group_done[nchunks + b], st));
-                }
-                if (timing) {
-                    HIPCHK(h, hipEventSynchronize(h->group_done[nchunks - 1]));
-                    t_compute = now();
-                }
-                for (int b = 0; b < nfin; ++b) {
-                    const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
-                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks + b], 0));
-                    if ((rc = d2h_staged(h, out_u8 + (size_t)y0 * row_b, d_img_out + (size_t)y0 * row_b, (size_t)(y1 - y0) * row_b,
-                                         false))) return rc;
-                    if (timing && b == 0) t_first = now();
-                }
-                if (timing)
-                    fprintf(stderr, "[s2sr job] finish: %d bands of %d rows; last chunk done %.2f ms after the finish was queued, first band on the host "
-                            "+%.2f ms, all bands +%.2f ms\n", nfin, fin_rows, t_compute - t_enq, t_first - t_compute, now() - t_compute);
-            }
-            HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-            HIPCHK(h, hipStreamSynchronize(st));
-            return S2SR_OK;
-        }
-        rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[2], nullptr, T, wh, ww, out_f32 ? nullptr : (uint8_t*)h->d_scratch[4],
-                         out_f32 ? (float*)h->d_scratch[4] : nullptr);
-        if (rc) return rc;
-        if (out_f32) HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
-        else HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
-    }
-    const uint8_t* d_final = (const uint8_t*)h->d_scratch[1];
-    if (whole_finish) {
-        if (job_rgb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[1], (size_t)OH * OW, (uint8_t*)h->d_scratch[1], st));
-        if (prm) {
-            // the windows' output buffer is free again once the stitch has read it; whole-image jobs get a buffer of their own
-            if ((rc = ensure_scratch(h, 4, opx))) return rc;
-            if ((rc = postprocess_dev_locked(h, h->d_scratch[1], 1, OH, OW, prm, h->d_scratch[4], st))) return rc;
-            d_final = (const uint8_t*)h->d_scratch[4];
-        }
-    }
-    if (h->group_done.empty()) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->group_done.push_back(e);
-    }
-    HIPCHK(h, hipEventRecord(h->group_done[0], st));
-    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[0], 0));
-    if ((rc = d2h_staged(h, out_f32 ? (uint8_t*)out_f32 : out_u8, out_f32 ? (const uint8_t*)h->d_scratch[1] : d_final, opx * (out_f32 ? 4 : 1), true))) return rc;
-    HIPCHK(h, hipStreamSynchronize(st));
-    return S2SR_OK;
-}
-
-int s2sr_enhance_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, uint8_t* out) {
-    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, img, H, W, tile, pad, out, nullptr));
-}
-
-// A whole /api/wow job's device work in one call (apply_wow_sr, wow_sr.py:85-110): RGB image in, RGB2BGR, RealESRGAN.enhance,
-// BGR2RGB, _enhance_for_crops (prm != NULL), RGB image out -- one upload, one download, nothing in between on the host.
-int s2sr_enhance_job_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
-                        uint8_t* out_rgb) {
-    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, rgb, H, W, tile, pad, out_rgb, nullptr, false, true, prm));
-}
-
-int s2sr_enhance_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out) {
-    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, img, H, W, tile, pad, nullptr, out));
-}
-
-int s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_t W, int32_t tile, int32_t pad,
-                            int32_t first, int32_t count, void* d_tiles, void* stream) {
-    if (!h || !d_img || !d_tiles || H <= 0 || W <= 0 || tile <= 0 || pad < 0 || first < 0 || count <= 0) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
-    int T = 0, PH, PW;
-    int rc = plan_dims(h, H, W, tile, &PH, &PW);
-    if (rc) return rc;
-    s2sr_plan_tiles(PH, PW, tile, pad, h->cfg.scale, nullptr, 0, &T);
-    if (first + count > T) return fail(h, S2SR_E_INVALID, "window range exceeds the plan");
-    std::vector<s2sr_window> wins(T);
-    s2sr_plan_tiles(PH, PW, tile, pad, h->cfg.scale, wins.data(), T, &T);
-    const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;
-    std::vector<int32_t> rects(4 * (size_t)count);
-    for (int t = 0; t < count; ++t) {
-        const s2sr_window& w = wins[first + t];
-        rects[4 * t] = w.y1; rects[4 * t + 1] = w.y2; rects[4 * t + 2] = w.x1; rects[4 * t + 3] = w.x2;
-    }
-    rc = ensure_scratch(h, 3, rects.size() * 4);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[3], rects.data(), rects.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (PH != H || PW != W)
-        HIPCHK(h, launch_gather_windows_reflect((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, (uint8_t*)d_tiles, st));
-    else HIPCHK(h, launch_gather_windows((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, (uint8_t*)d_tiles, st));
-    return S2SR_OK;
-}
-
-int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t oy0, int32_t oy1,
-                            void* d_out, void* stream) {
-    if (!h || !d_tiles || !d_out || H <= 0 || W <= 0 || tile <= 0 || pad < 0 || oy0 < 0 || oy1 > h->cfg.scale * H || oy0 > oy1) return S2SR_E_INVALID;
-    if (oy0 == oy1) return S2SR_OK;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
-    const int S = h->cfg.scale;
-    int T = 0, PH, PW;
-    int rc = plan_dims(h, H, W, tile, &PH, &PW);
-    if (rc) return rc;
-    s2sr_plan_tiles(PH, PW, tile, pad, S, nullptr, 0, &T);
-    std::vector<s2sr_window> wins(T);
-    s2sr_plan_tiles(PH, PW, tile, pad, S, wins.data(), T, &T);
-    const int nx = (PW + tile - 1) / tile, ny = (PH + tile - 1) / tile;
-    const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;
-    const size_t nrm = 2 * (size_t)(S * PH), ncm = 2 * (size_t)(S * PW);   // maps of the padded image; the stitch reads S H x S W
-    // the plan's paste maps: from the handle's LRU of map sets, or built and uploaded now.  A NEW set costs an allocation and a
-    // blocking upload on the handle's own stream -- nothing the caller has queued on ITS stream is waited for (r04: any key change
-    // synchronised the device under the process-wide gate, so the first band's stitch drained every compute chunk already queued
-    // and stalled the captures of other handles).  Only when all four sets are taken is the least recently used one recycled, and
-    // only then is the device synchronised: a stitch that still reads it may be in flight on a stream this library does not know.
-    const int key[4] = {H, W, tile, pad + 1};
-    s2sr_handle::StitchMaps* ms = nullptr;
-    for (auto& m : h->stitch_sets)
-        if (m.d && m.key[0] == key[0] && m.key[1] == key[1] && m.key[2] == key[2] && m.key[3] == key[3]) ms = &m;
-    if (!ms) {
-        for (auto& m : h->stitch_sets)
-            if (!m.d) { ms = &m; break; }
-        if (!ms) {
-            ms = &h->stitch_sets[0];
-            for (auto& m : h->stitch_sets)
-                if (m.last_use < ms->last_use) ms = &m;
-            HIPCHK(h, dev_sync());
-            if (ms->cap < (nrm + ncm) * 4) {
-                HIPCHK(h, dev_free(ms->d));
-                ms->d = nullptr; ms->cap = 0;
-            }
-        }
-        ms->key[0] = 0;                       // (invalid until the upload is through)
-        if (!ms->d) {
-            HIPCHK(h, dev_malloc(&ms->d, (nrm + ncm) * 4));
-            ms->cap = (nrm + ncm) * 4;
-        }
-        std::vector<int32_t> rm, cm;
-        build_stitch_maps(wins, nx, ny, S * PH, S * PW, rm, cm);
-        HIPCHK(h, copy_blocking(h, ms->d, rm.data(), nrm * 4, hipMemcpyHostToDevice));
-        HIPCHK(h, copy_blocking(h, ms->d + nrm, cm.data(), ncm * 4, hipMemcpyHostToDevice));
-        for (int i = 0; i < 4; ++i) ms->key[i] = key[i];
-    }
-    ms->last_use = ++h->stitch_clock;
-    const int32_t* d_rm = ms->d;
-    const int32_t* d_cm = d_rm + nrm;
-    HIPCHK(h, launch_stitch_u8((const uint8_t*)d_tiles, nx, wh * S, ww * S, d_rm + 2 * (size_t)oy0, d_cm, oy1 - oy0, S * W,
-                               (uint8_t*)d_out + (size_t)oy0 * S * W * 3, st));
-    return S2SR_OK;
-}
-
-int s2sr_stitch_windows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int32_t W, int32_t tile, int32_t pad,
-                               void* d_out, void* stream) {
-    if (!h) return S2SR_E_INVALID;
-    return s2sr_stitch_rows_u8_dev(h, d_tiles, H, W, tile, pad, 0, h->cfg.scale * H, d_out, stream);
-}
-
-// Device -> host for callers that hold device buffers (s2sr/dist.py's consuming rank): `bytes` from d_src into dst once
-// everything enqueued on `stream` so far is done; returns when the bytes are in dst.  A destination from s2sr_host_alloc is
-// filled by one DMA, a pageable one through the pinned staging slices (d2h_staged) -- never the runtime's copy kernels, which
-// take CUs from the conv workgroups of whatever computes meanwhile.
-int s2sr_copy_to_host(s2sr_handle* h, void* dst, const void* d_src, size_t bytes, void* stream) {
-    if (!h || !dst || !d_src) return S2SR_E_INVALID;
-    if (bytes == 0) return S2SR_OK;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!h->host_copy_ev) HIPCHK(h, hipEventCreateWithFlags(&h->host_copy_ev, hipEventDisableTiming));
-    HIPCHK(h, hipEventRecord(h->host_copy_ev, (hipStream_t)stream));
-    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->host_copy_ev, 0));
-    return d2h_staged(h, (uint8_t*)dst, (const uint8_t*)d_src, bytes, false);
-}
-
-int s2sr_tile_process_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out) {
-    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, img, H, W, tile, pad, nullptr, out, true));
-}
-
-// post-process on device buffers; the caller holds h->mu
-static int postprocess_dev_locked(s2sr_handle* h, const void* d_rgb, int32_t B, int32_t H, int32_t W, const s2sr_pp_params* prm,
-                                  void* d_out, hipStream_t st) {
-    const size_t wb = postprocess_work_bytes(B, H, W, *prm);
-    int rc = ensure_scratch(h, 5, wb);
-    if (rc) return rc;
-    Scope sc(h, st, F_POST, 0.0, (double)B * H * W * 9.0);
-    HIPCHK(h, launch_postprocess((const uint8_t*)d_rgb, B, H, W, *prm, (uint8_t*)d_out, h->d_scratch[5], wb, st));
-    return S2SR_OK;
-}
-
-int s2sr_postprocess_batch_u8_dev(s2sr_handle* h, const void* d_rgb, int32_t B, int32_t H, int32_t W,
-                                  const s2sr_pp_params* prm, void* d_out, void* stream) {
-    if (!h || !d_rgb || !d_out || !prm || B <= 0 || H <= 0 || W <= 0) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return postprocess_dev_locked(h, d_rgb, B, H, W, prm, d_out, (hipStream_t)stream);   // NULL = the default stream, as everywhere in HIP
-}
-
-// ---- the post-process over one device image in row bands (see postprocess.hip launch_pp_band_*) -------------------------------
-// order: S2SR_PP_ORDER_BGR = the image's bytes are B,G,R; S2SR_PP_ORDER_SWAP_OUT = R and B exchanged in the rows written
-static int pp_band_begin_locked(s2sr_handle* h, int H, int W, const s2sr_pp_params* prm, int order, hipStream_t st) {
-    if (prm->clahe_grid <= 0 || prm->clahe_grid > 64) return fail(h, S2SR_E_INVALID, "clahe_grid must be 1..64");
-    int rc = ensure_scratch(h, 5, postprocess_work_bytes(1, H, W, *prm));
-    if (rc) return rc;
-    s2sr_handle::PPBand& b = h->ppb;
-    b = s2sr_handle::PPBand();
-    b.H = H; b.W = W; b.prm = *prm;
-    b.bgr = (order & S2SR_PP_ORDER_BGR) ? 1 : 0;
-    b.swap_out = (order & S2SR_PP_ORDER_SWAP_OUT) ? 1 : 0;
-    b.radius = pp_band_radius(*prm);
-    HIPCHK(h, launch_pp_band_begin(H, W, *prm, h->d_scratch[5], st));
-    b.open = true;
-    return S2SR_OK;
-}
-
-static int pp_band_hist_locked(s2sr_handle* h, const void* d_img, int y0, int y1, hipStream_t st) {
-    s2sr_handle::PPBand& b = h->ppb;
-    if (!b.open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_hist: no banded post-process open, or its LUTs are already built");
-    if (y0 < 0 || y1 > b.H || y0 > y1) return fail(h, S2SR_E_INVALID, "pp_band_hist: rows outside the image");
-    Scope sc(h, st, F_POST, 0.0, (double)(y1 - y0) * b.W * 3.0);
-    HIPCHK(h, launch_pp_band_hist((const uint8_t*)d_img, b.H, b.W, b.prm, b.bgr, y0, y1, h->d_scratch[5], st));
-    return S2SR_OK;
-}
-
-static int pp_band_lut_locked(s2sr_handle* h, hipStream_t st) {
-    s2sr_handle::PPBand& b = h->ppb;
-    if (!b.open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_lut: no banded post-process open, or its LUTs are already built");
-    HIPCHK(h, launch_pp_band_lut(b.H, b.W, b.prm, h->d_scratch[5], st));
-    b.lut = true;
-    return S2SR_OK;
-}
-
-static int pp_band_rows_locked(s2sr_handle* h, const void* d_img, int y0, int y1, void* d_out, hipStream_t st) {
-    s2sr_handle::PPBand& b = h->ppb;
-    if (!b.open || !b.lut) return fail(h, S2SR_E_INVALID, "pp_band_rows: the LUTs are not built (begin, hist over every row, lut, then rows)");
-    if (y0 != b.rows_end || y1 <= y0 || y1 > b.H) return fail(h, S2SR_E_INVALID, "pp_band_rows: bands must follow each other from row 0");
-    const int need = y1 + b.radius < b.H ? y1 + b.radius : b.H;     // the blur of row y1-1 reads R rows below it
-    Scope sc(h, st, F_POST, 0.0, (double)(y1 - y0) * b.W * 6.0);
-    if (need > b.applied_end) {
-        HIPCHK(h, launch_pp_band_apply((const uint8_t*)d_img, b.H, b.W, b.prm, b.bgr, b.applied_end, need, h->d_scratch[5], st));
-        b.applied_end = need;
-    }
-    HIPCHK(h, launch_pp_band_sharpen(b.H, b.W, b.prm, b.bgr, b.swap_out, y0, y1, h->d_scratch[5], (uint8_t*)d_out, st));
-    b.rows_end = y1;
-    if (y1 == b.H) b.open = false;
-    return S2SR_OK;
-}
-
-int s2sr_pp_band_begin_dev(s2sr_handle* h, int32_t H, int32_t W, const s2sr_pp_params* prm, int32_t order, void* stream) {
-    if (!h || !prm || H <= 0 || W <= 0) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return pp_band_begin_locked(h, H, W, prm, order, (hipStream_t)stream);
-}
-
-int s2sr_pp_band_hist_dev(s2sr_handle* h, const void* d_img, int32_t y0, int32_t y1, void* stream) {
-    if (!h || !d_img) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return pp_band_hist_locked(h, d_img, y0, y1, (hipStream_t)stream);
-}
-
-int s2sr_pp_band_lut_dev(s2sr_handle* h, void* stream) {
-    if (!h) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return pp_band_lut_locked(h, (hipStream_t)stream);
-}
-
-int s2sr_pp_band_rows_dev(s2sr_handle* h, const void* d_img, int32_t y0, int32_t y1, void* d_out, void* stream) {
-    if (!h || !d_img || !d_out) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return pp_band_rows_locked(h, d_img, y0, y1, d_out, (hipStream_t)stream);
-}
-
-// Host image in, host image out.  ONE lock scope from the upload to the download: the staging buffers
-// (d_scratch[0], [1]) belong to the handle, and the app shares one post-process handle per device between
-// all jobs (app/wow_sr.py), which the reference runs from concurrent worker threads (main.py:247-368).
-int s2sr_postprocess_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, const s2sr_pp_params* prm, uint8_t* out) {
-    if (!h || !rgb || !out || !prm || H <= 0 || W <= 0) return S2SR_E_INVALID;
-    const size_t nb = (size_t)H * W * 3;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    int rc = ensure_scratch(h, 0, nb);
-    if (rc) return rc;
-    if ((rc = ensure_scratch(h, 1, nb))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], rgb, nb, hipMemcpyHostToDevice, h->stream));
-    if ((rc = postprocess_dev_locked(h, h->d_scratch[0], 1, H, W, prm, h->d_scratch[1], h->stream))) return rc;
-    HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[1], nb, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return S2SR_OK;
-}
-
-// ---- XYZ tile pyramid (host buffers in and out; geometry tables come from the caller) ---------------
-int s2sr_warp_bilinear_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, const float* grid, int32_t gh, int32_t gw,
-                          int32_t step, int32_t OH, int32_t OW, uint8_t* out_rgba) {
-    if (!h || !rgb || !grid || !out_rgba || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || gh <= 0 || gw <= 0) return S2SR_E_INVALID;
-    if (step <= 0 || (step & (step - 1))) return fail(h, S2SR_E_INVALID, "warp node spacing must be a power of two");
-    if ((int64_t)(gh - 1) * step < OH - 1 || (int64_t)(gw - 1) * step < OW - 1)
-        return fail(h, S2SR_E_INVALID, "warp node grid does not cover the output raster");
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const size_t ib = (size_t)H * W * 3, gb = (size_t)gh * gw * 8, ob = (size_t)OH * OW * 4;
-    int rc;
-    if ((rc = ensure_scratch(h, 0, ib))) return rc;
-    if ((rc = ensure_scratch(h, 1, ob))) return rc;
-    if ((rc = ensure_scratch(h, 3, gb))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], rgb, ib, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[3], grid, gb, hipMemcpyHostToDevice, st));
-    {
-        Scope sc(h, st, F_MISC, 0.0, (double)ob + (double)OH * OW * 12.0);
-        HIPCHK(h, launch_warp_bilinear((const uint8_t*)h->d_scratch[0], H, W, (const float*)h->d_scratch[3], gh, gw, step, OH, OW,
-                                       (uint8_t*)h->d_scratch[1], st));
-    }
-    HIPCHK(h, hipMemcpyAsync(out_rgba, h->d_scratch[1], ob, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    h->warp_slot = 1; h->warp_h = OH; h->warp_w = OW;      // the raster also stays on the device for the base level of its pyramid
-    return S2SR_OK;
-}
-
-int s2sr_tiles_base_u8(s2sr_handle* h, const uint8_t* rgba, int32_t H, int32_t W, const int32_t* col_lo, const int32_t* col_hi,
-                       const int32_t* row_lo, const int32_t* row_hi, int32_t nx, int32_t ny, uint8_t* out) {
-    if (!h || !col_lo || !col_hi || !row_lo || !row_hi || H <= 0 || W <= 0 || nx <= 0 || ny <= 0) return S2SR_E_INVALID;
-    for (int i = 0; i < nx * 256; ++i)
-        if (col_lo[i] < 0 || col_hi[i] >= W) return fail(h, S2SR_E_INVALID, "column footprint table leaves the raster");
-    for (int i = 0; i < ny * 256; ++i)
-        if (row_lo[i] < 0 || row_hi[i] >= H) return fail(h, S2SR_E_INVALID, "row footprint table leaves the raster");
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const size_t ib = (size_t)H * W * 4, ob = (size_t)nx * ny * 65536 * 4, cb = (size_t)nx * 256 * 4, rb = (size_t)ny * 256 * 4;
-    // rgba == NULL: the raster is the one the previous call on this handle -- s2sr_warp_bilinear_u8 -- produced, taken from its
-    // device copy (a 4096 x 4096 source: 67 MB that would cross PCIe twice between the two calls)
-    int in_slot = 0;
-    if (!rgba) {
-        if (h->warp_slot < 0 || h->warp_h != H || h->warp_w != W)
-            return fail(h, S2SR_E_INVALID, "rgba == NULL, but the previous call on this handle did not leave a warped raster of this size on the device");
-        in_slot = h->warp_slot;
-    }
-    const int out_slot = in_slot == 1 ? 0 : 1;
-    int rc;
-    if (rgba && (rc = ensure_scratch(h, in_slot, ib))) return rc;
-    if ((rc = ensure_scratch(h, out_slot, ob))) return rc;
-    if ((rc = ensure_scratch(h, 3, 2 * cb + 2 * rb))) return rc;
-    int32_t* t = (int32_t*)h->d_scratch[3];
-    if (rgba) HIPCHK(h, hipMemcpyAsync(h->d_scratch[in_slot], rgba, ib, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(t, col_lo, cb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(t + nx * 256, col_hi, cb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(t + 2 * nx * 256, row_lo, rb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(t + 2 * nx * 256 + ny * 256, row_hi, rb, hipMemcpyHostToDevice, st));
-    {
-        Scope sc(h, st, F_MISC, 0.0, (double)ib + (double)ob);
-        HIPCHK(h, launch_tiles_base((const uint8_t*)h->d_scratch[in_slot], W, t, t + nx * 256, t + 2 * nx * 256, t + 2 * nx * 256 + ny * 256, nx,
-                                    ny, (uint8_t*)h->d_scratch[out_slot], st));
-    }
-    if (out) HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[out_slot], ob, hipMemcpyDeviceToHost, st));      // out == NULL: the level stays on the device
-    HIPCHK(h, hipStreamSynchronize(st));
-    h->tiles_slot = out_slot; h->tiles_nx = nx; h->tiles_ny = ny;
-    return S2SR_OK;
-}
-
-int s2sr_tiles_overview_u8(s2sr_handle* h, const uint8_t* child, int32_t cnx, int32_t cny, int32_t ox, int32_t oy, int32_t pnx,
-                           int32_t pny, uint8_t* out) {
-    if (!h || cnx <= 0 || cny <= 0 || pnx <= 0 || pny <= 0) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const size_t ib = (size_t)cnx * cny * 65536 * 4, ob = (size_t)pnx * pny * 65536 * 4;
-    // child == NULL: the children are the level the previous pyramid call on this handle produced, still on the device (a
-    // z18 level is 2.9 GB: sending it back costs as much as fetching it did)
-    int in_slot = 0;
-    if (!child) {
-        if (h->tiles_slot < 0 || h->tiles_nx != cnx || h->tiles_ny != cny)
-            return fail(h, S2SR_E_INVALID, "child == NULL, but the previous call on this handle did not leave a tile level of this size on the device");
-        in_slot = h->tiles_slot;
-    }
-    const int out_slot = in_slot == 1 ? 0 : 1;
-    int rc;
-    if (child && (rc = ensure_scratch(h, in_slot, ib))) return rc;
-    if ((rc = ensure_scratch(h, out_slot, ob))) return rc;
-    if (child) HIPCHK(h, hipMemcpyAsync(h->d_scratch[in_slot], child, ib, hipMemcpyHostToDevice, st));
-    {
-        Scope sc(h, st, F_MISC, 0.0, (double)ib + (double)ob);
-        HIPCHK(h, launch_tiles_overview((const uint8_t*)h->d_scratch[in_slot], cnx, cny, ox, oy, pnx, pny, (uint8_t*)h->d_scratch[out_slot], st));
-    }
-    if (out) HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[out_slot], ob, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    h->tiles_slot = out_slot; h->tiles_nx = pnx; h->tiles_ny = pny;
-    return S2SR_OK;
-}
-
-// The PNG files of the tile level the previous base / overview call left on the device: token statistics on the device, Huffman
-// codes on the host, bit emission on the device, chunk framing + CRC + file writes on host threads (pngdev.hip).  Only the
-// compressed streams cross PCIe.
-static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const char* const* paths, int32_t flags, int32_t* written);
-
-int s2sr_tiles_write_png(s2sr_handle* h, int32_t nx, int32_t ny, const char* const* paths, int32_t flags, int32_t* written) {
-    if (!h || !paths || nx <= 0 || ny <= 0) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    return tiles_write_png_locked(h, nx, ny, paths, flags, written);
-}
-
-// The same with the XYZ layout spelled out instead of nx * ny path strings: tile (j, i) of the level goes to
-// <dir>/<zoom>/<x0 + i>/<y_rows[j]>.png (gdal2tiles --xyz, reference tiling.py:138-186).  A z18 level is 9801 paths: built here they
-// cost a millisecond, as Python strings plus a ctypes array 5-7 ms per level.
-int s2sr_tiles_write_png_xyz(s2sr_handle* h, int32_t nx, int32_t ny, const char* dir, int32_t zoom, int32_t x0, const int32_t* y_rows,
-                             int32_t flags, int32_t* written) {
-    if (!h || !dir || !y_rows || nx <= 0 || ny <= 0 || zoom < 0) return S2SR_E_INVALID;
-    const size_t dl = strlen(dir);
-    if (dl == 0 || dl > 3800) return S2SR_E_INVALID;
-    const size_t slot = dl + 48;                                  // "/zz/xxxxxxxxxx/yyyyyyyyyy.png" is at most 30 characters
-    std::vector<char> text((size_t)nx * ny * slot);
-    std::vector<const char*> paths((size_t)nx * ny);
-    for (int j = 0; j < ny; ++j)
-        for (int i = 0; i < nx; ++i) {
-            char* p = text.data() + ((size_t)j * nx + i) * slot;
-            snprintf(p, slot, "%s/%d/%d/%d.png", dir, zoom, x0 + i, y_rows[j]);
-            paths[(size_t)j * nx + i] = p;
-        }
-    std::lock_guard<std::mutex> lk(h->mu);
-    return tiles_write_png_locked(h, nx, ny, paths.data(), flags, written);
-}
-
-static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const char* const* paths, int32_t flags, int32_t* written) {
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (h->tiles_slot < 0 || h->tiles_nx != nx || h->tiles_ny != ny)
-        return fail(h, S2SR_E_INVALID, "the previous call on this handle did not leave a tile level of this size on the device");
-    const int slot = h->tiles_slot;
-    const uint8_t* d_tiles = (const uint8_t*)h->d_scratch[slot];
-    const int n = nx * ny;
-    hipStream_t st = h->stream;
-    const bool timing = getenv("S2SR_PNG_TIMING") != nullptr;
-    const bool row_threads = (flags & S2SR_PNG_ROW_THREADS) != 0;
-    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_begin = now();
-    double t_wait = 0, t_plan = 0, t_files = 0, t_hostenc = 0;
-    // The level goes through in GROUPS of ~2048 tiles so that the device phases of one group run under the host phases of another
-    // (r04 / first form of r05: one group = the level, the phases strictly one behind the other -- for z18's 9801 tiles 7 ms of
-    // statistics kernel + copy and 7 ms of upload + emit kernel with idle CPUs, 5 ms of Huffman codes and 27 ms of framing / CRC /
-    // file writes with an idle device).  All statistics kernels and their copies back are queued up front; then, group by group:
-    // wait for the group's statistics, build its codes (host pool), queue its upload + emit kernel, and -- while that runs --
-    // bring the PREVIOUS group's streams back and write its files.  Streams ping-pong between two device buffers.
-    int ngroups = (flags & S2SR_PNG_SMALL_GROUPS) ? (n + 2) / 3 : (n <= 1536 ? 1 : (n + 2047) / 2048);   // (the flag: groups of 3, for the tests)
-    if (const char* e = getenv("S2SR_PNG_GROUP_TILES")) {      // A/B knob (tools/tiles_ab.py): tiles per group, 0 = the whole level as one
-        const int v = atoi(e);
-        ngroups = v <= 0 ? 1 : (n + v - 1) / v;
-    }
-    const int gsz = (n + ngroups - 1) / ngroups;
-    const size_t tile_stats_b = (512 + 512 + 1) * 4;                       // per tile: token histogram, row Adler pairs, any-alpha flag
-    int rc;
-    if ((rc = ensure_scratch(h, 2, (size_t)n * tile_stats_b))) return rc;
-    if ((rc = ensure_scratch(h, 3, png_plan_bytes(n)))) return rc;
-    // the statistics come back into, and the plans go up from, ONE page-locked block kept on the handle (a z18 level: 40 MB down,
-    // 27 MB up; as fresh pageable vectors each crossed PCIe through the runtime's staging and was page-faulted in first)
-    const size_t stats_b = ((size_t)n * tile_stats_b + 255) & ~(size_t)255, plan_b = png_plan_bytes(n);
-    if (h->host_arena_bytes < stats_b + plan_b) {
-        if (h->host_arena) HIPCHK(h, host_free(h->host_arena));
-        h->host_arena = nullptr; h->host_arena_bytes = 0;
-        const size_t want = (stats_b + plan_b + ((size_t)8 << 20)) & ~(((size_t)1 << 20) - 1);
-        HIPCHK(h, host_malloc(&h->host_arena, want, hipHostMallocDefault));
-        h->host_arena_bytes = want;
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (!h->stage_buf[i]) HIPCHK(h, host_malloc(&h->stage_buf[i], kStageBytes, hipHostMallocDefault));
-        if (!h->stage_ev[i]) HIPCHK(h, hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming));
-    }
-    struct Group {
-        int a = 0, n = 0;                       // first tile, tiles
-        uint32_t *d_stats = nullptr;            // device: [hist n x 512 | adler n x 512 | flag n]
-        const uint32_t* stats = nullptr;        // ... its page-locked host copy
-        uint8_t* d_tables = nullptr;            // device: the plan's upload block
-        PngTilePlan plan;
-        size_t out_words = 0;
-        hipEvent_t ev_stats = nullptr, ev_emit = nullptr;
-    };
-    std::vector<Group> groups(ngroups);
-    struct EventsBack {          // the groups' events go back to the handle's pool on every way out
-        s2sr_handle* h; std::vector<Group>& gs;
-        ~EventsBack() { for (Group& G : gs) { if (G.ev_stats) h->ev_pool.push_back(G.ev_stats); if (G.ev_emit) h->ev_pool.push_back(G.ev_emit); } }
-    } events_back{h, groups};
-    for (int g = 0; g < ngroups; ++g) {
-        Group& G = groups[g];
-        G.a = g * gsz;
-        G.n = (G.a + gsz <= n ? gsz : n - G.a);
-        G.d_stats = (uint32_t*)((char*)h->d_scratch[2] + (size_t)G.a * tile_stats_b);
-        G.stats = (const uint32_t*)((const char*)h->host_arena + (size_t)G.a * tile_stats_b);
-        G.d_tables = (uint8_t*)h->d_scratch[3] + png_plan_bytes(G.a);
-        G.plan.arena = (char*)h->host_arena + stats_b + png_plan_bytes(G.a);
-        G.plan.arena_bytes = png_plan_bytes(G.n);
-        G.ev_stats = get_event(h);
-        G.ev_emit = get_event(h);
-        {
-            Scope sc(h, st, F_MISC, 0.0, (double)G.n * 262144.0);      // algorithmic: every tile byte once
-            HIPCHK(h, launch_png_tile_stats(d_tiles + (size_t)G.a * 262144, G.n, G.d_stats, G.d_stats + (size_t)G.n * 512,
-                                            G.d_stats + (size_t)G.n * 1024, row_threads, st));
-        }
-        HIPCHK(h, hipMemcpyAsync((void*)G.stats, G.d_stats, (size_t)G.n * tile_stats_b, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipEventRecord(G.ev_stats, st));
-    }
-    std::atomic<int> failed{0};
-    if (written) for (int t = 0; t < n; ++t) written[t] = 0;
-    size_t total_words = 0, n_host = 0;
-
-    // group g: its streams back in batches through the two page-locked staging buffers (while one batch is framed, checksummed and
-    // written from its buffer by the host threads, the next one is on the wire), then the few tiles the host encoder takes
-    auto write_group = [&](Group& G, const uint32_t* d_out) -> int {
-        const PngTilePlan& plan = G.plan;
-        const char* const* gpaths = paths + G.a;
-        int32_t* gwritten = written ? written + G.a : nullptr;
-        std::vector<int> host_tiles;
-        for (int t = 0; t < G.n; ++t) if (plan.mode[t] == 2) host_tiles.push_back(t);
-        std::vector<uint8_t> host_px(host_tiles.size() * (size_t)262144);
-        for (size_t k = 0; k < host_tiles.size(); ++k)          // (noise: stored blocks are smaller than a Huffman block) their pixels
-            HIPCHK(h, hipMemcpyAsync(host_px.data() + k * 262144, d_tiles + (size_t)(G.a + host_tiles[k]) * 262144, 262144, hipMemcpyDeviceToHost,
-                                     h->copy_stream));
-        struct Batch { int t0, t1; size_t w0, w1; };
-        std::vector<Batch> batches;
-        {
-            const size_t cap_words = kStageBytes / 4;
-            int t0 = 0;
-            while (t0 < G.n) {
-                int t1 = t0;
-                const size_t w0 = plan.out_word[t0];
-                auto end_of = [&](int t) { return t + 1 < G.n ? plan.out_word[t + 1] : G.out_words; };
-                while (t1 < G.n && end_of(t1) - w0 <= cap_words) ++t1;
-                if (t1 == t0) return fail(h, S2SR_E_CAPACITY, "a tile's stream is larger than a staging buffer");
-                batches.push_back(Batch{t0, t1, w0, end_of(t1 - 1)});
-                t0 = t1;
-            }
-        }
-        for (size_t k = 0; k <= batches.size(); ++k) {
-            if (k < batches.size() && batches[k].w1 > batches[k].w0)
-                HIPCHK(h, hipMemcpyAsync(h->stage_buf[k & 1], d_out + batches[k].w0, (batches[k].w1 - batches[k].w0) * 4, hipMemcpyDeviceToHost,
-                                         h->copy_stream));
-            if (k < batches.size()) HIPCHK(h, hipEventRecord(h->stage_ev[k & 1], h->copy_stream));
-            if (k > 0) {
-                const Batch& bt = batches[k - 1];
-                HIPCHK(h, hipEventSynchronize(h->stage_ev[(k - 1) & 1]));
-                const uint32_t* words = (const uint32_t*)h->stage_buf[(k - 1) & 1];
-                if (!png_parallel_for(bt.t1 - bt.t0, [&](int i) {
-                    const int t = bt.t0 + i;
-                    if (plan.mode[t] != 1) return;
-                    static thread_local std::vector<uint8_t> buf;
-                    if (!png_write_tile_file(gpaths[t], words + (plan.out_word[t] - bt.w0), plan.deflate_bytes[t], plan.eob[t], plan.eob_at[t],
-                                             plan.adler[t], buf))
-                        failed.store(1);
-                    else if (gwritten) gwritten[t] = 1;
-                })) failed.store(1);
-            }
-        }
-        const double t0 = now();
-        if (!host_tiles.empty()) {
-            HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-            const size_t cap = s2sr_png_bound(256, 256, 4);
-            if (!png_parallel_for((int)host_tiles.size(), [&](int k) {
-                static thread_local std::vector<uint8_t> buf;
-                buf.resize(cap);
-                size_t len = 0;
-                const int t = host_tiles[k];
-                if (s2sr_png_encode(host_px.data() + (size_t)k * 262144, 256, 256, 4, 1024, buf.data(), cap, &len) != S2SR_OK ||
-                    !png::write_file(gpaths[t], buf.data(), len))
-                    failed.store(1);
-                else if (gwritten) gwritten[t] = 1;
-            })) failed.store(1);
-            n_host += host_tiles.size();
-        }
-        t_hostenc += now() - t0;
-        return S2SR_OK;
-    };
-
-    for (int g = 0; g <= ngroups; ++g) {
-        if (g < ngroups) {
-            Group& G = groups[g];
-            double t0 = now();
-            HIPCHK(h, hipEventSynchronize(G.ev_stats));
-            double t1 = now();
-            t_wait += t1 - t0;
-            G.out_words = png_plan_tiles(G.n, G.stats, G.stats + (size_t)G.n * 512, G.stats + (size_t)G.n * 1024, paths + G.a,
-                                         (flags & S2SR_PNG_SKIP_TRANSPARENT) != 0, (flags & S2SR_PNG_HOST_ENCODER) != 0, &G.plan);
-            t_plan += now() - t1;
-            if (G.plan.failed) { return fail(h, S2SR_E_IO, "planning the tile streams failed (an encoder thread ran out of memory)"); }
-            total_words += G.out_words;
-            const int oslot = 4 + (g & 1);                       // the group's stream buffer: scratch 4 / 5 in turn
-            if ((rc = ensure_scratch(h, oslot, (G.out_words + 1) * 4))) return rc;
-            uint32_t* d_out = (uint32_t*)h->d_scratch[oslot];
-            HIPCHK(h, hipMemcpyAsync(G.d_tables, G.plan.tb, G.plan.upload_bytes, hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemsetAsync(d_out, 0, (G.out_words + 1) * 4, st));
-            {
-                Scope sc(h, st, F_MISC, 0.0, (double)G.n * 262144.0 + (double)G.out_words * 4.0);
-                const size_t tb_b = (size_t)G.n * 512 * 4, hdr_b = (size_t)G.n * 160 * 4;
-                HIPCHK(h, launch_png_tile_emit(d_tiles + (size_t)G.a * 262144, G.n, G.d_tables + tb_b + hdr_b, (const uint32_t*)G.d_tables,
-                                               (const uint32_t*)(G.d_tables + tb_b), d_out, row_threads, st));
-            }
-            HIPCHK(h, hipEventRecord(G.ev_emit, st));
-        }
-        if (g > 0) {
-            Group& P = groups[g - 1];
-            double t0 = now();
-            HIPCHK(h, hipEventSynchronize(P.ev_emit));           // the copy stream may read the group's streams
-            double t1 = now();
-            t_wait += t1 - t0;
-            if ((rc = write_group(P, (const uint32_t*)h->d_scratch[4 + ((g - 1) & 1)]))) return rc;
-            t_files += now() - t1;
-        }
-    }
-    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-    if (timing)
-        fprintf(stderr, "[s2sr png] %d tiles in %d group(s) (%zu on the host encoder), %.1f ms: waiting for the device %.1f, Huffman codes %.1f, "
-                "streams (%.0f MB) back in batches + files %.1f (of which host-encoded tiles %.1f)\n", n, ngroups, n_host, now() - t_begin, t_wait,
-                t_plan, (double)total_words * 4 / 1e6, t_files, t_hostenc);
-    h->tiles_slot = slot; h->tiles_nx = nx; h->tiles_ny = ny;      // the scratch requests above dropped the marker; the level is intact
-    if (failed.load()) return fail(h, S2SR_E_IO, "a tile file could not be written (or an encoder thread ran out of memory)");
-    return S2SR_OK;
 }
 
 int s2sr_set_profiling(s2sr_handle* h, int32_t on) {
@@ -2573,587 +1360,6 @@ int s2sr_calibrate_fp8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int32_t 
     h->fp8_g_exp = pick(m[1], old_g);
     if (x_exp) *x_exp = h->fp8_x_exp;
     if (g_exp) *g_exp = h->fp8_g_exp;
-    return S2SR_OK;
-}
-
-uint8_t s2sr_debug_f32_to_e4m3(float v) { return f32_to_e4m3(v); }
-
-size_t s2sr_debug_pack_f8_bytes(int32_t cin, int32_t cout) {
-    if (cin <= 0 || cout <= 0 || cout > 64) return 0;
-    return conv_wpack_bytes_f8(cin, cout);
-}
-
-int s2sr_debug_pack_f8(const float* w, int32_t cin, int32_t cout, uint8_t* out, int32_t* wscale) {
-    if (!w || !out || !wscale || cin <= 0 || cout <= 0 || cout > 64) return S2SR_E_INVALID;
-    pack_conv_weights_f8(w, cin, cout, out, wscale);
-    return S2SR_OK;
-}
-
-int s2sr_debug_conv(s2sr_handle* h, const float* x, int32_t N, int32_t Cin, int32_t H, int32_t W, const float* weight,
-                    const float* bias, int32_t Cout, int32_t upsample, int32_t act, float* y) {
-    if (!h || !x || !weight || !bias || !y || N <= 0 || Cin <= 0 || Cout <= 0 || Cout > 64 || H <= 0 || W <= 0)
-        return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const int NB = (Cin + 15) / 16;
-    const int OHh = upsample ? 2 * H : H, OWw = upsample ? 2 * W : W;
-    const int sHp = padded(H), sWp = padded(W), Hp = padded(OHh), Wp = padded(OWw);
-    const size_t sblk = (size_t)sHp * sWp * 32;
-    const size_t plane_b = (size_t)N * NB * sblk, xb = (size_t)N * Cin * H * W * 4,
-                 yb = (size_t)N * Cout * OHh * OWw * 4, wb = conv_wpack_bytes(Cin, Cout);
-    char *d_plane = nullptr, *d_w = nullptr;
-    float *d_x = nullptr, *d_y = nullptr, *d_b = nullptr;
-    HIPCHK(h, dev_malloc(&d_plane, plane_b));
-    HIPCHK(h, dev_malloc(&d_x, xb));
-    HIPCHK(h, dev_malloc(&d_y, yb));
-    HIPCHK(h, dev_malloc(&d_w, wb));
-    HIPCHK(h, dev_malloc(&d_b, 64 * 4));
-    std::vector<char> wp(wb);
-    pack_conv_weights(weight, Cin, Cout, 1, wp.data());
-    float bb[64] = {0};
-    memcpy(bb, bias, Cout * sizeof(float));
-    HIPCHK(h, hipMemsetAsync(d_plane, 0, plane_b, st));
-    HIPCHK(h, hipMemcpyAsync(d_x, x, xb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(d_w, wp.data(), wb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(d_b, bb, sizeof bb, hipMemcpyHostToDevice, st));
-    HIPCHK(h, launch_pack_f32_nchw(d_x, N, Cin, H, W, 1.0f, d_plane, NB, sHp, sWp, st));
-    ConvParams p{};
-    p.src = d_plane; p.src_img = (uint64_t)NB * sblk; p.nstage = NB;
-    p.wpack = d_w; p.bias = d_b; p.N = N; p.H = OHh; p.W = OWw; p.Hp = Hp; p.Wp = Wp; p.sHp = sHp; p.sWp = sWp;
-    p.out_f32 = d_y; p.cout = Cout; p.act = act; p.trash = h->d_trash;
-    HIPCHK(h, launch_conv(p, (Cout + 31) / 32, EPI_DEBUG, upsample != 0, false, st));
-    HIPCHK(h, hipMemcpyAsync(y, d_y, yb, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    dev_free(d_plane); dev_free(d_x); dev_free(d_y); dev_free(d_w); dev_free(d_b);
-    return S2SR_OK;
-}
-
-// diagnostic (bench.py secondary.mfma_ceiling): `launches` back-to-back launches of one of the three loops of ceiling.hip on one
-// workgroup per CU, timed with an event pair on the handle's stream behind launches / 4 + 1 untimed ones (the clock settles under load)
-int s2sr_debug_mfma_ceiling(s2sr_handle* h, int32_t mode, int32_t stages, int32_t launches, double* flop_per_launch, double* dma_bytes_per_launch,
-                            float* ms_total) {
-    if (!h || mode < 0 || mode > 8 || stages <= 0 || launches <= 0 || !ms_total) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-    const size_t src_bytes = (size_t)336 << 20;          // what a conv1-4 launch of 16 images fills its rings with; larger than L2 + MALL
-    int rc = ensure_scratch(h, 2, src_bytes);
-    if (rc) return rc;
-    const size_t sink_bytes = (size_t)ncu * 512 * 4, store_bytes = (size_t)64 << 20;      // mode 5 streams its stores through 64 MB
-    if ((rc = ensure_scratch(h, 3, sink_bytes + store_bytes))) return rc;
-    char* d_store = (char*)h->d_scratch[3] + sink_bytes;
-    hipStream_t st = h->stream;
-    hipEvent_t e0 = get_event(h), e1 = get_event(h);
-    HIPCHK(h, launch_mfma_ceiling(mode, (char*)h->d_scratch[2], src_bytes, true /* fill the operands: 0.1 ms */, (float*)h->d_scratch[3], ncu, stages, d_store,
-                                  store_bytes, st));
-    for (int i = 0; i < launches / 4; ++i)
-        HIPCHK(h, launch_mfma_ceiling(mode, (char*)h->d_scratch[2], src_bytes, false, (float*)h->d_scratch[3], ncu, stages, d_store, store_bytes, st));
-    HIPCHK(h, hipEventRecord(e0, st));
-    for (int i = 0; i < launches; ++i)
-        HIPCHK(h, launch_mfma_ceiling(mode, (char*)h->d_scratch[2], src_bytes, false, (float*)h->d_scratch[3], ncu, stages, d_store, store_bytes, st));
-    HIPCHK(h, hipEventRecord(e1, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipEventElapsedTime(ms_total, e0, e1));
-    h->ev_pool.push_back(e0); h->ev_pool.push_back(e1);
-    if (flop_per_launch) *flop_per_launch = mfma_ceiling_flop_per_launch(mode, ncu, stages);
-    if (dma_bytes_per_launch) *dma_bytes_per_launch = mfma_ceiling_dma_bytes_per_launch(mode, ncu, stages);
-    return S2SR_OK;
-}
-
-// diagnostic prototype (persist.hip): `launches` launches of the RDB-shaped loop whose workgroups stay across layers, `grid` workgroups (<= one per
-// CU: they must all be resident) of `P` patches each, `rdbs` RDBs per launch; flags in uncached device memory, zeroed in front of every launch
-int s2sr_debug_rdb_persistent(s2sr_handle* h, int32_t variant, int32_t grid, int32_t P, int32_t rdbs, int32_t launches, double* flop_per_launch,
-                              float* ms_total, int32_t* timeouts, int32_t* mismatches) {
-    if (!h || variant < 0 || variant > 5 || grid < 2 || P < 2 || P > 4 || rdbs < 1 || rdbs > 4000 || launches < 1 || !ms_total) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->compact()) return fail(h, S2SR_E_INVALID, "s2sr_debug_rdb_persistent: RRDB handles only");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    int ncu = 256;
-    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-    if (grid > ncu) return fail(h, S2SR_E_INVALID, "more workgroups than CUs: they would not all be resident");
-    const size_t wts_bytes = (size_t)8 << 20, ws_bytes = rdb_persistent_ws_bytes(variant, grid, P), sink_bytes = (size_t)grid * 512 * 4;
-    int rc = ensure_scratch(h, 2, wts_bytes);
-    if (rc) return rc;
-    if ((rc = ensure_scratch(h, 3, sink_bytes + 256))) return rc;
-    if ((rc = ensure_scratch(h, 4, ws_bytes))) return rc;
-    struct Uncached {
-        void* p = nullptr;
-        ~Uncached() { if (p) (void)hipFree(p); }
-    } fl;
-    const size_t flag_bytes = ((size_t)grid * P + 1) * 4;
-    HIPCHK(h, hipExtMallocWithFlags(&fl.p, flag_bytes, hipDeviceMallocUncached));
-    uint32_t* d_timeouts = (uint32_t*)((char*)h->d_scratch[3] + sink_bytes);
-    hipStream_t st = h->stream;
-    // operand data: the ceiling loops' generator fills the weights buffer and the working set (toggle rates as there)
-    HIPCHK(h, launch_mfma_ceiling(0, (char*)h->d_scratch[2], wts_bytes, true, (float*)h->d_scratch[3], 1, 1, nullptr, 0, st));
-    HIPCHK(h, launch_mfma_ceiling(0, (char*)h->d_scratch[4], ws_bytes, true, (float*)h->d_scratch[3], 1, 1, nullptr, 0, st));
-    HIPCHK(h, hipMemsetAsync(d_timeouts, 0, 12, st));
-    hipEvent_t e0 = get_event(h), e1 = get_event(h);
-    auto one = [&]() -> int {
-        HIPCHK(h, hipMemsetAsync(fl.p, 0, flag_bytes, st));
-        HIPCHK(h, launch_rdb_persistent(variant, (const char*)h->d_scratch[2], wts_bytes, (char*)h->d_scratch[4], (uint32_t*)fl.p, (float*)h->d_scratch[3],
-                                        grid, P, rdbs, d_timeouts, st));
-        return S2SR_OK;
-    };
-    for (int i = 0; i < launches / 4 + 1; ++i)
-        if ((rc = one())) return rc;
-    HIPCHK(h, hipEventRecord(e0, st));
-    for (int i = 0; i < launches; ++i)
-        if ((rc = one())) return rc;
-    HIPCHK(h, hipEventRecord(e1, st));
-    uint32_t to[3] = {0, 0, 0};
-    HIPCHK(h, hipMemcpyAsync(to, d_timeouts, 12, hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, hipEventElapsedTime(ms_total, e0, e1));
-    h->ev_pool.push_back(e0); h->ev_pool.push_back(e1);
-    if (flop_per_launch) *flop_per_launch = rdb_persistent_flop_per_launch(grid, P, rdbs);
-    if (timeouts) *timeouts = (int32_t)to[0];
-    if (mismatches) { mismatches[0] = (int32_t)to[1]; mismatches[1] = (int32_t)to[2]; }
-    return S2SR_OK;
-}
-
-int s2sr_debug_get_config(s2sr_handle* h, s2sr_debug_config* out) {
-    if (!h || !out) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    memset(out, 0, sizeof *out);
-    // trunk_w4 always 1; trunk_wino, fp8_form, reserved[1] and reserved[3] always 0 (the forms they named were removed)
-    out->precision = h->cfg.precision; out->group = h->cfg.group; out->trunk_w4 = 1; out->lo_exp = h->lo_exp;
-    out->fp8_x_exp = h->fp8_x_exp; out->fp8_g_exp = h->fp8_g_exp; out->fp8_hp_tail = h->fp8_hp_tail ? 1 : 0;
-    out->graphs_on = h->graphs_on ? 1 : 0; out->reserved[0] = h->mosaic_on ? 1 : 0; out->reserved[2] = h->last_fold ? 1 : 0; out->reserved[4] = h->f16_full ? 1 : 0; out->reserved[5] = (int32_t)h->ws_allocs;
-    return S2SR_OK;
-}
-
-// One RDB-shaped conv through conv_trunk_f16 / conv_trunk_f8.  Host-side packing and decoding (a test hook: clarity over
-// speed); the weights go through the production device packers (pack.hip).
-int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
-    if (!h || !a || !a->x || !a->weight || !a->bias || !a->y) return S2SR_E_INVALID;
-    if (h->compact()) return S2SR_E_INVALID;     // RRDB handles only
-    const int kind = a->kind, N = a->N, Cin = a->Cin, H = a->H, W = a->W;
-    if (kind < 0 || kind > 5 || N <= 0 || H <= 0 || W <= 0) return S2SR_E_INVALID;
-    const bool f8 = kind >= 3, c5 = (kind % 3) != 0, rr = (kind % 3) == 2;
-    const int Cout = c5 ? 64 : 32;
-    if (c5 ? Cin != 192 : (Cin != 64 && Cin != 96 && Cin != 128 && Cin != 160)) return fail(h, S2SR_E_INVALID, "Cin does not match the RDB form");
-    if (rr && !a->skip) return fail(h, S2SR_E_INVALID, "rdb3 form needs skip");
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const int Hp = padded(H), Wp = padded(W);
-    const size_t ppx = (size_t)Hp * Wp, blk = ppx * 32;
-    auto pix = [&](int y, int x) { return (size_t)(y + 1) * Wp + (x + 1); };
-    // ---- weights through the production device packers
-    DevBuf d_w32, d_wp, d_b, d_ws;
-    const size_t wn = (size_t)Cout * Cin * 9;
-    HIPCHK(h, dev_malloc(&d_w32.p, wn * 4));
-    HIPCHK(h, hipMemcpyAsync(d_w32.p, a->weight, wn * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, dev_malloc(&d_wp.p, f8 ? conv_wpack_bytes_f8(Cin, Cout) : conv_wpack_bytes(Cin, Cout)));
-    HIPCHK(h, dev_malloc(&d_b.p, 64 * 4));
-    HIPCHK(h, dev_malloc(&d_ws.p, 64 * 4));
-    float bb[64] = {0};
-    memcpy(bb, a->bias, Cout * sizeof(float));
-    HIPCHK(h, hipMemcpyAsync(d_b.p, bb, sizeof bb, hipMemcpyHostToDevice, st));
-    if (f8) HIPCHK(h, launch_pack_trunk_f8((const float*)d_w32.p, Cin, Cout, d_wp.p, (int32_t*)d_ws.p, st));
-    else HIPCHK(h, launch_pack_trunk_f16((const float*)d_w32.p, Cin, Cout, d_wp.p, st));
-    // ---- activations: the dense tensor D (12 fp16 blocks per image, or 6 e4m3 planes), packed on the host
-    const int xe = h->fp8_x_exp, ge = h->fp8_g_exp, le = h->lo_exp;
-    const size_t dimg = (f8 ? 6 : 12) * blk;
-    std::vector<char> D((size_t)N * dimg, 0);
-    for (int n = 0; n < N; ++n)
-        for (int c = 0; c < Cin; ++c)
-            for (int y = 0; y < H; ++y)
-                for (int x = 0; x < W; ++x) {
-                    const float v = a->x[(((size_t)n * Cin + c) * H + y) * W + x];
-                    if (f8) {
-                        const float sc = ldexpf(v, c < 64 ? xe : ge);
-                        ((uint8_t*)D.data())[(size_t)n * dimg + (size_t)(c >> 5) * blk + pix(y, x) * 32 + (c & 31)] = f32_to_e4m3(sc);
-                    } else {
-                        ((hf16*)(D.data() + (size_t)n * dimg + (size_t)(c >> 4) * blk + pix(y, x) * 32))[c & 15] = (hf16)v;
-                    }
-                }
-    // a 64-channel NCHW tensor as (fp16 hi blocks [4], e4m3(lo * 2^le) planes [2]) or as fp16 only
-    auto split64 = [&](const float* src, std::vector<char>& hi, size_t hi_img, std::vector<char>* lo8, bool hi_is_value) {
-        for (int n = 0; n < N; ++n)
-            for (int c = 0; c < 64; ++c)
-                for (int y = 0; y < H; ++y)
-                    for (int x = 0; x < W; ++x) {
-                        const float v = src ? src[(((size_t)n * 64 + c) * H + y) * W + x] : 0.f;
-                        const hf16 hv = (hf16)v;
-                        if (hi_is_value) ((hf16*)(hi.data() + (size_t)n * hi_img + (size_t)(c >> 4) * blk + pix(y, x) * 32))[c & 15] = hv;
-                        if (lo8) {
-                            const float l = hi_is_value ? v - (float)hv : v;
-                            ((uint8_t*)lo8->data())[(size_t)n * 2 * blk + (size_t)(c >> 5) * blk + pix(y, x) * 32 + (c & 31)] = f32_to_e4m3(ldexpf(l, le));
-                        }
-                    }
-    };
-    DevBuf d_D, d_D2, d_Tin, d_Tout, d_Sk, d_SkLo, d_Xin, d_Xout;
-    HIPCHK(h, dev_malloc(&d_D.p, D.size()));
-    HIPCHK(h, hipMemcpyAsync(d_D.p, D.data(), D.size(), hipMemcpyHostToDevice, st));
-    ConvParams p{};
-    p.N = N; p.H = H; p.W = W; p.Hp = Hp; p.Wp = Wp; p.sHp = Hp; p.sWp = Wp;
-    p.src = (const char*)d_D.p; p.src_img = dimg; p.wpack = d_wp.p; p.bias = (const float*)d_b.p; p.trash = h->d_trash;
-    const int epi = !c5 ? EPI_LRELU : (rr ? EPI_RDB5_RRDB : EPI_RDB5);
-    std::vector<char> tmp;
-    if (!f8) {
-        p.nstage = Cin / 16; p.seg_len = p.nstage; p.lo_exp = le;
-        if (!c5) {
-            p.dst = (char*)d_D.p + (size_t)(Cin / 16) * blk; p.dst_img = dimg;       // the next growth slot of the same dense tensor
-        } else {
-            HIPCHK(h, dev_malloc(&d_D2.p, D.size()));
-            HIPCHK(h, hipMemsetAsync(d_D2.p, 0, D.size(), st));
-            p.dst = (char*)d_D2.p; p.dst_img = dimg;
-            std::vector<char> lo8((size_t)N * 2 * blk, 0), none;
-            split64(a->lo, none, 0, &lo8, false);
-            HIPCHK(h, dev_malloc(&d_Tin.p, lo8.size()));
-            HIPCHK(h, dev_malloc(&d_Tout.p, lo8.size()));
-            HIPCHK(h, hipMemcpyAsync(d_Tin.p, lo8.data(), lo8.size(), hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemsetAsync(d_Tout.p, 0, lo8.size(), st));
-            HIPCHK(h, hipStreamSynchronize(st));
-            p.xh_in = (const char*)d_Tin.p; p.T = (char*)d_Tout.p;
-            if (rr) {
-                std::vector<char> shi((size_t)N * 4 * blk, 0), slo((size_t)N * 2 * blk, 0);
-                split64(a->skip, shi, 4 * blk, &slo, true);
-                HIPCHK(h, dev_malloc(&d_Sk.p, shi.size()));
-                HIPCHK(h, dev_malloc(&d_SkLo.p, slo.size()));
-                HIPCHK(h, hipMemcpyAsync(d_Sk.p, shi.data(), shi.size(), hipMemcpyHostToDevice, st));
-                HIPCHK(h, hipMemcpyAsync(d_SkLo.p, slo.data(), slo.size(), hipMemcpyHostToDevice, st));
-                HIPCHK(h, hipStreamSynchronize(st));
-                p.xh_skip = (const char*)d_Sk.p; p.xh_img = 4 * blk; p.lo_skip = (const char*)d_SkLo.p;
-            }
-        }
-        const hipError_t e = launch_conv_trunk(p, Cout / 32, epi, st, a->form);
-        if (e != hipSuccess) return fail(h, S2SR_E_HIP, std::string("launch_conv_trunk: ") + hipGetErrorString(e));
-    } else {
-        p.seg_len = Cin / 32; p.nstage = (p.seg_len + 1) & ~1; p.wscale = (const int32_t*)d_ws.p;
-        p.x_exp = xe; p.g_exp = ge; p.xh_img = 4 * blk;
-        if (!c5) {
-            p.dst = (char*)d_D.p + (size_t)(Cin / 32) * blk; p.dst_img = dimg;
-        } else {
-            HIPCHK(h, dev_malloc(&d_D2.p, D.size()));
-            HIPCHK(h, hipMemsetAsync(d_D2.p, 0, D.size(), st));
-            p.dst = (char*)d_D2.p; p.dst_img = dimg;
-            std::vector<char> xin((size_t)N * 4 * blk, 0);      // the fp16 trunk = the first 64 of the Cin input channels
-            for (int n = 0; n < N; ++n)
-                for (int c = 0; c < 64; ++c)
-                    for (int y = 0; y < H; ++y)
-                        for (int x = 0; x < W; ++x)
-                            ((hf16*)(xin.data() + (size_t)n * 4 * blk + (size_t)(c >> 4) * blk + pix(y, x) * 32))[c & 15] =
-                                (hf16)a->x[(((size_t)n * Cin + c) * H + y) * W + x];
-            HIPCHK(h, dev_malloc(&d_Xin.p, xin.size()));
-            HIPCHK(h, dev_malloc(&d_Xout.p, xin.size()));
-            HIPCHK(h, hipMemcpyAsync(d_Xin.p, xin.data(), xin.size(), hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemsetAsync(d_Xout.p, 0, xin.size(), st));
-            HIPCHK(h, hipStreamSynchronize(st));
-            p.xh_in = (const char*)d_Xin.p; p.xh_out = (char*)d_Xout.p;
-            if (rr) {
-                std::vector<char> shi((size_t)N * 4 * blk, 0);
-                split64(a->skip, shi, 4 * blk, nullptr, true);
-                HIPCHK(h, dev_malloc(&d_Sk.p, shi.size()));
-                HIPCHK(h, hipMemcpyAsync(d_Sk.p, shi.data(), shi.size(), hipMemcpyHostToDevice, st));
-                HIPCHK(h, hipStreamSynchronize(st));
-                p.xh_skip = (const char*)d_Sk.p;
-            }
-        }
-        // conv1-4: the loader-wave form is the only one (the others the measurements buried are refused)
-        const hipError_t e = (kind == 3 && a->form != 0) ? hipErrorNotSupported : launch_conv_trunk_f8(p, Cout / 32, epi, st);
-        if (e != hipSuccess) return fail(h, S2SR_E_HIP, std::string("launch_conv_trunk_f8: ") + hipGetErrorString(e));
-    }
-    HIPCHK(h, hipStreamSynchronize(st));
-    // ---- read back and decode
-    auto get = [&](const void* d, size_t bytes) -> int {
-        tmp.resize(bytes);
-        HIPCHK(h, copy_blocking(h, tmp.data(), d, bytes, hipMemcpyDeviceToHost));
-        return S2SR_OK;
-    };
-    int rc;
-    auto for_out = [&](int C, auto fn) {
-        for (int n = 0; n < N; ++n)
-            for (int c = 0; c < C; ++c)
-                for (int y = 0; y < H; ++y)
-                    for (int x = 0; x < W; ++x) fn(n, c, y, x, (((size_t)n * C + c) * H + y) * W + x);
-    };
-    if (!f8 && !c5) {
-        if ((rc = get(d_D.p, D.size()))) return rc;
-        const size_t ob = (size_t)(Cin / 16) * blk;
-        for_out(32, [&](int n, int c, int y, int x, size_t o) {
-            a->y[o] = (float)((const hf16*)(tmp.data() + (size_t)n * dimg + ob + (size_t)(c >> 4) * blk + pix(y, x) * 32))[c & 15];
-        });
-    } else if (!f8) {
-        if ((rc = get(d_D2.p, D.size()))) return rc;
-        std::vector<char> hi = tmp;
-        if ((rc = get(d_Tout.p, (size_t)N * 2 * blk))) return rc;
-        for_out(64, [&](int n, int c, int y, int x, size_t o) {
-            const float hv = (float)((const hf16*)(hi.data() + (size_t)n * dimg + (size_t)(c >> 4) * blk + pix(y, x) * 32))[c & 15];
-            const uint8_t lb = ((const uint8_t*)tmp.data())[(size_t)n * 2 * blk + (size_t)(c >> 5) * blk + pix(y, x) * 32 + (c & 31)];
-            a->y[o] = hv + ldexpf(e4m3_to_f32(lb), -le);
-        });
-    } else if (!c5) {
-        if ((rc = get(d_D.p, D.size()))) return rc;
-        const size_t ob = (size_t)(Cin / 32) * blk;
-        for_out(32, [&](int n, int c, int y, int x, size_t o) {
-            a->y[o] = ldexpf(e4m3_to_f32(((const uint8_t*)tmp.data())[(size_t)n * dimg + ob + pix(y, x) * 32 + c]), -ge);
-        });
-    } else {
-        if ((rc = get(d_Xout.p, (size_t)N * 4 * blk))) return rc;
-        for_out(64, [&](int n, int c, int y, int x, size_t o) {
-            a->y[o] = (float)((const hf16*)(tmp.data() + (size_t)n * 4 * blk + (size_t)(c >> 4) * blk + pix(y, x) * 32))[c & 15];
-        });
-        if (a->y_aux) {
-            if ((rc = get(d_D2.p, D.size()))) return rc;
-            for_out(64, [&](int n, int c, int y, int x, size_t o) {
-                a->y_aux[o] = ldexpf(e4m3_to_f32(((const uint8_t*)tmp.data())[(size_t)n * dimg + (size_t)(c >> 5) * blk + pix(y, x) * 32 + (c & 31)]), -xe);
-            });
-        }
-    }
-    return S2SR_OK;
-}
-
-int s2sr_debug_bench_conv(s2sr_handle* h, int32_t N, int32_t H, int32_t W, int32_t cin, int32_t cout, int32_t iters,
-                          float* avg_us, uint64_t* trace, int32_t trace_wgs) {
-    if (!h || !avg_us || N <= 0 || H <= 0 || W <= 0 || iters <= 0 || cin < 16 || cin > 192 || cin % 16 ||
-        (cout != 32 && cout != 64))
-        return S2SR_E_INVALID;
-    if (trace && trace_wgs > 0) return fail(h, S2SR_E_INVALID, "stamped kernel builds are not part of this library");
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const int Hp = padded(H), Wp = padded(W);
-    const size_t blk = (size_t)Hp * Wp * 32;
-    const size_t wb = conv_wpack_bytes(cin, cout), db = (size_t)N * 12 * blk;
-    DevBuf D0, D1, T, Rr, d_w, d_b;
-    HIPCHK(h, dev_malloc(&D0.p, db));
-    HIPCHK(h, dev_malloc(&D1.p, db));
-    HIPCHK(h, dev_malloc(&T.p, (size_t)N * 4 * blk));
-    HIPCHK(h, dev_malloc(&Rr.p, (size_t)N * 8 * blk));
-    HIPCHK(h, dev_malloc(&d_w.p, wb));
-    HIPCHK(h, dev_malloc(&d_b.p, 256));
-    // pseudo-random fp16 bit patterns (finite, |v| < 2)
-    std::vector<unsigned char> pat(db > wb ? db : wb);
-    unsigned s = 12345u;
-    for (size_t i = 0; i + 1 < pat.size(); i += 2) {
-        s = s * 1664525u + 1013904223u;
-        pat[i] = (unsigned char)(s >> 24);
-        pat[i + 1] = (unsigned char)(((s >> 16) & 0x80) | 0x30 | ((s >> 8) & 0x0b));
-    }
-    HIPCHK(h, copy_blocking(h, D0.p, pat.data(), db, hipMemcpyHostToDevice));
-    HIPCHK(h, copy_blocking(h, d_w.p, pat.data(), wb, hipMemcpyHostToDevice));
-    HIPCHK(h, fill_blocking(h, D1.p, 0, db));
-    HIPCHK(h, fill_blocking(h, T.p, 0, (size_t)N * 4 * blk));
-    HIPCHK(h, fill_blocking(h, Rr.p, 0, (size_t)N * 8 * blk));
-    HIPCHK(h, fill_blocking(h, d_b.p, 0, 256));
-    ConvParams p{};
-    p.src = (const char*)D0.p; p.src_img = 12 * blk; p.nstage = cin / 16;
-    p.wpack = d_w.p; p.bias = (const float*)d_b.p; p.N = N; p.H = H; p.W = W; p.Hp = Hp; p.Wp = Wp; p.sHp = Hp; p.sWp = Wp;
-    p.T = (char*)T.p; p.R = (float*)Rr.p; p.F = (float*)Rr.p; p.trash = h->d_trash;
-    p.xh_in = (const char*)T.p; p.lo_exp = h->lo_exp;   // conv_trunk_f16: trunk lo coming in (here read and written in place: timing only)
-    p.dst = (char*)D1.p; p.dst_img = 12 * blk;
-    p.f16_form = (h->small8 ? 0 : 2) | (h->f16_full ? 0 : 4);
-    const int epi = cout == 32 ? EPI_LRELU : EPI_RDB5, ct = cout / 32;
-    hipEvent_t e0, e1;
-    HIPCHK(h, hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); return fail(h, S2SR_E_HIP, "hipEventCreate failed"); }
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = launch_conv_trunk(p, ct, epi, st);
-    if (e == hipSuccess) e = hipEventRecord(e0, st);
-    for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_conv_trunk(p, ct, epi, st);
-    if (e == hipSuccess) e = hipEventRecord(e1, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    float ms = 0;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    HIPCHK(h, e);
-    *avg_us = ms * 1000.0f / iters;
-    return S2SR_OK;
-}
-
-namespace {
-// The launch plan a tap hook's batch gets from forward_dev (s2sr_forward_part_u8_dev: the job's mosaic) and the one launch group /
-// mosaic segment it must be.
-struct TapPlan {
-    Mosaic plan;
-    int NI = 0, skx = 0, sky = 0, SH = 0, SW = 0, IH = 0, IW = 0;
-};
-int tap_plan(s2sr_handle* h, bool u8, int32_t B, int32_t th, int32_t tw, int32_t job_windows, TapPlan* tp) {
-    const int job = job_windows > B ? job_windows : B;
-    const int u = h->unshuffle();
-    if (th % u || tw % u) return fail(h, S2SR_E_INVALID, "a scale-2 handle (pixel_unshuffle by 2) needs even tile sizes");
-    th /= u; tw /= u;                                   // the trunk grid from here on
-    Mosaic plan = u8 ? pick_mosaic_cfg(h->mosaic_on, job, th, tw) : Mosaic();
-    const int per = plan.on() ? plan.kx * plan.ky : 1;
-    int skx = plan.kx, sky = plan.ky;
-    if (plan.on()) {
-        if (B / per && B % per) return fail(h, S2SR_E_INVALID, "batch spans two mosaic segments (full mosaics and a remainder)");
-        if (B < per) mosaic_remainder(B, plan.kx, plan.ky, &skx, &sky);
-    }
-    const int sper = plan.on() ? skx * sky : 1;
-    tp->plan = plan; tp->skx = skx; tp->sky = sky;
-    tp->NI = (B + sper - 1) / sper;
-    tp->IH = plan.on() ? plan.ky * (th + 1) - 1 : th; tp->IW = plan.on() ? plan.kx * (tw + 1) - 1 : tw;
-    tp->SH = plan.on() ? sky * (th + 1) - 1 : th; tp->SW = plan.on() ? skx * (tw + 1) - 1 : tw;
-    if (tp->NI > group_size(h, (job + per - 1) / per, tp->IH, tp->IW)) return fail(h, S2SR_E_INVALID, "batch needs more than one launch group");
-    return S2SR_OK;
-}
-// ... and the run: forward_dev -> run_net eagerly (graphs off for the call) on buffers of its own, outputs copied back
-int tap_forward(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, const TapPlan& tp,
-                uint8_t* out_u8, float* out_f32) {
-    hipStream_t st = h->stream;
-    const size_t ib = tiles ? (size_t)B * th * tw * 3 : (size_t)B * 3 * th * tw * 4, opx = (size_t)B * h->cfg.scale * h->cfg.scale * th * tw;
-    DevBuf d_in, d_o8, d_o32;
-    HIPCHK(h, dev_malloc(&d_in.p, ib));
-    HIPCHK(h, dev_malloc(&d_o8.p, opx * 3));
-    HIPCHK(h, dev_malloc(&d_o32.p, opx * 3 * 4));
-    HIPCHK(h, hipMemcpyAsync(d_in.p, tiles ? (const void*)tiles : (const void*)x, ib, hipMemcpyHostToDevice, st));
-    const bool graphs = h->graphs_on;
-    h->graphs_on = false;
-    Mosaic plan = tp.plan;
-    int rc = forward_dev(h, st, tiles ? (const uint8_t*)d_in.p : nullptr, tiles ? nullptr : (const float*)d_in.p, B, th, tw,
-                         out_u8 ? (uint8_t*)d_o8.p : nullptr, out_f32 ? (float*)d_o32.p : nullptr, plan.on() ? &plan : nullptr);
-    h->graphs_on = graphs;
-    if (rc) return rc;
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (h->ws.G < tp.NI) return fail(h, S2SR_E_INVALID, "workspace fell back to a smaller launch group: the batch ran in two");
-    if (out_u8) HIPCHK(h, copy_blocking(h, out_u8, d_o8.p, opx * 3, hipMemcpyDeviceToHost));
-    if (out_f32) HIPCHK(h, copy_blocking(h, out_f32, d_o32.p, opx * 3 * 4, hipMemcpyDeviceToHost));
-    return S2SR_OK;
-}
-}  // namespace
-
-// The tail's per-layer parity hook: one batch through forward_dev -> run_net as production runs it (eagerly: graphs off for the
-// call), then the tensors of the six head / tail convs copied out of the workspace and decoded on the host.
-int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, int32_t job_windows,
-                            s2sr_debug_taps* t) {
-    if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->compact()) return fail(h, S2SR_E_INVALID, "s2sr_debug_forward_taps: RRDB handles only (compact: s2sr_debug_compact_taps)");
-    if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    TapPlan tp;
-    int rc = tap_plan(h, tiles != nullptr, B, th, tw, job_windows, &tp);
-    if (rc) return rc;
-    const int NI = tp.NI;
-    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;
-    const bool hp = h->cfg.precision == S2SR_PREC_F16_HP || (fp8 && h->fp8_hp_tail);
-    t->n = NI;
-    for (int k = 0; k < 3; ++k) {
-        const int s = k == 0 ? 1 : 2 * k;
-        t->H[k] = s * tp.SH; t->W[k] = s * tp.SW; t->Hp[k] = padded(s * tp.IH); t->Wp[k] = padded(s * tp.IW);
-    }
-    const bool mos = tp.plan.on();
-    t->mos_kx = mos ? tp.skx : 0; t->mos_ky = mos ? tp.sky : 0; t->mos_wh = mos ? tp.plan.wh : 0; t->mos_ww = mos ? tp.plan.ww : 0;
-    t->mos_count = mos ? B : 0;
-    t->trunk_lo_exp = fp8 ? -1 : h->lo_exp;
-    t->avail = 0;
-    for (int k = 0; k < S2SR_TAP_COUNT; ++k)
-        if (hp || (k != S2SR_TAP_T8 && k < S2SR_TAP_U0LO)) t->avail |= 1 << k;
-    bool any = t->out_f32 || t->out_u8;
-    for (int k = 0; k < S2SR_TAP_COUNT; ++k) any = any || t->tap[k];
-    if (!any) return S2SR_OK;
-    if ((rc = tap_forward(h, tiles, x, B, th, tw, tp, t->out_u8, t->out_f32))) return rc;
-    const Workspace& w = h->ws;
-    // ---- decoders: NI images of `nb` planes of 32 B per pixel at `img` bytes apart -> [n][channels][Hp][Wp] fp32
-    std::vector<uint8_t> buf;
-    auto blk_at = [&](int k) { return k == 0 ? w.blk1 : k == 1 ? w.blk2 : w.blk4; };
-    auto f16_planes = [&](float* dst, const char* src, uint64_t img, int nb, int k) { return decode_f16_planes(h, dst, src, img, NI, nb, blk_at(k)); };
-    auto e4m3_planes = [&](float* dst, const char* src, uint64_t img, int nb, int k, const float* scale /*[nb]*/) {   // 32 ch per plane
-        return decode_e4m3_planes(h, dst, src, img, NI, nb, blk_at(k), scale);
-    };
-    const float s_lo4[4] = {1.0f / 2048.0f, 1.0f / 2048.0f, 1.0f, 1.0f};
-    const int nb1 = 1;
-    if (t->tap[S2SR_TAP_P0] && (rc = f16_planes(t->tap[S2SR_TAP_P0], w.P0, w.blk1, nb1, 0))) return rc;
-    if (t->tap[S2SR_TAP_F]) {   // fp32 blocked-8: [n][8][Hp][Wp][8]
-        const size_t np = w.blk1 / 32;
-        if ((rc = fetch_planes(h, buf, (const char*)w.F, 8 * w.blk1, NI, 8, w.blk1))) return rc;
-        const float* v = (const float*)buf.data();
-        for (int i = 0; i < NI; ++i)
-            for (int b = 0; b < 8; ++b)
-                for (size_t q = 0; q < np; ++q)
-                    for (int c = 0; c < 8; ++c) t->tap[S2SR_TAP_F][(((size_t)i * 64 + b * 8 + c) * np) + q] = v[(((size_t)i * 8 + b) * np + q) * 8 + c];
-    }
-    const auto& tr = h->trunk_rec;
-    if (t->tap[S2SR_TAP_TRUNK_HI] && (rc = f16_planes(t->tap[S2SR_TAP_TRUNK_HI], tr.hi, tr.hi_img, 4, 0))) return rc;
-    if (t->tap[S2SR_TAP_TRUNK_LO]) {
-        if (tr.lo_exp >= 0) {
-            const float s = ldexpf(1.0f, -tr.lo_exp), sc[2] = {s, s};
-            if ((rc = e4m3_planes(t->tap[S2SR_TAP_TRUNK_LO], tr.lo, tr.lo_img, 2, 0, sc))) return rc;
-        } else if ((rc = f16_planes(t->tap[S2SR_TAP_TRUNK_LO], tr.lo, tr.lo_img, 4, 0))) return rc;
-    }
-    if (hp && t->tap[S2SR_TAP_T8] && (rc = e4m3_planes(t->tap[S2SR_TAP_T8], w.T8, 4 * w.blk1, 4, 0, s_lo4))) return rc;
-    const char* U[4] = {w.U0, w.U1, w.U2, w.U3};
-    const char* UL[4] = {w.U0lo, w.U1lo, w.U2lo, w.U3lo};
-    const int Uk[4] = {0, 1, 2, 2};
-    const size_t Ublk[4] = {w.blk1, w.blk2, w.blk4, w.blk4};
-    for (int u = 0; u < 4; ++u) {
-        if (t->tap[S2SR_TAP_U0 + u] && (rc = f16_planes(t->tap[S2SR_TAP_U0 + u], U[u], 4 * Ublk[u], 4, Uk[u]))) return rc;
-        if (hp && t->tap[S2SR_TAP_U0LO + u] && (rc = e4m3_planes(t->tap[S2SR_TAP_U0LO + u], UL[u], 4 * Ublk[u], 4, Uk[u], s_lo4))) return rc;
-    }
-    return S2SR_OK;
-}
-
-// The trunk's per-RDB parity hook: the batch of s2sr_debug_forward_taps, with run_net copying the trunk fields of the RDBs
-// [first, first + count) out at every RDB boundary (trunk_tap) and the conv launches recording their kernel forms.
-int s2sr_debug_trunk_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, int32_t job_windows,
-                          s2sr_debug_trunk_fields* t) {
-    if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->compact()) return fail(h, S2SR_E_INVALID, "s2sr_debug_trunk_taps: RRDB handles only (compact: s2sr_debug_compact_taps)");
-    if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
-    if (h->cfg.scale != 4) return fail(h, S2SR_E_INVALID, "trunk taps: scale-4 handles only (the scale-2 trunk is the same schedule on the half grid)");
-    if (t->first < 0 || t->count < 1 || t->first + t->count > 3 * h->cfg.num_block)
-        return fail(h, S2SR_E_INVALID, "RDB range outside [0, 3 * num_block)");
-    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;
-    if (h->d_calib) return fail(h, S2SR_E_INVALID, "trunk taps: the handle is calibrating");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    TapPlan tp;
-    int rc = tap_plan(h, tiles != nullptr, B, th, tw, job_windows, &tp);
-    if (rc) return rc;
-    const bool mos = tp.plan.on();
-    t->n = tp.NI; t->H = tp.SH; t->W = tp.SW; t->Hp = padded(tp.IH); t->Wp = padded(tp.IW);
-    t->mos_kx = mos ? tp.skx : 0; t->mos_ky = mos ? tp.sky : 0; t->mos_wh = mos ? th : 0; t->mos_ww = mos ? tw : 0;
-    t->mos_count = mos ? B : 0;
-    t->fp8 = fp8 ? 1 : 0;
-    t->lo_exp = fp8 ? -1 : h->lo_exp;
-    t->x_exp = fp8 ? h->fp8_x_exp : -1;
-    t->g_exp = fp8 ? h->fp8_g_exp : -1;
-    if (!(t->x_hi || t->x_lo || t->growth || t->skip_hi || t->skip_lo || t->entry_lo || t->form || t->out_f32 || t->out_u8)) return S2SR_OK;
-    if (t->form) memset(t->form, 0, sizeof(*t->form) * 5 * (size_t)t->count);
-    TrunkTap tt;
-    tt.first = t->first; tt.count = t->count; tt.t = t;
-    h->ttap = &tt;
-    rc = tap_forward(h, tiles, x, B, th, tw, tp, t->out_u8, t->out_f32);
-    h->ttap = nullptr;
-    return rc;
-}
-
-// SRVGGNetCompact's per-layer parity hook: the batch of s2sr_debug_forward_taps, with run_net_compact copying the chosen layers'
-// fp16 activations out right behind their launches.
-int s2sr_debug_compact_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw, int32_t job_windows,
-                            s2sr_debug_compact_fields* t) {
-    if (!h || !t || (!tiles == !x) || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!h->compact()) return fail(h, S2SR_E_INVALID, "s2sr_debug_compact_taps: compact handles only");
-    if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
-    if (t->nlayers < 0 || t->nlayers > S2SR_COMPACT_TAPS_MAX) return fail(h, S2SR_E_INVALID, "too many layers");
-    for (int k = 0; k < t->nlayers; ++k)
-        if (t->layers[k] < 0 || t->layers[k] > h->cfg.num_block || (k > 0 && t->layers[k] <= t->layers[k - 1]))
-            return fail(h, S2SR_E_INVALID, "layers must ascend inside [0, num_conv]");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    TapPlan tp;
-    int rc = tap_plan(h, tiles != nullptr, B, th, tw, job_windows, &tp);
-    if (rc) return rc;
-    const bool mos = tp.plan.on();
-    t->n = tp.NI; t->H = tp.SH; t->W = tp.SW; t->Hp = padded(tp.IH); t->Wp = padded(tp.IW);
-    t->mos_kx = mos ? tp.skx : 0; t->mos_ky = mos ? tp.sky : 0; t->mos_wh = mos ? th : 0; t->mos_ww = mos ? tw : 0;
-    t->mos_count = mos ? B : 0;
-    bool any = t->out_f32 || t->out_u8 || t->p0;
-    for (int k = 0; k < t->nlayers; ++k) any = any || t->act[k];
-    if (!any) return S2SR_OK;
-    CompactTap ct;
-    ct.t = t;
-    h->ctap = &ct;
-    rc = tap_forward(h, tiles, x, B, th, tw, tp, t->out_u8, t->out_f32);
-    h->ctap = nullptr;
-    if (rc) return rc;
-    if (t->p0 && (rc = decode_f16_planes(h, t->p0, h->ws.P0, h->ws.blk1, tp.NI, 1, h->ws.blk1))) return rc;
     return S2SR_OK;
 }
 

@@ -1,0 +1,642 @@
+// libs2sr engine, the whole-image (area of interest) path: the tile plan, RealESRGAN.enhance with its chunked window loop, the
+// device-side cut / stitch entries of the multi-GPU path, the staged device-to-host copies and the post-process drivers.
+#include <stdio.h>
+#include <string.h>
+
+#include <mutex>
+#include <vector>
+
+#include "engine_internal.h"
+
+using namespace s2sr;
+using namespace s2sr::engine;
+
+namespace s2sr::engine {
+
+static bool is_pinned_host(const void* p) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+        (void)hipGetLastError();   // an ordinary malloc'd pointer is "invalid value" to the runtime: not an error of ours
+        return false;
+    }
+    return a.type == hipMemoryTypeHost;
+}
+
+// Device -> caller's host buffer, `bytes` from `src`, ordered behind everything already on the copy stream; returns when the
+// bytes are in `dst`.  The caller's buffer is ordinary pageable memory (a numpy array): handed to hipMemcpyAsync directly, the
+// runtime moves it with copy KERNELS through its own staging at ~6 GB/s, and those kernels take CUs from the persistent conv
+// workgroups of the chunk computing meanwhile (4096 x 4096 AOI: +20 ms of compute under 130 ms of copies).  Here: two pinned
+// 32-MB slices filled by the DMA engines (pinned destination), emptied by this thread's memcpy while the next slice flies.
+// `exposed`: nothing computes under this copy (the last band, or the only one): below 128 MB the runtime's own path is then as
+// fast or faster (50 MB: 58.1 vs 60.3 ms per 1024 x 1024 call), and there are no conv workgroups for its copy kernels to displace.
+int d2h_staged(s2sr_handle* h, uint8_t* dst, const uint8_t* src, size_t bytes, bool exposed) {
+    if (is_pinned_host(dst)) {   // s2sr_host_alloc'd (or registered) destination: one DMA, nothing for this thread to copy
+        HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->copy_stream));
+        HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+        return S2SR_OK;
+    }
+    if (!h->d2h_staged_on || bytes < (exposed ? (128u << 20) : (24u << 20))) {
+        HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->copy_stream));
+        HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+        return S2SR_OK;
+    }
+    for (int i = 0; i < 2; ++i) {
+        if (!h->stage_buf[i]) HIPCHK(h, host_malloc(&h->stage_buf[i], kStageBytes, hipHostMallocDefault));
+        if (!h->stage_ev[i]) HIPCHK(h, hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming));
+    }
+    const size_t nsl = (bytes + kStageBytes - 1) / kStageBytes;
+    auto len = [&](size_t k) { return k + 1 < nsl ? kStageBytes : bytes - k * kStageBytes; };
+    for (size_t k = 0; k < nsl + 2; ++k) {
+        const int i = (int)(k & 1);
+        if (k >= 2) {   // slice k-2 sits in buffer i
+            HIPCHK(h, hipEventSynchronize(h->stage_ev[i]));
+            memcpy(dst + (k - 2) * kStageBytes, h->stage_buf[i], len(k - 2));
+        }
+        if (k < nsl) {
+            HIPCHK(h, hipMemcpyAsync(h->stage_buf[i], src + k * kStageBytes, len(k), hipMemcpyDeviceToHost, h->copy_stream));
+            HIPCHK(h, hipEventRecord(h->stage_ev[i], h->copy_stream));
+        }
+    }
+    return S2SR_OK;
+}
+
+// Chunk sizes of a tiled enhance(), front to back, in row units (pure host arithmetic; s2sr_debug_plan_chunks exposes it to the
+// CPU tests).  `unit_windows` windows per row unit, `per` windows per launch image (a mosaic; 1 without), `pimg` 32 x 32 patches per
+// launch image, `ncu` persistent workgroups.  The tail (last, middle) is searched for the fewest trunk-conv rounds plus the
+// exposed copy of the last band; what is left goes in front in pieces of at most u_max units.
+void plan_chunk_sizes(int units, int u_max, long unit_windows, int per, long pimg, int ncu, std::vector<int>& sizes) {
+    sizes.clear();
+    if (units <= 0) return;
+    if (u_max < 1) u_max = 1;
+    if (per < 1) per = 1;
+    if (ncu < 1) ncu = 1;
+    auto rounds = [&](int u) -> double {                                        // trunk-conv rounds of a chunk of u units
+        const long imgs = ((long)u * unit_windows + per - 1) / per;
+        return (double)((imgs * pimg + ncu - 1) / ncu);
+    };
+    const double copy_per_unit = (double)unit_windows * pimg / per / ncu / 6.0;  // exposed copy of one unit, in rounds
+    int best_last = 1, best_mid = 0;
+    double best = 1e300;
+    for (int last = 1; last <= 3 && last <= units; ++last)
+        for (int mid = 0; mid <= 12 && last + mid <= units; ++mid) {
+            if (mid > u_max || last > u_max || mid > 5 * last) continue;         // a band's copy must fit under the next chunk's compute (~6x)
+            const int front = units - last - mid;
+            if (front > 0 && mid == 0 && front > 5 * last) continue;            // a big chunk straight in front of the last one
+            if (front > 0 && mid > 0 && front > 6 * mid && front <= u_max) continue;
+            double c = rounds(last) + (mid ? rounds(mid) : 0.0) + last * copy_per_unit;
+            for (int left = front; left > 0;) { const int u = left < u_max ? left : u_max; c += rounds(u); left -= u; }
+            if (c < best - 1e-9) { best = c; best_last = last; best_mid = mid; }
+        }
+    for (int left = units - best_last - best_mid; left > 0;) { const int u = left < u_max ? left : u_max; sizes.push_back(u); left -= u; }
+    if (best_mid) sizes.push_back(best_mid);
+    sizes.push_back(best_last);
+}
+
+}  // namespace s2sr::engine
+
+extern "C" {
+
+int s2sr_plan_tiles(int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t scale, s2sr_window* out, int32_t cap,
+                    int32_t* n) {
+    if (H <= 0 || W <= 0 || tile <= 0 || pad < 0 || scale <= 0 || !n) return S2SR_E_INVALID;
+    const int nx = (W + tile - 1) / tile, ny = (H + tile - 1) / tile;
+    *n = nx * ny;
+    if (!out) return S2SR_OK;
+    if (cap < nx * ny) return S2SR_E_CAPACITY;
+    const int win = tile + 2 * pad, op = pad * scale;
+    for (int y = 0; y < ny; ++y)
+        for (int x = 0; x < nx; ++x) {
+            s2sr_window& w = out[y * nx + x];
+            // far edge first, then pull the near edge in so the window keeps its full extent
+            w.x2 = (x * tile + win < W) ? x * tile + win : W;
+            w.y2 = (y * tile + win < H) ? y * tile + win : H;
+            w.x1 = (w.x2 - win > 0) ? w.x2 - win : 0;
+            w.y1 = (w.y2 - win > 0) ? w.y2 - win : 0;
+            // the halo is dropped on every side that has a neighbouring tile INDEX
+            w.crop_left = x > 0 ? op : 0;
+            w.crop_top = y > 0 ? op : 0;
+            w.crop_right = x < nx - 1 ? op : 0;
+            w.crop_bottom = y < ny - 1 ? op : 0;
+            w.ox1 = w.x1 * scale + w.crop_left;
+            w.oy1 = w.y1 * scale + w.crop_top;
+            w.ox2 = w.x2 * scale - w.crop_right;
+            w.oy2 = w.y2 * scale - w.crop_bottom;
+        }
+    return S2SR_OK;
+}
+
+// host-side maps of the paste rule; shared by enhance and the multi-GPU stitch
+static void build_stitch_maps(const std::vector<s2sr_window>& wins, int nx, int ny, int OH, int OW,
+                              std::vector<int32_t>& rm, std::vector<int32_t>& cm) {
+    rm.assign(2 * (size_t)OH, -1);
+    cm.assign(2 * (size_t)OW, -1);
+    // last window in loop order wins (:278): ascending index, later entries overwrite the map
+    for (int y = 0; y < ny; ++y) {
+        const s2sr_window& w = wins[(size_t)y * nx];
+        for (int oy = w.oy1; oy < w.oy2; ++oy) { rm[2 * oy] = y; rm[2 * oy + 1] = oy - w.oy1 + w.crop_top; }
+    }
+    for (int x = 0; x < nx; ++x) {
+        const s2sr_window& w = wins[x];
+        for (int ox = w.ox1; ox < w.ox2; ++ox) { cm[2 * ox] = x; cm[2 * ox + 1] = ox - w.ox1 + w.crop_left; }
+    }
+}
+
+// post-process on device buffers; the caller holds h->mu
+static int postprocess_dev_locked(s2sr_handle* h, const void* d_rgb, int32_t B, int32_t H, int32_t W, const s2sr_pp_params* prm,
+                                  void* d_out, hipStream_t st) {
+    const size_t wb = postprocess_work_bytes(B, H, W, *prm);
+    int rc = ensure_scratch(h, 5, wb);
+    if (rc) return rc;
+    Scope sc(h, st, F_POST, 0.0, (double)B * H * W * 9.0);
+    HIPCHK(h, launch_postprocess((const uint8_t*)d_rgb, B, H, W, *prm, (uint8_t*)d_out, h->d_scratch[5], wb, st));
+    return S2SR_OK;
+}
+
+int s2sr_postprocess_batch_u8_dev(s2sr_handle* h, const void* d_rgb, int32_t B, int32_t H, int32_t W,
+                                  const s2sr_pp_params* prm, void* d_out, void* stream) {
+    if (!h || !d_rgb || !d_out || !prm || B <= 0 || H <= 0 || W <= 0) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return postprocess_dev_locked(h, d_rgb, B, H, W, prm, d_out, (hipStream_t)stream);   // NULL = the default stream, as everywhere in HIP
+}
+
+// ---- the post-process over one device image in row bands (see postprocess.hip launch_pp_band_*) -------------------------------
+// order: S2SR_PP_ORDER_BGR = the image's bytes are B,G,R; S2SR_PP_ORDER_SWAP_OUT = R and B exchanged in the rows written
+static int pp_band_begin_locked(s2sr_handle* h, int H, int W, const s2sr_pp_params* prm, int order, hipStream_t st) {
+    if (prm->clahe_grid <= 0 || prm->clahe_grid > 64) return fail(h, S2SR_E_INVALID, "clahe_grid must be 1..64");
+    int rc = ensure_scratch(h, 5, postprocess_work_bytes(1, H, W, *prm));
+    if (rc) return rc;
+    s2sr_handle::PPBand& b = h->ppb;
+    b = s2sr_handle::PPBand();
+    b.H = H; b.W = W; b.prm = *prm;
+    b.bgr = (order & S2SR_PP_ORDER_BGR) ? 1 : 0;
+    b.swap_out = (order & S2SR_PP_ORDER_SWAP_OUT) ? 1 : 0;
+    b.radius = pp_band_radius(*prm);
+    HIPCHK(h, launch_pp_band_begin(H, W, *prm, h->d_scratch[5], st));
+    b.open = true;
+    return S2SR_OK;
+}
+
+static int pp_band_hist_locked(s2sr_handle* h, const void* d_img, int y0, int y1, hipStream_t st) {
+    s2sr_handle::PPBand& b = h->ppb;
+    if (!b.open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_hist: no banded post-process open, or its LUTs are already built");
+    if (y0 < 0 || y1 > b.H || y0 > y1) return fail(h, S2SR_E_INVALID, "pp_band_hist: rows outside the image");
+    Scope sc(h, st, F_POST, 0.0, (double)(y1 - y0) * b.W * 3.0);
+    HIPCHK(h, launch_pp_band_hist((const uint8_t*)d_img, b.H, b.W, b.prm, b.bgr, y0, y1, h->d_scratch[5], st));
+    return S2SR_OK;
+}
+
+static int pp_band_lut_locked(s2sr_handle* h, hipStream_t st) {
+    s2sr_handle::PPBand& b = h->ppb;
+    if (!b.open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_lut: no banded post-process open, or its LUTs are already built");
+    HIPCHK(h, launch_pp_band_lut(b.H, b.W, b.prm, h->d_scratch[5], st));
+    b.lut = true;
+    return S2SR_OK;
+}
+
+static int pp_band_rows_locked(s2sr_handle* h, const void* d_img, int y0, int y1, void* d_out, hipStream_t st) {
+    s2sr_handle::PPBand& b = h->ppb;
+    if (!b.open || !b.lut) return fail(h, S2SR_E_INVALID, "pp_band_rows: the LUTs are not built (begin, hist over every row, lut, then rows)");
+    if (y0 != b.rows_end || y1 <= y0 || y1 > b.H) return fail(h, S2SR_E_INVALID, "pp_band_rows: bands must follow each other from row 0");
+    const int need = y1 + b.radius < b.H ? y1 + b.radius : b.H;     // the blur of row y1-1 reads R rows below it
+    Scope sc(h, st, F_POST, 0.0, (double)(y1 - y0) * b.W * 6.0);
+    if (need > b.applied_end) {
+        HIPCHK(h, launch_pp_band_apply((const uint8_t*)d_img, b.H, b.W, b.prm, b.bgr, b.applied_end, need, h->d_scratch[5], st));
+        b.applied_end = need;
+    }
+    HIPCHK(h, launch_pp_band_sharpen(b.H, b.W, b.prm, b.bgr, b.swap_out, y0, y1, h->d_scratch[5], (uint8_t*)d_out, st));
+    b.rows_end = y1;
+    if (y1 == b.H) b.open = false;
+    return S2SR_OK;
+}
+
+int s2sr_pp_band_begin_dev(s2sr_handle* h, int32_t H, int32_t W, const s2sr_pp_params* prm, int32_t order, void* stream) {
+    if (!h || !prm || H <= 0 || W <= 0) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pp_band_begin_locked(h, H, W, prm, order, (hipStream_t)stream);
+}
+
+int s2sr_pp_band_hist_dev(s2sr_handle* h, const void* d_img, int32_t y0, int32_t y1, void* stream) {
+    if (!h || !d_img) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pp_band_hist_locked(h, d_img, y0, y1, (hipStream_t)stream);
+}
+
+int s2sr_pp_band_lut_dev(s2sr_handle* h, void* stream) {
+    if (!h) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pp_band_lut_locked(h, (hipStream_t)stream);
+}
+
+int s2sr_pp_band_rows_dev(s2sr_handle* h, const void* d_img, int32_t y0, int32_t y1, void* d_out, void* stream) {
+    if (!h || !d_img || !d_out) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return pp_band_rows_locked(h, d_img, y0, y1, d_out, (hipStream_t)stream);
+}
+
+// Host image in, host image out.  ONE lock scope from the upload to the download: the staging buffers
+// (d_scratch[0], [1]) belong to the handle, and the app shares one post-process handle per device between
+// all jobs (app/wow_sr.py), which the reference runs from concurrent worker threads (main.py:247-368).
+int s2sr_postprocess_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, const s2sr_pp_params* prm, uint8_t* out) {
+    if (!h || !rgb || !out || !prm || H <= 0 || W <= 0) return S2SR_E_INVALID;
+    const size_t nb = (size_t)H * W * 3;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = ensure_scratch(h, 0, nb);
+    if (rc) return rc;
+    if ((rc = ensure_scratch(h, 1, nb))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], rgb, nb, hipMemcpyHostToDevice, h->stream));
+    if ((rc = postprocess_dev_locked(h, h->d_scratch[0], 1, H, W, prm, h->d_scratch[1], h->stream))) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[1], nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return S2SR_OK;
+}
+
+// The image a tile plan is made for.  Scale 2: H x W reflect-padded by one row / column at the bottom / right to even sizes
+// (RealESRGANer's mod-2 rule; the pad is read by index, see pack.hip), and an even tile, so that every window of the padded image
+// has even origin and extent.
+static int plan_dims(s2sr_handle* h, int H, int W, int tile, int* PH, int* PW) {
+    *PH = H; *PW = W;
+    if (h->unshuffle() == 1) return S2SR_OK;
+    if (H < 2 || W < 2) return fail(h, S2SR_E_INVALID, "scale 2 needs an image of at least 2 x 2 (the mod-2 reflect pad)");
+    if (tile % 2) return fail(h, S2SR_E_INVALID, "scale 2 needs an even tile: every window of the padded image must have even origin and size");
+    *PH = H + (H & 1); *PW = W + (W & 1);
+    return S2SR_OK;
+}
+
+// RealESRGAN.enhance (cnn_super_resolution.py:217-234) incl. _tile_process (:236-280)
+// job_rgb: the caller's image is RGB and wants RGB back -- R and B are swapped on the device in front of and behind the net (the
+// reference's cvtColor pair, wow_sr.py:85,103).  prm: the crop-visibility post-process (wow_sr.py:187-209) on the stitched RGB
+// image, on the device, before the one copy out (it is image-global: no band leaves before the whole mosaic is done).
+static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int tile, int pad, uint8_t* out_u8,
+                        float* out_f32, bool force_tiled = false, bool job_rgb = false, const s2sr_pp_params* prm = nullptr) {
+    if (!h || !img || (!out_u8 && !out_f32) || H <= 0 || W <= 0 || tile <= 0 || pad < 0) return S2SR_E_INVALID;
+    if ((job_rgb || prm) && !out_u8) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    int rc, PH, PW;
+    if ((rc = plan_dims(h, H, W, tile, &PH, &PW))) return rc;
+    // scale 2, odd H or W: everything below runs on the padded PH x PW image; the output is cropped to OH x OW by the stitch maps
+    const bool reflect = PH != H || PW != W;
+    const int scale = h->cfg.scale, u = h->unshuffle(), OH = H * scale, OW = W * scale, OHp = PH * scale, OWp = PW * scale;
+    const size_t ib = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
+    if ((rc = ensure_scratch(h, 0, ib))) return rc;
+    if ((rc = ensure_scratch(h, 1, opx * (out_f32 ? 4 : 1)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, ib, hipMemcpyHostToDevice, st));
+    if (job_rgb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[0], (size_t)H * W, (uint8_t*)h->d_scratch[0], st));
+    const bool whole_finish = job_rgb || prm != nullptr;      // the image leaves in one piece, behind the device-side finish
+    const bool tiled = force_tiled || (long long)PH * PW > (long long)tile * tile * 4;   // strict '>' (:226)
+    if (!tiled) {
+        if (out_f32 || reflect) {
+            // net output is NCHW (f32; enhance() returns HWC) or the padded image's (u8, odd scale-2 image) -> stitch with an
+            // identity map, cropped to OH x OW
+            const size_t opxp = (size_t)OHp * OWp * 3;
+            if ((rc = ensure_scratch(h, 2, opxp * (out_f32 ? 4 : 1)))) return rc;
+            rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[0], nullptr, 1, PH, PW, out_f32 ? nullptr : (uint8_t*)h->d_scratch[2],
+                             out_f32 ? (float*)h->d_scratch[2] : nullptr, nullptr, H, W);
+            if (rc) return rc;
+            std::vector<int32_t> rm(2 * OH), cm(2 * OW);
+            for (int i = 0; i < OH; ++i) { rm[2 * i] = 0; rm[2 * i + 1] = i; }
+            for (int i = 0; i < OW; ++i) { cm[2 * i] = 0; cm[2 * i + 1] = i; }
+            if ((rc = ensure_scratch(h, 3, (rm.size() + cm.size()) * 4))) return rc;
+            int32_t* d_rm = (int32_t*)h->d_scratch[3];
+            int32_t* d_cm = d_rm + rm.size();
+            HIPCHK(h, hipMemcpyAsync(d_rm, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(h, hipMemcpyAsync(d_cm, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(h, hipStreamSynchronize(st));   // rm/cm are stack-owned host buffers
+            if (out_f32) HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
+            else HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
+        } else {
+            rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[0], nullptr, 1, H, W, (uint8_t*)h->d_scratch[1], nullptr);
+            if (rc) return rc;
+        }
+    } else {
+        int T = 0;
+        s2sr_plan_tiles(PH, PW, tile, pad, scale, nullptr, 0, &T);
+        std::vector<s2sr_window> wins(T);
+        s2sr_plan_tiles(PH, PW, tile, pad, scale, wins.data(), T, &T);
+        const int pnx = (PW + tile - 1) / tile, pny = (PH + tile - 1) / tile;    // the reference's plan
+        const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;   // all windows share one shape
+        std::vector<int32_t> rm, cm;
+        build_stitch_maps(wins, pnx, pny, OHp, OWp, rm, cm);                    // (the stitches read the first OH x OW of them)
+        // When a dimension ends within 2*pad of a tile multiple, the last two window rows (columns)
+        // of the plan are the same rectangle: the reference runs the net on both (only the paste
+        // ranges differ).  Identical inputs give identical outputs, so each distinct rectangle is
+        // forwarded once and the paste maps point at it.
+        std::vector<int> uy(pny), ux(pnx), rows_y1, cols_x1;
+        for (int y = 0; y < pny; ++y) {
+            const int y1 = wins[(size_t)y * pnx].y1;
+            if (rows_y1.empty() || rows_y1.back() != y1) rows_y1.push_back(y1);
+            uy[y] = (int)rows_y1.size() - 1;
+        }
+        for (int x = 0; x < pnx; ++x) {
+            const int x1 = wins[x].x1;
+            if (cols_x1.empty() || cols_x1.back() != x1) cols_x1.push_back(x1);
+            ux[x] = (int)cols_x1.size() - 1;
+        }
+        for (size_t i = 0; i < rm.size(); i += 2)
+            if (rm[i] >= 0) rm[i] = uy[rm[i]];
+        for (size_t i = 0; i < cm.size(); i += 2)
+            if (cm[i] >= 0) cm[i] = ux[cm[i]];
+        const int nx = (int)cols_x1.size(), ny = (int)rows_y1.size();
+        T = nx * ny;
+        std::vector<int32_t> rects(4 * (size_t)T);
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) {
+                const int t = y * nx + x;
+                rects[4 * t] = rows_y1[y]; rects[4 * t + 1] = rows_y1[y] + wh; rects[4 * t + 2] = cols_x1[x]; rects[4 * t + 3] = cols_x1[x] + ww;
+            }
+        const size_t tin = (size_t)T * wh * ww * 3, tout = tin * scale * scale;
+        if ((rc = ensure_scratch(h, 2, tin))) return rc;
+        if ((rc = ensure_scratch(h, 4, tout * (out_f32 ? 4 : 1)))) return rc;
+        if ((rc = ensure_scratch(h, 3, (rects.size() + rm.size() + cm.size()) * 4))) return rc;
+        int32_t* d_rects = (int32_t*)h->d_scratch[3];
+        int32_t* d_rm = d_rects + rects.size();
+        int32_t* d_cm = d_rm + rm.size();
+        HIPCHK(h, hipMemcpyAsync(d_rects, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(d_rm, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(d_cm, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipStreamSynchronize(st));
+        if (reflect) HIPCHK(h, launch_gather_windows_reflect((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
+        else HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
+        // Chunks of whole window rows.  An output row is final once the last window row that pastes into it is done (the row
+        // map is monotone), so each chunk is followed by the stitch of its band of final rows, and the band's device-to-host
+        // copy runs on the copy stream under the next chunk's compute.  A chunk holds whole launch groups: for windows that
+        // travel as mosaics (forward_dev) rows in multiples of what fills a mosaic, and as many mosaics as the workspace
+        // allows -- the patch count of a launch must be large against the 256 workgroups (one 4 x 4 mosaic of 276-pixel
+        // windows is 1225 patches = 4.8 per CU, five rounds for 4.8 rounds of work; five mosaics are 23.9 -> 24).
+        // Chunk sizes.  The device-to-host copy of a chunk's band hides under the NEXT chunk's compute and only the last band's
+        // copy is exposed, so chunks shrink towards the end (a row of 276-pixel windows computes ~6x longer than its 13 MB band
+        // takes to reach pageable host memory; a chunk may be up to 5x its successor).  What a small chunk costs is the rounding
+        // of its patch count to whole rounds of the persistent workgroups in the trunk convs (32 x 32 patches; a 4 x 4 mosaic
+        // of 276-pixel windows = 1225 patches = 4.8 rounds of 256: 1, 2, 3, 4 mosaics lose 4.3 %, 5 or 10 lose 0.3 %).  The
+        // tail (last, middle) is searched over small sizes for the fewest rounds + exposed copy; the rest goes in front in
+        // workspace-sized pieces.  4096 x 4096 at 256/10: 16 rows of 16 windows -> 10 + 5 + 1.
+        std::vector<int> chunk_r0;   // first window row of each chunk, plus ny at the end
+        const Mosaic mo = pick_mosaic(h, T, wh, ww);   // ONE plan for the job: every chunk runs in its workspace geometry
+        {
+            const int per = mo.on() ? mo.kx * mo.ky : 1;
+            const int gw = (mo.on() ? group_size(h, (T + per - 1) / per, mo.ky * (mo.wh + 1) - 1, mo.kx * (mo.ww + 1) - 1)
+                                    : group_size(h, T, wh / u, ww / u)) * per;          // windows per launch group
+            const int r_min = (per + nx - 1) / nx;                                      // rows that fill a mosaic
+            const int units = (ny + r_min - 1) / r_min;                                 // ... and how many such row units the image has
+            int u_max = gw / nx / r_min;                                                // units per chunk the workspace allows
+            if (u_max < 1) u_max = 1;
+            int ncu = 256;
+            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
+            const long pimg = mo.on() ? (long)((mo.ky * (mo.wh + 1) - 1 + 31) / 32) * ((mo.kx * (mo.ww + 1) - 1 + 31) / 32)
+                                      : (long)((wh / u + 31) / 32) * ((ww / u + 31) / 32);   // 32 x 32 patches per launch image
+            std::vector<int> sizes;                                                     // in units, front to back
+            plan_chunk_sizes(units, u_max, r_min * nx, per, pimg, ncu, sizes);
+            int r = 0;
+            for (int u : sizes) { chunk_r0.push_back(r); r += u * r_min; }
+            chunk_r0.push_back(ny);
+        }
+        const int nchunks = (int)chunk_r0.size() - 1;
+        if (!out_f32 && nchunks > 1) {
+            // A job (job_rgb / prm) takes the same route: the channel swap behind the net is applied to every band as it is stitched;
+            // the post-process -- image-global through CLAHE's grid (wow_sr.py:191-192) -- counts every band into the histograms as
+            // it is stitched (under the compute of the chunks still to come), builds the LUTs behind the last band and then
+            // finishes the image in row bands, each followed by its copy out: what is exposed behind the last window is one band's
+            // kernels plus the PCIe time of the image (the r04 form waited for the whole mosaic, swapped, post-processed and only
+            // then started the one copy).
+            const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;
+            const size_t row_b = (size_t)OW * 3;
+            int fin_rows = 0, nfin = 0;          // finishing bands of the post-process: ~48 MB each, whole 32-row tile rows
+            if (prm) {
+                fin_rows = (int)(((size_t)48 << 20) / row_b) & ~31;
+                if (fin_rows < 64) fin_rows = 64;
+                nfin = (OH + fin_rows - 1) / fin_rows;
+                if ((rc = pp_band_begin_locked(h, OH, OW, prm, job_rgb ? 3 : 0, st))) return rc;   // (allocates: before anything is enqueued)
+            }
+            while ((int)h->group_done.size() < nchunks + nfin) {
+                hipEvent_t e;
+                HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+                h->group_done.push_back(e);
+            }
+            uint8_t* d_img_out = (uint8_t*)h->d_scratch[1];
+            int yb = 0, prev_yb = 0, prev_ye = 0;
+            for (int c = 0; c < nchunks; ++c) {
+                const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1] < ny ? chunk_r0[c + 1] : ny;
+                const int t0 = r0 * nx, n = (r1 - r0) * nx;
+                rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[2] + t0 * win_in, nullptr, n, wh, ww,
+                                 (uint8_t*)h->d_scratch[4] + t0 * win_out, nullptr, mo.on() ? &mo : nullptr);
+                if (rc) return rc;
+                int ye = OH;
+                if (r1 < ny)
+                    for (ye = yb; ye < OH && rm[2 * ye] < r1; ++ye) {}
+                if (ye > yb) {
+                    HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW,
+                                               d_img_out + (size_t)yb * row_b, st));
+                    if (prm) {
+                        if ((rc = pp_band_hist_locked(h, d_img_out, yb, ye, st))) return rc;
+                    } else if (job_rgb) {
+                        HIPCHK(h, launch_swap_rb_u8(d_img_out + (size_t)yb * row_b, (size_t)(ye - yb) * OW, d_img_out + (size_t)yb * row_b, st));
+                    }
+                }
+                HIPCHK(h, hipEventRecord(h->group_done[c], st));
+                if (!prm && c > 0 && prev_ye > prev_yb) {
+                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[c - 1], 0));
+                    if ((rc = d2h_staged(h, out_u8 + (size_t)prev_yb * row_b, d_img_out + (size_t)prev_yb * row_b,
+                                         (size_t)(prev_ye - prev_yb) * row_b, false))) return rc;
+                }
+                prev_yb = yb; prev_ye = ye; yb = ye;
+            }
+            if (!prm) {
+                if (prev_ye > prev_yb) {
+                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
+                    if ((rc = d2h_staged(h, out_u8 + (size_t)prev_yb * row_b, d_img_out + (size_t)prev_yb * row_b,
+                                         (size_t)(prev_ye - prev_yb) * row_b, true))) return rc;
+                }
+            } else {
+                // LUTs, then every finishing band's kernels (in place: a band's rows are rewritten only after the apply pass, which
+                // runs R rows ahead, has read them), an event behind each; the copies follow band by band on the copy stream
+                const bool timing = getenv("S2SR_JOB_TIMING") != nullptr;     // diagnostic: stage times of the finish on stderr
+                auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+                double t_enq = now(), t_compute = 0, t_first = 0;
+                if ((rc = pp_band_lut_locked(h, st))) return rc;
+                for (int b = 0; b < nfin; ++b) {
+                    const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
+                    if ((rc = pp_band_rows_locked(h, d_img_out, y0, y1, d_img_out, st))) return rc;
+                    HIPCHK(h, hipEventRecord(h->group_done[nchunks + b], st));
+                }
+                if (timing) {
+                    HIPCHK(h, hipEventSynchronize(h->group_done[nchunks - 1]));
+                    t_compute = now();
+                }
+                for (int b = 0; b < nfin; ++b) {
+                    const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
+                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks + b], 0));
+                    if ((rc = d2h_staged(h, out_u8 + (size_t)y0 * row_b, d_img_out + (size_t)y0 * row_b, (size_t)(y1 - y0) * row_b,
+                                         false))) return rc;
+                    if (timing && b == 0) t_first = now();
+                }
+                if (timing)
+                    fprintf(stderr, "[s2sr job] finish: %d bands of %d rows; last chunk done %.2f ms after the finish was queued, first band on the host "
+                            "+%.2f ms, all bands +%.2f ms\n", nfin, fin_rows, t_compute - t_enq, t_first - t_compute, now() - t_compute);
+            }
+            HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+            HIPCHK(h, hipStreamSynchronize(st));
+            return S2SR_OK;
+        }
+        rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[2], nullptr, T, wh, ww, out_f32 ? nullptr : (uint8_t*)h->d_scratch[4],
+                         out_f32 ? (float*)h->d_scratch[4] : nullptr);
+        if (rc) return rc;
+        if (out_f32) HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
+        else HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
+    }
+    const uint8_t* d_final = (const uint8_t*)h->d_scratch[1];
+    if (whole_finish) {
+        if (job_rgb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[1], (size_t)OH * OW, (uint8_t*)h->d_scratch[1], st));
+        if (prm) {
+            // the windows' output buffer is free again once the stitch has read it; whole-image jobs get a buffer of their own
+            if ((rc = ensure_scratch(h, 4, opx))) return rc;
+            if ((rc = postprocess_dev_locked(h, h->d_scratch[1], 1, OH, OW, prm, h->d_scratch[4], st))) return rc;
+            d_final = (const uint8_t*)h->d_scratch[4];
+        }
+    }
+    if (h->group_done.empty()) {
+        hipEvent_t e;
+        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        h->group_done.push_back(e);
+    }
+    HIPCHK(h, hipEventRecord(h->group_done[0], st));
+    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[0], 0));
+    if ((rc = d2h_staged(h, out_f32 ? (uint8_t*)out_f32 : out_u8, out_f32 ? (const uint8_t*)h->d_scratch[1] : d_final, opx * (out_f32 ? 4 : 1), true))) return rc;
+    HIPCHK(h, hipStreamSynchronize(st));
+    return S2SR_OK;
+}
+
+int s2sr_enhance_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, uint8_t* out) {
+    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, img, H, W, tile, pad, out, nullptr));
+}
+
+// A whole /api/wow job's device work in one call (apply_wow_sr, wow_sr.py:85-110): RGB image in, RGB2BGR, RealESRGAN.enhance,
+// BGR2RGB, _enhance_for_crops (prm != NULL), RGB image out -- one upload, one download, nothing in between on the host.
+int s2sr_enhance_job_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
+                        uint8_t* out_rgb) {
+    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, rgb, H, W, tile, pad, out_rgb, nullptr, false, true, prm));
+}
+
+int s2sr_enhance_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out) {
+    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, img, H, W, tile, pad, nullptr, out));
+}
+
+int s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_t W, int32_t tile, int32_t pad,
+                            int32_t first, int32_t count, void* d_tiles, void* stream) {
+    if (!h || !d_img || !d_tiles || H <= 0 || W <= 0 || tile <= 0 || pad < 0 || first < 0 || count <= 0) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
+    int T = 0, PH, PW;
+    int rc = plan_dims(h, H, W, tile, &PH, &PW);
+    if (rc) return rc;
+    s2sr_plan_tiles(PH, PW, tile, pad, h->cfg.scale, nullptr, 0, &T);
+    if (first + count > T) return fail(h, S2SR_E_INVALID, "window range exceeds the plan");
+    std::vector<s2sr_window> wins(T);
+    s2sr_plan_tiles(PH, PW, tile, pad, h->cfg.scale, wins.data(), T, &T);
+    const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;
+    std::vector<int32_t> rects(4 * (size_t)count);
+    for (int t = 0; t < count; ++t) {
+        const s2sr_window& w = wins[first + t];
+        rects[4 * t] = w.y1; rects[4 * t + 1] = w.y2; rects[4 * t + 2] = w.x1; rects[4 * t + 3] = w.x2;
+    }
+    rc = ensure_scratch(h, 3, rects.size() * 4);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[3], rects.data(), rects.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (PH != H || PW != W)
+        HIPCHK(h, launch_gather_windows_reflect((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, (uint8_t*)d_tiles, st));
+    else HIPCHK(h, launch_gather_windows((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, (uint8_t*)d_tiles, st));
+    return S2SR_OK;
+}
+
+int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t oy0, int32_t oy1,
+                            void* d_out, void* stream) {
+    if (!h || !d_tiles || !d_out || H <= 0 || W <= 0 || tile <= 0 || pad < 0 || oy0 < 0 || oy1 > h->cfg.scale * H || oy0 > oy1) return S2SR_E_INVALID;
+    if (oy0 == oy1) return S2SR_OK;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
+    const int S = h->cfg.scale;
+    int T = 0, PH, PW;
+    int rc = plan_dims(h, H, W, tile, &PH, &PW);
+    if (rc) return rc;
+    s2sr_plan_tiles(PH, PW, tile, pad, S, nullptr, 0, &T);
+    std::vector<s2sr_window> wins(T);
+    s2sr_plan_tiles(PH, PW, tile, pad, S, wins.data(), T, &T);
+    const int nx = (PW + tile - 1) / tile, ny = (PH + tile - 1) / tile;
+    const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;
+    const size_t nrm = 2 * (size_t)(S * PH), ncm = 2 * (size_t)(S * PW);   // maps of the padded image; the stitch reads S H x S W
+    // the plan's paste maps: from the handle's LRU of map sets, or built and uploaded now.  A NEW set costs an allocation and a
+    // blocking upload on the handle's own stream -- nothing the caller has queued on ITS stream is waited for (r04: any key change
+    // synchronised the device under the process-wide gate, so the first band's stitch drained every compute chunk already queued
+    // and stalled the captures of other handles).  Only when all four sets are taken is the least recently used one recycled, and
+    // only then is the device synchronised: a stitch that still reads it may be in flight on a stream this library does not know.
+    const int key[4] = {H, W, tile, pad + 1};
+    s2sr_handle::StitchMaps* ms = nullptr;
+    for (auto& m : h->stitch_sets)
+        if (m.d && m.key[0] == key[0] && m.key[1] == key[1] && m.key[2] == key[2] && m.key[3] == key[3]) ms = &m;
+    if (!ms) {
+        for (auto& m : h->stitch_sets)
+            if (!m.d) { ms = &m; break; }
+        if (!ms) {
+            ms = &h->stitch_sets[0];
+            for (auto& m : h->stitch_sets)
+                if (m.last_use < ms->last_use) ms = &m;
+            HIPCHK(h, dev_sync());
+            if (ms->cap < (nrm + ncm) * 4) {
+                HIPCHK(h, dev_free(ms->d));
+                ms->d = nullptr; ms->cap = 0;
+            }
+        }
+        ms->key[0] = 0;                       // (invalid until the upload is through)
+        if (!ms->d) {
+            HIPCHK(h, dev_malloc(&ms->d, (nrm + ncm) * 4));
+            ms->cap = (nrm + ncm) * 4;
+        }
+        std::vector<int32_t> rm, cm;
+        build_stitch_maps(wins, nx, ny, S * PH, S * PW, rm, cm);
+        HIPCHK(h, copy_blocking(h, ms->d, rm.data(), nrm * 4, hipMemcpyHostToDevice));
+        HIPCHK(h, copy_blocking(h, ms->d + nrm, cm.data(), ncm * 4, hipMemcpyHostToDevice));
+        for (int i = 0; i < 4; ++i) ms->key[i] = key[i];
+    }
+    ms->last_use = ++h->stitch_clock;
+    const int32_t* d_rm = ms->d;
+    const int32_t* d_cm = d_rm + nrm;
+    HIPCHK(h, launch_stitch_u8((const uint8_t*)d_tiles, nx, wh * S, ww * S, d_rm + 2 * (size_t)oy0, d_cm, oy1 - oy0, S * W,
+                               (uint8_t*)d_out + (size_t)oy0 * S * W * 3, st));
+    return S2SR_OK;
+}
+
+int s2sr_stitch_windows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int32_t W, int32_t tile, int32_t pad,
+                               void* d_out, void* stream) {
+    if (!h) return S2SR_E_INVALID;
+    return s2sr_stitch_rows_u8_dev(h, d_tiles, H, W, tile, pad, 0, h->cfg.scale * H, d_out, stream);
+}
+
+// Device -> host for callers that hold device buffers (s2sr/dist.py's consuming rank): `bytes` from d_src into dst once
+// everything enqueued on `stream` so far is done; returns when the bytes are in dst.  A destination from s2sr_host_alloc is
+// filled by one DMA, a pageable one through the pinned staging slices (d2h_staged) -- never the runtime's copy kernels, which
+// take CUs from the conv workgroups of whatever computes meanwhile.
+int s2sr_copy_to_host(s2sr_handle* h, void* dst, const void* d_src, size_t bytes, void* stream) {
+    if (!h || !dst || !d_src) return S2SR_E_INVALID;
+    if (bytes == 0) return S2SR_OK;
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->host_copy_ev) HIPCHK(h, hipEventCreateWithFlags(&h->host_copy_ev, hipEventDisableTiming));
+    HIPCHK(h, hipEventRecord(h->host_copy_ev, (hipStream_t)stream));
+    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->host_copy_ev, 0));
+    return d2h_staged(h, (uint8_t*)dst, (const uint8_t*)d_src, bytes, false);
+}
+
+int s2sr_tile_process_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out) {
+    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, img, H, W, tile, pad, nullptr, out, true));
+}
+
+}  // extern "C"

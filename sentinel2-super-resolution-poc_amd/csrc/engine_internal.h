@@ -1,0 +1,271 @@
+// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_debug.hip): the handle behind
+// the C ABI of include/s2sr.h, the types it is made of, and the helpers that more than one of those files uses.  What a single
+// file uses stays static or anonymous in that file.
+#pragma once
+#include <stdio.h>
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "s2sr_internal.h"
+
+namespace s2sr::engine {
+
+struct ConvW {
+    int cin = 0, cout = 0, nstage = 0, ct = 0;
+    int seg_len = 0, seg_lo_mask = 0;   // split-operand convs (precision S2SR_PREC_F16_HP), see ConvParams
+    bool fold = false;                  // conv_last in hp mode: w_lo folded into idle couts (pack_conv_weights)
+    bool f8 = false;                    // hp mode, cin 64: fp16 main term + e4m3 correction planes (pack_conv_weights_f8hp)
+    void* d_wphase[2] = {nullptr, nullptr};   // hp up-convs: the 2x2 sub-pixel kernels per output row parity (pack_conv_weights_phase_f8hp)
+    void* d_wpack = nullptr;
+    float* d_bias = nullptr;
+    // fp8 trunk mode (S2SR_PREC_FP8), the 345 RDB convs: e4m3 weight planes (pack_conv_weights_f8; nstage = planes padded
+    // to even, seg_len = real planes) + per-output-channel E8M0 scale bytes
+    bool f8trunk = false;
+    int32_t* d_wscale = nullptr;
+    bool pooled = false;                // d_wpack / d_wscale point into the handle's pools
+    float* d_slope = nullptr;           // SRVGGNetCompact: the 64 PReLU slopes behind this conv (in pool_b, next to the bias)
+};
+
+// kernel families for the HIP-event statistics
+enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_COUNT };
+inline constexpr const char* kFamName[F_COUNT] = {"pack_u8",   "conv_first", "rdb_conv1-4", "rdb_conv5",   "conv_body",
+                                 "conv_up",   "conv_hr",    "conv_last",   "postprocess", "misc",
+                                 "compact_first", "compact_body", "compact_last"};
+
+struct Workspace {
+    int G = 0, H = 0, W = 0;   // capacity (images) and logical LR dims
+    char* base = nullptr;
+    size_t bytes = 0;
+    // LR tensors (blocked-16 fp16 / blocked-8 fp32, see s2sr_internal.h)
+    char *P0 = nullptr;                  // input, 1 block
+    char *D[3] = {nullptr, nullptr, nullptr};   // dense-block tensors, 12 blocks: [x(4) | x1 | x2 | x3 | x4]; three of them rotate
+                                         // through an RRDB (rdb k reads D[k], writes the next x into D[(k+1)%3]), so the
+                                         // RRDB's input D[0] is still there when rdb3's conv5 needs it as the skip
+    char *U0 = nullptr;                  // 4 blocks
+    char *T = nullptr;                   // trunk lo as fp16 (4 blocks): conv_first writes it, the trunk's lo planes are made from it (Tr[0])
+    char *Tr[3] = {nullptr, nullptr, nullptr};  // one-wave-per-SIMD path: trunk lo of D[0..2] as e4m3(lo * 2^lo_exp), 2 planes of 32 channels
+    float *R = nullptr, *F = nullptr;    // fp32 RRDB skip / global skip (8 blocks of 8)
+    // 2x and 4x tensors, 4 blocks each
+    char *U1 = nullptr, *U2 = nullptr, *U3 = nullptr;
+    // split-operand mode only: e4m3 correction planes of U0..U3 and of the trunk, 4 planes of 32 B per
+    // pixel each ([lo*2^11 p0, p1, hi p0, p1]) -- the size of a 4-block fp16 tensor
+    char *U0lo = nullptr, *U1lo = nullptr, *U2lo = nullptr, *U3lo = nullptr, *T8 = nullptr;
+    // fp8 trunk mode only: the dense-block tensors as e4m3 planes of 32 channels [x(2) | x1 | x2 | x3 | x4], the trunk x in
+    // fp16 (three rotating buffers: an RRDB's input stays readable until its last conv5 has used it as the skip), and
+    // an all-zero "trunk lo" for conv_body's split-operand path
+    char *D8[2] = {nullptr, nullptr};
+    char *Xh[3] = {nullptr, nullptr, nullptr};
+    char *Tz = nullptr;
+    bool hp = false, fp8 = false;
+    int mos_py = 0, mos_px = 0;          // separator periods of the window mosaic these planes were zeroed for (0: plain images)
+    int Hp = 0, Wp = 0, Hp2 = 0, Wp2 = 0, Hp4 = 0, Wp4 = 0;
+    size_t blk1 = 0, blk2 = 0, blk4 = 0;   // bytes of one block plane at 1x / 2x / 4x
+};
+
+struct EvRec {
+    int fam;
+    hipEvent_t e0, e1;
+    double flops, bytes;
+    int n = 1;           // launches between the two events (a span of consecutive launches of one family)
+};
+
+// Window mosaic geometry of one forward (see ConvParams::mos_*): kx x ky windows of wh x ww per image, `count` windows in all.
+struct Mosaic {
+    int kx = 1, ky = 1, wh = 0, ww = 0, count = 0;
+    bool on() const { return wh > 0; }
+};
+
+// One captured group (pack + the whole layer schedule) for fixed shapes and buffers.  A net is
+// 351 dependent launches; small groups are launch-bound (~15 us per launch against a few us of
+// work), so the second time the same (shape, buffers) group shows up it is captured into a
+// hipGraph and replayed from then on.  GraphKey: everything a replay must have in common with the captured group.
+struct GraphKey {
+    int n = 0, th = 0, tw = 0;
+    int sh = 0, sw = 0;              // input rows / columns as stored (forward_dev src_h / src_w)
+    int mos_kx = 0, mos_ky = 0, mos_count = 0;
+    const void *in_u8 = nullptr, *in_f32 = nullptr;
+    void *out_u8 = nullptr, *out_f32 = nullptr;
+    hipStream_t st = nullptr;
+    bool operator==(const GraphKey& o) const {
+        return n == o.n && th == o.th && tw == o.tw && sh == o.sh && sw == o.sw && mos_kx == o.mos_kx && mos_ky == o.mos_ky &&
+               mos_count == o.mos_count && in_u8 == o.in_u8 && in_f32 == o.in_f32 && out_u8 == o.out_u8 && out_f32 == o.out_f32 && st == o.st;
+    }
+};
+struct GraphEntry {
+    GraphKey key;
+    hipGraphExec_t exec = nullptr;   // null until captured
+    bool refused = false;            // capture failed once: stay on direct launches
+    uint64_t last_use = 0;
+};
+
+// s2sr_debug_trunk_taps while its batch runs: the RDB range whose fields run_net copies out (trunk_tap) and where the form
+// records of the range's conv launches go
+struct TrunkTap {
+    int first = 0, count = 0;
+    s2sr_debug_trunk_fields* t = nullptr;
+    s2sr_debug_trunk_form spare[5];     // the records of RDBs outside the range
+    s2sr_debug_trunk_form* forms(int g) { return t->form && g >= first && g < first + count ? t->form + 5 * (g - first) : spare; }
+};
+
+// s2sr_debug_compact_taps while its batch runs: run_net_compact copies the chosen layers' activations out
+struct CompactTap {
+    s2sr_debug_compact_fields* t = nullptr;
+};
+
+}  // namespace s2sr::engine
+
+struct s2sr_handle {
+    s2sr_config cfg{};
+    // RealESRGAN_x2plus (cfg.scale 2) runs pixel_unshuffle(x, 2) and then the x4 net on the half grid.  Every entry takes input
+    // sizes: the trunk (workspace, mosaic, launch groups, graphs) is input / unshuffle(), the output input * cfg.scale.
+    int unshuffle() const { return cfg.scale == 2 ? 2 : 1; }
+    bool compact() const { return cfg.arch == S2SR_ARCH_COMPACT; }   // SRVGGNetCompact: cfg.num_block carries num_conv
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+    std::string err;
+    std::vector<s2sr::engine::ConvW> convs;
+    // the packed weights of the 345 RDB convs, their fp8 scales and every conv's bias live in three pooled allocations
+    // (ConvW pointers point into them); only the six head/tail convs own separate buffers (pooled == false)
+    char* pool_w = nullptr;
+    int32_t* pool_s = nullptr;
+    float* pool_b = nullptr;
+    bool has_weights = false;
+    char* d_trash = nullptr;      // parking area for out-of-image epilogue stores
+    s2sr::engine::Workspace ws;
+    // scratch device buffers (grown on demand)
+    void* d_scratch[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_bytes[6] = {0, 0, 0, 0, 0, 0};
+    int capture_failures = 0;            // captures voided by a device-wide call of another runtime user; 3 -> graphs off
+    int tiles_slot = -1;                 // scratch slot that still holds the tile level the last pyramid call produced (-1: none)
+    int tiles_nx = 0, tiles_ny = 0;
+    int warp_slot = -1, warp_h = 0, warp_w = 0;   // ... and the RGBA raster the last warp produced (s2sr_tiles_base_u8 with rgba == NULL)
+    // profiling
+    int prof = 0;                 // 0 off, N>=1: bracket every N-th launch of each family with events
+    bool span_on = false;         // a sampled span of consecutive launches of ONE family is open (span_begin / span_end): its launches
+    s2sr::engine::EvRec span;     // add their work to it instead of recording events of their own.  Two marker packets between two
+    int64_t span_count = 0;       // kernels cost ~2 us of a 70-us launch (r03: 71.6 us by events against 69.0 by rocprofv3); one pair around
+                                  // the four conv1-4 launches of an RDB spreads that over four
+    int64_t fam_count[16] = {0};
+    std::vector<s2sr::engine::EvRec> evs;
+    std::vector<hipEvent_t> ev_pool;
+    s2sr_kstat stats[s2sr::engine::F_COUNT];
+    hipStream_t copy_stream = nullptr;          // device-to-host copies behind the compute stream
+    std::vector<hipEvent_t> group_done;
+    void* stage_buf[2] = {nullptr, nullptr};    // pinned staging slices of the device-to-host path (d2h_staged)
+    hipEvent_t stage_ev[2] = {nullptr, nullptr};
+    bool d2h_staged_on = true;                  // S2SR_D2H_STAGED=0: hipMemcpyAsync straight into the caller's (pageable) buffer
+    float* d_calib = nullptr;     // fp8 calibration: [0] max |x| of the trunk, [1] max |x_k| of the growth planes (device)
+    bool fp8_hp_tail = false;     // S2SR_PREC_FP8: the six head / tail convs in plain fp16 (their ~2e-3 is below the trunk's e4m3
+                                  // error) unless S2SR_FP8_TAIL=hp asks for the split-operand forms
+    int lo_exp = 12;              // fp16 modes, one-wave-per-SIMD trunk: the trunk's lo half as e4m3(lo * 2^lo_exp): exact to 4 bits for
+                                  // |x| < 2^(20 - lo_exp) = 256, clamped beyond (S2SR_LO_EXP)
+    int fp8_x_exp = 3, fp8_g_exp = 5;   // S2SR_PREC_FP8 activation scales 2^e of the x / growth planes (S2SR_FP8_XEXP, S2SR_FP8_GEXP); calibrated
+                                        // on the synthetic set: profiles/r02_fp8_scale_sweep.txt (|x| up to 56, |x_k| up to 14 before clipping)
+    int fp8_x_exp0 = 3, fp8_g_exp0 = 5; // ... as s2sr_create left them: every weight load starts from these again (a calibration belongs to the weights it saw)
+    bool graphs_on = true;        // S2SR_GRAPH=0 turns it off
+    int64_t ws_allocs = 0;        // workspace (re)allocations since s2sr_create (s2sr_debug_get_config reserved[5])
+    bool last_fold = true;        // S2SR_LAST_FOLD=0: conv_last (hp) reads all four e4m3 planes (8 stages) instead of folding w_lo into idle couts
+    bool f16_full = true;         // S2SR_F16_FULL=0: fp16 conv1-4 never take the whole-patch form (no px_live arithmetic in the epilogue) on 32-multiple launches
+    bool small8 = true;           // S2SR_SMALL8=0: single tiles keep the 16x32-patch form of fp16 conv1-4 (default: 8x32 patches, 256 per 256x256 tile)
+    bool mosaic_on = true;        // S2SR_MOSAIC=0: windows that are no multiple of the 32-pixel patch travel one per image (ConvParams::mos_*)
+    // paste maps of the window plan last stitched through s2sr_stitch_rows_u8_dev (row map, column map), kept on the device:
+    // an AOI is stitched band by band, the maps are uploaded once per (H, W, tile, pad)
+    // (a small LRU of map sets: a service that alternates AOI sizes neither re-uploads nor synchronises the device per job)
+    struct StitchMaps { int key[4] = {0, 0, 0, 0}; int32_t* d = nullptr; size_t cap = 0; uint64_t last_use = 0; };
+    StitchMaps stitch_sets[4];
+    uint64_t stitch_clock = 0;
+    hipEvent_t host_copy_ev = nullptr;          // s2sr_copy_to_host: orders the copy stream behind the caller's stream
+    void* host_arena = nullptr;                 // page-locked host block of the tile-PNG stage (stats back, plan up): grown on demand, kept
+    size_t host_arena_bytes = 0;
+    // the banded post-process in progress on this handle (s2sr_pp_band_*_dev, enhance_impl): geometry, channel order, how far the
+    // CLAHE'd rows and the finished rows reach
+    struct PPBand {
+        bool open = false, lut = false;
+        int H = 0, W = 0, bgr = 0, swap_out = 0, radius = 0;
+        int applied_end = 0, rows_end = 0;
+        s2sr_pp_params prm{};
+    } ppb;
+    // hipGraph replay of repeated groups
+    std::vector<s2sr::engine::GraphEntry> graphs;
+    uint64_t graph_clock = 0;
+    int64_t graph_replays = 0, graph_captures = 0;
+    // where the last run_net left the trunk output conv_body reads (it differs between the fp16 and the fp8 trunk);
+    // read by s2sr_debug_forward_taps only
+    struct TrunkRec { const char* hi = nullptr; uint64_t hi_img = 0; const char* lo = nullptr; uint64_t lo_img = 0; int lo_exp = -1; } trunk_rec;
+    s2sr::engine::TrunkTap* ttap = nullptr;     // s2sr_debug_trunk_taps' batch is running (run_net taps the trunk at its RDB boundaries); null otherwise
+    s2sr::engine::CompactTap* ctap = nullptr;   // s2sr_debug_compact_taps' batch is running
+};
+
+namespace s2sr::engine {
+
+// ---- engine.hip (each is described at its definition)
+int fail(s2sr_handle* h, int code, const std::string& msg);
+
+#define HIPCHK(h, expr)                                                                        \
+    do {                                                                                       \
+        hipError_t e__ = (expr);                                                               \
+        if (e__ != hipSuccess) {                                                               \
+            char b__[512];                                                                     \
+            snprintf(b__, sizeof b__, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            return fail(h, S2SR_E_HIP, b__);                                                   \
+        }                                                                                      \
+    } while (0)
+
+bool recover_stream(s2sr_handle* h);
+#define RUN_WITH_STREAM_RECOVERY(h, call)            \
+    do {                                             \
+        int rc_ = (call);                            \
+        if (rc_ != S2SR_OK && (h) && recover_stream(h)) rc_ = (call); \
+        return rc_;                                  \
+    } while (0)
+
+int ensure_scratch(s2sr_handle* h, int slot, size_t bytes);
+hipError_t copy_blocking(s2sr_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
+hipError_t fill_blocking(s2sr_handle* h, void* dst, int value, size_t bytes);
+
+// the plane decoders of the test hooks
+typedef _Float16 hf16;
+float e4m3_to_f32(uint8_t b);
+int fetch_planes(s2sr_handle* h, std::vector<uint8_t>& buf, const char* src, uint64_t img, int n, int nb, size_t blk);
+int decode_f16_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img, int n, int nb, size_t blk);
+int decode_e4m3_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img, int n, int nb, size_t blk, const float* scale);
+
+hipEvent_t get_event(s2sr_handle* h);
+
+struct Scope {   // brackets one launch with events when profiling is on
+    s2sr_handle* h;
+    hipStream_t st;
+    EvRec r;
+    bool on;
+    Scope(s2sr_handle* h_, hipStream_t st_, int fam, double flops, double bytes) : h(h_), st(st_), on(false) {
+        if (h->prof <= 0) return;
+        if (h->span_on && h->span.fam == fam) { h->span.flops += flops; h->span.bytes += bytes; h->span.n += 1; return; }
+        on = (h->fam_count[fam]++ % h->prof) == 0;
+        if (!on) return;
+        r.fam = fam; r.flops = flops; r.bytes = bytes;
+        r.e0 = get_event(h); r.e1 = get_event(h);
+        hipEventRecord(r.e0, st);
+    }
+    ~Scope() {
+        if (!on) return;
+        hipEventRecord(r.e1, st);
+        h->evs.push_back(r);
+    }
+};
+
+int group_size(const s2sr_handle* h, int B, int H, int W);
+void mosaic_remainder(int rem, int kx, int ky, int* rkx, int* rky);
+long mosaic_patches(int B, int th, int tw, int kx, int ky);
+Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw);
+Mosaic pick_mosaic(const s2sr_handle* h, int B, int th, int tw);
+int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const float* d_x_f32, int B, int th, int tw,
+                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan = nullptr, int src_h = 0, int src_w = 0);
+
+// ---- engine_aoi.hip
+constexpr size_t kStageBytes = 32u << 20;   // one pinned staging slice (s2sr_handle::stage_buf)
+int d2h_staged(s2sr_handle* h, uint8_t* dst, const uint8_t* src, size_t bytes, bool exposed);
+void plan_chunk_sizes(int units, int u_max, long unit_windows, int per, long pimg, int ncu, std::vector<int>& sizes);
+
+}  // namespace s2sr::engine

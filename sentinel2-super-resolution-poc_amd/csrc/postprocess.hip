@@ -257,7 +257,7 @@ __global__ void __launch_bounds__(256) clahe_hist_kernel(const uint8_t* __restri
 }
 
 // ---- kernel 1b: the same counts for the SOURCE rows [gm.y0, gm.y1) of one image ------------------
-// An AOI's mosaic is complete band by band (engine.hip enhance_impl, s2sr/dist.py); its histograms accumulate band by band under
+// An AOI's mosaic is complete band by band (engine_aoi.hip enhance_impl, s2sr/dist.py); its histograms accumulate band by band under
 // the compute of the windows still to come.  A source row feeds the padded rows that map to it (itself, and its reflections in
 // the BORDER_REFLECT_101 padding), so the workgroups walk their CLAHE tile's padded rows and keep those whose source row is in
 // the band: integer counts, the same totals in any split.  grid.x = tile columns, grid.y = (tile rows ty_lo..ty_hi) x chunks of
@@ -772,7 +772,7 @@ hipError_t launch_postprocess(const uint8_t* d_rgb, int B, int H, int W, const s
 
 // ---- the same post-process over ONE image in row bands ---------------------------------------------------------------------
 // CLAHE's grid is image-global (wow_sr.py:191-192): no output row exists before every input row has been counted.  A mosaic that
-// arrives band by band (the chunks of an AOI, engine.hip enhance_impl / s2sr/dist.py) therefore feeds the histograms as it arrives
+// arrives band by band (the chunks of an AOI, engine_aoi.hip enhance_impl / s2sr/dist.py) therefore feeds the histograms as it arrives
 // (launch_pp_band_hist, under the compute of the windows still to come), and once the LUTs exist the image is finished band by
 // band (launch_pp_band_apply R rows ahead of launch_pp_band_sharpen), each band followed by its device-to-host copy, so what is
 // exposed behind the last window is one band's kernels plus the PCIe time of the image.  Same kernels, same bytes as

@@ -7,7 +7,7 @@ is an independent forward.  Collectives used, and only these:
   * broadcast of the flat weight blob from rank 0, once per model load;
   * gather (to the one rank that consumes the mosaic) or all-gather of the ranks' u8 output windows.
 
-The AOI path (`enhance_distributed`) is chunked like the single-GPU one (engine.hip enhance_impl): a rank's
+The AOI path (`enhance_distributed`) is chunked like the single-GPU one (engine_aoi.hip enhance_impl): a rank's
 contiguous block of windows is cut into chunks (whole launch groups of window mosaics, shrinking towards the end:
 `native.plan_chunks`), all chunks are enqueued on the compute stream up front, and chunk k's outputs travel on a
 communication stream while chunk k+1 computes -- into views of ONE preallocated buffer on the consumer, at the
@@ -191,7 +191,7 @@ class NativeBackend(BackendBase):
         self.engine.forward_part_u8_dev(tiles.data_ptr(), B, h, w, max(job_windows, B), out.data_ptr(), self._stream())
 
     def chunk_plan(self, per: int, wh: int, ww: int) -> List[int]:
-        """The single-GPU path's planner (engine.hip plan_chunk_sizes) on this rank's block: units of one launch image (a
+        """The single-GPU path's planner (engine_aoi.hip plan_chunk_sizes) on this rank's block: units of one launch image (a
         window mosaic), at most one launch group per chunk, small chunks last (their gather / stitch / copy is exposed)."""
         if per <= 0:
             return []

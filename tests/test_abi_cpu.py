@@ -205,7 +205,7 @@ def test_hidden_asm_load_before_fp8_loader_branch_is_caught(tmp_path):
 
 
 def test_enhance_chunk_plan_properties():
-    """The chunk plan of a tiled s2sr_enhance_u8 (engine.hip plan_chunk_sizes through s2sr_debug_plan_chunks; host arithmetic,
+    """The chunk plan of a tiled s2sr_enhance_u8 (engine_aoi.hip plan_chunk_sizes through s2sr_debug_plan_chunks; host arithmetic,
     no device): every row unit is covered once, no chunk exceeds the workspace limit, the last chunk (whose band copy is exposed)
     is small, the middle piece is at most 5x the last, and the plan is the one the measurements
     were made with -- 4096x4096 at 256/10 (16 row units of 16 windows, 4x4 mosaics of 1225 patches, 256 workgroups) goes as

@@ -267,7 +267,7 @@ def test_cut_forward_stitch_equals_enhance():
             for dst in (None, 0):
                 got = enhance_distributed(be, img, ts, tp, dst=dst)
                 assert np.array_equal(got, exp), (H, W, dst)
-        # a service that alternates AOI sizes: the plan's paste maps live in a 4-entry LRU on the handle (engine.hip
+        # a service that alternates AOI sizes: the plan's paste maps live in a 4-entry LRU on the handle (engine_aoi.hip
         # s2sr_stitch_rows_u8_dev); six geometries taken in turn, twice, recycle entries while bands of the previous job may
         # still be queued -- every mosaic must keep its bytes (and, with enhance_crops, the band-wise post-process its own)
         geos = [(37, 45, 16, 2), (50, 41, 16, 2), (64, 65, 32, 4), (33, 70, 16, 3), (49, 48, 16, 2), (70, 36, 32, 2)]
@@ -568,7 +568,7 @@ def test_conv_last_folded_and_eight_stage_forms(monkeypatch, golden_dir):
 
 def test_staged_device_to_host_bands_give_the_same_image(monkeypatch):
     """s2sr_enhance_u8 / s2sr_forward_batch_u8 bring bands of 64 MB and more to the caller through two pinned 32-MB slices
-    (engine.hip d2h_staged; S2SR_D2H_STAGED=0 hands the caller's buffer to hipMemcpyAsync).  A 1248 x 1216 image at 256/10
+    (engine_aoi.hip d2h_staged; S2SR_D2H_STAGED=0 hands the caller's buffer to hipMemcpyAsync).  A 1248 x 1216 image at 256/10
     (25 windows, chunks of unequal size, a 73-MB output with a band above the threshold and a last slice that is not full)
     and a batch of 40 tiles (groups of 16: two 50-MB bands staged, the last one direct): both routes give the same bytes, and the image equals the windows pasted by hand."""
     rng = np.random.default_rng(91)
