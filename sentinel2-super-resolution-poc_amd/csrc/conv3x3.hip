@@ -35,19 +35,14 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <mutex>
 #include <vector>
 
 #include "s2sr_internal.h"
 
-#ifndef S2SR_DMA_LATE
-#define S2SR_DMA_LATE 0
-#endif
-#ifndef S2SR_PREFETCH_D
-#define S2SR_PREFETCH_D 1
-#endif
-
 namespace s2sr {
+
+// stage_body: LDS fragments are requested this many B steps ahead of the MFMAs that take them
+constexpr int kPrefetchD = 1;
 
 typedef _Float16 f16;
 typedef f16 f16x8 __attribute__((ext_vector_type(8)));
@@ -128,12 +123,7 @@ __device__ __forceinline__ void wait_vm_barrier() {
 // wait for stage j may allow exactly the operations issued after stage j's DMA: the later stages' DMA and -- while the awaited
 // DMA is older than the epilogue -- the epilogue's NST stores.  Both stages in flight at the epilogue qualify (2); measured
 // against 1 (r03, conv_hr / conv_up): no difference, the stores are not what the next stages wait for.  1 ships.
-#ifndef S2SR_HPO_SHORT
-#define S2SR_HPO_SHORT 1   // short e4m3 encodings in the split-operand producers' epilogue (see there)
-#endif
-#ifndef S2SR_F8_STORE_SLACK
-#define S2SR_F8_STORE_SLACK 1
-#endif
+constexpr int kF8StoreSlack = 1;
 #ifndef S2SR_DIAG_F8
 #define S2SR_DIAG_F8 0   // timing diagnostics of the split-operand (F8) schedule: 1 no LDS-DMA, 2 no MFMA, 4 no epilogue, 8 epilogue without its stores
 #endif
@@ -299,7 +289,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
         // are fetched one step ahead of their first use instead of all up front: no LDS-read
         // bubble behind the barrier.
         f16x8 a[9][CT];
-        constexpr int D = S2SR_PREFETCH_D;   // fragments are requested D steps ahead of their MFMAs ...
+        constexpr int D = kPrefetchD;        // fragments are requested D steps ahead of their MFMAs ...
         f16x8 b[D + 1];
 #pragma unroll
         for (int t = 0; t < D; ++t) {
@@ -323,11 +313,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
 #pragma unroll
             for (int sq = 0; sq < MAXI * G::PW; ++sq) {
                 constexpr int LASTSTEP = G::NBSTEP - 1;
-#if S2SR_DMA_LATE
-                if ((LASTSTEP - sq > 0 ? LASTSTEP - sq : 0) != step) continue;   // DMA rides on the LAST steps
-#else
-                if ((sq < LASTSTEP ? sq : LASTSTEP) != step) continue;
-#endif
+                if ((sq < LASTSTEP ? sq : LASTSTEP) != step) continue;   // DMA rides on the FIRST steps of the stage
                 const int w = sq / G::PW, sl = sq % G::PW;
                 if (w >= n_issue) continue;
                 int j = wave + sl * WAVES;
@@ -688,34 +674,24 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
                         } else if (HPO) {
                             // e4m3 copies for the consumer's correction terms: lo*2^11 and hi, clamped to the
                             // finite range (the fp8 conversions turn anything past 448 into NaN)
-                            // lo, short form (S2SR_HPO_SHORT; same bytes as the long one, tools/check_hpo_forms.py): v - fp16(v) in ONE
+                            // lo, short form (same bytes as the long one -- subtract, scale, clamp at 448, v_cvt_pk_fp8_f32 -- it replaced): v - fp16(v) in ONE
                             // v_fma_mix_f32 that reads the packed half in place, the clamp on the unscaled value, the 2^11 inside
                             // v_cvt_scalef32_pk_fp8_f32 (it divides by the power of two of its scale operand): 2.5 instead of 5.5
                             // instructions per value.  (hi straight from the packed pair -- v_pk_min/max_f16 +
                             // v_cvt_scalef32_pk_fp8_f16 -- was tried too and does NOT give the long form's bytes; it stays long.)
                             typedef short v2s __attribute__((ext_vector_type(2)));
-                            if (S2SR_HPO_SHORT) {
-                                float q[4];
+                            float q[4];
 #pragma unroll
-                                for (int i = 0; i < 4; ++i) {
-                                    float d;
-                                    if (i & 1) asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpk[g][i >> 1]), "v"(v[i]));
-                                    else asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpk[g][i >> 1]), "v"(v[i]));
-                                    q[i] = __builtin_amdgcn_fmed3f(d, -448.0f / 2048.0f, 448.0f / 2048.0f);
-                                }
-                                v2s w8 = {0, 0};
-                                w8 = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w8, q[0], q[1], 1.0f / 2048.0f, false);
-                                w8 = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w8, q[2], q[3], 1.0f / 2048.0f, true);
-                                lo8[g] = __builtin_bit_cast(uint32_t, w8);
-                            } else {
-                                float l4[4];
-#pragma unroll
-                                for (int i = 0; i < 4; ++i)
-                                    l4[i] = __builtin_amdgcn_fmed3f(__fmul_rn(__fsub_rn(v[i], (float)hv[i]), 2048.0f), -448.0f, 448.0f);
-                                int lw = __builtin_amdgcn_cvt_pk_fp8_f32(l4[0], l4[1], 0, false);
-                                lw = __builtin_amdgcn_cvt_pk_fp8_f32(l4[2], l4[3], lw, true);
-                                lo8[g] = (uint32_t)lw;
+                            for (int i = 0; i < 4; ++i) {
+                                float d;
+                                if (i & 1) asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpk[g][i >> 1]), "v"(v[i]));
+                                else asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpk[g][i >> 1]), "v"(v[i]));
+                                q[i] = __builtin_amdgcn_fmed3f(d, -448.0f / 2048.0f, 448.0f / 2048.0f);
                             }
+                            v2s w8 = {0, 0};
+                            w8 = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w8, q[0], q[1], 1.0f / 2048.0f, false);
+                            w8 = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w8, q[2], q[3], 1.0f / 2048.0f, true);
+                            lo8[g] = __builtin_bit_cast(uint32_t, w8);
                             if (HPO == 1) {
                                 float h4[4];
 #pragma unroll
@@ -802,7 +778,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
         int issued = S < R - 1 ? S : R - 1;
         auto wait_pending = [&](int pend) __attribute__((always_inline)) {
             const int age = epi_age < 8 ? epi_age++ : 8;
-            const bool epi = NST > 0 && age < S2SR_F8_STORE_SLACK;
+            const bool epi = NST > 0 && age < kF8StoreSlack;
             if (pend >= 2) {
                 if (epi) wait_vm_barrier<(NST > 0 ? 2 * PWn + NST : 2 * PWn)>();
                 else wait_vm_barrier<2 * PWn>();
@@ -930,35 +906,16 @@ static hipError_t launch_t(const ConvParams& p, hipStream_t st) {
         return hipErrorInvalidValue;   // 4 fp16 blocks + 4 fp8 planes (conv_last folded: + 2)
     if (PH >= 0 && !F8 && p.nstage != 4) return hipErrorInvalidValue;
     if (EPI == EPI_LAST && (p.cout > 3 || CT != 1)) return hipErrorInvalidValue;   // its epilogue writes couts 0..2 (RGB) only
-    // the dynamic-LDS opt-in is per device: a process may hold handles on several GPUs, driven from
-    // different threads (each handle has its own mutex, so this table needs one of its own)
-    static std::mutex attr_mu;
-    static bool attr_set[64] = {false};
-    static int ncu_dev[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    static KernelLaunchState state;
     int ncu;
-    {
-        std::lock_guard<std::mutex> lk(attr_mu);
-        if (!attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            int n = 256;
-            (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-            ncu_dev[dev] = n;
-            attr_set[dev] = true;
-        }
-        ncu = ncu_dev[dev];
-    }
+    if (hipError_t e = state.prepare((const void*)kern, G::LDS_BYTES, &ncu); e != hipSuccess) return e;
     ConvParams q = p;
     if (q.seg_len <= 0) { q.seg_len = q.nstage; q.seg_lo_mask = 0; }
     if (!q.src_lo) { q.src_lo = q.src; q.lo_img = q.src_img; }
     q.tilesX = (p.W + G::TW - 1) / G::TW;
     q.tilesY = (p.H + G::TH - 1) / G::TH;
     const int ntiles = q.tilesX * q.tilesY * p.N;
-    int grid = (ncu * OCC) & ~7;              // OCC persistent workgroups per CU
-    if (ntiles < grid) grid = (ntiles + 7) & ~7;
+    int grid = persistent_grid(ncu, OCC, ntiles);   // OCC persistent workgroups per CU
 #if S2SR_DIAG_F8
     if (F8) {   // diagnostic builds only: run the split-operand convs on a subset of the CUs (S2SR_DIAG_GRID workgroups, multiple of 8)
         static const int dg = [] { const char* e = getenv("S2SR_DIAG_GRID"); return e ? atoi(e) & ~7 : 0; }();

@@ -40,36 +40,10 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include <mutex>
 #include <type_traits>
 
 #include "s2sr_internal.h"
 
-#ifndef S2SR_F16_BIASC
-#define S2SR_F16_BIASC 1   // conv_trunk_f16 conv1-4: bias as the first MFMA's C operand + packed LeakyReLU (0: bias add in the epilogue)
-#endif
-#ifndef S2SR_F16_ACCV
-#define S2SR_F16_ACCV 1    // conv_trunk_f16 conv1-4: accumulators (and the bias C operand) in architectural VGPRs instead of AGPRs (76 + 128 + 16
-                           // registers fit the 256): the epilogue reads them in place, 128 v_accvgpr_read per patch and wave less.  Same bytes out;
-                           // measured (tools/ab_macro.sh, A/B/A/B on one box) conv1-4 73.4 -> 72.0 us per launch, step 85.9 -> 85.4 ms
-#endif
-#ifndef S2SR_F16_LOENC
-#define S2SR_F16_LOENC 1   // conv_trunk_f16 conv5: the short form of the lo encoding (v_fma_mix_f32 + v_cvt_scalef32_pk_fp8_f32), see the epilogue
-#endif
-#ifndef S2SR_SMALL_PL
-#define S2SR_SMALL_PL 2         // conv_trunk_f16, the single-tile forms (8x32 patches): planes per pipeline stage (1: as until r04's first half)
-#endif
-#ifndef S2SR_F16_EARLYBIAS
-#define S2SR_F16_EARLYBIAS 1    // conv_trunk_f16: 1 = the bias is requested (inline-asm loads) before the ring fill and consumed behind the first
-                                // wait; 0 = plain C++ loads in front of the first DMA instruction, as until r03 (two dependent round trips)
-#endif
-#ifndef S2SR_DIAG_NOLO
-#define S2SR_DIAG_NOLO 0        // numerics diagnostic (tools/nolo_probe.sh): the fp16 trunk carried WITHOUT its lo half.  Measured: max-abs
-                                // 2.2e-3 .. 3.4e-3 instead of 7e-5 .. 1.8e-4: the pair is what the 1e-3 costs (its lo half needs only e4m3, see the epilogue)
-#endif
-#ifndef S2SR_DIAG_SKIPDY2
-#define S2SR_DIAG_SKIPDY2 0     // timing diagnostic, conv_trunk_f16: 1 = the dy == 2 MFMAs are not issued (results wrong): 2/3 of the MFMA work
-#endif
 #ifndef S2SR_DIAG_NOMFMA
 #define S2SR_DIAG_NOMFMA 0      // timing diagnostic, both kernels: 1 = issue no MFMA (results are wrong).  What is left is the memory
                                 // side of the kernel: profiles/r02_trunk_anatomy.txt section 8
@@ -145,7 +119,6 @@ __device__ __forceinline__ f32x4 half4_to_float(u32x2 h) {
     for (int i = 0; i < 4; ++i) o[i] = (float)v[i];
     return o;
 }
-__device__ __forceinline__ float lrelu(float v) { return fmaxf(v, __fmul_rn(v, 0.2f)); }
 
 // v_fma_mix_f32 with ONE fp16 operand read in place from a packed register (HI: its upper half): the compiler prefers
 // v_cvt_f32_f16 + v_pk_fma_f32 for these, one instruction more per value
@@ -166,18 +139,13 @@ __device__ __forceinline__ void mfma_first(f32x16& acc, const f16x8& a, const f1
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b));
 }
 
-// first MFMA of a patch with the bias vector (AGPRs, constant for the whole kernel) as C: the bias costs no instruction
-__device__ __forceinline__ void mfma_first_bias(f32x16& acc, const f16x8& a, const f16x8& b, const f32x16& bias) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&a"(acc) : "v"(a), "v"(b), "a"(bias));
-}
-// the same three with C / D in ARCHITECTURAL VGPRs (S2SR_F16_ACCV, conv1-4 form: 76 + 128 + 16 registers fit the 256):
-// the epilogue's VALU then reads the results in place instead of through 128 v_accvgpr_read per patch and wave
+// conv1-4: C / D in ARCHITECTURAL VGPRs (76 + 128 + 16 registers fit the 256): the epilogue's VALU reads the results in place
+// instead of through 128 v_accvgpr_read per patch and wave.  Same bytes out as the AGPR form; measured (tools/ab_macro.sh,
+// A/B/A/B on one box) conv1-4 73.4 -> 72.0 us per launch, step 85.9 -> 85.4 ms
 __device__ __forceinline__ void mfma_acc_v(f32x16& acc, const f16x8& a, const f16x8& b) {
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(a), "v"(b));
 }
-__device__ __forceinline__ void mfma_first_v(f32x16& acc, const f16x8& a, const f16x8& b) {
-    asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=v"(acc) : "v"(a), "v"(b));
-}
+// first MFMA of a patch with the bias vector (constant for the whole kernel) as C: the bias costs no instruction
 __device__ __forceinline__ void mfma_first_bias_v(f32x16& acc, const f16x8& a, const f16x8& b, const f32x16& bias) {
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(acc) : "v"(a), "v"(b), "v"(bias));
 }
@@ -237,8 +205,8 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
     const uint32_t sblk = (uint32_t)p.sHp * p.sWp * 32;
     const size_t oblk = (size_t)p.Hp * p.Wp * 32;
 
-    constexpr bool kBiasC = (EPI == EPI_LRELU) && S2SR_F16_BIASC;
-    constexpr bool kAccV = (EPI == EPI_LRELU) && S2SR_F16_ACCV;
+    // !kTrunk (conv1-4): the bias is the C operand of each accumulator's first MFMA and the accumulators live in architectural
+    // VGPRs; kTrunk (conv5): AGPR accumulators, the bias is added in the epilogue (its registers are spoken for by the residual operands)
     static_assert(NP <= 8, "accumulators of at most 8 rows per wave fit one register file next to the fragments");
 
     // ---- per-lane global offsets of this wave's PW DMA pieces (patch independent)
@@ -292,19 +260,15 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
     // 2 us prologue of a 7-8 us single-tile launch).  Inline asm: the compiler's own wait would drain the ring.
     // (A hidden load whose destination is dead on some path lands in registers the compiler has handed to something else there:
     // in front of a loader wave's role branch, its DMA offsets -- a memory fault, r04.  tools/check_asm_loads.py --cfg.)
-    constexpr bool kEarly = S2SR_F16_EARLYBIAS != 0;
     uint32_t bias_l = 0;
-    if (!kEarly && tid < CT * 32) ((float*)(smem + G::BIAS_OFF))[tid] = p.bias[tid];
-    if (kEarly && !kBiasC) bias_l = asm_load4v((const char*)(p.bias + (tid < CT * 32 ? tid : 0)));
-    f32x4 bq[kBiasC ? CT : 1][4];
-    if (kEarly && kBiasC) {
+    if (kTrunk) bias_l = asm_load4v((const char*)(p.bias + (tid < CT * 32 ? tid : 0)));
+    f32x4 bq[kTrunk ? 1 : CT][4];
+    if (!kTrunk) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const char* a = (const char*)(p.bias + ct * 32 + 8 * g + 4 * hh);
-                bq[kBiasC ? ct : 0][g] = kAccV ? asm_load16v(a) : asm_load16(a);
-            }
+            for (int g = 0; g < 4; ++g)
+                bq[kTrunk ? 0 : ct][g] = asm_load16v((const char*)(p.bias + ct * 32 + 8 * g + 4 * hh));
     }
 
     // ---- fragment addresses inside a slot: per-lane base + immediate
@@ -322,22 +286,7 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
     char* const trash = p.trash + (size_t)tid * 16;
 
     f32x16 acc[CT][NP];
-    // conv1-4: the bias rides in as the C operand of each accumulator's first MFMA (16 AGPRs per cout tile, loaded once);
-    // conv5 keeps adding it in the epilogue (its AGPRs are spoken for by the residual operands)
-    f32x16 bacc[kBiasC ? CT : 1];
-    if (!kEarly && kBiasC) {
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) bacc[kBiasC ? ct : 0][4 * g + i] = p.bias[ct * 32 + 8 * g + 4 * hh + i];
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            if (kAccV) asm volatile("" : "+v"(bacc[kBiasC ? ct : 0]));
-            else asm volatile("" : "+a"(bacc[kBiasC ? ct : 0]));
-        }
-    }
+    f32x16 bacc[kTrunk ? 1 : CT];   // conv1-4: the bias as the C operand (16 registers per cout tile, loaded once)
     f16x8 acol[3][3][CT];     // A fragments: [kernel column dx][kernel row dy][cout tile]
     f16x8 breg[6];            // B fragments of steps t, t+1, t+2, t+3 (ring indexed by step % 6)
 
@@ -356,22 +305,19 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
     wait_release_barrier<G::NW>();                                // stage 0 has landed
     // the bias requests are older than every DMA instruction: they have landed too.  conv5 reads it from LDS in its epilogue
     // (every stage barrier lies in between), conv1-4 feed it to the first MFMA of each accumulator as C.
-    if (kEarly && !kBiasC) {
+    if (kTrunk) {
         asm volatile("" : "+v"(bias_l));
         if (tid < CT * 32) ((uint32_t*)(smem + G::BIAS_OFF))[tid] = bias_l;
-    }
-    if (kEarly && kBiasC) {
+    } else {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                if (kAccV) asm_land_v(bq[kBiasC ? ct : 0][g]);
-                else asm_land(bq[kBiasC ? ct : 0][g]);
+                asm_land_v(bq[kTrunk ? 0 : ct][g]);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) bacc[kBiasC ? ct : 0][4 * g + i] = bq[kBiasC ? ct : 0][g][i];
+                for (int i = 0; i < 4; ++i) bacc[kTrunk ? 0 : ct][4 * g + i] = bq[kTrunk ? 0 : ct][g][i];
             }
-            if (kAccV) asm volatile("" : "+v"(bacc[kBiasC ? ct : 0]));
-            else asm volatile("" : "+a"(bacc[kBiasC ? ct : 0]));
+            asm volatile("" : "+v"(bacc[kTrunk ? 0 : ct]));
         }
     }
     {
@@ -501,25 +447,16 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
                     asm volatile("" : "+a"(acc[ct][np]) : "v"(acol[dx][dy][ct]), "v"(breg[t % 6]));
                     continue;
 #endif
-#if S2SR_DIAG_SKIPDY2
-                    // timing diagnostic only (wrong results): one MFMA in three is not issued (its operand reads stay) -- the MFMA
-                    // count of a row-Winograd F(2,3) form without its transform cost: an upper bound for what that form can buy
-                    if (dy == 2) {
-                        asm volatile("" : "+a"(acc[ct][np]) : "v"(acol[dx][dy][ct]), "v"(breg[t % 6]));
-                        continue;
+                    // (Not issuing the dy == 2 MFMAs -- the MFMA count of a row-Winograd F(2,3) form without its transform cost, an
+                    // upper bound for what that form could buy -- was priced once and the form dropped: profiles/r03_skipdy2_raw.txt.)
+                    const bool kFirstMfma = FIRST && pl == 0 && dx == 0 && dy == 0;
+                    if (kTrunk) {
+                        if (kFirstMfma) mfma_first(acc[ct][np], acol[dx][dy][ct], breg[t % 6]);
+                        else mfma_acc(acc[ct][np], acol[dx][dy][ct], breg[t % 6]);
+                    } else {
+                        if (kFirstMfma) mfma_first_bias_v(acc[ct][np], acol[dx][dy][ct], breg[t % 6], bacc[kTrunk ? 0 : ct]);
+                        else mfma_acc_v(acc[ct][np], acol[dx][dy][ct], breg[t % 6]);
                     }
-#endif
-                    if (kAccV) {
-                        if (FIRST && pl == 0 && dx == 0 && dy == 0) {
-                            if (kBiasC) mfma_first_bias_v(acc[ct][np], acol[dx][dy][ct], breg[t % 6], bacc[kBiasC ? ct : 0]);
-                            else mfma_first_v(acc[ct][np], acol[dx][dy][ct], breg[t % 6]);
-                        } else mfma_acc_v(acc[ct][np], acol[dx][dy][ct], breg[t % 6]);
-                        continue;
-                    }
-                    if (FIRST && pl == 0 && dx == 0 && dy == 0) {
-                        if (kBiasC) mfma_first_bias(acc[ct][np], acol[dx][dy][ct], breg[t % 6], bacc[kBiasC ? ct : 0]);
-                        else mfma_first(acc[ct][np], acol[dx][dy][ct], breg[t % 6]);
-                    } else mfma_acc(acc[ct][np], acol[dx][dy][ct], breg[t % 6]);
                 }
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -540,8 +477,8 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int np = 0; np < NP; ++np) {
-                if (kAccV) asm_land_v(acc[ct][np]);
-                else asm_land(acc[ct][np]);
+                if (kTrunk) asm_land(acc[ct][np]);
+                else asm_land_v(acc[ct][np]);
             }
         const int tile = it * nwg + slot_in_round;
         const int n = tile / tpi;
@@ -550,7 +487,7 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
         const int y0 = ty * G::TH, x0 = tx * G::TW;
         const int x = x0 + pcol;
         f32x16 bv[CT];
-        if constexpr (!(kBiasC && S2SR_F16_EARLYBIAS)) {          // (bias as the MFMA's C operand: nothing in LDS)
+        if constexpr (kTrunk) {                                   // (conv1-4, bias as the MFMA's C operand: nothing in LDS)
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -573,9 +510,9 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
             opix[np] = (size_t)(y + 1) * p.Wp + (x + 1);
         }
         const size_t ln = (size_t)n * 2 * oblk;   // image offset inside the e4m3 lo tensors, bytes
-        const float lo_dec = __builtin_ldexpf(1.0f, -p.lo_exp), lo_enc = __builtin_ldexpf(1.0f, p.lo_exp);   // e4m3 lo planes hold lo * 2^lo_exp
-        const float lo_lim = __builtin_ldexpf(448.0f, -p.lo_exp);                                            // ... of |lo| up to 448 * 2^-lo_exp
-        (void)lo_enc; (void)lo_lim;
+        const float lo_dec = __builtin_ldexpf(1.0f, -p.lo_exp);      // e4m3 lo planes hold lo * 2^lo_exp
+        const float lo_lim = __builtin_ldexpf(448.0f, -p.lo_exp);    // ... of |lo| up to 448 * 2^-lo_exp
+        (void)lo_lim;
         // the four dwords of a lane's channel groups out of the 16 bytes it fetched (q[g] = channels 8g+4hh.. of the plane)
         auto unswap = [&](const f32x4& o, uint32_t (&q)[4]) __attribute__((always_inline)) {
             const u32x4 u = __builtin_bit_cast(u32x4, o);
@@ -622,10 +559,7 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     f32x4 v;
-                    if (EPI == EPI_LRELU && !kBiasC) {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) v[i] = lrelu(__fadd_rn(acc[ct][np][4 * g + i], bv[ct][4 * g + i]));
-                    } else if (EPI == EPI_LRELU) {
+                    if (EPI == EPI_LRELU) {
                         // LeakyReLU on pairs (v_pk_mul_f32 / v_pk_max_f32): the bias is already in the accumulator
 #pragma unroll
                         for (int h2 = 0; h2 < 2; ++h2) {
@@ -677,42 +611,29 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
                     if (kTrunk) {
                         // lo = v - fp16(v), kept as e4m3(lo * 2^lo_exp): 4 significant bits of it are what the 1e-3 needs
                         // (measured: max-abs 8.8e-5 .. 1.85e-4 against 7.0e-5 .. 1.8e-4 with an fp16 lo, 2.2e-3 .. 3.4e-3 without one)
-                        // Two forms with the same bytes (S2SR_F16_LOENC; the short one ships, checked against tests/trunk_model.py's restatement
-                        // on stress operands by test_f16_conv5_lo_encoding_on_stress_operands).
+                        // (The last figure is from a diagnostic build that stored zeros for lo: the pair is what the 1e-3 costs.)  The encoding
+                        // is checked against tests/trunk_model.py's restatement on stress operands by test_f16_conv5_lo_encoding_on_stress_operands.
                         // (r02 tried another short form -- fma(fp16(v), -2^lo_exp, v * 2^lo_exp) as one asm v_fma_mix_f32 -- that measured
                         // 1.4e-3 instead of 1.3e-4 inside this kernel although it was bit-identical in isolation; never explained, and
                         // not this form: here the fma computes v - fp16(v), exact in fp32, and the scale rides in the conversion.)
-                        if constexpr (S2SR_F16_LOENC != 0) {
                         // r03: 2.5 instead of 4.5 instructions per value (the conv5 epilogue was 1/3 lo encoding): v - fp16(v) in ONE
                         // v_fma_mix_f32 that reads the packed half in place (exact: the difference of a float and its own fp16 rounding),
                         // the clamp on the unscaled value, and the 2^lo_exp inside v_cvt_scalef32_pk_fp8_f32 (it divides by the power
                         // of two of its scale operand and, like the plain conversion, turns overflow into NaN -- hence the clamp:
-                        // tools/micro/cvt_scale_probe.hip).  Same bytes as the long form.
+                        // tools/micro/cvt_scale_probe.hip).  Same bytes as the long form it replaced (subtract, scale, clamp at 448, v_cvt_pk_fp8_f32).
                         float q[4];
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
                             float d;
                             if (i & 1) asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpk[g][i >> 1]), "v"(v[i]));
                             else asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hpk[g][i >> 1]), "v"(v[i]));
-                            q[i] = S2SR_DIAG_NOLO ? 0.0f : __builtin_amdgcn_fmed3f(d, -lo_lim, lo_lim);
+                            q[i] = __builtin_amdgcn_fmed3f(d, -lo_lim, lo_lim);
                         }
                         typedef short v2s __attribute__((ext_vector_type(2)));
                         v2s w8 = {0, 0};
                         w8 = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w8, q[0], q[1], lo_dec, false);
                         w8 = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(w8, q[2], q[3], lo_dec, true);
                         lq8[g] = __builtin_bit_cast(uint32_t, w8);
-                        } else {
-                        float q[4];
-                        {
-                            const f16x4 hv4 = __builtin_bit_cast(f16x4, hpk[g]);
-#pragma unroll
-                            for (int i = 0; i < 4; ++i)
-                                q[i] = S2SR_DIAG_NOLO ? 0.0f : __builtin_amdgcn_fmed3f(__fmul_rn(__fsub_rn(v[i], (float)hv4[i]), lo_enc), -448.0f, 448.0f);
-                        }
-                        int w8 = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
-                        w8 = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], w8, true);
-                        lq8[g] = (uint32_t)w8;
-                        }
                     }
                 }
                 // pair the half-waves: one 16-B store per 16-channel block, 1 KiB contiguous per wave-instruction
@@ -771,7 +692,7 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
 template <int CT, int NP, int R, int EPI, int FULL = 0, int PL = 1>
 hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_form* form = nullptr) {
     using G = TG<CT, NP, R, PL>;
-    constexpr bool kNoLdsBias = (EPI == EPI_LRELU) && S2SR_F16_BIASC && S2SR_F16_EARLYBIAS;    // bias as the C operand: no LDS copy
+    constexpr bool kNoLdsBias = EPI == EPI_LRELU;                  // bias as the C operand: no LDS copy
     constexpr int LDSB = kNoLdsBias ? G::RING_BYTES : G::LDS_BYTES;
     static_assert(LDSB <= 160 * 1024, "LDS ring does not fit");
     static_assert(G::NW < 64, "vmcnt field is 6 bits");
@@ -780,25 +701,9 @@ hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_
     if (FULL == 3 && p.mos_py != 0) return hipErrorInvalidValue;
     if (FULL == 2 && (p.mos_py != 277 || p.mos_ry != 276 || p.mos_px != 277 || p.mos_rx != 276)) return hipErrorInvalidValue;
     auto kern = conv_trunk_f16<CT, NP, R, EPI, FULL, PL>;
-    static std::mutex attr_mu;
-    static bool attr_set[64] = {false};
-    static int ncu_dev[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    static KernelLaunchState state;
     int ncu;
-    {
-        std::lock_guard<std::mutex> lk(attr_mu);
-        if (!attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);
-            if (e != hipSuccess) return e;
-            int n = 256;
-            (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-            ncu_dev[dev] = n;
-            attr_set[dev] = true;
-        }
-        ncu = ncu_dev[dev];
-    }
+    if (hipError_t e = state.prepare((const void*)kern, LDSB, &ncu); e != hipSuccess) return e;
     // operand shapes the kernel's indexing assumes (a violation would read or write outside the tensors)
     if (p.nstage < 1 || p.nstage > 12 || p.sHp != p.Hp || p.sWp != p.Wp || p.Hp < p.H + 2 || p.Wp < p.W + 2) return hipErrorInvalidValue;
     if ((EPI == EPI_RDB5 || EPI == EPI_RDB5_RRDB) && (p.nstage < 5 * PL || !p.T || !p.xh_in || (EPI == EPI_RDB5_RRDB && (!p.xh_skip || !p.lo_skip))))
@@ -810,9 +715,8 @@ hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_
     q.tilesX = (p.W + G::TW - 1) / G::TW;
     q.tilesY = (p.H + G::TH - 1) / G::TH;
     const int ntiles = q.tilesX * q.tilesY * p.N;
-    int grid = ncu & ~7;
-    if (ntiles < grid) grid = (ntiles + 7) & ~7;
-    if (form) *form = s2sr_debug_trunk_form{1, CT, G::TH, R, FULL, PL, 0, 0, S2SR_F16_LOENC, 4, 0, EPI};
+    const int grid = persistent_grid(ncu, 1, ntiles);
+    if (form) *form = s2sr_debug_trunk_form{1, CT, G::TH, R, FULL, PL, 0, 0, 1, 4, 0, EPI};   // lo_enc: 1, the one encoding (see the epilogue)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDSB, st, q);
     return hipGetLastError();
 }
@@ -1444,25 +1348,9 @@ hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk
     static_assert(G::NW >= 0 && G::NW < 64, "vmcnt field is 6 bits");
     auto kern = conv_trunk_f8<CT, NP, RS, EPI, NPL, PROD>;
     if (NPL > 0 && p.nstage > NPL) return hipErrorInvalidValue;   // resident weights: the conv's planes must fit the LDS block
-    static std::mutex attr_mu;
-    static bool attr_set[64] = {false};
-    static int ncu_dev[64] = {0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+    static KernelLaunchState state;
     int ncu;
-    {
-        std::lock_guard<std::mutex> lk(attr_mu);
-        if (!attr_set[dev]) {
-            hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            int n = 256;
-            (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-            ncu_dev[dev] = n;
-            attr_set[dev] = true;
-        }
-        ncu = ncu_dev[dev];
-    }
+    if (hipError_t e = state.prepare((const void*)kern, G::LDS_BYTES, &ncu); e != hipSuccess) return e;
     // operand shapes the kernel's indexing assumes
     if (p.nstage < 2 || p.nstage > 6 || (p.nstage & 1) || p.seg_len < 1 || p.seg_len > p.nstage) return hipErrorInvalidValue;
     if ((EPI == EPI_RDB5 || EPI == EPI_RDB5_RRDB) && p.nstage < 4) return hipErrorInvalidValue;   // the residual prefetch rides on a later pair-step than the first
@@ -1475,8 +1363,7 @@ hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk
     q.tilesX = (p.W + G::TW - 1) / G::TW;
     q.tilesY = (p.H + G::TH - 1) / G::TH;
     const int ntiles = q.tilesX * q.tilesY * p.N;
-    int grid = ncu & ~7;
-    if (ntiles < grid) grid = (ntiles + 7) & ~7;
+    const int grid = persistent_grid(ncu, 1, ntiles);
     if (form) *form = s2sr_debug_trunk_form{2, CT, G::TH, RS, 0, 2, PROD, 0, 0, G::WAVES, NPL, EPI};
     hipLaunchKernelGGL(kern, dim3(grid), dim3((G::WAVES + PROD) * 64), G::LDS_BYTES, st, q);
     return hipGetLastError();
@@ -1506,10 +1393,11 @@ hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t s
         const bool full = p.mos_py == 0 && p.H % 32 == 0 && p.W % 32 == 0 && !(p.f16_form & 4);   // whole patches only (f16_form bit 2: diagnostic off switch)
         const bool plain = p.mos_py == 0 && !(p.f16_form & 4);                                  // ragged, but no mosaic: the extent test alone
         if (n32 < 96 && !(p.f16_form & 2)) {
-            if (S2SR_SMALL_PL == 2 && full) return launch_trunk_t<1, 2, 3, EPI_LRELU, 1, 2>(p, st, form);
-            if (S2SR_SMALL_PL == 2 && plain) return launch_trunk_t<1, 2, 3, EPI_LRELU, 3, 2>(p, st, form);
-            return full ? launch_trunk_t<1, 2, 7, EPI_LRELU, 1>(p, st, form)
-                        : plain ? launch_trunk_t<1, 2, 7, EPI_LRELU, 3>(p, st, form) : launch_trunk_t<1, 2, 7, EPI_LRELU>(p, st, form);
+            // two planes per stage (double-buffered) where the epilogue needs no mosaic test: half the barriers per patch
+            // (profiles/r04_latency_anatomy.txt); the 7-deep one-plane ring otherwise
+            if (full) return launch_trunk_t<1, 2, 3, EPI_LRELU, 1, 2>(p, st, form);
+            if (plain) return launch_trunk_t<1, 2, 3, EPI_LRELU, 3, 2>(p, st, form);
+            return launch_trunk_t<1, 2, 7, EPI_LRELU>(p, st, form);
         }
         if (n32 < 192)
             return full ? launch_trunk_t<1, 4, 5, EPI_LRELU, 1>(p, st, form)
@@ -1528,7 +1416,7 @@ hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t s
         if (force_form == 2) return hipErrorNotSupported;
         const long n16 = (long)((p.W + 31) / 32) * ((p.H + 15) / 16) * p.N;
         const bool small = force_form == 5 || (force_form == 0 && n16 < 192 && !(p.f16_form & 2));
-        if (force_form == 10 || (small && force_form == 0 && S2SR_SMALL_PL == 2))      // 8x32 patches, two planes per stage, double-buffered
+        if (force_form == 10 || (small && force_form == 0))      // 8x32 patches, two planes per stage, double-buffered
             return epi == EPI_RDB5 ? launch_trunk_t<2, 2, 2, EPI_RDB5, 0, 2>(p, st, form)
                                    : launch_trunk_t<2, 2, 2, EPI_RDB5_RRDB, 0, 2>(p, st, form);
         if (epi == EPI_RDB5) return small ? launch_trunk_t<2, 2, 5, EPI_RDB5>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5>(p, st, form);

@@ -174,6 +174,37 @@ __device__ __forceinline__ bool px_live(const ConvParams& p, const PatchLive& L,
     return ok;
 }
 
+// Per-device launch state of ONE persistent-workgroup kernel: the dynamic-LDS opt-in and the CU count.  Each launcher instantiation
+// keeps one static instance.  The opt-in is per device: a process may hold handles on several GPUs, driven from different threads
+// (each handle has its own mutex, so this table needs one of its own).
+struct KernelLaunchState {
+    std::mutex mu;
+    bool attr_set[64] = {false};
+    int ncu_dev[64] = {0};
+    // first launch on the current device: opt the kernel in to lds_bytes of dynamic LDS; always: *ncu = the device's CU count
+    hipError_t prepare(const void* kernel, int lds_bytes, int* ncu) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+        std::lock_guard<std::mutex> lk(mu);
+        if (!attr_set[dev]) {
+            hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+            if (e != hipSuccess) return e;
+            int n = 256;
+            (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+            ncu_dev[dev] = n;
+            attr_set[dev] = true;
+        }
+        *ncu = ncu_dev[dev];
+        return hipSuccess;
+    }
+};
+// grid of persistent workgroups: occ per CU, a multiple of 8 (one round over the XCDs); fewer tiles than that: the tiles, rounded up to 8
+static inline int persistent_grid(int ncu, int occ, int ntiles) {
+    const int grid = (ncu * occ) & ~7;
+    return ntiles < grid ? (ntiles + 7) & ~7 : grid;
+}
+
 // conv kernel (conv3x3.hip).  ct = ceil(Cout/32) in {1,2}.
 hipError_t launch_conv(const ConvParams& p, int ct, int epi, bool upsample, bool lo_out, hipStream_t st, bool f8_in = false);
 // the RRDB trunk convs as one-wave-per-SIMD workgroups (conv_trunk.hip): ct 1 + EPI_LRELU (conv1..4), ct 2 + EPI_RDB5 /

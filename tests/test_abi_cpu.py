@@ -23,6 +23,20 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.s2sr_version()
 
 
+def test_gpu_tests_clear_exactly_the_switches_s2sr_create_reads():
+    """tests/gpu_engines.py creates default engines with SWITCHES cleared: a switch s2sr_create reads and the list lacks would
+    leak a test's environment into a cached handle; a name the list has and nothing reads is rot."""
+    import gpu_engines
+
+    src = (REPO / "sentinel2-super-resolution-poc_amd" / "csrc" / "engine.hip").read_text()
+    body = src[src.index("int s2sr_create("):]
+    body = body[:body.index("\n}\n")]                       # up to the function's closing brace in column 0
+    read = re.findall(r'getenv\("(S2SR_[A-Z0-9_]+)"\)', body)
+    assert read, "no getenv call parsed in s2sr_create"
+    assert len(read) == len(set(read)) and len(gpu_engines.SWITCHES) == len(set(gpu_engines.SWITCHES))
+    assert set(read) == set(gpu_engines.SWITCHES)
+
+
 def test_expected_blob_size():
     lib = native.load_library()
     assert lib.s2sr_expected_blob_floats(23) == 16_697_987

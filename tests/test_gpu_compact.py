@@ -11,13 +11,13 @@ num_conv 32 (the CPU emulation of the same formats on the golden: 2.8e-4 / 1.2e-
 (num_conv 32); per layer in situ the worst element sits at 0.996 of the bound."""
 from __future__ import annotations
 
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import compact_insitu as ci
+import gpu_engines
 import compact_model as cm
 from s2sr import native
 from s2sr import rasterio_lite as rio
@@ -29,9 +29,6 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-3            # the project's tolerance against the fp32-class reference
 U8_CAP = 0.04         # share of u8 values allowed to be one level off (twice what the CPU emulation shows)
 HP, FAST, FP8 = native.PREC_F16_HP, native.PREC_F16, native.PREC_FP8
-_SWITCHES = ("S2SR_SMALL8", "S2SR_MOSAIC", "S2SR_LO_EXP", "S2SR_FP8_TAIL", "S2SR_GRAPH", "S2SR_F16_FULL", "S2SR_LAST_FOLD",
-             "S2SR_D2H_STAGED", "S2SR_FP8_XEXP", "S2SR_FP8_GEXP")
-_ENG = {}
 _SD = {}
 
 
@@ -41,27 +38,12 @@ def _sd(nc):
     return _SD[nc]
 
 
-def engine(nc, precision=HP, **kw):
-    key = (nc, precision, tuple(sorted(kw.items())))
-    if key not in _ENG:
-        saved = {k: os.environ.pop(k) for k in _SWITCHES if k in os.environ}
-        try:
-            e = native.Engine(num_block=nc, precision=precision, arch="compact", **kw)
-        finally:
-            os.environ.update(saved)
-        e.load_state_dict(_sd(nc))
-        _ENG[key] = e
-    return _ENG[key]
+def engine(nc, precision=HP):
+    return gpu_engines.default(nc, precision, arch="compact")
 
 
 def _fresh(monkeypatch, nc, env, sd=None, **kw):
-    for k in _SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    e = native.Engine(num_block=nc, precision=HP, arch="compact", **kw)
-    e.load_state_dict(sd if sd is not None else _sd(nc))
-    return e
+    return gpu_engines.fresh(monkeypatch, env, nc, HP, arch="compact", sd=sd if sd is not None else _sd(nc), **kw)
 
 
 def _u8(seed, *shape):

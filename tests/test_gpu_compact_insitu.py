@@ -29,7 +29,6 @@ once; x = 0.21868873f packed as 55.78125 where fp16(fp32(255 x)) is 55.75 (case 
 now keeps the fp32 product (csrc/pack.hip); on the u8 grid both roundings agree (test_compact_insitu_cpu.py)."""
 from __future__ import annotations
 
-import os
 import time
 
 import numpy as np
@@ -37,6 +36,7 @@ import pytest
 import torch
 
 import compact_insitu as ci
+import gpu_engines
 import compact_model as cm
 from s2sr import native
 from s2sr import weights as W
@@ -47,8 +47,6 @@ pytestmark = pytest.mark.gpu
 TOL = 1e-3            # the project's tolerance against the fp32-class reference (test_gpu_compact.TOL)
 U8_CAP = 0.04         # test_gpu_compact.U8_CAP
 HP = native.PREC_F16_HP
-_SWITCHES = ("S2SR_SMALL8", "S2SR_MOSAIC", "S2SR_LO_EXP", "S2SR_FP8_TAIL", "S2SR_GRAPH", "S2SR_F16_FULL", "S2SR_LAST_FOLD",
-             "S2SR_D2H_STAGED", "S2SR_FP8_XEXP", "S2SR_FP8_GEXP")
 _WORST = {}           # region -> (ratio, case), over the module's cases
 _COUNT = {"layers": 0, "cases": 0, "t0": None}
 
@@ -104,13 +102,7 @@ def shape_inputs(shape):
 
 
 def _fresh(monkeypatch, nc, env, sd):
-    for k in _SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    e = native.Engine(num_block=nc, precision=HP, arch="compact")
-    e.load_state_dict(sd)
-    return e
+    return gpu_engines.fresh(monkeypatch, env, nc, HP, arch="compact", sd=sd)
 
 
 def _note(title, rep, seen=()):
@@ -238,18 +230,8 @@ def test_off_grid_floats_at_network_level(nc, monkeypatch):
 
 
 # ---- 4. degenerate and changing shapes ---------------------------------------------------------------------------------------------
-_ENG = {}
-
-
 def _engine(nc):
-    if nc not in _ENG:
-        saved = {k: os.environ.pop(k) for k in _SWITCHES if k in os.environ}
-        try:
-            _ENG[nc] = native.Engine(num_block=nc, precision=HP, arch="compact")
-        finally:
-            os.environ.update(saved)
-        _ENG[nc].load_state_dict(W.synthetic_compact_state_dict(nc, seed=0))
-    return _ENG[nc]
+    return gpu_engines.default(nc, HP, arch="compact")
 
 
 @pytest.mark.parametrize("H,Wd", [(1, 1), (1, 7), (5, 1), (2, 3), (3, 33), (33, 2)])
@@ -344,5 +326,4 @@ def test_zz_summary():
         if r in _WORST:
             print(f"worst |err| / bound, {r}: {_WORST[r][0]:.3f} ({_WORST[r][1]})")
     assert all(v[0] <= 1.0 for v in _WORST.values())
-    for nc in list(_ENG):
-        _ENG.pop(nc).close()
+    gpu_engines.close_default(arch="compact")

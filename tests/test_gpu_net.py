@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_engines
 from oracle import rrdbnet_ref as ref
 from s2sr import native
 from s2sr.weights import synthetic_state_dict
@@ -25,27 +26,9 @@ TOL_FP8_STRESS = 3e-2
 TOL_FP8_6 = 1e-3
 
 
-_ENG = {}
-
-
-_SWITCHES = ("S2SR_SMALL8", "S2SR_F16_LOADER", "S2SR_MOSAIC", "S2SR_LO_EXP", "S2SR_TRUNK", "S2SR_FP8_LOADER", "S2SR_FP8_WSTREAM", "S2SR_FP8_W8", "S2SR_WINO", "S2SR_FP8_TAIL",
-             "S2SR_FP8_XEXP", "S2SR_FP8_GEXP", "S2SR_NO_SUBPIXEL", "S2SR_GRAPH", "S2SR_LAST_FOLD", "S2SR_TAIL_W4", "S2SR_D2H_STAGED", "S2SR_F16_FULL")
-
-
 def engine(nb, precision=native.PREC_F16, **kw):
-    """Cached DEFAULT-configuration engines.  s2sr_create reads every S2SR_* switch once, so the cache is filled with the
-    switches cleared, whatever a test has put into the environment: a cached handle never carries a test's setting."""
-    import os
-    key = (nb, precision, tuple(sorted(kw.items())))
-    if key not in _ENG:
-        saved = {k: os.environ.pop(k) for k in _SWITCHES if k in os.environ}
-        try:
-            e = native.Engine(num_block=nb, precision=precision)
-        finally:
-            os.environ.update(saved)
-        e.load_state_dict(synthetic_state_dict(nb, seed=0, **kw))
-        _ENG[key] = e
-    return _ENG[key]
+    """Cached DEFAULT-configuration engines (gpu_engines.default); kw: keyword arguments of the state dict."""
+    return gpu_engines.default(nb, precision, **kw)
 
 
 def test_g3_small_nets(golden_dir):
@@ -468,13 +451,7 @@ def test_hp_tolerance_holds_for_other_weight_draws(seed, gain):
 def _fresh(monkeypatch, nb, precision, env, **kw):
     """Every kernel-form / scale switch is read ONCE, in s2sr_create: a test of a switch must create its handle after
     setting it (never the module's engine() cache) and check that the handle took it (s2sr_debug_get_config)."""
-    for k in _SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    e = native.Engine(num_block=nb, precision=precision)
-    e.load_state_dict(synthetic_state_dict(nb, seed=0, **kw))
-    return e
+    return gpu_engines.fresh(monkeypatch, env, nb, precision, **kw)
 
 
 def test_trunk_lo_e4m3_scale_choices_and_ignored_switches(monkeypatch, golden_dir):

@@ -25,6 +25,7 @@ model against the fp64 conv of the true operands).
 import numpy as np
 import pytest
 
+import gpu_engines
 import tail_model as tm
 from s2sr import native
 from s2sr.weights import synthetic_state_dict
@@ -32,9 +33,6 @@ from s2sr.weights import synthetic_state_dict
 pytestmark = pytest.mark.gpu
 
 HP, FAST, FP8 = native.PREC_F16_HP, native.PREC_F16, native.PREC_FP8
-_SWITCHES = ("S2SR_SMALL8", "S2SR_F16_LOADER", "S2SR_MOSAIC", "S2SR_LO_EXP", "S2SR_TRUNK", "S2SR_FP8_LOADER", "S2SR_FP8_WSTREAM", "S2SR_FP8_W8",
-             "S2SR_WINO", "S2SR_FP8_TAIL", "S2SR_FP8_XEXP", "S2SR_FP8_GEXP", "S2SR_NO_SUBPIXEL", "S2SR_GRAPH", "S2SR_LAST_FOLD", "S2SR_TAIL_W4",
-             "S2SR_D2H_STAGED", "S2SR_F16_FULL", "S2SR_DIAG_NO_WLO")
 EXC_MAX = 1e-3      # fraction of elements allowed to differ in a stored field (all of them within tol of a rounding boundary)
 
 # shapes: (entry, B, th, tw, job_windows)
@@ -49,14 +47,8 @@ SHAPES = {
 
 
 def _engine(monkeypatch, precision, env, gain=1.0):
-    for k in _SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    e = native.Engine(num_block=1, precision=precision)
     sd = synthetic_state_dict(1, seed=0, other_gain=gain)
-    e.load_state_dict(sd)
-    return e, sd
+    return gpu_engines.fresh(monkeypatch, env, 1, precision, sd=sd), sd
 
 
 def _inputs(shape, seed=0):

@@ -21,6 +21,7 @@ ring, pixels next to a mosaic separator) and the exception rates; and the kernel
 import numpy as np
 import pytest
 
+import gpu_engines
 import trunk_model as tm
 from s2sr import native
 from s2sr.weights import synthetic_state_dict
@@ -28,9 +29,6 @@ from s2sr.weights import synthetic_state_dict
 pytestmark = pytest.mark.gpu
 
 HP, FAST, FP8 = native.PREC_F16_HP, native.PREC_F16, native.PREC_FP8
-_SWITCHES = ("S2SR_SMALL8", "S2SR_F16_LOADER", "S2SR_MOSAIC", "S2SR_LO_EXP", "S2SR_TRUNK", "S2SR_FP8_LOADER", "S2SR_FP8_WSTREAM", "S2SR_FP8_W8",
-             "S2SR_WINO", "S2SR_FP8_TAIL", "S2SR_FP8_XEXP", "S2SR_FP8_GEXP", "S2SR_NO_SUBPIXEL", "S2SR_GRAPH", "S2SR_LAST_FOLD", "S2SR_TAIL_W4",
-             "S2SR_D2H_STAGED", "S2SR_F16_FULL", "S2SR_DIAG_NO_WLO", "S2SR_F16_P64", "S2SR_F16_WGL")
 EXC_MAX = 1e-3      # fraction of the hi / growth / fp8-plane elements of a case allowed to differ (all within tol of a rounding boundary)
 # Capped per case and field kind (all the RDBs' fields of that kind together): one 16 x 32 field of 16k elements measured up to
 # 1.7e-3 on its own, the kinds together 5-8e-4.  Reported, not capped: the fp16 path's lo (its step near 0 is below the fp32
@@ -77,14 +75,8 @@ def _key(f):
 
 
 def _engine(monkeypatch, precision, env, nb, gain, other_gain=1.0):
-    for k in _SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    e = native.Engine(num_block=nb, precision=precision)
     sd = synthetic_state_dict(nb, seed=0, body_gain=gain, other_gain=other_gain)
-    e.load_state_dict(sd)
-    return e, sd
+    return gpu_engines.fresh(monkeypatch, env, nb, precision, sd=sd), sd
 
 
 def _inputs(shape, seed=0):

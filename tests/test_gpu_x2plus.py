@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_engines
 import tail_model as tm
 import x2plus_model as xm
 from oracle import postprocess_ref as pp
@@ -24,9 +25,6 @@ TOL_F16 = 2.5e-3
 TOL_HP = 3e-4
 TOL_FP8_23 = 1e-2
 HP, FAST, FP8 = native.PREC_F16_HP, native.PREC_F16, native.PREC_FP8
-_SWITCHES = ("S2SR_SMALL8", "S2SR_MOSAIC", "S2SR_LO_EXP", "S2SR_FP8_TAIL", "S2SR_GRAPH", "S2SR_F16_FULL", "S2SR_LAST_FOLD",
-             "S2SR_D2H_STAGED", "S2SR_FP8_XEXP", "S2SR_FP8_GEXP")
-_ENG = {}
 
 
 def _sd(nb):
@@ -37,30 +35,14 @@ def _tsd(nb):
     return ref.to_torch_sd(_sd(nb))
 
 
-def engine(nb, precision=HP, **kw):
+def engine(nb, precision=HP):
     """Cached default-configuration scale-2 engines (created with every S2SR_* switch cleared)."""
-    import os
-    key = (nb, precision, tuple(sorted(kw.items())))
-    if key not in _ENG:
-        saved = {k: os.environ.pop(k) for k in _SWITCHES if k in os.environ}
-        try:
-            e = native.Engine(num_block=nb, precision=precision, scale=2, **kw)
-        finally:
-            os.environ.update(saved)
-        e.load_state_dict(_sd(nb))
-        _ENG[key] = e
-    return _ENG[key]
+    return gpu_engines.default(nb, precision, scale=2)
 
 
 def _fresh(monkeypatch, nb, precision, env, **kw):
     """s2sr_create reads every switch once: a test of a switch creates its own handle after setting it."""
-    for k in _SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    e = native.Engine(num_block=nb, precision=precision, scale=2, **kw)
-    e.load_state_dict(_sd(nb))
-    return e
+    return gpu_engines.fresh(monkeypatch, env, nb, precision, scale=2, **kw)
 
 
 def _u8_close(a, b, frac=0.99):
