@@ -235,7 +235,11 @@ int  s2sr_postprocess_batch_u8_dev(s2sr_handle* h, const void* d_rgb, int32_t B,
  *          (a band is rewritten only after the CLAHE pass, which runs a blur radius ahead, has read it)
  * Same bytes as s2sr_postprocess_batch_u8_dev on the whole image.  order: S2SR_PP_ORDER_BGR = the bytes are B,G,R (what
  * RealESRGAN.enhance handles, wow_sr.py:85,94; the colour math is always RGB's); S2SR_PP_ORDER_SWAP_OUT = R and B exchanged in
- * the rows written (the job's cvtColor BGR2RGB, wow_sr.py:103, folded into the last pass).  One banded run per handle at a time. */
+ * the rows written (the job's cvtColor BGR2RGB, wow_sr.py:103, folded into the last pass).
+ * One banded run per handle at a time, and the handle enforces it: the run's histograms, LUTs and CLAHE'd rows live in a scratch area
+ * that s2sr_postprocess_u8, s2sr_postprocess_batch_u8_dev, an s2sr_enhance_job_u8 with post-process parameters, a multi-group
+ * s2sr_tiles_write_png and another begin also use.  Any of them on the same handle between begin and the last rows band ends the
+ * run: its next hist / lut / rows returns S2SR_E_INVALID and launches nothing (begin again). */
 #define S2SR_PP_ORDER_BGR      1
 #define S2SR_PP_ORDER_SWAP_OUT 2
 int  s2sr_pp_band_begin_dev(s2sr_handle* h, int32_t H, int32_t W, const s2sr_pp_params* prm, int32_t order, void* stream);

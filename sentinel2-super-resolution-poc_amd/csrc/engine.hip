@@ -372,6 +372,8 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
             Scope sc(h, st, F_MISC, 0.0, (double)n * w.Hp * w.Wp * (128.0 + 64.0));
             HIPCHK(h, launch_xh_to_fp8(w.Xh[0], 4 * w.blk1, n, w.Hp, w.Wp, xe, w.D8[0], 6 * w.blk1, st));
         }
+        if (h->d_calib)   // s2sr_calibrate_fp8: the trunk behind conv_first is stored at 2^x_exp too (the conversion above)
+            HIPCHK(h, launch_absmax_f16(w.Xh[0], (size_t)n * 4 * w.blk1 / 2, h->d_calib, st));
         for (int blk = 0; blk < nb; ++blk)
             for (int r = 0; r < 3; ++r) {
                 s2sr_debug_trunk_form* fo = nullptr;             // s2sr_debug_trunk_taps only
@@ -531,6 +533,7 @@ bool recover_stream(s2sr_handle* h) {
 int ensure_scratch(s2sr_handle* h, int slot, size_t bytes) {
     h->tiles_slot = -1;                  // whoever asks for scratch is about to overwrite it; the pyramid calls set it again
     h->warp_slot = -1;
+    if (slot == 5) h->ppb.open = false;  // ... and a banded post-process run lives there: void it (pp_band_begin_locked opens its own afterwards)
     if (h->scratch_bytes[slot] >= bytes) return S2SR_OK;
     if (h->d_scratch[slot]) {
         HIPCHK(h, hipStreamSynchronize(h->stream));

@@ -179,7 +179,7 @@ static int pp_band_begin_locked(s2sr_handle* h, int H, int W, const s2sr_pp_para
 
 static int pp_band_hist_locked(s2sr_handle* h, const void* d_img, int y0, int y1, hipStream_t st) {
     s2sr_handle::PPBand& b = h->ppb;
-    if (!b.open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_hist: no banded post-process open, or its LUTs are already built");
+    if (!b.open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_hist: no banded post-process open (none begun, or another call took its scratch area since: begin again), or its LUTs are already built");
     if (y0 < 0 || y1 > b.H || y0 > y1) return fail(h, S2SR_E_INVALID, "pp_band_hist: rows outside the image");
     Scope sc(h, st, F_POST, 0.0, (double)(y1 - y0) * b.W * 3.0);
     HIPCHK(h, launch_pp_band_hist((const uint8_t*)d_img, b.H, b.W, b.prm, b.bgr, y0, y1, h->d_scratch[5], st));
@@ -188,7 +188,7 @@ static int pp_band_hist_locked(s2sr_handle* h, const void* d_img, int y0, int y1
 
 static int pp_band_lut_locked(s2sr_handle* h, hipStream_t st) {
     s2sr_handle::PPBand& b = h->ppb;
-    if (!b.open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_lut: no banded post-process open, or its LUTs are already built");
+    if (!b.open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_lut: no banded post-process open (none begun, or another call took its scratch area since: begin again), or its LUTs are already built");
     HIPCHK(h, launch_pp_band_lut(b.H, b.W, b.prm, h->d_scratch[5], st));
     b.lut = true;
     return S2SR_OK;
@@ -196,7 +196,8 @@ static int pp_band_lut_locked(s2sr_handle* h, hipStream_t st) {
 
 static int pp_band_rows_locked(s2sr_handle* h, const void* d_img, int y0, int y1, void* d_out, hipStream_t st) {
     s2sr_handle::PPBand& b = h->ppb;
-    if (!b.open || !b.lut) return fail(h, S2SR_E_INVALID, "pp_band_rows: the LUTs are not built (begin, hist over every row, lut, then rows)");
+    if (!b.open || !b.lut) return fail(h, S2SR_E_INVALID, "pp_band_rows: no banded post-process open (none begun, or another call took its scratch area since: begin again), or its LUTs are not "
+                                                          "built (begin, hist over every row, lut, then rows)");
     if (y0 != b.rows_end || y1 <= y0 || y1 > b.H) return fail(h, S2SR_E_INVALID, "pp_band_rows: bands must follow each other from row 0");
     const int need = y1 + b.radius < b.H ? y1 + b.radius : b.H;     // the blur of row y1-1 reads R rows below it
     Scope sc(h, st, F_POST, 0.0, (double)(y1 - y0) * b.W * 6.0);
@@ -414,6 +415,9 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
                 nfin = (OH + fin_rows - 1) / fin_rows;
                 if ((rc = pp_band_begin_locked(h, OH, OW, prm, job_rgb ? 3 : 0, st))) return rc;   // (allocates: before anything is enqueued)
             }
+            // this job's run took scratch 5 from whatever run a caller had open there: it ends with the job on every way out, so
+            // that caller's next hist / lut / rows is refused
+            struct CloseRun { s2sr_handle* h; ~CloseRun() { if (h) h->ppb.open = false; } } close_run{prm ? h : nullptr};
             while ((int)h->group_done.size() < nchunks + nfin) {
                 hipEvent_t e;
                 HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));

@@ -193,6 +193,70 @@ def test_banded_postprocess_gives_the_bytes_of_the_whole_image(eng):
     torch.cuda.synchronize()
 
 
+@pytest.fixture(scope="module")
+def weng():
+    """a handle with weights (s2sr_enhance_job_u8 runs the net) whose scratch only ever serves 64 x 64 post-process work"""
+    from s2sr.weights import synthetic_state_dict
+    e = native.Engine(num_block=1)
+    e.load_state_dict(synthetic_state_dict(1, seed=0))
+    yield e
+    e.close()
+
+
+def _take_batch_dev(e, img, prm):
+    import torch
+    x = torch.from_numpy(np.ascontiguousarray(img[:40, :48])).cuda()
+    y = torch.empty_like(x)
+    e.postprocess_batch_u8_dev(x.data_ptr(), 1, 40, 48, prm, y.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+
+
+# calls that take the scratch area a banded run keeps its histograms, LUTs and CLAHE'd rows in.  Each works on the run's 64 x 64
+# pixels or fewer (an enhance job's output is 4 x its input), so the area is never regrown.
+_TAKERS = {
+    "postprocess_u8": lambda e, img, prm: e.postprocess_u8(img, prm),
+    "postprocess_batch_u8_dev": _take_batch_dev,
+    "enhance_job_u8": lambda e, img, prm: e.enhance_job_u8(img[:16, :16], prm),
+}
+
+
+@pytest.mark.parametrize("taker", list(_TAKERS))
+def test_banded_run_is_void_once_its_scratch_is_taken(weng, taker):
+    """Another post-process on the handle between begin and the last rows band overwrites the run's state: the run's next call must
+    fail (it used to pass `open && !lut` and answer with wrong bytes), and a complete run afterwards gives the whole image's bytes."""
+    import torch
+    rng = np.random.default_rng(47)
+    img = rng.integers(0, 256, (64, 64, 3), dtype=np.uint8)
+    img[..., 1] = np.maximum(img[..., 1], 90)
+    prm = native.pp_wow()
+    want = weng.postprocess_u8(img, prm)
+    assert np.array_equal(want, pp.enhance_for_crops(img))
+    x = torch.from_numpy(img).cuda()
+    y = torch.empty_like(x)
+    st = torch.cuda.current_stream().cuda_stream
+    # taken while the histograms are being counted
+    weng.pp_band_begin_dev(64, 64, prm, 0, st)
+    weng.pp_band_hist_dev(x.data_ptr(), 0, 32, st)
+    torch.cuda.synchronize()
+    _TAKERS[taker](weng, img, prm)
+    with pytest.raises(native.S2srError, match="took its scratch"):
+        weng.pp_band_hist_dev(x.data_ptr(), 32, 64, st)
+    with pytest.raises(native.S2srError, match="took its scratch"):
+        weng.pp_band_lut_dev(st)
+    assert np.array_equal(_banded(weng, img, prm, [0, 32, 64], [0, 32, 64]), want)
+    # taken between two finishing bands
+    weng.pp_band_begin_dev(64, 64, prm, 0, st)
+    weng.pp_band_hist_dev(x.data_ptr(), 0, 64, st)
+    weng.pp_band_lut_dev(st)
+    weng.pp_band_rows_dev(x.data_ptr(), 0, 32, y.data_ptr(), st)
+    torch.cuda.synchronize()
+    _TAKERS[taker](weng, img, prm)
+    with pytest.raises(native.S2srError, match="took its scratch"):
+        weng.pp_band_rows_dev(x.data_ptr(), 32, 64, y.data_ptr(), st)
+    torch.cuda.synchronize()
+    assert np.array_equal(_banded(weng, img, prm, [0, 32, 64], [0, 32, 64]), want)
+
+
 def test_gpu_against_cv2_golden(eng, golden_dir):
     """With tests/golden/g9_cv2_postprocess.npz present (tools/make_cv2_golden.py, run where cv2 is installed): the HIP
     post-process against OpenCV's own output of the reference's call chain, end to end, within 2 LSB per byte at >= 99 % of the
