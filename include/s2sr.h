@@ -88,11 +88,16 @@ typedef struct s2sr_window {
     int32_t oy1, oy2, ox1, ox2;         /* paste rectangle in the output image                 */
 } s2sr_window;
 
-/* Constants of the crop-visibility post-process (wow_sr.py:187-209 / farm_sr.py:61-108,170-178). */
+/* Constants of the crop-visibility post-process (wow_sr.py:187-209 / farm_sr.py:61-108,170-178).
+ * Supported range: clahe_grid 1..64; with the unsharp stage (bit1) 0 < blur_sigma < 2.75.  OpenCV's kernel for sigma is
+ * cvRound(6 sigma + 1) | 1 taps wide and the device's holds 17; a wider one is not cut short: every entry that takes these
+ * parameters (s2sr_postprocess_u8, s2sr_postprocess_batch_u8_dev, s2sr_pp_band_begin_dev, s2sr_enhance_job_u8) returns
+ * S2SR_E_INVALID, s2sr_last_error names the limit, and nothing is computed.  A sigma below 1/12 gives the 1-tap kernel: the blur is
+ * the image and the weighted sum img * (w_img + w_blur) is still taken, as addWeighted does.  clahe_clip <= 0 turns clipping off. */
 typedef struct s2sr_pp_params {
     float   clahe_clip;      /* cv2.createCLAHE clipLimit: 2.5                     */
-    int32_t clahe_grid;      /* tileGridSize (g,g): 8                              */
-    float   blur_sigma;      /* GaussianBlur sigma: 1.2 (wow) / 1.5 (farm)         */
+    int32_t clahe_grid;      /* tileGridSize (g,g): 8; 1..64                       */
+    float   blur_sigma;      /* GaussianBlur sigma: 1.2 (wow) / 1.5 (farm); < 2.75 */
     float   w_img;           /* addWeighted alpha: 1.4 (wow) / 2.2 (farm)          */
     float   w_blur;          /* addWeighted beta: -0.4 (wow) / -1.2 (farm)         */
     int32_t hue_lo, hue_hi;  /* exclusive hue bounds of the green mask: 35, 85     */

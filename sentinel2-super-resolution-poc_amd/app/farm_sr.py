@@ -17,9 +17,17 @@ from s2sr import native
 
 
 def apply_unsharp_mask(img: np.ndarray, strength: float = 1.5, radius: float = 1.0) -> np.ndarray:
-    """addWeighted(img, 1+s, GaussianBlur(img, sigma=radius), -s) (farm_sr.py:61-71)."""
+    """addWeighted(img, 1+s, GaussianBlur(img, sigma=radius), -s) (farm_sr.py:61-71).
+
+    0 < radius < 2.75 (the reference calls it with 1.0 and 1.5): the device's Gaussian kernel holds 17 taps, OpenCV's for a larger
+    sigma is wider, and the library refuses to answer with a kernel cut short -- S2srError, with the library's text."""
     p = native.PPParams(0.0, 8, float(radius), 1.0 + float(strength), -float(strength), 35, 85, 1.0, 2)
-    return _pp_engine().postprocess_u8(img, p)
+    try:
+        return _pp_engine().postprocess_u8(img, p)
+    except native.S2srError as e:
+        if "blur_sigma" in str(e):
+            raise native.S2srError(f"apply_unsharp_mask(radius={radius}): {e}") from e
+        raise
 
 
 def enhance_local_contrast(img: np.ndarray, clip_limit: float = 3.0, grid_size: int = 8) -> np.ndarray:

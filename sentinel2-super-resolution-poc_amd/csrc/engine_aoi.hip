@@ -144,6 +144,7 @@ static void build_stitch_maps(const std::vector<s2sr_window>& wins, int nx, int 
 // post-process on device buffers; the caller holds h->mu
 static int postprocess_dev_locked(s2sr_handle* h, const void* d_rgb, int32_t B, int32_t H, int32_t W, const s2sr_pp_params* prm,
                                   void* d_out, hipStream_t st) {
+    if (const char* why = pp_params_error(*prm)) return fail(h, S2SR_E_INVALID, why);
     const size_t wb = postprocess_work_bytes(B, H, W, *prm);
     int rc = ensure_scratch(h, 5, wb);
     if (rc) return rc;
@@ -163,7 +164,10 @@ int s2sr_postprocess_batch_u8_dev(s2sr_handle* h, const void* d_rgb, int32_t B, 
 // ---- the post-process over one device image in row bands (see postprocess.hip launch_pp_band_*) -------------------------------
 // order: S2SR_PP_ORDER_BGR = the image's bytes are B,G,R; S2SR_PP_ORDER_SWAP_OUT = R and B exchanged in the rows written
 static int pp_band_begin_locked(s2sr_handle* h, int H, int W, const s2sr_pp_params* prm, int order, hipStream_t st) {
-    if (prm->clahe_grid <= 0 || prm->clahe_grid > 64) return fail(h, S2SR_E_INVALID, "clahe_grid must be 1..64");
+    if (const char* why = pp_params_error(*prm)) {
+        h->ppb.open = false;           // a refused begin leaves no run behind, the caller's earlier one included
+        return fail(h, S2SR_E_INVALID, why);
+    }
     int rc = ensure_scratch(h, 5, postprocess_work_bytes(1, H, W, *prm));
     if (rc) return rc;
     s2sr_handle::PPBand& b = h->ppb;
@@ -278,6 +282,8 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
     if (!h || !img || (!out_u8 && !out_f32) || H <= 0 || W <= 0 || tile <= 0 || pad < 0) return S2SR_E_INVALID;
     if ((job_rgb || prm) && !out_u8) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
+    if (prm)                                                  // before the net runs, not behind it
+        if (const char* why = pp_params_error(*prm)) return fail(h, S2SR_E_INVALID, why);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = h->stream;
     int rc, PH, PW;

@@ -442,7 +442,7 @@ constexpr int ST = 32;          // output tile edge
 constexpr int MAXR = 8;         // max Gaussian radius (ksize <= 17)
 struct SharpParams {
     int H, W, B;
-    int radius;                 // taps = 2*radius+1, 0 = no blur stage
+    int radius;                 // taps = 2*radius+1; 0 with taps[0] == 0: no unsharp stage, 0 with taps[0] == 256: its 1-tap kernel
     int taps[2 * MAXR + 1];     // 8.8 fixed point, sum 256
     float w_img, w_blur;
     int do_veg, hue_lo, hue_hi;
@@ -504,6 +504,9 @@ __global__ void __launch_bounds__(256) sharpen_veg_kernel(const uint8_t* __restr
                 for (int k = 0; k <= 2 * r; ++k) acc += (uint32_t)sp.taps[k] * s_h[((ly + k) * ST + lx) * 3 + c];
                 const int blur = clamp255((int)((acc + (1u << 15)) >> 16));
                 px[c] = sat_round((float)center * sp.w_img + (float)blur * sp.w_blur);
+            } else if (sp.taps[0]) {
+                // unsharp stage with a 1-tap kernel (sigma < 1/12): the blur is the image itself, addWeighted still runs
+                px[c] = sat_round((float)center * sp.w_img + (float)center * sp.w_blur);
             } else {
                 px[c] = center;
             }
@@ -665,7 +668,7 @@ __global__ void __launch_bounds__(256) sharpen_veg_kernel_r(const uint8_t* __res
 
 void gaussian_taps_q8(double sigma, int& radius, int* taps) {
     int n = ((int)rint(sigma * 6 + 1)) | 1;
-    if (n > 2 * MAXR + 1) n = 2 * MAXR + 1;
+    if (n > 2 * MAXR + 1) n = 2 * MAXR + 1;   // (never taken: the entries refuse such a sigma, pp_params_error)
     radius = n / 2;
     std::vector<double> k(n);
     double sum = 0;
@@ -708,6 +711,17 @@ ClaheGeom clahe_geom(int H, int W, const s2sr_pp_params& prm) {
 
 }  // namespace
 
+// Why the kernels do not compute `prm`, or nullptr.  OpenCV's kernel for sigma is cvRound(6 sigma + 1) | 1 taps wide; past
+// 2 * MAXR + 1 = 17 taps (6 sigma + 1 >= 17.5, which rounds to 18) the device would have to cut it short, so every entry refuses.
+const char* pp_params_error(const s2sr_pp_params& prm) {
+    if (prm.clahe_grid <= 0 || prm.clahe_grid > 64) return "clahe_grid must be 1..64";
+    constexpr float sigma_end = (2 * MAXR + 0.5f) / 6.0f;   // 2.75, exact in float
+    if ((prm.stages & 2) && !(prm.blur_sigma > 0.0f && prm.blur_sigma < sigma_end))
+        return "blur_sigma must be > 0 and < 2.75 when the unsharp stage is on: the Gaussian kernel, cvRound(6 sigma + 1) | 1 taps, "
+               "may be at most 17 taps wide";
+    return nullptr;
+}
+
 size_t postprocess_work_bytes(int B, int H, int W, const s2sr_pp_params& prm) {
     const size_t tiles = (size_t)B * prm.clahe_grid * prm.clahe_grid;
     return tiles * 256 * 4 + tiles * 256 + (size_t)B * H * W * 3 + 1024;
@@ -715,7 +729,7 @@ size_t postprocess_work_bytes(int B, int H, int W, const s2sr_pp_params& prm) {
 
 hipError_t launch_postprocess(const uint8_t* d_rgb, int B, int H, int W, const s2sr_pp_params& prm, uint8_t* d_out,
                               void* d_work, size_t work_bytes, hipStream_t st) {
-    if (prm.clahe_grid <= 0 || prm.clahe_grid > 64) return hipErrorInvalidValue;
+    if (pp_params_error(prm)) return hipErrorInvalidValue;
     if (work_bytes < postprocess_work_bytes(B, H, W, prm)) return hipErrorInvalidValue;
     PPTables* t = nullptr;
     hipError_t e = get_tables(&t);
@@ -797,7 +811,7 @@ int pp_band_radius(const s2sr_pp_params& prm) {
 }
 
 hipError_t launch_pp_band_begin(int H, int W, const s2sr_pp_params& prm, void* d_work, hipStream_t st) {
-    if (prm.clahe_grid <= 0 || prm.clahe_grid > 64 || H <= 0 || W <= 0) return hipErrorInvalidValue;
+    if (pp_params_error(prm) || H <= 0 || W <= 0) return hipErrorInvalidValue;
     if (!(prm.stages & 1)) return hipSuccess;
     return hipMemsetAsync(d_work, 0, (size_t)prm.clahe_grid * prm.clahe_grid * 256 * 4, st);
 }

@@ -315,6 +315,8 @@ hipError_t launch_stitch_f32(const float* d_tiles /*[T,3,oth,otw]*/, int tilesX,
 hipError_t launch_postprocess(const uint8_t* d_rgb, int B, int H, int W, const s2sr_pp_params& prm, uint8_t* d_out,
                               void* d_work, size_t work_bytes, hipStream_t st);
 size_t postprocess_work_bytes(int B, int H, int W, const s2sr_pp_params& prm);
+// nullptr, or why `prm` is refused (clahe_grid outside 1..64; unsharp stage with a sigma whose kernel is wider than the device's 17 taps)
+const char* pp_params_error(const s2sr_pp_params& prm);
 // ... over ONE image in row bands (an AOI's mosaic arrives band by band; CLAHE's grid is image-global): histograms as the bands
 // arrive, LUTs once, then apply (R rows ahead) + sharpen band by band.  d_work = postprocess_work_bytes(1, H, W, prm) bytes; bgr:
 // the image's bytes are B,G,R; swap_out: R and B exchanged in the rows written.  Same bytes as launch_postprocess.

@@ -245,12 +245,62 @@ def test_gaussian_blur_tracks_the_float_definition():
         assert d.max() <= 1.6 and d.mean() <= 0.45, (sigma, float(d.max()), float(d.mean()))
 
 
+# ---- where tests/test_gpu_postprocess_params.py leans on the oracle outside the product's parameter sets --------------------------
+@pytest.mark.parametrize("sigma", [0.3, 0.5, 0.84, 2.0, 2.3, 2.7, 3.0])
+def test_gaussian_taps_at_other_sigmas(sigma):
+    """ksize = cvRound(6 sigma + 1) | 1 taps, symmetric, non-negative, sum exactly 256, each within one unit of the documented
+    getGaussianKernel value 256 exp(-x^2 / 2 sigma^2) / sum (the property test_gaussian_fixed_point_taps_are_pinned holds at the
+    product's three sigmas)."""
+    n = int(np.rint(6 * sigma + 1)) | 1
+    assert n == {0.3: 3, 0.5: 5, 0.84: 7, 2.0: 13, 2.3: 15, 2.7: 17, 3.0: 19}[sigma]
+    t = pp.gaussian_kernel_q8(sigma)
+    x = np.arange(n) - (n - 1) / 2
+    w = np.exp(-x * x / (2 * sigma * sigma))
+    w = w / w.sum() * 256.0
+    assert len(t) == n and t.sum() == 256 and np.array_equal(t, t[::-1]) and t.min() >= 0
+    assert np.all(np.abs(t - w) <= 1.0), (sigma, t.tolist(), w.round(2).tolist())
+
+
+def _global_equalise(plane):
+    """Histogram equalisation of a whole plane: lut = rint(cdf * 255 / area), in float32 as clahe.cpp scales it."""
+    cdf = np.cumsum(np.bincount(plane.ravel(), minlength=256))
+    lut = np.clip(np.rint(cdf.astype(np.float32) * (np.float32(255.0) / np.float32(plane.size))), 0, 255).astype(np.uint8)
+    return lut[plane]
+
+
+def test_clahe_one_tile_no_clip_is_global_equalisation():
+    """At grid 1 every size divides, so nothing is padded, and all four neighbours of every pixel are the one tile, so the
+    interpolation returns that tile's LUT whatever the weights (they sum to 1, the four values are equal).  What is left of
+    clahe.cpp is the histogram, the running sum and the 255 / area scale: an independent statement of the CLAHE core."""
+    rng = np.random.default_rng(21)
+    for H, W in ((64, 64), (70, 101)):
+        plane = np.minimum(rng.integers(0, 256, (H, W)), rng.integers(0, 256, (H, W))).astype(np.uint8)    # skewed: equalising moves it
+        want = _global_equalise(plane)
+        assert not np.array_equal(want, plane)
+        assert np.array_equal(pp.clahe_u8(plane, 0.0, 1), want), (H, W)
+
+
+@pytest.mark.parametrize("grid", [1, 3, 8, 16])
+def test_clahe_clip_above_the_largest_bin_changes_nothing(grid):
+    """clip >= tile area: no bin can exceed it, nothing is cut or redistributed -> the bytes of clip 0 (clipping off)."""
+    rng = np.random.default_rng(22)
+    for H, W in ((64, 64), (70, 101)):
+        plane = rng.integers(0, 256, (H, W), dtype=np.uint8)
+        eh, ew = (H, W) if H % grid == 0 and W % grid == 0 else (H + grid - H % grid, W + grid - W % grid)
+        area = (eh // grid) * (ew // grid)
+        clip_limit = 257.0                                  # clip = int(clip_limit * area / 256) >= area
+        assert int(clip_limit * area / 256) >= area
+        assert np.array_equal(pp.clahe_u8(plane, clip_limit, grid), pp.clahe_u8(plane, 0.0, grid)), (H, W)
+
+
 def test_oracle_against_cv2_golden(golden_dir):
     """The pin this oracle lacks (no cv2 in the build image, no reference-held fixture): when someone with an
     OpenCV wheel has run tools/make_cv2_golden.py, tests/golden/g9_cv2_postprocess.npz holds every stage of the reference's
     cv2 call chain (wow_sr.py:190-207, farm_sr.py:66-106) on this repo's test images and on the reference's own upload.  Each
     oracle stage is then fed cv2's own previous stage (so a difference is not carried along) and must agree within 2 LSB; the
-    exact-match rate per stage is printed.  Skipped when the file is absent -- the oracle then stays "parity unpinned"."""
+    exact-match rate per stage is printed.  A file that also holds the tool's `extra_index` (single stages at the parameter sets of
+    tests/test_gpu_postprocess_params.py: kernel widths 1..19, CLAHE grids 1..64 and clip limits 0..1000, hue bounds, gains) has
+    each of those checked the same way.  Skipped when the file is absent -- the oracle then stays "parity unpinned"."""
     f = golden_dir / "g9_cv2_postprocess.npz"
     if not f.exists():
         pytest.skip("no cv2 golden (run tools/make_cv2_golden.py where opencv-contrib-python>=4.8.0 is installed)")
@@ -286,3 +336,22 @@ def test_oracle_against_cv2_golden(golden_dir):
             d = np.abs(end.astype(np.int16) - ref["final"].astype(np.int16))
             print(f"cv2 {name}/{tag}/end-to-end: max |d| {int(d.max())}, identical {np.mean(d == 0):.5f}")
     print("worst per stage:", worst)
+    if "extra_index" not in g.files:        # a file made before the tool recorded the sets outside the product's two
+        return
+    import json
+    for e in json.loads(str(g["extra_index"])):
+        img = g[e["key"].split(".")[0] + ".img"]
+        if e["kind"] == "blur":
+            got = pp.gaussian_blur_u8(img, e["sigma"])
+        elif e["kind"] == "sharp":
+            got = pp.add_weighted_u8(img, e["w_img"], g[e["blur"]], e["w_blur"])
+        elif e["kind"] == "clahe":
+            got = pp.clahe_u8(g[e["plane"]], e["clip"], e["grid"])
+        else:
+            h = g[e["hsv"]].astype(np.float32)
+            mask = (h[..., 0] > e["hue_lo"]) & (h[..., 0] < e["hue_hi"])
+            h[..., 1] = np.where(mask, np.clip(h[..., 1] * np.float32(e["gain"]), 0, 255), h[..., 1])
+            got = pp.hsv2rgb_u8(h.astype(np.uint8))
+        d = np.abs(got.astype(np.int16) - g[e["key"]].astype(np.int16))
+        print(f"cv2 {g['cv2_version']} {e}: max |d| {int(d.max())}, identical {np.mean(d == 0):.5f}")
+        assert d.max() <= 2, (e, int(d.max()))

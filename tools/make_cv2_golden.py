@@ -12,6 +12,7 @@ tests/test_gpu_postprocess.py::test_gpu_against_cv2_golden does the same for the
     python tools/make_cv2_golden.py
 
 Nothing of the reference is imported: the calls are restated here with the constants cited."""
+import json
 import sys
 from pathlib import Path
 
@@ -67,6 +68,47 @@ def stages(cv2, img, clip, grid, sigma, w_img, w_blur, gain):
     return s
 
 
+# Parameter sets outside the product's two, as tests/test_gpu_postprocess_params.py uses them: every kernel width the device
+# computes (and 19 taps, which it refuses: the oracle alone is held to it), CLAHE grids and clip limits, hue bounds and gains.
+EXTRA_IMAGE = "ragged"          # one small image: these sets add about 1 MB before compression
+EXTRA_SIGMAS = (0.05, 0.3, 0.5, 0.84, 2.0, 2.3, 2.7, 3.0)
+EXTRA_WEIGHTS = ((2.5, -1.5), (2.0, 0.0))
+EXTRA_GRIDS = (1, 2, 3, 4, 7, 16, 64)
+EXTRA_CLIPS = (2.5, 0.0, 0.01, 40.0, 1000.0)
+EXTRA_HUES = ((0, 180), (-1, 180), (100, 20), (84, 86))
+EXTRA_GAINS = (0.0, 2.5, -1.0)
+
+
+def extra_sets(cv2, img):
+    """-> (arrays, index): single cv2 stages at the sets above, each on cv2's own input, and a JSON index that says for every
+    key which call made it (test_oracle_against_cv2_golden replays the index; a file without it is checked as before)."""
+    arrays, index = {}, []
+    pre = f"{EXTRA_IMAGE}.extra"
+    for i, sigma in enumerate(EXTRA_SIGMAS):
+        blur = cv2.GaussianBlur(img, (0, 0), sigma)
+        arrays[f"{pre}.blur{i}"] = blur
+        index.append({"key": f"{pre}.blur{i}", "kind": "blur", "sigma": sigma})
+        for j, (a, b) in enumerate(EXTRA_WEIGHTS):
+            arrays[f"{pre}.sharp{i}_{j}"] = cv2.addWeighted(img, a, blur, b, 0)
+            index.append({"key": f"{pre}.sharp{i}_{j}", "kind": "sharp", "blur": f"{pre}.blur{i}", "w_img": a, "w_blur": b})
+    L = cv2.cvtColor(img, cv2.COLOR_RGB2LAB)[:, :, 0].copy()
+    arrays[f"{pre}.L"] = L
+    for grid in EXTRA_GRIDS:
+        for j, clip in enumerate(EXTRA_CLIPS):
+            arrays[f"{pre}.clahe{grid}_{j}"] = cv2.createCLAHE(clipLimit=clip, tileGridSize=(grid, grid)).apply(L)
+            index.append({"key": f"{pre}.clahe{grid}_{j}", "kind": "clahe", "plane": f"{pre}.L", "clip": clip, "grid": grid})
+    hsv = cv2.cvtColor(img, cv2.COLOR_RGB2HSV)
+    arrays[f"{pre}.hsv"] = hsv
+    for i, (lo, hi) in enumerate(EXTRA_HUES):
+        for j, gain in enumerate(EXTRA_GAINS):
+            h = hsv.astype(np.float32)
+            mask = (h[:, :, 0] > lo) & (h[:, :, 0] < hi)
+            h[:, :, 1] = np.where(mask, np.clip(h[:, :, 1] * gain, 0, 255), h[:, :, 1])
+            arrays[f"{pre}.veg{i}_{j}"] = cv2.cvtColor(h.astype(np.uint8), cv2.COLOR_HSV2RGB)
+            index.append({"key": f"{pre}.veg{i}_{j}", "kind": "veg", "hsv": f"{pre}.hsv", "hue_lo": lo, "hue_hi": hi, "gain": gain})
+    return arrays, index
+
+
 def main():
     try:
         import cv2
@@ -78,6 +120,9 @@ def main():
         for tag, prm in (("wow", (2.5, 8, 1.2, 1.4, -0.4, 1.2)), ("farm", (2.5, 8, 1.5, 2.2, -1.2, 1.3))):
             for k, v in stages(cv2, img, *prm).items():
                 out[f"{name}.{tag}.{k}"] = v
+    arrays, index = extra_sets(cv2, images()[EXTRA_IMAGE])
+    out.update(arrays)
+    out["extra_index"] = np.array(json.dumps(index))
     GOLDEN.mkdir(parents=True, exist_ok=True)
     np.savez_compressed(GOLDEN / "g9_cv2_postprocess.npz", **out)
     print(f"wrote {GOLDEN / 'g9_cv2_postprocess.npz'} with OpenCV {cv2.__version__}: {len(out) - 1} arrays")
