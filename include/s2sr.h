@@ -197,6 +197,33 @@ int  s2sr_enhance_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W,
 int  s2sr_tile_process_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W,
                            int32_t tile, int32_t pad, float* out);
 
+/* The 16-bit door: uint16 samples in, uint16 x4 out, no 8-bit squeeze (upstream RealESRGANer's max_range = 65535 branch; the
+ * reference quantises its rasters to 8 bits first, so there is no reference to be byte-equal to here).  A call carries a value
+ * range lo, hi (0 <= lo < hi <= 65535; 0, 65535 is upstream's rule):
+ *   in :  d = clamp(v, lo, hi) - lo, the net sees x = d / (hi - lo) -- exactly: d reaches conv_first as two exact fp16 integers
+ *         (d & 255, d & 0xff00) against a doubled weight set, the 1 / (hi - lo) lives in conv_first as the u8 door's 1 / 255 does
+ *   out:  q = lo + rint(clamp(y, 0, 1) * (hi - lo)), the product taken in fp32 and rounded once, rint to nearest even; numpy:
+ *         lo + np.rint(np.clip(y, 0, 1).astype(np.float32) * np.float32(hi - lo)).astype(np.int64).  (Rounds, where the u8 door
+ *         truncates: truncation is the reference's quirk and stays with the u8 door.)
+ * For data with d < 256 the float output is bit-identical to the u8 door's on the same values.  x4 RRDB handles of every
+ * precision; S2SR_E_INVALID (text in s2sr_last_error) for a bad range, a scale-2 handle or an S2SR_ARCH_COMPACT handle,
+ * S2SR_E_NOWEIGHTS before weights are loaded.  The u8 door is untouched and may be mixed freely with this one on one handle.
+ *
+ * s2sr_forward_batch_u16: [B,th,tw,3] u16 -> out_u16 [B,4th,4tw,3] u16 and / or out_f32 [B,3,4th,4tw] fp32 (the unquantised net
+ * output); at least one of the two. */
+int  s2sr_forward_batch_u16(s2sr_handle* h, const uint16_t* tiles, int32_t B, int32_t th, int32_t tw, int32_t lo, int32_t hi,
+                            uint16_t* out_u16 /* [B,4th,4tw,3] or NULL */, float* out_f32 /* [B,3,4th,4tw] or NULL */);
+/* same with device-resident input / output, asynchronous on `stream` (NULL = the default stream).  The fp32 tiles between the
+ * net and the quantiser live in a scratch buffer of the handle: 48 B per output pixel, regrown when a larger batch arrives. */
+int  s2sr_forward_batch_u16_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int32_t th, int32_t tw, int32_t lo, int32_t hi,
+                                void* d_out_u16, void* stream);
+/* RealESRGAN.enhance for a 16-bit raster: HxWx3 u16 -> out_u16 [4H,4W,3] u16 and / or out_f32 [4H,4W,3] fp32 (the unquantised
+ * image, HWC), channel order as given; the whole / tiled switch, the window plan and the paste order of s2sr_enhance_u8.  The
+ * windows leave the net as fp32 tiles (12 B per output pixel written and read again, against the u8 door's 3), one chunk of
+ * window rows at a time; a fused crop + paste + quantise kernel writes each chunk's band of final rows. */
+int  s2sr_enhance_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
+                      uint16_t* out_u16 /* [4H,4W,3] or NULL */, float* out_f32 /* [4H,4W,3] or NULL */);
+
 /* Multi-GPU building blocks of _tile_process (cnn_super_resolution.py:244-278), device-resident:
  * cut windows [first, first+count) of the plan into d_tiles [count, wh, ww, 3] (wh/ww = the
  * plan's common window size), and paste ALL T windows' outputs d_tiles [T, 4wh, 4ww, 3] into

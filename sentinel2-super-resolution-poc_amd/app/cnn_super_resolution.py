@@ -366,6 +366,22 @@ class RealESRGAN:
             raise TypeError(f"expected uint8 image, got {img.dtype}")
         return self._engine.enhance_u8(img, tile=self.tile_size, pad=self.tile_pad)
 
+    def enhance16(self, img: np.ndarray, value_range=None) -> np.ndarray:
+        """HxWx3 uint16 (channel order as given) -> 4Hx4Wx3 uint16, in the source's units: the 16-bit door of the native library
+        (upstream RealESRGANer's max_range = 65535 branch; the reference has none).  value_range (lo, hi), None = (0, 65535): the
+        net sees (clip(v, lo, hi) - lo) / (hi - lo), the output is lo + rint(clip(y, 0, 1) * (hi - lo)).  Same whole / tiled
+        switch and window plan as `enhance`.  The x4 RRDB models only (realesrgan_x4, realesrgan_anime)."""
+        if self.scale != 4 or getattr(self.model, "arch", "rrdb") != "rrdb":
+            raise ValueError(f"enhance16 is built for the x4 RRDB models, not {self.model_name}")
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"expected HxWx3 image, got shape {img.shape}")
+        if img.dtype != np.uint16:
+            raise TypeError(f"expected uint16 image, got {img.dtype}")
+        lo, hi = (0, 65535) if value_range is None else (int(value_range[0]), int(value_range[1]))
+        if not (0 <= lo < hi <= 65535):
+            raise ValueError(f"value_range {value_range}: need 0 <= lo < hi <= 65535")
+        return self._engine.enhance_u16(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
+
     def enhance_job(self, rgb: np.ndarray, post=None) -> np.ndarray:
         """What a job does around `enhance` (wow_sr.py:85-110, farm_sr.py:156-178) in one native call: RGB in, RGB2BGR, the net,
         BGR2RGB, the crop-visibility post-process `post` (native.pp_wow() / pp_farm(); None: none), RGB out.  The same bytes as

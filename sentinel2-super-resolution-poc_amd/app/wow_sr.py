@@ -35,10 +35,65 @@ def _enhance_for_crops(img: np.ndarray) -> np.ndarray:
     return _pp_engine().postprocess_u8(img, native.pp_wow())
 
 
-def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True,
-                 model: str = "realesrgan_x4") -> Tuple[Path, dict]:
-    """Reference wow_sr.py:28-184 -- same outputs (GeoTIFF and/or PNG) and metadata dict."""
+def _apply_wow_sr16(input_path: Path, output_path: Path, model: str) -> Tuple[Path, dict]:
+    """bit_depth=16 of apply_wow_sr: a uint16 GeoTIFF read raw, value_range = the image's own (min, max) -- the reference's
+    min-max (wow_sr.py:67-73) minus its quantisation to 8 bits -- the net fed BGR as ever (:85,94), RealESRGAN.enhance16, RGB back,
+    a uint16 GeoTIFF out.  No PNG (the encoder is 8-bit) and no crop-visibility post-process (OpenCV's 8-bit arithmetic)."""
     from s2sr import rasterio_lite as rio
+
+    input_path = Path(input_path)
+    print(f"\nWOW Super-Resolution ({model}, 16-bit)\n   Input: {input_path}")
+    try:
+        img, georef = rio.read_rgb_raw(input_path)
+    except ValueError as e:
+        raise ValueError(f"bit_depth=16 needs a uint16 GeoTIFF: {e}") from e
+    if img.dtype != np.uint16:
+        raise ValueError(f"bit_depth=16 needs a uint16 GeoTIFF, {input_path} holds {img.dtype}")
+    lo, hi = int(img.min()), int(img.max())
+    if hi == lo:                      # a constant raster: any range that contains it
+        lo, hi = (lo - 1, hi) if hi > 0 else (0, 1)
+    esrgan = RealESRGAN(model_name=model, tile_size=256)
+    out_bgr = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi))
+    output_rgb = np.ascontiguousarray(out_bgr[:, :, ::-1])
+    scale = esrgan.scale
+    del esrgan
+    final_output = Path(output_path).with_suffix(".tif")
+    final_output.parent.mkdir(parents=True, exist_ok=True)
+    rio.write_geotiff_rgb16(final_output, output_rgb, georef.scaled(scale))
+    metadata = {
+        "input_file": str(input_path),
+        "output_file": str(final_output),
+        "scale": scale,
+        "pipeline": "Real-ESRGAN x4 (16-bit)",
+        "stages": [{"model": model, "scale": scale, "purpose": "GAN upscaling"}],
+        "enhancements": [],
+        "original_size": list(img.shape[:2]),
+        "output_size": list(output_rgb.shape[:2]),
+        "original_resolution_m": 10.0,
+        "effective_resolution_m": 10.0 / scale,
+        "optimized_for": "z18_crop_visibility",
+        "bit_depth": 16,
+        "value_range": [lo, hi],
+    }
+    return final_output, metadata
+
+
+def _check_bit_depth(bit_depth: int, enhance_crops: bool) -> None:
+    if bit_depth not in (8, 16):
+        raise ValueError(f"bit_depth {bit_depth!r}: 8 or 16")
+    if bit_depth == 16 and enhance_crops:
+        raise ValueError("bit_depth=16 has no crop-visibility post-process (it is OpenCV's 8-bit arithmetic by definition): pass enhance_crops=False")
+
+
+def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True,
+                 model: str = "realesrgan_x4", bit_depth: int = 8) -> Tuple[Path, dict]:
+    """Reference wow_sr.py:28-184 -- same outputs (GeoTIFF and/or PNG) and metadata dict.  bit_depth=16 (not in the reference): a
+    uint16 GeoTIFF goes through the net without the 8-bit squeeze and comes back as a uint16 GeoTIFF (_apply_wow_sr16)."""
+    from s2sr import rasterio_lite as rio
+
+    _check_bit_depth(bit_depth, enhance_crops)
+    if bit_depth == 16:
+        return _apply_wow_sr16(input_path, output_path, model)
 
     model_display = {"realesrgan_x4": "Real-ESRGAN x4",
                      "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)",
@@ -98,19 +153,25 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
 
 
 def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True,
-                   model: str = "realesrgan_x4") -> dict:
-    """Reference wow_sr.py:212-266 -- file naming, metadata JSON and result dict schema."""
+                   model: str = "realesrgan_x4", bit_depth: int = 8) -> dict:
+    """Reference wow_sr.py:212-266 -- file naming, metadata JSON and result dict schema.  bit_depth=16: see apply_wow_sr (no PNG:
+    "sr_png" is None)."""
+    _check_bit_depth(bit_depth, enhance_crops)          # before anything is created
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
     wow_tif = output_dir / f"{base_name}_wow_sr.tif"
-    _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model)
     png = wow_tif.with_suffix(".png")
+    if bit_depth == 16:
+        _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model, bit_depth=16)
+        png = None       # (a PNG an earlier 8-bit job left under this name is not this job's output)
+    else:
+        _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model)
     result = {
         "timestamp": datetime.now().strftime("%Y%m%d_%H%M%S"),
         "input": str(input_tif),
         "outputs": {"sr_tif": str(wow_tif) if wow_tif.exists() else None,
-                    "sr_png": str(png) if png.exists() else None},
+                    "sr_png": str(png) if png is not None and png.exists() else None},
         "sr_metadata": sr_metadata,
     }
     with open(output_dir / f"{base_name}_wow_sr_metadata.json", "w") as f:

@@ -58,6 +58,8 @@ void free_weights(s2sr_handle* h) {
         for (int k = 0; k < 2; ++k)
             if (c.d_wphase[k]) dev_free(c.d_wphase[k]);
     }
+    if (h->first16.d_wpack) dev_free(h->first16.d_wpack);
+    h->first16 = ConvW();
     if (h->pool_w) dev_free(h->pool_w);
     if (h->pool_s) dev_free(h->pool_s);
     if (h->pool_b) dev_free(h->pool_b);
@@ -342,7 +344,9 @@ int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* 
 // (:85-91, :103-107).  The torch.cat of the dense block is "the first k blocks of D[cur]",
 // never a copy; conv5 writes the next x into the other dense tensor because neighbouring
 // workgroups still read this one's x as halo.
-int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f32, uint8_t* d_out_u8, const Mosaic& mo = Mosaic()) {
+// in16: the planes hold 16-bit input (pack_u16): conv_first takes the cin-6 weight set and the range's in_scale.
+int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f32, uint8_t* d_out_u8, const Mosaic& mo = Mosaic(),
+            const U16In* in16 = nullptr) {
     if (h->compact()) return run_net_compact(h, st, n, H, W, d_out_f32, d_out_u8, mo);
     Workspace& w = h->ws;
     const int nb = h->cfg.num_block;
@@ -354,10 +358,11 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
     const bool fp8 = w.fp8;
     {   // conv_first: 3 -> 64 (input = one 16-channel block)
         ConvParams p = b;
-        p.src = w.P0; p.src_img = w.blk1; p.in_scale = 1.0f / 255.0f;
+        p.src = w.P0; p.src_img = w.blk1; p.in_scale = in16 ? 1.0f / (float)(in16->hi - in16->lo) : 1.0f / 255.0f;
         if (fp8) { p.dst = w.Xh[0]; p.dst_img = 4 * w.blk1; }
         else { p.dst = w.D[0]; p.dst_img = 12 * w.blk1; }
-        if ((rc = run_conv(h, st, F_FIRST, h->convs[ci++], p, EPI_FIRST, false))) return rc;
+        if ((rc = run_conv(h, st, F_FIRST, in16 ? h->first16 : h->convs[ci], p, EPI_FIRST, false))) return rc;
+        ++ci;
     }
     int cur = 0;
     const char* trunk_hi = nullptr;   // fp16 x of the trunk after the body (conv_body's main operand)
@@ -701,8 +706,10 @@ Mosaic pick_mosaic(const s2sr_handle* h, int B, int th, int tw) { return pick_mo
 // window count gave a short last chunk another image height, and with it a workspace reallocation, a device synchronise and
 // dropped graphs inside the chunk loop, on every call).  nullptr: choose from B.
 int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const float* d_x_f32, int B, int th, int tw,
-                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan, int src_h, int src_w) {
+                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan, int src_h, int src_w, const U16In* in16) {
     if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
+    if (in16 && (!in16->tiles || d_tiles || d_x_f32 || !h->first16.d_wpack || in16->lo < 0 || in16->hi > 65535 || in16->lo >= in16->hi))
+        return fail(h, S2SR_E_INVALID, "16-bit input: an x4 RRDB handle, tiles, and a range 0 <= lo < hi <= 65535");
     if (B <= 0 || th <= 0 || tw <= 0) return fail(h, S2SR_E_INVALID, "bad batch/tile dims");
     const int u = h->unshuffle();
     if (th % u || tw % u) {
@@ -713,7 +720,7 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
     const int sh = src_h ? src_h : th, sw = src_w ? src_w : tw;     // input rows / columns as stored
     const int TH = th / u, TW = tw / u;                            // the trunk grid: what the schedule, workspace and graphs see
     // u8 tiles may travel as window mosaics; "images" below are then mosaics of per = kx*ky windows
-    const Mosaic mo = !d_tiles ? Mosaic() : (plan ? *plan : pick_mosaic(h, B, th, tw));
+    const Mosaic mo = !(d_tiles || in16) ? Mosaic() : (plan ? *plan : pick_mosaic(h, B, th, tw));
     const int per = mo.on() ? mo.kx * mo.ky : 1;
     const int IH = mo.on() ? mo.ky * (TH + 1) - 1 : TH, IW = mo.on() ? mo.kx * (TW + 1) - 1 : TW;   // the plan's image: the workspace geometry
     const int NIplan = ((plan && plan->count > B ? plan->count : B) + per - 1) / per;
@@ -746,7 +753,8 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
         const int t0 = sg.t0 + g0 * sper;                                     // first window / tile of this group
         const int nt = (sg.t0 + sg.nwin - t0 < n * sper) ? (sg.t0 + sg.nwin - t0) : n * sper;   // windows / tiles in it
         const uint8_t* in8 = d_tiles ? d_tiles + (size_t)t0 * sh * sw * 3 : nullptr;
-        const float* in32 = d_tiles ? nullptr : d_x_f32 + (size_t)t0 * 3 * th * tw;
+        const float* in32 = (d_tiles || in16) ? nullptr : d_x_f32 + (size_t)t0 * 3 * th * tw;
+        const uint16_t* in16p = in16 ? in16->tiles + (size_t)t0 * th * tw * 3 : nullptr;
         float* o32 = d_out_f32 ? d_out_f32 + (size_t)t0 * 3 * opx : nullptr;
         uint8_t* o8 = d_out_u8 ? d_out_u8 + (size_t)t0 * 3 * opx : nullptr;
         Mosaic mg = mo;
@@ -758,16 +766,19 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
                     if (in8 && mo.on()) HIPCHK(h, launch_pack_u8_unshuffle_mosaic(in8, nt, TH, TW, sg.kx, sg.ky, w.P0, w.Hp, w.Wp, st));
                     else if (in8) HIPCHK(h, launch_pack_u8_unshuffle(in8, n, sh, sw, TH, TW, w.P0, w.Hp, w.Wp, st));
                     else HIPCHK(h, launch_pack_f32_nchw_unshuffle(in32, n, TH, TW, 255.0f, w.P0, w.Hp, w.Wp, st));
-                } else if (in8 && mo.on()) HIPCHK(h, launch_pack_u8_mosaic(in8, nt, th, tw, sg.kx, sg.ky, w.P0, w.Hp, w.Wp, st));
+                } else if (in16p && mo.on()) HIPCHK(h, launch_pack_u16_mosaic(in16p, nt, th, tw, sg.kx, sg.ky, in16->lo, in16->hi, w.P0, w.Hp, w.Wp, st));
+                else if (in16p) HIPCHK(h, launch_pack_u16(in16p, n, th, tw, in16->lo, in16->hi, w.P0, w.Hp, w.Wp, st));
+                else if (in8 && mo.on()) HIPCHK(h, launch_pack_u8_mosaic(in8, nt, th, tw, sg.kx, sg.ky, w.P0, w.Hp, w.Wp, st));
                 else if (in8) HIPCHK(h, launch_pack_u8(in8, n, th, tw, w.P0, w.Hp, w.Wp, st));
                 else HIPCHK(h, launch_pack_f32_nchw(in32, n, 3, th, tw, 255.0f, w.P0, 1, w.Hp, w.Wp, st));
             }
-            return run_net(h, st, n, SH, SW, o32, o8, mo.on() ? mg : Mosaic());
+            return run_net(h, st, n, SH, SW, o32, o8, mo.on() ? mg : Mosaic(), in16);
         };
         // the legacy null stream cannot be captured; profiling wants its events between launches
         GraphEntry* ge = nullptr;
         if (h->graphs_on && h->prof <= 0 && st != nullptr) {
-            const GraphKey key{n, th, tw, sh, sw, mo.on() ? sg.kx : 0, mo.on() ? sg.ky : 0, mo.on() ? nt : 0, in8, in32, o8, o32, st};
+            GraphKey key{n, th, tw, sh, sw, mo.on() ? sg.kx : 0, mo.on() ? sg.ky : 0, mo.on() ? nt : 0, in8, in32, o8, o32, st};
+            if (in16p) { key.in_u16 = in16p; key.lo = in16->lo; key.hi = in16->hi; }
             for (GraphEntry& g : h->graphs)
                 if (g.key == key) { ge = &g; break; }
             if (!ge) {   // first sighting: remember it, launch directly (also warms the per-kernel attributes)
@@ -816,6 +827,19 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
         }
     }
     }
+    return S2SR_OK;
+}
+
+// what every 16-bit entry refuses before it touches the device: a net it is not built for, or a bad value range
+int check_u16(s2sr_handle* h, int lo, int hi) {
+    if (h->compact()) return fail(h, S2SR_E_INVALID, "16-bit input is not available on an S2SR_ARCH_COMPACT handle (its tail reads the 8-bit base image from the input plane)");
+    if (h->cfg.scale != 4) return fail(h, S2SR_E_INVALID, "16-bit input is not available on a scale-2 handle (24 unshuffled channels need a second input block)");
+    if (lo < 0 || hi > 65535 || lo >= hi) {
+        char b[160];
+        snprintf(b, sizeof b, "16-bit value range [%d, %d]: need 0 <= lo < hi <= 65535", lo, hi);
+        return fail(h, S2SR_E_INVALID, b);
+    }
+    if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
     return S2SR_OK;
 }
 
@@ -1111,6 +1135,21 @@ static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_flo
             }
             HIPCHK(h, dev_malloc(&cw.d_wpack, wb));
             HIPCHK(h, copy_blocking(h, cw.d_wpack, tmp.data(), wb, hipMemcpyHostToDevice));
+            if (idx == 0 && s.cin == 3) {
+                // the 16-bit door's conv_first: input channels c and c + 3 (d & 255 and d & 0xff00, pack.hip) both meet w[:, c] --
+                // same packer, same segments (hp: w_hi / w_lo), still one 16-channel stage per segment, the same bias
+                std::vector<float> w6((size_t)s.cout * 6 * 9);
+                for (int co = 0; co < s.cout; ++co)
+                    for (int c = 0; c < 6; ++c) memcpy(&w6[((size_t)co * 6 + c) * 9], pw + ((size_t)co * 3 + c % 3) * 9, 9 * sizeof(float));
+                ConvW c6 = cw;
+                c6.cin = 6; c6.d_wpack = nullptr;
+                const size_t wb6 = conv_wpack_bytes_seg(6, s.cout, nseg);
+                tmp.resize(wb6);
+                pack_conv_weights(w6.data(), 6, s.cout, nseg, tmp.data(), fold);
+                HIPCHK(h, dev_malloc(&c6.d_wpack, wb6));
+                HIPCHK(h, copy_blocking(h, c6.d_wpack, tmp.data(), wb6, hipMemcpyHostToDevice));
+                h->first16 = c6;
+            }
         }
         h->convs.push_back(cw);
     }
@@ -1230,6 +1269,67 @@ static int forward_batch_u8_once(s2sr_handle* h, const uint8_t* tiles, int32_t B
 
 int s2sr_forward_batch_u8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int32_t th, int32_t tw, uint8_t* out) {
     RUN_WITH_STREAM_RECOVERY(h, forward_batch_u8_once(h, tiles, B, th, tw, out));
+}
+
+// The 16-bit door on a batch of tiles: the net's fp32 tile output [B,3,4th,4tw] goes to a scratch buffer, the quantiser
+// (launch_stitch_quant_u16 in its plain-batch form) turns it into [B,4th,4tw,3] u16.  The caller holds h->mu.
+static int forward_u16_locked(s2sr_handle* h, hipStream_t st, const uint16_t* d_tiles, int B, int th, int tw, int lo, int hi,
+                              uint16_t* d_out_u16, float* d_f32) {
+    const U16In in16{d_tiles, lo, hi};
+    int rc = forward_dev(h, st, nullptr, nullptr, B, th, tw, nullptr, d_f32, nullptr, 0, 0, &in16);
+    if (rc || !d_out_u16) return rc;
+    Scope sc(h, st, F_MISC, 0.0, (double)B * 16.0 * th * tw * 3.0 * (4.0 + 2.0));
+    HIPCHK(h, launch_stitch_quant_u16(d_f32, 1, 0, 4 * th, 4 * tw, nullptr, nullptr, B * 4 * th, 4 * tw, lo, hi, d_out_u16, st));
+    return S2SR_OK;
+}
+
+int s2sr_forward_batch_u16_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int32_t th, int32_t tw, int32_t lo, int32_t hi,
+                               void* d_out_u16, void* stream) {
+    if (!h || !d_tiles || !d_out_u16 || B <= 0 || th <= 0 || tw <= 0) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    int rc = check_u16(h, lo, hi);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    // the fp32 tiles between the net and the quantiser live in the handle's scratch (slot 1); work already queued on the caller's
+    // stream that reads an earlier call's tiles is ordered before this call's on the same stream
+    if ((rc = ensure_scratch(h, 1, (size_t)B * 3 * 16 * th * tw * sizeof(float)))) return rc;
+    return forward_u16_locked(h, (hipStream_t)stream, (const uint16_t*)d_tiles, B, th, tw, lo, hi, (uint16_t*)d_out_u16, (float*)h->d_scratch[1]);
+}
+
+static int forward_batch_u16_once(s2sr_handle* h, const uint16_t* tiles, int32_t B, int32_t th, int32_t tw, int32_t lo, int32_t hi,
+                                  uint16_t* out_u16, float* out_f32) {
+    if (!h || !tiles || (!out_u16 && !out_f32) || B <= 0 || th <= 0 || tw <= 0) {
+        if (h) fail(h, S2SR_E_INVALID, "s2sr_forward_batch_u16: tiles, positive sizes and at least one output are required");
+        return S2SR_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    int rc = check_u16(h, lo, hi);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t npx = (size_t)B * th * tw * 3, ib = npx * 2, fb = npx * 16 * sizeof(float), qb = npx * 16 * 2;
+    if ((rc = ensure_scratch(h, 0, ib))) return rc;
+    if ((rc = ensure_scratch(h, 1, fb))) return rc;
+    if (out_u16 && (rc = ensure_scratch(h, 2, qb))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], tiles, ib, hipMemcpyHostToDevice, h->stream));
+    if ((rc = forward_u16_locked(h, h->stream, (const uint16_t*)h->d_scratch[0], B, th, tw, lo, hi, out_u16 ? (uint16_t*)h->d_scratch[2] : nullptr,
+                                 (float*)h->d_scratch[1]))) return rc;
+    if (h->group_done.empty()) {
+        hipEvent_t e;
+        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        h->group_done.push_back(e);
+    }
+    HIPCHK(h, hipEventRecord(h->group_done[0], h->stream));
+    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[0], 0));
+    if (out_u16 && (rc = d2h_staged(h, (uint8_t*)out_u16, (const uint8_t*)h->d_scratch[2], qb, true))) return rc;
+    if (out_f32 && (rc = d2h_staged(h, (uint8_t*)out_f32, (const uint8_t*)h->d_scratch[1], fb, true))) return rc;
+    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return S2SR_OK;
+}
+
+int s2sr_forward_batch_u16(s2sr_handle* h, const uint16_t* tiles, int32_t B, int32_t th, int32_t tw, int32_t lo, int32_t hi,
+                           uint16_t* out_u16, float* out_f32) {
+    RUN_WITH_STREAM_RECOVERY(h, forward_batch_u16_once(h, tiles, B, th, tw, lo, hi, out_u16, out_f32));
 }
 
 static int forward_f32_once(s2sr_handle* h, const float* x, int32_t N, int32_t H, int32_t W, float* y) {

@@ -537,6 +537,168 @@ int s2sr_enhance_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, i
     RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, img, H, W, tile, pad, nullptr, out));
 }
 
+// RealESRGAN.enhance for 16-bit rasters (upstream RealESRGANer's max_range = 65535 branch, with a value range): HxWx3 u16 ->
+// 4Hx4Wx3 u16 and / or the unquantised HWC fp32 image.  A sibling of enhance_impl, not a mode of it: the same whole / tiled
+// switch, window plan, de-duplication of repeated window rows / columns, mosaic and chunk plan, but every chunk's windows leave
+// the net as fp32 tiles into ONE chunk-sized buffer (the same pointers for every chunk, so the chunks' graphs hit), and
+// launch_stitch_quant_u16 pastes and quantises the chunk's band of final rows from it; the band's copy out runs on the copy stream
+// under the next chunk.  With out_f32 the tiles of the whole image are kept and stitched once at the end, as enhance_impl does.
+static int enhance16_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int tile, int pad, int lo, int hi, uint16_t* out_u16,
+                          float* out_f32) {
+    if (!h || !img || (!out_u16 && !out_f32) || H <= 0 || W <= 0 || tile <= 0 || pad < 0) {
+        if (h) fail(h, S2SR_E_INVALID, "s2sr_enhance_u16: an image, positive sizes and at least one output are required");
+        return S2SR_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    int rc = check_u16(h, lo, hi);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    const int scale = 4, OH = H * scale, OW = W * scale;
+    const size_t ipx = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
+    const size_t q_bytes = (opx * 2 + 255) & ~(size_t)255;       // scratch 1: the u16 image, then (out_f32) the fp32 image
+    if ((rc = ensure_scratch(h, 0, ipx * 2))) return rc;
+    if ((rc = ensure_scratch(h, 1, q_bytes + (out_f32 ? opx * 4 : 0)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, ipx * 2, hipMemcpyHostToDevice, st));
+    const bool tiled = (long long)H * W > (long long)tile * tile * 4;   // strict '>' (:226)
+    // the windows the net runs on (ny rows of nx, wh x ww each), the paste maps and the chunks of window rows
+    int nx = 1, ny = 1, wh = H, ww = W;
+    std::vector<int32_t> rm, cm, rects;
+    std::vector<int> chunk_r0;   // first window row of each chunk, plus ny at the end
+    Mosaic mo;
+    const uint16_t* d_win = (const uint16_t*)h->d_scratch[0];
+    if (!tiled) {
+        rm.resize(2 * (size_t)OH); cm.resize(2 * (size_t)OW);
+        for (int i = 0; i < OH; ++i) { rm[2 * i] = 0; rm[2 * i + 1] = i; }
+        for (int i = 0; i < OW; ++i) { cm[2 * i] = 0; cm[2 * i + 1] = i; }
+        chunk_r0 = {0, 1};
+    } else {
+        int T = 0;
+        s2sr_plan_tiles(H, W, tile, pad, scale, nullptr, 0, &T);
+        std::vector<s2sr_window> wins(T);
+        s2sr_plan_tiles(H, W, tile, pad, scale, wins.data(), T, &T);
+        const int pnx = (W + tile - 1) / tile, pny = (H + tile - 1) / tile;    // the reference's plan
+        wh = wins[0].y2 - wins[0].y1; ww = wins[0].x2 - wins[0].x1;            // all windows share one shape
+        build_stitch_maps(wins, pnx, pny, OH, OW, rm, cm);
+        // each distinct window rectangle is forwarded once (enhance_impl: the last two rows / columns of a plan can coincide)
+        std::vector<int> uy(pny), ux(pnx), rows_y1, cols_x1;
+        for (int y = 0; y < pny; ++y) {
+            const int y1 = wins[(size_t)y * pnx].y1;
+            if (rows_y1.empty() || rows_y1.back() != y1) rows_y1.push_back(y1);
+            uy[y] = (int)rows_y1.size() - 1;
+        }
+        for (int x = 0; x < pnx; ++x) {
+            const int x1 = wins[x].x1;
+            if (cols_x1.empty() || cols_x1.back() != x1) cols_x1.push_back(x1);
+            ux[x] = (int)cols_x1.size() - 1;
+        }
+        for (size_t i = 0; i < rm.size(); i += 2)
+            if (rm[i] >= 0) rm[i] = uy[rm[i]];
+        for (size_t i = 0; i < cm.size(); i += 2)
+            if (cm[i] >= 0) cm[i] = ux[cm[i]];
+        nx = (int)cols_x1.size(); ny = (int)rows_y1.size();
+        T = nx * ny;
+        rects.resize(4 * (size_t)T);
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) {
+                const int t = y * nx + x;
+                rects[4 * t] = rows_y1[y]; rects[4 * t + 1] = rows_y1[y] + wh; rects[4 * t + 2] = cols_x1[x]; rects[4 * t + 3] = cols_x1[x] + ww;
+            }
+        mo = pick_mosaic(h, T, wh, ww);   // ONE plan for the job: every chunk runs in its workspace geometry
+        if (out_f32) chunk_r0 = {0, ny};  // the fp32 image is stitched from all the tiles at the end
+        else {                            // enhance_impl's chunk plan
+            const int per = mo.on() ? mo.kx * mo.ky : 1;
+            const int gw = (mo.on() ? group_size(h, (T + per - 1) / per, mo.ky * (mo.wh + 1) - 1, mo.kx * (mo.ww + 1) - 1) : group_size(h, T, wh, ww)) * per;
+            const int r_min = (per + nx - 1) / nx;
+            const int units = (ny + r_min - 1) / r_min;
+            int u_max = gw / nx / r_min;
+            if (u_max < 1) u_max = 1;
+            int ncu = 256;
+            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
+            const long pimg = mo.on() ? (long)((mo.ky * (mo.wh + 1) - 1 + 31) / 32) * ((mo.kx * (mo.ww + 1) - 1 + 31) / 32)
+                                      : (long)((wh + 31) / 32) * ((ww + 31) / 32);
+            std::vector<int> sizes;
+            plan_chunk_sizes(units, u_max, r_min * nx, per, pimg, ncu, sizes);
+            int r = 0;
+            for (int u : sizes) { chunk_r0.push_back(r); r += u * r_min; }
+            chunk_r0.push_back(ny);
+        }
+    }
+    const int nchunks = (int)chunk_r0.size() - 1;
+    int max_rows = 0;
+    for (int c = 0; c < nchunks; ++c) {
+        const int r1 = chunk_r0[c + 1] < ny ? chunk_r0[c + 1] : ny;
+        if (r1 - chunk_r0[c] > max_rows) max_rows = r1 - chunk_r0[c];
+    }
+    const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;      // samples per window, in and out
+    if (tiled && (rc = ensure_scratch(h, 2, (size_t)nx * ny * win_in * 2))) return rc;
+    if ((rc = ensure_scratch(h, 4, (size_t)max_rows * nx * win_out * sizeof(float)))) return rc;
+    if ((rc = ensure_scratch(h, 3, (rects.size() + rm.size() + cm.size()) * 4))) return rc;
+    int32_t* d_rects = (int32_t*)h->d_scratch[3];
+    int32_t* d_rm = d_rects + rects.size();
+    int32_t* d_cm = d_rm + rm.size();
+    if (!rects.empty()) HIPCHK(h, hipMemcpyAsync(d_rects, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(d_rm, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(d_cm, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (tiled) {
+        HIPCHK(h, launch_gather_windows_u16((const uint16_t*)h->d_scratch[0], H, W, d_rects, nx * ny, wh, ww, (uint16_t*)h->d_scratch[2], st));
+        d_win = (const uint16_t*)h->d_scratch[2];
+    }
+    while ((int)h->group_done.size() < nchunks + 1) {
+        hipEvent_t e;
+        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        h->group_done.push_back(e);
+    }
+    uint16_t* d_q = (uint16_t*)h->d_scratch[1];
+    float* d_tiles = (float*)h->d_scratch[4];
+    const size_t row_b = (size_t)OW * 3 * 2;                     // bytes of one output row
+    int yb = 0, prev_yb = 0, prev_ye = 0;
+    for (int c = 0; c < nchunks; ++c) {
+        const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1] < ny ? chunk_r0[c + 1] : ny;
+        const int t0 = r0 * nx, n = (r1 - r0) * nx;
+        const U16In in16{d_win + (size_t)t0 * win_in, lo, hi};
+        if ((rc = forward_dev(h, st, nullptr, nullptr, n, wh, ww, nullptr, d_tiles, mo.on() ? &mo : nullptr, 0, 0, &in16))) return rc;
+        int ye = OH;
+        if (r1 < ny)
+            for (ye = yb; ye < OH && rm[2 * ye] < r1; ++ye) {}
+        if (out_u16 && ye > yb) {   // the band's rows come from window rows [r0, r1) only (the row map is monotone): tiles of this chunk
+            Scope sc(h, st, F_MISC, 0.0, (double)(ye - yb) * OW * 3.0 * (4.0 + 2.0));
+            HIPCHK(h, launch_stitch_quant_u16(d_tiles, nx, t0, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW, lo, hi,
+                                              d_q + (size_t)yb * OW * 3, st));
+        }
+        HIPCHK(h, hipEventRecord(h->group_done[c], st));
+        if (out_u16 && c > 0 && prev_ye > prev_yb) {
+            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[c - 1], 0));
+            if ((rc = d2h_staged(h, (uint8_t*)out_u16 + (size_t)prev_yb * row_b, (const uint8_t*)d_q + (size_t)prev_yb * row_b,
+                                 (size_t)(prev_ye - prev_yb) * row_b, false))) return rc;
+        }
+        prev_yb = yb; prev_ye = ye; yb = ye;
+    }
+    if (out_f32) {   // (one chunk: d_tiles holds every window)
+        float* d_f = (float*)((char*)h->d_scratch[1] + q_bytes);
+        HIPCHK(h, launch_stitch_f32(d_tiles, nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, d_f, st));
+        HIPCHK(h, hipEventRecord(h->group_done[nchunks], st));
+    }
+    if (out_u16 && prev_ye > prev_yb) {
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
+        if ((rc = d2h_staged(h, (uint8_t*)out_u16 + (size_t)prev_yb * row_b, (const uint8_t*)d_q + (size_t)prev_yb * row_b,
+                             (size_t)(prev_ye - prev_yb) * row_b, true))) return rc;
+    }
+    if (out_f32) {
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks], 0));
+        if ((rc = d2h_staged(h, (uint8_t*)out_f32, (const uint8_t*)h->d_scratch[1] + q_bytes, opx * 4, true))) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    HIPCHK(h, hipStreamSynchronize(st));
+    return S2SR_OK;
+}
+
+int s2sr_enhance_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
+                     uint16_t* out_u16, float* out_f32) {
+    RUN_WITH_STREAM_RECOVERY(h, enhance16_impl(h, img, H, W, tile, pad, lo, hi, out_u16, out_f32));
+}
+
 int s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_t W, int32_t tile, int32_t pad,
                             int32_t first, int32_t count, void* d_tiles, void* stream) {
     if (!h || !d_img || !d_tiles || H <= 0 || W <= 0 || tile <= 0 || pad < 0 || first < 0 || count <= 0) return S2SR_E_INVALID;

@@ -88,10 +88,20 @@ struct GraphKey {
     const void *in_u8 = nullptr, *in_f32 = nullptr;
     void *out_u8 = nullptr, *out_f32 = nullptr;
     hipStream_t st = nullptr;
+    // the input kind: 16-bit tiles and their value range (the packer's constants and conv_first's in_scale are baked into the
+    // captured launches, and the host entries reuse one scratch pointer for every range)
+    const void* in_u16 = nullptr;
+    int lo = 0, hi = 0;
     bool operator==(const GraphKey& o) const {
         return n == o.n && th == o.th && tw == o.tw && sh == o.sh && sw == o.sw && mos_kx == o.mos_kx && mos_ky == o.mos_ky &&
-               mos_count == o.mos_count && in_u8 == o.in_u8 && in_f32 == o.in_f32 && out_u8 == o.out_u8 && out_f32 == o.out_f32 && st == o.st;
+               mos_count == o.mos_count && in_u8 == o.in_u8 && in_f32 == o.in_f32 && out_u8 == o.out_u8 && out_f32 == o.out_f32 && st == o.st &&
+               in_u16 == o.in_u16 && lo == o.lo && hi == o.hi;
     }
+};
+// forward_dev's 16-bit input kind: [B,th,tw,3] uint16 tiles (device) with the value range 0 <= lo < hi <= 65535 (pack.hip)
+struct U16In {
+    const uint16_t* tiles = nullptr;
+    int lo = 0, hi = 65535;
 };
 struct GraphEntry {
     GraphKey key;
@@ -126,6 +136,9 @@ struct s2sr_handle {
     std::mutex mu;
     std::string err;
     std::vector<s2sr::engine::ConvW> convs;
+    // conv_first of the 16-bit door (x4 RRDB nets): the same conv on a cin-6 weight set, w6[:, c] = w6[:, c + 3] = w[:, c], for
+    // the (d & 255, d & 0xff00) channel pairs pack_u16 writes; built next to convs[0], sharing its bias (d_wpack null: not built)
+    s2sr::engine::ConvW first16;
     // the packed weights of the 345 RDB convs, their fp8 scales and every conv's bias live in three pooled allocations
     // (ConvW pointers point into them); only the six head/tail convs own separate buffers (pooled == false)
     char* pool_w = nullptr;
@@ -261,7 +274,9 @@ long mosaic_patches(int B, int th, int tw, int kx, int ky);
 Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw);
 Mosaic pick_mosaic(const s2sr_handle* h, int B, int th, int tw);
 int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const float* d_x_f32, int B, int th, int tw,
-                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan = nullptr, int src_h = 0, int src_w = 0);
+                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan = nullptr, int src_h = 0, int src_w = 0,
+                const U16In* in16 = nullptr);
+int check_u16(s2sr_handle* h, int lo, int hi);
 
 // ---- engine_aoi.hip
 constexpr size_t kStageBytes = 32u << 20;   // one pinned staging slice (s2sr_handle::stage_buf)

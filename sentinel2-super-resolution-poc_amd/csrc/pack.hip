@@ -565,4 +565,173 @@ hipError_t launch_stitch_f32(const float* d_tiles, int tilesX, int oth, int otw,
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// The 16-bit door (s2sr_forward_batch_u16 / s2sr_enhance_u16): uint16 samples with a value range [lo, hi].
+//   in : d = clamp(v, lo, hi) - lo (0..65535) travels as TWO exact fp16 integers, d = 256 * dh + dl: channels 0..2 of the
+//        one-block input plane carry dl (0..255), channels 3..5 carry 256 * dh (0..65280: 8 significant bits, below fp16's
+//        65504).  conv_first runs on a cin-6 weight set with w6[:, c] = w6[:, c + 3] = w[:, c] and in_scale 1 / (hi - lo), so
+//        its accumulator sums w * d exactly as it sums w * u for u8 input.
+//   out: q = lo + rint(clamp(y, 0, 1) * (hi - lo)), the product in fp32 rounded once, rint to nearest even (upstream
+//        RealESRGANer's 16-bit branch rounds; the u8 door's truncation is the reference's quirk and stays there).
+// ------------------------------------------------------------------------------------------
+__device__ inline f16x8 split_u16(const uint16_t* s, int lo, int hi) {
+    f16x8 v;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int d = (int)s[c];
+        d = (d < lo ? lo : (d > hi ? hi : d)) - lo;
+        v[c] = (f16)(float)(d & 0xff);
+        v[3 + c] = (f16)(float)(d & 0xff00);
+    }
+    v[6] = (f16)0.f;
+    v[7] = (f16)0.f;
+    return v;
+}
+
+// twin of pack_u8_kernel: one 16-byte store per pixel.  pack_u8's 8-byte store leaves channels 4..5 of a plane this kernel wrote
+// as they are (finite values); the u8 conv_first weights of those channels are zero.
+__global__ void pack_u16_kernel(const uint16_t* __restrict__ in, int N, int H, int W, int lo, int hi, char* __restrict__ blk, int Hp,
+                                int Wp) {
+    const size_t total = (size_t)N * H * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W);
+        const size_t r = i / W;
+        const int y = (int)(r % H);
+        const int n = (int)(r / H);
+        *(f16x8*)(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32) = split_u16(in + i * 3, lo, hi);
+    }
+}
+
+hipError_t launch_pack_u16(const uint16_t* d_tiles, int N, int H, int W, int lo, int hi, char* blk, int Hp, int Wp, hipStream_t st) {
+    const size_t total = (size_t)N * H * W;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(pack_u16_kernel, dim3(grid), dim3(256), 0, st, d_tiles, N, H, W, lo, hi, blk, Hp, Wp);
+    return hipGetLastError();
+}
+
+// twin of pack_u8_mosaic_kernel
+__global__ void pack_u16_mosaic_kernel(const uint16_t* __restrict__ in, int B, int h, int w, int kx, int ky, int lo, int hi,
+                                       char* __restrict__ blk, int Hp, int Wp) {
+    const size_t total = (size_t)B * h * w;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int lx = (int)(i % w);
+        const size_t r = i / w;
+        const int ly = (int)(r % h);
+        const int t = (int)(r / h);
+        const int n = t / (kx * ky), slot = t - n * (kx * ky);
+        const int wy = slot / kx, wx = slot - wy * kx;
+        const int y = wy * (h + 1) + ly, x = wx * (w + 1) + lx;
+        *(f16x8*)(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32) = split_u16(in + i * 3, lo, hi);
+    }
+}
+
+hipError_t launch_pack_u16_mosaic(const uint16_t* d_tiles, int B, int h, int w, int kx, int ky, int lo, int hi, char* blk, int Hp, int Wp,
+                                  hipStream_t st) {
+    const size_t total = (size_t)B * h * w;
+    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL(pack_u16_mosaic_kernel, dim3(grid), dim3(256), 0, st, d_tiles, B, h, w, kx, ky, lo, hi, blk, Hp, Wp);
+    return hipGetLastError();
+}
+
+// gather_windows_kernel on 2-byte samples
+__global__ void gather_windows_u16_kernel(const uint16_t* __restrict__ img, int H, int W, const int32_t* __restrict__ rects,
+                                          int T, int wh, int ww, uint16_t* __restrict__ tiles) {
+    const size_t total = (size_t)T * wh * ww * 3;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % 3);
+        size_t r = i / 3;
+        const int x = (int)(r % ww);
+        r /= ww;
+        const int y = (int)(r % wh);
+        const int t = (int)(r / wh);
+        const int y1 = rects[t * 4 + 0], x1 = rects[t * 4 + 2];
+        tiles[i] = img[((size_t)(y1 + y) * W + (x1 + x)) * 3 + c];
+    }
+}
+
+hipError_t launch_gather_windows_u16(const uint16_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
+                                     uint16_t* d_tiles, hipStream_t st) {
+    const size_t total = (size_t)T * wh * ww * 3;
+    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+    hipLaunchKernelGGL(gather_windows_u16_kernel, dim3(grid), dim3(256), 0, st, d_img, H, W, d_rects, T, wh, ww, d_tiles);
+    return hipGetLastError();
+}
+
+__device__ inline uint32_t quant_u16(float y, float range, int lo) {
+    const float c = fminf(fmaxf(y, 0.f), 1.f);
+    return (uint32_t)(lo + (int)rintf(__fmul_rn(c, range)));   // a lone fp32 product: nothing here to fuse it with
+}
+
+// Crop + paste + quantise: planar fp32 tiles [.., 3, oth, otw] -> rows [0, OH) of an HWC u16 image through the paste maps, as
+// stitch_f32_kernel reads them (rowmap already offset to the band's first row; window (ty, tx) is tile ty * tilesX + tx - tile0
+// of `tiles`, so a chunk's buffer holds only its own window rows).  rowmap == nullptr: a plain batch, row oy of the output is row
+// oy % oth of tile oy / oth.  One thread = 4 consecutive output pixels (OW is a multiple of 4: the x4 net): paste rectangles
+// start and end on multiples of 4 on both sides, so the 4 pixels are one float4 per colour plane (checked, with a scalar
+// route), and leave as 24 contiguous bytes.
+__global__ void stitch_quant_u16_kernel(const float* __restrict__ tiles, int oth, int otw, const int32_t* __restrict__ rowmap,
+                                        const int32_t* __restrict__ colmap, int tilesX, int tile0, int OH, int OW, int lo, int hi,
+                                        uint16_t* __restrict__ out) {
+    const int gw = OW >> 2;
+    const size_t total = (size_t)OH * gw;
+    const float range = (float)(hi - lo);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int ox = (int)(i % gw) << 2;
+        const int oy = (int)(i / gw);
+        int ty, sy;
+        if (rowmap) { ty = rowmap[2 * oy]; sy = rowmap[2 * oy + 1]; }
+        else { ty = oy / oth; sy = oy - ty * oth; }
+        float v[3][4];
+        int tx[4], sx[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (colmap) { tx[k] = colmap[2 * (ox + k)]; sx[k] = colmap[2 * (ox + k) + 1]; }
+            else { tx[k] = 0; sx[k] = ox + k; }
+        }
+        const bool vec = ty >= 0 && tx[0] >= 0 && tx[1] == tx[0] && tx[2] == tx[0] && tx[3] == tx[0] && sx[1] == sx[0] + 1 &&
+                         sx[2] == sx[0] + 2 && sx[3] == sx[0] + 3 && (sx[0] & 3) == 0 && (otw & 3) == 0;
+        if (vec) {
+            const float* p = tiles + (((size_t)(ty * tilesX + tx[0] - tile0) * 3) * oth + sy) * otw + sx[0];
+            const size_t plane = (size_t)oth * otw;
+            if (((uintptr_t)p & 15) == 0 && (plane & 3) == 0) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float4 f = *(const float4*)(p + c * plane);
+                    v[c][0] = f.x; v[c][1] = f.y; v[c][2] = f.z; v[c][3] = f.w;
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[c][k] = p[c * plane + k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+                    v[c][k] = (ty >= 0 && tx[k] >= 0) ? tiles[(((size_t)(ty * tilesX + tx[k] - tile0) * 3 + c) * oth + sy) * otw + sx[k]] : 0.f;
+        }
+        uint32_t q[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) q[3 * k + c] = quant_u16(v[c][k], range, lo);
+        // (oy * OW + ox) * 6 bytes: a multiple of 24, so the three 8-byte stores are aligned
+        uint2* d = (uint2*)(out + ((size_t)oy * OW + ox) * 3);
+        d[0] = make_uint2(q[0] | (q[1] << 16), q[2] | (q[3] << 16));
+        d[1] = make_uint2(q[4] | (q[5] << 16), q[6] | (q[7] << 16));
+        d[2] = make_uint2(q[8] | (q[9] << 16), q[10] | (q[11] << 16));
+    }
+}
+
+hipError_t launch_stitch_quant_u16(const float* d_tiles, int tilesX, int tile0, int oth, int otw, const int32_t* d_rowmap,
+                                   const int32_t* d_colmap, int OH, int OW, int lo, int hi, uint16_t* d_out, hipStream_t st) {
+    if (OH <= 0 || OW <= 0 || (OW & 3) || ((uintptr_t)d_out & 7)) return hipErrorInvalidValue;
+    const size_t total = (size_t)OH * (OW >> 2);
+    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+    hipLaunchKernelGGL(stitch_quant_u16_kernel, dim3(grid), dim3(256), 0, st, d_tiles, oth, otw, d_rowmap, d_colmap, tilesX, tile0, OH, OW,
+                       lo, hi, d_out);
+    return hipGetLastError();
+}
+
 }  // namespace s2sr

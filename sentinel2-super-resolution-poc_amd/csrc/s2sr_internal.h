@@ -310,6 +310,20 @@ hipError_t launch_stitch_u8(const uint8_t* d_tiles, int tilesX, int oth, int otw
                             const int32_t* d_colmap, int OH, int OW, uint8_t* d_out, hipStream_t st);
 hipError_t launch_stitch_f32(const float* d_tiles /*[T,3,oth,otw]*/, int tilesX, int oth, int otw, const int32_t* d_rowmap,
                              const int32_t* d_colmap, int OH, int OW, float* d_out /*HWC*/, hipStream_t st);
+// the 16-bit door (uint16 samples, value range 0 <= lo < hi <= 65535; the arithmetic is stated in pack.hip).  pack_u16 /
+// pack_u16_mosaic: twins of the u8 packers, d = clamp(v, lo, hi) - lo as channels 0..2 = d & 255, 3..5 = d & 0xff00 of the input
+// plane (one 16-byte store per pixel).  gather_windows_u16: gather_windows on 2-byte samples (scale 4 only: no reflect form).
+hipError_t launch_pack_u16(const uint16_t* d_tiles, int N, int H, int W, int lo, int hi, char* blk, int Hp, int Wp, hipStream_t st);
+hipError_t launch_pack_u16_mosaic(const uint16_t* d_tiles, int B, int h, int w, int kx, int ky, int lo, int hi, char* blk, int Hp, int Wp,
+                                  hipStream_t st);
+hipError_t launch_gather_windows_u16(const uint16_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
+                                     uint16_t* d_tiles, hipStream_t st);
+// crop + paste + quantise: planar fp32 tiles [.., 3, oth, otw] -> OH rows of an HWC u16 image, q = lo + rint(clamp(y, 0, 1) * (hi - lo)).
+// d_rowmap points at the first row of the band (d_out likewise); window (ty, tx) is tile ty * tilesX + tx - tile0 of d_tiles.
+// d_rowmap == nullptr: a plain batch (output row oy = row oy % oth of tile oy / oth); d_colmap == nullptr: identity columns.
+// OW must be a multiple of 4 and d_out 8-byte aligned (hipErrorInvalidValue otherwise).
+hipError_t launch_stitch_quant_u16(const float* d_tiles, int tilesX, int tile0, int oth, int otw, const int32_t* d_rowmap,
+                                   const int32_t* d_colmap, int OH, int OW, int lo, int hi, uint16_t* d_out, hipStream_t st);
 
 // post-process kernels (postprocess.hip)
 hipError_t launch_postprocess(const uint8_t* d_rgb, int B, int H, int W, const s2sr_pp_params& prm, uint8_t* d_out,

@@ -129,6 +129,9 @@ _PROTOS = {
     "s2sr_forward_batch_u8_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                             C.c_void_p]),
     "s2sr_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "s2sr_forward_batch_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
+    "s2sr_forward_batch_u16_dev": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
+    "s2sr_enhance_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]),
     "s2sr_enhance_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_enhance_job_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PPParams), C.c_void_p]),
     "s2sr_enhance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -590,6 +593,39 @@ class Engine:
         self._check(self._lib.s2sr_tile_process_f32(self._h, _ptr(img), H, W, tile, pad, _ptr(out)),
                     "s2sr_tile_process_f32")
         return out
+
+    # -- the 16-bit door (include/s2sr.h: uint16 in, uint16 x4 out, value range lo, hi) ---------
+    def forward_batch_u16(self, tiles: np.ndarray, lo: int = 0, hi: int = 65535, want_f32: bool = False):
+        """[B,h,w,3] uint16 -> [B,4h,4w,3] uint16 = lo + rint(clip(y, 0, 1) * (hi - lo)); want_f32: (that, the unquantised net
+        output [B,3,4h,4w] float32)."""
+        if np.asarray(tiles).dtype != np.uint16:
+            raise TypeError(f"forward_batch_u16 takes uint16 tiles, got {np.asarray(tiles).dtype}")
+        tiles = np.ascontiguousarray(tiles)
+        B, h, w, c = tiles.shape
+        assert c == 3
+        out = pinned_pool.empty((B, 4 * h, 4 * w, 3), np.uint16)
+        f = np.empty((B, 3, 4 * h, 4 * w), dtype=np.float32) if want_f32 else None
+        self._check(self._lib.s2sr_forward_batch_u16(self._h, _ptr(tiles), B, h, w, int(lo), int(hi), _ptr(out), _ptr(f) if want_f32 else None),
+                    "s2sr_forward_batch_u16")
+        return (out, f) if want_f32 else out
+
+    def forward_batch_u16_dev(self, d_in: int, B: int, h: int, w: int, d_out: int, lo: int = 0, hi: int = 65535, stream: int = 0):
+        """Device pointers (ints): [B,h,w,3] uint16 -> [B,4h,4w,3] uint16; asynchronous on `stream`."""
+        self._check(self._lib.s2sr_forward_batch_u16_dev(self._h, d_in, B, h, w, int(lo), int(hi), d_out, C.c_void_p(stream)),
+                    "s2sr_forward_batch_u16_dev")
+
+    def enhance_u16(self, img: np.ndarray, lo: int = 0, hi: int = 65535, tile: int = 256, pad: int = 10, want_f32: bool = False):
+        """HxWx3 uint16 -> 4Hx4Wx3 uint16 (whole / tiled as enhance_u8); want_f32: (that, the unquantised HWC float32 image)."""
+        if np.asarray(img).dtype != np.uint16:
+            raise TypeError(f"enhance_u16 takes a uint16 image, got {np.asarray(img).dtype}")
+        img = np.ascontiguousarray(img)
+        H, W, c = img.shape
+        assert c == 3
+        out = pinned_pool.empty((4 * H, 4 * W, 3), np.uint16)
+        f = np.empty((4 * H, 4 * W, 3), dtype=np.float32) if want_f32 else None
+        self._check(self._lib.s2sr_enhance_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), _ptr(out), _ptr(f) if want_f32 else None),
+                    "s2sr_enhance_u16")
+        return (out, f) if want_f32 else out
 
     # -- multi-GPU building blocks (device pointers) ------------------------------------------
     def cut_windows_u8_dev(self, d_img: int, H: int, W: int, tile: int, pad: int, first: int, count: int,

@@ -111,6 +111,22 @@ def read_rgb_u8(path: Path, minmax_eps: float = 0.0) -> Tuple[np.ndarray, Option
     return np.ascontiguousarray(_to_u8(arr, minmax_eps)), georef
 
 
+def read_rgb_raw(path: Path) -> Tuple[np.ndarray, Optional[GeoRef]]:
+    """-> (HxWx3 array of bands 1-3 AS STORED (dtype of the file; the single band three times), GeoRef).  GeoTIFFs only, through
+    `tiff_lite`: what `read_rgb_u8` reads, without its `_to_u8` -- a uint16 raster keeps its 16 bits (the 16-bit path of app.wow_sr)."""
+    from . import tiff_lite
+    path = Path(path)
+    if path.suffix.lower() not in (".tif", ".tiff"):
+        raise ValueError(f"{path}: read_rgb_raw reads GeoTIFFs (.tif / .tiff)")
+    try:
+        arr, tv = tiff_lite.read_tiff(path)
+    except tiff_lite.TiffError as e:
+        raise ValueError(f"{path}: unsupported raster layout (tiff_lite: {e})") from e
+    arr = arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2)   # bands 1-3 / gray three times (wow_sr.py:61-65)
+    georef = GeoRef({t: (tv[t][0] if t == TAG_GEOASCII else tuple(tv[t])) for t in _GEO_TAGS if t in tv})
+    return np.ascontiguousarray(arr), georef
+
+
 _ADLER = 65521
 
 
@@ -384,3 +400,70 @@ def write_geotiff_rgb(path: Path, rgb: np.ndarray, georef: GeoRef, rows_per_stri
                 pass
     if remember:
         _remember_written(path, rgb, georef)
+
+
+def write_geotiff_rgb16(path: Path, rgb16: np.ndarray, georef: GeoRef, rows_per_strip: int = 64) -> None:
+    """uint16 RGB, the 16-bit sibling of `write_geotiff_rgb`: BitsPerSample 16,16,16, little-endian samples, LZW strips through
+    the same native encoder (no predictor), the same geo tags, classic little-endian TIFF with the IFD behind the data."""
+    import struct
+
+    from . import hostpool, native
+
+    rgb16 = np.asarray(rgb16)
+    if rgb16.ndim != 3 or rgb16.shape[2] != 3 or rgb16.dtype != np.uint16:
+        raise ValueError(f"expected HxWx3 uint16, got {rgb16.shape} {rgb16.dtype}")
+    rgb16 = np.ascontiguousarray(rgb16.astype("<u2", copy=False))
+    h, w, _ = rgb16.shape
+    strips = [(y, min(h, y + rows_per_strip)) for y in range(0, h, rows_per_strip)]
+    offs, sizes, pos = [], [], 8
+    ok = False
+    try:
+        with open(path, "wb") as f:
+            f.write(b"II" + struct.pack("<HI", 42, 0))
+            for e in hostpool.pool().map(lambda s: native.tiff_lzw_encode(rgb16[s[0]:s[1]].reshape(-1).view(np.uint8)), strips):
+                offs.append(pos)
+                sizes.append(len(e))
+                f.write(e)
+                if len(e) & 1:
+                    f.write(b"\0")
+                pos += len(e) + (len(e) & 1)
+                if pos >= (1 << 32) - (1 << 20):
+                    raise ValueError("output exceeds the 4 GiB of a classic TIFF")
+            ent = [(256, 4, (w,)), (257, 4, (h,)), (258, 3, (16, 16, 16)), (259, 3, (5,)), (262, 3, (2,)), (273, 4, tuple(offs)),
+                   (277, 3, (3,)), (278, 4, (rows_per_strip,)), (279, 4, tuple(sizes)), (284, 3, (1,)), (339, 3, (1, 1, 1))]
+            for tag, val in georef.tags.items():
+                if tag == TAG_GEOKEYS:
+                    ent.append((tag, 3, tuple(int(v) for v in val)))
+                elif tag == TAG_GEOASCII:
+                    ent.append((tag, 2, val if isinstance(val, str) else str(val)))
+                else:
+                    ent.append((tag, 12, tuple(float(v) for v in val)))
+            ent.sort(key=lambda e: e[0])
+            fmt = {3: "H", 4: "I", 12: "d"}
+            ifd_off = pos
+            val_pos = ifd_off + 2 + 12 * len(ent) + 4
+            ifd, tail = b"", b""
+            for tag, typ, vals in ent:
+                if typ == 2:
+                    data = vals.encode("latin-1") + b"\0"
+                    cnt = len(data)
+                else:
+                    data = struct.pack("<" + fmt[typ] * len(vals), *vals)
+                    cnt = len(vals)
+                e = struct.pack("<HHI", tag, typ, cnt)
+                if len(data) <= 4:
+                    e += data.ljust(4, b"\0")
+                else:
+                    e += struct.pack("<I", val_pos + len(tail))
+                    tail += data + (b"\0" if len(data) & 1 else b"")
+                ifd += e
+            f.write(struct.pack("<H", len(ent)) + ifd + struct.pack("<I", 0) + tail)
+            f.seek(4)
+            f.write(struct.pack("<I", ifd_off))
+        ok = True
+    finally:
+        if not ok:
+            try:
+                os.unlink(path)            # no half-written GeoTIFF stays behind a failed writer
+            except OSError:
+                pass
