@@ -404,6 +404,14 @@ int  s2sr_debug_mosaic_patches(int32_t B, int32_t th, int32_t tw, int64_t* launc
  * workgroups.  Writes the chunk sizes front to back; *n = their number (cap 0: count only). */
 int  s2sr_debug_plan_chunks(int32_t units, int32_t u_max, int32_t unit_windows, int32_t per, int32_t pimg, int32_t ncu,
                             int32_t* sizes, int32_t cap, int32_t* n);
+/* The window job of s2sr_enhance_u8 / s2sr_enhance_u16 on a PH x PW image (for scale 2: already padded to even sizes); host
+ * arithmetic only, no device needed.  dims = {nx, ny, wh, ww}: ny rows of nx DISTINCT windows of wh x ww (window rows / columns of
+ * the reference's plan that coincide run once).  rects: y1, y2, x1, x2 per window, row-major, `cap` windows of room
+ * (ceil(PH / tile) * ceil(PW / tile) always suffice); none for tiled == 0, where the image is its own window.  rm (2 * scale * PH
+ * entries) and cm (2 * scale * PW): per output row / column the window row / column that is pasted there and the row / column
+ * inside that window's output. */
+int  s2sr_debug_plan_windows(int32_t PH, int32_t PW, int32_t tile, int32_t pad, int32_t scale, int32_t tiled, int32_t* dims,
+                             int32_t* rects, int32_t cap, int32_t* rm, int32_t* cm);
 
 /* test hook: ONE RDB-shaped conv through the TRUNK kernels (conv_trunk.hip: conv_trunk_f16 / conv_trunk_f8), host tensors in
  * NCHW fp32 -- the per-layer parity check of the kernels that carry 84 % of a step (s2sr_debug_conv goes through conv3x3.hip).

@@ -614,6 +614,15 @@ hipEvent_t get_event(s2sr_handle* h) {
     return e;
 }
 
+int ensure_group_events(s2sr_handle* h, int n) {   // h->group_done holds at least n events
+    while ((int)h->group_done.size() < n) {
+        hipEvent_t e;
+        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        h->group_done.push_back(e);
+    }
+    return S2SR_OK;
+}
+
 constexpr int kCompactGroup = 16;
 int group_size(const s2sr_handle* h, int B, int H, int W) {
     // default group: 16 images per launch sequence; the fp8 trunk's launches are half as long, so it takes 32 (measured:
@@ -653,7 +662,7 @@ void mosaic_remainder(int rem, int kx, int ky, int* rkx, int* rky) {
     *rkx = (*rky == 1) ? rem : kx;
 }
 static long mosaic_area(int th, int tw, int kx, int ky) {   // 32 x 32 patches of one kx x ky mosaic image
-    return (long)(roundup32(ky * (th + 1) - 1) / 32) * (roundup32(kx * (tw + 1) - 1) / 32);
+    return (long)(roundup32(mosaic_extent(ky, th)) / 32) * (roundup32(mosaic_extent(kx, tw)) / 32);
 }
 long mosaic_patches(int B, int th, int tw, int kx, int ky) {   // patches launched for B windows
     const int per = kx * ky, full = B / per, rem = B % per;
@@ -697,6 +706,12 @@ Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw) {
 }
 // th x tw: input windows; the mosaic is laid out on the trunk grid (its wh x ww are trunk sizes)
 Mosaic pick_mosaic(const s2sr_handle* h, int B, int th, int tw) { return pick_mosaic_cfg(h->mosaic_on, B, th / h->unshuffle(), tw / h->unshuffle()); }
+// Windows per launch group of a job of T windows of th x tw (input sizes) that travels under `mo`: what the workspace allows,
+// in whole launch images.
+int group_windows(const s2sr_handle* h, const Mosaic& mo, int T, int th, int tw) {
+    const int u = h->unshuffle(), per = mo.per();
+    return group_size(h, (T + per - 1) / per, mo.image_h(th / u), mo.image_w(tw / u)) * per;
+}
 
 // [B,th,tw,3] u8 (device) -> u8 [B,S th,S tw,3] and/or f32 [B,3,S th,S tw] (device), S = cfg.scale.  At scale 2 th and tw are even
 // and the net runs on the th/2 x tw/2 trunk grid.  `src_h` x `src_w` (0: th x tw): the rows / columns the single input image holds
@@ -721,10 +736,9 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
     const int TH = th / u, TW = tw / u;                            // the trunk grid: what the schedule, workspace and graphs see
     // u8 tiles may travel as window mosaics; "images" below are then mosaics of per = kx*ky windows
     const Mosaic mo = !(d_tiles || in16) ? Mosaic() : (plan ? *plan : pick_mosaic(h, B, th, tw));
-    const int per = mo.on() ? mo.kx * mo.ky : 1;
-    const int IH = mo.on() ? mo.ky * (TH + 1) - 1 : TH, IW = mo.on() ? mo.kx * (TW + 1) - 1 : TW;   // the plan's image: the workspace geometry
-    const int NIplan = ((plan && plan->count > B ? plan->count : B) + per - 1) / per;
-    int G = group_size(h, NIplan, IH, IW);
+    const int per = mo.per();
+    const int IH = mo.image_h(TH), IW = mo.image_w(TW);            // the plan's image: the workspace geometry
+    int G = group_windows(h, mo, plan && plan->count > B ? plan->count : B, th, tw) / per;   // in images
     int rc = ensure_workspace(h, G, IH, IW, mo.on() ? TH + 1 : 0, mo.on() ? TW + 1 : 0);
     while (rc == S2SR_E_CAPACITY && G > 1) {          // the card is shared: fall back to smaller launch groups rather than fail the job
         G = (G + 1) / 2;
@@ -747,7 +761,7 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
     const Seg& sg = segs[si];
     const int sper = sg.kx * sg.ky;
     const int NI = (sg.nwin + sper - 1) / sper;                                // images of this segment
-    const int SH = mo.on() ? sg.ky * (TH + 1) - 1 : TH, SW = mo.on() ? sg.kx * (TW + 1) - 1 : TW;
+    const int SH = mo.on() ? mosaic_extent(sg.ky, TH) : TH, SW = mo.on() ? mosaic_extent(sg.kx, TW) : TW;
     for (int g0 = 0; g0 < NI; g0 += G) {
         const int n = (NI - g0 < G) ? (NI - g0) : G;
         const int t0 = sg.t0 + g0 * sper;                                     // first window / tile of this group
@@ -1230,7 +1244,7 @@ static int forward_batch_u8_once(s2sr_handle* h, const uint8_t* tiles, int32_t B
     if (!h || !tiles || !out) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const int S = h->cfg.scale, u = h->unshuffle();
+    const int S = h->cfg.scale;
     const size_t ib = (size_t)B * th * tw * 3, ob = ib * S * S;
     int rc = ensure_scratch(h, 0, ib);
     if (rc) return rc;
@@ -1241,15 +1255,10 @@ static int forward_batch_u8_once(s2sr_handle* h, const uint8_t* tiles, int32_t B
     // runs on the copy stream while group g+1 computes, so only the last group's copy is exposed.
     // one mosaic plan for the whole batch (ragged tiles): every group runs in the same workspace geometry
     const Mosaic mo = pick_mosaic(h, B, th, tw);
-    const int per = mo.on() ? mo.kx * mo.ky : 1;
-    const int G = (mo.on() ? group_size(h, (B + per - 1) / per, mo.ky * (mo.wh + 1) - 1, mo.kx * (mo.ww + 1) - 1) : group_size(h, B, th / u, tw / u)) * per;
+    const int G = group_windows(h, mo, B, th, tw);
     const size_t tin = (size_t)th * tw * 3, tout = tin * S * S;
     const int ngroups = (B + G - 1) / G;
-    while ((int)h->group_done.size() < ngroups) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->group_done.push_back(e);
-    }
+    if ((rc = ensure_group_events(h, ngroups))) return rc;
     for (int g = 0; g < ngroups; ++g) {
         const int g0 = g * G, n = (B - g0 < G) ? (B - g0) : G;
         rc = forward_dev(h, h->stream, (const uint8_t*)h->d_scratch[0] + g0 * tin, nullptr, n, th, tw,
@@ -1313,11 +1322,7 @@ static int forward_batch_u16_once(s2sr_handle* h, const uint16_t* tiles, int32_t
     HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], tiles, ib, hipMemcpyHostToDevice, h->stream));
     if ((rc = forward_u16_locked(h, h->stream, (const uint16_t*)h->d_scratch[0], B, th, tw, lo, hi, out_u16 ? (uint16_t*)h->d_scratch[2] : nullptr,
                                  (float*)h->d_scratch[1]))) return rc;
-    if (h->group_done.empty()) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->group_done.push_back(e);
-    }
+    if ((rc = ensure_group_events(h, 1))) return rc;
     HIPCHK(h, hipEventRecord(h->group_done[0], h->stream));
     HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[0], 0));
     if (out_u16 && (rc = d2h_staged(h, (uint8_t*)out_u16, (const uint8_t*)h->d_scratch[2], qb, true))) return rc;

@@ -92,6 +92,160 @@ void plan_chunk_sizes(int units, int u_max, long unit_windows, int per, long pim
     sizes.push_back(best_last);
 }
 
+// The reference's window plan of a PH x PW image (s2sr_plan_tiles, in its y-outer / x-inner order): ny rows of nx windows, all of
+// one shape wh x ww.
+struct TilePlan {
+    std::vector<s2sr_window> wins;
+    int nx = 0, ny = 0, wh = 0, ww = 0;
+};
+constexpr const char* kBadPlan = "window plan: s2sr_plan_tiles refuses these image / tile / pad sizes";
+static int plan_windows(int PH, int PW, int tile, int pad, int scale, TilePlan& p) {   // s2sr_plan_tiles' code
+    int T = 0;
+    int rc = s2sr_plan_tiles(PH, PW, tile, pad, scale, nullptr, 0, &T);
+    if (rc) return rc;
+    p.wins.resize(T);
+    if ((rc = s2sr_plan_tiles(PH, PW, tile, pad, scale, p.wins.data(), T, &T))) return rc;
+    p.nx = (PW + tile - 1) / tile; p.ny = (PH + tile - 1) / tile;
+    p.wh = p.wins[0].y2 - p.wins[0].y1; p.ww = p.wins[0].x2 - p.wins[0].x1;
+    return S2SR_OK;
+}
+
+// host-side maps of the paste rule; shared by enhance and the multi-GPU stitch
+static void build_stitch_maps(const TilePlan& p, int OH, int OW, std::vector<int32_t>& rm, std::vector<int32_t>& cm) {
+    rm.assign(2 * (size_t)OH, -1);
+    cm.assign(2 * (size_t)OW, -1);
+    // last window in loop order wins (:278): ascending index, later entries overwrite the map
+    for (int y = 0; y < p.ny; ++y) {
+        const s2sr_window& w = p.wins[(size_t)y * p.nx];
+        for (int oy = w.oy1; oy < w.oy2; ++oy) { rm[2 * oy] = y; rm[2 * oy + 1] = oy - w.oy1 + w.crop_top; }
+    }
+    for (int x = 0; x < p.nx; ++x) {
+        const s2sr_window& w = p.wins[x];
+        for (int ox = w.ox1; ox < w.ox2; ++ox) { cm[2 * ox] = x; cm[2 * ox + 1] = ox - w.ox1 + w.crop_left; }
+    }
+}
+
+// The window job of RealESRGAN.enhance on a PH x PW image (pure host arithmetic; s2sr_debug_plan_windows exposes it to the CPU
+// tests).  Callers that crop read the first OH x OW entries of the maps.  Returns s2sr_plan_tiles' code (sizes it refuses).
+int plan_window_job(int PH, int PW, int tile, int pad, int scale, bool tiled, WindowJob& job) {
+    job = WindowJob();
+    if (PH <= 0 || PW <= 0 || scale <= 0) return S2SR_E_INVALID;
+    if (!tiled) {   // the image is its own window: identity maps
+        job.wh = PH; job.ww = PW;
+        job.rm.resize(2 * (size_t)PH * scale); job.cm.resize(2 * (size_t)PW * scale);
+        for (int i = 0; i < PH * scale; ++i) { job.rm[2 * i] = 0; job.rm[2 * i + 1] = i; }
+        for (int i = 0; i < PW * scale; ++i) { job.cm[2 * i] = 0; job.cm[2 * i + 1] = i; }
+        return S2SR_OK;
+    }
+    TilePlan p;
+    if (int rc = plan_windows(PH, PW, tile, pad, scale, p)) return rc;
+    job.wh = p.wh; job.ww = p.ww;
+    build_stitch_maps(p, PH * scale, PW * scale, job.rm, job.cm);
+    // When a dimension ends within 2*pad of a tile multiple, the last two window rows (columns)
+    // of the plan are the same rectangle: the reference runs the net on both (only the paste
+    // ranges differ).  Identical inputs give identical outputs, so each distinct rectangle is
+    // forwarded once and the paste maps point at it.
+    std::vector<int> uy(p.ny), ux(p.nx), rows_y1, cols_x1;
+    for (int y = 0; y < p.ny; ++y) {
+        const int y1 = p.wins[(size_t)y * p.nx].y1;
+        if (rows_y1.empty() || rows_y1.back() != y1) rows_y1.push_back(y1);
+        uy[y] = (int)rows_y1.size() - 1;
+    }
+    for (int x = 0; x < p.nx; ++x) {
+        const int x1 = p.wins[x].x1;
+        if (cols_x1.empty() || cols_x1.back() != x1) cols_x1.push_back(x1);
+        ux[x] = (int)cols_x1.size() - 1;
+    }
+    for (size_t i = 0; i < job.rm.size(); i += 2)
+        if (job.rm[i] >= 0) job.rm[i] = uy[job.rm[i]];
+    for (size_t i = 0; i < job.cm.size(); i += 2)
+        if (job.cm[i] >= 0) job.cm[i] = ux[job.cm[i]];
+    job.nx = (int)cols_x1.size(); job.ny = (int)rows_y1.size();
+    job.rects.resize(4 * (size_t)job.nx * job.ny);
+    for (int y = 0; y < job.ny; ++y)
+        for (int x = 0; x < job.nx; ++x) {
+            const int t = y * job.nx + x;
+            job.rects[4 * t] = rows_y1[y]; job.rects[4 * t + 1] = rows_y1[y] + p.wh; job.rects[4 * t + 2] = cols_x1[x]; job.rects[4 * t + 3] = cols_x1[x] + p.ww;
+        }
+    return S2SR_OK;
+}
+
+// The job's rectangles and paste maps on the device (scratch 3), uploaded before this returns
+static int upload_window_job(s2sr_handle* h, hipStream_t st, const WindowJob& job, int32_t** d_rects, int32_t** d_rm, int32_t** d_cm) {
+    int rc = ensure_scratch(h, 3, (job.rects.size() + job.rm.size() + job.cm.size()) * 4);
+    if (rc) return rc;
+    *d_rects = (int32_t*)h->d_scratch[3];
+    *d_rm = *d_rects + job.rects.size();
+    *d_cm = *d_rm + job.rm.size();
+    if (!job.rects.empty()) HIPCHK(h, hipMemcpyAsync(*d_rects, job.rects.data(), job.rects.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(*d_rm, job.rm.data(), job.rm.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(*d_cm, job.cm.data(), job.cm.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));   // the job's vectors are host buffers of the caller
+    return S2SR_OK;
+}
+
+// The chunks of a tiled job: the first window row of each chunk, plus ny at the end.
+// Chunks of whole window rows.  An output row is final once the last window row that pastes into it is done (the row
+// map is monotone), so each chunk is followed by the stitch of its band of final rows, and the band's device-to-host
+// copy runs on the copy stream under the next chunk's compute.  A chunk holds whole launch groups: for windows that
+// travel as mosaics (forward_dev) rows in multiples of what fills a mosaic, and as many mosaics as the workspace
+// allows -- the patch count of a launch must be large against the 256 workgroups (one 4 x 4 mosaic of 276-pixel
+// windows is 1225 patches = 4.8 per CU, five rounds for 4.8 rounds of work; five mosaics are 23.9 -> 24).
+// Chunk sizes.  The device-to-host copy of a chunk's band hides under the NEXT chunk's compute and only the last band's
+// copy is exposed, so chunks shrink towards the end (a row of 276-pixel windows computes ~6x longer than its 13 MB band
+// takes to reach pageable host memory; a chunk may be up to 5x its successor).  What a small chunk costs is the rounding
+// of its patch count to whole rounds of the persistent workgroups in the trunk convs (32 x 32 patches; a 4 x 4 mosaic
+// of 276-pixel windows = 1225 patches = 4.8 rounds of 256: 1, 2, 3, 4 mosaics lose 4.3 %, 5 or 10 lose 0.3 %).  The
+// tail (last, middle) is searched over small sizes for the fewest rounds + exposed copy; the rest goes in front in
+// workspace-sized pieces.  4096 x 4096 at 256/10: 16 rows of 16 windows -> 10 + 5 + 1.
+// `mo`: the ONE mosaic plan of the job -- every chunk runs in its workspace geometry.
+static std::vector<int> plan_chunk_rows(const s2sr_handle* h, const WindowJob& job, const Mosaic& mo) {
+    const int nx = job.nx, ny = job.ny, u = h->unshuffle(), per = mo.per();
+    const int gw = group_windows(h, mo, nx * ny, job.wh, job.ww);               // windows per launch group
+    const int r_min = (per + nx - 1) / nx;                                      // rows that fill a mosaic
+    const int units = (ny + r_min - 1) / r_min;                                 // ... and how many such row units the image has
+    int u_max = gw / nx / r_min;                                                // units per chunk the workspace allows
+    if (u_max < 1) u_max = 1;
+    int ncu = 256;
+    (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
+    std::vector<int> sizes, chunk_r0;                                           // sizes: in units, front to back
+    plan_chunk_sizes(units, u_max, r_min * nx, per, mo.patches(job.wh / u, job.ww / u), ncu, sizes);
+    int r = 0;
+    for (int n : sizes) { chunk_r0.push_back(r); r += n * r_min; }
+    chunk_r0.push_back(ny);
+    return chunk_r0;
+}
+
+// The chunk loop of a tiled job: forward(t0, n) runs the net on windows [t0, t0 + n), finish(t0, yb, ye) turns the band of output
+// rows that chunk made final into image rows on the device (t0: the chunk's first window, for a door that keeps one chunk's
+// tiles).  `copy`: each band (row_b bytes per row, at dev, to host) leaves on the copy stream under the next chunk's compute,
+// the last one exposed.  Events group_done[0 .. nchunks) are the caller's to provide.
+template <class Forward, class Finish>
+static int run_chunks(s2sr_handle* h, hipStream_t st, const WindowJob& job, const std::vector<int>& chunk_r0, int OH, Forward forward,
+                      Finish finish, uint8_t* host, const uint8_t* dev, size_t row_b, bool copy) {
+    const int nx = job.nx, ny = job.ny, nchunks = (int)chunk_r0.size() - 1;
+    int rc, yb = 0, prev_yb = 0, prev_ye = 0;
+    for (int c = 0; c < nchunks; ++c) {
+        const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1] < ny ? chunk_r0[c + 1] : ny;
+        if ((rc = forward(r0 * nx, (r1 - r0) * nx))) return rc;
+        int ye = OH;
+        if (r1 < ny)
+            for (ye = yb; ye < OH && job.rm[2 * ye] < r1; ++ye) {}
+        if (ye > yb && (rc = finish(r0 * nx, yb, ye))) return rc;
+        HIPCHK(h, hipEventRecord(h->group_done[c], st));
+        if (copy && c > 0 && prev_ye > prev_yb) {
+            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[c - 1], 0));
+            if ((rc = d2h_staged(h, host + (size_t)prev_yb * row_b, dev + (size_t)prev_yb * row_b, (size_t)(prev_ye - prev_yb) * row_b, false))) return rc;
+        }
+        prev_yb = yb; prev_ye = ye; yb = ye;
+    }
+    if (copy && prev_ye > prev_yb) {
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
+        if ((rc = d2h_staged(h, host + (size_t)prev_yb * row_b, dev + (size_t)prev_yb * row_b, (size_t)(prev_ye - prev_yb) * row_b, true))) return rc;
+    }
+    return S2SR_OK;
+}
+
 }  // namespace s2sr::engine
 
 extern "C" {
@@ -123,22 +277,6 @@ int s2sr_plan_tiles(int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t sca
             w.oy2 = w.y2 * scale - w.crop_bottom;
         }
     return S2SR_OK;
-}
-
-// host-side maps of the paste rule; shared by enhance and the multi-GPU stitch
-static void build_stitch_maps(const std::vector<s2sr_window>& wins, int nx, int ny, int OH, int OW,
-                              std::vector<int32_t>& rm, std::vector<int32_t>& cm) {
-    rm.assign(2 * (size_t)OH, -1);
-    cm.assign(2 * (size_t)OW, -1);
-    // last window in loop order wins (:278): ascending index, later entries overwrite the map
-    for (int y = 0; y < ny; ++y) {
-        const s2sr_window& w = wins[(size_t)y * nx];
-        for (int oy = w.oy1; oy < w.oy2; ++oy) { rm[2 * oy] = y; rm[2 * oy + 1] = oy - w.oy1 + w.crop_top; }
-    }
-    for (int x = 0; x < nx; ++x) {
-        const s2sr_window& w = wins[x];
-        for (int ox = w.ox1; ox < w.ox2; ++ox) { cm[2 * ox] = x; cm[2 * ox + 1] = ox - w.ox1 + w.crop_left; }
-    }
 }
 
 // post-process on device buffers; the caller holds h->mu
@@ -290,7 +428,7 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
     if ((rc = plan_dims(h, H, W, tile, &PH, &PW))) return rc;
     // scale 2, odd H or W: everything below runs on the padded PH x PW image; the output is cropped to OH x OW by the stitch maps
     const bool reflect = PH != H || PW != W;
-    const int scale = h->cfg.scale, u = h->unshuffle(), OH = H * scale, OW = W * scale, OHp = PH * scale, OWp = PW * scale;
+    const int scale = h->cfg.scale, OH = H * scale, OW = W * scale, OHp = PH * scale, OWp = PW * scale;
     const size_t ib = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
     if ((rc = ensure_scratch(h, 0, ib))) return rc;
     if ((rc = ensure_scratch(h, 1, opx * (out_f32 ? 4 : 1)))) return rc;
@@ -307,15 +445,10 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
             rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[0], nullptr, 1, PH, PW, out_f32 ? nullptr : (uint8_t*)h->d_scratch[2],
                              out_f32 ? (float*)h->d_scratch[2] : nullptr, nullptr, H, W);
             if (rc) return rc;
-            std::vector<int32_t> rm(2 * OH), cm(2 * OW);
-            for (int i = 0; i < OH; ++i) { rm[2 * i] = 0; rm[2 * i + 1] = i; }
-            for (int i = 0; i < OW; ++i) { cm[2 * i] = 0; cm[2 * i + 1] = i; }
-            if ((rc = ensure_scratch(h, 3, (rm.size() + cm.size()) * 4))) return rc;
-            int32_t* d_rm = (int32_t*)h->d_scratch[3];
-            int32_t* d_cm = d_rm + rm.size();
-            HIPCHK(h, hipMemcpyAsync(d_rm, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipMemcpyAsync(d_cm, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
-            HIPCHK(h, hipStreamSynchronize(st));   // rm/cm are stack-owned host buffers
+            WindowJob job;
+            if ((rc = plan_window_job(PH, PW, tile, pad, scale, false, job))) return fail(h, rc, kBadPlan);
+            int32_t *d_rects, *d_rm, *d_cm;
+            if ((rc = upload_window_job(h, st, job, &d_rects, &d_rm, &d_cm))) return rc;
             if (out_f32) HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
             else HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
         } else {
@@ -323,87 +456,18 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
             if (rc) return rc;
         }
     } else {
-        int T = 0;
-        s2sr_plan_tiles(PH, PW, tile, pad, scale, nullptr, 0, &T);
-        std::vector<s2sr_window> wins(T);
-        s2sr_plan_tiles(PH, PW, tile, pad, scale, wins.data(), T, &T);
-        const int pnx = (PW + tile - 1) / tile, pny = (PH + tile - 1) / tile;    // the reference's plan
-        const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;   // all windows share one shape
-        std::vector<int32_t> rm, cm;
-        build_stitch_maps(wins, pnx, pny, OHp, OWp, rm, cm);                    // (the stitches read the first OH x OW of them)
-        // When a dimension ends within 2*pad of a tile multiple, the last two window rows (columns)
-        // of the plan are the same rectangle: the reference runs the net on both (only the paste
-        // ranges differ).  Identical inputs give identical outputs, so each distinct rectangle is
-        // forwarded once and the paste maps point at it.
-        std::vector<int> uy(pny), ux(pnx), rows_y1, cols_x1;
-        for (int y = 0; y < pny; ++y) {
-            const int y1 = wins[(size_t)y * pnx].y1;
-            if (rows_y1.empty() || rows_y1.back() != y1) rows_y1.push_back(y1);
-            uy[y] = (int)rows_y1.size() - 1;
-        }
-        for (int x = 0; x < pnx; ++x) {
-            const int x1 = wins[x].x1;
-            if (cols_x1.empty() || cols_x1.back() != x1) cols_x1.push_back(x1);
-            ux[x] = (int)cols_x1.size() - 1;
-        }
-        for (size_t i = 0; i < rm.size(); i += 2)
-            if (rm[i] >= 0) rm[i] = uy[rm[i]];
-        for (size_t i = 0; i < cm.size(); i += 2)
-            if (cm[i] >= 0) cm[i] = ux[cm[i]];
-        const int nx = (int)cols_x1.size(), ny = (int)rows_y1.size();
-        T = nx * ny;
-        std::vector<int32_t> rects(4 * (size_t)T);
-        for (int y = 0; y < ny; ++y)
-            for (int x = 0; x < nx; ++x) {
-                const int t = y * nx + x;
-                rects[4 * t] = rows_y1[y]; rects[4 * t + 1] = rows_y1[y] + wh; rects[4 * t + 2] = cols_x1[x]; rects[4 * t + 3] = cols_x1[x] + ww;
-            }
+        WindowJob job;
+        if ((rc = plan_window_job(PH, PW, tile, pad, scale, true, job))) return fail(h, rc, kBadPlan);
+        const int nx = job.nx, wh = job.wh, ww = job.ww, T = nx * job.ny;
         const size_t tin = (size_t)T * wh * ww * 3, tout = tin * scale * scale;
         if ((rc = ensure_scratch(h, 2, tin))) return rc;
         if ((rc = ensure_scratch(h, 4, tout * (out_f32 ? 4 : 1)))) return rc;
-        if ((rc = ensure_scratch(h, 3, (rects.size() + rm.size() + cm.size()) * 4))) return rc;
-        int32_t* d_rects = (int32_t*)h->d_scratch[3];
-        int32_t* d_rm = d_rects + rects.size();
-        int32_t* d_cm = d_rm + rm.size();
-        HIPCHK(h, hipMemcpyAsync(d_rects, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(d_rm, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync(d_cm, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipStreamSynchronize(st));
+        int32_t *d_rects, *d_rm, *d_cm;
+        if ((rc = upload_window_job(h, st, job, &d_rects, &d_rm, &d_cm))) return rc;
         if (reflect) HIPCHK(h, launch_gather_windows_reflect((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
         else HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
-        // Chunks of whole window rows.  An output row is final once the last window row that pastes into it is done (the row
-        // map is monotone), so each chunk is followed by the stitch of its band of final rows, and the band's device-to-host
-        // copy runs on the copy stream under the next chunk's compute.  A chunk holds whole launch groups: for windows that
-        // travel as mosaics (forward_dev) rows in multiples of what fills a mosaic, and as many mosaics as the workspace
-        // allows -- the patch count of a launch must be large against the 256 workgroups (one 4 x 4 mosaic of 276-pixel
-        // windows is 1225 patches = 4.8 per CU, five rounds for 4.8 rounds of work; five mosaics are 23.9 -> 24).
-        // Chunk sizes.  The device-to-host copy of a chunk's band hides under the NEXT chunk's compute and only the last band's
-        // copy is exposed, so chunks shrink towards the end (a row of 276-pixel windows computes ~6x longer than its 13 MB band
-        // takes to reach pageable host memory; a chunk may be up to 5x its successor).  What a small chunk costs is the rounding
-        // of its patch count to whole rounds of the persistent workgroups in the trunk convs (32 x 32 patches; a 4 x 4 mosaic
-        // of 276-pixel windows = 1225 patches = 4.8 rounds of 256: 1, 2, 3, 4 mosaics lose 4.3 %, 5 or 10 lose 0.3 %).  The
-        // tail (last, middle) is searched over small sizes for the fewest rounds + exposed copy; the rest goes in front in
-        // workspace-sized pieces.  4096 x 4096 at 256/10: 16 rows of 16 windows -> 10 + 5 + 1.
-        std::vector<int> chunk_r0;   // first window row of each chunk, plus ny at the end
         const Mosaic mo = pick_mosaic(h, T, wh, ww);   // ONE plan for the job: every chunk runs in its workspace geometry
-        {
-            const int per = mo.on() ? mo.kx * mo.ky : 1;
-            const int gw = (mo.on() ? group_size(h, (T + per - 1) / per, mo.ky * (mo.wh + 1) - 1, mo.kx * (mo.ww + 1) - 1)
-                                    : group_size(h, T, wh / u, ww / u)) * per;          // windows per launch group
-            const int r_min = (per + nx - 1) / nx;                                      // rows that fill a mosaic
-            const int units = (ny + r_min - 1) / r_min;                                 // ... and how many such row units the image has
-            int u_max = gw / nx / r_min;                                                // units per chunk the workspace allows
-            if (u_max < 1) u_max = 1;
-            int ncu = 256;
-            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-            const long pimg = mo.on() ? (long)((mo.ky * (mo.wh + 1) - 1 + 31) / 32) * ((mo.kx * (mo.ww + 1) - 1 + 31) / 32)
-                                      : (long)((wh / u + 31) / 32) * ((ww / u + 31) / 32);   // 32 x 32 patches per launch image
-            std::vector<int> sizes;                                                     // in units, front to back
-            plan_chunk_sizes(units, u_max, r_min * nx, per, pimg, ncu, sizes);
-            int r = 0;
-            for (int u : sizes) { chunk_r0.push_back(r); r += u * r_min; }
-            chunk_r0.push_back(ny);
-        }
+        const std::vector<int> chunk_r0 = plan_chunk_rows(h, job, mo);
         const int nchunks = (int)chunk_r0.size() - 1;
         if (!out_f32 && nchunks > 1) {
             // A job (job_rgb / prm) takes the same route: the channel swap behind the net is applied to every band as it is stitched;
@@ -424,46 +488,22 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
             // this job's run took scratch 5 from whatever run a caller had open there: it ends with the job on every way out, so
             // that caller's next hist / lut / rows is refused
             struct CloseRun { s2sr_handle* h; ~CloseRun() { if (h) h->ppb.open = false; } } close_run{prm ? h : nullptr};
-            while ((int)h->group_done.size() < nchunks + nfin) {
-                hipEvent_t e;
-                HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                h->group_done.push_back(e);
-            }
+            if ((rc = ensure_group_events(h, nchunks + nfin))) return rc;
             uint8_t* d_img_out = (uint8_t*)h->d_scratch[1];
-            int yb = 0, prev_yb = 0, prev_ye = 0;
-            for (int c = 0; c < nchunks; ++c) {
-                const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1] < ny ? chunk_r0[c + 1] : ny;
-                const int t0 = r0 * nx, n = (r1 - r0) * nx;
-                rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[2] + t0 * win_in, nullptr, n, wh, ww,
-                                 (uint8_t*)h->d_scratch[4] + t0 * win_out, nullptr, mo.on() ? &mo : nullptr);
-                if (rc) return rc;
-                int ye = OH;
-                if (r1 < ny)
-                    for (ye = yb; ye < OH && rm[2 * ye] < r1; ++ye) {}
-                if (ye > yb) {
-                    HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW,
-                                               d_img_out + (size_t)yb * row_b, st));
-                    if (prm) {
-                        if ((rc = pp_band_hist_locked(h, d_img_out, yb, ye, st))) return rc;
-                    } else if (job_rgb) {
-                        HIPCHK(h, launch_swap_rb_u8(d_img_out + (size_t)yb * row_b, (size_t)(ye - yb) * OW, d_img_out + (size_t)yb * row_b, st));
-                    }
-                }
-                HIPCHK(h, hipEventRecord(h->group_done[c], st));
-                if (!prm && c > 0 && prev_ye > prev_yb) {
-                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[c - 1], 0));
-                    if ((rc = d2h_staged(h, out_u8 + (size_t)prev_yb * row_b, d_img_out + (size_t)prev_yb * row_b,
-                                         (size_t)(prev_ye - prev_yb) * row_b, false))) return rc;
-                }
-                prev_yb = yb; prev_ye = ye; yb = ye;
-            }
-            if (!prm) {
-                if (prev_ye > prev_yb) {
-                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
-                    if ((rc = d2h_staged(h, out_u8 + (size_t)prev_yb * row_b, d_img_out + (size_t)prev_yb * row_b,
-                                         (size_t)(prev_ye - prev_yb) * row_b, true))) return rc;
-                }
-            } else {
+            auto forward = [&](int t0, int n) {
+                return forward_dev(h, st, (const uint8_t*)h->d_scratch[2] + t0 * win_in, nullptr, n, wh, ww,
+                                   (uint8_t*)h->d_scratch[4] + t0 * win_out, nullptr, mo.on() ? &mo : nullptr);
+            };
+            auto finish = [&](int, int yb, int ye) -> int {   // (scratch 4 holds every window's output)
+                HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW,
+                                           d_img_out + (size_t)yb * row_b, st));
+                if (prm) return pp_band_hist_locked(h, d_img_out, yb, ye, st);
+                if (job_rgb) HIPCHK(h, launch_swap_rb_u8(d_img_out + (size_t)yb * row_b, (size_t)(ye - yb) * OW, d_img_out + (size_t)yb * row_b, st));
+                return S2SR_OK;
+            };
+            // with a post-process no band is copied here: the bands leave through the finishing pass below
+            if ((rc = run_chunks(h, st, job, chunk_r0, OH, forward, finish, out_u8, d_img_out, row_b, !prm))) return rc;
+            if (prm) {
                 // LUTs, then every finishing band's kernels (in place: a band's rows are rewritten only after the apply pass, which
                 // runs R rows ahead, has read them), an event behind each; the copies follow band by band on the copy stream
                 const bool timing = getenv("S2SR_JOB_TIMING") != nullptr;     // diagnostic: stage times of the finish on stderr
@@ -510,11 +550,7 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
             d_final = (const uint8_t*)h->d_scratch[4];
         }
     }
-    if (h->group_done.empty()) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->group_done.push_back(e);
-    }
+    if ((rc = ensure_group_events(h, 1))) return rc;
     HIPCHK(h, hipEventRecord(h->group_done[0], st));
     HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[0], 0));
     if ((rc = d2h_staged(h, out_f32 ? (uint8_t*)out_f32 : out_u8, out_f32 ? (const uint8_t*)h->d_scratch[1] : d_final, opx * (out_f32 ? 4 : 1), true))) return rc;
@@ -561,69 +597,13 @@ static int enhance16_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int
     if ((rc = ensure_scratch(h, 1, q_bytes + (out_f32 ? opx * 4 : 0)))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, ipx * 2, hipMemcpyHostToDevice, st));
     const bool tiled = (long long)H * W > (long long)tile * tile * 4;   // strict '>' (:226)
-    // the windows the net runs on (ny rows of nx, wh x ww each), the paste maps and the chunks of window rows
-    int nx = 1, ny = 1, wh = H, ww = W;
-    std::vector<int32_t> rm, cm, rects;
-    std::vector<int> chunk_r0;   // first window row of each chunk, plus ny at the end
-    Mosaic mo;
-    const uint16_t* d_win = (const uint16_t*)h->d_scratch[0];
-    if (!tiled) {
-        rm.resize(2 * (size_t)OH); cm.resize(2 * (size_t)OW);
-        for (int i = 0; i < OH; ++i) { rm[2 * i] = 0; rm[2 * i + 1] = i; }
-        for (int i = 0; i < OW; ++i) { cm[2 * i] = 0; cm[2 * i + 1] = i; }
-        chunk_r0 = {0, 1};
-    } else {
-        int T = 0;
-        s2sr_plan_tiles(H, W, tile, pad, scale, nullptr, 0, &T);
-        std::vector<s2sr_window> wins(T);
-        s2sr_plan_tiles(H, W, tile, pad, scale, wins.data(), T, &T);
-        const int pnx = (W + tile - 1) / tile, pny = (H + tile - 1) / tile;    // the reference's plan
-        wh = wins[0].y2 - wins[0].y1; ww = wins[0].x2 - wins[0].x1;            // all windows share one shape
-        build_stitch_maps(wins, pnx, pny, OH, OW, rm, cm);
-        // each distinct window rectangle is forwarded once (enhance_impl: the last two rows / columns of a plan can coincide)
-        std::vector<int> uy(pny), ux(pnx), rows_y1, cols_x1;
-        for (int y = 0; y < pny; ++y) {
-            const int y1 = wins[(size_t)y * pnx].y1;
-            if (rows_y1.empty() || rows_y1.back() != y1) rows_y1.push_back(y1);
-            uy[y] = (int)rows_y1.size() - 1;
-        }
-        for (int x = 0; x < pnx; ++x) {
-            const int x1 = wins[x].x1;
-            if (cols_x1.empty() || cols_x1.back() != x1) cols_x1.push_back(x1);
-            ux[x] = (int)cols_x1.size() - 1;
-        }
-        for (size_t i = 0; i < rm.size(); i += 2)
-            if (rm[i] >= 0) rm[i] = uy[rm[i]];
-        for (size_t i = 0; i < cm.size(); i += 2)
-            if (cm[i] >= 0) cm[i] = ux[cm[i]];
-        nx = (int)cols_x1.size(); ny = (int)rows_y1.size();
-        T = nx * ny;
-        rects.resize(4 * (size_t)T);
-        for (int y = 0; y < ny; ++y)
-            for (int x = 0; x < nx; ++x) {
-                const int t = y * nx + x;
-                rects[4 * t] = rows_y1[y]; rects[4 * t + 1] = rows_y1[y] + wh; rects[4 * t + 2] = cols_x1[x]; rects[4 * t + 3] = cols_x1[x] + ww;
-            }
-        mo = pick_mosaic(h, T, wh, ww);   // ONE plan for the job: every chunk runs in its workspace geometry
-        if (out_f32) chunk_r0 = {0, ny};  // the fp32 image is stitched from all the tiles at the end
-        else {                            // enhance_impl's chunk plan
-            const int per = mo.on() ? mo.kx * mo.ky : 1;
-            const int gw = (mo.on() ? group_size(h, (T + per - 1) / per, mo.ky * (mo.wh + 1) - 1, mo.kx * (mo.ww + 1) - 1) : group_size(h, T, wh, ww)) * per;
-            const int r_min = (per + nx - 1) / nx;
-            const int units = (ny + r_min - 1) / r_min;
-            int u_max = gw / nx / r_min;
-            if (u_max < 1) u_max = 1;
-            int ncu = 256;
-            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
-            const long pimg = mo.on() ? (long)((mo.ky * (mo.wh + 1) - 1 + 31) / 32) * ((mo.kx * (mo.ww + 1) - 1 + 31) / 32)
-                                      : (long)((wh + 31) / 32) * ((ww + 31) / 32);
-            std::vector<int> sizes;
-            plan_chunk_sizes(units, u_max, r_min * nx, per, pimg, ncu, sizes);
-            int r = 0;
-            for (int u : sizes) { chunk_r0.push_back(r); r += u * r_min; }
-            chunk_r0.push_back(ny);
-        }
-    }
+    // the windows the net runs on, the paste maps and the chunks of window rows
+    WindowJob job;
+    if ((rc = plan_window_job(H, W, tile, pad, scale, tiled, job))) return fail(h, rc, kBadPlan);
+    const int nx = job.nx, ny = job.ny, wh = job.wh, ww = job.ww;
+    const Mosaic mo = tiled ? pick_mosaic(h, nx * ny, wh, ww) : Mosaic();   // ONE plan for the job: every chunk runs in its workspace geometry
+    // one chunk for the untiled image, and with out_f32: the fp32 image is stitched from all the tiles at the end
+    const std::vector<int> chunk_r0 = tiled && !out_f32 ? plan_chunk_rows(h, job, mo) : std::vector<int>{0, ny};
     const int nchunks = (int)chunk_r0.size() - 1;
     int max_rows = 0;
     for (int c = 0; c < nchunks; ++c) {
@@ -633,61 +613,41 @@ static int enhance16_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int
     const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;      // samples per window, in and out
     if (tiled && (rc = ensure_scratch(h, 2, (size_t)nx * ny * win_in * 2))) return rc;
     if ((rc = ensure_scratch(h, 4, (size_t)max_rows * nx * win_out * sizeof(float)))) return rc;
-    if ((rc = ensure_scratch(h, 3, (rects.size() + rm.size() + cm.size()) * 4))) return rc;
-    int32_t* d_rects = (int32_t*)h->d_scratch[3];
-    int32_t* d_rm = d_rects + rects.size();
-    int32_t* d_cm = d_rm + rm.size();
-    if (!rects.empty()) HIPCHK(h, hipMemcpyAsync(d_rects, rects.data(), rects.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(d_rm, rm.data(), rm.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(d_cm, cm.data(), cm.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));
+    int32_t *d_rects, *d_rm, *d_cm;
+    if ((rc = upload_window_job(h, st, job, &d_rects, &d_rm, &d_cm))) return rc;
+    const uint16_t* d_win = (const uint16_t*)h->d_scratch[0];
     if (tiled) {
         HIPCHK(h, launch_gather_windows_u16((const uint16_t*)h->d_scratch[0], H, W, d_rects, nx * ny, wh, ww, (uint16_t*)h->d_scratch[2], st));
         d_win = (const uint16_t*)h->d_scratch[2];
     }
-    while ((int)h->group_done.size() < nchunks + 1) {
-        hipEvent_t e;
-        HIPCHK(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->group_done.push_back(e);
-    }
+    if ((rc = ensure_group_events(h, nchunks + 1))) return rc;
     uint16_t* d_q = (uint16_t*)h->d_scratch[1];
     float* d_tiles = (float*)h->d_scratch[4];
     const size_t row_b = (size_t)OW * 3 * 2;                     // bytes of one output row
-    int yb = 0, prev_yb = 0, prev_ye = 0;
-    for (int c = 0; c < nchunks; ++c) {
-        const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1] < ny ? chunk_r0[c + 1] : ny;
-        const int t0 = r0 * nx, n = (r1 - r0) * nx;
+    auto forward = [&](int t0, int n) {
         const U16In in16{d_win + (size_t)t0 * win_in, lo, hi};
-        if ((rc = forward_dev(h, st, nullptr, nullptr, n, wh, ww, nullptr, d_tiles, mo.on() ? &mo : nullptr, 0, 0, &in16))) return rc;
-        int ye = OH;
-        if (r1 < ny)
-            for (ye = yb; ye < OH && rm[2 * ye] < r1; ++ye) {}
-        if (out_u16 && ye > yb) {   // the band's rows come from window rows [r0, r1) only (the row map is monotone): tiles of this chunk
-            Scope sc(h, st, F_MISC, 0.0, (double)(ye - yb) * OW * 3.0 * (4.0 + 2.0));
-            HIPCHK(h, launch_stitch_quant_u16(d_tiles, nx, t0, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW, lo, hi,
-                                              d_q + (size_t)yb * OW * 3, st));
-        }
-        HIPCHK(h, hipEventRecord(h->group_done[c], st));
-        if (out_u16 && c > 0 && prev_ye > prev_yb) {
-            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[c - 1], 0));
-            if ((rc = d2h_staged(h, (uint8_t*)out_u16 + (size_t)prev_yb * row_b, (const uint8_t*)d_q + (size_t)prev_yb * row_b,
-                                 (size_t)(prev_ye - prev_yb) * row_b, false))) return rc;
-        }
-        prev_yb = yb; prev_ye = ye; yb = ye;
-    }
-    if (out_f32) {   // (one chunk: d_tiles holds every window)
+        return forward_dev(h, st, nullptr, nullptr, n, wh, ww, nullptr, d_tiles, mo.on() ? &mo : nullptr, 0, 0, &in16);
+    };
+    // the band's rows come from the chunk's window rows only (the row map is monotone): d_tiles holds them, from window t0 on
+    auto finish = [&](int t0, int yb, int ye) -> int {
+        if (!out_u16) return S2SR_OK;
+        Scope sc(h, st, F_MISC, 0.0, (double)(ye - yb) * OW * 3.0 * (4.0 + 2.0));
+        HIPCHK(h, launch_stitch_quant_u16(d_tiles, nx, t0, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW, lo, hi,
+                                          d_q + (size_t)yb * OW * 3, st));
+        return S2SR_OK;
+    };
+    // with out_f32 (one chunk: d_tiles holds every window) both images leave behind the fp32 stitch
+    if ((rc = run_chunks(h, st, job, chunk_r0, OH, forward, finish, (uint8_t*)out_u16, (const uint8_t*)d_q, row_b, out_u16 && !out_f32))) return rc;
+    if (out_f32) {
         float* d_f = (float*)((char*)h->d_scratch[1] + q_bytes);
         HIPCHK(h, launch_stitch_f32(d_tiles, nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, d_f, st));
         HIPCHK(h, hipEventRecord(h->group_done[nchunks], st));
-    }
-    if (out_u16 && prev_ye > prev_yb) {
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
-        if ((rc = d2h_staged(h, (uint8_t*)out_u16 + (size_t)prev_yb * row_b, (const uint8_t*)d_q + (size_t)prev_yb * row_b,
-                             (size_t)(prev_ye - prev_yb) * row_b, true))) return rc;
-    }
-    if (out_f32) {
+        if (out_u16) {
+            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
+            if ((rc = d2h_staged(h, (uint8_t*)out_u16, (const uint8_t*)d_q, OH * row_b, true))) return rc;
+        }
         HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks], 0));
-        if ((rc = d2h_staged(h, (uint8_t*)out_f32, (const uint8_t*)h->d_scratch[1] + q_bytes, opx * 4, true))) return rc;
+        if ((rc = d2h_staged(h, (uint8_t*)out_f32, (const uint8_t*)d_f, opx * 4, true))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     HIPCHK(h, hipStreamSynchronize(st));
@@ -705,17 +665,16 @@ int s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
-    int T = 0, PH, PW;
+    int PH, PW;
     int rc = plan_dims(h, H, W, tile, &PH, &PW);
     if (rc) return rc;
-    s2sr_plan_tiles(PH, PW, tile, pad, h->cfg.scale, nullptr, 0, &T);
-    if (first + count > T) return fail(h, S2SR_E_INVALID, "window range exceeds the plan");
-    std::vector<s2sr_window> wins(T);
-    s2sr_plan_tiles(PH, PW, tile, pad, h->cfg.scale, wins.data(), T, &T);
-    const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;
+    TilePlan p;                                                         // the reference's plan: s2sr/dist.py indexes windows by plan position
+    if ((rc = plan_windows(PH, PW, tile, pad, h->cfg.scale, p))) return fail(h, rc, kBadPlan);
+    if (first + count > (int)p.wins.size()) return fail(h, S2SR_E_INVALID, "window range exceeds the plan");
+    const int wh = p.wh, ww = p.ww;
     std::vector<int32_t> rects(4 * (size_t)count);
     for (int t = 0; t < count; ++t) {
-        const s2sr_window& w = wins[first + t];
+        const s2sr_window& w = p.wins[first + t];
         rects[4 * t] = w.y1; rects[4 * t + 1] = w.y2; rects[4 * t + 2] = w.x1; rects[4 * t + 3] = w.x2;
     }
     rc = ensure_scratch(h, 3, rects.size() * 4);
@@ -736,14 +695,12 @@ int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int3
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
     const int S = h->cfg.scale;
-    int T = 0, PH, PW;
+    int PH, PW;
     int rc = plan_dims(h, H, W, tile, &PH, &PW);
     if (rc) return rc;
-    s2sr_plan_tiles(PH, PW, tile, pad, S, nullptr, 0, &T);
-    std::vector<s2sr_window> wins(T);
-    s2sr_plan_tiles(PH, PW, tile, pad, S, wins.data(), T, &T);
-    const int nx = (PW + tile - 1) / tile, ny = (PH + tile - 1) / tile;
-    const int wh = wins[0].y2 - wins[0].y1, ww = wins[0].x2 - wins[0].x1;
+    TilePlan p;                                              // the reference's plan, as s2sr_cut_windows_u8_dev cuts it
+    if ((rc = plan_windows(PH, PW, tile, pad, S, p))) return fail(h, rc, kBadPlan);
+    const int nx = p.nx, wh = p.wh, ww = p.ww;
     const size_t nrm = 2 * (size_t)(S * PH), ncm = 2 * (size_t)(S * PW);   // maps of the padded image; the stitch reads S H x S W
     // the plan's paste maps: from the handle's LRU of map sets, or built and uploaded now.  A NEW set costs an allocation and a
     // blocking upload on the handle's own stream -- nothing the caller has queued on ITS stream is waited for (r04: any key change
@@ -773,7 +730,7 @@ int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int3
             ms->cap = (nrm + ncm) * 4;
         }
         std::vector<int32_t> rm, cm;
-        build_stitch_maps(wins, nx, ny, S * PH, S * PW, rm, cm);
+        build_stitch_maps(p, S * PH, S * PW, rm, cm);
         HIPCHK(h, copy_blocking(h, ms->d, rm.data(), nrm * 4, hipMemcpyHostToDevice));
         HIPCHK(h, copy_blocking(h, ms->d + nrm, cm.data(), ncm * 4, hipMemcpyHostToDevice));
         for (int i = 0; i < 4; ++i) ms->key[i] = key[i];

@@ -30,9 +30,9 @@ int tap_plan(s2sr_handle* h, bool u8, int32_t B, int32_t th, int32_t tw, int32_t
     const int job = job_windows > B ? job_windows : B;
     const int u = h->unshuffle();
     if (th % u || tw % u) return fail(h, S2SR_E_INVALID, "a scale-2 handle (pixel_unshuffle by 2) needs even tile sizes");
-    th /= u; tw /= u;                                   // the trunk grid from here on
-    Mosaic plan = u8 ? pick_mosaic_cfg(h->mosaic_on, job, th, tw) : Mosaic();
-    const int per = plan.on() ? plan.kx * plan.ky : 1;
+    const int TH = th / u, TW = tw / u;                 // the trunk grid
+    Mosaic plan = u8 ? pick_mosaic_cfg(h->mosaic_on, job, TH, TW) : Mosaic();
+    const int per = plan.per();
     int skx = plan.kx, sky = plan.ky;
     if (plan.on()) {
         if (B / per && B % per) return fail(h, S2SR_E_INVALID, "batch spans two mosaic segments (full mosaics and a remainder)");
@@ -41,9 +41,9 @@ int tap_plan(s2sr_handle* h, bool u8, int32_t B, int32_t th, int32_t tw, int32_t
     const int sper = plan.on() ? skx * sky : 1;
     tp->plan = plan; tp->skx = skx; tp->sky = sky;
     tp->NI = (B + sper - 1) / sper;
-    tp->IH = plan.on() ? plan.ky * (th + 1) - 1 : th; tp->IW = plan.on() ? plan.kx * (tw + 1) - 1 : tw;
-    tp->SH = plan.on() ? sky * (th + 1) - 1 : th; tp->SW = plan.on() ? skx * (tw + 1) - 1 : tw;
-    if (tp->NI > group_size(h, (job + per - 1) / per, tp->IH, tp->IW)) return fail(h, S2SR_E_INVALID, "batch needs more than one launch group");
+    tp->IH = plan.image_h(TH); tp->IW = plan.image_w(TW);
+    tp->SH = plan.on() ? mosaic_extent(sky, TH) : TH; tp->SW = plan.on() ? mosaic_extent(skx, TW) : TW;
+    if (tp->NI > group_windows(h, plan, job, th, tw) / per) return fail(h, S2SR_E_INVALID, "batch needs more than one launch group");
     return S2SR_OK;
 }
 // ... and the run: forward_dev -> run_net eagerly (graphs off for the call) on buffers of its own, outputs copied back
@@ -97,6 +97,19 @@ int s2sr_debug_plan_chunks(int32_t units, int32_t u_max, int32_t unit_windows, i
     *n = (int32_t)v.size();
     if ((int)v.size() > cap) return cap == 0 ? S2SR_OK : S2SR_E_CAPACITY;
     for (size_t i = 0; i < v.size(); ++i) sizes[i] = v[i];
+    return S2SR_OK;
+}
+
+int s2sr_debug_plan_windows(int32_t PH, int32_t PW, int32_t tile, int32_t pad, int32_t scale, int32_t tiled, int32_t* dims,
+                            int32_t* rects, int32_t cap, int32_t* rm, int32_t* cm) {
+    if (!dims || !rects || !rm || !cm || PH <= 0 || PW <= 0 || tile <= 0 || pad < 0 || scale <= 0 || cap < 0) return S2SR_E_INVALID;
+    WindowJob job;
+    if (int rc = plan_window_job(PH, PW, tile, pad, scale, tiled != 0, job)) return rc;
+    dims[0] = job.nx; dims[1] = job.ny; dims[2] = job.wh; dims[3] = job.ww;
+    if (job.rects.size() > 4 * (size_t)cap) return S2SR_E_CAPACITY;
+    memcpy(rects, job.rects.data(), job.rects.size() * 4);
+    memcpy(rm, job.rm.data(), job.rm.size() * 4);
+    memcpy(cm, job.cm.data(), job.cm.size() * 4);
     return S2SR_OK;
 }
 

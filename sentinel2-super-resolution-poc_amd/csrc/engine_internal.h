@@ -72,9 +72,16 @@ struct EvRec {
 };
 
 // Window mosaic geometry of one forward (see ConvParams::mos_*): kx x ky windows of wh x ww per image, `count` windows in all.
+inline int mosaic_extent(int k, int w) { return k * (w + 1) - 1; }   // rows / columns of k windows of w with their separators
 struct Mosaic {
     int kx = 1, ky = 1, wh = 0, ww = 0, count = 0;
     bool on() const { return wh > 0; }
+    // per launch image, for windows of th x tw on the trunk grid: windows, rows, columns, 32 x 32 patches.  A mosaic that is on was
+    // picked for these very windows (pick_mosaic sets wh x ww = th x tw), so it answers from its own wh x ww; th, tw serve the plain image.
+    int per() const { return on() ? kx * ky : 1; }
+    int image_h(int th) const { return on() ? mosaic_extent(ky, wh) : th; }
+    int image_w(int tw) const { return on() ? mosaic_extent(kx, ww) : tw; }
+    long patches(int th, int tw) const { return (long)((image_h(th) + 31) / 32) * ((image_w(tw) + 31) / 32); }
 };
 
 // One captured group (pack + the whole layer schedule) for fixed shapes and buffers.  A net is
@@ -246,6 +253,7 @@ int decode_f16_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img,
 int decode_e4m3_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img, int n, int nb, size_t blk, const float* scale);
 
 hipEvent_t get_event(s2sr_handle* h);
+int ensure_group_events(s2sr_handle* h, int n);
 
 struct Scope {   // brackets one launch with events when profiling is on
     s2sr_handle* h;
@@ -269,6 +277,7 @@ struct Scope {   // brackets one launch with events when profiling is on
 };
 
 int group_size(const s2sr_handle* h, int B, int H, int W);
+int group_windows(const s2sr_handle* h, const Mosaic& mo, int T, int th, int tw);
 void mosaic_remainder(int rem, int kx, int ky, int* rkx, int* rky);
 long mosaic_patches(int B, int th, int tw, int kx, int ky);
 Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw);
@@ -282,5 +291,13 @@ int check_u16(s2sr_handle* h, int lo, int hi);
 constexpr size_t kStageBytes = 32u << 20;   // one pinned staging slice (s2sr_handle::stage_buf)
 int d2h_staged(s2sr_handle* h, uint8_t* dst, const uint8_t* src, size_t bytes, bool exposed);
 void plan_chunk_sizes(int units, int u_max, long unit_windows, int per, long pimg, int ncu, std::vector<int>& sizes);
+// The windows a whole-image call runs the net on: ny rows of nx distinct windows of wh x ww, their rectangles (y1, y2, x1, x2 each,
+// row-major; empty for the untiled image, which is its own window) and the paste maps of the scale PH x scale PW output: per output
+// row (column) the window row (column) it comes from and the row (column) inside that window's output.
+struct WindowJob {
+    int nx = 1, ny = 1, wh = 0, ww = 0;
+    std::vector<int32_t> rects, rm, cm;
+};
+int plan_window_job(int PH, int PW, int tile, int pad, int scale, bool tiled, WindowJob& job);
 
 }  // namespace s2sr::engine

@@ -176,6 +176,7 @@ _PROTOS = {
     "s2sr_debug_pick_mosaic": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 2),
     "s2sr_debug_mosaic_patches": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_int64)] * 2),
     "s2sr_debug_plan_chunks": (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
+    "s2sr_debug_plan_windows": (C.c_int, [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "s2sr_debug_get_config": (C.c_int, [C.c_void_p, C.POINTER(DebugConfig)]),
     "s2sr_debug_conv_trunk": (C.c_int, [C.c_void_p, C.POINTER(DebugTrunkArgs)]),
     "s2sr_debug_forward_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(DebugTaps)]),
@@ -382,6 +383,19 @@ def plan_chunks(units: int, u_max: int, unit_windows: int, per: int, pimg: int, 
     if rc:
         raise S2srError(f"s2sr_debug_plan_chunks failed ({_ERR.get(rc, rc)})")
     return [int(buf[i]) for i in range(n.value)]
+
+
+def plan_windows(PH: int, PW: int, tile: int, pad: int, scale: int = 4, tiled: bool = True) -> tuple:
+    """(nx, ny, wh, ww, rects[nx * ny, 4], rm[scale * PH, 2], cm[scale * PW, 2]): the distinct windows enhance runs the net on and
+    its paste maps (window row / column, row / column inside the window's output); host arithmetic, works without a GPU."""
+    cap = ((PH + tile - 1) // tile) * ((PW + tile - 1) // tile)
+    dims, rects = np.zeros(4, np.int32), np.zeros((cap, 4), np.int32)
+    rm, cm = np.zeros((scale * PH, 2), np.int32), np.zeros((scale * PW, 2), np.int32)
+    rc = load_library().s2sr_debug_plan_windows(PH, PW, tile, pad, scale, int(tiled), _ptr(dims), _ptr(rects), cap, _ptr(rm), _ptr(cm))
+    if rc:
+        raise S2srError(f"s2sr_debug_plan_windows failed ({_ERR.get(rc, rc)})")
+    nx, ny, wh, ww = (int(v) for v in dims)
+    return nx, ny, wh, ww, rects[:nx * ny if tiled else 0], rm, cm
 
 
 def _ptr(a: np.ndarray):

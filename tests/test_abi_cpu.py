@@ -243,6 +243,54 @@ def test_enhance_chunk_plan_properties():
         assert sum(1 for u in front if u != u_max) <= 1
 
 
+# H, W of the planned image, tile, pad, scale, tiled -- and what the reference's plan does there
+WINDOW_JOBS = [
+    (34, 36, 16, 2, 4, True),        # the last two window rows and the last two window columns coincide
+    (34, 45, 16, 2, 4, True),        # rows coincide, columns do not
+    (37, 35, 16, 2, 4, True),        # columns coincide, rows do not
+    (37, 45, 16, 2, 4, True),        # nothing coincides (the golden size)
+    (100, 90, 16, 2, 4, True),       # 7 x 6 planned -> 6 x 6 distinct
+    (53, 200, 16, 3, 4, True),       # 4 x 13 -> 3 x 13
+    (513, 512, 256, 10, 4, True),    # window rows 1 and 2 coincide
+    (38, 46, 16, 2, 2, True),        # a 37 x 45 image at scale 2, padded to even sizes
+    (28, 36, 16, 2, 4, False),       # untiled: the image is its own window
+]
+
+
+@pytest.mark.parametrize("H,W,ts,tp,scale,tiled", WINDOW_JOBS)
+def test_window_job_equals_the_references_paste(H, W, ts, tp, scale, tiled):
+    """The window job both enhance doors run (engine_aoi.hip plan_window_job through s2sr_debug_plan_windows; host arithmetic, no
+    device) against the reference's paste loop replayed in numpy: in plan order every window writes (its origin, the row inside
+    its output, the column inside its output) into its paste rectangle, later windows overwriting earlier ones.  The job forwards
+    each distinct rectangle once, so its maps must name, for every output pixel, a window with that origin and those offsets."""
+    from oracle import rrdbnet_ref as ref
+    plan = ref.tile_plan(H, W, ts, tp, scale) if tiled else [((0, H, 0, W), (0, 0, 0, 0), (0, scale * H, 0, scale * W))]
+    big = 1 << 20
+    origin = np.full((scale * H, scale * W), -1, np.int64)
+    row, col = origin.copy(), origin.copy()
+    for (y1, y2, x1, x2), (top, _, left, _), (oy1, oy2, ox1, ox2) in plan:
+        origin[oy1:oy2, ox1:ox2] = y1 * big + x1
+        row[oy1:oy2, ox1:ox2] = (np.arange(oy1, oy2) - oy1 + top)[:, None]
+        col[oy1:oy2, ox1:ox2] = (np.arange(ox1, ox2) - ox1 + left)[None, :]
+    assert origin.min() >= 0                                        # the reference's plan covers the image
+    nx, ny, wh, ww, rects, rm, cm = native.plan_windows(H, W, ts, tp, scale, tiled)
+    assert rm.shape == (scale * H, 2) and cm.shape == (scale * W, 2) and rm.min() >= 0 and cm.min() >= 0
+    distinct = {p[0] for p in plan}
+    assert nx * ny == len(distinct)
+    if tiled:
+        assert rects.shape == (nx * ny, 4) and len({tuple(r) for r in rects.tolist()}) == nx * ny
+        assert np.all(rects[:, 1] - rects[:, 0] == wh) and np.all(rects[:, 3] - rects[:, 2] == ww)
+        assert {tuple(r) for r in rects.tolist()} == distinct
+    else:
+        assert rects.shape == (0, 4) and (nx, ny, wh, ww) == (1, 1, H, W)
+        rects = np.array([[0, H, 0, W]], np.int32)
+    assert rm[:, 0].max() < ny and cm[:, 0].max() < nx
+    win = rm[:, 0][:, None] * nx + cm[:, 0][None, :]                # the window each output pixel is pasted from
+    assert np.array_equal(rects[win, 0].astype(np.int64) * big + rects[win, 2], origin)
+    assert np.array_equal(np.broadcast_to(rm[:, 1][:, None], row.shape), row)
+    assert np.array_equal(np.broadcast_to(cm[:, 1][None, :], col.shape), col)
+
+
 def test_window_mosaic_choice():
     """pick_mosaic (engine.hip) through s2sr_debug_pick_mosaic / s2sr_debug_mosaic_patches: the reference's default 276-pixel
     windows (tile 256 + 2 x pad 10, cnn_super_resolution.py:244-257) travel 4 x 4 per launch image (1107 -> 1120 of patch extent:

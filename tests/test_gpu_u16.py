@@ -29,7 +29,9 @@ TOL_FP8_6 = 1e-3
 F16, HP, FP8 = native.PREC_F16, native.PREC_F16_HP, native.PREC_FP8
 MODES = [(HP, TOL_HP), (F16, TOL_F16)]
 FULL, SUB = (0, 65535), (1000, 11000)
-BANDED = (100, 90, 16, 2)        # H, W, tile, pad: 42 windows, more than one chunk (test_banded_mosaic_path_matches_single_pass)
+BANDED = (100, 90, 16, 2)        # H, W, tile, pad: 42 planned windows, 36 distinct ones that fill one 6 x 6 mosaic -- ONE chunk
+CHUNKED = (53, 200, 16, 3)       # 3 x 13 distinct windows of 22 x 22, one per launch image, a launch group of 16: three chunks of one row
+assert native.pick_mosaic(39, 22, 22) == (1, 1) and native.plan_chunks(3, 1, 13, 1, 1, 256) == [1, 1, 1]
 
 
 def quantise(y, lo, hi):
@@ -53,9 +55,9 @@ def tsd(nb):
 @functools.lru_cache(maxsize=None)
 def data(kind):
     """The inputs the tests share (never written to)."""
-    rng = np.random.default_rng({"img_full": 1, "img_stray": 2, "batch_full": 3, "batch_stray": 4}[kind])
+    rng = np.random.default_rng({"img_full": 1, "img_stray": 2, "batch_full": 3, "batch_stray": 4, "chunked_full": 5, "chunked_stray": 6}[kind])
     top = 65536 if kind.endswith("full") else 13000          # 'stray': values below 1000 and above 11000
-    shape = (BANDED[0], BANDED[1], 3) if kind.startswith("img") else (3, 50, 33, 3)
+    shape = {"img": (BANDED[0], BANDED[1], 3), "chunked": (CHUNKED[0], CHUNKED[1], 3), "batch": (3, 50, 33, 3)}[kind.split("_")[0]]
     a = rng.integers(0, top, size=shape).astype(np.uint16)
     a.setflags(write=False)
     return a
@@ -92,9 +94,10 @@ def test_bit_identity_with_the_8_bit_door(prec):
         f8 = e.forward_f32(np.ascontiguousarray((t8.astype(np.float32) / np.float32(255.0)).transpose(0, 3, 1, 2)))
         assert np.array_equal(f, f8), (shape, float(np.abs(f - f8).max()))
         assert np.array_equal(q, quantise(nhwc(f), 0, 255))
-    img = rng.integers(0, 256, size=(BANDED[0], BANDED[1], 3), dtype=np.uint8)
-    _, f = e.enhance_u16(img.astype(np.uint16), 0, 255, tile=BANDED[2], pad=BANDED[3], want_f32=True)
-    assert np.array_equal(f, e.enhance_f32(img, tile=BANDED[2], pad=BANDED[3]))
+    for H, W, ts, tp in (BANDED, CHUNKED):
+        img = rng.integers(0, 256, size=(H, W, 3), dtype=np.uint8)
+        _, f = e.enhance_u16(img.astype(np.uint16), 0, 255, tile=ts, pad=tp, want_f32=True)
+        assert np.array_equal(f, e.enhance_f32(img, tile=ts, pad=tp)), (H, W)
     whole = rng.integers(0, 256, size=(28, 36, 3), dtype=np.uint8)
     _, f = e.enhance_u16(whole.astype(np.uint16), 0, 255, want_f32=True)
     assert np.array_equal(f, e.enhance_f32(whole))
@@ -119,6 +122,9 @@ def test_full_range_parity_and_own_quantisation(prec, tol):
     assert dq.max() <= levels(tol, *FULL)
     # the chunked route (u16 only: bands stitched and copied chunk by chunk) gives the same image
     assert np.array_equal(e.enhance_u16(img, tile=ts, pad=tp), q)
+    _, _, tsc, tpc = CHUNKED                                                             # ... in several chunks
+    qc, _ = e.enhance_u16(data("chunked_full"), tile=tsc, pad=tpc, want_f32=True)
+    assert np.array_equal(e.enhance_u16(data("chunked_full"), tile=tsc, pad=tpc), qc)
     qb, fb = e.forward_batch_u16(tiles, want_f32=True)
     errb = float(np.abs(fb - oracle("batch_full", *FULL)).max())
     print(f"batch u16 (3, 50, 33) prec {prec}: float err {errb:.3e}")
@@ -147,6 +153,9 @@ def test_value_range_clamps_and_rescales(prec, tol):
     assert np.array_equal(q, quantise(f, lo, hi)) and q.min() >= lo and q.max() <= hi
     assert np.abs(q.astype(np.int64) - quantise(oracle("img_stray", lo, hi), lo, hi)).max() <= levels(tol, lo, hi)
     assert np.array_equal(e.enhance_u16(img, lo, hi, tile=ts, pad=tp), q)               # the chunked route
+    _, _, tsc, tpc = CHUNKED                                                             # ... in several chunks
+    qc, _ = e.enhance_u16(data("chunked_stray"), lo, hi, tile=tsc, pad=tpc, want_f32=True)
+    assert np.array_equal(e.enhance_u16(data("chunked_stray"), lo, hi, tile=tsc, pad=tpc), qc)
     qb, fb = e.forward_batch_u16(tiles, lo, hi, want_f32=True)
     qbc, fbc = e.forward_batch_u16(np.clip(tiles, lo, hi), lo, hi, want_f32=True)
     assert np.array_equal(qb, qbc) and np.array_equal(fb, fbc)
