@@ -344,9 +344,9 @@ int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* 
 // (:85-91, :103-107).  The torch.cat of the dense block is "the first k blocks of D[cur]",
 // never a copy; conv5 writes the next x into the other dense tensor because neighbouring
 // workgroups still read this one's x as halo.
-// in16: the planes hold 16-bit input (pack_u16): conv_first takes the cin-6 weight set and the range's in_scale.
-int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f32, uint8_t* d_out_u8, const Mosaic& mo = Mosaic(),
-            const U16In* in16 = nullptr) {
+// in: what was packed.  For 16-bit input (TILE_U16) conv_first takes the cin-6 weight set and the range's in_scale.
+int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f32, uint8_t* d_out_u8, const Mosaic& mo, const TileIn& in) {
+    const bool in16 = in.kind == TILE_U16;
     if (h->compact()) return run_net_compact(h, st, n, H, W, d_out_f32, d_out_u8, mo);
     Workspace& w = h->ws;
     const int nb = h->cfg.num_block;
@@ -358,7 +358,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
     const bool fp8 = w.fp8;
     {   // conv_first: 3 -> 64 (input = one 16-channel block)
         ConvParams p = b;
-        p.src = w.P0; p.src_img = w.blk1; p.in_scale = in16 ? 1.0f / (float)(in16->hi - in16->lo) : 1.0f / 255.0f;
+        p.src = w.P0; p.src_img = w.blk1; p.in_scale = in16 ? 1.0f / (float)(in.hi - in.lo) : 1.0f / 255.0f;
         if (fp8) { p.dst = w.Xh[0]; p.dst_img = 4 * w.blk1; }
         else { p.dst = w.D[0]; p.dst_img = 12 * w.blk1; }
         if ((rc = run_conv(h, st, F_FIRST, in16 ? h->first16 : h->convs[ci], p, EPI_FIRST, false))) return rc;
@@ -713,17 +713,86 @@ int group_windows(const s2sr_handle* h, const Mosaic& mo, int T, int th, int tw)
     return group_size(h, (T + per - 1) / per, mo.image_h(th / u), mo.image_w(tw / u)) * per;
 }
 
-// [B,th,tw,3] u8 (device) -> u8 [B,S th,S tw,3] and/or f32 [B,3,S th,S tw] (device), S = cfg.scale.  At scale 2 th and tw are even
-// and the net runs on the th/2 x tw/2 trunk grid.  `src_h` x `src_w` (0: th x tw): the rows / columns the single input image holds
-// when it is one short of th / tw (scale 2, odd image: the packer reads the reflect row / column by index).
+// Segments of equal image geometry that B windows travel as: the full mosaics, then the remainder as one smaller mosaic (plain
+// images: one segment of B one-window images).  Returns how many.
+struct Seg { int t0, nwin, kx, ky; };
+static int split_segments(const Mosaic& mo, int B, Seg (&segs)[2]) {
+    int nseg = 0;
+    if (!mo.on()) segs[nseg++] = Seg{0, B, 1, 1};
+    else {
+        const int per = mo.per(), full = B / per, rem = B % per;
+        if (full) segs[nseg++] = Seg{0, full * per, mo.kx, mo.ky};
+        if (rem) { Seg r{full * per, rem, 1, 1}; mosaic_remainder(rem, mo.kx, mo.ky, &r.kx, &r.ky); segs[nseg++] = r; }
+    }
+    return nseg;
+}
+
+// The only place a packer is chosen: nt tiles of th x tw of `in` into ws.P0, as the windows of the mosaic mg or (mg off) one per image.
+static int pack_group(s2sr_handle* h, hipStream_t st, const TileIn& in, int nt, int th, int tw, const Mosaic& mg) {
+    const Workspace& w = h->ws;
+    const int u = h->unshuffle();      // 2: pixel_unshuffle(x, 2) folded into the packers
+    Scope sc(h, st, F_PACK, 0.0, (double)nt * th * tw * (3.0 + 8.0));   // (scale 2: 32 B per trunk pixel = 8 per input pixel)
+    HIPCHK(h, launch_pack_tiles(in, u, 255.0f, nt, th / u, tw / u, mg.on() ? mg.kx : 0, mg.on() ? mg.ky : 0, w.P0, w.Hp, w.Wp, st));
+    return S2SR_OK;
+}
+
+// One captured group (GraphKey) runs `enqueue` or replays its graph: a first sighting launches directly (and warms the per-kernel
+// attributes), a second one captures, a failed capture leaves the entry on direct launches for good; 24 entries, least recently used out.
+template <class Enqueue>
+static int run_or_replay(s2sr_handle* h, hipStream_t st, const GraphKey& key, Enqueue enqueue) {
+    GraphEntry* ge = nullptr;
+    // the legacy null stream cannot be captured; profiling wants its events between launches
+    if (h->graphs_on && h->prof <= 0 && st != nullptr) {
+        for (GraphEntry& g : h->graphs)
+            if (g.key == key) { ge = &g; break; }
+        if (!ge) {   // first sighting: remember it
+            if (h->graphs.size() >= 24) {
+                size_t victim = 0;
+                for (size_t i = 1; i < h->graphs.size(); ++i)
+                    if (h->graphs[i].last_use < h->graphs[victim].last_use) victim = i;
+                if (h->graphs[victim].exec) hipGraphExecDestroy(h->graphs[victim].exec);
+                h->graphs.erase(h->graphs.begin() + victim);
+            }
+            GraphEntry g;
+            g.key = key;
+            g.last_use = ++h->graph_clock;
+            h->graphs.push_back(g);
+        } else if (!ge->exec && !ge->refused) {   // second sighting: capture
+            hipGraph_t graph = nullptr;
+            DeviceGate gate;     // no device-wide call of any handle while this one captures (s2sr_internal.h)
+            bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
+            if (ok) {
+                const int erc = enqueue();
+                const hipError_t ee = hipStreamEndCapture(st, &graph);
+                ok = (erc == S2SR_OK) && ee == hipSuccess && graph != nullptr;
+            }
+            if (ok) ok = hipGraphInstantiate(&ge->exec, graph, nullptr, nullptr, 0) == hipSuccess;
+            if (graph) hipGraphDestroy(graph);
+            if (!ok) {
+                (void)hipGetLastError();
+                ge->exec = nullptr;
+                ge->refused = true;
+            } else {
+                ++h->graph_captures;
+            }
+        }
+    }
+    if (!ge || !ge->exec) return enqueue();
+    ge->last_use = ++h->graph_clock;
+    HIPCHK(h, hipGraphLaunch(ge->exec, st));
+    ++h->graph_replays;
+    return S2SR_OK;
+}
+
+// B tiles of th x tw (`in`, device) -> `out`, S = cfg.scale.  At scale 2 th and tw are even and the net runs on the th/2 x tw/2
+// trunk grid.
 // `plan`: the mosaic chosen for the whole job this call is a part of (a chunk of an AOI, a group of a batch) -- its geometry
 // sizes the workspace, so every part of the job runs in the same planes (r03 ADVICE: re-picking the mosaic from each chunk's own
 // window count gave a short last chunk another image height, and with it a workspace reallocation, a device synchronise and
 // dropped graphs inside the chunk loop, on every call).  nullptr: choose from B.
-int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const float* d_x_f32, int B, int th, int tw,
-                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan, int src_h, int src_w, const U16In* in16) {
+int forward_dev(s2sr_handle* h, hipStream_t st, TileIn in, int B, int th, int tw, const TileOut& out, const Mosaic* plan) {
     if (!h->has_weights) return fail(h, S2SR_E_NOWEIGHTS, "s2sr_load_weights has not been called");
-    if (in16 && (!in16->tiles || d_tiles || d_x_f32 || !h->first16.d_wpack || in16->lo < 0 || in16->hi > 65535 || in16->lo >= in16->hi))
+    if (in.kind == TILE_U16 && (!in.p || !h->first16.d_wpack || in.lo < 0 || in.hi > 65535 || in.lo >= in.hi))
         return fail(h, S2SR_E_INVALID, "16-bit input: an x4 RRDB handle, tiles, and a range 0 <= lo < hi <= 65535");
     if (B <= 0 || th <= 0 || tw <= 0) return fail(h, S2SR_E_INVALID, "bad batch/tile dims");
     const int u = h->unshuffle();
@@ -732,10 +801,11 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
         snprintf(b, sizeof b, "tiles of %d x %d: a scale-2 handle (pixel_unshuffle by 2) needs even tile sizes", th, tw);
         return fail(h, S2SR_E_INVALID, b);
     }
-    const int sh = src_h ? src_h : th, sw = src_w ? src_w : tw;     // input rows / columns as stored
+    if (!in.src_h) in.src_h = th;                                  // the rows / columns as stored
+    if (!in.src_w) in.src_w = tw;
     const int TH = th / u, TW = tw / u;                            // the trunk grid: what the schedule, workspace and graphs see
-    // u8 tiles may travel as window mosaics; "images" below are then mosaics of per = kx*ky windows
-    const Mosaic mo = !(d_tiles || in16) ? Mosaic() : (plan ? *plan : pick_mosaic(h, B, th, tw));
+    // u8 and u16 tiles may travel as window mosaics; "images" below are then mosaics of per = kx*ky windows
+    const Mosaic mo = in.kind == TILE_F32 ? Mosaic() : (plan ? *plan : pick_mosaic(h, B, th, tw));
     const int per = mo.per();
     const int IH = mo.image_h(TH), IW = mo.image_w(TW);            // the plan's image: the workspace geometry
     int G = group_windows(h, mo, plan && plan->count > B ? plan->count : B, th, tw) / per;   // in images
@@ -745,101 +815,29 @@ int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const fl
         rc = ensure_workspace(h, G, IH, IW, mo.on() ? TH + 1 : 0, mo.on() ? TW + 1 : 0);
     }
     if (rc) return rc;
-    Workspace& w = h->ws;
     const size_t opx = (size_t)16 * TH * TW;          // output pixels per tile: the x4 tail on the trunk grid
-    // segments of equal image geometry: the full mosaics, then the remainder as one smaller mosaic
-    struct Seg { int t0, nwin, kx, ky; };
     Seg segs[2];
-    int nseg = 0;
-    if (!mo.on()) segs[nseg++] = Seg{0, B, 1, 1};
-    else {
-        const int full = B / per, rem = B % per;
-        if (full) segs[nseg++] = Seg{0, full * per, mo.kx, mo.ky};
-        if (rem) { Seg r{full * per, rem, 1, 1}; mosaic_remainder(rem, mo.kx, mo.ky, &r.kx, &r.ky); segs[nseg++] = r; }
-    }
+    const int nseg = split_segments(mo, B, segs);
     for (int si = 0; si < nseg; ++si) {
-    const Seg& sg = segs[si];
-    const int sper = sg.kx * sg.ky;
-    const int NI = (sg.nwin + sper - 1) / sper;                                // images of this segment
-    const int SH = mo.on() ? mosaic_extent(sg.ky, TH) : TH, SW = mo.on() ? mosaic_extent(sg.kx, TW) : TW;
-    for (int g0 = 0; g0 < NI; g0 += G) {
-        const int n = (NI - g0 < G) ? (NI - g0) : G;
-        const int t0 = sg.t0 + g0 * sper;                                     // first window / tile of this group
-        const int nt = (sg.t0 + sg.nwin - t0 < n * sper) ? (sg.t0 + sg.nwin - t0) : n * sper;   // windows / tiles in it
-        const uint8_t* in8 = d_tiles ? d_tiles + (size_t)t0 * sh * sw * 3 : nullptr;
-        const float* in32 = (d_tiles || in16) ? nullptr : d_x_f32 + (size_t)t0 * 3 * th * tw;
-        const uint16_t* in16p = in16 ? in16->tiles + (size_t)t0 * th * tw * 3 : nullptr;
-        float* o32 = d_out_f32 ? d_out_f32 + (size_t)t0 * 3 * opx : nullptr;
-        uint8_t* o8 = d_out_u8 ? d_out_u8 + (size_t)t0 * 3 * opx : nullptr;
-        Mosaic mg = mo;
-        mg.kx = sg.kx; mg.ky = sg.ky; mg.count = nt;
-        auto enqueue = [&]() -> int {
-            {
-                Scope sc(h, st, F_PACK, 0.0, (double)nt * th * tw * (3.0 + 8.0));   // (scale 2: 32 B per trunk pixel = 8 per input pixel)
-                if (u == 2) {      // pixel_unshuffle(x, 2) folded into the packers
-                    if (in8 && mo.on()) HIPCHK(h, launch_pack_u8_unshuffle_mosaic(in8, nt, TH, TW, sg.kx, sg.ky, w.P0, w.Hp, w.Wp, st));
-                    else if (in8) HIPCHK(h, launch_pack_u8_unshuffle(in8, n, sh, sw, TH, TW, w.P0, w.Hp, w.Wp, st));
-                    else HIPCHK(h, launch_pack_f32_nchw_unshuffle(in32, n, TH, TW, 255.0f, w.P0, w.Hp, w.Wp, st));
-                } else if (in16p && mo.on()) HIPCHK(h, launch_pack_u16_mosaic(in16p, nt, th, tw, sg.kx, sg.ky, in16->lo, in16->hi, w.P0, w.Hp, w.Wp, st));
-                else if (in16p) HIPCHK(h, launch_pack_u16(in16p, n, th, tw, in16->lo, in16->hi, w.P0, w.Hp, w.Wp, st));
-                else if (in8 && mo.on()) HIPCHK(h, launch_pack_u8_mosaic(in8, nt, th, tw, sg.kx, sg.ky, w.P0, w.Hp, w.Wp, st));
-                else if (in8) HIPCHK(h, launch_pack_u8(in8, n, th, tw, w.P0, w.Hp, w.Wp, st));
-                else HIPCHK(h, launch_pack_f32_nchw(in32, n, 3, th, tw, 255.0f, w.P0, 1, w.Hp, w.Wp, st));
-            }
-            return run_net(h, st, n, SH, SW, o32, o8, mo.on() ? mg : Mosaic(), in16);
-        };
-        // the legacy null stream cannot be captured; profiling wants its events between launches
-        GraphEntry* ge = nullptr;
-        if (h->graphs_on && h->prof <= 0 && st != nullptr) {
-            GraphKey key{n, th, tw, sh, sw, mo.on() ? sg.kx : 0, mo.on() ? sg.ky : 0, mo.on() ? nt : 0, in8, in32, o8, o32, st};
-            if (in16p) { key.in_u16 = in16p; key.lo = in16->lo; key.hi = in16->hi; }
-            for (GraphEntry& g : h->graphs)
-                if (g.key == key) { ge = &g; break; }
-            if (!ge) {   // first sighting: remember it, launch directly (also warms the per-kernel attributes)
-                if (h->graphs.size() >= 24) {
-                    size_t victim = 0;
-                    for (size_t i = 1; i < h->graphs.size(); ++i)
-                        if (h->graphs[i].last_use < h->graphs[victim].last_use) victim = i;
-                    if (h->graphs[victim].exec) hipGraphExecDestroy(h->graphs[victim].exec);
-                    h->graphs.erase(h->graphs.begin() + victim);
-                }
-                GraphEntry g;
-                g.key = key;
-                g.last_use = ++h->graph_clock;
-                h->graphs.push_back(g);
-                ge = nullptr;
-            } else if (!ge->exec && !ge->refused) {   // second sighting: capture
-                hipGraph_t graph = nullptr;
-                DeviceGate gate;     // no device-wide call of any handle while this one captures (s2sr_internal.h)
-                bool ok = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess;
-                if (ok) {
-                    const int erc = enqueue();
-                    const hipError_t ee = hipStreamEndCapture(st, &graph);
-                    ok = (erc == S2SR_OK) && ee == hipSuccess && graph != nullptr;
-                }
-                if (ok) ok = hipGraphInstantiate(&ge->exec, graph, nullptr, nullptr, 0) == hipSuccess;
-                if (graph) hipGraphDestroy(graph);
-                if (!ok) {
-                    (void)hipGetLastError();
-                    ge->exec = nullptr;
-                    ge->refused = true;
-                    ge = nullptr;
-                } else {
-                    ++h->graph_captures;
-                }
-            } else if (ge->refused) {
-                ge = nullptr;
-            }
-        }
-        if (ge && ge->exec) {
-            ge->last_use = ++h->graph_clock;
-            HIPCHK(h, hipGraphLaunch(ge->exec, st));
-            ++h->graph_replays;
-        } else {
-            rc = enqueue();
+        const Seg& sg = segs[si];
+        const int sper = sg.kx * sg.ky;
+        const int NI = (sg.nwin + sper - 1) / sper;                                // images of this segment
+        const int SH = mo.on() ? mosaic_extent(sg.ky, TH) : TH, SW = mo.on() ? mosaic_extent(sg.kx, TW) : TW;
+        for (int g0 = 0; g0 < NI; g0 += G) {
+            const int n = (NI - g0 < G) ? (NI - g0) : G;
+            const int t0 = sg.t0 + g0 * sper;                                     // first window / tile of this group
+            const int nt = (sg.t0 + sg.nwin - t0 < n * sper) ? (sg.t0 + sg.nwin - t0) : n * sper;   // windows / tiles in it
+            const TileIn gin = in.from(t0);
+            const TileOut gout = out.from((size_t)t0 * 3 * opx);
+            Mosaic mg;                                                            // the group's mosaic (off: plain images)
+            if (mo.on()) { mg = mo; mg.kx = sg.kx; mg.ky = sg.ky; mg.count = nt; }
+            const GraphKey key{n, th, tw, mg.on() ? mg.kx : 0, mg.on() ? mg.ky : 0, mg.on() ? nt : 0, gin, gout, st};
+            rc = run_or_replay(h, st, key, [&]() -> int {
+                const int prc = pack_group(h, st, gin, nt, th, tw, mg);
+                return prc ? prc : run_net(h, st, n, SH, SW, gout.f32, gout.u8, mg, gin);
+            });
             if (rc) return rc;
         }
-    }
     }
     return S2SR_OK;
 }
@@ -1206,7 +1204,7 @@ int s2sr_forward_batch_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t B, in
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
-    return forward_dev(h, st, (const uint8_t*)d_tiles, nullptr, B, th, tw, (uint8_t*)d_out, nullptr);
+    return forward_dev(h, st, TileIn::u8(d_tiles), B, th, tw, TileOut{(uint8_t*)d_out});
 }
 
 // A PART of a larger job of `job_windows` equal windows (a chunk of an AOI's windows on one rank, s2sr/dist.py): the window
@@ -1217,7 +1215,7 @@ int s2sr_forward_part_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const Mosaic mo = pick_mosaic(h, job_windows, th, tw);
-    return forward_dev(h, (hipStream_t)stream, (const uint8_t*)d_tiles, nullptr, B, th, tw, (uint8_t*)d_out, nullptr, mo.on() ? &mo : nullptr);
+    return forward_dev(h, (hipStream_t)stream, TileIn::u8(d_tiles), B, th, tw, TileOut{(uint8_t*)d_out}, mo.on() ? &mo : nullptr);
 }
 
 int s2sr_host_alloc(size_t bytes, void** out) {
@@ -1261,8 +1259,8 @@ static int forward_batch_u8_once(s2sr_handle* h, const uint8_t* tiles, int32_t B
     if ((rc = ensure_group_events(h, ngroups))) return rc;
     for (int g = 0; g < ngroups; ++g) {
         const int g0 = g * G, n = (B - g0 < G) ? (B - g0) : G;
-        rc = forward_dev(h, h->stream, (const uint8_t*)h->d_scratch[0] + g0 * tin, nullptr, n, th, tw,
-                         (uint8_t*)h->d_scratch[1] + g0 * tout, nullptr, mo.on() ? &mo : nullptr);
+        rc = forward_dev(h, h->stream, TileIn::u8((const uint8_t*)h->d_scratch[0] + g0 * tin), n, th, tw,
+                         TileOut{(uint8_t*)h->d_scratch[1] + g0 * tout}, mo.on() ? &mo : nullptr);
         if (rc) return rc;
         HIPCHK(h, hipEventRecord(h->group_done[g], h->stream));
     }
@@ -1284,8 +1282,7 @@ int s2sr_forward_batch_u8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int32
 // (launch_stitch_quant_u16 in its plain-batch form) turns it into [B,4th,4tw,3] u16.  The caller holds h->mu.
 static int forward_u16_locked(s2sr_handle* h, hipStream_t st, const uint16_t* d_tiles, int B, int th, int tw, int lo, int hi,
                               uint16_t* d_out_u16, float* d_f32) {
-    const U16In in16{d_tiles, lo, hi};
-    int rc = forward_dev(h, st, nullptr, nullptr, B, th, tw, nullptr, d_f32, nullptr, 0, 0, &in16);
+    int rc = forward_dev(h, st, TileIn::u16(d_tiles, lo, hi), B, th, tw, TileOut{nullptr, d_f32});
     if (rc || !d_out_u16) return rc;
     Scope sc(h, st, F_MISC, 0.0, (double)B * 16.0 * th * tw * 3.0 * (4.0 + 2.0));
     HIPCHK(h, launch_stitch_quant_u16(d_f32, 1, 0, 4 * th, 4 * tw, nullptr, nullptr, B * 4 * th, 4 * tw, lo, hi, d_out_u16, st));
@@ -1347,7 +1344,7 @@ static int forward_f32_once(s2sr_handle* h, const float* x, int32_t N, int32_t H
     rc = ensure_scratch(h, 1, ob);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], x, ib, hipMemcpyHostToDevice, h->stream));
-    rc = forward_dev(h, h->stream, nullptr, (const float*)h->d_scratch[0], N, H, W, nullptr, (float*)h->d_scratch[1]);
+    rc = forward_dev(h, h->stream, TileIn::f32(h->d_scratch[0]), N, H, W, TileOut{nullptr, (float*)h->d_scratch[1]});
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(y, h->d_scratch[1], ob, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1434,7 +1431,7 @@ int s2sr_calibrate_fp8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int32_t 
         h->fp8_x_exp = mx; h->fp8_g_exp = mg;
         h->graphs_on = false; h->prof = 0;
         h->d_calib = d_c;
-        rc = forward_dev(h, h->stream, (const uint8_t*)h->d_scratch[0], nullptr, B, th, tw, (uint8_t*)h->d_scratch[1], nullptr);
+        rc = forward_dev(h, h->stream, TileIn::u8(h->d_scratch[0]), B, th, tw, TileOut{(uint8_t*)h->d_scratch[1]});
         h->d_calib = nullptr;
         h->graphs_on = old_graphs; h->prof = old_prof;
         e = hipMemcpyAsync(m, d_c, sizeof m, hipMemcpyDeviceToHost, h->stream);

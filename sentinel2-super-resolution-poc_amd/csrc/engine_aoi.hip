@@ -442,17 +442,17 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
             // identity map, cropped to OH x OW
             const size_t opxp = (size_t)OHp * OWp * 3;
             if ((rc = ensure_scratch(h, 2, opxp * (out_f32 ? 4 : 1)))) return rc;
-            rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[0], nullptr, 1, PH, PW, out_f32 ? nullptr : (uint8_t*)h->d_scratch[2],
-                             out_f32 ? (float*)h->d_scratch[2] : nullptr, nullptr, H, W);
+            rc = forward_dev(h, st, TileIn::u8(h->d_scratch[0], H, W), 1, PH, PW,
+                             TileOut{out_f32 ? nullptr : (uint8_t*)h->d_scratch[2], out_f32 ? (float*)h->d_scratch[2] : nullptr});
             if (rc) return rc;
             WindowJob job;
             if ((rc = plan_window_job(PH, PW, tile, pad, scale, false, job))) return fail(h, rc, kBadPlan);
             int32_t *d_rects, *d_rm, *d_cm;
             if ((rc = upload_window_job(h, st, job, &d_rects, &d_rm, &d_cm))) return rc;
-            if (out_f32) HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
-            else HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
+            if (out_f32) HIPCHK(h, launch_stitch((const float*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
+            else HIPCHK(h, launch_stitch((const uint8_t*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
         } else {
-            rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[0], nullptr, 1, H, W, (uint8_t*)h->d_scratch[1], nullptr);
+            rc = forward_dev(h, st, TileIn::u8(h->d_scratch[0]), 1, H, W, TileOut{(uint8_t*)h->d_scratch[1]});
             if (rc) return rc;
         }
     } else {
@@ -464,8 +464,7 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
         if ((rc = ensure_scratch(h, 4, tout * (out_f32 ? 4 : 1)))) return rc;
         int32_t *d_rects, *d_rm, *d_cm;
         if ((rc = upload_window_job(h, st, job, &d_rects, &d_rm, &d_cm))) return rc;
-        if (reflect) HIPCHK(h, launch_gather_windows_reflect((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
-        else HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, (uint8_t*)h->d_scratch[2], st));
+        HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, reflect, (uint8_t*)h->d_scratch[2], st));
         const Mosaic mo = pick_mosaic(h, T, wh, ww);   // ONE plan for the job: every chunk runs in its workspace geometry
         const std::vector<int> chunk_r0 = plan_chunk_rows(h, job, mo);
         const int nchunks = (int)chunk_r0.size() - 1;
@@ -491,11 +490,11 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
             if ((rc = ensure_group_events(h, nchunks + nfin))) return rc;
             uint8_t* d_img_out = (uint8_t*)h->d_scratch[1];
             auto forward = [&](int t0, int n) {
-                return forward_dev(h, st, (const uint8_t*)h->d_scratch[2] + t0 * win_in, nullptr, n, wh, ww,
-                                   (uint8_t*)h->d_scratch[4] + t0 * win_out, nullptr, mo.on() ? &mo : nullptr);
+                return forward_dev(h, st, TileIn::u8((const uint8_t*)h->d_scratch[2] + t0 * win_in), n, wh, ww,
+                                   TileOut{(uint8_t*)h->d_scratch[4] + t0 * win_out}, mo.on() ? &mo : nullptr);
             };
             auto finish = [&](int, int yb, int ye) -> int {   // (scratch 4 holds every window's output)
-                HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW,
+                HIPCHK(h, launch_stitch((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW,
                                            d_img_out + (size_t)yb * row_b, st));
                 if (prm) return pp_band_hist_locked(h, d_img_out, yb, ye, st);
                 if (job_rgb) HIPCHK(h, launch_swap_rb_u8(d_img_out + (size_t)yb * row_b, (size_t)(ye - yb) * OW, d_img_out + (size_t)yb * row_b, st));
@@ -534,11 +533,11 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
             HIPCHK(h, hipStreamSynchronize(st));
             return S2SR_OK;
         }
-        rc = forward_dev(h, st, (const uint8_t*)h->d_scratch[2], nullptr, T, wh, ww, out_f32 ? nullptr : (uint8_t*)h->d_scratch[4],
-                         out_f32 ? (float*)h->d_scratch[4] : nullptr);
+        rc = forward_dev(h, st, TileIn::u8(h->d_scratch[2]), T, wh, ww,
+                         TileOut{out_f32 ? nullptr : (uint8_t*)h->d_scratch[4], out_f32 ? (float*)h->d_scratch[4] : nullptr});
         if (rc) return rc;
-        if (out_f32) HIPCHK(h, launch_stitch_f32((const float*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
-        else HIPCHK(h, launch_stitch_u8((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
+        if (out_f32) HIPCHK(h, launch_stitch((const float*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
+        else HIPCHK(h, launch_stitch((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
     }
     const uint8_t* d_final = (const uint8_t*)h->d_scratch[1];
     if (whole_finish) {
@@ -617,7 +616,7 @@ static int enhance16_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int
     if ((rc = upload_window_job(h, st, job, &d_rects, &d_rm, &d_cm))) return rc;
     const uint16_t* d_win = (const uint16_t*)h->d_scratch[0];
     if (tiled) {
-        HIPCHK(h, launch_gather_windows_u16((const uint16_t*)h->d_scratch[0], H, W, d_rects, nx * ny, wh, ww, (uint16_t*)h->d_scratch[2], st));
+        HIPCHK(h, launch_gather_windows((const uint16_t*)h->d_scratch[0], H, W, d_rects, nx * ny, wh, ww, (uint16_t*)h->d_scratch[2], st));
         d_win = (const uint16_t*)h->d_scratch[2];
     }
     if ((rc = ensure_group_events(h, nchunks + 1))) return rc;
@@ -625,8 +624,7 @@ static int enhance16_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int
     float* d_tiles = (float*)h->d_scratch[4];
     const size_t row_b = (size_t)OW * 3 * 2;                     // bytes of one output row
     auto forward = [&](int t0, int n) {
-        const U16In in16{d_win + (size_t)t0 * win_in, lo, hi};
-        return forward_dev(h, st, nullptr, nullptr, n, wh, ww, nullptr, d_tiles, mo.on() ? &mo : nullptr, 0, 0, &in16);
+        return forward_dev(h, st, TileIn::u16(d_win + (size_t)t0 * win_in, lo, hi), n, wh, ww, TileOut{nullptr, d_tiles}, mo.on() ? &mo : nullptr);
     };
     // the band's rows come from the chunk's window rows only (the row map is monotone): d_tiles holds them, from window t0 on
     auto finish = [&](int t0, int yb, int ye) -> int {
@@ -640,7 +638,7 @@ static int enhance16_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int
     if ((rc = run_chunks(h, st, job, chunk_r0, OH, forward, finish, (uint8_t*)out_u16, (const uint8_t*)d_q, row_b, out_u16 && !out_f32))) return rc;
     if (out_f32) {
         float* d_f = (float*)((char*)h->d_scratch[1] + q_bytes);
-        HIPCHK(h, launch_stitch_f32(d_tiles, nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, d_f, st));
+        HIPCHK(h, launch_stitch(d_tiles, nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, d_f, st));
         HIPCHK(h, hipEventRecord(h->group_done[nchunks], st));
         if (out_u16) {
             HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
@@ -681,9 +679,7 @@ int s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_scratch[3], rects.data(), rects.size() * 4, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    if (PH != H || PW != W)
-        HIPCHK(h, launch_gather_windows_reflect((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, (uint8_t*)d_tiles, st));
-    else HIPCHK(h, launch_gather_windows((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, (uint8_t*)d_tiles, st));
+    HIPCHK(h, launch_gather_windows((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, PH != H || PW != W, (uint8_t*)d_tiles, st));
     return S2SR_OK;
 }
 
@@ -738,7 +734,7 @@ int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int3
     ms->last_use = ++h->stitch_clock;
     const int32_t* d_rm = ms->d;
     const int32_t* d_cm = d_rm + nrm;
-    HIPCHK(h, launch_stitch_u8((const uint8_t*)d_tiles, nx, wh * S, ww * S, d_rm + 2 * (size_t)oy0, d_cm, oy1 - oy0, S * W,
+    HIPCHK(h, launch_stitch((const uint8_t*)d_tiles, nx, wh * S, ww * S, d_rm + 2 * (size_t)oy0, d_cm, oy1 - oy0, S * W,
                                (uint8_t*)d_out + (size_t)oy0 * S * W * 3, st));
     return S2SR_OK;
 }

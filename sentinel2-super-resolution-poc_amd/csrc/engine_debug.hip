@@ -59,8 +59,8 @@ int tap_forward(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B,
     const bool graphs = h->graphs_on;
     h->graphs_on = false;
     Mosaic plan = tp.plan;
-    int rc = forward_dev(h, st, tiles ? (const uint8_t*)d_in.p : nullptr, tiles ? nullptr : (const float*)d_in.p, B, th, tw,
-                         out_u8 ? (uint8_t*)d_o8.p : nullptr, out_f32 ? (float*)d_o32.p : nullptr, plan.on() ? &plan : nullptr);
+    int rc = forward_dev(h, st, tiles ? TileIn::u8(d_in.p) : TileIn::f32(d_in.p), B, th, tw,
+                         TileOut{out_u8 ? (uint8_t*)d_o8.p : nullptr, out_f32 ? (float*)d_o32.p : nullptr}, plan.on() ? &plan : nullptr);
     h->graphs_on = graphs;
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(st));

@@ -84,31 +84,31 @@ struct Mosaic {
     long patches(int th, int tw) const { return (long)((image_h(th) + 31) / 32) * ((image_w(tw) + 31) / 32); }
 };
 
+// What a forward writes, either or both (device): u8 [B,S th,S tw,3], f32 [B,3,S th,S tw], S = cfg.scale.  What it reads is a
+// TileIn (s2sr_internal.h).
+struct TileOut {
+    uint8_t* u8 = nullptr;
+    float* f32 = nullptr;
+    TileOut from(size_t px) const { return TileOut{u8 ? u8 + px : nullptr, f32 ? f32 + px : nullptr}; }   // px samples further on
+    bool operator==(const TileOut& o) const { return u8 == o.u8 && f32 == o.f32; }
+};
+
 // One captured group (pack + the whole layer schedule) for fixed shapes and buffers.  A net is
 // 351 dependent launches; small groups are launch-bound (~15 us per launch against a few us of
 // work), so the second time the same (shape, buffers) group shows up it is captured into a
 // hipGraph and replayed from then on.  GraphKey: everything a replay must have in common with the captured group.
 struct GraphKey {
     int n = 0, th = 0, tw = 0;
-    int sh = 0, sw = 0;              // input rows / columns as stored (forward_dev src_h / src_w)
     int mos_kx = 0, mos_ky = 0, mos_count = 0;
-    const void *in_u8 = nullptr, *in_f32 = nullptr;
-    void *out_u8 = nullptr, *out_f32 = nullptr;
+    // the group's input: kind, pointer, the rows / columns as stored, and for 16-bit tiles the value range (the packer's constants
+    // and conv_first's in_scale are baked into the captured launches, and the host entries reuse one scratch pointer for every range)
+    TileIn in;
+    TileOut out;
     hipStream_t st = nullptr;
-    // the input kind: 16-bit tiles and their value range (the packer's constants and conv_first's in_scale are baked into the
-    // captured launches, and the host entries reuse one scratch pointer for every range)
-    const void* in_u16 = nullptr;
-    int lo = 0, hi = 0;
     bool operator==(const GraphKey& o) const {
-        return n == o.n && th == o.th && tw == o.tw && sh == o.sh && sw == o.sw && mos_kx == o.mos_kx && mos_ky == o.mos_ky &&
-               mos_count == o.mos_count && in_u8 == o.in_u8 && in_f32 == o.in_f32 && out_u8 == o.out_u8 && out_f32 == o.out_f32 && st == o.st &&
-               in_u16 == o.in_u16 && lo == o.lo && hi == o.hi;
+        return n == o.n && th == o.th && tw == o.tw && mos_kx == o.mos_kx && mos_ky == o.mos_ky && mos_count == o.mos_count && in == o.in &&
+               out == o.out && st == o.st;
     }
-};
-// forward_dev's 16-bit input kind: [B,th,tw,3] uint16 tiles (device) with the value range 0 <= lo < hi <= 65535 (pack.hip)
-struct U16In {
-    const uint16_t* tiles = nullptr;
-    int lo = 0, hi = 65535;
 };
 struct GraphEntry {
     GraphKey key;
@@ -282,9 +282,7 @@ void mosaic_remainder(int rem, int kx, int ky, int* rkx, int* rky);
 long mosaic_patches(int B, int th, int tw, int kx, int ky);
 Mosaic pick_mosaic_cfg(bool mosaic_on, int B, int th, int tw);
 Mosaic pick_mosaic(const s2sr_handle* h, int B, int th, int tw);
-int forward_dev(s2sr_handle* h, hipStream_t st, const uint8_t* d_tiles, const float* d_x_f32, int B, int th, int tw,
-                uint8_t* d_out_u8, float* d_out_f32, const Mosaic* plan = nullptr, int src_h = 0, int src_w = 0,
-                const U16In* in16 = nullptr);
+int forward_dev(s2sr_handle* h, hipStream_t st, TileIn in, int B, int th, int tw, const TileOut& out, const Mosaic* plan = nullptr);
 int check_u16(s2sr_handle* h, int lo, int hi);
 
 // ---- engine_aoi.hip

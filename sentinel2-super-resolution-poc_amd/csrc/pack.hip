@@ -1,68 +1,247 @@
 // Data-movement kernels around the conv stack: HBM-bound byte work, one element per thread,
 // coalesced on the side that moves the most bytes.
-//   pack_u8            : [N,H,W,3] u8 -> one fp16 blocked-16 plane with zero halo; replaces
+//   pack_tiles         : [N,H,W,3] u8 -> one fp16 blocked-16 plane with zero halo; replaces
 //                        `img.astype(float32)/255` + permute (cnn_super_resolution.py:220-222);
 //                        values stay the exact integers 0..255, the 1/255 lives in conv_first.
+//                        One pixel template over what is read (u8, u16 with a range, u8 / f32 unshuffled by 2) and where it
+//                        lands (image or mosaic cell), one kernel per built pair, one host entry.
 //   gather_windows     : cut the _tile_process windows (cnn_super_resolution.py:249-256)
-//   stitch_*           : crop + paste with the reference's overwrite order (:259-278)
+//   stitch             : crop + paste with the reference's overwrite order (:259-278)
 #include "s2sr_internal.h"
 
 namespace s2sr {
 
 typedef _Float16 f16;
 typedef f16 f16x4 __attribute__((ext_vector_type(4)));
+typedef f16 f16x8 __attribute__((ext_vector_type(8)));
 
-__global__ void pack_u8_kernel(const uint8_t* __restrict__ in, int N, int H, int W, char* __restrict__ blk, int Hp,
-                               int Wp) {
-    const size_t total = (size_t)N * H * W;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(i % W);
-        const size_t r = i / W;
-        const int y = (int)(r % H);
-        const int n = (int)(r / H);
+// blocks of 256 threads for a grid-stride loop over `total` elements, at most `cap` of them
+static inline int grid_for(size_t total, int cap) { return (int)((total + 255) / 256 > (size_t)cap ? (size_t)cap : (total + 255) / 256); }
+
+// ------------------------------------------------------------------------------------------
+// The tile packers: B tiles -> the one-block input plane, one thread per plane pixel, consecutive lanes along a row.
+// Where pixel (ly, lx) of tile t lands:
+//   Plain : image t, pixel (ly, lx).
+//   Cells : a window mosaic, B windows of h x w into ceil(B / (kx*ky)) images of (ky*(h+1)-1) x (kx*(w+1)-1), window t at grid
+//           cell (t % (kx*ky)) / kx, % kx of image t / (kx*ky); separator rows / columns are never written.
+// What is read (a source: its sample type, its constants, and get() = the channels of one plane pixel, stored as they come):
+//   SrcU8          : [B,h,w,3] u8 as the exact integers 0..255, one 8-byte store (one 16-channel block per image; channels
+//                    4..15 stay zero from the allocation memset).
+//   SrcU16         : the 16-bit door, see split_u16; one 16-byte store.  SrcU8's 8-byte store leaves channels 4..5 of a plane
+//                    this source wrote as they are (finite values); the u8 conv_first weights of those channels are zero.
+//   SrcU8Unshuffle, SrcF32Unshuffle : RealESRGAN_x2plus (s2sr_config.scale 2), F.pixel_unshuffle(x, 2) in front of conv_first:
+//                    the input at full resolution, the plane at half resolution (the trunk grid h x w).  Channel c*4 + i*2 + j of
+//                    trunk pixel (y, x) is input channel c at (2y+i, 2x+j) (torch's order); all 16 channels (12..15 zero) leave
+//                    as two 16-byte stores.
+// ------------------------------------------------------------------------------------------
+struct Plain {
+    __device__ void move(int&, int&, int&, int, int) const {}
+};
+struct Cells {   // (tile, ly, lx) of an h x w window -> (image, y, x) of its mosaic
+    int kx, ky;
+    __device__ void move(int& n, int& y, int& x, int h, int w) const {
+        const int t = n;
+        n = t / (kx * ky);
+        const int slot = t - n * (kx * ky);
+        const int wy = slot / kx, wx = slot - wy * kx;
+        y += wy * (h + 1);
+        x += wx * (w + 1);
+    }
+};
+template <class V>
+struct Channels {   // the first channels of a plane pixel as one vector
+    V v;
+    __device__ void store(char* dst) const { *(V*)dst = v; }
+};
+
+struct SrcU8 {
+    typedef uint8_t sample;
+    __device__ Channels<f16x4> get(const uint8_t* in, size_t i, int, int, int, int, int) const {
         const uint8_t* s = in + i * 3;
         f16x4 v;
         v[0] = (f16)(float)s[0];
         v[1] = (f16)(float)s[1];
         v[2] = (f16)(float)s[2];
         v[3] = (f16)0.f;
-        // one 16-channel block per image; channels 4..15 stay zero from the allocation memset
-        *(f16x4*)(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32) = v;
+        return {v};
     }
+};
+
+// uint16 samples with a value range [lo, hi] (s2sr_forward_batch_u16 / s2sr_enhance_u16):
+//   in : d = clamp(v, lo, hi) - lo (0..65535) travels as TWO exact fp16 integers, d = 256 * dh + dl: channels 0..2 of the
+//        one-block input plane carry dl (0..255), channels 3..5 carry 256 * dh (0..65280: 8 significant bits, below fp16's
+//        65504).  conv_first runs on a cin-6 weight set with w6[:, c] = w6[:, c + 3] = w[:, c] and in_scale 1 / (hi - lo), so
+//        its accumulator sums w * d exactly as it sums w * u for u8 input.
+//   out: q = lo + rint(clamp(y, 0, 1) * (hi - lo)), the product in fp32 rounded once, rint to nearest even (upstream
+//        RealESRGANer's 16-bit branch rounds; the u8 door's truncation is the reference's quirk and stays there).
+__device__ inline f16x8 split_u16(const uint16_t* s, int lo, int hi) {
+    f16x8 v;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int d = (int)s[c];
+        d = (d < lo ? lo : (d > hi ? hi : d)) - lo;
+        v[c] = (f16)(float)(d & 0xff);
+        v[3 + c] = (f16)(float)(d & 0xff00);
+    }
+    v[6] = (f16)0.f;
+    v[7] = (f16)0.f;
+    return v;
 }
 
-hipError_t launch_pack_u8(const uint8_t* d_tiles, int N, int H, int W, char* blk, int Hp, int Wp, hipStream_t st) {
+struct SrcU16 {
+    typedef uint16_t sample;
+    int lo, hi;
+    __device__ Channels<f16x8> get(const uint16_t* in, size_t i, int, int, int, int, int) const { return {split_u16(in + i * 3, lo, hi)}; }
+};
+
+struct Unshuffled {   // channels 0..11 of a plane pixel; 12..15 are zero
+    float v[12];
+    __device__ void store(char* dst) const {
+        f16x8 a, b;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a[k] = (f16)v[k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { b[k] = (f16)v[8 + k]; b[4 + k] = (f16)0.f; }
+        *(f16x8*)dst = a;
+        *(f16x8*)(dst + 16) = b;
+    }
+};
+
+// u8 images of H x W as stored: H is 2h or, for an odd image, 2h - 1.  A row / column 2y+i that is not stored is the one-pixel
+// reflect pad of RealESRGANer's mod-2 rule (torch 'reflect': row H reads row H - 2), read by index -- there is no padded copy.
+struct SrcU8Unshuffle {
+    typedef uint8_t sample;
+    int H, W;
+    __device__ Unshuffled get(const uint8_t* in, size_t, int t, int ly, int lx, int, int) const {
+        const uint8_t* img = in + (size_t)t * H * W * 3;
+        Unshuffled p;
+#pragma unroll
+        for (int di = 0; di < 2; ++di) {
+            const int sy0 = 2 * ly + di, sy = sy0 < H ? sy0 : 2 * H - 2 - sy0;
+#pragma unroll
+            for (int dj = 0; dj < 2; ++dj) {
+                const int sx0 = 2 * lx + dj, sx = sx0 < W ? sx0 : 2 * W - 2 - sx0;
+                const uint8_t* s = img + ((size_t)sy * W + sx) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) p.v[c * 4 + di * 2 + dj] = (float)s[c];
+            }
+        }
+        return p;
+    }
+};
+
+// [B,3,2h,2w] fp32 (plane = 2h * 2w samples per colour), values x * scale (255: the f32 entries feed [0,1] floats)
+struct SrcF32Unshuffle {
+    typedef float sample;
+    float scale;
+    size_t plane;
+    __device__ Unshuffled get(const float* x, size_t, int n, int y, int xx, int, int w) const {
+        Unshuffled p;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int di = 0; di < 2; ++di)
+#pragma unroll
+                for (int dj = 0; dj < 2; ++dj)
+                    p.v[c * 4 + di * 2 + dj] = x[((size_t)n * 3 + c) * plane + (size_t)(2 * y + di) * (2 * w) + 2 * xx + dj] * scale;
+        return p;
+    }
+};
+
+// plane pixel i of B tiles of h x w: where it lands, then the source reads and stores it
+template <class Src, class Place>
+__device__ inline void pack_pixel(size_t i, const typename Src::sample* in, int h, int w, Place at, Src src, char* blk, int Hp, int Wp) {
+    const int lx = (int)(i % w);
+    const size_t r = i / w;
+    const int ly = (int)(r % h);
+    const int t = (int)(r / h);
+    int n = t, y = ly, x = lx;
+    at.move(n, y, x, h, w);
+    src.get(in, i, t, ly, lx, h, w).store(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32);
+}
+
+// The kernels: one per built pair of source and placement, each the grid-stride loop around pack_pixel.  They are not one kernel
+// template: each takes the scalars it uses, as scalars and in this order, because handed over as structs they arrive through other
+// scalar loads, and with the loop inside a __device__ function blockDim.x keeps the device library's partial-block select -- either
+// way the registers of the whole loop come out renamed.  So a new input kind costs a source struct, a kernel of four lines here and
+// a branch in launch_pack_tiles.
+__global__ void pack_u8_kernel(const uint8_t* __restrict__ in, int N, int H, int W, char* __restrict__ blk, int Hp, int Wp) {
     const size_t total = (size_t)N * H * W;
-    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(pack_u8_kernel, dim3(grid), dim3(256), 0, st, d_tiles, N, H, W, blk, Hp, Wp);
-    return hipGetLastError();
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        pack_pixel(i, in, H, W, Plain{}, SrcU8{}, blk, Hp, Wp);
 }
-
-__global__ void pack_u8_mosaic_kernel(const uint8_t* __restrict__ in, int B, int h, int w, int kx, int ky, char* __restrict__ blk, int Hp,
-                                      int Wp) {
+__global__ void pack_u8_mosaic_kernel(const uint8_t* __restrict__ in, int B, int h, int w, int kx, int ky, char* __restrict__ blk, int Hp, int Wp) {
+    const size_t total = (size_t)B * h * w;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        pack_pixel(i, in, h, w, Cells{kx, ky}, SrcU8{}, blk, Hp, Wp);
+}
+__global__ void pack_u16_kernel(const uint16_t* __restrict__ in, int N, int H, int W, int lo, int hi, char* __restrict__ blk, int Hp, int Wp) {
+    const size_t total = (size_t)N * H * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        pack_pixel(i, in, H, W, Plain{}, SrcU16{lo, hi}, blk, Hp, Wp);
+}
+__global__ void pack_u16_mosaic_kernel(const uint16_t* __restrict__ in, int B, int h, int w, int kx, int ky, int lo, int hi, char* __restrict__ blk, int Hp, int Wp) {
+    const size_t total = (size_t)B * h * w;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        pack_pixel(i, in, h, w, Cells{kx, ky}, SrcU16{lo, hi}, blk, Hp, Wp);
+}
+__global__ void pack_u8_unshuffle_kernel(const uint8_t* __restrict__ in, int N, int H, int W, int h, int w, char* __restrict__ blk, int Hp, int Wp) {
+    const size_t total = (size_t)N * h * w;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        pack_pixel(i, in, h, w, Plain{}, SrcU8Unshuffle{H, W}, blk, Hp, Wp);
+}
+__global__ void pack_u8_unshuffle_mosaic_kernel(const uint8_t* __restrict__ in, int B, int h, int w, int kx, int ky, char* __restrict__ blk, int Hp, int Wp) {
     const size_t total = (size_t)B * h * w;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        // pack_pixel with the read of whole 2h x 2w tiles (no reflect) written out: behind get() the compiler shares the address
+        // arithmetic of the two columns before it unrolls, and the loop comes out with other registers and waits
         const int lx = (int)(i % w);
         const size_t r = i / w;
         const int ly = (int)(r % h);
         const int t = (int)(r / h);
-        const int n = t / (kx * ky), slot = t - n * (kx * ky);
-        const int wy = slot / kx, wx = slot - wy * kx;
-        const int y = wy * (h + 1) + ly, x = wx * (w + 1) + lx;
-        const uint8_t* s = in + i * 3;
-        f16x4 v;
-        v[0] = (f16)(float)s[0];
-        v[1] = (f16)(float)s[1];
-        v[2] = (f16)(float)s[2];
-        v[3] = (f16)0.f;
-        *(f16x4*)(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32) = v;
+        int n = t, y = ly, x = lx;
+        Cells{kx, ky}.move(n, y, x, h, w);
+        const uint8_t* img = in + (size_t)t * (4 * h) * w * 3;
+        Unshuffled p;
+#pragma unroll
+        for (int di = 0; di < 2; ++di)
+#pragma unroll
+            for (int dj = 0; dj < 2; ++dj) {
+                const uint8_t* s = img + ((size_t)(2 * ly + di) * (2 * w) + 2 * lx + dj) * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) p.v[c * 4 + di * 2 + dj] = (float)s[c];
+            }
+        p.store(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32);
     }
 }
+__global__ void pack_f32_nchw_unshuffle_kernel(const float* __restrict__ x, int N, int h, int w, float scale, char* __restrict__ blk, int Hp, int Wp) {
+    const size_t total = (size_t)N * h * w;
+    const size_t plane = (size_t)(2 * h) * (2 * w);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x)
+        pack_pixel(i, x, h, w, Plain{}, SrcF32Unshuffle{scale, plane}, blk, Hp, Wp);
+}
 
-hipError_t launch_pack_u8_mosaic(const uint8_t* d_tiles, int B, int h, int w, int kx, int ky, char* blk, int Hp, int Wp, hipStream_t st) {
-    const size_t total = (size_t)B * h * w;
-    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(pack_u8_mosaic_kernel, dim3(grid), dim3(256), 0, st, d_tiles, B, h, w, kx, ky, blk, Hp, Wp);
+hipError_t launch_pack_tiles(const TileIn& in, int unshuffle, float f32_scale, int B, int h, int w, int kx, int ky, char* blk, int Hp, int Wp,
+                             hipStream_t st) {
+    const bool mosaic = kx > 0;
+    const dim3 grid(grid_for((size_t)B * h * w, 4096)), block(256);
+    const uint8_t* u8 = (const uint8_t*)in.p;
+    const uint16_t* u16 = (const uint16_t*)in.p;
+    if (in.kind == TILE_F32 && !mosaic) {
+        if (unshuffle == 2) hipLaunchKernelGGL(pack_f32_nchw_unshuffle_kernel, grid, block, 0, st, (const float*)in.p, B, h, w, f32_scale, blk, Hp, Wp);
+        else return launch_pack_f32_nchw((const float*)in.p, B, 3, h, w, f32_scale, blk, 1, Hp, Wp, st);
+    } else if (in.kind == TILE_U8 && unshuffle == 2) {
+        if (mosaic) hipLaunchKernelGGL(pack_u8_unshuffle_mosaic_kernel, grid, block, 0, st, u8, B, h, w, kx, ky, blk, Hp, Wp);
+        else hipLaunchKernelGGL(pack_u8_unshuffle_kernel, grid, block, 0, st, u8, B, in.src_h, in.src_w, h, w, blk, Hp, Wp);
+    } else if (in.kind == TILE_U8 && unshuffle == 1) {
+        if (mosaic) hipLaunchKernelGGL(pack_u8_mosaic_kernel, grid, block, 0, st, u8, B, h, w, kx, ky, blk, Hp, Wp);
+        else hipLaunchKernelGGL(pack_u8_kernel, grid, block, 0, st, u8, B, h, w, blk, Hp, Wp);
+    } else if (in.kind == TILE_U16 && unshuffle == 1) {
+        if (mosaic) hipLaunchKernelGGL(pack_u16_mosaic_kernel, grid, block, 0, st, u16, B, h, w, kx, ky, in.lo, in.hi, blk, Hp, Wp);
+        else hipLaunchKernelGGL(pack_u16_kernel, grid, block, 0, st, u16, B, h, w, in.lo, in.hi, blk, Hp, Wp);
+    } else {
+        return hipErrorInvalidValue;   // not built: f32 mosaics; u16 at scale 2 (24 unshuffled channels need a second input block)
+    }
     return hipGetLastError();
 }
 
@@ -89,123 +268,28 @@ __global__ void pack_f32_nchw_kernel(const float* __restrict__ x, int N, int C, 
 
 hipError_t launch_pack_f32_nchw(const float* d_x, int N, int C, int H, int W, float scale, char* blk, int NB, int Hp,
                                 int Wp, hipStream_t st) {
-    const size_t total = (size_t)N * C * H * W;
-    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(pack_f32_nchw_kernel, dim3(grid), dim3(256), 0, st, d_x, N, C, H, W, scale, blk, NB, Hp, Wp);
+    hipLaunchKernelGGL(pack_f32_nchw_kernel, dim3(grid_for((size_t)N * C * H * W, 4096)), dim3(256), 0, st, d_x, N, C, H, W, scale, blk, NB, Hp, Wp);
     return hipGetLastError();
 }
 
-// RealESRGAN_x2plus (s2sr_config.scale 2): F.pixel_unshuffle(x, 2) in front of conv_first.  Twins of the three packers above:
-// the input at full resolution, the blocked-16 plane at half resolution (the trunk grid h x w).  Channel c*4 + i*2 + j of trunk
-// pixel (y, x) is input channel c at (2y+i, 2x+j) (torch's order), as the exact integers 0..255.  One thread per trunk pixel,
-// consecutive lanes along a trunk row; all 16 channels (12..15 zero) leave as two 16-byte stores.
-typedef f16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ inline void store_unshuffled(char* dst, const float (&v)[12]) {
-    f16x8 a, b;
+// one pixel of two fp16 blocks of 16 channels (ppx * 32 bytes apart) x scale -> 32 e4m3 bytes, saturating at +-448
+struct E4m3Pixel { uint4 a, b; };
+__device__ inline E4m3Pixel f16_pixel_to_e4m3(const char* src, size_t ppx, float scale) {
+    uint32_t o[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = (f16)v[k];
+    for (int b = 0; b < 2; ++b) {
+        const f16* v = (const f16*)(src + (size_t)b * ppx * 32);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { b[k] = (f16)v[8 + k]; b[4 + k] = (f16)0.f; }
-    *(f16x8*)dst = a;
-    *(f16x8*)(dst + 16) = b;
-}
-
-// [N,H,W,3] u8, H x W as stored: H is 2h or, for an odd image, 2h - 1.  A row / column 2y+i that is not stored is the one-pixel
-// reflect pad of RealESRGANer's mod-2 rule (torch 'reflect': row H reads row H - 2), read by index -- there is no padded copy.
-__global__ void pack_u8_unshuffle_kernel(const uint8_t* __restrict__ in, int N, int H, int W, int h, int w, char* __restrict__ blk,
-                                         int Hp, int Wp) {
-    const size_t total = (size_t)N * h * w;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(i % w);
-        const size_t r = i / w;
-        const int y = (int)(r % h);
-        const int n = (int)(r / h);
-        const uint8_t* img = in + (size_t)n * H * W * 3;
-        float v[12];
+        for (int q = 0; q < 4; ++q) {
+            float f[4];
 #pragma unroll
-        for (int di = 0; di < 2; ++di) {
-            const int sy0 = 2 * y + di, sy = sy0 < H ? sy0 : 2 * H - 2 - sy0;
-#pragma unroll
-            for (int dj = 0; dj < 2; ++dj) {
-                const int sx0 = 2 * x + dj, sx = sx0 < W ? sx0 : 2 * W - 2 - sx0;
-                const uint8_t* s = img + ((size_t)sy * W + sx) * 3;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c * 4 + di * 2 + dj] = (float)s[c];
-            }
+            for (int k = 0; k < 4; ++k) f[k] = __builtin_amdgcn_fmed3f((float)v[4 * q + k] * scale, -448.0f, 448.0f);
+            int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
+            w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
+            o[4 * b + q] = (uint32_t)w;
         }
-        store_unshuffled(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32, v);
     }
-}
-
-hipError_t launch_pack_u8_unshuffle(const uint8_t* d_img, int N, int H, int W, int h, int w, char* blk, int Hp, int Wp, hipStream_t st) {
-    const size_t total = (size_t)N * h * w;
-    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(pack_u8_unshuffle_kernel, dim3(grid), dim3(256), 0, st, d_img, N, H, W, h, w, blk, Hp, Wp);
-    return hipGetLastError();
-}
-
-// B windows of 2h x 2w u8 -> kx x ky windows of h x w per mosaic image (the geometry of pack_u8_mosaic_kernel on the trunk grid)
-__global__ void pack_u8_unshuffle_mosaic_kernel(const uint8_t* __restrict__ in, int B, int h, int w, int kx, int ky,
-                                                char* __restrict__ blk, int Hp, int Wp) {
-    const size_t total = (size_t)B * h * w;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int lx = (int)(i % w);
-        const size_t r = i / w;
-        const int ly = (int)(r % h);
-        const int t = (int)(r / h);
-        const int n = t / (kx * ky), slot = t - n * (kx * ky);
-        const int wy = slot / kx, wx = slot - wy * kx;
-        const int y = wy * (h + 1) + ly, x = wx * (w + 1) + lx;
-        const uint8_t* img = in + (size_t)t * (4 * h) * w * 3;
-        float v[12];
-#pragma unroll
-        for (int di = 0; di < 2; ++di)
-#pragma unroll
-            for (int dj = 0; dj < 2; ++dj) {
-                const uint8_t* s = img + ((size_t)(2 * ly + di) * (2 * w) + 2 * lx + dj) * 3;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c * 4 + di * 2 + dj] = (float)s[c];
-            }
-        store_unshuffled(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32, v);
-    }
-}
-
-hipError_t launch_pack_u8_unshuffle_mosaic(const uint8_t* d_tiles, int B, int h, int w, int kx, int ky, char* blk, int Hp, int Wp,
-                                           hipStream_t st) {
-    const size_t total = (size_t)B * h * w;
-    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(pack_u8_unshuffle_mosaic_kernel, dim3(grid), dim3(256), 0, st, d_tiles, B, h, w, kx, ky, blk, Hp, Wp);
-    return hipGetLastError();
-}
-
-// [N,3,2h,2w] fp32 -> the plane of the h x w grid, values x * scale (255: the f32 entries feed [0,1] floats)
-__global__ void pack_f32_nchw_unshuffle_kernel(const float* __restrict__ x, int N, int h, int w, float scale, char* __restrict__ blk,
-                                               int Hp, int Wp) {
-    const size_t total = (size_t)N * h * w;
-    const size_t plane = (size_t)(2 * h) * (2 * w);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int xx = (int)(i % w);
-        const size_t r = i / w;
-        const int y = (int)(r % h);
-        const int n = (int)(r / h);
-        float v[12];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int di = 0; di < 2; ++di)
-#pragma unroll
-                for (int dj = 0; dj < 2; ++dj)
-                    v[c * 4 + di * 2 + dj] = x[((size_t)n * 3 + c) * plane + (size_t)(2 * y + di) * (2 * w) + 2 * xx + dj] * scale;
-        store_unshuffled(blk + (((size_t)n * Hp + y + 1) * Wp + xx + 1) * 32, v);
-    }
-}
-
-hipError_t launch_pack_f32_nchw_unshuffle(const float* d_x, int N, int h, int w, float scale, char* blk, int Hp, int Wp, hipStream_t st) {
-    const size_t total = (size_t)N * h * w;
-    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(pack_f32_nchw_unshuffle_kernel, dim3(grid), dim3(256), 0, st, d_x, N, h, w, scale, blk, Hp, Wp);
-    return hipGetLastError();
+    return E4m3Pixel{make_uint4(o[0], o[1], o[2], o[3]), make_uint4(o[4], o[5], o[6], o[7])};
 }
 
 // conv_body's correction operands (S2SR_PREC_F16_HP): the trunk arrives as an fp16 pair (hi = dense
@@ -243,32 +327,14 @@ __global__ void trunk_to_fp8_kernel(const char* __restrict__ hi, size_t hi_img, 
             continue;
         }
         const char* src = (is_hi ? hi + (size_t)n * hi_img : lo + (size_t)n * lo_img) + (size_t)(2 * (plane & 1)) * ppx * 32 + pix * 32;
-        const float scale = is_hi ? 1.0f : 2048.0f;
-        uint32_t o[8];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {   // two fp16 blocks of 16 channels -> 32 e4m3 bytes
-            const f16* v = (const f16*)(src + (size_t)b * ppx * 32);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float f[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) f[k] = __builtin_amdgcn_fmed3f((float)v[4 * q + k] * scale, -448.0f, 448.0f);
-                int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
-                w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
-                o[4 * b + q] = (uint32_t)w;
-            }
-        }
-        uint4* d = (uint4*)(out + ((size_t)n * 4 + plane) * ppx * 32 + pix * 32);
-        d[0] = make_uint4(o[0], o[1], o[2], o[3]);
-        d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+        *(E4m3Pixel*)(out + ((size_t)n * 4 + plane) * ppx * 32 + pix * 32) = f16_pixel_to_e4m3(src, ppx, is_hi ? 1.0f : 2048.0f);
     }
 }
 
 hipError_t launch_trunk_to_fp8(const char* hi, size_t hi_img, const char* lo, size_t lo_img, int lo_e4m3_exp, int N, int Hp, int Wp, char* out,
                                hipStream_t st) {
     const size_t ppx = (size_t)Hp * Wp, total = (size_t)N * 4 * ppx;
-    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(trunk_to_fp8_kernel, dim3(grid), dim3(256), 0, st, hi, hi_img, lo, lo_img, lo_e4m3_exp, N, ppx, out);
+    hipLaunchKernelGGL(trunk_to_fp8_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, st, hi, hi_img, lo, lo_img, lo_e4m3_exp, N, ppx, out);
     return hipGetLastError();
 }
 
@@ -281,31 +347,14 @@ __global__ void xh_to_fp8_kernel(const char* __restrict__ xh, size_t xh_img, int
         const size_t pix = i % ppx;
         const int plane = (int)((i / ppx) & 1);
         const int n = (int)(i / (2 * ppx));
-        const char* src = xh + (size_t)n * xh_img + (size_t)(2 * plane) * ppx * 32 + pix * 32;
-        uint32_t o[8];
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const f16* v = (const f16*)(src + (size_t)b * ppx * 32);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                float f[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) f[k] = __builtin_amdgcn_fmed3f((float)v[4 * q + k] * scale, -448.0f, 448.0f);
-                int w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false);
-                w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
-                o[4 * b + q] = (uint32_t)w;
-            }
-        }
-        uint4* d = (uint4*)(out + (size_t)n * out_img + (size_t)plane * ppx * 32 + pix * 32);
-        d[0] = make_uint4(o[0], o[1], o[2], o[3]);
-        d[1] = make_uint4(o[4], o[5], o[6], o[7]);
+        *(E4m3Pixel*)(out + (size_t)n * out_img + (size_t)plane * ppx * 32 + pix * 32) =
+            f16_pixel_to_e4m3(xh + (size_t)n * xh_img + (size_t)(2 * plane) * ppx * 32 + pix * 32, ppx, scale);
     }
 }
 
 hipError_t launch_xh_to_fp8(const char* xh, size_t xh_img, int N, int Hp, int Wp, int x_exp, char* out, size_t out_img, hipStream_t st) {
     const size_t ppx = (size_t)Hp * Wp, total = (size_t)N * 2 * ppx;
-    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(xh_to_fp8_kernel, dim3(grid), dim3(256), 0, st, xh, xh_img, N, ppx, ldexpf(1.0f, x_exp), out, out_img);
+    hipLaunchKernelGGL(xh_to_fp8_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, st, xh, xh_img, N, ppx, ldexpf(1.0f, x_exp), out, out_img);
     return hipGetLastError();
 }
 
@@ -453,13 +502,16 @@ __global__ void swap_rb_kernel(const uint8_t* __restrict__ in, size_t npx, uint8
 }
 
 hipError_t launch_swap_rb_u8(const uint8_t* d_in, size_t npx, uint8_t* d_out, hipStream_t st) {
-    const int grid = (int)((npx + 255) / 256 > 8192 ? 8192 : (npx + 255) / 256);
+    const int grid = grid_for(npx, 8192);
     hipLaunchKernelGGL(swap_rb_kernel, dim3(grid ? grid : 1), dim3(256), 0, st, d_in, npx, d_out);
     return hipGetLastError();
 }
 
-__global__ void gather_windows_kernel(const uint8_t* __restrict__ img, int H, int W, const int32_t* __restrict__ rects,
-                                      int T, int wh, int ww, uint8_t* __restrict__ tiles) {
+// T windows of wh x ww out of an H x W image of 1- or 2-byte samples.  REFLECT (scale 2 with an odd H or W): the windows are planned
+// on the reflect-padded image (one row / column more); that row / column is read by index (row H = row H - 2, as torch's 'reflect').
+template <class S, bool REFLECT>
+__global__ void gather_windows_kernel(const S* __restrict__ img, int H, int W, const int32_t* __restrict__ rects,
+                                      int T, int wh, int ww, S* __restrict__ tiles) {
     const size_t total = (size_t)T * wh * ww * 3;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % 3);
@@ -468,43 +520,26 @@ __global__ void gather_windows_kernel(const uint8_t* __restrict__ img, int H, in
         r /= ww;
         const int y = (int)(r % wh);
         const int t = (int)(r / wh);
-        const int y1 = rects[t * 4 + 0], x1 = rects[t * 4 + 2];
-        tiles[i] = img[((size_t)(y1 + y) * W + (x1 + x)) * 3 + c];
-    }
-}
-
-hipError_t launch_gather_windows(const uint8_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
-                                 uint8_t* d_tiles, hipStream_t st) {
-    const size_t total = (size_t)T * wh * ww * 3;
-    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(gather_windows_kernel, dim3(grid), dim3(256), 0, st, d_img, H, W, d_rects, T, wh, ww, d_tiles);
-    return hipGetLastError();
-}
-
-// Scale 2 with an odd H or W: the windows are planned on the reflect-padded image (one row / column more); that row / column is
-// read by index (row H = row H - 2, as torch's 'reflect').
-__global__ void gather_windows_reflect_kernel(const uint8_t* __restrict__ img, int H, int W, const int32_t* __restrict__ rects,
-                                              int T, int wh, int ww, uint8_t* __restrict__ tiles) {
-    const size_t total = (size_t)T * wh * ww * 3;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % 3);
-        size_t r = i / 3;
-        const int x = (int)(r % ww);
-        r /= ww;
-        const int y = (int)(r % wh);
-        const int t = (int)(r / wh);
-        const int sy0 = rects[t * 4 + 0] + y, sx0 = rects[t * 4 + 2] + x;
-        const int sy = sy0 < H ? sy0 : 2 * H - 2 - sy0, sx = sx0 < W ? sx0 : 2 * W - 2 - sx0;
+        int sy = rects[t * 4 + 0] + y, sx = rects[t * 4 + 2] + x;
+        if constexpr (REFLECT) { sy = sy < H ? sy : 2 * H - 2 - sy; sx = sx < W ? sx : 2 * W - 2 - sx; }
         tiles[i] = img[((size_t)sy * W + sx) * 3 + c];
     }
 }
 
-hipError_t launch_gather_windows_reflect(const uint8_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
-                                         uint8_t* d_tiles, hipStream_t st) {
-    const size_t total = (size_t)T * wh * ww * 3;
-    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(gather_windows_reflect_kernel, dim3(grid), dim3(256), 0, st, d_img, H, W, d_rects, T, wh, ww, d_tiles);
+template <class S, bool REFLECT>
+static hipError_t gather_windows(const S* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww, S* d_tiles, hipStream_t st) {
+    hipLaunchKernelGGL((gather_windows_kernel<S, REFLECT>), dim3(grid_for((size_t)T * wh * ww * 3, 8192)), dim3(256), 0, st, d_img, H, W, d_rects,
+                       T, wh, ww, d_tiles);
     return hipGetLastError();
+}
+hipError_t launch_gather_windows(const uint8_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww, bool reflect,
+                                 uint8_t* d_tiles, hipStream_t st) {
+    return reflect ? gather_windows<uint8_t, true>(d_img, H, W, d_rects, T, wh, ww, d_tiles, st)
+                   : gather_windows<uint8_t, false>(d_img, H, W, d_rects, T, wh, ww, d_tiles, st);
+}
+hipError_t launch_gather_windows(const uint16_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww, uint16_t* d_tiles,
+                                 hipStream_t st) {
+    return gather_windows<uint16_t, false>(d_img, H, W, d_rects, T, wh, ww, d_tiles, st);
 }
 
 // rowmap[2*oy] = window-row index ty (or -1: not covered), rowmap[2*oy+1] = row inside that
@@ -513,9 +548,10 @@ hipError_t launch_gather_windows_reflect(const uint8_t* d_img, int H, int W, con
 // whose paste rectangle contains the pixel; paste rectangles are row-range x column-range
 // products, so that is (last covering ty, last covering tx) -- resolved on the host into
 // these maps, which makes the paste race-free and order-independent.
-__global__ void stitch_u8_kernel(const uint8_t* __restrict__ tiles, int oth, int otw, const int32_t* __restrict__ rowmap,
-                                 const int32_t* __restrict__ colmap, int tilesX, int OH, int OW,
-                                 uint8_t* __restrict__ out) {
+// PLANAR: the tiles are [T,3,oth,otw] (the net's fp32 output), else [T,oth,otw,3]; the output is HWC either way.
+template <class E, bool PLANAR>
+__global__ void stitch_kernel(const E* __restrict__ tiles, int oth, int otw, const int32_t* __restrict__ rowmap,
+                              const int32_t* __restrict__ colmap, int tilesX, int OH, int OW, E* __restrict__ out) {
     const size_t total = (size_t)OH * OW * 3;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % 3);
@@ -524,137 +560,28 @@ __global__ void stitch_u8_kernel(const uint8_t* __restrict__ tiles, int oth, int
         const int oy = (int)(r / OW);
         const int ty = rowmap[2 * oy], sy = rowmap[2 * oy + 1];
         const int tx = colmap[2 * ox], sx = colmap[2 * ox + 1];
-        uint8_t v = 0;   // reference output starts as zeros (cnn_super_resolution.py:242)
-        if (ty >= 0 && tx >= 0) v = tiles[(((size_t)(ty * tilesX + tx) * oth + sy) * otw + sx) * 3 + c];
+        E v = 0;   // reference output starts as zeros (cnn_super_resolution.py:242)
+        if (ty >= 0 && tx >= 0)
+            v = PLANAR ? tiles[(((size_t)(ty * tilesX + tx) * 3 + c) * oth + sy) * otw + sx]
+                       : tiles[(((size_t)(ty * tilesX + tx) * oth + sy) * otw + sx) * 3 + c];
         out[i] = v;
     }
 }
 
-__global__ void stitch_f32_kernel(const float* __restrict__ tiles, int oth, int otw, const int32_t* __restrict__ rowmap,
-                                  const int32_t* __restrict__ colmap, int tilesX, int OH, int OW,
-                                  float* __restrict__ out) {
-    const size_t total = (size_t)OH * OW * 3;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % 3);
-        const size_t r = i / 3;
-        const int ox = (int)(r % OW);
-        const int oy = (int)(r / OW);
-        const int ty = rowmap[2 * oy], sy = rowmap[2 * oy + 1];
-        const int tx = colmap[2 * ox], sx = colmap[2 * ox + 1];
-        float v = 0.f;
-        if (ty >= 0 && tx >= 0) v = tiles[(((size_t)(ty * tilesX + tx) * 3 + c) * oth + sy) * otw + sx];
-        out[i] = v;
-    }
-}
-
-hipError_t launch_stitch_u8(const uint8_t* d_tiles, int tilesX, int oth, int otw, const int32_t* d_rowmap,
-                            const int32_t* d_colmap, int OH, int OW, uint8_t* d_out, hipStream_t st) {
-    const size_t total = (size_t)OH * OW * 3;
-    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(stitch_u8_kernel, dim3(grid), dim3(256), 0, st, d_tiles, oth, otw, d_rowmap, d_colmap, tilesX, OH, OW,
-                       d_out);
+template <class E, bool PLANAR>
+static hipError_t stitch(const E* d_tiles, int tilesX, int oth, int otw, const int32_t* d_rowmap, const int32_t* d_colmap, int OH, int OW,
+                         E* d_out, hipStream_t st) {
+    hipLaunchKernelGGL((stitch_kernel<E, PLANAR>), dim3(grid_for((size_t)OH * OW * 3, 8192)), dim3(256), 0, st, d_tiles, oth, otw, d_rowmap,
+                       d_colmap, tilesX, OH, OW, d_out);
     return hipGetLastError();
 }
-
-hipError_t launch_stitch_f32(const float* d_tiles, int tilesX, int oth, int otw, const int32_t* d_rowmap,
-                             const int32_t* d_colmap, int OH, int OW, float* d_out, hipStream_t st) {
-    const size_t total = (size_t)OH * OW * 3;
-    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(stitch_f32_kernel, dim3(grid), dim3(256), 0, st, d_tiles, oth, otw, d_rowmap, d_colmap, tilesX, OH,
-                       OW, d_out);
-    return hipGetLastError();
+hipError_t launch_stitch(const uint8_t* d_tiles, int tilesX, int oth, int otw, const int32_t* d_rowmap, const int32_t* d_colmap, int OH,
+                         int OW, uint8_t* d_out, hipStream_t st) {
+    return stitch<uint8_t, false>(d_tiles, tilesX, oth, otw, d_rowmap, d_colmap, OH, OW, d_out, st);
 }
-
-// ------------------------------------------------------------------------------------------
-// The 16-bit door (s2sr_forward_batch_u16 / s2sr_enhance_u16): uint16 samples with a value range [lo, hi].
-//   in : d = clamp(v, lo, hi) - lo (0..65535) travels as TWO exact fp16 integers, d = 256 * dh + dl: channels 0..2 of the
-//        one-block input plane carry dl (0..255), channels 3..5 carry 256 * dh (0..65280: 8 significant bits, below fp16's
-//        65504).  conv_first runs on a cin-6 weight set with w6[:, c] = w6[:, c + 3] = w[:, c] and in_scale 1 / (hi - lo), so
-//        its accumulator sums w * d exactly as it sums w * u for u8 input.
-//   out: q = lo + rint(clamp(y, 0, 1) * (hi - lo)), the product in fp32 rounded once, rint to nearest even (upstream
-//        RealESRGANer's 16-bit branch rounds; the u8 door's truncation is the reference's quirk and stays there).
-// ------------------------------------------------------------------------------------------
-__device__ inline f16x8 split_u16(const uint16_t* s, int lo, int hi) {
-    f16x8 v;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        int d = (int)s[c];
-        d = (d < lo ? lo : (d > hi ? hi : d)) - lo;
-        v[c] = (f16)(float)(d & 0xff);
-        v[3 + c] = (f16)(float)(d & 0xff00);
-    }
-    v[6] = (f16)0.f;
-    v[7] = (f16)0.f;
-    return v;
-}
-
-// twin of pack_u8_kernel: one 16-byte store per pixel.  pack_u8's 8-byte store leaves channels 4..5 of a plane this kernel wrote
-// as they are (finite values); the u8 conv_first weights of those channels are zero.
-__global__ void pack_u16_kernel(const uint16_t* __restrict__ in, int N, int H, int W, int lo, int hi, char* __restrict__ blk, int Hp,
-                                int Wp) {
-    const size_t total = (size_t)N * H * W;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(i % W);
-        const size_t r = i / W;
-        const int y = (int)(r % H);
-        const int n = (int)(r / H);
-        *(f16x8*)(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32) = split_u16(in + i * 3, lo, hi);
-    }
-}
-
-hipError_t launch_pack_u16(const uint16_t* d_tiles, int N, int H, int W, int lo, int hi, char* blk, int Hp, int Wp, hipStream_t st) {
-    const size_t total = (size_t)N * H * W;
-    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(pack_u16_kernel, dim3(grid), dim3(256), 0, st, d_tiles, N, H, W, lo, hi, blk, Hp, Wp);
-    return hipGetLastError();
-}
-
-// twin of pack_u8_mosaic_kernel
-__global__ void pack_u16_mosaic_kernel(const uint16_t* __restrict__ in, int B, int h, int w, int kx, int ky, int lo, int hi,
-                                       char* __restrict__ blk, int Hp, int Wp) {
-    const size_t total = (size_t)B * h * w;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int lx = (int)(i % w);
-        const size_t r = i / w;
-        const int ly = (int)(r % h);
-        const int t = (int)(r / h);
-        const int n = t / (kx * ky), slot = t - n * (kx * ky);
-        const int wy = slot / kx, wx = slot - wy * kx;
-        const int y = wy * (h + 1) + ly, x = wx * (w + 1) + lx;
-        *(f16x8*)(blk + (((size_t)n * Hp + y + 1) * Wp + x + 1) * 32) = split_u16(in + i * 3, lo, hi);
-    }
-}
-
-hipError_t launch_pack_u16_mosaic(const uint16_t* d_tiles, int B, int h, int w, int kx, int ky, int lo, int hi, char* blk, int Hp, int Wp,
-                                  hipStream_t st) {
-    const size_t total = (size_t)B * h * w;
-    const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(pack_u16_mosaic_kernel, dim3(grid), dim3(256), 0, st, d_tiles, B, h, w, kx, ky, lo, hi, blk, Hp, Wp);
-    return hipGetLastError();
-}
-
-// gather_windows_kernel on 2-byte samples
-__global__ void gather_windows_u16_kernel(const uint16_t* __restrict__ img, int H, int W, const int32_t* __restrict__ rects,
-                                          int T, int wh, int ww, uint16_t* __restrict__ tiles) {
-    const size_t total = (size_t)T * wh * ww * 3;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % 3);
-        size_t r = i / 3;
-        const int x = (int)(r % ww);
-        r /= ww;
-        const int y = (int)(r % wh);
-        const int t = (int)(r / wh);
-        const int y1 = rects[t * 4 + 0], x1 = rects[t * 4 + 2];
-        tiles[i] = img[((size_t)(y1 + y) * W + (x1 + x)) * 3 + c];
-    }
-}
-
-hipError_t launch_gather_windows_u16(const uint16_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
-                                     uint16_t* d_tiles, hipStream_t st) {
-    const size_t total = (size_t)T * wh * ww * 3;
-    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(gather_windows_u16_kernel, dim3(grid), dim3(256), 0, st, d_img, H, W, d_rects, T, wh, ww, d_tiles);
-    return hipGetLastError();
+hipError_t launch_stitch(const float* d_tiles, int tilesX, int oth, int otw, const int32_t* d_rowmap, const int32_t* d_colmap, int OH,
+                         int OW, float* d_out, hipStream_t st) {
+    return stitch<float, true>(d_tiles, tilesX, oth, otw, d_rowmap, d_colmap, OH, OW, d_out, st);
 }
 
 __device__ inline uint32_t quant_u16(float y, float range, int lo) {
@@ -663,7 +590,7 @@ __device__ inline uint32_t quant_u16(float y, float range, int lo) {
 }
 
 // Crop + paste + quantise: planar fp32 tiles [.., 3, oth, otw] -> rows [0, OH) of an HWC u16 image through the paste maps, as
-// stitch_f32_kernel reads them (rowmap already offset to the band's first row; window (ty, tx) is tile ty * tilesX + tx - tile0
+// stitch_kernel<float, true> reads them (rowmap already offset to the band's first row; window (ty, tx) is tile ty * tilesX + tx - tile0
 // of `tiles`, so a chunk's buffer holds only its own window rows).  rowmap == nullptr: a plain batch, row oy of the output is row
 // oy % oth of tile oy / oth.  One thread = 4 consecutive output pixels (OW is a multiple of 4: the x4 net): paste rectangles
 // start and end on multiples of 4 on both sides, so the 4 pixels are one float4 per colour plane (checked, with a scalar
@@ -728,8 +655,7 @@ hipError_t launch_stitch_quant_u16(const float* d_tiles, int tilesX, int tile0, 
                                    const int32_t* d_colmap, int OH, int OW, int lo, int hi, uint16_t* d_out, hipStream_t st) {
     if (OH <= 0 || OW <= 0 || (OW & 3) || ((uintptr_t)d_out & 7)) return hipErrorInvalidValue;
     const size_t total = (size_t)OH * (OW >> 2);
-    const int grid = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
-    hipLaunchKernelGGL(stitch_quant_u16_kernel, dim3(grid), dim3(256), 0, st, d_tiles, oth, otw, d_rowmap, d_colmap, tilesX, tile0, OH, OW,
+    hipLaunchKernelGGL(stitch_quant_u16_kernel, dim3(grid_for(total, 8192)), dim3(256), 0, st, d_tiles, oth, otw, d_rowmap, d_colmap, tilesX, tile0, OH, OW,
                        lo, hi, d_out);
     return hipGetLastError();
 }

@@ -285,39 +285,47 @@ bool png_write_tile_file(const char* path, const uint32_t* words, uint32_t defla
 bool png_parallel_for(int n, const std::function<void(int)>& body);   // false: a body threw (the other indices still ran)
 
 // data-movement kernels (pack.hip)
-hipError_t launch_pack_u8(const uint8_t* d_tiles, int N, int H, int W, char* blk, int Hp, int Wp, hipStream_t st);
-// the same for a window mosaic: B windows of h x w into ceil(B / (kx*ky)) images of (ky*(h+1)-1) x (kx*(w+1)-1), window t at grid
-// cell (t % (kx*ky)) / kx, % kx of image t / (kx*ky); separator rows / columns are never written
-hipError_t launch_pack_u8_mosaic(const uint8_t* d_tiles, int B, int h, int w, int kx, int ky, char* blk, int Hp, int Wp, hipStream_t st);
+// What a forward reads: B tiles of th x tw on the device, [B,th,tw,3] u8 or u16 (value range lo < hi) or [B,3,th,tw] fp32 in [0, 1].
+// src_h x src_w (0: th x tw): what the single u8 image holds when it is one short of th / tw (scale 2, odd image).
+enum TileKind { TILE_U8, TILE_U16, TILE_F32 };
+struct TileIn {
+    TileKind kind = TILE_U8;
+    const void* p = nullptr;
+    int lo = 0, hi = 0;
+    int src_h = 0, src_w = 0;
+    static TileIn u8(const void* p, int src_h = 0, int src_w = 0) { return TileIn{TILE_U8, p, 0, 0, src_h, src_w}; }
+    static TileIn u16(const void* p, int lo, int hi) { return TileIn{TILE_U16, p, lo, hi, 0, 0}; }
+    static TileIn f32(const void* p) { return TileIn{TILE_F32, p, 0, 0, 0, 0}; }
+    // the same input from tile t0 on (src_h x src_w filled in: every kind stores 3 * src_h * src_w samples per tile)
+    TileIn from(size_t t0) const {
+        TileIn r = *this;
+        r.p = (const char*)p + t0 * 3 * src_h * src_w * (kind == TILE_U8 ? 1 : kind == TILE_U16 ? 2 : 4);
+        return r;
+    }
+    bool operator==(const TileIn& o) const { return kind == o.kind && p == o.p && lo == o.lo && hi == o.hi && src_h == o.src_h && src_w == o.src_w; }
+};
+// B tiles of `in` -> the one-block input plane blk of the h x w trunk grid; the layouts are stated at the family in pack.hip.
+// unshuffle 2: pixel_unshuffle(x, 2) on the way, tiles of 2h x 2w.  f32 values leave as x * f32_scale.  kx > 0: a window mosaic of
+// kx x ky cells per image.  hipErrorInvalidValue for a combination that is not built.
+hipError_t launch_pack_tiles(const TileIn& in, int unshuffle, float f32_scale, int B, int h, int w, int kx, int ky, char* blk, int Hp, int Wp,
+                             hipStream_t st);
+// [N,C,H,W] fp32 -> NB blocks per image, any channel count (launch_pack_tiles' plain f32 form; the per-layer test hooks)
 hipError_t launch_pack_f32_nchw(const float* d_x, int N, int C, int H, int W, float scale, char* blk, int NB,
                                 int Hp, int Wp, hipStream_t st);
-// scale 2 (RealESRGAN_x2plus): the same three with pixel_unshuffle(x, 2) -- full-resolution input, plane of the h x w trunk grid,
-// channels 0..11 in torch's order, 12..15 zero.  pack_u8_unshuffle: images of H x W as stored (H = 2h, or 2h - 1 with the reflect
-// row read by index; likewise W); the mosaic form takes windows of 2h x 2w; the f32 form [N,3,2h,2w]
-hipError_t launch_pack_u8_unshuffle(const uint8_t* d_img, int N, int H, int W, int h, int w, char* blk, int Hp, int Wp, hipStream_t st);
-hipError_t launch_pack_u8_unshuffle_mosaic(const uint8_t* d_tiles, int B, int h, int w, int kx, int ky, char* blk, int Hp, int Wp,
-                                           hipStream_t st);
-hipError_t launch_pack_f32_nchw_unshuffle(const float* d_x, int N, int h, int w, float scale, char* blk, int Hp, int Wp, hipStream_t st);
 hipError_t launch_trunk_to_fp8(const char* hi, size_t hi_img, const char* lo, size_t lo_img, int lo_e4m3_exp, int N, int Hp, int Wp, char* out,
                                hipStream_t st);
 hipError_t launch_swap_rb_u8(const uint8_t* d_in, size_t npx, uint8_t* d_out, hipStream_t st);
-hipError_t launch_gather_windows(const uint8_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
+// T windows (d_rects: y1, y2, x1, x2 each) of wh x ww out of an H x W image.  reflect: windows of the reflect-padded image (scale 2,
+// odd H or W): row H reads row H - 2, column W column W - 2.  2-byte samples: scale 4 only, no reflect form.
+hipError_t launch_gather_windows(const uint8_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww, bool reflect,
                                  uint8_t* d_tiles, hipStream_t st);
-// ... windows of the reflect-padded image (scale 2, odd H or W): row H reads row H - 2, column W column W - 2
-hipError_t launch_gather_windows_reflect(const uint8_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
-                                         uint8_t* d_tiles, hipStream_t st);
-hipError_t launch_stitch_u8(const uint8_t* d_tiles, int tilesX, int oth, int otw, const int32_t* d_rowmap,
-                            const int32_t* d_colmap, int OH, int OW, uint8_t* d_out, hipStream_t st);
-hipError_t launch_stitch_f32(const float* d_tiles /*[T,3,oth,otw]*/, int tilesX, int oth, int otw, const int32_t* d_rowmap,
-                             const int32_t* d_colmap, int OH, int OW, float* d_out /*HWC*/, hipStream_t st);
-// the 16-bit door (uint16 samples, value range 0 <= lo < hi <= 65535; the arithmetic is stated in pack.hip).  pack_u16 /
-// pack_u16_mosaic: twins of the u8 packers, d = clamp(v, lo, hi) - lo as channels 0..2 = d & 255, 3..5 = d & 0xff00 of the input
-// plane (one 16-byte store per pixel).  gather_windows_u16: gather_windows on 2-byte samples (scale 4 only: no reflect form).
-hipError_t launch_pack_u16(const uint16_t* d_tiles, int N, int H, int W, int lo, int hi, char* blk, int Hp, int Wp, hipStream_t st);
-hipError_t launch_pack_u16_mosaic(const uint16_t* d_tiles, int B, int h, int w, int kx, int ky, int lo, int hi, char* blk, int Hp, int Wp,
-                                  hipStream_t st);
-hipError_t launch_gather_windows_u16(const uint16_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww,
-                                     uint16_t* d_tiles, hipStream_t st);
+hipError_t launch_gather_windows(const uint16_t* d_img, int H, int W, const int32_t* d_rects, int T, int wh, int ww, uint16_t* d_tiles,
+                                 hipStream_t st);
+// crop + paste through the paste maps into an HWC image: u8 tiles [T,oth,otw,3], fp32 tiles [T,3,oth,otw]
+hipError_t launch_stitch(const uint8_t* d_tiles, int tilesX, int oth, int otw, const int32_t* d_rowmap, const int32_t* d_colmap, int OH,
+                         int OW, uint8_t* d_out, hipStream_t st);
+hipError_t launch_stitch(const float* d_tiles, int tilesX, int oth, int otw, const int32_t* d_rowmap, const int32_t* d_colmap, int OH,
+                         int OW, float* d_out, hipStream_t st);
 // crop + paste + quantise: planar fp32 tiles [.., 3, oth, otw] -> OH rows of an HWC u16 image, q = lo + rint(clamp(y, 0, 1) * (hi - lo)).
 // d_rowmap points at the first row of the band (d_out likewise); window (ty, tx) is tile ty * tilesX + tx - tile0 of d_tiles.
 // d_rowmap == nullptr: a plain batch (output row oy = row oy % oth of tile oy / oth); d_colmap == nullptr: identity columns.
