@@ -300,6 +300,24 @@ int  s2sr_tiles_base_u8(s2sr_handle* h, const uint8_t* rgba, int32_t H, int32_t 
                         const int32_t* row_lo, const int32_t* row_hi, int32_t nx, int32_t ny, uint8_t* out);
 int  s2sr_tiles_overview_u8(s2sr_handle* h, const uint8_t* child, int32_t cnx, int32_t cny, int32_t ox, int32_t oy, int32_t pnx,
                             int32_t pny, uint8_t* out);
+/* resample: a level through a separable filter given as tap tables -- the other form of base (source: a raster) and of overview
+ * (source: the level below, crossing its tile borders).  The entry knows no filter: Lanczos, cubic and bilinear are tables.
+ * Column sample j of nx*256 reads source columns col_first[j] .. col_first[j] + col_count[j] - 1 with the integer coefficients
+ * col_coef[j][0 .. Kx) (22 fractional bits; count 0 = the sample misses the source); rows alike.  Pixels are RGBA u8, not
+ * premultiplied; the arithmetic is Pillow's Image.resize: premultiply on load (c' = ((m >> 8) + m) >> 8, m = c * a + 128),
+ * horizontal pass clip((2^21 + sum coef * px) >> 22, 0, 255) per channel stored as 8 bits, the same down the columns,
+ * un-premultiply on store (alpha 0 / 255: copy; else min(255, 255 * c' / a)).
+ * Refused with S2SR_E_INVALID before the device is touched: K outside 1..S2SR_RESAMPLE_MAX_TAPS, a count outside 0..K, taps that
+ * leave the source (first < 0 or first + count > its extent), a sample with 255 * sum|coef| + 2^21 >= 2^31, and src == NULL when
+ * the previous call on the handle left no raster / level of the stated size.  out == NULL: the level stays on the device, for
+ * s2sr_tiles_write_png and as the source of the next overview or resample call, exactly like base / overview. */
+#define S2SR_TILES_SRC_RASTER 0   /* src: [sa = H, sb = W, 4] u8;  NULL: the raster s2sr_warp_bilinear_u8 left on the device */
+#define S2SR_TILES_SRC_LEVEL  1   /* src: [sa = cny, sb = cnx] tiles; NULL: the level the previous tiles call left on the device */
+#define S2SR_RESAMPLE_MAX_TAPS 64
+int  s2sr_tiles_resample_u8(s2sr_handle* h, const uint8_t* src, int32_t src_kind, int32_t sa, int32_t sb,
+                            const int32_t* col_first, const int32_t* col_count, const int32_t* col_coef, int32_t Kx,
+                            const int32_t* row_first, const int32_t* row_count, const int32_t* row_coef, int32_t Ky,
+                            int32_t nx, int32_t ny, uint8_t* out /* NULL: the level stays on the device */);
 /* base / overview with out == NULL: the level is computed and stays on the device (for s2sr_tiles_write_png and as the next
  * overview's children).
  * write_png: the PNG files (8-bit RGBA, what s2sr_png_encode writes up to the tokenisation: runs do not cross rows) of the level the

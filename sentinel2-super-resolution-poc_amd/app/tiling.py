@@ -5,7 +5,9 @@ process_raster_to_tiles :227-275), without gdalinfo / gdalwarp / gdal2tiles.py s
 
 Scope: 8-bit RGB rasters (what the SR path writes) in UTM (EPSG:326xx / 327xx), EPSG:4326 or
 EPSG:3857, north-up.  Resampling definitions are this build's (s2sr/tiles.py, csrc/tiles.hip);
-GDAL is not available to compare against, see DESIGN.md.
+GDAL is not available to compare against, see DESIGN.md.  The pyramid is cut with "average" (the
+default, what tiling.py:138-186 passes) or with "lanczos" / "cubic" / "bilinear" (what the SR-to-tiles
+job passes, reference esrgan_tiles.py:138; csrc/resample.hip, Pillow's arithmetic).
 """
 from __future__ import annotations
 
@@ -151,14 +153,30 @@ def reproject_to_web_mercator(input_path: Path, output_path: Path, resample_meth
 LAST_STATS: dict = {}        # where the last process_raster_to_tiles / generate_xyz_tiles call spent its time (seconds; tools/bench_job.py)
 
 
-def _cut_pyramid(rgba: np.ndarray, place: geo.Placement, output_dir: Path, min_zoom: int, max_zoom: int, on_device: bool = False) -> None:
+RESAMPLINGS = ("average",) + tiles.FILTERS
+
+
+def _check_tile_args(tile_size: int, resampling: str) -> None:
+    if tile_size != 256:
+        raise ValueError(f"tile_size {tile_size!r}: 256-pixel tiles are what is implemented")
+    if resampling not in RESAMPLINGS:
+        raise ValueError(f"resampling {resampling!r}: one of {', '.join(RESAMPLINGS)} (the reference passes average for its pyramids and "
+                         "lanczos for the SR-to-tiles job)")
+
+
+def _cut_pyramid(rgba: np.ndarray, place: geo.Placement, output_dir: Path, min_zoom: int, max_zoom: int, on_device: bool = False,
+                 resampling: str = "average") -> None:
     """RGBA raster on the EPSG:3857 grid -> z/x/y.png files (deepest zoom from the raster, the others from their children).
     The levels never leave the device as pixels: each is computed from the previous one's device copy and its PNG files are encoded
     there (s2sr_tiles_write_png: token statistics and bit emission are kernels, the Huffman codes come from the host in between;
     chunk framing, CRC and the file writes run on native host threads).  on_device: `rgba` is what the caller's warp call just left on
     the engine (the caller holds the engine's lock across both): the base level reads that copy.  r04, same 12.8k-tile pyramid: levels fetched and deflated
-    by zlib on a Python pool 1.9 s -> native host encoder, one call per 8 tiles 0.6 s -> encoded on the device (this)."""
+    by zlib on a Python pool 1.9 s -> native host encoder, one call per 8 tiles 0.6 s -> encoded on the device (this).
+    resampling: "average" = footprint means (tiles_base / tiles_overview); a filter of tiles.FILTERS = the deepest level resampled
+    from the raster and every shallower one 2:1 from the level below it, across its tile borders (tiles_resample_u8); alpha is
+    then fractional along the raster's edge."""
     import time
+    _check_tile_args(256, resampling)
     h, w = rgba.shape[:2]
     output_dir.mkdir(parents=True, exist_ok=True)
     eng, lock = _engine_and_lock()
@@ -169,7 +187,15 @@ def _cut_pyramid(rgba: np.ndarray, place: geo.Placement, output_dir: Path, min_z
     with lock:
         for lv in levels:
             t0 = time.perf_counter()
-            if prev_lv is None:
+            if resampling != "average":
+                if prev_lv is None:
+                    cols, rows = tiles.plan_resample_level(lv, tiles.level_box(lv, place), w, h, resampling)
+                    eng.tiles_resample_u8(rgba, cols, rows, lv.nx, lv.ny, on_device=on_device, fetch=False)
+                else:
+                    cols, rows = tiles.plan_resample_level(lv, tiles.overview_box(lv, prev_lv), prev_lv.nx * geo.TILE, prev_lv.ny * geo.TILE,
+                                                           resampling)
+                    eng.tiles_resample_u8(None, cols, rows, lv.nx, lv.ny, level_shape=(prev_lv.ny, prev_lv.nx), on_device=True, fetch=False)
+            elif prev_lv is None:
                 eng.tiles_base_u8(rgba, *tiles.plan_base(lv, place, w, h), fetch=False, on_device=on_device)
             else:
                 ox, oy = tiles.overview_offsets(lv, prev_lv)
@@ -186,8 +212,7 @@ def _cut_pyramid(rgba: np.ndarray, place: geo.Placement, output_dir: Path, min_z
 def generate_xyz_tiles(input_path: Path, output_dir: Path, min_zoom: int = 10, max_zoom: int = 16, tile_size: int = 256,
                        resampling: str = "average") -> Path:
     """z/x/y.png (XYZ row order, RGBA) for every tile of zooms min..max that holds data."""
-    if tile_size != 256 or resampling != "average":
-        raise ValueError("tile_size 256 and average resampling are what the reference uses and what is implemented")
+    _check_tile_args(tile_size, resampling)
     input_path, output_dir = Path(input_path), Path(output_dir)
     arr, _tags, place, crs = _read(input_path)
     if crs.epsg != 3857:
@@ -196,7 +221,7 @@ def generate_xyz_tiles(input_path: Path, output_dir: Path, min_zoom: int = 10, m
     rgba = np.empty((h, w, 4), np.uint8)
     rgba[..., :3] = arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2)
     rgba[..., 3] = 255
-    _cut_pyramid(rgba, place, output_dir, min_zoom, max_zoom)
+    _cut_pyramid(rgba, place, output_dir, min_zoom, max_zoom, resampling=resampling)
     logger.info("Tile generation complete: %s", output_dir)
     return output_dir
 
@@ -211,9 +236,11 @@ def create_tileset_metadata(tiles_dir: Path, bounds_4326: list, min_zoom: int, m
     return metadata
 
 
-def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 10, max_zoom: int = 16) -> dict:
+def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 10, max_zoom: int = 16, resampling: str = "average",
+                            tile_template: str = "/tiles/{z}/{x}/{y}.png") -> dict:
     """Check the CRS, reproject if needed, cut the pyramid, write tileset.json."""
     import time
+    _check_tile_args(256, resampling)
     input_path, tiles_dir = Path(input_path), Path(tiles_dir)
     LAST_STATS.clear()
     t0 = time.perf_counter()
@@ -252,7 +279,7 @@ def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 1
             rgba = np.dstack([rgb, np.full((h, w), 255, np.uint8)])
         t4 = time.perf_counter()
         try:
-            _cut_pyramid(np.ascontiguousarray(rgba), place, tiles_dir, min_zoom, max_zoom, on_device=side is not None)
+            _cut_pyramid(np.ascontiguousarray(rgba), place, tiles_dir, min_zoom, max_zoom, on_device=side is not None, resampling=resampling)
         finally:
             if side is not None:
                 t5 = time.perf_counter()
@@ -261,4 +288,4 @@ def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 1
     if err:
         raise err[0]
     LAST_STATS["pyramid"] = time.perf_counter() - t4
-    return create_tileset_metadata(tiles_dir, bounds_4326, min_zoom, max_zoom)
+    return create_tileset_metadata(tiles_dir, bounds_4326, min_zoom, max_zoom, tile_template=tile_template)

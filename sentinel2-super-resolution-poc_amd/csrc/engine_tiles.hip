@@ -1,5 +1,5 @@
-// libs2sr engine, the XYZ tile pyramid: the reprojection warp, the base and overview levels and the driver of the device PNG
-// writer (pngdev.hip).
+// libs2sr engine, the XYZ tile pyramid: the reprojection warp, the base and overview levels (averaged, or resampled through tap
+// tables) and the driver of the device PNG writer (pngdev.hip).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -12,6 +12,7 @@
 
 #include "engine_internal.h"
 #include "png_internal.h"
+#include "resample_tables.h"
 
 using namespace s2sr;
 using namespace s2sr::engine;
@@ -114,6 +115,76 @@ int s2sr_tiles_overview_u8(s2sr_handle* h, const uint8_t* child, int32_t cnx, in
     if (out) HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[out_slot], ob, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     h->tiles_slot = out_slot; h->tiles_nx = pnx; h->tiles_ny = pny;
+    return S2SR_OK;
+}
+
+// A level resampled through tap tables (resample.hip): the deepest one from a raster, a shallower one from the level below it.
+// Same protocol as the two calls above: the source in scratch 0 (or where the previous call left it), the level in the other of
+// 0 / 1, tables in 3; the 8-bit intermediate between the passes lives in scratch 2, which only s2sr_tiles_write_png uses, and only
+// inside its own call.
+int s2sr_tiles_resample_u8(s2sr_handle* h, const uint8_t* src, int32_t src_kind, int32_t sa, int32_t sb, const int32_t* col_first,
+                           const int32_t* col_count, const int32_t* col_coef, int32_t Kx, const int32_t* row_first,
+                           const int32_t* row_count, const int32_t* row_coef, int32_t Ky, int32_t nx, int32_t ny, uint8_t* out) {
+    if (!h) return S2SR_E_INVALID;
+    if (!col_first || !col_count || !col_coef || !row_first || !row_count || !row_coef || sa <= 0 || sb <= 0 || nx <= 0 || ny <= 0 ||
+        nx > (1 << 15) || ny > (1 << 15))
+        return fail(h, S2SR_E_INVALID, "resample: a table is missing or a size is not positive");
+    if (src_kind != S2SR_TILES_SRC_RASTER && src_kind != S2SR_TILES_SRC_LEVEL)
+        return fail(h, S2SR_E_INVALID, "resample: src_kind is neither S2SR_TILES_SRC_RASTER nor S2SR_TILES_SRC_LEVEL");
+    const bool level = src_kind == S2SR_TILES_SRC_LEVEL;
+    if (level && (sa > (1 << 15) || sb > (1 << 15))) return fail(h, S2SR_E_INVALID, "resample: the source level is too large");
+    const int64_t MW = (int64_t)nx * 256, MH = (int64_t)ny * 256;
+    const int64_t src_w = level ? (int64_t)sb * 256 : sb, src_h = level ? (int64_t)sa * 256 : sa;
+    int32_t c_lo, c_hi, r_lo, r_hi;
+    if (const char* why = resample_check_axis(col_first, col_count, col_coef, MW, Kx, src_w, &c_lo, &c_hi)) {
+        std::string m = std::string("resample, column tables: ") + why;
+        return fail(h, S2SR_E_INVALID, m.c_str());
+    }
+    if (const char* why = resample_check_axis(row_first, row_count, row_coef, MH, Ky, src_h, &r_lo, &r_hi)) {
+        std::string m = std::string("resample, row tables: ") + why;
+        return fail(h, S2SR_E_INVALID, m.c_str());
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    // src == NULL: the source is what the previous call on this handle left on the device -- the raster of s2sr_warp_bilinear_u8,
+    // or the level of a base / overview / resample call
+    int in_slot = 0;
+    if (!src) {
+        if (!level && (h->warp_slot < 0 || h->warp_h != sa || h->warp_w != sb))
+            return fail(h, S2SR_E_INVALID, "src == NULL, but the previous call on this handle did not leave a warped raster of this size on the device");
+        if (level && (h->tiles_slot < 0 || h->tiles_ny != sa || h->tiles_nx != sb))
+            return fail(h, S2SR_E_INVALID, "src == NULL, but the previous call on this handle did not leave a tile level of this size on the device");
+        in_slot = level ? h->tiles_slot : h->warp_slot;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    const int out_slot = in_slot == 1 ? 0 : 1;
+    const int nrows = r_hi - r_lo;                                  // the source rows some output row reads
+    const size_t ib = (size_t)src_h * src_w * 4, ob = (size_t)MW * MH * 4, mb = (size_t)MW * (nrows > 0 ? nrows : 1) * 4;
+    const size_t cw = (size_t)MW * (2 + Kx), rw = (size_t)MH * (2 + Ky);
+    std::vector<int32_t> tables(cw + rw);                           // [col first | count | coef Kx x MW][row first | count | coef Ky x MH]
+    resample_pack_axis(col_first, col_count, col_coef, MW, Kx, tables.data());
+    resample_pack_axis(row_first, row_count, row_coef, MH, Ky, tables.data() + cw);
+    int rc;
+    if (src && (rc = ensure_scratch(h, in_slot, ib))) return rc;
+    if ((rc = ensure_scratch(h, out_slot, ob))) return rc;
+    if ((rc = ensure_scratch(h, 2, mb))) return rc;
+    if ((rc = ensure_scratch(h, 3, (cw + rw) * 4))) return rc;
+    const int32_t* tc = (const int32_t*)h->d_scratch[3];
+    const int32_t* tr = tc + cw;
+    if (src) HIPCHK(h, hipMemcpyAsync(h->d_scratch[in_slot], src, ib, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[3], tables.data(), (cw + rw) * 4, hipMemcpyHostToDevice, st));
+    {
+        Scope sc(h, st, F_MISC, 0.0, (double)nrows * (double)(c_hi - c_lo) * 4.0 + (double)mb);      // algorithmic: each byte once
+        HIPCHK(h, launch_resample_h((const uint8_t*)h->d_scratch[in_slot], level, sb, tc, tc + MW, tc + 2 * MW, nx, r_lo, nrows,
+                                    (uint8_t*)h->d_scratch[2], st));
+    }
+    {
+        Scope sc(h, st, F_MISC, 0.0, (double)mb + (double)ob);
+        HIPCHK(h, launch_resample_v((const uint8_t*)h->d_scratch[2], r_lo, tr, tr + MH, tr + 2 * MH, nx, ny, (uint8_t*)h->d_scratch[out_slot], st));
+    }
+    if (out) HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[out_slot], ob, hipMemcpyDeviceToHost, st));      // out == NULL: the level stays on the device
+    HIPCHK(h, hipStreamSynchronize(st));
+    h->tiles_slot = out_slot; h->tiles_nx = nx; h->tiles_ny = ny;
     return S2SR_OK;
 }
 

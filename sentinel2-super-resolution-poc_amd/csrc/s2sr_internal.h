@@ -257,6 +257,13 @@ hipError_t launch_tiles_base(const uint8_t* d_rgba, int W, const int32_t* d_col_
 hipError_t launch_tiles_overview(const uint8_t* d_child, int cnx, int cny, int ox, int oy, int pnx, int pny, uint8_t* d_out,
                                  hipStream_t st);
 
+// resampled tile levels (resample.hip): tap tables in, no notion of a filter.  level: the source is a tile-major level sb tiles
+// wide (else a raster sb pixels wide); the horizontal pass fills the intermediate's rows [r0, r0 + nrows) of the source
+hipError_t launch_resample_h(const uint8_t* d_src, bool level, int sb, const int32_t* d_first, const int32_t* d_count,
+                             const int32_t* d_coef, int nx, int r0, int nrows, uint8_t* d_inter, hipStream_t st);
+hipError_t launch_resample_v(const uint8_t* d_inter, int r0, const int32_t* d_first, const int32_t* d_count, const int32_t* d_coef,
+                             int nx, int ny, uint8_t* d_out, hipStream_t st);
+
 // PNG encoding of a tile level on the device (pngdev.hip): stats kernel -> host plan (Huffman codes, sizes) -> emit kernel.
 struct PngTilePlan {
     std::vector<uint8_t> mode;            // 0 nothing to write, 1 device stream, 2 host encoder (stored blocks are smaller)

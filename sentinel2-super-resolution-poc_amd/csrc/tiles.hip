@@ -8,6 +8,7 @@
 //   tiles_base     : deepest zoom: every tile pixel = rounded mean of the valid source pixels in its
 //                    footprint [col_lo..col_hi] x [row_lo..row_hi] (tables per mosaic column / row).
 //   tiles_overview : parent tile pixel = rounded mean of the valid pixels of its 2x2 children group.
+// These are the "average" levels; the levels' other form (Lanczos / cubic / bilinear through tap tables) is resample.hip.
 // Float steps are single IEEE operations in a fixed order (-ffp-contract=off): the numpy oracle
 // (oracle/tiles_ref.py) reproduces them bit for bit.
 #include "s2sr_internal.h"

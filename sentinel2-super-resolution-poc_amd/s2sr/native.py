@@ -159,6 +159,8 @@ _PROTOS = {
                                         C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tiles_base_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tiles_overview_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p]),
+    "s2sr_tiles_resample_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + ([C.c_void_p] * 3 + [C.c_int32]) * 2 +
+                               [C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tiles_write_png": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_int32)]),
     "s2sr_tiles_write_png_xyz": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                            C.POINTER(C.c_int32)]),
@@ -772,6 +774,38 @@ class Engine:
             src = _ptr(child)
         self._check(self._lib.s2sr_tiles_overview_u8(self._h, src, cnx, cny, ox, oy, pnx, pny, _ptr(out) if fetch else None),
                     "s2sr_tiles_overview_u8")
+        return out
+
+    def tiles_resample_u8(self, src, cols, rows, nx: int, ny: int, level_shape=None, on_device: bool = False,
+                          fetch: bool = True) -> Optional[np.ndarray]:
+        """A level through tap tables (s2sr_tiles_resample_u8): cols / rows = (first, count, coef[, K]) of nx*256 / ny*256 samples,
+        as s2sr.tiles.plan_resample_axis returns them.  src: an RGBA raster [H, W, 4], or a level [cny, cnx, 256, 256, 4].
+        on_device: the source is what the previous call on this engine left on the device -- the raster of warp_bilinear_u8, or with
+        level_shape = (cny, cnx) the level of a tiles call -- and `src` is then only read for its shape (an array, (H, W), or
+        None with level_shape).  fetch=False: the level stays on the device, returns None."""
+        is_level = level_shape is not None or (hasattr(src, "ndim") and src.ndim == 5)
+        if on_device:
+            sa, sb = level_shape if level_shape is not None else (src.shape[:2] if hasattr(src, "shape") else src)
+            ptr = None
+        else:
+            src = np.ascontiguousarray(src, np.uint8)
+            if src.shape[-1] != 4 or (is_level and src.shape[2:4] != (256, 256)) or (level_shape is not None and tuple(level_shape) != src.shape[:2]):
+                raise ValueError(f"expected [H, W, 4] or [cny, cnx, 256, 256, 4] uint8, got {src.shape}")
+            sa, sb = src.shape[:2]
+            ptr = _ptr(src)
+        t = []
+        for first, count, coef in (cols[:3], rows[:3]):
+            first, count, coef = (np.ascontiguousarray(a, np.int32) for a in (first, count, coef))
+            if coef.ndim != 2 or first.shape != (coef.shape[0],) or count.shape != first.shape:
+                raise ValueError(f"tap tables: first {first.shape}, count {count.shape}, coef {coef.shape}")
+            t.append((first, count, coef))
+        if t[0][0].size != nx * 256 or t[1][0].size != ny * 256:
+            raise ValueError(f"{nx} x {ny} tiles, tables of {t[0][0].size} columns and {t[1][0].size} rows")
+        out = np.empty((ny, nx, 256, 256, 4), np.uint8) if fetch else None
+        self._check(self._lib.s2sr_tiles_resample_u8(self._h, ptr, 1 if is_level else 0, int(sa), int(sb),
+                                                     _ptr(t[0][0]), _ptr(t[0][1]), _ptr(t[0][2]), t[0][2].shape[1],
+                                                     _ptr(t[1][0]), _ptr(t[1][1]), _ptr(t[1][2]), t[1][2].shape[1],
+                                                     nx, ny, _ptr(out) if fetch else None), "s2sr_tiles_resample_u8")
         return out
 
     def tiles_write_png(self, nx: int, ny: int, paths, skip_transparent: bool = True, host_encoder: bool = False,

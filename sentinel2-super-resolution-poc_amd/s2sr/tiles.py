@@ -11,10 +11,16 @@ The geometry is resolved here in float64 into plain integer / float32 tables; th
             fall inside its footprint (nearest source pixel when the footprint holds none), given
             as [lo, hi] column / row index tables per tile column / row;
   overview  every shallower zoom from the four children of a tile: mean of the valid (alpha > 0)
-            pixels of each 2x2 group.
+            pixels of each 2x2 group;
+  resample  the other form of both levels (csrc/resample.hip): a separable Lanczos / cubic / bilinear
+            filter, given as per-column and per-row tap tables (first source index, tap count, integer
+            coefficients) -- plan_resample_axis; the deepest level's box in raster pixels is level_box,
+            a shallower level's box in the pixels of the level below it is overview_box.
 
-Parity note: GDAL is not available to this build, so these are this build's definitions of
-"bilinear" and "average" (DESIGN.md section 7), not bit-for-bit gdalwarp / gdal2tiles.
+Parity note: GDAL is not available to this build, so "bilinear" (warp) and "average" are this
+build's definitions, not bit-for-bit gdalwarp / gdal2tiles.  The resampled
+levels are Pillow's Image.resize arithmetic, integer throughout, and pinned to it byte for byte
+(tests/test_resample_cpu.py).
 """
 from __future__ import annotations
 
@@ -114,3 +120,90 @@ def plan_base(level: LevelPlan, src: geo.Placement, width: int, height: int) -> 
 def overview_offsets(parent: LevelPlan, child: LevelPlan) -> Tuple[int, int]:
     """Child-array (col, row) of the north-west child of the parent array's first tile."""
     return 2 * parent.tminx - child.tminx, child.tmaxy - (2 * parent.tmaxy + 1)
+
+
+# ---------------------------------------------------------------------------------------------
+# resampled levels: Lanczos / cubic / bilinear as tap tables (DESIGN.md section 7.1)
+# ---------------------------------------------------------------------------------------------
+FILTERS = ("lanczos", "cubic", "bilinear")
+RESAMPLE_MAX_TAPS = 64          # S2SR_RESAMPLE_MAX_TAPS
+COEF_BITS = 22                  # fractional bits of a coefficient: 32 - 8 (pixel) - 2 (headroom for sum|coef| < 2)
+_SUPPORT = {"lanczos": 3.0, "cubic": 2.0, "bilinear": 1.0}
+
+
+def _sinc(x: np.ndarray) -> np.ndarray:
+    y = x * np.pi
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(x == 0.0, 1.0, np.sin(y) / y)
+
+
+def _filter(name: str, x: np.ndarray) -> np.ndarray:
+    x = np.abs(x)               # all three are even
+    if name == "bilinear":
+        return np.where(x < 1.0, 1.0 - x, 0.0)
+    if name == "cubic":         # Keys, a = -0.5
+        a = -0.5
+        return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0,
+                        np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * a, 0.0))
+    return np.where(x < 3.0, _sinc(x) * _sinc(x / 3.0), 0.0)
+
+
+def plan_resample_axis(n_out: int, a0: float, a1: float, n_src: int, filter: str):
+    """One axis of a resampled level: n_out samples cover [a0, a1) in continuous source-pixel coordinates (either end may lie
+    outside [0, n_src]).  -> first [n_out] int32, count [n_out] int32, coef [n_out, K] int32, K: sample j is
+    clip((2^21 + sum_t coef[j, t] * src[first[j] + t]) >> 22) over t < count[j].  The weights of the whole window
+    [floor(c - support + 0.5), floor(c + support + 0.5)) are normalised in float64 and rounded (half away from zero) to 22
+    fractional bits FIRST; the taps outside [0, n_src) are dropped afterwards: the raster lies in a transparent plane, its edge is
+    not replicated, a window that misses it has 0 taps.  K is the largest whole window."""
+    if filter not in FILTERS:
+        raise ValueError(f"filter {filter!r}: one of {FILTERS}")
+    if n_out <= 0 or n_src <= 0 or not a1 > a0:
+        raise ValueError(f"n_out {n_out}, n_src {n_src}, [{a0}, {a1}): nothing to resample")
+    scale = (float(a1) - float(a0)) / n_out
+    fs = max(scale, 1.0)
+    support = _SUPPORT[filter] * fs
+    ss = 1.0 / fs
+    c = float(a0) + (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    lo = np.floor(c - support + 0.5).astype(np.int64)
+    hi = np.floor(c + support + 0.5).astype(np.int64)
+    K = max(1, int((hi - lo).max()))
+    if K > RESAMPLE_MAX_TAPS:
+        raise ValueError(f"{filter} at {scale:.2f} source pixels per tile pixel needs {K} taps, {RESAMPLE_MAX_TAPS} is the limit: "
+                         "choose a deeper max_zoom")
+    t = np.arange(K, dtype=np.int64)[None, :]
+    inside = t < (hi - lo)[:, None]
+    w = np.where(inside, _filter(filter, ((lo[:, None] + t).astype(np.float64) - c[:, None] + 0.5) * ss), 0.0)
+    ww = np.add.accumulate(w, axis=1)[:, -1:]                       # summed left to right
+    w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    full = np.trunc(w * float(1 << COEF_BITS) + np.where(w < 0.0, -0.5, 0.5)).astype(np.int64)
+    skip = np.clip(-lo, 0, None)                                    # taps west / north of the raster
+    first = lo + skip
+    count = np.clip(np.minimum(hi, n_src) - first, 0, None)
+    first = np.where(count > 0, first, 0)
+    coef = np.take_along_axis(full, np.minimum(t + skip[:, None], K - 1), axis=1)
+    coef = np.where(t < count[:, None], coef, 0)
+    return first.astype(np.int32), count.astype(np.int32), np.ascontiguousarray(coef, np.int32), K
+
+
+def level_box(level: LevelPlan, place: geo.Placement) -> Tuple[float, float, float, float]:
+    """(x0, y0, x1, y1): the level mosaic's west, north, east and south edges in the raster's continuous pixel coordinates
+    (columns rightwards, rows downwards) -- the geometry of plan_base."""
+    r = geo.resolution(level.zoom)
+    x_lo = level.tminx * geo.TILE * r - geo.ORIGIN_SHIFT
+    y_hi = (level.tmaxy + 1) * geo.TILE * r - geo.ORIGIN_SHIFT
+    return ((x_lo - place.x0) / place.dx, (place.y0 - y_hi) / place.dy,
+            (x_lo + level.nx * geo.TILE * r - place.x0) / place.dx, (place.y0 - (y_hi - level.ny * geo.TILE * r)) / place.dy)
+
+
+def overview_box(parent: LevelPlan, child: LevelPlan) -> Tuple[float, float, float, float]:
+    """(x0, y0, x1, y1): the parent mosaic's extent in child-mosaic pixels; the scale is exactly 2."""
+    ox, oy = overview_offsets(parent, child)
+    return (float(ox * geo.TILE), float(oy * geo.TILE), float((ox + 2 * parent.nx) * geo.TILE), float((oy + 2 * parent.ny) * geo.TILE))
+
+
+def plan_resample_level(level: LevelPlan, box, n_cols: int, n_rows: int, filter: str):
+    """-> (cols, rows): the column and row tables (first, count, coef, K) of a level whose mosaic covers `box` of a source n_cols
+    wide and n_rows high."""
+    x0, y0, x1, y1 = box
+    return (plan_resample_axis(level.nx * geo.TILE, x0, x1, n_cols, filter),
+            plan_resample_axis(level.ny * geo.TILE, y0, y1, n_rows, filter))
