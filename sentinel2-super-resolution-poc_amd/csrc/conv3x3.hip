@@ -932,42 +932,32 @@ static hipError_t launch_w(const ConvParams& p, hipStream_t st) {
     return launch_t<CT, EPI, UP, 8, 2, (CT == 1) ? 5 : 4>(p, st);
 }
 
-hipError_t launch_conv(const ConvParams& p, int ct, int epi, bool up, bool lo_out, hipStream_t st, bool f8_in) {
-    if (f8_in) {   // split-operand mode: fp16 main term + fp8 correction planes in; lo_out: fp8 planes out as well
-        const bool full = p.mos_py == 0 && p.H % 16 == 0 && p.W % 32 == 0 && !(p.tail_form & 8);   // whole 16x32 patches (bit 3: diagnostic off switch)
-        if (ct == 2 && lo_out && epi == EPI_LRELU && !up && (p.tail_form & 2))   // conv_hr in front of a folded conv_last: no hi8 planes out
-            return full ? launch_t<2, EPI_LRELU, false, 8, 2, 4, 2, 1, true, -1, true>(p, st)
-                        : launch_t<2, EPI_LRELU, false, 8, 2, 4, 2, 1, true>(p, st);
-        if (ct == 2 && lo_out && epi == EPI_BODY && !up && full) return launch_t<2, EPI_BODY, false, 8, 2, 4, 1, 1, true, -1, true>(p, st);
-        if (ct == 2 && lo_out) {
-            if (epi == EPI_LRELU && !up) return launch_t<2, EPI_LRELU, false, 8, 2, 4, 1, 1, true>(p, st);
-            if (epi == EPI_BODY && !up) return launch_t<2, EPI_BODY, false, 8, 2, 4, 1, 1, true>(p, st);
-        }
-        if (ct == 1 && !lo_out && epi == EPI_LAST && !up) {
-            if (p.nstage == 6 && p.fold_lo)
-                return full ? launch_t<1, EPI_LAST, false, 8, 2, 4, 3, 1, true, -1, true>(p, st)
-                            : launch_t<1, EPI_LAST, false, 8, 2, 4, 3, 1, true>(p, st);
-            return launch_t<1, EPI_LAST, false, 8, 2, 4, 0, 1, true>(p, st);
-        }
-        return hipErrorInvalidValue;
-    }
-    if (lo_out) return hipErrorInvalidValue;
-    // the RDB convs run on conv_trunk.hip, the up-convs in sub-pixel form (launch_conv_phase)
-    if ((ct == 1 && epi == EPI_LRELU && !up) || (ct == 2 && epi == EPI_LRELU && up) ||
-        (ct == 2 && (epi == EPI_RDB5 || epi == EPI_RDB5_RRDB) && !up))
-        return hipErrorNotSupported;
-    if (ct == 1) {
-        if (epi == EPI_LAST && !up) return launch_w<1, EPI_LAST, false>(p, st);
-        if (epi == EPI_DEBUG) return up ? launch_w<1, EPI_DEBUG, true>(p, st) : launch_w<1, EPI_DEBUG, false>(p, st);
-    } else if (ct == 2) {
-        if (epi == EPI_LRELU) return launch_w<2, EPI_LRELU, false>(p, st);
-        if (epi == EPI_FIRST && !up) return launch_w<2, EPI_FIRST, false>(p, st);
-        if (epi == EPI_BODY && !up) return launch_w<2, EPI_BODY, false>(p, st);
-        // SRVGGNetCompact: the same 8-wave, 16x32-patch form with the PReLU / pixel-shuffle epilogues
-        if (epi == EPI_PRELU && !up && p.slope) return launch_w<2, EPI_PRELU, false>(p, st);
-        if (epi == EPI_CFIRST && !up && p.slope) return launch_w<2, EPI_CFIRST, false>(p, st);
-        if (epi == EPI_CLAST && !up && p.src_lo) return launch_w<2, EPI_CLAST, false>(p, st);
-        if (epi == EPI_DEBUG) return up ? launch_w<2, EPI_DEBUG, true>(p, st) : launch_w<2, EPI_DEBUG, false>(p, st);
+hipError_t launch_conv(const ConvParams& p, ConvForm form, hipStream_t st) {
+    // the split-operand forms take whole 16x32 patches when the launch has nothing else (tail_form bit 3: diagnostic off switch)
+    const bool full = p.mos_py == 0 && p.H % 16 == 0 && p.W % 32 == 0 && !(p.tail_form & 8);
+    switch (form) {
+    case CF_FIRST: return launch_w<2, EPI_FIRST, false>(p, st);
+    case CF_BODY: return launch_w<2, EPI_BODY, false>(p, st);
+    case CF_HR: return launch_w<2, EPI_LRELU, false>(p, st);
+    case CF_LAST: return launch_w<1, EPI_LAST, false>(p, st);
+    case CF_BODY_SPLIT:
+        return full ? launch_t<2, EPI_BODY, false, 8, 2, 4, 1, 1, true, -1, true>(p, st) : launch_t<2, EPI_BODY, false, 8, 2, 4, 1, 1, true>(p, st);
+    case CF_HR_SPLIT: return launch_t<2, EPI_LRELU, false, 8, 2, 4, 1, 1, true>(p, st);
+    case CF_HR_SPLIT_NOHI:
+        if (!(p.tail_form & 2)) return hipErrorInvalidValue;
+        return full ? launch_t<2, EPI_LRELU, false, 8, 2, 4, 2, 1, true, -1, true>(p, st) : launch_t<2, EPI_LRELU, false, 8, 2, 4, 2, 1, true>(p, st);
+    case CF_LAST_SPLIT8: return launch_t<1, EPI_LAST, false, 8, 2, 4, 0, 1, true>(p, st);
+    case CF_LAST_FOLD:
+        return full ? launch_t<1, EPI_LAST, false, 8, 2, 4, 3, 1, true, -1, true>(p, st) : launch_t<1, EPI_LAST, false, 8, 2, 4, 3, 1, true>(p, st);
+    // SRVGGNetCompact: the same 8-wave, 16x32-patch form with the PReLU / pixel-shuffle epilogues
+    case CF_PRELU: return p.slope ? launch_w<2, EPI_PRELU, false>(p, st) : hipErrorInvalidValue;
+    case CF_CFIRST: return p.slope ? launch_w<2, EPI_CFIRST, false>(p, st) : hipErrorInvalidValue;
+    case CF_CLAST: return p.src_lo ? launch_w<2, EPI_CLAST, false>(p, st) : hipErrorInvalidValue;
+    case CF_DEBUG1: return launch_w<1, EPI_DEBUG, false>(p, st);
+    case CF_DEBUG1_UP: return launch_w<1, EPI_DEBUG, true>(p, st);
+    case CF_DEBUG2: return launch_w<2, EPI_DEBUG, false>(p, st);
+    case CF_DEBUG2_UP: return launch_w<2, EPI_DEBUG, true>(p, st);
+    case CF_NONE: break;   // the RDB convs run on conv_trunk.hip, the up-convs in sub-pixel form (launch_conv_phase)
     }
     return hipErrorInvalidValue;
 }

@@ -26,32 +26,6 @@ namespace {
 
 thread_local std::string g_create_error;
 
-struct ConvSpec {
-    int cin, cout;
-};
-
-std::vector<ConvSpec> conv_specs(int num_block, int scale) {
-    std::vector<ConvSpec> v;
-    v.push_back({scale == 2 ? 12 : 3, 64});   // conv_first; scale 2 reads the 12 channels of pixel_unshuffle(x, 2)
-    for (int b = 0; b < num_block; ++b)
-        for (int r = 0; r < 3; ++r)
-            for (int k = 1; k <= 5; ++k) v.push_back({64 + (k - 1) * 32, k < 5 ? 32 : 64});
-    v.push_back({64, 64});   // conv_body
-    v.push_back({64, 64});   // conv_up1
-    v.push_back({64, 64});   // conv_up2
-    v.push_back({64, 64});   // conv_hr
-    v.push_back({64, 3});    // conv_last
-    return v;
-}
-
-// SRVGGNetCompact(num_feat 64, num_conv, upscale 4): floats of its flat `body` list (conv weight, conv bias, 64 slopes, ...)
-size_t compact_blob_floats(int num_conv) {
-    return (size_t)(3 * 64 * 9 + 64 + 64) + (size_t)num_conv * (64 * 64 * 9 + 64 + 64) + (size_t)(64 * 48 * 9 + 48);
-}
-size_t handle_blob_floats(const s2sr_handle* h) {
-    return h->compact() ? compact_blob_floats(h->cfg.num_block) : s2sr_expected_blob_floats_scale(h->cfg.num_block, h->cfg.scale);
-}
-
 void free_weights(s2sr_handle* h) {
     for (ConvW& c : h->convs) {
         if (!c.pooled && c.d_wpack) dev_free(c.d_wpack);
@@ -77,8 +51,7 @@ size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mos_px = 0) {
     Workspace& w = h->ws;
-    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;
-    const bool hp = h->cfg.precision == S2SR_PREC_F16_HP || (fp8 && h->fp8_hp_tail);   // split-operand head / tail convs
+    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8, hp = h->hp();
     // a mosaic's separator rows / columns are conv zero padding: they must come from the allocation memset, so planes that
     // were written as plain images (or as a mosaic of another period) are not reused
     if (w.base && w.G >= G && w.H == H && w.W == W && w.hp == hp && w.fp8 == fp8 && w.mos_py == mos_py && w.mos_px == mos_px) return S2SR_OK;
@@ -190,62 +163,66 @@ void mosaic_at(ConvParams& q, const Mosaic& mo, int scale) {
     q.mos_kx = mo.kx; q.mos_ky = mo.ky; q.mos_count = mo.count;
 }
 
-// one conv launch
-int run_conv(s2sr_handle* h, hipStream_t st, int fam, const ConvW& cw, ConvParams p, int epi, bool up,
-             bool lo_out = false, s2sr_debug_trunk_form* form = nullptr) {   // form: where the RDB convs record their kernel form
-    p.wpack = cw.d_wpack;
-    p.bias = cw.d_bias;
-    p.nstage = cw.nstage;
-    p.seg_len = cw.seg_len;
-    p.seg_lo_mask = cw.seg_lo_mask;
-    p.fold_lo = cw.fold ? 1 : 0;
-    p.tail_form = h->f16_full ? 0 : 8;
-    // conv_hr: a folded conv_last (the last conv) reads x_lo planes only, so the e4m3(x_hi) planes need not be written
-    if (fam == F_HR && lo_out && !h->convs.empty() && h->convs.back().f8 && h->convs.back().fold) p.tail_form |= 2;
-    p.trash = h->d_trash;
+// The statistics of one launch of a layer: its family, and the nominal FLOPs and algorithmic bytes (every input and output element
+// once) over the launch's p.N x p.H x p.W pixels -- output pixels; the up-convs: source pixels of one row-parity launch.
+Scope layer_scope(s2sr_handle* h, hipStream_t st, const ConvW& cw, const ConvParams& p) {
+    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;  // the RDB convs on e4m3 planes of 32 channels
     const double px = (double)p.N * p.H * p.W;
-    const double flops = 2.0 * 9.0 * cw.cin * cw.cout * px;
-    double bytes = px * (up ? 0.25 : 1.0) * cw.cin * 2.0;   // algorithmic: every input element once
-    if (epi == EPI_LAST) bytes += px * 3.0 * ((p.out_u8 ? 1.0 : 0.0) + (p.out_f32 ? 4.0 : 0.0));
-    else bytes += px * cw.cout * 2.0;
-    // split-operand convs (hp): the e4m3 correction planes they read (4 planes of 32 B per pixel; a folded conv_last reads the
-    // two x_lo planes only) and write (4 planes; 2 when the consumer is a folded conv_last)
-    if (cw.f8) bytes += px * (up ? 0.25 : 1.0) * (cw.fold ? 64.0 : 128.0);
-    if (lo_out) bytes += px * ((p.tail_form & 2) ? 64.0 : 128.0);
-    // the trunk's lo half travels as e4m3 planes (1 B per channel)
-    if (epi == EPI_RDB5) bytes += px * 64 * 2.0;                        // lo: read + write
-    if (epi == EPI_RDB5_RRDB) bytes += px * 64 * (p.xh_skip ? 5.0 : 12.0);    // lo r/w + RRDB skip: (fp16 hi, e4m3 lo) pair read, or fp32 R r/w
-    if (epi == EPI_FIRST) bytes += px * 64 * 10.0;        // lo + R + F
-    if (epi == EPI_BODY) bytes += px * 64 * 4.0;
-    Scope sc(h, st, fam, flops, bytes);
+    const double out_b = (p.out_u8 ? 1.0 : 0.0) + (p.out_f32 ? 4.0 : 0.0);   // bytes per output sample the caller asked for
+    const double io = cw.cin * 2.0 + cw.cout * 2.0;      // fp16 in and out
+    const double planes = cw.split ? 128.0 : 0.0;        // hp: the four e4m3 correction planes of a 64-channel tensor (32 B per pixel each)
+    const double f8in = 32.0 * cw.seg_len;
+    double flops = 2.0 * 9.0 * cw.cin * cw.cout * px, b = 0.0;
+    switch (cw.role) {
+    case L_FIRST: b = io + 64 * 10.0; break;                                      // + trunk lo, R, F
+    case L_RDB14: b = fp8 ? f8in + 32.0 : io; break;
+    case L_RDB5: b = fp8 ? f8in + 64.0 + 128.0 + 128.0 : io + 64 * 2.0; break;    // fp8: e4m3 x out, fp16 trunk in + out; fp16: lo read + write
+    case L_RDB5_RRDB: b = fp8 ? f8in + 64.0 + 3 * 128.0 : io + 64 * 5.0; break;   // + the RRDB skip: fp16 x; (fp16 hi, e4m3 lo) pair
+    case L_BODY: b = io + 2 * planes + 64 * 4.0; break;                           // planes in and out, F
+    case L_HR: b = io + planes + (cw.form == CF_HR_SPLIT_NOHI ? 64.0 : planes); break;   // a folded conv_last wants the two x_lo planes only
+    case L_LAST: b = cw.cin * 2.0 + 3.0 * out_b + (cw.form == CF_LAST_FOLD ? 64.0 : planes); break;
+    // sub-pixel up-convs: the nominal work of the 3x3 form (2*9*cin*cout per OUTPUT pixel; one row parity = half of the four); the
+    // source block once (fp16 128 B, + 128 B of planes), two output pixels (both column parities) of 128 B (+ 128 B of planes) each
+    case L_UP1: case L_UP2: flops *= 2.0; b = cw.split ? 768.0 : 384.0; break;
+    case L_CFIRST: b = 32.0 + 128.0; break;
+    case L_CBODY: b = 256.0; break;                                               // 128 B read + 128 B written per pixel
+    case L_CLAST: b = 128.0 + 32.0 + 48.0 * out_b; break;
+    }
+    return Scope(h, st, kRoleFam[cw.role], flops, px * b);
+}
+int epi_of(Role r) { return r == L_RDB5 ? EPI_RDB5 : r == L_RDB5_RRDB ? EPI_RDB5_RRDB : EPI_LRELU; }   // the trunk launchers' epilogues
+
+// one conv launch of the RRDB nets outside the fp8 trunk and the up-convs
+int run_conv(s2sr_handle* h, hipStream_t st, const ConvW& cw, ConvParams p, s2sr_debug_trunk_form* form = nullptr) {   // form: where the RDB convs record their kernel form
+    p.wpack = cw.d_wpack; p.bias = cw.d_bias; p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.seg_lo_mask = cw.seg_lo_mask;
+    p.fold_lo = cw.form == CF_LAST_FOLD ? 1 : 0;
+    p.tail_form = (h->f16_full ? 0 : 8) | (cw.form == CF_HR_SPLIT_NOHI ? 2 : 0);
+    p.trash = h->d_trash;
+    Scope sc = layer_scope(h, st, cw, p);
     if (form) *form = s2sr_debug_trunk_form{};
-    if ((fam == F_RDB14 || fam == F_RDB5) && !up && !lo_out && !cw.f8) {   // the RRDB trunk: conv_trunk.hip
+    if (cw.form == CF_NONE) {   // the RRDB trunk: conv_trunk.hip
         p.f16_form = (h->small8 ? 0 : 2) | (h->f16_full ? 0 : 4);
-        HIPCHK(h, launch_conv_trunk(p, cw.ct, epi, st, 0, form));
+        HIPCHK(h, launch_conv_trunk(p, cw.ct, epi_of(cw.role), st, 0, form));
         return S2SR_OK;
     }
-    HIPCHK(h, launch_conv(p, cw.ct, epi, up, lo_out, st, cw.f8));
+    HIPCHK(h, launch_conv(p, cw.form, st));
     return S2SR_OK;
 }
 
-// conv_up1 / conv_up2 in hp mode: "nearest-2x, then 3x3" as four 2x2-tap convs of the source image, one
+// conv_up1 / conv_up2: "nearest-2x, then 3x3" as four 2x2-tap convs of the source image, one
 // launch per output ROW parity (conv3x3.hip, PH template parameter): 4 MACs per output pixel instead of 9.
-// `p` arrives filled for the upsample-on-load form (src / src_lo / dst / T and their image strides).
+// `p` arrives with the tensors (src / src_lo / dst / T and their image strides) and the mosaic; the geometry is set here:
+// n images of Hs x Ws SOURCE pixels in planes of sHp x sWp, written to planes of oHp x oWp.
 int run_up_subpixel(s2sr_handle* h, hipStream_t st, const ConvW& cw, ConvParams p, int n, int Hs, int Ws, int sHp, int sWp,
                     int oHp, int oWp) {
     p.N = n; p.H = Hs; p.W = Ws; p.sHp = sHp; p.sWp = sWp; p.Hp = oHp; p.Wp = oWp;
-    p.bias = cw.d_bias; p.nstage = cw.f8 ? 8 : 4; p.seg_len = 4; p.seg_lo_mask = cw.f8 ? 0x2 : 0x0; p.fold_lo = 0;
+    p.bias = cw.d_bias; p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.seg_lo_mask = cw.seg_lo_mask; p.fold_lo = 0;
     p.tail_form = h->f16_full ? 0 : 8;
     p.trash = h->d_trash;
-    const double px = (double)n * Hs * Ws;
     for (int k = 0; k < 2; ++k) {
         p.wpack = cw.d_wphase[k];
-        // statistics keep the nominal work of the 3x3 form (2*9*cin*cout per OUTPUT pixel; one row parity = half of them)
-        // bytes per SOURCE pixel and launch: the source block once (fp16 128 B, + 128 B of e4m3 correction planes in the
-        // split-operand form), two output pixels (both column parities of this row parity) of 128 B (+ 128 B of planes) each
-        // (r03 counted the split-operand figure for the plain fp16 form too: 8.2 TB/s "algorithmic" in the fp8 leg)
-        Scope sc(h, st, F_UP, 2.0 * 9.0 * cw.cin * cw.cout * 2.0 * px, px * (cw.f8 ? 768.0 : 384.0));
-        HIPCHK(h, launch_conv_phase(p, k, st, cw.f8));
+        Scope sc = layer_scope(h, st, cw, p);
+        HIPCHK(h, launch_conv_phase(p, k, st, cw.split));
     }
     return S2SR_OK;
 }
@@ -291,12 +268,11 @@ int trunk_tap(s2sr_handle* h, hipStream_t st, int g) {
 int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f32, uint8_t* d_out_u8, const Mosaic& mo) {
     Workspace& w = h->ws;
     const int nc = h->cfg.num_block;
-    if ((int)h->convs.size() != nc + 2) return fail(h, S2SR_E_NOWEIGHTS, "compact weights are not loaded");
+    if (h->convs.empty()) return fail(h, S2SR_E_NOWEIGHTS, "compact weights are not loaded");
     ConvParams b{};
     b.N = n; b.H = H; b.W = W; b.Hp = w.Hp; b.Wp = w.Wp; b.sHp = w.Hp; b.sWp = w.Wp;
     b.trash = h->d_trash; b.in_scale = 1.0f / 255.0f;
     mosaic_at(b, mo, 1);
-    const double px = (double)n * H * W;
     auto tap = [&](int layer, const char* act) -> int {       // s2sr_debug_compact_taps only
         if (!h->ctap) return S2SR_OK;
         s2sr_debug_compact_fields* t = h->ctap->t;
@@ -308,23 +284,23 @@ int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* 
             }
         return S2SR_OK;
     };
-    auto launch = [&](int fam, const ConvW& cw, ConvParams p, int epi, double bytes) -> int {
+    auto launch = [&](const ConvW& cw, ConvParams p) -> int {
         p.wpack = cw.d_wpack; p.bias = cw.d_bias; p.slope = cw.d_slope; p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.seg_lo_mask = 0;
-        Scope sc(h, st, fam, 2.0 * 9.0 * cw.cin * cw.cout * px, bytes);
-        HIPCHK(h, launch_conv(p, cw.ct, epi, false, false, st, false));
+        Scope sc = layer_scope(h, st, cw, p);
+        HIPCHK(h, launch_conv(p, cw.form, st));
         return S2SR_OK;
     };
     int rc, cur = 0;
     {   // first conv 3 -> 64 on the exact 0..255 input, x 1/255 in the epilogue
         ConvParams p = b;
         p.src = w.P0; p.src_img = w.blk1; p.dst = w.D[0]; p.dst_img = 4 * w.blk1;
-        if ((rc = launch(F_CFIRST, h->convs[0], p, EPI_CFIRST, px * (32.0 + 128.0)))) return rc;
+        if ((rc = launch(h->conv(L_CFIRST), p))) return rc;
         if ((rc = tap(0, w.D[0]))) return rc;
     }
     for (int k = 1; k <= nc; ++k) {
         ConvParams p = b;
         p.src = w.D[cur]; p.src_img = 4 * w.blk1; p.dst = w.D[cur ^ 1]; p.dst_img = 4 * w.blk1;
-        if ((rc = launch(F_CBODY, h->convs[k], p, EPI_PRELU, px * 256.0))) return rc;   // 128 B read + 128 B written per pixel
+        if ((rc = launch(h->conv(L_CBODY, k - 1), p))) return rc;
         cur ^= 1;
         if ((rc = tap(k, w.D[cur]))) return rc;
     }
@@ -333,8 +309,7 @@ int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* 
         p.src = w.D[cur]; p.src_img = 4 * w.blk1;
         p.src_lo = w.P0; p.lo_img = w.blk1;               // the base: this LR pixel's own colour (ConvParams::slope's note)
         p.out_f32 = d_out_f32; p.out_u8 = d_out_u8; p.cout = 3;
-        const double ob = px * 48.0 * ((d_out_u8 ? 1.0 : 0.0) + (d_out_f32 ? 4.0 : 0.0));
-        if ((rc = launch(F_CLAST, h->convs[nc + 1], p, EPI_CLAST, px * (128.0 + 32.0) + ob))) return rc;
+        if ((rc = launch(h->conv(L_CLAST), p))) return rc;
     }
     return S2SR_OK;
 }
@@ -354,15 +329,15 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
     b.N = n; b.H = H; b.W = W; b.Hp = w.Hp; b.Wp = w.Wp; b.sHp = w.Hp; b.sWp = w.Wp;
     b.T = w.T; b.R = w.R; b.F = w.F;
     mosaic_at(b, mo, 1);
-    int ci = 0, rc;
+    auto rdb_conv = [&](int g, int k) -> const ConvW& { return h->conv(L_RDB14, 5 * g + (k - 1)); };   // conv k (1..5) of global RDB g
+    int rc;
     const bool fp8 = w.fp8;
     {   // conv_first: 3 -> 64 (input = one 16-channel block)
         ConvParams p = b;
         p.src = w.P0; p.src_img = w.blk1; p.in_scale = in16 ? 1.0f / (float)(in.hi - in.lo) : 1.0f / 255.0f;
         if (fp8) { p.dst = w.Xh[0]; p.dst_img = 4 * w.blk1; }
         else { p.dst = w.D[0]; p.dst_img = 12 * w.blk1; }
-        if ((rc = run_conv(h, st, F_FIRST, in16 ? h->first16 : h->convs[ci], p, EPI_FIRST, false))) return rc;
-        ++ci;
+        if ((rc = run_conv(h, st, in16 ? h->first16 : h->conv(L_FIRST), p))) return rc;
     }
     int cur = 0;
     const char* trunk_hi = nullptr;   // fp16 x of the trunk after the body (conv_body's main operand)
@@ -372,7 +347,6 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
     if (fp8) {
         // the trunk on e4m3 operands (conv_trunk.hip, conv_trunk_f8): D8[cur] planes [x(2) | x1 | x2 | x3 | x4]
         const int xe = h->fp8_x_exp, ge = h->fp8_g_exp;
-        const double px = (double)n * H * W;
         {
             Scope sc(h, st, F_MISC, 0.0, (double)n * w.Hp * w.Wp * (128.0 + 64.0));
             HIPCHK(h, launch_xh_to_fp8(w.Xh[0], 4 * w.blk1, n, w.Hp, w.Wp, xe, w.D8[0], 6 * w.blk1, st));
@@ -389,26 +363,21 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
                 span_begin(h, st, F_RDB14);                      // conv1..4 of this RDB: one sample
                 for (int k = 1; k <= 5; ++k) {
                     if (k == 5) span_end(h, st);
-                    const ConvW& cw = h->convs[ci++];
+                    const ConvW& cw = rdb_conv(3 * blk + r, k);
                     ConvParams p = b;
                     p.src = w.D8[cur]; p.src_img = 6 * w.blk1;
                     p.wpack = cw.d_wpack; p.bias = cw.d_bias; p.wscale = cw.d_wscale;
                     p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.trash = h->d_trash;
                     p.x_exp = xe; p.g_exp = ge; p.xh_img = 4 * w.blk1;
-                    int epi = EPI_LRELU;
-                    double bytes = px * (32.0 * cw.seg_len);                     // algorithmic: every input byte once
                     if (k < 5) {
                         p.dst = w.D8[cur] + (size_t)(2 + (k - 1)) * w.blk1; p.dst_img = 6 * w.blk1;
-                        bytes += px * 32.0;
                     } else {
                         p.dst = w.D8[cur ^ 1]; p.dst_img = 6 * w.blk1;
                         p.xh_in = w.Xh[r]; p.xh_out = w.Xh[(r + 1) % 3];
-                        epi = EPI_RDB5;
-                        bytes += px * (64.0 + 128.0 + 128.0);                     // e4m3 x out, fp16 trunk in + out
-                        if (r == 2) { p.xh_skip = w.Xh[0]; epi = EPI_RDB5_RRDB; bytes += px * 128.0; }
+                        if (cw.role == L_RDB5_RRDB) p.xh_skip = w.Xh[0];
                     }
-                    Scope sc(h, st, k < 5 ? F_RDB14 : F_RDB5, 2.0 * 9.0 * cw.cin * cw.cout * px, bytes);
-                    HIPCHK(h, launch_conv_trunk_f8(p, cw.ct, epi, st, fo ? fo + (k - 1) : nullptr));
+                    Scope sc = layer_scope(h, st, cw, p);
+                    HIPCHK(h, launch_conv_trunk_f8(p, cw.ct, epi_of(cw.role), st, fo ? fo + (k - 1) : nullptr));
                 }
                 if (h->d_calib) {   // s2sr_calibrate_fp8: ranges of this RDB's growth planes and of the trunk it produced
                     HIPCHK(h, launch_absmax_e4m3(w.D8[cur] + 2 * w.blk1, (size_t)4 * w.blk1, ge, h->d_calib + 1, st));
@@ -443,15 +412,16 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
                     ConvParams p = b;
                     p.src = w.D[r]; p.src_img = 12 * w.blk1;
                     p.dst = w.D[r] + (size_t)(4 + 2 * (k - 1)) * w.blk1; p.dst_img = 12 * w.blk1;
-                    if ((rc = run_conv(h, st, F_RDB14, h->convs[ci++], p, EPI_LRELU, false, false, fo ? fo + (k - 1) : nullptr))) { span_end(h, st); return rc; }
+                    if ((rc = run_conv(h, st, rdb_conv(3 * blk + r, k), p, fo ? fo + (k - 1) : nullptr))) { span_end(h, st); return rc; }
                 }
                 span_end(h, st);
                 ConvParams p = b;
                 p.src = w.D[r]; p.src_img = 12 * w.blk1;
                 p.dst = w.D[nx]; p.dst_img = 12 * w.blk1;
                 p.xh_in = w.Tr[r]; p.T = w.Tr[nx]; p.lo_exp = h->lo_exp;
-                if (r == 2) { p.xh_skip = w.D[0]; p.xh_img = 12 * w.blk1; p.lo_skip = w.Tr[0]; }
-                if ((rc = run_conv(h, st, F_RDB5, h->convs[ci++], p, r == 2 ? EPI_RDB5_RRDB : EPI_RDB5, false, false, fo ? fo + 4 : nullptr))) return rc;
+                const ConvW& c5 = rdb_conv(3 * blk + r, 5);
+                if (c5.role == L_RDB5_RRDB) { p.xh_skip = w.D[0]; p.xh_img = 12 * w.blk1; p.lo_skip = w.Tr[0]; }
+                if ((rc = run_conv(h, st, c5, p, fo ? fo + 4 : nullptr))) return rc;
             }
         if (h->ttap && (rc = trunk_tap(h, st, 3 * nb))) return rc;
         trunk_hi = w.D[0]; trunk_hi_img = 12 * w.blk1; trunk_lo = w.Tr[0]; trunk_lo_exp = h->lo_exp;
@@ -466,7 +436,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
             HIPCHK(h, launch_trunk_to_fp8(trunk_hi, trunk_hi_img, trunk_lo, (trunk_lo_exp >= 0 ? 2 : 4) * w.blk1, trunk_lo_exp, n, w.Hp, w.Wp, w.T8, st));
             p.src_lo = w.T8; p.lo_img = 4 * w.blk1; p.T = w.U0lo;
         }
-        if ((rc = run_conv(h, st, F_BODY, h->convs[ci++], p, EPI_BODY, false, hp))) return rc;
+        if ((rc = run_conv(h, st, h->conv(L_BODY), p))) return rc;
     }
     {   // conv_up1 on nearest-2x
         ConvParams p{};
@@ -474,7 +444,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         p.src = w.U0; p.src_img = 4 * w.blk1; p.dst = w.U1; p.dst_img = 4 * w.blk2;
         if (hp) { p.src_lo = w.U0lo; p.lo_img = 4 * w.blk1; p.T = w.U1lo; }
         mosaic_at(p, mo, 1);                                         // sub-pixel form: the epilogue walks SOURCE pixels
-        if ((rc = run_up_subpixel(h, st, h->convs[ci++], p, n, H, W, w.Hp, w.Wp, w.Hp2, w.Wp2))) return rc;
+        if ((rc = run_up_subpixel(h, st, h->conv(L_UP1), p, n, H, W, w.Hp, w.Wp, w.Hp2, w.Wp2))) return rc;
     }
     {   // conv_up2 on nearest-2x
         ConvParams p{};
@@ -482,7 +452,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         p.src = w.U1; p.src_img = 4 * w.blk2; p.dst = w.U2; p.dst_img = 4 * w.blk4;
         if (hp) { p.src_lo = w.U1lo; p.lo_img = 4 * w.blk2; p.T = w.U2lo; }
         mosaic_at(p, mo, 2);
-        if ((rc = run_up_subpixel(h, st, h->convs[ci++], p, n, 2 * H, 2 * W, w.Hp2, w.Wp2, w.Hp4, w.Wp4))) return rc;
+        if ((rc = run_up_subpixel(h, st, h->conv(L_UP2), p, n, 2 * H, 2 * W, w.Hp2, w.Wp2, w.Hp4, w.Wp4))) return rc;
     }
     ConvParams hr{};
     hr.N = n; hr.H = 4 * H; hr.W = 4 * W; hr.Hp = w.Hp4; hr.Wp = w.Wp4; hr.sHp = w.Hp4; hr.sWp = w.Wp4;
@@ -491,13 +461,13 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         ConvParams p = hr;
         p.src = w.U2; p.src_img = 4 * w.blk4; p.dst = w.U3; p.dst_img = 4 * w.blk4;
         if (hp) { p.src_lo = w.U2lo; p.lo_img = 4 * w.blk4; p.T = w.U3lo; }
-        if ((rc = run_conv(h, st, F_HR, h->convs[ci++], p, EPI_LRELU, false, hp))) return rc;
+        if ((rc = run_conv(h, st, h->conv(L_HR), p))) return rc;
     }
     {
         ConvParams p = hr;
         p.src = w.U3; p.src_img = 4 * w.blk4; p.out_f32 = d_out_f32; p.out_u8 = d_out_u8; p.cout = 3;
         if (hp) { p.src_lo = w.U3lo; p.lo_img = 4 * w.blk4; }
-        if ((rc = run_conv(h, st, F_LAST, h->convs[ci++], p, EPI_LAST, false))) return rc;
+        if ((rc = run_conv(h, st, h->conv(L_LAST), p))) return rc;
     }
     return S2SR_OK;
 }
@@ -506,6 +476,28 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
 
 // ---- what the other engine files use too (declared in engine_internal.h)
 namespace s2sr::engine {
+
+// RRDBNet(num_block) at scale 4 or 2 and SRVGGNetCompact(num_feat 64, num_conv = num_block, upscale 4), as their state dicts
+// list them (s2sr/weights.py).  No validity rule lives here: s2sr_create and s2sr_expected_blob_floats_cfg say what is supported.
+std::vector<Layer> layer_table(int arch, int num_block, int scale) {
+    std::vector<Layer> v;
+    if (arch == S2SR_ARCH_COMPACT) {
+        v.push_back({L_CFIRST, 3, 64, 64});
+        for (int k = 0; k < num_block; ++k) v.push_back({L_CBODY, 64, 64, 64});
+        v.push_back({L_CLAST, 64, 48, 0});       // 3 colours x 4 x 4 sub-pixels
+        return v;
+    }
+    v.push_back({L_FIRST, scale == 2 ? 12 : 3, 64, 0});   // scale 2 reads the 12 channels of pixel_unshuffle(x, 2)
+    for (int b = 0; b < num_block; ++b)
+        for (int r = 0; r < 3; ++r) {
+            for (int k = 1; k <= 4; ++k) v.push_back({L_RDB14, 64 + (k - 1) * 32, 32, 0});
+            v.push_back({r == 2 ? L_RDB5_RRDB : L_RDB5, 64 + 4 * 32, 64, 0});
+        }
+    for (Role r : {L_BODY, L_UP1, L_UP2, L_HR}) v.push_back({r, 64, 64, 0});
+    v.push_back({L_LAST, 64, 3, 0});
+    return v;
+}
+size_t table_floats(const std::vector<Layer>& table) { size_t n = 0; for (const Layer& l : table) n += l.floats(); return n; }
 
 int fail(s2sr_handle* h, int code, const std::string& msg) {
     if (h) h->err = msg;
@@ -874,19 +866,18 @@ int s2sr_device_count(void) {
 
 size_t s2sr_expected_blob_floats_scale(int32_t num_block, int32_t scale) {
     if (scale != 2 && scale != 4) return 0;
-    size_t n = 0;
-    for (const ConvSpec& s : conv_specs(num_block, scale)) n += (size_t)s.cin * s.cout * 9 + s.cout;
-    return n;
+    return table_floats(layer_table(S2SR_ARCH_RRDB, num_block, scale));
 }
 
 size_t s2sr_expected_blob_floats(int32_t num_block) { return s2sr_expected_blob_floats_scale(num_block, 4); }
 
 size_t s2sr_expected_blob_floats_cfg(const s2sr_config* cfg) {
     if (!cfg) return 0;
-    if (cfg->arch == S2SR_ARCH_COMPACT)
-        return ((cfg->num_block == 16 || cfg->num_block == 32) && cfg->num_feat == 64 && cfg->scale == 4) ? compact_blob_floats(cfg->num_block) : 0;
-    if (cfg->arch != S2SR_ARCH_RRDB || cfg->num_block <= 0 || cfg->num_feat != 64 || cfg->num_grow != 32) return 0;
-    return s2sr_expected_blob_floats_scale(cfg->num_block, cfg->scale);
+    if (cfg->arch == S2SR_ARCH_COMPACT) {
+        if ((cfg->num_block != 16 && cfg->num_block != 32) || cfg->num_feat != 64 || cfg->scale != 4) return 0;
+    } else if (cfg->arch != S2SR_ARCH_RRDB || cfg->num_block <= 0 || cfg->num_feat != 64 || cfg->num_grow != 32 || (cfg->scale != 2 && cfg->scale != 4))
+        return 0;
+    return table_floats(layer_table(cfg->arch, cfg->num_block, cfg->scale));
 }
 
 const char* s2sr_last_error(const s2sr_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
@@ -980,76 +971,19 @@ void s2sr_destroy(s2sr_handle* h) {
     delete h;
 }
 
-// SRVGGNetCompact: 1.2 M parameters -- the blob comes to the host whole and every conv goes through pack_conv_weights (plain
-// fp16, one segment).  The last conv's 48 output channels are placed in the rows the pixel-shuffle epilogue wants
-// (compact_last_row_channel); bias and slopes stay fp32.
-static int load_weights_compact(s2sr_handle* h, const float* d_blob, size_t n_floats, hipStream_t st) {
-    const int nc = h->cfg.num_block;
-    const size_t want = compact_blob_floats(nc);
-    if (n_floats != want) {
-        char b[160];
-        snprintf(b, sizeof b, "weight blob has %zu floats, a compact net of %d convs needs %zu", n_floats, nc, want);
-        return fail(h, S2SR_E_BADBLOB, b);
-    }
-    HIPCHK(h, dev_sync());
-    drop_graphs(h);
-    free_weights(h);
-    h->has_weights = false;
-    std::vector<float> blob(n_floats);
-    HIPCHK(h, hipMemcpyAsync(blob.data(), d_blob, n_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    const int nconv = nc + 2;
-    std::vector<float> pb((size_t)nconv * 128, 0.f);     // per conv: [64 bias | 64 slopes]
-    HIPCHK(h, dev_malloc(&h->pool_b, pb.size() * sizeof(float)));
-    std::vector<char> tmp;
-    std::vector<float> wperm((size_t)64 * 64 * 9);
-    size_t off = 0;
-    for (int idx = 0; idx < nconv; ++idx) {
-        const int cin = idx == 0 ? 3 : 64, cout = idx == nconv - 1 ? 48 : 64;
-        const float* wsrc = blob.data() + off; off += (size_t)cin * cout * 9;
-        const float* bsrc = blob.data() + off; off += cout;
-        float* bias = pb.data() + (size_t)idx * 128;
-        ConvW cw;
-        cw.cin = cin; cw.cout = cout; cw.ct = 2; cw.seg_len = (cin + 15) / 16; cw.nstage = cw.seg_len; cw.seg_lo_mask = 0;
-        const float* pw = wsrc;
-        if (idx == nconv - 1) {     // rows in the epilogue's order, idle rows zero
-            std::fill(wperm.begin(), wperm.end(), 0.f);
-            for (int row = 0; row < 64; ++row) {
-                const int ch = compact_last_row_channel(row);
-                if (ch < 0) continue;
-                memcpy(&wperm[(size_t)row * 64 * 9], wsrc + (size_t)ch * 64 * 9, sizeof(float) * 64 * 9);
-                bias[row] = bsrc[ch];
-            }
-            pw = wperm.data();
-        } else {
-            memcpy(bias, bsrc, sizeof(float) * 64);
-            memcpy(bias + 64, blob.data() + off, sizeof(float) * 64);   // the PReLU behind this conv
-            off += 64;
-        }
-        const size_t wb = conv_wpack_bytes(cin, 64);
-        tmp.resize(wb);
-        pack_conv_weights(pw, cin, 64, 1, tmp.data(), false);
-        HIPCHK(h, dev_malloc(&cw.d_wpack, wb));
-        HIPCHK(h, copy_blocking(h, cw.d_wpack, tmp.data(), wb, hipMemcpyHostToDevice));
-        cw.d_bias = h->pool_b + (size_t)idx * 128;
-        cw.d_slope = h->pool_b + (size_t)idx * 128 + 64;
-        h->convs.push_back(cw);
-    }
-    HIPCHK(h, copy_blocking(h, h->pool_b, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
-    h->has_weights = true;
-    return S2SR_OK;
-}
-
-// Weights in, by either door.  `d_blob` is the fp32 blob ON THE DEVICE (the host entry uploads it first): the 345 RDB convs
-// are repacked by device kernels straight from it (pack.hip), every bias is gathered on the device; only the six head/tail
-// convs (0.9 MB of the 67 MB) come back to the host, because their split-operand / sub-pixel packers are host code.
+// Weights in, by either door.  `d_blob` is the fp32 blob ON THE DEVICE (the host entry uploads it first).  One walk over the
+// layer table, one case per role: the 345 RDB convs are repacked by device kernels straight from the blob (pack.hip) and the RRDB
+// nets' biases are gathered on the device; only the six head/tail convs (0.9 MB of the 67 MB) come back to the host, because their
+// split-operand / sub-pixel packers are host code.  SRVGGNetCompact (1.2 M parameters) comes to the host layer by layer; its bias
+// and slopes stay fp32.  Each case also decides the conv's kernel form (ConvW::form).
 static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_floats, hipStream_t st) {
-    if (h->compact()) return load_weights_compact(h, d_blob, n_floats, st);
-    const std::vector<ConvSpec> specs = conv_specs(h->cfg.num_block, h->cfg.scale);
-    const size_t want = s2sr_expected_blob_floats_scale(h->cfg.num_block, h->cfg.scale);
+    const std::vector<Layer> table = layer_table(h->cfg.arch, h->cfg.num_block, h->cfg.scale);
+    const size_t want = table_floats(table), nconv = table.size();
+    const bool compact = h->compact();
     if (n_floats != want) {
         char b[160];
-        snprintf(b, sizeof b, "weight blob has %zu floats, a %d-block scale-%d net needs %zu", n_floats, h->cfg.num_block, h->cfg.scale, want);
+        if (compact) snprintf(b, sizeof b, "weight blob has %zu floats, a compact net of %d convs needs %zu", n_floats, h->cfg.num_block, want);
+        else snprintf(b, sizeof b, "weight blob has %zu floats, a %d-block scale-%d net needs %zu", n_floats, h->cfg.num_block, h->cfg.scale, want);
         return fail(h, S2SR_E_BADBLOB, b);
     }
     HIPCHK(h, dev_sync());
@@ -1057,27 +991,29 @@ static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_flo
     free_weights(h);
     h->has_weights = false;
     h->fp8_x_exp = h->fp8_x_exp0; h->fp8_g_exp = h->fp8_g_exp0;     // exponents calibrated for the previous weights do not carry over
-    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;
-    const bool hp = h->cfg.precision == S2SR_PREC_F16_HP || (fp8 && h->fp8_hp_tail);
-    const size_t nconv = specs.size();
-    // ---- plan: blob offsets, pooled sizes
+    const bool fp8 = h->cfg.precision == S2SR_PREC_FP8, hp = h->hp();
+    // ---- plan: blob offsets, pooled sizes, where the schedules find each layer
     std::vector<uint64_t> woff(nconv), boff(nconv), poff(nconv, 0);
     std::vector<int32_t> couts(nconv);
     size_t off = 0, pool_bytes = 0;
+    std::fill(h->at, h->at + kRoles, -1);
     for (size_t i = 0; i < nconv; ++i) {
-        woff[i] = off; off += (size_t)specs[i].cin * specs[i].cout * 9;
-        boff[i] = off; off += specs[i].cout;
-        couts[i] = specs[i].cout;
-        const bool trunk = i >= 1 && i + 5 < nconv;
-        if (trunk) {
+        const Layer& l = table[i];
+        woff[i] = off; boff[i] = off + (size_t)l.cin * l.cout * 9; off += l.floats();
+        couts[i] = l.cout;
+        if (h->at[l.role] < 0) h->at[l.role] = (int)i;
+        if (is_rdb(l.role)) {
             poff[i] = pool_bytes;
-            pool_bytes += align256(fp8 ? conv_wpack_bytes_f8(specs[i].cin, specs[i].cout) : conv_wpack_bytes(specs[i].cin, specs[i].cout));
+            pool_bytes += align256(fp8 ? conv_wpack_bytes_f8(l.cin, l.cout) : conv_wpack_bytes(l.cin, l.cout));
         }
     }
-    HIPCHK(h, dev_malloc(&h->pool_w, pool_bytes ? pool_bytes : 256));
-    HIPCHK(h, dev_malloc(&h->pool_b, nconv * 64 * sizeof(float)));
+    // pool_b, per conv: [64 bias], compact: [64 bias | 64 slopes], built on the host (the last conv's rows are permuted)
+    const size_t brow = compact ? 128 : 64;
+    std::vector<float> pb(compact ? nconv * brow : 0, 0.f);
+    if (pool_bytes) HIPCHK(h, dev_malloc(&h->pool_w, pool_bytes));
+    HIPCHK(h, dev_malloc(&h->pool_b, nconv * brow * sizeof(float)));
     if (fp8) HIPCHK(h, dev_malloc(&h->pool_s, nconv * 64 * sizeof(int32_t)));
-    {   // biases: one gather kernel
+    if (!compact) {   // biases: one gather kernel
         uint64_t* d_off = nullptr;
         int32_t* d_cout = nullptr;
         HIPCHK(h, dev_malloc(&d_off, nconv * 8));
@@ -1089,82 +1025,115 @@ static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_flo
         dev_free(d_off); dev_free(d_cout);
     }
     std::vector<char> tmp;
-    std::vector<float> hw;
+    std::vector<float> hl, w2;
+    auto upload = [&](void** d) -> int {   // the packed weights in tmp to a device buffer of their own
+        HIPCHK(h, dev_malloc(d, tmp.size()));
+        HIPCHK(h, copy_blocking(h, *d, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
+        return S2SR_OK;
+    };
+    int rc;
     for (size_t idx = 0; idx < nconv; ++idx) {
-        const ConvSpec& s = specs[idx];
+        const Layer& l = table[idx];
         ConvW cw;
-        const int nb = (s.cin + 15) / 16;
-        // split-operand convs: the six outside the RRDB trunk (conv_first, conv_body, up1, up2, hr, last)
-        const bool split = hp && (idx == 0 || idx + 5 >= nconv);
-        // conv_first's inputs are exact integers: no x_lo.  conv_last has 29 idle output channels: w_lo
-        // rides in couts 8..10 of both segments (x_hi, x_lo), one pass over x_hi less
-        // All the others (cin 64): x_hi*w_hi on the fp16 MFMA, x_lo*w_hi + x_hi*w_lo as e4m3 planes on the
-        // block-scaled fp8 MFMA (twice the rate, half the bytes; 2^-15-relative error on 2^-11-sized terms).
-        const bool f8 = split && idx != 0 && s.cin == 64;
-        // conv_last (3 couts of 32): w_lo rides in the idle couts 8..10 of the fp16 stages, so only the x_lo planes come in
-        // as e4m3 -- 6 stages instead of 8, 192 instead of 256 B per pixel read (S2SR_LAST_FOLD=0: the 8-stage form)
-        const bool last_fold = f8 && idx + 1 == nconv && s.cout <= 8 && h->last_fold;
-        const bool fold = (split && !f8 && idx + 1 == nconv && s.cout <= 8) || last_fold;
-        const int nseg = !split ? 1 : ((idx == 0 || fold || f8) ? 2 : 3);
-        cw.cin = s.cin; cw.cout = s.cout; cw.ct = (s.cout + 31) / 32;
-        cw.seg_len = nb; cw.nstage = nseg * nb; cw.seg_lo_mask = (nseg == 3 || fold || f8) ? 0x2 : 0x0;
-        if (last_fold) cw.nstage = nb + 2;
-        cw.f8 = f8;
-        cw.fold = fold;
-        cw.d_bias = h->pool_b + idx * 64;
-        const bool trunk = idx >= 1 && idx + 5 < nconv;     // the 345 RDB convs
-        if (trunk) {
+        cw.role = l.role; cw.cin = l.cin; cw.cout = l.cout; cw.ct = (l.cout + 31) / 32;
+        cw.seg_len = (l.cin + 15) / 16; cw.nstage = cw.seg_len; cw.seg_lo_mask = 0;   // plain fp16: one segment
+        cw.d_bias = h->pool_b + idx * brow;
+        if (!is_rdb(l.role)) {   // a host-packed conv: its layer (weights, bias, slopes) comes to the host
+            hl.resize(l.floats());
+            HIPCHK(h, hipMemcpyAsync(hl.data(), d_blob + woff[idx], hl.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+            HIPCHK(h, hipStreamSynchronize(st));
+        }
+        switch (l.role) {
+        case L_RDB14: case L_RDB5: case L_RDB5_RRDB:   // the trunk: packed on the device, launched by conv_trunk.hip
             cw.pooled = true;
             cw.d_wpack = h->pool_w + poff[idx];
             if (fp8) {
-                cw.f8trunk = true;
-                cw.seg_len = (s.cin + 31) / 32;
+                cw.seg_len = (l.cin + 31) / 32;
                 cw.nstage = (cw.seg_len + 1) & ~1;
-                cw.seg_lo_mask = 0;
                 cw.d_wscale = h->pool_s + idx * 64;
-                HIPCHK(h, launch_pack_trunk_f8(d_blob + woff[idx], s.cin, s.cout, cw.d_wpack, cw.d_wscale, st));
+                HIPCHK(h, launch_pack_trunk_f8(d_blob + woff[idx], l.cin, l.cout, cw.d_wpack, cw.d_wscale, st));
             } else {
-                HIPCHK(h, launch_pack_trunk_f16(d_blob + woff[idx], s.cin, s.cout, cw.d_wpack, st));
+                HIPCHK(h, launch_pack_trunk_f16(d_blob + woff[idx], l.cin, l.cout, cw.d_wpack, st));
             }
-        } else {
-            // head / tail conv: its weights come to the host for the split-operand / sub-pixel packers
-            hw.resize((size_t)s.cin * s.cout * 9);
-            HIPCHK(h, hipMemcpyAsync(hw.data(), d_blob + woff[idx], hw.size() * sizeof(float), hipMemcpyDeviceToHost, st));
-            HIPCHK(h, hipStreamSynchronize(st));
-            const float* pw = hw.data();
-            const size_t wb = last_fold ? (size_t)cw.nstage * 9 * cw.ct * 1024 : conv_wpack_bytes_seg(s.cin, s.cout, nseg);
-            tmp.resize(wb);
-            if (f8) pack_conv_weights_f8hp(pw, s.cin, s.cout, tmp.data(), last_fold);
-            else pack_conv_weights(pw, s.cin, s.cout, nseg, tmp.data(), fold);
-            if (s.cin == 64 && s.cout == 64 && (idx + 4 == nconv || idx + 3 == nconv)) {   // conv_up1, conv_up2: sub-pixel form
-                const size_t pb = conv_wpack_bytes_phase(s.cin, s.cout);
-                std::vector<char> ph(pb);
-                for (int k = 0; k < 2; ++k) {
-                    pack_conv_weights_phase_f8hp(pw, s.cin, s.cout, k, ph.data());
-                    HIPCHK(h, dev_malloc(&cw.d_wphase[k], pb));
-                    HIPCHK(h, copy_blocking(h, cw.d_wphase[k], ph.data(), pb, hipMemcpyHostToDevice));
-                }
-            }
-            HIPCHK(h, dev_malloc(&cw.d_wpack, wb));
-            HIPCHK(h, copy_blocking(h, cw.d_wpack, tmp.data(), wb, hipMemcpyHostToDevice));
-            if (idx == 0 && s.cin == 3) {
+            break;
+        case L_FIRST: {   // its inputs are exact integers: no x_lo; hp: two fp16 segments [w_hi][w_lo] on the same x
+            const int nseg = hp ? 2 : 1;
+            cw.form = CF_FIRST; cw.nstage = nseg * cw.seg_len;
+            tmp.resize(conv_wpack_bytes_seg(l.cin, l.cout, nseg));
+            pack_conv_weights(hl.data(), l.cin, l.cout, nseg, tmp.data());
+            if ((rc = upload(&cw.d_wpack))) return rc;
+            if (l.cin == 3) {
                 // the 16-bit door's conv_first: input channels c and c + 3 (d & 255 and d & 0xff00, pack.hip) both meet w[:, c] --
-                // same packer, same segments (hp: w_hi / w_lo), still one 16-channel stage per segment, the same bias
-                std::vector<float> w6((size_t)s.cout * 6 * 9);
-                for (int co = 0; co < s.cout; ++co)
-                    for (int c = 0; c < 6; ++c) memcpy(&w6[((size_t)co * 6 + c) * 9], pw + ((size_t)co * 3 + c % 3) * 9, 9 * sizeof(float));
+                // same packer, same segments, still one 16-channel stage per segment, the same bias
+                w2.resize((size_t)l.cout * 6 * 9);
+                for (int co = 0; co < l.cout; ++co)
+                    for (int c = 0; c < 6; ++c) memcpy(&w2[((size_t)co * 6 + c) * 9], &hl[((size_t)co * 3 + c % 3) * 9], 9 * sizeof(float));
                 ConvW c6 = cw;
                 c6.cin = 6; c6.d_wpack = nullptr;
-                const size_t wb6 = conv_wpack_bytes_seg(6, s.cout, nseg);
-                tmp.resize(wb6);
-                pack_conv_weights(w6.data(), 6, s.cout, nseg, tmp.data(), fold);
-                HIPCHK(h, dev_malloc(&c6.d_wpack, wb6));
-                HIPCHK(h, copy_blocking(h, c6.d_wpack, tmp.data(), wb6, hipMemcpyHostToDevice));
+                tmp.resize(conv_wpack_bytes_seg(6, l.cout, nseg));
+                pack_conv_weights(w2.data(), 6, l.cout, nseg, tmp.data());
+                if ((rc = upload(&c6.d_wpack))) return rc;
                 h->first16 = c6;
             }
+            break;
+        }
+        case L_BODY: case L_HR: case L_LAST: {
+            // hp, cin 64: x_hi*w_hi on the fp16 MFMA, x_lo*w_hi + x_hi*w_lo as e4m3 planes on the block-scaled fp8 MFMA (twice
+            // the rate, half the bytes; 2^-15-relative error on 2^-11-sized terms); body and hr write such planes for their consumer.
+            // conv_last has 3 couts of 32, so w_lo rides in the idle couts 8..10 of the fp16 stages and only the x_lo planes come in as
+            // e4m3 -- 6 stages instead of 8, 192 instead of 256 B per pixel read, and conv_hr need not write the x_hi planes
+            // (S2SR_LAST_FOLD=0: the 8-stage form)
+            const bool fold = hp && h->last_fold;
+            cw.split = hp;
+            if (l.role == L_BODY) cw.form = hp ? CF_BODY_SPLIT : CF_BODY;
+            else if (l.role == L_HR) cw.form = !hp ? CF_HR : fold ? CF_HR_SPLIT_NOHI : CF_HR_SPLIT;
+            else cw.form = !hp ? CF_LAST : fold ? CF_LAST_FOLD : CF_LAST_SPLIT8;
+            if (hp) {
+                cw.nstage = cw.form == CF_LAST_FOLD ? cw.seg_len + 2 : 2 * cw.seg_len; cw.seg_lo_mask = 0x2;
+                tmp.resize((size_t)cw.nstage * 9 * cw.ct * 1024);
+                pack_conv_weights_f8hp(hl.data(), l.cin, l.cout, tmp.data(), cw.form == CF_LAST_FOLD);
+            } else {
+                tmp.resize(conv_wpack_bytes(l.cin, l.cout));
+                pack_conv_weights(hl.data(), l.cin, l.cout, 1, tmp.data());
+            }
+            if ((rc = upload(&cw.d_wpack))) return rc;
+            break;
+        }
+        case L_UP1: case L_UP2:   // sub-pixel form in every precision: four fp16 stages of 2x2 taps, hp: + their four e4m3 planes
+            cw.split = hp;
+            cw.seg_len = 4; cw.nstage = hp ? 8 : 4; cw.seg_lo_mask = hp ? 0x2 : 0x0;
+            tmp.resize(conv_wpack_bytes_phase(l.cin, l.cout));
+            for (int k = 0; k < 2; ++k) {
+                pack_conv_weights_phase_f8hp(hl.data(), l.cin, l.cout, k, tmp.data());
+                if ((rc = upload(&cw.d_wphase[k]))) return rc;
+            }
+            break;
+        case L_CFIRST: case L_CBODY: case L_CLAST: {   // plain fp16, 64 rows; bias and the PReLU slopes behind it to pool_b
+            const float *wsrc = hl.data(), *bsrc = wsrc + (size_t)l.cin * l.cout * 9;
+            float* bias = pb.data() + idx * brow;
+            cw.form = l.role == L_CFIRST ? CF_CFIRST : l.role == L_CBODY ? CF_PRELU : CF_CLAST;
+            cw.d_slope = cw.d_bias + 64;
+            if (l.role == L_CLAST) {   // its 48 output channels in the rows the pixel-shuffle epilogue wants, idle rows zero
+                w2.assign((size_t)64 * l.cin * 9, 0.f);
+                for (int row = 0; row < 64; ++row) {
+                    const int ch = compact_last_row_channel(row);
+                    if (ch < 0) continue;
+                    memcpy(&w2[(size_t)row * l.cin * 9], wsrc + (size_t)ch * l.cin * 9, sizeof(float) * l.cin * 9);
+                    bias[row] = bsrc[ch];
+                }
+                wsrc = w2.data();
+            } else {
+                memcpy(bias, bsrc, sizeof(float) * (64 + l.extra));   // the slopes follow the bias in the blob as in the pool
+            }
+            tmp.resize(conv_wpack_bytes(l.cin, 64));
+            pack_conv_weights(wsrc, l.cin, 64, 1, tmp.data());
+            if ((rc = upload(&cw.d_wpack))) return rc;
+            break;
+        }
         }
         h->convs.push_back(cw);
     }
+    if (compact) HIPCHK(h, copy_blocking(h, h->pool_b, pb.data(), pb.size() * sizeof(float), hipMemcpyHostToDevice));
     HIPCHK(h, hipStreamSynchronize(st));
     h->has_weights = true;
     return S2SR_OK;
@@ -1174,7 +1143,7 @@ int s2sr_load_weights(s2sr_handle* h, const float* blob, size_t n_floats) {
     if (!h || !blob) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (n_floats != handle_blob_floats(h)) return load_weights_locked(h, nullptr, n_floats, h->stream);   // -> BADBLOB text
+    if (n_floats != s2sr_expected_blob_floats_cfg(&h->cfg)) return load_weights_locked(h, nullptr, n_floats, h->stream);   // -> BADBLOB text
     float* d_blob = nullptr;
     HIPCHK(h, dev_malloc(&d_blob, n_floats * sizeof(float)));
     hipError_t e = hipMemcpyAsync(d_blob, blob, n_floats * sizeof(float), hipMemcpyHostToDevice, h->stream);

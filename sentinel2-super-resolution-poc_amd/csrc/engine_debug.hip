@@ -159,7 +159,8 @@ int s2sr_debug_conv(s2sr_handle* h, const float* x, int32_t N, int32_t Cin, int3
     p.src = d_plane; p.src_img = (uint64_t)NB * sblk; p.nstage = NB;
     p.wpack = d_w; p.bias = d_b; p.N = N; p.H = OHh; p.W = OWw; p.Hp = Hp; p.Wp = Wp; p.sHp = sHp; p.sWp = sWp;
     p.out_f32 = d_y; p.cout = Cout; p.act = act; p.trash = h->d_trash;
-    HIPCHK(h, launch_conv(p, (Cout + 31) / 32, EPI_DEBUG, upsample != 0, false, st));
+    const ConvForm form = Cout <= 32 ? (upsample ? CF_DEBUG1_UP : CF_DEBUG1) : (upsample ? CF_DEBUG2_UP : CF_DEBUG2);
+    HIPCHK(h, launch_conv(p, form, st));
     HIPCHK(h, hipMemcpyAsync(y, d_y, yb, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     dev_free(d_plane); dev_free(d_x); dev_free(d_y); dev_free(d_w); dev_free(d_b);
@@ -517,7 +518,7 @@ int s2sr_debug_forward_taps(s2sr_handle* h, const uint8_t* tiles, const float* x
     if (rc) return rc;
     const int NI = tp.NI;
     const bool fp8 = h->cfg.precision == S2SR_PREC_FP8;
-    const bool hp = h->cfg.precision == S2SR_PREC_F16_HP || (fp8 && h->fp8_hp_tail);
+    const bool hp = h->hp();
     t->n = NI;
     for (int k = 0; k < 3; ++k) {
         const int s = k == 0 ? 1 : 2 * k;

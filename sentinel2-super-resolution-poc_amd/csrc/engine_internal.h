@@ -12,17 +12,38 @@
 
 namespace s2sr::engine {
 
+// The net, layer by layer, in the order of the weight blob: the one place a layer or a model is declared.  layer_table() builds
+// it from the config; the blob sizes of the C ABI, the loader (load_weights_locked: one case per role) and the schedules
+// (run_net, run_net_compact, through s2sr_handle::conv) all read it.
+enum Role {
+    L_FIRST,        // RRDB nets: conv_first (scale 2: on the 12 channels of pixel_unshuffle(x, 2))
+    L_RDB14,        // conv1..4 of a ResidualDenseBlock
+    L_RDB5,         // its conv5 ...
+    L_RDB5_RRDB,    // ... and the conv5 that closes an RRDB (third RDB: the RRDB skip in its epilogue)
+    L_BODY, L_UP1, L_UP2, L_HR, L_LAST,
+    L_CFIRST, L_CBODY, L_CLAST,   // SRVGGNetCompact: first conv, PReLU body convs, the last conv with the pixel-shuffle tail
+};
+constexpr int kRoles = L_CLAST + 1;
+inline bool is_rdb(Role r) { return r == L_RDB14 || r == L_RDB5 || r == L_RDB5_RRDB; }
+struct Layer {
+    Role role;
+    int cin, cout, extra;      // extra: floats behind the bias (the 64 PReLU slopes of a compact conv, 0 otherwise)
+    size_t floats() const { return (size_t)cin * cout * 9 + cout + extra; }
+};
+std::vector<Layer> layer_table(int arch, int num_block, int scale);   // arch: S2SR_ARCH_*; compact: num_block carries num_conv
+size_t table_floats(const std::vector<Layer>& table);
+
 struct ConvW {
+    Role role = L_FIRST;
+    ConvForm form = CF_NONE;            // its launch_conv form; CF_NONE: the RDB convs (conv_trunk.hip) and the up-convs (launch_conv_phase)
     int cin = 0, cout = 0, nstage = 0, ct = 0;
     int seg_len = 0, seg_lo_mask = 0;   // split-operand convs (precision S2SR_PREC_F16_HP), see ConvParams
-    bool fold = false;                  // conv_last in hp mode: w_lo folded into idle couts (pack_conv_weights)
-    bool f8 = false;                    // hp mode, cin 64: fp16 main term + e4m3 correction planes (pack_conv_weights_f8hp)
-    void* d_wphase[2] = {nullptr, nullptr};   // hp up-convs: the 2x2 sub-pixel kernels per output row parity (pack_conv_weights_phase_f8hp)
+    bool split = false;                 // hp mode, cin 64: fp16 main term + e4m3 correction planes in (pack_conv_weights_f8hp, ..._phase_f8hp)
+    void* d_wphase[2] = {nullptr, nullptr};   // up-convs: the 2x2 sub-pixel kernels per output row parity (pack_conv_weights_phase_f8hp)
     void* d_wpack = nullptr;
     float* d_bias = nullptr;
     // fp8 trunk mode (S2SR_PREC_FP8), the 345 RDB convs: e4m3 weight planes (pack_conv_weights_f8; nstage = planes padded
     // to even, seg_len = real planes) + per-output-channel E8M0 scale bytes
-    bool f8trunk = false;
     int32_t* d_wscale = nullptr;
     bool pooled = false;                // d_wpack / d_wscale point into the handle's pools
     float* d_slope = nullptr;           // SRVGGNetCompact: the 64 PReLU slopes behind this conv (in pool_b, next to the bias)
@@ -33,6 +54,8 @@ enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST,
 inline constexpr const char* kFamName[F_COUNT] = {"pack_u8",   "conv_first", "rdb_conv1-4", "rdb_conv5",   "conv_body",
                                  "conv_up",   "conv_hr",    "conv_last",   "postprocess", "misc",
                                  "compact_first", "compact_body", "compact_last"};
+
+inline constexpr int kRoleFam[kRoles] = {F_FIRST, F_RDB14, F_RDB5, F_RDB5, F_BODY, F_UP, F_UP, F_HR, F_LAST, F_CFIRST, F_CBODY, F_CLAST};   // by Role
 
 struct Workspace {
     int G = 0, H = 0, W = 0;   // capacity (images) and logical LR dims
@@ -142,9 +165,13 @@ struct s2sr_handle {
     hipStream_t stream = nullptr;
     std::mutex mu;
     std::string err;
-    std::vector<s2sr::engine::ConvW> convs;
+    // split-operand ("hp") head / tail convs: S2SR_PREC_F16_HP, or the fp8 trunk with S2SR_FP8_TAIL=hp
+    bool hp() const { return cfg.precision == S2SR_PREC_F16_HP || (cfg.precision == S2SR_PREC_FP8 && fp8_hp_tail); }
+    std::vector<s2sr::engine::ConvW> convs;      // one per entry of layer_table(cfg), in its order
+    int at[s2sr::engine::kRoles] = {};             // where each role's first conv sits in convs (the loader fills it)
+    const s2sr::engine::ConvW& conv(s2sr::engine::Role r, int k = 0) const { return convs[at[r] + k]; }   // the k-th conv from there on
     // conv_first of the 16-bit door (x4 RRDB nets): the same conv on a cin-6 weight set, w6[:, c] = w6[:, c + 3] = w[:, c], for
-    // the (d & 255, d & 0xff00) channel pairs pack_u16 writes; built next to convs[0], sharing its bias (d_wpack null: not built)
+    // the (d & 255, d & 0xff00) channel pairs pack_u16 writes; built next to conv_first, sharing its bias (d_wpack null: not built)
     s2sr::engine::ConvW first16;
     // the packed weights of the 345 RDB convs, their fp8 scales and every conv's bias live in three pooled allocations
     // (ConvW pointers point into them); only the six head/tail convs own separate buffers (pooled == false)

@@ -80,7 +80,7 @@ struct ConvParams {
     // Split-operand ("hp") convs run the K loop over segments of seg_len stages that all accumulate
     // into the same fp32 accumulator.  Bit s of seg_lo_mask says segment s reads the src_lo tensor.
     //   conv_first: (x, w_hi) (x, w_lo), both fp16 (x is an exact integer);
-    //   cin-64 convs (f8_in launch): 4 fp16 stages (x_hi, w_hi), then the 4 e4m3 planes of src_lo
+    //   cin-64 convs (the split forms of ConvForm): 4 fp16 stages (x_hi, w_hi), then the 4 e4m3 planes of src_lo
     //   [x_lo*2^11 p0, p1, x_hi p0, p1] against [w_hi, w_hi, w_lo*2^11, w_lo*2^11] on the fp8 MFMA.
     // Plain convs: seg_len == nstage, mask 0.
     const char* src_lo;      // second operand tensor (same padded geometry as src: fp16 lo blocks or e4m3 planes), or null
@@ -205,8 +205,20 @@ static inline int persistent_grid(int ncu, int occ, int ntiles) {
     return ntiles < grid ? (ntiles + 7) & ~7 : grid;
 }
 
-// conv kernel (conv3x3.hip).  ct = ceil(Cout/32) in {1,2}.
-hipError_t launch_conv(const ConvParams& p, int ct, int epi, bool upsample, bool lo_out, hipStream_t st, bool f8_in = false);
+// conv kernel (conv3x3.hip): one enumerator per family of instantiations.  The loader decides a conv's form once (engine.hip,
+// ConvW::form); the launcher only adds the whole-patch (FULL) variant, which depends on the launch's geometry, and refuses
+// parameters that do not fit the form.
+enum ConvForm : int {
+    CF_NONE = 0,                                    // not a launch_conv conv
+    CF_FIRST, CF_BODY, CF_HR, CF_LAST,              // 8 waves, 16x32 patches, fp16 (conv_first in hp mode too: [w_hi][w_lo] on exact integers)
+    // split-operand (hp) convs, cin 64: fp16 main term + e4m3 correction planes in; body / hr write such planes as well
+    CF_BODY_SPLIT, CF_HR_SPLIT,
+    CF_HR_SPLIT_NOHI,                               // conv_hr in front of a folded conv_last: no e4m3(x_hi) planes out (tail_form bit 1)
+    CF_LAST_SPLIT8, CF_LAST_FOLD,                   // conv_last on all four planes (8 stages) / w_lo folded into idle couts (6 stages)
+    CF_PRELU, CF_CFIRST, CF_CLAST,                  // SRVGGNetCompact: PReLU / pixel-shuffle epilogues
+    CF_DEBUG1, CF_DEBUG1_UP, CF_DEBUG2, CF_DEBUG2_UP,   // s2sr_debug_conv: 1 or 2 cout tiles, plain or nearest-2x on load
+};
+hipError_t launch_conv(const ConvParams& p, ConvForm form, hipStream_t st);
 // the RRDB trunk convs as one-wave-per-SIMD workgroups (conv_trunk.hip): ct 1 + EPI_LRELU (conv1..4), ct 2 + EPI_RDB5 /
 // EPI_RDB5_RRDB (conv5).  hipErrorNotSupported = not a trunk form / launch too small: use launch_conv.
 // force_form (the per-layer parity hook): 0 = by launch size; conv1-4: 1 = 16x32 patches / 5-deep ring, 2 = 32x32 patches / 3-deep ring,

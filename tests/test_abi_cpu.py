@@ -40,8 +40,20 @@ def test_gpu_tests_clear_exactly_the_switches_s2sr_create_reads():
 def test_expected_blob_size():
     lib = native.load_library()
     assert lib.s2sr_expected_blob_floats(23) == 16_697_987
-    from s2sr.weights import num_params
+    from s2sr.weights import num_params, num_params_compact
     assert lib.s2sr_expected_blob_floats(6) == num_params(6)
+    # the layer table behind the sizes (csrc/engine.hip layer_table) against the state dicts' own arithmetic
+    for nb in (1, 6, 23):
+        for scale in (2, 4):
+            assert native.expected_blob_floats_cfg(nb, scale) == num_params(nb, scale)
+    for n in (16, 32):
+        assert native.expected_blob_floats_cfg(n, 4, "compact") == num_params_compact(n)
+    # ... and the configurations it refuses
+    assert native.expected_blob_floats_cfg(8, 4, "compact") == 0
+    assert native.expected_blob_floats_cfg(6, 3) == 0 and native.expected_blob_floats_cfg(16, 3, "compact") == 0
+    for arch in (native.ARCH_RRDB, native.ARCH_COMPACT):
+        cfg = native._Config(16, 32, 32, 4, native.PREC_F16, 0, 0, arch)      # num_feat 32
+        assert lib.s2sr_expected_blob_floats_cfg(cfg) == 0
 
 
 def test_plan_tiles_matches_reference_golden(golden_dir):

@@ -1092,3 +1092,29 @@ def test_rdb_persistent_prototype_drains():
                 e.rdb_persistent(*bad)
     finally:
         e.close()
+
+
+@pytest.mark.parametrize("nb, precision, scale, arch", [(1, native.PREC_F16_HP, 4, "rrdb"), (1, native.PREC_FP8, 4, "rrdb"),
+                                                        (1, native.PREC_F16_HP, 2, "rrdb"), (16, native.PREC_F16, 4, "compact")],
+                         ids=["hp", "fp8", "x2plus", "compact16"])
+def test_reloading_weights_replaces_every_layer(monkeypatch, nb, precision, scale, arch):
+    """Weights A, weights B, weights A again on ONE handle: the first and third outputs are the bytes of a fresh handle holding A
+    (nothing of B survives a load: packed weights, pools, fp8 scales, captured graphs), the second differs."""
+    from s2sr import weights as W
+
+    def sd(seed):
+        return W.synthetic_compact_state_dict(nb, seed=seed) if arch == "compact" else W.synthetic_state_dict(nb, seed=seed, scale=scale)
+
+    u = 2 if scale == 2 else 1                                   # scale 2 takes even sizes: 20 x 37 on its trunk grid
+    tiles = np.random.default_rng(11).integers(0, 256, (2, 20 * u, 37 * u, 3), dtype=np.uint8)
+    want = gpu_engines.default(nb, precision, scale, arch).forward_batch_u8(tiles)
+    e = gpu_engines.fresh(monkeypatch, {}, nb, precision, scale, arch)
+    try:
+        outs = []
+        for seed in (0, 1, 0):
+            e.load_state_dict(sd(seed))
+            outs.append(e.forward_batch_u8(tiles).copy())
+    finally:
+        e.close()
+    assert np.array_equal(outs[0], want) and np.array_equal(outs[2], want)
+    assert not np.array_equal(outs[1], want)
