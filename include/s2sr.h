@@ -224,6 +224,32 @@ int  s2sr_forward_batch_u16_dev(s2sr_handle* h, const void* d_tiles, int32_t B, 
 int  s2sr_enhance_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
                       uint16_t* out_u16 /* [4H,4W,3] or NULL */, float* out_f32 /* [4H,4W,3] or NULL */);
 
+/* The seam-blended stitch, opt-in: the windows, forwards and whole / tiled switch of s2sr_enhance_u8 / s2sr_enhance_u16 with
+ * another paste.  The overwrite paste crops every window hard, so where two windows disagree in their overlap (the net sees far
+ * beyond the pad) the output steps along every tile line.  Here, per axis: owner(o) is the window the overwrite paste takes output
+ * coordinate o from; a seam S is a coordinate whose owner is another rectangle than owner(S - 1); around it lies a ramp of
+ * half-width r = min(pad * scale, half the way to the previous seam or the axis start, half the way to the next seam or the axis
+ * end).  For o in [S - r, S + r) the output cross-fades from a = owner(S - 1) to b = owner(S), b weighing
+ * w = fp32(2 (o - S + r) + 1) / fp32(4 r); where a row ramp meets a column ramp four windows take part:
+ *     top = A + wx (B - A),  bot = C + wx (D - C),  v = top + wy (bot - top)       A = (a_y, a_x), B = (a_y, b_x), C = (b_y, a_x), D = (b_y, b_x)
+ * in fp32, every product and sum rounded on its own, terms of weight 0 left out.  Outside every ramp v is the overwrite paste's
+ * value, bit for bit.  The windows leave the net as fp32 tiles (the 16-bit door's route) and one kernel pastes, blends and
+ * quantises each chunk's band of final rows; a row ramp reads the last window row of the chunk before, which is carried along.
+ * An image the switch leaves whole, or a plan without ramps (pad 0), runs through the default doors as it is.  A plan whose ramps
+ * would leave their windows, or that leaves output pixels uncovered (pad > tile / 2 on an image shorter than two pads), is refused
+ * with S2SR_E_INVALID and a text before the device is touched.
+ *
+ * s2sr_enhance_blend_u8: out_u8 [S H, S W, 3] = trunc(clip(v * 255, 0, 255)) and / or out_f32 [S H, S W, 3] = v; at least one.
+ *   prm == NULL, swap_rb == 0: s2sr_enhance_u8's contract.  swap_rb != 0: s2sr_enhance_job_u8's (RGB in, RGB out, the
+ *   post-process prm behind the stitch when not NULL); prm without swap_rb: the post-process on the image in the order given.
+ *   out_f32 only with prm == NULL and swap_rb == 0; a job needs out_u8.
+ * s2sr_enhance_blend_u16: s2sr_enhance_u16's contract and refusals (x4 RRDB nets only), out_u16 = lo + rint(clip(v, 0, 1) * (hi - lo)). */
+int  s2sr_enhance_blend_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad,
+                           const s2sr_pp_params* prm /* or NULL */, int32_t swap_rb, uint8_t* out_u8 /* or NULL */,
+                           float* out_f32 /* or NULL */);
+int  s2sr_enhance_blend_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo,
+                            int32_t hi, uint16_t* out_u16 /* [4H,4W,3] or NULL */, float* out_f32 /* [4H,4W,3] or NULL */);
+
 /* Multi-GPU building blocks of _tile_process (cnn_super_resolution.py:244-278), device-resident:
  * cut windows [first, first+count) of the plan into d_tiles [count, wh, ww, 3] (wh/ww = the
  * plan's common window size), and paste ALL T windows' outputs d_tiles [T, 4wh, 4ww, 3] into
@@ -430,6 +456,12 @@ int  s2sr_debug_plan_chunks(int32_t units, int32_t u_max, int32_t unit_windows, 
  * inside that window's output. */
 int  s2sr_debug_plan_windows(int32_t PH, int32_t PW, int32_t tile, int32_t pad, int32_t scale, int32_t tiled, int32_t* dims,
                              int32_t* rects, int32_t cap, int32_t* rm, int32_t* cm);
+/* The blend tables of s2sr_enhance_blend_* for that window job (host arithmetic only): rows (6 * scale * PH ints) and cols
+ * (6 * scale * PW), per output row / column {a, ia, b, ib, num, den}: the two windows (indices of s2sr_debug_plan_windows'
+ * distinct window rows / columns), the row / column inside each one's output, and the weight of b, w = num / den; outside every
+ * ramp a == b, ia == ib, num = 0, den = 1. */
+int  s2sr_debug_plan_blend(int32_t PH, int32_t PW, int32_t tile, int32_t pad, int32_t scale, int32_t tiled, int32_t* rows,
+                           int32_t* cols);
 
 /* test hook: ONE RDB-shaped conv through the TRUNK kernels (conv_trunk.hip: conv_trunk_f16 / conv_trunk_f8), host tensors in
  * NCHW fp32 -- the per-layer parity check of the kernels that carry 84 % of a step (s2sr_debug_conv goes through conv3x3.hip).

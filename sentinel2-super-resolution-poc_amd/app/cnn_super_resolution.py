@@ -288,11 +288,14 @@ class RealESRGAN:
     """Real-ESRGAN inference wrapper with the reference's interface (:161-280)."""
 
     def __init__(self, scale: int = 4, device: str = None, tile_size: int = 256, model_name: str = None,
-                 state_dict=None, denoise_strength: Optional[float] = None):
-        """denoise_strength (realesr_general_x4v3 only, upstream's knob): s in [0, 1] loads realesr_general_x4v3.pth and
+                 state_dict=None, denoise_strength: Optional[float] = None, seam_blend: bool = False):
+        """seam_blend (not in the reference): tiled images are stitched with the cross-faded paste (s2sr_enhance_blend_*) -- the
+        same windows and forwards, the window overlaps blended over a ramp around every tile line in place of the hard crop.
+        denoise_strength (realesr_general_x4v3 only, upstream's knob): s in [0, 1] loads realesr_general_x4v3.pth and
         realesr_general_wdn_x4v3.pth and runs dni(x4v3, wdn, s) = s * x4v3 + (1 - s) * wdn: 1 = no denoising, 0 = the wdn model."""
         self.tile_size = tile_size
         self.tile_pad = 10
+        self.seam_blend = bool(seam_blend)
         self.device = _resolve_device(device)
         print(f"   Device: {self.device}")
 
@@ -364,6 +367,8 @@ class RealESRGAN:
         if img.dtype != np.uint8:
             # the reference divides whatever it gets by 255 (:220); only u8 is on the native path
             raise TypeError(f"expected uint8 image, got {img.dtype}")
+        if self.seam_blend:
+            return self._engine.enhance_blend_u8(img, tile=self.tile_size, pad=self.tile_pad)
         return self._engine.enhance_u8(img, tile=self.tile_size, pad=self.tile_pad)
 
     def enhance16(self, img: np.ndarray, value_range=None) -> np.ndarray:
@@ -380,6 +385,8 @@ class RealESRGAN:
         lo, hi = (0, 65535) if value_range is None else (int(value_range[0]), int(value_range[1]))
         if not (0 <= lo < hi <= 65535):
             raise ValueError(f"value_range {value_range}: need 0 <= lo < hi <= 65535")
+        if self.seam_blend:
+            return self._engine.enhance_blend_u16(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
         return self._engine.enhance_u16(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
 
     def enhance_job(self, rgb: np.ndarray, post=None) -> np.ndarray:
@@ -391,6 +398,8 @@ class RealESRGAN:
             raise ValueError(f"expected HxWx3 image, got shape {rgb.shape}")
         if rgb.dtype != np.uint8:
             raise TypeError(f"expected uint8 image, got {rgb.dtype}")
+        if self.seam_blend:
+            return self._engine.enhance_blend_u8(rgb, post, swap_rb=True, tile=self.tile_size, pad=self.tile_pad)
         return self._engine.enhance_job_u8(rgb, post, tile=self.tile_size, pad=self.tile_pad)
 
     def _tile_process(self, img: torch.Tensor) -> torch.Tensor:

@@ -42,8 +42,9 @@ def enhance_vegetation(img: np.ndarray) -> np.ndarray:
     return _pp_engine().postprocess_u8(img, p)
 
 
-def apply_farm_sr(input_path: Path, output_path: Path, scale: int = 4) -> Tuple[Path, dict]:
-    """Reference farm_sr.py:111-241."""
+def apply_farm_sr(input_path: Path, output_path: Path, scale: int = 4, seam_blend: bool = False) -> Tuple[Path, dict]:
+    """Reference farm_sr.py:111-241.  seam_blend (not in the reference): the tiled stitch cross-fades the window overlaps
+    (RealESRGAN(seam_blend=True)); the metadata gains "seam_blend": true, and only then."""
     from s2sr import rasterio_lite as rio
 
     print(f"\nFarm Super-Resolution x{scale}\n   Input: {input_path}")
@@ -55,7 +56,7 @@ def apply_farm_sr(input_path: Path, output_path: Path, scale: int = 4) -> Tuple[
     import os
     from app.cnn_super_resolution import thread_precision
     with thread_precision(os.environ.get("S2SR_FARM_PRECISION") or None):
-        esrgan = RealESRGAN(scale=scale, tile_size=256)
+        esrgan = RealESRGAN(scale=scale, tile_size=256, **({"seam_blend": True} if seam_blend else {}))
         if hasattr(esrgan, "enhance_job"):      # RGB2BGR -> net -> BGR2RGB -> the three steps of :170-178, one native call
             final = esrgan.enhance_job(img, native.pp_farm())
         else:
@@ -83,16 +84,18 @@ def apply_farm_sr(input_path: Path, output_path: Path, scale: int = 4) -> Tuple[
         "original_resolution_m": 10.0,
         "optimized_for": "crop_row_visibility",
     }
+    if seam_blend:
+        metadata["seam_blend"] = True
     return final_output, metadata
 
 
-def process_farm_sr(input_tif: Path, output_dir: Path, scale: int = 4) -> dict:
-    """Reference farm_sr.py:244-286."""
+def process_farm_sr(input_tif: Path, output_dir: Path, scale: int = 4, seam_blend: bool = False) -> dict:
+    """Reference farm_sr.py:244-286.  seam_blend: see apply_farm_sr."""
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
     sr_tif = output_dir / f"{base_name}_farm_sr_x{scale}.tif"
-    _, sr_metadata = apply_farm_sr(input_path=input_tif, output_path=sr_tif, scale=scale)
+    _, sr_metadata = apply_farm_sr(input_path=input_tif, output_path=sr_tif, scale=scale, **({"seam_blend": True} if seam_blend else {}))
     png = sr_tif.with_suffix(".png")
     result = {
         "timestamp": datetime.now().strftime("%Y%m%d_%H%M%S"),

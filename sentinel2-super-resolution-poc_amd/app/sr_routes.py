@@ -30,6 +30,7 @@ class SRRequest(BaseModel):          # main.py:192-197
     input_file: Optional[str] = None
     scale: int = 4
     model: str = "edsr"
+    seam_blend: bool = False         # not in the reference: cross-fade the window overlaps of the tiled stitch
 
 
 class WowRequest(BaseModel):         # main.py:200-208
@@ -39,6 +40,7 @@ class WowRequest(BaseModel):         # main.py:200-208
     max_age_days: int = 30
     max_cloud_cover: float = 30.0
     force_fetch: bool = False
+    seam_blend: bool = False         # not in the reference: cross-fade the window overlaps of the tiled stitch
 
 
 class SRResponse(BaseModel):         # main.py:230-235
@@ -200,11 +202,11 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             run(Path(sr_tif), tiles_dir)
             result["tiles_dir"] = str(tiles_dir)
 
-    def run_sr_job(job_id, input_file, scale, model, output_dir):          # main.py:247-287
+    def run_sr_job(job_id, input_file, scale, model, output_dir, seam_blend=False):          # main.py:247-287
         try:
             _set(job_id, status="processing", message=f"Applying {model.upper()} x{scale} super-resolution...")
             from app.farm_sr import process_farm_sr                          # `model` is ignored, as in the reference
-            result = process_farm_sr(input_tif=input_file, output_dir=output_dir, scale=scale)
+            result = process_farm_sr(input_tif=input_file, output_dir=output_dir, scale=scale, **({"seam_blend": True} if seam_blend else {}))
             _set(job_id, status="tiling", message="Generating tiles from SR image...")
             _tile(result, "tiles_sr")
             _set(job_id, status="completed", message="Super-resolution complete!", result=result)
@@ -212,7 +214,7 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             _set(job_id, status="failed", message=str(e))
 
     def run_wow_job(job_id, input_file, output_dir, enhance_crops, auto_fetch=True, max_age_days=30,
-                    max_cloud_cover=30.0, force_fetch=False, model="realesrgan_x4"):   # main.py:290-368
+                    max_cloud_cover=30.0, force_fetch=False, model="realesrgan_x4", seam_blend=False):   # main.py:290-368
         try:
             if input_file is None and auto_fetch:
                 _set(job_id, status="fetching",
@@ -226,7 +228,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                        "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)"}.get(model, model)
             _set(job_id, status="processing", message=f"Stage 1/2: {display} (GAN upscaling)...")
             from app.wow_sr import process_wow_sr
-            result = process_wow_sr(input_tif=input_file, output_dir=output_dir, enhance_crops=enhance_crops, model=model)
+            result = process_wow_sr(input_tif=input_file, output_dir=output_dir, enhance_crops=enhance_crops, model=model,
+                                    **({"seam_blend": True} if seam_blend else {}))
             _set(job_id, status="tiling", message="Generating tiles from WOW SR image...")
             _tile(result, "tiles_wow")
             _set(job_id, status="completed", message="WOW Super-resolution complete!", result=result)
@@ -254,7 +257,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             sr_jobs[job_id] = {"status": "queued", "message": "Job queued", "input_file": str(input_file),
                                "scale": request.scale, "model": request.model, "output_dir": str(output_dir),
                                "created_at": datetime.now().isoformat()}
-        background_tasks.add_task(run_sr_job, job_id, input_file, request.scale, request.model, output_dir)
+        background_tasks.add_task(run_sr_job, job_id, input_file, request.scale, request.model, output_dir,
+                                  **({"seam_blend": True} if request.seam_blend else {}))
         return SRResponse(job_id=job_id, status="queued", message=f"SR job started: {input_file.name} -> x{request.scale}")
 
     @app.get("/api/sr/{job_id}")                                             # main.py:437-443
@@ -292,7 +296,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                                "max_age_days": request.max_age_days, "max_cloud_cover": request.max_cloud_cover,
                                "output_dir": str(output_dir), "created_at": datetime.now().isoformat()}
         background_tasks.add_task(run_wow_job, job_id, input_file, output_dir, request.enhance_crops,
-                                  request.auto_fetch, request.max_age_days, request.max_cloud_cover, request.force_fetch)
+                                  request.auto_fetch, request.max_age_days, request.max_cloud_cover, request.force_fetch,
+                                  **({"seam_blend": True} if request.seam_blend else {}))
         msg = (f"WOW SR started: {input_file.name} -> Real-ESRGAN x4 + Enhanced" if input_file else
                f"WOW SR started: auto-fetching best image (last {request.max_age_days}d, cloud <={request.max_cloud_cover}%)")
         return SRResponse(job_id=job_id, status="queued", message=msg)

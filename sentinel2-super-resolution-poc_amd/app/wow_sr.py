@@ -35,7 +35,7 @@ def _enhance_for_crops(img: np.ndarray) -> np.ndarray:
     return _pp_engine().postprocess_u8(img, native.pp_wow())
 
 
-def _apply_wow_sr16(input_path: Path, output_path: Path, model: str) -> Tuple[Path, dict]:
+def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend: bool = False) -> Tuple[Path, dict]:
     """bit_depth=16 of apply_wow_sr: a uint16 GeoTIFF read raw, value_range = the image's own (min, max) -- the reference's
     min-max (wow_sr.py:67-73) minus its quantisation to 8 bits -- the net fed BGR as ever (:85,94), RealESRGAN.enhance16, RGB back,
     a uint16 GeoTIFF out.  No PNG (the encoder is 8-bit) and no crop-visibility post-process (OpenCV's 8-bit arithmetic)."""
@@ -52,7 +52,7 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str) -> Tuple[Pa
     lo, hi = int(img.min()), int(img.max())
     if hi == lo:                      # a constant raster: any range that contains it
         lo, hi = (lo - 1, hi) if hi > 0 else (0, 1)
-    esrgan = RealESRGAN(model_name=model, tile_size=256)
+    esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}))
     out_bgr = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi))
     output_rgb = np.ascontiguousarray(out_bgr[:, :, ::-1])
     scale = esrgan.scale
@@ -75,6 +75,8 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str) -> Tuple[Pa
         "bit_depth": 16,
         "value_range": [lo, hi],
     }
+    if seam_blend:
+        metadata["seam_blend"] = True
     return final_output, metadata
 
 
@@ -86,14 +88,16 @@ def _check_bit_depth(bit_depth: int, enhance_crops: bool) -> None:
 
 
 def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True,
-                 model: str = "realesrgan_x4", bit_depth: int = 8) -> Tuple[Path, dict]:
+                 model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False) -> Tuple[Path, dict]:
     """Reference wow_sr.py:28-184 -- same outputs (GeoTIFF and/or PNG) and metadata dict.  bit_depth=16 (not in the reference): a
-    uint16 GeoTIFF goes through the net without the 8-bit squeeze and comes back as a uint16 GeoTIFF (_apply_wow_sr16)."""
+    uint16 GeoTIFF goes through the net without the 8-bit squeeze and comes back as a uint16 GeoTIFF (_apply_wow_sr16).
+    seam_blend (not in the reference): the tiled stitch cross-fades the window overlaps (RealESRGAN(seam_blend=True)); the metadata
+    gains "seam_blend": true, and only then."""
     from s2sr import rasterio_lite as rio
 
     _check_bit_depth(bit_depth, enhance_crops)
     if bit_depth == 16:
-        return _apply_wow_sr16(input_path, output_path, model)
+        return _apply_wow_sr16(input_path, output_path, model, seam_blend)
 
     model_display = {"realesrgan_x4": "Real-ESRGAN x4",
                      "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)",
@@ -108,7 +112,7 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
 
     pipeline_stages = []
     print(f"   Stage 1/2: {model_display} (GAN upscaling)...")
-    esrgan = RealESRGAN(model_name=model, tile_size=256)
+    esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}))
     # RGB2BGR -> enhance -> BGR2RGB -> _enhance_for_crops (:85-110) as ONE native call: the 16x image crosses PCIe once
     if enhance_crops:
         print("   Stage 2/2: Crop visibility enhancement...")
@@ -149,24 +153,27 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
         "effective_resolution_m": 10.0 / scale,
         "optimized_for": "z18_crop_visibility",
     }
+    if seam_blend:
+        metadata["seam_blend"] = True
     return final_output, metadata
 
 
 def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True,
-                   model: str = "realesrgan_x4", bit_depth: int = 8) -> dict:
+                   model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False) -> dict:
     """Reference wow_sr.py:212-266 -- file naming, metadata JSON and result dict schema.  bit_depth=16: see apply_wow_sr (no PNG:
-    "sr_png" is None)."""
+    "sr_png" is None).  seam_blend: see apply_wow_sr."""
     _check_bit_depth(bit_depth, enhance_crops)          # before anything is created
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
     wow_tif = output_dir / f"{base_name}_wow_sr.tif"
     png = wow_tif.with_suffix(".png")
+    blend = {"seam_blend": True} if seam_blend else {}   # (tests patch apply_wow_sr with the reference's signature)
     if bit_depth == 16:
-        _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model, bit_depth=16)
+        _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model, bit_depth=16, **blend)
         png = None       # (a PNG an earlier 8-bit job left under this name is not this job's output)
     else:
-        _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model)
+        _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model, **blend)
     result = {
         "timestamp": datetime.now().strftime("%Y%m%d_%H%M%S"),
         "input": str(input_tif),

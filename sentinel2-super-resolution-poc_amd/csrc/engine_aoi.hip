@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "blend_plan.h"
 #include "engine_internal.h"
 
 using namespace s2sr;
@@ -220,9 +221,10 @@ static std::vector<int> plan_chunk_rows(const s2sr_handle* h, const WindowJob& j
 // rows that chunk made final into image rows on the device (t0: the chunk's first window, for a door that keeps one chunk's
 // tiles).  `copy`: each band (row_b bytes per row, at dev, to host) leaves on the copy stream under the next chunk's compute,
 // the last one exposed.  Events group_done[0 .. nchunks) are the caller's to provide.
-template <class Forward, class Finish>
+// last_row(y): the last window row output row y reads (monotone in y): rows [yb, ye) with last_row < the chunk's end are final.
+template <class Forward, class Finish, class LastRow>
 static int run_chunks(s2sr_handle* h, hipStream_t st, const WindowJob& job, const std::vector<int>& chunk_r0, int OH, Forward forward,
-                      Finish finish, uint8_t* host, const uint8_t* dev, size_t row_b, bool copy) {
+                      Finish finish, uint8_t* host, const uint8_t* dev, size_t row_b, bool copy, LastRow last_row) {
     const int nx = job.nx, ny = job.ny, nchunks = (int)chunk_r0.size() - 1;
     int rc, yb = 0, prev_yb = 0, prev_ye = 0;
     for (int c = 0; c < nchunks; ++c) {
@@ -230,7 +232,7 @@ static int run_chunks(s2sr_handle* h, hipStream_t st, const WindowJob& job, cons
         if ((rc = forward(r0 * nx, (r1 - r0) * nx))) return rc;
         int ye = OH;
         if (r1 < ny)
-            for (ye = yb; ye < OH && job.rm[2 * ye] < r1; ++ye) {}
+            for (ye = yb; ye < OH && last_row(ye) < r1; ++ye) {}
         if (ye > yb && (rc = finish(r0 * nx, yb, ye))) return rc;
         HIPCHK(h, hipEventRecord(h->group_done[c], st));
         if (copy && c > 0 && prev_ye > prev_yb) {
@@ -244,6 +246,13 @@ static int run_chunks(s2sr_handle* h, hipStream_t st, const WindowJob& job, cons
         if ((rc = d2h_staged(h, host + (size_t)prev_yb * row_b, dev + (size_t)prev_yb * row_b, (size_t)(prev_ye - prev_yb) * row_b, true))) return rc;
     }
     return S2SR_OK;
+}
+
+// the overwrite paste: a row is final once the window row that owns it is done (the paste map)
+template <class Forward, class Finish>
+static int run_chunks(s2sr_handle* h, hipStream_t st, const WindowJob& job, const std::vector<int>& chunk_r0, int OH, Forward forward,
+                      Finish finish, uint8_t* host, const uint8_t* dev, size_t row_b, bool copy) {
+    return run_chunks(h, st, job, chunk_r0, OH, forward, finish, host, dev, row_b, copy, [&](int y) { return job.rm[2 * y]; });
 }
 
 }  // namespace s2sr::engine
@@ -411,6 +420,40 @@ static int plan_dims(s2sr_handle* h, int H, int W, int tile, int* PH, int* PW) {
     return S2SR_OK;
 }
 
+// The finish of a banded post-process whose histograms hold every row (pp_band_hist_locked over each stitched band): the LUTs, then
+// the image in nfin row bands of fin_rows rows, each followed by its copy out.  group_done[nchunks .. nchunks + nfin) are free for
+// the bands; group_done[nchunks - 1] marks the last chunk.
+static int pp_finish_bands(s2sr_handle* h, hipStream_t st, uint8_t* d_img_out, uint8_t* out_u8, int OH, size_t row_b, int fin_rows, int nfin,
+                           int nchunks) {
+    int rc;
+    // LUTs, then every finishing band's kernels (in place: a band's rows are rewritten only after the apply pass, which
+    // runs R rows ahead, has read them), an event behind each; the copies follow band by band on the copy stream
+    const bool timing = getenv("S2SR_JOB_TIMING") != nullptr;     // diagnostic: stage times of the finish on stderr
+    auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double t_enq = now(), t_compute = 0, t_first = 0;
+    if ((rc = pp_band_lut_locked(h, st))) return rc;
+    for (int b = 0; b < nfin; ++b) {
+        const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
+        if ((rc = pp_band_rows_locked(h, d_img_out, y0, y1, d_img_out, st))) return rc;
+        HIPCHK(h, hipEventRecord(h->group_done[nchunks + b], st));
+    }
+    if (timing) {
+        HIPCHK(h, hipEventSynchronize(h->group_done[nchunks - 1]));
+        t_compute = now();
+    }
+    for (int b = 0; b < nfin; ++b) {
+        const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks + b], 0));
+        if ((rc = d2h_staged(h, out_u8 + (size_t)y0 * row_b, d_img_out + (size_t)y0 * row_b, (size_t)(y1 - y0) * row_b,
+                             false))) return rc;
+        if (timing && b == 0) t_first = now();
+    }
+    if (timing)
+        fprintf(stderr, "[s2sr job] finish: %d bands of %d rows; last chunk done %.2f ms after the finish was queued, first band on the host "
+                "+%.2f ms, all bands +%.2f ms\n", nfin, fin_rows, t_compute - t_enq, t_first - t_compute, now() - t_compute);
+    return S2SR_OK;
+}
+
 // RealESRGAN.enhance (cnn_super_resolution.py:217-234) incl. _tile_process (:236-280)
 // job_rgb: the caller's image is RGB and wants RGB back -- R and B are swapped on the device in front of and behind the net (the
 // reference's cvtColor pair, wow_sr.py:85,103).  prm: the crop-visibility post-process (wow_sr.py:187-209) on the stitched RGB
@@ -502,33 +545,7 @@ static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int ti
             };
             // with a post-process no band is copied here: the bands leave through the finishing pass below
             if ((rc = run_chunks(h, st, job, chunk_r0, OH, forward, finish, out_u8, d_img_out, row_b, !prm))) return rc;
-            if (prm) {
-                // LUTs, then every finishing band's kernels (in place: a band's rows are rewritten only after the apply pass, which
-                // runs R rows ahead, has read them), an event behind each; the copies follow band by band on the copy stream
-                const bool timing = getenv("S2SR_JOB_TIMING") != nullptr;     // diagnostic: stage times of the finish on stderr
-                auto now = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-                double t_enq = now(), t_compute = 0, t_first = 0;
-                if ((rc = pp_band_lut_locked(h, st))) return rc;
-                for (int b = 0; b < nfin; ++b) {
-                    const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
-                    if ((rc = pp_band_rows_locked(h, d_img_out, y0, y1, d_img_out, st))) return rc;
-                    HIPCHK(h, hipEventRecord(h->group_done[nchunks + b], st));
-                }
-                if (timing) {
-                    HIPCHK(h, hipEventSynchronize(h->group_done[nchunks - 1]));
-                    t_compute = now();
-                }
-                for (int b = 0; b < nfin; ++b) {
-                    const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
-                    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks + b], 0));
-                    if ((rc = d2h_staged(h, out_u8 + (size_t)y0 * row_b, d_img_out + (size_t)y0 * row_b, (size_t)(y1 - y0) * row_b,
-                                         false))) return rc;
-                    if (timing && b == 0) t_first = now();
-                }
-                if (timing)
-                    fprintf(stderr, "[s2sr job] finish: %d bands of %d rows; last chunk done %.2f ms after the finish was queued, first band on the host "
-                            "+%.2f ms, all bands +%.2f ms\n", nfin, fin_rows, t_compute - t_enq, t_first - t_compute, now() - t_compute);
-            }
+            if (prm && (rc = pp_finish_bands(h, st, d_img_out, out_u8, OH, row_b, fin_rows, nfin, nchunks))) return rc;
             HIPCHK(h, hipStreamSynchronize(h->copy_stream));
             HIPCHK(h, hipStreamSynchronize(st));
             return S2SR_OK;
@@ -655,6 +672,188 @@ static int enhance16_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int
 int s2sr_enhance_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
                      uint16_t* out_u16, float* out_f32) {
     RUN_WITH_STREAM_RECOVERY(h, enhance16_impl(h, img, H, W, tile, pad, lo, hi, out_u16, out_f32));
+}
+
+// The seam-blended doors (s2sr_enhance_blend_u8 / _u16): enhance_impl's / enhance16_impl's windows, forwards and whole / tiled
+// switch with another paste.  A sibling of enhance16_impl: every chunk's windows leave the net as fp32 tiles into one chunk-sized
+// buffer, and launch_stitch_blend turns the chunk's band of final rows into image rows, cross-fading inside the ramps of the blend
+// plan (blend_plan.h).  A row ramp reads the last window row of one chunk and the first of the next, so the buffer has one window
+// row in front of the chunk's (the same pointers for every chunk: their graphs hit), filled from the previous chunk's last window
+// row by one device-to-device copy; a row is final once the later of its two window rows is done.  An image the switch leaves
+// whole, or whose plan has no ramp (pad 0), goes through the default doors as it is.
+struct BlendCall {
+    const uint8_t* img8 = nullptr;
+    const uint16_t* img16 = nullptr;
+    int lo = 0, hi = 0;                       // 16-bit: the value range
+    const s2sr_pp_params* prm = nullptr;      // 8-bit: the job's post-process ...
+    bool swap_rb = false;                     // ... and its R / B exchange in front of and behind the net
+    uint8_t* out_u8 = nullptr;
+    uint16_t* out_u16 = nullptr;
+    float* out_f32 = nullptr;
+};
+
+static int enhance_blend_impl(s2sr_handle* h, const BlendCall& c, int H, int W, int tile, int pad) {
+    const bool in16 = c.img16 != nullptr;
+    if (!h) return S2SR_E_INVALID;
+    WindowJob job;
+    std::vector<int32_t> rows, cols;          // the blend tables (blend_plan.h), 6 ints per output row / column of the padded image
+    std::vector<int> chunk_r0;
+    int PH = H, PW = W, rc;
+    bool blend = false;
+    {
+        std::lock_guard<std::mutex> lk(h->mu);
+        if ((!c.img8 && !c.img16) || (!c.out_u8 && !c.out_u16 && !c.out_f32) || H <= 0 || W <= 0 || tile <= 0 || pad < 0)
+            return fail(h, S2SR_E_INVALID, "s2sr_enhance_blend: an image, positive sizes and at least one output are required");
+        if (!in16 && c.out_f32 && (c.prm || c.swap_rb))
+            return fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: the float image is the net's own output: not with a post-process or swap_rb");
+        if (!in16 && (c.prm || c.swap_rb) && !c.out_u8) return fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: a job needs out_u8");
+        if (in16 && (rc = check_u16(h, c.lo, c.hi))) return rc;
+        if (c.prm)
+            if (const char* why = pp_params_error(*c.prm)) return fail(h, S2SR_E_INVALID, why);
+        if (!in16 && (rc = plan_dims(h, H, W, tile, &PH, &PW))) return rc;
+        if ((long long)PH * PW > (long long)tile * tile * 4) {   // strict '>' (:226)
+            const int scale = h->cfg.scale;
+            if ((rc = plan_window_job(PH, PW, tile, pad, scale, true, job))) return fail(h, rc, kBadPlan);
+            rows.resize((size_t)kBlendStride * PH * scale); cols.resize((size_t)kBlendStride * PW * scale);
+            const char* why = blend_plan_axis(job.rm.data(), (int64_t)PH * scale, job.ny, job.wh * scale, pad * scale, rows.data());
+            if (!why) why = blend_plan_axis(job.cm.data(), (int64_t)PW * scale, job.nx, job.ww * scale, pad * scale, cols.data());
+            if (why) return fail(h, S2SR_E_INVALID, why);
+            for (size_t i = 4; i < rows.size() && !blend; i += kBlendStride) blend = rows[i] != 0;
+            for (size_t i = 4; i < cols.size() && !blend; i += kBlendStride) blend = cols[i] != 0;
+        }
+    }
+    if (!blend) {   // whole, or no ramp anywhere: today's doors (an 8-bit call for both images is two of them)
+        if (in16) return enhance16_impl(h, c.img16, H, W, tile, pad, c.lo, c.hi, c.out_u16, c.out_f32);
+        if (c.out_f32 && (rc = enhance_impl(h, c.img8, H, W, tile, pad, nullptr, c.out_f32))) return rc;
+        return c.out_u8 ? enhance_impl(h, c.img8, H, W, tile, pad, c.out_u8, nullptr, false, c.swap_rb, c.prm) : S2SR_OK;
+    }
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    const bool reflect = PH != H || PW != W;
+    const int scale = h->cfg.scale, OH = H * scale, OW = W * scale, esz = in16 ? 2 : 1;
+    const int nx = job.nx, ny = job.ny, wh = job.wh, ww = job.ww;
+    void* out_q = in16 ? (void*)c.out_u16 : (void*)c.out_u8;
+    const Mosaic mo = pick_mosaic(h, nx * ny, wh, ww);   // ONE plan for the job: every chunk runs in its workspace geometry
+    // one chunk with out_f32: the float image is blended from all the tiles at the end
+    chunk_r0 = !c.out_f32 ? plan_chunk_rows(h, job, mo) : std::vector<int>{0, ny};
+    const int nchunks = (int)chunk_r0.size() - 1, carry = nchunks > 1 ? 1 : 0;
+    auto last_row = [&](int y) { return (int)rows[(size_t)kBlendStride * y + 2]; };
+    // the bands, on the host first: every row reads window rows its chunk's buffer holds (its own, and the one carried in front)
+    int max_rows = 0;
+    for (int k = 0, yb = 0; k < nchunks; ++k) {
+        const int r0 = chunk_r0[k], r1 = chunk_r0[k + 1] < ny ? chunk_r0[k + 1] : ny;
+        if (r1 - r0 > max_rows) max_rows = r1 - r0;
+        int ye = OH;
+        if (r1 < ny)
+            for (ye = yb; ye < OH && last_row(ye) < r1; ++ye) {}
+        if (const char* why = blend_check_band(rows.data(), yb, ye, k > 0 ? r0 - carry : r0, r1)) return fail(h, S2SR_E_INVALID, why);
+        yb = ye;
+    }
+    blend_device_axis(rows.data(), (int64_t)PH * scale);
+    blend_device_axis(cols.data(), (int64_t)PW * scale);
+    const size_t ipx = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
+    const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;      // samples per window, in and out
+    const size_t q_bytes = (opx * esz + 255) & ~(size_t)255;     // scratch 1: the quantised image, then (out_f32) the fp32 image
+    const size_t row_b = (size_t)OW * 3 * esz;                   // bytes of one output row
+    if ((rc = ensure_scratch(h, 0, ipx * esz))) return rc;
+    if ((rc = ensure_scratch(h, 1, q_bytes + (c.out_f32 ? opx * 4 : 0)))) return rc;
+    if ((rc = ensure_scratch(h, 2, (size_t)nx * ny * win_in * esz))) return rc;
+    if ((rc = ensure_scratch(h, 3, (job.rects.size() + rows.size() + cols.size()) * 4))) return rc;
+    if ((rc = ensure_scratch(h, 4, (size_t)(max_rows + carry) * nx * win_out * sizeof(float)))) return rc;
+    int fin_rows = 0, nfin = 0;          // finishing bands of the post-process, as enhance_impl cuts them
+    if (c.prm) {
+        fin_rows = (int)(((size_t)48 << 20) / row_b) & ~31;
+        if (fin_rows < 64) fin_rows = 64;
+        nfin = (OH + fin_rows - 1) / fin_rows;
+        if ((rc = pp_band_begin_locked(h, OH, OW, c.prm, c.swap_rb ? 3 : 0, st))) return rc;   // (allocates: before anything is enqueued)
+    }
+    struct CloseRun { s2sr_handle* h; ~CloseRun() { if (h) h->ppb.open = false; } } close_run{c.prm ? h : nullptr};   // as enhance_impl
+    if ((rc = ensure_group_events(h, nchunks + nfin + 1))) return rc;
+    int32_t* d_rects = (int32_t*)h->d_scratch[3];
+    int32_t* d_rows = d_rects + job.rects.size();
+    int32_t* d_cols = d_rows + rows.size();
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], in16 ? (const void*)c.img16 : (const void*)c.img8, ipx * esz, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(d_rects, job.rects.data(), job.rects.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(d_cols, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipStreamSynchronize(st));   // the tables are host vectors of this call
+    if (in16) {
+        HIPCHK(h, launch_gather_windows((const uint16_t*)h->d_scratch[0], H, W, d_rects, nx * ny, wh, ww, (uint16_t*)h->d_scratch[2], st));
+    } else {
+        if (c.swap_rb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[0], (size_t)H * W, (uint8_t*)h->d_scratch[0], st));
+        HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_rects, nx * ny, wh, ww, reflect, (uint8_t*)h->d_scratch[2], st));
+    }
+    uint8_t* d_q = (uint8_t*)h->d_scratch[1];
+    float* d_buf = (float*)h->d_scratch[4];                      // [carry window row | the chunk's window rows]
+    float* d_tiles = d_buf + (size_t)carry * nx * win_out;
+    const int oth = wh * scale, otw = ww * scale;
+    int prev_n = 0;                                              // windows of the chunk before
+    auto forward = [&](int t0, int n) -> int {
+        if (t0 > 0)   // the last window row of the chunk before, to the front of the buffer (its band is stitched: same stream)
+            HIPCHK(h, hipMemcpyAsync(d_buf, d_tiles + (size_t)(prev_n - nx) * win_out, (size_t)nx * win_out * sizeof(float), hipMemcpyDeviceToDevice, st));
+        prev_n = n;
+        const TileIn in = in16 ? TileIn::u16((const uint16_t*)h->d_scratch[2] + (size_t)t0 * win_in, c.lo, c.hi)
+                               : TileIn::u8((const uint8_t*)h->d_scratch[2] + (size_t)t0 * win_in);
+        return forward_dev(h, st, in, n, wh, ww, TileOut{nullptr, d_tiles}, mo.on() ? &mo : nullptr);
+    };
+    // rows [yb, ye) into the quantised image; the buffer's first tile is window t0 - carry * nx
+    auto paste = [&](int t0, int yb, int ye) -> int {
+        Scope sc(h, st, F_MISC, 0.0, (double)(ye - yb) * OW * 3.0 * (4.0 + esz));
+        const int32_t* r = d_rows + (size_t)kBlendStride * yb;
+        if (in16) HIPCHK(h, launch_stitch_blend(d_buf, nx, t0 - carry * nx, oth, otw, r, d_cols, ye - yb, OW, c.lo, c.hi, (uint16_t*)(d_q + (size_t)yb * row_b), st));
+        else HIPCHK(h, launch_stitch_blend(d_buf, nx, t0 - carry * nx, oth, otw, r, d_cols, ye - yb, OW, c.swap_rb && !c.prm, d_q + (size_t)yb * row_b, st));
+        return S2SR_OK;
+    };
+    auto finish = [&](int t0, int yb, int ye) -> int {
+        if (!out_q) return S2SR_OK;
+        if (int prc = paste(t0, yb, ye)) return prc;
+        return c.prm ? pp_band_hist_locked(h, d_q, yb, ye, st) : S2SR_OK;   // (the post-process exchanges R and B itself)
+    };
+    // with a post-process the bands leave through its finishing pass; with out_f32 (one chunk) both images leave behind the float blend
+    if ((rc = run_chunks(h, st, job, chunk_r0, OH, forward, finish, (uint8_t*)out_q, d_q, row_b, out_q && !c.prm && !c.out_f32, last_row))) return rc;
+    if (c.prm && (rc = pp_finish_bands(h, st, d_q, c.out_u8, OH, row_b, fin_rows, nfin, nchunks))) return rc;
+    if (c.out_f32) {
+        float* d_f = (float*)((char*)h->d_scratch[1] + q_bytes);
+        HIPCHK(h, launch_stitch_blend(d_buf, nx, 0, oth, otw, d_rows, d_cols, OH, OW, d_f, st));
+        HIPCHK(h, hipEventRecord(h->group_done[nchunks + nfin], st));
+        if (out_q) {
+            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
+            if ((rc = d2h_staged(h, (uint8_t*)out_q, d_q, OH * row_b, true))) return rc;
+        }
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks + nfin], 0));
+        if ((rc = d2h_staged(h, (uint8_t*)c.out_f32, (const uint8_t*)d_f, opx * 4, true))) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    HIPCHK(h, hipStreamSynchronize(st));
+    return S2SR_OK;
+}
+
+int s2sr_enhance_blend_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
+                          int32_t swap_rb, uint8_t* out_u8, float* out_f32) {
+    BlendCall c;
+    c.img8 = img; c.prm = prm; c.swap_rb = swap_rb != 0; c.out_u8 = out_u8; c.out_f32 = out_f32;
+    if (!img) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: an image is required") : S2SR_E_INVALID;
+    RUN_WITH_STREAM_RECOVERY(h, enhance_blend_impl(h, c, H, W, tile, pad));
+}
+
+int s2sr_enhance_blend_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
+                           uint16_t* out_u16, float* out_f32) {
+    BlendCall c;
+    c.img16 = img; c.lo = lo; c.hi = hi; c.out_u16 = out_u16; c.out_f32 = out_f32;
+    if (!img) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u16: an image is required") : S2SR_E_INVALID;
+    RUN_WITH_STREAM_RECOVERY(h, enhance_blend_impl(h, c, H, W, tile, pad));
+}
+
+// The blend tables of a PH x PW image's window job (pure host arithmetic, for the CPU tests): six ints per output row / column,
+// {a, ia, b, ib, num, den}; window indices are those of s2sr_debug_plan_windows.
+int s2sr_debug_plan_blend(int32_t PH, int32_t PW, int32_t tile, int32_t pad, int32_t scale, int32_t tiled, int32_t* rows, int32_t* cols) {
+    if (!rows || !cols || PH <= 0 || PW <= 0 || tile <= 0 || pad < 0 || scale <= 0) return S2SR_E_INVALID;
+    WindowJob job;
+    if (int rc = plan_window_job(PH, PW, tile, pad, scale, tiled != 0, job)) return rc;
+    if (blend_plan_axis(job.rm.data(), (int64_t)PH * scale, job.ny, job.wh * scale, pad * scale, rows)) return S2SR_E_INVALID;
+    if (blend_plan_axis(job.cm.data(), (int64_t)PW * scale, job.nx, job.ww * scale, pad * scale, cols)) return S2SR_E_INVALID;
+    return S2SR_OK;
 }
 
 int s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_t W, int32_t tile, int32_t pad,

@@ -660,4 +660,164 @@ hipError_t launch_stitch_quant_u16(const float* d_tiles, int tilesX, int tile0, 
     return hipGetLastError();
 }
 
+// ---- the seam-blended stitch (s2sr_enhance_blend_*) ---------------------------------------------------------------------------
+// Planar fp32 tiles [.., 3, oth, otw] -> rows [0, OH) of an HWC image, cross-faded inside the ramps of the blend plan
+// (blend_plan.h).  rows / cols: six ints per output row / column, {a, ia, b, ib, bits of the fp32 weight of b, 0}: the two windows
+// (window (ty, tx) is tile ty * tilesX + tx - tile0 of `tiles`), the offsets inside their outputs, and w = 0 outside every ramp,
+// where a == b.  With A = (a_y, a_x), B = (a_y, b_x), C = (b_y, a_x), D = (b_y, b_x):
+//     top = A + wx (B - A),  bot = C + wx (D - C),  v = top + wy (bot - top)
+// each product and sum rounded on its own (no FMA), and a term whose weight is 0 neither read nor computed (A + 0 * x is not A
+// for A = -0 or an infinite x).  The output: u8 trunc(clip(v * 255, 0, 255)) as conv_last's epilogue, u16 quant_u16, or v itself.
+struct BlendQ { int lo; float range; };
+__device__ inline uint32_t blend_quant(float v, uint8_t, const BlendQ&) { return (uint32_t)(int)fminf(fmaxf(__fmul_rn(v, 255.0f), 0.f), 255.f); }
+__device__ inline uint32_t blend_quant(float v, uint16_t, const BlendQ& q) { return quant_u16(v, q.range, q.lo); }
+__device__ inline uint32_t blend_quant(float v, float, const BlendQ&) { return __float_as_uint(v); }
+
+// a + w (b - a), the difference, the product and the sum each rounded to fp32.  This file is compiled with contraction on, and
+// __fmul_rn / __fadd_rn are header functions whose operators carry that setting with them when inlined (conv3x3.hip, where the
+// epilogues use them, is built with -ffp-contract=off): the pragma on plain operators is what keeps the product and the sum apart.
+__device__ inline float blend_lerp(float a, float b, float w) {
+#pragma clang fp contract(off)
+    const float d = b - a;
+    const float p = w * d;
+    return a + p;
+}
+
+// One thread = 4 consecutive output pixels of a row.  Where the 4 share their windows (a ramp edge does not split them: edges of
+// shortened ramps fall on any column) and the offsets are consecutive and 16-byte aligned, each sample row is one float4 per colour
+// plane; else pixel by pixel.  The stores are 12 (u8) / 24 (u16) / 48 (fp32) contiguous bytes when OW is a multiple of 4 (every x4
+// net), element by element otherwise (the x2 net on an odd width).  swap: R and B exchanged in the pixels written.
+template <class O>
+__global__ void stitch_blend_kernel(const float* __restrict__ tiles, int oth, int otw, const int32_t* __restrict__ rows,
+                                    const int32_t* __restrict__ cols, int tilesX, int tile0, int OH, int OW, int swap, BlendQ q,
+                                    O* __restrict__ out) {
+    const int gw = (OW + 3) >> 2;
+    const size_t total = (size_t)OH * gw;
+    const size_t plane = (size_t)oth * otw;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int ox = (int)(i % gw) << 2;
+        const int oy = (int)(i / gw);
+        const int npx = OW - ox < 4 ? OW - ox : 4;
+        const int32_t* re = rows + 6 * (size_t)oy;
+        const int ya = re[0], iya = re[1], yb = re[2], iyb = re[3];
+        const float wy = __int_as_float(re[4]);
+        int xa[4], ixa[4], xb[4], ixb[4];
+        float wx[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int32_t* ce = cols + 6 * (size_t)(ox + (k < npx ? k : 0));
+            xa[k] = ce[0]; ixa[k] = ce[1]; xb[k] = ce[2]; ixb[k] = ce[3]; wx[k] = __int_as_float(ce[4]);
+        }
+        // start of the planes of window (ty, tx), row sy
+        auto at = [&](int ty, int sy, int tx) { return tiles + (((size_t)(ty * tilesX + tx - tile0) * 3) * oth + sy) * otw; };
+        bool vec = npx == 4 && (otw & 3) == 0 && (plane & 3) == 0 && ((uintptr_t)tiles & 15) == 0 && (ixa[0] & 3) == 0 && (ixb[0] & 3) == 0;
+#pragma unroll
+        for (int k = 1; k < 4; ++k)
+            vec = vec && xa[k] == xa[0] && xb[k] == xb[0] && ixa[k] == ixa[0] + k && ixb[k] == ixb[0] + k && (wx[k] != 0.f) == (wx[0] != 0.f);
+        float v[3][4];
+        if (vec) {
+            const bool fx = wx[0] != 0.f, fy = wy != 0.f;
+            const float* pA = at(ya, iya, xa[0]) + ixa[0];
+            const float* pB = at(ya, iya, xb[0]) + ixb[0];
+            const float* pC = at(yb, iyb, xa[0]) + ixa[0];
+            const float* pD = at(yb, iyb, xb[0]) + ixb[0];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float t[4];
+                const float4 A = *(const float4*)(pA + c * plane);
+                t[0] = A.x; t[1] = A.y; t[2] = A.z; t[3] = A.w;
+                if (fx) {
+                    const float4 B = *(const float4*)(pB + c * plane);
+                    t[0] = blend_lerp(t[0], B.x, wx[0]); t[1] = blend_lerp(t[1], B.y, wx[1]);
+                    t[2] = blend_lerp(t[2], B.z, wx[2]); t[3] = blend_lerp(t[3], B.w, wx[3]);
+                }
+                if (fy) {
+                    float u[4];
+                    const float4 Cc = *(const float4*)(pC + c * plane);
+                    u[0] = Cc.x; u[1] = Cc.y; u[2] = Cc.z; u[3] = Cc.w;
+                    if (fx) {
+                        const float4 D = *(const float4*)(pD + c * plane);
+                        u[0] = blend_lerp(u[0], D.x, wx[0]); u[1] = blend_lerp(u[1], D.y, wx[1]);
+                        u[2] = blend_lerp(u[2], D.z, wx[2]); u[3] = blend_lerp(u[3], D.w, wx[3]);
+                    }
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) t[k] = blend_lerp(t[k], u[k], wy);
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[c][k] = t[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const bool fx = wx[k] != 0.f, fy = wy != 0.f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float t = 0.f;
+                    if (k < npx) {
+                        t = at(ya, iya, xa[k])[c * plane + ixa[k]];
+                        if (fx) t = blend_lerp(t, at(ya, iya, xb[k])[c * plane + ixb[k]], wx[k]);
+                        if (fy) {
+                            float u = at(yb, iyb, xa[k])[c * plane + ixa[k]];
+                            if (fx) u = blend_lerp(u, at(yb, iyb, xb[k])[c * plane + ixb[k]], wx[k]);
+                            t = blend_lerp(t, u, wy);
+                        }
+                    }
+                    v[c][k] = t;
+                }
+            }
+        }
+        uint32_t e[12];                                   // the 4 pixels in output order, quantised (fp32: the value's bits)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) e[3 * k + c] = blend_quant(v[swap ? 2 - c : c][k], O(), q);
+        O* d = out + ((size_t)oy * OW + ox) * 3;
+        if ((OW & 3) == 0) {   // (oy * OW + ox) * 3 elements: a multiple of 12, so the stores below are aligned (the launcher checks `out`)
+            if constexpr (sizeof(O) == 1) {
+                uint32_t* d4 = (uint32_t*)d;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) d4[j] = e[4 * j] | (e[4 * j + 1] << 8) | (e[4 * j + 2] << 16) | (e[4 * j + 3] << 24);
+            } else if constexpr (sizeof(O) == 2) {
+                uint2* d8 = (uint2*)d;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) d8[j] = make_uint2(e[4 * j] | (e[4 * j + 1] << 16), e[4 * j + 2] | (e[4 * j + 3] << 16));
+            } else {
+                uint4* d16 = (uint4*)d;
+#pragma unroll
+                for (int j = 0; j < 3; ++j) d16[j] = make_uint4(e[4 * j], e[4 * j + 1], e[4 * j + 2], e[4 * j + 3]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 12; ++j)
+                if (j < 3 * npx) {
+                    if constexpr (sizeof(O) == 4) d[j] = __uint_as_float(e[j]);
+                    else d[j] = (O)e[j];
+                }
+        }
+    }
+}
+
+template <class O>
+static hipError_t stitch_blend(const float* d_tiles, int tilesX, int tile0, int oth, int otw, const int32_t* d_rows, const int32_t* d_cols,
+                               int OH, int OW, bool swap_rb, BlendQ q, O* d_out, hipStream_t st) {
+    if (OH <= 0 || OW <= 0 || !d_tiles || !d_rows || !d_cols || !d_out) return hipErrorInvalidValue;
+    if ((uintptr_t)d_out & ((OW & 3) ? sizeof(O) - 1 : 4 * sizeof(O) - 1)) return hipErrorInvalidValue;   // the kernel's 4-pixel stores
+    const size_t total = (size_t)OH * ((OW + 3) >> 2);
+    hipLaunchKernelGGL((stitch_blend_kernel<O>), dim3(grid_for(total, 8192)), dim3(256), 0, st, d_tiles, oth, otw, d_rows, d_cols, tilesX, tile0,
+                       OH, OW, swap_rb ? 1 : 0, q, d_out);
+    return hipGetLastError();
+}
+hipError_t launch_stitch_blend(const float* d_tiles, int tilesX, int tile0, int oth, int otw, const int32_t* d_rows, const int32_t* d_cols,
+                               int OH, int OW, bool swap_rb, uint8_t* d_out, hipStream_t st) {
+    return stitch_blend(d_tiles, tilesX, tile0, oth, otw, d_rows, d_cols, OH, OW, swap_rb, BlendQ{0, 255.f}, d_out, st);
+}
+hipError_t launch_stitch_blend(const float* d_tiles, int tilesX, int tile0, int oth, int otw, const int32_t* d_rows, const int32_t* d_cols,
+                               int OH, int OW, int lo, int hi, uint16_t* d_out, hipStream_t st) {
+    return stitch_blend(d_tiles, tilesX, tile0, oth, otw, d_rows, d_cols, OH, OW, false, BlendQ{lo, (float)(hi - lo)}, d_out, st);
+}
+hipError_t launch_stitch_blend(const float* d_tiles, int tilesX, int tile0, int oth, int otw, const int32_t* d_rows, const int32_t* d_cols,
+                               int OH, int OW, float* d_out, hipStream_t st) {
+    return stitch_blend(d_tiles, tilesX, tile0, oth, otw, d_rows, d_cols, OH, OW, false, BlendQ{0, 1.f}, d_out, st);
+}
+
 }  // namespace s2sr

@@ -351,6 +351,16 @@ hipError_t launch_stitch(const float* d_tiles, int tilesX, int oth, int otw, con
 // OW must be a multiple of 4 and d_out 8-byte aligned (hipErrorInvalidValue otherwise).
 hipError_t launch_stitch_quant_u16(const float* d_tiles, int tilesX, int tile0, int oth, int otw, const int32_t* d_rowmap,
                                    const int32_t* d_colmap, int OH, int OW, int lo, int hi, uint16_t* d_out, hipStream_t st);
+// seam-blended stitch (blend_plan.h): planar fp32 tiles -> OH rows of an HWC image, cross-faded inside the ramps of the blend tables
+// d_rows (already at the band's first row, d_out likewise) and d_cols; window (ty, tx) is tile ty * tilesX + tx - tile0 of d_tiles
+// (tile0 may be negative: a buffer with rows in front of the chunk's).  u8: trunc(clip(v * 255, 0, 255)), optionally with R and B
+// exchanged; u16: lo + rint(clamp(v, 0, 1) * (hi - lo)); fp32: v.
+hipError_t launch_stitch_blend(const float* d_tiles, int tilesX, int tile0, int oth, int otw, const int32_t* d_rows, const int32_t* d_cols,
+                               int OH, int OW, bool swap_rb, uint8_t* d_out, hipStream_t st);
+hipError_t launch_stitch_blend(const float* d_tiles, int tilesX, int tile0, int oth, int otw, const int32_t* d_rows, const int32_t* d_cols,
+                               int OH, int OW, int lo, int hi, uint16_t* d_out, hipStream_t st);
+hipError_t launch_stitch_blend(const float* d_tiles, int tilesX, int tile0, int oth, int otw, const int32_t* d_rows, const int32_t* d_cols,
+                               int OH, int OW, float* d_out, hipStream_t st);
 
 // post-process kernels (postprocess.hip)
 hipError_t launch_postprocess(const uint8_t* d_rgb, int B, int H, int W, const s2sr_pp_params& prm, uint8_t* d_out,

@@ -133,6 +133,8 @@ _PROTOS = {
     "s2sr_forward_batch_u16_dev": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
     "s2sr_enhance_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]),
     "s2sr_enhance_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "s2sr_enhance_blend_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(PPParams), C.c_int32, C.c_void_p, C.c_void_p]),
+    "s2sr_enhance_blend_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]),
     "s2sr_enhance_job_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PPParams), C.c_void_p]),
     "s2sr_enhance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tile_process_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -179,6 +181,7 @@ _PROTOS = {
     "s2sr_debug_mosaic_patches": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_int64)] * 2),
     "s2sr_debug_plan_chunks": (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "s2sr_debug_plan_windows": (C.c_int, [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "s2sr_debug_plan_blend": (C.c_int, [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]),
     "s2sr_debug_get_config": (C.c_int, [C.c_void_p, C.POINTER(DebugConfig)]),
     "s2sr_debug_conv_trunk": (C.c_int, [C.c_void_p, C.POINTER(DebugTrunkArgs)]),
     "s2sr_debug_forward_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(DebugTaps)]),
@@ -398,6 +401,17 @@ def plan_windows(PH: int, PW: int, tile: int, pad: int, scale: int = 4, tiled: b
         raise S2srError(f"s2sr_debug_plan_windows failed ({_ERR.get(rc, rc)})")
     nx, ny, wh, ww = (int(v) for v in dims)
     return nx, ny, wh, ww, rects[:nx * ny if tiled else 0], rm, cm
+
+
+def plan_blend(PH: int, PW: int, tile: int, pad: int, scale: int = 4, tiled: bool = True) -> tuple:
+    """(rows[scale * PH, 6], cols[scale * PW, 6]): the blend tables of enhance_blend_* for plan_windows' job, per output row /
+    column {a, ia, b, ib, num, den} -- the two windows, the row / column inside each one's output and the weight num / den of b
+    (0 / 1 outside the ramps, where a == b); host arithmetic, works without a GPU."""
+    rows, cols = np.zeros((scale * PH, 6), np.int32), np.zeros((scale * PW, 6), np.int32)
+    rc = load_library().s2sr_debug_plan_blend(PH, PW, tile, pad, scale, int(tiled), _ptr(rows), _ptr(cols))
+    if rc:
+        raise S2srError(f"s2sr_debug_plan_blend failed ({_ERR.get(rc, rc)})")
+    return rows, cols
 
 
 def _ptr(a: np.ndarray):
@@ -641,6 +655,33 @@ class Engine:
         f = np.empty((4 * H, 4 * W, 3), dtype=np.float32) if want_f32 else None
         self._check(self._lib.s2sr_enhance_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), _ptr(out), _ptr(f) if want_f32 else None),
                     "s2sr_enhance_u16")
+        return (out, f) if want_f32 else out
+
+    # -- the seam-blended stitch (include/s2sr.h: the default doors' windows, cross-faded where they overlap) -------------------
+    def enhance_blend_u8(self, img: np.ndarray, prm: Optional[PPParams] = None, swap_rb: bool = False, tile: int = 256, pad: int = 10,
+                         want_f32: bool = False):
+        """enhance_u8 (prm None, swap_rb False) or enhance_job_u8 (swap_rb True) with the blended paste; want_f32 (plain calls
+        only): (the u8 image, the unquantised HWC float32 image)."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        H, W, c = img.shape
+        assert c == 3
+        out = pinned_pool.empty((self.scale * H, self.scale * W, 3), np.uint8)
+        f = np.empty((self.scale * H, self.scale * W, 3), dtype=np.float32) if want_f32 else None
+        self._check(self._lib.s2sr_enhance_blend_u8(self._h, _ptr(img), H, W, tile, pad, C.byref(prm) if prm is not None else None,
+                                                    int(bool(swap_rb)), _ptr(out), _ptr(f) if want_f32 else None), "s2sr_enhance_blend_u8")
+        return (out, f) if want_f32 else out
+
+    def enhance_blend_u16(self, img: np.ndarray, lo: int = 0, hi: int = 65535, tile: int = 256, pad: int = 10, want_f32: bool = False):
+        """enhance_u16 with the blended paste."""
+        if np.asarray(img).dtype != np.uint16:
+            raise TypeError(f"enhance_blend_u16 takes a uint16 image, got {np.asarray(img).dtype}")
+        img = np.ascontiguousarray(img)
+        H, W, c = img.shape
+        assert c == 3
+        out = pinned_pool.empty((4 * H, 4 * W, 3), np.uint16)
+        f = np.empty((4 * H, 4 * W, 3), dtype=np.float32) if want_f32 else None
+        self._check(self._lib.s2sr_enhance_blend_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), _ptr(out),
+                                                     _ptr(f) if want_f32 else None), "s2sr_enhance_blend_u16")
         return (out, f) if want_f32 else out
 
     # -- multi-GPU building blocks (device pointers) ------------------------------------------
