@@ -250,6 +250,25 @@ int  s2sr_enhance_blend_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_
 int  s2sr_enhance_blend_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo,
                             int32_t hi, uint16_t* out_u16 /* [4H,4W,3] or NULL */, float* out_f32 /* [4H,4W,3] or NULL */);
 
+/* Display rendering of a 16-bit image: the two passes over a uint16 [H, W, 3] interleaved image that reduce it to
+ * the 8-bit image the PNG writer, the warp, the pyramid and the post-process take.  Neither entry needs weights.  What lies between
+ * them -- percentile limits from the histogram, the stretch LUT -- is the caller's (s2sr/display.py).
+ * hist:  hist[c][v] = the exact number of samples of channel c with value v, the samples equal to nodata (0..65535; -1: none)
+ *   left out.
+ * apply: out[y, x, c] = lut[c][img[y, x, c]], lut = uint8 [3][65536].
+ * img == NULL in either entry: the uint16 image of exactly H x W that the previous call on this handle left on the device -- the
+ *   uploaded copy of a host-image display call, or the x4 image of s2sr_enhance_u16 / s2sr_enhance_blend_u16 called with out_u16
+ *   (pass their 4H, 4W).  Any other call on the handle in between invalidates the copy.
+ * band_rows (0: the library's choice, ~32 MB) sets the row bands the passes work in; for a host image band i + 1 uploads under
+ *   band i's kernel and band i's output leaves under band i + 1's.  The result does not depend on it.
+ * Limits: a row holds at most 2^30 samples (W <= 357913941); counts are 64 bits wide and exact for every image.
+ * S2SR_E_INVALID with a text, before the device is touched: nodata outside -1..65535, non-positive H or W, band_rows < 0, a NULL
+ * hist / lut / out, and img == NULL without a device image of that size. */
+int  s2sr_display_hist_u16(s2sr_handle* h, const uint16_t* img /* or NULL */, int32_t H, int32_t W, int32_t nodata, int32_t band_rows,
+                           uint64_t* hist /* [3][65536] */);
+int  s2sr_display_apply_u16(s2sr_handle* h, const uint16_t* img /* or NULL */, int32_t H, int32_t W, const uint8_t* lut /* [3][65536] */,
+                            int32_t band_rows, uint8_t* out /* [H,W,3] */);
+
 /* Multi-GPU building blocks of _tile_process (cnn_super_resolution.py:244-278), device-resident:
  * cut windows [first, first+count) of the plan into d_tiles [count, wh, ww, 3] (wh/ww = the
  * plan's common window size), and paste ALL T windows' outputs d_tiles [T, 4wh, 4ww, 3] into

@@ -367,15 +367,19 @@ class RealESRGAN:
         if img.dtype != np.uint8:
             # the reference divides whatever it gets by 255 (:220); only u8 is on the native path
             raise TypeError(f"expected uint8 image, got {img.dtype}")
-        if self.seam_blend:
-            return self._engine.enhance_blend_u8(img, tile=self.tile_size, pad=self.tile_pad)
-        return self._engine.enhance_u8(img, tile=self.tile_size, pad=self.tile_pad)
+        with self._engine.chain_lock:        # (not between another job's enhance16 and its display rendering)
+            if self.seam_blend:
+                return self._engine.enhance_blend_u8(img, tile=self.tile_size, pad=self.tile_pad)
+            return self._engine.enhance_u8(img, tile=self.tile_size, pad=self.tile_pad)
 
-    def enhance16(self, img: np.ndarray, value_range=None) -> np.ndarray:
+    def enhance16(self, img: np.ndarray, value_range=None, display=None):
         """HxWx3 uint16 (channel order as given) -> 4Hx4Wx3 uint16, in the source's units: the 16-bit door of the native library
         (upstream RealESRGANer's max_range = 65535 branch; the reference has none).  value_range (lo, hi), None = (0, 65535): the
         net sees (clip(v, lo, hi) - lo) / (hi - lo), the output is lo + rint(clip(y, 0, 1) * (hi - lo)).  Same whole / tiled
-        switch and window plan as `enhance`.  The x4 RRDB models only (realesrgan_x4, realesrgan_anime)."""
+        switch and window plan as `enhance`.  The x4 RRDB models only (realesrgan_x4, realesrgan_anime).
+        display (a s2sr.display.Stretch or a dict of its fields): -> (out16, display_u8, info), the 8-bit display rendering of the
+        output (percentile stretch, s2sr/display.py) made from the output's device copy, without a second upload; per-band
+        limits are in the channel order of `img`."""
         if self.scale != 4 or getattr(self.model, "arch", "rrdb") != "rrdb":
             raise ValueError(f"enhance16 is built for the x4 RRDB models, not {self.model_name}")
         if img.ndim != 3 or img.shape[2] != 3:
@@ -385,9 +389,16 @@ class RealESRGAN:
         lo, hi = (0, 65535) if value_range is None else (int(value_range[0]), int(value_range[1]))
         if not (0 <= lo < hi <= 65535):
             raise ValueError(f"value_range {value_range}: need 0 <= lo < hi <= 65535")
-        if self.seam_blend:
-            return self._engine.enhance_blend_u16(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
-        return self._engine.enhance_u16(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
+        door = self._engine.enhance_blend_u16 if self.seam_blend else self._engine.enhance_u16
+        if display is None:
+            with self._engine.chain_lock:
+                return door(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
+        from s2sr.display import Stretch, render_u16
+        stretch = Stretch.of(display)
+        with self._engine.chain_lock:        # the engine is shared by every job of the process: nothing between the door and the rendering
+            out16 = door(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
+            disp, info = render_u16(None, stretch, self._engine, shape=out16.shape[:2])
+        return out16, disp, info
 
     def enhance_job(self, rgb: np.ndarray, post=None) -> np.ndarray:
         """What a job does around `enhance` (wow_sr.py:85-110, farm_sr.py:156-178) in one native call: RGB in, RGB2BGR, the net,
@@ -398,9 +409,10 @@ class RealESRGAN:
             raise ValueError(f"expected HxWx3 image, got shape {rgb.shape}")
         if rgb.dtype != np.uint8:
             raise TypeError(f"expected uint8 image, got {rgb.dtype}")
-        if self.seam_blend:
-            return self._engine.enhance_blend_u8(rgb, post, swap_rb=True, tile=self.tile_size, pad=self.tile_pad)
-        return self._engine.enhance_job_u8(rgb, post, tile=self.tile_size, pad=self.tile_pad)
+        with self._engine.chain_lock:
+            if self.seam_blend:
+                return self._engine.enhance_blend_u8(rgb, post, swap_rb=True, tile=self.tile_size, pad=self.tile_pad)
+            return self._engine.enhance_job_u8(rgb, post, tile=self.tile_size, pad=self.tile_pad)
 
     def _tile_process(self, img: torch.Tensor) -> torch.Tensor:
         """[1,3,H,W] float in [0,1] -> [1,3,sH,sW] float32 (s = self.scale) through the tiled path (:236-280)."""

@@ -41,6 +41,8 @@ class WowRequest(BaseModel):         # main.py:200-208
     max_cloud_cover: float = 30.0
     force_fetch: bool = False
     seam_blend: bool = False         # not in the reference: cross-fade the window overlaps of the tiled stitch
+    bit_depth: int = 8               # not in the reference: 16 = a uint16 GeoTIFF through the net in its own units (app.wow_sr)
+    display: Optional[dict] = None   # ... and its 8-bit rendering for the PNG and the tiles (fields of s2sr.display.Stretch); 16-bit jobs only
 
 
 class SRResponse(BaseModel):         # main.py:230-235
@@ -189,17 +191,21 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
         tifs = sorted(source_dir.glob("*.tif"), key=lambda x: x.stat().st_mtime, reverse=True)
         return tifs[0] if tifs else None
 
-    def _default_tiler(sr_tif, tiles_dir):
+    def _default_tiler(sr_tif, tiles_dir, stretch=None):
         from app.tiling import process_raster_to_tiles
         process_raster_to_tiles(input_path=sr_tif, tiles_dir=tiles_dir, min_zoom=tile_min_zoom,
-                                max_zoom=min(tile_max_zoom + 2, 20))          # "Higher zoom for SR" (main.py:276)
+                                max_zoom=min(tile_max_zoom + 2, 20),          # "Higher zoom for SR" (main.py:276)
+                                **({"stretch": stretch} if stretch is not None else {}))
 
-    def _tile(result, sub):
+    def _tile(result, sub, stretch=None):
         sr_tif = result["outputs"].get("sr_tif")
         run = _default_tiler if tiler is None else tiler
         if run and sr_tif and Path(sr_tif).exists():
             tiles_dir = data_dir / sub
-            run(Path(sr_tif), tiles_dir)
+            if tiler is None and stretch is not None:
+                run(Path(sr_tif), tiles_dir, stretch)
+            else:
+                run(Path(sr_tif), tiles_dir)
             result["tiles_dir"] = str(tiles_dir)
 
     def run_sr_job(job_id, input_file, scale, model, output_dir, seam_blend=False):          # main.py:247-287
@@ -214,7 +220,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             _set(job_id, status="failed", message=str(e))
 
     def run_wow_job(job_id, input_file, output_dir, enhance_crops, auto_fetch=True, max_age_days=30,
-                    max_cloud_cover=30.0, force_fetch=False, model="realesrgan_x4", seam_blend=False):   # main.py:290-368
+                    max_cloud_cover=30.0, force_fetch=False, model="realesrgan_x4", seam_blend=False, bit_depth=8,
+                    display=None):                                           # main.py:290-368
         try:
             if input_file is None and auto_fetch:
                 _set(job_id, status="fetching",
@@ -224,14 +231,21 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                                        "pass input_file or plug a fetcher into create_app()")
                 input_file, fetch_metadata = fetcher(source_dir, max_age_days, max_cloud_cover, force_fetch)
                 _set(job_id, input_file=str(input_file), fetch_metadata=fetch_metadata)
-            display = {"realesrgan_x4": "Real-ESRGAN x4",
-                       "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)"}.get(model, model)
-            _set(job_id, status="processing", message=f"Stage 1/2: {display} (GAN upscaling)...")
+            model_display = {"realesrgan_x4": "Real-ESRGAN x4",
+                             "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)"}.get(model, model)
+            _set(job_id, status="processing", message=f"Stage 1/2: {model_display} (GAN upscaling)...")
             from app.wow_sr import process_wow_sr
-            result = process_wow_sr(input_tif=input_file, output_dir=output_dir, enhance_crops=enhance_crops, model=model,
-                                    **({"seam_blend": True} if seam_blend else {}))
+            extra = {"seam_blend": True} if seam_blend else {}
+            if bit_depth != 8:
+                extra["bit_depth"] = bit_depth
+            if display is not None:
+                extra["display"] = display
+            result = process_wow_sr(input_tif=input_file, output_dir=output_dir, enhance_crops=enhance_crops, model=model, **extra)
             _set(job_id, status="tiling", message="Generating tiles from WOW SR image...")
-            _tile(result, "tiles_wow")
+            # a 16-bit job's tiles show the rendering of its PNG: the job's stretch with the limits it found
+            info = result.get("sr_metadata", {}).get("display") if display is not None else None
+            _tile(result, "tiles_wow", stretch=None if info is None else
+                  {k: info[k] for k in ("p_lo", "p_hi", "linked", "gamma", "nodata", "limits")})
             _set(job_id, status="completed", message="WOW Super-resolution complete!", result=result)
         except Exception as e:                                               # noqa: BLE001
             _set(job_id, status="failed", message=str(e))
@@ -285,6 +299,16 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             if input_file is None:
                 raise HTTPException(status_code=404,
                                     detail="No GeoTIFF files found. Enable auto_fetch=true or run fetch first.")
+        if request.bit_depth not in (8, 16):
+            raise HTTPException(status_code=400, detail="bit_depth must be 8 or 16")
+        if request.display is not None:
+            if request.bit_depth != 16:
+                raise HTTPException(status_code=400, detail="display is the 8-bit rendering of a 16-bit job: pass bit_depth=16")
+            try:
+                from s2sr.display import Stretch
+                Stretch.of(request.display)
+            except (ValueError, TypeError) as e:
+                raise HTTPException(status_code=400, detail=f"display: {e}")
         job_id = f"wow_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
         output_dir = data_dir / "wow" / job_id
         output_dir.mkdir(parents=True, exist_ok=True)
@@ -297,7 +321,9 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                                "output_dir": str(output_dir), "created_at": datetime.now().isoformat()}
         background_tasks.add_task(run_wow_job, job_id, input_file, output_dir, request.enhance_crops,
                                   request.auto_fetch, request.max_age_days, request.max_cloud_cover, request.force_fetch,
-                                  **({"seam_blend": True} if request.seam_blend else {}))
+                                  **({"seam_blend": True} if request.seam_blend else {}),
+                                  **({"bit_depth": request.bit_depth} if request.bit_depth != 8 else {}),
+                                  **({"display": request.display} if request.display is not None else {}))
         msg = (f"WOW SR started: {input_file.name} -> Real-ESRGAN x4 + Enhanced" if input_file else
                f"WOW SR started: auto-fetching best image (last {request.max_age_days}d, cloud <={request.max_cloud_cover}%)")
         return SRResponse(job_id=job_id, status="queued", message=msg)

@@ -132,14 +132,27 @@ def _mercator_tags(place: geo.Placement) -> rio.GeoRef:
                        rio.TAG_GEOKEYS: (1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 3072, 0, 1, 3857)})
 
 
-def reproject_to_web_mercator(input_path: Path, output_path: Path, resample_method: str = "bilinear") -> Path:
+def _rgb_u8(arr: np.ndarray, stretch=None) -> np.ndarray:
+    """Bands 1-3 (the single band three times) as the 8-bit image the warp and the pyramid take: the reference's global min-max
+    (rasterio_lite._to_u8), or -- a uint16 raster with `stretch` (s2sr.display.Stretch or a dict of its fields) -- its display
+    rendering, made on the device (pass the `limits` of a job's metadata to get the rendering of the job's PNG)."""
+    rgb = arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2)
+    if stretch is None or arr.dtype != np.uint16:
+        return rio._to_u8(rgb, 0.0)
+    from s2sr.display import render_u16
+    eng, lock = _engine_and_lock()
+    with lock:
+        return render_u16(np.ascontiguousarray(rgb), stretch, eng)[0]
+
+
+def reproject_to_web_mercator(input_path: Path, output_path: Path, resample_method: str = "bilinear", stretch=None) -> Path:
     """Writes an RGB GeoTIFF on the EPSG:3857 grid (pixels outside the source are black; the tile
-    generator recomputes coverage from the geometry, so no alpha band is stored)."""
+    generator recomputes coverage from the geometry, so no alpha band is stored).  stretch: see _rgb_u8."""
     if resample_method != "bilinear":
         raise ValueError("only bilinear resampling is implemented (the reference never passes anything else)")
     input_path, output_path = Path(input_path), Path(output_path)
     arr, _tags, place, crs = _read(input_path)
-    rgb = rio._to_u8(arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2), 0.0)
+    rgb = _rgb_u8(arr, stretch)
     plan = tiles.plan_warp(rgb.shape[1], rgb.shape[0], place, crs)
     eng, lock = _engine_and_lock()
     with lock:                   # the engine's scratch holds a pyramid chain's previous level (see _cut_pyramid)
@@ -237,8 +250,9 @@ def create_tileset_metadata(tiles_dir: Path, bounds_4326: list, min_zoom: int, m
 
 
 def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 10, max_zoom: int = 16, resampling: str = "average",
-                            tile_template: str = "/tiles/{z}/{x}/{y}.png") -> dict:
-    """Check the CRS, reproject if needed, cut the pyramid, write tileset.json."""
+                            tile_template: str = "/tiles/{z}/{x}/{y}.png", stretch=None) -> dict:
+    """Check the CRS, reproject if needed, cut the pyramid, write tileset.json.  stretch (uint16 rasters; ignored for uint8): the
+    8-bit image is the raster's display rendering instead of the global min-max, see _rgb_u8."""
     import time
     _check_tile_args(256, resampling)
     input_path, tiles_dir = Path(input_path), Path(tiles_dir)
@@ -252,7 +266,7 @@ def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 1
     ey = np.concatenate([np.full(21, north), north - (north - south) * t, np.full(21, south), south + (north - south) * t])
     lon, lat = crs.to_lonlat(ex, ey)
     bounds_4326 = [float(lon.min()), float(lat.min()), float(lon.max()), float(lat.max())]
-    rgb = rio._to_u8(arr[..., :3] if b >= 3 else np.repeat(arr[..., :1], 3, axis=2), 0.0)
+    rgb = _rgb_u8(arr, stretch)
     t1 = time.perf_counter()
     LAST_STATS["read"] = t1 - t0
     side, err = None, []

@@ -35,11 +35,18 @@ def _enhance_for_crops(img: np.ndarray) -> np.ndarray:
     return _pp_engine().postprocess_u8(img, native.pp_wow())
 
 
-def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend: bool = False) -> Tuple[Path, dict]:
+def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend: bool = False, display=None,
+                    enhance_crops: bool = False) -> Tuple[Path, dict]:
     """bit_depth=16 of apply_wow_sr: a uint16 GeoTIFF read raw, value_range = the image's own (min, max) -- the reference's
     min-max (wow_sr.py:67-73) minus its quantisation to 8 bits -- the net fed BGR as ever (:85,94), RealESRGAN.enhance16, RGB back,
-    a uint16 GeoTIFF out.  No PNG (the encoder is 8-bit) and no crop-visibility post-process (OpenCV's 8-bit arithmetic)."""
+    a uint16 GeoTIFF out.  Without `display`: no PNG (the encoder is 8-bit) and no crop-visibility post-process (OpenCV's 8-bit
+    arithmetic).  With it (s2sr.display.Stretch or a dict of its fields): the output's display rendering, made on the device from
+    the output's copy there, is written as the PNG, after the crop-visibility post-process when enhance_crops; the GeoTIFF stays raw."""
+    import dataclasses
+
     from s2sr import rasterio_lite as rio
+    from s2sr.display import Stretch
+    stretch = None if display is None else Stretch.of(display)
 
     input_path = Path(input_path)
     print(f"\nWOW Super-Resolution ({model}, 16-bit)\n   Input: {input_path}")
@@ -53,20 +60,35 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     if hi == lo:                      # a constant raster: any range that contains it
         lo, hi = (lo - 1, hi) if hi > 0 else (0, 1)
     esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}))
-    out_bgr = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi))
+    display_rgb = info = None
+    if stretch is None:
+        out_bgr = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi))
+    else:
+        # the device copy is BGR like the net's input: explicit per-band limits go in reversed, the info's come back reversed
+        bgr = stretch if stretch.limits is None else dataclasses.replace(stretch, limits=stretch.limits[::-1])
+        out_bgr, disp_bgr, info = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), display=bgr)
+        display_rgb = np.ascontiguousarray(disp_bgr[:, :, ::-1])
+        info = dict(info, limits=info["limits"][::-1])
+        if enhance_crops:
+            print("   Stage 2/2: Crop visibility enhancement (on the display image)...")
+            display_rgb = _enhance_for_crops(display_rgb)
     output_rgb = np.ascontiguousarray(out_bgr[:, :, ::-1])
     scale = esrgan.scale
     del esrgan
     final_output = Path(output_path).with_suffix(".tif")
     final_output.parent.mkdir(parents=True, exist_ok=True)
     rio.write_geotiff_rgb16(final_output, output_rgb, georef.scaled(scale))
+    if display_rgb is not None:
+        rio.write_png(final_output.with_suffix(".png"), display_rgb)
+    crops = display_rgb is not None and enhance_crops
     metadata = {
         "input_file": str(input_path),
         "output_file": str(final_output),
         "scale": scale,
         "pipeline": "Real-ESRGAN x4 (16-bit)",
-        "stages": [{"model": model, "scale": scale, "purpose": "GAN upscaling"}],
-        "enhancements": [],
+        "stages": [{"model": model, "scale": scale, "purpose": "GAN upscaling"}] +
+                  ([{"post_processing": "Enhanced", "purpose": "Crop visibility"}] if crops else []),
+        "enhancements": ["CLAHE local contrast", "Unsharp mask", "Vegetation boost"] if crops else [],
         "original_size": list(img.shape[:2]),
         "output_size": list(output_rgb.shape[:2]),
         "original_resolution_m": 10.0,
@@ -77,27 +99,37 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     }
     if seam_blend:
         metadata["seam_blend"] = True
+    if info is not None:
+        metadata["display"] = info
     return final_output, metadata
 
 
-def _check_bit_depth(bit_depth: int, enhance_crops: bool) -> None:
+def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None) -> None:
     if bit_depth not in (8, 16):
         raise ValueError(f"bit_depth {bit_depth!r}: 8 or 16")
-    if bit_depth == 16 and enhance_crops:
-        raise ValueError("bit_depth=16 has no crop-visibility post-process (it is OpenCV's 8-bit arithmetic by definition): pass enhance_crops=False")
+    if display is not None:
+        if bit_depth != 16:
+            raise ValueError("display is the 8-bit rendering of a 16-bit job: pass bit_depth=16 (an 8-bit job's image is its display image)")
+        from s2sr.display import Stretch
+        Stretch.of(display)              # refuses a bad stretch here, before anything is created
+    elif bit_depth == 16 and enhance_crops:
+        raise ValueError("bit_depth=16 has no crop-visibility post-process (it is OpenCV's 8-bit arithmetic by definition): pass enhance_crops=False, "
+                         "or display=... to run it on the display image")
 
 
 def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True,
-                 model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False) -> Tuple[Path, dict]:
+                 model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None) -> Tuple[Path, dict]:
     """Reference wow_sr.py:28-184 -- same outputs (GeoTIFF and/or PNG) and metadata dict.  bit_depth=16 (not in the reference): a
     uint16 GeoTIFF goes through the net without the 8-bit squeeze and comes back as a uint16 GeoTIFF (_apply_wow_sr16).
+    display (bit_depth=16 only; a s2sr.display.Stretch or a dict of its fields): the job also writes the PNG, from the output's
+    display rendering (percentile stretch); enhance_crops then runs on that image; the metadata gains "display", and only then.
     seam_blend (not in the reference): the tiled stitch cross-fades the window overlaps (RealESRGAN(seam_blend=True)); the metadata
     gains "seam_blend": true, and only then."""
     from s2sr import rasterio_lite as rio
 
-    _check_bit_depth(bit_depth, enhance_crops)
+    _check_bit_depth(bit_depth, enhance_crops, display)
     if bit_depth == 16:
-        return _apply_wow_sr16(input_path, output_path, model, seam_blend)
+        return _apply_wow_sr16(input_path, output_path, model, seam_blend, display, enhance_crops)
 
     model_display = {"realesrgan_x4": "Real-ESRGAN x4",
                      "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)",
@@ -159,10 +191,10 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
 
 
 def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True,
-                   model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False) -> dict:
+                   model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None) -> dict:
     """Reference wow_sr.py:212-266 -- file naming, metadata JSON and result dict schema.  bit_depth=16: see apply_wow_sr (no PNG:
-    "sr_png" is None).  seam_blend: see apply_wow_sr."""
-    _check_bit_depth(bit_depth, enhance_crops)          # before anything is created
+    "sr_png" is None -- unless `display` is given: the PNG is the output's display rendering).  seam_blend: see apply_wow_sr."""
+    _check_bit_depth(bit_depth, enhance_crops, display)          # before anything is created
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
@@ -170,8 +202,11 @@ def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True
     png = wow_tif.with_suffix(".png")
     blend = {"seam_blend": True} if seam_blend else {}   # (tests patch apply_wow_sr with the reference's signature)
     if bit_depth == 16:
+        if display is not None:
+            blend["display"] = display
         _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model, bit_depth=16, **blend)
-        png = None       # (a PNG an earlier 8-bit job left under this name is not this job's output)
+        if display is None:
+            png = None   # (a PNG an earlier 8-bit job left under this name is not this job's output)
     else:
         _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model, **blend)
     result = {

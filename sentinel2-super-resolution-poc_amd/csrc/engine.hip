@@ -530,6 +530,7 @@ bool recover_stream(s2sr_handle* h) {
 int ensure_scratch(s2sr_handle* h, int slot, size_t bytes) {
     h->tiles_slot = -1;                  // whoever asks for scratch is about to overwrite it; the pyramid calls set it again
     h->warp_slot = -1;
+    h->disp_slot = -1;
     if (slot == 5) h->ppb.open = false;  // ... and a banded post-process run lives there: void it (pp_band_begin_locked opens its own afterwards)
     if (h->scratch_bytes[slot] >= bytes) return S2SR_OK;
     if (h->d_scratch[slot]) {

@@ -666,6 +666,7 @@ static int enhance16_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int
     }
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     HIPCHK(h, hipStreamSynchronize(st));
+    if (out_u16) { h->disp_slot = 1; h->disp_h = OH; h->disp_w = OW; }   // the x4 image also stays on the device, for s2sr_display_*_u16
     return S2SR_OK;
 }
 
@@ -826,6 +827,7 @@ static int enhance_blend_impl(s2sr_handle* h, const BlendCall& c, int H, int W, 
     }
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     HIPCHK(h, hipStreamSynchronize(st));
+    if (in16 && c.out_u16) { h->disp_slot = 1; h->disp_h = OH; h->disp_w = OW; }   // as enhance16_impl
     return S2SR_OK;
 }
 

@@ -1,4 +1,4 @@
-// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_debug.hip): the handle behind
+// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_display.hip, engine_debug.hip): the handle behind
 // the C ABI of include/s2sr.h, the types it is made of, and the helpers that more than one of those files uses.  What a single
 // file uses stays static or anonymous in that file.
 #pragma once
@@ -50,10 +50,10 @@ struct ConvW {
 };
 
 // kernel families for the HIP-event statistics
-enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_COUNT };
+enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_DHIST, F_DAPPLY, F_COUNT };
 inline constexpr const char* kFamName[F_COUNT] = {"pack_u8",   "conv_first", "rdb_conv1-4", "rdb_conv5",   "conv_body",
                                  "conv_up",   "conv_hr",    "conv_last",   "postprocess", "misc",
-                                 "compact_first", "compact_body", "compact_last"};
+                                 "compact_first", "compact_body", "compact_last", "display_hist", "display_apply"};
 
 inline constexpr int kRoleFam[kRoles] = {F_FIRST, F_RDB14, F_RDB5, F_RDB5, F_BODY, F_UP, F_UP, F_HR, F_LAST, F_CFIRST, F_CBODY, F_CLAST};   // by Role
 
@@ -188,6 +188,8 @@ struct s2sr_handle {
     int tiles_slot = -1;                 // scratch slot that still holds the tile level the last pyramid call produced (-1: none)
     int tiles_nx = 0, tiles_ny = 0;
     int warp_slot = -1, warp_h = 0, warp_w = 0;   // ... and the RGBA raster the last warp produced (s2sr_tiles_base_u8 with rgba == NULL)
+    int disp_slot = -1, disp_h = 0, disp_w = 0;   // ... and the uint16 [disp_h, disp_w, 3] image the 16-bit enhance doors (x4, scratch 1) or a
+                                                  // display call (its upload, scratch 0) left there (s2sr_display_*_u16 with img == NULL)
     // profiling
     int prof = 0;                 // 0 off, N>=1: bracket every N-th launch of each family with events
     bool span_on = false;         // a sampled span of consecutive launches of ONE family is open (span_begin / span_end): its launches

@@ -261,6 +261,12 @@ size_t conv_wpack_bytes_phase(int cin, int cout);
 hipError_t launch_conv_phase(const ConvParams& p, int row_parity, hipStream_t st, bool f8);
 uint8_t f32_to_e4m3(float f);   // OCP e4m3fn, round to nearest even, saturating at +-448
 
+// display rendering of 16-bit images (display.hip): the samples [s0, s1) of a uint16 [H, W, 3] image (a band of whole rows; at
+// most 2^30 for the histogram).  d_img: 16-byte aligned and readable up to the next multiple of 16 bytes behind its last sample;
+// d_out is addressed from the image's first sample like d_img.  hist: uint64 [3][65536], added to; nodata -1: none.
+hipError_t launch_display_hist(const uint16_t* d_img, size_t s0, size_t s1, int nodata, unsigned long long* d_hist, hipStream_t st);
+hipError_t launch_display_apply(const uint16_t* d_img, size_t s0, size_t s1, const uint8_t* d_lut, uint8_t* d_out, hipStream_t st);
+
 // XYZ tile pyramid (tiles.hip)
 hipError_t launch_warp_bilinear(const uint8_t* d_rgb, int H, int W, const float* d_grid, int gh, int gw, int step, int OH, int OW,
                                 uint8_t* d_out, hipStream_t st);

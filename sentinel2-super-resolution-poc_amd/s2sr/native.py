@@ -135,6 +135,8 @@ _PROTOS = {
     "s2sr_enhance_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_enhance_blend_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(PPParams), C.c_int32, C.c_void_p, C.c_void_p]),
     "s2sr_enhance_blend_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]),
+    "s2sr_display_hist_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
+    "s2sr_display_apply_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "s2sr_enhance_job_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PPParams), C.c_void_p]),
     "s2sr_enhance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tile_process_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -507,6 +509,9 @@ class Engine:
         PREC_F16 and PREC_F16_HP run the same arithmetic there, PREC_FP8 is refused."""
         self._lib = load_library()
         self._h = C.c_void_p()
+        # held by callers across calls that depend on what the call before left on the device (enhance_u16 -> display_*_u16 with
+        # img=None): the library serialises single calls, not such pairs
+        self.chain_lock = threading.RLock()
         if arch not in _ARCH:
             raise ValueError(f"arch {arch!r}: 'rrdb' or 'compact'")
         self.arch = arch
@@ -683,6 +688,41 @@ class Engine:
         self._check(self._lib.s2sr_enhance_blend_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), _ptr(out),
                                                      _ptr(f) if want_f32 else None), "s2sr_enhance_blend_u16")
         return (out, f) if want_f32 else out
+
+    # -- display rendering of 16-bit images (include/s2sr.h; policy between the two passes: s2sr/display.py) ---------------------
+    @staticmethod
+    def _display_source(img, shape, what: str):
+        if img is None:
+            if shape is None:
+                raise ValueError(f"{what}: img=None (the device copy) needs shape=(H, W)")
+            return None, int(shape[0]), int(shape[1])
+        if np.asarray(img).dtype != np.uint16:
+            raise TypeError(f"{what} takes a uint16 image, got {np.asarray(img).dtype}")
+        img = np.ascontiguousarray(img)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"{what}: expected HxWx3, got shape {img.shape}")
+        return img, img.shape[0], img.shape[1]
+
+    def display_hist_u16(self, img: Optional[np.ndarray], nodata: int = -1, band_rows: int = 0, shape=None) -> np.ndarray:
+        """HxWx3 uint16 -> uint64 [3][65536]: samples per channel and value, those equal to nodata (-1: none) left out.  img None: the
+        uint16 image of `shape` (H, W) the previous call on this engine left on the device (enhance_u16 / enhance_blend_u16: their
+        4H x 4W output; a display call: its upload)."""
+        img, H, W = self._display_source(img, shape, "display_hist_u16")
+        hist = np.empty((3, 65536), np.uint64)
+        self._check(self._lib.s2sr_display_hist_u16(self._h, _ptr(img) if img is not None else None, H, W, int(nodata), int(band_rows),
+                                                    _ptr(hist)), "s2sr_display_hist_u16")
+        return hist
+
+    def display_apply_u16(self, img: Optional[np.ndarray], lut: np.ndarray, band_rows: int = 0, shape=None) -> np.ndarray:
+        """out[y, x, c] = lut[c][img[y, x, c]], lut uint8 [3][65536]; img None as in display_hist_u16."""
+        img, H, W = self._display_source(img, shape, "display_apply_u16")
+        lut = np.ascontiguousarray(lut)
+        if lut.dtype != np.uint8 or lut.shape != (3, 65536):
+            raise ValueError(f"display_apply_u16: lut must be uint8 [3][65536], got {lut.dtype} {lut.shape}")
+        out = np.empty((H, W, 3), np.uint8) if H > 0 and W > 0 else np.empty((1,), np.uint8)
+        self._check(self._lib.s2sr_display_apply_u16(self._h, _ptr(img) if img is not None else None, H, W, _ptr(lut), int(band_rows),
+                                                     _ptr(out)), "s2sr_display_apply_u16")
+        return out
 
     # -- multi-GPU building blocks (device pointers) ------------------------------------------
     def cut_windows_u8_dev(self, d_img: int, H: int, W: int, tile: int, pad: int, first: int, count: int,
