@@ -214,7 +214,8 @@ int  s2sr_tile_process_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_
 int  s2sr_forward_batch_u16(s2sr_handle* h, const uint16_t* tiles, int32_t B, int32_t th, int32_t tw, int32_t lo, int32_t hi,
                             uint16_t* out_u16 /* [B,4th,4tw,3] or NULL */, float* out_f32 /* [B,3,4th,4tw] or NULL */);
 /* same with device-resident input / output, asynchronous on `stream` (NULL = the default stream).  The fp32 tiles between the
- * net and the quantiser live in a scratch buffer of the handle: 48 B per output pixel, regrown when a larger batch arrives. */
+ * net and the quantiser live in a scratch buffer of the handle: 48 B per output pixel, regrown when a larger batch arrives.
+ * d_out_u16 must be 8-byte aligned (the quantiser stores four samples at a time; S2SR_E_HIP before anything is written to it). */
 int  s2sr_forward_batch_u16_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int32_t th, int32_t tw, int32_t lo, int32_t hi,
                                 void* d_out_u16, void* stream);
 /* RealESRGAN.enhance for a 16-bit raster: HxWx3 u16 -> out_u16 [4H,4W,3] u16 and / or out_f32 [4H,4W,3] fp32 (the unquantised
@@ -635,6 +636,35 @@ typedef struct s2sr_debug_compact_fields {
 } s2sr_debug_compact_fields;
 int  s2sr_debug_compact_taps(s2sr_handle* h, const uint8_t* tiles, const float* x, int32_t B, int32_t th, int32_t tw,
                              int32_t job_windows, s2sr_debug_compact_fields* t);
+
+/* test hooks: red zones around the library's device allocations (csrc/redzone.h).  A diagnostic for stores that land in front
+ * of or behind the buffer they belong to -- allocator slack, a neighbouring workspace plane -- where no output comparison
+ * looks.  Reads past a buffer are not detected.  Process-wide; off by default, and then every allocation, pointer and byte is
+ * what it is without these entries.  The environment variable S2SR_REDZONE=<bytes>, read once when the library is loaded,
+ * sets the initial zone size (a value that is no number, or no multiple of 4096, is reported on stderr and leaves the mode
+ * off); with it set the process prints "s2sr redzones: <n> allocations checked, <m> damaged" to stderr when it exits.  That
+ * line counts what was checked at a free or by s2sr_debug_redzone_check: a buffer still live at exit -- a handle that was
+ * never destroyed -- is NOT read then, so call s2sr_debug_redzone_check (or destroy the handles) before the process ends.
+ *
+ * s2sr_debug_redzone: device allocations made FROM NOW ON get `bytes` of patterned memory in front and behind (and every
+ *   plane carved out of a handle's workspace a zone behind it); 0 turns the mode off.  Existing allocations keep what they
+ *   have: handles created before the switch have no zones until a buffer of theirs regrows.  S2SR_E_INVALID unless bytes is 0
+ *   or a positive multiple of 4096 (pointers keep their alignment).  When a zoned buffer is freed, its zones are checked and
+ *   damage is remembered for the next s2sr_debug_redzone_check.
+ * s2sr_debug_redzone_check: waits for the handle's streams (work a caller put on a stream of its own: synchronise it first),
+ *   then checks the zones of EVERY live zoned allocation of the process.  *damaged = zones found damaged now + zones found
+ *   damaged at a free since the last check; *allocations = the zoned allocations this handle owns (workspace planes count
+ *   one each).  With damage, s2sr_last_error(h) describes the first: "redzone: allocation of <user bytes> bytes, <front|back>
+ *   zone damaged at offset <byte offset from the zone's start>: found 0x.., expected 0x..".  Damaged zones are patterned
+ *   again and the remembered damage is cleared: the next check is clean.
+ * s2sr_debug_redzone_poke: the negative control.  Writes one wrong byte into the back zone of scratch buffer `slot` (0..5),
+ *   `offset` bytes behind its last byte (offset >= 0), or into its front zone, -offset bytes in front of its first byte
+ *   (offset < 0; offset -1 is the zone's last byte).  The byte lies inside the library's own allocation.  S2SR_E_INVALID when
+ *   the slot has no zones or the offset is not inside the zone. */
+int  s2sr_debug_redzone(int64_t bytes);
+int64_t s2sr_debug_redzone_bytes(void);       /* the zone size in force (0: off), for callers that switch it and put it back */
+int  s2sr_debug_redzone_check(s2sr_handle* h, int64_t* allocations, int64_t* damaged);
+int  s2sr_debug_redzone_poke(s2sr_handle* h, int32_t slot, int64_t offset);
 
 #ifdef __cplusplus
 }

@@ -77,20 +77,34 @@ int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mo
         ++h->ws_allocs;
         return S2SR_OK;
     };
+    // The planes are carved out of the allocation one behind the other.  Red-zone mode (s2sr_internal.h): a zone behind every
+    // plane, patterned after the zeroing, so a plane that runs into its neighbour is caught like one that leaves the allocation.
+    const size_t rz = g_redzone_bytes.load(std::memory_order_relaxed);
+    struct Plane { size_t off, bytes; };
+    std::vector<Plane> zoned;
+    size_t off = 0;
+    auto take = [&](size_t b) {
+        size_t o = off;
+        off += align256(b);
+        if (rz && b) { zoned.push_back({o, b}); off += rz; }
+        return o;
+    };
+    auto zone_planes = [&]() -> int {
+        for (const Plane& p : zoned) HIPCHK(h, redzone_add_plane(w.base, w.base + p.off, p.bytes, align256(p.bytes) - p.bytes + rz));
+        return S2SR_OK;
+    };
     if (h->compact()) {
         // SRVGGNetCompact: the packed input (1 block) and two 64-channel fp16 tensors (D[0], D[1]: 4 blocks each) that the
         // layers ping-pong between -- 288 B per padded LR pixel; everything stays at input resolution
         w.blk1 = (size_t)w.Hp * w.Wp * 32;
-        const size_t g = (size_t)G, bP0 = align256(g * w.blk1), bA = align256(g * 4 * w.blk1);
-        if (int rc = alloc_zeroed(bP0 + 2 * bA)) return rc;
-        w.P0 = w.base; w.D[0] = w.base + bP0; w.D[1] = w.base + bP0 + bA;
-        return S2SR_OK;
+        const size_t g = (size_t)G, oP0 = take(g * w.blk1), oA = take(g * 4 * w.blk1), oB = take(g * 4 * w.blk1);
+        if (int rc = alloc_zeroed(off)) return rc;
+        w.P0 = w.base + oP0; w.D[0] = w.base + oA; w.D[1] = w.base + oB;
+        return zone_planes();
     }
     w.Hp2 = padded(2 * H); w.Wp2 = padded(2 * W);
     w.Hp4 = padded(4 * H); w.Wp4 = padded(4 * W);
     w.blk1 = (size_t)w.Hp * w.Wp * 32; w.blk2 = (size_t)w.Hp2 * w.Wp2 * 32; w.blk4 = (size_t)w.Hp4 * w.Wp4 * 32;
-    size_t off = 0;
-    auto take = [&](size_t b) { size_t o = off; off += align256(b); return o; };
     const size_t g = (size_t)G;
     const size_t nd = fp8 ? 0 : 12;     // the fp16 dense tensors are not used by the fp8 trunk
     const size_t oP0 = take(g * w.blk1), oD0 = take(g * nd * w.blk1), oD1 = take(g * nd * w.blk1), oD2 = take(g * nd * w.blk1),
@@ -120,7 +134,7 @@ int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mo
         for (int i = 0; i < 3; ++i) w.Xh[i] = w.base + oXh[i];
         w.Tz = w.base + oTz;
     }
-    return S2SR_OK;
+    return zone_planes();
 }
 
 // a span: one event pair around the next launches of `fam` (every prof-th span is sampled, the others record nothing at all)

@@ -156,6 +156,9 @@ struct CompactTap {
 
 }  // namespace s2sr::engine
 
+// A device buffer added to this struct is also added to the list in s2sr_debug_redzone_check (redzone.hip), which counts the
+// handle's zoned allocations: d_trash, pool_w / pool_s / pool_b, the convs' own d_wpack / d_wphase, first16.d_wpack, ws.base,
+// d_scratch, stitch_sets[].d.
 struct s2sr_handle {
     s2sr_config cfg{};
     // RealESRGAN_x2plus (cfg.scale 2) runs pixel_unshuffle(x, 2) and then the x4 net on the half grid.  Every entry takes input

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <atomic>
 #include <functional>
 #include <mutex>
 #include <vector>
@@ -32,8 +33,26 @@ struct DeviceGate {
     DeviceGate() : lk(device_gate()) {}
 };
 static inline hipError_t dev_sync() { DeviceGate g; return hipDeviceSynchronize(); }
-template <class T> static inline hipError_t dev_malloc(T** p, size_t bytes) { DeviceGate g; return hipMalloc((void**)p, bytes); }
-static inline hipError_t dev_free(void* p) { DeviceGate g; return hipFree(p); }
+// Red zones (redzone.h, redzone.hip; the diagnostic mode of s2sr_debug_redzone / S2SR_REDZONE): with a zone size Z > 0 every
+// allocation is [Z patterned bytes | the caller's bytes | Z patterned bytes] and dev_free checks both zones before it frees.  Z is
+// a multiple of 4096, so the pointer handed out keeps every alignment hipMalloc's has.  Off (the default), the cost is one atomic
+// load here and one in dev_free; allocations made while the mode was off are freed as ever.
+extern std::atomic<size_t> g_redzone_bytes;     // Z of the allocations made from now on
+extern std::atomic<bool> g_redzone_ever;        // the mode has been on at some point: dev_free looks its pointer up
+hipError_t redzone_malloc(void** p, size_t bytes, size_t zone);   // both with the device gate held
+hipError_t redzone_free(void* p);
+template <class T> static inline hipError_t dev_malloc(T** p, size_t bytes) {
+    DeviceGate g;
+    if (const size_t z = g_redzone_bytes.load(std::memory_order_relaxed)) return redzone_malloc((void**)p, bytes, z);
+    return hipMalloc((void**)p, bytes);
+}
+static inline hipError_t dev_free(void* p) {
+    DeviceGate g;
+    if (g_redzone_ever.load(std::memory_order_relaxed)) return redzone_free(p);
+    return hipFree(p);
+}
+// a zone of `back` bytes behind the `bytes` of `plane`, a piece of the zoned allocation `parent` (the workspace planes)
+hipError_t redzone_add_plane(void* parent, void* plane, size_t bytes, size_t back);
 static inline hipError_t host_malloc(void** p, size_t bytes, unsigned flags) { DeviceGate g; return hipHostMalloc(p, bytes, flags); }
 static inline hipError_t host_free(void* p) { DeviceGate g; return hipHostFree(p); }
 

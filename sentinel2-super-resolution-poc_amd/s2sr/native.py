@@ -194,6 +194,10 @@ _PROTOS = {
     "s2sr_debug_bench_conv": (C.c_int, [C.c_void_p] + [C.c_int32] * 6 + [C.POINTER(C.c_float), C.c_void_p, C.c_int32]),
     "s2sr_debug_rdb_persistent": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                             C.POINTER(C.c_int32)]),
+    "s2sr_debug_redzone": (C.c_int, [C.c_int64]),
+    "s2sr_debug_redzone_bytes": (C.c_int64, []),
+    "s2sr_debug_redzone_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "s2sr_debug_redzone_poke": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -1075,6 +1079,37 @@ def _debug_compact_taps(self, layers, tiles=None, x=None, job_windows=0):
     t.p0, t.out_f32, t.out_u8 = p0.ctypes.data, out_f32.ctypes.data, out_u8.ctypes.data
     call()
     return geo, acts, p0, out_f32, out_u8
+
+
+def redzone(nbytes: int):
+    """Red zones of `nbytes` (0: off; a multiple of 4096) around every device allocation the library makes from now on
+    (include/s2sr.h: s2sr_debug_redzone).  Process-wide; a diagnostic."""
+    rc = load_library().s2sr_debug_redzone(int(nbytes))
+    if rc:
+        raise S2srError(f"s2sr_debug_redzone({nbytes}) failed ({_ERR.get(rc, rc)}): 0 or a multiple of 4096")
+
+
+def redzone_bytes() -> int:
+    """The zone size in force (0: off): what a caller that switches the mode puts back."""
+    return int(load_library().s2sr_debug_redzone_bytes())
+
+
+def _redzone_check(self) -> tuple:
+    """(zoned allocations this engine owns, damaged zones in the process since the last check, the first damage's description or
+    ""): include/s2sr.h s2sr_debug_redzone_check."""
+    n, bad = C.c_int64(0), C.c_int64(0)
+    self._check(self._lib.s2sr_debug_redzone_check(self._h, C.byref(n), C.byref(bad)), "s2sr_debug_redzone_check")
+    msg = self._lib.s2sr_last_error(self._h) if bad.value else b""
+    return int(n.value), int(bad.value), (msg or b"").decode()
+
+
+def _redzone_poke(self, slot: int, offset: int):
+    """The negative control: one wrong byte into the back (offset >= 0) or front (offset < 0) zone of scratch buffer `slot`."""
+    self._check(self._lib.s2sr_debug_redzone_poke(self._h, int(slot), int(offset)), "s2sr_debug_redzone_poke")
+
+
+Engine.redzone_check = _redzone_check
+Engine.redzone_poke = _redzone_poke
 
 
 def expected_blob_floats_cfg(num_block: int, scale: int = 4, arch: str = "rrdb") -> int:
