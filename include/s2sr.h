@@ -482,6 +482,10 @@ int  s2sr_debug_plan_windows(int32_t PH, int32_t PW, int32_t tile, int32_t pad, 
  * ramp a == b, ia == ib, num = 0, den = 1. */
 int  s2sr_debug_plan_blend(int32_t PH, int32_t PW, int32_t tile, int32_t pad, int32_t scale, int32_t tiled, int32_t* rows,
                            int32_t* cols);
+/* The bands of a chunked whole-image call (host arithmetic only): chunk_r0[0 .. nchunks] = the first window row of each chunk,
+ * ascending from 0, then ny; last_row[OH] = per output row the last window row it reads (s2sr_debug_plan_windows' rm[:, 0], or
+ * column 2 of s2sr_debug_plan_blend's rows), monotone.  bands[2 k], bands[2 k + 1] = the output rows [yb, ye) chunk k makes final. */
+int  s2sr_debug_plan_bands(const int32_t* chunk_r0, int32_t nchunks, int32_t ny, int32_t OH, const int32_t* last_row, int32_t* bands);
 
 /* test hook: ONE RDB-shaped conv through the TRUNK kernels (conv_trunk.hip: conv_trunk_f16 / conv_trunk_f8), host tensors in
  * NCHW fp32 -- the per-layer parity check of the kernels that carry 84 % of a step (s2sr_debug_conv goes through conv3x3.hip).

@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "band_plan.h"
 #include "blend_plan.h"
 #include "engine_internal.h"
 
@@ -171,17 +172,19 @@ int plan_window_job(int PH, int PW, int tile, int pad, int scale, bool tiled, Wi
     return S2SR_OK;
 }
 
-// The job's rectangles and paste maps on the device (scratch 3), uploaded before this returns
-static int upload_window_job(s2sr_handle* h, hipStream_t st, const WindowJob& job, int32_t** d_rects, int32_t** d_rm, int32_t** d_cm) {
-    int rc = ensure_scratch(h, 3, (job.rects.size() + job.rm.size() + job.cm.size()) * 4);
+// Window rectangles and the row / column tables of a paste (the paste maps, or the blend tables; empty: none) on the device, one
+// behind the other in scratch 3: d[0 .. 3) point at them.  Uploaded before this returns.
+static int upload_tables(s2sr_handle* h, hipStream_t st, const std::vector<int32_t>& rects, const std::vector<int32_t>& rows,
+                         const std::vector<int32_t>& cols, int32_t* d[3]) {
+    const std::vector<int32_t>* v[3] = {&rects, &rows, &cols};
+    int rc = ensure_scratch(h, 3, (rects.size() + rows.size() + cols.size()) * 4);
     if (rc) return rc;
-    *d_rects = (int32_t*)h->d_scratch[3];
-    *d_rm = *d_rects + job.rects.size();
-    *d_cm = *d_rm + job.rm.size();
-    if (!job.rects.empty()) HIPCHK(h, hipMemcpyAsync(*d_rects, job.rects.data(), job.rects.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(*d_rm, job.rm.data(), job.rm.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(*d_cm, job.cm.data(), job.cm.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));   // the job's vectors are host buffers of the caller
+    int32_t* at = (int32_t*)h->d_scratch[3];
+    for (int i = 0; i < 3; at += v[i++]->size()) {
+        d[i] = at;
+        if (!v[i]->empty()) HIPCHK(h, hipMemcpyAsync(at, v[i]->data(), v[i]->size() * 4, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(h, hipStreamSynchronize(st));   // the vectors are host buffers of the caller
     return S2SR_OK;
 }
 
@@ -217,22 +220,19 @@ static std::vector<int> plan_chunk_rows(const s2sr_handle* h, const WindowJob& j
     return chunk_r0;
 }
 
-// The chunk loop of a tiled job: forward(t0, n) runs the net on windows [t0, t0 + n), finish(t0, yb, ye) turns the band of output
+// The chunk loop of a whole-image job (the untiled image: one chunk of one window): forward(t0, n) runs the net on windows [t0, t0 + n), finish(t0, yb, ye) turns the band of output
 // rows that chunk made final into image rows on the device (t0: the chunk's first window, for a door that keeps one chunk's
 // tiles).  `copy`: each band (row_b bytes per row, at dev, to host) leaves on the copy stream under the next chunk's compute,
 // the last one exposed.  Events group_done[0 .. nchunks) are the caller's to provide.
-// last_row(y): the last window row output row y reads (monotone in y): rows [yb, ye) with last_row < the chunk's end are final.
-template <class Forward, class Finish, class LastRow>
-static int run_chunks(s2sr_handle* h, hipStream_t st, const WindowJob& job, const std::vector<int>& chunk_r0, int OH, Forward forward,
-                      Finish finish, uint8_t* host, const uint8_t* dev, size_t row_b, bool copy, LastRow last_row) {
-    const int nx = job.nx, ny = job.ny, nchunks = (int)chunk_r0.size() - 1;
+// band_end: the bands (plan_bands, band_plan.h) -- chunk c makes rows [band_end[c - 1], band_end[c]) final.
+template <class Forward, class Finish>
+static int run_chunks(s2sr_handle* h, hipStream_t st, int nx, const std::vector<int>& chunk_r0, const std::vector<int>& band_end, Forward forward,
+                      Finish finish, uint8_t* host, const uint8_t* dev, size_t row_b, bool copy) {
+    const int nchunks = (int)band_end.size();
     int rc, yb = 0, prev_yb = 0, prev_ye = 0;
     for (int c = 0; c < nchunks; ++c) {
-        const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1] < ny ? chunk_r0[c + 1] : ny;
+        const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1], ye = band_end[c];
         if ((rc = forward(r0 * nx, (r1 - r0) * nx))) return rc;
-        int ye = OH;
-        if (r1 < ny)
-            for (ye = yb; ye < OH && last_row(ye) < r1; ++ye) {}
         if (ye > yb && (rc = finish(r0 * nx, yb, ye))) return rc;
         HIPCHK(h, hipEventRecord(h->group_done[c], st));
         if (copy && c > 0 && prev_ye > prev_yb) {
@@ -246,13 +246,6 @@ static int run_chunks(s2sr_handle* h, hipStream_t st, const WindowJob& job, cons
         if ((rc = d2h_staged(h, host + (size_t)prev_yb * row_b, dev + (size_t)prev_yb * row_b, (size_t)(prev_ye - prev_yb) * row_b, true))) return rc;
     }
     return S2SR_OK;
-}
-
-// the overwrite paste: a row is final once the window row that owns it is done (the paste map)
-template <class Forward, class Finish>
-static int run_chunks(s2sr_handle* h, hipStream_t st, const WindowJob& job, const std::vector<int>& chunk_r0, int OH, Forward forward,
-                      Finish finish, uint8_t* host, const uint8_t* dev, size_t row_b, bool copy) {
-    return run_chunks(h, st, job, chunk_r0, OH, forward, finish, host, dev, row_b, copy, [&](int y) { return job.rm[2 * y]; });
 }
 
 }  // namespace s2sr::engine
@@ -454,397 +447,284 @@ static int pp_finish_bands(s2sr_handle* h, hipStream_t st, uint8_t* d_img_out, u
     return S2SR_OK;
 }
 
-// RealESRGAN.enhance (cnn_super_resolution.py:217-234) incl. _tile_process (:236-280)
-// job_rgb: the caller's image is RGB and wants RGB back -- R and B are swapped on the device in front of and behind the net (the
-// reference's cvtColor pair, wow_sr.py:85,103).  prm: the crop-visibility post-process (wow_sr.py:187-209) on the stitched RGB
-// image, on the device, before the one copy out (it is image-global: no band leaves before the whole mosaic is done).
-static int enhance_impl(s2sr_handle* h, const uint8_t* img, int H, int W, int tile, int pad, uint8_t* out_u8,
-                        float* out_f32, bool force_tiled = false, bool job_rgb = false, const s2sr_pp_params* prm = nullptr) {
-    if (!h || !img || (!out_u8 && !out_f32) || H <= 0 || W <= 0 || tile <= 0 || pad < 0) return S2SR_E_INVALID;
-    if ((job_rgb || prm) && !out_u8) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (prm)                                                  // before the net runs, not behind it
-        if (const char* why = pp_params_error(*prm)) return fail(h, S2SR_E_INVALID, why);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    int rc, PH, PW;
-    if ((rc = plan_dims(h, H, W, tile, &PH, &PW))) return rc;
-    // scale 2, odd H or W: everything below runs on the padded PH x PW image; the output is cropped to OH x OW by the stitch maps
-    const bool reflect = PH != H || PW != W;
-    const int scale = h->cfg.scale, OH = H * scale, OW = W * scale, OHp = PH * scale, OWp = PW * scale;
-    const size_t ib = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
-    if ((rc = ensure_scratch(h, 0, ib))) return rc;
-    if ((rc = ensure_scratch(h, 1, opx * (out_f32 ? 4 : 1)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, ib, hipMemcpyHostToDevice, st));
-    if (job_rgb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[0], (size_t)H * W, (uint8_t*)h->d_scratch[0], st));
-    const bool whole_finish = job_rgb || prm != nullptr;      // the image leaves in one piece, behind the device-side finish
-    const bool tiled = force_tiled || (long long)PH * PW > (long long)tile * tile * 4;   // strict '>' (:226)
-    if (!tiled) {
-        if (out_f32 || reflect) {
-            // net output is NCHW (f32; enhance() returns HWC) or the padded image's (u8, odd scale-2 image) -> stitch with an
-            // identity map, cropped to OH x OW
-            const size_t opxp = (size_t)OHp * OWp * 3;
-            if ((rc = ensure_scratch(h, 2, opxp * (out_f32 ? 4 : 1)))) return rc;
-            rc = forward_dev(h, st, TileIn::u8(h->d_scratch[0], H, W), 1, PH, PW,
-                             TileOut{out_f32 ? nullptr : (uint8_t*)h->d_scratch[2], out_f32 ? (float*)h->d_scratch[2] : nullptr});
-            if (rc) return rc;
-            WindowJob job;
-            if ((rc = plan_window_job(PH, PW, tile, pad, scale, false, job))) return fail(h, rc, kBadPlan);
-            int32_t *d_rects, *d_rm, *d_cm;
-            if ((rc = upload_window_job(h, st, job, &d_rects, &d_rm, &d_cm))) return rc;
-            if (out_f32) HIPCHK(h, launch_stitch((const float*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
-            else HIPCHK(h, launch_stitch((const uint8_t*)h->d_scratch[2], 1, OHp, OWp, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
-        } else {
-            rc = forward_dev(h, st, TileIn::u8(h->d_scratch[0]), 1, H, W, TileOut{(uint8_t*)h->d_scratch[1]});
-            if (rc) return rc;
-        }
-    } else {
-        WindowJob job;
-        if ((rc = plan_window_job(PH, PW, tile, pad, scale, true, job))) return fail(h, rc, kBadPlan);
-        const int nx = job.nx, wh = job.wh, ww = job.ww, T = nx * job.ny;
-        const size_t tin = (size_t)T * wh * ww * 3, tout = tin * scale * scale;
-        if ((rc = ensure_scratch(h, 2, tin))) return rc;
-        if ((rc = ensure_scratch(h, 4, tout * (out_f32 ? 4 : 1)))) return rc;
-        int32_t *d_rects, *d_rm, *d_cm;
-        if ((rc = upload_window_job(h, st, job, &d_rects, &d_rm, &d_cm))) return rc;
-        HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_rects, T, wh, ww, reflect, (uint8_t*)h->d_scratch[2], st));
-        const Mosaic mo = pick_mosaic(h, T, wh, ww);   // ONE plan for the job: every chunk runs in its workspace geometry
-        const std::vector<int> chunk_r0 = plan_chunk_rows(h, job, mo);
-        const int nchunks = (int)chunk_r0.size() - 1;
-        if (!out_f32 && nchunks > 1) {
-            // A job (job_rgb / prm) takes the same route: the channel swap behind the net is applied to every band as it is stitched;
-            // the post-process -- image-global through CLAHE's grid (wow_sr.py:191-192) -- counts every band into the histograms as
-            // it is stitched (under the compute of the chunks still to come), builds the LUTs behind the last band and then
-            // finishes the image in row bands, each followed by its copy out: what is exposed behind the last window is one band's
-            // kernels plus the PCIe time of the image (the r04 form waited for the whole mosaic, swapped, post-processed and only
-            // then started the one copy).
-            const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;
-            const size_t row_b = (size_t)OW * 3;
-            int fin_rows = 0, nfin = 0;          // finishing bands of the post-process: ~48 MB each, whole 32-row tile rows
-            if (prm) {
-                fin_rows = (int)(((size_t)48 << 20) / row_b) & ~31;
-                if (fin_rows < 64) fin_rows = 64;
-                nfin = (OH + fin_rows - 1) / fin_rows;
-                if ((rc = pp_band_begin_locked(h, OH, OW, prm, job_rgb ? 3 : 0, st))) return rc;   // (allocates: before anything is enqueued)
-            }
-            // this job's run took scratch 5 from whatever run a caller had open there: it ends with the job on every way out, so
-            // that caller's next hist / lut / rows is refused
-            struct CloseRun { s2sr_handle* h; ~CloseRun() { if (h) h->ppb.open = false; } } close_run{prm ? h : nullptr};
-            if ((rc = ensure_group_events(h, nchunks + nfin))) return rc;
-            uint8_t* d_img_out = (uint8_t*)h->d_scratch[1];
-            auto forward = [&](int t0, int n) {
-                return forward_dev(h, st, TileIn::u8((const uint8_t*)h->d_scratch[2] + t0 * win_in), n, wh, ww,
-                                   TileOut{(uint8_t*)h->d_scratch[4] + t0 * win_out}, mo.on() ? &mo : nullptr);
-            };
-            auto finish = [&](int, int yb, int ye) -> int {   // (scratch 4 holds every window's output)
-                HIPCHK(h, launch_stitch((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW,
-                                           d_img_out + (size_t)yb * row_b, st));
-                if (prm) return pp_band_hist_locked(h, d_img_out, yb, ye, st);
-                if (job_rgb) HIPCHK(h, launch_swap_rb_u8(d_img_out + (size_t)yb * row_b, (size_t)(ye - yb) * OW, d_img_out + (size_t)yb * row_b, st));
-                return S2SR_OK;
-            };
-            // with a post-process no band is copied here: the bands leave through the finishing pass below
-            if ((rc = run_chunks(h, st, job, chunk_r0, OH, forward, finish, out_u8, d_img_out, row_b, !prm))) return rc;
-            if (prm && (rc = pp_finish_bands(h, st, d_img_out, out_u8, OH, row_b, fin_rows, nfin, nchunks))) return rc;
-            HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-            HIPCHK(h, hipStreamSynchronize(st));
-            return S2SR_OK;
-        }
-        rc = forward_dev(h, st, TileIn::u8(h->d_scratch[2]), T, wh, ww,
-                         TileOut{out_f32 ? nullptr : (uint8_t*)h->d_scratch[4], out_f32 ? (float*)h->d_scratch[4] : nullptr});
-        if (rc) return rc;
-        if (out_f32) HIPCHK(h, launch_stitch((const float*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (float*)h->d_scratch[1], st));
-        else HIPCHK(h, launch_stitch((const uint8_t*)h->d_scratch[4], nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, (uint8_t*)h->d_scratch[1], st));
-    }
-    const uint8_t* d_final = (const uint8_t*)h->d_scratch[1];
-    if (whole_finish) {
-        if (job_rgb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[1], (size_t)OH * OW, (uint8_t*)h->d_scratch[1], st));
-        if (prm) {
-            // the windows' output buffer is free again once the stitch has read it; whole-image jobs get a buffer of their own
-            if ((rc = ensure_scratch(h, 4, opx))) return rc;
-            if ((rc = postprocess_dev_locked(h, h->d_scratch[1], 1, OH, OW, prm, h->d_scratch[4], st))) return rc;
-            d_final = (const uint8_t*)h->d_scratch[4];
-        }
-    }
-    if ((rc = ensure_group_events(h, 1))) return rc;
-    HIPCHK(h, hipEventRecord(h->group_done[0], st));
-    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[0], 0));
-    if ((rc = d2h_staged(h, out_f32 ? (uint8_t*)out_f32 : out_u8, out_f32 ? (const uint8_t*)h->d_scratch[1] : d_final, opx * (out_f32 ? 4 : 1), true))) return rc;
-    HIPCHK(h, hipStreamSynchronize(st));
+// What a whole-image call asks for.  Every door (s2sr_enhance_u8 / _f32 / _job_u8 / _u16 / _blend_u8 / _blend_u16 and
+// s2sr_tile_process_f32) fills one and enters enhance_call.
+struct EnhanceCall {
+    const uint8_t* img8 = nullptr;
+    const uint16_t* img16 = nullptr;
+    int H = 0, W = 0, tile = 0, pad = 0;
+    int lo = 0, hi = 0;                       // 16-bit: the value range
+    const s2sr_pp_params* prm = nullptr;      // 8-bit: the job's crop-visibility post-process (wow_sr.py:187-209) on the stitched image ...
+    bool swap_rb = false;                     // ... and its R / B exchange in front of and behind the net (the cvtColor pair, wow_sr.py:85,103)
+    bool force_tiled = false;                 // _tile_process whatever the size
+    bool blend = false;                       // cross-fade the window overlaps (blend_plan.h) where the plan has a ramp
+    uint8_t* out_u8 = nullptr;
+    uint16_t* out_u16 = nullptr;
+    float* out_f32 = nullptr;
+    const char* required = nullptr;           // the door's words for a call without image, sizes or output (none: the bare code)
+};
+
+static int check_call(s2sr_handle* h, const EnhanceCall& c) {
+    const bool in16 = c.img16 != nullptr;
+    if ((!c.img8 && !c.img16) || (!c.out_u8 && !c.out_u16 && !c.out_f32) || c.H <= 0 || c.W <= 0 || c.tile <= 0 || c.pad < 0)
+        return c.required ? fail(h, S2SR_E_INVALID, c.required) : S2SR_E_INVALID;
+    if (!in16 && c.out_f32 && (c.prm || c.swap_rb))          // (only the blend door can ask for it)
+        return fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: the float image is the net's own output: not with a post-process or swap_rb");
+    if (!in16 && (c.prm || c.swap_rb) && !c.out_u8) return c.blend ? fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: a job needs out_u8") : S2SR_E_INVALID;
+    if (in16)
+        if (int rc = check_u16(h, c.lo, c.hi)) return rc;
+    if (c.prm)                                               // before the net runs, not behind it
+        if (const char* why = pp_params_error(*c.prm)) return fail(h, S2SR_E_INVALID, why);
     return S2SR_OK;
 }
 
+// Everything about a call that is host arithmetic (the one HIP call in here is plan_chunk_rows' CU count).  Scale 2, odd H or W:
+// the job runs on the padded PH x PW image and the paste crops to the output.
+struct EnhancePlan {
+    int PH = 0, PW = 0;
+    bool tiled = false;                       // RealESRGAN.enhance's whole / tiled switch
+    bool blend = false;                       // the seam-blended paste: asked for, tiled, and a ramp exists
+    WindowJob job;
+    std::vector<int32_t> rows, cols;          // blend: the tables (blend_plan.h), 6 ints per output row / column of the padded image, as the kernel reads them
+    Mosaic mo;                                // ONE plan for the job: every chunk runs in its workspace geometry
+    std::vector<int> chunk_r0, band_end;      // the chunks of window rows (plan_chunk_rows) and the band of output rows each makes final (plan_bands)
+    int max_rows = 0;                         // window rows of the largest chunk
+};
+
+static int plan_enhance(s2sr_handle* h, const EnhanceCall& c, EnhancePlan& p) {
+    int rc;
+    if ((rc = plan_dims(h, c.H, c.W, c.tile, &p.PH, &p.PW))) return rc;
+    const int scale = h->cfg.scale;
+    p.tiled = c.force_tiled || (long long)p.PH * p.PW > (long long)c.tile * c.tile * 4;   // strict '>' (:226)
+    WindowJob& job = p.job;
+    if ((rc = plan_window_job(p.PH, p.PW, c.tile, c.pad, scale, p.tiled, job))) return fail(h, rc, kBadPlan);
+    if (c.blend && p.tiled) {
+        p.rows.resize((size_t)kBlendStride * p.PH * scale); p.cols.resize((size_t)kBlendStride * p.PW * scale);
+        const char* why = blend_plan_axis(job.rm.data(), (int64_t)p.PH * scale, job.ny, job.wh * scale, c.pad * scale, p.rows.data());
+        if (!why) why = blend_plan_axis(job.cm.data(), (int64_t)p.PW * scale, job.nx, job.ww * scale, c.pad * scale, p.cols.data());
+        if (why) return fail(h, S2SR_E_INVALID, why);
+        for (size_t i = 4; i < p.rows.size() && !p.blend; i += kBlendStride) p.blend = p.rows[i] != 0;
+        for (size_t i = 4; i < p.cols.size() && !p.blend; i += kBlendStride) p.blend = p.cols[i] != 0;
+    }
+    if (p.tiled) p.mo = pick_mosaic(h, job.nx * job.ny, job.wh, job.ww);
+    // one chunk for the untiled image, and with out_f32: the fp32 image is pasted from all the tiles at the end
+    p.chunk_r0 = p.tiled && !c.out_f32 ? plan_chunk_rows(h, job, p.mo) : std::vector<int>{0, job.ny};
+    const int nchunks = (int)p.chunk_r0.size() - 1;
+    // a row is final once the last window row it reads is done: the window row that owns it (the paste map), or the later of a ramp's two
+    p.band_end.resize(nchunks);
+    plan_bands(p.chunk_r0.data(), nchunks, job.ny, c.H * scale, p.blend ? p.rows.data() + 2 : job.rm.data(), p.blend ? kBlendStride : 2, p.band_end.data());
+    for (int k = 0; k < nchunks; ++k) {
+        const int r0 = p.chunk_r0[k], r1 = p.chunk_r0[k + 1];
+        if (r1 - r0 > p.max_rows) p.max_rows = r1 - r0;
+        // blend: every row reads window rows its chunk's buffer holds (its own, and the one carried in front)
+        if (p.blend)
+            if (const char* why = blend_check_band(p.rows.data(), k ? p.band_end[k - 1] : 0, p.band_end[k], r0 - (k > 0), r1)) return fail(h, S2SR_E_INVALID, why);
+    }
+    if (p.blend) { blend_device_axis(p.rows.data(), (int64_t)p.PH * scale); blend_device_axis(p.cols.data(), (int64_t)p.PW * scale); }
+    return S2SR_OK;
+}
+
+// RealESRGAN.enhance (cnn_super_resolution.py:217-234) incl. _tile_process (:236-280), behind every door; the caller holds h->mu.
+// Upload, gather the windows (scratch 0 -> 2), the chunk loop -- forward a chunk of window rows, paste the band of output rows it
+// made final into the image (scratch 1), copy the band out under the next chunk -- and the tail.  Only the paste varies:
+//   overwrite (8-bit in): the net writes u8 (or NCHW fp32) tiles of the WHOLE image into scratch 4, each chunk at its own offset, and
+//     launch_stitch pastes.  The untiled image is one window: the net writes it straight into scratch 1, or (fp32, or the padded
+//     image of an odd scale-2 one) into scratch 2 and an identity map crops it.  A job's R / B exchange follows each band;
+//   quantise (16-bit in): every chunk's windows leave the net as fp32 tiles into ONE chunk-sized buffer (scratch 4; the same
+//     pointers for every chunk, so the chunks' graphs hit) and launch_stitch_quant_u16 pastes and quantises from it;
+//   blend: as quantise, for both inputs, and launch_stitch_blend cross-fades inside the ramps.  A row ramp reads the last window
+//     row of one chunk and the first of the next, so the buffer has one window row in front of the chunk's, filled from the chunk
+//     before by one device-to-device copy.
+// A post-process is image-global through CLAHE's grid (wow_sr.py:191-192): in bands it counts every band into the histograms as it
+// is pasted (under the compute of the chunks still to come), builds the LUTs behind the last band and finishes the image in row
+// bands, each followed by its copy out; a single chunk of the overwrite paste runs it on the whole image instead.
+// The fp32 image (one chunk) is pasted from the chunk's tiles behind the loop, and both images leave behind that.
+static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
+    EnhancePlan p;
+    int rc = plan_enhance(h, c, p);
+    if (rc) return rc;
+    const bool in16 = c.img16 != nullptr, over = !p.blend && !in16;
+    if (over && c.out_u8 && c.out_f32) {   // a blend call left whole or without a ramp: u8 and fp32 tiles are two forwards of the net
+        EnhanceCall f = c, q = c;
+        f.blend = q.blend = false; f.out_u8 = nullptr; q.out_f32 = nullptr;
+        return (rc = enhance_locked(h, f)) ? rc : enhance_locked(h, q);
+    }
+    hipStream_t st = h->stream;
+    const WindowJob& job = p.job;
+    const int H = c.H, W = c.W, scale = h->cfg.scale, OH = H * scale, OW = W * scale, esz = in16 ? 2 : 1;
+    const int nx = job.nx, ny = job.ny, wh = job.wh, ww = job.ww, oth = wh * scale, otw = ww * scale;
+    const int nchunks = (int)p.chunk_r0.size() - 1, carry = p.blend && nchunks > 1 ? 1 : 0;
+    const bool reflect = p.PH != H || p.PW != W;
+    const bool direct = over && !p.tiled && !c.out_f32 && !reflect;     // the net writes the image itself: no tiles, no tables, no paste
+    const bool banded = c.prm && (p.blend || nchunks > 1);              // the post-process runs in bands (else, if any, on the whole image)
+    void* out_q = in16 ? (void*)c.out_u16 : (void*)c.out_u8;
+    const size_t ipx = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
+    const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;      // samples per window, in and out
+    const size_t row_b = (size_t)OW * 3 * esz;                                         // bytes of one output row
+    // ---- staging.  scratch 1: the quantised image, then the fp32 image (the overwrite paste makes one of them per call)
+    const size_t f_off = over ? 0 : (opx * esz + 255) & ~(size_t)255;
+    const int tslot = over && !p.tiled ? 2 : 4;
+    const size_t tile_b = over ? (size_t)nx * ny * win_out * (c.out_f32 ? 4 : 1) : (size_t)(p.max_rows + carry) * nx * win_out * sizeof(float);
+    if ((rc = ensure_scratch(h, 0, ipx * esz))) return rc;
+    if ((rc = ensure_scratch(h, 1, c.out_f32 ? f_off + opx * 4 : over ? opx : f_off))) return rc;
+    if (p.tiled && (rc = ensure_scratch(h, 2, (size_t)nx * ny * win_in * esz))) return rc;
+    if (!direct && (rc = ensure_scratch(h, tslot, tile_b))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], in16 ? (const void*)c.img16 : (const void*)c.img8, ipx * esz, hipMemcpyHostToDevice, st));
+    if (c.swap_rb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[0], (size_t)H * W, (uint8_t*)h->d_scratch[0], st));
+    int32_t* d_tab[3] = {nullptr, nullptr, nullptr};   // rectangles, row table, column table
+    if (!direct && (rc = upload_tables(h, st, job.rects, p.blend ? p.rows : job.rm, p.blend ? p.cols : job.cm, d_tab))) return rc;
+    if (p.tiled) {
+        if (in16) HIPCHK(h, launch_gather_windows((const uint16_t*)h->d_scratch[0], H, W, d_tab[0], nx * ny, wh, ww, (uint16_t*)h->d_scratch[2], st));
+        else HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_tab[0], nx * ny, wh, ww, reflect, (uint8_t*)h->d_scratch[2], st));
+    }
+    const char* d_win = (const char*)h->d_scratch[p.tiled ? 2 : 0];
+    uint8_t* d_q = (uint8_t*)h->d_scratch[1];
+    float* d_f = (float*)(d_q + f_off);
+    void* d_buf = direct ? (void*)d_q : h->d_scratch[tslot];      // blend: [carry window row | the chunk's window rows]
+    float* d_tiles = (float*)d_buf + (size_t)carry * nx * win_out;
+    int fin_rows = 0, nfin = 0;          // finishing bands of the post-process: ~48 MB each, whole 32-row tile rows
+    if (banded) {
+        fin_rows = (int)(((size_t)48 << 20) / row_b) & ~31;
+        if (fin_rows < 64) fin_rows = 64;
+        nfin = (OH + fin_rows - 1) / fin_rows;
+        if ((rc = pp_band_begin_locked(h, OH, OW, c.prm, c.swap_rb ? 3 : 0, st))) return rc;
+    }
+    // this call's run took scratch 5 from whatever run a caller had open there: it ends with the call on every way out, so that
+    // caller's next hist / lut / rows is refused
+    struct CloseRun { s2sr_handle* h; ~CloseRun() { if (h) h->ppb.open = false; } } close_run{banded ? h : nullptr};
+    if ((rc = ensure_group_events(h, nchunks + nfin + 1))) return rc;
+    // ---- the chunk loop
+    int prev_n = 0;                                              // windows of the chunk before
+    auto forward = [&](int t0, int n) -> int {
+        if (carry && t0 > 0)   // the last window row of the chunk before, to the front of the buffer (its band is pasted: same stream)
+            HIPCHK(h, hipMemcpyAsync(d_buf, d_tiles + (size_t)(prev_n - nx) * win_out, (size_t)nx * win_out * sizeof(float), hipMemcpyDeviceToDevice, st));
+        prev_n = n;
+        const TileIn in = in16 ? TileIn::u16((const uint16_t*)d_win + (size_t)t0 * win_in, c.lo, c.hi)
+                               : TileIn::u8((const uint8_t*)d_win + (size_t)t0 * win_in, p.tiled ? wh : H, p.tiled ? ww : W);
+        TileOut out;
+        if (!over) out.f32 = d_tiles;
+        else if (c.out_f32) out.f32 = (float*)d_buf + (size_t)t0 * win_out;
+        else out.u8 = (uint8_t*)d_buf + (size_t)t0 * win_out;
+        return forward_dev(h, st, in, n, wh, ww, out, p.mo.on() ? &p.mo : nullptr);
+    };
+    // rows [yb, ye) into the quantised image; t0: the chunk's first window (the one-chunk buffers start at window t0 - carry * nx)
+    auto finish = [&](int t0, int yb, int ye) -> int {
+        if (!out_q) return S2SR_OK;
+        uint8_t* dst = d_q + (size_t)yb * row_b;
+        if (over) {
+            if (!direct) HIPCHK(h, launch_stitch((const uint8_t*)d_buf, nx, oth, otw, d_tab[1] + 2 * yb, d_tab[2], ye - yb, OW, dst, st));
+            if (c.swap_rb && !banded) HIPCHK(h, launch_swap_rb_u8(dst, (size_t)(ye - yb) * OW, dst, st));   // (a banded post-process exchanges R and B itself)
+        } else {
+            Scope sc(h, st, F_MISC, 0.0, (double)(ye - yb) * OW * 3.0 * (4.0 + esz));
+            const int32_t* r = d_tab[1] + (size_t)kBlendStride * yb;
+            if (!p.blend) HIPCHK(h, launch_stitch_quant_u16(d_tiles, nx, t0, oth, otw, d_tab[1] + 2 * yb, d_tab[2], ye - yb, OW, c.lo, c.hi, (uint16_t*)dst, st));
+            else if (in16) HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, t0 - carry * nx, oth, otw, r, d_tab[2], ye - yb, OW, c.lo, c.hi, (uint16_t*)dst, st));
+            else HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, t0 - carry * nx, oth, otw, r, d_tab[2], ye - yb, OW, c.swap_rb && !c.prm, dst, st));
+        }
+        return banded ? pp_band_hist_locked(h, d_q, yb, ye, st) : S2SR_OK;
+    };
+    // with a post-process or the fp32 image no band is copied here: they leave through the tail below
+    if ((rc = run_chunks(h, st, nx, p.chunk_r0, p.band_end, forward, finish, (uint8_t*)out_q, d_q, row_b, out_q && !c.prm && !c.out_f32))) return rc;
+    // ---- the tail
+    hipEvent_t tail_done = h->group_done[nchunks + nfin];
+    if (banded && (rc = pp_finish_bands(h, st, d_q, c.out_u8, OH, row_b, fin_rows, nfin, nchunks))) return rc;
+    if (c.prm && !banded) {
+        // the windows' output buffer is free again once the stitch has read it; the untiled image gets a buffer of its own
+        if ((rc = ensure_scratch(h, 4, opx))) return rc;
+        if ((rc = postprocess_dev_locked(h, d_q, 1, OH, OW, c.prm, h->d_scratch[4], st))) return rc;
+        HIPCHK(h, hipEventRecord(tail_done, st));
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, tail_done, 0));
+        if ((rc = d2h_staged(h, c.out_u8, (const uint8_t*)h->d_scratch[4], opx, true))) return rc;
+    }
+    if (c.out_f32) {
+        if (p.blend) HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, 0, oth, otw, d_tab[1], d_tab[2], OH, OW, d_f, st));
+        else HIPCHK(h, launch_stitch((const float*)d_buf, nx, oth, otw, d_tab[1], d_tab[2], OH, OW, d_f, st));
+        HIPCHK(h, hipEventRecord(tail_done, st));
+        if (out_q) {
+            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
+            if ((rc = d2h_staged(h, (uint8_t*)out_q, d_q, OH * row_b, true))) return rc;
+        }
+        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, tail_done, 0));
+        if ((rc = d2h_staged(h, (uint8_t*)c.out_f32, (const uint8_t*)d_f, opx * 4, true))) return rc;
+    }
+    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (c.out_u16) { h->disp_slot = 1; h->disp_h = OH; h->disp_w = OW; }   // the x4 image also stays on the device, for s2sr_display_*_u16
+    return S2SR_OK;
+}
+
+// ONE lock scope per call, from the checks to the last synchronise (as s2sr_postprocess_u8): the scratch areas belong to the handle
+static int enhance_call(s2sr_handle* h, const EnhanceCall& c) {
+    if (!h) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (int rc = check_call(h, c)) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return enhance_locked(h, c);
+}
+
+static EnhanceCall call_u8(const uint8_t* img, int H, int W, int tile, int pad, uint8_t* out_u8, float* out_f32) {
+    EnhanceCall c;
+    c.img8 = img; c.H = H; c.W = W; c.tile = tile; c.pad = pad; c.out_u8 = out_u8; c.out_f32 = out_f32;
+    return c;
+}
+static EnhanceCall call_u16(const uint16_t* img, int H, int W, int tile, int pad, int lo, int hi, uint16_t* out_u16, float* out_f32) {
+    EnhanceCall c;
+    c.img16 = img; c.H = H; c.W = W; c.tile = tile; c.pad = pad; c.lo = lo; c.hi = hi; c.out_u16 = out_u16; c.out_f32 = out_f32;
+    return c;
+}
+
 int s2sr_enhance_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, uint8_t* out) {
-    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, img, H, W, tile, pad, out, nullptr));
+    const EnhanceCall c = call_u8(img, H, W, tile, pad, out, nullptr);
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
 }
 
 // A whole /api/wow job's device work in one call (apply_wow_sr, wow_sr.py:85-110): RGB image in, RGB2BGR, RealESRGAN.enhance,
 // BGR2RGB, _enhance_for_crops (prm != NULL), RGB image out -- one upload, one download, nothing in between on the host.
 int s2sr_enhance_job_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
                         uint8_t* out_rgb) {
-    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, rgb, H, W, tile, pad, out_rgb, nullptr, false, true, prm));
+    EnhanceCall c = call_u8(rgb, H, W, tile, pad, out_rgb, nullptr);
+    c.swap_rb = true; c.prm = prm;
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
 }
 
 int s2sr_enhance_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out) {
-    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, img, H, W, tile, pad, nullptr, out));
+    const EnhanceCall c = call_u8(img, H, W, tile, pad, nullptr, out);
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+}
+
+int s2sr_tile_process_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out) {
+    EnhanceCall c = call_u8(img, H, W, tile, pad, nullptr, out);
+    c.force_tiled = true;
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
 }
 
 // RealESRGAN.enhance for 16-bit rasters (upstream RealESRGANer's max_range = 65535 branch, with a value range): HxWx3 u16 ->
-// 4Hx4Wx3 u16 and / or the unquantised HWC fp32 image.  A sibling of enhance_impl, not a mode of it: the same whole / tiled
-// switch, window plan, de-duplication of repeated window rows / columns, mosaic and chunk plan, but every chunk's windows leave
-// the net as fp32 tiles into ONE chunk-sized buffer (the same pointers for every chunk, so the chunks' graphs hit), and
-// launch_stitch_quant_u16 pastes and quantises the chunk's band of final rows from it; the band's copy out runs on the copy stream
-// under the next chunk.  With out_f32 the tiles of the whole image are kept and stitched once at the end, as enhance_impl does.
-static int enhance16_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int tile, int pad, int lo, int hi, uint16_t* out_u16,
-                          float* out_f32) {
-    if (!h || !img || (!out_u16 && !out_f32) || H <= 0 || W <= 0 || tile <= 0 || pad < 0) {
-        if (h) fail(h, S2SR_E_INVALID, "s2sr_enhance_u16: an image, positive sizes and at least one output are required");
-        return S2SR_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(h->mu);
-    int rc = check_u16(h, lo, hi);
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const int scale = 4, OH = H * scale, OW = W * scale;
-    const size_t ipx = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
-    const size_t q_bytes = (opx * 2 + 255) & ~(size_t)255;       // scratch 1: the u16 image, then (out_f32) the fp32 image
-    if ((rc = ensure_scratch(h, 0, ipx * 2))) return rc;
-    if ((rc = ensure_scratch(h, 1, q_bytes + (out_f32 ? opx * 4 : 0)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, ipx * 2, hipMemcpyHostToDevice, st));
-    const bool tiled = (long long)H * W > (long long)tile * tile * 4;   // strict '>' (:226)
-    // the windows the net runs on, the paste maps and the chunks of window rows
-    WindowJob job;
-    if ((rc = plan_window_job(H, W, tile, pad, scale, tiled, job))) return fail(h, rc, kBadPlan);
-    const int nx = job.nx, ny = job.ny, wh = job.wh, ww = job.ww;
-    const Mosaic mo = tiled ? pick_mosaic(h, nx * ny, wh, ww) : Mosaic();   // ONE plan for the job: every chunk runs in its workspace geometry
-    // one chunk for the untiled image, and with out_f32: the fp32 image is stitched from all the tiles at the end
-    const std::vector<int> chunk_r0 = tiled && !out_f32 ? plan_chunk_rows(h, job, mo) : std::vector<int>{0, ny};
-    const int nchunks = (int)chunk_r0.size() - 1;
-    int max_rows = 0;
-    for (int c = 0; c < nchunks; ++c) {
-        const int r1 = chunk_r0[c + 1] < ny ? chunk_r0[c + 1] : ny;
-        if (r1 - chunk_r0[c] > max_rows) max_rows = r1 - chunk_r0[c];
-    }
-    const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;      // samples per window, in and out
-    if (tiled && (rc = ensure_scratch(h, 2, (size_t)nx * ny * win_in * 2))) return rc;
-    if ((rc = ensure_scratch(h, 4, (size_t)max_rows * nx * win_out * sizeof(float)))) return rc;
-    int32_t *d_rects, *d_rm, *d_cm;
-    if ((rc = upload_window_job(h, st, job, &d_rects, &d_rm, &d_cm))) return rc;
-    const uint16_t* d_win = (const uint16_t*)h->d_scratch[0];
-    if (tiled) {
-        HIPCHK(h, launch_gather_windows((const uint16_t*)h->d_scratch[0], H, W, d_rects, nx * ny, wh, ww, (uint16_t*)h->d_scratch[2], st));
-        d_win = (const uint16_t*)h->d_scratch[2];
-    }
-    if ((rc = ensure_group_events(h, nchunks + 1))) return rc;
-    uint16_t* d_q = (uint16_t*)h->d_scratch[1];
-    float* d_tiles = (float*)h->d_scratch[4];
-    const size_t row_b = (size_t)OW * 3 * 2;                     // bytes of one output row
-    auto forward = [&](int t0, int n) {
-        return forward_dev(h, st, TileIn::u16(d_win + (size_t)t0 * win_in, lo, hi), n, wh, ww, TileOut{nullptr, d_tiles}, mo.on() ? &mo : nullptr);
-    };
-    // the band's rows come from the chunk's window rows only (the row map is monotone): d_tiles holds them, from window t0 on
-    auto finish = [&](int t0, int yb, int ye) -> int {
-        if (!out_u16) return S2SR_OK;
-        Scope sc(h, st, F_MISC, 0.0, (double)(ye - yb) * OW * 3.0 * (4.0 + 2.0));
-        HIPCHK(h, launch_stitch_quant_u16(d_tiles, nx, t0, wh * scale, ww * scale, d_rm + 2 * yb, d_cm, ye - yb, OW, lo, hi,
-                                          d_q + (size_t)yb * OW * 3, st));
-        return S2SR_OK;
-    };
-    // with out_f32 (one chunk: d_tiles holds every window) both images leave behind the fp32 stitch
-    if ((rc = run_chunks(h, st, job, chunk_r0, OH, forward, finish, (uint8_t*)out_u16, (const uint8_t*)d_q, row_b, out_u16 && !out_f32))) return rc;
-    if (out_f32) {
-        float* d_f = (float*)((char*)h->d_scratch[1] + q_bytes);
-        HIPCHK(h, launch_stitch(d_tiles, nx, wh * scale, ww * scale, d_rm, d_cm, OH, OW, d_f, st));
-        HIPCHK(h, hipEventRecord(h->group_done[nchunks], st));
-        if (out_u16) {
-            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
-            if ((rc = d2h_staged(h, (uint8_t*)out_u16, (const uint8_t*)d_q, OH * row_b, true))) return rc;
-        }
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks], 0));
-        if ((rc = d2h_staged(h, (uint8_t*)out_f32, (const uint8_t*)d_f, opx * 4, true))) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (out_u16) { h->disp_slot = 1; h->disp_h = OH; h->disp_w = OW; }   // the x4 image also stays on the device, for s2sr_display_*_u16
-    return S2SR_OK;
-}
-
+// 4Hx4Wx3 u16 and / or the unquantised HWC fp32 image.
 int s2sr_enhance_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
                      uint16_t* out_u16, float* out_f32) {
-    RUN_WITH_STREAM_RECOVERY(h, enhance16_impl(h, img, H, W, tile, pad, lo, hi, out_u16, out_f32));
+    EnhanceCall c = call_u16(img, H, W, tile, pad, lo, hi, out_u16, out_f32);
+    c.required = "s2sr_enhance_u16: an image, positive sizes and at least one output are required";
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
 }
 
-// The seam-blended doors (s2sr_enhance_blend_u8 / _u16): enhance_impl's / enhance16_impl's windows, forwards and whole / tiled
-// switch with another paste.  A sibling of enhance16_impl: every chunk's windows leave the net as fp32 tiles into one chunk-sized
-// buffer, and launch_stitch_blend turns the chunk's band of final rows into image rows, cross-fading inside the ramps of the blend
-// plan (blend_plan.h).  A row ramp reads the last window row of one chunk and the first of the next, so the buffer has one window
-// row in front of the chunk's (the same pointers for every chunk: their graphs hit), filled from the previous chunk's last window
-// row by one device-to-device copy; a row is final once the later of its two window rows is done.  An image the switch leaves
-// whole, or whose plan has no ramp (pad 0), goes through the default doors as it is.
-struct BlendCall {
-    const uint8_t* img8 = nullptr;
-    const uint16_t* img16 = nullptr;
-    int lo = 0, hi = 0;                       // 16-bit: the value range
-    const s2sr_pp_params* prm = nullptr;      // 8-bit: the job's post-process ...
-    bool swap_rb = false;                     // ... and its R / B exchange in front of and behind the net
-    uint8_t* out_u8 = nullptr;
-    uint16_t* out_u16 = nullptr;
-    float* out_f32 = nullptr;
-};
-
-static int enhance_blend_impl(s2sr_handle* h, const BlendCall& c, int H, int W, int tile, int pad) {
-    const bool in16 = c.img16 != nullptr;
-    if (!h) return S2SR_E_INVALID;
-    WindowJob job;
-    std::vector<int32_t> rows, cols;          // the blend tables (blend_plan.h), 6 ints per output row / column of the padded image
-    std::vector<int> chunk_r0;
-    int PH = H, PW = W, rc;
-    bool blend = false;
-    {
-        std::lock_guard<std::mutex> lk(h->mu);
-        if ((!c.img8 && !c.img16) || (!c.out_u8 && !c.out_u16 && !c.out_f32) || H <= 0 || W <= 0 || tile <= 0 || pad < 0)
-            return fail(h, S2SR_E_INVALID, "s2sr_enhance_blend: an image, positive sizes and at least one output are required");
-        if (!in16 && c.out_f32 && (c.prm || c.swap_rb))
-            return fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: the float image is the net's own output: not with a post-process or swap_rb");
-        if (!in16 && (c.prm || c.swap_rb) && !c.out_u8) return fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: a job needs out_u8");
-        if (in16 && (rc = check_u16(h, c.lo, c.hi))) return rc;
-        if (c.prm)
-            if (const char* why = pp_params_error(*c.prm)) return fail(h, S2SR_E_INVALID, why);
-        if (!in16 && (rc = plan_dims(h, H, W, tile, &PH, &PW))) return rc;
-        if ((long long)PH * PW > (long long)tile * tile * 4) {   // strict '>' (:226)
-            const int scale = h->cfg.scale;
-            if ((rc = plan_window_job(PH, PW, tile, pad, scale, true, job))) return fail(h, rc, kBadPlan);
-            rows.resize((size_t)kBlendStride * PH * scale); cols.resize((size_t)kBlendStride * PW * scale);
-            const char* why = blend_plan_axis(job.rm.data(), (int64_t)PH * scale, job.ny, job.wh * scale, pad * scale, rows.data());
-            if (!why) why = blend_plan_axis(job.cm.data(), (int64_t)PW * scale, job.nx, job.ww * scale, pad * scale, cols.data());
-            if (why) return fail(h, S2SR_E_INVALID, why);
-            for (size_t i = 4; i < rows.size() && !blend; i += kBlendStride) blend = rows[i] != 0;
-            for (size_t i = 4; i < cols.size() && !blend; i += kBlendStride) blend = cols[i] != 0;
-        }
-    }
-    if (!blend) {   // whole, or no ramp anywhere: today's doors (an 8-bit call for both images is two of them)
-        if (in16) return enhance16_impl(h, c.img16, H, W, tile, pad, c.lo, c.hi, c.out_u16, c.out_f32);
-        if (c.out_f32 && (rc = enhance_impl(h, c.img8, H, W, tile, pad, nullptr, c.out_f32))) return rc;
-        return c.out_u8 ? enhance_impl(h, c.img8, H, W, tile, pad, c.out_u8, nullptr, false, c.swap_rb, c.prm) : S2SR_OK;
-    }
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = h->stream;
-    const bool reflect = PH != H || PW != W;
-    const int scale = h->cfg.scale, OH = H * scale, OW = W * scale, esz = in16 ? 2 : 1;
-    const int nx = job.nx, ny = job.ny, wh = job.wh, ww = job.ww;
-    void* out_q = in16 ? (void*)c.out_u16 : (void*)c.out_u8;
-    const Mosaic mo = pick_mosaic(h, nx * ny, wh, ww);   // ONE plan for the job: every chunk runs in its workspace geometry
-    // one chunk with out_f32: the float image is blended from all the tiles at the end
-    chunk_r0 = !c.out_f32 ? plan_chunk_rows(h, job, mo) : std::vector<int>{0, ny};
-    const int nchunks = (int)chunk_r0.size() - 1, carry = nchunks > 1 ? 1 : 0;
-    auto last_row = [&](int y) { return (int)rows[(size_t)kBlendStride * y + 2]; };
-    // the bands, on the host first: every row reads window rows its chunk's buffer holds (its own, and the one carried in front)
-    int max_rows = 0;
-    for (int k = 0, yb = 0; k < nchunks; ++k) {
-        const int r0 = chunk_r0[k], r1 = chunk_r0[k + 1] < ny ? chunk_r0[k + 1] : ny;
-        if (r1 - r0 > max_rows) max_rows = r1 - r0;
-        int ye = OH;
-        if (r1 < ny)
-            for (ye = yb; ye < OH && last_row(ye) < r1; ++ye) {}
-        if (const char* why = blend_check_band(rows.data(), yb, ye, k > 0 ? r0 - carry : r0, r1)) return fail(h, S2SR_E_INVALID, why);
-        yb = ye;
-    }
-    blend_device_axis(rows.data(), (int64_t)PH * scale);
-    blend_device_axis(cols.data(), (int64_t)PW * scale);
-    const size_t ipx = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
-    const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;      // samples per window, in and out
-    const size_t q_bytes = (opx * esz + 255) & ~(size_t)255;     // scratch 1: the quantised image, then (out_f32) the fp32 image
-    const size_t row_b = (size_t)OW * 3 * esz;                   // bytes of one output row
-    if ((rc = ensure_scratch(h, 0, ipx * esz))) return rc;
-    if ((rc = ensure_scratch(h, 1, q_bytes + (c.out_f32 ? opx * 4 : 0)))) return rc;
-    if ((rc = ensure_scratch(h, 2, (size_t)nx * ny * win_in * esz))) return rc;
-    if ((rc = ensure_scratch(h, 3, (job.rects.size() + rows.size() + cols.size()) * 4))) return rc;
-    if ((rc = ensure_scratch(h, 4, (size_t)(max_rows + carry) * nx * win_out * sizeof(float)))) return rc;
-    int fin_rows = 0, nfin = 0;          // finishing bands of the post-process, as enhance_impl cuts them
-    if (c.prm) {
-        fin_rows = (int)(((size_t)48 << 20) / row_b) & ~31;
-        if (fin_rows < 64) fin_rows = 64;
-        nfin = (OH + fin_rows - 1) / fin_rows;
-        if ((rc = pp_band_begin_locked(h, OH, OW, c.prm, c.swap_rb ? 3 : 0, st))) return rc;   // (allocates: before anything is enqueued)
-    }
-    struct CloseRun { s2sr_handle* h; ~CloseRun() { if (h) h->ppb.open = false; } } close_run{c.prm ? h : nullptr};   // as enhance_impl
-    if ((rc = ensure_group_events(h, nchunks + nfin + 1))) return rc;
-    int32_t* d_rects = (int32_t*)h->d_scratch[3];
-    int32_t* d_rows = d_rects + job.rects.size();
-    int32_t* d_cols = d_rows + rows.size();
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], in16 ? (const void*)c.img16 : (const void*)c.img8, ipx * esz, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(d_rects, job.rects.data(), job.rects.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(d_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(d_cols, cols.data(), cols.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));   // the tables are host vectors of this call
-    if (in16) {
-        HIPCHK(h, launch_gather_windows((const uint16_t*)h->d_scratch[0], H, W, d_rects, nx * ny, wh, ww, (uint16_t*)h->d_scratch[2], st));
-    } else {
-        if (c.swap_rb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[0], (size_t)H * W, (uint8_t*)h->d_scratch[0], st));
-        HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_rects, nx * ny, wh, ww, reflect, (uint8_t*)h->d_scratch[2], st));
-    }
-    uint8_t* d_q = (uint8_t*)h->d_scratch[1];
-    float* d_buf = (float*)h->d_scratch[4];                      // [carry window row | the chunk's window rows]
-    float* d_tiles = d_buf + (size_t)carry * nx * win_out;
-    const int oth = wh * scale, otw = ww * scale;
-    int prev_n = 0;                                              // windows of the chunk before
-    auto forward = [&](int t0, int n) -> int {
-        if (t0 > 0)   // the last window row of the chunk before, to the front of the buffer (its band is stitched: same stream)
-            HIPCHK(h, hipMemcpyAsync(d_buf, d_tiles + (size_t)(prev_n - nx) * win_out, (size_t)nx * win_out * sizeof(float), hipMemcpyDeviceToDevice, st));
-        prev_n = n;
-        const TileIn in = in16 ? TileIn::u16((const uint16_t*)h->d_scratch[2] + (size_t)t0 * win_in, c.lo, c.hi)
-                               : TileIn::u8((const uint8_t*)h->d_scratch[2] + (size_t)t0 * win_in);
-        return forward_dev(h, st, in, n, wh, ww, TileOut{nullptr, d_tiles}, mo.on() ? &mo : nullptr);
-    };
-    // rows [yb, ye) into the quantised image; the buffer's first tile is window t0 - carry * nx
-    auto paste = [&](int t0, int yb, int ye) -> int {
-        Scope sc(h, st, F_MISC, 0.0, (double)(ye - yb) * OW * 3.0 * (4.0 + esz));
-        const int32_t* r = d_rows + (size_t)kBlendStride * yb;
-        if (in16) HIPCHK(h, launch_stitch_blend(d_buf, nx, t0 - carry * nx, oth, otw, r, d_cols, ye - yb, OW, c.lo, c.hi, (uint16_t*)(d_q + (size_t)yb * row_b), st));
-        else HIPCHK(h, launch_stitch_blend(d_buf, nx, t0 - carry * nx, oth, otw, r, d_cols, ye - yb, OW, c.swap_rb && !c.prm, d_q + (size_t)yb * row_b, st));
-        return S2SR_OK;
-    };
-    auto finish = [&](int t0, int yb, int ye) -> int {
-        if (!out_q) return S2SR_OK;
-        if (int prc = paste(t0, yb, ye)) return prc;
-        return c.prm ? pp_band_hist_locked(h, d_q, yb, ye, st) : S2SR_OK;   // (the post-process exchanges R and B itself)
-    };
-    // with a post-process the bands leave through its finishing pass; with out_f32 (one chunk) both images leave behind the float blend
-    if ((rc = run_chunks(h, st, job, chunk_r0, OH, forward, finish, (uint8_t*)out_q, d_q, row_b, out_q && !c.prm && !c.out_f32, last_row))) return rc;
-    if (c.prm && (rc = pp_finish_bands(h, st, d_q, c.out_u8, OH, row_b, fin_rows, nfin, nchunks))) return rc;
-    if (c.out_f32) {
-        float* d_f = (float*)((char*)h->d_scratch[1] + q_bytes);
-        HIPCHK(h, launch_stitch_blend(d_buf, nx, 0, oth, otw, d_rows, d_cols, OH, OW, d_f, st));
-        HIPCHK(h, hipEventRecord(h->group_done[nchunks + nfin], st));
-        if (out_q) {
-            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
-            if ((rc = d2h_staged(h, (uint8_t*)out_q, d_q, OH * row_b, true))) return rc;
-        }
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks + nfin], 0));
-        if ((rc = d2h_staged(h, (uint8_t*)c.out_f32, (const uint8_t*)d_f, opx * 4, true))) return rc;
-    }
-    HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-    HIPCHK(h, hipStreamSynchronize(st));
-    if (in16 && c.out_u16) { h->disp_slot = 1; h->disp_h = OH; h->disp_w = OW; }   // as enhance16_impl
-    return S2SR_OK;
-}
-
+// The seam-blended doors.  An image the switch leaves whole, or whose plan has no ramp (pad 0), is pasted as the default doors
+// paste it (an 8-bit call for both images then runs the net twice).
 int s2sr_enhance_blend_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
                           int32_t swap_rb, uint8_t* out_u8, float* out_f32) {
-    BlendCall c;
-    c.img8 = img; c.prm = prm; c.swap_rb = swap_rb != 0; c.out_u8 = out_u8; c.out_f32 = out_f32;
+    EnhanceCall c = call_u8(img, H, W, tile, pad, out_u8, out_f32);
+    c.blend = true; c.prm = prm; c.swap_rb = swap_rb != 0;
+    c.required = "s2sr_enhance_blend: an image, positive sizes and at least one output are required";
     if (!img) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: an image is required") : S2SR_E_INVALID;
-    RUN_WITH_STREAM_RECOVERY(h, enhance_blend_impl(h, c, H, W, tile, pad));
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
 }
 
 int s2sr_enhance_blend_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
                            uint16_t* out_u16, float* out_f32) {
-    BlendCall c;
-    c.img16 = img; c.lo = lo; c.hi = hi; c.out_u16 = out_u16; c.out_f32 = out_f32;
+    EnhanceCall c = call_u16(img, H, W, tile, pad, lo, hi, out_u16, out_f32);
+    c.blend = true;
+    c.required = "s2sr_enhance_blend: an image, positive sizes and at least one output are required";
     if (!img) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u16: an image is required") : S2SR_E_INVALID;
-    RUN_WITH_STREAM_RECOVERY(h, enhance_blend_impl(h, c, H, W, tile, pad));
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
 }
 
 // The blend tables of a PH x PW image's window job (pure host arithmetic, for the CPU tests): six ints per output row / column,
@@ -876,11 +756,9 @@ int s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_
         const s2sr_window& w = p.wins[first + t];
         rects[4 * t] = w.y1; rects[4 * t + 1] = w.y2; rects[4 * t + 2] = w.x1; rects[4 * t + 3] = w.x2;
     }
-    rc = ensure_scratch(h, 3, rects.size() * 4);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[3], rects.data(), rects.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipStreamSynchronize(st));
-    HIPCHK(h, launch_gather_windows((const uint8_t*)d_img, H, W, (const int32_t*)h->d_scratch[3], count, wh, ww, PH != H || PW != W, (uint8_t*)d_tiles, st));
+    int32_t* d_tab[3];
+    if ((rc = upload_tables(h, st, rects, {}, {}, d_tab))) return rc;
+    HIPCHK(h, launch_gather_windows((const uint8_t*)d_img, H, W, d_tab[0], count, wh, ww, PH != H || PW != W, (uint8_t*)d_tiles, st));
     return S2SR_OK;
 }
 
@@ -959,10 +837,6 @@ int s2sr_copy_to_host(s2sr_handle* h, void* dst, const void* d_src, size_t bytes
     HIPCHK(h, hipEventRecord(h->host_copy_ev, (hipStream_t)stream));
     HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->host_copy_ev, 0));
     return d2h_staged(h, (uint8_t*)dst, (const uint8_t*)d_src, bytes, false);
-}
-
-int s2sr_tile_process_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out) {
-    RUN_WITH_STREAM_RECOVERY(h, enhance_impl(h, img, H, W, tile, pad, nullptr, out, true));
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "band_plan.h"
 #include "engine_internal.h"
 
 using namespace s2sr;
@@ -110,6 +111,16 @@ int s2sr_debug_plan_windows(int32_t PH, int32_t PW, int32_t tile, int32_t pad, i
     memcpy(rects, job.rects.data(), job.rects.size() * 4);
     memcpy(rm, job.rm.data(), job.rm.size() * 4);
     memcpy(cm, job.cm.data(), job.cm.size() * 4);
+    return S2SR_OK;
+}
+
+int s2sr_debug_plan_bands(const int32_t* chunk_r0, int32_t nchunks, int32_t ny, int32_t OH, const int32_t* last_row, int32_t* bands) {
+    if (!chunk_r0 || !last_row || !bands || nchunks <= 0 || ny <= 0 || OH <= 0 || chunk_r0[0] != 0 || chunk_r0[nchunks] != ny) return S2SR_E_INVALID;
+    for (int k = 0; k < nchunks; ++k)
+        if (chunk_r0[k] >= chunk_r0[k + 1]) return S2SR_E_INVALID;
+    std::vector<int> end(nchunks);
+    plan_bands(chunk_r0, nchunks, ny, OH, last_row, 1, end.data());
+    for (int k = 0; k < nchunks; ++k) { bands[2 * k] = k ? end[k - 1] : 0; bands[2 * k + 1] = end[k]; }
     return S2SR_OK;
 }
 

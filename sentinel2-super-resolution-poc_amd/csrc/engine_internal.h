@@ -231,7 +231,7 @@ struct s2sr_handle {
     hipEvent_t host_copy_ev = nullptr;          // s2sr_copy_to_host: orders the copy stream behind the caller's stream
     void* host_arena = nullptr;                 // page-locked host block of the tile-PNG stage (stats back, plan up): grown on demand, kept
     size_t host_arena_bytes = 0;
-    // the banded post-process in progress on this handle (s2sr_pp_band_*_dev, enhance_impl): geometry, channel order, how far the
+    // the banded post-process in progress on this handle (s2sr_pp_band_*_dev, or a whole-image job: enhance_locked): geometry, channel order, how far the
     // CLAHE'd rows and the finished rows reach
     struct PPBand {
         bool open = false, lut = false;

@@ -7,7 +7,7 @@ is an independent forward.  Collectives used, and only these:
   * broadcast of the flat weight blob from rank 0, once per model load;
   * gather (to the one rank that consumes the mosaic) or all-gather of the ranks' u8 output windows.
 
-The AOI path (`enhance_distributed`) is chunked like the single-GPU one (engine_aoi.hip enhance_impl): a rank's
+The AOI path (`enhance_distributed`) is chunked like the single-GPU one (engine_aoi.hip enhance_locked): a rank's
 contiguous block of windows is cut into chunks (whole launch groups of window mosaics, shrinking towards the end:
 `native.plan_chunks`), all chunks are enqueued on the compute stream up front, and chunk k's outputs travel on a
 communication stream while chunk k+1 computes -- into views of ONE preallocated buffer on the consumer, at the

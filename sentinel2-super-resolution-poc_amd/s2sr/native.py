@@ -184,6 +184,7 @@ _PROTOS = {
     "s2sr_debug_plan_chunks": (C.c_int, [C.c_int32] * 6 + [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "s2sr_debug_plan_windows": (C.c_int, [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "s2sr_debug_plan_blend": (C.c_int, [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]),
+    "s2sr_debug_plan_bands": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "s2sr_debug_get_config": (C.c_int, [C.c_void_p, C.POINTER(DebugConfig)]),
     "s2sr_debug_conv_trunk": (C.c_int, [C.c_void_p, C.POINTER(DebugTrunkArgs)]),
     "s2sr_debug_forward_taps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(DebugTaps)]),
@@ -418,6 +419,20 @@ def plan_blend(PH: int, PW: int, tile: int, pad: int, scale: int = 4, tiled: boo
     if rc:
         raise S2srError(f"s2sr_debug_plan_blend failed ({_ERR.get(rc, rc)})")
     return rows, cols
+
+
+def plan_bands(chunk_r0, ny: int, OH: int, last_row) -> np.ndarray:
+    """bands[nchunks, 2]: the output rows [yb, ye) each chunk of a whole-image call makes final.  chunk_r0: the first window row of
+    each chunk, then ny; last_row[OH]: the last window row every output row reads (plan_windows' rm[:, 0], plan_blend's
+    rows[:, 2]); host arithmetic, works without a GPU."""
+    r0, last = np.ascontiguousarray(chunk_r0, np.int32), np.ascontiguousarray(last_row[:OH], np.int32)
+    if r0.ndim != 1 or len(r0) < 2 or last.shape != (OH,):
+        raise ValueError("chunk_r0 holds nchunks + 1 window rows, last_row at least OH rows")
+    bands = np.zeros((len(r0) - 1, 2), np.int32)
+    rc = load_library().s2sr_debug_plan_bands(_ptr(r0), len(r0) - 1, ny, OH, _ptr(last), _ptr(bands))
+    if rc:
+        raise S2srError(f"s2sr_debug_plan_bands failed ({_ERR.get(rc, rc)})")
+    return bands
 
 
 def _ptr(a: np.ndarray):

@@ -7,6 +7,7 @@
 
 #include <vector>
 
+#include "band_plan.h"
 #include "blend_plan.h"
 
 using namespace s2sr;
@@ -111,6 +112,25 @@ int main() {
         // bands: rows of window 1 are not in a buffer that holds window 0 only, nor in one that starts at window 2
         EXPECT(blend_check_band(tab.data(), 0, a.n, 0, 1) != nullptr && blend_check_band(tab.data(), 0, a.n, 2, a.nwin) != nullptr);
         EXPECT(blend_check_band(tab.data(), 0, 8, 0, 1) == nullptr && blend_check_band(tab.data(), 5, 5, 7, 7) == nullptr);
+        // the bands of every cut of the axis' windows into two and three chunks (band_plan.h), over the paste map and over the
+        // table's later window: in order, up to the axis' end (also when the output is cropped by a row), inside their chunk's buffer
+        for (int r1 = 1; r1 < a.nwin; ++r1)
+            for (int r2 = r1; r2 < a.nwin; ++r2)
+                for (int crop = 0; crop < 2; ++crop) {
+                    std::vector<int> r0 = {0, r1};
+                    if (r2 > r1) r0.push_back(r2);
+                    r0.push_back(a.nwin);
+                    const int nch = (int)r0.size() - 1, OH = (int)a.n - crop;
+                    std::vector<int> end(nch), end_map(nch);
+                    plan_bands(r0.data(), nch, a.nwin, OH, tab.data() + 2, kBlendStride, end.data());
+                    plan_bands(r0.data(), nch, a.nwin, OH, a.map.data(), 2, end_map.data());
+                    EXPECT(end[nch - 1] == OH && end_map[nch - 1] == OH);
+                    for (int k = 0; k < nch; ++k) {
+                        const int yb = k ? end[k - 1] : 0;
+                        EXPECT(yb <= end[k] && end[k] <= end_map[k]);      // a ramp's rows wait for the later window
+                        EXPECT(blend_check_band(tab.data(), yb, end[k], r0[k] - (k > 0), r0[k + 1]) == nullptr);
+                    }
+                }
     }
     if (failures) { printf("%d failure(s)\n", failures); return 1; }
     printf("ok: %ld seams, %ld with a shortened ramp\n", seams, shortened);

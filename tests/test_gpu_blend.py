@@ -259,6 +259,41 @@ def test_refusals_leave_the_engine_working():
     assert np.array_equal(e.enhance_blend_u8(img, tile=tile, pad=pad), want)
 
 
+def test_two_threads_on_one_handle_get_the_bytes_of_calls_made_alone(monkeypatch):
+    """A whole-image call holds the handle's lock from its checks to its last synchronise (engine_aoi.hip enhance_call): the
+    scratch areas, the carry buffer and the tables of a three-chunk blend call are not another thread's to rewrite in between."""
+    import threading
+    e = gpu_engines.fresh(monkeypatch, {}, 1, HP)
+    try:
+        H, W, tile, pad = CHUNKED
+        img, img16 = image(H, W), image(H, W).astype(np.uint16) * 257
+        calls = {"blend_u8": lambda: e.enhance_blend_u8(img, tile=tile, pad=pad), "u8": lambda: e.enhance_u8(img, tile=tile, pad=pad),
+                 "blend_u16": lambda: e.enhance_blend_u16(img16, tile=tile, pad=pad)}
+        alone = {k: f().copy() for k, f in calls.items()}
+        got, errors = {}, []
+
+        def run(name, seq):
+            try:
+                got[name] = [(k, calls[k]().copy()) for k in seq]
+            except Exception as ex:       # noqa: BLE001 (reported below, on the test's thread)
+                errors.append((name, repr(ex)))
+
+        threads = [threading.Thread(target=run, args=("a", ["blend_u8"] * 3)),
+                   threading.Thread(target=run, args=("b", ["u8", "blend_u16", "u8"]))]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join(120)
+        assert not any(t.is_alive() for t in threads) and not errors, errors
+        assert [len(v) for v in got.values()] == [3, 3]
+        for name, results in got.items():
+            for i, (k, a) in enumerate(results):
+                same(a, alone[k], f"thread {name} call {i} ({k}) against the call made alone")
+        same(e.enhance_u8(img, tile=tile, pad=pad), alone["u8"], "a plain enhance_u8 afterwards")
+    finally:
+        e.close()
+
+
 # ---- the app -----------------------------------------------------------------------------------------------------------------------
 def _patch_weights(monkeypatch, tmp_path, nb_by_name):
     """Seeded synthetic checkpoints where the drop-in looks for them (tests/test_gpu_app.py)."""

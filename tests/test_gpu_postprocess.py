@@ -147,7 +147,7 @@ def _banded(eng, img, prm, hist_cuts, row_cuts, order=0, in_place=False):
 
 
 def test_banded_postprocess_gives_the_bytes_of_the_whole_image(eng):
-    """The band-wise route an AOI's mosaic takes (engine_aoi.hip enhance_impl, s2sr/dist.py: CLAHE histograms counted as the bands are
+    """The band-wise route an AOI's mosaic takes (engine_aoi.hip enhance_locked, s2sr/dist.py: CLAHE histograms counted as the bands are
     stitched, LUTs behind the last band, apply + sharpen band by band in front of the copy out) against the whole-image launch:
     ragged sizes (both CLAHE paddings, the reflected rows counted into the last tile row from whichever band holds them), images
     smaller than the grid (padding that bounces more than once), bands that are no multiple of any tile, one-row bands, in place,
