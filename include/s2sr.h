@@ -251,6 +251,36 @@ int  s2sr_enhance_blend_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_
 int  s2sr_enhance_blend_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo,
                             int32_t hi, uint16_t* out_u16 /* [4H,4W,3] or NULL */, float* out_f32 /* [4H,4W,3] or NULL */);
 
+/* Nodata-aware enhance, opt-in: pixels that were never measured (a clipped AOI, a swath edge, a cloud mask) are
+ * kept out of the net's way and come out as nodata again.  valid is uint8 [H, W], nonzero = valid.  Integers throughout:
+ *   fill (in front of the net, of the R / B exchange and of the window gather): a valid pixel is unchanged; an invalid pixel
+ *     (y, x) takes all three samples of the valid pixel (qy, qx) that minimises (d2, qy, qx) lexicographically,
+ *     d2 = (qy - y)^2 + (qx - x)^2, among those with d2 <= radius^2; none: it keeps its samples.  The image edge is not
+ *     replicated.  radius 1..64 (the app's default of 32 is policy, not a measurement).
+ *   mask (behind the paste and the post-process, before a byte leaves the device): output pixel (Y, X) is invalid iff input pixel
+ *     (Y / S, X / S) is, S = s2sr_config.scale; an invalid output pixel gets out_nodata in all three samples, a valid one is the
+ *     unmasked call's byte (also where it happens to equal out_nodata: the mask is the truth, the value only the file convention).
+ *   The post-process runs on the filled image: its CLAHE sees extrapolated ground, not a black plane.
+ * So a masked call's bytes are mask(unmasked door(fill(img))), and a mask that is valid everywhere gives the unmasked door's bytes.
+ * s2sr_enhance_masked_u8: the doors s2sr_enhance_u8 (prm NULL, swap_rb 0), s2sr_enhance_job_u8 (swap_rb 1) and, with blend != 0,
+ *   s2sr_enhance_blend_u8, with their sizes, scales and refusals.  s2sr_enhance_masked_u16: s2sr_enhance_u16 / _blend_u16; the
+ *   uint16 image it leaves on the device for s2sr_display_*_u16 is the masked one.  The fp32 images are the net's own output and
+ *   are not offered here.
+ * s2sr_fill_nodata_u8 / _u16: the fill alone, host image in, filled host image out (out may be img); no weights needed.
+ * S2SR_E_INVALID with a text, before the device is touched: m or m->valid NULL, radius outside 1..64, out_nodata outside 0..255
+ * (0..65535 for uint16).  The handle keeps working afterwards. */
+typedef struct s2sr_mask {
+    const uint8_t* valid;    /* [H, W], nonzero = valid */
+    int32_t radius;          /* fill radius, 1..64 */
+    int32_t out_nodata;      /* the value invalid output pixels get: 0..255, or 0..65535 */
+} s2sr_mask;
+int  s2sr_fill_nodata_u8(s2sr_handle* h, const uint8_t* img, const uint8_t* valid, int32_t H, int32_t W, int32_t radius, uint8_t* out);
+int  s2sr_fill_nodata_u16(s2sr_handle* h, const uint16_t* img, const uint8_t* valid, int32_t H, int32_t W, int32_t radius, uint16_t* out);
+int  s2sr_enhance_masked_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad,
+                            const s2sr_pp_params* prm /* or NULL */, int32_t swap_rb, int32_t blend, const s2sr_mask* m, uint8_t* out_u8);
+int  s2sr_enhance_masked_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo,
+                             int32_t hi, int32_t blend, const s2sr_mask* m, uint16_t* out_u16);
+
 /* Display rendering of a 16-bit image: the two passes over a uint16 [H, W, 3] interleaved image that reduce it to
  * the 8-bit image the PNG writer, the warp, the pyramid and the post-process take.  Neither entry needs weights.  What lies between
  * them -- percentile limits from the histogram, the stretch LUT -- is the caller's (s2sr/display.py).

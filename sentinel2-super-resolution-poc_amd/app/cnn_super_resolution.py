@@ -355,9 +355,30 @@ class RealESRGAN:
         self._engine = self.model.engine(self.device.index or 0)
         print(f"   Loaded {model_name} (x{self.scale})")
 
-    def enhance(self, img: np.ndarray) -> np.ndarray:
+    @staticmethod
+    def _mask_of(img: np.ndarray, valid, nodata, fill_radius):
+        """The mask of a nodata call -> (valid uint8 [H, W] or None, the value invalid output pixels get).  valid: the mask itself
+        (nonzero = valid); nodata: the value -- without `valid`, a pixel is invalid iff all three bands equal it.  Neither: None."""
+        from s2sr.nodata import check_args, mask_from_value
+        if valid is None and nodata is None:
+            return None, 0
+        check_args(nodata, fill_radius)
+        if nodata == "tag":
+            raise ValueError("nodata=\"tag\" belongs to the file-level jobs (app.wow_sr): an array has no tags")
+        if valid is None:
+            valid = mask_from_value(img, nodata)
+        valid = np.asarray(valid)
+        if valid.shape != img.shape[:2]:
+            raise ValueError(f"valid: expected shape {img.shape[:2]}, got {valid.shape}")
+        return valid, 0 if nodata is None else int(nodata)
+
+    def enhance(self, img: np.ndarray, valid=None, nodata=None, fill_radius: int = 32) -> np.ndarray:
         """HxWx3 uint8 (channel order as given) -> 4Hx4Wx3 uint8 (self.scale x: 2Hx2Wx3 for realesrgan_x2plus, whose odd
         sizes are reflect-padded by one row / column and cropped back, RealESRGANer's mod-2 rule).
+
+        valid / nodata (not in the reference): pixels that were never measured -- `valid` uint8 [H, W], or all
+        three bands equal to `nodata` -- are filled from their nearest valid neighbour within fill_radius in front of the net
+        and come out as `nodata` (0 without one) again; see native.Engine.enhance_masked_u8.
 
         Whole-image forward when h*w <= tile_size^2*4, otherwise the reference's window plan
         (tile_size + 2*tile_pad windows, halo crop, later windows overwrite) -- both inside
@@ -367,19 +388,25 @@ class RealESRGAN:
         if img.dtype != np.uint8:
             # the reference divides whatever it gets by 255 (:220); only u8 is on the native path
             raise TypeError(f"expected uint8 image, got {img.dtype}")
+        valid, out_nodata = self._mask_of(img, valid, nodata, fill_radius)
         with self._engine.chain_lock:        # (not between another job's enhance16 and its display rendering)
+            if valid is not None:
+                return self._engine.enhance_masked_u8(img, valid, radius=fill_radius, out_nodata=out_nodata, blend=self.seam_blend,
+                                                      tile=self.tile_size, pad=self.tile_pad)
             if self.seam_blend:
                 return self._engine.enhance_blend_u8(img, tile=self.tile_size, pad=self.tile_pad)
             return self._engine.enhance_u8(img, tile=self.tile_size, pad=self.tile_pad)
 
-    def enhance16(self, img: np.ndarray, value_range=None, display=None):
+    def enhance16(self, img: np.ndarray, value_range=None, display=None, valid=None, nodata=None, fill_radius: int = 32):
         """HxWx3 uint16 (channel order as given) -> 4Hx4Wx3 uint16, in the source's units: the 16-bit door of the native library
         (upstream RealESRGANer's max_range = 65535 branch; the reference has none).  value_range (lo, hi), None = (0, 65535): the
         net sees (clip(v, lo, hi) - lo) / (hi - lo), the output is lo + rint(clip(y, 0, 1) * (hi - lo)).  Same whole / tiled
         switch and window plan as `enhance`.  The x4 RRDB models only (realesrgan_x4, realesrgan_anime).
         display (a s2sr.display.Stretch or a dict of its fields): -> (out16, display_u8, info), the 8-bit display rendering of the
         output (percentile stretch, s2sr/display.py) made from the output's device copy, without a second upload; per-band
-        limits are in the channel order of `img`."""
+        limits are in the channel order of `img`.
+        valid / nodata / fill_radius: as `enhance`; a display stretch that names no nodata of its own leaves the job's out of its
+        statistics."""
         if self.scale != 4 or getattr(self.model, "arch", "rrdb") != "rrdb":
             raise ValueError(f"enhance16 is built for the x4 RRDB models, not {self.model_name}")
         if img.ndim != 3 or img.shape[2] != 3:
@@ -389,27 +416,41 @@ class RealESRGAN:
         lo, hi = (0, 65535) if value_range is None else (int(value_range[0]), int(value_range[1]))
         if not (0 <= lo < hi <= 65535):
             raise ValueError(f"value_range {value_range}: need 0 <= lo < hi <= 65535")
-        door = self._engine.enhance_blend_u16 if self.seam_blend else self._engine.enhance_u16
+        valid, out_nodata = self._mask_of(img, valid, nodata, fill_radius)
+        if valid is None:
+            door = self._engine.enhance_blend_u16 if self.seam_blend else self._engine.enhance_u16
+        else:
+            def door(img, lo, hi, tile, pad):
+                return self._engine.enhance_masked_u16(img, valid, lo, hi, radius=fill_radius, out_nodata=out_nodata, blend=self.seam_blend,
+                                                       tile=tile, pad=pad)
         if display is None:
             with self._engine.chain_lock:
                 return door(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
         from s2sr.display import Stretch, render_u16
         stretch = Stretch.of(display)
+        if nodata is not None and stretch.nodata is None:
+            import dataclasses
+            stretch = dataclasses.replace(stretch, nodata=out_nodata)
         with self._engine.chain_lock:        # the engine is shared by every job of the process: nothing between the door and the rendering
             out16 = door(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
             disp, info = render_u16(None, stretch, self._engine, shape=out16.shape[:2])
         return out16, disp, info
 
-    def enhance_job(self, rgb: np.ndarray, post=None) -> np.ndarray:
+    def enhance_job(self, rgb: np.ndarray, post=None, valid=None, nodata=None, fill_radius: int = 32) -> np.ndarray:
         """What a job does around `enhance` (wow_sr.py:85-110, farm_sr.py:156-178) in one native call: RGB in, RGB2BGR, the net,
         BGR2RGB, the crop-visibility post-process `post` (native.pp_wow() / pp_farm(); None: none), RGB out.  The same bytes as
         `enhance(rgb[:, :, ::-1])[:, :, ::-1]` followed by the post-process -- one upload and one download instead of three
-        round trips and two host-side channel flips of the 16x image (tests/test_gpu_app.py)."""
+        round trips and two host-side channel flips of the 16x image (tests/test_gpu_app.py).
+        valid / nodata / fill_radius: as `enhance`; the post-process runs on the filled image, the mask goes on last."""
         if rgb.ndim != 3 or rgb.shape[2] != 3:
             raise ValueError(f"expected HxWx3 image, got shape {rgb.shape}")
         if rgb.dtype != np.uint8:
             raise TypeError(f"expected uint8 image, got {rgb.dtype}")
+        valid, out_nodata = self._mask_of(rgb, valid, nodata, fill_radius)
         with self._engine.chain_lock:
+            if valid is not None:
+                return self._engine.enhance_masked_u8(rgb, valid, radius=fill_radius, out_nodata=out_nodata, prm=post, swap_rb=True,
+                                                      blend=self.seam_blend, tile=self.tile_size, pad=self.tile_pad)
             if self.seam_blend:
                 return self._engine.enhance_blend_u8(rgb, post, swap_rb=True, tile=self.tile_size, pad=self.tile_pad)
             return self._engine.enhance_job_u8(rgb, post, tile=self.tile_size, pad=self.tile_pad)

@@ -18,7 +18,7 @@ from collections import deque
 from datetime import datetime
 from email.parser import BytesParser
 from pathlib import Path
-from typing import Callable, List, Optional
+from typing import Callable, List, Optional, Union
 
 from fastapi import BackgroundTasks, FastAPI, HTTPException, Request
 from pydantic import BaseModel
@@ -43,6 +43,8 @@ class WowRequest(BaseModel):         # main.py:200-208
     seam_blend: bool = False         # not in the reference: cross-fade the window overlaps of the tiled stitch
     bit_depth: int = 8               # not in the reference: 16 = a uint16 GeoTIFF through the net in its own units (app.wow_sr)
     display: Optional[dict] = None   # ... and its 8-bit rendering for the PNG and the tiles (fields of s2sr.display.Stretch); 16-bit jobs only
+    nodata: Optional[Union[int, str]] = None   # not in the reference: the value of the pixels that were never measured, or "tag" (app.wow_sr)
+    fill_radius: int = 32            # ... and how far they are filled from their valid neighbours in front of the net (1..64)
 
 
 class SRResponse(BaseModel):         # main.py:230-235
@@ -221,7 +223,7 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
 
     def run_wow_job(job_id, input_file, output_dir, enhance_crops, auto_fetch=True, max_age_days=30,
                     max_cloud_cover=30.0, force_fetch=False, model="realesrgan_x4", seam_blend=False, bit_depth=8,
-                    display=None):                                           # main.py:290-368
+                    display=None, nodata=None, fill_radius=32):              # main.py:290-368
         try:
             if input_file is None and auto_fetch:
                 _set(job_id, status="fetching",
@@ -240,6 +242,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                 extra["bit_depth"] = bit_depth
             if display is not None:
                 extra["display"] = display
+            if nodata is not None:
+                extra.update(nodata=nodata, fill_radius=fill_radius)
             result = process_wow_sr(input_tif=input_file, output_dir=output_dir, enhance_crops=enhance_crops, model=model, **extra)
             _set(job_id, status="tiling", message="Generating tiles from WOW SR image...")
             # a 16-bit job's tiles show the rendering of its PNG: the job's stretch with the limits it found
@@ -309,6 +313,12 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                 Stretch.of(request.display)
             except (ValueError, TypeError) as e:
                 raise HTTPException(status_code=400, detail=f"display: {e}")
+        if request.nodata is not None:
+            try:
+                from s2sr.nodata import check_args
+                check_args(request.nodata, request.fill_radius)
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
         job_id = f"wow_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
         output_dir = data_dir / "wow" / job_id
         output_dir.mkdir(parents=True, exist_ok=True)
@@ -323,7 +333,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                                   request.auto_fetch, request.max_age_days, request.max_cloud_cover, request.force_fetch,
                                   **({"seam_blend": True} if request.seam_blend else {}),
                                   **({"bit_depth": request.bit_depth} if request.bit_depth != 8 else {}),
-                                  **({"display": request.display} if request.display is not None else {}))
+                                  **({"display": request.display} if request.display is not None else {}),
+                                  **({"nodata": request.nodata, "fill_radius": request.fill_radius} if request.nodata is not None else {}))
         msg = (f"WOW SR started: {input_file.name} -> Real-ESRGAN x4 + Enhanced" if input_file else
                f"WOW SR started: auto-fetching best image (last {request.max_age_days}d, cloud <={request.max_cloud_cover}%)")
         return SRResponse(job_id=job_id, status="queued", message=msg)

@@ -35,13 +35,21 @@ def _enhance_for_crops(img: np.ndarray) -> np.ndarray:
     return _pp_engine().postprocess_u8(img, native.pp_wow())
 
 
+def _nodata_block(value, valid: np.ndarray, fill_radius: int) -> dict:
+    """The metadata of a nodata job."""
+    return {"value": value, "invalid_pixels": int(valid.size - np.count_nonzero(valid)), "fill_radius": int(fill_radius)}
+
+
 def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend: bool = False, display=None,
-                    enhance_crops: bool = False) -> Tuple[Path, dict]:
+                    enhance_crops: bool = False, nodata=None, fill_radius: int = 32) -> Tuple[Path, dict]:
     """bit_depth=16 of apply_wow_sr: a uint16 GeoTIFF read raw, value_range = the image's own (min, max) -- the reference's
     min-max (wow_sr.py:67-73) minus its quantisation to 8 bits -- the net fed BGR as ever (:85,94), RealESRGAN.enhance16, RGB back,
     a uint16 GeoTIFF out.  Without `display`: no PNG (the encoder is 8-bit) and no crop-visibility post-process (OpenCV's 8-bit
     arithmetic).  With it (s2sr.display.Stretch or a dict of its fields): the output's display rendering, made on the device from
-    the output's copy there, is written as the PNG, after the crop-visibility post-process when enhance_crops; the GeoTIFF stays raw."""
+    the output's copy there, is written as the PNG, after the crop-visibility post-process when enhance_crops; the GeoTIFF stays raw.
+    nodata (an integer, or "tag"): see apply_wow_sr; the value range is that of the valid pixels (s2sr.nodata.valid_range), the
+    GeoTIFF declares the value, the PNG (with `display`) carries the mask as alpha, and the stretch leaves the value out of its
+    statistics unless it names a nodata of its own."""
     import dataclasses
 
     from s2sr import rasterio_lite as rio
@@ -56,17 +64,23 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
         raise ValueError(f"bit_depth=16 needs a uint16 GeoTIFF: {e}") from e
     if img.dtype != np.uint16:
         raise ValueError(f"bit_depth=16 needs a uint16 GeoTIFF, {input_path} holds {img.dtype}")
-    lo, hi = int(img.min()), int(img.max())
-    if hi == lo:                      # a constant raster: any range that contains it
-        lo, hi = (lo - 1, hi) if hi > 0 else (0, 1)
+    from s2sr.nodata import mask_from_value, valid_range
+    valid = value = None
+    if nodata is not None:
+        value = rio.resolve_nodata(nodata, georef, input_path)
+        if not 0 <= value <= 65535 or value != int(value):
+            raise ValueError(f"nodata {value!r}: a uint16 raster takes an integer in 0..65535")
+        valid = mask_from_value(img, value)
+    lo, hi = valid_range(img, valid)
+    mask_kw = {} if valid is None else {"valid": valid, "nodata": value, "fill_radius": fill_radius}
     esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}))
     display_rgb = info = None
     if stretch is None:
-        out_bgr = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi))
+        out_bgr = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), **mask_kw)
     else:
         # the device copy is BGR like the net's input: explicit per-band limits go in reversed, the info's come back reversed
         bgr = stretch if stretch.limits is None else dataclasses.replace(stretch, limits=stretch.limits[::-1])
-        out_bgr, disp_bgr, info = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), display=bgr)
+        out_bgr, disp_bgr, info = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), display=bgr, **mask_kw)
         display_rgb = np.ascontiguousarray(disp_bgr[:, :, ::-1])
         info = dict(info, limits=info["limits"][::-1])
         if enhance_crops:
@@ -77,9 +91,9 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     del esrgan
     final_output = Path(output_path).with_suffix(".tif")
     final_output.parent.mkdir(parents=True, exist_ok=True)
-    rio.write_geotiff_rgb16(final_output, output_rgb, georef.scaled(scale))
+    rio.write_geotiff_rgb16(final_output, output_rgb, georef.scaled(scale), **({} if valid is None else {"nodata": value}))
     if display_rgb is not None:
-        rio.write_png(final_output.with_suffix(".png"), display_rgb)
+        rio.write_png(final_output.with_suffix(".png"), display_rgb, **({} if valid is None else {"valid": valid, "valid_scale": scale}))
     crops = display_rgb is not None and enhance_crops
     metadata = {
         "input_file": str(input_path),
@@ -101,10 +115,17 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
         metadata["seam_blend"] = True
     if info is not None:
         metadata["display"] = info
+    if valid is not None:
+        metadata["nodata"] = _nodata_block(value, valid, fill_radius)
     return final_output, metadata
 
 
-def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None) -> None:
+def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=None, fill_radius: int = 32) -> None:
+    from s2sr.nodata import check_args
+    check_args(nodata, fill_radius)
+    if nodata is not None and nodata != "tag" and not 0 <= int(nodata) <= 65535:
+        # (compared with the bands as stored: an 8-bit job of a uint16 raster names the uint16 value)
+        raise ValueError(f"nodata {nodata!r}: an integer in 0..65535")
     if bit_depth not in (8, 16):
         raise ValueError(f"bit_depth {bit_depth!r}: 8 or 16")
     if display is not None:
@@ -118,18 +139,24 @@ def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None) -> None:
 
 
 def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True,
-                 model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None) -> Tuple[Path, dict]:
+                 model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None, nodata=None,
+                 fill_radius: int = 32) -> Tuple[Path, dict]:
     """Reference wow_sr.py:28-184 -- same outputs (GeoTIFF and/or PNG) and metadata dict.  bit_depth=16 (not in the reference): a
     uint16 GeoTIFF goes through the net without the 8-bit squeeze and comes back as a uint16 GeoTIFF (_apply_wow_sr16).
     display (bit_depth=16 only; a s2sr.display.Stretch or a dict of its fields): the job also writes the PNG, from the output's
     display rendering (percentile stretch); enhance_crops then runs on that image; the metadata gains "display", and only then.
     seam_blend (not in the reference): the tiled stitch cross-fades the window overlaps (RealESRGAN(seam_blend=True)); the metadata
-    gains "seam_blend": true, and only then."""
+    gains "seam_blend": true, and only then.
+    nodata (not in the reference): None, an integer, or "tag" = the file's GDAL_NODATA tag (a ValueError if it
+    has none).  A pixel whose bands 1-3 all equal it was never measured: it is filled from its nearest valid neighbour within
+    fill_radius (1..64) in front of the net, the post-process runs on the filled image, and the outputs say which pixels they
+    are -- the GeoTIFF carries the GDAL_NODATA tag and the value in those pixels, the PNG is RGBA with alpha 255 x mask.  The
+    metadata gains "nodata": {"value", "invalid_pixels", "fill_radius"}, and only then."""
     from s2sr import rasterio_lite as rio
 
-    _check_bit_depth(bit_depth, enhance_crops, display)
+    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius)
     if bit_depth == 16:
-        return _apply_wow_sr16(input_path, output_path, model, seam_blend, display, enhance_crops)
+        return _apply_wow_sr16(input_path, output_path, model, seam_blend, display, enhance_crops, nodata, fill_radius)
 
     model_display = {"realesrgan_x4": "Real-ESRGAN x4",
                      "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)",
@@ -139,7 +166,13 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
                      "realesr_animevideov3": "Real-ESRGAN animevideov3 (compact)"}.get(model, model)
     print(f"\nWOW Super-Resolution ({model_display} + Enhanced)\n   Input: {input_path}")
     input_path = Path(input_path)
-    img, georef = rio.read_rgb_u8(input_path)           # u8 RGB (min-max normalised if >255, :67-73)
+    valid = value = None
+    if nodata is None:
+        img, georef = rio.read_rgb_u8(input_path)           # u8 RGB (min-max normalised if >255, :67-73)
+    else:
+        img, georef, valid, value = rio.read_rgb_u8_nodata(input_path, nodata)
+    # the 8-bit image's invalid pixels get the value where it is one of its own, 0 otherwise (the mask is the truth: alpha, metadata)
+    out_nodata = value if valid is not None and 0 <= value <= 255 and value == int(value) else 0
     original_shape = img.shape[:2]
 
     pipeline_stages = []
@@ -148,7 +181,9 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
     # RGB2BGR -> enhance -> BGR2RGB -> _enhance_for_crops (:85-110) as ONE native call: the 16x image crosses PCIe once
     if enhance_crops:
         print("   Stage 2/2: Crop visibility enhancement...")
-    if hasattr(esrgan, "enhance_job"):
+    if valid is not None:
+        output_rgb = esrgan.enhance_job(img, native.pp_wow() if enhance_crops else None, valid=valid, nodata=int(out_nodata), fill_radius=fill_radius)
+    elif hasattr(esrgan, "enhance_job"):
         output_rgb = esrgan.enhance_job(img, native.pp_wow() if enhance_crops else None)
     else:      # an operator with the reference's interface only: the reference's own sequence
         output_rgb = np.ascontiguousarray(esrgan.enhance(np.ascontiguousarray(img[:, :, ::-1]))[:, :, ::-1])   # the net is fed BGR (:85,94)
@@ -167,10 +202,11 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
     if georef is not None:
         final_output = output_path.with_suffix(".tif")
         # the two encoders side by side (both are thread pools over strips / bands of the same array)
-        rio.write_outputs(output_rgb, output_png, final_output, georef.scaled(scale), remember=True)   # pixel size / scale (:128-135)
+        rio.write_outputs(output_rgb, output_png, final_output, georef.scaled(scale), remember=True,       # pixel size / scale (:128-135)
+                          **({} if valid is None else {"nodata": out_nodata, "valid": valid, "valid_scale": scale}))
     else:
         final_output = output_png
-        rio.write_png(output_png, output_rgb)
+        rio.write_png(output_png, output_rgb, **({} if valid is None else {"valid": valid, "valid_scale": scale}))
 
     metadata = {
         "input_file": str(input_path),
@@ -187,20 +223,26 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
     }
     if seam_blend:
         metadata["seam_blend"] = True
+    if valid is not None:
+        metadata["nodata"] = _nodata_block(value, valid, fill_radius)
     return final_output, metadata
 
 
 def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True,
-                   model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None) -> dict:
+                   model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None, nodata=None,
+                   fill_radius: int = 32) -> dict:
     """Reference wow_sr.py:212-266 -- file naming, metadata JSON and result dict schema.  bit_depth=16: see apply_wow_sr (no PNG:
-    "sr_png" is None -- unless `display` is given: the PNG is the output's display rendering).  seam_blend: see apply_wow_sr."""
-    _check_bit_depth(bit_depth, enhance_crops, display)          # before anything is created
+    "sr_png" is None -- unless `display` is given: the PNG is the output's display rendering).  seam_blend, nodata, fill_radius: see
+    apply_wow_sr."""
+    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius)          # before anything is created
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
     wow_tif = output_dir / f"{base_name}_wow_sr.tif"
     png = wow_tif.with_suffix(".png")
     blend = {"seam_blend": True} if seam_blend else {}   # (tests patch apply_wow_sr with the reference's signature)
+    if nodata is not None:
+        blend.update(nodata=nodata, fill_radius=fill_radius)
     if bit_depth == 16:
         if display is not None:
             blend["display"] = display

@@ -968,7 +968,7 @@ void s2sr_destroy(s2sr_handle* h) {
     free_weights(h);
     if (h->ws.base) dev_free(h->ws.base);
     if (h->d_trash) dev_free(h->d_trash);
-    for (int i = 0; i < 6; ++i)
+    for (int i = 0; i < s2sr_handle::kScratchSlots; ++i)
         if (h->d_scratch[i]) dev_free(h->d_scratch[i]);
     for (EvRec& r : h->evs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
@@ -1344,7 +1344,7 @@ int s2sr_set_profiling(s2sr_handle* h, int32_t on) {
     std::lock_guard<std::mutex> lk(h->mu);
     h->prof = on < 0 ? 0 : on;
     h->span_on = false; h->span_count = 0;
-    for (int i = 0; i < 16; ++i) h->fam_count[i] = 0;
+    for (int i = 0; i < F_COUNT; ++i) h->fam_count[i] = 0;
     return S2SR_OK;
 }
 

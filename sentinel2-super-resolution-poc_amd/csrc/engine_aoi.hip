@@ -413,11 +413,45 @@ static int plan_dims(s2sr_handle* h, int H, int W, int tile, int* PH, int* PW) {
     return S2SR_OK;
 }
 
+// The device copy of a masked call's `valid` (scratch 6) and what the mask kernel needs with it.
+struct MaskDev {
+    const uint8_t* d_valid = nullptr;         // null: the call is not masked
+    int H = 0, W = 0, scale = 0, out_nodata = 0;
+    bool u16 = false;
+};
+
+// out_nodata over the output pixels of the invalid input pixels, rows [yb, ye) of the quantised image at d_img
+static int mask_rows(s2sr_handle* h, hipStream_t st, const MaskDev& m, void* d_img, int yb, int ye) {
+    if (!m.d_valid) return S2SR_OK;
+    Scope sc(h, st, F_NMASK, 0.0, (double)(ye - yb) / m.scale * m.W);
+    if (m.u16) HIPCHK(h, launch_nodata_mask(m.d_valid, m.H, m.W, m.scale, yb, ye, m.out_nodata, (uint16_t*)d_img, st));
+    else HIPCHK(h, launch_nodata_mask(m.d_valid, m.H, m.W, m.scale, yb, ye, m.out_nodata, (uint8_t*)d_img, st));
+    return S2SR_OK;
+}
+
+// `valid` (host) to scratch 6 and the fill of the image at d_img [H, W, 3] (uint8, or uint16), both on st.  The caller has asked for
+// scratch 6 (H * W bytes) already: a scratch request may free and synchronise, which belongs in front of a call's first launch.
+static int fill_locked(s2sr_handle* h, hipStream_t st, const uint8_t* valid, int H, int W, int radius, bool u16, void* d_img) {
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[6], valid, (size_t)H * W, hipMemcpyHostToDevice, st));
+    Scope sc(h, st, F_NFILL, 0.0, (double)H * W);
+    if (u16) HIPCHK(h, launch_nodata_fill((uint16_t*)d_img, (const uint8_t*)h->d_scratch[6], H, W, radius, st));
+    else HIPCHK(h, launch_nodata_fill((uint8_t*)d_img, (const uint8_t*)h->d_scratch[6], H, W, radius, st));
+    return S2SR_OK;
+}
+
+static const char* mask_error(const uint8_t* valid, int radius, int out_nodata, bool u16) {
+    if (!valid) return "nodata: a mask (valid, uint8 [H, W]) is required";
+    if (radius < 1 || radius > 64) return "nodata: the fill radius must be 1..64";
+    if (out_nodata < 0 || out_nodata > (u16 ? 65535 : 255)) return u16 ? "nodata: out_nodata must be 0..65535" : "nodata: out_nodata must be 0..255";
+    return nullptr;
+}
+
 // The finish of a banded post-process whose histograms hold every row (pp_band_hist_locked over each stitched band): the LUTs, then
 // the image in nfin row bands of fin_rows rows, each followed by its copy out.  group_done[nchunks .. nchunks + nfin) are free for
 // the bands; group_done[nchunks - 1] marks the last chunk.
+// mk: a masked call's mask, written over each band behind its last kernel (the apply pass, R rows ahead, has read those rows).
 static int pp_finish_bands(s2sr_handle* h, hipStream_t st, uint8_t* d_img_out, uint8_t* out_u8, int OH, size_t row_b, int fin_rows, int nfin,
-                           int nchunks) {
+                           int nchunks, const MaskDev& mk) {
     int rc;
     // LUTs, then every finishing band's kernels (in place: a band's rows are rewritten only after the apply pass, which
     // runs R rows ahead, has read them), an event behind each; the copies follow band by band on the copy stream
@@ -428,6 +462,7 @@ static int pp_finish_bands(s2sr_handle* h, hipStream_t st, uint8_t* d_img_out, u
     for (int b = 0; b < nfin; ++b) {
         const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
         if ((rc = pp_band_rows_locked(h, d_img_out, y0, y1, d_img_out, st))) return rc;
+        if ((rc = mask_rows(h, st, mk, d_img_out, y0, y1))) return rc;
         HIPCHK(h, hipEventRecord(h->group_done[nchunks + b], st));
     }
     if (timing) {
@@ -462,6 +497,10 @@ struct EnhanceCall {
     uint16_t* out_u16 = nullptr;
     float* out_f32 = nullptr;
     const char* required = nullptr;           // the door's words for a call without image, sizes or output (none: the bare code)
+    // the masked doors: fill the invalid pixels in front of the net, out_nodata over their output pixels behind everything
+    bool masked = false;
+    const uint8_t* valid = nullptr;           // uint8 [H, W], nonzero = valid
+    int radius = 0, out_nodata = 0;
 };
 
 static int check_call(s2sr_handle* h, const EnhanceCall& c) {
@@ -471,6 +510,10 @@ static int check_call(s2sr_handle* h, const EnhanceCall& c) {
     if (!in16 && c.out_f32 && (c.prm || c.swap_rb))          // (only the blend door can ask for it)
         return fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: the float image is the net's own output: not with a post-process or swap_rb");
     if (!in16 && (c.prm || c.swap_rb) && !c.out_u8) return c.blend ? fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: a job needs out_u8") : S2SR_E_INVALID;
+    if (c.masked) {
+        if (const char* why = mask_error(c.valid, c.radius, c.out_nodata, in16)) return fail(h, S2SR_E_INVALID, why);
+        if (c.out_f32) return fail(h, S2SR_E_INVALID, "nodata: the float image is the net's own output and is never masked");
+    }
     if (in16)
         if (int rc = check_u16(h, c.lo, c.hi)) return rc;
     if (c.prm)                                               // before the net runs, not behind it
@@ -569,7 +612,13 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
     if ((rc = ensure_scratch(h, 1, c.out_f32 ? f_off + opx * 4 : over ? opx : f_off))) return rc;
     if (p.tiled && (rc = ensure_scratch(h, 2, (size_t)nx * ny * win_in * esz))) return rc;
     if (!direct && (rc = ensure_scratch(h, tslot, tile_b))) return rc;
+    if (c.masked && (rc = ensure_scratch(h, 6, (size_t)H * W))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], in16 ? (const void*)c.img16 : (const void*)c.img8, ipx * esz, hipMemcpyHostToDevice, st));
+    MaskDev mk;                                        // masked: the fill in front of everything that reads the image, the mask at each exit of a quantised band
+    if (c.masked) {
+        if ((rc = fill_locked(h, st, c.valid, H, W, c.radius, in16, h->d_scratch[0]))) return rc;
+        mk.d_valid = (const uint8_t*)h->d_scratch[6]; mk.H = H; mk.W = W; mk.scale = scale; mk.out_nodata = c.out_nodata; mk.u16 = in16;
+    }
     if (c.swap_rb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[0], (size_t)H * W, (uint8_t*)h->d_scratch[0], st));
     int32_t* d_tab[3] = {nullptr, nullptr, nullptr};   // rectangles, row table, column table
     if (!direct && (rc = upload_tables(h, st, job.rects, p.blend ? p.rows : job.rm, p.blend ? p.cols : job.cm, d_tab))) return rc;
@@ -621,17 +670,19 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
             else if (in16) HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, t0 - carry * nx, oth, otw, r, d_tab[2], ye - yb, OW, c.lo, c.hi, (uint16_t*)dst, st));
             else HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, t0 - carry * nx, oth, otw, r, d_tab[2], ye - yb, OW, c.swap_rb && !c.prm, dst, st));
         }
-        return banded ? pp_band_hist_locked(h, d_q, yb, ye, st) : S2SR_OK;
+        if (banded) return pp_band_hist_locked(h, d_q, yb, ye, st);
+        return c.prm ? S2SR_OK : mask_rows(h, st, mk, d_q, yb, ye);       // (a post-process reads the filled image: its exits mask)
     };
     // with a post-process or the fp32 image no band is copied here: they leave through the tail below
     if ((rc = run_chunks(h, st, nx, p.chunk_r0, p.band_end, forward, finish, (uint8_t*)out_q, d_q, row_b, out_q && !c.prm && !c.out_f32))) return rc;
     // ---- the tail
     hipEvent_t tail_done = h->group_done[nchunks + nfin];
-    if (banded && (rc = pp_finish_bands(h, st, d_q, c.out_u8, OH, row_b, fin_rows, nfin, nchunks))) return rc;
+    if (banded && (rc = pp_finish_bands(h, st, d_q, c.out_u8, OH, row_b, fin_rows, nfin, nchunks, mk))) return rc;
     if (c.prm && !banded) {
         // the windows' output buffer is free again once the stitch has read it; the untiled image gets a buffer of its own
         if ((rc = ensure_scratch(h, 4, opx))) return rc;
         if ((rc = postprocess_dev_locked(h, d_q, 1, OH, OW, c.prm, h->d_scratch[4], st))) return rc;
+        if ((rc = mask_rows(h, st, mk, h->d_scratch[4], 0, OH))) return rc;
         HIPCHK(h, hipEventRecord(tail_done, st));
         HIPCHK(h, hipStreamWaitEvent(h->copy_stream, tail_done, 0));
         if ((rc = d2h_staged(h, c.out_u8, (const uint8_t*)h->d_scratch[4], opx, true))) return rc;
@@ -725,6 +776,53 @@ int s2sr_enhance_blend_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32
     c.required = "s2sr_enhance_blend: an image, positive sizes and at least one output are required";
     if (!img) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u16: an image is required") : S2SR_E_INVALID;
     RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+}
+
+// The masked doors: every 8-bit / 16-bit whole-image door with a mask.  blend, prm, swap_rb as s2sr_enhance_blend_u8.
+int s2sr_enhance_masked_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
+                           int32_t swap_rb, int32_t blend, const s2sr_mask* m, uint8_t* out_u8) {
+    EnhanceCall c = call_u8(img, H, W, tile, pad, out_u8, nullptr);
+    c.prm = prm; c.swap_rb = swap_rb != 0; c.blend = blend != 0;
+    c.required = "s2sr_enhance_masked_u8: an image, positive sizes and out_u8 are required";
+    if (!m) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_masked_u8: a mask is required (m == NULL)") : S2SR_E_INVALID;
+    c.masked = true; c.valid = m->valid; c.radius = m->radius; c.out_nodata = m->out_nodata;
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+}
+
+int s2sr_enhance_masked_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
+                            int32_t blend, const s2sr_mask* m, uint16_t* out_u16) {
+    EnhanceCall c = call_u16(img, H, W, tile, pad, lo, hi, out_u16, nullptr);
+    c.blend = blend != 0;
+    c.required = "s2sr_enhance_masked_u16: an image, positive sizes and out_u16 are required";
+    if (!m) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_masked_u16: a mask is required (m == NULL)") : S2SR_E_INVALID;
+    c.masked = true; c.valid = m->valid; c.radius = m->radius; c.out_nodata = m->out_nodata;
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+}
+
+// The fill alone: host image and mask in, filled host image out.  No weights needed.  ONE lock scope, as s2sr_postprocess_u8.
+static int fill_nodata_impl(s2sr_handle* h, const void* img, const uint8_t* valid, int H, int W, int radius, bool u16, void* out) {
+    if (!h) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!img || !out || H <= 0 || W <= 0) return fail(h, S2SR_E_INVALID, "s2sr_fill_nodata: an image, positive sizes and an output are required");
+    if (const char* why = mask_error(valid, radius, 0, u16)) return fail(h, S2SR_E_INVALID, why);
+    const size_t nb = (size_t)H * W * 3 * (u16 ? 2 : 1);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = ensure_scratch(h, 0, nb);
+    if (rc) return rc;
+    if ((rc = ensure_scratch(h, 6, (size_t)H * W))) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, nb, hipMemcpyHostToDevice, h->stream));
+    if ((rc = fill_locked(h, h->stream, valid, H, W, radius, u16, h->d_scratch[0]))) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[0], nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return S2SR_OK;
+}
+
+int s2sr_fill_nodata_u8(s2sr_handle* h, const uint8_t* img, const uint8_t* valid, int32_t H, int32_t W, int32_t radius, uint8_t* out) {
+    return fill_nodata_impl(h, img, valid, H, W, radius, false, out);
+}
+
+int s2sr_fill_nodata_u16(s2sr_handle* h, const uint16_t* img, const uint8_t* valid, int32_t H, int32_t W, int32_t radius, uint16_t* out) {
+    return fill_nodata_impl(h, img, valid, H, W, radius, true, out);
 }
 
 // The blend tables of a PH x PW image's window job (pure host arithmetic, for the CPU tests): six ints per output row / column,

@@ -50,10 +50,11 @@ struct ConvW {
 };
 
 // kernel families for the HIP-event statistics
-enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_DHIST, F_DAPPLY, F_COUNT };
+enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_DHIST, F_DAPPLY, F_NFILL, F_NMASK, F_COUNT };
 inline constexpr const char* kFamName[F_COUNT] = {"pack_u8",   "conv_first", "rdb_conv1-4", "rdb_conv5",   "conv_body",
                                  "conv_up",   "conv_hr",    "conv_last",   "postprocess", "misc",
-                                 "compact_first", "compact_body", "compact_last", "display_hist", "display_apply"};
+                                 "compact_first", "compact_body", "compact_last", "display_hist", "display_apply",
+                                 "nodata_fill", "nodata_mask"};
 
 inline constexpr int kRoleFam[kRoles] = {F_FIRST, F_RDB14, F_RDB5, F_RDB5, F_BODY, F_UP, F_UP, F_HR, F_LAST, F_CFIRST, F_CBODY, F_CLAST};   // by Role
 
@@ -185,8 +186,11 @@ struct s2sr_handle {
     char* d_trash = nullptr;      // parking area for out-of-image epilogue stores
     s2sr::engine::Workspace ws;
     // scratch device buffers (grown on demand)
-    void* d_scratch[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[6] = {0, 0, 0, 0, 0, 0};
+    // 0 .. 5: the calls' staging areas; 6: the device copy of a masked call's `valid` (nodata.hip), an area of its own because
+    // upload_tables owns 3 and the others hold images
+    static constexpr int kScratchSlots = 7;
+    void* d_scratch[kScratchSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_bytes[kScratchSlots] = {0, 0, 0, 0, 0, 0, 0};
     int capture_failures = 0;            // captures voided by a device-wide call of another runtime user; 3 -> graphs off
     int tiles_slot = -1;                 // scratch slot that still holds the tile level the last pyramid call produced (-1: none)
     int tiles_nx = 0, tiles_ny = 0;
@@ -199,7 +203,7 @@ struct s2sr_handle {
     s2sr::engine::EvRec span;     // add their work to it instead of recording events of their own.  Two marker packets between two
     int64_t span_count = 0;       // kernels cost ~2 us of a 70-us launch (r03: 71.6 us by events against 69.0 by rocprofv3); one pair around
                                   // the four conv1-4 launches of an RDB spreads that over four
-    int64_t fam_count[16] = {0};
+    int64_t fam_count[s2sr::engine::F_COUNT] = {0};
     std::vector<s2sr::engine::EvRec> evs;
     std::vector<hipEvent_t> ev_pool;
     s2sr_kstat stats[s2sr::engine::F_COUNT];

@@ -126,7 +126,7 @@ int s2sr_debug_redzone_check(s2sr_handle* h, int64_t* allocations, int64_t* dama
         if (!c.pooled) count(c.d_wpack);
         count(c.d_wphase[0]); count(c.d_wphase[1]);
     }
-    for (int i = 0; i < 6; ++i) count(h->d_scratch[i]);
+    for (int i = 0; i < s2sr_handle::kScratchSlots; ++i) count(h->d_scratch[i]);
     for (const auto& m : h->stitch_sets) count(m.d);
     if (h->ws.base && registry().find(h->ws.base)) own += 1 + (int64_t)registry().planes(h->ws.base);
     size_t n = 0, bad = 0;

@@ -286,6 +286,14 @@ uint8_t f32_to_e4m3(float f);   // OCP e4m3fn, round to nearest even, saturating
 hipError_t launch_display_hist(const uint16_t* d_img, size_t s0, size_t s1, int nodata, unsigned long long* d_hist, hipStream_t st);
 hipError_t launch_display_apply(const uint16_t* d_img, size_t s0, size_t s1, const uint8_t* d_lut, uint8_t* d_out, hipStream_t st);
 
+// nodata-aware enhance (nodata.hip).  fill: the invalid pixels of d_img [H, W, 3] take their nearest valid neighbour's
+// samples within `radius` (1..64), in place; d_valid: uint8 [H, W], nonzero = valid.  mask: out_nodata into the scale x scale output
+// pixels of every invalid input pixel, rows [yb, ye) of d_out [scale H, scale W, 3] (the image's base); scale 2 or 4.
+hipError_t launch_nodata_fill(uint8_t* d_img, const uint8_t* d_valid, int H, int W, int radius, hipStream_t st);
+hipError_t launch_nodata_fill(uint16_t* d_img, const uint8_t* d_valid, int H, int W, int radius, hipStream_t st);
+hipError_t launch_nodata_mask(const uint8_t* d_valid, int H, int W, int scale, int yb, int ye, int out_nodata, uint8_t* d_out, hipStream_t st);
+hipError_t launch_nodata_mask(const uint8_t* d_valid, int H, int W, int scale, int yb, int ye, int out_nodata, uint16_t* d_out, hipStream_t st);
+
 // XYZ tile pyramid (tiles.hip)
 hipError_t launch_warp_bilinear(const uint8_t* d_rgb, int H, int W, const float* d_grid, int gh, int gw, int step, int OH, int OW,
                                 uint8_t* d_out, hipStream_t st);

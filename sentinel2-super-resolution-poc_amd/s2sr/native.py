@@ -42,6 +42,10 @@ class PPParams(C.Structure):
                 ("sat_gain", C.c_float), ("stages", C.c_int32)]
 
 
+class Mask(C.Structure):                   # s2sr_mask
+    _fields_ = [("valid", C.c_void_p), ("radius", C.c_int32), ("out_nodata", C.c_int32)]
+
+
 class DebugConfig(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("precision", "group", "trunk_w4", "lo_exp", "fp8_form", "fp8_x_exp", "fp8_g_exp",
                                          "fp8_hp_tail", "graphs_on", "trunk_wino")] + [("reserved", C.c_int32 * 6)]
@@ -135,6 +139,11 @@ _PROTOS = {
     "s2sr_enhance_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_enhance_blend_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(PPParams), C.c_int32, C.c_void_p, C.c_void_p]),
     "s2sr_enhance_blend_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]),
+    "s2sr_fill_nodata_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "s2sr_fill_nodata_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "s2sr_enhance_masked_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(PPParams), C.c_int32, C.c_int32, C.POINTER(Mask),
+                                         C.c_void_p]),
+    "s2sr_enhance_masked_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.POINTER(Mask), C.c_void_p]),
     "s2sr_display_hist_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
     "s2sr_display_apply_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "s2sr_enhance_job_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PPParams), C.c_void_p]),
@@ -707,6 +716,60 @@ class Engine:
         self._check(self._lib.s2sr_enhance_blend_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), _ptr(out),
                                                      _ptr(f) if want_f32 else None), "s2sr_enhance_blend_u16")
         return (out, f) if want_f32 else out
+
+    # -- nodata-aware enhance (include/s2sr.h, DESIGN.md 7.4: fill the invalid pixels in front of the net, mask behind everything) ----
+    @staticmethod
+    def _valid(valid, H: int, W: int, what: str) -> np.ndarray:
+        v = np.asarray(valid)
+        if v.shape != (H, W):
+            raise ValueError(f"{what}: valid must be [H, W] = {(H, W)}, got shape {v.shape}")
+        return np.ascontiguousarray(v != 0, dtype=np.uint8) if v.dtype != np.uint8 else np.ascontiguousarray(v)
+
+    def fill_nodata(self, img: np.ndarray, valid: np.ndarray, radius: int = 32) -> np.ndarray:
+        """HxWx3 uint8 or uint16 -> the same image with every invalid pixel (valid == 0) replaced by its nearest valid neighbour
+        within `radius` (ties: the upper, then the left one); no weights needed."""
+        img = np.asarray(img)
+        if img.dtype not in (np.uint8, np.uint16):
+            raise TypeError(f"fill_nodata takes a uint8 or uint16 image, got {img.dtype}")
+        img = np.ascontiguousarray(img)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError(f"fill_nodata: expected HxWx3, got shape {img.shape}")
+        H, W, _ = img.shape
+        valid = self._valid(valid, H, W, "fill_nodata")
+        out = np.empty_like(img)
+        fn, name = (self._lib.s2sr_fill_nodata_u8, "s2sr_fill_nodata_u8") if img.dtype == np.uint8 else \
+                   (self._lib.s2sr_fill_nodata_u16, "s2sr_fill_nodata_u16")
+        self._check(fn(self._h, _ptr(img), _ptr(valid), H, W, int(radius), _ptr(out)), name)
+        return out
+
+    def enhance_masked_u8(self, img: np.ndarray, valid: np.ndarray, radius: int = 32, out_nodata: int = 0, prm: Optional[PPParams] = None,
+                          swap_rb: bool = False, blend: bool = False, tile: int = 256, pad: int = 10) -> np.ndarray:
+        """enhance_u8 / enhance_job_u8 (swap_rb) / enhance_blend_u8 (blend) on the filled image, out_nodata written over the output
+        pixels of the invalid input pixels."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        H, W, c = img.shape
+        assert c == 3
+        valid = self._valid(valid, H, W, "enhance_masked_u8")
+        m = Mask(valid.ctypes.data, int(radius), int(out_nodata))
+        out = pinned_pool.empty((self.scale * H, self.scale * W, 3), np.uint8)
+        self._check(self._lib.s2sr_enhance_masked_u8(self._h, _ptr(img), H, W, tile, pad, C.byref(prm) if prm is not None else None,
+                                                     int(bool(swap_rb)), int(bool(blend)), C.byref(m), _ptr(out)), "s2sr_enhance_masked_u8")
+        return out
+
+    def enhance_masked_u16(self, img: np.ndarray, valid: np.ndarray, lo: int = 0, hi: int = 65535, radius: int = 32, out_nodata: int = 0,
+                           blend: bool = False, tile: int = 256, pad: int = 10) -> np.ndarray:
+        """enhance_u16 / enhance_blend_u16 (blend) on the filled image, masked as enhance_masked_u8."""
+        if np.asarray(img).dtype != np.uint16:
+            raise TypeError(f"enhance_masked_u16 takes a uint16 image, got {np.asarray(img).dtype}")
+        img = np.ascontiguousarray(img)
+        H, W, c = img.shape
+        assert c == 3
+        valid = self._valid(valid, H, W, "enhance_masked_u16")
+        m = Mask(valid.ctypes.data, int(radius), int(out_nodata))
+        out = pinned_pool.empty((4 * H, 4 * W, 3), np.uint16)
+        self._check(self._lib.s2sr_enhance_masked_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), int(bool(blend)), C.byref(m),
+                                                      _ptr(out)), "s2sr_enhance_masked_u16")
+        return out
 
     # -- display rendering of 16-bit images (include/s2sr.h; policy between the two passes: s2sr/display.py) ---------------------
     @staticmethod

@@ -19,6 +19,8 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 from PIL import Image, TiffImagePlugin, TiffTags
 
+from .tiff_lite import GDAL_NODATA as TAG_GDAL_NODATA, parse_nodata
+
 Image.MAX_IMAGE_PIXELS = None
 
 TAG_PIXEL_SCALE = 33550      # ModelPixelScaleTag  (sx, sy, sz)
@@ -28,6 +30,8 @@ TAG_GEOKEYS = 34735          # GeoKeyDirectoryTag
 TAG_GEODOUBLE = 34736
 TAG_GEOASCII = 34737
 _GEO_TAGS = (TAG_PIXEL_SCALE, TAG_TIEPOINT, TAG_TRANSFORM, TAG_GEOKEYS, TAG_GEODOUBLE, TAG_GEOASCII)
+def _nodata_text(nodata) -> str:
+    return str(int(nodata)) if float(nodata) == int(nodata) else repr(float(nodata))
 
 
 @dataclass
@@ -35,6 +39,7 @@ class GeoRef:
     """The GeoTIFF tags that place the raster; `scaled(s)` is the reference's
     `Affine(a/s, b, c, d, e/s, f)` (wow_sr.py:128-135): same origin, pixel size / s."""
     tags: Dict[int, tuple] = field(default_factory=dict)
+    nodata: Optional[float] = None      # the file's GDAL_NODATA value (read only: the writers take theirs as an argument)
 
     def scaled(self, s: float) -> "GeoRef":
         t = dict(self.tags)
@@ -46,7 +51,7 @@ class GeoRef:
             m[0] /= s      # a
             m[5] /= s      # e
             t[TAG_TRANSFORM] = tuple(m)
-        return GeoRef(t)
+        return GeoRef(t, self.nodata)
 
     @property
     def pixel_size(self) -> Optional[Tuple[float, float]]:
@@ -57,11 +62,18 @@ class GeoRef:
         return None
 
 
-def _to_u8(img: np.ndarray, minmax_eps: float) -> np.ndarray:
+def _to_u8(img: np.ndarray, minmax_eps: float, valid: Optional[np.ndarray] = None) -> np.ndarray:
     """Reference normalisation (wow_sr.py:67-73): min-max to 0..255 (truncating) only when
-    max > 255, plain astype otherwise.  `minmax_eps` is the +1e-6 of apply_cnn_sr (:309)."""
+    max > 255, plain astype otherwise.  `minmax_eps` is the +1e-6 of apply_cnn_sr (:309).
+    valid (a nodata job): the min and max are those of the valid pixels; the others are clipped into that range."""
     if img.dtype == np.uint8:
         return img
+    if valid is not None:
+        px = img[np.asarray(valid) != 0]
+        if px.size == 0 or px.max() <= 255:
+            return np.clip(img, 0, 255).astype(np.uint8)
+        lo, hi = px.min(), px.max()
+        return ((np.clip(img, lo, hi) - lo) / (max(hi - lo, 1) + minmax_eps) * 255).astype(np.uint8)
     if img.max() > 255:
         lo, hi = img.min(), img.max()
         return ((img - lo) / (hi - lo + minmax_eps) * 255).astype(np.uint8)
@@ -86,7 +98,8 @@ def read_rgb_u8(path: Path, minmax_eps: float = 0.0) -> Tuple[np.ndarray, Option
         else:
             # bands 1-3, or the single band three times (wow_sr.py:61-65)
             arr = arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2)
-            georef = GeoRef({t: (tv[t][0] if t == TAG_GEOASCII else tuple(tv[t])) for t in _GEO_TAGS if t in tv})
+            georef = GeoRef({t: (tv[t][0] if t == TAG_GEOASCII else tuple(tv[t])) for t in _GEO_TAGS if t in tv},
+                            parse_nodata(tv.get(TAG_GDAL_NODATA)))
             return np.ascontiguousarray(_to_u8(arr, minmax_eps)), georef
     try:
         im = Image.open(path)
@@ -102,7 +115,7 @@ def read_rgb_u8(path: Path, minmax_eps: float = 0.0) -> Tuple[np.ndarray, Option
             if t in tv2:
                 v = tv2[t]
                 tags[t] = tuple(v) if isinstance(v, (tuple, list)) else v
-        georef = GeoRef(tags)
+        georef = GeoRef(tags, parse_nodata(tv2.get(TAG_GDAL_NODATA)))
     if im.mode in ("RGB", "RGBA", "P", "CMYK", "LA", "1"):
         arr = np.asarray(im.convert("RGB"))
     else:                        # single band: L, I;16, I, F
@@ -123,8 +136,36 @@ def read_rgb_raw(path: Path) -> Tuple[np.ndarray, Optional[GeoRef]]:
     except tiff_lite.TiffError as e:
         raise ValueError(f"{path}: unsupported raster layout (tiff_lite: {e})") from e
     arr = arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2)   # bands 1-3 / gray three times (wow_sr.py:61-65)
-    georef = GeoRef({t: (tv[t][0] if t == TAG_GEOASCII else tuple(tv[t])) for t in _GEO_TAGS if t in tv})
+    georef = GeoRef({t: (tv[t][0] if t == TAG_GEOASCII else tuple(tv[t])) for t in _GEO_TAGS if t in tv}, parse_nodata(tv.get(TAG_GDAL_NODATA)))
     return np.ascontiguousarray(arr), georef
+
+
+def resolve_nodata(nodata, georef: Optional[GeoRef], path=""):
+    """A job's nodata argument as a number: an integer as it is, "tag" = the file's GDAL_NODATA tag (ValueError if it has none)."""
+    if nodata != "tag":
+        return int(nodata)
+    if georef is None or georef.nodata is None:
+        raise ValueError(f"{path}: nodata=\"tag\", but the file has no GDAL_NODATA tag (pass the value)")
+    return georef.nodata
+
+
+def read_rgb_u8_nodata(path: Path, nodata, minmax_eps: float = 0.0):
+    """`read_rgb_u8` for a nodata job -> (HxWx3 uint8 RGB, GeoRef or None, valid uint8 [H, W], the nodata value).  nodata: an
+    integer, or "tag".  A pixel is invalid iff bands 1-3 AS STORED all equal the value (s2sr.nodata.mask_from_value), and the
+    min-max of a raster above 255 is taken over the valid pixels."""
+    from .nodata import mask_from_value
+    path = Path(path)
+    raw = None
+    if path.suffix.lower() in (".tif", ".tiff"):
+        try:
+            raw, georef = read_rgb_raw(path)
+        except ValueError:
+            raw = None           # a layout only PIL decodes: its 8-bit image is the raster
+    if raw is None:
+        raw, georef = read_rgb_u8(path, minmax_eps)
+    value = resolve_nodata(nodata, georef, path)
+    valid = mask_from_value(raw, value)
+    return np.ascontiguousarray(_to_u8(raw, minmax_eps, valid)), georef, valid, value
 
 
 _ADLER = 65521
@@ -148,7 +189,7 @@ def _adler32_combine(a1: int, a2: int, len2: int) -> int:
 
 
 def encode_png_pieces(img: np.ndarray, level: int = 1, band_rows: int = 128, workers: Optional[int] = None,
-                      strategy: Optional[int] = None, stream: bool = False):
+                      strategy: Optional[int] = None, stream: bool = False, valid: Optional[np.ndarray] = None, valid_scale: int = 1):
     """HxWx3 (RGB) or HxWx4 (RGBA) uint8 -> the PNG file as a list of byte strings to be written in order.  The SR outputs are
     tens of megapixels and PNG deflate is what a job's writer spends its time in, so the image is cut into bands that are
     filtered (Sub) and deflated in parallel, each band ending on a sync flush so that the pieces concatenate into one valid zlib
@@ -159,7 +200,10 @@ def encode_png_pieces(img: np.ndarray, level: int = 1, band_rows: int = 128, wor
     encoder (csrc/pngenc.hip: the same filter and run-length matching, 2-3x zlib's speed); `level` / `strategy` other than the
     defaults select zlib.  Any setting decodes to the same pixels.  stream: a generator over the same pieces -- a band's chunk is
     handed out as soon as it and its predecessors are deflated (the bands run on the shared host pool), so a writer's loop runs under
-    the deflating of the bands behind it."""
+    the deflating of the bands behind it.
+    valid (HxWx3 images only; uint8 [h / valid_scale, w / valid_scale], nonzero = valid): the file is RGBA with alpha = 255 where
+    the pixel's mask pixel (y // valid_scale, x // valid_scale) is valid and 0 elsewhere.  The alpha is interleaved band by band
+    inside the bands' threads: there is no RGBA copy of the whole image."""
     import struct
     import zlib
     from concurrent.futures import ThreadPoolExecutor
@@ -168,7 +212,20 @@ def encode_png_pieces(img: np.ndarray, level: int = 1, band_rows: int = 128, wor
     h, w, c = img.shape
     if img.dtype != np.uint8 or c not in (3, 4):
         raise ValueError(f"expected HxWx3 or HxWx4 uint8, got {img.shape} {img.dtype}")
-    rows = img.reshape(h, w * c)
+    if valid is not None:
+        valid, vs = np.asarray(valid), int(valid_scale)
+        if c != 3 or valid.ndim != 2 or vs < 1 or valid.shape != (-(-h // vs), -(-w // vs)):
+            raise ValueError(f"valid: expected an HxWx3 image and a [{-(-h // max(int(valid_scale), 1))}, {-(-w // max(int(valid_scale), 1))}] mask, "
+                             f"got {img.shape} and {valid.shape} at scale {valid_scale}")
+        rgb, c = img, 4
+
+        def band_rgba(y0, y1):                                     # the band as RGBA: its own copy, made in the band's thread
+            blk = np.empty((y1 - y0, w, 4), np.uint8)
+            blk[..., :3] = rgb[y0:y1]
+            a = (valid[y0 // vs:-(-y1 // vs)] != 0).astype(np.uint8) * np.uint8(255)
+            blk[..., 3] = np.repeat(np.repeat(a, vs, axis=0), vs, axis=1)[y0 - y0 // vs * vs:, :w][:y1 - y0]
+            return blk
+    rows = img.reshape(h, w * c) if valid is None else None
     bands = [(y, min(h, y + band_rows)) for y in range(0, h, band_rows)]
     idat_crc0 = zlib.crc32(b"IDAT")
     use_native = level == 1 and strategy in (None, zlib.Z_RLE)
@@ -176,11 +233,11 @@ def encode_png_pieces(img: np.ndarray, level: int = 1, band_rows: int = 128, wor
     def work_native(i):                                            # -> (one complete IDAT chunk, adler, filtered bytes)
         from . import native
         y0, y1 = bands[i]
-        return native.png_idat_band(img[y0:y1], i == 0, i == len(bands) - 1)
+        return native.png_idat_band(img[y0:y1] if valid is None else band_rgba(y0, y1), i == 0, i == len(bands) - 1)
 
     def work_zlib(i):
         y0, y1 = bands[i]
-        blk = rows[y0:y1]
+        blk = rows[y0:y1] if valid is None else band_rgba(y0, y1).reshape(y1 - y0, w * c)
         raw = np.empty((y1 - y0, w * c + 1), np.uint8)
         raw[:, 0] = 1                                              # filter type Sub
         raw[:, 1:c + 1] = blk[:, :c]
@@ -246,8 +303,9 @@ def write_pieces(path: Path, pieces) -> None:
                 pass
 
 
-def write_png(path: Path, rgb: np.ndarray) -> None:
-    write_pieces(path, encode_png_pieces(rgb, stream=True))       # (a generator: bands reach the file while later bands deflate)
+def write_png(path: Path, rgb: np.ndarray, valid: Optional[np.ndarray] = None, valid_scale: int = 1) -> None:
+    """valid: an RGBA file whose alpha is the mask (encode_png_pieces)."""
+    write_pieces(path, encode_png_pieces(rgb, stream=True, valid=valid, valid_scale=valid_scale))   # (a generator: bands reach the file while later bands deflate)
 
 
 # ---- the rasters this process wrote last, for the stage that reads them right back ---------------------------------------------
@@ -298,9 +356,12 @@ def forget_written() -> None:
         _WRITTEN.clear()
 
 
-def write_outputs(rgb: np.ndarray, png_path: Path, tif_path: Path, georef: "GeoRef", remember: bool = False) -> None:
+def write_outputs(rgb: np.ndarray, png_path: Path, tif_path: Path, georef: "GeoRef", remember: bool = False, nodata=None,
+                  valid: Optional[np.ndarray] = None, valid_scale: int = 1) -> None:
     """The GeoTIFF and the PNG of one job (wow_sr.py:126-164) written side by side: two threads, each a pool over strips /
-    bands of the same array (zlib and the native LZW encoder release the GIL).  remember: see write_geotiff_rgb."""
+    bands of the same array (zlib and the native LZW encoder release the GIL).  remember: see write_geotiff_rgb.
+    A nodata job: nodata goes into the GeoTIFF's GDAL_NODATA tag, valid (the input's mask, valid_scale = the SR scale) into the
+    PNG's alpha."""
     import threading
     err = []
 
@@ -309,20 +370,20 @@ def write_outputs(rgb: np.ndarray, png_path: Path, tif_path: Path, georef: "GeoR
             fn(*a)
         except BaseException as e:      # surfaced below: a failed writer must fail the job
             err.append(e)
-    t = threading.Thread(target=run, args=(write_geotiff_rgb, tif_path, rgb, georef, 64, remember))
+    t = threading.Thread(target=run, args=(write_geotiff_rgb, tif_path, rgb, georef, 64, remember, nodata))
     t.start()
-    run(write_png, png_path, rgb)
+    run(write_png, png_path, rgb, valid, valid_scale)
     t.join()
     if err:
         raise err[0]
 
 
-def write_geotiff_rgb(path: Path, rgb: np.ndarray, georef: GeoRef, rows_per_strip: int = 64, remember: bool = False) -> None:
+def write_geotiff_rgb(path: Path, rgb: np.ndarray, georef: GeoRef, rows_per_strip: int = 64, remember: bool = False, nodata=None) -> None:
     """uint8 RGB, LZW compressed (compress="lzw", wow_sr.py:138-151) with the geo tags.  Classic
     little-endian TIFF, chunky RGB strips; the strips are LZW-encoded by the native library on a
     thread pool (the SR outputs are tens of megapixels; a single-threaded encoder is what a job would
     otherwise wait for).  remember: the caller will not write to `rgb` again -- a view of it is kept for the stage that reads this
-    file right back (`recall_written`)."""
+    file right back (`recall_written`).  nodata (None: no tag, the file as ever): the value the GDAL_NODATA tag declares."""
     import os
     import struct
     from concurrent.futures import ThreadPoolExecutor
@@ -369,6 +430,8 @@ def write_geotiff_rgb(path: Path, rgb: np.ndarray, georef: GeoRef, rows_per_stri
                     ent.append((tag, 2, val if isinstance(val, str) else str(val)))
                 else:
                     ent.append((tag, 12, tuple(float(v) for v in val)))
+            if nodata is not None:
+                ent.append((TAG_GDAL_NODATA, 2, _nodata_text(nodata)))
             ent.sort(key=lambda e: e[0])
             fmt = {3: "H", 4: "I", 12: "d"}
             ifd_off = pos
@@ -402,9 +465,10 @@ def write_geotiff_rgb(path: Path, rgb: np.ndarray, georef: GeoRef, rows_per_stri
         _remember_written(path, rgb, georef)
 
 
-def write_geotiff_rgb16(path: Path, rgb16: np.ndarray, georef: GeoRef, rows_per_strip: int = 64) -> None:
+def write_geotiff_rgb16(path: Path, rgb16: np.ndarray, georef: GeoRef, rows_per_strip: int = 64, nodata=None) -> None:
     """uint16 RGB, the 16-bit sibling of `write_geotiff_rgb`: BitsPerSample 16,16,16, little-endian samples, LZW strips through
-    the same native encoder (no predictor), the same geo tags, classic little-endian TIFF with the IFD behind the data."""
+    the same native encoder (no predictor), the same geo tags, classic little-endian TIFF with the IFD behind the data.  nodata:
+    as write_geotiff_rgb."""
     import struct
 
     from . import hostpool, native
@@ -438,6 +502,8 @@ def write_geotiff_rgb16(path: Path, rgb16: np.ndarray, georef: GeoRef, rows_per_
                     ent.append((tag, 2, val if isinstance(val, str) else str(val)))
                 else:
                     ent.append((tag, 12, tuple(float(v) for v in val)))
+            if nodata is not None:
+                ent.append((TAG_GDAL_NODATA, 2, _nodata_text(nodata)))
             ent.sort(key=lambda e: e[0])
             fmt = {3: "H", 4: "I", 12: "d"}
             ifd_off = pos

@@ -6,7 +6,7 @@ Supports: little/big endian, classic TIFF and BigTIFF, strips or tiles, PlanarCo
 (chunky) and 2 (separate planes), compression none / LZW (5) / Deflate (8, 32946) / PackBits
 (32773), Predictor 1 and 2 (horizontal differencing), uint8/uint16/uint32/int16/int32/float32/
 float64 samples of 8/16/32/64 bits.  Returns the first image of the file as [H, W, bands] plus
-the raw tag dictionary (GeoTIFF tags included).  LZW strips are decoded by the native library
+the raw tag dictionary (GeoTIFF tags included; GDAL_NODATA as its text: parse_nodata).  LZW strips are decoded by the native library
 (host code, s2sr_tiff_lzw_decode); everything else is numpy + zlib.
 
 Uploaded files reach this reader (app/sr_routes.py /api/enhance), so a malformed file is a TiffError whatever it breaks
@@ -30,6 +30,7 @@ STRIP_OFFSETS, SAMPLES_PER_PIXEL, ROWS_PER_STRIP, STRIP_BYTE_COUNTS = 273, 277, 
 PLANAR_CONFIG, PREDICTOR = 284, 317
 TILE_WIDTH, TILE_LENGTH, TILE_OFFSETS, TILE_BYTE_COUNTS = 322, 323, 324, 325
 SAMPLE_FORMAT = 339
+GDAL_NODATA = 42113          # ASCII: the value of the pixels that were never measured (parse_nodata)
 
 _TYPE = {1: ("B", 1), 2: ("c", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8), 6: ("b", 1), 7: ("B", 1), 8: ("h", 2),
          9: ("i", 4), 10: ("ii", 8), 11: ("f", 4), 12: ("d", 8), 16: ("Q", 8), 17: ("q", 8), 18: ("Q", 8)}
@@ -37,6 +38,21 @@ _TYPE = {1: ("B", 1), 2: ("c", 1), 3: ("H", 2), 4: ("I", 4), 5: ("II", 8), 6: ("
 
 class TiffError(ValueError):
     pass
+
+
+def parse_nodata(tag_value):
+    """The number a GDAL_NODATA tag holds -- read_tiff's tags.get(GDAL_NODATA) -- as an int where it is integral; None for no tag,
+    text that is no number, or nan."""
+    if tag_value is None:
+        return None
+    text = tag_value[0] if isinstance(tag_value, (tuple, list)) and tag_value else tag_value
+    try:
+        v = float(str(text).strip().strip("\0"))
+    except ValueError:
+        return None
+    if v != v:
+        return None
+    return int(v) if v not in (float("inf"), float("-inf")) and v == int(v) else v
 
 
 def _read_ifd(buf: memoryview, bo: str, big: bool, off: int) -> Dict[int, tuple]:
