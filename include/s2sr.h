@@ -281,6 +281,46 @@ int  s2sr_enhance_masked_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32
 int  s2sr_enhance_masked_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo,
                              int32_t hi, int32_t blend, const s2sr_mask* m, uint16_t* out_u16);
 
+/* Radiometric consistency, opt-in: one back-projection step against the box-average sensor model, so that the mean
+ * of the S x S output samples over an input pixel is that input pixel again.  Integers throughout, per channel: S = 2 or 4,
+ * n = S S; q the door's quantised image [S H, S W, 3]; v = clamp(img, lo, hi) the input the net saw (8 bits: 0, 255; 16 bits: the
+ * call's range); sum[y, x] the sum of q over block [S y, S y + S) x [S x, S x + S); e = n v - sum.
+ *   exact step:  k = floor(e / n), r = e - n k (0..n-1); block sample (i, j) gets d = k + (rank[i][j] < r), rank the 4 x 4 Bayer
+ *     order [[0,8,2,10],[12,4,14,6],[3,11,1,9],[15,7,13,5]] (S = 2: [[0,2],[3,1]]); q' = clip(q + d, lo, hi).  Where no sample of a
+ *     block clips, sum' = n v exactly.
+ *   smooth step: e interpolated bilinearly between input-pixel centres, edges replicated.  Output row Y = S y + i: t = 2 i + 1 - S,
+ *     neighbour row clamp(y + sign(t), 0, H - 1), weights w1 = |t| (neighbour) and w0 = 2 S - w1 (y); columns alike; num = the sum
+ *     of wy wx e over the four pairs, den = 4 S S n, d = floor((num + den / 2) / den), q' = clip(q + d, lo, hi).
+ *   S2SR_CONSISTENCY_EXACT: the exact step.  S2SR_CONSISTENCY_SMOOTH: the smooth step, the block sums again on its result, the
+ *     exact step on what remains: most of the correction then lies in a field without steps along the block grid.
+ *   inexact[c] = the blocks of channel c whose final sum differs from n v (a sample clipped); every block of the image counts,
+ *     filled ones included; c is a channel of the call's images as given (a swap_rb job: R, G, B).
+ * In a whole-image call the pass runs on the quantised image on the device behind the paste (overwrite, quantise or blend, and
+ * the untiled image) and in front of the R / B exchange back, the post-process, the mask and the copy out: a masked call is
+ * mask(pp(consistency(door(fill(img)), fill(img)))).  With a post-process the product is consistent BEFORE it: the crop-visibility
+ * step changes radiometry on purpose.  The uint16 image left on the device for s2sr_display_*_u16 is the consistent one.  The
+ * result does not depend on the chunk plan.  The fp32 images are the net's own output and are not offered; s2sr/dist.py's cut /
+ * stitch entries do not run the pass; a saturated block stays inexact (no redistribution among its unclipped samples).
+ * s2sr_consistency_u8 / _u16: the pass alone, host images in and out (out may be sr), no weights needed; band_rows (0: the library's
+ *   choice, ~32 MB) sets the bands of output rows it works in, and the result does not depend on it.
+ * s2sr_enhance_consistent_u8: the doors s2sr_enhance_u8 (prm NULL, swap_rb 0), s2sr_enhance_job_u8 (swap_rb 1), s2sr_enhance_blend_u8
+ *   (blend != 0) and, with m != NULL, s2sr_enhance_masked_u8, with their sizes, scales and refusals: every handle, x4, x2plus (odd
+ *   H or W too) and compact.  s2sr_enhance_consistent_u16: s2sr_enhance_u16 / _blend_u16 / _masked_u16 and their refusals.
+ * S2SR_E_INVALID with a text, before the device is touched: a mode outside 1..2, S outside {2, 4}, band_rows < 0, a NULL image or
+ * output, a bad range.  The handle keeps working afterwards. */
+#define S2SR_CONSISTENCY_EXACT  1
+#define S2SR_CONSISTENCY_SMOOTH 2
+int  s2sr_consistency_u8(s2sr_handle* h, const uint8_t* sr /* [S H, S W, 3] */, const uint8_t* img /* [H, W, 3] */, int32_t H, int32_t W,
+                         int32_t S, int32_t mode, int32_t band_rows, uint8_t* out, uint64_t* inexact /* [3] or NULL */);
+int  s2sr_consistency_u16(s2sr_handle* h, const uint16_t* sr, const uint16_t* img, int32_t H, int32_t W, int32_t S, int32_t lo, int32_t hi,
+                          int32_t mode, int32_t band_rows, uint16_t* out, uint64_t* inexact /* [3] or NULL */);
+int  s2sr_enhance_consistent_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad,
+                                const s2sr_pp_params* prm /* or NULL */, int32_t swap_rb, int32_t blend, const s2sr_mask* m /* or NULL */,
+                                int32_t mode, uint8_t* out_u8, uint64_t* inexact /* [3] or NULL */);
+int  s2sr_enhance_consistent_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo,
+                                 int32_t hi, int32_t blend, const s2sr_mask* m /* or NULL */, int32_t mode, uint16_t* out_u16,
+                                 uint64_t* inexact /* [3] or NULL */);
+
 /* Display rendering of a 16-bit image: the two passes over a uint16 [H, W, 3] interleaved image that reduce it to
  * the 8-bit image the PNG writer, the warp, the pyramid and the post-process take.  Neither entry needs weights.  What lies between
  * them -- percentile limits from the histogram, the stretch LUT -- is the caller's (s2sr/display.py).

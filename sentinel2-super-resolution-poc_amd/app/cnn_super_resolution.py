@@ -288,14 +288,22 @@ class RealESRGAN:
     """Real-ESRGAN inference wrapper with the reference's interface (:161-280)."""
 
     def __init__(self, scale: int = 4, device: str = None, tile_size: int = 256, model_name: str = None,
-                 state_dict=None, denoise_strength: Optional[float] = None, seam_blend: bool = False):
-        """seam_blend (not in the reference): tiled images are stitched with the cross-faded paste (s2sr_enhance_blend_*) -- the
+                 state_dict=None, denoise_strength: Optional[float] = None, seam_blend: bool = False, consistency=None):
+        """consistency (not in the reference): None, "exact" or "smooth" -- one back-projection step on the quantised
+        image (s2sr_enhance_consistent_*), so that the mean of the scale x scale output samples over an input pixel is that pixel
+        again; honoured by enhance, enhance16 and enhance_job, with or without valid / nodata.  last_inexact_blocks: the blocks per
+        band of the last such call that a clip kept off (None before one).
+        seam_blend (not in the reference): tiled images are stitched with the cross-faded paste (s2sr_enhance_blend_*) -- the
         same windows and forwards, the window overlaps blended over a ramp around every tile line in place of the hard crop.
         denoise_strength (realesr_general_x4v3 only, upstream's knob): s in [0, 1] loads realesr_general_x4v3.pth and
         realesr_general_wdn_x4v3.pth and runs dni(x4v3, wdn, s) = s * x4v3 + (1 - s) * wdn: 1 = no denoising, 0 = the wdn model."""
         self.tile_size = tile_size
         self.tile_pad = 10
         self.seam_blend = bool(seam_blend)
+        from s2sr.consistency import mode_of
+        self.consistency = consistency
+        self._cmode = mode_of(consistency)           # refuses an unknown name here, before anything is created
+        self.last_inexact_blocks = None
         self.device = _resolve_device(device)
         print(f"   Device: {self.device}")
 
@@ -390,6 +398,11 @@ class RealESRGAN:
             raise TypeError(f"expected uint8 image, got {img.dtype}")
         valid, out_nodata = self._mask_of(img, valid, nodata, fill_radius)
         with self._engine.chain_lock:        # (not between another job's enhance16 and its display rendering)
+            if self._cmode:
+                out, bad = self._engine.enhance_consistent_u8(img, self._cmode, blend=self.seam_blend, valid=valid, radius=fill_radius,
+                                                              out_nodata=out_nodata, tile=self.tile_size, pad=self.tile_pad)
+                self.last_inexact_blocks = [int(v) for v in bad]
+                return out
             if valid is not None:
                 return self._engine.enhance_masked_u8(img, valid, radius=fill_radius, out_nodata=out_nodata, blend=self.seam_blend,
                                                       tile=self.tile_size, pad=self.tile_pad)
@@ -417,7 +430,13 @@ class RealESRGAN:
         if not (0 <= lo < hi <= 65535):
             raise ValueError(f"value_range {value_range}: need 0 <= lo < hi <= 65535")
         valid, out_nodata = self._mask_of(img, valid, nodata, fill_radius)
-        if valid is None:
+        if self._cmode:
+            def door(img, lo, hi, tile, pad):
+                out, bad = self._engine.enhance_consistent_u16(img, lo, hi, self._cmode, blend=self.seam_blend, valid=valid, radius=fill_radius,
+                                                               out_nodata=out_nodata, tile=tile, pad=pad)
+                self.last_inexact_blocks = [int(v) for v in bad]
+                return out
+        elif valid is None:
             door = self._engine.enhance_blend_u16 if self.seam_blend else self._engine.enhance_u16
         else:
             def door(img, lo, hi, tile, pad):
@@ -448,6 +467,11 @@ class RealESRGAN:
             raise TypeError(f"expected uint8 image, got {rgb.dtype}")
         valid, out_nodata = self._mask_of(rgb, valid, nodata, fill_radius)
         with self._engine.chain_lock:
+            if self._cmode:       # the pass sits in front of the post-process: the product is consistent before it
+                out, bad = self._engine.enhance_consistent_u8(rgb, self._cmode, prm=post, swap_rb=True, blend=self.seam_blend, valid=valid,
+                                                              radius=fill_radius, out_nodata=out_nodata, tile=self.tile_size, pad=self.tile_pad)
+                self.last_inexact_blocks = [int(v) for v in bad]
+                return out
             if valid is not None:
                 return self._engine.enhance_masked_u8(rgb, valid, radius=fill_radius, out_nodata=out_nodata, prm=post, swap_rb=True,
                                                       blend=self.seam_blend, tile=self.tile_size, pad=self.tile_pad)

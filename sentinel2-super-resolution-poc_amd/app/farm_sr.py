@@ -42,10 +42,15 @@ def enhance_vegetation(img: np.ndarray) -> np.ndarray:
     return _pp_engine().postprocess_u8(img, p)
 
 
-def apply_farm_sr(input_path: Path, output_path: Path, scale: int = 4, seam_blend: bool = False) -> Tuple[Path, dict]:
+def apply_farm_sr(input_path: Path, output_path: Path, scale: int = 4, seam_blend: bool = False, consistency=None) -> Tuple[Path, dict]:
     """Reference farm_sr.py:111-241.  seam_blend (not in the reference): the tiled stitch cross-fades the window overlaps
-    (RealESRGAN(seam_blend=True)); the metadata gains "seam_blend": true, and only then."""
+    (RealESRGAN(seam_blend=True)); the metadata gains "seam_blend": true, and only then.
+    consistency (not in the reference): None, "exact" or "smooth", see app.wow_sr.apply_wow_sr; the farm steps
+    always follow the pass, so the metadata block says "applied_before": "post_process"."""
     from s2sr import rasterio_lite as rio
+    from s2sr.consistency import check_args as check_consistency, metadata_block
+
+    check_consistency(consistency)                                   # before anything is created
 
     print(f"\nFarm Super-Resolution x{scale}\n   Input: {input_path}")
     input_path = Path(input_path)
@@ -56,7 +61,8 @@ def apply_farm_sr(input_path: Path, output_path: Path, scale: int = 4, seam_blen
     import os
     from app.cnn_super_resolution import thread_precision
     with thread_precision(os.environ.get("S2SR_FARM_PRECISION") or None):
-        esrgan = RealESRGAN(scale=scale, tile_size=256, **({"seam_blend": True} if seam_blend else {}))
+        esrgan = RealESRGAN(scale=scale, tile_size=256, **({"seam_blend": True} if seam_blend else {}),
+                            **({"consistency": consistency} if consistency is not None else {}))
         if hasattr(esrgan, "enhance_job"):      # RGB2BGR -> net -> BGR2RGB -> the three steps of :170-178, one native call
             final = esrgan.enhance_job(img, native.pp_farm())
         else:
@@ -86,16 +92,19 @@ def apply_farm_sr(input_path: Path, output_path: Path, scale: int = 4, seam_blen
     }
     if seam_blend:
         metadata["seam_blend"] = True
+    if consistency is not None:
+        metadata["consistency"] = metadata_block(consistency, esrgan.last_inexact_blocks, "post_process")
     return final_output, metadata
 
 
-def process_farm_sr(input_tif: Path, output_dir: Path, scale: int = 4, seam_blend: bool = False) -> dict:
-    """Reference farm_sr.py:244-286.  seam_blend: see apply_farm_sr."""
+def process_farm_sr(input_tif: Path, output_dir: Path, scale: int = 4, seam_blend: bool = False, consistency=None) -> dict:
+    """Reference farm_sr.py:244-286.  seam_blend, consistency: see apply_farm_sr."""
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
     sr_tif = output_dir / f"{base_name}_farm_sr_x{scale}.tif"
-    _, sr_metadata = apply_farm_sr(input_path=input_tif, output_path=sr_tif, scale=scale, **({"seam_blend": True} if seam_blend else {}))
+    _, sr_metadata = apply_farm_sr(input_path=input_tif, output_path=sr_tif, scale=scale, **({"seam_blend": True} if seam_blend else {}),
+                                   **({"consistency": consistency} if consistency is not None else {}))
     png = sr_tif.with_suffix(".png")
     result = {
         "timestamp": datetime.now().strftime("%Y%m%d_%H%M%S"),

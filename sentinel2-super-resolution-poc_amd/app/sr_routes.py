@@ -31,6 +31,7 @@ class SRRequest(BaseModel):          # main.py:192-197
     scale: int = 4
     model: str = "edsr"
     seam_blend: bool = False         # not in the reference: cross-fade the window overlaps of the tiled stitch
+    consistency: Optional[str] = None   # not in the reference: "exact" or "smooth" -- block means reproduce the input pixels
 
 
 class WowRequest(BaseModel):         # main.py:200-208
@@ -45,6 +46,7 @@ class WowRequest(BaseModel):         # main.py:200-208
     display: Optional[dict] = None   # ... and its 8-bit rendering for the PNG and the tiles (fields of s2sr.display.Stretch); 16-bit jobs only
     nodata: Optional[Union[int, str]] = None   # not in the reference: the value of the pixels that were never measured, or "tag" (app.wow_sr)
     fill_radius: int = 32            # ... and how far they are filled from their valid neighbours in front of the net (1..64)
+    consistency: Optional[str] = None   # not in the reference: "exact" or "smooth" -- block means reproduce the input pixels
 
 
 class SRResponse(BaseModel):         # main.py:230-235
@@ -210,11 +212,19 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                 run(Path(sr_tif), tiles_dir)
             result["tiles_dir"] = str(tiles_dir)
 
-    def run_sr_job(job_id, input_file, scale, model, output_dir, seam_blend=False):          # main.py:247-287
+    def _check_consistency(value):                                           # an unknown mode is a 400, before a job exists
+        try:
+            from s2sr.consistency import check_args
+            check_args(value)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+
+    def run_sr_job(job_id, input_file, scale, model, output_dir, seam_blend=False, consistency=None):          # main.py:247-287
         try:
             _set(job_id, status="processing", message=f"Applying {model.upper()} x{scale} super-resolution...")
             from app.farm_sr import process_farm_sr                          # `model` is ignored, as in the reference
-            result = process_farm_sr(input_tif=input_file, output_dir=output_dir, scale=scale, **({"seam_blend": True} if seam_blend else {}))
+            result = process_farm_sr(input_tif=input_file, output_dir=output_dir, scale=scale, **({"seam_blend": True} if seam_blend else {}),
+                                     **({"consistency": consistency} if consistency is not None else {}))
             _set(job_id, status="tiling", message="Generating tiles from SR image...")
             _tile(result, "tiles_sr")
             _set(job_id, status="completed", message="Super-resolution complete!", result=result)
@@ -223,7 +233,7 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
 
     def run_wow_job(job_id, input_file, output_dir, enhance_crops, auto_fetch=True, max_age_days=30,
                     max_cloud_cover=30.0, force_fetch=False, model="realesrgan_x4", seam_blend=False, bit_depth=8,
-                    display=None, nodata=None, fill_radius=32):              # main.py:290-368
+                    display=None, nodata=None, fill_radius=32, consistency=None):              # main.py:290-368
         try:
             if input_file is None and auto_fetch:
                 _set(job_id, status="fetching",
@@ -244,6 +254,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                 extra["display"] = display
             if nodata is not None:
                 extra.update(nodata=nodata, fill_radius=fill_radius)
+            if consistency is not None:
+                extra["consistency"] = consistency
             result = process_wow_sr(input_tif=input_file, output_dir=output_dir, enhance_crops=enhance_crops, model=model, **extra)
             _set(job_id, status="tiling", message="Generating tiles from WOW SR image...")
             # a 16-bit job's tiles show the rendering of its PNG: the job's stretch with the limits it found
@@ -268,6 +280,7 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             raise HTTPException(status_code=400, detail="Scale must be 2, 3, or 4")
         if request.model not in ["edsr", "espcn", "lapsrn"]:
             raise HTTPException(status_code=400, detail="Model must be edsr, espcn, or lapsrn")
+        _check_consistency(request.consistency)
         job_id = datetime.now().strftime("%Y%m%d_%H%M%S")
         output_dir = data_dir / "sr" / job_id
         output_dir.mkdir(parents=True, exist_ok=True)
@@ -276,7 +289,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                                "scale": request.scale, "model": request.model, "output_dir": str(output_dir),
                                "created_at": datetime.now().isoformat()}
         background_tasks.add_task(run_sr_job, job_id, input_file, request.scale, request.model, output_dir,
-                                  **({"seam_blend": True} if request.seam_blend else {}))
+                                  **({"seam_blend": True} if request.seam_blend else {}),
+                                  **({"consistency": request.consistency} if request.consistency is not None else {}))
         return SRResponse(job_id=job_id, status="queued", message=f"SR job started: {input_file.name} -> x{request.scale}")
 
     @app.get("/api/sr/{job_id}")                                             # main.py:437-443
@@ -319,6 +333,7 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                 check_args(request.nodata, request.fill_radius)
             except ValueError as e:
                 raise HTTPException(status_code=400, detail=str(e))
+        _check_consistency(request.consistency)
         job_id = f"wow_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
         output_dir = data_dir / "wow" / job_id
         output_dir.mkdir(parents=True, exist_ok=True)
@@ -334,7 +349,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                                   **({"seam_blend": True} if request.seam_blend else {}),
                                   **({"bit_depth": request.bit_depth} if request.bit_depth != 8 else {}),
                                   **({"display": request.display} if request.display is not None else {}),
-                                  **({"nodata": request.nodata, "fill_radius": request.fill_radius} if request.nodata is not None else {}))
+                                  **({"nodata": request.nodata, "fill_radius": request.fill_radius} if request.nodata is not None else {}),
+                                  **({"consistency": request.consistency} if request.consistency is not None else {}))
         msg = (f"WOW SR started: {input_file.name} -> Real-ESRGAN x4 + Enhanced" if input_file else
                f"WOW SR started: auto-fetching best image (last {request.max_age_days}d, cloud <={request.max_cloud_cover}%)")
         return SRResponse(job_id=job_id, status="queued", message=msg)

@@ -41,7 +41,7 @@ def _nodata_block(value, valid: np.ndarray, fill_radius: int) -> dict:
 
 
 def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend: bool = False, display=None,
-                    enhance_crops: bool = False, nodata=None, fill_radius: int = 32) -> Tuple[Path, dict]:
+                    enhance_crops: bool = False, nodata=None, fill_radius: int = 32, consistency=None) -> Tuple[Path, dict]:
     """bit_depth=16 of apply_wow_sr: a uint16 GeoTIFF read raw, value_range = the image's own (min, max) -- the reference's
     min-max (wow_sr.py:67-73) minus its quantisation to 8 bits -- the net fed BGR as ever (:85,94), RealESRGAN.enhance16, RGB back,
     a uint16 GeoTIFF out.  Without `display`: no PNG (the encoder is 8-bit) and no crop-visibility post-process (OpenCV's 8-bit
@@ -73,7 +73,8 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
         valid = mask_from_value(img, value)
     lo, hi = valid_range(img, valid)
     mask_kw = {} if valid is None else {"valid": valid, "nodata": value, "fill_radius": fill_radius}
-    esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}))
+    esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}),
+                        **({"consistency": consistency} if consistency is not None else {}))
     display_rgb = info = None
     if stretch is None:
         out_bgr = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), **mask_kw)
@@ -88,6 +89,7 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
             display_rgb = _enhance_for_crops(display_rgb)
     output_rgb = np.ascontiguousarray(out_bgr[:, :, ::-1])
     scale = esrgan.scale
+    inexact = None if consistency is None else esrgan.last_inexact_blocks[::-1]      # (the net's image is B, G, R)
     del esrgan
     final_output = Path(output_path).with_suffix(".tif")
     final_output.parent.mkdir(parents=True, exist_ok=True)
@@ -117,12 +119,17 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
         metadata["display"] = info
     if valid is not None:
         metadata["nodata"] = _nodata_block(value, valid, fill_radius)
+    if consistency is not None:      # the GeoTIFF is the consistent product; the display image and its crop step are renderings of it
+        from s2sr.consistency import metadata_block
+        metadata["consistency"] = metadata_block(consistency, inexact)
     return final_output, metadata
 
 
-def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=None, fill_radius: int = 32) -> None:
+def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=None, fill_radius: int = 32, consistency=None) -> None:
+    from s2sr.consistency import check_args as check_consistency
     from s2sr.nodata import check_args
     check_args(nodata, fill_radius)
+    check_consistency(consistency)
     if nodata is not None and nodata != "tag" and not 0 <= int(nodata) <= 65535:
         # (compared with the bands as stored: an 8-bit job of a uint16 raster names the uint16 value)
         raise ValueError(f"nodata {nodata!r}: an integer in 0..65535")
@@ -140,7 +147,7 @@ def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=N
 
 def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True,
                  model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None, nodata=None,
-                 fill_radius: int = 32) -> Tuple[Path, dict]:
+                 fill_radius: int = 32, consistency=None) -> Tuple[Path, dict]:
     """Reference wow_sr.py:28-184 -- same outputs (GeoTIFF and/or PNG) and metadata dict.  bit_depth=16 (not in the reference): a
     uint16 GeoTIFF goes through the net without the 8-bit squeeze and comes back as a uint16 GeoTIFF (_apply_wow_sr16).
     display (bit_depth=16 only; a s2sr.display.Stretch or a dict of its fields): the job also writes the PNG, from the output's
@@ -151,12 +158,16 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
     has none).  A pixel whose bands 1-3 all equal it was never measured: it is filled from its nearest valid neighbour within
     fill_radius (1..64) in front of the net, the post-process runs on the filled image, and the outputs say which pixels they
     are -- the GeoTIFF carries the GDAL_NODATA tag and the value in those pixels, the PNG is RGBA with alpha 255 x mask.  The
-    metadata gains "nodata": {"value", "invalid_pixels", "fill_radius"}, and only then."""
+    metadata gains "nodata": {"value", "invalid_pixels", "fill_radius"}, and only then.
+    consistency (not in the reference): None, "exact" or "smooth" -- the block means of the super-resolved image
+    reproduce the input pixels (RealESRGAN(consistency=...)).  The metadata gains "consistency": {"mode", "inexact_blocks": [r, g,
+    b]}, and only then; with enhance_crops the block also says "applied_before": "post_process" -- the crop-visibility step
+    changes radiometry on purpose, so the written 8-bit image is consistent only up to it."""
     from s2sr import rasterio_lite as rio
 
-    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius)
+    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency)
     if bit_depth == 16:
-        return _apply_wow_sr16(input_path, output_path, model, seam_blend, display, enhance_crops, nodata, fill_radius)
+        return _apply_wow_sr16(input_path, output_path, model, seam_blend, display, enhance_crops, nodata, fill_radius, consistency)
 
     model_display = {"realesrgan_x4": "Real-ESRGAN x4",
                      "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)",
@@ -177,7 +188,8 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
 
     pipeline_stages = []
     print(f"   Stage 1/2: {model_display} (GAN upscaling)...")
-    esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}))
+    esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}),
+                        **({"consistency": consistency} if consistency is not None else {}))
     # RGB2BGR -> enhance -> BGR2RGB -> _enhance_for_crops (:85-110) as ONE native call: the 16x image crosses PCIe once
     if enhance_crops:
         print("   Stage 2/2: Crop visibility enhancement...")
@@ -190,6 +202,7 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
         if enhance_crops:
             output_rgb = _enhance_for_crops(output_rgb)
     scale = esrgan.scale
+    inexact = None if consistency is None else esrgan.last_inexact_blocks
     del esrgan
     pipeline_stages.append({"model": model, "scale": scale, "purpose": "GAN upscaling"})
     if enhance_crops:
@@ -225,16 +238,19 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
         metadata["seam_blend"] = True
     if valid is not None:
         metadata["nodata"] = _nodata_block(value, valid, fill_radius)
+    if consistency is not None:
+        from s2sr.consistency import metadata_block
+        metadata["consistency"] = metadata_block(consistency, inexact, "post_process" if enhance_crops else None)
     return final_output, metadata
 
 
 def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True,
                    model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None, nodata=None,
-                   fill_radius: int = 32) -> dict:
+                   fill_radius: int = 32, consistency=None) -> dict:
     """Reference wow_sr.py:212-266 -- file naming, metadata JSON and result dict schema.  bit_depth=16: see apply_wow_sr (no PNG:
-    "sr_png" is None -- unless `display` is given: the PNG is the output's display rendering).  seam_blend, nodata, fill_radius: see
-    apply_wow_sr."""
-    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius)          # before anything is created
+    "sr_png" is None -- unless `display` is given: the PNG is the output's display rendering).  seam_blend, nodata, fill_radius,
+    consistency: see apply_wow_sr."""
+    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency)          # before anything is created
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
@@ -243,6 +259,8 @@ def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True
     blend = {"seam_blend": True} if seam_blend else {}   # (tests patch apply_wow_sr with the reference's signature)
     if nodata is not None:
         blend.update(nodata=nodata, fill_radius=fill_radius)
+    if consistency is not None:
+        blend["consistency"] = consistency
     if bit_depth == 16:
         if display is not None:
             blend["display"] = display

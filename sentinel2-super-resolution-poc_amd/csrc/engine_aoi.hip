@@ -224,22 +224,24 @@ static std::vector<int> plan_chunk_rows(const s2sr_handle* h, const WindowJob& j
 // rows that chunk made final into image rows on the device (t0: the chunk's first window, for a door that keeps one chunk's
 // tiles).  `copy`: each band (row_b bytes per row, at dev, to host) leaves on the copy stream under the next chunk's compute,
 // the last one exposed.  Events group_done[0 .. nchunks) are the caller's to provide.
-// band_end: the bands (plan_bands, band_plan.h) -- chunk c makes rows [band_end[c - 1], band_end[c]) final.
+// band_end: the bands (plan_bands, band_plan.h) -- chunk c makes rows [band_end[c - 1], band_end[c]) final, the paste's band.
+// out_end: the rows that are ready to leave behind chunk c, [out_end[c - 1], out_end[c]) -- band_end itself, unless a consistency
+// pass trails the paste (cons_out_end); finish(t0, pyb, pye, yb, ye) gets both bands.
 template <class Forward, class Finish>
-static int run_chunks(s2sr_handle* h, hipStream_t st, int nx, const std::vector<int>& chunk_r0, const std::vector<int>& band_end, Forward forward,
-                      Finish finish, uint8_t* host, const uint8_t* dev, size_t row_b, bool copy) {
+static int run_chunks(s2sr_handle* h, hipStream_t st, int nx, const std::vector<int>& chunk_r0, const std::vector<int>& band_end,
+                      const std::vector<int>& out_end, Forward forward, Finish finish, uint8_t* host, const uint8_t* dev, size_t row_b, bool copy) {
     const int nchunks = (int)band_end.size();
-    int rc, yb = 0, prev_yb = 0, prev_ye = 0;
+    int rc, pyb = 0, yb = 0, prev_yb = 0, prev_ye = 0;
     for (int c = 0; c < nchunks; ++c) {
-        const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1], ye = band_end[c];
+        const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1], pye = band_end[c], ye = out_end[c];
         if ((rc = forward(r0 * nx, (r1 - r0) * nx))) return rc;
-        if (ye > yb && (rc = finish(r0 * nx, yb, ye))) return rc;
+        if ((pye > pyb || ye > yb) && (rc = finish(r0 * nx, pyb, pye, yb, ye))) return rc;
         HIPCHK(h, hipEventRecord(h->group_done[c], st));
         if (copy && c > 0 && prev_ye > prev_yb) {
             HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[c - 1], 0));
             if ((rc = d2h_staged(h, host + (size_t)prev_yb * row_b, dev + (size_t)prev_yb * row_b, (size_t)(prev_ye - prev_yb) * row_b, false))) return rc;
         }
-        prev_yb = yb; prev_ye = ye; yb = ye;
+        prev_yb = yb; prev_ye = ye; yb = ye; pyb = pye;
     }
     if (copy && prev_ye > prev_yb) {
         HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
@@ -439,6 +441,71 @@ static int fill_locked(s2sr_handle* h, hipStream_t st, const uint8_t* valid, int
     return S2SR_OK;
 }
 
+// A consistency pass over one quantised image on the device (consistency.hip), in place, in bands of whole block
+// rows behind whatever makes the image's rows final (the paste of a whole-image call, the upload of s2sr_consistency_*).  A band
+// may end on a row that is no multiple of S, and mode 2 reads the residuals of the block row below: the pass trails.  Scratch 7:
+// the inexact counters (uint64[3]) in the first 256 bytes, behind them mode 2's residual plane (int32 [H, W, 3]).
+struct ConsRun {
+    int mode = 0;                             // 0: no pass
+    int H = 0, W = 0, S = 0, lo = 0, hi = 255, swap = 0;
+    bool u16 = false;
+    const void* d_lr = nullptr;               // the input the net saw [H, W, 3]
+    void* d_img = nullptr;                    // the image [S H, S W, 3]
+    int e_end = 0, done = 0;                  // block rows whose residuals are taken (mode 2); block rows finished
+};
+constexpr size_t kConsHead = 256;
+static size_t cons_scratch_bytes(int mode, int H, int W) { return kConsHead + (mode == S2SR_CONSISTENCY_SMOOTH ? (size_t)H * W * 3 * sizeof(int32_t) : 0); }
+
+// The image rows the pass can finish once rows [0, final_rows) are final (last: and nothing more comes): the whole block rows
+// among them, in mode 2 less the last one, whose lower neighbour's residual does not exist yet.
+static int cons_out_end(int mode, int S, int H, int final_rows, bool last) {
+    if (last) return H * S;
+    const int b = final_rows / S - (mode == S2SR_CONSISTENCY_SMOOTH ? 1 : 0);
+    return b > 0 ? b * S : 0;
+}
+
+// zeroes the counters; the caller has asked for scratch 7 (cons_scratch_bytes) in front of its first launch
+static int cons_begin(s2sr_handle* h, hipStream_t st, ConsRun& r) {
+    r.e_end = r.done = 0;
+    HIPCHK(h, hipMemsetAsync(h->d_scratch[7], 0, kConsHead, st));
+    return S2SR_OK;
+}
+
+// rows [0, final_rows) of the image are final: the pass up to row out_end (cons_out_end of them)
+static int cons_advance(s2sr_handle* h, hipStream_t st, ConsRun& r, int final_rows, int out_end) {
+    const int fb = final_rows / r.S, target = out_end / r.S;
+    unsigned long long* cnt = (unsigned long long*)h->d_scratch[7];
+    int32_t* d_e = (int32_t*)((char*)h->d_scratch[7] + kConsHead);
+    auto launch = [&](int form, int b0, int b1) -> int {
+        const double img_b = (double)(b1 - b0) * r.S * r.S * r.W * 3.0 * (r.u16 ? 2 : 1);
+        Scope sc(h, st, F_CONS, 0.0, form == 0 ? img_b : 2.0 * img_b);
+        if (r.u16) HIPCHK(h, launch_consistency(form, (uint16_t*)r.d_img, (const uint16_t*)r.d_lr, d_e, cnt, r.H, r.W, r.S, b0, b1, r.lo, r.hi, st));
+        else HIPCHK(h, launch_consistency(form, (uint8_t*)r.d_img, (const uint8_t*)r.d_lr, d_e, cnt, r.H, r.W, r.S, b0, b1, r.swap, st));
+        return S2SR_OK;
+    };
+    int rc;
+    if (r.mode == S2SR_CONSISTENCY_SMOOTH && fb > r.e_end) {
+        if ((rc = launch(0, r.e_end, fb))) return rc;
+        r.e_end = fb;
+    }
+    if (target > r.done) {
+        if (r.mode == S2SR_CONSISTENCY_SMOOTH && r.e_end < (target + 1 < r.H ? target + 1 : r.H))
+            return fail(h, S2SR_E_INVALID, "consistency: a band ran ahead of its residuals");
+        if ((rc = launch(r.mode, r.done, target))) return rc;
+        r.done = target;
+    }
+    return S2SR_OK;
+}
+
+// the counters to the host, behind everything on st; returns when they are there
+static int cons_counts(s2sr_handle* h, hipStream_t st, uint64_t* inexact) {
+    unsigned long long n[3];
+    HIPCHK(h, hipMemcpyAsync(n, h->d_scratch[7], sizeof n, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    if (inexact) for (int c = 0; c < 3; ++c) inexact[c] = n[c];
+    return S2SR_OK;
+}
+
 static const char* mask_error(const uint8_t* valid, int radius, int out_nodata, bool u16) {
     if (!valid) return "nodata: a mask (valid, uint8 [H, W]) is required";
     if (radius < 1 || radius > 64) return "nodata: the fill radius must be 1..64";
@@ -501,6 +568,9 @@ struct EnhanceCall {
     bool masked = false;
     const uint8_t* valid = nullptr;           // uint8 [H, W], nonzero = valid
     int radius = 0, out_nodata = 0;
+    // the consistent doors: the back-projection pass on the quantised image, behind the paste and in front of all else
+    int consistency = 0;                      // 0: off, S2SR_CONSISTENCY_*
+    uint64_t* inexact = nullptr;              // [3] or null: the blocks per channel whose sum a clip kept off n v
 };
 
 static int check_call(s2sr_handle* h, const EnhanceCall& c) {
@@ -513,6 +583,11 @@ static int check_call(s2sr_handle* h, const EnhanceCall& c) {
     if (c.masked) {
         if (const char* why = mask_error(c.valid, c.radius, c.out_nodata, in16)) return fail(h, S2SR_E_INVALID, why);
         if (c.out_f32) return fail(h, S2SR_E_INVALID, "nodata: the float image is the net's own output and is never masked");
+    }
+    if (c.consistency) {
+        if (c.consistency != S2SR_CONSISTENCY_EXACT && c.consistency != S2SR_CONSISTENCY_SMOOTH)
+            return fail(h, S2SR_E_INVALID, "consistency: mode must be 1 (S2SR_CONSISTENCY_EXACT) or 2 (S2SR_CONSISTENCY_SMOOTH)");
+        if (c.out_f32) return fail(h, S2SR_E_INVALID, "consistency: the float image is the net's own output and is never corrected");
     }
     if (in16)
         if (int rc = check_u16(h, c.lo, c.hi)) return rc;
@@ -582,6 +657,8 @@ static int plan_enhance(s2sr_handle* h, const EnhanceCall& c, EnhancePlan& p) {
 // is pasted (under the compute of the chunks still to come), builds the LUTs behind the last band and finishes the image in row
 // bands, each followed by its copy out; a single chunk of the overwrite paste runs it on the whole image instead.
 // The fp32 image (one chunk) is pasted from the chunk's tiles behind the loop, and both images leave behind that.
+// A consistency pass sits between the paste and everything else: it trails the paste by whole block rows, and the
+// exchange back, the histograms, the mask and the copies follow its bands instead of the paste's (ConsRun, cons_out_end).
 static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
     EnhancePlan p;
     int rc = plan_enhance(h, c, p);
@@ -613,6 +690,7 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
     if (p.tiled && (rc = ensure_scratch(h, 2, (size_t)nx * ny * win_in * esz))) return rc;
     if (!direct && (rc = ensure_scratch(h, tslot, tile_b))) return rc;
     if (c.masked && (rc = ensure_scratch(h, 6, (size_t)H * W))) return rc;
+    if (c.consistency && (rc = ensure_scratch(h, 7, cons_scratch_bytes(c.consistency, H, W)))) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], in16 ? (const void*)c.img16 : (const void*)c.img8, ipx * esz, hipMemcpyHostToDevice, st));
     MaskDev mk;                                        // masked: the fill in front of everything that reads the image, the mask at each exit of a quantised band
     if (c.masked) {
@@ -642,6 +720,20 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
     // caller's next hist / lut / rows is refused
     struct CloseRun { s2sr_handle* h; ~CloseRun() { if (h) h->ppb.open = false; } } close_run{banded ? h : nullptr};
     if ((rc = ensure_group_events(h, nchunks + nfin + 1))) return rc;
+    // consistency: the pass trails the paste (whole block rows; mode 2 one more), and everything behind the paste follows the pass's
+    // bands -- the R / B exchange back, the histograms of a banded post-process, the mask, the copy out.  Scratch 0 holds the image
+    // the net saw (filled, exchanged) for the whole call.  The 8-bit blend paste of a job without post-process has exchanged R and
+    // B already: image channel c is then input channel 2 - c.
+    ConsRun cr;
+    std::vector<int> out_end = p.band_end;
+    if (c.consistency) {
+        cr.mode = c.consistency; cr.H = H; cr.W = W; cr.S = scale; cr.u16 = in16;
+        if (in16) { cr.lo = c.lo; cr.hi = c.hi; }
+        cr.swap = !over && !in16 && c.swap_rb && !c.prm;
+        cr.d_lr = h->d_scratch[0]; cr.d_img = d_q;
+        for (int k = 0; k < nchunks; ++k) out_end[k] = cons_out_end(cr.mode, scale, H, p.band_end[k], k == nchunks - 1);
+        if ((rc = cons_begin(h, st, cr))) return rc;
+    }
     // ---- the chunk loop
     int prev_n = 0;                                              // windows of the chunk before
     auto forward = [&](int t0, int n) -> int {
@@ -656,25 +748,32 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
         else out.u8 = (uint8_t*)d_buf + (size_t)t0 * win_out;
         return forward_dev(h, st, in, n, wh, ww, out, p.mo.on() ? &p.mo : nullptr);
     };
-    // rows [yb, ye) into the quantised image; t0: the chunk's first window (the one-chunk buffers start at window t0 - carry * nx)
-    auto finish = [&](int t0, int yb, int ye) -> int {
+    // rows [pyb, pye) into the quantised image, and what follows the paste on rows [yb, ye) (the same rows, unless a consistency pass
+    // trails); t0: the chunk's first window (the one-chunk buffers start at window t0 - carry * nx)
+    auto finish = [&](int t0, int pyb, int pye, int yb, int ye) -> int {
         if (!out_q) return S2SR_OK;
-        uint8_t* dst = d_q + (size_t)yb * row_b;
-        if (over) {
-            if (!direct) HIPCHK(h, launch_stitch((const uint8_t*)d_buf, nx, oth, otw, d_tab[1] + 2 * yb, d_tab[2], ye - yb, OW, dst, st));
-            if (c.swap_rb && !banded) HIPCHK(h, launch_swap_rb_u8(dst, (size_t)(ye - yb) * OW, dst, st));   // (a banded post-process exchanges R and B itself)
+        uint8_t* dst = d_q + (size_t)pyb * row_b;
+        if (pye <= pyb) {                                        // (nothing new is final: only the trailing pass moves)
+        } else if (over) {
+            if (!direct) HIPCHK(h, launch_stitch((const uint8_t*)d_buf, nx, oth, otw, d_tab[1] + 2 * pyb, d_tab[2], pye - pyb, OW, dst, st));
         } else {
-            Scope sc(h, st, F_MISC, 0.0, (double)(ye - yb) * OW * 3.0 * (4.0 + esz));
-            const int32_t* r = d_tab[1] + (size_t)kBlendStride * yb;
-            if (!p.blend) HIPCHK(h, launch_stitch_quant_u16(d_tiles, nx, t0, oth, otw, d_tab[1] + 2 * yb, d_tab[2], ye - yb, OW, c.lo, c.hi, (uint16_t*)dst, st));
-            else if (in16) HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, t0 - carry * nx, oth, otw, r, d_tab[2], ye - yb, OW, c.lo, c.hi, (uint16_t*)dst, st));
-            else HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, t0 - carry * nx, oth, otw, r, d_tab[2], ye - yb, OW, c.swap_rb && !c.prm, dst, st));
+            Scope sc(h, st, F_MISC, 0.0, (double)(pye - pyb) * OW * 3.0 * (4.0 + esz));
+            const int32_t* r = d_tab[1] + (size_t)kBlendStride * pyb;
+            if (!p.blend) HIPCHK(h, launch_stitch_quant_u16(d_tiles, nx, t0, oth, otw, d_tab[1] + 2 * pyb, d_tab[2], pye - pyb, OW, c.lo, c.hi, (uint16_t*)dst, st));
+            else if (in16) HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, t0 - carry * nx, oth, otw, r, d_tab[2], pye - pyb, OW, c.lo, c.hi, (uint16_t*)dst, st));
+            else HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, t0 - carry * nx, oth, otw, r, d_tab[2], pye - pyb, OW, c.swap_rb && !c.prm, dst, st));
+        }
+        if (cr.mode && (rc = cons_advance(h, st, cr, pye, ye))) return rc;
+        if (ye <= yb) return S2SR_OK;
+        if (over && c.swap_rb && !banded) {                      // (a banded post-process exchanges R and B itself)
+            uint8_t* band = d_q + (size_t)yb * row_b;
+            HIPCHK(h, launch_swap_rb_u8(band, (size_t)(ye - yb) * OW, band, st));
         }
         if (banded) return pp_band_hist_locked(h, d_q, yb, ye, st);
         return c.prm ? S2SR_OK : mask_rows(h, st, mk, d_q, yb, ye);       // (a post-process reads the filled image: its exits mask)
     };
     // with a post-process or the fp32 image no band is copied here: they leave through the tail below
-    if ((rc = run_chunks(h, st, nx, p.chunk_r0, p.band_end, forward, finish, (uint8_t*)out_q, d_q, row_b, out_q && !c.prm && !c.out_f32))) return rc;
+    if ((rc = run_chunks(h, st, nx, p.chunk_r0, p.band_end, out_end, forward, finish, (uint8_t*)out_q, d_q, row_b, out_q && !c.prm && !c.out_f32))) return rc;
     // ---- the tail
     hipEvent_t tail_done = h->group_done[nchunks + nfin];
     if (banded && (rc = pp_finish_bands(h, st, d_q, c.out_u8, OH, row_b, fin_rows, nfin, nchunks, mk))) return rc;
@@ -700,6 +799,11 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
     }
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     HIPCHK(h, hipStreamSynchronize(st));
+    if (cr.mode && (rc = cons_counts(h, st, c.inexact))) return rc;
+    if (cr.mode && c.inexact && c.swap_rb && !cr.swap) {       // the pass saw B, G, R: the counts go by the channels of the call's images
+        const uint64_t b = c.inexact[0];
+        c.inexact[0] = c.inexact[2]; c.inexact[2] = b;
+    }
     if (c.out_u16) { h->disp_slot = 1; h->disp_h = OH; h->disp_w = OW; }   // the x4 image also stays on the device, for s2sr_display_*_u16
     return S2SR_OK;
 }
@@ -797,6 +901,84 @@ int s2sr_enhance_masked_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int3
     if (!m) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_masked_u16: a mask is required (m == NULL)") : S2SR_E_INVALID;
     c.masked = true; c.valid = m->valid; c.radius = m->radius; c.out_nodata = m->out_nodata;
     RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+}
+
+// The consistent doors: every 8-bit / 16-bit whole-image door with the back-projection pass.  prm, swap_rb, blend as
+// s2sr_enhance_blend_u8; m NULL or as the masked doors.
+static const char* kConsMode = "consistency: mode must be 1 (S2SR_CONSISTENCY_EXACT) or 2 (S2SR_CONSISTENCY_SMOOTH)";
+int s2sr_enhance_consistent_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
+                               int32_t swap_rb, int32_t blend, const s2sr_mask* m, int32_t mode, uint8_t* out_u8, uint64_t* inexact) {
+    EnhanceCall c = call_u8(img, H, W, tile, pad, out_u8, nullptr);
+    c.prm = prm; c.swap_rb = swap_rb != 0; c.blend = blend != 0;
+    c.required = "s2sr_enhance_consistent_u8: an image, positive sizes and out_u8 are required";
+    if (mode != S2SR_CONSISTENCY_EXACT && mode != S2SR_CONSISTENCY_SMOOTH) return h ? fail(h, S2SR_E_INVALID, kConsMode) : S2SR_E_INVALID;
+    c.consistency = mode; c.inexact = inexact;
+    if (m) { c.masked = true; c.valid = m->valid; c.radius = m->radius; c.out_nodata = m->out_nodata; }
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+}
+
+int s2sr_enhance_consistent_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
+                                int32_t blend, const s2sr_mask* m, int32_t mode, uint16_t* out_u16, uint64_t* inexact) {
+    EnhanceCall c = call_u16(img, H, W, tile, pad, lo, hi, out_u16, nullptr);
+    c.blend = blend != 0;
+    c.required = "s2sr_enhance_consistent_u16: an image, positive sizes and out_u16 are required";
+    if (mode != S2SR_CONSISTENCY_EXACT && mode != S2SR_CONSISTENCY_SMOOTH) return h ? fail(h, S2SR_E_INVALID, kConsMode) : S2SR_E_INVALID;
+    c.consistency = mode; c.inexact = inexact;
+    if (m) { c.masked = true; c.valid = m->valid; c.radius = m->radius; c.out_nodata = m->out_nodata; }
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+}
+
+// The pass alone: host images in, host image out (out may be sr).  No weights needed.  ONE lock scope, as s2sr_postprocess_u8.
+// The image goes up, through the pass and out again in bands of band_rows output rows on one stream: a band's rows are final once
+// it is uploaded, the pass trails as it does behind a paste (cons_out_end), and what it has finished leaves.
+static int consistency_impl(s2sr_handle* h, const void* sr, const void* img, int H, int W, int S, int lo, int hi, int mode, int band_rows,
+                            bool u16, void* out, uint64_t* inexact) {
+    if (!h) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!sr || !img || !out || H <= 0 || W <= 0) return fail(h, S2SR_E_INVALID, "s2sr_consistency: the two images, positive sizes and an output are required");
+    if (S != 2 && S != 4) return fail(h, S2SR_E_INVALID, "s2sr_consistency: S must be 2 or 4");
+    if (mode != S2SR_CONSISTENCY_EXACT && mode != S2SR_CONSISTENCY_SMOOTH) return fail(h, S2SR_E_INVALID, kConsMode);
+    if (band_rows < 0) return fail(h, S2SR_E_INVALID, "s2sr_consistency: band_rows must be >= 0");
+    if (u16 && !(0 <= lo && lo < hi && hi <= 65535)) return fail(h, S2SR_E_INVALID, "s2sr_consistency_u16: need 0 <= lo < hi <= 65535");
+    if ((long long)H * S > 0x3fffffffLL || (long long)W * S * 3 > 0x3fffffffLL) return fail(h, S2SR_E_INVALID, "s2sr_consistency: the image is too large");
+    const int esz = u16 ? 2 : 1, OH = H * S;
+    const size_t row_b = (size_t)W * S * 3 * esz, ipx = (size_t)H * W * 3;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = h->stream;
+    int rc = ensure_scratch(h, 0, ipx * esz);
+    if (rc) return rc;
+    if ((rc = ensure_scratch(h, 1, row_b * OH))) return rc;
+    if ((rc = ensure_scratch(h, 7, cons_scratch_bytes(mode, H, W)))) return rc;
+    size_t rows = band_rows > 0 ? (size_t)band_rows : ((size_t)32 << 20) / row_b;      // the library's choice: ~32 MB
+    if (rows < 1) rows = 1;
+    if (rows > (size_t)OH) rows = OH;
+    ConsRun cr;
+    cr.mode = mode; cr.H = H; cr.W = W; cr.S = S; cr.u16 = u16;
+    if (u16) { cr.lo = lo; cr.hi = hi; }
+    cr.d_lr = h->d_scratch[0]; cr.d_img = h->d_scratch[1];
+    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, ipx * esz, hipMemcpyHostToDevice, st));
+    if ((rc = cons_begin(h, st, cr))) return rc;
+    uint8_t* d_img = (uint8_t*)h->d_scratch[1];
+    int left = 0;                                                                       // rows that have left
+    for (size_t y0 = 0; y0 < (size_t)OH; y0 += rows) {
+        const int y1 = (int)(y0 + rows < (size_t)OH ? y0 + rows : OH);
+        HIPCHK(h, hipMemcpyAsync(d_img + y0 * row_b, (const uint8_t*)sr + y0 * row_b, (y1 - y0) * row_b, hipMemcpyHostToDevice, st));
+        const int oe = cons_out_end(mode, S, H, y1, y1 == OH);
+        if ((rc = cons_advance(h, st, cr, y1, oe))) return rc;
+        if (oe > left) HIPCHK(h, hipMemcpyAsync((uint8_t*)out + (size_t)left * row_b, d_img + (size_t)left * row_b, (size_t)(oe - left) * row_b, hipMemcpyDeviceToHost, st));
+        if (oe > left) left = oe;
+    }
+    return cons_counts(h, st, inexact);
+}
+
+int s2sr_consistency_u8(s2sr_handle* h, const uint8_t* sr, const uint8_t* img, int32_t H, int32_t W, int32_t S, int32_t mode, int32_t band_rows,
+                        uint8_t* out, uint64_t* inexact) {
+    RUN_WITH_STREAM_RECOVERY(h, consistency_impl(h, sr, img, H, W, S, 0, 255, mode, band_rows, false, out, inexact));
+}
+
+int s2sr_consistency_u16(s2sr_handle* h, const uint16_t* sr, const uint16_t* img, int32_t H, int32_t W, int32_t S, int32_t lo, int32_t hi,
+                         int32_t mode, int32_t band_rows, uint16_t* out, uint64_t* inexact) {
+    RUN_WITH_STREAM_RECOVERY(h, consistency_impl(h, sr, img, H, W, S, lo, hi, mode, band_rows, true, out, inexact));
 }
 
 // The fill alone: host image and mask in, filled host image out.  No weights needed.  ONE lock scope, as s2sr_postprocess_u8.

@@ -50,11 +50,11 @@ struct ConvW {
 };
 
 // kernel families for the HIP-event statistics
-enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_DHIST, F_DAPPLY, F_NFILL, F_NMASK, F_COUNT };
+enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_DHIST, F_DAPPLY, F_NFILL, F_NMASK, F_CONS, F_COUNT };
 inline constexpr const char* kFamName[F_COUNT] = {"pack_u8",   "conv_first", "rdb_conv1-4", "rdb_conv5",   "conv_body",
                                  "conv_up",   "conv_hr",    "conv_last",   "postprocess", "misc",
                                  "compact_first", "compact_body", "compact_last", "display_hist", "display_apply",
-                                 "nodata_fill", "nodata_mask"};
+                                 "nodata_fill", "nodata_mask", "consistency"};
 
 inline constexpr int kRoleFam[kRoles] = {F_FIRST, F_RDB14, F_RDB5, F_RDB5, F_BODY, F_UP, F_UP, F_HR, F_LAST, F_CFIRST, F_CBODY, F_CLAST};   // by Role
 
@@ -187,10 +187,11 @@ struct s2sr_handle {
     s2sr::engine::Workspace ws;
     // scratch device buffers (grown on demand)
     // 0 .. 5: the calls' staging areas; 6: the device copy of a masked call's `valid` (nodata.hip), an area of its own because
-    // upload_tables owns 3 and the others hold images
-    static constexpr int kScratchSlots = 7;
-    void* d_scratch[kScratchSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[kScratchSlots] = {0, 0, 0, 0, 0, 0, 0};
+    // upload_tables owns 3 and the others hold images; 7: a consistency pass's inexact counters (uint64[3], the first 256 bytes) and,
+    // in mode 2, its residual plane (consistency.hip)
+    static constexpr int kScratchSlots = 8;
+    void* d_scratch[kScratchSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    size_t scratch_bytes[kScratchSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
     int capture_failures = 0;            // captures voided by a device-wide call of another runtime user; 3 -> graphs off
     int tiles_slot = -1;                 // scratch slot that still holds the tile level the last pyramid call produced (-1: none)
     int tiles_nx = 0, tiles_ny = 0;

@@ -294,6 +294,16 @@ hipError_t launch_nodata_fill(uint16_t* d_img, const uint8_t* d_valid, int H, in
 hipError_t launch_nodata_mask(const uint8_t* d_valid, int H, int W, int scale, int yb, int ye, int out_nodata, uint8_t* d_out, hipStream_t st);
 hipError_t launch_nodata_mask(const uint8_t* d_valid, int H, int W, int scale, int yb, int ye, int out_nodata, uint16_t* d_out, hipStream_t st);
 
+// radiometric consistency (consistency.hip), in place on block rows [by0, by1) of d_img [S H, S W, 3]; d_lr: the input
+// [H, W, 3]; S 2 or 4.  form 0: the residuals n v - sum of those block rows into d_e (int32 [H, W, 3]; the image is only read);
+// form 1: the exact step; form 2: the smooth step, then the exact one -- it reads d_e of block rows by0 - 1 .. by1 (clamped to the
+// image), which form 0 must have filled from the untouched image.  d_cnt: uint64[3], the inexact blocks per channel, added to.
+// swap: image channel c belongs to input channel 2 - c.
+hipError_t launch_consistency(int form, uint8_t* d_img, const uint8_t* d_lr, int32_t* d_e, unsigned long long* d_cnt, int H, int W, int S,
+                              int by0, int by1, int swap, hipStream_t st);
+hipError_t launch_consistency(int form, uint16_t* d_img, const uint16_t* d_lr, int32_t* d_e, unsigned long long* d_cnt, int H, int W, int S,
+                              int by0, int by1, int lo, int hi, hipStream_t st);
+
 // XYZ tile pyramid (tiles.hip)
 hipError_t launch_warp_bilinear(const uint8_t* d_rgb, int H, int W, const float* d_grid, int gh, int gw, int step, int OH, int OW,
                                 uint8_t* d_out, hipStream_t st);

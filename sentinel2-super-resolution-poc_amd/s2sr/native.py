@@ -144,6 +144,11 @@ _PROTOS = {
     "s2sr_enhance_masked_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(PPParams), C.c_int32, C.c_int32, C.POINTER(Mask),
                                          C.c_void_p]),
     "s2sr_enhance_masked_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.POINTER(Mask), C.c_void_p]),
+    "s2sr_consistency_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
+    "s2sr_consistency_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_void_p]),
+    "s2sr_enhance_consistent_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(PPParams), C.c_int32, C.c_int32, C.POINTER(Mask),
+                                             C.c_int32, C.c_void_p, C.c_void_p]),
+    "s2sr_enhance_consistent_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.POINTER(Mask), C.c_int32, C.c_void_p, C.c_void_p]),
     "s2sr_display_hist_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
     "s2sr_display_apply_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "s2sr_enhance_job_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PPParams), C.c_void_p]),
@@ -770,6 +775,73 @@ class Engine:
         self._check(self._lib.s2sr_enhance_masked_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), int(bool(blend)), C.byref(m),
                                                       _ptr(out)), "s2sr_enhance_masked_u16")
         return out
+
+    # -- radiometric consistency (include/s2sr.h, DESIGN.md 7.5: block means of the output reproduce the input pixels) ------------
+    def consistency(self, sr: np.ndarray, img: np.ndarray, mode: int = 1, lo: int = 0, hi: int = 65535, band_rows: int = 0):
+        """The pass alone: sr [S H, S W, 3] and img [H, W, 3], both uint8 or both uint16 (lo, hi: the 16-bit range), S = 2 or 4
+        from the shapes -> (the consistent image, inexact uint64 [3]); mode 1 exact, 2 smooth; no weights needed."""
+        sr, img = np.asarray(sr), np.asarray(img)
+        if sr.dtype != img.dtype or sr.dtype not in (np.uint8, np.uint16):
+            raise TypeError(f"consistency takes two uint8 or two uint16 images, got {sr.dtype} and {img.dtype}")
+        if sr.ndim != 3 or img.ndim != 3 or sr.shape[2] != 3 or img.shape[2] != 3:
+            raise ValueError(f"consistency: expected [S H, S W, 3] and [H, W, 3], got {sr.shape} and {img.shape}")
+        H, W, _ = img.shape
+        S = sr.shape[0] // H if H else 0
+        if S not in (2, 4) or sr.shape[:2] != (S * H, S * W):
+            raise ValueError(f"consistency: sr {sr.shape} is not 2x or 4x img {img.shape}")
+        sr, img = np.ascontiguousarray(sr), np.ascontiguousarray(img)
+        out = np.empty_like(sr)
+        bad = np.zeros(3, np.uint64)
+        if sr.dtype == np.uint8:
+            self._check(self._lib.s2sr_consistency_u8(self._h, _ptr(sr), _ptr(img), H, W, S, int(mode), int(band_rows), _ptr(out), _ptr(bad)),
+                        "s2sr_consistency_u8")
+        else:
+            self._check(self._lib.s2sr_consistency_u16(self._h, _ptr(sr), _ptr(img), H, W, S, int(lo), int(hi), int(mode), int(band_rows),
+                                                       _ptr(out), _ptr(bad)), "s2sr_consistency_u16")
+        return out, bad
+
+    consistency_u8 = consistency
+    consistency_u16 = consistency
+
+    def _mask_arg(self, valid, H: int, W: int, radius: int, out_nodata: int, what: str):
+        """(the s2sr_mask argument or None, what must stay alive during the call)"""
+        if valid is None:
+            return None, None
+        valid = self._valid(valid, H, W, what)
+        m = Mask(valid.ctypes.data, int(radius), int(out_nodata))
+        return C.byref(m), (valid, m)
+
+    def enhance_consistent_u8(self, img: np.ndarray, mode: int = 1, prm: Optional[PPParams] = None, swap_rb: bool = False, blend: bool = False,
+                              valid=None, radius: int = 32, out_nodata: int = 0, tile: int = 256, pad: int = 10):
+        """enhance_u8 / enhance_job_u8 (swap_rb) / enhance_blend_u8 (blend) / enhance_masked_u8 (valid) with the consistency pass
+        behind the paste -> (the image, inexact uint64 [3])."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        H, W, c = img.shape
+        assert c == 3
+        m, keep = self._mask_arg(valid, H, W, radius, out_nodata, "enhance_consistent_u8")
+        out = pinned_pool.empty((self.scale * H, self.scale * W, 3), np.uint8)
+        bad = np.zeros(3, np.uint64)
+        self._check(self._lib.s2sr_enhance_consistent_u8(self._h, _ptr(img), H, W, tile, pad, C.byref(prm) if prm is not None else None,
+                                                         int(bool(swap_rb)), int(bool(blend)), m, int(mode), _ptr(out), _ptr(bad)),
+                    "s2sr_enhance_consistent_u8")
+        del keep
+        return out, bad
+
+    def enhance_consistent_u16(self, img: np.ndarray, lo: int = 0, hi: int = 65535, mode: int = 1, blend: bool = False, valid=None,
+                               radius: int = 32, out_nodata: int = 0, tile: int = 256, pad: int = 10):
+        """enhance_u16 / enhance_blend_u16 (blend) / enhance_masked_u16 (valid) with the consistency pass -> (the image, inexact)."""
+        if np.asarray(img).dtype != np.uint16:
+            raise TypeError(f"enhance_consistent_u16 takes a uint16 image, got {np.asarray(img).dtype}")
+        img = np.ascontiguousarray(img)
+        H, W, c = img.shape
+        assert c == 3
+        m, keep = self._mask_arg(valid, H, W, radius, out_nodata, "enhance_consistent_u16")
+        out = pinned_pool.empty((4 * H, 4 * W, 3), np.uint16)
+        bad = np.zeros(3, np.uint64)
+        self._check(self._lib.s2sr_enhance_consistent_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), int(bool(blend)), m, int(mode),
+                                                          _ptr(out), _ptr(bad)), "s2sr_enhance_consistent_u16")
+        del keep
+        return out, bad
 
     # -- display rendering of 16-bit images (include/s2sr.h; policy between the two passes: s2sr/display.py) ---------------------
     @staticmethod
