@@ -505,7 +505,7 @@ int  s2sr_debug_pack_f8(const float* w, int32_t cin, int32_t cout, uint8_t* out,
 /* test hook: one 3x3 conv layer on NCHW fp32 host tensors through the generic fp16 form of conv3x3.hip (the EPI_DEBUG
  * instantiations: plain fp16 operands, no split-operand stages, no sub-pixel or whole-patch forms, none of the head / tail
  * epilogues -- no launch of the net runs this form; s2sr_debug_forward_taps checks what does).
- * upsample != 0 -> nearest-2x on load.  act: 0 none, 1 LeakyReLU(0.2). */
+ * upsample != 0 -> nearest-2x on load.  act: 0 none, 1 LeakyReLU(0.2); + 0x100: the launch walks its patches back to front (same bytes). */
 int  s2sr_debug_conv(s2sr_handle* h, const float* x, int32_t N, int32_t Cin, int32_t H, int32_t W,
                      const float* weight, const float* bias, int32_t Cout, int32_t upsample,
                      int32_t act, float* y);
@@ -517,7 +517,7 @@ typedef struct s2sr_debug_config {
     int32_t group;          /* cfg.group as given (0 = default) */
     int32_t trunk_w4;       /* always 1: RDB convs on the one-wave-per-SIMD kernels (conv_trunk.hip) */
     int32_t lo_exp;         /* trunk lo half as e4m3(lo * 2^lo_exp) (S2SR_LO_EXP) */
-    int32_t fp8_form;       /* always 0 (conv_trunk_f8 conv1-4 runs in its one, loader-wave form) */
+    int32_t fp8_form;       /* the launch-order mask (S2SR_SERPENTINE; 0 = every launch walks its patches front to back).  The form this slot named was removed */
     int32_t fp8_x_exp, fp8_g_exp;   /* fp8 trunk activation scales (S2SR_FP8_XEXP / _GEXP or s2sr_calibrate_fp8) */
     int32_t fp8_hp_tail;    /* S2SR_FP8_TAIL=hp */
     int32_t graphs_on;      /* S2SR_GRAPH */
@@ -570,7 +570,8 @@ int  s2sr_debug_plan_bands(const int32_t* chunk_r0, int32_t nchunks, int32_t ny,
  * (fp16 hi, e4m3 lo) pair (kind 2) or fp16 (kind 5).  form: kind 0: 0 auto, 1 = 16x32 patches, 2 = 32x32 patches,
  * 5 = 8x32 patches (single tiles), 6 / 7 / 8 = the whole-patch forms of 2 / 1 / 5, 10 = 8x32 patches with two planes per pipeline
  * stage; kinds 1-2: 0 auto, 1 = 16x32 patches, 5 = 8x32 patches, 10 = 8x32 patches with two planes per stage; kind 3: 0.  The removed
- * forms (kind 0: 3, 4, 9, 11; kinds 1-2: 2; kind 3: anything but 0) are refused (S2SR_E_HIP, not supported). */
+ * forms (kind 0: 3, 4, 9, 11; kinds 1-2: 2; kind 3: anything but 0) are refused (S2SR_E_HIP, not supported).
+ * form + 0x100 (every kind): the launch walks its patches back to front (same bytes). */
 typedef struct s2sr_debug_trunk_args {
     int32_t kind, form;
     int32_t N, Cin, H, W;

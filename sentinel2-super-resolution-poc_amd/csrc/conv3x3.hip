@@ -174,6 +174,9 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
     const int tpi = p.tilesX * p.tilesY;
     const int ntiles = tpi * p.N;
     const int my_tiles = (ntiles - slot_in_round + nwg - 1) / nwg;   // >= 0
+    // my patch of round `it` is tile0 + it * tstep: front to back, or (ConvParams::dbg bit 0) the mirrored walk ntiles - 1 - tile
+    const bool rev = (p.dbg & 1) != 0;
+    const int tile0 = rev ? ntiles - 1 - slot_in_round : slot_in_round, tstep = rev ? -nwg : nwg;
     const int NS = p.nstage;                                         // stages per patch
     const int S = my_tiles * NS;
     const uint32_t sblk = (uint32_t)p.sHp * p.sWp * 32;              // bytes between source blocks
@@ -209,7 +212,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
     // source pointer of the stage under the issue cursor, then advance the cursor
     auto next_src = [&]() __attribute__((always_inline)) -> const char* {
         if (st_i == 0) {
-            const int tile = it_i * nwg + slot_in_round;
+            const int tile = tile0 + it_i * tstep;
             const int n = tile / tpi;
             const int trem = tile - n * tpi;
             const int ty = trem / p.tilesX, tx = trem - ty * p.tilesX;
@@ -484,7 +487,7 @@ __global__ void __launch_bounds__(WAVES * 64, OCC * WAVES / 4) conv3x3_f16(const
 
     // ---- epilogue of the patch at tile iteration `it`
     auto epilogue = [&](int it) __attribute__((always_inline)) {
-        const int tile = it * nwg + slot_in_round;
+        const int tile = tile0 + it * tstep;
         const int n = tile / tpi;
         const int trem = tile - n * tpi;
         const int ty = trem / p.tilesX, tx = trem - ty * p.tilesX;

@@ -201,6 +201,9 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
     const int ntiles = tpi * p.N;
     const int my_tiles = (ntiles - slot_in_round + nwg - 1) / nwg;
     if (my_tiles <= 0) return;                                   // workgroup-uniform
+    // my patch of round `it` is tile0 + it * tstep: front to back, or (ConvParams::dbg bit 0) the mirrored walk ntiles - 1 - tile
+    const bool rev = (p.dbg & 1) != 0;
+    const int tile0 = rev ? ntiles - 1 - slot_in_round : slot_in_round, tstep = rev ? -nwg : nwg;
     const int NS = p.nstage / PL;                                // stages per patch (of PL planes each)
     const uint32_t sblk = (uint32_t)p.sHp * p.sWp * 32;
     const size_t oblk = (size_t)p.Hp * p.Wp * 32;
@@ -235,7 +238,7 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
     const char* wb_i = nullptr;          // its weights
     auto cursor_next = [&]() __attribute__((always_inline)) {
         if (st_i == 0) {
-            const int tile = it_i * nwg + slot_in_round;
+            const int tile = tile0 + it_i * tstep;
             const int n = tile / tpi;
             const int trem = tile - n * tpi;
             const int ty = trem / p.tilesX, tx = trem - ty * p.tilesX;
@@ -353,7 +356,7 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
             rlo[kRR ? buf : 0][kRR ? ct : 0] = asm_load16(p.lo_skip + ln + (size_t)ct * oblk + opix * 32 + hh * 16);
     };
     auto prefetch_lo = [&](int it) __attribute__((always_inline)) {
-        const int tile = it * nwg + slot_in_round;
+        const int tile = tile0 + it * tstep;
         const int n = tile / tpi;
         const int trem = tile - n * tpi;
         const int ty = trem / p.tilesX, tx = trem - ty * p.tilesX;
@@ -480,7 +483,7 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
                 if (kTrunk) asm_land(acc[ct][np]);
                 else asm_land_v(acc[ct][np]);
             }
-        const int tile = it * nwg + slot_in_round;
+        const int tile = tile0 + it * tstep;
         const int n = tile / tpi;
         const int trem = tile - n * tpi;
         const int ty = trem / p.tilesX, tx = trem - ty * p.tilesX;
@@ -809,6 +812,8 @@ __global__ void __launch_bounds__((4 + PROD) * 64, 1) conv_trunk_f8(const ConvPa
     const int ntiles = tpi * p.N;
     const int my_tiles = (ntiles - slot_in_round + nwg - 1) / nwg;
     if (my_tiles <= 0) return;
+    const bool rev = (p.dbg & 1) != 0;                           // the mirrored walk, as in conv_trunk_f16
+    const int tile0 = rev ? ntiles - 1 - slot_in_round : slot_in_round, tstep = rev ? -nwg : nwg;
     const int NSTEP = p.nstage >> 1;                             // pair-steps per patch (nstage is even, host)
     const int nreal = p.seg_len;                                 // real planes; the rest are phantoms
     const uint32_t sblk = (uint32_t)p.sHp * p.sWp * 32;          // bytes between planes
@@ -852,7 +857,7 @@ __global__ void __launch_bounds__((4 + PROD) * 64, 1) conv_trunk_f8(const ConvPa
     };
     auto slab_next = [&]() __attribute__((always_inline)) {
         if (cs.st == 0) {
-            const int tile = cs.it * nwg + slot_in_round;
+            const int tile = tile0 + cs.it * tstep;
             const int n = tile / tpi;
             const int trem = tile - n * tpi;
             const int ty = trem / p.tilesX, tx = trem - ty * p.tilesX;
@@ -1061,7 +1066,7 @@ __global__ void __launch_bounds__((4 + PROD) * 64, 1) conv_trunk_f8(const ConvPa
     // step's barrier drains them with everything else issued before it) instead of stalling the epilogue for an HBM round trip
     u32x2 t_in[kTrunk ? CT : 1][kTrunk ? NP : 1][4];
     auto prefetch_residuals = [&](int it) __attribute__((always_inline)) {
-        const int tile = it * nwg + slot_in_round;
+        const int tile = tile0 + it * tstep;
         const int n = tile / tpi;
         const int trem = tile - n * tpi;
         const int ty = trem / p.tilesX, tx = trem - ty * p.tilesX;
@@ -1180,7 +1185,7 @@ __global__ void __launch_bounds__((4 + PROD) * 64, 1) conv_trunk_f8(const ConvPa
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int np = 0; np < NP; ++np) asm_land(acc[ct][np]);   // tie the wait to the data
-        const int tile = it * nwg + slot_in_round;
+        const int tile = tile0 + it * tstep;
         const int n = tile / tpi;
         const int trem = tile - n * tpi;
         const int ty = trem / p.tilesX, tx = trem - ty * p.tilesX;
@@ -1419,6 +1424,8 @@ hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t s
         if (force_form == 10 || (small && force_form == 0))      // 8x32 patches, two planes per stage, double-buffered
             return epi == EPI_RDB5 ? launch_trunk_t<2, 2, 2, EPI_RDB5, 0, 2>(p, st, form)
                                    : launch_trunk_t<2, 2, 2, EPI_RDB5_RRDB, 0, 2>(p, st, form);
+        // (No whole-patch form here: <2, 4, 4, EPI, FULL = 1> was measured at 221.8 -> 220.2 us and 247.9 -> 246.1 us per headline launch, 0.3 %
+        // of a step and inside the step's repeat spread -- DESIGN.md section 9, profiles/serpentine_bench.txt.)
         if (epi == EPI_RDB5) return small ? launch_trunk_t<2, 2, 5, EPI_RDB5>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5>(p, st, form);
         return small ? launch_trunk_t<2, 2, 5, EPI_RDB5_RRDB>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5_RRDB>(p, st, form);
     }

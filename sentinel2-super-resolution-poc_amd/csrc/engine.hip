@@ -227,14 +227,15 @@ int run_conv(s2sr_handle* h, hipStream_t st, const ConvW& cw, ConvParams p, s2sr
 // launch per output ROW parity (conv3x3.hip, PH template parameter): 4 MACs per output pixel instead of 9.
 // `p` arrives with the tensors (src / src_lo / dst / T and their image strides) and the mosaic; the geometry is set here:
 // n images of Hs x Ws SOURCE pixels in planes of sHp x sWp, written to planes of oHp x oWp.
+// walk[k]: the patch order of row-parity launch k (ConvParams::dbg).
 int run_up_subpixel(s2sr_handle* h, hipStream_t st, const ConvW& cw, ConvParams p, int n, int Hs, int Ws, int sHp, int sWp,
-                    int oHp, int oWp) {
+                    int oHp, int oWp, const int (&walk)[2]) {
     p.N = n; p.H = Hs; p.W = Ws; p.sHp = sHp; p.sWp = sWp; p.Hp = oHp; p.Wp = oWp;
     p.bias = cw.d_bias; p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.seg_lo_mask = cw.seg_lo_mask; p.fold_lo = 0;
     p.tail_form = h->f16_full ? 0 : 8;
     p.trash = h->d_trash;
     for (int k = 0; k < 2; ++k) {
-        p.wpack = cw.d_wphase[k];
+        p.wpack = cw.d_wphase[k]; p.dbg = walk[k];
         Scope sc = layer_scope(h, st, cw, p);
         HIPCHK(h, launch_conv_phase(p, k, st, cw.split));
     }
@@ -298,7 +299,10 @@ int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* 
             }
         return S2SR_OK;
     };
+    int dir = 0;                                              // launch order: see serp_bit (engine_internal.h)
     auto launch = [&](const ConvW& cw, ConvParams p) -> int {
+        if ((h->serpentine >> serp_bit(cw.role)) & 1) dir ^= 1;
+        p.dbg = dir;
         p.wpack = cw.d_wpack; p.bias = cw.d_bias; p.slope = cw.d_slope; p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.seg_lo_mask = 0;
         Scope sc = layer_scope(h, st, cw, p);
         HIPCHK(h, launch_conv(p, cw.form, st));
@@ -346,8 +350,11 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
     auto rdb_conv = [&](int g, int k) -> const ConvW& { return h->conv(L_RDB14, 5 * g + (k - 1)); };   // conv k (1..5) of global RDB g
     int rc;
     const bool fp8 = w.fp8;
+    int dir = 0;                                                  // launch order: the walk of the launch in front, turned where the rule says
+    auto walk = [&](int bit) { if ((h->serpentine >> bit) & 1) dir ^= 1; return dir; };
     {   // conv_first: 3 -> 64 (input = one 16-channel block)
         ConvParams p = b;
+        p.dbg = walk(serp_bit(L_FIRST));
         p.src = w.P0; p.src_img = w.blk1; p.in_scale = in16 ? 1.0f / (float)(in.hi - in.lo) : 1.0f / 255.0f;
         if (fp8) { p.dst = w.Xh[0]; p.dst_img = 4 * w.blk1; }
         else { p.dst = w.D[0]; p.dst_img = 12 * w.blk1; }
@@ -383,6 +390,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
                     p.wpack = cw.d_wpack; p.bias = cw.d_bias; p.wscale = cw.d_wscale;
                     p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.trash = h->d_trash;
                     p.x_exp = xe; p.g_exp = ge; p.xh_img = 4 * w.blk1;
+                    p.dbg = walk(serp_bit(cw.role, k));
                     if (k < 5) {
                         p.dst = w.D8[cur] + (size_t)(2 + (k - 1)) * w.blk1; p.dst_img = 6 * w.blk1;
                     } else {
@@ -424,6 +432,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
                 span_begin(h, st, F_RDB14);                      // conv1..4 of this RDB: one sample
                 for (int k = 1; k <= 4; ++k) {
                     ConvParams p = b;
+                    p.dbg = walk(serp_bit(L_RDB14, k));
                     p.src = w.D[r]; p.src_img = 12 * w.blk1;
                     p.dst = w.D[r] + (size_t)(4 + 2 * (k - 1)) * w.blk1; p.dst_img = 12 * w.blk1;
                     if ((rc = run_conv(h, st, rdb_conv(3 * blk + r, k), p, fo ? fo + (k - 1) : nullptr))) { span_end(h, st); return rc; }
@@ -434,6 +443,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
                 p.dst = w.D[nx]; p.dst_img = 12 * w.blk1;
                 p.xh_in = w.Tr[r]; p.T = w.Tr[nx]; p.lo_exp = h->lo_exp;
                 const ConvW& c5 = rdb_conv(3 * blk + r, 5);
+                p.dbg = walk(serp_bit(c5.role));
                 if (c5.role == L_RDB5_RRDB) { p.xh_skip = w.D[0]; p.xh_img = 12 * w.blk1; p.lo_skip = w.Tr[0]; }
                 if ((rc = run_conv(h, st, c5, p, fo ? fo + 4 : nullptr))) return rc;
             }
@@ -450,6 +460,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
             HIPCHK(h, launch_trunk_to_fp8(trunk_hi, trunk_hi_img, trunk_lo, (trunk_lo_exp >= 0 ? 2 : 4) * w.blk1, trunk_lo_exp, n, w.Hp, w.Wp, w.T8, st));
             p.src_lo = w.T8; p.lo_img = 4 * w.blk1; p.T = w.U0lo;
         }
+        p.dbg = walk(serp_bit(L_BODY));
         if ((rc = run_conv(h, st, h->conv(L_BODY), p))) return rc;
     }
     {   // conv_up1 on nearest-2x
@@ -458,7 +469,8 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         p.src = w.U0; p.src_img = 4 * w.blk1; p.dst = w.U1; p.dst_img = 4 * w.blk2;
         if (hp) { p.src_lo = w.U0lo; p.lo_img = 4 * w.blk1; p.T = w.U1lo; }
         mosaic_at(p, mo, 1);                                         // sub-pixel form: the epilogue walks SOURCE pixels
-        if ((rc = run_up_subpixel(h, st, h->conv(L_UP1), p, n, H, W, w.Hp, w.Wp, w.Hp2, w.Wp2))) return rc;
+        const int wk[2] = {walk(serp_bit(L_UP1)), walk(kSerpUpSecond)};
+        if ((rc = run_up_subpixel(h, st, h->conv(L_UP1), p, n, H, W, w.Hp, w.Wp, w.Hp2, w.Wp2, wk))) return rc;
     }
     {   // conv_up2 on nearest-2x
         ConvParams p{};
@@ -466,7 +478,8 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         p.src = w.U1; p.src_img = 4 * w.blk2; p.dst = w.U2; p.dst_img = 4 * w.blk4;
         if (hp) { p.src_lo = w.U1lo; p.lo_img = 4 * w.blk2; p.T = w.U2lo; }
         mosaic_at(p, mo, 2);
-        if ((rc = run_up_subpixel(h, st, h->conv(L_UP2), p, n, 2 * H, 2 * W, w.Hp2, w.Wp2, w.Hp4, w.Wp4))) return rc;
+        const int wk[2] = {walk(serp_bit(L_UP2)), walk(kSerpUpSecond)};
+        if ((rc = run_up_subpixel(h, st, h->conv(L_UP2), p, n, 2 * H, 2 * W, w.Hp2, w.Wp2, w.Hp4, w.Wp4, wk))) return rc;
     }
     ConvParams hr{};
     hr.N = n; hr.H = 4 * H; hr.W = 4 * W; hr.Hp = w.Hp4; hr.Wp = w.Wp4; hr.sHp = w.Hp4; hr.sWp = w.Wp4;
@@ -475,12 +488,14 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
         ConvParams p = hr;
         p.src = w.U2; p.src_img = 4 * w.blk4; p.dst = w.U3; p.dst_img = 4 * w.blk4;
         if (hp) { p.src_lo = w.U2lo; p.lo_img = 4 * w.blk4; p.T = w.U3lo; }
+        p.dbg = walk(serp_bit(L_HR));
         if ((rc = run_conv(h, st, h->conv(L_HR), p))) return rc;
     }
     {
         ConvParams p = hr;
         p.src = w.U3; p.src_img = 4 * w.blk4; p.out_f32 = d_out_f32; p.out_u8 = d_out_u8; p.cout = 3;
         if (hp) { p.src_lo = w.U3lo; p.lo_img = 4 * w.blk4; }
+        p.dbg = walk(serp_bit(L_LAST));
         if ((rc = run_conv(h, st, h->conv(L_LAST), p))) return rc;
     }
     return S2SR_OK;
@@ -897,6 +912,14 @@ size_t s2sr_expected_blob_floats_cfg(const s2sr_config* cfg) {
 
 const char* s2sr_last_error(const s2sr_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
+// S2SR_SERPENTINE: the launch order of a handle (engine_internal.h serp_bit), fixed at creation like the kernel-form switches read in
+// s2sr_create.  0: every launch walks front to back; any other number: that turn mask; unset: kSerpentineDefault.  Unlike those
+// switches it selects no kernel and changes no byte of any result.
+static int launch_order_from_env() {
+    const char* g = getenv("S2SR_SERPENTINE");
+    return g ? (int)strtol(g, nullptr, 0) : s2sr::engine::kSerpentineDefault;
+}
+
 int s2sr_create(const s2sr_config* cfg, s2sr_handle** out) {
     if (!cfg || !out) return fail(nullptr, S2SR_E_INVALID, "null argument");
     *out = nullptr;
@@ -936,6 +959,7 @@ int s2sr_create(const s2sr_config* cfg, s2sr_handle** out) {
     if (const char* g = getenv("S2SR_MOSAIC")) h->mosaic_on = atoi(g) != 0;
     if (const char* g = getenv("S2SR_SMALL8")) h->small8 = atoi(g) != 0;
     if (const char* g = getenv("S2SR_F16_FULL")) h->f16_full = atoi(g) != 0;
+    h->serpentine = launch_order_from_env();                 // S2SR_SERPENTINE, read here with the others
     if (const char* g = getenv("S2SR_LAST_FOLD")) h->last_fold = atoi(g) != 0;
     if (const char* g = getenv("S2SR_D2H_STAGED")) h->d2h_staged_on = atoi(g) != 0;
     if (const char* g = getenv("S2SR_FP8_TAIL")) h->fp8_hp_tail = strcmp(g, "hp") == 0;

@@ -169,7 +169,8 @@ int s2sr_debug_conv(s2sr_handle* h, const float* x, int32_t N, int32_t Cin, int3
     ConvParams p{};
     p.src = d_plane; p.src_img = (uint64_t)NB * sblk; p.nstage = NB;
     p.wpack = d_w; p.bias = d_b; p.N = N; p.H = OHh; p.W = OWw; p.Hp = Hp; p.Wp = Wp; p.sHp = sHp; p.sWp = sWp;
-    p.out_f32 = d_y; p.cout = Cout; p.act = act; p.trash = h->d_trash;
+    p.out_f32 = d_y; p.cout = Cout; p.act = act & 0xff; p.trash = h->d_trash;
+    p.dbg = (act >> 8) & 1;                                   // bit 8 of `act`: the patches back to front
     const ConvForm form = Cout <= 32 ? (upsample ? CF_DEBUG1_UP : CF_DEBUG1) : (upsample ? CF_DEBUG2_UP : CF_DEBUG2);
     HIPCHK(h, launch_conv(p, form, st));
     HIPCHK(h, hipMemcpyAsync(y, d_y, yb, hipMemcpyDeviceToHost, st));
@@ -267,9 +268,9 @@ int s2sr_debug_get_config(s2sr_handle* h, s2sr_debug_config* out) {
     if (!h || !out) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     memset(out, 0, sizeof *out);
-    // trunk_w4 always 1; trunk_wino, fp8_form, reserved[1] and reserved[3] always 0 (the forms they named were removed)
+    // trunk_w4 always 1; trunk_wino, reserved[1] and reserved[3] always 0 (the forms they named were removed); fp8_form's slot: the launch-order mask
     out->precision = h->cfg.precision; out->group = h->cfg.group; out->trunk_w4 = 1; out->lo_exp = h->lo_exp;
-    out->fp8_x_exp = h->fp8_x_exp; out->fp8_g_exp = h->fp8_g_exp; out->fp8_hp_tail = h->fp8_hp_tail ? 1 : 0;
+    out->fp8_x_exp = h->fp8_x_exp; out->fp8_g_exp = h->fp8_g_exp; out->fp8_hp_tail = h->fp8_hp_tail ? 1 : 0; out->fp8_form = h->serpentine;
     out->graphs_on = h->graphs_on ? 1 : 0; out->reserved[0] = h->mosaic_on ? 1 : 0; out->reserved[2] = h->last_fold ? 1 : 0; out->reserved[4] = h->f16_full ? 1 : 0; out->reserved[5] = (int32_t)h->ws_allocs;
     return S2SR_OK;
 }
@@ -342,6 +343,8 @@ int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
     p.N = N; p.H = H; p.W = W; p.Hp = Hp; p.Wp = Wp; p.sHp = Hp; p.sWp = Wp;
     p.src = (const char*)d_D.p; p.src_img = dimg; p.wpack = d_wp.p; p.bias = (const float*)d_b.p; p.trash = h->d_trash;
     const int epi = !c5 ? EPI_LRELU : (rr ? EPI_RDB5_RRDB : EPI_RDB5);
+    const int form = a->form & 0xff;                          // bit 8 of `form`: the patches back to front
+    p.dbg = (a->form >> 8) & 1;
     std::vector<char> tmp;
     if (!f8) {
         p.nstage = Cin / 16; p.seg_len = p.nstage; p.lo_exp = le;
@@ -370,7 +373,7 @@ int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
                 p.xh_skip = (const char*)d_Sk.p; p.xh_img = 4 * blk; p.lo_skip = (const char*)d_SkLo.p;
             }
         }
-        const hipError_t e = launch_conv_trunk(p, Cout / 32, epi, st, a->form);
+        const hipError_t e = launch_conv_trunk(p, Cout / 32, epi, st, form);
         if (e != hipSuccess) return fail(h, S2SR_E_HIP, std::string("launch_conv_trunk: ") + hipGetErrorString(e));
     } else {
         p.seg_len = Cin / 32; p.nstage = (p.seg_len + 1) & ~1; p.wscale = (const int32_t*)d_ws.p;
@@ -404,7 +407,7 @@ int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
             }
         }
         // conv1-4: the loader-wave form is the only one (the others the measurements buried are refused)
-        const hipError_t e = (kind == 3 && a->form != 0) ? hipErrorNotSupported : launch_conv_trunk_f8(p, Cout / 32, epi, st);
+        const hipError_t e = (kind == 3 && form != 0) ? hipErrorNotSupported : launch_conv_trunk_f8(p, Cout / 32, epi, st);
         if (e != hipSuccess) return fail(h, S2SR_E_HIP, std::string("launch_conv_trunk_f8: ") + hipGetErrorString(e));
     }
     HIPCHK(h, hipStreamSynchronize(st));

@@ -25,6 +25,16 @@ enum Role {
 };
 constexpr int kRoles = L_CLAST + 1;
 inline bool is_rdb(Role r) { return r == L_RDB14 || r == L_RDB5 || r == L_RDB5_RRDB; }
+
+// Launch order.  Every conv kernel walks its patches image-major, front to back, or mirrored (ConvParams::dbg bit 0).
+// The schedules keep one direction and turn it round in front of the launches whose bit is set in s2sr_handle::serpentine: bit `role`
+// for a layer of that Role, bits 12..15 for conv1..4 of an RDB (L_RDB14 itself has none), bit 16 for the second row-parity launch of an
+// up-conv.  A turned launch meets the planes the launch before it touched last.  The rule is static, so a captured graph replays one order.
+inline int serp_bit(Role r, int k = 0) { return r == L_RDB14 ? 12 + (k - 1) : (int)r; }
+constexpr int kSerpUpSecond = 16;
+// Default: every launch of the RRDB nets walks opposite to the one in front of it (profiles/serpentine_bench.txt: the gain is the trunk's,
+// conv2..5 meeting the planes of the launch before; the tail neither gains nor loses).  The compact nets were not measured and keep one direction.
+constexpr int kSerpentineDefault = 0x1F1FC;
 struct Layer {
     Role role;
     int cin, cout, extra;      // extra: floats behind the bias (the 64 PReLU slopes of a compact conv, 0 otherwise)
@@ -225,7 +235,8 @@ struct s2sr_handle {
     int64_t ws_allocs = 0;        // workspace (re)allocations since s2sr_create (s2sr_debug_get_config reserved[5])
     bool last_fold = true;        // S2SR_LAST_FOLD=0: conv_last (hp) reads all four e4m3 planes (8 stages) instead of folding w_lo into idle couts
     bool f16_full = true;         // S2SR_F16_FULL=0: fp16 conv1-4 never take the whole-patch form (no px_live arithmetic in the epilogue) on 32-multiple launches
-    bool small8 = true;           // S2SR_SMALL8=0: single tiles keep the 16x32-patch form of fp16 conv1-4 (default: 8x32 patches, 256 per 256x256 tile)
+    int serpentine = s2sr::engine::kSerpentineDefault;   // S2SR_SERPENTINE=0: every launch walks its patches front to back; otherwise the flip mask of run_net's launch order
+    bool small8 = true;          // S2SR_SMALL8=0: single tiles keep the 16x32-patch form of fp16 conv1-4 (default: 8x32 patches, 256 per 256x256 tile)
     bool mosaic_on = true;        // S2SR_MOSAIC=0: windows that are no multiple of the 32-pixel patch travel one per image (ConvParams::mos_*)
     // paste maps of the window plan last stitched through s2sr_stitch_rows_u8_dev (row map, column map), kept on the device:
     // an AOI is stitched band by band, the maps are uploaded once per (H, W, tile, pad)

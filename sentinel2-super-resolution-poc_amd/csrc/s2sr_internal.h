@@ -155,7 +155,8 @@ struct ConvParams {
                              // argument its offset: the RRDB kernels compile to the parent's instructions.)
                              // EPI_CLAST takes the packed input (fp16 blocked-16, one block: channels 0..2 = the pixel's exact 0..255
                              // values, for the nearest-x4 base) as src_lo / lo_img: the loader never reads src_lo of a plain conv
-    int32_t dbg;                 // unused (kept so that every kernel argument stays at its offset)
+    int32_t dbg;                 // bit 0: walk the launch's patches back to front (tile -> ntiles - 1 - tile; same patches, same bytes: the
+                                 // launch order of engine.hip's schedules, engine_internal.h serp_bit).  Took an unused slot: no argument moved
 };
 
 // is output pixel (y, x) of this launch one the reference writes (inside the image, and not a mosaic separator)?

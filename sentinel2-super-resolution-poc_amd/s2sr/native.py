@@ -1078,7 +1078,8 @@ class Engine:
 
     # -- test hook --------------------------------------------------------------------------
     def debug_conv(self, x: np.ndarray, weight: np.ndarray, bias: np.ndarray, upsample: bool = False,
-                   act: bool = False) -> np.ndarray:
+                   act: bool = False, backwards: bool = False) -> np.ndarray:
+        # backwards: the launch walks its patches back to front (bit 8 of the hook's `act`; same bytes)
         x = np.ascontiguousarray(x, dtype=np.float32)
         weight = np.ascontiguousarray(weight, dtype=np.float32)
         bias = np.ascontiguousarray(bias, dtype=np.float32)
@@ -1088,11 +1089,12 @@ class Engine:
         s = 2 if upsample else 1
         y = np.empty((N, cout, s * H, s * W), dtype=np.float32)
         self._check(self._lib.s2sr_debug_conv(self._h, _ptr(x), N, cin, H, W, _ptr(weight), _ptr(bias), cout,
-                                              int(upsample), int(act), _ptr(y)), "s2sr_debug_conv")
+                                              int(upsample), int(act) | (WALK_BACKWARDS if backwards else 0), _ptr(y)), "s2sr_debug_conv")
         return y
 
 
 TRUNK_F16_CONV14, TRUNK_F16_CONV5, TRUNK_F16_CONV5_RRDB, TRUNK_F8_CONV14, TRUNK_F8_CONV5, TRUNK_F8_CONV5_RRDB = range(6)
+WALK_BACKWARDS = 0x100      # bit 8 of s2sr_debug_conv_trunk's `form` / s2sr_debug_conv's `act`: the launch's patches back to front
 
 
 def _debug_config(self) -> dict:
@@ -1105,12 +1107,14 @@ def _debug_config(self) -> dict:
     d["last_fold"] = int(c.reserved[2])
     d["tail_w4"] = int(c.reserved[3])
     d["f16_full"] = int(c.reserved[4])
+    d["serpentine"] = int(c.fp8_form)       # the launch-order mask travels in the retired fp8_form slot
     d["ws_allocs"] = int(c.reserved[5])
     return d
 
 
-def _debug_conv_trunk(self, kind, x, weight, bias, lo=None, skip=None, form=0):
+def _debug_conv_trunk(self, kind, x, weight, bias, lo=None, skip=None, form=0, backwards=False):
     """One RDB-shaped conv through conv_trunk_f16 / conv_trunk_f8 (include/s2sr.h: s2sr_debug_conv_trunk).
+    backwards: the launch walks its patches back to front (WALK_BACKWARDS in `form`; same bytes).
     Returns y, or (y, y_aux) for the fp8 conv5 kinds."""
     x = np.ascontiguousarray(x, np.float32)
     weight = np.ascontiguousarray(weight, np.float32)
@@ -1123,7 +1127,7 @@ def _debug_conv_trunk(self, kind, x, weight, bias, lo=None, skip=None, form=0):
     lo = None if lo is None else np.ascontiguousarray(lo, np.float32)
     skip = None if skip is None else np.ascontiguousarray(skip, np.float32)
     p = lambda a: None if a is None else a.ctypes.data
-    args = DebugTrunkArgs(kind, form, N, cin, H, W, p(x), p(weight), p(bias), p(lo), p(skip), p(y), p(aux))
+    args = DebugTrunkArgs(kind, form | (WALK_BACKWARDS if backwards else 0), N, cin, H, W, p(x), p(weight), p(bias), p(lo), p(skip), p(y), p(aux))
     self._check(self._lib.s2sr_debug_conv_trunk(self._h, C.byref(args)), "s2sr_debug_conv_trunk")
     return y if aux is None else (y, aux)
 
