@@ -741,6 +741,34 @@ int64_t s2sr_debug_redzone_bytes(void);       /* the zone size in force (0: off)
 int  s2sr_debug_redzone_check(s2sr_handle* h, int64_t* allocations, int64_t* damaged);
 int  s2sr_debug_redzone_poke(s2sr_handle* h, int32_t slot, int64_t offset);
 
+/* test hooks: poisoned device memory (csrc/redzone.h, namespace poison).  The red zones catch a store outside a buffer; this catches
+ * a LOAD of in-bounds bytes that nobody wrote in this call -- a histogram without its memset, a stream assembled with atomicOr,
+ * a scratch slot that still holds the previous call's bytes.  Fresh device memory reads as zeros in practice and the scratch slots
+ * of a handle grow and are never cleared, so such a load returns a plausible value in a fresh process and something else in a
+ * long-lived one.  Process-wide; off by default, and then every allocation, pointer and byte is what it is without these entries.
+ * Works with and without red zones.  The environment variable S2SR_POISON=<1|2>, read once when the library is loaded, sets the
+ * initial pattern (another value is reported on stderr and leaves the mode off).
+ *
+ * s2sr_debug_poison: every device and page-locked host allocation the library makes FROM NOW ON is filled with the pattern before
+ *   anybody sees it; 0 turns the mode off.  Pattern 1: every byte 0xFF (a NaN as fp32, fp16 and e4m3, -1 as an int32, 255 as a
+ *   u8); pattern 2: a non-zero byte that depends on its position (the red zones' front pattern).  The workspace is still zeroed
+ *   after the fill: its zero halos are the convs' padding, part of the contract and no leftover.  S2SR_E_INVALID for any other
+ *   value.  Existing allocations keep their bytes.
+ * s2sr_debug_poison_scratch: waits for the handle's streams (work a caller put on a stream of its own: synchronise it first),
+ *   then fills every allocated scratch slot over its whole capacity, and the trash page, with the pattern in force, and forgets
+ *   what a call left in scratch for the next one (the tile level, the warped raster, the 16-bit image, an open banded
+ *   post-process) exactly as a call that takes scratch does.  Nothing is moved or freed: captured graphs stay valid and replay
+ *   on the poisoned bytes.  *slots: bit i set = slot i was filled; bytes[i] (S2SR_SCRATCH_SLOTS entries): its capacity, 0 when
+ *   the slot is not allocated.  S2SR_E_INVALID when the mode is off.
+ * s2sr_debug_scratch_peek: copies n bytes at `offset` of scratch slot `slot` (-1: the trash page, S2SR_TRASH_BYTES long) to `out`,
+ *   after waiting for the handle's streams.  S2SR_E_INVALID when the range is not inside the slot's capacity.  Works in either mode. */
+#define S2SR_SCRATCH_SLOTS 8
+#define S2SR_TRASH_BYTES 8192
+int  s2sr_debug_poison(int32_t pattern);
+int32_t s2sr_debug_poison_pattern(void);      /* the pattern in force (0: off), for callers that switch it and put it back */
+int  s2sr_debug_poison_scratch(s2sr_handle* h, int64_t* slots, int64_t* bytes);
+int  s2sr_debug_scratch_peek(s2sr_handle* h, int32_t slot, int64_t offset, int64_t n, uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -289,6 +289,7 @@ bool recover_stream(s2sr_handle* h);
         return rc_;                                  \
     } while (0)
 
+constexpr size_t kTrashBytes = 8192;   // s2sr_handle::d_trash
 int ensure_scratch(s2sr_handle* h, int slot, size_t bytes);
 hipError_t copy_blocking(s2sr_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
 hipError_t fill_blocking(s2sr_handle* h, void* dst, int value, size_t bytes);

@@ -183,3 +183,46 @@ private:
 };
 
 }  // namespace s2sr::redzone
+
+// Poisoned memory (the diagnostic mode behind s2sr_debug_poison, include/s2sr.h): the bytes an allocation hands out, and the bytes a
+// scratch slot keeps between calls, are filled with a pattern that is never the zeros fresh memory reads as, so a kernel that reads
+// in-bounds bytes nobody wrote in this call computes something visibly different.  The pattern and the fill live here, host-only and
+// reached through the same two callbacks, so tests/native/poison_main.cpp runs them on exact-size heap blocks under ASan / UBSan.
+namespace s2sr::poison {
+
+constexpr int kOff = 0, kOnes = 1, kPositional = 2;
+inline bool valid(int64_t pat) { return pat >= kOff && pat <= kPositional; }
+
+// Byte i of a poisoned range.  Pattern 1: 0xFF everywhere -- a NaN in fp32 and fp16, the e4m3 NaN code, -1 as an int32 (an index
+// that was never uploaded points in front of its table), 255 as a u8.  Pattern 2: the front-zone pattern of the red zones, non-zero
+// and different from byte to byte, so a value assembled from stale bytes differs from one position to the next.
+inline uint8_t byte_at(int pat, size_t i) { return pat == kOnes ? (uint8_t)0xFF : redzone::pattern(false, i); }
+
+// The fill goes out in chunks of kChunk bytes; pattern 2 repeats every 65536 bytes (167 * 65536 and 13 * 256 are multiples of
+// 256), so one chunk's bytes serve every chunk.
+constexpr size_t kPeriod = 65536, kChunk = 16 * kPeriod;
+
+// fill [dst, dst + bytes) with pattern `pat` (kOff: nothing is written); false: a callback failed
+inline bool fill(const redzone::DeviceIo& io, void* dst, size_t bytes, int pat) {
+    if (pat == kOff || !bytes) return true;
+    std::vector<uint8_t> buf(std::min(bytes, kChunk));
+    for (size_t i = 0; i < buf.size(); ++i) buf[i] = byte_at(pat, i);
+    for (size_t o = 0; o < bytes; o += kChunk)
+        if (!io.write(io.ctx, (char*)dst + o, buf.data(), std::min(kChunk, bytes - o))) return false;
+    return true;
+}
+
+// *first: the offset of the first byte of [src, src + bytes) that does not hold pattern `pat`, `bytes` when all do; false: a callback failed
+inline bool first_unpoisoned(const redzone::DeviceIo& io, const void* src, size_t bytes, int pat, size_t* first) {
+    std::vector<uint8_t> buf(std::min(bytes, kChunk));
+    *first = bytes;
+    for (size_t o = 0; o < bytes; o += kChunk) {
+        const size_t n = std::min(kChunk, bytes - o);
+        if (!io.read(io.ctx, buf.data(), (const char*)src + o, n)) return false;
+        for (size_t i = 0; i < n; ++i)
+            if (buf[i] != byte_at(pat, o + i)) { *first = o + i; return true; }
+    }
+    return true;
+}
+
+}  // namespace s2sr::poison

@@ -1,7 +1,9 @@
-// libs2sr red-zone mode (host code only): the device side of csrc/redzone.h -- dev_malloc / dev_free with zones, the zones between
-// the workspace planes, and the three s2sr_debug_redzone* entries of include/s2sr.h.  Off by default; see s2sr_internal.h.
+// libs2sr red-zone and poison modes (host code only): the device side of csrc/redzone.h -- dev_malloc / dev_free with zones, the zones
+// between the workspace planes, the poison fill of fresh allocations and of the scratch slots, and the s2sr_debug_redzone* /
+// s2sr_debug_poison* / s2sr_debug_scratch_peek entries of include/s2sr.h.  Both off by default; see s2sr_internal.h.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <mutex>
 #include <string>
@@ -14,6 +16,7 @@ using namespace s2sr::engine;
 
 std::atomic<size_t> s2sr::g_redzone_bytes{0};
 std::atomic<bool> s2sr::g_redzone_ever{false};
+std::atomic<int> s2sr::g_poison{0};
 
 namespace {
 
@@ -69,6 +72,25 @@ struct EnvSwitch {
     }
 } g_env_switch;
 
+// pinned host memory is the host's to write: the same fill through a memcpy
+bool host_write(void*, void* dst, const uint8_t* src, size_t n) { memcpy(dst, src, n); return true; }
+bool host_read(void*, uint8_t* dst, const void* src, size_t n) { memcpy(dst, src, n); return true; }
+const redzone::DeviceIo kHostIo{host_write, host_read, nullptr};
+
+// S2SR_POISON=<1|2>, read once when the library is loaded: the initial pattern
+struct PoisonEnvSwitch {
+    PoisonEnvSwitch() {
+        const char* g = getenv("S2SR_POISON");
+        if (!g || !*g) return;
+        char* end = nullptr;
+        const long long v = strtoll(g, &end, 10);
+        if (end == g || *end || v < 1 || !poison::valid(v))
+            fprintf(stderr, "s2sr: S2SR_POISON=%s is neither 1 nor 2: poison stays off\n", g);
+        else
+            g_poison.store((int)v);
+    }
+} g_poison_env_switch;
+
 void sync_handle(s2sr_handle* h) {
     hipSetDevice(h->cfg.device);
     if (h->stream) hipStreamSynchronize(h->stream);
@@ -103,7 +125,62 @@ hipError_t s2sr::redzone_add_plane(void* parent, void* plane, size_t bytes, size
     return registry().add(kIo, plane, bytes, 0, back, parent) ? hipSuccess : hipErrorUnknown;
 }
 
+hipError_t s2sr::poison_device(void* p, size_t bytes, int pat) {
+    return poison::fill(kIo, p, bytes, pat) ? hipSuccess : hipErrorUnknown;
+}
+
+void s2sr::poison_host(void* p, size_t bytes, int pat) { (void)poison::fill(kHostIo, p, bytes, pat); }
+
 extern "C" {
+
+static_assert(s2sr_handle::kScratchSlots == S2SR_SCRATCH_SLOTS && kTrashBytes == S2SR_TRASH_BYTES, "include/s2sr.h states both");
+
+int s2sr_debug_poison(int32_t pattern) {
+    if (!poison::valid(pattern)) return fail(nullptr, S2SR_E_INVALID, "poison pattern must be 0 (off), 1 (all 0xFF) or 2 (position-dependent)");
+    g_poison.store(pattern);
+    return S2SR_OK;
+}
+
+int32_t s2sr_debug_poison_pattern(void) { return g_poison.load(); }
+
+int s2sr_debug_poison_scratch(s2sr_handle* h, int64_t* slots, int64_t* bytes) {
+    if (!h || !slots || !bytes) return fail(h, S2SR_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int pat = g_poison.load();
+    if (pat == poison::kOff) return fail(h, S2SR_E_INVALID, "poison mode is off (s2sr_debug_poison)");
+    sync_handle(h);
+    DeviceGate g;
+    // what ensure_scratch voids, for the same reason: whatever a call left in scratch for the next one is gone
+    h->tiles_slot = -1;
+    h->warp_slot = -1;
+    h->disp_slot = -1;
+    h->ppb.open = false;
+    *slots = 0;
+    for (int i = 0; i < s2sr_handle::kScratchSlots; ++i) {
+        bytes[i] = 0;
+        if (!h->d_scratch[i] || !h->scratch_bytes[i]) continue;
+        if (!poison::fill(kIo, h->d_scratch[i], h->scratch_bytes[i], pat)) return fail(h, S2SR_E_HIP, "poison fill of a scratch slot failed");
+        *slots |= (int64_t)1 << i;
+        bytes[i] = (int64_t)h->scratch_bytes[i];
+    }
+    if (h->d_trash && !poison::fill(kIo, h->d_trash, kTrashBytes, pat)) return fail(h, S2SR_E_HIP, "poison fill of the trash page failed");
+    return S2SR_OK;
+}
+
+int s2sr_debug_scratch_peek(s2sr_handle* h, int32_t slot, int64_t offset, int64_t n, uint8_t* out) {
+    if (!h || !out) return fail(h, S2SR_E_INVALID, "null argument");
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (slot < -1 || slot >= s2sr_handle::kScratchSlots) return fail(h, S2SR_E_INVALID, "scratch slot out of range (-1: the trash page, 0..7)");
+    const char* base = slot < 0 ? h->d_trash : (const char*)h->d_scratch[slot];
+    const size_t cap = slot < 0 ? (h->d_trash ? kTrashBytes : 0) : h->scratch_bytes[slot];
+    if (!base || offset < 0 || n < 0 || (uint64_t)offset > cap || (uint64_t)n > cap - (uint64_t)offset)
+        return fail(h, S2SR_E_INVALID, "the range is not inside this scratch slot");
+    if (!n) return S2SR_OK;
+    sync_handle(h);
+    DeviceGate g;
+    if (!io_read(nullptr, out, base + offset, (size_t)n)) return fail(h, S2SR_E_HIP, "scratch read-back failed");
+    return S2SR_OK;
+}
 
 int s2sr_debug_redzone(int64_t bytes) {
     if (!set_zone(bytes)) return fail(nullptr, S2SR_E_INVALID, "red zone bytes must be 0 or a positive multiple of 4096");

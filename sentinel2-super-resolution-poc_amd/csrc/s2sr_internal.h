@@ -41,10 +41,26 @@ extern std::atomic<size_t> g_redzone_bytes;     // Z of the allocations made fro
 extern std::atomic<bool> g_redzone_ever;        // the mode has been on at some point: dev_free looks its pointer up
 hipError_t redzone_malloc(void** p, size_t bytes, size_t zone);   // both with the device gate held
 hipError_t redzone_free(void* p);
+// Poison (redzone.h namespace poison, redzone.hip; the diagnostic mode of s2sr_debug_poison / S2SR_POISON): with a pattern in force
+// dev_malloc and host_malloc fill the caller's bytes with it before they hand the pointer out, so nobody finds the zeros fresh memory
+// reads as.  With and without zones; off (the default), the cost is one atomic load per allocation.
+extern std::atomic<int> g_poison;               // 0 off, 1 all 0xFF, 2 position-dependent
+hipError_t poison_device(void* p, size_t bytes, int pat);   // with the device gate held; on the red-zone I/O stream
+void poison_host(void* p, size_t bytes, int pat);
 template <class T> static inline hipError_t dev_malloc(T** p, size_t bytes) {
     DeviceGate g;
-    if (const size_t z = g_redzone_bytes.load(std::memory_order_relaxed)) return redzone_malloc((void**)p, bytes, z);
-    return hipMalloc((void**)p, bytes);
+    const size_t z = g_redzone_bytes.load(std::memory_order_relaxed);
+    const hipError_t e = z ? redzone_malloc((void**)p, bytes, z) : hipMalloc((void**)p, bytes);
+    if (e != hipSuccess) return e;
+    if (const int pat = g_poison.load(std::memory_order_relaxed)) {
+        const hipError_t ep = poison_device(*p, bytes, pat);
+        if (ep != hipSuccess) {                       // nothing half-poisoned is handed out
+            (void)(g_redzone_ever.load(std::memory_order_relaxed) ? redzone_free(*p) : hipFree(*p));
+            *p = nullptr;
+            return ep;
+        }
+    }
+    return e;
 }
 static inline hipError_t dev_free(void* p) {
     DeviceGate g;
@@ -53,7 +69,13 @@ static inline hipError_t dev_free(void* p) {
 }
 // a zone of `back` bytes behind the `bytes` of `plane`, a piece of the zoned allocation `parent` (the workspace planes)
 hipError_t redzone_add_plane(void* parent, void* plane, size_t bytes, size_t back);
-static inline hipError_t host_malloc(void** p, size_t bytes, unsigned flags) { DeviceGate g; return hipHostMalloc(p, bytes, flags); }
+static inline hipError_t host_malloc(void** p, size_t bytes, unsigned flags) {
+    DeviceGate g;
+    const hipError_t e = hipHostMalloc(p, bytes, flags);
+    if (e != hipSuccess) return e;
+    if (const int pat = g_poison.load(std::memory_order_relaxed)) poison_host(*p, bytes, pat);
+    return e;
+}
 static inline hipError_t host_free(void* p) { DeviceGate g; return hipHostFree(p); }
 
 // ------------------------------------------------------------------------------------------

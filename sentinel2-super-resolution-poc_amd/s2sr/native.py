@@ -213,6 +213,10 @@ _PROTOS = {
     "s2sr_debug_redzone_bytes": (C.c_int64, []),
     "s2sr_debug_redzone_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "s2sr_debug_redzone_poke": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64]),
+    "s2sr_debug_poison": (C.c_int, [C.c_int32]),
+    "s2sr_debug_poison_pattern": (C.c_int32, []),
+    "s2sr_debug_poison_scratch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "s2sr_debug_scratch_peek": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -1264,6 +1268,48 @@ def _redzone_poke(self, slot: int, offset: int):
 
 Engine.redzone_check = _redzone_check
 Engine.redzone_poke = _redzone_poke
+
+SCRATCH_SLOTS, TRASH_BYTES = 8, 8192            # include/s2sr.h S2SR_SCRATCH_SLOTS, S2SR_TRASH_BYTES
+
+
+def poison(pattern: int):
+    """Fill every device and page-locked allocation the library makes from now on with a pattern (include/s2sr.h:
+    s2sr_debug_poison): 0 off, 1 every byte 0xFF, 2 a position-dependent non-zero byte.  Process-wide; a diagnostic."""
+    rc = load_library().s2sr_debug_poison(int(pattern))
+    if rc:
+        raise S2srError(f"s2sr_debug_poison({pattern}) failed ({_ERR.get(rc, rc)}): 0, 1 or 2")
+
+
+def poison_pattern() -> int:
+    """The pattern in force (0: off): what a caller that switches the mode puts back."""
+    return int(load_library().s2sr_debug_poison_pattern())
+
+
+def poison_byte(pattern: int, i):
+    """Byte(s) i of a range poisoned with `pattern` (csrc/redzone.h poison::byte_at), for the controls."""
+    i = np.asarray(i, dtype=np.uint64)
+    if pattern == 1:
+        return np.full(i.shape, 0xFF, np.uint8)
+    return (((i * np.uint64(167) + (i >> np.uint64(8)) * np.uint64(13) + np.uint64(0x5B)) & np.uint64(0xFF)) | np.uint64(1)).astype(np.uint8)
+
+
+def _poison_scratch(self) -> dict:
+    """Fill this engine's scratch slots and trash page with the pattern in force and forget what the last call left there
+    (include/s2sr.h s2sr_debug_poison_scratch).  Returns {slot: capacity in bytes} of the slots filled."""
+    mask, cap = C.c_int64(0), (C.c_int64 * SCRATCH_SLOTS)()
+    self._check(self._lib.s2sr_debug_poison_scratch(self._h, C.byref(mask), cap), "s2sr_debug_poison_scratch")
+    return {i: int(cap[i]) for i in range(SCRATCH_SLOTS) if mask.value >> i & 1}
+
+
+def _scratch_peek(self, slot: int, offset: int, n: int) -> np.ndarray:
+    """n bytes at `offset` of scratch slot `slot` (-1: the trash page): include/s2sr.h s2sr_debug_scratch_peek."""
+    out = np.empty(int(n), np.uint8)
+    self._check(self._lib.s2sr_debug_scratch_peek(self._h, int(slot), int(offset), int(n), out.ctypes.data), "s2sr_debug_scratch_peek")
+    return out
+
+
+Engine.poison_scratch = _poison_scratch
+Engine.scratch_peek = _scratch_peek
 
 
 def expected_blob_floats_cfg(num_block: int, scale: int = 4, arch: str = "rrdb") -> int:
