@@ -167,7 +167,17 @@ int  s2sr_plan_tiles(int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t sc
 int  s2sr_forward_batch_u8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int32_t th, int32_t tw,
                            uint8_t* out);
 /* same with device-resident input/output, asynchronous on `stream` (a hipStream_t; NULL = the
- * default stream, ordered with the caller's other default-stream work) */
+ * default stream, ordered with the caller's other default-stream work).
+ * STREAMS, for this and every other *_dev entry (forward_batch_u16, forward_part, cut_windows, stitch_windows / stitch_rows,
+ * postprocess_batch, pp_band_*): the call returns while its work is queued on `stream`.
+ *   The library orders by itself: everything it enqueues for the call behind what `stream` already holds (so behind the work
+ *   that produces the input); the call behind an earlier call on the same handle that is still running on ANOTHER stream --
+ *   the handle records an event behind each *_dev call's last enqueue, and the next call on a different stream (a caller's, or
+ *   the handle's own for the host-facing entries) makes that stream wait for it before it touches the workspace, the scratch
+ *   slots or a graph; and its own copy stream against the compute stream.
+ *   Left to the caller: its own buffers.  The input must not be overwritten, nor the output read, on another stream before
+ *   `stream` has passed the call (synchronise it, or record an event behind the call and wait for that); a buffer handed to
+ *   two calls on two streams is the caller's race.  A stream must stay alive until its work is done. */
 int  s2sr_forward_batch_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int32_t th, int32_t tw,
                                void* d_out, void* stream);
 /* unquantised net output for parity tests: x [N,3,H,W] fp32 in [0,1] -> y [N,3,4H,4W] fp32 (scale 2: even H, W -> [N,3,2H,2W]).
@@ -768,6 +778,37 @@ int  s2sr_debug_poison(int32_t pattern);
 int32_t s2sr_debug_poison_pattern(void);      /* the pattern in force (0: off), for callers that switch it and put it back */
 int  s2sr_debug_poison_scratch(s2sr_handle* h, int64_t* slots, int64_t* bytes);
 int  s2sr_debug_scratch_peek(s2sr_handle* h, int32_t slot, int64_t offset, int64_t n, uint8_t* out);
+
+/* test hooks: stalled streams (csrc/stall.hip, csrc/engine_internal.h "ordering events").  The red zones catch a store outside a
+ * buffer, poison a load of bytes nobody wrote; this catches a CONSUMER THAT DOES NOT WAIT for its producer on another stream -- a
+ * missing or mis-indexed event wait between the compute stream (the handle's, or the one a *_dev door was given) and the handle's
+ * copy stream, which changes no byte as long as the producer happens to be done in time.  A stall is a one-wave kernel that reads
+ * the constant-rate counter until the time has passed; it touches no memory and ends after a fixed number of iterations whatever
+ * the counter does.  Process-wide; off by default, and then the library enqueues nothing it would not enqueue without these entries.
+ *
+ * s2sr_debug_delay: mode bit 1 stalls the compute side, bit 2 the copy side, for `usec` microseconds (1 .. S2SR_DEBUG_STALL_MAX_USEC)
+ *   at the head of every stream segment: at the entry of every door on each stream it uses, behind every ordering event recorded
+ *   on that side's stream and behind every wait of that stream.  Never on a stream that is capturing (no captured region holds an
+ *   ordering event, and a door's entry stall precedes its capture).  Mode 0 (usec 0) turns it off.  S2SR_E_INVALID otherwise.
+ * s2sr_debug_delay_drop: the negative control.  While the mode is on, the stream-waits of ordering site `site` are skipped (-1:
+ *   none).  Only the S2SR_SITE_* below are accepted: the waits behind which the copy stream copies finished pixels to the host and
+ *   does nothing else, so a dropped wait yields early pixels and cannot send a load or a store anywhere (engine_internal.h says
+ *   why, site by site).  S2SR_E_INVALID for every other site.
+ * s2sr_debug_stall: one stall of `usec` on the handle's stream (which 0), its copy stream (1) or `stream` (2), in either mode.
+ * s2sr_debug_stream_touch: 64 bytes of the handle's trash page set to zero on that stream (which as above); wait != 0: returns
+ *   when that stream is idle.  With s2sr_debug_stall on another stream it shows whether two streams run side by side. */
+#define S2SR_DEBUG_STALL_MAX_USEC 20000
+#define S2SR_SITE_BATCH_GROUP_D2H 0     /* s2sr_forward_batch_u8: a group's tiles leave under the next group's forward */
+#define S2SR_SITE_CHUNK_BAND_D2H 2      /* the whole-image doors: a band leaves under the next chunk */
+#define S2SR_SITE_DISPLAY_BAND_D2H 6    /* s2sr_display_apply_u16: a band leaves under the next band's kernel */
+#define S2SR_SITE_COPY_TO_HOST 7        /* s2sr_copy_to_host: the copy stream behind the caller's stream */
+int  s2sr_debug_delay(int32_t mode, int32_t usec);
+int32_t s2sr_debug_delay_mode(void);          /* the mode in force (0: off), for callers that switch it and put it back */
+int32_t s2sr_debug_delay_usec(void);
+int  s2sr_debug_delay_drop(int32_t site);
+int32_t s2sr_debug_delay_dropped(void);       /* the site being dropped, -1: none */
+int  s2sr_debug_stall(s2sr_handle* h, int32_t which, void* stream, int32_t usec);
+int  s2sr_debug_stream_touch(s2sr_handle* h, int32_t which, void* stream, int32_t wait);
 
 #ifdef __cplusplus
 }

@@ -1005,6 +1005,7 @@ void s2sr_destroy(s2sr_handle* h) {
         if (m.d) dev_free(m.d);
     if (h->host_arena) host_free(h->host_arena);
     if (h->host_copy_ev) hipEventDestroy(h->host_copy_ev);
+    if (h->order_ev) hipEventDestroy(h->order_ev);
     if (h->copy_stream) hipStreamDestroy(h->copy_stream);
     if (h->stream) hipStreamDestroy(h->stream);
     delete h;
@@ -1212,7 +1213,8 @@ int s2sr_forward_batch_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t B, in
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
-    return forward_dev(h, st, TileIn::u8(d_tiles), B, th, tw, TileOut{(uint8_t*)d_out});
+    DOOR_ENTER(h, st);
+    return door_leave(h, st, forward_dev(h, st, TileIn::u8(d_tiles), B, th, tw, TileOut{(uint8_t*)d_out}));
 }
 
 // A PART of a larger job of `job_windows` equal windows (a chunk of an AOI's windows on one rank, s2sr/dist.py): the window
@@ -1223,7 +1225,9 @@ int s2sr_forward_part_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const Mosaic mo = pick_mosaic(h, job_windows, th, tw);
-    return forward_dev(h, (hipStream_t)stream, TileIn::u8(d_tiles), B, th, tw, TileOut{(uint8_t*)d_out}, mo.on() ? &mo : nullptr);
+    hipStream_t st = (hipStream_t)stream;
+    DOOR_ENTER(h, st);
+    return door_leave(h, st, forward_dev(h, st, TileIn::u8(d_tiles), B, th, tw, TileOut{(uint8_t*)d_out}, mo.on() ? &mo : nullptr));
 }
 
 int s2sr_host_alloc(size_t bytes, void** out) {
@@ -1250,6 +1254,7 @@ static int forward_batch_u8_once(s2sr_handle* h, const uint8_t* tiles, int32_t B
     if (!h || !tiles || !out) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     const int S = h->cfg.scale;
     const size_t ib = (size_t)B * th * tw * 3, ob = ib * S * S;
     int rc = ensure_scratch(h, 0, ib);
@@ -1270,11 +1275,11 @@ static int forward_batch_u8_once(s2sr_handle* h, const uint8_t* tiles, int32_t B
         rc = forward_dev(h, h->stream, TileIn::u8((const uint8_t*)h->d_scratch[0] + g0 * tin), n, th, tw,
                          TileOut{(uint8_t*)h->d_scratch[1] + g0 * tout}, mo.on() ? &mo : nullptr);
         if (rc) return rc;
-        HIPCHK(h, hipEventRecord(h->group_done[g], h->stream));
+        HIPCHK(h, ev_record(h, h->group_done[g], h->stream, SITE_BATCH_GROUP_D2H));
     }
     for (int g = 0; g < ngroups; ++g) {
         const int g0 = g * G, n = (B - g0 < G) ? (B - g0) : G;
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[g], 0));
+        HIPCHK(h, ev_stream_wait(h, h->copy_stream, h->group_done[g], SITE_BATCH_GROUP_D2H));
         if ((rc = d2h_staged(h, out + g0 * tout, (const uint8_t*)h->d_scratch[1] + g0 * tout, n * tout, g + 1 == ngroups))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
@@ -1305,9 +1310,11 @@ int s2sr_forward_batch_u16_dev(s2sr_handle* h, const void* d_tiles, int32_t B, i
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     // the fp32 tiles between the net and the quantiser live in the handle's scratch (slot 1); work already queued on the caller's
-    // stream that reads an earlier call's tiles is ordered before this call's on the same stream
+    // stream that reads an earlier call's tiles is ordered before this call's on the same stream, work on another stream by door_enter
+    hipStream_t st = (hipStream_t)stream;
+    DOOR_ENTER(h, st);
     if ((rc = ensure_scratch(h, 1, (size_t)B * 3 * 16 * th * tw * sizeof(float)))) return rc;
-    return forward_u16_locked(h, (hipStream_t)stream, (const uint16_t*)d_tiles, B, th, tw, lo, hi, (uint16_t*)d_out_u16, (float*)h->d_scratch[1]);
+    return door_leave(h, st, forward_u16_locked(h, st, (const uint16_t*)d_tiles, B, th, tw, lo, hi, (uint16_t*)d_out_u16, (float*)h->d_scratch[1]));
 }
 
 static int forward_batch_u16_once(s2sr_handle* h, const uint16_t* tiles, int32_t B, int32_t th, int32_t tw, int32_t lo, int32_t hi,
@@ -1320,6 +1327,7 @@ static int forward_batch_u16_once(s2sr_handle* h, const uint16_t* tiles, int32_t
     int rc = check_u16(h, lo, hi);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     const size_t npx = (size_t)B * th * tw * 3, ib = npx * 2, fb = npx * 16 * sizeof(float), qb = npx * 16 * 2;
     if ((rc = ensure_scratch(h, 0, ib))) return rc;
     if ((rc = ensure_scratch(h, 1, fb))) return rc;
@@ -1328,8 +1336,8 @@ static int forward_batch_u16_once(s2sr_handle* h, const uint16_t* tiles, int32_t
     if ((rc = forward_u16_locked(h, h->stream, (const uint16_t*)h->d_scratch[0], B, th, tw, lo, hi, out_u16 ? (uint16_t*)h->d_scratch[2] : nullptr,
                                  (float*)h->d_scratch[1]))) return rc;
     if ((rc = ensure_group_events(h, 1))) return rc;
-    HIPCHK(h, hipEventRecord(h->group_done[0], h->stream));
-    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[0], 0));
+    HIPCHK(h, ev_record(h, h->group_done[0], h->stream, SITE_BATCH_U16_D2H));
+    HIPCHK(h, ev_stream_wait(h, h->copy_stream, h->group_done[0], SITE_BATCH_U16_D2H));
     if (out_u16 && (rc = d2h_staged(h, (uint8_t*)out_u16, (const uint8_t*)h->d_scratch[2], qb, true))) return rc;
     if (out_f32 && (rc = d2h_staged(h, (uint8_t*)out_f32, (const uint8_t*)h->d_scratch[1], fb, true))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
@@ -1346,6 +1354,7 @@ static int forward_f32_once(s2sr_handle* h, const float* x, int32_t N, int32_t H
     if (!h || !x || !y) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     const size_t ib = (size_t)N * 3 * H * W * 4, ob = ib * h->cfg.scale * h->cfg.scale;
     int rc = ensure_scratch(h, 0, ib);
     if (rc) return rc;
@@ -1417,6 +1426,7 @@ int s2sr_calibrate_fp8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int32_t 
     std::lock_guard<std::mutex> lk(h->mu);
     if (h->cfg.precision != S2SR_PREC_FP8) return fail(h, S2SR_E_INVALID, "s2sr_calibrate_fp8 needs a handle created with S2SR_PREC_FP8");
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     const size_t ib = (size_t)B * th * tw * 3, ob = ib * h->cfg.scale * h->cfg.scale;
     int rc = ensure_scratch(h, 0, ib);
     if (rc) return rc;

@@ -51,12 +51,12 @@ int d2h_staged(s2sr_handle* h, uint8_t* dst, const uint8_t* src, size_t bytes, b
     for (size_t k = 0; k < nsl + 2; ++k) {
         const int i = (int)(k & 1);
         if (k >= 2) {   // slice k-2 sits in buffer i
-            HIPCHK(h, hipEventSynchronize(h->stage_ev[i]));
+            HIPCHK(h, ev_host_wait(h, h->stage_ev[i], SITE_STAGE_SLICE));
             memcpy(dst + (k - 2) * kStageBytes, h->stage_buf[i], len(k - 2));
         }
         if (k < nsl) {
             HIPCHK(h, hipMemcpyAsync(h->stage_buf[i], src + k * kStageBytes, len(k), hipMemcpyDeviceToHost, h->copy_stream));
-            HIPCHK(h, hipEventRecord(h->stage_ev[i], h->copy_stream));
+            HIPCHK(h, ev_record(h, h->stage_ev[i], h->copy_stream, SITE_STAGE_SLICE));
         }
     }
     return S2SR_OK;
@@ -236,15 +236,15 @@ static int run_chunks(s2sr_handle* h, hipStream_t st, int nx, const std::vector<
         const int r0 = chunk_r0[c], r1 = chunk_r0[c + 1], pye = band_end[c], ye = out_end[c];
         if ((rc = forward(r0 * nx, (r1 - r0) * nx))) return rc;
         if ((pye > pyb || ye > yb) && (rc = finish(r0 * nx, pyb, pye, yb, ye))) return rc;
-        HIPCHK(h, hipEventRecord(h->group_done[c], st));
+        HIPCHK(h, ev_record(h, h->group_done[c], st, SITE_CHUNK_BAND_D2H));
         if (copy && c > 0 && prev_ye > prev_yb) {
-            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[c - 1], 0));
+            HIPCHK(h, ev_stream_wait(h, h->copy_stream, h->group_done[c - 1], SITE_CHUNK_BAND_D2H));
             if ((rc = d2h_staged(h, host + (size_t)prev_yb * row_b, dev + (size_t)prev_yb * row_b, (size_t)(prev_ye - prev_yb) * row_b, false))) return rc;
         }
         prev_yb = yb; prev_ye = ye; yb = ye; pyb = pye;
     }
     if (copy && prev_ye > prev_yb) {
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
+        HIPCHK(h, ev_stream_wait(h, h->copy_stream, h->group_done[nchunks - 1], SITE_CHUNK_BAND_D2H));
         if ((rc = d2h_staged(h, host + (size_t)prev_yb * row_b, dev + (size_t)prev_yb * row_b, (size_t)(prev_ye - prev_yb) * row_b, true))) return rc;
     }
     return S2SR_OK;
@@ -300,7 +300,9 @@ int s2sr_postprocess_batch_u8_dev(s2sr_handle* h, const void* d_rgb, int32_t B, 
     if (!h || !d_rgb || !d_out || !prm || B <= 0 || H <= 0 || W <= 0) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    return postprocess_dev_locked(h, d_rgb, B, H, W, prm, d_out, (hipStream_t)stream);   // NULL = the default stream, as everywhere in HIP
+    hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
+    DOOR_ENTER(h, st);
+    return door_leave(h, st, postprocess_dev_locked(h, d_rgb, B, H, W, prm, d_out, st));
 }
 
 // ---- the post-process over one device image in row bands (see postprocess.hip launch_pp_band_*) -------------------------------
@@ -361,28 +363,32 @@ int s2sr_pp_band_begin_dev(s2sr_handle* h, int32_t H, int32_t W, const s2sr_pp_p
     if (!h || !prm || H <= 0 || W <= 0) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    return pp_band_begin_locked(h, H, W, prm, order, (hipStream_t)stream);
+    DOOR_ENTER(h, (hipStream_t)stream);
+    return door_leave(h, (hipStream_t)stream, pp_band_begin_locked(h, H, W, prm, order, (hipStream_t)stream));
 }
 
 int s2sr_pp_band_hist_dev(s2sr_handle* h, const void* d_img, int32_t y0, int32_t y1, void* stream) {
     if (!h || !d_img) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    return pp_band_hist_locked(h, d_img, y0, y1, (hipStream_t)stream);
+    DOOR_ENTER(h, (hipStream_t)stream);
+    return door_leave(h, (hipStream_t)stream, pp_band_hist_locked(h, d_img, y0, y1, (hipStream_t)stream));
 }
 
 int s2sr_pp_band_lut_dev(s2sr_handle* h, void* stream) {
     if (!h) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    return pp_band_lut_locked(h, (hipStream_t)stream);
+    DOOR_ENTER(h, (hipStream_t)stream);
+    return door_leave(h, (hipStream_t)stream, pp_band_lut_locked(h, (hipStream_t)stream));
 }
 
 int s2sr_pp_band_rows_dev(s2sr_handle* h, const void* d_img, int32_t y0, int32_t y1, void* d_out, void* stream) {
     if (!h || !d_img || !d_out) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    return pp_band_rows_locked(h, d_img, y0, y1, d_out, (hipStream_t)stream);
+    DOOR_ENTER(h, (hipStream_t)stream);
+    return door_leave(h, (hipStream_t)stream, pp_band_rows_locked(h, d_img, y0, y1, d_out, (hipStream_t)stream));
 }
 
 // Host image in, host image out.  ONE lock scope from the upload to the download: the staging buffers
@@ -393,6 +399,7 @@ int s2sr_postprocess_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W
     const size_t nb = (size_t)H * W * 3;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     int rc = ensure_scratch(h, 0, nb);
     if (rc) return rc;
     if ((rc = ensure_scratch(h, 1, nb))) return rc;
@@ -530,15 +537,15 @@ static int pp_finish_bands(s2sr_handle* h, hipStream_t st, uint8_t* d_img_out, u
         const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
         if ((rc = pp_band_rows_locked(h, d_img_out, y0, y1, d_img_out, st))) return rc;
         if ((rc = mask_rows(h, st, mk, d_img_out, y0, y1))) return rc;
-        HIPCHK(h, hipEventRecord(h->group_done[nchunks + b], st));
+        HIPCHK(h, ev_record(h, h->group_done[nchunks + b], st, SITE_PP_BAND_D2H));
     }
     if (timing) {
-        HIPCHK(h, hipEventSynchronize(h->group_done[nchunks - 1]));
+        HIPCHK(h, ev_host_wait(h, h->group_done[nchunks - 1], SITE_CHUNK_BAND_D2H));
         t_compute = now();
     }
     for (int b = 0; b < nfin; ++b) {
         const int y0 = b * fin_rows, y1 = y0 + fin_rows < OH ? y0 + fin_rows : OH;
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks + b], 0));
+        HIPCHK(h, ev_stream_wait(h, h->copy_stream, h->group_done[nchunks + b], SITE_PP_BAND_D2H));
         if ((rc = d2h_staged(h, out_u8 + (size_t)y0 * row_b, d_img_out + (size_t)y0 * row_b, (size_t)(y1 - y0) * row_b,
                              false))) return rc;
         if (timing && b == 0) t_first = now();
@@ -782,19 +789,19 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
         if ((rc = ensure_scratch(h, 4, opx))) return rc;
         if ((rc = postprocess_dev_locked(h, d_q, 1, OH, OW, c.prm, h->d_scratch[4], st))) return rc;
         if ((rc = mask_rows(h, st, mk, h->d_scratch[4], 0, OH))) return rc;
-        HIPCHK(h, hipEventRecord(tail_done, st));
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, tail_done, 0));
+        HIPCHK(h, ev_record(h, tail_done, st, SITE_TAIL_D2H));
+        HIPCHK(h, ev_stream_wait(h, h->copy_stream, tail_done, SITE_TAIL_D2H));
         if ((rc = d2h_staged(h, c.out_u8, (const uint8_t*)h->d_scratch[4], opx, true))) return rc;
     }
     if (c.out_f32) {
         if (p.blend) HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, 0, oth, otw, d_tab[1], d_tab[2], OH, OW, d_f, st));
         else HIPCHK(h, launch_stitch((const float*)d_buf, nx, oth, otw, d_tab[1], d_tab[2], OH, OW, d_f, st));
-        HIPCHK(h, hipEventRecord(tail_done, st));
+        HIPCHK(h, ev_record(h, tail_done, st, SITE_TAIL_D2H));
         if (out_q) {
-            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->group_done[nchunks - 1], 0));
+            HIPCHK(h, ev_stream_wait(h, h->copy_stream, h->group_done[nchunks - 1], SITE_CHUNK_BAND_D2H));
             if ((rc = d2h_staged(h, (uint8_t*)out_q, d_q, OH * row_b, true))) return rc;
         }
-        HIPCHK(h, hipStreamWaitEvent(h->copy_stream, tail_done, 0));
+        HIPCHK(h, ev_stream_wait(h, h->copy_stream, tail_done, SITE_TAIL_D2H));
         if ((rc = d2h_staged(h, (uint8_t*)c.out_f32, (const uint8_t*)d_f, opx * 4, true))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
@@ -814,6 +821,7 @@ static int enhance_call(s2sr_handle* h, const EnhanceCall& c) {
     std::lock_guard<std::mutex> lk(h->mu);
     if (int rc = check_call(h, c)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     return enhance_locked(h, c);
 }
 
@@ -944,6 +952,7 @@ static int consistency_impl(s2sr_handle* h, const void* sr, const void* img, int
     const int esz = u16 ? 2 : 1, OH = H * S;
     const size_t row_b = (size_t)W * S * 3 * esz, ipx = (size_t)H * W * 3;
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
     int rc = ensure_scratch(h, 0, ipx * esz);
     if (rc) return rc;
@@ -989,6 +998,7 @@ static int fill_nodata_impl(s2sr_handle* h, const void* img, const uint8_t* vali
     if (const char* why = mask_error(valid, radius, 0, u16)) return fail(h, S2SR_E_INVALID, why);
     const size_t nb = (size_t)H * W * 3 * (u16 ? 2 : 1);
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     int rc = ensure_scratch(h, 0, nb);
     if (rc) return rc;
     if ((rc = ensure_scratch(h, 6, (size_t)H * W))) return rc;
@@ -1024,6 +1034,7 @@ int s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
+    DOOR_ENTER(h, st);
     int PH, PW;
     int rc = plan_dims(h, H, W, tile, &PH, &PW);
     if (rc) return rc;
@@ -1038,8 +1049,10 @@ int s2sr_cut_windows_u8_dev(s2sr_handle* h, const void* d_img, int32_t H, int32_
     }
     int32_t* d_tab[3];
     if ((rc = upload_tables(h, st, rects, {}, {}, d_tab))) return rc;
-    HIPCHK(h, launch_gather_windows((const uint8_t*)d_img, H, W, d_tab[0], count, wh, ww, PH != H || PW != W, (uint8_t*)d_tiles, st));
-    return S2SR_OK;
+    const hipError_t eg = launch_gather_windows((const uint8_t*)d_img, H, W, d_tab[0], count, wh, ww, PH != H || PW != W, (uint8_t*)d_tiles, st);
+    rc = door_leave(h, st, S2SR_OK);
+    if (eg != hipSuccess) return fail(h, S2SR_E_HIP, std::string("launch_gather_windows failed: ") + hipGetErrorString(eg));
+    return rc;
 }
 
 int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t oy0, int32_t oy1,
@@ -1049,6 +1062,7 @@ int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int3
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;   // NULL = the default stream, as everywhere in HIP
+    DOOR_ENTER(h, st);
     const int S = h->cfg.scale;
     int PH, PW;
     int rc = plan_dims(h, H, W, tile, &PH, &PW);
@@ -1093,9 +1107,11 @@ int s2sr_stitch_rows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int3
     ms->last_use = ++h->stitch_clock;
     const int32_t* d_rm = ms->d;
     const int32_t* d_cm = d_rm + nrm;
-    HIPCHK(h, launch_stitch((const uint8_t*)d_tiles, nx, wh * S, ww * S, d_rm + 2 * (size_t)oy0, d_cm, oy1 - oy0, S * W,
-                               (uint8_t*)d_out + (size_t)oy0 * S * W * 3, st));
-    return S2SR_OK;
+    const hipError_t es = launch_stitch((const uint8_t*)d_tiles, nx, wh * S, ww * S, d_rm + 2 * (size_t)oy0, d_cm, oy1 - oy0, S * W,
+                                        (uint8_t*)d_out + (size_t)oy0 * S * W * 3, st);
+    rc = door_leave(h, st, S2SR_OK);
+    if (es != hipSuccess) return fail(h, S2SR_E_HIP, std::string("launch_stitch failed: ") + hipGetErrorString(es));
+    return rc;
 }
 
 int s2sr_stitch_windows_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t H, int32_t W, int32_t tile, int32_t pad,
@@ -1113,9 +1129,10 @@ int s2sr_copy_to_host(s2sr_handle* h, void* dst, const void* d_src, size_t bytes
     if (bytes == 0) return S2SR_OK;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, (hipStream_t)stream);
     if (!h->host_copy_ev) HIPCHK(h, hipEventCreateWithFlags(&h->host_copy_ev, hipEventDisableTiming));
-    HIPCHK(h, hipEventRecord(h->host_copy_ev, (hipStream_t)stream));
-    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, h->host_copy_ev, 0));
+    HIPCHK(h, ev_record(h, h->host_copy_ev, (hipStream_t)stream, SITE_COPY_TO_HOST));
+    HIPCHK(h, ev_stream_wait(h, h->copy_stream, h->host_copy_ev, SITE_COPY_TO_HOST));
     return d2h_staged(h, (uint8_t*)dst, (const uint8_t*)d_src, bytes, false);
 }
 

@@ -55,7 +55,7 @@ int plan_source(s2sr_handle* h, const char* who, const uint16_t* img, int H, int
 int upload_band(s2sr_handle* h, const uint16_t* img, const Source& s, int H, int i, hipEvent_t ev) {
     const size_t y0 = (size_t)i * s.rows, y1 = y0 + s.rows < (size_t)H ? y0 + s.rows : H;
     HIPCHK(h, hipMemcpyAsync((uint16_t*)h->d_scratch[0] + y0 * s.row_s, img + y0 * s.row_s, (y1 - y0) * s.row_s * 2, hipMemcpyHostToDevice, h->copy_stream));
-    HIPCHK(h, hipEventRecord(ev, h->copy_stream));
+    HIPCHK(h, ev_record(h, ev, h->copy_stream, SITE_DISPLAY_UPLOAD));
     return S2SR_OK;
 }
 
@@ -68,6 +68,7 @@ int display_hist_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int nod
     int rc = plan_source(h, "s2sr_display_hist_u16", img, H, W, band_rows, s);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
     if (img && (rc = ensure_scratch(h, 0, (s.total * 2 + 255) & ~(size_t)255))) return rc;
     if ((rc = ensure_scratch(h, 3, kHistBytes + kLutBytes))) return rc;
@@ -79,7 +80,7 @@ int display_hist_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int nod
     if (img && (rc = upload_band(h, img, s, H, 0, h->group_done[0]))) return rc;
     for (int i = 0; i < s.nbands; ++i) {
         const size_t y0 = (size_t)i * s.rows, y1 = y0 + s.rows < (size_t)H ? y0 + s.rows : H;
-        if (img) HIPCHK(h, hipStreamWaitEvent(st, h->group_done[i & 1], 0));
+        if (img) HIPCHK(h, ev_stream_wait(h, st, h->group_done[i & 1], SITE_DISPLAY_UPLOAD));
         {
             Scope sc(h, st, F_DHIST, 0.0, (double)(y1 - y0) * s.row_s * 2.0);
             HIPCHK(h, launch_display_hist(d_img, y0 * s.row_s, y1 * s.row_s, nodata, d_hist, st));
@@ -101,6 +102,7 @@ int display_apply_impl(s2sr_handle* h, const uint16_t* img, int H, int W, const 
     int rc = plan_source(h, "s2sr_display_apply_u16", img, H, W, band_rows, s);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
     const int out_slot = s.slot == 1 ? 0 : 1;                // the 8-bit image: the other of 0 / 1, as the pyramid calls do
     if (img && (rc = ensure_scratch(h, 0, (s.total * 2 + 255) & ~(size_t)255))) return rc;
@@ -118,20 +120,20 @@ int display_apply_impl(s2sr_handle* h, const uint16_t* img, int H, int W, const 
     size_t pb0 = 0, pb1 = 0;                                 // the band before, in bytes of the output
     for (int i = 0; i < s.nbands; ++i) {
         const size_t y0 = (size_t)i * s.rows, y1 = y0 + s.rows < (size_t)H ? y0 + s.rows : H;
-        if (img) HIPCHK(h, hipStreamWaitEvent(st, up[i & 1], 0));
+        if (img) HIPCHK(h, ev_stream_wait(h, st, up[i & 1], SITE_DISPLAY_UPLOAD));
         {
             Scope sc(h, st, F_DAPPLY, 0.0, (double)(y1 - y0) * s.row_s * 3.0);
             HIPCHK(h, launch_display_apply(d_img, y0 * s.row_s, y1 * s.row_s, d_lut, d_out, st));
         }
-        HIPCHK(h, hipEventRecord(done[i & 1], st));
+        HIPCHK(h, ev_record(h, done[i & 1], st, SITE_DISPLAY_BAND_D2H));
         if (img && i + 1 < s.nbands && (rc = upload_band(h, img, s, H, i + 1, up[(i + 1) & 1]))) return rc;
         if (i > 0) {
-            HIPCHK(h, hipStreamWaitEvent(h->copy_stream, done[(i - 1) & 1], 0));
+            HIPCHK(h, ev_stream_wait(h, h->copy_stream, done[(i - 1) & 1], SITE_DISPLAY_BAND_D2H));
             if ((rc = d2h_staged(h, out + pb0, d_out + pb0, pb1 - pb0, false))) return rc;
         }
         pb0 = y0 * s.row_s; pb1 = y1 * s.row_s;
     }
-    HIPCHK(h, hipStreamWaitEvent(h->copy_stream, done[(s.nbands - 1) & 1], 0));
+    HIPCHK(h, ev_stream_wait(h, h->copy_stream, done[(s.nbands - 1) & 1], SITE_DISPLAY_BAND_D2H));
     if ((rc = d2h_staged(h, out + pb0, d_out + pb0, pb1 - pb0, true))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     HIPCHK(h, hipStreamSynchronize(st));

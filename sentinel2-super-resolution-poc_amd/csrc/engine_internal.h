@@ -245,6 +245,12 @@ struct s2sr_handle {
     StitchMaps stitch_sets[4];
     uint64_t stitch_clock = 0;
     hipEvent_t host_copy_ev = nullptr;          // s2sr_copy_to_host: orders the copy stream behind the caller's stream
+    // The last call that returned with work still queued (a *_dev door): the event behind its last enqueue and the stream it went to.
+    // A later call on ANOTHER stream makes that stream wait for it first (door_enter): the workspace and the scratch slots are the
+    // handle's, and the mutex only orders the enqueues.  Never cleared: a wait for an event that has fired costs nothing on the device.
+    hipEvent_t order_ev = nullptr;
+    hipStream_t order_stream = nullptr;
+    bool order_pending = false;
     void* host_arena = nullptr;                 // page-locked host block of the tile-PNG stage (stats back, plan up): grown on demand, kept
     size_t host_arena_bytes = 0;
     // the banded post-process in progress on this handle (s2sr_pp_band_*_dev, or a whole-image job: enhance_locked): geometry, channel order, how far the
@@ -303,6 +309,63 @@ int decode_e4m3_planes(s2sr_handle* h, float* dst, const char* src, uint64_t img
 
 hipEvent_t get_event(s2sr_handle* h);
 int ensure_group_events(s2sr_handle* h, int n);
+
+// ---- ordering events (stall.hip) ---------------------------------------------------------------------------------
+// Every event that ORDERS two streams, or a stream and the host, goes through ev_record / ev_stream_wait / ev_host_wait with the
+// Site that names its producer / consumer pair; hipEventRecord, hipStreamWaitEvent and hipEventSynchronize appear nowhere else in
+// csrc/ except at the timing events (Scope, span_begin / span_end, the e0 / e1 pairs of engine_debug.hip), which order nothing
+// (tests/test_stall_cpu.py scans for that).  With the stall mode off a wrapper is the call it wraps plus one relaxed atomic load.
+enum Site {
+    SITE_BATCH_GROUP_D2H,       // forward_batch_u8_once: group g's tiles leave on the copy stream under group g + 1's forward
+    SITE_BATCH_U16_D2H,         // forward_batch_u16_once: the quantised and / or fp32 tiles leave behind the quantiser
+    SITE_CHUNK_BAND_D2H,        // run_chunks / enhance_locked: band c - 1 leaves under chunk c; the whole quantised image next to an fp32 one
+    SITE_PP_BAND_D2H,           // pp_finish_bands: a finished band of a banded post-process leaves
+    SITE_TAIL_D2H,              // enhance_locked: the unbanded post-process's image, the fp32 image
+    SITE_DISPLAY_UPLOAD,        // display_hist_impl / display_apply_impl: band i + 1 uploads on the copy stream under band i's kernel
+    SITE_DISPLAY_BAND_D2H,      // display_apply_impl: band i - 1 leaves under band i's kernel (two ping-pong events)
+    SITE_COPY_TO_HOST,          // s2sr_copy_to_host: the copy stream behind the caller's stream
+    SITE_STAGE_SLICE,           // d2h_staged: a page-locked slice is full (host wait)
+    SITE_PNG_STATS,             // tiles_write_png_locked: a group's statistics are on the host (host wait)
+    SITE_PNG_EMIT,              // ... its streams are emitted: the copy stream may read them (host wait)
+    SITE_PNG_BATCH,             // ... a batch of streams sits in its staging buffer (host wait)
+    SITE_HANDLE_ORDER,          // door_enter / door_leave: a call on one stream behind the unfinished call on another
+    SITE_COUNT
+};
+// The negative control (s2sr_debug_delay_drop) may skip the stream-waits of these sites and no others.  At each of them the waiting
+// stream is the copy stream and what it runs next is a device-to-host hipMemcpyAsync of finished pixel bytes, with source, size and
+// destination computed on the host before the wait: a wait that is missing lets the copy read pixels too early and nothing else.
+//   SITE_BATCH_GROUP_D2H   d2h_staged of scratch 1 [g0 tout, n tout): u8 tiles; no kernel runs on the copy stream
+//   SITE_CHUNK_BAND_D2H    d2h_staged of rows [prev_yb, prev_ye) of the quantised image (scratch 1 / 2 / 4): pixels; as above
+//   SITE_DISPLAY_BAND_D2H  d2h_staged of bytes [pb0, pb1) of the 8-bit image (scratch 0 / 1); the NEXT upload on the copy stream
+//                          writes the uint16 image in the other slot, which this wait never guarded
+//   SITE_COPY_TO_HOST      d2h_staged of the caller's [d_src, d_src + bytes)
+// Never droppable: SITE_DISPLAY_UPLOAD (a kernel consumes it), SITE_HANDLE_ORDER (tables, plans and LUTs of the call before live in
+// the scratch it guards), the host waits (the host reads statistics, offsets and plans behind them), and the rest, which no control needs.
+inline constexpr int kDroppableSites[] = {SITE_BATCH_GROUP_D2H, SITE_CHUNK_BAND_D2H, SITE_DISPLAY_BAND_D2H, SITE_COPY_TO_HOST};
+
+extern std::atomic<int> g_delay_mode;      // s2sr_debug_delay: bit 1 the compute side, bit 2 the copy side; 0 off
+extern std::atomic<int> g_delay_drop;      // s2sr_debug_delay_drop: the Site whose stream-waits are skipped, -1 none
+hipError_t delay_stall(s2sr_handle* h, hipStream_t st);   // one stall on st when its side's bit is set and st is not capturing
+inline hipError_t ev_record(s2sr_handle* h, hipEvent_t ev, hipStream_t st, Site) {
+    const hipError_t e = hipEventRecord(ev, st);
+    return e == hipSuccess && g_delay_mode.load(std::memory_order_relaxed) ? delay_stall(h, st) : e;
+}
+inline hipError_t ev_stream_wait(s2sr_handle* h, hipStream_t st, hipEvent_t ev, Site site) {
+    const bool on = g_delay_mode.load(std::memory_order_relaxed) != 0;
+    if (on && g_delay_drop.load(std::memory_order_relaxed) == (int)site) return delay_stall(h, st);
+    const hipError_t e = hipStreamWaitEvent(st, ev, 0);
+    return e == hipSuccess && on ? delay_stall(h, st) : e;
+}
+inline hipError_t ev_host_wait(s2sr_handle*, hipEvent_t ev, Site) { return hipEventSynchronize(ev); }
+// The first and last line of a door behind hipSetDevice.  door_enter: st (and, for a door on the handle's own stream, the copy
+// stream) waits for the unfinished call on another stream, then the mode's entry stalls.  door_leave: a *_dev door returns with
+// work queued on the caller's stream: the event behind it.  rc is passed through.
+int door_enter(s2sr_handle* h, hipStream_t st);
+int door_leave(s2sr_handle* h, hipStream_t st, int rc);
+#define DOOR_ENTER(h, st)                                    \
+    do {                                                     \
+        if (int rc__ = door_enter((h), (st))) return rc__;   \
+    } while (0)
 
 struct Scope {   // brackets one launch with events when profiling is on
     s2sr_handle* h;

@@ -28,6 +28,7 @@ int s2sr_warp_bilinear_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t
         return fail(h, S2SR_E_INVALID, "warp node grid does not cover the output raster");
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
     const size_t ib = (size_t)H * W * 3, gb = (size_t)gh * gw * 8, ob = (size_t)OH * OW * 4;
     int rc;
@@ -56,6 +57,7 @@ int s2sr_tiles_base_u8(s2sr_handle* h, const uint8_t* rgba, int32_t H, int32_t W
         if (row_lo[i] < 0 || row_hi[i] >= H) return fail(h, S2SR_E_INVALID, "row footprint table leaves the raster");
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
     const size_t ib = (size_t)H * W * 4, ob = (size_t)nx * ny * 65536 * 4, cb = (size_t)nx * 256 * 4, rb = (size_t)ny * 256 * 4;
     // rgba == NULL: the raster is the one the previous call on this handle -- s2sr_warp_bilinear_u8 -- produced, taken from its
@@ -93,6 +95,7 @@ int s2sr_tiles_overview_u8(s2sr_handle* h, const uint8_t* child, int32_t cnx, in
     if (!h || cnx <= 0 || cny <= 0 || pnx <= 0 || pny <= 0) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
     const size_t ib = (size_t)cnx * cny * 65536 * 4, ob = (size_t)pnx * pny * 65536 * 4;
     // child == NULL: the children are the level the previous pyramid call on this handle produced, still on the device (a
@@ -156,6 +159,7 @@ int s2sr_tiles_resample_u8(s2sr_handle* h, const uint8_t* src, int32_t src_kind,
         in_slot = level ? h->tiles_slot : h->warp_slot;
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
     const int out_slot = in_slot == 1 ? 0 : 1;
     const int nrows = r_hi - r_lo;                                  // the source rows some output row reads
@@ -193,6 +197,7 @@ int s2sr_tiles_resample_u8(s2sr_handle* h, const uint8_t* src, int32_t src_kind,
 // compressed streams cross PCIe.
 static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const char* const* paths, int32_t flags, int32_t* written) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
     if (h->tiles_slot < 0 || h->tiles_nx != nx || h->tiles_ny != ny)
         return fail(h, S2SR_E_INVALID, "the previous call on this handle did not leave a tile level of this size on the device");
     const int slot = h->tiles_slot;
@@ -265,7 +270,7 @@ static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const 
                                             G.d_stats + (size_t)G.n * 1024, row_threads, st));
         }
         HIPCHK(h, hipMemcpyAsync((void*)G.stats, G.d_stats, (size_t)G.n * tile_stats_b, hipMemcpyDeviceToHost, st));
-        HIPCHK(h, hipEventRecord(G.ev_stats, st));
+        HIPCHK(h, ev_record(h, G.ev_stats, st, SITE_PNG_STATS));
     }
     std::atomic<int> failed{0};
     if (written) for (int t = 0; t < n; ++t) written[t] = 0;
@@ -302,10 +307,10 @@ static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const 
             if (k < batches.size() && batches[k].w1 > batches[k].w0)
                 HIPCHK(h, hipMemcpyAsync(h->stage_buf[k & 1], d_out + batches[k].w0, (batches[k].w1 - batches[k].w0) * 4, hipMemcpyDeviceToHost,
                                          h->copy_stream));
-            if (k < batches.size()) HIPCHK(h, hipEventRecord(h->stage_ev[k & 1], h->copy_stream));
+            if (k < batches.size()) HIPCHK(h, ev_record(h, h->stage_ev[k & 1], h->copy_stream, SITE_PNG_BATCH));
             if (k > 0) {
                 const Batch& bt = batches[k - 1];
-                HIPCHK(h, hipEventSynchronize(h->stage_ev[(k - 1) & 1]));
+                HIPCHK(h, ev_host_wait(h, h->stage_ev[(k - 1) & 1], SITE_PNG_BATCH));
                 const uint32_t* words = (const uint32_t*)h->stage_buf[(k - 1) & 1];
                 if (!png_parallel_for(bt.t1 - bt.t0, [&](int i) {
                     const int t = bt.t0 + i;
@@ -342,7 +347,7 @@ static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const 
         if (g < ngroups) {
             Group& G = groups[g];
             double t0 = now();
-            HIPCHK(h, hipEventSynchronize(G.ev_stats));
+            HIPCHK(h, ev_host_wait(h, G.ev_stats, SITE_PNG_STATS));
             double t1 = now();
             t_wait += t1 - t0;
             G.out_words = png_plan_tiles(G.n, G.stats, G.stats + (size_t)G.n * 512, G.stats + (size_t)G.n * 1024, paths + G.a,
@@ -361,12 +366,12 @@ static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const 
                 HIPCHK(h, launch_png_tile_emit(d_tiles + (size_t)G.a * 262144, G.n, G.d_tables + tb_b + hdr_b, (const uint32_t*)G.d_tables,
                                                (const uint32_t*)(G.d_tables + tb_b), d_out, row_threads, st));
             }
-            HIPCHK(h, hipEventRecord(G.ev_emit, st));
+            HIPCHK(h, ev_record(h, G.ev_emit, st, SITE_PNG_EMIT));
         }
         if (g > 0) {
             Group& P = groups[g - 1];
             double t0 = now();
-            HIPCHK(h, hipEventSynchronize(P.ev_emit));           // the copy stream may read the group's streams
+            HIPCHK(h, ev_host_wait(h, P.ev_emit, SITE_PNG_EMIT));           // the copy stream may read the group's streams
             double t1 = now();
             t_wait += t1 - t0;
             if ((rc = write_group(P, (const uint32_t*)h->d_scratch[4 + ((g - 1) & 1)]))) return rc;

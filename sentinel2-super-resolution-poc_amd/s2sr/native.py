@@ -217,6 +217,13 @@ _PROTOS = {
     "s2sr_debug_poison_pattern": (C.c_int32, []),
     "s2sr_debug_poison_scratch": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "s2sr_debug_scratch_peek": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p]),
+    "s2sr_debug_delay": (C.c_int, [C.c_int32, C.c_int32]),
+    "s2sr_debug_delay_mode": (C.c_int32, []),
+    "s2sr_debug_delay_usec": (C.c_int32, []),
+    "s2sr_debug_delay_drop": (C.c_int, [C.c_int32]),
+    "s2sr_debug_delay_dropped": (C.c_int32, []),
+    "s2sr_debug_stall": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "s2sr_debug_stream_touch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -1310,6 +1317,50 @@ def _scratch_peek(self, slot: int, offset: int, n: int) -> np.ndarray:
 
 Engine.poison_scratch = _poison_scratch
 Engine.scratch_peek = _scratch_peek
+
+STALL_MAX_USEC = 20000                          # include/s2sr.h S2SR_DEBUG_STALL_MAX_USEC
+# the ordering sites whose waits s2sr_debug_delay_drop accepts (include/s2sr.h S2SR_SITE_*)
+SITE_BATCH_GROUP_D2H, SITE_CHUNK_BAND_D2H, SITE_DISPLAY_BAND_D2H, SITE_COPY_TO_HOST = 0, 2, 6, 7
+DROPPABLE_SITES = (SITE_BATCH_GROUP_D2H, SITE_CHUNK_BAND_D2H, SITE_DISPLAY_BAND_D2H, SITE_COPY_TO_HOST)
+
+
+def delay(mode: int, usec: int = 0):
+    """Stall the compute side (mode bit 1) and / or the copy side (bit 2) for `usec` microseconds at the head of every stream
+    segment (include/s2sr.h: s2sr_debug_delay); 0 turns the mode off.  Process-wide; a diagnostic."""
+    rc = load_library().s2sr_debug_delay(int(mode), int(usec))
+    if rc:
+        raise S2srError(f"s2sr_debug_delay({mode}, {usec}) failed ({_ERR.get(rc, rc)}): mode 0..3, 1..{STALL_MAX_USEC} microseconds")
+
+
+def delay_mode() -> tuple:
+    """(mode, microseconds) in force ((0, 0): off): what a caller that switches the mode puts back."""
+    lib = load_library()
+    return int(lib.s2sr_debug_delay_mode()), int(lib.s2sr_debug_delay_usec())
+
+
+def delay_drop(site: int):
+    """The negative control: while the mode is on, skip the stream-waits of one droppable ordering site (-1: none)."""
+    rc = load_library().s2sr_debug_delay_drop(int(site))
+    if rc:
+        raise S2srError(f"s2sr_debug_delay_drop({site}) failed ({_ERR.get(rc, rc)}): only a wait in front of a copy of finished pixels can be dropped")
+
+
+def delay_dropped() -> int:
+    return int(load_library().s2sr_debug_delay_dropped())
+
+
+def _stall(self, which: int, usec: int, stream: int = 0):
+    """One stall of `usec` microseconds on the engine's stream (which 0), its copy stream (1) or `stream` (2)."""
+    self._check(self._lib.s2sr_debug_stall(self._h, int(which), C.c_void_p(stream), int(usec)), "s2sr_debug_stall")
+
+
+def _stream_touch(self, which: int, stream: int = 0, wait: bool = True):
+    """A 64-byte memset on that stream (which as in stall); wait: returns when the stream is idle."""
+    self._check(self._lib.s2sr_debug_stream_touch(self._h, int(which), C.c_void_p(stream), int(bool(wait))), "s2sr_debug_stream_touch")
+
+
+Engine.stall = _stall
+Engine.stream_touch = _stream_touch
 
 
 def expected_blob_floats_cfg(num_block: int, scale: int = 4, arch: str = "rrdb") -> int:
