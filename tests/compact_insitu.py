@@ -284,3 +284,46 @@ def judge(geo, acts, p0, out_f32, out_u8, sd, B, th, tw, tiles=None, x=None, fre
             bad = out_u8 != want
             rep.fail("u8", f"{int(bad.sum())} bytes differ from trunc(clip(out_f32 * 255)) (first at {np.argwhere(bad)[0].tolist()})")
     return rep
+
+
+# ---- the shape classes tests/test_gpu_compact_insitu.py runs --------------------------------------------------------------------------
+# shapes: (entry, B, th, tw, job_windows, environment, all layers)
+SHAPES = {
+    "tiny_1x16x32": ("u8", 1, 16, 32, 0, {}, True),                 # one patch exactly
+    "tile_1x64x64": ("u8", 1, 64, 64, 0, {}, True),
+    "ragged_2x37x53": ("u8", 2, 37, 53, 0, {}, True),               # 1 x 2 mosaic, period 38 x 54: the multiply-high route of px_live
+    "mosaic_9x20x20": ("u8", 9, 20, 20, 0, {}, True),               # 3 x 3 mosaic, period 21: the modulo route
+    "dead_7of9x20x20": ("u8", 7, 20, 20, 9, {}, True),              # the job's 3 x 3 mosaic with two dead slots
+    "big_1x300x330": ("u8", 1, 300, 330, 0, {}, False),             # H % 16 and W % 32 nonzero, many patches, no mosaic
+    "full_3x256x256": ("u8", 3, 256, 256, 0, {}, False),            # whole tiles: no mosaic
+    "aoi_3x276x276": ("u8", 3, 276, 276, 0, {}, False),             # what enhance_u8 launches (tile 256, pad 10): 3 x 1 mosaic, multiply-high
+    "mosaic_16x24x40": ("u8", 16, 24, 40, 0, {}, False),            # 2 x 8 mosaic, period 25 x 41: modulo
+    "group_16x24x40": ("u8", 16, 24, 40, 0, {"S2SR_MOSAIC": "0"}, False),   # a full default group of 16 images in one launch
+    "one_1x1x1": ("u8", 1, 1, 1, 0, {}, True),
+    "row_1x1x9": ("u8", 1, 1, 9, 0, {}, True),
+    "col_1x7x1": ("u8", 1, 7, 1, 0, {}, True),
+    "f32_1x21x27": ("f32", 1, 21, 27, 0, {}, True),                 # the fp32 entry, input off the u8 grid (u8 / 255 + 1e-3)
+    "f32_2x37x53": ("f32", 2, 37, 53, 0, {}, True),                 # the fp32 entry never mosaics: two images
+    "f32u_2x37x53": ("f32u", 2, 37, 53, 0, {}, True),               # uniform random floats
+}
+# A judged layer must see a negative pre-activation in every channel (else its slopes went untested).  That is asserted where
+# the CPU emulation shows it holds (test_compact_insitu_cpu.test_shape_inputs_reach_every_channel runs the same inputs, the
+# large shapes on a corner).  A few pixels cannot drive 64 channels of 17 layers negative, so the degenerate sizes are judged
+# without it, and so is the batch of uniform floats (noise alone leaves channels of the first conv positive; the same shape is
+# guarded in f32_2x37x53).
+NO_NEGATIVE_GUARD = {"one_1x1x1", "row_1x1x9", "col_1x7x1", "f32u_2x37x53"}
+
+
+def shape_inputs(shape):
+    """-> (keyword arguments of debug_compact_taps, keyword arguments of the judge)"""
+    kind, B, th, tw, job = SHAPES[shape][:5]
+    seed = sum(map(ord, shape))
+    rng = np.random.default_rng(seed + 1)
+    u8 = structured_tiles(seed, B, th, tw)
+    if kind == "u8":
+        return dict(tiles=u8, job_windows=job), dict(tiles=u8)
+    if kind == "f32":
+        x = (u8.transpose(0, 3, 1, 2).astype(np.float32) / 255.0 + 1e-3).clip(0, 1).astype(np.float32)
+    else:
+        x = rng.random((B, 3, th, tw), dtype=np.float32)
+    return dict(x=x), dict(x=x)

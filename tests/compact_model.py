@@ -110,3 +110,16 @@ def quantise(out: np.ndarray) -> np.ndarray:
 def enhance(img_u8: np.ndarray, sd, tile_size: int = 256, tile_pad: int = 10, emulated: bool = False) -> np.ndarray:
     """`RealESRGAN.enhance`: HxWx3 u8 -> 4Hx4Wx3 u8."""
     return quantise(enhance_float(img_u8, sd, tile_size, tile_pad, emulated=emulated))
+
+
+def gpu_test_images():
+    """The u8 images tests/test_gpu_compact.py runs through forward_batch_u8 / enhance_u8 / tile_process_f32 (seeded)."""
+    rng = np.random.default_rng(77)
+    return {"batch": rng.integers(0, 256, size=(3, 40, 56, 3), dtype=np.uint8),
+            "whole": rng.integers(0, 256, size=(300, 420, 3), dtype=np.uint8),
+            "tiled": rng.integers(0, 256, size=(700, 900, 3), dtype=np.uint8)}
+
+
+def u8_cap_check(a_u8, b_u8, cap):
+    d = np.abs(a_u8.astype(np.int16) - b_u8.astype(np.int16))
+    return int(d.max()), float((d > 0).mean()), bool(d.max() <= 1 and (d > 0).mean() <= cap)

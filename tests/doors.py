@@ -1,7 +1,13 @@
 """The doors of the library as a table: id -> (engine config, fn(engine, inputs) -> arrays).  One entry is ONE call (or the short
-sequence that makes a door, such as base level + overview), on the configs and shapes of tests/test_gpu_redzones.py: the smallest
-that take each route.  tests/test_gpu_poison.py runs every entry in its three states; `inputs` lets a state ask for the same
-call, with the same geometry, on a saturated input (Inputs(dirty=True): all 255 / 65535 / 1.0)."""
+sequence that makes a door, such as base level + overview), on the smallest configs and shapes that take each route.  Three
+modules judge every entry, each under one diagnostic mode of the library: tests/test_gpu_redzones.py (no store outside a buffer),
+tests/test_gpu_poison.py (no load of bytes nobody wrote) and tests/test_gpu_stall.py (no dependence on which stream runs first);
+tests/diag.py holds what they share.  `inputs` lets a judge ask for the same call, with the same geometry, on a saturated input
+(Inputs(dirty=True): all 255 / 65535 / 1.0).  Importing this file builds the table and touches no device
+(tests/test_doors_cpu.py; tests/golden/doors_idents.txt lists the identifiers).
+
+x2plus refuses odd tile sizes (pixel_unshuffle by 2), so its net doors run the listed shapes as the trunk grid: tiles of
+2 th x 2 tw.  The 16-bit doors exist on the x4 RRDB nets only."""
 import tempfile
 from pathlib import Path
 
@@ -9,10 +15,19 @@ import numpy as np
 import torch
 
 import resample_model as rm
-import test_gpu_redzones as rz
 from s2sr import geo, native, tiles
 
-CONFIGS, NET_SHAPES, IMAGES, FULL, SUB = rz.CONFIGS, rz.NET_SHAPES, rz.IMAGES, rz.FULL, rz.SUB
+HP, F16, FP8 = native.PREC_F16_HP, native.PREC_F16, native.PREC_FP8
+# name -> gpu_engines.default's arguments: num_block, precision, scale, arch
+CONFIGS = {"x4_hp": (1, HP, 4, "rrdb"), "x4_f16": (1, F16, 4, "rrdb"), "x4_fp8": (1, FP8, 4, "rrdb"), "x2plus": (1, HP, 2, "rrdb"),
+           "compact": (16, HP, 4, "compact")}
+# tests/test_gpu_tail.py SHAPES (B, th, tw, job_windows) and the degenerate ones
+NET_SHAPES = {"full_1x16x32": (1, 16, 32, 0), "ragged_2x37x53": (2, 37, 53, 0), "short_3x7x45": (3, 7, 45, 0),
+              "mosaic_9x20x20": (9, 20, 20, 0), "dead_7of9x20x20": (7, 20, 20, 9), "one_1x1x1": (1, 1, 1, 0), "row_1x1x9": (1, 1, 9, 0),
+              "col_1x7x1": (1, 7, 1, 0)}
+BANDED, CHUNKED = (100, 90, 16, 2), (53, 200, 16, 3)          # tests/test_gpu_u16.py, tests/test_gpu_blend.py
+IMAGES = {"banded": BANDED, "chunked": CHUNKED, "short_ramps": (39, 39, 16, 3), "untiled": (28, 36, 256, 10), "one_pixel": (1, 1, 256, 10)}
+FULL, SUB = (0, 65535), (1000, 11000)
 FILL = 0x5A                      # what a caller-owned output buffer holds before the call, on both sides of a comparison
 
 
@@ -52,6 +67,10 @@ def _back(t):
     return t.cpu().numpy()
 
 
+def _dev_u8(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
 DOORS = {}
 
 
@@ -64,9 +83,17 @@ def door(ident, config):
 
 
 # ---- net doors -----------------------------------------------------------------------------------------------------------------------
+def _part(e, tiles_u8, job, scale):
+    B, th, tw, _ = tiles_u8.shape
+    x = _dev_u8(tiles_u8)
+    y = torch.zeros((B, scale * th, scale * tw, 3), dtype=torch.uint8, device="cuda")
+    e.forward_part_u8_dev(x.data_ptr(), B, th, tw, job, y.data_ptr(), _stream())
+    return _back(y)
+
+
 def _fwd_u8_dev(e, t8, S):
     B, th, tw, _ = t8.shape
-    x, y = rz._dev_u8(t8), _out((B, S * th, S * tw, 3))
+    x, y = _dev_u8(t8), _out((B, S * th, S * tw, 3))
     e.forward_batch_u8_dev(x.data_ptr(), B, th, tw, y.data_ptr(), _stream())
     return _back(y)
 
@@ -87,7 +114,7 @@ def _net_doors():
             dims, seed = (B, th, tw, 3), B * 10000 + th * 100 + tw
             pre = f"{name}-{shape}"
             if job:                                      # the dead-window job: B windows of a mosaic planned for `job`
-                door(f"{pre}-forward_part_u8_dev", name)(lambda e, X, d=dims, s=seed, j=job, S=S: rz._part(e, X.u8(d, s), j, S))
+                door(f"{pre}-forward_part_u8_dev", name)(lambda e, X, d=dims, s=seed, j=job, S=S: _part(e, X.u8(d, s), j, S))
                 continue
             door(f"{pre}-forward_batch_u8", name)(lambda e, X, d=dims, s=seed: e.forward_batch_u8(X.u8(d, s)))
             door(f"{pre}-forward_f32", name)(lambda e, X, d=dims, s=seed: e.forward_f32(
@@ -120,9 +147,9 @@ def _u8_image_doors(name, case, H, W, tile, pad, full):
     door(f"{pre}-enhance_f32", name)(lambda e, X: e.enhance_f32(X.u8(sh, seed), **g))
     door(f"{pre}-enhance_job_u8", name)(lambda e, X: e.enhance_job_u8(X.u8(sh, seed), native.pp_wow(), **g))
     door(f"{pre}-blend_u8", name)(lambda e, X: e.enhance_blend_u8(X.u8(sh, seed), **g))
+    door(f"{pre}-blend_u8_f32", name)(lambda e, X: e.enhance_blend_u8(X.u8(sh, seed), want_f32=True, **g))
     if not full:
         return
-    door(f"{pre}-blend_u8_f32", name)(lambda e, X: e.enhance_blend_u8(X.u8(sh, seed), want_f32=True, **g))
     door(f"{pre}-blend_u8_job", name)(lambda e, X: e.enhance_blend_u8(X.u8(sh, seed), native.pp_wow(), swap_rb=True, **g))
     door(f"{pre}-masked_u8", name)(lambda e, X: e.enhance_masked_u8(X.u8(sh, seed), _valid(H, W, seed), radius=5, out_nodata=3, **g))
     door(f"{pre}-masked_u8_blend", name)(
@@ -171,7 +198,7 @@ def _plan(e, H, W, tile, pad):
 
 def _cut(e, X, H, W, tile, pad):
     T, wh, ww = _plan(e, H, W, tile, pad)
-    img = rz._dev_u8(X.u8((H, W, 3), H + W))
+    img = _dev_u8(X.u8((H, W, 3), H + W))
     buf = _out((T, wh, ww, 3))
     e.cut_windows_u8_dev(img.data_ptr(), H, W, tile, pad, 0, T, buf.data_ptr(), _stream())
     if T > 2:                                            # a part of the plan into a buffer of its own
@@ -184,7 +211,7 @@ def _cut(e, X, H, W, tile, pad):
 def _stitch(e, X, H, W, tile, pad, rows):
     S = e.scale
     T, wh, ww = _plan(e, H, W, tile, pad)
-    d_tiles = rz._dev_u8(X.u8((T, S * wh, S * ww, 3), H * W))
+    d_tiles = _dev_u8(X.u8((T, S * wh, S * ww, 3), H * W))
     out = _out((S * H, S * W, 3))
     if not rows:
         e.stitch_windows_u8_dev(d_tiles.data_ptr(), H, W, tile, pad, out.data_ptr(), _stream())
@@ -215,48 +242,92 @@ def _block_doors():
 
 
 # ---- post-process --------------------------------------------------------------------------------------------------------------------
+def _pp(grid, sigma=1.2):
+    return native.PPParams(2.5, grid, sigma, 1.4, -0.4, 35, 85, 1.2, 7)
+
+
+def banded(e, img, prm, hist_cuts, row_cuts, order=0, in_place=False):
+    """The s2sr_pp_band_*_dev sequence on a device copy of `img`: hist over the bands of hist_cuts (given out of order on purpose),
+    lut, rows over the bands of row_cuts."""
+    H, W, _ = img.shape
+    x = _dev_u8(img)
+    y = x if in_place else torch.full_like(x, FILL)
+    st = _stream()
+    e.pp_band_begin_dev(H, W, prm, order, st)
+    bands = list(zip(hist_cuts[:-1], hist_cuts[1:]))
+    for a, b in bands[1::2] + bands[0::2]:
+        e.pp_band_hist_dev(x.data_ptr(), a, b, st)
+    e.pp_band_lut_dev(st)
+    for a, b in zip(row_cuts[:-1], row_cuts[1:]):
+        e.pp_band_rows_dev(x.data_ptr(), a, b, y.data_ptr(), st)
+    return _back(y)
+
+
+def _banded(e, img, prm, step):
+    cuts = [*range(0, img.shape[0], step), img.shape[0]]
+    return banded(e, img, prm, cuts, cuts)
+
+
 def _pp_batch(e, X, B, H, W, prm):
-    x = rz._dev_u8(X.green((B, H, W, 3), 12))
+    x = _dev_u8(X.green((B, H, W, 3), 12))
     y = _out((B, H, W, 3))
     e.postprocess_batch_u8_dev(x.data_ptr(), B, H, W, prm, y.data_ptr(), _stream())
     return _back(y)
 
 
 def _postprocess_doors():
-    prms = {"wow": native.pp_wow(), "farm": native.pp_farm(), "grid16_wide": rz._pp(16, sigma=2.7)}
+    prms = {"wow": native.pp_wow(), "farm": native.pp_farm(), "grid16_wide": _pp(16, sigma=2.7)}
     for H, W in ((67, 101), (5, 9)):
         for pn, prm in prms.items():
             pre = f"{H}x{W}-{pn}"
             door(f"postprocess_u8-{pre}", "x4_hp")(lambda e, X, a=(H, W, 3), p=prm: e.postprocess_u8(X.green(a, 10), p))
             door(f"postprocess_batch_u8_dev-{pre}", "x4_hp")(lambda e, X, a=(3, H, W), p=prm: _pp_batch(e, X, *a, p))
-            door(f"pp_band_sequence-{pre}", "x4_hp")(lambda e, X, a=(H, W, 3), p=prm: rz._banded(e, X.green(a, 11), p, 5, fill=FILL))
+            door(f"pp_band_sequence-{pre}", "x4_hp")(lambda e, X, a=(H, W, 3), p=prm: _banded(e, X.green(a, 11), p, 5))
+    # one pixel, a sliver, and 70 x 101 with both CLAHE grids: whole at sigma 1.2, and with the widest Gaussian the entries accept
+    # (sigma < 2.75: 17 taps, 8 rows of look-ahead, more than a band) whole and in bands of 5 rows ON THE SAME IMAGE, which
+    # tests/test_gpu_redzones.py holds to each other
+    for H, W in ((1, 1), (3, 300), (70, 101)):
+        for grid in (8, 16):
+            door(f"postprocess_u8-{H}x{W}-grid{grid}", "x4_hp")(lambda e, X, a=(H, W, 3), p=_pp(grid): e.postprocess_u8(X.green(a, 13), p))
+    for grid in (8, 16):
+        prm = _pp(grid, sigma=2.7)
+        door(f"postprocess_u8-70x101-grid{grid}_wide", "x4_hp")(lambda e, X, p=prm: e.postprocess_u8(X.green((70, 101, 3), 13), p))
+        door(f"pp_band_sequence-70x101-grid{grid}_wide", "x4_hp")(lambda e, X, p=prm: _banded(e, X.green((70, 101, 3), 13), p, 5))
 
 
 # ---- display -------------------------------------------------------------------------------------------------------------------------
 def _display_doors():
-    H, W = 37, 53
     lut = np.random.default_rng(99).integers(0, 256, size=(3, 65536), dtype=np.uint8)
-    sh = (H, W, 3)
-    for rows in (0, 7):
-        door(f"display_hist_u16-bands{rows}", "x4_hp")(lambda e, X, r=rows: e.display_hist_u16(X.u16(sh, H), band_rows=r))
-        door(f"display_hist_u16-nodata-bands{rows}", "x4_hp")(
-            lambda e, X, r=rows: e.display_hist_u16(X.u16(sh, H), nodata=int(X.u16(sh, H)[0, 0, 0]), band_rows=r))
-        door(f"display_apply_u16-bands{rows}", "x4_hp")(lambda e, X, r=rows: e.display_apply_u16(X.u16(sh, H), lut, band_rows=r))
 
-    @door("display_behind_enhance_u16", "x4_hp")
-    def behind_enhance(e, X):                            # the device copy enhance_u16 leaves: 4H x 4W
+    def behind_enhance(e, X, H, W, rows):                # the device copy enhance_u16 leaves: 4H x 4W
         with e.chain_lock:
-            q = rz.keep(e.enhance_u16(X.u16(sh, H)))
-            h = e.display_hist_u16(None, band_rows=7, shape=(4 * H, 4 * W))
-            a = e.display_apply_u16(None, lut, band_rows=7, shape=(4 * H, 4 * W))
+            q = np.array(e.enhance_u16(X.u16((H, W, 3), H)))
+            h = e.display_hist_u16(None, band_rows=rows, shape=(4 * H, 4 * W))
+            a = e.display_apply_u16(None, lut, band_rows=rows, shape=(4 * H, 4 * W))
         return q, h, a
+    # 37 x 53 whole and in bands of 7 rows; 255 x 257 whole: more than one workgroup's pixels, odd on both axes
+    for H, W, rows, tag in ((37, 53, 0, "bands0"), (37, 53, 7, "bands7"), (255, 257, 0, "255x257-bands0")):
+        sh = (H, W, 3)
+        door(f"display_hist_u16-{tag}", "x4_hp")(lambda e, X, sh=sh, r=rows: e.display_hist_u16(X.u16(sh, sh[0]), band_rows=r))
+        door(f"display_hist_u16-nodata-{tag}", "x4_hp")(
+            lambda e, X, sh=sh, r=rows: e.display_hist_u16(X.u16(sh, sh[0]), nodata=int(X.u16(sh, sh[0])[0, 0, 0]), band_rows=r))
+        door(f"display_apply_u16-{tag}", "x4_hp")(lambda e, X, sh=sh, r=rows: e.display_apply_u16(X.u16(sh, sh[0]), lut, band_rows=r))
+    door("display_behind_enhance_u16", "x4_hp")(lambda e, X: behind_enhance(e, X, 37, 53, 7))
+    door("display_behind_enhance_u16-255x257-bands0", "x4_hp")(lambda e, X: behind_enhance(e, X, 255, 257, 0))
 
 
 # ---- pyramid -------------------------------------------------------------------------------------------------------------------------
+def _scene(h, w, seed=0):
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w]
+    img = np.stack([120 + 90 * np.sin(xx / 11.0 + c) * np.cos(yy / 7.0) + rng.integers(-15, 16, (h, w)) for c in range(3)], -1)
+    return np.clip(img, 0, 255).astype(np.uint8)
+
+
 def _rgba(X, h, w, seed):
     if X.dirty:
         return np.full((h, w, 4), 255, np.uint8)
-    rgba = np.concatenate([rz._scene(h, w, seed=seed), np.full((h, w, 1), 255, np.uint8)], -1)
+    rgba = np.concatenate([_scene(h, w, seed=seed), np.full((h, w, 1), 255, np.uint8)], -1)
     rgba[..., 3] = np.where(np.random.default_rng(seed).random((h, w)) < 0.15, 0, 255)
     return rgba
 
@@ -276,20 +347,40 @@ def png_level(X):
     return rgba
 
 
-def _pngs(e, X, **flags):
-    ident = np.arange(512, dtype=np.int32)
-    e.tiles_base_u8(png_level(X), ident, ident, ident, ident, fetch=False)
+def png_level_5x4(X):
+    """The 5 x 4 level of tests/test_gpu_tiles.py's PNG pipeline test: smooth tiles, one of noise (tile 7), a half-covered and a
+    transparent one."""
+    H, W = 4 * 256, 5 * 256
+    if X.dirty:
+        return np.full((H, W, 4), 255, np.uint8)
+    rng = np.random.default_rng(23)
+    yy, xx = np.mgrid[0:H, 0:W]
+    rgba = np.empty((H, W, 4), np.uint8)
+    rgba[..., :3] = np.clip(120 + 80 * np.sin(xx / 37.0)[..., None] * np.cos(yy / 23.0)[..., None] + rng.integers(-4, 5, (H, W, 3)), 0, 255)
+    rgba[256:512, 512:768, :3] = rng.integers(0, 256, (256, 256, 3))
+    rgba[..., 3] = 255
+    rgba[768:, :256, 3] = 0
+    rgba[:128, 1024:, 3] = 0
+    return rgba
+
+
+def _pngs(e, X, level=png_level, no_path=(), **flags):
+    """(the 0/1 array of files written, each tile's file bytes -- empty where there is no file); no_path: tiles given no path"""
+    rgba = level(X)
+    ny, nx = rgba.shape[0] // 256, rgba.shape[1] // 256
+    iy, ix = np.arange(rgba.shape[0], dtype=np.int32), np.arange(rgba.shape[1], dtype=np.int32)
+    e.tiles_base_u8(rgba, ix, ix, iy, iy, fetch=False)
     with tempfile.TemporaryDirectory() as d:
-        paths = [Path(d) / f"{j}_{i}.png" for j in range(2) for i in range(2)]
-        wrote = e.tiles_write_png(2, 2, paths, **flags).copy()
-        files = [np.frombuffer(q.read_bytes(), np.uint8) if q.exists() else np.zeros(0, np.uint8) for q in paths]
+        paths = [None if j * nx + i in no_path else Path(d) / f"{j}_{i}.png" for j in range(ny) for i in range(nx)]
+        wrote = e.tiles_write_png(nx, ny, paths, **flags).copy()
+        files = [np.frombuffer(q.read_bytes(), np.uint8) if q is not None and q.exists() else np.zeros(0, np.uint8) for q in paths]
     return (wrote, *files)
 
 
 def _pyramid_doors():
     @door("warp_bilinear_u8", "x4_hp")
     def warp(e, X):
-        rgb = np.full((150, 211, 3), 255, np.uint8) if X.dirty else rz._scene(150, 211, seed=32633)
+        rgb = np.full((150, 211, 3), 255, np.uint8) if X.dirty else _scene(150, 211, seed=32633)
         plan = tiles.plan_warp(211, 150, geo.Placement(600000.0, 5100000.0, 2.5, 2.5), geo.CRS(32633))
         return e.warp_bilinear_u8(rgb, plan.grid, plan.step, plan.out_h, plan.out_w)
 
@@ -304,6 +395,14 @@ def _pyramid_doors():
         return e.tiles_overview_u8(child, ox, oy, levels[1].nx, levels[1].ny, on_device=on_device)
     door("tiles_overview_u8-host_child", "x4_hp")(lambda e, X: overview(e, X, False))
     door("tiles_overview_u8-device_child", "x4_hp")(lambda e, X: overview(e, X, True))
+
+    @door("tiles_overview_u8-two_levels", "x4_hp")
+    def two_overviews(e, X):                             # the first from the host copy, the second from the level the first left on the device
+        out = [np.array(e.tiles_base_u8(_rgba(X, 300, 420, 2), *base))]
+        for k in (1, 2):
+            ox, oy = tiles.overview_offsets(levels[k], levels[k - 1])
+            out.append(np.array(e.tiles_overview_u8(out[-1], ox, oy, levels[k].nx, levels[k].ny, on_device=(k == 2))))
+        return tuple(out)
     box = (-3.7, -46.0, -3.7 + 512 / 9.0, 38.1)          # tests/test_gpu_resample.py OVERZOOM
     for filt in tiles.FILTERS:
         cols = tiles.plan_resample_axis(2 * 256, box[0], box[2], rm.W, filt)
@@ -314,6 +413,8 @@ def _pyramid_doors():
     door("tiles_write_png-row_threads", "x4_hp")(lambda e, X: _pngs(e, X, row_threads=True))
     door("tiles_write_png-host_encoder", "x4_hp")(lambda e, X: _pngs(e, X, host_encoder=True))
     door("tiles_write_png-small_groups", "x4_hp")(lambda e, X: _pngs(e, X, small_groups=True))
+    # groups of 3 tiles over 20: the stream buffers regrow between groups, so buffers are freed (and their zones checked) mid-call
+    door("tiles_write_png-small_groups_5x4", "x4_hp")(lambda e, X: _pngs(e, X, png_level_5x4, no_path=(7,), small_groups=True))
 
 
 _net_doors()

@@ -25,6 +25,8 @@ import numpy as np
 from oracle import rrdbnet_ref as ref
 from s2sr.weights import compact_specs, synthetic_state_dict
 
+# the plans of tests/test_gpu_cut_stitch.py (those of test_cut_forward_stitch_equals_enhance): H, W, tile, pad
+STITCH_GEOS = [(37, 45, 16, 2), (50, 41, 16, 2), (64, 65, 32, 4), (33, 70, 16, 3), (49, 48, 16, 2), (70, 36, 32, 2)]
 TAP_LAYERS = ("conv_first", "conv_up1", "conv_up2", "conv_hr", "conv_last")
 # the H / W at which window plans change shape, for a tile t and pad p (win = t + 2p)
 def edge_sizes(t, p):

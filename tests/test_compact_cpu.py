@@ -219,30 +219,17 @@ def test_golden_weights_are_well_chosen(golden_dir):
         assert moved >= 0.01
 
 
-def gpu_test_images():
-    """The u8 images tests/test_gpu_compact.py runs through forward_batch_u8 / enhance_u8 / tile_process_f32 (seeded)."""
-    rng = np.random.default_rng(77)
-    return {"batch": rng.integers(0, 256, size=(3, 40, 56, 3), dtype=np.uint8),
-            "whole": rng.integers(0, 256, size=(300, 420, 3), dtype=np.uint8),
-            "tiled": rng.integers(0, 256, size=(700, 900, 3), dtype=np.uint8)}
-
-
-def u8_cap_check(a_u8, b_u8, cap):
-    d = np.abs(a_u8.astype(np.int16) - b_u8.astype(np.int16))
-    return int(d.max()), float((d > 0).mean()), bool(d.max() <= 1 and (d > 0).mean() <= cap)
-
-
 def test_u8_cap_is_reachable_on_the_gpu_images():
     """The GPU test allows 1 level at no more than 4 % of the values.  Truncation flips a level wherever the float lands within
     the error of an integer; here the checker-versus-emulation pair must stay within HALF that (2 %, 1 level) on the very images
     the GPU test uses, so the cap is known to be reachable before a GPU run.  (The two large images are checked on a corner
     each: the error statistics are per pixel, and the float64 net on 700 x 900 pixels takes minutes on a CPU.)"""
-    imgs = gpu_test_images()
+    imgs = cm.gpu_test_images()
     sd = W.synthetic_compact_state_dict(32, seed=0)
     for name, img in (("batch", imgs["batch"][0]), ("whole", imgs["whole"][:160, :200]), ("tiled", imgs["tiled"][:128, :160])):
         q = cm.enhance(img, sd)
         e = cm.enhance(img, sd, emulated=True)
-        mx, share, ok = u8_cap_check(q, e, 0.02)
+        mx, share, ok = cm.u8_cap_check(q, e, 0.02)
         print(f"{name}: checker vs emulation max {mx}, share {share:.4f}")
         assert ok, (name, mx, share)
 

@@ -349,14 +349,13 @@ def _negative_everywhere(sd, x, margin=0):
 
 
 def test_shape_inputs_reach_every_channel():
-    """The inputs of test_gpu_compact_insitu.SHAPES on which the GPU test demands negative pre-activations in every channel of every
+    """The inputs of compact_insitu.SHAPES on which the GPU test demands negative pre-activations in every channel of every
     judged layer do have them (float32 emulation; windows of a mosaic are independent images).  Shapes above 96 x 96 are run on the
     top-left 96 x 96 of their windows and counted on its 63 x 63 corner, which 33 convs from the cut cannot reach."""
-    import test_gpu_compact_insitu as g
-    for shape, (kind, B, th, tw, job, env, every) in g.SHAPES.items():
-        if shape in g.NO_NEGATIVE_GUARD:
+    for shape, (kind, B, th, tw, job, env, every) in ci.SHAPES.items():
+        if shape in ci.NO_NEGATIVE_GUARD:
             continue
-        _, kw = g.shape_inputs(shape)
+        _, kw = ci.shape_inputs(shape)
         if "tiles" in kw:
             x = _f32(kw["tiles"].transpose(0, 3, 1, 2))
         else:

@@ -22,7 +22,6 @@ import compact_model as cm
 from s2sr import native
 from s2sr import rasterio_lite as rio
 from s2sr import weights as W
-from test_compact_cpu import gpu_test_images, u8_cap_check
 
 pytestmark = pytest.mark.gpu
 
@@ -146,10 +145,10 @@ def test_sub_pixel_order_on_the_device(monkeypatch):
 
 # ---- 4. u8 paths -----------------------------------------------------------------------------------------------------------
 def test_u8_paths_vs_checker():
-    imgs = gpu_test_images()
+    imgs = cm.gpu_test_images()
     sd, e = _sd(32), engine(32)
     q = cm.quantise(_ref_f64(imgs["batch"], sd).transpose(0, 2, 3, 1))
-    mx, share, ok = u8_cap_check(e.forward_batch_u8(imgs["batch"]), q, U8_CAP)
+    mx, share, ok = cm.u8_cap_check(e.forward_batch_u8(imgs["batch"]), q, U8_CAP)
     print(f"forward_batch_u8: max {mx}, share {share:.4f}")
     assert ok
     for name, tile in (("whole", 256), ("tiled", 256)):          # 300 x 420 <= 256^2 * 4 < 700 x 900: both branches of the rule
@@ -157,7 +156,7 @@ def test_u8_paths_vs_checker():
         assert (img.shape[0] * img.shape[1] > tile * tile * 4) == (name == "tiled")
         exp_f = cm.enhance_float(img, sd, tile, 10)
         out = e.enhance_u8(img, tile=tile, pad=10)
-        mx, share, ok = u8_cap_check(out, cm.quantise(exp_f), U8_CAP)
+        mx, share, ok = cm.u8_cap_check(out, cm.quantise(exp_f), U8_CAP)
         print(f"enhance_u8 {name}: max {mx}, share {share:.4f}")
         assert out.shape == (4 * img.shape[0], 4 * img.shape[1], 3) and ok
         f = e.enhance_f32(img, tile=tile, pad=10)
@@ -166,7 +165,7 @@ def test_u8_paths_vs_checker():
     t = e.tile_process_f32(img, tile=128, pad=10)
     exp_t = cm.enhance_float(img, sd, 128, 10, force_tiled=True)
     err = float(np.abs(t - exp_t).max())
-    mx, share, ok = u8_cap_check(cm.quantise(t.astype(np.float64)), cm.quantise(exp_t), U8_CAP)
+    mx, share, ok = cm.u8_cap_check(cm.quantise(t.astype(np.float64)), cm.quantise(exp_t), U8_CAP)
     print(f"tile_process_f32: max-abs {err:.3g}; u8 max {mx}, share {share:.4f}")
     assert err <= TOL and ok
 
@@ -335,14 +334,14 @@ def test_app_compact(monkeypatch, tmp_path):
     e = m.RealESRGAN(model_name="realesr_general_x4v3")
     assert e.scale == 4 and e._engine.arch == "compact" and e._engine.num_block == 32
     out = e.enhance(img)
-    assert out.shape == (160, 224, 3) and u8_cap_check(out, cm.enhance(img, a), U8_CAP)[2]
+    assert out.shape == (160, 224, 3) and cm.u8_cap_check(out, cm.enhance(img, a), U8_CAP)[2]
     assert tuple(e._tile_process(torch.from_numpy(img.astype(np.float32) / 255.0).permute(2, 0, 1).unsqueeze(0)).shape) == (1, 3, 160, 224)
     assert e.enhance_job(img).shape == (160, 224, 3)
     d = m.RealESRGAN(model_name="realesr_general_x4v3", denoise_strength=0.5)
     mix = W.dni(a, b, 0.5)
     out_d = d.enhance(img)
-    assert u8_cap_check(out_d, cm.enhance(img, mix), U8_CAP)[2]
-    assert not u8_cap_check(out_d, out, U8_CAP)[2]                   # the interpolated weights are another net
+    assert cm.u8_cap_check(out_d, cm.enhance(img, mix), U8_CAP)[2]
+    assert not cm.u8_cap_check(out_d, out, U8_CAP)[2]                   # the interpolated weights are another net
     with pytest.raises(ValueError, match="denoise_strength"):
         m.RealESRGAN(model_name="realesr_general_wdn_x4v3", denoise_strength=0.5)
     # process_wow_sr end to end on a GeoTIFF
@@ -356,4 +355,4 @@ def test_app_compact(monkeypatch, tmp_path):
     sr, g2 = rio.read_rgb_u8(res["outputs"]["sr_tif"])
     assert sr.shape == (100, 132, 3) and g2.pixel_size == (2.5, 2.5)
     exp_sr = cm.enhance(np.ascontiguousarray(rgb[:, :, ::-1]), a)[:, :, ::-1]
-    assert u8_cap_check(sr, exp_sr, U8_CAP)[2]
+    assert cm.u8_cap_check(sr, exp_sr, U8_CAP)[2]

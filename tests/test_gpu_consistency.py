@@ -13,16 +13,16 @@ import numpy as np
 import pytest
 
 import consistency_model as cm
-import gpu_engines
+import diag
 import nodata_model as nm
 import probe_model as pm
+from diag import Z, clean
 from s2sr import native
 
 pytestmark = pytest.mark.gpu
 
-Z = 65536
 HP = native.PREC_F16_HP
-CONFIGS = {"x4": (1, HP, 4, "rrdb"), "x2": (1, HP, 2, "rrdb"), "compact": (16, HP, 4, "compact")}
+NAMES = {"x4": "x4_hp", "x2": "x2plus", "compact": "compact"}       # this module's names for the 1-block HP configs of tests/doors.py
 WHOLE, BANDED, CHUNKED = (28, 36, 256, 10), (100, 90, 16, 2), (53, 200, 16, 3)     # tests/test_gpu_blend.py: untiled, one chunk, three chunks
 # 1 x 1; odd; ragged; three 16-pixel workgroup tiles on both axes, ragged on both (S = 2: two 32-pixel tiles); one block row; one block column
 PASS_SHAPES = [(1, 1), (3, 5), (17, 33), (40, 75), (5, 300), (300, 5)]
@@ -33,30 +33,9 @@ MODES = [cm.EXACT, cm.SMOOTH]
 
 @pytest.fixture(scope="module")
 def zoned():
-    """name -> an engine created (and so allocated) under red zones; closed at the end, the zone size put back."""
-    before = native.redzone_bytes()
-    native.redzone(Z)
-    made = {}
-
-    def get(name):
-        if name not in made:
-            nb, prec, scale, arch = CONFIGS[name]
-            e = native.Engine(num_block=nb, precision=prec, scale=scale, arch=arch)
-            e.load_state_dict(gpu_engines.state_dict(nb, scale, arch))
-            made[name] = e
-        return made[name]
-    yield get
-    for e in made.values():
-        e.close()
-    native.redzone(before)
-
-
-def clean(e, least=4):
-    """no damaged zone anywhere in the process, and the engine counts at least `least` zoned allocations of its own (an engine
-    created under zones with weights loaded owns at least 4; the operator's shared engine may be older than this module: 0)."""
-    n, bad, msg = e.redzone_check()
-    assert bad == 0, msg
-    assert n >= least, n
+    """name -> an engine created (and so allocated) under red zones"""
+    with diag.engines_under(native.redzone_bytes, native.redzone, Z) as get:
+        yield lambda name: get(NAMES[name])
 
 
 def same(got, want, what):

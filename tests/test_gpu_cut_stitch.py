@@ -11,7 +11,6 @@ import gpu_engines
 import probe_model as pm
 from oracle import rrdbnet_ref as ref
 from s2sr import native
-from test_probe_cpu import STITCH_GEOS
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +36,7 @@ def _same(got, want, what):
 
 def test_cut_windows_equal_numpy_slices(engine):
     S = engine.scale
-    geos = STITCH_GEOS + [(17, 53, 16, 2), (19, 60, 16, 2), (3, 40, 16, 2)]       # + duplicate window rows, H < win, a 3-pixel side
+    geos = pm.STITCH_GEOS + [(17, 53, 16, 2), (19, 60, 16, 2), (3, 40, 16, 2)]       # + duplicate window rows, H < win, a 3-pixel side
     for H, W, t, p in geos:
         if S == 2 and min(H, W) < 2:
             continue
@@ -78,7 +77,7 @@ def test_stitch_equals_the_reference_paste(engine):
     S = engine.scale
     st = lambda: torch.cuda.current_stream().cuda_stream
     cases = []
-    for H, W, t, p in STITCH_GEOS:
+    for H, W, t, p in pm.STITCH_GEOS:
         PH, PW = (H + H % 2, W + W % 2) if S == 2 else (H, W)
         plan = ref.tile_plan(PH, PW, t, p, S)
         (y1, y2, x1, x2) = plan[0][0]

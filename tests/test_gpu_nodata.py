@@ -11,16 +11,16 @@ import json
 import numpy as np
 import pytest
 
-import gpu_engines
+import diag
 import nodata_model as nm
 import probe_model as pm
+from diag import Z, clean
 from s2sr import native
 
 pytestmark = pytest.mark.gpu
 
-Z = 65536
 HP = native.PREC_F16_HP
-CONFIGS = {"x4": (1, HP, 4, "rrdb"), "x2": (1, HP, 2, "rrdb"), "compact": (16, HP, 4, "compact")}
+NAMES = {"x4": "x4_hp", "x2": "x2plus", "compact": "compact"}       # this module's names for the 1-block HP configs of tests/doors.py
 WHOLE, BANDED, CHUNKED = (28, 36, 256, 10), (100, 90, 16, 2), (53, 200, 16, 3)     # tests/test_gpu_blend.py: untiled, one chunk, three chunks
 FILL_SHAPES = [(37, 53), (70, 300)]                # the second: wider than one workgroup tile (256 columns), five tile rows
 RADII = [1, 5, 32, 64]
@@ -30,33 +30,9 @@ LO, HI = 100, 10300
 
 @pytest.fixture(scope="module")
 def zoned():
-    """name -> an engine created (and so allocated) under red zones; closed at the end, the zone size put back."""
-    before = native.redzone_bytes()
-    native.redzone(Z)
-    made = {}
-
-    def get(name):
-        if name not in made:
-            nb, prec, scale, arch = CONFIGS[name]
-            e = native.Engine(num_block=nb, precision=prec, scale=scale, arch=arch)
-            e.load_state_dict(gpu_engines.state_dict(nb, scale, arch))
-            made[name] = e
-        return made[name]
-    yield get
-    for e in made.values():
-        e.close()
-    native.redzone(before)
-
-
-def clean(e, least=4):
-    """no damaged zone anywhere in the process, and the engine counts at least `least` zoned allocations of its own.  An engine
-    created under zones with weights loaded: the trash page, the bias pool and at least two weight buffers, so 4 (the bound of
-    tests/test_gpu_redzones.py).  One without weights that ran only the fill owns exactly three: the trash page s2sr_create
-    allocates, the image (scratch 0) and the mask copy (scratch 6).  The operator's engine is shared by the process and may be
-    older than this module (allocated without zones): 0."""
-    n, bad, msg = e.redzone_check()
-    assert bad == 0, msg
-    assert n >= least, n
+    """name -> an engine created (and so allocated) under red zones"""
+    with diag.engines_under(native.redzone_bytes, native.redzone, Z) as get:
+        yield lambda name: get(NAMES[name])
 
 
 def same(got, want, what):
@@ -122,7 +98,7 @@ def test_fill_needs_no_weights_and_takes_any_truthy_mask(zoned):
         img, valid = nodata_image(H, W, "holes"), nm.make_mask("holes", H, W)
         same(e.fill_nodata(img, valid * 200, 5), model_fill(img, "holes", 5), "mask bytes of 200")
         same(e.fill_nodata(img, valid.astype(bool), 5), model_fill(img, "holes", 5), "a bool mask")
-        clean(e, least=3)
+        clean(e, least=3)                                        # the trash page, the image (scratch 0), the mask copy (scratch 6)
     finally:
         e.close()
 

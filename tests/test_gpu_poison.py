@@ -6,8 +6,9 @@ workspace is zeroed once and reused -- so a histogram without its memset, a stre
 mosaic window or a ragged patch edge reads a plausible value in every fresh process and something else in a long-lived one.  The
 library's poison mode (include/s2sr.h s2sr_debug_poison; csrc/redzone.h namespace poison) fills what an allocation hands out, and
 on request what the scratch slots hold, with 0xFF bytes (pattern 1: NaN as fp32 / fp16 / e4m3, -1 as an index) or with a
-position-dependent non-zero byte (pattern 2).  Each door of tests/doors.py must return, byte for byte (dtype and shape included),
-what the same call returns on the cached engine of gpu_engines.py with the mode off, in three states:
+position-dependent non-zero byte (pattern 2).  Each door of tests/doors.py -- the table the red-zone and the
+stall module judge too -- must return, byte for byte (dtype and shape included), what the same call returns on the cached engine of
+gpu_engines.py with every mode off (diag.baseline), in three states:
   (a) fresh: on an engine created under poison, so every first allocation and every regrow is poisoned -- patterns 1 and 2;
   (b) scratch: poison_scratch() in front of every sighting -- the second sighting is the graph capture, the third (net doors) a
       replay -- the patterns taking turns from sighting to sighting;
@@ -52,63 +53,24 @@ import numpy as np
 import pytest
 import torch
 
+import diag
 import doors
-import gpu_engines
-import test_gpu_redzones as rz
+from diag import baseline, keep, new_engine, same
 from doors import DOORS, Inputs
 from s2sr import native
 
 pytestmark = pytest.mark.gpu
 
-CONFIGS = doors.CONFIGS
-NET_ENTRIES = ("forward_batch_u8", "forward_f32", "forward_batch_u16", "forward_part_u8_dev")
-
 
 @pytest.fixture(scope="module")
 def poisoned():
-    """(config, pattern) -> an engine created, and its weights loaded, under that pattern; all closed at the end and the pattern
-    put back to what the module found (0, or what S2SR_POISON set for the whole run)."""
-    before = native.poison_pattern()
-    made = {}
-
-    def get(name, pattern):
-        if (name, pattern) not in made:
-            native.poison(pattern)
-            made[name, pattern] = rz._new_engine(name)
-        return made[name, pattern]
-    yield get
-    for e in made.values():
-        e.close()
-    native.poison(before)
-
-
-_BASELINE = {}
-
-
-def baseline(ident):
-    """The door on the cached un-poisoned engine, mode off: computed once and shared by the states."""
-    if ident not in _BASELINE:
-        now = native.poison_pattern()
-        native.poison(0)
-        try:
-            name, fn = DOORS[ident]
-            _BASELINE[ident] = rz.keep(fn(gpu_engines.default(*CONFIGS[name]), Inputs()))
-        finally:
-            native.poison(now)
-    return _BASELINE[ident]
-
-
-def same(got, want, what):
-    got, want = (got, want) if isinstance(got, tuple) else ((got,), (want,))
-    assert len(got) == len(want), what
-    for k, (g, w) in enumerate(zip(got, want)):
-        assert g.shape == w.shape and g.dtype == w.dtype, f"{what}: output {k} is {g.dtype} {g.shape}, un-poisoned {w.dtype} {w.shape}"
-        differ = int((g.view(np.uint8) != w.view(np.uint8)).sum())
-        assert differ == 0, f"{what}: {differ} of {g.nbytes} bytes of output {k} differ from the un-poisoned call"
+    """(config, pattern) -> an engine created, and its weights loaded, under that pattern"""
+    with diag.engines_under(native.poison_pattern, native.poison) as get:
+        yield get
 
 
 def judged(e, ident, what):
-    same(rz.keep(DOORS[ident][1](e, Inputs())), baseline(ident), f"{ident}, {what}")
+    same(keep(DOORS[ident][1](e, Inputs())), baseline(ident), f"{ident}, {what}")
 
 
 @pytest.mark.parametrize("pattern", [1, 2])
@@ -154,16 +116,16 @@ def test_the_saturated_inputs_keep_type_and_shape():
 def test_calibrate_fp8_chooses_the_same_exponents(poisoned, pattern):
     t8 = Inputs().u8((2, 37, 53, 3), 5)
     native.poison(0)
-    b = rz._new_engine("x4_fp8")
+    b = new_engine("x4_fp8")
     try:
-        want = b.calibrate_fp8(t8), rz.keep(b.forward_batch_u8(t8))
+        want = b.calibrate_fp8(t8), keep(b.forward_batch_u8(t8))
     finally:
         b.close()
     native.poison(pattern)
-    e = rz._new_engine("x4_fp8")
+    e = new_engine("x4_fp8")
     try:
         assert e.calibrate_fp8(t8) == want[0]                          # (a) fresh
-        same(rz.keep(e.forward_batch_u8(t8)), want[1], "forward after the calibration")
+        same(keep(e.forward_batch_u8(t8)), want[1], "forward after the calibration")
         e.poison_scratch()                                             # (b) scratch
         assert e.calibrate_fp8(t8) == want[0]
         native.poison(0)                                               # (c) dirty: a saturated calibration set first
@@ -171,7 +133,7 @@ def test_calibrate_fp8_chooses_the_same_exponents(poisoned, pattern):
         allocs = e.debug_config()["ws_allocs"]
         assert e.calibrate_fp8(t8) == want[0]
         assert e.debug_config()["ws_allocs"] == allocs
-        same(rz.keep(e.forward_batch_u8(t8)), want[1], "forward after the last calibration")
+        same(keep(e.forward_batch_u8(t8)), want[1], "forward after the last calibration")
     finally:
         e.close()
 
@@ -245,7 +207,7 @@ def test_doors_that_consume_what_the_last_call_left_refuse_after_poison_scratch(
         e.display_apply_u16(None, lut, shape=(37, 53))
     with pytest.raises(native.S2srError, match="did not leave a uint16 image"):
         e.display_hist_u16(None, shape=(37, 53))
-    img = rz._dev_u8(Inputs().green((20, 24, 3), 2))
+    img = doors._dev_u8(Inputs().green((20, 24, 3), 2))
     out = torch.zeros_like(img)
     st = torch.cuda.current_stream().cuda_stream
     e.pp_band_begin_dev(20, 24, native.pp_wow(), 0, st)

@@ -4,6 +4,7 @@ the bar is BIT-EXACT."""
 import numpy as np
 import pytest
 
+from doors import banded
 from oracle import postprocess_ref as pp
 from s2sr import native
 
@@ -127,25 +128,6 @@ def test_full_pipelines_on_tiny_and_thin_images(eng):
             assert np.array_equal(got, fn(img)), shape
 
 
-def _banded(eng, img, prm, hist_cuts, row_cuts, order=0, in_place=False):
-    """The s2sr_pp_band_*_dev sequence on a device copy of `img`: hist over the bands of hist_cuts (given out of order on purpose),
-    lut, rows over the bands of row_cuts."""
-    import torch
-    H, W, _ = img.shape
-    x = torch.from_numpy(np.ascontiguousarray(img)).cuda()
-    y = x if in_place else torch.full_like(x, 0x5a)
-    st = torch.cuda.current_stream().cuda_stream
-    eng.pp_band_begin_dev(H, W, prm, order, st)
-    bands = list(zip(hist_cuts[:-1], hist_cuts[1:]))
-    for (a, b) in bands[1::2] + bands[0::2]:
-        eng.pp_band_hist_dev(x.data_ptr(), a, b, st)
-    eng.pp_band_lut_dev(st)
-    for a, b in zip(row_cuts[:-1], row_cuts[1:]):
-        eng.pp_band_rows_dev(x.data_ptr(), a, b, y.data_ptr(), st)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
-
-
 def test_banded_postprocess_gives_the_bytes_of_the_whole_image(eng):
     """The band-wise route an AOI's mosaic takes (engine_aoi.hip enhance_locked, s2sr/dist.py: CLAHE histograms counted as the bands are
     stitched, LUTs behind the last band, apply + sharpen band by band in front of the copy out) against the whole-image launch:
@@ -166,19 +148,19 @@ def test_banded_postprocess_gives_the_bytes_of_the_whole_image(eng):
         img[..., 1] = np.maximum(img[..., 1], 90)
         for prm in (native.pp_wow(), native.pp_farm()):
             want = eng.postprocess_u8(img, prm)
-            assert np.array_equal(_banded(eng, img, prm, hc, rc), want), (H, W, "rgb")
-            assert np.array_equal(_banded(eng, img, prm, hc, rc, in_place=True), want), (H, W, "in place")
+            assert np.array_equal(banded(eng, img, prm, hc, rc), want), (H, W, "rgb")
+            assert np.array_equal(banded(eng, img, prm, hc, rc, in_place=True), want), (H, W, "in place")
             bgr = np.ascontiguousarray(img[:, :, ::-1])
-            got = _banded(eng, bgr, prm, hc, rc, native.PP_ORDER_BGR, in_place=True)
+            got = banded(eng, bgr, prm, hc, rc, native.PP_ORDER_BGR, in_place=True)
             assert np.array_equal(got[:, :, ::-1], want), (H, W, "bgr in, bgr out")
-            got = _banded(eng, bgr, prm, hc, rc, native.PP_ORDER_BGR | native.PP_ORDER_SWAP_OUT)
+            got = banded(eng, bgr, prm, hc, rc, native.PP_ORDER_BGR | native.PP_ORDER_SWAP_OUT)
             assert np.array_equal(got, want), (H, W, "bgr in, rgb out")
-            got = _banded(eng, img, prm, hc, rc, native.PP_ORDER_SWAP_OUT)
+            got = banded(eng, img, prm, hc, rc, native.PP_ORDER_SWAP_OUT)
             assert np.array_equal(got[:, :, ::-1], want), (H, W, "rgb in, bgr out")
     img = rng.integers(0, 256, (150, 203, 3), dtype=np.uint8)
     for stages in (1, 2, 3, 4, 5, 6):
         prm = P(2.5, 8, 1.2, 1.4, -0.4, 35, 85, 1.2, stages)
-        assert np.array_equal(_banded(eng, img, prm, [0, 70, 150], [0, 31, 150], in_place=True), eng.postprocess_u8(img, prm)), stages
+        assert np.array_equal(banded(eng, img, prm, [0, 70, 150], [0, 31, 150], in_place=True), eng.postprocess_u8(img, prm)), stages
     # misuse is refused, not computed: rows before the LUTs, bands out of order
     import torch
     x = torch.zeros((64, 64, 3), dtype=torch.uint8, device="cuda")
@@ -243,7 +225,7 @@ def test_banded_run_is_void_once_its_scratch_is_taken(weng, taker):
         weng.pp_band_hist_dev(x.data_ptr(), 32, 64, st)
     with pytest.raises(native.S2srError, match="took its scratch"):
         weng.pp_band_lut_dev(st)
-    assert np.array_equal(_banded(weng, img, prm, [0, 32, 64], [0, 32, 64]), want)
+    assert np.array_equal(banded(weng, img, prm, [0, 32, 64], [0, 32, 64]), want)
     # taken between two finishing bands
     weng.pp_band_begin_dev(64, 64, prm, 0, st)
     weng.pp_band_hist_dev(x.data_ptr(), 0, 64, st)
@@ -254,7 +236,7 @@ def test_banded_run_is_void_once_its_scratch_is_taken(weng, taker):
     with pytest.raises(native.S2srError, match="took its scratch"):
         weng.pp_band_rows_dev(x.data_ptr(), 32, 64, y.data_ptr(), st)
     torch.cuda.synchronize()
-    assert np.array_equal(_banded(weng, img, prm, [0, 32, 64], [0, 32, 64]), want)
+    assert np.array_equal(banded(weng, img, prm, [0, 32, 64], [0, 32, 64]), want)
 
 
 def test_gpu_against_cv2_golden(eng, golden_dir):

@@ -8,9 +8,9 @@ sequence) against oracle/postprocess_ref.py, and the bar is the one of that modu
 import numpy as np
 import pytest
 
+from doors import banded
 from oracle import postprocess_ref as pp
 from s2sr import native
-from test_gpu_postprocess import _banded
 
 pytestmark = pytest.mark.gpu
 
@@ -113,9 +113,9 @@ def test_unsharp_every_radius_banded(eng, sigma):
                 what = f"sigma {sigma} {name} weights {a}/{b} stages {stages}"
                 want = _unsharp_then(img, sigma, a, b, stages)
                 _same(eng.postprocess_u8(img, prm), want, what + " whole")
-                _same(_banded(eng, img, prm, hc, rc), want, what + " banded")
-                _same(_banded(eng, img, prm, hc, rc, in_place=True), want, what + " banded in place")
-                _same(_banded(eng, bgr, prm, hc, rc, native.PP_ORDER_BGR | native.PP_ORDER_SWAP_OUT), want, what + " banded bgr in, rgb out")
+                _same(banded(eng, img, prm, hc, rc), want, what + " banded")
+                _same(banded(eng, img, prm, hc, rc, in_place=True), want, what + " banded in place")
+                _same(banded(eng, bgr, prm, hc, rc, native.PP_ORDER_BGR | native.PP_ORDER_SWAP_OUT), want, what + " banded bgr in, rgb out")
 
 
 # ---- CLAHE grids and clip limits -------------------------------------------------------------------------------------------
@@ -143,8 +143,8 @@ def test_clahe_grids_banded(eng, grid):
             what = f"grid {grid} clip {clip} stages {stages}"
             want = pp.postprocess(img, clip, grid, prm.blur_sigma, prm.w_img, prm.w_blur, prm.hue_lo, prm.hue_hi, prm.sat_gain, stages)
             _same(eng.postprocess_u8(img, prm), want, what + " whole")
-            _same(_banded(eng, img, prm, hc, rc), want, what + " banded")
-            _same(_banded(eng, img, prm, hc, rc, in_place=True), want, what + " banded in place")
+            _same(banded(eng, img, prm, hc, rc), want, what + " banded")
+            _same(banded(eng, img, prm, hc, rc, in_place=True), want, what + " banded in place")
 
 
 def test_clahe_grid16_batch(eng):
@@ -264,7 +264,7 @@ def test_sigma_the_device_cannot_compute_is_refused(weng, sigma):
         _no_run_open(weng, x)
         with pytest.raises(native.S2srError, match="no banded post-process open"):
             weng.pp_band_lut_dev(st)
-        _same(_banded(weng, img, native.pp_wow(), [0, 32, 64], [0, 32, 64]), pp.enhance_for_crops(img), "banded wow after a refusal")
+        _same(banded(weng, img, native.pp_wow(), [0, 32, 64], [0, 32, 64]), pp.enhance_for_crops(img), "banded wow after a refusal")
         with pytest.raises(native.S2srError, match="blur_sigma must be > 0 and < 2.75.*17 taps"):
             weng.enhance_job_u8(img[:16, :16], prm)
         _wow_still_right(weng)
@@ -286,7 +286,7 @@ def test_widest_sigma_computes_through_every_entry(weng):
     weng.postprocess_batch_u8_dev(x.data_ptr(), 1, 64, 64, prm, y.data_ptr(), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     _same(y.cpu().numpy(), want, "postprocess_batch_u8_dev")
-    _same(_banded(weng, img, prm, [0, 64], [0, 7, 64]), want, "banded")
+    _same(banded(weng, img, prm, [0, 64], [0, 7, 64]), want, "banded")
     small = img[:16, :16]
     sr = weng.enhance_job_u8(small, None)
     _same(weng.enhance_job_u8(small, prm), pp.unsharp(sr, 2.7, 2.5, -1.5), "enhance_job_u8")
@@ -315,4 +315,4 @@ def test_one_tap_kernel_still_weighs(eng, a, b):
             eng.postprocess_batch_u8_dev(x.data_ptr(), 1, H, W, prm, y.data_ptr(), torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
             _same(y.cpu().numpy(), want, what + " batch")
-            _same(_banded(eng, img, prm, [0, H], [0, 1, H], in_place=True), want, what + " banded")
+            _same(banded(eng, img, prm, [0, H], [0, 1, H], in_place=True), want, what + " banded")

@@ -6,6 +6,7 @@ make any two neighbouring pixels differ in every channel, so a value taken from 
 
 The f32 doors are held to |f * 255 - 0.5 - expectation| <= 0.13: the one rounding is the fp16 storage of u / 255 (relative
 2^-11, at most 0.1245 after the x 255), which is also why the truncating u8 door is exact (it sees u + 0.5 +- 0.125)."""
+import math
 import time
 
 import numpy as np
@@ -14,12 +15,12 @@ import pytest
 import gpu_engines
 import probe_model as pm
 from s2sr import native
-from test_gpu_u16 import TOL_F16, TOL_HP, levels
 
 pytestmark = pytest.mark.gpu
 
 F16, HP, FP8 = native.PREC_F16, native.PREC_F16_HP, native.PREC_FP8
 F32_TOL = 0.13
+TOL_F16, TOL_HP = 2.5e-3, 3e-4                     # tests/test_gpu_net.py's constants for the same nets
 CHUNKED = [(100, 90, 16, 2), (53, 200, 16, 3), (130, 37, 16, 2)]
 # geometries a door refuses: (door, H, W, tile, pad) -> the error text it must raise (none known: every geometry below runs)
 REFUSED = {}
@@ -244,10 +245,10 @@ def test_u16_door_narrow_ranges_are_exact(monkeypatch, prec):
 
 @pytest.mark.parametrize("prec,tol", [(HP, TOL_HP), (F16, TOL_F16)])
 def test_u16_door_full_range_places_every_pixel(monkeypatch, prec, tol):
-    """Full range on the u16 coded image: values within test_gpu_u16's levels(tol, 0, 65535) of the expectation; any neighbour is
+    """Full range on the u16 coded image: values within tests/test_gpu_u16.py's levels(tol, 0, 65535) of the expectation; any neighbour is
     >= 1024 levels away, so WHERE every value came from is still decided exactly."""
     tap = (2, 0)
-    bound = levels(tol, 0, 65535)
+    bound = math.ceil(tol * 65535) + 1
     assert 2 * bound < 1024
     e = gpu_engines.fresh(monkeypatch, {}, 1, prec, sd=pm.probe_state_dict(1, tap=tap, bias=0.0))
     try:

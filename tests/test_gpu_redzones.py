@@ -4,317 +4,80 @@ The parity tests read what a kernel was meant to write.  A stray vector store at
 one padded row long, lands in allocator slack or in the neighbouring workspace plane and changes no byte any of them reads.  Here
 the library's red-zone mode (include/s2sr.h s2sr_debug_redzone; csrc/redzone.h) puts Z = 65536 patterned bytes in front of and
 behind every device allocation and behind every workspace plane -- a whole padded row of these shapes is about 2 KB, so a
-row-long overrun stays inside a zone -- and each case asserts
-  (a) the bytes returned equal those of the same call on an engine without zones (the cached engines of gpu_engines.py, every
-      allocation of theirs made with the mode off), and
-  (b) redzone_check() finds no damaged zone anywhere in the process, and counts a plausible number of zoned allocations.
-The controls poke one wrong byte into a zone and must be caught, with side and offset.  The `_dev` doors write into the caller's
-memory, which the library cannot zone: torch buffers with guard bytes around the output, two fills, no byte outside may change
-and every byte inside must be written.
+row-long overrun stays inside a zone -- and each door of tests/doors.py, the table the poison and the stall module judge too, must
+  (a) return on an engine created under zones the bytes of the same call on an engine without them (diag.baseline: the cached
+      engines of gpu_engines.py with every mode off, so whatever they allocate or regrow on the way has no zones), and
+  (b) leave no damaged zone anywhere in the process, with a plausible number of zoned allocations (redzone_check()).
+Beside the matrix: the banded post-process against the whole image, the 18 files of the PNG writer in small groups, the refusals
+(16-bit input on x2plus and compact, odd tiles on x2plus) that must leave the zones clean, and fp8 calibration.  The controls poke
+one wrong byte into a zone and must be caught, with side and offset.  The `_dev` doors write into the caller's memory, which the
+library cannot zone: torch buffers with guard bytes around the output, two fills, no byte outside may change and every byte inside
+must be written."""
+import functools
 
-x2plus refuses odd tile sizes (pixel_unshuffle by 2), so its net-door cases run the listed shapes as the trunk grid: tiles of
-2 th x 2 tw.  The 16-bit doors exist on the x4 RRDB nets only; x2plus and the compact net must refuse them and stay clean."""
 import numpy as np
 import pytest
 import torch
 
-import gpu_engines
-import resample_model as rm
-from s2sr import geo, native, tiles
+import diag
+import doors
+from diag import Z, baseline, keep, new_engine, same
+from doors import CONFIGS, DOORS, FULL, NET_SHAPES, SUB, Inputs
+from s2sr import native
 
 pytestmark = pytest.mark.gpu
 
-Z = 65536
-HP, F16, FP8 = native.PREC_F16_HP, native.PREC_F16, native.PREC_FP8
-# name -> gpu_engines.default's arguments: num_block, precision, scale, arch
-CONFIGS = {"x4_hp": (1, HP, 4, "rrdb"), "x4_f16": (1, F16, 4, "rrdb"), "x4_fp8": (1, FP8, 4, "rrdb"), "x2plus": (1, HP, 2, "rrdb"),
-           "compact": (16, HP, 4, "compact")}
-# tests/test_gpu_tail.py SHAPES (B, th, tw, job_windows) and the degenerate ones
-NET_SHAPES = {"full_1x16x32": (1, 16, 32, 0), "ragged_2x37x53": (2, 37, 53, 0), "short_3x7x45": (3, 7, 45, 0),
-              "mosaic_9x20x20": (9, 20, 20, 0), "dead_7of9x20x20": (7, 20, 20, 9), "one_1x1x1": (1, 1, 1, 0), "row_1x1x9": (1, 1, 9, 0),
-              "col_1x7x1": (1, 7, 1, 0)}
-BANDED, CHUNKED = (100, 90, 16, 2), (53, 200, 16, 3)          # tests/test_gpu_u16.py, tests/test_gpu_blend.py
-IMAGES = {"banded": BANDED, "chunked": CHUNKED, "short_ramps": (39, 39, 16, 3), "untiled": (28, 36, 256, 10), "one_pixel": (1, 1, 256, 10)}
-FULL, SUB = (0, 65535), (1000, 11000)
-
-
-def _new_engine(name):
-    nb, prec, scale, arch = CONFIGS[name]
-    e = native.Engine(num_block=nb, precision=prec, scale=scale, arch=arch)
-    e.load_state_dict(gpu_engines.state_dict(nb, scale, arch))
-    return e
+clean = functools.partial(diag.clean, most=400)
 
 
 @pytest.fixture(scope="module")
 def zoned():
-    """name -> a fresh engine created (and so allocated) with Z = 65536; all closed at the end, and the zone size put back to what
-    the module found (0, or what S2SR_REDZONE set for the whole run)."""
-    before = native.redzone_bytes()
-    native.redzone(Z)
-    made = {}
-
-    def get(name):
-        if name not in made:
-            made[name] = _new_engine(name)
-        return made[name]
-    yield get
-    for e in made.values():
-        e.close()
-    native.redzone(before)
+    """name -> a fresh engine created (and so allocated) with Z = 65536"""
+    with diag.engines_under(native.redzone_bytes, native.redzone, Z) as get:
+        yield get
 
 
-def baseline(name, fn):
-    """fn(the cached engine without zones), run with the mode off: whatever it allocates or regrows on the way has no zones."""
-    native.redzone(0)
-    try:
-        return fn(gpu_engines.default(*CONFIGS[name]))
-    finally:
-        native.redzone(Z)
-
-
-def clean(e):
-    n, bad, msg = e.redzone_check()
-    assert bad == 0, msg
-    # its own: the trash page, the bias pool, at least two head / tail weight buffers ... up to some dozens with workspace planes
-    assert 4 <= n <= 400, n
-    return n
-
-
-def keep(r):
-    """results may live in the pinned pool, which the next call reuses"""
-    return tuple(np.array(a) for a in r) if isinstance(r, tuple) else np.array(r)
-
-
-def same(got, want, what):
-    got, want = (got, want) if isinstance(got, tuple) else ((got,), (want,))
-    assert len(got) == len(want)
-    for g, w in zip(got, want):
-        assert g.shape == w.shape and g.dtype == w.dtype, what
-        assert np.array_equal(g.view(np.uint8), w.view(np.uint8)), f"{what}: {int((g != w).sum())} of {g.size} elements differ with red zones"
-
-
-def both(zoned, name, fn, what):
-    """(a) and (b) for one call"""
+# ---- the door matrix -----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ident", list(DOORS))
+def test_door_under_red_zones(zoned, ident):
+    name, fn = DOORS[ident]
     e = zoned(name)
-    got = keep(fn(e))
-    same(got, baseline(name, lambda b: keep(fn(b))), f"{name} {what}")
+    same(keep(fn(e, Inputs())), baseline(ident), f"{ident}, with red zones")
     clean(e)
-    return got
-
-
-def _dev_u8(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-# ---- net doors -----------------------------------------------------------------------------------------------------------------------
-def _part(e, tiles_u8, job, scale):
-    B, th, tw, _ = tiles_u8.shape
-    x = _dev_u8(tiles_u8)
-    y = torch.zeros((B, scale * th, scale * tw, 3), dtype=torch.uint8, device="cuda")
-    e.forward_part_u8_dev(x.data_ptr(), B, th, tw, job, y.data_ptr(), torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
-
-
-@pytest.mark.parametrize("shape", list(NET_SHAPES))
-@pytest.mark.parametrize("name", list(CONFIGS))
-def test_net_doors(zoned, name, shape):
-    B, th, tw, job = NET_SHAPES[shape]
-    scale = CONFIGS[name][2]
-    if scale == 2:
-        th, tw = 2 * th, 2 * tw                      # the listed shape is the trunk grid
-    rng = np.random.default_rng(B * 10000 + th * 100 + tw)
-    t8 = rng.integers(0, 256, (B, th, tw, 3), dtype=np.uint8)
-    if job:
-        both(zoned, name, lambda e: _part(e, t8, job, scale), f"{shape} forward_part_u8_dev")
-        return
-    both(zoned, name, lambda e: e.forward_batch_u8(t8), f"{shape} forward_batch_u8")
-    x = np.ascontiguousarray(t8.transpose(0, 3, 1, 2).astype(np.float32) / np.float32(255.0))
-    both(zoned, name, lambda e: e.forward_f32(x), f"{shape} forward_f32")
-    t16 = rng.integers(0, 65536, (B, th, tw, 3)).astype(np.uint16)
-    if name.startswith("x4"):
-        for lo, hi in (FULL, SUB):
-            both(zoned, name, lambda e: e.forward_batch_u16(t16, lo, hi, want_f32=True), f"{shape} forward_batch_u16 + f32 {lo, hi}")
-            both(zoned, name, lambda e: e.forward_batch_u16(t16, lo, hi), f"{shape} forward_batch_u16 {lo, hi}")
-    else:
-        with pytest.raises(native.S2srError, match="16-bit input is not available"):
-            zoned(name).forward_batch_u16(t16)
-        clean(zoned(name))
-
-
-def test_x2plus_refuses_odd_tiles_and_stays_clean(zoned):
-    """why the x2plus cases above run doubled"""
-    with pytest.raises(native.S2srError, match="even tile sizes"):
-        zoned("x2plus").forward_batch_u8(np.zeros((1, 7, 45, 3), np.uint8))
-    clean(zoned("x2plus"))
-
-
-# ---- image doors ---------------------------------------------------------------------------------------------------------------------
-def _image(H, W, seed):
-    return np.random.default_rng(seed + 1000 * H + W).integers(0, 256, (H, W, 3), dtype=np.uint8)
-
-
-def _image_doors_u8(zoned, name, img, tile, pad, what):
-    both(zoned, name, lambda e: e.enhance_u8(img, tile=tile, pad=pad), f"{what} enhance_u8")
-    both(zoned, name, lambda e: e.enhance_f32(img, tile=tile, pad=pad), f"{what} enhance_f32")
-    both(zoned, name, lambda e: e.enhance_blend_u8(img, tile=tile, pad=pad), f"{what} enhance_blend_u8")
-    both(zoned, name, lambda e: e.enhance_blend_u8(img, tile=tile, pad=pad, want_f32=True), f"{what} enhance_blend_u8 + f32")
-    both(zoned, name, lambda e: e.enhance_job_u8(img, native.pp_wow(), tile=tile, pad=pad), f"{what} enhance_job_u8 wow")
-
-
-@pytest.mark.parametrize("case", list(IMAGES))
-def test_image_doors_x4(zoned, case):
-    H, W, tile, pad = IMAGES[case]
-    img = _image(H, W, 7)
-    _image_doors_u8(zoned, "x4_hp", img, tile, pad, case)
-    img16 = np.random.default_rng(H).integers(0, 65536, (H, W, 3)).astype(np.uint16)
-    for lo, hi in (FULL, SUB):
-        both(zoned, "x4_hp", lambda e: e.enhance_u16(img16, lo, hi, tile=tile, pad=pad), f"{case} enhance_u16 {lo, hi}")
-        both(zoned, "x4_hp", lambda e: e.enhance_blend_u16(img16, lo, hi, tile=tile, pad=pad), f"{case} enhance_blend_u16 {lo, hi}")
-    both(zoned, "x4_hp", lambda e: e.enhance_u16(img16, tile=tile, pad=pad, want_f32=True), f"{case} enhance_u16 + f32")
-    both(zoned, "x4_hp", lambda e: e.enhance_blend_u16(img16, tile=tile, pad=pad, want_f32=True), f"{case} enhance_blend_u16 + f32")
-
-
-@pytest.mark.parametrize("name", ["x4_f16", "x4_fp8", "compact"])
-def test_image_doors_other_nets(zoned, name):
-    H, W, tile, pad = CHUNKED
-    _image_doors_u8(zoned, name, _image(H, W, 8), tile, pad, "chunked")
-    _image_doors_u8(zoned, name, _image(39, 39, 8), 16, 3, "short_ramps")
-
-
-def test_image_doors_x2plus_odd_image(zoned):
-    """39 x 39 at scale 2: the reflect-padded 40 x 40 image, tiled and untiled, output cropped by the stitch maps"""
-    img = _image(39, 39, 9)
-    _image_doors_u8(zoned, "x2plus", img, 16, 3, "x2plus 39x39 tiled")
-    _image_doors_u8(zoned, "x2plus", img, 256, 10, "x2plus 39x39 untiled")
-    _image_doors_u8(zoned, "x2plus", _image(3, 3, 9), 256, 10, "x2plus 3x3")       # the smallest odd image: 2 x 2 is the entry's minimum
-
-
-# ---- post-process --------------------------------------------------------------------------------------------------------------------
-def _pp(grid, sigma=1.2):
-    return native.PPParams(2.5, grid, sigma, 1.4, -0.4, 35, 85, 1.2, 7)
 
 
 @pytest.mark.parametrize("grid", [8, 16])
-@pytest.mark.parametrize("H,W", [(1, 1), (3, 300), (70, 101)])
-def test_postprocess(zoned, H, W, grid):
-    img = _image(H, W, 10)
-    img[..., 1] = np.maximum(img[..., 1], 90)
-    both(zoned, "x4_hp", lambda e: e.postprocess_u8(img, _pp(grid)), f"postprocess_u8 {H}x{W} grid {grid}")
-
-
-def _banded(e, img, prm, step, fill=0x5A, after_band=None):
-    H, W, _ = img.shape
-    x = _dev_u8(img)
-    y = torch.full_like(x, fill)
-    st = torch.cuda.current_stream().cuda_stream
-    e.pp_band_begin_dev(H, W, prm, 0, st)
-    for a in range(0, H, step):
-        e.pp_band_hist_dev(x.data_ptr(), a, min(a + step, H), st)
-    e.pp_band_lut_dev(st)
-    for a in range(0, H, step):
-        e.pp_band_rows_dev(x.data_ptr(), a, min(a + step, H), y.data_ptr(), st)
-        if after_band:
-            torch.cuda.synchronize()
-            after_band(min(a + step, H), y)
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
-
-
-def test_postprocess_in_bands_of_five_rows(zoned):
+def test_postprocess_in_bands_of_five_rows_is_the_whole_image(grid):
     """70 x 101 in bands of 5 rows with the widest Gaussian the entries accept (sigma < 2.75: 17 taps, 8 rows of look-ahead,
-    more than a band)"""
-    img = _image(70, 101, 11)
-    img[..., 1] = np.maximum(img[..., 1], 90)
-    for grid in (8, 16):
-        prm = _pp(grid, sigma=2.7)
-        got = both(zoned, "x4_hp", lambda e: _banded(e, img, prm, 5), f"banded post-process, grid {grid}")
-        same(got, baseline("x4_hp", lambda b: keep(b.postprocess_u8(img, prm))), "banded against the whole image")
+    more than a band): the two doors run on one image"""
+    same(baseline(f"pp_band_sequence-70x101-grid{grid}_wide"), baseline(f"postprocess_u8-70x101-grid{grid}_wide"), "banded against the whole image")
 
 
-# ---- pyramid -------------------------------------------------------------------------------------------------------------------------
-def _scene(h, w, seed=0):
-    rng = np.random.default_rng(seed)
-    yy, xx = np.mgrid[0:h, 0:w]
-    img = np.stack([120 + 90 * np.sin(xx / 11.0 + c) * np.cos(yy / 7.0) + rng.integers(-15, 16, (h, w)) for c in range(3)], -1)
-    return np.clip(img, 0, 255).astype(np.uint8)
+def test_tile_pngs_in_small_groups_are_18_files(zoned):
+    """the 5 x 4 level has one transparent tile and one without a path"""
+    wrote, *files = DOORS["tiles_write_png-small_groups_5x4"][1](zoned("x4_hp"), Inputs())
+    assert wrote.sum() == 18 and sum(f.size > 0 for f in files) == 18
+    assert not wrote[1, 2] and not wrote[3, 0]
+    clean(zoned("x4_hp"))
 
 
-def test_warp(zoned):
-    rgb = _scene(150, 211, seed=32633)
-    plan = tiles.plan_warp(211, 150, geo.Placement(600000.0, 5100000.0, 2.5, 2.5), geo.CRS(32633))
-    both(zoned, "x4_hp", lambda e: e.warp_bilinear_u8(rgb, plan.grid, plan.step, plan.out_h, plan.out_w), "warp 150x211")
+# ---- the refusals --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", [s for s, (_, _, _, job) in NET_SHAPES.items() if not job])
+@pytest.mark.parametrize("name", ["x2plus", "compact"])
+def test_16_bit_input_is_refused_off_the_x4_nets_and_the_zones_stay_clean(zoned, name, shape):
+    B, th, tw, _ = NET_SHAPES[shape]
+    if CONFIGS[name][2] == 2:
+        th, tw = 2 * th, 2 * tw                      # the listed shape is the trunk grid
+    with pytest.raises(native.S2srError, match="16-bit input is not available"):
+        zoned(name).forward_batch_u16(Inputs().u16((B, th, tw, 3), B + th))
+    clean(zoned(name))
 
 
-def test_base_and_two_overviews(zoned):
-    rng = np.random.default_rng(9)
-    rgba = np.concatenate([_scene(300, 420, seed=2), np.full((300, 420, 1), 255, np.uint8)], -1)
-    rgba[..., 3] = np.where(rng.random((300, 420)) < 0.15, 0, 255)
-    place = geo.Placement(1500017.3, 5999994.9, 3.1, 3.1)
-    levels = tiles.plan_levels(place.bounds(420, 300), 12, 15)[:3]
-    assert len(levels) == 3
-
-    def run(e):
-        out = [e.tiles_base_u8(rgba, *tiles.plan_base(levels[0], place, 420, 300))]
-        for k in (1, 2):                            # the first from the host copy, the second from the level left on the device
-            ox, oy = tiles.overview_offsets(levels[k], levels[k - 1])
-            out.append(e.tiles_overview_u8(out[-1], ox, oy, levels[k].nx, levels[k].ny, on_device=(k == 2)))
-        return tuple(out)
-    both(zoned, "x4_hp", run, "base + two overviews of 300x420")
-
-
-@pytest.mark.parametrize("filt", tiles.FILTERS)
-def test_resample_overzoom(zoned, filt):
-    box = (-3.7, -46.0, -3.7 + 512 / 9.0, 38.1)     # tests/test_gpu_resample.py OVERZOOM
-    cols = tiles.plan_resample_axis(2 * 256, box[0], box[2], rm.W, filt)
-    rows = tiles.plan_resample_axis(2 * 256, box[1], box[3], rm.H, filt)
-    src = rm.source()
-    both(zoned, "x4_hp", lambda e: e.tiles_resample_u8(src, cols, rows, 2, 2), f"over-zoom {filt}")
-
-
-def test_tile_pngs_in_small_groups(zoned, tmp_path):
-    """The 5 x 4 level of test_gpu_tiles.test_tile_png_groups_pipeline_writes_the_same_files in groups of 3 tiles: the stream
-    buffers regrow between groups, so zoned buffers are freed -- and checked -- while the call runs."""
-    rng = np.random.default_rng(23)
-    H, W = 4 * 256, 5 * 256
-    yy, xx = np.mgrid[0:H, 0:W]
-    rgba = np.empty((H, W, 4), np.uint8)
-    rgba[..., :3] = np.clip(120 + 80 * np.sin(xx / 37.0)[..., None] * np.cos(yy / 23.0)[..., None] + rng.integers(-4, 5, (H, W, 3)), 0, 255)
-    rgba[256:512, 512:768, :3] = rng.integers(0, 256, (256, 256, 3))
-    rgba[..., 3] = 255
-    rgba[768:, :256, 3] = 0
-    rgba[:128, 1024:, 3] = 0
-    iy, ix = np.arange(H, dtype=np.int32), np.arange(W, dtype=np.int32)
-
-    def run(e, sub):
-        e.tiles_base_u8(rgba, ix, ix, iy, iy, fetch=False)
-        paths = [tmp_path / sub / f"{j}_{i}.png" for j in range(4) for i in range(5)]
-        paths[7] = None
-        wrote = e.tiles_write_png(5, 4, paths, small_groups=True)
-        return wrote.copy(), [None if q is None or not q.exists() else q.read_bytes() for q in paths]
-    e = zoned("x4_hp")
-    wrote, files = run(e, "zoned")
-    wrote0, files0 = baseline("x4_hp", lambda b: run(b, "plain"))
-    assert np.array_equal(wrote, wrote0) and files == files0 and sum(f is not None for f in files) == 18
-    clean(e)
-
-
-# ---- display -------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("H,W,band_rows", [(37, 53, 7), (255, 257, 0)])
-def test_display(zoned, H, W, band_rows):
-    lut = np.random.default_rng(99).integers(0, 256, size=(3, 65536), dtype=np.uint8)
-    img = np.random.default_rng(H).integers(0, 65536, (H, W, 3)).astype(np.uint16)
-    both(zoned, "x4_hp", lambda e: e.display_hist_u16(img, band_rows=band_rows), f"display_hist_u16 {H}x{W}")
-    both(zoned, "x4_hp", lambda e: e.display_hist_u16(img, nodata=int(img[0, 0, 0]), band_rows=band_rows), f"display_hist_u16 nodata {H}x{W}")
-    both(zoned, "x4_hp", lambda e: e.display_apply_u16(img, lut, band_rows=band_rows), f"display_apply_u16 {H}x{W}")
-
-    def behind_enhance(e):                          # the device copy enhance_u16 leaves: 4H x 4W
-        with e.chain_lock:
-            q = keep(e.enhance_u16(img))
-            h = e.display_hist_u16(None, band_rows=band_rows, shape=(4 * H, 4 * W))
-            a = e.display_apply_u16(None, lut, band_rows=band_rows, shape=(4 * H, 4 * W))
-        return q, h, a
-    both(zoned, "x4_hp", behind_enhance, f"display behind enhance_u16 {H}x{W}")
+def test_x2plus_refuses_odd_tiles_and_stays_clean(zoned):
+    """why the x2plus net doors run doubled"""
+    with pytest.raises(native.S2srError, match="even tile sizes"):
+        zoned("x2plus").forward_batch_u8(np.zeros((1, 7, 45, 3), np.uint8))
+    clean(zoned("x2plus"))
 
 
 # ---- calibration ---------------------------------------------------------------------------------------------------------------------
@@ -322,10 +85,10 @@ def test_calibrate_fp8(zoned):
     """engines of their own on both sides: a calibration changes the scales of the handle it runs on"""
     t8 = np.random.default_rng(5).integers(0, 256, (2, 37, 53, 3), dtype=np.uint8)
     zoned("x4_hp")                                  # the mode is on
-    e = _new_engine("x4_fp8")
+    e = new_engine("x4_fp8")
     native.redzone(0)
     try:
-        b = _new_engine("x4_fp8")
+        b = new_engine("x4_fp8")
         try:
             want = b.calibrate_fp8(t8), keep(b.forward_batch_u8(t8))
             assert b.redzone_check()[:2] == (0, 0)  # nothing of the plain engine's has zones
@@ -375,7 +138,7 @@ def test_with_the_mode_off_nothing_is_zoned(zoned):
     e0 = zoned("x4_hp")
     native.redzone(0)
     try:
-        e = _new_engine("x4_hp")
+        e = new_engine("x4_hp")
         try:
             e.enhance_u16(np.zeros((39, 39, 3), np.uint16), tile=16, pad=3)
             for slot in range(6):
@@ -391,7 +154,7 @@ def test_with_the_mode_off_nothing_is_zoned(zoned):
     for bad in (1, 4095, 65536 + 512):
         with pytest.raises(native.S2srError):
             native.redzone(bad)
-    e0.enhance_u8(_image(20, 20, 1))                              # a refused size changed nothing: still Z
+    e0.enhance_u8(Inputs().u8((20, 20, 3), 1))                             # a refused size changed nothing: still Z
     clean(e0)
 
 
@@ -421,7 +184,7 @@ def test_caller_owned_output_u8(zoned, name, B, th, tw):
         th, tw = 2 * th, 2 * tw
     t8 = np.random.default_rng(B + th).integers(0, 256, (B, th, tw, 3), dtype=np.uint8)
     exp = keep(e.forward_batch_u8(t8))
-    x = _dev_u8(t8)
+    x = doors._dev_u8(t8)
     st = torch.cuda.current_stream().cuda_stream
     per = S * S * th * tw * 3
     part = 2 if B > 2 else 1
@@ -469,7 +232,7 @@ def test_caller_owned_output_postprocess_batch(zoned):
     B, H, W = 3, 35, 203
     imgs = np.random.default_rng(12).integers(0, 256, (B, H, W, 3), dtype=np.uint8)
     imgs[..., 1] = np.maximum(imgs[..., 1], 90)
-    x = _dev_u8(imgs)
+    x = doors._dev_u8(imgs)
     for prm in (native.pp_wow(), native.pp_farm()):
         exp = np.stack([keep(e.postprocess_u8(imgs[i], prm)) for i in range(B)])
         for fill in FILLS:
@@ -485,13 +248,12 @@ def test_caller_owned_output_pp_band_rows(zoned):
     """band by band into a filled whole image: after each band the rows not yet written still hold the fill"""
     e = zoned("x4_hp")
     H, W = 70, 101
-    img = _image(H, W, 13)
-    img[..., 1] = np.maximum(img[..., 1], 90)
+    img = Inputs().green((H, W, 3), 13)
     row = W * 3
-    for prm in (native.pp_wow(), _pp(16, sigma=2.7)):
+    for prm in (native.pp_wow(), doors._pp(16, sigma=2.7)):
         exp = keep(e.postprocess_u8(img, prm))
         for fill in FILLS:
-            x = _dev_u8(img)
+            x = doors._dev_u8(img)
             buf, out = _guarded(img.nbytes, fill)
             st = torch.cuda.current_stream().cuda_stream
             e.pp_band_begin_dev(H, W, prm, 0, st)

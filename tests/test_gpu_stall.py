@@ -7,9 +7,10 @@ two calls on one handle that run on different streams?  A missing or mis-indexed
 timing, where the producer happens to be done in time.  The library's stall mode (include/s2sr.h s2sr_debug_delay; csrc/stall.hip,
 the wrappers of csrc/engine_internal.h) holds one side back with a kernel that only lets time pass, at the head of every stream
 segment, so the producer is provably late; poison and a saturated predecessor make the stale bytes provably different.
-  (a) every door of tests/doors.py, on a real side stream, with the compute side stalled (mode 1) and the copy side (mode 2),
-      returns byte for byte what the un-stalled call returns on the cached engine; net doors in three sightings (direct launches,
-      the graph capture, a replay); the workspace counter does not move.
+  (a) every door of tests/doors.py (the table the red-zone and the poison module judge too), on a real side stream, with the
+      compute side stalled (mode 1) and the copy side (mode 2), returns byte for byte what the call returns on the cached engine
+      with every mode off (diag.baseline); net doors in three sightings (direct launches, the graph capture, a replay); the
+      workspace counter does not move.
   (b) the *_dev doors as stream citizens: input arriving late on the caller's stream from pinned memory, an in-stream consumer,
       a stream synchronise only -- no device-wide synchronise anywhere.
   (c) two calls on one handle, two streams, nothing in between, timed so that they overlap.
@@ -30,12 +31,12 @@ import numpy as np
 import pytest
 import torch
 
+import diag
 import doors
 import gpu_engines
-import test_gpu_redzones as rz
+from diag import baseline, keep, same
 from doors import DOORS, FILL, Inputs
 from s2sr import native
-from test_gpu_poison import baseline, same
 
 pytestmark = pytest.mark.gpu
 
@@ -46,21 +47,18 @@ CONFIGS, NET_SHAPES, IMAGES, SUB = doors.CONFIGS, doors.NET_SHAPES, doors.IMAGES
 
 @pytest.fixture(scope="module")
 def stalled():
-    """name -> an engine created under poison pattern 2 (so poison_scratch() is allowed); all closed at the end, and the three
-    modes put back to what the module found."""
-    poison, (mode, usec), dropped = native.poison_pattern(), native.delay_mode(), native.delay_dropped()
-    made = {}
-
-    def get(name):
-        if name not in made:
-            native.poison(2)
-            made[name] = e = rz._new_engine(name)
-            assert _beside(e, (0, 0), (1, 0)) and _beside(e, (1, 0), (0, 0)), f"{name}: the engine's stream and its copy stream share a hardware queue"
-        return made[name]
-    yield get
-    for e in made.values():
-        e.close()
-    native.poison(poison)
+    """name -> an engine created under poison pattern 2 (so poison_scratch() is allowed), its two streams probed; at the end the
+    three modes are put back to what the module found."""
+    (mode, usec), dropped = native.delay_mode(), native.delay_dropped()
+    probed = set()
+    with diag.engines_under(native.poison_pattern, native.poison) as made:
+        def get(name):
+            e = made(name, 2)
+            if name not in probed:
+                probed.add(name)
+                assert _beside(e, (0, 0), (1, 0)) and _beside(e, (1, 0), (0, 0)), f"{name}: the engine's stream and its copy stream share a hardware queue"
+            return e
+        yield get
     native.delay_drop(dropped)
     native.delay(mode, usec)
 
@@ -139,7 +137,7 @@ def test_door_under_stalls(stalled, side, ident, mode):
         native.delay(mode, STALL_USEC)
         try:
             with torch.cuda.stream(side):
-                got = rz.keep(fn(e, Inputs()))
+                got = keep(fn(e, Inputs()))
         finally:
             native.delay(0)
         same(got, want, f"{ident}, mode {mode}, sighting {k + 1}")
@@ -261,7 +259,7 @@ def test_postprocess_dev_doors_are_stream_citizens(stalled, side):
         return y
     same(_citizen(side, batch), baseline(f"postprocess_batch_u8_dev-{H}x{W}-wow"), "postprocess_batch_u8_dev")
 
-    def bands():                                                        # rz._banded, on the side stream and without its synchronise
+    def bands():                                                        # doors._banded, on the side stream and without its synchronise
         x, _keep = _late(e, side, Inputs().green((H, W, 3), 11))
         y = torch.full_like(x, FILL)
         st = side.cuda_stream
@@ -323,14 +321,10 @@ PAIR_SHAPE = (8, 64, 64, 3)
 
 def _ref(fn):
     """fn(the cached engine) alone, everything synchronised before and after"""
-    now = native.poison_pattern()
-    native.poison(0)
-    try:
+    with diag.modes_off():
         torch.cuda.synchronize()
-        r = rz.keep(fn(gpu_engines.default(*CONFIGS["x4_hp"])))
+        r = keep(fn(gpu_engines.default(*CONFIGS["x4_hp"])))
         torch.cuda.synchronize()
-    finally:
-        native.poison(now)
     return r
 
 
@@ -357,14 +351,14 @@ def test_pair_forward_u8_dev_then_forward_u8(stalled, side):
     B, th, tw, _ = PAIR_SHAPE
     t1, t2 = Inputs().u8(PAIR_SHAPE, 1), Inputs().u8(PAIR_SHAPE, 2)
     want1, want2 = _ref(lambda b: b.forward_batch_u8(t1)), _ref(lambda b: b.forward_batch_u8(t2))
-    x1, y1 = rz._dev_u8(t1), doors._out((B, 4 * th, 4 * tw, 3))
+    x1, y1 = doors._dev_u8(t1), doors._out((B, 4 * th, 4 * tw, 3))
     for k in range(3):                                                  # direct launches, the capture, a replay
         y1.fill_(FILL)
         torch.cuda.synchronize()
         e.stall(2, PAIR_T, side.cuda_stream)
         e.stall(0, PAIR_T + PAIR_LEAD)
         e.forward_batch_u8_dev(x1.data_ptr(), B, th, tw, y1.data_ptr(), side.cuda_stream)
-        got2 = rz.keep(e.forward_batch_u8(t2))
+        got2 = keep(e.forward_batch_u8(t2))
         side.synchronize()
         same(y1.cpu().numpy(), want1, f"the *_dev call on the side stream, sighting {k + 1}")
         same(got2, want2, f"the host-facing call behind it, sighting {k + 1}")
@@ -376,7 +370,7 @@ def test_pair_forward_u8_dev_on_two_streams(stalled, side, other):
     B, th, tw, _ = PAIR_SHAPE
     t1, t2 = Inputs().u8(PAIR_SHAPE, 3), Inputs().u8(PAIR_SHAPE, 4)
     want1, want2 = _ref(lambda b: b.forward_batch_u8(t1)), _ref(lambda b: b.forward_batch_u8(t2))
-    x1, x2 = rz._dev_u8(t1), rz._dev_u8(t2)
+    x1, x2 = doors._dev_u8(t1), doors._dev_u8(t2)
     y1, y2 = doors._out((B, 4 * th, 4 * tw, 3)), doors._out((B, 4 * th, 4 * tw, 3))
     for k in range(3):
         y1.fill_(FILL), y2.fill_(FILL)
@@ -406,7 +400,7 @@ def test_pair_forward_u16_dev_then_forward_u16(stalled, side):
         e.stall(2, PAIR_T, side.cuda_stream)
         e.stall(0, PAIR_T + PAIR_LEAD)
         e.forward_batch_u16_dev(x1.data_ptr(), B, th, tw, y1.data_ptr(), *SUB, stream=side.cuda_stream)
-        got2 = rz.keep(e.forward_batch_u16(t2, *SUB))
+        got2 = keep(e.forward_batch_u16(t2, *SUB))
         side.synchronize()
         same(y1.cpu().numpy().view(np.uint16), want1, f"the *_dev call on the side stream, sighting {k + 1}")
         same(got2, want2, f"the host-facing call behind it, sighting {k + 1}")
@@ -421,13 +415,13 @@ def test_pair_postprocess_dev_then_postprocess_u8(stalled, side):
     H, W, prm = 512, 512, native.pp_wow()
     i1, i2 = Inputs().green((1, H, W, 3), 7), Inputs().green((H, W, 3), 8)
     want1, want2 = _ref(lambda b: b.postprocess_u8(i1[0], prm)), _ref(lambda b: b.postprocess_u8(i2, prm))
-    x1, y1 = rz._dev_u8(i1), doors._out((1, H, W, 3))
+    x1, y1 = doors._dev_u8(i1), doors._out((1, H, W, 3))
     e.postprocess_u8(i2, prm)                                           # scratch at its sizes
     torch.cuda.synchronize()
     e.stall(2, PAIR_T, side.cuda_stream)
     e.stall(0, PAIR_T + PAIR_LEAD // 3)                                 # a post-process of 512 x 512 is short
     e.postprocess_batch_u8_dev(x1.data_ptr(), 1, H, W, prm, y1.data_ptr(), side.cuda_stream)
-    got2 = rz.keep(e.postprocess_u8(i2, prm))
+    got2 = keep(e.postprocess_u8(i2, prm))
     side.synchronize()
     same(y1.cpu().numpy()[0], want1, "the *_dev call on the side stream")
     same(got2, want2, "the host-facing call behind it")
@@ -442,12 +436,12 @@ def test_pair_cut_windows_dev_on_two_streams(stalled, side, other):
     i1, i2 = Inputs().u8((H, W, 3), 9), Inputs().u8((H, W, 3), 10)
 
     def cut(b, img, st):
-        x, buf = rz._dev_u8(img), doors._out((T, wh, ww, 3))
+        x, buf = doors._dev_u8(img), doors._out((T, wh, ww, 3))
         b.cut_windows_u8_dev(x.data_ptr(), H, W, tile, pad, 0, T, buf.data_ptr(), st.cuda_stream)
         return x, buf
     want = [_ref(lambda b, i=i: doors._back(cut(b, i, torch.cuda.current_stream())[1])) for i in (i1, i2)]
     torch.cuda.synchronize()
-    x1, x2 = rz._dev_u8(i1), rz._dev_u8(i2)
+    x1, x2 = doors._dev_u8(i1), doors._dev_u8(i2)
     b1, b2 = doors._out((T, wh, ww, 3)), doors._out((T, wh, ww, 3))
     torch.cuda.synchronize()
     e.stall(2, PAIR_T, side.cuda_stream)
@@ -467,11 +461,11 @@ def test_pair_stitch_rows_dev_then_stitch_windows_dev(stalled, side, other):
     t1, t2 = Inputs().u8((T, 4 * wh, 4 * ww, 3), 11), Inputs().u8((T, 4 * wh, 4 * ww, 3), 12)
 
     def whole(b, tiles_u8):
-        d, out = rz._dev_u8(tiles_u8), doors._out((4 * H, 4 * W, 3))
+        d, out = doors._dev_u8(tiles_u8), doors._out((4 * H, 4 * W, 3))
         b.stitch_windows_u8_dev(d.data_ptr(), H, W, tile, pad, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         return doors._back(out)
     want1, want2 = _ref(lambda b: whole(b, t1)), _ref(lambda b: whole(b, t2))
-    d1, d2 = rz._dev_u8(t1), rz._dev_u8(t2)
+    d1, d2 = doors._dev_u8(t1), doors._dev_u8(t2)
     o1, o2 = doors._out((4 * H, 4 * W, 3)), doors._out((4 * H, 4 * W, 3))
     torch.cuda.synchronize()
     e.stall(2, PAIR_T, side.cuda_stream)
@@ -498,16 +492,16 @@ def _control(e, site, call, want, what):
     native.delay(1, STALL_USEC)
     native.delay_drop(site)
     try:
-        got = rz.keep(call())
+        got = keep(call())
     finally:
         native.delay_drop(-1)
     assert _differs(got, want), f"{what}: the wait of site {site} was dropped and nobody noticed"
     try:
-        again = rz.keep(call())
+        again = keep(call())
     finally:
         native.delay(0)
     same(again, want, f"{what}, the wait restored")
-    same(rz.keep(call()), want, f"{what}, the mode off")
+    same(keep(call()), want, f"{what}, the mode off")
 
 
 def test_control_batch_group_wait(stalled):

@@ -105,22 +105,6 @@ def test_enhance_ragged_and_odd_vs_model(hw, tile):
 
 
 # ---- 4. the head in situ ------------------------------------------------------------------------------------------------------
-def _expected_p0(tiles, geo):
-    """The unshuffled integers at the positions the packer writes (plain images or a mosaic), zeros everywhere else."""
-    B, th, tw, _ = tiles.shape
-    n, Hp, Wp = geo["n"], geo["Hp"][0], geo["Wp"][0]
-    p0 = np.zeros((n, 16, Hp, Wp), np.float64)
-    un = torch.nn.functional.pixel_unshuffle(torch.from_numpy(tiles.transpose(0, 3, 1, 2).astype(np.float64)), 2).numpy()
-    kx, ky = (geo["mos_kx"], geo["mos_ky"]) if geo["mos_kx"] else (1, 1)
-    h, w = th // 2, tw // 2
-    for t in range(B):
-        i, slot = divmod(t, kx * ky)
-        wy, wx = divmod(slot, kx)
-        y0, x0 = 1 + wy * (h + 1), 1 + wx * (w + 1)
-        p0[i, :12, y0:y0 + h, x0:x0 + w] = un[t]
-    return p0
-
-
 @pytest.mark.parametrize("prec", [HP, FAST])
 @pytest.mark.parametrize("B,th,tw", [(1, 24, 32), (5, 40, 44)])
 def test_head_in_situ(prec, B, th, tw):
@@ -130,7 +114,7 @@ def test_head_in_situ(prec, B, th, tw):
     assert ou8.shape == (B, 2 * th, 2 * tw, 3) and of32.shape == (B, 3, 2 * th, 2 * tw)
     if B > 1:
         assert geo["mos_kx"] * geo["mos_ky"] >= 2 and (geo["mos_wh"], geo["mos_ww"]) == (th // 2, tw // 2)
-    p0 = _expected_p0(tiles, geo)
+    p0 = xm.expected_p0(tiles, geo)
     bad = taps["P0"] != p0
     assert not bad.any(), f"P0: {int(bad.sum())} elements differ (first at {np.argwhere(bad)[0].tolist()})"
     sd = _sd(1)

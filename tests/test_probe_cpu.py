@@ -11,8 +11,6 @@ import probe_model as pm
 import x2plus_model as xm
 from oracle import rrdbnet_ref as ref
 
-# the plans of tests/test_gpu_cut_stitch.py (those of test_cut_forward_stitch_equals_enhance): H, W, tile, pad
-STITCH_GEOS = [(37, 45, 16, 2), (50, 41, 16, 2), (64, 65, 32, 4), (33, 70, 16, 3), (49, 48, 16, 2), (70, 36, 32, 2)]
 REPLAY_TILE_PADS = [(16, 1), (16, 2), (16, 3), (32, 4)]
 REPLAY_TAPS = [(1, 1), (0, 0), (2, 2)]
 
@@ -134,7 +132,7 @@ def test_oracle_tile_process_on_a_duplicate_window_plan():
 def test_power_of_the_stitch_inputs(scale):
     """On the window-coded tiles of tests/test_gpu_cut_stitch.py a 'first covering window wins' paste and a paste with each crop
     moved by one output pixel both differ from the true paste, on every geometry that test uses."""
-    for H, W, t, p in STITCH_GEOS:
+    for H, W, t, p in pm.STITCH_GEOS:
         PH, PW = (H + H % 2, W + W % 2) if scale == 2 else (H, W)
         plan = ref.tile_plan(PH, PW, t, p, scale)
         (y1, y2, x1, x2) = plan[0][0]
@@ -149,9 +147,8 @@ def test_power_of_the_stitch_inputs(scale):
 
 def test_f32_packing_rule_in_the_scale_2_channel_order():
     """fp16(fp32(x * 255)), as tests/test_compact_insitu_cpu.py models it, laid out as the scale-2 packer lays it out: on u8-grid
-    input it is test_gpu_x2plus._expected_p0 (the integers), and the known tie value lands as 55.75 in its unshuffled channel."""
+    input it is x2plus_model.expected_p0 (the integers), and the known tie value lands as 55.75 in its unshuffled channel."""
     import compact_insitu as ci
-    import test_gpu_x2plus as gx
     x1 = np.array([0.21868873], np.float32)
     assert float(pm.pack_f32_rule(x1)[0]) == 55.75 and float((x1.astype(np.float64) * 255.0).astype(np.float16)[0]) == 55.78125
     rng = np.random.default_rng(3)
@@ -163,7 +160,7 @@ def test_f32_packing_rule_in_the_scale_2_channel_order():
                            (5, 6, 8, {"n": 2, "Hp": [9], "Wp": [11], "mos_kx": 2, "mos_ky": 2})]:
         tiles = rng.integers(0, 256, (B, th, tw, 3), dtype=np.uint8)
         x = np.ascontiguousarray((tiles.astype(np.float32) / np.float32(255.0)).transpose(0, 3, 1, 2))
-        _same(pm.expected_p0_f32(x, geo, 2), gx._expected_p0(tiles, geo).astype(np.float32), ("scale 2", B))
+        _same(pm.expected_p0_f32(x, geo, 2), xm.expected_p0(tiles, geo).astype(np.float32), ("scale 2", B))
     x = np.full((1, 3, 2, 2), 0.5, np.float32)
     x[0, 1, 1, 0] = x1[0]                                     # colour 1, sub-pixel (1, 0): channel 1*4 + 1*2 + 0
     p0 = pm.expected_p0_f32(x, {"n": 1, "Hp": [3], "Wp": [3], "mos_kx": 0, "mos_ky": 0}, 2)

@@ -5,7 +5,7 @@ import pytest
 
 from s2sr import rasterio_lite as rio
 from s2sr import tiff_lite
-from test_tiff_cpu import _write_tiff
+from tiff_fixture import write_tiff
 
 GEO = {rio.TAG_PIXEL_SCALE: (10.0, 10.0, 0.0),
        rio.TAG_TIEPOINT: (0.0, 0.0, 0.0, 500000.0, 4000000.0, 0.0),
@@ -60,7 +60,7 @@ def test_read_rgb_raw_returns_the_stored_values(tmp_path):
     for B in (3, 4, 1):
         a = rng.integers(0, 65536, (21, 34, B), dtype=np.uint16)
         p = tmp_path / f"b{B}.tif"
-        _write_tiff(p, a, extra=geo)
+        write_tiff(p, a, extra=geo)
         raw, g = rio.read_rgb_raw(p)
         assert raw.dtype == np.uint16 and raw.shape == (21, 34, 3) and raw.flags["C_CONTIGUOUS"]
         want = a[..., :3] if B >= 3 else np.repeat(a, 3, axis=2)

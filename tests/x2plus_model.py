@@ -51,3 +51,19 @@ def enhance_float(img_u8: np.ndarray, sd, num_block: int, tile_size: int = 256, 
 def enhance(img_u8: np.ndarray, sd, num_block: int, tile_size: int = 256, tile_pad: int = 10) -> np.ndarray:
     """`RealESRGAN.enhance` at scale 2: HxWx3 u8 -> 2Hx2Wx3 u8 (truncating quantisation)."""
     return (enhance_float(img_u8, sd, num_block, tile_size, tile_pad) * 255.0).clip(0, 255).astype(np.uint8)
+
+
+def expected_p0(tiles, geo):
+    """The unshuffled integers at the positions the packer writes (plain images or a mosaic), zeros everywhere else."""
+    B, th, tw, _ = tiles.shape
+    n, Hp, Wp = geo["n"], geo["Hp"][0], geo["Wp"][0]
+    p0 = np.zeros((n, 16, Hp, Wp), np.float64)
+    un = torch.nn.functional.pixel_unshuffle(torch.from_numpy(tiles.transpose(0, 3, 1, 2).astype(np.float64)), 2).numpy()
+    kx, ky = (geo["mos_kx"], geo["mos_ky"]) if geo["mos_kx"] else (1, 1)
+    h, w = th // 2, tw // 2
+    for t in range(B):
+        i, slot = divmod(t, kx * ky)
+        wy, wx = divmod(slot, kx)
+        y0, x0 = 1 + wy * (h + 1), 1 + wx * (w + 1)
+        p0[i, :12, y0:y0 + h, x0:x0 + w] = un[t]
+    return p0
