@@ -556,21 +556,27 @@ bool recover_stream(s2sr_handle* h) {
     return true;
 }
 
-int ensure_scratch(s2sr_handle* h, int slot, size_t bytes) {
-    h->tiles_slot = -1;                  // whoever asks for scratch is about to overwrite it; the pyramid calls set it again
-    h->warp_slot = -1;
-    h->disp_slot = -1;
-    if (slot == 5) h->ppb.open = false;  // ... and a banded post-process run lives there: void it (pp_band_begin_locked opens its own afterwards)
-    if (h->scratch_bytes[slot] >= bytes) return S2SR_OK;
-    if (h->d_scratch[slot]) {
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        drop_graphs(h);
-        HIPCHK(h, dev_free(h->d_scratch[slot]));
-        h->d_scratch[slot] = nullptr;
-        h->scratch_bytes[slot] = 0;
+// The HIP side of slots::Book::request.  A slot that has to move: the handle's stream drains, the graphs that hold its address go.
+static int scratch_alloc(void* ctx, void** p, size_t bytes) {
+    s2sr_handle* h = (s2sr_handle*)ctx;
+    HIPCHK(h, dev_malloc(p, bytes));
+    return S2SR_OK;
+}
+static int scratch_release(void* ctx, void* p) {
+    s2sr_handle* h = (s2sr_handle*)ctx;
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    drop_graphs(h);
+    HIPCHK(h, dev_free(p));
+    return S2SR_OK;
+}
+int ensure_scratch(s2sr_handle* h, std::initializer_list<Want> wants) {
+    const slots::DeviceMem mem{scratch_alloc, scratch_release, h};
+    for (const Want& w : wants) {
+        if (!w.on) continue;
+        const int rc = h->scratch.request(mem, w.slot, w.bytes);
+        if (rc == slots::kTakenRegrow) return fail(h, S2SR_E_INVALID, "a scratch request would move the slot this call reads the previous call's result from");
+        if (rc) return rc;
     }
-    HIPCHK(h, dev_malloc(&h->d_scratch[slot], bytes));
-    h->scratch_bytes[slot] = bytes;
     return S2SR_OK;
 }
 
@@ -989,11 +995,7 @@ void s2sr_destroy(s2sr_handle* h) {
     hipSetDevice(h->cfg.device);
     dev_sync();
     drop_graphs(h);
-    free_weights(h);
-    if (h->ws.base) dev_free(h->ws.base);
-    if (h->d_trash) dev_free(h->d_trash);
-    for (int i = 0; i < s2sr_handle::kScratchSlots; ++i)
-        if (h->d_scratch[i]) dev_free(h->d_scratch[i]);
+    for_each_device_buffer(h, [](void* p) { if (p) dev_free(p); });
     for (EvRec& r : h->evs) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
     for (hipEvent_t e : h->ev_pool) hipEventDestroy(e);
     for (hipEvent_t e : h->group_done) hipEventDestroy(e);
@@ -1001,8 +1003,6 @@ void s2sr_destroy(s2sr_handle* h) {
         if (h->stage_buf[i]) host_free(h->stage_buf[i]);
         if (h->stage_ev[i]) hipEventDestroy(h->stage_ev[i]);
     }
-    for (auto& m : h->stitch_sets)
-        if (m.d) dev_free(m.d);
     if (h->host_arena) host_free(h->host_arena);
     if (h->host_copy_ev) hipEventDestroy(h->host_copy_ev);
     if (h->order_ev) hipEventDestroy(h->order_ev);
@@ -1257,11 +1257,9 @@ static int forward_batch_u8_once(s2sr_handle* h, const uint8_t* tiles, int32_t B
     DOOR_ENTER(h, h->stream);
     const int S = h->cfg.scale;
     const size_t ib = (size_t)B * th * tw * 3, ob = ib * S * S;
-    int rc = ensure_scratch(h, 0, ib);
+    int rc = ensure_scratch(h, {{SL_SRC, ib}, {SL_DST, ob}});
     if (rc) return rc;
-    rc = ensure_scratch(h, 1, ob);
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], tiles, ib, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), tiles, ib, hipMemcpyHostToDevice, h->stream));
     // Groups are enqueued one by one with an event after each; the device-to-host copy of group g
     // runs on the copy stream while group g+1 computes, so only the last group's copy is exposed.
     // one mosaic plan for the whole batch (ragged tiles): every group runs in the same workspace geometry
@@ -1272,15 +1270,15 @@ static int forward_batch_u8_once(s2sr_handle* h, const uint8_t* tiles, int32_t B
     if ((rc = ensure_group_events(h, ngroups))) return rc;
     for (int g = 0; g < ngroups; ++g) {
         const int g0 = g * G, n = (B - g0 < G) ? (B - g0) : G;
-        rc = forward_dev(h, h->stream, TileIn::u8((const uint8_t*)h->d_scratch[0] + g0 * tin), n, th, tw,
-                         TileOut{(uint8_t*)h->d_scratch[1] + g0 * tout}, mo.on() ? &mo : nullptr);
+        rc = forward_dev(h, h->stream, TileIn::u8(scratch<const uint8_t>(h, SL_SRC) + g0 * tin), n, th, tw,
+                         TileOut{scratch<uint8_t>(h, SL_DST) + g0 * tout}, mo.on() ? &mo : nullptr);
         if (rc) return rc;
         HIPCHK(h, ev_record(h, h->group_done[g], h->stream, SITE_BATCH_GROUP_D2H));
     }
     for (int g = 0; g < ngroups; ++g) {
         const int g0 = g * G, n = (B - g0 < G) ? (B - g0) : G;
         HIPCHK(h, ev_stream_wait(h, h->copy_stream, h->group_done[g], SITE_BATCH_GROUP_D2H));
-        if ((rc = d2h_staged(h, out + g0 * tout, (const uint8_t*)h->d_scratch[1] + g0 * tout, n * tout, g + 1 == ngroups))) return rc;
+        if ((rc = d2h_staged(h, out + g0 * tout, scratch<const uint8_t>(h, SL_DST) + g0 * tout, n * tout, g + 1 == ngroups))) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -1309,12 +1307,12 @@ int s2sr_forward_batch_u16_dev(s2sr_handle* h, const void* d_tiles, int32_t B, i
     int rc = check_u16(h, lo, hi);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    // the fp32 tiles between the net and the quantiser live in the handle's scratch (slot 1); work already queued on the caller's
+    // the fp32 tiles between the net and the quantiser live in the handle's scratch (SL_DST); work already queued on the caller's
     // stream that reads an earlier call's tiles is ordered before this call's on the same stream, work on another stream by door_enter
     hipStream_t st = (hipStream_t)stream;
     DOOR_ENTER(h, st);
-    if ((rc = ensure_scratch(h, 1, (size_t)B * 3 * 16 * th * tw * sizeof(float)))) return rc;
-    return door_leave(h, st, forward_u16_locked(h, st, (const uint16_t*)d_tiles, B, th, tw, lo, hi, (uint16_t*)d_out_u16, (float*)h->d_scratch[1]));
+    if ((rc = ensure_scratch(h, SL_DST, (size_t)B * 3 * 16 * th * tw * sizeof(float)))) return rc;
+    return door_leave(h, st, forward_u16_locked(h, st, (const uint16_t*)d_tiles, B, th, tw, lo, hi, (uint16_t*)d_out_u16, scratch<float>(h, SL_DST)));
 }
 
 static int forward_batch_u16_once(s2sr_handle* h, const uint16_t* tiles, int32_t B, int32_t th, int32_t tw, int32_t lo, int32_t hi,
@@ -1329,17 +1327,15 @@ static int forward_batch_u16_once(s2sr_handle* h, const uint16_t* tiles, int32_t
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
     const size_t npx = (size_t)B * th * tw * 3, ib = npx * 2, fb = npx * 16 * sizeof(float), qb = npx * 16 * 2;
-    if ((rc = ensure_scratch(h, 0, ib))) return rc;
-    if ((rc = ensure_scratch(h, 1, fb))) return rc;
-    if (out_u16 && (rc = ensure_scratch(h, 2, qb))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], tiles, ib, hipMemcpyHostToDevice, h->stream));
-    if ((rc = forward_u16_locked(h, h->stream, (const uint16_t*)h->d_scratch[0], B, th, tw, lo, hi, out_u16 ? (uint16_t*)h->d_scratch[2] : nullptr,
-                                 (float*)h->d_scratch[1]))) return rc;
+    if ((rc = ensure_scratch(h, {{SL_SRC, ib}, {SL_DST, fb}, {SL_MID, qb, out_u16 != nullptr}}))) return rc;
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), tiles, ib, hipMemcpyHostToDevice, h->stream));
+    if ((rc = forward_u16_locked(h, h->stream, scratch<const uint16_t>(h, SL_SRC), B, th, tw, lo, hi, out_u16 ? scratch<uint16_t>(h, SL_MID) : nullptr,
+                                 scratch<float>(h, SL_DST)))) return rc;
     if ((rc = ensure_group_events(h, 1))) return rc;
     HIPCHK(h, ev_record(h, h->group_done[0], h->stream, SITE_BATCH_U16_D2H));
     HIPCHK(h, ev_stream_wait(h, h->copy_stream, h->group_done[0], SITE_BATCH_U16_D2H));
-    if (out_u16 && (rc = d2h_staged(h, (uint8_t*)out_u16, (const uint8_t*)h->d_scratch[2], qb, true))) return rc;
-    if (out_f32 && (rc = d2h_staged(h, (uint8_t*)out_f32, (const uint8_t*)h->d_scratch[1], fb, true))) return rc;
+    if (out_u16 && (rc = d2h_staged(h, (uint8_t*)out_u16, scratch<const uint8_t>(h, SL_MID), qb, true))) return rc;
+    if (out_f32 && (rc = d2h_staged(h, (uint8_t*)out_f32, scratch<const uint8_t>(h, SL_DST), fb, true))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return S2SR_OK;
@@ -1356,14 +1352,12 @@ static int forward_f32_once(s2sr_handle* h, const float* x, int32_t N, int32_t H
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
     const size_t ib = (size_t)N * 3 * H * W * 4, ob = ib * h->cfg.scale * h->cfg.scale;
-    int rc = ensure_scratch(h, 0, ib);
+    int rc = ensure_scratch(h, {{SL_SRC, ib}, {SL_DST, ob}});
     if (rc) return rc;
-    rc = ensure_scratch(h, 1, ob);
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), x, ib, hipMemcpyHostToDevice, h->stream));
+    rc = forward_dev(h, h->stream, TileIn::f32(scratch(h, SL_SRC)), N, H, W, TileOut{nullptr, scratch<float>(h, SL_DST)});
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], x, ib, hipMemcpyHostToDevice, h->stream));
-    rc = forward_dev(h, h->stream, TileIn::f32(h->d_scratch[0]), N, H, W, TileOut{nullptr, (float*)h->d_scratch[1]});
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(y, h->d_scratch[1], ob, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(y, scratch(h, SL_DST), ob, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return S2SR_OK;
 }
@@ -1428,12 +1422,11 @@ int s2sr_calibrate_fp8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int32_t 
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
     const size_t ib = (size_t)B * th * tw * 3, ob = ib * h->cfg.scale * h->cfg.scale;
-    int rc = ensure_scratch(h, 0, ib);
+    int rc = ensure_scratch(h, {{SL_SRC, ib}, {SL_DST, ob}});
     if (rc) return rc;
-    if ((rc = ensure_scratch(h, 1, ob))) return rc;
     float* d_c = nullptr;
     HIPCHK(h, dev_malloc(&d_c, 2 * sizeof(float)));
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], tiles, ib, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), tiles, ib, hipMemcpyHostToDevice, h->stream));
     const int old_x = h->fp8_x_exp, old_g = h->fp8_g_exp, old_prof = h->prof;
     const bool old_graphs = h->graphs_on;
     float m[2] = {0.f, 0.f};
@@ -1449,7 +1442,7 @@ int s2sr_calibrate_fp8(s2sr_handle* h, const uint8_t* tiles, int32_t B, int32_t 
         h->fp8_x_exp = mx; h->fp8_g_exp = mg;
         h->graphs_on = false; h->prof = 0;
         h->d_calib = d_c;
-        rc = forward_dev(h, h->stream, TileIn::u8(h->d_scratch[0]), B, th, tw, TileOut{(uint8_t*)h->d_scratch[1]});
+        rc = forward_dev(h, h->stream, TileIn::u8(scratch(h, SL_SRC)), B, th, tw, TileOut{scratch<uint8_t>(h, SL_DST)});
         h->d_calib = nullptr;
         h->graphs_on = old_graphs; h->prof = old_prof;
         e = hipMemcpyAsync(m, d_c, sizeof m, hipMemcpyDeviceToHost, h->stream);

@@ -173,13 +173,13 @@ int plan_window_job(int PH, int PW, int tile, int pad, int scale, bool tiled, Wi
 }
 
 // Window rectangles and the row / column tables of a paste (the paste maps, or the blend tables; empty: none) on the device, one
-// behind the other in scratch 3: d[0 .. 3) point at them.  Uploaded before this returns.
+// behind the other in SL_TABLES: d[0 .. 3) point at them.  Uploaded before this returns.
 static int upload_tables(s2sr_handle* h, hipStream_t st, const std::vector<int32_t>& rects, const std::vector<int32_t>& rows,
                          const std::vector<int32_t>& cols, int32_t* d[3]) {
     const std::vector<int32_t>* v[3] = {&rects, &rows, &cols};
-    int rc = ensure_scratch(h, 3, (rects.size() + rows.size() + cols.size()) * 4);
+    int rc = ensure_scratch(h, SL_TABLES, (rects.size() + rows.size() + cols.size()) * 4);
     if (rc) return rc;
-    int32_t* at = (int32_t*)h->d_scratch[3];
+    int32_t* at = scratch<int32_t>(h, SL_TABLES);
     for (int i = 0; i < 3; at += v[i++]->size()) {
         d[i] = at;
         if (!v[i]->empty()) HIPCHK(h, hipMemcpyAsync(at, v[i]->data(), v[i]->size() * 4, hipMemcpyHostToDevice, st));
@@ -288,10 +288,10 @@ static int postprocess_dev_locked(s2sr_handle* h, const void* d_rgb, int32_t B, 
                                   void* d_out, hipStream_t st) {
     if (const char* why = pp_params_error(*prm)) return fail(h, S2SR_E_INVALID, why);
     const size_t wb = postprocess_work_bytes(B, H, W, *prm);
-    int rc = ensure_scratch(h, 5, wb);
+    int rc = ensure_scratch(h, SL_PP, wb);
     if (rc) return rc;
     Scope sc(h, st, F_POST, 0.0, (double)B * H * W * 9.0);
-    HIPCHK(h, launch_postprocess((const uint8_t*)d_rgb, B, H, W, *prm, (uint8_t*)d_out, h->d_scratch[5], wb, st));
+    HIPCHK(h, launch_postprocess((const uint8_t*)d_rgb, B, H, W, *prm, (uint8_t*)d_out, scratch(h, SL_PP), wb, st));
     return S2SR_OK;
 }
 
@@ -309,10 +309,10 @@ int s2sr_postprocess_batch_u8_dev(s2sr_handle* h, const void* d_rgb, int32_t B, 
 // order: S2SR_PP_ORDER_BGR = the image's bytes are B,G,R; S2SR_PP_ORDER_SWAP_OUT = R and B exchanged in the rows written
 static int pp_band_begin_locked(s2sr_handle* h, int H, int W, const s2sr_pp_params* prm, int order, hipStream_t st) {
     if (const char* why = pp_params_error(*prm)) {
-        h->ppb.open = false;           // a refused begin leaves no run behind, the caller's earlier one included
+        h->scratch.run_open = false;   // a refused begin leaves no run behind, the caller's earlier one included
         return fail(h, S2SR_E_INVALID, why);
     }
-    int rc = ensure_scratch(h, 5, postprocess_work_bytes(1, H, W, *prm));
+    int rc = ensure_scratch(h, SL_PP, postprocess_work_bytes(1, H, W, *prm));
     if (rc) return rc;
     s2sr_handle::PPBand& b = h->ppb;
     b = s2sr_handle::PPBand();
@@ -320,42 +320,42 @@ static int pp_band_begin_locked(s2sr_handle* h, int H, int W, const s2sr_pp_para
     b.bgr = (order & S2SR_PP_ORDER_BGR) ? 1 : 0;
     b.swap_out = (order & S2SR_PP_ORDER_SWAP_OUT) ? 1 : 0;
     b.radius = pp_band_radius(*prm);
-    HIPCHK(h, launch_pp_band_begin(H, W, *prm, h->d_scratch[5], st));
-    b.open = true;
+    HIPCHK(h, launch_pp_band_begin(H, W, *prm, scratch(h, SL_PP), st));
+    h->scratch.run_open = true;
     return S2SR_OK;
 }
 
 static int pp_band_hist_locked(s2sr_handle* h, const void* d_img, int y0, int y1, hipStream_t st) {
     s2sr_handle::PPBand& b = h->ppb;
-    if (!b.open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_hist: no banded post-process open (none begun, or another call took its scratch area since: begin again), or its LUTs are already built");
+    if (!h->scratch.run_open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_hist: no banded post-process open (none begun, or another call took its scratch area since: begin again), or its LUTs are already built");
     if (y0 < 0 || y1 > b.H || y0 > y1) return fail(h, S2SR_E_INVALID, "pp_band_hist: rows outside the image");
     Scope sc(h, st, F_POST, 0.0, (double)(y1 - y0) * b.W * 3.0);
-    HIPCHK(h, launch_pp_band_hist((const uint8_t*)d_img, b.H, b.W, b.prm, b.bgr, y0, y1, h->d_scratch[5], st));
+    HIPCHK(h, launch_pp_band_hist((const uint8_t*)d_img, b.H, b.W, b.prm, b.bgr, y0, y1, scratch(h, SL_PP), st));
     return S2SR_OK;
 }
 
 static int pp_band_lut_locked(s2sr_handle* h, hipStream_t st) {
     s2sr_handle::PPBand& b = h->ppb;
-    if (!b.open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_lut: no banded post-process open (none begun, or another call took its scratch area since: begin again), or its LUTs are already built");
-    HIPCHK(h, launch_pp_band_lut(b.H, b.W, b.prm, h->d_scratch[5], st));
+    if (!h->scratch.run_open || b.lut) return fail(h, S2SR_E_INVALID, "pp_band_lut: no banded post-process open (none begun, or another call took its scratch area since: begin again), or its LUTs are already built");
+    HIPCHK(h, launch_pp_band_lut(b.H, b.W, b.prm, scratch(h, SL_PP), st));
     b.lut = true;
     return S2SR_OK;
 }
 
 static int pp_band_rows_locked(s2sr_handle* h, const void* d_img, int y0, int y1, void* d_out, hipStream_t st) {
     s2sr_handle::PPBand& b = h->ppb;
-    if (!b.open || !b.lut) return fail(h, S2SR_E_INVALID, "pp_band_rows: no banded post-process open (none begun, or another call took its scratch area since: begin again), or its LUTs are not "
+    if (!h->scratch.run_open || !b.lut) return fail(h, S2SR_E_INVALID, "pp_band_rows: no banded post-process open (none begun, or another call took its scratch area since: begin again), or its LUTs are not "
                                                           "built (begin, hist over every row, lut, then rows)");
     if (y0 != b.rows_end || y1 <= y0 || y1 > b.H) return fail(h, S2SR_E_INVALID, "pp_band_rows: bands must follow each other from row 0");
     const int need = y1 + b.radius < b.H ? y1 + b.radius : b.H;     // the blur of row y1-1 reads R rows below it
     Scope sc(h, st, F_POST, 0.0, (double)(y1 - y0) * b.W * 6.0);
     if (need > b.applied_end) {
-        HIPCHK(h, launch_pp_band_apply((const uint8_t*)d_img, b.H, b.W, b.prm, b.bgr, b.applied_end, need, h->d_scratch[5], st));
+        HIPCHK(h, launch_pp_band_apply((const uint8_t*)d_img, b.H, b.W, b.prm, b.bgr, b.applied_end, need, scratch(h, SL_PP), st));
         b.applied_end = need;
     }
-    HIPCHK(h, launch_pp_band_sharpen(b.H, b.W, b.prm, b.bgr, b.swap_out, y0, y1, h->d_scratch[5], (uint8_t*)d_out, st));
+    HIPCHK(h, launch_pp_band_sharpen(b.H, b.W, b.prm, b.bgr, b.swap_out, y0, y1, scratch(h, SL_PP), (uint8_t*)d_out, st));
     b.rows_end = y1;
-    if (y1 == b.H) b.open = false;
+    if (y1 == b.H) h->scratch.run_open = false;
     return S2SR_OK;
 }
 
@@ -392,7 +392,7 @@ int s2sr_pp_band_rows_dev(s2sr_handle* h, const void* d_img, int32_t y0, int32_t
 }
 
 // Host image in, host image out.  ONE lock scope from the upload to the download: the staging buffers
-// (d_scratch[0], [1]) belong to the handle, and the app shares one post-process handle per device between
+// (SL_SRC, SL_DST) belong to the handle, and the app shares one post-process handle per device between
 // all jobs (app/wow_sr.py), which the reference runs from concurrent worker threads (main.py:247-368).
 int s2sr_postprocess_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, const s2sr_pp_params* prm, uint8_t* out) {
     if (!h || !rgb || !out || !prm || H <= 0 || W <= 0) return S2SR_E_INVALID;
@@ -400,12 +400,11 @@ int s2sr_postprocess_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W
     std::lock_guard<std::mutex> lk(h->mu);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
-    int rc = ensure_scratch(h, 0, nb);
+    int rc = ensure_scratch(h, {{SL_SRC, nb}, {SL_DST, nb}});
     if (rc) return rc;
-    if ((rc = ensure_scratch(h, 1, nb))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], rgb, nb, hipMemcpyHostToDevice, h->stream));
-    if ((rc = postprocess_dev_locked(h, h->d_scratch[0], 1, H, W, prm, h->d_scratch[1], h->stream))) return rc;
-    HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[1], nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), rgb, nb, hipMemcpyHostToDevice, h->stream));
+    if ((rc = postprocess_dev_locked(h, scratch(h, SL_SRC), 1, H, W, prm, scratch(h, SL_DST), h->stream))) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, scratch(h, SL_DST), nb, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return S2SR_OK;
 }
@@ -422,7 +421,7 @@ static int plan_dims(s2sr_handle* h, int H, int W, int tile, int* PH, int* PW) {
     return S2SR_OK;
 }
 
-// The device copy of a masked call's `valid` (scratch 6) and what the mask kernel needs with it.
+// The device copy of a masked call's `valid` (SL_VALID) and what the mask kernel needs with it.
 struct MaskDev {
     const uint8_t* d_valid = nullptr;         // null: the call is not masked
     int H = 0, W = 0, scale = 0, out_nodata = 0;
@@ -438,19 +437,19 @@ static int mask_rows(s2sr_handle* h, hipStream_t st, const MaskDev& m, void* d_i
     return S2SR_OK;
 }
 
-// `valid` (host) to scratch 6 and the fill of the image at d_img [H, W, 3] (uint8, or uint16), both on st.  The caller has asked for
-// scratch 6 (H * W bytes) already: a scratch request may free and synchronise, which belongs in front of a call's first launch.
+// `valid` (host) to SL_VALID and the fill of the image at d_img [H, W, 3] (uint8, or uint16), both on st.  The caller has asked for
+// SL_VALID (H * W bytes) already: a scratch request may free and synchronise, which belongs in front of a call's first launch.
 static int fill_locked(s2sr_handle* h, hipStream_t st, const uint8_t* valid, int H, int W, int radius, bool u16, void* d_img) {
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[6], valid, (size_t)H * W, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_VALID), valid, (size_t)H * W, hipMemcpyHostToDevice, st));
     Scope sc(h, st, F_NFILL, 0.0, (double)H * W);
-    if (u16) HIPCHK(h, launch_nodata_fill((uint16_t*)d_img, (const uint8_t*)h->d_scratch[6], H, W, radius, st));
-    else HIPCHK(h, launch_nodata_fill((uint8_t*)d_img, (const uint8_t*)h->d_scratch[6], H, W, radius, st));
+    if (u16) HIPCHK(h, launch_nodata_fill((uint16_t*)d_img, scratch<const uint8_t>(h, SL_VALID), H, W, radius, st));
+    else HIPCHK(h, launch_nodata_fill((uint8_t*)d_img, scratch<const uint8_t>(h, SL_VALID), H, W, radius, st));
     return S2SR_OK;
 }
 
 // A consistency pass over one quantised image on the device (consistency.hip), in place, in bands of whole block
 // rows behind whatever makes the image's rows final (the paste of a whole-image call, the upload of s2sr_consistency_*).  A band
-// may end on a row that is no multiple of S, and mode 2 reads the residuals of the block row below: the pass trails.  Scratch 7:
+// may end on a row that is no multiple of S, and mode 2 reads the residuals of the block row below: the pass trails.  SL_CONS:
 // the inexact counters (uint64[3]) in the first 256 bytes, behind them mode 2's residual plane (int32 [H, W, 3]).
 struct ConsRun {
     int mode = 0;                             // 0: no pass
@@ -471,18 +470,18 @@ static int cons_out_end(int mode, int S, int H, int final_rows, bool last) {
     return b > 0 ? b * S : 0;
 }
 
-// zeroes the counters; the caller has asked for scratch 7 (cons_scratch_bytes) in front of its first launch
+// zeroes the counters; the caller has asked for SL_CONS (cons_scratch_bytes) in front of its first launch
 static int cons_begin(s2sr_handle* h, hipStream_t st, ConsRun& r) {
     r.e_end = r.done = 0;
-    HIPCHK(h, hipMemsetAsync(h->d_scratch[7], 0, kConsHead, st));
+    HIPCHK(h, hipMemsetAsync(scratch(h, SL_CONS), 0, kConsHead, st));
     return S2SR_OK;
 }
 
 // rows [0, final_rows) of the image are final: the pass up to row out_end (cons_out_end of them)
 static int cons_advance(s2sr_handle* h, hipStream_t st, ConsRun& r, int final_rows, int out_end) {
     const int fb = final_rows / r.S, target = out_end / r.S;
-    unsigned long long* cnt = (unsigned long long*)h->d_scratch[7];
-    int32_t* d_e = (int32_t*)((char*)h->d_scratch[7] + kConsHead);
+    unsigned long long* cnt = scratch<unsigned long long>(h, SL_CONS);
+    int32_t* d_e = (int32_t*)(scratch<char>(h, SL_CONS) + kConsHead);
     auto launch = [&](int form, int b0, int b1) -> int {
         const double img_b = (double)(b1 - b0) * r.S * r.S * r.W * 3.0 * (r.u16 ? 2 : 1);
         Scope sc(h, st, F_CONS, 0.0, form == 0 ? img_b : 2.0 * img_b);
@@ -507,7 +506,7 @@ static int cons_advance(s2sr_handle* h, hipStream_t st, ConsRun& r, int final_ro
 // the counters to the host, behind everything on st; returns when they are there
 static int cons_counts(s2sr_handle* h, hipStream_t st, uint64_t* inexact) {
     unsigned long long n[3];
-    HIPCHK(h, hipMemcpyAsync(n, h->d_scratch[7], sizeof n, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(n, scratch(h, SL_CONS), sizeof n, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     if (inexact) for (int c = 0; c < 3; ++c) inexact[c] = n[c];
     return S2SR_OK;
@@ -650,12 +649,12 @@ static int plan_enhance(s2sr_handle* h, const EnhanceCall& c, EnhancePlan& p) {
 }
 
 // RealESRGAN.enhance (cnn_super_resolution.py:217-234) incl. _tile_process (:236-280), behind every door; the caller holds h->mu.
-// Upload, gather the windows (scratch 0 -> 2), the chunk loop -- forward a chunk of window rows, paste the band of output rows it
-// made final into the image (scratch 1), copy the band out under the next chunk -- and the tail.  Only the paste varies:
-//   overwrite (8-bit in): the net writes u8 (or NCHW fp32) tiles of the WHOLE image into scratch 4, each chunk at its own offset, and
-//     launch_stitch pastes.  The untiled image is one window: the net writes it straight into scratch 1, or (fp32, or the padded
-//     image of an odd scale-2 one) into scratch 2 and an identity map crops it.  A job's R / B exchange follows each band;
-//   quantise (16-bit in): every chunk's windows leave the net as fp32 tiles into ONE chunk-sized buffer (scratch 4; the same
+// Upload, gather the windows (SL_SRC -> SL_MID), the chunk loop -- forward a chunk of window rows, paste the band of output rows it
+// made final into the image (SL_DST), copy the band out under the next chunk -- and the tail.  Only the paste varies:
+//   overwrite (8-bit in): the net writes u8 (or NCHW fp32) tiles of the WHOLE image into SL_CHUNK, each chunk at its own offset, and
+//     launch_stitch pastes.  The untiled image is one window: the net writes it straight into SL_DST, or (fp32, or the padded
+//     image of an odd scale-2 one) into SL_MID and an identity map crops it.  A job's R / B exchange follows each band;
+//   quantise (16-bit in): every chunk's windows leave the net as fp32 tiles into ONE chunk-sized buffer (SL_CHUNK; the same
 //     pointers for every chunk, so the chunks' graphs hit) and launch_stitch_quant_u16 pastes and quantises from it;
 //   blend: as quantise, for both inputs, and launch_stitch_blend cross-fades inside the ramps.  A row ramp reads the last window
 //     row of one chunk and the first of the next, so the buffer has one window row in front of the chunk's, filled from the chunk
@@ -688,33 +687,30 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
     const size_t ipx = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
     const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;      // samples per window, in and out
     const size_t row_b = (size_t)OW * 3 * esz;                                         // bytes of one output row
-    // ---- staging.  scratch 1: the quantised image, then the fp32 image (the overwrite paste makes one of them per call)
+    // ---- staging.  SL_DST: the quantised image, then the fp32 image (the overwrite paste makes one of them per call)
     const size_t f_off = over ? 0 : (opx * esz + 255) & ~(size_t)255;
-    const int tslot = over && !p.tiled ? 2 : 4;
+    const Slot tslot = over && !p.tiled ? SL_MID : SL_CHUNK;
     const size_t tile_b = over ? (size_t)nx * ny * win_out * (c.out_f32 ? 4 : 1) : (size_t)(p.max_rows + carry) * nx * win_out * sizeof(float);
-    if ((rc = ensure_scratch(h, 0, ipx * esz))) return rc;
-    if ((rc = ensure_scratch(h, 1, c.out_f32 ? f_off + opx * 4 : over ? opx : f_off))) return rc;
-    if (p.tiled && (rc = ensure_scratch(h, 2, (size_t)nx * ny * win_in * esz))) return rc;
-    if (!direct && (rc = ensure_scratch(h, tslot, tile_b))) return rc;
-    if (c.masked && (rc = ensure_scratch(h, 6, (size_t)H * W))) return rc;
-    if (c.consistency && (rc = ensure_scratch(h, 7, cons_scratch_bytes(c.consistency, H, W)))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], in16 ? (const void*)c.img16 : (const void*)c.img8, ipx * esz, hipMemcpyHostToDevice, st));
+    if ((rc = ensure_scratch(h, {{SL_SRC, ipx * esz}, {SL_DST, c.out_f32 ? f_off + opx * 4 : over ? opx : f_off},
+                                 {SL_MID, (size_t)nx * ny * win_in * esz, p.tiled}, {tslot, tile_b, !direct}, {SL_VALID, (size_t)H * W, c.masked},
+                                 {SL_CONS, cons_scratch_bytes(c.consistency, H, W), c.consistency != 0}}))) return rc;
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), in16 ? (const void*)c.img16 : (const void*)c.img8, ipx * esz, hipMemcpyHostToDevice, st));
     MaskDev mk;                                        // masked: the fill in front of everything that reads the image, the mask at each exit of a quantised band
     if (c.masked) {
-        if ((rc = fill_locked(h, st, c.valid, H, W, c.radius, in16, h->d_scratch[0]))) return rc;
-        mk.d_valid = (const uint8_t*)h->d_scratch[6]; mk.H = H; mk.W = W; mk.scale = scale; mk.out_nodata = c.out_nodata; mk.u16 = in16;
+        if ((rc = fill_locked(h, st, c.valid, H, W, c.radius, in16, scratch(h, SL_SRC)))) return rc;
+        mk.d_valid = scratch<const uint8_t>(h, SL_VALID); mk.H = H; mk.W = W; mk.scale = scale; mk.out_nodata = c.out_nodata; mk.u16 = in16;
     }
-    if (c.swap_rb) HIPCHK(h, launch_swap_rb_u8((const uint8_t*)h->d_scratch[0], (size_t)H * W, (uint8_t*)h->d_scratch[0], st));
+    if (c.swap_rb) HIPCHK(h, launch_swap_rb_u8(scratch<const uint8_t>(h, SL_SRC), (size_t)H * W, scratch<uint8_t>(h, SL_SRC), st));
     int32_t* d_tab[3] = {nullptr, nullptr, nullptr};   // rectangles, row table, column table
     if (!direct && (rc = upload_tables(h, st, job.rects, p.blend ? p.rows : job.rm, p.blend ? p.cols : job.cm, d_tab))) return rc;
     if (p.tiled) {
-        if (in16) HIPCHK(h, launch_gather_windows((const uint16_t*)h->d_scratch[0], H, W, d_tab[0], nx * ny, wh, ww, (uint16_t*)h->d_scratch[2], st));
-        else HIPCHK(h, launch_gather_windows((const uint8_t*)h->d_scratch[0], H, W, d_tab[0], nx * ny, wh, ww, reflect, (uint8_t*)h->d_scratch[2], st));
+        if (in16) HIPCHK(h, launch_gather_windows(scratch<const uint16_t>(h, SL_SRC), H, W, d_tab[0], nx * ny, wh, ww, scratch<uint16_t>(h, SL_MID), st));
+        else HIPCHK(h, launch_gather_windows(scratch<const uint8_t>(h, SL_SRC), H, W, d_tab[0], nx * ny, wh, ww, reflect, scratch<uint8_t>(h, SL_MID), st));
     }
-    const char* d_win = (const char*)h->d_scratch[p.tiled ? 2 : 0];
-    uint8_t* d_q = (uint8_t*)h->d_scratch[1];
+    const char* d_win = scratch<const char>(h, p.tiled ? SL_MID : SL_SRC);
+    uint8_t* d_q = scratch<uint8_t>(h, SL_DST);
     float* d_f = (float*)(d_q + f_off);
-    void* d_buf = direct ? (void*)d_q : h->d_scratch[tslot];      // blend: [carry window row | the chunk's window rows]
+    void* d_buf = direct ? (void*)d_q : scratch(h, tslot);      // blend: [carry window row | the chunk's window rows]
     float* d_tiles = (float*)d_buf + (size_t)carry * nx * win_out;
     int fin_rows = 0, nfin = 0;          // finishing bands of the post-process: ~48 MB each, whole 32-row tile rows
     if (banded) {
@@ -723,12 +719,12 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
         nfin = (OH + fin_rows - 1) / fin_rows;
         if ((rc = pp_band_begin_locked(h, OH, OW, c.prm, c.swap_rb ? 3 : 0, st))) return rc;
     }
-    // this call's run took scratch 5 from whatever run a caller had open there: it ends with the call on every way out, so that
+    // this call's run took SL_PP from whatever run a caller had open there: it ends with the call on every way out, so that
     // caller's next hist / lut / rows is refused
-    struct CloseRun { s2sr_handle* h; ~CloseRun() { if (h) h->ppb.open = false; } } close_run{banded ? h : nullptr};
+    struct CloseRun { s2sr_handle* h; ~CloseRun() { if (h) h->scratch.run_open = false; } } close_run{banded ? h : nullptr};
     if ((rc = ensure_group_events(h, nchunks + nfin + 1))) return rc;
     // consistency: the pass trails the paste (whole block rows; mode 2 one more), and everything behind the paste follows the pass's
-    // bands -- the R / B exchange back, the histograms of a banded post-process, the mask, the copy out.  Scratch 0 holds the image
+    // bands -- the R / B exchange back, the histograms of a banded post-process, the mask, the copy out.  SL_SRC holds the image
     // the net saw (filled, exchanged) for the whole call.  The 8-bit blend paste of a job without post-process has exchanged R and
     // B already: image channel c is then input channel 2 - c.
     ConsRun cr;
@@ -737,7 +733,7 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
         cr.mode = c.consistency; cr.H = H; cr.W = W; cr.S = scale; cr.u16 = in16;
         if (in16) { cr.lo = c.lo; cr.hi = c.hi; }
         cr.swap = !over && !in16 && c.swap_rb && !c.prm;
-        cr.d_lr = h->d_scratch[0]; cr.d_img = d_q;
+        cr.d_lr = scratch(h, SL_SRC); cr.d_img = d_q;
         for (int k = 0; k < nchunks; ++k) out_end[k] = cons_out_end(cr.mode, scale, H, p.band_end[k], k == nchunks - 1);
         if ((rc = cons_begin(h, st, cr))) return rc;
     }
@@ -786,12 +782,12 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
     if (banded && (rc = pp_finish_bands(h, st, d_q, c.out_u8, OH, row_b, fin_rows, nfin, nchunks, mk))) return rc;
     if (c.prm && !banded) {
         // the windows' output buffer is free again once the stitch has read it; the untiled image gets a buffer of its own
-        if ((rc = ensure_scratch(h, 4, opx))) return rc;
-        if ((rc = postprocess_dev_locked(h, d_q, 1, OH, OW, c.prm, h->d_scratch[4], st))) return rc;
-        if ((rc = mask_rows(h, st, mk, h->d_scratch[4], 0, OH))) return rc;
+        if ((rc = ensure_scratch(h, SL_CHUNK, opx))) return rc;
+        if ((rc = postprocess_dev_locked(h, d_q, 1, OH, OW, c.prm, scratch(h, SL_CHUNK), st))) return rc;
+        if ((rc = mask_rows(h, st, mk, scratch(h, SL_CHUNK), 0, OH))) return rc;
         HIPCHK(h, ev_record(h, tail_done, st, SITE_TAIL_D2H));
         HIPCHK(h, ev_stream_wait(h, h->copy_stream, tail_done, SITE_TAIL_D2H));
-        if ((rc = d2h_staged(h, c.out_u8, (const uint8_t*)h->d_scratch[4], opx, true))) return rc;
+        if ((rc = d2h_staged(h, c.out_u8, scratch<const uint8_t>(h, SL_CHUNK), opx, true))) return rc;
     }
     if (c.out_f32) {
         if (p.blend) HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, 0, oth, otw, d_tab[1], d_tab[2], OH, OW, d_f, st));
@@ -811,7 +807,7 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
         const uint64_t b = c.inexact[0];
         c.inexact[0] = c.inexact[2]; c.inexact[2] = b;
     }
-    if (c.out_u16) { h->disp_slot = 1; h->disp_h = OH; h->disp_w = OW; }   // the x4 image also stays on the device, for s2sr_display_*_u16
+    if (c.out_u16) h->scratch.keep(KEPT_U16, SL_DST, OH, OW);                // the x4 image also stays on the device, for s2sr_display_*_u16
     return S2SR_OK;
 }
 
@@ -954,20 +950,18 @@ static int consistency_impl(s2sr_handle* h, const void* sr, const void* img, int
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
-    int rc = ensure_scratch(h, 0, ipx * esz);
+    int rc = ensure_scratch(h, {{SL_SRC, ipx * esz}, {SL_DST, row_b * OH}, {SL_CONS, cons_scratch_bytes(mode, H, W)}});
     if (rc) return rc;
-    if ((rc = ensure_scratch(h, 1, row_b * OH))) return rc;
-    if ((rc = ensure_scratch(h, 7, cons_scratch_bytes(mode, H, W)))) return rc;
     size_t rows = band_rows > 0 ? (size_t)band_rows : ((size_t)32 << 20) / row_b;      // the library's choice: ~32 MB
     if (rows < 1) rows = 1;
     if (rows > (size_t)OH) rows = OH;
     ConsRun cr;
     cr.mode = mode; cr.H = H; cr.W = W; cr.S = S; cr.u16 = u16;
     if (u16) { cr.lo = lo; cr.hi = hi; }
-    cr.d_lr = h->d_scratch[0]; cr.d_img = h->d_scratch[1];
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, ipx * esz, hipMemcpyHostToDevice, st));
+    cr.d_lr = scratch(h, SL_SRC); cr.d_img = scratch(h, SL_DST);
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), img, ipx * esz, hipMemcpyHostToDevice, st));
     if ((rc = cons_begin(h, st, cr))) return rc;
-    uint8_t* d_img = (uint8_t*)h->d_scratch[1];
+    uint8_t* d_img = scratch<uint8_t>(h, SL_DST);
     int left = 0;                                                                       // rows that have left
     for (size_t y0 = 0; y0 < (size_t)OH; y0 += rows) {
         const int y1 = (int)(y0 + rows < (size_t)OH ? y0 + rows : OH);
@@ -999,12 +993,11 @@ static int fill_nodata_impl(s2sr_handle* h, const void* img, const uint8_t* vali
     const size_t nb = (size_t)H * W * 3 * (u16 ? 2 : 1);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
-    int rc = ensure_scratch(h, 0, nb);
+    int rc = ensure_scratch(h, {{SL_SRC, nb}, {SL_VALID, (size_t)H * W}});
     if (rc) return rc;
-    if ((rc = ensure_scratch(h, 6, (size_t)H * W))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], img, nb, hipMemcpyHostToDevice, h->stream));
-    if ((rc = fill_locked(h, h->stream, valid, H, W, radius, u16, h->d_scratch[0]))) return rc;
-    HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[0], nb, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), img, nb, hipMemcpyHostToDevice, h->stream));
+    if ((rc = fill_locked(h, h->stream, valid, H, W, radius, u16, scratch(h, SL_SRC)))) return rc;
+    HIPCHK(h, hipMemcpyAsync(out, scratch(h, SL_SRC), nb, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return S2SR_OK;
 }

@@ -189,20 +189,19 @@ int s2sr_debug_mfma_ceiling(s2sr_handle* h, int32_t mode, int32_t stages, int32_
     int ncu = 256;
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
     const size_t src_bytes = (size_t)336 << 20;          // what a conv1-4 launch of 16 images fills its rings with; larger than L2 + MALL
-    int rc = ensure_scratch(h, 2, src_bytes);
-    if (rc) return rc;
     const size_t sink_bytes = (size_t)ncu * 512 * 4, store_bytes = (size_t)64 << 20;      // mode 5 streams its stores through 64 MB
-    if ((rc = ensure_scratch(h, 3, sink_bytes + store_bytes))) return rc;
-    char* d_store = (char*)h->d_scratch[3] + sink_bytes;
+    int rc = ensure_scratch(h, {{SL_MID, src_bytes}, {SL_TABLES, sink_bytes + store_bytes}});
+    if (rc) return rc;
+    char* d_store = scratch<char>(h, SL_TABLES) + sink_bytes;
     hipStream_t st = h->stream;
     hipEvent_t e0 = get_event(h), e1 = get_event(h);
-    HIPCHK(h, launch_mfma_ceiling(mode, (char*)h->d_scratch[2], src_bytes, true /* fill the operands: 0.1 ms */, (float*)h->d_scratch[3], ncu, stages, d_store,
+    HIPCHK(h, launch_mfma_ceiling(mode, scratch<char>(h, SL_MID), src_bytes, true /* fill the operands: 0.1 ms */, scratch<float>(h, SL_TABLES), ncu, stages, d_store,
                                   store_bytes, st));
     for (int i = 0; i < launches / 4; ++i)
-        HIPCHK(h, launch_mfma_ceiling(mode, (char*)h->d_scratch[2], src_bytes, false, (float*)h->d_scratch[3], ncu, stages, d_store, store_bytes, st));
+        HIPCHK(h, launch_mfma_ceiling(mode, scratch<char>(h, SL_MID), src_bytes, false, scratch<float>(h, SL_TABLES), ncu, stages, d_store, store_bytes, st));
     HIPCHK(h, hipEventRecord(e0, st));
     for (int i = 0; i < launches; ++i)
-        HIPCHK(h, launch_mfma_ceiling(mode, (char*)h->d_scratch[2], src_bytes, false, (float*)h->d_scratch[3], ncu, stages, d_store, store_bytes, st));
+        HIPCHK(h, launch_mfma_ceiling(mode, scratch<char>(h, SL_MID), src_bytes, false, scratch<float>(h, SL_TABLES), ncu, stages, d_store, store_bytes, st));
     HIPCHK(h, hipEventRecord(e1, st));
     HIPCHK(h, hipStreamSynchronize(st));
     HIPCHK(h, hipEventElapsedTime(ms_total, e0, e1));
@@ -224,26 +223,24 @@ int s2sr_debug_rdb_persistent(s2sr_handle* h, int32_t variant, int32_t grid, int
     (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device);
     if (grid > ncu) return fail(h, S2SR_E_INVALID, "more workgroups than CUs: they would not all be resident");
     const size_t wts_bytes = (size_t)8 << 20, ws_bytes = rdb_persistent_ws_bytes(variant, grid, P), sink_bytes = (size_t)grid * 512 * 4;
-    int rc = ensure_scratch(h, 2, wts_bytes);
+    int rc = ensure_scratch(h, {{SL_MID, wts_bytes}, {SL_TABLES, sink_bytes + 256}, {SL_CHUNK, ws_bytes}});
     if (rc) return rc;
-    if ((rc = ensure_scratch(h, 3, sink_bytes + 256))) return rc;
-    if ((rc = ensure_scratch(h, 4, ws_bytes))) return rc;
     struct Uncached {
         void* p = nullptr;
         ~Uncached() { if (p) (void)hipFree(p); }
     } fl;
     const size_t flag_bytes = ((size_t)grid * P + 1) * 4;
     HIPCHK(h, hipExtMallocWithFlags(&fl.p, flag_bytes, hipDeviceMallocUncached));
-    uint32_t* d_timeouts = (uint32_t*)((char*)h->d_scratch[3] + sink_bytes);
+    uint32_t* d_timeouts = (uint32_t*)(scratch<char>(h, SL_TABLES) + sink_bytes);
     hipStream_t st = h->stream;
     // operand data: the ceiling loops' generator fills the weights buffer and the working set (toggle rates as there)
-    HIPCHK(h, launch_mfma_ceiling(0, (char*)h->d_scratch[2], wts_bytes, true, (float*)h->d_scratch[3], 1, 1, nullptr, 0, st));
-    HIPCHK(h, launch_mfma_ceiling(0, (char*)h->d_scratch[4], ws_bytes, true, (float*)h->d_scratch[3], 1, 1, nullptr, 0, st));
+    HIPCHK(h, launch_mfma_ceiling(0, scratch<char>(h, SL_MID), wts_bytes, true, scratch<float>(h, SL_TABLES), 1, 1, nullptr, 0, st));
+    HIPCHK(h, launch_mfma_ceiling(0, scratch<char>(h, SL_CHUNK), ws_bytes, true, scratch<float>(h, SL_TABLES), 1, 1, nullptr, 0, st));
     HIPCHK(h, hipMemsetAsync(d_timeouts, 0, 12, st));
     hipEvent_t e0 = get_event(h), e1 = get_event(h);
     auto one = [&]() -> int {
         HIPCHK(h, hipMemsetAsync(fl.p, 0, flag_bytes, st));
-        HIPCHK(h, launch_rdb_persistent(variant, (const char*)h->d_scratch[2], wts_bytes, (char*)h->d_scratch[4], (uint32_t*)fl.p, (float*)h->d_scratch[3],
+        HIPCHK(h, launch_rdb_persistent(variant, scratch<const char>(h, SL_MID), wts_bytes, scratch<char>(h, SL_CHUNK), (uint32_t*)fl.p, scratch<float>(h, SL_TABLES),
                                         grid, P, rdbs, d_timeouts, st));
         return S2SR_OK;
     };

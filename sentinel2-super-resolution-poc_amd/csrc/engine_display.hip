@@ -15,10 +15,11 @@ namespace {
 constexpr size_t kHistBytes = 3 * 65536 * sizeof(uint64_t), kLutBytes = 3 * 65536;
 constexpr size_t kBandSamples = (size_t)1 << 30;       // most samples one histogram launch counts (32-bit LDS counters)
 
-// The source of a display call and its row bands.  img == NULL: the H x W image of the handle's record (s2sr_handle::disp_*), where
-// it lies; a host image goes to scratch 0.  Scratch requests drop the record, so a call keeps what it found and sets it again.
+// The source of a display call and its row bands.  img == NULL: the H x W image the last call kept, where it lies; a host image
+// goes to SL_SRC.  Either way the image is what the call keeps at its end.
 struct Source {
-    int slot = 0, rows = 0, nbands = 0;
+    KeptInput in;
+    int rows = 0, nbands = 0;
     size_t row_s = 0, total = 0;         // samples per row and in the image
 };
 
@@ -34,12 +35,9 @@ int plan_source(s2sr_handle* h, const char* who, const uint16_t* img, int H, int
         snprintf(b, sizeof b, "%s: rows of more than 2^30 samples are not supported", who);
         return fail(h, S2SR_E_INVALID, b);
     }
-    if (!img) {
-        if (h->disp_slot < 0 || h->disp_h != H || h->disp_w != W) {
-            snprintf(b, sizeof b, "%s: img == NULL, but the previous call on this handle did not leave a uint16 image of this size on the device", who);
-            return fail(h, S2SR_E_INVALID, b);
-        }
-        s.slot = h->disp_slot;
+    if (!img && !s.in.take(KEPT_U16, H, W)) {
+        snprintf(b, sizeof b, "%s: img == NULL, but the previous call on this handle did not leave a uint16 image of this size on the device", who);
+        return fail(h, S2SR_E_INVALID, b);
     }
     // the library's choice: ~32 MB of samples per band (its upload hides the band before's kernel); never more than one launch counts
     size_t rows = band_rows > 0 ? (size_t)band_rows : ((size_t)16 << 20) / s.row_s;
@@ -51,10 +49,10 @@ int plan_source(s2sr_handle* h, const char* who, const uint16_t* img, int H, int
     return S2SR_OK;
 }
 
-// upload of band i of a host image into scratch 0, on the copy stream, and the event behind it
+// upload of band i of a host image into SL_SRC, on the copy stream, and the event behind it
 int upload_band(s2sr_handle* h, const uint16_t* img, const Source& s, int H, int i, hipEvent_t ev) {
     const size_t y0 = (size_t)i * s.rows, y1 = y0 + s.rows < (size_t)H ? y0 + s.rows : H;
-    HIPCHK(h, hipMemcpyAsync((uint16_t*)h->d_scratch[0] + y0 * s.row_s, img + y0 * s.row_s, (y1 - y0) * s.row_s * 2, hipMemcpyHostToDevice, h->copy_stream));
+    HIPCHK(h, hipMemcpyAsync(scratch<uint16_t>(h, SL_SRC) + y0 * s.row_s, img + y0 * s.row_s, (y1 - y0) * s.row_s * 2, hipMemcpyHostToDevice, h->copy_stream));
     HIPCHK(h, ev_record(h, ev, h->copy_stream, SITE_DISPLAY_UPLOAD));
     return S2SR_OK;
 }
@@ -64,17 +62,16 @@ int display_hist_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int nod
     std::lock_guard<std::mutex> lk(h->mu);
     if (!hist) return fail(h, S2SR_E_INVALID, "s2sr_display_hist_u16: hist is required");
     if (nodata < -1 || nodata > 65535) return fail(h, S2SR_E_INVALID, "s2sr_display_hist_u16: nodata must be -1 (none) or 0..65535");
-    Source s;
+    Source s{KeptInput(h)};
     int rc = plan_source(h, "s2sr_display_hist_u16", img, H, W, band_rows, s);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
-    if (img && (rc = ensure_scratch(h, 0, (s.total * 2 + 255) & ~(size_t)255))) return rc;
-    if ((rc = ensure_scratch(h, 3, kHistBytes + kLutBytes))) return rc;
+    if ((rc = ensure_scratch(h, {{SL_SRC, (s.total * 2 + 255) & ~(size_t)255, img != nullptr}, {SL_TABLES, kHistBytes + kLutBytes}}))) return rc;
     if ((rc = ensure_group_events(h, 4))) return rc;
-    const uint16_t* d_img = (const uint16_t*)h->d_scratch[s.slot];
-    unsigned long long* d_hist = (unsigned long long*)h->d_scratch[3];
+    const uint16_t* d_img = scratch<const uint16_t>(h, s.in.slot);
+    unsigned long long* d_hist = scratch<unsigned long long>(h, SL_TABLES);
     HIPCHK(h, hipMemsetAsync(d_hist, 0, kHistBytes, st));
     // a host image: band i + 1 uploads on the copy stream under band i's kernel
     if (img && (rc = upload_band(h, img, s, H, 0, h->group_done[0]))) return rc;
@@ -90,7 +87,7 @@ int display_hist_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int nod
     HIPCHK(h, hipMemcpyAsync(hist, d_hist, kHistBytes, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
-    h->disp_slot = s.slot; h->disp_h = H; h->disp_w = W;     // the scratch requests above dropped the record; the image is intact
+    h->scratch.keep(KEPT_U16, s.in.slot, H, W);
     return S2SR_OK;
 }
 
@@ -98,20 +95,18 @@ int display_apply_impl(s2sr_handle* h, const uint16_t* img, int H, int W, const 
     if (!h) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
     if (!lut || !out) return fail(h, S2SR_E_INVALID, "s2sr_display_apply_u16: lut and out are required");
-    Source s;
+    Source s{KeptInput(h)};
     int rc = plan_source(h, "s2sr_display_apply_u16", img, H, W, band_rows, s);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
-    const int out_slot = s.slot == 1 ? 0 : 1;                // the 8-bit image: the other of 0 / 1, as the pyramid calls do
-    if (img && (rc = ensure_scratch(h, 0, (s.total * 2 + 255) & ~(size_t)255))) return rc;
-    if ((rc = ensure_scratch(h, out_slot, s.total))) return rc;
-    if ((rc = ensure_scratch(h, 3, kHistBytes + kLutBytes))) return rc;
+    const Slot out_slot = other(s.in.slot);                   // the 8-bit image: the other of 0 / 1, as the pyramid calls do
+    if ((rc = ensure_scratch(h, {{SL_SRC, (s.total * 2 + 255) & ~(size_t)255, img != nullptr}, {out_slot, s.total}, {SL_TABLES, kHistBytes + kLutBytes}}))) return rc;
     if ((rc = ensure_group_events(h, 4))) return rc;
-    const uint16_t* d_img = (const uint16_t*)h->d_scratch[s.slot];
-    uint8_t* d_out = (uint8_t*)h->d_scratch[out_slot];
-    uint8_t* d_lut = (uint8_t*)h->d_scratch[3] + kHistBytes;
+    const uint16_t* d_img = scratch<const uint16_t>(h, s.in.slot);
+    uint8_t* d_out = scratch<uint8_t>(h, out_slot);
+    uint8_t* d_lut = scratch<uint8_t>(h, SL_TABLES) + kHistBytes;
     HIPCHK(h, hipMemcpyAsync(d_lut, lut, kLutBytes, hipMemcpyHostToDevice, st));
     // band i + 1 uploads under band i's kernel (a host image); band i's bytes leave under band i + 1's
     hipEvent_t* up = &h->group_done[0];
@@ -137,7 +132,7 @@ int display_apply_impl(s2sr_handle* h, const uint16_t* img, int H, int W, const 
     if ((rc = d2h_staged(h, out + pb0, d_out + pb0, pb1 - pb0, true))) return rc;
     HIPCHK(h, hipStreamSynchronize(h->copy_stream));
     HIPCHK(h, hipStreamSynchronize(st));
-    h->disp_slot = s.slot; h->disp_h = H; h->disp_w = W;     // as display_hist_impl
+    h->scratch.keep(KEPT_U16, s.in.slot, H, W);
     return S2SR_OK;
 }
 

@@ -4,13 +4,34 @@
 #pragma once
 #include <stdio.h>
 
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "s2sr_internal.h"
+#include "scratch.h"
 
 namespace s2sr::engine {
+
+// The handle's scratch slots (grown on demand, shared by every door; the book-keeping is csrc/scratch.h).  The numbers are debug ABI
+// (include/s2sr.h: scratch_peek, redzone_poke, the mask of poison_scratch).  THE table of what each holds, door family by family:
+enum Slot : int {
+    SL_SRC = 0,   // 0 and 1: a call's source and its result: the upload and the image / tiles / level that leave.  Along a chain of
+    SL_DST,       //   pyramid or display calls the roles swap: the source is where the call before kept its result, the result other() of it
+    SL_MID,       // what lies between: gathered windows (the untiled image's tiles), the 16-bit batch's quantised tiles, the resample
+                  //   intermediate, the PNG writer's statistics
+    SL_TABLES,    // tables and plans: paste / blend tables, warp grid, footprint and tap tables, PNG plans, display histogram + LUT
+    SL_CHUNK,     // a chunk's tile outputs, the unbanded post-process's image, the PNG streams of even groups
+    SL_PP,        // the post-process work area, where a banded run lives while it is open; the PNG streams of odd groups (the level the
+                  //   writer reads is in 0 / 1, so while it runs 2 .. 5 are free)
+    SL_VALID,     // the device copy of a masked call's `valid` (nodata.hip)
+    SL_CONS,      // a consistency pass's inexact counters (uint64[3], the first 256 bytes) and, in mode 2, its residual plane (consistency.hip)
+};
+static_assert(SL_CONS + 1 == slots::kSlots, "one enumerator per slot");
+inline Slot other(Slot s) { return s == SL_DST ? SL_SRC : SL_DST; }            // of the 0 / 1 pair
+inline Slot png_stream_slot(int group) { return group & 1 ? SL_PP : SL_CHUNK; }   // tiles_write_png_locked: the streams ping-pong
+using slots::KEPT_RASTER; using slots::KEPT_LEVEL; using slots::KEPT_U16;
 
 // The net, layer by layer, in the order of the weight blob: the one place a layer or a model is declared.  layer_table() builds
 // it from the config; the blob sizes of the C ABI, the loader (load_weights_locked: one case per role) and the schedules
@@ -167,9 +188,7 @@ struct CompactTap {
 
 }  // namespace s2sr::engine
 
-// A device buffer added to this struct is also added to the list in s2sr_debug_redzone_check (redzone.hip), which counts the
-// handle's zoned allocations: d_trash, pool_w / pool_s / pool_b, the convs' own d_wpack / d_wphase, first16.d_wpack, ws.base,
-// d_scratch, stitch_sets[].d.
+// A device buffer added to this struct is also added to for_each_device_buffer below.
 struct s2sr_handle {
     s2sr_config cfg{};
     // RealESRGAN_x2plus (cfg.scale 2) runs pixel_unshuffle(x, 2) and then the x4 net on the half grid.  Every entry takes input
@@ -195,19 +214,10 @@ struct s2sr_handle {
     bool has_weights = false;
     char* d_trash = nullptr;      // parking area for out-of-image epilogue stores
     s2sr::engine::Workspace ws;
-    // scratch device buffers (grown on demand)
-    // 0 .. 5: the calls' staging areas; 6: the device copy of a masked call's `valid` (nodata.hip), an area of its own because
-    // upload_tables owns 3 and the others hold images; 7: a consistency pass's inexact counters (uint64[3], the first 256 bytes) and,
-    // in mode 2, its residual plane (consistency.hip)
-    static constexpr int kScratchSlots = 8;
-    void* d_scratch[kScratchSlots] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_bytes[kScratchSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the scratch slots (enum Slot), what the last call kept in one of them for the next (the pyramid calls a raster or a level, the
+    // 16-bit enhance doors and the display calls a uint16 image), and whether a banded post-process run is open in SL_PP
+    s2sr::slots::Book scratch{s2sr::engine::SL_PP};
     int capture_failures = 0;            // captures voided by a device-wide call of another runtime user; 3 -> graphs off
-    int tiles_slot = -1;                 // scratch slot that still holds the tile level the last pyramid call produced (-1: none)
-    int tiles_nx = 0, tiles_ny = 0;
-    int warp_slot = -1, warp_h = 0, warp_w = 0;   // ... and the RGBA raster the last warp produced (s2sr_tiles_base_u8 with rgba == NULL)
-    int disp_slot = -1, disp_h = 0, disp_w = 0;   // ... and the uint16 [disp_h, disp_w, 3] image the 16-bit enhance doors (x4, scratch 1) or a
-                                                  // display call (its upload, scratch 0) left there (s2sr_display_*_u16 with img == NULL)
     // profiling
     int prof = 0;                 // 0 off, N>=1: bracket every N-th launch of each family with events
     bool span_on = false;         // a sampled span of consecutive launches of ONE family is open (span_begin / span_end): its launches
@@ -256,7 +266,7 @@ struct s2sr_handle {
     // the banded post-process in progress on this handle (s2sr_pp_band_*_dev, or a whole-image job: enhance_locked): geometry, channel order, how far the
     // CLAHE'd rows and the finished rows reach
     struct PPBand {
-        bool open = false, lut = false;
+        bool lut = false;             // (whether the run is open: scratch.run_open)
         int H = 0, W = 0, bgr = 0, swap_out = 0, radius = 0;
         int applied_end = 0, rows_end = 0;
         s2sr_pp_params prm{};
@@ -296,7 +306,37 @@ bool recover_stream(s2sr_handle* h);
     } while (0)
 
 constexpr size_t kTrashBytes = 8192;   // s2sr_handle::d_trash
-int ensure_scratch(s2sr_handle* h, int slot, size_t bytes);
+// Every device allocation the handle owns, each once: s2sr_destroy frees them, s2sr_debug_redzone_check counts the zoned ones.
+template <class F>
+void for_each_device_buffer(s2sr_handle* h, F f) {
+    f(h->d_trash); f(h->pool_w); f(h->pool_s); f(h->pool_b); f(h->first16.d_wpack); f(h->ws.base);
+    for (const ConvW& c : h->convs) {
+        if (!c.pooled) f(c.d_wpack);
+        f(c.d_wphase[0]); f(c.d_wphase[1]);
+    }
+    for (void* p : h->scratch.ptr) f(p);
+    for (const auto& m : h->stitch_sets) f(m.d);
+}
+
+// Scratch requests, in the order written; `on` false: this one is skipped.  Any request voids what the last call kept (slots::Book::drop).
+struct Want { Slot slot; size_t bytes; bool on = true; };
+int ensure_scratch(s2sr_handle* h, std::initializer_list<Want> wants);
+inline int ensure_scratch(s2sr_handle* h, Slot slot, size_t bytes) { return ensure_scratch(h, {{slot, bytes}}); }
+template <class T = void>
+T* scratch(s2sr_handle* h, Slot s) { return (T*)h->scratch.ptr[s]; }
+// The source of a door that may read what the last call kept: SL_SRC for a host buffer, or the slot take() finds.  The slot is
+// guarded against regrowth while the door runs; keep() at the door's successful end says what it leaves.
+struct KeptInput {
+    s2sr_handle* h;
+    Slot slot = SL_SRC;
+    explicit KeptInput(s2sr_handle* h_) : h(h_) {}
+    ~KeptInput() { h->scratch.release(); }
+    bool take(slots::Kind kind, int a, int b) {
+        const int s = h->scratch.take(kind, a, b);
+        if (s >= 0) slot = (Slot)s;
+        return s >= 0;
+    }
+};
 hipError_t copy_blocking(s2sr_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
 hipError_t fill_blocking(s2sr_handle* h, void* dst, int value, size_t bytes);
 
@@ -334,9 +374,9 @@ enum Site {
 // The negative control (s2sr_debug_delay_drop) may skip the stream-waits of these sites and no others.  At each of them the waiting
 // stream is the copy stream and what it runs next is a device-to-host hipMemcpyAsync of finished pixel bytes, with source, size and
 // destination computed on the host before the wait: a wait that is missing lets the copy read pixels too early and nothing else.
-//   SITE_BATCH_GROUP_D2H   d2h_staged of scratch 1 [g0 tout, n tout): u8 tiles; no kernel runs on the copy stream
-//   SITE_CHUNK_BAND_D2H    d2h_staged of rows [prev_yb, prev_ye) of the quantised image (scratch 1 / 2 / 4): pixels; as above
-//   SITE_DISPLAY_BAND_D2H  d2h_staged of bytes [pb0, pb1) of the 8-bit image (scratch 0 / 1); the NEXT upload on the copy stream
+//   SITE_BATCH_GROUP_D2H   d2h_staged of SL_DST [g0 tout, n tout): u8 tiles; no kernel runs on the copy stream
+//   SITE_CHUNK_BAND_D2H    d2h_staged of rows [prev_yb, prev_ye) of the quantised image (SL_DST): pixels; as above
+//   SITE_DISPLAY_BAND_D2H  d2h_staged of bytes [pb0, pb1) of the 8-bit image (SL_SRC / SL_DST); the NEXT upload on the copy stream
 //                          writes the uint16 image in the other slot, which this wait never guarded
 //   SITE_COPY_TO_HOST      d2h_staged of the caller's [d_src, d_src + bytes)
 // Never droppable: SITE_DISPLAY_UPLOAD (a kernel consumes it), SITE_HANDLE_ORDER (tables, plans and LUTs of the call before live in

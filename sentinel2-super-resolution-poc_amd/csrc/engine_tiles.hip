@@ -32,19 +32,17 @@ int s2sr_warp_bilinear_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t
     hipStream_t st = h->stream;
     const size_t ib = (size_t)H * W * 3, gb = (size_t)gh * gw * 8, ob = (size_t)OH * OW * 4;
     int rc;
-    if ((rc = ensure_scratch(h, 0, ib))) return rc;
-    if ((rc = ensure_scratch(h, 1, ob))) return rc;
-    if ((rc = ensure_scratch(h, 3, gb))) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[0], rgb, ib, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[3], grid, gb, hipMemcpyHostToDevice, st));
+    if ((rc = ensure_scratch(h, {{SL_SRC, ib}, {SL_DST, ob}, {SL_TABLES, gb}}))) return rc;
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), rgb, ib, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_TABLES), grid, gb, hipMemcpyHostToDevice, st));
     {
         Scope sc(h, st, F_MISC, 0.0, (double)ob + (double)OH * OW * 12.0);
-        HIPCHK(h, launch_warp_bilinear((const uint8_t*)h->d_scratch[0], H, W, (const float*)h->d_scratch[3], gh, gw, step, OH, OW,
-                                       (uint8_t*)h->d_scratch[1], st));
+        HIPCHK(h, launch_warp_bilinear(scratch<const uint8_t>(h, SL_SRC), H, W, scratch<const float>(h, SL_TABLES), gh, gw, step, OH, OW,
+                                       scratch<uint8_t>(h, SL_DST), st));
     }
-    HIPCHK(h, hipMemcpyAsync(out_rgba, h->d_scratch[1], ob, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(out_rgba, scratch(h, SL_DST), ob, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    h->warp_slot = 1; h->warp_h = OH; h->warp_w = OW;      // the raster also stays on the device for the base level of its pyramid
+    h->scratch.keep(KEPT_RASTER, SL_DST, OH, OW);          // the raster also stays on the device for the base level of its pyramid
     return S2SR_OK;
 }
 
@@ -62,31 +60,26 @@ int s2sr_tiles_base_u8(s2sr_handle* h, const uint8_t* rgba, int32_t H, int32_t W
     const size_t ib = (size_t)H * W * 4, ob = (size_t)nx * ny * 65536 * 4, cb = (size_t)nx * 256 * 4, rb = (size_t)ny * 256 * 4;
     // rgba == NULL: the raster is the one the previous call on this handle -- s2sr_warp_bilinear_u8 -- produced, taken from its
     // device copy (a 4096 x 4096 source: 67 MB that would cross PCIe twice between the two calls)
-    int in_slot = 0;
-    if (!rgba) {
-        if (h->warp_slot < 0 || h->warp_h != H || h->warp_w != W)
-            return fail(h, S2SR_E_INVALID, "rgba == NULL, but the previous call on this handle did not leave a warped raster of this size on the device");
-        in_slot = h->warp_slot;
-    }
-    const int out_slot = in_slot == 1 ? 0 : 1;
+    KeptInput in(h);
+    if (!rgba && !in.take(KEPT_RASTER, H, W))
+        return fail(h, S2SR_E_INVALID, "rgba == NULL, but the previous call on this handle did not leave a warped raster of this size on the device");
+    const Slot out_slot = other(in.slot);
     int rc;
-    if (rgba && (rc = ensure_scratch(h, in_slot, ib))) return rc;
-    if ((rc = ensure_scratch(h, out_slot, ob))) return rc;
-    if ((rc = ensure_scratch(h, 3, 2 * cb + 2 * rb))) return rc;
-    int32_t* t = (int32_t*)h->d_scratch[3];
-    if (rgba) HIPCHK(h, hipMemcpyAsync(h->d_scratch[in_slot], rgba, ib, hipMemcpyHostToDevice, st));
+    if ((rc = ensure_scratch(h, {{in.slot, ib, rgba != nullptr}, {out_slot, ob}, {SL_TABLES, 2 * cb + 2 * rb}}))) return rc;
+    int32_t* t = scratch<int32_t>(h, SL_TABLES);
+    if (rgba) HIPCHK(h, hipMemcpyAsync(scratch(h, in.slot), rgba, ib, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(t, col_lo, cb, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(t + nx * 256, col_hi, cb, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(t + 2 * nx * 256, row_lo, rb, hipMemcpyHostToDevice, st));
     HIPCHK(h, hipMemcpyAsync(t + 2 * nx * 256 + ny * 256, row_hi, rb, hipMemcpyHostToDevice, st));
     {
         Scope sc(h, st, F_MISC, 0.0, (double)ib + (double)ob);
-        HIPCHK(h, launch_tiles_base((const uint8_t*)h->d_scratch[in_slot], W, t, t + nx * 256, t + 2 * nx * 256, t + 2 * nx * 256 + ny * 256, nx,
-                                    ny, (uint8_t*)h->d_scratch[out_slot], st));
+        HIPCHK(h, launch_tiles_base(scratch<const uint8_t>(h, in.slot), W, t, t + nx * 256, t + 2 * nx * 256, t + 2 * nx * 256 + ny * 256, nx,
+                                    ny, scratch<uint8_t>(h, out_slot), st));
     }
-    if (out) HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[out_slot], ob, hipMemcpyDeviceToHost, st));      // out == NULL: the level stays on the device
+    if (out) HIPCHK(h, hipMemcpyAsync(out, scratch(h, out_slot), ob, hipMemcpyDeviceToHost, st));      // out == NULL: the level stays on the device
     HIPCHK(h, hipStreamSynchronize(st));
-    h->tiles_slot = out_slot; h->tiles_nx = nx; h->tiles_ny = ny;
+    h->scratch.keep(KEPT_LEVEL, out_slot, nx, ny);
     return S2SR_OK;
 }
 
@@ -100,31 +93,25 @@ int s2sr_tiles_overview_u8(s2sr_handle* h, const uint8_t* child, int32_t cnx, in
     const size_t ib = (size_t)cnx * cny * 65536 * 4, ob = (size_t)pnx * pny * 65536 * 4;
     // child == NULL: the children are the level the previous pyramid call on this handle produced, still on the device (a
     // z18 level is 2.9 GB: sending it back costs as much as fetching it did)
-    int in_slot = 0;
-    if (!child) {
-        if (h->tiles_slot < 0 || h->tiles_nx != cnx || h->tiles_ny != cny)
-            return fail(h, S2SR_E_INVALID, "child == NULL, but the previous call on this handle did not leave a tile level of this size on the device");
-        in_slot = h->tiles_slot;
-    }
-    const int out_slot = in_slot == 1 ? 0 : 1;
+    KeptInput in(h);
+    if (!child && !in.take(KEPT_LEVEL, cnx, cny))
+        return fail(h, S2SR_E_INVALID, "child == NULL, but the previous call on this handle did not leave a tile level of this size on the device");
+    const Slot out_slot = other(in.slot);
     int rc;
-    if (child && (rc = ensure_scratch(h, in_slot, ib))) return rc;
-    if ((rc = ensure_scratch(h, out_slot, ob))) return rc;
-    if (child) HIPCHK(h, hipMemcpyAsync(h->d_scratch[in_slot], child, ib, hipMemcpyHostToDevice, st));
+    if ((rc = ensure_scratch(h, {{in.slot, ib, child != nullptr}, {out_slot, ob}}))) return rc;
+    if (child) HIPCHK(h, hipMemcpyAsync(scratch(h, in.slot), child, ib, hipMemcpyHostToDevice, st));
     {
         Scope sc(h, st, F_MISC, 0.0, (double)ib + (double)ob);
-        HIPCHK(h, launch_tiles_overview((const uint8_t*)h->d_scratch[in_slot], cnx, cny, ox, oy, pnx, pny, (uint8_t*)h->d_scratch[out_slot], st));
+        HIPCHK(h, launch_tiles_overview(scratch<const uint8_t>(h, in.slot), cnx, cny, ox, oy, pnx, pny, scratch<uint8_t>(h, out_slot), st));
     }
-    if (out) HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[out_slot], ob, hipMemcpyDeviceToHost, st));
+    if (out) HIPCHK(h, hipMemcpyAsync(out, scratch(h, out_slot), ob, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    h->tiles_slot = out_slot; h->tiles_nx = pnx; h->tiles_ny = pny;
+    h->scratch.keep(KEPT_LEVEL, out_slot, pnx, pny);
     return S2SR_OK;
 }
 
 // A level resampled through tap tables (resample.hip): the deepest one from a raster, a shallower one from the level below it.
-// Same protocol as the two calls above: the source in scratch 0 (or where the previous call left it), the level in the other of
-// 0 / 1, tables in 3; the 8-bit intermediate between the passes lives in scratch 2, which only s2sr_tiles_write_png uses, and only
-// inside its own call.
+// Same protocol as the two calls above (enum Slot); the 8-bit intermediate between the passes lives in SL_MID.
 int s2sr_tiles_resample_u8(s2sr_handle* h, const uint8_t* src, int32_t src_kind, int32_t sa, int32_t sb, const int32_t* col_first,
                            const int32_t* col_count, const int32_t* col_coef, int32_t Kx, const int32_t* row_first,
                            const int32_t* row_count, const int32_t* row_coef, int32_t Ky, int32_t nx, int32_t ny, uint8_t* out) {
@@ -150,18 +137,15 @@ int s2sr_tiles_resample_u8(s2sr_handle* h, const uint8_t* src, int32_t src_kind,
     std::lock_guard<std::mutex> lk(h->mu);
     // src == NULL: the source is what the previous call on this handle left on the device -- the raster of s2sr_warp_bilinear_u8,
     // or the level of a base / overview / resample call
-    int in_slot = 0;
-    if (!src) {
-        if (!level && (h->warp_slot < 0 || h->warp_h != sa || h->warp_w != sb))
-            return fail(h, S2SR_E_INVALID, "src == NULL, but the previous call on this handle did not leave a warped raster of this size on the device");
-        if (level && (h->tiles_slot < 0 || h->tiles_ny != sa || h->tiles_nx != sb))
-            return fail(h, S2SR_E_INVALID, "src == NULL, but the previous call on this handle did not leave a tile level of this size on the device");
-        in_slot = level ? h->tiles_slot : h->warp_slot;
-    }
+    KeptInput in(h);
+    if (!src && !level && !in.take(KEPT_RASTER, sa, sb))
+        return fail(h, S2SR_E_INVALID, "src == NULL, but the previous call on this handle did not leave a warped raster of this size on the device");
+    if (!src && level && !in.take(KEPT_LEVEL, sb, sa))
+        return fail(h, S2SR_E_INVALID, "src == NULL, but the previous call on this handle did not leave a tile level of this size on the device");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
-    const int out_slot = in_slot == 1 ? 0 : 1;
+    const Slot out_slot = other(in.slot);
     const int nrows = r_hi - r_lo;                                  // the source rows some output row reads
     const size_t ib = (size_t)src_h * src_w * 4, ob = (size_t)MW * MH * 4, mb = (size_t)MW * (nrows > 0 ? nrows : 1) * 4;
     const size_t cw = (size_t)MW * (2 + Kx), rw = (size_t)MH * (2 + Ky);
@@ -169,26 +153,23 @@ int s2sr_tiles_resample_u8(s2sr_handle* h, const uint8_t* src, int32_t src_kind,
     resample_pack_axis(col_first, col_count, col_coef, MW, Kx, tables.data());
     resample_pack_axis(row_first, row_count, row_coef, MH, Ky, tables.data() + cw);
     int rc;
-    if (src && (rc = ensure_scratch(h, in_slot, ib))) return rc;
-    if ((rc = ensure_scratch(h, out_slot, ob))) return rc;
-    if ((rc = ensure_scratch(h, 2, mb))) return rc;
-    if ((rc = ensure_scratch(h, 3, (cw + rw) * 4))) return rc;
-    const int32_t* tc = (const int32_t*)h->d_scratch[3];
+    if ((rc = ensure_scratch(h, {{in.slot, ib, src != nullptr}, {out_slot, ob}, {SL_MID, mb}, {SL_TABLES, (cw + rw) * 4}}))) return rc;
+    const int32_t* tc = scratch<const int32_t>(h, SL_TABLES);
     const int32_t* tr = tc + cw;
-    if (src) HIPCHK(h, hipMemcpyAsync(h->d_scratch[in_slot], src, ib, hipMemcpyHostToDevice, st));
-    HIPCHK(h, hipMemcpyAsync(h->d_scratch[3], tables.data(), (cw + rw) * 4, hipMemcpyHostToDevice, st));
+    if (src) HIPCHK(h, hipMemcpyAsync(scratch(h, in.slot), src, ib, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_TABLES), tables.data(), (cw + rw) * 4, hipMemcpyHostToDevice, st));
     {
         Scope sc(h, st, F_MISC, 0.0, (double)nrows * (double)(c_hi - c_lo) * 4.0 + (double)mb);      // algorithmic: each byte once
-        HIPCHK(h, launch_resample_h((const uint8_t*)h->d_scratch[in_slot], level, sb, tc, tc + MW, tc + 2 * MW, nx, r_lo, nrows,
-                                    (uint8_t*)h->d_scratch[2], st));
+        HIPCHK(h, launch_resample_h(scratch<const uint8_t>(h, in.slot), level, sb, tc, tc + MW, tc + 2 * MW, nx, r_lo, nrows,
+                                    scratch<uint8_t>(h, SL_MID), st));
     }
     {
         Scope sc(h, st, F_MISC, 0.0, (double)mb + (double)ob);
-        HIPCHK(h, launch_resample_v((const uint8_t*)h->d_scratch[2], r_lo, tr, tr + MH, tr + 2 * MH, nx, ny, (uint8_t*)h->d_scratch[out_slot], st));
+        HIPCHK(h, launch_resample_v(scratch<const uint8_t>(h, SL_MID), r_lo, tr, tr + MH, tr + 2 * MH, nx, ny, scratch<uint8_t>(h, out_slot), st));
     }
-    if (out) HIPCHK(h, hipMemcpyAsync(out, h->d_scratch[out_slot], ob, hipMemcpyDeviceToHost, st));      // out == NULL: the level stays on the device
+    if (out) HIPCHK(h, hipMemcpyAsync(out, scratch(h, out_slot), ob, hipMemcpyDeviceToHost, st));      // out == NULL: the level stays on the device
     HIPCHK(h, hipStreamSynchronize(st));
-    h->tiles_slot = out_slot; h->tiles_nx = nx; h->tiles_ny = ny;
+    h->scratch.keep(KEPT_LEVEL, out_slot, nx, ny);
     return S2SR_OK;
 }
 
@@ -198,10 +179,10 @@ int s2sr_tiles_resample_u8(s2sr_handle* h, const uint8_t* src, int32_t src_kind,
 static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const char* const* paths, int32_t flags, int32_t* written) {
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
-    if (h->tiles_slot < 0 || h->tiles_nx != nx || h->tiles_ny != ny)
+    KeptInput in(h);
+    if (!in.take(KEPT_LEVEL, nx, ny))
         return fail(h, S2SR_E_INVALID, "the previous call on this handle did not leave a tile level of this size on the device");
-    const int slot = h->tiles_slot;
-    const uint8_t* d_tiles = (const uint8_t*)h->d_scratch[slot];
+    const uint8_t* d_tiles = scratch<const uint8_t>(h, in.slot);
     const int n = nx * ny;
     hipStream_t st = h->stream;
     const bool timing = getenv("S2SR_PNG_TIMING") != nullptr;
@@ -223,8 +204,7 @@ static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const 
     const int gsz = (n + ngroups - 1) / ngroups;
     const size_t tile_stats_b = (512 + 512 + 1) * 4;                       // per tile: token histogram, row Adler pairs, any-alpha flag
     int rc;
-    if ((rc = ensure_scratch(h, 2, (size_t)n * tile_stats_b))) return rc;
-    if ((rc = ensure_scratch(h, 3, png_plan_bytes(n)))) return rc;
+    if ((rc = ensure_scratch(h, {{SL_MID, (size_t)n * tile_stats_b}, {SL_TABLES, png_plan_bytes(n)}}))) return rc;
     // the statistics come back into, and the plans go up from, ONE page-locked block kept on the handle (a z18 level: 40 MB down,
     // 27 MB up; as fresh pageable vectors each crossed PCIe through the runtime's staging and was page-faulted in first)
     const size_t stats_b = ((size_t)n * tile_stats_b + 255) & ~(size_t)255, plan_b = png_plan_bytes(n);
@@ -257,9 +237,9 @@ static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const 
         Group& G = groups[g];
         G.a = g * gsz;
         G.n = (G.a + gsz <= n ? gsz : n - G.a);
-        G.d_stats = (uint32_t*)((char*)h->d_scratch[2] + (size_t)G.a * tile_stats_b);
+        G.d_stats = (uint32_t*)(scratch<char>(h, SL_MID) + (size_t)G.a * tile_stats_b);
         G.stats = (const uint32_t*)((const char*)h->host_arena + (size_t)G.a * tile_stats_b);
-        G.d_tables = (uint8_t*)h->d_scratch[3] + png_plan_bytes(G.a);
+        G.d_tables = scratch<uint8_t>(h, SL_TABLES) + png_plan_bytes(G.a);
         G.plan.arena = (char*)h->host_arena + stats_b + png_plan_bytes(G.a);
         G.plan.arena_bytes = png_plan_bytes(G.n);
         G.ev_stats = get_event(h);
@@ -355,9 +335,9 @@ static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const 
             t_plan += now() - t1;
             if (G.plan.failed) { return fail(h, S2SR_E_IO, "planning the tile streams failed (an encoder thread ran out of memory)"); }
             total_words += G.out_words;
-            const int oslot = 4 + (g & 1);                       // the group's stream buffer: scratch 4 / 5 in turn
+            const Slot oslot = png_stream_slot(g);               // the group's stream buffer
             if ((rc = ensure_scratch(h, oslot, (G.out_words + 1) * 4))) return rc;
-            uint32_t* d_out = (uint32_t*)h->d_scratch[oslot];
+            uint32_t* d_out = scratch<uint32_t>(h, oslot);
             HIPCHK(h, hipMemcpyAsync(G.d_tables, G.plan.tb, G.plan.upload_bytes, hipMemcpyHostToDevice, st));
             HIPCHK(h, hipMemsetAsync(d_out, 0, (G.out_words + 1) * 4, st));
             {
@@ -374,7 +354,7 @@ static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const 
             HIPCHK(h, ev_host_wait(h, P.ev_emit, SITE_PNG_EMIT));           // the copy stream may read the group's streams
             double t1 = now();
             t_wait += t1 - t0;
-            if ((rc = write_group(P, (const uint32_t*)h->d_scratch[4 + ((g - 1) & 1)]))) return rc;
+            if ((rc = write_group(P, scratch<const uint32_t>(h, png_stream_slot(g - 1))))) return rc;
             t_files += now() - t1;
         }
     }
@@ -383,7 +363,7 @@ static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const 
         fprintf(stderr, "[s2sr png] %d tiles in %d group(s) (%zu on the host encoder), %.1f ms: waiting for the device %.1f, Huffman codes %.1f, "
                 "streams (%.0f MB) back in batches + files %.1f (of which host-encoded tiles %.1f)\n", n, ngroups, n_host, now() - t_begin, t_wait,
                 t_plan, (double)total_words * 4 / 1e6, t_files, t_hostenc);
-    h->tiles_slot = slot; h->tiles_nx = nx; h->tiles_ny = ny;      // the scratch requests above dropped the marker; the level is intact
+    h->scratch.keep(KEPT_LEVEL, in.slot, nx, ny);                  // the level is intact
     if (failed.load()) return fail(h, S2SR_E_IO, "a tile file could not be written (or an encoder thread ran out of memory)");
     return S2SR_OK;
 }

@@ -133,7 +133,7 @@ void s2sr::poison_host(void* p, size_t bytes, int pat) { (void)poison::fill(kHos
 
 extern "C" {
 
-static_assert(s2sr_handle::kScratchSlots == S2SR_SCRATCH_SLOTS && kTrashBytes == S2SR_TRASH_BYTES, "include/s2sr.h states both");
+static_assert(slots::kSlots == S2SR_SCRATCH_SLOTS && kTrashBytes == S2SR_TRASH_BYTES, "include/s2sr.h states both");
 
 int s2sr_debug_poison(int32_t pattern) {
     if (!poison::valid(pattern)) return fail(nullptr, S2SR_E_INVALID, "poison pattern must be 0 (off), 1 (all 0xFF) or 2 (position-dependent)");
@@ -150,18 +150,14 @@ int s2sr_debug_poison_scratch(s2sr_handle* h, int64_t* slots, int64_t* bytes) {
     if (pat == poison::kOff) return fail(h, S2SR_E_INVALID, "poison mode is off (s2sr_debug_poison)");
     sync_handle(h);
     DeviceGate g;
-    // what ensure_scratch voids, for the same reason: whatever a call left in scratch for the next one is gone
-    h->tiles_slot = -1;
-    h->warp_slot = -1;
-    h->disp_slot = -1;
-    h->ppb.open = false;
+    h->scratch.drop(slots::kAllSlots);
     *slots = 0;
-    for (int i = 0; i < s2sr_handle::kScratchSlots; ++i) {
+    for (int i = 0; i < slots::kSlots; ++i) {
         bytes[i] = 0;
-        if (!h->d_scratch[i] || !h->scratch_bytes[i]) continue;
-        if (!poison::fill(kIo, h->d_scratch[i], h->scratch_bytes[i], pat)) return fail(h, S2SR_E_HIP, "poison fill of a scratch slot failed");
+        if (!h->scratch.ptr[i] || !h->scratch.cap[i]) continue;
+        if (!poison::fill(kIo, h->scratch.ptr[i], h->scratch.cap[i], pat)) return fail(h, S2SR_E_HIP, "poison fill of a scratch slot failed");
         *slots |= (int64_t)1 << i;
-        bytes[i] = (int64_t)h->scratch_bytes[i];
+        bytes[i] = (int64_t)h->scratch.cap[i];
     }
     if (h->d_trash && !poison::fill(kIo, h->d_trash, kTrashBytes, pat)) return fail(h, S2SR_E_HIP, "poison fill of the trash page failed");
     return S2SR_OK;
@@ -170,9 +166,9 @@ int s2sr_debug_poison_scratch(s2sr_handle* h, int64_t* slots, int64_t* bytes) {
 int s2sr_debug_scratch_peek(s2sr_handle* h, int32_t slot, int64_t offset, int64_t n, uint8_t* out) {
     if (!h || !out) return fail(h, S2SR_E_INVALID, "null argument");
     std::lock_guard<std::mutex> lk(h->mu);
-    if (slot < -1 || slot >= s2sr_handle::kScratchSlots) return fail(h, S2SR_E_INVALID, "scratch slot out of range (-1: the trash page, 0..7)");
-    const char* base = slot < 0 ? h->d_trash : (const char*)h->d_scratch[slot];
-    const size_t cap = slot < 0 ? (h->d_trash ? kTrashBytes : 0) : h->scratch_bytes[slot];
+    if (slot < -1 || slot >= slots::kSlots) return fail(h, S2SR_E_INVALID, "scratch slot out of range (-1: the trash page, 0..7)");
+    const char* base = slot < 0 ? h->d_trash : (const char*)h->scratch.ptr[slot];
+    const size_t cap = slot < 0 ? (h->d_trash ? kTrashBytes : 0) : h->scratch.cap[slot];
     if (!base || offset < 0 || n < 0 || (uint64_t)offset > cap || (uint64_t)n > cap - (uint64_t)offset)
         return fail(h, S2SR_E_INVALID, "the range is not inside this scratch slot");
     if (!n) return S2SR_OK;
@@ -194,18 +190,9 @@ int s2sr_debug_redzone_check(s2sr_handle* h, int64_t* allocations, int64_t* dama
     std::lock_guard<std::mutex> lk(h->mu);
     sync_handle(h);
     DeviceGate g;
-    // this handle's own allocations, planes included: what `allocations` counts.  The list follows the device buffers of
-    // s2sr_handle (engine_internal.h, which points here): a new one is added in both places.
+    // this handle's own zoned allocations, the workspace's planes included: what `allocations` counts
     int64_t own = 0;
-    auto count = [&](const void* p) { if (p && registry().find(p)) ++own; };
-    count(h->d_trash); count(h->pool_w); count(h->pool_s); count(h->pool_b); count(h->first16.d_wpack);
-    for (const ConvW& c : h->convs) {
-        if (!c.pooled) count(c.d_wpack);
-        count(c.d_wphase[0]); count(c.d_wphase[1]);
-    }
-    for (int i = 0; i < s2sr_handle::kScratchSlots; ++i) count(h->d_scratch[i]);
-    for (const auto& m : h->stitch_sets) count(m.d);
-    if (h->ws.base && registry().find(h->ws.base)) own += 1 + (int64_t)registry().planes(h->ws.base);
+    for_each_device_buffer(h, [&](const void* p) { if (p && registry().find(p)) own += 1 + (int64_t)registry().planes(p); });
     size_t n = 0, bad = 0;
     redzone::Damage first;
     if (!registry().check_all(kIo, &n, &bad, &first)) return fail(h, S2SR_E_HIP, "red zone read-back failed");
@@ -220,7 +207,7 @@ int s2sr_debug_redzone_poke(s2sr_handle* h, int32_t slot, int64_t offset) {
     std::lock_guard<std::mutex> lk(h->mu);
     if (slot < 0 || slot >= 6) return fail(h, S2SR_E_INVALID, "scratch slot out of range (0..5)");
     redzone::Record r;
-    if (!h->d_scratch[slot] || !registry().find(h->d_scratch[slot], &r)) return fail(h, S2SR_E_INVALID, "this scratch slot has no red zone");
+    if (!h->scratch.ptr[slot] || !registry().find(h->scratch.ptr[slot], &r)) return fail(h, S2SR_E_INVALID, "this scratch slot has no red zone");
     const bool back = offset >= 0;
     const uint64_t dist = back ? (uint64_t)offset : (uint64_t)(-(offset + 1));   // bytes from the user range's edge, 0 = the nearest
     if (dist >= (back ? r.back : r.front)) return fail(h, S2SR_E_INVALID, "offset is not inside the red zone");

@@ -19,34 +19,35 @@ consume what the last call left refuse after poison_scratch(), and with the mode
 
 Garbage read as an index could send a load anywhere, so before this module first ran every ensure_scratch call site was read for
 its index and offset tables: each is uploaded in full, on the stream of the kernel that reads it, before that kernel is queued.
-  engine.hip forward_batch_u8_once 0, 1: tiles uploaded whole; the net writes every output tile.  No table.
-  engine.hip s2sr_forward_batch_u16_dev 1: the fp32 tiles, written by the net before the quantiser reads them.  No table.
-  engine.hip forward_batch_u16_once 0, 1, 2: tiles uploaded whole; fp32 tiles and the quantised image written in full.  No table.
-  engine.hip forward_f32_once 0, 1: input uploaded whole, output written by the net.  No table.
-  engine.hip s2sr_calibrate_fp8 0, 1: as forward_batch_u8; the two maxima live in an allocation of their own, memset per pass.
-  engine_aoi.hip upload_tables 3: rectangles, row table, column table, one behind the other, each copied whole, then a stream
+(The slots by the names of enum Slot, csrc/engine_internal.h: SRC 0, DST 1, MID 2, TABLES 3, CHUNK 4, PP 5, VALID 6, CONS 7.)
+  engine.hip forward_batch_u8_once SRC, DST: tiles uploaded whole; the net writes every output tile.  No table.
+  engine.hip s2sr_forward_batch_u16_dev DST: the fp32 tiles, written by the net before the quantiser reads them.  No table.
+  engine.hip forward_batch_u16_once SRC, DST, MID: tiles uploaded whole; fp32 tiles and the quantised image written in full.  No table.
+  engine.hip forward_f32_once SRC, DST: input uploaded whole, output written by the net.  No table.
+  engine.hip s2sr_calibrate_fp8 SRC, DST: as forward_batch_u8; the two maxima live in an allocation of their own, memset per pass.
+  engine_aoi.hip upload_tables TABLES: rectangles, row table, column table, one behind the other, each copied whole, then a stream
     synchronise: gather, stitch, quantise and blend kernels are queued behind it.  (enhance_locked, s2sr_cut_windows_u8_dev.)
-  engine_aoi.hip postprocess_dev_locked 5: histograms memset in launch_postprocess, LUTs and the CLAHE'd image written before read.
-  engine_aoi.hip pp_band_begin_locked 5: histograms memset by launch_pp_band_begin; a run another call took scratch from is refused.
-  engine_aoi.hip s2sr_postprocess_u8 0, 1: image uploaded whole; output written by the last stage.
-  engine_aoi.hip enhance_locked 0, 1, 2, 4 (2 untiled), 6, 7 and 4 again for an unbanded post-process: image and mask uploaded
-    whole; windows gathered for the whole plan; every chunk's tiles written by the net before the paste; the blend's carry row
+  engine_aoi.hip postprocess_dev_locked PP: histograms memset in launch_postprocess, LUTs and the CLAHE'd image written before read.
+  engine_aoi.hip pp_band_begin_locked PP: histograms memset by launch_pp_band_begin; a run another call took scratch from is refused.
+  engine_aoi.hip s2sr_postprocess_u8 SRC, DST: image uploaded whole; output written by the last stage.
+  engine_aoi.hip enhance_locked SRC, DST, MID, CHUNK (MID untiled), VALID, CONS and CHUNK again for an unbanded post-process: image
+    and mask uploaded whole; windows gathered for the whole plan; every chunk's tiles written by the net before the paste; the blend's carry row
     copied from the chunk before (the first chunk's tables never point in front of it); counters memset by cons_begin, mode 2's
     residual plane written by form 0 for the block rows form 2 reads.
-  engine_aoi.hip consistency_impl 0, 1, 7: both images uploaded (the large one band by band, ahead of the pass), 7 as above.
-  engine_aoi.hip fill_nodata_impl 0, 6: image and mask uploaded whole.
+  engine_aoi.hip consistency_impl SRC, DST, CONS: both images uploaded (the large one band by band, ahead of the pass), CONS as above.
+  engine_aoi.hip fill_nodata_impl SRC, VALID: image and mask uploaded whole.
   engine_aoi.hip s2sr_stitch_rows_u8_dev: the paste maps are an allocation of their own, uploaded whole (blocking) before use.
-  engine_tiles.hip s2sr_warp_bilinear_u8 0, 1, 3: raster and node grid uploaded whole; every output pixel written.
-  engine_tiles.hip s2sr_tiles_base_u8 0 / 1, 3: the four footprint tables (checked against the raster on the host) uploaded whole.
-  engine_tiles.hip s2sr_tiles_overview_u8 0 / 1: child level uploaded whole or left by the call before; no table.
-  engine_tiles.hip s2sr_tiles_resample_u8 0 / 1, 2, 3: both packed tap tables (checked on the host) in one copy; the intermediate
+  engine_tiles.hip s2sr_warp_bilinear_u8 SRC, DST, TABLES: raster and node grid uploaded whole; every output pixel written.
+  engine_tiles.hip s2sr_tiles_base_u8 SRC / DST, TABLES: the four footprint tables (checked against the raster on the host) uploaded whole.
+  engine_tiles.hip s2sr_tiles_overview_u8 SRC / DST: child level uploaded whole or left by the call before; no table.
+  engine_tiles.hip s2sr_tiles_resample_u8 SRC / DST, MID, TABLES: both packed tap tables (checked on the host) in one copy; the intermediate
     rows the vertical pass reads are the rows the horizontal pass writes (r_lo .. r_hi).
-  engine_tiles.hip tiles_write_png_locked 2, 3, 4 / 5: statistics written per tile by the stats kernel (histogram, Adler pairs,
+  engine_tiles.hip tiles_write_png_locked MID, TABLES, CHUNK / PP: statistics written per tile by the stats kernel (histogram, Adler pairs,
     flag); the plan block carries a TileMeta for EVERY tile (skip = 1, out_word set) and token table + cleared header for every
     emitting one; the stream buffer is memset before the atomicOr emit.
-  engine_display.hip display_hist_impl 0, 3: image uploaded band by band ahead of its kernel; histogram memset.
-  engine_display.hip display_apply_impl 0, 0 / 1, 3: as above; the LUT uploaded whole.
-  engine_debug.hip s2sr_debug_mfma_ceiling 2, 3 and s2sr_debug_rdb_persistent 2, 3, 4: measuring prototypes, not doors; their
+  engine_display.hip display_hist_impl SRC, TABLES: image uploaded band by band ahead of its kernel; histogram memset.
+  engine_display.hip display_apply_impl SRC, SRC / DST, TABLES: as above; the LUT uploaded whole.
+  engine_debug.hip s2sr_debug_mfma_ceiling MID, TABLES and s2sr_debug_rdb_persistent MID, TABLES, CHUNK: measuring prototypes, not doors; their
     buffers hold operands whose values do not matter and flags they memset themselves; no index is read from them.
 """
 import numpy as np
