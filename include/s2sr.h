@@ -350,6 +350,34 @@ int  s2sr_display_hist_u16(s2sr_handle* h, const uint16_t* img /* or NULL */, in
 int  s2sr_display_apply_u16(s2sr_handle* h, const uint16_t* img /* or NULL */, int32_t H, int32_t W, const uint8_t* lut /* [3][65536] */,
                             int32_t band_rows, uint8_t* out /* [H,W,3] */);
 
+/* Carrying an extra band to the SR grid: a uint16 band [H, W] the net never saw (NIR, red edge) is upsampled S
+ * times against the uint16 image [S H, S W, 3] a 16-bit door produced, by a local linear model (the fast guided filter), and one
+ * back-projection step then makes every block mean the measured band value again.  Integers throughout; no weights needed.
+ * n = S S; q the guide; w the guide weights (0..255 each, Wt their sum, >= 1); p = clamp(band, lo, hi), lo < hi the band's own range.
+ *   guide:  I[Y, X] = floor((w0 q0 + w1 q1 + w2 q2) / Wt) over the guide's channels as stored; G[y, x] = floor(blocksum(I) / n).
+ *   coefficients, one pair per valid input pixel, from sums over the valid pixels of the window [y - r, y + r] x [x - r, x + r] cut
+ *     at the image border: N (their number), SG, Sp, SGG, SGp; cov = N SGp - SG Sp, var = N SGG - SG SG;
+ *     A = clamp(floor((cov << 16) / (var + N N eps)), -(4 << 16), 4 << 16) (Q16, gain limit 4); C = floor(((Sp << 16) - A SG) / N).
+ *   apply:  A and C interpolated bilinearly between input-pixel centres with the consistency pass's weights (above), an invalid
+ *     neighbour replaced by the pixel itself; Abar, Cbar the undivided weighted sums, den = 4 S S;
+ *     g0 = floor((Abar I + Cbar + (den << 15)) / (den << 16)), g = clamp(g0, lo, hi).
+ *   exact step: the consistency pass's, towards n p: e = n p - blocksum(g), k = floor(e / n), rr = e - n k, sample (i, j) gets
+ *     k + (rank[i][j] < rr), clamped to [lo, hi].
+ *   valid (uint8 [H, W], nonzero = valid; NULL: every pixel): invalid pixels take no part in any sum, their blocks are written `fill`.
+ *   inexact = the valid blocks whose final sum differs from n p (a sample clipped at lo or hi).
+ * sr == NULL: the uint16 image of exactly S H x S W that the previous call on this handle left on the device (s2sr_enhance_u16 and
+ *   its kin, a display call, another carried band).  The call leaves that image intact and names it kept again at its end, a host
+ *   sr's upload likewise: several bands, and a display call afterwards, read one copy.
+ * band_rows (0: the library's choice, ~32 MB of guide) sets the bands of guide rows the call works in; the coefficients trail the
+ *   upload by r input rows, the output the coefficients by one more.  The result does not depend on it.
+ * S2SR_E_INVALID with a text, before the device is touched: S outside {2, 4}, r outside 1..4, eps < 1, a range that is not
+ * 0 <= lo < hi <= 65535, a weight outside 0..255 or all weights zero, fill outside 0..65535, band_rows < 0, a NULL band or out,
+ * non-positive H or W, and sr == NULL without a device image of that size.  The handle keeps working afterwards. */
+int  s2sr_carry_band_u16(s2sr_handle* h, const uint16_t* sr /* [S H, S W, 3] or NULL */, const uint16_t* band /* [H, W] */, int32_t H, int32_t W,
+                         int32_t S, int32_t lo, int32_t hi, const int32_t* w /* [3] */, int32_t r, int32_t eps,
+                         const uint8_t* valid /* [H, W] or NULL */, int32_t fill, int32_t band_rows, uint16_t* out /* [S H, S W] */,
+                         uint64_t* inexact /* or NULL */);
+
 /* Multi-GPU building blocks of _tile_process (cnn_super_resolution.py:244-278), device-resident:
  * cut windows [first, first+count) of the plan into d_tiles [count, wh, ww, 3] (wh/ww = the
  * plan's common window size), and paste ALL T windows' outputs d_tiles [T, 4wh, 4ww, 3] into

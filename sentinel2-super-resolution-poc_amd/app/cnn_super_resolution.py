@@ -304,6 +304,7 @@ class RealESRGAN:
         self.consistency = consistency
         self._cmode = mode_of(consistency)           # refuses an unknown name here, before anything is created
         self.last_inexact_blocks = None
+        self.last_extra = None                # enhance16(extra=...): the ranges, eps and inexact blocks of the carried bands
         self.device = _resolve_device(device)
         print(f"   Device: {self.device}")
 
@@ -410,7 +411,8 @@ class RealESRGAN:
                 return self._engine.enhance_blend_u8(img, tile=self.tile_size, pad=self.tile_pad)
             return self._engine.enhance_u8(img, tile=self.tile_size, pad=self.tile_pad)
 
-    def enhance16(self, img: np.ndarray, value_range=None, display=None, valid=None, nodata=None, fill_radius: int = 32):
+    def enhance16(self, img: np.ndarray, value_range=None, display=None, valid=None, nodata=None, fill_radius: int = 32, extra=None,
+                  extra_range=None, extra_weights=None):
         """HxWx3 uint16 (channel order as given) -> 4Hx4Wx3 uint16, in the source's units: the 16-bit door of the native library
         (upstream RealESRGANer's max_range = 65535 branch; the reference has none).  value_range (lo, hi), None = (0, 65535): the
         net sees (clip(v, lo, hi) - lo) / (hi - lo), the output is lo + rint(clip(y, 0, 1) * (hi - lo)).  Same whole / tiled
@@ -419,7 +421,12 @@ class RealESRGAN:
         output (percentile stretch, s2sr/display.py) made from the output's device copy, without a second upload; per-band
         limits are in the channel order of `img`.
         valid / nodata / fill_radius: as `enhance`; a display stretch that names no nodata of its own leaves the job's out of its
-        statistics."""
+        statistics.
+        extra (HxWxk uint16): bands the net never saw, carried to the output grid against the output's device copy
+        (native.Engine.carry_band_u16: guided upsampling, then block means that reproduce the band), behind the door and in front of
+        the display rendering, under the call's mask.  The carried 4Hx4Wxk array comes back as one more, last, return value.
+        extra_range: one (lo, hi) or one per band; None: each band's own min and max over the valid pixels.  extra_weights: the
+        three guide weights in the channel order of `img` (None: 1, 1, 1).  last_extra: the ranges, eps and inexact blocks per band."""
         if self.scale != 4 or getattr(self.model, "arch", "rrdb") != "rrdb":
             raise ValueError(f"enhance16 is built for the x4 RRDB models, not {self.model_name}")
         if img.ndim != 3 or img.shape[2] != 3:
@@ -442,9 +449,11 @@ class RealESRGAN:
             def door(img, lo, hi, tile, pad):
                 return self._engine.enhance_masked_u16(img, valid, lo, hi, radius=fill_radius, out_nodata=out_nodata, blend=self.seam_blend,
                                                        tile=tile, pad=pad)
+        plan = None if extra is None else self._extra_plan(img, extra, extra_range, extra_weights, valid, out_nodata)
         if display is None:
             with self._engine.chain_lock:
-                return door(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
+                out16 = door(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
+                return out16 if plan is None else (out16, self._carry_extra(plan))
         from s2sr.display import Stretch, render_u16
         stretch = Stretch.of(display)
         if nodata is not None and stretch.nodata is None:
@@ -452,8 +461,42 @@ class RealESRGAN:
             stretch = dataclasses.replace(stretch, nodata=out_nodata)
         with self._engine.chain_lock:        # the engine is shared by every job of the process: nothing between the door and the rendering
             out16 = door(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
+            carried = None if plan is None else self._carry_extra(plan)      # (it leaves the device copy as the door left it)
             disp, info = render_u16(None, stretch, self._engine, shape=out16.shape[:2])
-        return out16, disp, info
+        return (out16, disp, info) if plan is None else (out16, disp, info, carried)
+
+    @staticmethod
+    def _extra_plan(img, extra, extra_range, extra_weights, valid, fill):
+        """The arguments of every band of `extra`, checked before the door runs: [(band [H, W], s2sr.bands.check_args's dict)], valid."""
+        from s2sr import bands as B
+        extra = np.asarray(extra)
+        if extra.ndim != 3 or extra.shape[:2] != img.shape[:2] or extra.shape[2] < 1:
+            raise ValueError(f"extra: expected {img.shape[:2]} x k bands, got shape {extra.shape}")
+        if extra.dtype != np.uint16:
+            raise TypeError(f"extra: expected uint16 bands, got {extra.dtype}")
+        k = extra.shape[2]
+        if extra_range is None:
+            ranges = [B.band_range(extra[..., i], valid) for i in range(k)]
+        else:
+            r = np.asarray(extra_range)
+            if r.shape not in ((2,), (k, 2)):
+                raise ValueError(f"extra_range: one (lo, hi) or one per band ({k}), got {extra_range!r}")
+            ranges = [(int(a), int(b)) for a, b in (np.broadcast_to(r, (k, 2)))]
+        w = B.WEIGHTS if extra_weights is None else extra_weights
+        return [(np.ascontiguousarray(extra[..., i]), B.check_args(4, lo, hi, w, fill=int(fill))) for i, (lo, hi) in enumerate(ranges)], valid
+
+    def _carry_extra(self, plan):
+        """Inside the chain lock, behind the door: every band against the device copy -> uint16 [4H, 4W, k]."""
+        bands, valid = plan
+        out, rec = [], {"ranges": [], "eps": [], "inexact": []}
+        for band, a in bands:
+            g, bad = self._engine.carry_band_u16(band, 4, lo=a["lo"], hi=a["hi"], weights=a["weights"], r=a["r"], eps=a["eps"], valid=valid,
+                                                 fill=a["fill"])
+            out.append(g)
+            rec["ranges"].append((a["lo"], a["hi"])); rec["eps"].append(a["eps"]); rec["inexact"].append(bad)
+        rec.update(weights=bands[0][1]["weights"], r=bands[0][1]["r"])
+        self.last_extra = rec
+        return np.stack(out, axis=-1)
 
     def enhance_job(self, rgb: np.ndarray, post=None, valid=None, nodata=None, fill_radius: int = 32) -> np.ndarray:
         """What a job does around `enhance` (wow_sr.py:85-110, farm_sr.py:156-178) in one native call: RGB in, RGB2BGR, the net,

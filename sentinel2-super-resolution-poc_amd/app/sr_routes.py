@@ -47,6 +47,7 @@ class WowRequest(BaseModel):         # main.py:200-208
     nodata: Optional[Union[int, str]] = None   # not in the reference: the value of the pixels that were never measured, or "tag" (app.wow_sr)
     fill_radius: int = 32            # ... and how far they are filled from their valid neighbours in front of the net (1..64)
     consistency: Optional[str] = None   # not in the reference: "exact" or "smooth" -- block means reproduce the input pixels
+    extra_bands: Optional[Union[str, List[int]]] = None   # not in the reference: "all" or band numbers from 4 on, carried to the SR grid; 16-bit jobs only
 
 
 class SRResponse(BaseModel):         # main.py:230-235
@@ -233,7 +234,7 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
 
     def run_wow_job(job_id, input_file, output_dir, enhance_crops, auto_fetch=True, max_age_days=30,
                     max_cloud_cover=30.0, force_fetch=False, model="realesrgan_x4", seam_blend=False, bit_depth=8,
-                    display=None, nodata=None, fill_radius=32, consistency=None):              # main.py:290-368
+                    display=None, nodata=None, fill_radius=32, consistency=None, extra_bands=None):   # main.py:290-368
         try:
             if input_file is None and auto_fetch:
                 _set(job_id, status="fetching",
@@ -256,6 +257,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                 extra.update(nodata=nodata, fill_radius=fill_radius)
             if consistency is not None:
                 extra["consistency"] = consistency
+            if extra_bands is not None:
+                extra["extra_bands"] = extra_bands
             result = process_wow_sr(input_tif=input_file, output_dir=output_dir, enhance_crops=enhance_crops, model=model, **extra)
             _set(job_id, status="tiling", message="Generating tiles from WOW SR image...")
             # a 16-bit job's tiles show the rendering of its PNG: the job's stretch with the limits it found
@@ -334,6 +337,18 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             except ValueError as e:
                 raise HTTPException(status_code=400, detail=str(e))
         _check_consistency(request.consistency)
+        if request.extra_bands is not None:
+            if request.bit_depth != 16:
+                raise HTTPException(status_code=400, detail="extra_bands are carried on the 16-bit path: pass bit_depth=16")
+            try:
+                from s2sr.bands import select_bands
+                count = None
+                if input_file is not None:                                   # the file is at hand: its band count too
+                    from s2sr import rasterio_lite as rio
+                    count = rio.read_bands_raw(input_file)[0].shape[2]
+                select_bands(request.extra_bands, count)
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
         job_id = f"wow_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
         output_dir = data_dir / "wow" / job_id
         output_dir.mkdir(parents=True, exist_ok=True)
@@ -350,7 +365,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                                   **({"bit_depth": request.bit_depth} if request.bit_depth != 8 else {}),
                                   **({"display": request.display} if request.display is not None else {}),
                                   **({"nodata": request.nodata, "fill_radius": request.fill_radius} if request.nodata is not None else {}),
-                                  **({"consistency": request.consistency} if request.consistency is not None else {}))
+                                  **({"consistency": request.consistency} if request.consistency is not None else {}),
+                                  **({"extra_bands": request.extra_bands} if request.extra_bands is not None else {}))
         msg = (f"WOW SR started: {input_file.name} -> Real-ESRGAN x4 + Enhanced" if input_file else
                f"WOW SR started: auto-fetching best image (last {request.max_age_days}d, cloud <={request.max_cloud_cover}%)")
         return SRResponse(job_id=job_id, status="queued", message=msg)

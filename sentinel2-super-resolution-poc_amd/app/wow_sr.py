@@ -41,7 +41,8 @@ def _nodata_block(value, valid: np.ndarray, fill_radius: int) -> dict:
 
 
 def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend: bool = False, display=None,
-                    enhance_crops: bool = False, nodata=None, fill_radius: int = 32, consistency=None) -> Tuple[Path, dict]:
+                    enhance_crops: bool = False, nodata=None, fill_radius: int = 32, consistency=None, extra_bands=None,
+                    extra_weights=None) -> Tuple[Path, dict]:
     """bit_depth=16 of apply_wow_sr: a uint16 GeoTIFF read raw, value_range = the image's own (min, max) -- the reference's
     min-max (wow_sr.py:67-73) minus its quantisation to 8 bits -- the net fed BGR as ever (:85,94), RealESRGAN.enhance16, RGB back,
     a uint16 GeoTIFF out.  Without `display`: no PNG (the encoder is 8-bit) and no crop-visibility post-process (OpenCV's 8-bit
@@ -49,7 +50,11 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     the output's copy there, is written as the PNG, after the crop-visibility post-process when enhance_crops; the GeoTIFF stays raw.
     nodata (an integer, or "tag"): see apply_wow_sr; the value range is that of the valid pixels (s2sr.nodata.valid_range), the
     GeoTIFF declares the value, the PNG (with `display`) carries the mask as alpha, and the stretch leaves the value out of its
-    statistics unless it names a nodata of its own."""
+    statistics unless it names a nodata of its own.
+    extra_bands ("all" or band numbers from 4 on): those bands of the file are carried to the output grid against the
+    super-resolved image (RealESRGAN.enhance16(extra=...)), each with its own min-max over the valid pixels as its range, and the
+    GeoTIFF holds 3 + k bands: RGB as without the option, then the carried bands in the order given.  extra_weights: the guide
+    weights in R, G, B terms (None: 1, 1, 1)."""
     import dataclasses
 
     from s2sr import rasterio_lite as rio
@@ -64,6 +69,17 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
         raise ValueError(f"bit_depth=16 needs a uint16 GeoTIFF: {e}") from e
     if img.dtype != np.uint16:
         raise ValueError(f"bit_depth=16 needs a uint16 GeoTIFF, {input_path} holds {img.dtype}")
+    extra = numbers = None
+    if extra_bands is not None:
+        from s2sr import bands as xb
+        try:
+            every, _ = rio.read_bands_raw(input_path)
+        except ValueError as e:
+            raise ValueError(f"extra_bands needs a GeoTIFF whose bands share one uint16 layout: {e}") from e
+        numbers = xb.select_bands(extra_bands, every.shape[2])
+        extra = np.ascontiguousarray(every[:, :, [b - 1 for b in numbers]])
+        del every
+        w_rgb = xb.check_args(4, 0, 65535, xb.WEIGHTS if extra_weights is None else extra_weights)["weights"]
     from s2sr.nodata import mask_from_value, valid_range
     valid = value = None
     if nodata is not None:
@@ -75,13 +91,18 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     mask_kw = {} if valid is None else {"valid": valid, "nodata": value, "fill_radius": fill_radius}
     esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}),
                         **({"consistency": consistency} if consistency is not None else {}))
-    display_rgb = info = None
+    display_rgb = info = carried = None
+    if extra is not None:            # the device copy is BGR: the guide weights go in reversed
+        mask_kw = dict(mask_kw, extra=extra, extra_weights=w_rgb[::-1])
     if stretch is None:
         out_bgr = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), **mask_kw)
+        if extra is not None:
+            out_bgr, carried = out_bgr
     else:
         # the device copy is BGR like the net's input: explicit per-band limits go in reversed, the info's come back reversed
         bgr = stretch if stretch.limits is None else dataclasses.replace(stretch, limits=stretch.limits[::-1])
-        out_bgr, disp_bgr, info = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), display=bgr, **mask_kw)
+        out_bgr, disp_bgr, info, *rest = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), display=bgr, **mask_kw)
+        carried = rest[0] if rest else None
         display_rgb = np.ascontiguousarray(disp_bgr[:, :, ::-1])
         info = dict(info, limits=info["limits"][::-1])
         if enhance_crops:
@@ -90,10 +111,15 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     output_rgb = np.ascontiguousarray(out_bgr[:, :, ::-1])
     scale = esrgan.scale
     inexact = None if consistency is None else esrgan.last_inexact_blocks[::-1]      # (the net's image is B, G, R)
+    carried_rec = esrgan.last_extra if carried is not None else None
     del esrgan
     final_output = Path(output_path).with_suffix(".tif")
     final_output.parent.mkdir(parents=True, exist_ok=True)
-    rio.write_geotiff_rgb16(final_output, output_rgb, georef.scaled(scale), **({} if valid is None else {"nodata": value}))
+    if carried is None:
+        rio.write_geotiff_rgb16(final_output, output_rgb, georef.scaled(scale), **({} if valid is None else {"nodata": value}))
+    else:
+        rio.write_geotiff_u16(final_output, np.concatenate([output_rgb, carried], axis=2), georef.scaled(scale),
+                              **({} if valid is None else {"nodata": value}))
     if display_rgb is not None:
         rio.write_png(final_output.with_suffix(".png"), display_rgb, **({} if valid is None else {"valid": valid, "valid_scale": scale}))
     crops = display_rgb is not None and enhance_crops
@@ -122,10 +148,13 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     if consistency is not None:      # the GeoTIFF is the consistent product; the display image and its crop step are renderings of it
         from s2sr.consistency import metadata_block
         metadata["consistency"] = metadata_block(consistency, inexact)
+    if carried_rec is not None:
+        metadata["extra_bands"] = xb.metadata_block(numbers, carried_rec["ranges"], w_rgb, carried_rec["r"], carried_rec["eps"], carried_rec["inexact"])
     return final_output, metadata
 
 
-def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=None, fill_radius: int = 32, consistency=None) -> None:
+def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=None, fill_radius: int = 32, consistency=None,
+                     extra_bands=None, extra_weights=None) -> None:
     from s2sr.consistency import check_args as check_consistency
     from s2sr.nodata import check_args
     check_args(nodata, fill_radius)
@@ -135,6 +164,14 @@ def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=N
         raise ValueError(f"nodata {nodata!r}: an integer in 0..65535")
     if bit_depth not in (8, 16):
         raise ValueError(f"bit_depth {bit_depth!r}: 8 or 16")
+    if extra_bands is not None:
+        from s2sr import bands as xb
+        if bit_depth != 16:
+            raise ValueError("extra_bands are carried on the 16-bit path: pass bit_depth=16 (an 8-bit job has no uint16 image to guide them)")
+        xb.select_bands(extra_bands)               # what can be refused without the file: the form, numbers below 4, repeats
+        xb.check_args(4, 0, 65535, xb.WEIGHTS if extra_weights is None else extra_weights)
+    elif extra_weights is not None:
+        raise ValueError("extra_weights are the guide weights of extra_bands: pass extra_bands")
     if display is not None:
         if bit_depth != 16:
             raise ValueError("display is the 8-bit rendering of a 16-bit job: pass bit_depth=16 (an 8-bit job's image is its display image)")
@@ -147,7 +184,7 @@ def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=N
 
 def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True,
                  model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None, nodata=None,
-                 fill_radius: int = 32, consistency=None) -> Tuple[Path, dict]:
+                 fill_radius: int = 32, consistency=None, extra_bands=None, extra_weights=None) -> Tuple[Path, dict]:
     """Reference wow_sr.py:28-184 -- same outputs (GeoTIFF and/or PNG) and metadata dict.  bit_depth=16 (not in the reference): a
     uint16 GeoTIFF goes through the net without the 8-bit squeeze and comes back as a uint16 GeoTIFF (_apply_wow_sr16).
     display (bit_depth=16 only; a s2sr.display.Stretch or a dict of its fields): the job also writes the PNG, from the output's
@@ -162,12 +199,16 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
     consistency (not in the reference): None, "exact" or "smooth" -- the block means of the super-resolved image
     reproduce the input pixels (RealESRGAN(consistency=...)).  The metadata gains "consistency": {"mode", "inexact_blocks": [r, g,
     b]}, and only then; with enhance_crops the block also says "applied_before": "post_process" -- the crop-visibility step
-    changes radiometry on purpose, so the written 8-bit image is consistent only up to it."""
+    changes radiometry on purpose, so the written 8-bit image is consistent only up to it.
+    extra_bands, extra_weights (bit_depth=16 only; not in the reference): see _apply_wow_sr16.  The GeoTIFF gains
+    the carried bands behind R, G, B and the metadata "extra_bands": {"bands", "ranges", "weights_rgb", "r", "eps", "gain_limit",
+    "inexact_blocks"}, and only then."""
     from s2sr import rasterio_lite as rio
 
-    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency)
+    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency, extra_bands, extra_weights)
     if bit_depth == 16:
-        return _apply_wow_sr16(input_path, output_path, model, seam_blend, display, enhance_crops, nodata, fill_radius, consistency)
+        return _apply_wow_sr16(input_path, output_path, model, seam_blend, display, enhance_crops, nodata, fill_radius, consistency,
+                               extra_bands, extra_weights)
 
     model_display = {"realesrgan_x4": "Real-ESRGAN x4",
                      "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)",
@@ -246,11 +287,11 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
 
 def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True,
                    model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None, nodata=None,
-                   fill_radius: int = 32, consistency=None) -> dict:
+                   fill_radius: int = 32, consistency=None, extra_bands=None, extra_weights=None) -> dict:
     """Reference wow_sr.py:212-266 -- file naming, metadata JSON and result dict schema.  bit_depth=16: see apply_wow_sr (no PNG:
     "sr_png" is None -- unless `display` is given: the PNG is the output's display rendering).  seam_blend, nodata, fill_radius,
-    consistency: see apply_wow_sr."""
-    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency)          # before anything is created
+    consistency, extra_bands, extra_weights: see apply_wow_sr."""
+    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency, extra_bands, extra_weights)   # before anything is created
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
@@ -261,6 +302,10 @@ def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True
         blend.update(nodata=nodata, fill_radius=fill_radius)
     if consistency is not None:
         blend["consistency"] = consistency
+    if extra_bands is not None:
+        blend["extra_bands"] = extra_bands
+        if extra_weights is not None:
+            blend["extra_weights"] = extra_weights
     if bit_depth == 16:
         if display is not None:
             blend["display"] = display

@@ -327,6 +327,17 @@ hipError_t launch_consistency(int form, uint8_t* d_img, const uint8_t* d_lr, int
 hipError_t launch_consistency(int form, uint16_t* d_img, const uint16_t* d_lr, int32_t* d_e, unsigned long long* d_cnt, int H, int W, int S,
                               int by0, int by1, int lo, int hi, hipStream_t st);
 
+// carrying an extra band to the SR grid (bands.hip).  d_q: the guide, uint16 [S H, S W, 3]; d_band: uint16 [H, W];
+// d_valid: uint8 [H, W], nonzero = valid, or null; S 2 or 4; w: the three guide weights (0..255, not all zero).  coeffs: A (int32
+// [H, W], Q16) and C (int64 [H, W]) of pixel rows [y0, y1) -- it reads the guide, the band and the mask of rows y0 - r .. y1 - 1 + r
+// (cut at the image).  apply: block rows [by0, by1) of d_out (uint16 [S H, S W]) -- it reads A and C of rows by0 - 1 .. by1 (clamped
+// to the image); d_cnt: one uint64, the inexact valid blocks, added to; fill goes over the invalid blocks.
+hipError_t launch_band_coeffs(const uint16_t* d_q, const uint16_t* d_band, const uint8_t* d_valid, int32_t* d_A, long long* d_C, int H, int W,
+                              int S, int y0, int y1, int lo, int hi, const int w[3], int r, long long eps, hipStream_t st);
+hipError_t launch_band_apply(const uint16_t* d_q, const uint16_t* d_band, const uint8_t* d_valid, const int32_t* d_A, const long long* d_C,
+                             uint16_t* d_out, unsigned long long* d_cnt, int H, int W, int S, int by0, int by1, int lo, int hi, const int w[3],
+                             int fill, hipStream_t st);
+
 // XYZ tile pyramid (tiles.hip)
 hipError_t launch_warp_bilinear(const uint8_t* d_rgb, int H, int W, const float* d_grid, int gh, int gw, int step, int OH, int OW,
                                 uint8_t* d_out, hipStream_t st);

@@ -151,6 +151,8 @@ _PROTOS = {
     "s2sr_enhance_consistent_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.POINTER(Mask), C.c_int32, C.c_void_p, C.c_void_p]),
     "s2sr_display_hist_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
     "s2sr_display_apply_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "s2sr_carry_band_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "s2sr_enhance_job_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PPParams), C.c_void_p]),
     "s2sr_enhance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tile_process_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -888,6 +890,38 @@ class Engine:
         self._check(self._lib.s2sr_display_apply_u16(self._h, _ptr(img) if img is not None else None, H, W, _ptr(lut), int(band_rows),
                                                      _ptr(out)), "s2sr_display_apply_u16")
         return out
+
+    # -- carrying an extra band to the SR grid (include/s2sr.h; defaults and argument checks: s2sr/bands.py) -----------
+    def carry_band_u16(self, band: np.ndarray, S: int, sr: Optional[np.ndarray] = None, lo: int = 0, hi: int = 65535, weights=(1, 1, 1),
+                       r: int = 2, eps: int = 1, valid=None, fill: int = 0, band_rows: int = 0):
+        """band [H, W] uint16 -> (the band on the SR grid, uint16 [S H, S W], inexact): guided upsampling against sr [S H, S W, 3]
+        uint16, or (sr None) against the S H x S W uint16 image the previous call on this engine left on the device, which stays
+        there for the next band or a display call.  No weights needed."""
+        band = np.asarray(band)
+        if band.dtype != np.uint16:
+            raise TypeError(f"carry_band_u16 takes a uint16 band, got {band.dtype}")
+        if band.ndim != 2:
+            raise ValueError(f"carry_band_u16: expected a band [H, W], got shape {band.shape}")
+        band = np.ascontiguousarray(band)
+        H, W = band.shape
+        S = int(S)
+        if sr is not None:
+            if np.asarray(sr).dtype != np.uint16:
+                raise TypeError(f"carry_band_u16 takes a uint16 image, got {np.asarray(sr).dtype}")
+            sr = np.ascontiguousarray(sr)
+            if sr.shape != (S * H, S * W, 3):
+                raise ValueError(f"carry_band_u16: sr {sr.shape} is not [S H, S W, 3] = {(S * H, S * W, 3)}")
+        if valid is not None:
+            valid = self._valid(valid, H, W, "carry_band_u16")
+        w = np.array([int(x) for x in weights], np.int32)
+        if w.shape != (3,):
+            raise ValueError(f"carry_band_u16: three guide weights are required, got {weights!r}")
+        out = pinned_pool.empty((S * H, S * W), np.uint16) if H > 0 and W > 0 and S > 0 else np.empty((1,), np.uint16)
+        bad = np.zeros(1, np.uint64)
+        self._check(self._lib.s2sr_carry_band_u16(self._h, _ptr(sr) if sr is not None else None, _ptr(band), H, W, S, int(lo), int(hi), _ptr(w),
+                                                  int(r), int(eps), _ptr(valid) if valid is not None else None, int(fill), int(band_rows),
+                                                  _ptr(out), _ptr(bad)), "s2sr_carry_band_u16")
+        return out, int(bad[0])
 
     # -- multi-GPU building blocks (device pointers) ------------------------------------------
     def cut_windows_u8_dev(self, d_img: int, H: int, W: int, tile: int, pad: int, first: int, count: int,

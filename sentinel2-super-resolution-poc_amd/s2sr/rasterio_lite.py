@@ -533,3 +533,93 @@ def write_geotiff_rgb16(path: Path, rgb16: np.ndarray, georef: GeoRef, rows_per_
                 os.unlink(path)            # no half-written GeoTIFF stays behind a failed writer
             except OSError:
                 pass
+
+
+def read_bands_raw(path: Path) -> Tuple[np.ndarray, Optional[GeoRef]]:
+    """-> (HxWxB array of EVERY band AS STORED (dtype of the file), GeoRef).  GeoTIFFs only, through `tiff_lite`: `read_rgb_raw`
+    without its cut to bands 1-3 (the extra bands of app.wow_sr's 16-bit path)."""
+    from . import tiff_lite
+    path = Path(path)
+    if path.suffix.lower() not in (".tif", ".tiff"):
+        raise ValueError(f"{path}: read_bands_raw reads GeoTIFFs (.tif / .tiff)")
+    try:
+        arr, tv = tiff_lite.read_tiff(path)
+    except tiff_lite.TiffError as e:
+        raise ValueError(f"{path}: unsupported raster layout (tiff_lite: {e})") from e
+    georef = GeoRef({t: (tv[t][0] if t == TAG_GEOASCII else tuple(tv[t])) for t in _GEO_TAGS if t in tv}, parse_nodata(tv.get(TAG_GDAL_NODATA)))
+    return np.ascontiguousarray(arr), georef
+
+
+def write_geotiff_u16(path: Path, bands: np.ndarray, georef: GeoRef, nodata=None, rows_per_strip: int = 64) -> None:
+    """uint16 [H, W, B], any B >= 1: the B-band sibling of `write_geotiff_rgb16` -- SamplesPerPixel B, chunky little-endian samples,
+    LZW strips through the same native encoder, the same geo tags.  B = 3 IS write_geotiff_rgb16 (the same bytes).  B >= 4: RGB and
+    B - 3 unspecified ExtraSamples; B = 1, 2: BlackIsZero (B = 2: one ExtraSample)."""
+    import struct
+
+    from . import hostpool, native
+
+    bands = np.asarray(bands)
+    if bands.ndim != 3 or bands.shape[2] < 1 or bands.dtype != np.uint16:
+        raise ValueError(f"expected HxWxB uint16, got {bands.shape} {bands.dtype}")
+    if bands.shape[2] == 3:
+        return write_geotiff_rgb16(path, bands, georef, rows_per_strip, nodata)
+    bands = np.ascontiguousarray(bands.astype("<u2", copy=False))
+    h, w, nb = bands.shape
+    strips = [(y, min(h, y + rows_per_strip)) for y in range(0, h, rows_per_strip)]
+    offs, sizes, pos = [], [], 8
+    ok = False
+    try:
+        with open(path, "wb") as f:
+            f.write(b"II" + struct.pack("<HI", 42, 0))
+            for e in hostpool.pool().map(lambda s: native.tiff_lzw_encode(bands[s[0]:s[1]].reshape(-1).view(np.uint8)), strips):
+                offs.append(pos)
+                sizes.append(len(e))
+                f.write(e)
+                if len(e) & 1:
+                    f.write(b"\0")
+                pos += len(e) + (len(e) & 1)
+                if pos >= (1 << 32) - (1 << 20):
+                    raise ValueError("output exceeds the 4 GiB of a classic TIFF")
+            colour = 3 if nb >= 4 else 1                               # samples the photometric interpretation accounts for
+            ent = [(256, 4, (w,)), (257, 4, (h,)), (258, 3, (16,) * nb), (259, 3, (5,)), (262, 3, (2 if nb >= 4 else 1,)), (273, 4, tuple(offs)),
+                   (277, 3, (nb,)), (278, 4, (rows_per_strip,)), (279, 4, tuple(sizes)), (284, 3, (1,)), (339, 3, (1,) * nb)]
+            if nb > colour:
+                ent.append((338, 3, (0,) * (nb - colour)))             # ExtraSamples: unspecified data
+            for tag, val in georef.tags.items():
+                if tag == TAG_GEOKEYS:
+                    ent.append((tag, 3, tuple(int(v) for v in val)))
+                elif tag == TAG_GEOASCII:
+                    ent.append((tag, 2, val if isinstance(val, str) else str(val)))
+                else:
+                    ent.append((tag, 12, tuple(float(v) for v in val)))
+            if nodata is not None:
+                ent.append((TAG_GDAL_NODATA, 2, _nodata_text(nodata)))
+            ent.sort(key=lambda e: e[0])
+            fmt = {3: "H", 4: "I", 12: "d"}
+            ifd_off = pos
+            val_pos = ifd_off + 2 + 12 * len(ent) + 4
+            ifd, tail = b"", b""
+            for tag, typ, vals in ent:
+                if typ == 2:
+                    data = vals.encode("latin-1") + b"\0"
+                    cnt = len(data)
+                else:
+                    data = struct.pack("<" + fmt[typ] * len(vals), *vals)
+                    cnt = len(vals)
+                e = struct.pack("<HHI", tag, typ, cnt)
+                if len(data) <= 4:
+                    e += data.ljust(4, b"\0")
+                else:
+                    e += struct.pack("<I", val_pos + len(tail))
+                    tail += data + (b"\0" if len(data) & 1 else b"")
+                ifd += e
+            f.write(struct.pack("<H", len(ent)) + ifd + struct.pack("<I", 0) + tail)
+            f.seek(4)
+            f.write(struct.pack("<I", ifd_off))
+        ok = True
+    finally:
+        if not ok:
+            try:
+                os.unlink(path)            # no half-written GeoTIFF stays behind a failed writer
+            except OSError:
+                pass
