@@ -838,6 +838,37 @@ int32_t s2sr_debug_delay_dropped(void);       /* the site being dropped, -1: non
 int  s2sr_debug_stall(s2sr_handle* h, int32_t which, void* stream, int32_t usec);
 int  s2sr_debug_stream_touch(s2sr_handle* h, int32_t which, void* stream, int32_t wait);
 
+/* test hooks: capped grids (csrc/gridcap.hip, csrc/s2sr_internal.h capped_grid).  The fourth question to the doors: does any byte
+ * depend on HOW THE WORK WAS DEALT OUT TO WORKGROUPS?  Every hot kernel is a loop over work items (patches, tiles, blocks' worth of
+ * elements) inside a workgroup that stays; on a 256-CU part a small image gives every workgroup one item, and the second trip
+ * through the loop never runs.  With a cap in force every launch whose kernel loops over its grid takes at most `workgroups`
+ * workgroups (the conv kernels, whose grids stay a positive multiple of 8: max(8, workgroups & ~7)), so small shapes make many
+ * trips.  No kernel changes, and every byte must be what it is without the cap.  Launches where a workgroup IS the work item (the
+ * PNG kernels, the CLAHE histogram / LUT and the blur tile grids) and the diagnostic kernels (ceiling, persist, stall) are never
+ * capped.  Process-wide; off by default, and then every launch has the grid it has without these entries (one relaxed atomic load
+ * per launch).  Not for production: a capped launch leaves most of the device idle.  The environment variable
+ * S2SR_GRID_CAP=<workgroups>, read once when the library is loaded, sets the initial cap (a value that is no number in
+ * 0 .. S2SR_DEBUG_GRID_CAP_MAX is reported on stderr and leaves the mode off).
+ *
+ * The contract: the cap is read when a launch is ENQUEUED.  A captured graph keeps the grids it was captured with, whatever the
+ * cap is when it replays; so a caller that wants capped replays creates its handle, or at least captures, under the cap (handles
+ * cache their graphs per shape).
+ *
+ * s2sr_debug_grid_cap: 0 turns the mode off; 1 .. S2SR_DEBUG_GRID_CAP_MAX the cap.  S2SR_E_INVALID otherwise, and the cap stays
+ *   what it was.
+ * s2sr_debug_grid_cap_stats: the precondition of a test that relies on the cap.  Per launcher family i (names:
+ *   s2sr_debug_grid_cap_family(i), NULL past the last) launches[i] = the launches the cap made smaller since the last reset, and
+ *   max_trips[i] = the largest ceil(work items / workgroups) among them -- how often the busiest workgroup went through its loop.
+ *   Host arithmetic at enqueue time; a replayed graph counts nothing.  `cap` entries of room, at least S2SR_GRID_CAP_FAMILIES;
+ *   *n = the number written. */
+#define S2SR_DEBUG_GRID_CAP_MAX 1048576
+#define S2SR_GRID_CAP_FAMILIES 11
+int  s2sr_debug_grid_cap(int32_t workgroups);
+int32_t s2sr_debug_grid_cap_workgroups(void); /* the cap in force (0: off), for callers that switch it and put it back */
+int  s2sr_debug_grid_cap_stats(int64_t* launches, int64_t* max_trips, int32_t cap, int32_t* n);
+void s2sr_debug_grid_cap_stats_reset(void);
+const char* s2sr_debug_grid_cap_family(int32_t i);
+
 #ifdef __cplusplus
 }
 #endif

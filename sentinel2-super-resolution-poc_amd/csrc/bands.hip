@@ -261,7 +261,7 @@ bool tile_grid(int W, int rows, int& tiles_x, int& ntiles, unsigned& grid) {
     const long long tx = ((long long)W + kTI - 1) / kTI, nt = tx * (((long long)rows + kTI - 1) / kTI);
     if (nt > 0x7fffffffLL) return false;
     tiles_x = (int)tx; ntiles = (int)nt;
-    grid = (unsigned)(nt < 16384 ? nt : 16384);
+    grid = (unsigned)capped_grid((int)(nt < 16384 ? nt : 16384), nt, GF_BANDS);
     return true;
 }
 

@@ -163,7 +163,7 @@ hipError_t launch_form(int form, T* d_img, const T* d_lr, int32_t* d_e, unsigned
     // dword rows: the image's base and the bytes of a row are multiples of 4 (a tile's first column, 64 k pixels, always is; a
     // ragged tile's row then holds S (W - x0) 3 esz bytes, a multiple of 4 with the row)
     const int wide = (uintptr_t)d_img % 4 == 0 && ((size_t)W * S * 3 * sizeof(T)) % 4 == 0;
-    const unsigned grid = (unsigned)(ntiles < 16384 ? ntiles : 16384);
+    const unsigned grid = (unsigned)capped_grid((int)(ntiles < 16384 ? ntiles : 16384), ntiles, GF_CONSISTENCY);
     const dim3 g(grid), b(kThreads);
     if (form == FORM_RESIDUAL)
         hipLaunchKernelGGL((consistency_kernel<T, S, FORM_RESIDUAL>), g, b, 0, st, d_img, d_lr, d_e, d_cnt, H, W, by0, by1, lo, hi, swap, wide, (int)tiles_x, (int)ntiles);

@@ -918,13 +918,7 @@ static hipError_t launch_t(const ConvParams& p, hipStream_t st) {
     q.tilesX = (p.W + G::TW - 1) / G::TW;
     q.tilesY = (p.H + G::TH - 1) / G::TH;
     const int ntiles = q.tilesX * q.tilesY * p.N;
-    int grid = persistent_grid(ncu, OCC, ntiles);   // OCC persistent workgroups per CU
-#if S2SR_DIAG_F8
-    if (F8) {   // diagnostic builds only: run the split-operand convs on a subset of the CUs (S2SR_DIAG_GRID workgroups, multiple of 8)
-        static const int dg = [] { const char* e = getenv("S2SR_DIAG_GRID"); return e ? atoi(e) & ~7 : 0; }();
-        if (dg > 0 && dg < grid) grid = dg;
-    }
-#endif
+    const int grid = persistent_grid(ncu, OCC, ntiles, GF_CONV);   // OCC persistent workgroups per CU (a timing build that wants fewer: S2SR_GRID_CAP)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(WAVES * 64), G::LDS_BYTES, st, q);
     return hipGetLastError();
 }

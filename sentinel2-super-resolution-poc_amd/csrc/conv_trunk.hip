@@ -718,7 +718,7 @@ hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_
     q.tilesX = (p.W + G::TW - 1) / G::TW;
     q.tilesY = (p.H + G::TH - 1) / G::TH;
     const int ntiles = q.tilesX * q.tilesY * p.N;
-    const int grid = persistent_grid(ncu, 1, ntiles);
+    const int grid = persistent_grid(ncu, 1, ntiles, GF_TRUNK_F16);
     if (form) *form = s2sr_debug_trunk_form{1, CT, G::TH, R, FULL, PL, 0, 0, 1, 4, 0, EPI};   // lo_enc: 1, the one encoding (see the epilogue)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDSB, st, q);
     return hipGetLastError();
@@ -1368,7 +1368,7 @@ hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk
     q.tilesX = (p.W + G::TW - 1) / G::TW;
     q.tilesY = (p.H + G::TH - 1) / G::TH;
     const int ntiles = q.tilesX * q.tilesY * p.N;
-    const int grid = persistent_grid(ncu, 1, ntiles);
+    const int grid = persistent_grid(ncu, 1, ntiles, GF_TRUNK_F8);
     if (form) *form = s2sr_debug_trunk_form{2, CT, G::TH, RS, 0, 2, PROD, 0, 0, G::WAVES, NPL, EPI};
     hipLaunchKernelGGL(kern, dim3(grid), dim3((G::WAVES + PROD) * 64), G::LDS_BYTES, st, q);
     return hipGetLastError();

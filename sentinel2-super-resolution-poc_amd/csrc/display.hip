@@ -133,7 +133,10 @@ hipError_t launch_display_hist(const uint16_t* d_img, size_t s0, size_t s1, int 
     const size_t groups = (s1 + kGroup - 1) / kGroup - s0 / kGroup;
     size_t chunks = (groups + kHistThreads - 1) / kHistThreads;
     const size_t cap = (size_t)(2 * ncu / kRanges > 1 ? 2 * ncu / kRanges : 1);   // two rounds of one workgroup per CU
+    const size_t needed = chunks;
     if (chunks > cap) chunks = cap;
+    // the kernel strides over its `chunks` argument, one workgroup per (chunk, range): the grid stays a multiple of kRanges
+    chunks = (size_t)capped_grid((int)(chunks * kRanges), (long long)(needed * kRanges), GF_DISPLAY, kRanges) / kRanges;
     hipLaunchKernelGGL(display_hist_kernel, dim3((unsigned)(chunks * kRanges)), dim3(kHistThreads), kHistLdsBytes, st, d_img, s0, s1, nodata,
                        (int)chunks, d_hist);
     return hipGetLastError();
@@ -144,9 +147,7 @@ hipError_t launch_display_apply(const uint16_t* d_img, size_t s0, size_t s1, con
     if (s1 <= s0) return hipSuccess;
     if (((uintptr_t)d_img & 15) || ((uintptr_t)d_out & 7)) return hipErrorInvalidValue;
     const size_t groups = (s1 + kGroup - 1) / kGroup - s0 / kGroup;
-    size_t blocks = (groups + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(display_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, st, d_img, s0, s1, d_lut, d_out);
+    hipLaunchKernelGGL(display_apply_kernel, dim3((unsigned)stride_grid(groups, 8192, GF_DISPLAY)), dim3(256), 0, st, d_img, s0, s1, d_lut, d_out);
     return hipGetLastError();
 }
 

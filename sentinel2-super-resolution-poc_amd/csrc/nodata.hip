@@ -123,7 +123,7 @@ hipError_t fill_impl(T* d_img, const uint8_t* d_valid, int H, int W, int radius,
     if (ntiles > 0x7fffffffLL) return hipErrorInvalidValue;
     const int SW = kFillCols + 2 * radius, SH = kFillRows + 2 * radius;
     const int lds = ((SH * SW + 15) & ~15) + kFillRows * SW;         // R = 64: 61440 bytes, inside the 64 KB a kernel gets without opting in
-    const unsigned grid = (unsigned)(ntiles < 16384 ? ntiles : 16384);
+    const unsigned grid = (unsigned)capped_grid((int)(ntiles < 16384 ? ntiles : 16384), ntiles, GF_NODATA);
     hipLaunchKernelGGL(nodata_fill_kernel<T>, dim3(grid), dim3(kFillThreads), lds, st, d_img, d_valid, H, W, radius, (int)tiles_x, (int)ntiles);
     return hipGetLastError();
 }
@@ -133,9 +133,7 @@ hipError_t mask_launch(const uint8_t* d_valid, int W, int scale, int yb, int ye,
     if ((uintptr_t)d_out % sizeof(Wd)) return hipErrorInvalidValue;
     const int iy0 = yb / scale, iy1 = (ye + scale - 1) / scale;
     const size_t n = (size_t)(iy1 - iy0) * W;
-    size_t blocks = (n + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(nodata_mask_kernel<Wd>, dim3((unsigned)blocks), dim3(256), 0, st, d_valid, W, scale, iy0, iy1, yb, ye, fill, (Wd*)d_out);
+    hipLaunchKernelGGL(nodata_mask_kernel<Wd>, dim3((unsigned)stride_grid(n, 8192, GF_NODATA)), dim3(256), 0, st, d_valid, W, scale, iy0, iy1, yb, ye, fill, (Wd*)d_out);
     return hipGetLastError();
 }
 

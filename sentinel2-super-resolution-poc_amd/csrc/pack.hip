@@ -16,7 +16,7 @@ typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 typedef f16 f16x8 __attribute__((ext_vector_type(8)));
 
 // blocks of 256 threads for a grid-stride loop over `total` elements, at most `cap` of them
-static inline int grid_for(size_t total, int cap) { return (int)((total + 255) / 256 > (size_t)cap ? (size_t)cap : (total + 255) / 256); }
+static inline int grid_for(size_t total, int most) { return stride_grid(total, most, GF_PACK); }   // under the diagnostic grid cap (s2sr_internal.h)
 
 // ------------------------------------------------------------------------------------------
 // The tile packers: B tiles -> the one-block input plane, one thread per plane pixel, consecutive lanes along a row.
@@ -380,7 +380,7 @@ __global__ void pack_trunk_f16_kernel(const float* __restrict__ w, int cin, int 
 hipError_t launch_pack_trunk_f16(const float* d_w, int cin, int cout, void* d_out, hipStream_t st) {
     const int ns = (cin + 15) / 16, CT = (cout + 31) / 32;
     const size_t total = (size_t)ns * 9 * CT * 512;
-    hipLaunchKernelGGL(pack_trunk_f16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_w, cin, cout, ns, CT, (f16*)d_out);
+    hipLaunchKernelGGL(pack_trunk_f16_kernel, dim3((unsigned)grid_for(total, 0x7fffffff)), dim3(256), 0, st, d_w, cin, cout, ns, CT, (f16*)d_out);
     return hipGetLastError();
 }
 
@@ -440,7 +440,7 @@ hipError_t launch_pack_trunk_f8(const float* d_w, int cin, int cout, void* d_out
     const int nreal = (cin + 31) / 32, npad = (nreal + 1) & ~1, CT = (cout + 31) / 32;
     hipLaunchKernelGGL(f8_scale_kernel, dim3(64), dim3(256), 0, st, d_w, cin, cout, d_wscale);
     const size_t total4 = (size_t)npad * 9 * CT * 256;
-    hipLaunchKernelGGL(pack_trunk_f8_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, st, d_w, cin, cout, nreal, npad, CT, d_wscale,
+    hipLaunchKernelGGL(pack_trunk_f8_kernel, dim3((unsigned)grid_for(total4, 0x7fffffff)), dim3(256), 0, st, d_w, cin, cout, nreal, npad, CT, d_wscale,
                        (uint8_t*)d_out);
     return hipGetLastError();
 }
@@ -484,11 +484,11 @@ __global__ void absmax_e4m3_kernel(const uint8_t* __restrict__ v, size_t n, floa
     if ((threadIdx.x & 63) == 0) atomicMax((unsigned int*)out, __float_as_uint(m));
 }
 hipError_t launch_absmax_f16(const void* d, size_t n_halves, float* d_out, hipStream_t st) {
-    hipLaunchKernelGGL(absmax_f16_kernel, dim3(1024), dim3(256), 0, st, (const f16*)d, n_halves, d_out);
+    hipLaunchKernelGGL(absmax_f16_kernel, dim3((unsigned)capped_grid(1024, (long long)((n_halves + 255) / 256), GF_PACK)), dim3(256), 0, st, (const f16*)d, n_halves, d_out);
     return hipGetLastError();
 }
 hipError_t launch_absmax_e4m3(const void* d, size_t n_bytes, int exp2, float* d_out, hipStream_t st) {
-    hipLaunchKernelGGL(absmax_e4m3_kernel, dim3(1024), dim3(256), 0, st, (const uint8_t*)d, n_bytes, ldexpf(1.0f, -exp2), d_out);
+    hipLaunchKernelGGL(absmax_e4m3_kernel, dim3((unsigned)capped_grid(1024, (long long)((n_bytes + 255) / 256), GF_PACK)), dim3(256), 0, st, (const uint8_t*)d, n_bytes, ldexpf(1.0f, -exp2), d_out);
     return hipGetLastError();
 }
 

@@ -751,13 +751,13 @@ hipError_t launch_postprocess(const uint8_t* d_rgb, int B, int H, int W, const s
         hipLaunchKernelGGL(clahe_lut_kernel, dim3((unsigned)tiles), dim3(256), 0, st, d_hist, g, d_lut);
         uint8_t* o = (s2 || s3) ? d_tmp : d_out;
         const size_t total = (size_t)B * H * W;
-        const unsigned grid = (unsigned)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
         const bool aligned = (((uintptr_t)cur | (uintptr_t)o) & 3) == 0 && total < (1ull << 32);
         if (aligned) {
             const size_t ng = (total + 3) / 4;
-            const unsigned grid4 = (unsigned)((ng + 255) / 256 > 2048 ? 2048 : (ng + 255) / 256);
+            const unsigned grid4 = (unsigned)stride_grid(ng, 2048, GF_POSTPROCESS);
             hipLaunchKernelGGL(clahe_apply4_kernel, dim3(grid4), dim3(256), 0, st, cur, g, B, t, d_lut, o);
         } else {
+            const unsigned grid = (unsigned)stride_grid(total, 2048, GF_POSTPROCESS);
             hipLaunchKernelGGL(clahe_apply_kernel, dim3(grid), dim3(256), 0, st, cur, g, B, t, d_lut, o);
         }
         cur = o;
@@ -871,10 +871,10 @@ hipError_t launch_pp_band_apply(const uint8_t* d_img, int H, int W, const s2sr_p
     const size_t total = (size_t)(y1 - y0) * W;
     if ((((uintptr_t)src | (uintptr_t)dst) & 3) == 0 && total < (1ull << 32)) {
         const size_t ng = (total + 3) / 4;
-        const unsigned grid4 = (unsigned)((ng + 255) / 256 > 2048 ? 2048 : (ng + 255) / 256);
+        const unsigned grid4 = (unsigned)stride_grid(ng, 2048, GF_POSTPROCESS);
         hipLaunchKernelGGL(clahe_apply4_kernel, dim3(grid4), dim3(256), 0, st, src, g, 1, t, w.lut, dst);
     } else {
-        const unsigned grid = (unsigned)((total + 255) / 256 > 2048 ? 2048 : (total + 255) / 256);
+        const unsigned grid = (unsigned)stride_grid(total, 2048, GF_POSTPROCESS);
         hipLaunchKernelGGL(clahe_apply_kernel, dim3(grid), dim3(256), 0, st, src, g, 1, t, w.lut, dst);
     }
     return hipGetLastError();

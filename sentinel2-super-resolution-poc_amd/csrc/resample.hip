@@ -67,7 +67,7 @@ __global__ void __launch_bounds__(256) resample_v_kernel(const uint8_t* __restri
     }
 }
 
-inline int grid_for(size_t total) { return (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256); }
+inline int grid_for(size_t total) { return stride_grid(total, 16384, GF_RESAMPLE); }   // under the diagnostic grid cap (s2sr_internal.h)
 
 }  // namespace
 

@@ -241,10 +241,37 @@ struct KernelLaunchState {
         return hipSuccess;
     }
 };
-// grid of persistent workgroups: occ per CU, a multiple of 8 (one round over the XCDs); fewer tiles than that: the tiles, rounded up to 8
-static inline int persistent_grid(int ncu, int occ, int ntiles) {
+// Grid cap (gridcap.hip; the diagnostic mode of s2sr_debug_grid_cap / S2SR_GRID_CAP; DESIGN.md section 2, "Capped grids"): every
+// launch whose kernel loops over gridDim.x takes its grid through capped_grid, so that a small image can send each workgroup
+// through its loop several times.  `grid` is what the launch would take, `items` what the loop deals out (patches, tiles, or blocks' worth of elements),
+// `quantum` what the grid must stay a multiple of.  Off (the default): one relaxed atomic load, and the grid is what it was.  A
+// launch that the cap made smaller is counted per family, with ceil(items / grid): what the tests read to know that the second
+// trip ran (s2sr_debug_grid_cap_stats).  Launches whose blockIdx IS the work item must not come here: see the list in DESIGN.md.
+enum GridFam : int { GF_CONV, GF_TRUNK_F16, GF_TRUNK_F8, GF_PACK, GF_TILES, GF_RESAMPLE, GF_DISPLAY, GF_NODATA, GF_CONSISTENCY, GF_BANDS,
+                     GF_POSTPROCESS, GF_COUNT };
+inline constexpr const char* kGridFamName[GF_COUNT] = {"conv",    "trunk_f16", "trunk_f8",    "pack",  "tiles",      "resample",
+                                                       "display", "nodata",    "consistency", "bands", "postprocess"};
+extern std::atomic<int> g_grid_cap;             // 0 off
+void grid_cap_note(int fam, long long items, int grid);
+static inline int capped_grid(int grid, long long items, int fam, int quantum = 1) {
+    int cap = g_grid_cap.load(std::memory_order_relaxed);
+    if (!cap) return grid;
+    if (quantum > 1) cap = (cap & ~(quantum - 1)) < quantum ? quantum : cap & ~(quantum - 1);   // quantum: a power of two
+    if (cap >= grid) return grid;
+    grid_cap_note(fam, items, cap);
+    return cap;
+}
+// grid of persistent workgroups: occ per CU, a multiple of 8 (one round over the XCDs); fewer tiles than that: the tiles, rounded up to 8.
+// The kernels' tile schedulers turn blockIdx into a slot of the round as (blockIdx % 8) * (grid / 8) + blockIdx / 8, which is a
+// permutation only while the grid is a multiple of 8: so a cap of c gives max(8, c & ~7).
+static inline int persistent_grid(int ncu, int occ, int ntiles, int fam) {
     const int grid = (ncu * occ) & ~7;
-    return ntiles < grid ? (ntiles + 7) & ~7 : grid;
+    return capped_grid(ntiles < grid ? (ntiles + 7) & ~7 : grid, ntiles, fam, 8);
+}
+// grid of a grid-stride loop over `total` elements, 256 per block, at most `most` blocks
+static inline int stride_grid(size_t total, int most, int fam) {
+    const size_t blocks = (total + 255) / 256;
+    return capped_grid((int)(blocks > (size_t)most ? (size_t)most : blocks), (long long)blocks, fam);
 }
 
 // conv kernel (conv3x3.hip): one enumerator per family of instantiations.  The loader decides a conv's form once (engine.hip,

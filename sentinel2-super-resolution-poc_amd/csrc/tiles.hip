@@ -104,7 +104,7 @@ __global__ void __launch_bounds__(256) tiles_overview_kernel(const uint8_t* __re
     }
 }
 
-inline int grid_for(size_t total) { return (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256); }
+inline int grid_for(size_t total) { return stride_grid(total, 16384, GF_TILES); }   // under the diagnostic grid cap (s2sr_internal.h)
 
 }  // namespace
 

@@ -226,6 +226,11 @@ _PROTOS = {
     "s2sr_debug_delay_dropped": (C.c_int32, []),
     "s2sr_debug_stall": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
     "s2sr_debug_stream_touch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),
+    "s2sr_debug_grid_cap": (C.c_int, [C.c_int32]),
+    "s2sr_debug_grid_cap_workgroups": (C.c_int32, []),
+    "s2sr_debug_grid_cap_stats": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int32)]),
+    "s2sr_debug_grid_cap_stats_reset": (None, []),
+    "s2sr_debug_grid_cap_family": (C.c_char_p, [C.c_int32]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 
@@ -1423,3 +1428,38 @@ Engine.bench_conv = _bench_conv
 
 def device_count() -> int:
     return int(load_library().s2sr_device_count())
+
+GRID_CAP_MAX, GRID_CAP_FAMILIES = 1048576, 11   # include/s2sr.h S2SR_DEBUG_GRID_CAP_MAX, S2SR_GRID_CAP_FAMILIES
+
+
+def grid_cap(workgroups: int):
+    """At most `workgroups` workgroups for every launch whose kernel loops over its grid (include/s2sr.h: s2sr_debug_grid_cap; the
+    conv kernels take max(8, workgroups & ~7)); 0 turns the mode off.  Read when a launch is enqueued: a captured graph keeps its
+    grids.  Process-wide; a diagnostic."""
+    rc = load_library().s2sr_debug_grid_cap(int(workgroups))
+    if rc:
+        raise S2srError(f"s2sr_debug_grid_cap({workgroups}) failed ({_ERR.get(rc, rc)}): 0 or 1..{GRID_CAP_MAX}")
+
+
+def grid_cap_workgroups() -> int:
+    """The cap in force (0: off): what a caller that switches the mode puts back."""
+    return int(load_library().s2sr_debug_grid_cap_workgroups())
+
+
+def grid_cap_families() -> tuple:
+    """the launcher families of grid_cap_stats, in the library's order"""
+    lib = load_library()
+    return tuple(lib.s2sr_debug_grid_cap_family(i).decode() for i in range(GRID_CAP_FAMILIES))
+
+
+def grid_cap_stats(reset: bool = False) -> dict:
+    """{family: (launches the cap made smaller, the largest ceil(work items / workgroups) among them)} since the last reset
+    (include/s2sr.h s2sr_debug_grid_cap_stats); reset: start counting afresh afterwards."""
+    lib = load_library()
+    launches, trips, n = (C.c_int64 * GRID_CAP_FAMILIES)(), (C.c_int64 * GRID_CAP_FAMILIES)(), C.c_int32(0)
+    rc = lib.s2sr_debug_grid_cap_stats(launches, trips, GRID_CAP_FAMILIES, C.byref(n))
+    if rc or n.value != GRID_CAP_FAMILIES:
+        raise S2srError(f"s2sr_debug_grid_cap_stats failed ({_ERR.get(rc, rc)}; {n.value} families)")
+    if reset:
+        lib.s2sr_debug_grid_cap_stats_reset()
+    return {name: (int(launches[i]), int(trips[i])) for i, name in enumerate(grid_cap_families())}

@@ -1,5 +1,5 @@
-"""What the modules that run under a diagnostic mode share (red zones, poison, stall; tests/test_gpu_redzones.py, _poison.py,
-_stall.py, and the nodata and consistency modules, which run under red zones): engines made and closed under a mode, the door
+"""What the modules that run under a diagnostic mode share (red zones, poison, stall, grid cap; tests/test_gpu_redzones.py, _poison.py,
+_stall.py, _gridcap.py, and the nodata and consistency modules, which run under red zones): engines made and closed under a mode, the door
 table's baseline with every mode off, the byte-for-byte comparison and the red-zone verdict."""
 import contextlib
 
@@ -46,13 +46,14 @@ def engines_under(read, write, value=None):
 
 @contextlib.contextmanager
 def modes_off():
-    """all three modes off, each put back afterwards: what runs inside allocates, reads and waits as the shipped library does"""
-    zone, pattern, (mode, usec) = native.redzone_bytes(), native.poison_pattern(), native.delay_mode()
-    native.redzone(0), native.poison(0), native.delay(0)
+    """all four modes off, each put back afterwards: what runs inside allocates, reads, waits and deals its work out as the shipped
+    library does"""
+    zone, pattern, (mode, usec), cap = native.redzone_bytes(), native.poison_pattern(), native.delay_mode(), native.grid_cap_workgroups()
+    native.redzone(0), native.poison(0), native.delay(0), native.grid_cap(0)
     try:
         yield
     finally:
-        native.redzone(zone), native.poison(pattern), native.delay(mode, usec)
+        native.redzone(zone), native.poison(pattern), native.delay(mode, usec), native.grid_cap(cap)
 
 
 def keep(r):

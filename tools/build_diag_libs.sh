@@ -2,7 +2,8 @@
 # Diagnostic builds of libs2sr.so for the split-operand tail convs (conv3x3.hip), made next to the shipped library
 # (csrc/diag/*.so, git-ignored):
 #   libs2sr_f8diag{1,2,4,8}.so  -DS2SR_DIAG_F8=n   1 no LDS-DMA, 2 no MFMA, 4 no epilogue, 8 epilogue without stores (tools/tail_anatomy.sh)
-#   libs2sr_f8diag16.so         diagnostics hooks only (S2SR_DIAG_GRID=<workgroups>)
+#   libs2sr_f8diag16.so         no diagnostic bit that changes a kernel: the shipped conv3x3 under another name (fewer workgroups: the
+#                               shipped library's S2SR_GRID_CAP=<workgroups>, which took over from this build's S2SR_DIAG_GRID)
 # Each links every object of the shipped build (csrc/Makefile's OBJS) except conv3x3.o, which it recompiles.
 # Usage: tools/build_diag_libs.sh [names...]   (default: all);  rm -rf csrc/diag afterwards.
 set -e
