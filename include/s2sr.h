@@ -187,27 +187,8 @@ int  s2sr_forward_batch_u8_dev(s2sr_handle* h, const void* d_tiles, int32_t B, i
  * 1.3e-4); tests/test_gpu_compact_insitu.py holds both to 1e-3. */
 int  s2sr_forward_f32(s2sr_handle* h, const float* x, int32_t N, int32_t H, int32_t W, float* y);
 
-/* replaces RealESRGAN.enhance incl. the whole/tiled switch and _tile_process
- * (cnn_super_resolution.py:217-280): HxWx3 u8 -> 4Hx4Wx3 u8, channel order as given.  Scale 2: -> 2Hx2Wx3, H, W >= 2, even
- * tile; the whole / tiled switch compares the padded size (s2sr_config.scale). */
-int  s2sr_enhance_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W,
-                     int32_t tile, int32_t pad, uint8_t* out);
-/* The device work of one /api/wow or /api/sr job in ONE call (apply_wow_sr, wow_sr.py:85-110; apply_farm_sr, farm_sr.py:156-178):
- * RGB image in -> cvtColor RGB2BGR -> RealESRGAN.enhance -> BGR2RGB -> the crop-visibility post-process (prm; NULL: none) ->
- * RGB image out.  Same bytes as s2sr_enhance_u8 on the swapped image followed by s2sr_postprocess_u8; one upload and one
- * download instead of three round trips and two host-side channel flips of the 16x image. */
-int  s2sr_enhance_job_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, int32_t tile, int32_t pad,
-                         const s2sr_pp_params* prm, uint8_t* out_rgb);
-/* float image before quantisation (HWC fp32), for parity tests of the tiled path */
-int  s2sr_enhance_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W,
-                      int32_t tile, int32_t pad, float* out);
-
-/* RealESRGAN._tile_process alone (cnn_super_resolution.py:236-280): always the window plan,
- * whatever the image size; HWC fp32 out (unquantised). */
-int  s2sr_tile_process_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W,
-                           int32_t tile, int32_t pad, float* out);
-
-/* The 16-bit door: uint16 samples in, uint16 x4 out, no 8-bit squeeze (upstream RealESRGANer's max_range = 65535 branch; the
+/* s2sr_enhance_args.bits == 16, and the 16-bit tile entries.
+ * The 16-bit door: uint16 samples in, uint16 x4 out, no 8-bit squeeze (upstream RealESRGANer's max_range = 65535 branch; the
  * reference quantises its rasters to 8 bits first, so there is no reference to be byte-equal to here).  A call carries a value
  * range lo, hi (0 <= lo < hi <= 65535; 0, 65535 is upstream's rule):
  *   in :  d = clamp(v, lo, hi) - lo, the net sees x = d / (hi - lo) -- exactly: d reaches conv_first as two exact fp16 integers
@@ -228,14 +209,9 @@ int  s2sr_forward_batch_u16(s2sr_handle* h, const uint16_t* tiles, int32_t B, in
  * d_out_u16 must be 8-byte aligned (the quantiser stores four samples at a time; S2SR_E_HIP before anything is written to it). */
 int  s2sr_forward_batch_u16_dev(s2sr_handle* h, const void* d_tiles, int32_t B, int32_t th, int32_t tw, int32_t lo, int32_t hi,
                                 void* d_out_u16, void* stream);
-/* RealESRGAN.enhance for a 16-bit raster: HxWx3 u16 -> out_u16 [4H,4W,3] u16 and / or out_f32 [4H,4W,3] fp32 (the unquantised
- * image, HWC), channel order as given; the whole / tiled switch, the window plan and the paste order of s2sr_enhance_u8.  The
- * windows leave the net as fp32 tiles (12 B per output pixel written and read again, against the u8 door's 3), one chunk of
- * window rows at a time; a fused crop + paste + quantise kernel writes each chunk's band of final rows. */
-int  s2sr_enhance_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
-                      uint16_t* out_u16 /* [4H,4W,3] or NULL */, float* out_f32 /* [4H,4W,3] or NULL */);
 
-/* The seam-blended stitch, opt-in: the windows, forwards and whole / tiled switch of s2sr_enhance_u8 / s2sr_enhance_u16 with
+/* s2sr_enhance_args.blend.
+ * The seam-blended stitch, opt-in: the windows, forwards and whole / tiled switch of s2sr_enhance_u8 / s2sr_enhance_u16 with
  * another paste.  The overwrite paste crops every window hard, so where two windows disagree in their overlap (the net sees far
  * beyond the pad) the output steps along every tile line.  Here, per axis: owner(o) is the window the overwrite paste takes output
  * coordinate o from; a seam S is a coordinate whose owner is another rectangle than owner(S - 1); around it lies a ramp of
@@ -249,19 +225,11 @@ int  s2sr_enhance_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W,
  * An image the switch leaves whole, or a plan without ramps (pad 0), runs through the default doors as it is.  A plan whose ramps
  * would leave their windows, or that leaves output pixels uncovered (pad > tile / 2 on an image shorter than two pads), is refused
  * with S2SR_E_INVALID and a text before the device is touched.
- *
- * s2sr_enhance_blend_u8: out_u8 [S H, S W, 3] = trunc(clip(v * 255, 0, 255)) and / or out_f32 [S H, S W, 3] = v; at least one.
- *   prm == NULL, swap_rb == 0: s2sr_enhance_u8's contract.  swap_rb != 0: s2sr_enhance_job_u8's (RGB in, RGB out, the
- *   post-process prm behind the stitch when not NULL); prm without swap_rb: the post-process on the image in the order given.
- *   out_f32 only with prm == NULL and swap_rb == 0; a job needs out_u8.
- * s2sr_enhance_blend_u16: s2sr_enhance_u16's contract and refusals (x4 RRDB nets only), out_u16 = lo + rint(clip(v, 0, 1) * (hi - lo)). */
-int  s2sr_enhance_blend_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad,
-                           const s2sr_pp_params* prm /* or NULL */, int32_t swap_rb, uint8_t* out_u8 /* or NULL */,
-                           float* out_f32 /* or NULL */);
-int  s2sr_enhance_blend_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo,
-                            int32_t hi, uint16_t* out_u16 /* [4H,4W,3] or NULL */, float* out_f32 /* [4H,4W,3] or NULL */);
+ * 8 bits: out [S H, S W, 3] = trunc(clip(v * 255, 0, 255)) and / or out_f32 [S H, S W, 3] = v; at least one.
+ * 16 bits: the 16-bit door's contract and refusals (x4 RRDB nets only), out = lo + rint(clip(v, 0, 1) * (hi - lo)). */
 
-/* Nodata-aware enhance, opt-in: pixels that were never measured (a clipped AOI, a swath edge, a cloud mask) are
+/* s2sr_enhance_args.mask.
+ * Nodata-aware enhance, opt-in: pixels that were never measured (a clipped AOI, a swath edge, a cloud mask) are
  * kept out of the net's way and come out as nodata again.  valid is uint8 [H, W], nonzero = valid.  Integers throughout:
  *   fill (in front of the net, of the R / B exchange and of the window gather): a valid pixel is unchanged; an invalid pixel
  *     (y, x) takes all three samples of the valid pixel (qy, qx) that minimises (d2, qy, qx) lexicographically,
@@ -272,10 +240,8 @@ int  s2sr_enhance_blend_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int3
  *     unmasked call's byte (also where it happens to equal out_nodata: the mask is the truth, the value only the file convention).
  *   The post-process runs on the filled image: its CLAHE sees extrapolated ground, not a black plane.
  * So a masked call's bytes are mask(unmasked door(fill(img))), and a mask that is valid everywhere gives the unmasked door's bytes.
- * s2sr_enhance_masked_u8: the doors s2sr_enhance_u8 (prm NULL, swap_rb 0), s2sr_enhance_job_u8 (swap_rb 1) and, with blend != 0,
- *   s2sr_enhance_blend_u8, with their sizes, scales and refusals.  s2sr_enhance_masked_u16: s2sr_enhance_u16 / _blend_u16; the
- *   uint16 image it leaves on the device for s2sr_display_*_u16 is the masked one.  The fp32 images are the net's own output and
- *   are not offered here.
+ * The uint16 image a masked call leaves on the device for s2sr_display_*_u16 is the masked one.  The fp32 images are the net's own
+ * output and are not offered with a mask.
  * s2sr_fill_nodata_u8 / _u16: the fill alone, host image in, filled host image out (out may be img); no weights needed.
  * S2SR_E_INVALID with a text, before the device is touched: m or m->valid NULL, radius outside 1..64, out_nodata outside 0..255
  * (0..65535 for uint16).  The handle keeps working afterwards. */
@@ -286,12 +252,9 @@ typedef struct s2sr_mask {
 } s2sr_mask;
 int  s2sr_fill_nodata_u8(s2sr_handle* h, const uint8_t* img, const uint8_t* valid, int32_t H, int32_t W, int32_t radius, uint8_t* out);
 int  s2sr_fill_nodata_u16(s2sr_handle* h, const uint16_t* img, const uint8_t* valid, int32_t H, int32_t W, int32_t radius, uint16_t* out);
-int  s2sr_enhance_masked_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad,
-                            const s2sr_pp_params* prm /* or NULL */, int32_t swap_rb, int32_t blend, const s2sr_mask* m, uint8_t* out_u8);
-int  s2sr_enhance_masked_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo,
-                             int32_t hi, int32_t blend, const s2sr_mask* m, uint16_t* out_u16);
 
-/* Radiometric consistency, opt-in: one back-projection step against the box-average sensor model, so that the mean
+/* s2sr_enhance_args.consistency.
+ * Radiometric consistency, opt-in: one back-projection step against the box-average sensor model, so that the mean
  * of the S x S output samples over an input pixel is that input pixel again.  Integers throughout, per channel: S = 2 or 4,
  * n = S S; q the door's quantised image [S H, S W, 3]; v = clamp(img, lo, hi) the input the net saw (8 bits: 0, 255; 16 bits: the
  * call's range); sum[y, x] the sum of q over block [S y, S y + S) x [S x, S x + S); e = n v - sum.
@@ -313,9 +276,7 @@ int  s2sr_enhance_masked_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int
  * stitch entries do not run the pass; a saturated block stays inexact (no redistribution among its unclipped samples).
  * s2sr_consistency_u8 / _u16: the pass alone, host images in and out (out may be sr), no weights needed; band_rows (0: the library's
  *   choice, ~32 MB) sets the bands of output rows it works in, and the result does not depend on it.
- * s2sr_enhance_consistent_u8: the doors s2sr_enhance_u8 (prm NULL, swap_rb 0), s2sr_enhance_job_u8 (swap_rb 1), s2sr_enhance_blend_u8
- *   (blend != 0) and, with m != NULL, s2sr_enhance_masked_u8, with their sizes, scales and refusals: every handle, x4, x2plus (odd
- *   H or W too) and compact.  s2sr_enhance_consistent_u16: s2sr_enhance_u16 / _blend_u16 / _masked_u16 and their refusals.
+ * Every handle takes the pass: x4, x2plus (odd H or W too) and compact.
  * S2SR_E_INVALID with a text, before the device is touched: a mode outside 1..2, S outside {2, 4}, band_rows < 0, a NULL image or
  * output, a bad range.  The handle keeps working afterwards. */
 #define S2SR_CONSISTENCY_EXACT  1
@@ -324,6 +285,79 @@ int  s2sr_consistency_u8(s2sr_handle* h, const uint8_t* sr /* [S H, S W, 3] */, 
                          int32_t S, int32_t mode, int32_t band_rows, uint8_t* out, uint64_t* inexact /* [3] or NULL */);
 int  s2sr_consistency_u16(s2sr_handle* h, const uint16_t* sr, const uint16_t* img, int32_t H, int32_t W, int32_t S, int32_t lo, int32_t hi,
                           int32_t mode, int32_t band_rows, uint16_t* out, uint64_t* inexact /* [3] or NULL */);
+
+/* ---- The whole-image door.  ONE record describes a call and s2sr_enhance runs it: RealESRGAN.enhance incl. the whole / tiled
+ * switch and _tile_process (cnn_super_resolution.py:217-280) with the options that are on.  Every option is a field; its contract
+ * stands once, at the field or in the block above that the field names.  With every option on a call's bytes are
+ * mask(pp(consistency(door(fill(img))))): fill, R / B exchange, the net and the paste, the consistency pass, the exchange back, the
+ * post-process, the mask.  Which records exist is stated in one place (engine_aoi.hip check_call), each refusal S2SR_E_INVALID with a
+ * text in s2sr_last_error before the device is touched, and the handle keeps working afterwards:
+ *   size != sizeof(s2sr_enhance_args); bits not 8 or 16; no image, no output at all, H, W, tile <= 0 or pad < 0;
+ *   bits 16 with prm or swap_rb; bits 16 on a scale-2 or S2SR_ARCH_COMPACT handle, or with a bad range;
+ *   force_tiled with anything but an 8-bit image, out_f32 alone and every option off;
+ *   bits 8 with out and out_f32 both and blend == 0;
+ *   out_f32 with prm, swap_rb, mask or consistency (the float image is the net's own output);
+ *   a mask with valid NULL, radius outside 1..64 or out_nodata outside the sample range; a consistency outside 0..2; bad prm.
+ * Everything else is a union of independent options and runs, also where no form below spells it (prm without swap_rb, blend, mask
+ * or consistency: the post-process on the plain door's image in the order given). */
+typedef struct s2sr_enhance_args {
+    uint32_t size;              /* sizeof(s2sr_enhance_args); anything else is refused */
+    int32_t  bits;              /* 8: img is uint8 [H,W,3] -> out uint8 [S H, S W, 3], S = s2sr_config.scale, channel order as given,
+                                 * quantised by the reference's truncation.  Scale 2: H, W >= 2, even tile; the whole / tiled
+                                 * switch compares the padded size.
+                                 * 16: img is uint16 [H,W,3] -> out uint16 [4H,4W,3] and / or out_f32 (the 16-bit rule above): the
+                                 * whole / tiled switch, the window plan and the paste order of 8 bits.  The windows leave the net as
+                                 * fp32 tiles (12 B per output pixel written and read again, against 3), one chunk of window rows
+                                 * at a time; a fused crop + paste + quantise kernel writes each chunk's band of final rows. */
+    const void* img;
+    int32_t  H, W, tile, pad;
+    int32_t  lo, hi;            /* bits 16: the value range; bits 8: ignored */
+    const s2sr_pp_params* prm;  /* or NULL.  bits 8: the crop-visibility post-process on the stitched image, in the order given */
+    int32_t  swap_rb;           /* != 0, bits 8: the device work of one /api/wow or /api/sr job (apply_wow_sr, wow_sr.py:85-110;
+                                 * apply_farm_sr, farm_sr.py:156-178): RGB image in -> cvtColor RGB2BGR -> RealESRGAN.enhance ->
+                                 * BGR2RGB -> the crop-visibility post-process (prm; NULL: none) -> RGB image out.  Same bytes as the
+                                 * plain call on the swapped image followed by s2sr_postprocess_u8; one upload and one download
+                                 * instead of three round trips and two host-side channel flips of the 16x image. */
+    int32_t  blend;             /* != 0: the seam-blended paste (above) */
+    int32_t  force_tiled;       /* != 0: RealESRGAN._tile_process alone (cnn_super_resolution.py:236-280): always the window plan,
+                                 * whatever the image size; HWC fp32 out (unquantised) */
+    const s2sr_mask* mask;      /* or NULL: not masked.  Fill before the net, out_nodata behind everything (above) */
+    int32_t  consistency;       /* 0: off, S2SR_CONSISTENCY_* (above) */
+    void*    out;               /* the quantised image (uint8 / uint16 [S H, S W, 3]) or NULL */
+    float*   out_f32;           /* the float image before quantisation (HWC fp32 [S H, S W, 3]) or NULL */
+    uint64_t* inexact;          /* [3] or NULL; read only when consistency != 0 */
+} s2sr_enhance_args;
+int  s2sr_enhance(s2sr_handle* h, const s2sr_enhance_args* a);
+
+/* The forms: the signatures from before the record, kept for callers that bind them.  Each builds the record below (what it does not
+ * name is 0 / NULL) and runs s2sr_enhance's code, with its own words for a missing image, size or output.
+ *   s2sr_enhance_u8             bits 8, out
+ *   s2sr_enhance_job_u8         bits 8, out, swap_rb 1, prm
+ *   s2sr_enhance_f32            bits 8, out_f32
+ *   s2sr_tile_process_f32       bits 8, out_f32, force_tiled 1
+ *   s2sr_enhance_u16            bits 16, lo, hi, out and / or out_f32
+ *   s2sr_enhance_blend_u8       bits 8, blend 1, prm, swap_rb, out and / or out_f32; img NULL is refused by name
+ *   s2sr_enhance_blend_u16      bits 16, lo, hi, blend 1, out and / or out_f32; img NULL is refused by name
+ *   s2sr_enhance_masked_u8      bits 8, prm, swap_rb, blend, mask m, out; m NULL is refused
+ *   s2sr_enhance_masked_u16     bits 16, lo, hi, blend, mask m, out; m NULL is refused
+ *   s2sr_enhance_consistent_u8  bits 8, prm, swap_rb, blend, mask m (or NULL), consistency mode, out, inexact; a mode outside 1..2 is refused
+ *   s2sr_enhance_consistent_u16 bits 16, lo, hi, blend, mask m (or NULL), consistency mode, out, inexact; a mode outside 1..2 is refused */
+int  s2sr_enhance_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, uint8_t* out);
+int  s2sr_enhance_job_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, int32_t tile, int32_t pad,
+                         const s2sr_pp_params* prm, uint8_t* out_rgb);
+int  s2sr_enhance_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out);
+int  s2sr_tile_process_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out);
+int  s2sr_enhance_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
+                      uint16_t* out_u16 /* or NULL */, float* out_f32 /* or NULL */);
+int  s2sr_enhance_blend_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad,
+                           const s2sr_pp_params* prm /* or NULL */, int32_t swap_rb, uint8_t* out_u8 /* or NULL */,
+                           float* out_f32 /* or NULL */);
+int  s2sr_enhance_blend_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo,
+                            int32_t hi, uint16_t* out_u16 /* or NULL */, float* out_f32 /* or NULL */);
+int  s2sr_enhance_masked_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad,
+                            const s2sr_pp_params* prm /* or NULL */, int32_t swap_rb, int32_t blend, const s2sr_mask* m, uint8_t* out_u8);
+int  s2sr_enhance_masked_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo,
+                             int32_t hi, int32_t blend, const s2sr_mask* m, uint16_t* out_u16);
 int  s2sr_enhance_consistent_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad,
                                 const s2sr_pp_params* prm /* or NULL */, int32_t swap_rb, int32_t blend, const s2sr_mask* m /* or NULL */,
                                 int32_t mode, uint8_t* out_u8, uint64_t* inexact /* [3] or NULL */);

@@ -399,17 +399,16 @@ class RealESRGAN:
             raise TypeError(f"expected uint8 image, got {img.dtype}")
         valid, out_nodata = self._mask_of(img, valid, nodata, fill_radius)
         with self._engine.chain_lock:        # (not between another job's enhance16 and its display rendering)
-            if self._cmode:
-                out, bad = self._engine.enhance_consistent_u8(img, self._cmode, blend=self.seam_blend, valid=valid, radius=fill_radius,
-                                                              out_nodata=out_nodata, tile=self.tile_size, pad=self.tile_pad)
-                self.last_inexact_blocks = [int(v) for v in bad]
-                return out
-            if valid is not None:
-                return self._engine.enhance_masked_u8(img, valid, radius=fill_radius, out_nodata=out_nodata, blend=self.seam_blend,
-                                                      tile=self.tile_size, pad=self.tile_pad)
-            if self.seam_blend:
-                return self._engine.enhance_blend_u8(img, tile=self.tile_size, pad=self.tile_pad)
-            return self._engine.enhance_u8(img, tile=self.tile_size, pad=self.tile_pad)
+            return self._door(img, valid, fill_radius, out_nodata)
+
+    def _door(self, img: np.ndarray, valid, fill_radius, out_nodata, **fields) -> np.ndarray:
+        """One whole-image call with this object's options (seam blend, consistency mode) and the call's (its mask; fields: what
+        else the record takes) -> the quantised image.  The caller holds the chain lock."""
+        r = self._engine.enhance(img, tile=self.tile_size, pad=self.tile_pad, blend=self.seam_blend, consistency=self._cmode or 0,
+                                 valid=valid, radius=fill_radius, out_nodata=out_nodata, **fields)
+        if self._cmode:
+            self.last_inexact_blocks = [int(v) for v in r.inexact]
+        return r.q
 
     def enhance16(self, img: np.ndarray, value_range=None, display=None, valid=None, nodata=None, fill_radius: int = 32, extra=None,
                   extra_range=None, extra_weights=None):
@@ -437,22 +436,10 @@ class RealESRGAN:
         if not (0 <= lo < hi <= 65535):
             raise ValueError(f"value_range {value_range}: need 0 <= lo < hi <= 65535")
         valid, out_nodata = self._mask_of(img, valid, nodata, fill_radius)
-        if self._cmode:
-            def door(img, lo, hi, tile, pad):
-                out, bad = self._engine.enhance_consistent_u16(img, lo, hi, self._cmode, blend=self.seam_blend, valid=valid, radius=fill_radius,
-                                                               out_nodata=out_nodata, tile=tile, pad=pad)
-                self.last_inexact_blocks = [int(v) for v in bad]
-                return out
-        elif valid is None:
-            door = self._engine.enhance_blend_u16 if self.seam_blend else self._engine.enhance_u16
-        else:
-            def door(img, lo, hi, tile, pad):
-                return self._engine.enhance_masked_u16(img, valid, lo, hi, radius=fill_radius, out_nodata=out_nodata, blend=self.seam_blend,
-                                                       tile=tile, pad=pad)
         plan = None if extra is None else self._extra_plan(img, extra, extra_range, extra_weights, valid, out_nodata)
         if display is None:
             with self._engine.chain_lock:
-                out16 = door(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
+                out16 = self._door(img, valid, fill_radius, out_nodata, lo=lo, hi=hi)
                 return out16 if plan is None else (out16, self._carry_extra(plan))
         from s2sr.display import Stretch, render_u16
         stretch = Stretch.of(display)
@@ -460,7 +447,7 @@ class RealESRGAN:
             import dataclasses
             stretch = dataclasses.replace(stretch, nodata=out_nodata)
         with self._engine.chain_lock:        # the engine is shared by every job of the process: nothing between the door and the rendering
-            out16 = door(img, lo, hi, tile=self.tile_size, pad=self.tile_pad)
+            out16 = self._door(img, valid, fill_radius, out_nodata, lo=lo, hi=hi)
             carried = None if plan is None else self._carry_extra(plan)      # (it leaves the device copy as the door left it)
             disp, info = render_u16(None, stretch, self._engine, shape=out16.shape[:2])
         return (out16, disp, info) if plan is None else (out16, disp, info, carried)
@@ -509,18 +496,8 @@ class RealESRGAN:
         if rgb.dtype != np.uint8:
             raise TypeError(f"expected uint8 image, got {rgb.dtype}")
         valid, out_nodata = self._mask_of(rgb, valid, nodata, fill_radius)
-        with self._engine.chain_lock:
-            if self._cmode:       # the pass sits in front of the post-process: the product is consistent before it
-                out, bad = self._engine.enhance_consistent_u8(rgb, self._cmode, prm=post, swap_rb=True, blend=self.seam_blend, valid=valid,
-                                                              radius=fill_radius, out_nodata=out_nodata, tile=self.tile_size, pad=self.tile_pad)
-                self.last_inexact_blocks = [int(v) for v in bad]
-                return out
-            if valid is not None:
-                return self._engine.enhance_masked_u8(rgb, valid, radius=fill_radius, out_nodata=out_nodata, prm=post, swap_rb=True,
-                                                      blend=self.seam_blend, tile=self.tile_size, pad=self.tile_pad)
-            if self.seam_blend:
-                return self._engine.enhance_blend_u8(rgb, post, swap_rb=True, tile=self.tile_size, pad=self.tile_pad)
-            return self._engine.enhance_job_u8(rgb, post, tile=self.tile_size, pad=self.tile_pad)
+        with self._engine.chain_lock:            # (a consistency pass sits in front of the post-process: the product is consistent before it)
+            return self._door(rgb, valid, fill_radius, out_nodata, prm=post, swap_rb=True)
 
     def _tile_process(self, img: torch.Tensor) -> torch.Tensor:
         """[1,3,H,W] float in [0,1] -> [1,3,sH,sW] float32 (s = self.scale) through the tiled path (:236-280)."""

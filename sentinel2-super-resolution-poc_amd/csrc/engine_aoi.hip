@@ -512,6 +512,7 @@ static int cons_counts(s2sr_handle* h, hipStream_t st, uint64_t* inexact) {
     return S2SR_OK;
 }
 
+static const char* kConsMode = "consistency: mode must be 1 (S2SR_CONSISTENCY_EXACT) or 2 (S2SR_CONSISTENCY_SMOOTH)";
 static const char* mask_error(const uint8_t* valid, int radius, int out_nodata, bool u16) {
     if (!valid) return "nodata: a mask (valid, uint8 [H, W]) is required";
     if (radius < 1 || radius > 64) return "nodata: the fill radius must be 1..64";
@@ -555,44 +556,27 @@ static int pp_finish_bands(s2sr_handle* h, hipStream_t st, uint8_t* d_img_out, u
     return S2SR_OK;
 }
 
-// What a whole-image call asks for.  Every door (s2sr_enhance_u8 / _f32 / _job_u8 / _u16 / _blend_u8 / _blend_u16 and
-// s2sr_tile_process_f32) fills one and enters enhance_call.
-struct EnhanceCall {
-    const uint8_t* img8 = nullptr;
-    const uint16_t* img16 = nullptr;
-    int H = 0, W = 0, tile = 0, pad = 0;
-    int lo = 0, hi = 0;                       // 16-bit: the value range
-    const s2sr_pp_params* prm = nullptr;      // 8-bit: the job's crop-visibility post-process (wow_sr.py:187-209) on the stitched image ...
-    bool swap_rb = false;                     // ... and its R / B exchange in front of and behind the net (the cvtColor pair, wow_sr.py:85,103)
-    bool force_tiled = false;                 // _tile_process whatever the size
-    bool blend = false;                       // cross-fade the window overlaps (blend_plan.h) where the plan has a ramp
-    uint8_t* out_u8 = nullptr;
-    uint16_t* out_u16 = nullptr;
-    float* out_f32 = nullptr;
-    const char* required = nullptr;           // the door's words for a call without image, sizes or output (none: the bare code)
-    // the masked doors: fill the invalid pixels in front of the net, out_nodata over their output pixels behind everything
-    bool masked = false;
-    const uint8_t* valid = nullptr;           // uint8 [H, W], nonzero = valid
-    int radius = 0, out_nodata = 0;
-    // the consistent doors: the back-projection pass on the quantised image, behind the paste and in front of all else
-    int consistency = 0;                      // 0: off, S2SR_CONSISTENCY_*
-    uint64_t* inexact = nullptr;              // [3] or null: the blocks per channel whose sum a clip kept off n v
-};
-
-static int check_call(s2sr_handle* h, const EnhanceCall& c) {
-    const bool in16 = c.img16 != nullptr;
-    if ((!c.img8 && !c.img16) || (!c.out_u8 && !c.out_u16 && !c.out_f32) || c.H <= 0 || c.W <= 0 || c.tile <= 0 || c.pad < 0)
-        return c.required ? fail(h, S2SR_E_INVALID, c.required) : S2SR_E_INVALID;
-    if (!in16 && c.out_f32 && (c.prm || c.swap_rb))          // (only the blend door can ask for it)
+// What a whole-image call asks for is one s2sr_enhance_args (include/s2sr.h: the fields and what each means), read by everything from
+// here to enhance_door.  check_call is the single statement of which records exist: every refusal before the device is touched.
+// required: the door's words for a call without image, sizes or output (none: the bare code).
+static int check_call(s2sr_handle* h, const s2sr_enhance_args& c, const char* required) {
+    if (c.size != sizeof(s2sr_enhance_args)) return fail(h, S2SR_E_INVALID, "s2sr_enhance_args: size must be sizeof(s2sr_enhance_args)");
+    if (c.bits != 8 && c.bits != 16) return fail(h, S2SR_E_INVALID, "s2sr_enhance_args: bits must be 8 or 16");
+    const bool in16 = c.bits == 16;
+    if (!c.img || (!c.out && !c.out_f32) || c.H <= 0 || c.W <= 0 || c.tile <= 0 || c.pad < 0)
+        return required ? fail(h, S2SR_E_INVALID, required) : S2SR_E_INVALID;
+    if (in16 && (c.prm || c.swap_rb)) return fail(h, S2SR_E_INVALID, "s2sr_enhance_args: prm and swap_rb belong to 8-bit images (bits 16 has no post-process)");
+    if (c.force_tiled && (in16 || c.out || c.prm || c.swap_rb || c.blend || c.mask || c.consistency))
+        return fail(h, S2SR_E_INVALID, "s2sr_enhance_args: force_tiled is s2sr_tile_process_f32: an 8-bit image, out_f32 alone, every option off");
+    if (!in16 && c.out && c.out_f32 && !c.blend) return fail(h, S2SR_E_INVALID, "s2sr_enhance_args: an 8-bit call for out and out_f32 together needs blend");
+    if (!in16 && c.out_f32 && (c.prm || c.swap_rb))
         return fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: the float image is the net's own output: not with a post-process or swap_rb");
-    if (!in16 && (c.prm || c.swap_rb) && !c.out_u8) return c.blend ? fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: a job needs out_u8") : S2SR_E_INVALID;
-    if (c.masked) {
-        if (const char* why = mask_error(c.valid, c.radius, c.out_nodata, in16)) return fail(h, S2SR_E_INVALID, why);
+    if (c.mask) {
+        if (const char* why = mask_error(c.mask->valid, c.mask->radius, c.mask->out_nodata, in16)) return fail(h, S2SR_E_INVALID, why);
         if (c.out_f32) return fail(h, S2SR_E_INVALID, "nodata: the float image is the net's own output and is never masked");
     }
     if (c.consistency) {
-        if (c.consistency != S2SR_CONSISTENCY_EXACT && c.consistency != S2SR_CONSISTENCY_SMOOTH)
-            return fail(h, S2SR_E_INVALID, "consistency: mode must be 1 (S2SR_CONSISTENCY_EXACT) or 2 (S2SR_CONSISTENCY_SMOOTH)");
+        if (c.consistency != S2SR_CONSISTENCY_EXACT && c.consistency != S2SR_CONSISTENCY_SMOOTH) return fail(h, S2SR_E_INVALID, kConsMode);
         if (c.out_f32) return fail(h, S2SR_E_INVALID, "consistency: the float image is the net's own output and is never corrected");
     }
     if (in16)
@@ -615,7 +599,7 @@ struct EnhancePlan {
     int max_rows = 0;                         // window rows of the largest chunk
 };
 
-static int plan_enhance(s2sr_handle* h, const EnhanceCall& c, EnhancePlan& p) {
+static int plan_enhance(s2sr_handle* h, const s2sr_enhance_args& c, EnhancePlan& p) {
     int rc;
     if ((rc = plan_dims(h, c.H, c.W, c.tile, &p.PH, &p.PW))) return rc;
     const int scale = h->cfg.scale;
@@ -665,14 +649,14 @@ static int plan_enhance(s2sr_handle* h, const EnhanceCall& c, EnhancePlan& p) {
 // The fp32 image (one chunk) is pasted from the chunk's tiles behind the loop, and both images leave behind that.
 // A consistency pass sits between the paste and everything else: it trails the paste by whole block rows, and the
 // exchange back, the histograms, the mask and the copies follow its bands instead of the paste's (ConsRun, cons_out_end).
-static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
+static int enhance_locked(s2sr_handle* h, const s2sr_enhance_args& c) {
     EnhancePlan p;
     int rc = plan_enhance(h, c, p);
     if (rc) return rc;
-    const bool in16 = c.img16 != nullptr, over = !p.blend && !in16;
-    if (over && c.out_u8 && c.out_f32) {   // a blend call left whole or without a ramp: u8 and fp32 tiles are two forwards of the net
-        EnhanceCall f = c, q = c;
-        f.blend = q.blend = false; f.out_u8 = nullptr; q.out_f32 = nullptr;
+    const bool in16 = c.bits == 16, over = !p.blend && !in16;
+    if (over && c.out && c.out_f32) {   // a blend call left whole or without a ramp: u8 and fp32 tiles are two forwards of the net
+        s2sr_enhance_args f = c, q = c;
+        f.blend = q.blend = 0; f.out = nullptr; q.out_f32 = nullptr;
         return (rc = enhance_locked(h, f)) ? rc : enhance_locked(h, q);
     }
     hipStream_t st = h->stream;
@@ -683,7 +667,6 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
     const bool reflect = p.PH != H || p.PW != W;
     const bool direct = over && !p.tiled && !c.out_f32 && !reflect;     // the net writes the image itself: no tiles, no tables, no paste
     const bool banded = c.prm && (p.blend || nchunks > 1);              // the post-process runs in bands (else, if any, on the whole image)
-    void* out_q = in16 ? (void*)c.out_u16 : (void*)c.out_u8;
     const size_t ipx = (size_t)H * W * 3, opx = (size_t)OH * OW * 3;
     const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;      // samples per window, in and out
     const size_t row_b = (size_t)OW * 3 * esz;                                         // bytes of one output row
@@ -692,13 +675,13 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
     const Slot tslot = over && !p.tiled ? SL_MID : SL_CHUNK;
     const size_t tile_b = over ? (size_t)nx * ny * win_out * (c.out_f32 ? 4 : 1) : (size_t)(p.max_rows + carry) * nx * win_out * sizeof(float);
     if ((rc = ensure_scratch(h, {{SL_SRC, ipx * esz}, {SL_DST, c.out_f32 ? f_off + opx * 4 : over ? opx : f_off},
-                                 {SL_MID, (size_t)nx * ny * win_in * esz, p.tiled}, {tslot, tile_b, !direct}, {SL_VALID, (size_t)H * W, c.masked},
+                                 {SL_MID, (size_t)nx * ny * win_in * esz, p.tiled}, {tslot, tile_b, !direct}, {SL_VALID, (size_t)H * W, c.mask != nullptr},
                                  {SL_CONS, cons_scratch_bytes(c.consistency, H, W), c.consistency != 0}}))) return rc;
-    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), in16 ? (const void*)c.img16 : (const void*)c.img8, ipx * esz, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), c.img, ipx * esz, hipMemcpyHostToDevice, st));
     MaskDev mk;                                        // masked: the fill in front of everything that reads the image, the mask at each exit of a quantised band
-    if (c.masked) {
-        if ((rc = fill_locked(h, st, c.valid, H, W, c.radius, in16, scratch(h, SL_SRC)))) return rc;
-        mk.d_valid = scratch<const uint8_t>(h, SL_VALID); mk.H = H; mk.W = W; mk.scale = scale; mk.out_nodata = c.out_nodata; mk.u16 = in16;
+    if (c.mask) {
+        if ((rc = fill_locked(h, st, c.mask->valid, H, W, c.mask->radius, in16, scratch(h, SL_SRC)))) return rc;
+        mk.d_valid = scratch<const uint8_t>(h, SL_VALID); mk.H = H; mk.W = W; mk.scale = scale; mk.out_nodata = c.mask->out_nodata; mk.u16 = in16;
     }
     if (c.swap_rb) HIPCHK(h, launch_swap_rb_u8(scratch<const uint8_t>(h, SL_SRC), (size_t)H * W, scratch<uint8_t>(h, SL_SRC), st));
     int32_t* d_tab[3] = {nullptr, nullptr, nullptr};   // rectangles, row table, column table
@@ -754,7 +737,7 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
     // rows [pyb, pye) into the quantised image, and what follows the paste on rows [yb, ye) (the same rows, unless a consistency pass
     // trails); t0: the chunk's first window (the one-chunk buffers start at window t0 - carry * nx)
     auto finish = [&](int t0, int pyb, int pye, int yb, int ye) -> int {
-        if (!out_q) return S2SR_OK;
+        if (!c.out) return S2SR_OK;
         uint8_t* dst = d_q + (size_t)pyb * row_b;
         if (pye <= pyb) {                                        // (nothing new is final: only the trailing pass moves)
         } else if (over) {
@@ -776,10 +759,10 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
         return c.prm ? S2SR_OK : mask_rows(h, st, mk, d_q, yb, ye);       // (a post-process reads the filled image: its exits mask)
     };
     // with a post-process or the fp32 image no band is copied here: they leave through the tail below
-    if ((rc = run_chunks(h, st, nx, p.chunk_r0, p.band_end, out_end, forward, finish, (uint8_t*)out_q, d_q, row_b, out_q && !c.prm && !c.out_f32))) return rc;
+    if ((rc = run_chunks(h, st, nx, p.chunk_r0, p.band_end, out_end, forward, finish, (uint8_t*)c.out, d_q, row_b, c.out && !c.prm && !c.out_f32))) return rc;
     // ---- the tail
     hipEvent_t tail_done = h->group_done[nchunks + nfin];
-    if (banded && (rc = pp_finish_bands(h, st, d_q, c.out_u8, OH, row_b, fin_rows, nfin, nchunks, mk))) return rc;
+    if (banded && (rc = pp_finish_bands(h, st, d_q, (uint8_t*)c.out, OH, row_b, fin_rows, nfin, nchunks, mk))) return rc;
     if (c.prm && !banded) {
         // the windows' output buffer is free again once the stitch has read it; the untiled image gets a buffer of its own
         if ((rc = ensure_scratch(h, SL_CHUNK, opx))) return rc;
@@ -787,15 +770,15 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
         if ((rc = mask_rows(h, st, mk, scratch(h, SL_CHUNK), 0, OH))) return rc;
         HIPCHK(h, ev_record(h, tail_done, st, SITE_TAIL_D2H));
         HIPCHK(h, ev_stream_wait(h, h->copy_stream, tail_done, SITE_TAIL_D2H));
-        if ((rc = d2h_staged(h, c.out_u8, scratch<const uint8_t>(h, SL_CHUNK), opx, true))) return rc;
+        if ((rc = d2h_staged(h, (uint8_t*)c.out, scratch<const uint8_t>(h, SL_CHUNK), opx, true))) return rc;
     }
     if (c.out_f32) {
         if (p.blend) HIPCHK(h, launch_stitch_blend((const float*)d_buf, nx, 0, oth, otw, d_tab[1], d_tab[2], OH, OW, d_f, st));
         else HIPCHK(h, launch_stitch((const float*)d_buf, nx, oth, otw, d_tab[1], d_tab[2], OH, OW, d_f, st));
         HIPCHK(h, ev_record(h, tail_done, st, SITE_TAIL_D2H));
-        if (out_q) {
+        if (c.out) {
             HIPCHK(h, ev_stream_wait(h, h->copy_stream, h->group_done[nchunks - 1], SITE_CHUNK_BAND_D2H));
-            if ((rc = d2h_staged(h, (uint8_t*)out_q, d_q, OH * row_b, true))) return rc;
+            if ((rc = d2h_staged(h, (uint8_t*)c.out, d_q, OH * row_b, true))) return rc;
         }
         HIPCHK(h, ev_stream_wait(h, h->copy_stream, tail_done, SITE_TAIL_D2H));
         if ((rc = d2h_staged(h, (uint8_t*)c.out_f32, (const uint8_t*)d_f, opx * 4, true))) return rc;
@@ -807,129 +790,114 @@ static int enhance_locked(s2sr_handle* h, const EnhanceCall& c) {
         const uint64_t b = c.inexact[0];
         c.inexact[0] = c.inexact[2]; c.inexact[2] = b;
     }
-    if (c.out_u16) h->scratch.keep(KEPT_U16, SL_DST, OH, OW);                // the x4 image also stays on the device, for s2sr_display_*_u16
+    if (in16 && c.out) h->scratch.keep(KEPT_U16, SL_DST, OH, OW);                // the x4 image also stays on the device, for s2sr_display_*_u16
     return S2SR_OK;
 }
 
 // ONE lock scope per call, from the checks to the last synchronise (as s2sr_postprocess_u8): the scratch areas belong to the handle
-static int enhance_call(s2sr_handle* h, const EnhanceCall& c) {
-    if (!h) return S2SR_E_INVALID;
+static int enhance_call(s2sr_handle* h, const s2sr_enhance_args* a, const char* required) {
+    if (!h || !a) return S2SR_E_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    if (int rc = check_call(h, c)) return rc;
+    if (int rc = check_call(h, *a, required)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
-    return enhance_locked(h, c);
+    return enhance_locked(h, *a);
 }
 
-static EnhanceCall call_u8(const uint8_t* img, int H, int W, int tile, int pad, uint8_t* out_u8, float* out_f32) {
-    EnhanceCall c;
-    c.img8 = img; c.H = H; c.W = W; c.tile = tile; c.pad = pad; c.out_u8 = out_u8; c.out_f32 = out_f32;
-    return c;
+// The entry behind s2sr_enhance and every form of it: one recovery around the one lock scope.
+static int enhance_door(s2sr_handle* h, const s2sr_enhance_args* a, const char* required) {
+    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, a, required));
 }
-static EnhanceCall call_u16(const uint16_t* img, int H, int W, int tile, int pad, int lo, int hi, uint16_t* out_u16, float* out_f32) {
-    EnhanceCall c;
-    c.img16 = img; c.H = H; c.W = W; c.tile = tile; c.pad = pad; c.lo = lo; c.hi = hi; c.out_u16 = out_u16; c.out_f32 = out_f32;
-    return c;
+
+int s2sr_enhance(s2sr_handle* h, const s2sr_enhance_args* a) {
+    return enhance_door(h, a, "s2sr_enhance: an image, positive sizes and at least one output are required");
 }
+
+// ---- the forms (include/s2sr.h: the table under s2sr_enhance).  Each builds the record its signature spells and enters enhance_door
+// with its own words; what only a signature can get wrong (no image for a blend, no mask, mode 0) it refuses itself.
+static s2sr_enhance_args form(int bits, const void* img, int H, int W, int tile, int pad, void* out, float* out_f32) {
+    s2sr_enhance_args a = {};
+    a.size = sizeof a; a.bits = bits; a.img = img; a.H = H; a.W = W; a.tile = tile; a.pad = pad; a.out = out; a.out_f32 = out_f32;
+    return a;
+}
+static int form_refusal(s2sr_handle* h, const char* why) { return h ? fail(h, S2SR_E_INVALID, why) : S2SR_E_INVALID; }
 
 int s2sr_enhance_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, uint8_t* out) {
-    const EnhanceCall c = call_u8(img, H, W, tile, pad, out, nullptr);
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    const s2sr_enhance_args a = form(8, img, H, W, tile, pad, out, nullptr);
+    return enhance_door(h, &a, nullptr);
 }
 
-// A whole /api/wow job's device work in one call (apply_wow_sr, wow_sr.py:85-110): RGB image in, RGB2BGR, RealESRGAN.enhance,
-// BGR2RGB, _enhance_for_crops (prm != NULL), RGB image out -- one upload, one download, nothing in between on the host.
 int s2sr_enhance_job_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
                         uint8_t* out_rgb) {
-    EnhanceCall c = call_u8(rgb, H, W, tile, pad, out_rgb, nullptr);
-    c.swap_rb = true; c.prm = prm;
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    s2sr_enhance_args a = form(8, rgb, H, W, tile, pad, out_rgb, nullptr);
+    a.swap_rb = 1; a.prm = prm;
+    return enhance_door(h, &a, nullptr);
 }
 
 int s2sr_enhance_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out) {
-    const EnhanceCall c = call_u8(img, H, W, tile, pad, nullptr, out);
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    const s2sr_enhance_args a = form(8, img, H, W, tile, pad, nullptr, out);
+    return enhance_door(h, &a, nullptr);
 }
 
 int s2sr_tile_process_f32(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, float* out) {
-    EnhanceCall c = call_u8(img, H, W, tile, pad, nullptr, out);
-    c.force_tiled = true;
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    s2sr_enhance_args a = form(8, img, H, W, tile, pad, nullptr, out);
+    a.force_tiled = 1;
+    return enhance_door(h, &a, nullptr);
 }
 
-// RealESRGAN.enhance for 16-bit rasters (upstream RealESRGANer's max_range = 65535 branch, with a value range): HxWx3 u16 ->
-// 4Hx4Wx3 u16 and / or the unquantised HWC fp32 image.
 int s2sr_enhance_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
                      uint16_t* out_u16, float* out_f32) {
-    EnhanceCall c = call_u16(img, H, W, tile, pad, lo, hi, out_u16, out_f32);
-    c.required = "s2sr_enhance_u16: an image, positive sizes and at least one output are required";
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    s2sr_enhance_args a = form(16, img, H, W, tile, pad, out_u16, out_f32);
+    a.lo = lo; a.hi = hi;
+    return enhance_door(h, &a, "s2sr_enhance_u16: an image, positive sizes and at least one output are required");
 }
 
-// The seam-blended doors.  An image the switch leaves whole, or whose plan has no ramp (pad 0), is pasted as the default doors
-// paste it (an 8-bit call for both images then runs the net twice).
 int s2sr_enhance_blend_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
                           int32_t swap_rb, uint8_t* out_u8, float* out_f32) {
-    EnhanceCall c = call_u8(img, H, W, tile, pad, out_u8, out_f32);
-    c.blend = true; c.prm = prm; c.swap_rb = swap_rb != 0;
-    c.required = "s2sr_enhance_blend: an image, positive sizes and at least one output are required";
-    if (!img) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u8: an image is required") : S2SR_E_INVALID;
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    s2sr_enhance_args a = form(8, img, H, W, tile, pad, out_u8, out_f32);
+    a.blend = 1; a.prm = prm; a.swap_rb = swap_rb;
+    if (!img) return form_refusal(h, "s2sr_enhance_blend_u8: an image is required");
+    return enhance_door(h, &a, "s2sr_enhance_blend: an image, positive sizes and at least one output are required");
 }
 
 int s2sr_enhance_blend_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
                            uint16_t* out_u16, float* out_f32) {
-    EnhanceCall c = call_u16(img, H, W, tile, pad, lo, hi, out_u16, out_f32);
-    c.blend = true;
-    c.required = "s2sr_enhance_blend: an image, positive sizes and at least one output are required";
-    if (!img) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_blend_u16: an image is required") : S2SR_E_INVALID;
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    s2sr_enhance_args a = form(16, img, H, W, tile, pad, out_u16, out_f32);
+    a.lo = lo; a.hi = hi; a.blend = 1;
+    if (!img) return form_refusal(h, "s2sr_enhance_blend_u16: an image is required");
+    return enhance_door(h, &a, "s2sr_enhance_blend: an image, positive sizes and at least one output are required");
 }
 
-// The masked doors: every 8-bit / 16-bit whole-image door with a mask.  blend, prm, swap_rb as s2sr_enhance_blend_u8.
 int s2sr_enhance_masked_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
                            int32_t swap_rb, int32_t blend, const s2sr_mask* m, uint8_t* out_u8) {
-    EnhanceCall c = call_u8(img, H, W, tile, pad, out_u8, nullptr);
-    c.prm = prm; c.swap_rb = swap_rb != 0; c.blend = blend != 0;
-    c.required = "s2sr_enhance_masked_u8: an image, positive sizes and out_u8 are required";
-    if (!m) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_masked_u8: a mask is required (m == NULL)") : S2SR_E_INVALID;
-    c.masked = true; c.valid = m->valid; c.radius = m->radius; c.out_nodata = m->out_nodata;
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    s2sr_enhance_args a = form(8, img, H, W, tile, pad, out_u8, nullptr);
+    a.prm = prm; a.swap_rb = swap_rb; a.blend = blend; a.mask = m;
+    if (!m) return form_refusal(h, "s2sr_enhance_masked_u8: a mask is required (m == NULL)");
+    return enhance_door(h, &a, "s2sr_enhance_masked_u8: an image, positive sizes and out_u8 are required");
 }
 
 int s2sr_enhance_masked_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
                             int32_t blend, const s2sr_mask* m, uint16_t* out_u16) {
-    EnhanceCall c = call_u16(img, H, W, tile, pad, lo, hi, out_u16, nullptr);
-    c.blend = blend != 0;
-    c.required = "s2sr_enhance_masked_u16: an image, positive sizes and out_u16 are required";
-    if (!m) return h ? fail(h, S2SR_E_INVALID, "s2sr_enhance_masked_u16: a mask is required (m == NULL)") : S2SR_E_INVALID;
-    c.masked = true; c.valid = m->valid; c.radius = m->radius; c.out_nodata = m->out_nodata;
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    s2sr_enhance_args a = form(16, img, H, W, tile, pad, out_u16, nullptr);
+    a.lo = lo; a.hi = hi; a.blend = blend; a.mask = m;
+    if (!m) return form_refusal(h, "s2sr_enhance_masked_u16: a mask is required (m == NULL)");
+    return enhance_door(h, &a, "s2sr_enhance_masked_u16: an image, positive sizes and out_u16 are required");
 }
 
-// The consistent doors: every 8-bit / 16-bit whole-image door with the back-projection pass.  prm, swap_rb, blend as
-// s2sr_enhance_blend_u8; m NULL or as the masked doors.
-static const char* kConsMode = "consistency: mode must be 1 (S2SR_CONSISTENCY_EXACT) or 2 (S2SR_CONSISTENCY_SMOOTH)";
 int s2sr_enhance_consistent_u8(s2sr_handle* h, const uint8_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, const s2sr_pp_params* prm,
                                int32_t swap_rb, int32_t blend, const s2sr_mask* m, int32_t mode, uint8_t* out_u8, uint64_t* inexact) {
-    EnhanceCall c = call_u8(img, H, W, tile, pad, out_u8, nullptr);
-    c.prm = prm; c.swap_rb = swap_rb != 0; c.blend = blend != 0;
-    c.required = "s2sr_enhance_consistent_u8: an image, positive sizes and out_u8 are required";
-    if (mode != S2SR_CONSISTENCY_EXACT && mode != S2SR_CONSISTENCY_SMOOTH) return h ? fail(h, S2SR_E_INVALID, kConsMode) : S2SR_E_INVALID;
-    c.consistency = mode; c.inexact = inexact;
-    if (m) { c.masked = true; c.valid = m->valid; c.radius = m->radius; c.out_nodata = m->out_nodata; }
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    s2sr_enhance_args a = form(8, img, H, W, tile, pad, out_u8, nullptr);
+    a.prm = prm; a.swap_rb = swap_rb; a.blend = blend; a.mask = m; a.consistency = mode; a.inexact = inexact;
+    if (mode != S2SR_CONSISTENCY_EXACT && mode != S2SR_CONSISTENCY_SMOOTH) return form_refusal(h, kConsMode);   // (0 is "off" in the record)
+    return enhance_door(h, &a, "s2sr_enhance_consistent_u8: an image, positive sizes and out_u8 are required");
 }
 
 int s2sr_enhance_consistent_u16(s2sr_handle* h, const uint16_t* img, int32_t H, int32_t W, int32_t tile, int32_t pad, int32_t lo, int32_t hi,
                                 int32_t blend, const s2sr_mask* m, int32_t mode, uint16_t* out_u16, uint64_t* inexact) {
-    EnhanceCall c = call_u16(img, H, W, tile, pad, lo, hi, out_u16, nullptr);
-    c.blend = blend != 0;
-    c.required = "s2sr_enhance_consistent_u16: an image, positive sizes and out_u16 are required";
-    if (mode != S2SR_CONSISTENCY_EXACT && mode != S2SR_CONSISTENCY_SMOOTH) return h ? fail(h, S2SR_E_INVALID, kConsMode) : S2SR_E_INVALID;
-    c.consistency = mode; c.inexact = inexact;
-    if (m) { c.masked = true; c.valid = m->valid; c.radius = m->radius; c.out_nodata = m->out_nodata; }
-    RUN_WITH_STREAM_RECOVERY(h, enhance_call(h, c));
+    s2sr_enhance_args a = form(16, img, H, W, tile, pad, out_u16, nullptr);
+    a.lo = lo; a.hi = hi; a.blend = blend; a.mask = m; a.consistency = mode; a.inexact = inexact;
+    if (mode != S2SR_CONSISTENCY_EXACT && mode != S2SR_CONSISTENCY_SMOOTH) return form_refusal(h, kConsMode);
+    return enhance_door(h, &a, "s2sr_enhance_consistent_u16: an image, positive sizes and out_u16 are required");
 }
 
 // The pass alone: host images in, host image out (out may be sr).  No weights needed.  ONE lock scope, as s2sr_postprocess_u8.

@@ -10,7 +10,7 @@ import os
 import threading
 import weakref
 from pathlib import Path
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 
@@ -44,6 +44,19 @@ class PPParams(C.Structure):
 
 class Mask(C.Structure):                   # s2sr_mask
     _fields_ = [("valid", C.c_void_p), ("radius", C.c_int32), ("out_nodata", C.c_int32)]
+
+
+class EnhanceArgs(C.Structure):            # s2sr_enhance_args: one whole-image call
+    _fields_ = [("size", C.c_uint32), ("bits", C.c_int32), ("img", C.c_void_p)] + \
+               [(n, C.c_int32) for n in ("H", "W", "tile", "pad", "lo", "hi")] + \
+               [("prm", C.POINTER(PPParams)), ("swap_rb", C.c_int32), ("blend", C.c_int32), ("force_tiled", C.c_int32),
+                ("mask", C.POINTER(Mask)), ("consistency", C.c_int32), ("out", C.c_void_p), ("out_f32", C.c_void_p), ("inexact", C.c_void_p)]
+
+
+class Enhanced(NamedTuple):                # Engine.enhance's result; None for what was not asked
+    q: Optional[np.ndarray]                # the quantised image
+    f32: Optional[np.ndarray]              # the unquantised HWC float32 image
+    inexact: Optional[np.ndarray]          # uint64 [3], with a consistency pass
 
 
 class DebugConfig(C.Structure):
@@ -135,6 +148,7 @@ _PROTOS = {
     "s2sr_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_forward_batch_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
     "s2sr_forward_batch_u16_dev": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
+    "s2sr_enhance": (C.c_int, [C.c_void_p, C.POINTER(EnhanceArgs)]),
     "s2sr_enhance_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p]),
     "s2sr_enhance_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_enhance_blend_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.POINTER(PPParams), C.c_int32, C.c_void_p, C.c_void_p]),
@@ -647,38 +661,48 @@ class Engine:
         self._check(self._lib.s2sr_forward_f32(self._h, _ptr(x), N, H, W, _ptr(y)), "s2sr_forward_f32")
         return y
 
-    def enhance_u8(self, img: np.ndarray, tile: int = 256, pad: int = 10) -> np.ndarray:
-        img = np.ascontiguousarray(img, dtype=np.uint8)
+    # -- the whole-image door (include/s2sr.h s2sr_enhance_args: every keyword below is the field of that name) ------------------
+    def enhance(self, img: np.ndarray, *, tile: int = 256, pad: int = 10, lo: int = 0, hi: int = 65535, prm: Optional[PPParams] = None,
+                swap_rb: bool = False, blend: bool = False, force_tiled: bool = False, valid=None, radius: int = 32, out_nodata: int = 0,
+                consistency: int = 0, quantised: bool = True, want_f32: bool = False) -> Enhanced:
+        """HxWx3 uint8 or uint16 (bits from the dtype) through s2sr_enhance with the options that are on -> Enhanced(q, f32,
+        inexact).  valid (uint8 [H, W], nonzero = valid; None: not masked) with radius and out_nodata is the record's mask;
+        quantised / want_f32 choose the outputs.  Which combinations exist is the library's to say (S2srError with its text)."""
+        img = np.asarray(img)
+        if img.dtype not in (np.uint8, np.uint16):
+            raise TypeError(f"enhance takes a uint8 or uint16 image, got {img.dtype}")
+        img = np.ascontiguousarray(img)
         H, W, c = img.shape
         assert c == 3
-        out = pinned_pool.empty((self.scale * H, self.scale * W, 3), np.uint8)
-        self._check(self._lib.s2sr_enhance_u8(self._h, _ptr(img), H, W, tile, pad, _ptr(out)), "s2sr_enhance_u8")
-        return out
+        shape = (self.scale * H, self.scale * W, 3)
+        m = None
+        if valid is not None:
+            valid = self._valid(valid, H, W, "enhance")      # (valid and m stay alive to the end of the call)
+            m = Mask(valid.ctypes.data, int(radius), int(out_nodata))
+        q = pinned_pool.empty(shape, img.dtype) if quantised else None
+        f = np.empty(shape, dtype=np.float32) if want_f32 else None
+        bad = np.zeros(3, np.uint64) if consistency else None
+        data = lambda a: None if a is None else a.ctypes.data
+        args = EnhanceArgs(C.sizeof(EnhanceArgs), 8 * img.itemsize, img.ctypes.data, H, W, int(tile), int(pad), int(lo), int(hi),
+                           None if prm is None else C.pointer(prm), int(bool(swap_rb)), int(bool(blend)), int(bool(force_tiled)),
+                           None if m is None else C.pointer(m), int(consistency), data(q), data(f), data(bad))
+        self._check(self._lib.s2sr_enhance(self._h, C.byref(args)), "s2sr_enhance")
+        return Enhanced(q, f, bad)
+
+    # The forms: the doors from before the record, each a spelling of `enhance` (include/s2sr.h lists the fields each sets).
+    def enhance_u8(self, img: np.ndarray, tile: int = 256, pad: int = 10) -> np.ndarray:
+        return self.enhance(np.ascontiguousarray(img, dtype=np.uint8), tile=tile, pad=pad).q
 
     def enhance_job_u8(self, rgb: np.ndarray, prm: Optional[PPParams] = None, tile: int = 256, pad: int = 10) -> np.ndarray:
         """RGB in -> (BGR) net -> RGB -> post-process `prm` (None: none) -> RGB out: a job's device work in one call."""
-        rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
-        H, W, c = rgb.shape
-        assert c == 3
-        out = pinned_pool.empty((self.scale * H, self.scale * W, 3), np.uint8)
-        self._check(self._lib.s2sr_enhance_job_u8(self._h, _ptr(rgb), H, W, tile, pad, C.byref(prm) if prm is not None else None, _ptr(out)),
-                    "s2sr_enhance_job_u8")
-        return out
+        return self.enhance(np.ascontiguousarray(rgb, dtype=np.uint8), prm=prm, swap_rb=True, tile=tile, pad=pad).q
 
     def enhance_f32(self, img: np.ndarray, tile: int = 256, pad: int = 10) -> np.ndarray:
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        H, W, c = img.shape
-        out = np.empty((self.scale * H, self.scale * W, 3), dtype=np.float32)
-        self._check(self._lib.s2sr_enhance_f32(self._h, _ptr(img), H, W, tile, pad, _ptr(out)), "s2sr_enhance_f32")
-        return out
+        return self.enhance(np.ascontiguousarray(img, dtype=np.uint8), tile=tile, pad=pad, quantised=False, want_f32=True).f32
 
     def tile_process_f32(self, img: np.ndarray, tile: int = 256, pad: int = 10) -> np.ndarray:
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        H, W, c = img.shape
-        out = np.empty((self.scale * H, self.scale * W, 3), dtype=np.float32)
-        self._check(self._lib.s2sr_tile_process_f32(self._h, _ptr(img), H, W, tile, pad, _ptr(out)),
-                    "s2sr_tile_process_f32")
-        return out
+        return self.enhance(np.ascontiguousarray(img, dtype=np.uint8), tile=tile, pad=pad, force_tiled=True, quantised=False,
+                            want_f32=True).f32
 
     # -- the 16-bit door (include/s2sr.h: uint16 in, uint16 x4 out, value range lo, hi) ---------
     def forward_batch_u16(self, tiles: np.ndarray, lo: int = 0, hi: int = 65535, want_f32: bool = False):
@@ -700,45 +724,29 @@ class Engine:
         self._check(self._lib.s2sr_forward_batch_u16_dev(self._h, d_in, B, h, w, int(lo), int(hi), d_out, C.c_void_p(stream)),
                     "s2sr_forward_batch_u16_dev")
 
+    @staticmethod
+    def _u16(img, what: str):
+        if np.asarray(img).dtype != np.uint16:
+            raise TypeError(f"{what} takes a uint16 image, got {np.asarray(img).dtype}")
+        return img
+
     def enhance_u16(self, img: np.ndarray, lo: int = 0, hi: int = 65535, tile: int = 256, pad: int = 10, want_f32: bool = False):
         """HxWx3 uint16 -> 4Hx4Wx3 uint16 (whole / tiled as enhance_u8); want_f32: (that, the unquantised HWC float32 image)."""
-        if np.asarray(img).dtype != np.uint16:
-            raise TypeError(f"enhance_u16 takes a uint16 image, got {np.asarray(img).dtype}")
-        img = np.ascontiguousarray(img)
-        H, W, c = img.shape
-        assert c == 3
-        out = pinned_pool.empty((4 * H, 4 * W, 3), np.uint16)
-        f = np.empty((4 * H, 4 * W, 3), dtype=np.float32) if want_f32 else None
-        self._check(self._lib.s2sr_enhance_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), _ptr(out), _ptr(f) if want_f32 else None),
-                    "s2sr_enhance_u16")
-        return (out, f) if want_f32 else out
+        r = self.enhance(self._u16(img, "enhance_u16"), lo=lo, hi=hi, tile=tile, pad=pad, want_f32=want_f32)
+        return (r.q, r.f32) if want_f32 else r.q
 
     # -- the seam-blended stitch (include/s2sr.h: the default doors' windows, cross-faded where they overlap) -------------------
     def enhance_blend_u8(self, img: np.ndarray, prm: Optional[PPParams] = None, swap_rb: bool = False, tile: int = 256, pad: int = 10,
                          want_f32: bool = False):
         """enhance_u8 (prm None, swap_rb False) or enhance_job_u8 (swap_rb True) with the blended paste; want_f32 (plain calls
         only): (the u8 image, the unquantised HWC float32 image)."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        H, W, c = img.shape
-        assert c == 3
-        out = pinned_pool.empty((self.scale * H, self.scale * W, 3), np.uint8)
-        f = np.empty((self.scale * H, self.scale * W, 3), dtype=np.float32) if want_f32 else None
-        self._check(self._lib.s2sr_enhance_blend_u8(self._h, _ptr(img), H, W, tile, pad, C.byref(prm) if prm is not None else None,
-                                                    int(bool(swap_rb)), _ptr(out), _ptr(f) if want_f32 else None), "s2sr_enhance_blend_u8")
-        return (out, f) if want_f32 else out
+        r = self.enhance(np.ascontiguousarray(img, dtype=np.uint8), prm=prm, swap_rb=swap_rb, blend=True, tile=tile, pad=pad, want_f32=want_f32)
+        return (r.q, r.f32) if want_f32 else r.q
 
     def enhance_blend_u16(self, img: np.ndarray, lo: int = 0, hi: int = 65535, tile: int = 256, pad: int = 10, want_f32: bool = False):
         """enhance_u16 with the blended paste."""
-        if np.asarray(img).dtype != np.uint16:
-            raise TypeError(f"enhance_blend_u16 takes a uint16 image, got {np.asarray(img).dtype}")
-        img = np.ascontiguousarray(img)
-        H, W, c = img.shape
-        assert c == 3
-        out = pinned_pool.empty((4 * H, 4 * W, 3), np.uint16)
-        f = np.empty((4 * H, 4 * W, 3), dtype=np.float32) if want_f32 else None
-        self._check(self._lib.s2sr_enhance_blend_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), _ptr(out),
-                                                     _ptr(f) if want_f32 else None), "s2sr_enhance_blend_u16")
-        return (out, f) if want_f32 else out
+        r = self.enhance(self._u16(img, "enhance_blend_u16"), lo=lo, hi=hi, blend=True, tile=tile, pad=pad, want_f32=want_f32)
+        return (r.q, r.f32) if want_f32 else r.q
 
     # -- nodata-aware enhance (include/s2sr.h, DESIGN.md 7.4: fill the invalid pixels in front of the net, mask behind everything) ----
     @staticmethod
@@ -769,30 +777,18 @@ class Engine:
                           swap_rb: bool = False, blend: bool = False, tile: int = 256, pad: int = 10) -> np.ndarray:
         """enhance_u8 / enhance_job_u8 (swap_rb) / enhance_blend_u8 (blend) on the filled image, out_nodata written over the output
         pixels of the invalid input pixels."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        H, W, c = img.shape
-        assert c == 3
-        valid = self._valid(valid, H, W, "enhance_masked_u8")
-        m = Mask(valid.ctypes.data, int(radius), int(out_nodata))
-        out = pinned_pool.empty((self.scale * H, self.scale * W, 3), np.uint8)
-        self._check(self._lib.s2sr_enhance_masked_u8(self._h, _ptr(img), H, W, tile, pad, C.byref(prm) if prm is not None else None,
-                                                     int(bool(swap_rb)), int(bool(blend)), C.byref(m), _ptr(out)), "s2sr_enhance_masked_u8")
-        return out
+        if valid is None:
+            raise ValueError("enhance_masked_u8: valid must be [H, W], got None")
+        return self.enhance(np.ascontiguousarray(img, dtype=np.uint8), valid=valid, radius=radius, out_nodata=out_nodata, prm=prm,
+                            swap_rb=swap_rb, blend=blend, tile=tile, pad=pad).q
 
     def enhance_masked_u16(self, img: np.ndarray, valid: np.ndarray, lo: int = 0, hi: int = 65535, radius: int = 32, out_nodata: int = 0,
                            blend: bool = False, tile: int = 256, pad: int = 10) -> np.ndarray:
         """enhance_u16 / enhance_blend_u16 (blend) on the filled image, masked as enhance_masked_u8."""
-        if np.asarray(img).dtype != np.uint16:
-            raise TypeError(f"enhance_masked_u16 takes a uint16 image, got {np.asarray(img).dtype}")
-        img = np.ascontiguousarray(img)
-        H, W, c = img.shape
-        assert c == 3
-        valid = self._valid(valid, H, W, "enhance_masked_u16")
-        m = Mask(valid.ctypes.data, int(radius), int(out_nodata))
-        out = pinned_pool.empty((4 * H, 4 * W, 3), np.uint16)
-        self._check(self._lib.s2sr_enhance_masked_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), int(bool(blend)), C.byref(m),
-                                                      _ptr(out)), "s2sr_enhance_masked_u16")
-        return out
+        if valid is None:
+            raise ValueError("enhance_masked_u16: valid must be [H, W], got None")
+        return self.enhance(self._u16(img, "enhance_masked_u16"), valid=valid, lo=lo, hi=hi, radius=radius, out_nodata=out_nodata,
+                            blend=blend, tile=tile, pad=pad).q
 
     # -- radiometric consistency (include/s2sr.h, DESIGN.md 7.5: block means of the output reproduce the input pixels) ------------
     def consistency(self, sr: np.ndarray, img: np.ndarray, mode: int = 1, lo: int = 0, hi: int = 65535, band_rows: int = 0):
@@ -821,45 +817,26 @@ class Engine:
     consistency_u8 = consistency
     consistency_u16 = consistency
 
-    def _mask_arg(self, valid, H: int, W: int, radius: int, out_nodata: int, what: str):
-        """(the s2sr_mask argument or None, what must stay alive during the call)"""
-        if valid is None:
-            return None, None
-        valid = self._valid(valid, H, W, what)
-        m = Mask(valid.ctypes.data, int(radius), int(out_nodata))
-        return C.byref(m), (valid, m)
+    @staticmethod
+    def _mode(mode, what: str) -> int:
+        if mode not in (1, 2):                         # (0 means "off" in the record: the consistent forms do not offer it)
+            raise S2srError(f"{what} failed (invalid argument): consistency: mode must be 1 or 2, got {mode}")
+        return int(mode)
 
     def enhance_consistent_u8(self, img: np.ndarray, mode: int = 1, prm: Optional[PPParams] = None, swap_rb: bool = False, blend: bool = False,
                               valid=None, radius: int = 32, out_nodata: int = 0, tile: int = 256, pad: int = 10):
         """enhance_u8 / enhance_job_u8 (swap_rb) / enhance_blend_u8 (blend) / enhance_masked_u8 (valid) with the consistency pass
         behind the paste -> (the image, inexact uint64 [3])."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        H, W, c = img.shape
-        assert c == 3
-        m, keep = self._mask_arg(valid, H, W, radius, out_nodata, "enhance_consistent_u8")
-        out = pinned_pool.empty((self.scale * H, self.scale * W, 3), np.uint8)
-        bad = np.zeros(3, np.uint64)
-        self._check(self._lib.s2sr_enhance_consistent_u8(self._h, _ptr(img), H, W, tile, pad, C.byref(prm) if prm is not None else None,
-                                                         int(bool(swap_rb)), int(bool(blend)), m, int(mode), _ptr(out), _ptr(bad)),
-                    "s2sr_enhance_consistent_u8")
-        del keep
-        return out, bad
+        r = self.enhance(np.ascontiguousarray(img, dtype=np.uint8), consistency=self._mode(mode, "enhance_consistent_u8"), prm=prm,
+                         swap_rb=swap_rb, blend=blend, valid=valid, radius=radius, out_nodata=out_nodata, tile=tile, pad=pad)
+        return r.q, r.inexact
 
     def enhance_consistent_u16(self, img: np.ndarray, lo: int = 0, hi: int = 65535, mode: int = 1, blend: bool = False, valid=None,
                                radius: int = 32, out_nodata: int = 0, tile: int = 256, pad: int = 10):
         """enhance_u16 / enhance_blend_u16 (blend) / enhance_masked_u16 (valid) with the consistency pass -> (the image, inexact)."""
-        if np.asarray(img).dtype != np.uint16:
-            raise TypeError(f"enhance_consistent_u16 takes a uint16 image, got {np.asarray(img).dtype}")
-        img = np.ascontiguousarray(img)
-        H, W, c = img.shape
-        assert c == 3
-        m, keep = self._mask_arg(valid, H, W, radius, out_nodata, "enhance_consistent_u16")
-        out = pinned_pool.empty((4 * H, 4 * W, 3), np.uint16)
-        bad = np.zeros(3, np.uint64)
-        self._check(self._lib.s2sr_enhance_consistent_u16(self._h, _ptr(img), H, W, tile, pad, int(lo), int(hi), int(bool(blend)), m, int(mode),
-                                                          _ptr(out), _ptr(bad)), "s2sr_enhance_consistent_u16")
-        del keep
-        return out, bad
+        r = self.enhance(self._u16(img, "enhance_consistent_u16"), consistency=self._mode(mode, "enhance_consistent_u16"), lo=lo, hi=hi,
+                         blend=blend, valid=valid, radius=radius, out_nodata=out_nodata, tile=tile, pad=pad)
+        return r.q, r.inexact
 
     # -- display rendering of 16-bit images (include/s2sr.h; policy between the two passes: s2sr/display.py) ---------------------
     @staticmethod
