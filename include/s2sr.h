@@ -484,6 +484,15 @@ int  s2sr_pp_band_rows_dev(s2sr_handle* h, const void* d_img, int32_t y0, int32_
  *   device copy (cnx, cny must match it; any other call on the handle in between invalidates the copy -> S2SR_E_INVALID). */
 int  s2sr_warp_bilinear_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, const float* grid, int32_t gh, int32_t gw,
                            int32_t step, int32_t OH, int32_t OW, uint8_t* out_rgba);
+/* The warp in front of a nodata-transparent pyramid.  valid = uint8 [ceil(H / valid_scale)][ceil(W / valid_scale)], nonzero = valid:
+ * source pixel (y, x) is valid iff valid[y / valid_scale][x / valid_scale] != 0 (the convention of s2sr_mask).  Coordinates, coverage
+ * and taps are the plain call's.  All four taps valid: the plain call's bytes.  No tap valid: (0,0,0,0).  Otherwise the valid taps'
+ * bilinear weights are summed to ws; ws < 0.5: (0,0,0,0); else colour = (sum of w * p over the valid taps) / ws rounded half up,
+ * alpha 255 (fp32, every operation rounded on its own, fixed order).  Alpha is 0 or 255 and colour is 0 wherever alpha is 0; the
+ * bytes of an invalid source pixel never reach the output.  Refused with S2SR_E_INVALID: valid == NULL, valid_scale < 1, and what
+ * the plain call refuses.  Leaves its raster on the device exactly as the plain call does. */
+int  s2sr_warp_bilinear_masked_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* valid, int32_t valid_scale,
+                                  const float* grid, int32_t gh, int32_t gw, int32_t step, int32_t OH, int32_t OW, uint8_t* out_rgba);
 int  s2sr_tiles_base_u8(s2sr_handle* h, const uint8_t* rgba, int32_t H, int32_t W, const int32_t* col_lo, const int32_t* col_hi,
                         const int32_t* row_lo, const int32_t* row_hi, int32_t nx, int32_t ny, uint8_t* out);
 int  s2sr_tiles_overview_u8(s2sr_handle* h, const uint8_t* child, int32_t cnx, int32_t cny, int32_t ox, int32_t oy, int32_t pnx,

@@ -48,6 +48,7 @@ class WowRequest(BaseModel):         # main.py:200-208
     fill_radius: int = 32            # ... and how far they are filled from their valid neighbours in front of the net (1..64)
     consistency: Optional[str] = None   # not in the reference: "exact" or "smooth" -- block means reproduce the input pixels
     extra_bands: Optional[Union[str, List[int]]] = None   # not in the reference: "all" or band numbers from 4 on, carried to the SR grid; 16-bit jobs only
+    transparent_tiles: bool = False  # not in the reference: the tile pyramid shows the map through the job's nodata pixels; with nodata only
 
 
 class SRResponse(BaseModel):         # main.py:230-235
@@ -196,19 +197,21 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
         tifs = sorted(source_dir.glob("*.tif"), key=lambda x: x.stat().st_mtime, reverse=True)
         return tifs[0] if tifs else None
 
-    def _default_tiler(sr_tif, tiles_dir, stretch=None):
+    def _default_tiler(sr_tif, tiles_dir, stretch=None, mask=None):
         from app.tiling import process_raster_to_tiles
         process_raster_to_tiles(input_path=sr_tif, tiles_dir=tiles_dir, min_zoom=tile_min_zoom,
                                 max_zoom=min(tile_max_zoom + 2, 20),          # "Higher zoom for SR" (main.py:276)
-                                **({"stretch": stretch} if stretch is not None else {}))
+                                **({"stretch": stretch} if stretch is not None else {}),
+                                **({"valid": mask[0], "valid_scale": mask[1], "nodata": mask[2]} if mask is not None else {}))
 
-    def _tile(result, sub, stretch=None):
+    def _tile(result, sub, stretch=None, mask=None):
+        """mask (a transparent_tiles job; the default tiler only): (the input's mask, the SR scale, the value the SR GeoTIFF declares)"""
         sr_tif = result["outputs"].get("sr_tif")
         run = _default_tiler if tiler is None else tiler
         if run and sr_tif and Path(sr_tif).exists():
             tiles_dir = data_dir / sub
-            if tiler is None and stretch is not None:
-                run(Path(sr_tif), tiles_dir, stretch)
+            if tiler is None and (stretch is not None or mask is not None):
+                run(Path(sr_tif), tiles_dir, stretch, mask)
             else:
                 run(Path(sr_tif), tiles_dir)
             result["tiles_dir"] = str(tiles_dir)
@@ -234,7 +237,7 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
 
     def run_wow_job(job_id, input_file, output_dir, enhance_crops, auto_fetch=True, max_age_days=30,
                     max_cloud_cover=30.0, force_fetch=False, model="realesrgan_x4", seam_blend=False, bit_depth=8,
-                    display=None, nodata=None, fill_radius=32, consistency=None, extra_bands=None):   # main.py:290-368
+                    display=None, nodata=None, fill_radius=32, consistency=None, extra_bands=None, transparent_tiles=False):   # main.py:290-368
         try:
             if input_file is None and auto_fetch:
                 _set(job_id, status="fetching",
@@ -263,8 +266,13 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             _set(job_id, status="tiling", message="Generating tiles from WOW SR image...")
             # a 16-bit job's tiles show the rendering of its PNG: the job's stretch with the limits it found
             info = result.get("sr_metadata", {}).get("display") if display is not None else None
+            mask = None
+            if transparent_tiles and nodata is not None:
+                # the job's own mask (input resolution; the warp reads it at the SR scale); the value is the one its GeoTIFF declares
+                from app.wow_sr import input_mask
+                mask = (input_mask(input_file, nodata, bit_depth), 4, "tag")
             _tile(result, "tiles_wow", stretch=None if info is None else
-                  {k: info[k] for k in ("p_lo", "p_hi", "linked", "gamma", "nodata", "limits")})
+                  {k: info[k] for k in ("p_lo", "p_hi", "linked", "gamma", "nodata", "limits")}, mask=mask)
             _set(job_id, status="completed", message="WOW Super-resolution complete!", result=result)
         except Exception as e:                                               # noqa: BLE001
             _set(job_id, status="failed", message=str(e))
@@ -336,6 +344,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                 check_args(request.nodata, request.fill_radius)
             except ValueError as e:
                 raise HTTPException(status_code=400, detail=str(e))
+        if request.transparent_tiles and request.nodata is None:
+            raise HTTPException(status_code=400, detail="transparent_tiles shows the map through the job's nodata pixels: pass nodata")
         _check_consistency(request.consistency)
         if request.extra_bands is not None:
             if request.bit_depth != 16:
@@ -366,7 +376,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                                   **({"display": request.display} if request.display is not None else {}),
                                   **({"nodata": request.nodata, "fill_radius": request.fill_radius} if request.nodata is not None else {}),
                                   **({"consistency": request.consistency} if request.consistency is not None else {}),
-                                  **({"extra_bands": request.extra_bands} if request.extra_bands is not None else {}))
+                                  **({"extra_bands": request.extra_bands} if request.extra_bands is not None else {}),
+                                  **({"transparent_tiles": True} if request.transparent_tiles else {}))
         msg = (f"WOW SR started: {input_file.name} -> Real-ESRGAN x4 + Enhanced" if input_file else
                f"WOW SR started: auto-fetching best image (last {request.max_age_days}d, cloud <={request.max_cloud_cover}%)")
         return SRResponse(job_id=job_id, status="queued", message=msg)

@@ -145,20 +145,84 @@ def _rgb_u8(arr: np.ndarray, stretch=None) -> np.ndarray:
         return render_u16(np.ascontiguousarray(rgb), stretch, eng)[0]
 
 
-def reproject_to_web_mercator(input_path: Path, output_path: Path, resample_method: str = "bilinear", stretch=None) -> Path:
+def _check_mask_args(nodata, valid, valid_scale) -> None:
+    """The refusals of the nodata arguments, before a file is read: nodata None, an integer or "tag" (s2sr.nodata.check_args);
+    valid_scale an integer of at least 1."""
+    from s2sr.nodata import DEFAULT_FILL_RADIUS, check_args
+    check_args(nodata, DEFAULT_FILL_RADIUS)
+    if isinstance(valid_scale, bool) or not isinstance(valid_scale, (int, np.integer)) or valid_scale < 1:
+        raise ValueError(f"valid_scale {valid_scale!r}: an integer of at least 1")
+
+
+def _mask_of(arr: np.ndarray, tags: dict, path, nodata, valid, valid_scale: int):
+    """The mask a nodata-transparent pyramid is cut with -> (valid uint8 or None, its scale, the nodata value or None).
+    nodata: an integer, or "tag" = the file's GDAL_NODATA tag (ValueError when it has none); the mask is then
+    s2sr.nodata.mask_from_value on bands 1-3 of the raster AS READ (before _rgb_u8's stretch), scale 1.  valid: the caller's own
+    mask, [ceil(H / valid_scale), ceil(W / valid_scale)]; it wins over the value (at 8 bits a measured pixel can equal it)."""
+    from s2sr.nodata import mask_from_value
+    value = None
+    if nodata is not None:
+        value = rio.resolve_nodata(nodata, rio.GeoRef({}, tiff_lite.parse_nodata(tags.get(tiff_lite.GDAL_NODATA))), path)
+    if valid is not None:
+        return native.warp_mask(arr.shape[:2] + (3,), valid, valid_scale), int(valid_scale), value
+    if value is None:
+        return None, 1, None
+    raw = arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2)
+    return mask_from_value(raw, value), 1, value
+
+
+def _u8_nodata(value) -> Optional[int]:
+    """What the 8-bit <stem>_3857.tif holds in its alpha-0 pixels and declares in GDAL_NODATA: the value where a byte can hold it,
+    0 otherwise (a 16-bit product's value above 255 under a display stretch); None: no value known, the file as ever."""
+    if value is None:
+        return None
+    return int(value) if value == int(value) and 0 <= value <= 255 else 0
+
+
+def _rgb_with_nodata(rgba: np.ndarray, fill: int) -> np.ndarray:
+    """the RGB(A) raster whose alpha-0 pixels hold `fill`: colour is already 0 there (the warp's contract), so 0 costs nothing"""
+    if fill == 0:
+        return rgba
+    rgb = np.ascontiguousarray(rgba[..., :3])
+    rgb[rgba[..., 3] == 0] = fill
+    return rgb
+
+
+def _masked_rgba(rgb: np.ndarray, mask: Optional[np.ndarray], vs: int) -> np.ndarray:
+    """A raster that is on the EPSG:3857 grid already: alpha 255 (x mask), RGB zeroed where invalid"""
+    h, w = rgb.shape[:2]
+    rgba = np.empty((h, w, 4), np.uint8)
+    rgba[..., :3] = rgb
+    rgba[..., 3] = 255
+    if mask is not None:
+        from s2sr.nodata import upsample_mask
+        rgba[upsample_mask(mask, vs)[:h, :w] == 0] = 0
+    return rgba
+
+
+def reproject_to_web_mercator(input_path: Path, output_path: Path, resample_method: str = "bilinear", stretch=None, nodata=None) -> Path:
     """Writes an RGB GeoTIFF on the EPSG:3857 grid (pixels outside the source are black; the tile
-    generator recomputes coverage from the geometry, so no alpha band is stored).  stretch: see _rgb_u8."""
+    generator recomputes coverage from the geometry, so no alpha band is stored).  stretch: see _rgb_u8.
+    nodata (None, an integer, or "tag"): the input's pixels that hold the value are left out of the bilinear taps,
+    and the file carries the GDAL_NODATA tag and holds the value wherever nothing valid was warped to, the wedges outside the
+    source included -- generate_xyz_tiles(nodata="tag") then cuts a pyramid that is transparent there."""
     if resample_method != "bilinear":
         raise ValueError("only bilinear resampling is implemented (the reference never passes anything else)")
+    _check_mask_args(nodata, None, 1)
     input_path, output_path = Path(input_path), Path(output_path)
-    arr, _tags, place, crs = _read(input_path)
+    arr, tags, place, crs = _read(input_path)
+    mask, vs, value = _mask_of(arr, tags, input_path, nodata, None, 1)
     rgb = _rgb_u8(arr, stretch)
     plan = tiles.plan_warp(rgb.shape[1], rgb.shape[0], place, crs)
     eng, lock = _engine_and_lock()
     with lock:                   # the engine's scratch holds a pyramid chain's previous level (see _cut_pyramid)
-        out = eng.warp_bilinear_u8(rgb, plan.grid, plan.step, plan.out_h, plan.out_w)
+        out = eng.warp_bilinear_u8(rgb, plan.grid, plan.step, plan.out_h, plan.out_w, **({} if mask is None else {"valid": mask, "valid_scale": vs}))
     output_path.parent.mkdir(parents=True, exist_ok=True)
-    rio.write_geotiff_rgb(output_path, np.ascontiguousarray(out[..., :3]), _mercator_tags(plan.placement))
+    fill = _u8_nodata(value)
+    if fill is None:
+        rio.write_geotiff_rgb(output_path, np.ascontiguousarray(out[..., :3]), _mercator_tags(plan.placement))
+    else:
+        rio.write_geotiff_rgb(output_path, np.ascontiguousarray(_rgb_with_nodata(out, fill)[..., :3]), _mercator_tags(plan.placement), nodata=fill)
     logger.info("Reprojection complete: %s", output_path)
     return output_path
 
@@ -223,17 +287,17 @@ def _cut_pyramid(rgba: np.ndarray, place: geo.Placement, output_dir: Path, min_z
 
 
 def generate_xyz_tiles(input_path: Path, output_dir: Path, min_zoom: int = 10, max_zoom: int = 16, tile_size: int = 256,
-                       resampling: str = "average") -> Path:
-    """z/x/y.png (XYZ row order, RGBA) for every tile of zooms min..max that holds data."""
+                       resampling: str = "average", nodata=None, valid=None, valid_scale: int = 1) -> Path:
+    """z/x/y.png (XYZ row order, RGBA) for every tile of zooms min..max that holds data.  nodata / valid / valid_scale: the pixels
+    the pyramid leaves transparent (see _mask_of)."""
     _check_tile_args(tile_size, resampling)
+    _check_mask_args(nodata, valid, valid_scale)
     input_path, output_dir = Path(input_path), Path(output_dir)
-    arr, _tags, place, crs = _read(input_path)
+    arr, tags, place, crs = _read(input_path)
     if crs.epsg != 3857:
         raise ValueError(f"{input_path}: {crs}, tiles are cut from an EPSG:3857 raster (reproject_to_web_mercator first)")
-    h, w = arr.shape[:2]
-    rgba = np.empty((h, w, 4), np.uint8)
-    rgba[..., :3] = arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2)
-    rgba[..., 3] = 255
+    mask, vs, _value = _mask_of(arr, tags, input_path, nodata, valid, valid_scale)
+    rgba = _masked_rgba(arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2), mask, vs)
     _cut_pyramid(rgba, place, output_dir, min_zoom, max_zoom, resampling=resampling)
     logger.info("Tile generation complete: %s", output_dir)
     return output_dir
@@ -250,15 +314,22 @@ def create_tileset_metadata(tiles_dir: Path, bounds_4326: list, min_zoom: int, m
 
 
 def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 10, max_zoom: int = 16, resampling: str = "average",
-                            tile_template: str = "/tiles/{z}/{x}/{y}.png", stretch=None) -> dict:
+                            tile_template: str = "/tiles/{z}/{x}/{y}.png", stretch=None, nodata=None, valid=None,
+                            valid_scale: int = 1) -> dict:
     """Check the CRS, reproject if needed, cut the pyramid, write tileset.json.  stretch (uint16 rasters; ignored for uint8): the
-    8-bit image is the raster's display rendering instead of the global min-max, see _rgb_u8."""
+    8-bit image is the raster's display rendering instead of the global min-max, see _rgb_u8.
+    nodata (None, an integer, or "tag") / valid, valid_scale (the caller's own mask, which wins; see _mask_of): the pyramid is
+    transparent over the pixels that were never measured -- a raster that needs reprojecting goes through the
+    masked warp, one that is EPSG:3857 already gets alpha 255 x mask and RGB 0 where invalid; with a value known <stem>_3857.tif
+    carries the GDAL_NODATA tag and holds the value in every alpha-0 pixel.  Without them every file is what it always was."""
     import time
     _check_tile_args(256, resampling)
+    _check_mask_args(nodata, valid, valid_scale)
     input_path, tiles_dir = Path(input_path), Path(tiles_dir)
     LAST_STATS.clear()
     t0 = time.perf_counter()
-    arr, _tags, place, crs = _read(input_path)
+    arr, tags, place, crs = _read(input_path)
+    mask, vs, value = _mask_of(arr, tags, input_path, nodata, valid, valid_scale)
     h, w, b = arr.shape
     west, south, east, north = place.bounds(w, h)
     t = np.linspace(0.0, 1.0, 21)
@@ -277,18 +348,25 @@ def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 1
             # but the pyramid is cut from the array in hand, with the coverage mask of the warp as alpha
             plan = tiles.plan_warp(w, h, place, crs)
             t2 = time.perf_counter()
-            rgba = eng.warp_bilinear_u8(rgb, plan.grid, plan.step, plan.out_h, plan.out_w)
+            rgba = eng.warp_bilinear_u8(rgb, plan.grid, plan.step, plan.out_h, plan.out_w, **({} if mask is None else {"valid": mask, "valid_scale": vs}))
             t3 = time.perf_counter()
             place = plan.placement
             LAST_STATS.update(warp_plan=t2 - t1, warp_call=t3 - t2)
+            fill = _u8_nodata(value)
 
             def write_3857():            # next to the pyramid, not in front of it: its strips fill the CPUs the device calls leave idle
                 try:
-                    rio.write_geotiff_rgb(input_path.parent / f"{input_path.stem}_3857.tif", rgba, _mercator_tags(plan.placement))   # alpha dropped per strip
+                    out_3857 = input_path.parent / f"{input_path.stem}_3857.tif"
+                    if fill is None:
+                        rio.write_geotiff_rgb(out_3857, rgba, _mercator_tags(plan.placement))   # alpha dropped per strip
+                    else:                # (the pyramid reads the warp's device copy: the host raster is this thread's)
+                        rio.write_geotiff_rgb(out_3857, _rgb_with_nodata(rgba, fill), _mercator_tags(plan.placement), nodata=fill)
                 except BaseException as e:      # noqa: BLE001 -- surfaced below: a failed writer fails the call
                     err.append(e)
             side = threading.Thread(target=write_3857)
             side.start()
+        elif mask is not None:
+            rgba = _masked_rgba(rgb, mask, vs)
         else:
             rgba = np.dstack([rgb, np.full((h, w), 255, np.uint8)])
         t4 = time.perf_counter()

@@ -40,6 +40,34 @@ def _nodata_block(value, valid: np.ndarray, fill_radius: int) -> dict:
     return {"value": value, "invalid_pixels": int(valid.size - np.count_nonzero(valid)), "fill_radius": int(fill_radius)}
 
 
+def read_masked(input_path: Path, nodata, bit_depth: int = 8):
+    """A nodata job's input and its mask, one definition for the job and for whoever needs the job's mask again (the tiler of a
+    transparent_tiles job, app.sr_routes) -> (image, GeoRef, valid uint8 [H, W], the nodata value).  bit_depth 8: the 8-bit image
+    of rio.read_rgb_u8_nodata (mask from the raster AS STORED); 16: the raw uint16 raster, the value an integer in 0..65535."""
+    from s2sr import rasterio_lite as rio
+    from s2sr.nodata import mask_from_value
+    input_path = Path(input_path)
+    if bit_depth != 16:
+        return rio.read_rgb_u8_nodata(input_path, nodata)
+    try:
+        img, georef = rio.read_rgb_raw(input_path)
+    except ValueError as e:
+        raise ValueError(f"bit_depth=16 needs a uint16 GeoTIFF: {e}") from e
+    if img.dtype != np.uint16:
+        raise ValueError(f"bit_depth=16 needs a uint16 GeoTIFF, {input_path} holds {img.dtype}")
+    if nodata is None:               # (the 16-bit job without the option reads its file here too: no mask, no value)
+        return img, georef, None, None
+    value = rio.resolve_nodata(nodata, georef, input_path)
+    if not 0 <= value <= 65535 or value != int(value):
+        raise ValueError(f"nodata {value!r}: a uint16 raster takes an integer in 0..65535")
+    return img, georef, mask_from_value(img, value), value
+
+
+def input_mask(input_path: Path, nodata, bit_depth: int = 8) -> np.ndarray:
+    """The mask a nodata job derives from its input file (uint8 [H, W] at the INPUT resolution, 1 = valid)."""
+    return read_masked(input_path, nodata, bit_depth)[2]
+
+
 def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend: bool = False, display=None,
                     enhance_crops: bool = False, nodata=None, fill_radius: int = 32, consistency=None, extra_bands=None,
                     extra_weights=None) -> Tuple[Path, dict]:
@@ -63,12 +91,7 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
 
     input_path = Path(input_path)
     print(f"\nWOW Super-Resolution ({model}, 16-bit)\n   Input: {input_path}")
-    try:
-        img, georef = rio.read_rgb_raw(input_path)
-    except ValueError as e:
-        raise ValueError(f"bit_depth=16 needs a uint16 GeoTIFF: {e}") from e
-    if img.dtype != np.uint16:
-        raise ValueError(f"bit_depth=16 needs a uint16 GeoTIFF, {input_path} holds {img.dtype}")
+    img, georef, valid, value = read_masked(input_path, nodata, 16)
     extra = numbers = None
     if extra_bands is not None:
         from s2sr import bands as xb
@@ -80,13 +103,7 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
         extra = np.ascontiguousarray(every[:, :, [b - 1 for b in numbers]])
         del every
         w_rgb = xb.check_args(4, 0, 65535, xb.WEIGHTS if extra_weights is None else extra_weights)["weights"]
-    from s2sr.nodata import mask_from_value, valid_range
-    valid = value = None
-    if nodata is not None:
-        value = rio.resolve_nodata(nodata, georef, input_path)
-        if not 0 <= value <= 65535 or value != int(value):
-            raise ValueError(f"nodata {value!r}: a uint16 raster takes an integer in 0..65535")
-        valid = mask_from_value(img, value)
+    from s2sr.nodata import valid_range
     lo, hi = valid_range(img, valid)
     mask_kw = {} if valid is None else {"valid": valid, "nodata": value, "fill_radius": fill_radius}
     esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}),
@@ -222,7 +239,7 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
     if nodata is None:
         img, georef = rio.read_rgb_u8(input_path)           # u8 RGB (min-max normalised if >255, :67-73)
     else:
-        img, georef, valid, value = rio.read_rgb_u8_nodata(input_path, nodata)
+        img, georef, valid, value = read_masked(input_path, nodata)
     # the 8-bit image's invalid pixels get the value where it is one of its own, 0 otherwise (the mask is the truth: alpha, metadata)
     out_nodata = value if valid is not None and 0 <= value <= 255 and value == int(value) else 0
     original_shape = img.shape[:2]

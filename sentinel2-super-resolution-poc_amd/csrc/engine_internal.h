@@ -25,7 +25,7 @@ enum Slot : int {
     SL_CHUNK,     // a chunk's tile outputs, the unbanded post-process's image, the PNG streams of even groups
     SL_PP,        // the post-process work area, where a banded run lives while it is open; the PNG streams of odd groups (the level the
                   //   writer reads is in 0 / 1, so while it runs 2 .. 5 are free)
-    SL_VALID,     // the device copy of a masked call's `valid` (nodata.hip)
+    SL_VALID,     // the device copy of a masked call's `valid` (nodata.hip; the masked warp of tiles.hip)
     SL_CONS,      // a consistency pass's inexact counters (uint64[3], the first 256 bytes) and, in mode 2, its residual plane (consistency.hip);
                   //   a carried band's inexact counter (uint64, the first 256 bytes) and its coefficient planes A, C (bands.hip)
 };

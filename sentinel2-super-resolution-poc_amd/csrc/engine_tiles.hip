@@ -46,6 +46,38 @@ int s2sr_warp_bilinear_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t
     return S2SR_OK;
 }
 
+// The warp with a validity mask: the same call, the mask [ceil(H / vs)][ceil(W / vs)] uploaded whole into SL_VALID.
+int s2sr_warp_bilinear_masked_u8(s2sr_handle* h, const uint8_t* rgb, int32_t H, int32_t W, const uint8_t* valid, int32_t valid_scale,
+                                 const float* grid, int32_t gh, int32_t gw, int32_t step, int32_t OH, int32_t OW, uint8_t* out_rgba) {
+    if (!h || !rgb || !grid || !out_rgba || H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || gh <= 0 || gw <= 0) return S2SR_E_INVALID;
+    if (!valid) return fail(h, S2SR_E_INVALID, "masked warp: valid is NULL (s2sr_warp_bilinear_u8 is the call without a mask)");
+    if (valid_scale < 1) return fail(h, S2SR_E_INVALID, "masked warp: valid_scale must be at least 1");
+    if (step <= 0 || (step & (step - 1))) return fail(h, S2SR_E_INVALID, "warp node spacing must be a power of two");
+    if ((int64_t)(gh - 1) * step < OH - 1 || (int64_t)(gw - 1) * step < OW - 1)
+        return fail(h, S2SR_E_INVALID, "warp node grid does not cover the output raster");
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    DOOR_ENTER(h, h->stream);
+    hipStream_t st = h->stream;
+    const int vs = valid_scale;
+    const size_t ib = (size_t)H * W * 3, gb = (size_t)gh * gw * 8, ob = (size_t)OH * OW * 4;
+    const size_t vb = (size_t)((H + vs - 1) / vs) * (size_t)((W + vs - 1) / vs);
+    int rc;
+    if ((rc = ensure_scratch(h, {{SL_SRC, ib}, {SL_DST, ob}, {SL_TABLES, gb}, {SL_VALID, vb}}))) return rc;
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_SRC), rgb, ib, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_TABLES), grid, gb, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemcpyAsync(scratch(h, SL_VALID), valid, vb, hipMemcpyHostToDevice, st));
+    {
+        Scope sc(h, st, F_MISC, 0.0, (double)ob + (double)OH * OW * 12.0);
+        HIPCHK(h, launch_warp_bilinear_masked(scratch<const uint8_t>(h, SL_SRC), H, W, scratch<const uint8_t>(h, SL_VALID), vs,
+                                              scratch<const float>(h, SL_TABLES), gh, gw, step, OH, OW, scratch<uint8_t>(h, SL_DST), st));
+    }
+    HIPCHK(h, hipMemcpyAsync(out_rgba, scratch(h, SL_DST), ob, hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));
+    h->scratch.keep(KEPT_RASTER, SL_DST, OH, OW);          // as the plain call: the raster stays for the base level of its pyramid
+    return S2SR_OK;
+}
+
 int s2sr_tiles_base_u8(s2sr_handle* h, const uint8_t* rgba, int32_t H, int32_t W, const int32_t* col_lo, const int32_t* col_hi,
                        const int32_t* row_lo, const int32_t* row_hi, int32_t nx, int32_t ny, uint8_t* out) {
     if (!h || !col_lo || !col_hi || !row_lo || !row_hi || H <= 0 || W <= 0 || nx <= 0 || ny <= 0) return S2SR_E_INVALID;

@@ -368,6 +368,9 @@ hipError_t launch_band_apply(const uint16_t* d_q, const uint16_t* d_band, const 
 // XYZ tile pyramid (tiles.hip)
 hipError_t launch_warp_bilinear(const uint8_t* d_rgb, int H, int W, const float* d_grid, int gh, int gw, int step, int OH, int OW,
                                 uint8_t* d_out, hipStream_t st);
+// ... with the validity mask d_valid [ceil(H / vs)][ceil(W / vs)], nonzero = valid
+hipError_t launch_warp_bilinear_masked(const uint8_t* d_rgb, int H, int W, const uint8_t* d_valid, int vs, const float* d_grid, int gh,
+                                       int gw, int step, int OH, int OW, uint8_t* d_out, hipStream_t st);
 hipError_t launch_tiles_base(const uint8_t* d_rgba, int W, const int32_t* d_col_lo, const int32_t* d_col_hi, const int32_t* d_row_lo,
                              const int32_t* d_row_hi, int nx, int ny, uint8_t* d_out, hipStream_t st);
 hipError_t launch_tiles_overview(const uint8_t* d_child, int cnx, int cny, int ox, int oy, int pnx, int pny, uint8_t* d_out,

@@ -191,6 +191,8 @@ _PROTOS = {
     "s2sr_debug_pack_f8": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "s2sr_warp_bilinear_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_int32, C.c_int32, C.c_void_p]),
+    "s2sr_warp_bilinear_masked_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p] +
+                                     [C.c_int32] * 5 + [C.c_void_p]),
     "s2sr_tiles_base_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tiles_overview_u8": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 6 + [C.c_void_p]),
     "s2sr_tiles_resample_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + ([C.c_void_p] * 3 + [C.c_int32]) * 2 +
@@ -562,6 +564,22 @@ class _PinnedPool:
 
 
 pinned_pool = _PinnedPool()
+
+
+def warp_mask(rgb_shape, valid, valid_scale) -> np.ndarray:
+    """The mask of Engine.warp_bilinear_u8 as the library takes it, or ValueError: uint8 [ceil(H / valid_scale), ceil(W / valid_scale)]
+    for an [H, W, 3] raster, valid_scale an integer >= 1 (host arithmetic: refused before the engine is touched)."""
+    vs = valid_scale
+    if isinstance(vs, bool) or not isinstance(vs, (int, np.integer)) or vs < 1:
+        raise ValueError(f"valid_scale {vs!r}: an integer of at least 1")
+    valid = np.ascontiguousarray(valid)
+    rgb_shape = tuple(rgb_shape)
+    if len(rgb_shape) != 3 or rgb_shape[2] != 3:
+        raise ValueError(f"expected an [H, W, 3] raster, got {rgb_shape}")
+    want = (-(-rgb_shape[0] // int(vs)), -(-rgb_shape[1] // int(vs)))
+    if valid.dtype != np.uint8 or valid.shape != want:
+        raise ValueError(f"valid: expected uint8 {want} for a {rgb_shape} raster at valid_scale {vs}, got {valid.dtype} {valid.shape}")
+    return valid
 
 
 class Engine:
@@ -995,10 +1013,21 @@ class Engine:
                 for s in arr}
 
     # -- XYZ tile pyramid -----------------------------------------------------------------
-    def warp_bilinear_u8(self, rgb: np.ndarray, grid: np.ndarray, step: int, out_h: int, out_w: int) -> np.ndarray:
+    def warp_bilinear_u8(self, rgb: np.ndarray, grid: np.ndarray, step: int, out_h: int, out_w: int, valid: Optional[np.ndarray] = None,
+                         valid_scale: int = 1) -> np.ndarray:
+        """valid (uint8 [ceil(H / valid_scale), ceil(W / valid_scale)], nonzero = valid; None: the plain warp): source pixel (y, x)
+        counts iff valid[y // valid_scale, x // valid_scale]; output pixels that lean on invalid ones by half their weight or more
+        come out (0, 0, 0, 0) (s2sr_warp_bilinear_masked_u8)."""
         rgb = np.ascontiguousarray(rgb, np.uint8)
         grid = np.ascontiguousarray(grid, np.float32)
+        if valid is not None:
+            valid = warp_mask(rgb.shape, valid, valid_scale)
         out = pinned_pool.empty((out_h, out_w, 4), np.uint8)        # (page-locked when large: the raster comes back with one DMA)
+        if valid is not None:
+            self._check(self._lib.s2sr_warp_bilinear_masked_u8(self._h, _ptr(rgb), rgb.shape[0], rgb.shape[1], _ptr(valid), int(valid_scale),
+                                                               _ptr(grid), grid.shape[0], grid.shape[1], step, out_h, out_w, _ptr(out)),
+                        "s2sr_warp_bilinear_masked_u8")
+            return out
         self._check(self._lib.s2sr_warp_bilinear_u8(self._h, _ptr(rgb), rgb.shape[0], rgb.shape[1], _ptr(grid), grid.shape[0],
                                                     grid.shape[1], step, out_h, out_w, _ptr(out)), "s2sr_warp_bilinear_u8")
         return out

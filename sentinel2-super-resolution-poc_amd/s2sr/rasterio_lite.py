@@ -318,13 +318,15 @@ _WRITTEN: Dict[str, tuple] = {}
 _WRITTEN_LOCK = threading.Lock()
 
 
-def _remember_written(path, rgb: np.ndarray, georef: "GeoRef") -> None:
+def _remember_written(path, rgb: np.ndarray, georef: "GeoRef", nodata=None) -> None:
     try:
         key = str(Path(path).resolve())
         st = os.stat(key)
         view = rgb.view()
         view.flags.writeable = False
         tags = {t: (tuple(v) if isinstance(v, (tuple, list)) else (v,)) for t, v in georef.tags.items()}
+        if nodata is not None:       # the file's GDAL_NODATA tag, as read_tiff would hand it back
+            tags[TAG_GDAL_NODATA] = (_nodata_text(nodata),)
         with _WRITTEN_LOCK:
             _WRITTEN.pop(key, None)
             while len(_WRITTEN) >= 2:
@@ -462,7 +464,7 @@ def write_geotiff_rgb(path: Path, rgb: np.ndarray, georef: GeoRef, rows_per_stri
             except OSError:
                 pass
     if remember:
-        _remember_written(path, rgb, georef)
+        _remember_written(path, rgb, georef, nodata)
 
 
 def write_geotiff_rgb16(path: Path, rgb16: np.ndarray, georef: GeoRef, rows_per_strip: int = 64, nodata=None) -> None:
