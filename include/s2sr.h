@@ -651,7 +651,8 @@ int  s2sr_debug_plan_bands(const int32_t* chunk_r0, int32_t nchunks, int32_t ny,
  * (fp16 hi, e4m3 lo) pair (kind 2) or fp16 (kind 5).  form: kind 0: 0 auto, 1 = 16x32 patches, 2 = 32x32 patches,
  * 5 = 8x32 patches (single tiles), 6 / 7 / 8 = the whole-patch forms of 2 / 1 / 5, 10 = 8x32 patches with two planes per pipeline
  * stage; kinds 1-2: 0 auto, 1 = 16x32 patches, 5 = 8x32 patches, 10 = 8x32 patches with two planes per stage; kind 3: 0.  The removed
- * forms (kind 0: 3, 4, 9, 11; kinds 1-2: 2; kind 3: anything but 0) are refused (S2SR_E_HIP, not supported).
+ * forms (kind 0: 3, 4, 9, 11; kinds 1-2: 2; kind 3: anything but 0) are refused (S2SR_E_HIP, not supported).  Kinds 1-2 refuse
+ * every number conv5 has no form for in the same way: they answer to 0, 1, 5 and 10 only.
  * form + 0x100 (every kind): the launch walks its patches back to front (same bytes). */
 typedef struct s2sr_debug_trunk_args {
     int32_t kind, form;

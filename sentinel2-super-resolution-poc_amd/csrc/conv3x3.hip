@@ -35,6 +35,8 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <array>
+#include <utility>
 #include <vector>
 
 #include "s2sr_internal.h"
@@ -923,57 +925,27 @@ static hipError_t launch_t(const ConvParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-// the generic form: 8 waves x 2 rows (16x32 patches)
-template <int CT, int EPI, bool UP>
-static hipError_t launch_w(const ConvParams& p, hipStream_t st) {
-    return launch_t<CT, EPI, UP, 8, 2, (CT == 1) ? 5 : 4>(p, st);
+// One launcher per row of kTailForms (conv_forms.h): entry I instantiates the kernel the row describes.
+template <size_t I>
+static hipError_t launch_tail_row(const ConvParams& p, hipStream_t st) {
+    constexpr TailForm f = kTailForms[I];
+    return launch_t<f.ct, f.epi, f.up, f.waves, f.np, f.ring, f.hpo, f.occ, f.f8, f.ph, f.full>(p, st);
+}
+using TailLauncher = hipError_t (*)(const ConvParams&, hipStream_t);
+template <size_t... I>
+static constexpr std::array<TailLauncher, sizeof...(I)> tail_launchers(std::index_sequence<I...>) { return {{&launch_tail_row<I>...}}; }
+static constexpr auto kTailLaunchers = tail_launchers(std::make_index_sequence<kTailFormCount>{});
+
+hipError_t launch_conv(const ConvParams& p, ConvForm form, hipStream_t st, const FormSwitches& sw) {
+    const int row = pick_tail_form(TailQuery{form, p.H, p.W, p.mos_py, p.slope != nullptr, p.src_lo != nullptr, sw});
+    return row < 0 ? hipErrorInvalidValue : kTailLaunchers[row](p, st);
 }
 
-hipError_t launch_conv(const ConvParams& p, ConvForm form, hipStream_t st) {
-    // the split-operand forms take whole 16x32 patches when the launch has nothing else (tail_form bit 3: diagnostic off switch)
-    const bool full = p.mos_py == 0 && p.H % 16 == 0 && p.W % 32 == 0 && !(p.tail_form & 8);
-    switch (form) {
-    case CF_FIRST: return launch_w<2, EPI_FIRST, false>(p, st);
-    case CF_BODY: return launch_w<2, EPI_BODY, false>(p, st);
-    case CF_HR: return launch_w<2, EPI_LRELU, false>(p, st);
-    case CF_LAST: return launch_w<1, EPI_LAST, false>(p, st);
-    case CF_BODY_SPLIT:
-        return full ? launch_t<2, EPI_BODY, false, 8, 2, 4, 1, 1, true, -1, true>(p, st) : launch_t<2, EPI_BODY, false, 8, 2, 4, 1, 1, true>(p, st);
-    case CF_HR_SPLIT: return launch_t<2, EPI_LRELU, false, 8, 2, 4, 1, 1, true>(p, st);
-    case CF_HR_SPLIT_NOHI:
-        if (!(p.tail_form & 2)) return hipErrorInvalidValue;
-        return full ? launch_t<2, EPI_LRELU, false, 8, 2, 4, 2, 1, true, -1, true>(p, st) : launch_t<2, EPI_LRELU, false, 8, 2, 4, 2, 1, true>(p, st);
-    case CF_LAST_SPLIT8: return launch_t<1, EPI_LAST, false, 8, 2, 4, 0, 1, true>(p, st);
-    case CF_LAST_FOLD:
-        return full ? launch_t<1, EPI_LAST, false, 8, 2, 4, 3, 1, true, -1, true>(p, st) : launch_t<1, EPI_LAST, false, 8, 2, 4, 3, 1, true>(p, st);
-    // SRVGGNetCompact: the same 8-wave, 16x32-patch form with the PReLU / pixel-shuffle epilogues
-    case CF_PRELU: return p.slope ? launch_w<2, EPI_PRELU, false>(p, st) : hipErrorInvalidValue;
-    case CF_CFIRST: return p.slope ? launch_w<2, EPI_CFIRST, false>(p, st) : hipErrorInvalidValue;
-    case CF_CLAST: return p.src_lo ? launch_w<2, EPI_CLAST, false>(p, st) : hipErrorInvalidValue;
-    case CF_DEBUG1: return launch_w<1, EPI_DEBUG, false>(p, st);
-    case CF_DEBUG1_UP: return launch_w<1, EPI_DEBUG, true>(p, st);
-    case CF_DEBUG2: return launch_w<2, EPI_DEBUG, false>(p, st);
-    case CF_DEBUG2_UP: return launch_w<2, EPI_DEBUG, true>(p, st);
-    case CF_NONE: break;   // the RDB convs run on conv_trunk.hip, the up-convs in sub-pixel form (launch_conv_phase)
-    }
-    return hipErrorInvalidValue;
-}
-
-// one ROW parity of a split-operand up-conv in sub-pixel form (both column parities inside the launch;
+// one ROW parity of an up-conv in sub-pixel form (both column parities inside the launch;
 // p.H, p.W = source dims, p.Hp, p.Wp = 2x tensor)
-hipError_t launch_conv_phase(const ConvParams& p, int py, hipStream_t st, bool f8) {
-    if (f8 && p.mos_py == 0 && p.H % 8 == 0 && p.W % 32 == 0 && !(p.tail_form & 8)) {   // whole 8x32 source patches
-        if (py == 0) return launch_t<4, EPI_LRELU, false, 8, 1, 4, 1, 1, true, 0, true>(p, st);
-        if (py == 1) return launch_t<4, EPI_LRELU, false, 8, 1, 4, 1, 1, true, 1, true>(p, st);
-    }
-    if (f8) {
-        if (py == 0) return launch_t<4, EPI_LRELU, false, 8, 1, 4, 1, 1, true, 0>(p, st);
-        if (py == 1) return launch_t<4, EPI_LRELU, false, 8, 1, 4, 1, 1, true, 1>(p, st);
-    } else {   // plain fp16 mode: the same four fp16 stages, no correction planes in or out
-        if (py == 0) return launch_t<4, EPI_LRELU, false, 8, 2, 4, 0, 1, false, 0>(p, st);
-        if (py == 1) return launch_t<4, EPI_LRELU, false, 8, 2, 4, 0, 1, false, 1>(p, st);
-    }
-    return hipErrorInvalidValue;
+hipError_t launch_conv_phase(const ConvParams& p, int py, hipStream_t st, bool f8, const FormSwitches& sw) {
+    const int row = pick_phase_form(py, f8, p.H, p.W, p.mos_py, sw);
+    return row < 0 ? hipErrorInvalidValue : kTailLaunchers[row](p, st);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -40,7 +40,9 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <array>
 #include <type_traits>
+#include <utility>
 
 #include "s2sr_internal.h"
 
@@ -693,7 +695,7 @@ __global__ void __launch_bounds__(256, 1) conv_trunk_f16(const ConvParams p) {
 }
 
 template <int CT, int NP, int R, int EPI, int FULL = 0, int PL = 1>
-hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_form* form = nullptr) {
+hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st) {
     using G = TG<CT, NP, R, PL>;
     constexpr bool kNoLdsBias = EPI == EPI_LRELU;                  // bias as the C operand: no LDS copy
     constexpr int LDSB = kNoLdsBias ? G::RING_BYTES : G::LDS_BYTES;
@@ -719,7 +721,6 @@ hipError_t launch_trunk_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_
     q.tilesY = (p.H + G::TH - 1) / G::TH;
     const int ntiles = q.tilesX * q.tilesY * p.N;
     const int grid = persistent_grid(ncu, 1, ntiles, GF_TRUNK_F16);
-    if (form) *form = s2sr_debug_trunk_form{1, CT, G::TH, R, FULL, PL, 0, 0, 1, 4, 0, EPI};   // lo_enc: 1, the one encoding (see the epilogue)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDSB, st, q);
     return hipGetLastError();
 }
@@ -760,7 +761,7 @@ template <int CT_, int NP_, int RS_, int NPL_ = 0>
 struct TG8 {
     static constexpr int CT = CT_, NP = NP_, RS = RS_, WAVES = 4;
     // NPL > 0: ALL of the conv's weight planes (up to NPL, 9*CT KiB each) are loaded into LDS once per workgroup and stay:
-    // no weight DMA in the loop (+1 % on conv1-3, see launch_conv_trunk_f8).
+    // no weight DMA in the loop (+1 % on conv1-3, see pick_trunk_form, conv_forms.h).
     static constexpr int NPL = NPL_;
     static constexpr bool WRES = NPL_ > 0;
     static constexpr int TH = WAVES * NP, TW = 32, SW = TW + 2, SH = TH + 2, SPX = SH * SW;
@@ -1347,7 +1348,7 @@ __global__ void __launch_bounds__((4 + PROD) * 64, 1) conv_trunk_f8(const ConvPa
 }
 
 template <int CT, int NP, int RS, int EPI, int NPL = 0, int PROD = 0>
-hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk_form* form = nullptr) {
+hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st) {
     using G = TG8<CT, NP, RS, NPL>;
     static_assert(G::LDS_BYTES <= 160 * 1024, "LDS rings do not fit");
     static_assert(G::NW >= 0 && G::NW < 64, "vmcnt field is 6 bits");
@@ -1369,67 +1370,37 @@ hipError_t launch_trunk8_t(const ConvParams& p, hipStream_t st, s2sr_debug_trunk
     q.tilesY = (p.H + G::TH - 1) / G::TH;
     const int ntiles = q.tilesX * q.tilesY * p.N;
     const int grid = persistent_grid(ncu, 1, ntiles, GF_TRUNK_F8);
-    if (form) *form = s2sr_debug_trunk_form{2, CT, G::TH, RS, 0, 2, PROD, 0, 0, G::WAVES, NPL, EPI};
     hipLaunchKernelGGL(kern, dim3(grid), dim3((G::WAVES + PROD) * 64), G::LDS_BYTES, st, q);
     return hipGetLastError();
 }
 
+// One launcher per row of kTrunkForms (conv_forms.h): entry I instantiates the kernel the row describes.
+template <size_t I>
+hipError_t launch_trunk_row(const ConvParams& p, hipStream_t st) {
+    constexpr TrunkForm f = kTrunkForms[I];
+    if constexpr (f.kernel == 1) return launch_trunk_t<f.ct, f.rows / 4, f.ring, f.epi, f.full, f.pl>(p, st);
+    else return launch_trunk8_t<f.ct, f.rows / 4, f.ring, f.epi, f.npl, f.prod>(p, st);
+}
+using TrunkLauncher = hipError_t (*)(const ConvParams&, hipStream_t);
+template <size_t... I>
+constexpr std::array<TrunkLauncher, sizeof...(I)> trunk_launchers(std::index_sequence<I...>) { return {{&launch_trunk_row<I>...}}; }
+constexpr auto kTrunkLaunchers = trunk_launchers(std::make_index_sequence<TF_COUNT>{});
+
+// build the query, pick, call the row's entry; the form record is the row's
+hipError_t launch_picked(const ConvParams& p, int ct, int epi, bool fp8, const FormSwitches& sw, int hook, hipStream_t st,
+                         s2sr_debug_trunk_form* form) {
+    const int row = pick_trunk_form(TrunkQuery{p.N, p.H, p.W, p.mos_py, p.mos_ry, p.mos_px, p.mos_rx, ct, epi, fp8, p.nstage, sw, hook});
+    if (row < 0) return row == kFormNotSupported ? hipErrorNotSupported : hipErrorInvalidValue;
+    const hipError_t e = kTrunkLaunchers[row](p, st);
+    if (e == hipSuccess && form) *form = trunk_form_record(kTrunkForms[row]);
+    return e;
+}
+
 }  // namespace
 
-// ct = 1: conv1..4 (EPI_LRELU); ct = 2: conv5 (EPI_RDB5 / EPI_RDB5_RRDB).  Returns hipErrorNotSupported for
-// anything else.
-hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, int force_form, s2sr_debug_trunk_form* form) {
-    if (force_form == 4) return hipErrorNotSupported;        // the loader wave: the forms the measurements buried are refused
-    if (ct == 1 && epi == EPI_LRELU) {
-        if (force_form == 1) return launch_trunk_t<1, 4, 5, EPI_LRELU>(p, st, form);      // per-layer parity hook: name the patch form
-        if (force_form == 2) return launch_trunk_t<1, 8, 3, EPI_LRELU>(p, st, form);
-        if (force_form == 5) return launch_trunk_t<1, 2, 7, EPI_LRELU>(p, st, form);
-        if (force_form == 6) return launch_trunk_t<1, 8, 3, EPI_LRELU, 1>(p, st, form);    // whole-patch forms (invalid-value on ragged sizes / mosaics)
-        if (force_form == 7) return launch_trunk_t<1, 4, 5, EPI_LRELU, 1>(p, st, form);
-        if (force_form == 8) return launch_trunk_t<1, 2, 7, EPI_LRELU, 1>(p, st, form);
-        if (force_form == 10) return launch_trunk_t<1, 2, 3, EPI_LRELU, 3, 2>(p, st, form);   // 8x32 patches, two planes per stage
-        if (force_form == 3 || force_form == 9 || force_form == 11) return hipErrorNotSupported;   // Winograd, weights from global, 64x32
-        // 32x32 patches (8 rows per wave, 3-deep ring) unless that leaves most CUs without a patch (single tiles):
-        // then 16x32 patches (4 rows per wave, 5-deep ring) spread the image over twice as many workgroups.  Both
-        // forms accumulate in the same order, so the result does not depend on the choice.
-        const long n32 = (long)((p.W + 31) / 32) * ((p.H + 31) / 32) * p.N;
-        // ... and 8x32 patches (2 rows per wave, 7-deep ring) for a single tile: 256 patches for 256 CUs instead of 128 (one 256x256 tile
-        // is launch-bound: 351 dependent launches; S2SR_SMALL8=0 keeps the 16x32 form)
-        const bool full = p.mos_py == 0 && p.H % 32 == 0 && p.W % 32 == 0 && !(p.f16_form & 4);   // whole patches only (f16_form bit 2: diagnostic off switch)
-        const bool plain = p.mos_py == 0 && !(p.f16_form & 4);                                  // ragged, but no mosaic: the extent test alone
-        if (n32 < 96 && !(p.f16_form & 2)) {
-            // two planes per stage (double-buffered) where the epilogue needs no mosaic test: half the barriers per patch
-            // (profiles/r04_latency_anatomy.txt); the 7-deep one-plane ring otherwise
-            if (full) return launch_trunk_t<1, 2, 3, EPI_LRELU, 1, 2>(p, st, form);
-            if (plain) return launch_trunk_t<1, 2, 3, EPI_LRELU, 3, 2>(p, st, form);
-            return launch_trunk_t<1, 2, 7, EPI_LRELU>(p, st, form);
-        }
-        if (n32 < 192)
-            return full ? launch_trunk_t<1, 4, 5, EPI_LRELU, 1>(p, st, form)
-                        : plain ? launch_trunk_t<1, 4, 5, EPI_LRELU, 3>(p, st, form) : launch_trunk_t<1, 4, 5, EPI_LRELU>(p, st, form);
-        if (full) return launch_trunk_t<1, 8, 3, EPI_LRELU, 1>(p, st, form);
-        if (plain) return launch_trunk_t<1, 8, 3, EPI_LRELU, 3>(p, st, form);
-        if (!(p.f16_form & 4) && p.mos_py == 277 && p.mos_ry == 276 && p.mos_px == 277 && p.mos_rx == 276)
-            return launch_trunk_t<1, 8, 3, EPI_LRELU, 2>(p, st, form);                             // mosaics of 276-pixel windows (tile 256, pad 10)
-        return launch_trunk_t<1, 8, 3, EPI_LRELU>(p, st, form);
-    }
-    // conv5: 16x32 patches (4 rows per wave, 4-deep ring); single tiles take 8x32 patches (2 rows per wave, 5-deep ring): one
-    // 256x256 tile is 128 patches of 16x32 -- half the CUs idle through twelve MFMA-bound stages (r04 kernel trace: 24 us per
-    // conv5 launch, 69 of them = 37 % of one tile's latency) -- and 256 of 8x32.  Same accumulation order, same bytes.
-    // force_form 1 / 5: name the patch form (per-layer parity hook).
-    if (ct == 2 && (epi == EPI_RDB5 || epi == EPI_RDB5_RRDB)) {
-        if (force_form == 2) return hipErrorNotSupported;
-        const long n16 = (long)((p.W + 31) / 32) * ((p.H + 15) / 16) * p.N;
-        const bool small = force_form == 5 || (force_form == 0 && n16 < 192 && !(p.f16_form & 2));
-        if (force_form == 10 || (small && force_form == 0))      // 8x32 patches, two planes per stage, double-buffered
-            return epi == EPI_RDB5 ? launch_trunk_t<2, 2, 2, EPI_RDB5, 0, 2>(p, st, form)
-                                   : launch_trunk_t<2, 2, 2, EPI_RDB5_RRDB, 0, 2>(p, st, form);
-        // (No whole-patch form here: <2, 4, 4, EPI, FULL = 1> was measured at 221.8 -> 220.2 us and 247.9 -> 246.1 us per headline launch, 0.3 %
-        // of a step and inside the step's repeat spread -- DESIGN.md section 9, profiles/serpentine_bench.txt.)
-        if (epi == EPI_RDB5) return small ? launch_trunk_t<2, 2, 5, EPI_RDB5>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5>(p, st, form);
-        return small ? launch_trunk_t<2, 2, 5, EPI_RDB5_RRDB>(p, st, form) : launch_trunk_t<2, 4, 4, EPI_RDB5_RRDB>(p, st, form);
-    }
-    return hipErrorNotSupported;
+hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, const FormSwitches& sw, int force_form,
+                             s2sr_debug_trunk_form* form) {
+    return launch_picked(p, ct, epi, false, sw, force_form, st, form);
 }
 
 }  // namespace s2sr
@@ -1476,15 +1447,7 @@ void pack_conv_weights_f8(const float* w, int cin, int cout, void* dst_host, int
                         }
 }
 
-hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_t st, s2sr_debug_trunk_form* form) {
-    if (ct == 1 && epi == EPI_LRELU) {
-        // The loader-wave form (conv_trunk_f8 PROD): conv1-3 keep their weights resident in LDS (<= 4 planes incl. a phantom, next
-        // to the 6-slot slab ring), conv4 streams them (6 planes would cost two slab slots).  The other forms the measurements buried
-        // (DESIGN section 9): four waves without the loader (-3 %), all weights streamed or all resident (+-1 %), two waves per SIMD.
-        return p.nstage <= 4 ? launch_trunk8_t<1, 4, 6, EPI_LRELU, 4, 1>(p, st, form) : launch_trunk8_t<1, 4, 6, EPI_LRELU, 0, 1>(p, st, form);
-    }
-    if (ct == 2 && epi == EPI_RDB5) return launch_trunk8_t<2, 4, 4, EPI_RDB5>(p, st, form);
-    if (ct == 2 && epi == EPI_RDB5_RRDB) return launch_trunk8_t<2, 4, 4, EPI_RDB5_RRDB>(p, st, form);
-    return hipErrorNotSupported;
+hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_t st, int force_form, s2sr_debug_trunk_form* form) {
+    return launch_picked(p, ct, epi, true, FormSwitches{}, force_form, st, form);
 }
 }  // namespace s2sr

@@ -210,16 +210,14 @@ int epi_of(Role r) { return r == L_RDB5 ? EPI_RDB5 : r == L_RDB5_RRDB ? EPI_RDB5
 int run_conv(s2sr_handle* h, hipStream_t st, const ConvW& cw, ConvParams p, s2sr_debug_trunk_form* form = nullptr) {   // form: where the RDB convs record their kernel form
     p.wpack = cw.d_wpack; p.bias = cw.d_bias; p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.seg_lo_mask = cw.seg_lo_mask;
     p.fold_lo = cw.form == CF_LAST_FOLD ? 1 : 0;
-    p.tail_form = (h->f16_full ? 0 : 8) | (cw.form == CF_HR_SPLIT_NOHI ? 2 : 0);
     p.trash = h->d_trash;
     Scope sc = layer_scope(h, st, cw, p);
     if (form) *form = s2sr_debug_trunk_form{};
     if (cw.form == CF_NONE) {   // the RRDB trunk: conv_trunk.hip
-        p.f16_form = (h->small8 ? 0 : 2) | (h->f16_full ? 0 : 4);
-        HIPCHK(h, launch_conv_trunk(p, cw.ct, epi_of(cw.role), st, 0, form));
+        HIPCHK(h, launch_conv_trunk(p, cw.ct, epi_of(cw.role), st, h->form_switches(), 0, form));
         return S2SR_OK;
     }
-    HIPCHK(h, launch_conv(p, cw.form, st));
+    HIPCHK(h, launch_conv(p, cw.form, st, h->form_switches()));
     return S2SR_OK;
 }
 
@@ -232,12 +230,11 @@ int run_up_subpixel(s2sr_handle* h, hipStream_t st, const ConvW& cw, ConvParams 
                     int oHp, int oWp, const int (&walk)[2]) {
     p.N = n; p.H = Hs; p.W = Ws; p.sHp = sHp; p.sWp = sWp; p.Hp = oHp; p.Wp = oWp;
     p.bias = cw.d_bias; p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.seg_lo_mask = cw.seg_lo_mask; p.fold_lo = 0;
-    p.tail_form = h->f16_full ? 0 : 8;
     p.trash = h->d_trash;
     for (int k = 0; k < 2; ++k) {
         p.wpack = cw.d_wphase[k]; p.dbg = walk[k];
         Scope sc = layer_scope(h, st, cw, p);
-        HIPCHK(h, launch_conv_phase(p, k, st, cw.split));
+        HIPCHK(h, launch_conv_phase(p, k, st, cw.split, h->form_switches()));
     }
     return S2SR_OK;
 }
@@ -305,7 +302,7 @@ int run_net_compact(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* 
         p.dbg = dir;
         p.wpack = cw.d_wpack; p.bias = cw.d_bias; p.slope = cw.d_slope; p.nstage = cw.nstage; p.seg_len = cw.seg_len; p.seg_lo_mask = 0;
         Scope sc = layer_scope(h, st, cw, p);
-        HIPCHK(h, launch_conv(p, cw.form, st));
+        HIPCHK(h, launch_conv(p, cw.form, st, h->form_switches()));
         return S2SR_OK;
     };
     int rc, cur = 0;
@@ -399,7 +396,7 @@ int run_net(s2sr_handle* h, hipStream_t st, int n, int H, int W, float* d_out_f3
                         if (cw.role == L_RDB5_RRDB) p.xh_skip = w.Xh[0];
                     }
                     Scope sc = layer_scope(h, st, cw, p);
-                    HIPCHK(h, launch_conv_trunk_f8(p, cw.ct, epi_of(cw.role), st, fo ? fo + (k - 1) : nullptr));
+                    HIPCHK(h, launch_conv_trunk_f8(p, cw.ct, epi_of(cw.role), st, 0, fo ? fo + (k - 1) : nullptr));
                 }
                 if (h->d_calib) {   // s2sr_calibrate_fp8: ranges of this RDB's growth planes and of the trunk it produced
                     HIPCHK(h, launch_absmax_e4m3(w.D8[cur] + 2 * w.blk1, (size_t)4 * w.blk1, ge, h->d_calib + 1, st));

@@ -172,7 +172,7 @@ int s2sr_debug_conv(s2sr_handle* h, const float* x, int32_t N, int32_t Cin, int3
     p.out_f32 = d_y; p.cout = Cout; p.act = act & 0xff; p.trash = h->d_trash;
     p.dbg = (act >> 8) & 1;                                   // bit 8 of `act`: the patches back to front
     const ConvForm form = Cout <= 32 ? (upsample ? CF_DEBUG1_UP : CF_DEBUG1) : (upsample ? CF_DEBUG2_UP : CF_DEBUG2);
-    HIPCHK(h, launch_conv(p, form, st));
+    HIPCHK(h, launch_conv(p, form, st, FormSwitches{}));
     HIPCHK(h, hipMemcpyAsync(y, d_y, yb, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     dev_free(d_plane); dev_free(d_x); dev_free(d_y); dev_free(d_w); dev_free(d_b);
@@ -370,7 +370,7 @@ int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
                 p.xh_skip = (const char*)d_Sk.p; p.xh_img = 4 * blk; p.lo_skip = (const char*)d_SkLo.p;
             }
         }
-        const hipError_t e = launch_conv_trunk(p, Cout / 32, epi, st, form);
+        const hipError_t e = launch_conv_trunk(p, Cout / 32, epi, st, FormSwitches{}, form);   // the hook names forms; form 0 picks with the default switches
         if (e != hipSuccess) return fail(h, S2SR_E_HIP, std::string("launch_conv_trunk: ") + hipGetErrorString(e));
     } else {
         p.seg_len = Cin / 32; p.nstage = (p.seg_len + 1) & ~1; p.wscale = (const int32_t*)d_ws.p;
@@ -403,8 +403,7 @@ int s2sr_debug_conv_trunk(s2sr_handle* h, const s2sr_debug_trunk_args* a) {
                 p.xh_skip = (const char*)d_Sk.p;
             }
         }
-        // conv1-4: the loader-wave form is the only one (the others the measurements buried are refused)
-        const hipError_t e = (kind == 3 && form != 0) ? hipErrorNotSupported : launch_conv_trunk_f8(p, Cout / 32, epi, st);
+        const hipError_t e = launch_conv_trunk_f8(p, Cout / 32, epi, st, form);   // conv1-4: no row answers to a hook number; conv5: one form
         if (e != hipSuccess) return fail(h, S2SR_E_HIP, std::string("launch_conv_trunk_f8: ") + hipGetErrorString(e));
     }
     HIPCHK(h, hipStreamSynchronize(st));
@@ -496,15 +495,14 @@ int s2sr_debug_bench_conv(s2sr_handle* h, int32_t N, int32_t H, int32_t W, int32
     p.T = (char*)T.p; p.R = (float*)Rr.p; p.F = (float*)Rr.p; p.trash = h->d_trash;
     p.xh_in = (const char*)T.p; p.lo_exp = h->lo_exp;   // conv_trunk_f16: trunk lo coming in (here read and written in place: timing only)
     p.dst = (char*)D1.p; p.dst_img = 12 * blk;
-    p.f16_form = (h->small8 ? 0 : 2) | (h->f16_full ? 0 : 4);
     const int epi = cout == 32 ? EPI_LRELU : EPI_RDB5, ct = cout / 32;
     hipEvent_t e0, e1;
     HIPCHK(h, hipEventCreate(&e0));
     if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); return fail(h, S2SR_E_HIP, "hipEventCreate failed"); }
     hipError_t e = hipSuccess;
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = launch_conv_trunk(p, ct, epi, st);
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = launch_conv_trunk(p, ct, epi, st, h->form_switches());
     if (e == hipSuccess) e = hipEventRecord(e0, st);
-    for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_conv_trunk(p, ct, epi, st);
+    for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_conv_trunk(p, ct, epi, st, h->form_switches());
     if (e == hipSuccess) e = hipEventRecord(e1, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     float ms = 0;

@@ -248,6 +248,7 @@ struct s2sr_handle {
     bool f16_full = true;         // S2SR_F16_FULL=0: fp16 conv1-4 never take the whole-patch form (no px_live arithmetic in the epilogue) on 32-multiple launches
     int serpentine = s2sr::engine::kSerpentineDefault;   // S2SR_SERPENTINE=0: every launch walks its patches front to back; otherwise the flip mask of run_net's launch order
     bool small8 = true;          // S2SR_SMALL8=0: single tiles keep the 16x32-patch form of fp16 conv1-4 (default: 8x32 patches, 256 per 256x256 tile)
+    s2sr::FormSwitches form_switches() const { return s2sr::FormSwitches{small8, f16_full}; }   // what the conv launchers' picks read (conv_forms.h)
     bool mosaic_on = true;        // S2SR_MOSAIC=0: windows that are no multiple of the 32-pixel patch travel one per image (ConvParams::mos_*)
     // paste maps of the window plan last stitched through s2sr_stitch_rows_u8_dev (row map, column map), kept on the device:
     // an AOI is stitched band by band, the maps are uploaded once per (H, W, tile, pad)

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/s2sr.h"
+#include "conv_forms.h"   // Epilogue, ConvForm, the kernel-form tables and picks (host-only)
 
 // The library carries only the kernel forms that run.  The ones the measurements buried (the row-Winograd trunk form, the fp16
 // loader-wave form, the one-wave-per-SIMD tail convs, the 8-wave RDB path, the non-default fp8 conv1-4 forms, the upsample-on-load
@@ -100,20 +101,6 @@ static inline hipError_t host_free(void* p) { DeviceGate g; return hipHostFree(p
 static inline int roundup32(int v) { return (v + 31) & ~31; }
 static inline int padded(int v) { return roundup32(v) + 2; }
 
-enum Epilogue : int {
-    EPI_LRELU = 0,      // y = lrelu(acc)                  -> fp16 blocks        (RDB conv1..4, up1, up2, hr)
-    EPI_RDB5 = 1,       // v = acc*0.2 + (x+lo)            -> fp16 x_next, lo    (RDB conv5, rdb1/rdb2)
-    EPI_RDB5_RRDB = 2,  // v = (acc*0.2+(x+lo))*0.2 + R; R=v-> fp16 x_next, lo    (RDB conv5 of rdb3)
-    EPI_FIRST = 3,      // v = acc*in_scale + bias; F=R=v  -> fp16 x, lo          (conv_first)
-    EPI_BODY = 4,       // v = F + acc                     -> fp16               (conv_body + trunk skip)
-    EPI_LAST = 5,       // out fp32 NCHW and/or u8 NHWC (x255, clip, truncate)   (conv_last)
-    EPI_DEBUG = 6,      // out fp32 NCHW, all Cout, optional lrelu               (s2sr_debug_conv)
-    // SRVGGNetCompact (S2SR_ARCH_COMPACT): per-channel PReLU, pixel-shuffle tail
-    EPI_PRELU = 7,      // y = prelu(acc, slope[c])        -> fp16 blocks        (compact body convs)
-    EPI_CFIRST = 8,     // y = prelu(acc*in_scale + bias)  -> fp16 blocks        (compact first conv; no lo / R / F)
-    EPI_CLAST = 9,      // pixel_shuffle(acc, 4) + x/255 -> fp32 NCHW and/or u8 NHWC at 4x (compact last conv, rows permuted on the host)
-};
-
 struct ConvParams {
     const char* src;         // first input block of image 0 (fp16 blocked tensor)
     uint64_t src_img;        // bytes between images of src
@@ -158,9 +145,8 @@ struct ConvParams {
     const int32_t* wscale;   // [64] E8M0 bytes 127 - k_co of the per-output-channel weight scales 2^k_co
     int32_t x_exp, g_exp;    // activation scales: x planes hold e4m3(x * 2^x_exp), growth planes e4m3(x_k * 2^g_exp)
     int32_t f8_form;         // unused (kept so that every kernel argument stays at its offset)
-    int32_t f16_form;        // conv_trunk_f16 conv1-4 kernel form: bit 1 = single tiles keep the 16x32-patch form instead of 8x32 (S2SR_SMALL8=0),
-                             // bit 2 = never the whole-patch (FULL) forms (S2SR_F16_FULL=0); bits 0, 3, 4 unused
-    int32_t tail_form;       // split-operand head/tail convs (conv3x3.hip F8 schedule): bit 1 = this conv's consumer reads no e4m3(x_hi) planes (conv_hr before a folded conv_last): do not write them, bit 3 = never the whole-patch (FULL) forms (S2SR_F16_FULL=0); bit 0 unused
+    int32_t f16_form;        // reserved, always 0 (the form switches travel as FormSwitches, conv_forms.h; kept like f8_form)
+    int32_t tail_form;       // reserved, always 0
     int32_t lo_exp;          // conv_trunk_f16 conv5: the trunk's lo half is stored as e4m3(lo * 2^lo_exp) planes (xh_in, T, lo_skip)
     // Window mosaics (the AOI path, engine.hip forward_dev): equal-size windows of `_tile_process` (cnn_super_resolution.py:249-257) laid
     // out on a grid inside ONE image with a single zero row / column between neighbours -- the conv zero padding of both, at
@@ -274,29 +260,17 @@ static inline int stride_grid(size_t total, int most, int fam) {
     return capped_grid((int)(blocks > (size_t)most ? (size_t)most : blocks), (long long)blocks, fam);
 }
 
-// conv kernel (conv3x3.hip): one enumerator per family of instantiations.  The loader decides a conv's form once (engine.hip,
-// ConvW::form); the launcher only adds the whole-patch (FULL) variant, which depends on the launch's geometry, and refuses
-// parameters that do not fit the form.
-enum ConvForm : int {
-    CF_NONE = 0,                                    // not a launch_conv conv
-    CF_FIRST, CF_BODY, CF_HR, CF_LAST,              // 8 waves, 16x32 patches, fp16 (conv_first in hp mode too: [w_hi][w_lo] on exact integers)
-    // split-operand (hp) convs, cin 64: fp16 main term + e4m3 correction planes in; body / hr write such planes as well
-    CF_BODY_SPLIT, CF_HR_SPLIT,
-    CF_HR_SPLIT_NOHI,                               // conv_hr in front of a folded conv_last: no e4m3(x_hi) planes out (tail_form bit 1)
-    CF_LAST_SPLIT8, CF_LAST_FOLD,                   // conv_last on all four planes (8 stages) / w_lo folded into idle couts (6 stages)
-    CF_PRELU, CF_CFIRST, CF_CLAST,                  // SRVGGNetCompact: PReLU / pixel-shuffle epilogues
-    CF_DEBUG1, CF_DEBUG1_UP, CF_DEBUG2, CF_DEBUG2_UP,   // s2sr_debug_conv: 1 or 2 cout tiles, plain or nearest-2x on load
-};
-hipError_t launch_conv(const ConvParams& p, ConvForm form, hipStream_t st);
+// conv3x3.hip: the conv of `form` on the row of kTailForms that pick_tail_form (conv_forms.h) answers for the launch
+hipError_t launch_conv(const ConvParams& p, ConvForm form, hipStream_t st, const FormSwitches& sw);
 // the RRDB trunk convs as one-wave-per-SIMD workgroups (conv_trunk.hip): ct 1 + EPI_LRELU (conv1..4), ct 2 + EPI_RDB5 /
-// EPI_RDB5_RRDB (conv5).  hipErrorNotSupported = not a trunk form / launch too small: use launch_conv.
-// force_form (the per-layer parity hook): 0 = by launch size; conv1-4: 1 = 16x32 patches / 5-deep ring, 2 = 32x32 patches / 3-deep ring,
-// 5 = 8x32 patches, 6 / 7 / 8 = the whole-patch (FULL) forms of 2 / 1 / 5, 10 = 8x32 patches with two planes per stage; conv5: 1, 5, 10.
-// The removed forms 3, 4, 9, 11 (and conv5's 2) answer hipErrorNotSupported.
+// EPI_RDB5_RRDB (conv5), on the row of kTrunkForms that pick_trunk_form (conv_forms.h) answers.  hipErrorNotSupported = not a
+// trunk form, or a hook number no row answers to.
+// force_form (the per-layer parity hook, s2sr_debug_conv_trunk's `form`): 0 = by launch size, else the row whose `hook` it is.
 // form (optional): the instantiation the launch took (s2sr_debug_trunk_taps' form record), written when the launch was issued
-hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, int force_form = 0, s2sr_debug_trunk_form* form = nullptr);
+hipError_t launch_conv_trunk(const ConvParams& p, int ct, int epi, hipStream_t st, const FormSwitches& sw, int force_form = 0,
+                             s2sr_debug_trunk_form* form = nullptr);
 // the same convs on e4m3 operands, block-scaled fp8 MFMA (K = 64 = two planes per instruction)
-hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_t st, s2sr_debug_trunk_form* form = nullptr);
+hipError_t launch_conv_trunk_f8(const ConvParams& p, int ct, int epi, hipStream_t st, int force_form = 0, s2sr_debug_trunk_form* form = nullptr);
 // per-plane weight stages for conv_trunk_f8: [plane][tap][ct][16-B half][cout row 0..31][16 channel bytes] e4m3 of
 // w * 2^k_co, planes padded to an even count with a zero plane; wscale_out[co] = 127 - k_co
 size_t conv_wpack_bytes_f8(int cin, int cout);
@@ -327,7 +301,7 @@ void pack_conv_weights_f8hp(const float* w, int cin, int cout, void* dst_host, b
 // sub-pixel form of the split-operand up-convs: four 2x2-tap kernels (one per output parity), same stage layout
 void pack_conv_weights_phase_f8hp(const float* w, int cin, int cout, int phase, void* dst_host);
 size_t conv_wpack_bytes_phase(int cin, int cout);
-hipError_t launch_conv_phase(const ConvParams& p, int row_parity, hipStream_t st, bool f8);
+hipError_t launch_conv_phase(const ConvParams& p, int row_parity, hipStream_t st, bool f8, const FormSwitches& sw);
 uint8_t f32_to_e4m3(float f);   // OCP e4m3fn, round to nearest even, saturating at +-448
 
 // display rendering of 16-bit images (display.hip): the samples [s0, s1) of a uint16 [H, W, 3] image (a band of whole rows; at

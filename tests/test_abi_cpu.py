@@ -201,6 +201,7 @@ def test_hidden_asm_load_before_fp8_loader_branch_is_caught(tmp_path):
     (tmp_path / "include").mkdir()
     shutil.copy(REPO / "include" / "s2sr.h", tmp_path / "include" / "s2sr.h")
     shutil.copy(csrc / "s2sr_internal.h", work / "s2sr_internal.h")
+    shutil.copy(csrc / "conv_forms.h", work / "conv_forms.h")       # s2sr_internal.h includes it
     src = (csrc / "conv_trunk.hip").read_text()
     role = "    // ---- the loader wave (PROD): the whole workgroup's DMA schedule, one barrier per pair-step like everybody else   [role-branch]"
     compute = "    // ---- fragment addresses: per-lane base + immediate.  b0 / b1 = logical 16-B halves 0 / 1 of pixel (row, pcol + dx)"
