@@ -412,6 +412,33 @@ int  s2sr_carry_band_u16(s2sr_handle* h, const uint16_t* sr /* [S H, S W, 3] or 
                          const uint8_t* valid /* [H, W] or NULL */, int32_t fill, int32_t band_rows, uint16_t* out /* [S H, S W] */,
                          uint64_t* inexact /* or NULL */);
 
+/* Normalised-difference indices on one grid: NDVI, NDWI, NDRE, SAVI and their kin from two uint16 planes, with the
+ * rendering, the histogram and per-zone sums out of the same read.  Integers throughout; no weights needed.
+ *   a' = max(a - offset, 0), b' = max(b - offset, 0), n = a' - b', d = a' + b' + L
+ *   v  = sign(n) floor((2 |n| K + d) / (2 d)) for d > 0 (round half away from zero; |v| <= K), -32768 (nodata) for d == 0
+ *   offset 0..65535 (the DN offset of both planes), L 0..65535 (the soil term in DN), K 1..16383 (the output scale).
+ * a, b: uint16 [H, W, ac] / [H, W, bc] with ac, bc 1 or 3; ca, cb the channel read.  a == NULL: channel ca of the uint16 image of
+ *   exactly H x W x 3 that the previous call on this handle left on the device (as s2sr_carry_band_u16 takes sr == NULL); the call
+ *   leaves that image intact and names it kept again at its end.
+ * valid: uint8 [ceil(H / valid_scale)][ceil(W / valid_scale)] or NULL; a pixel whose cell is 0 gets -32768.
+ * undefined: the unmasked pixels with d == 0.
+ * out_i16: int16 [H, W].  hist: uint64 [2 K + 1], hist[v + K] = the pixels of value v, nodata left out.
+ * rgba: uint8 [H, W, 4] = lut[(uint16)(v + 32768)], lut uint8 [65536][4]; a nodata pixel is 0, 0, 0, 0 whatever the LUT holds.
+ * zones: uint16 labels [ceil(H / zone_scale)][ceil(W / zone_scale)], 0 = no zone, 1..Z (Z <= 65535; a label above Z counts as 0);
+ *   zonal: int64 [Z + 1][3] = count, sum v, sum v^2 over the defined pixels of each label, row 0 the pixels without a zone.
+ * Every output may be NULL, not all of them.  band_rows (0: the library's choice) sets the row bands; the result does not depend on it.
+ * S2SR_E_INVALID with a text, before the device is touched: K, L, offset or Z out of range, ac or bc not 1 or 3, a channel outside
+ * its image, valid_scale or zone_scale < 1, zonal without zones or zones without zonal, rgba without lut, every output NULL, a NULL
+ * b, non-positive H or W, H W >= 2^31, band_rows < 0, and a == NULL without a device image of that size.  The handle keeps working. */
+int  s2sr_index_nd_u16(s2sr_handle* h, const uint16_t* a /* [H, W, ac] or NULL */, int32_t ac, int32_t ca, const uint16_t* b /* [H, W, bc] */,
+                       int32_t bc, int32_t cb, int32_t H, int32_t W, int32_t offset, int32_t L, int32_t K, const uint8_t* valid /* or NULL */,
+                       int32_t valid_scale, const uint16_t* zones /* or NULL */, int32_t zone_scale, int32_t Z,
+                       const uint8_t* lut /* [65536][4] or NULL */, int32_t band_rows, int16_t* out_i16 /* or NULL */,
+                       uint64_t* hist /* or NULL */, int64_t* zonal /* or NULL */, uint8_t* rgba /* or NULL */, uint64_t* undefined /* or NULL */);
+/* The same mapping for an index raster that already exists: rgba[y, x] = lut[(uint16)(idx[y, x] + 32768)], -32768 -> 0, 0, 0, 0. */
+int  s2sr_index_render_i16(s2sr_handle* h, const int16_t* idx /* [H, W] */, int32_t H, int32_t W, const uint8_t* lut /* [65536][4] */,
+                           int32_t band_rows, uint8_t* rgba /* [H, W, 4] */);
+
 /* Multi-GPU building blocks of _tile_process (cnn_super_resolution.py:244-278), device-resident:
  * cut windows [first, first+count) of the plan into d_tiles [count, wh, ww, 3] (wh/ww = the
  * plan's common window size), and paste ALL T windows' outputs d_tiles [T, 4wh, 4ww, 3] into

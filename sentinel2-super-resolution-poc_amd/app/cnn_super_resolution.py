@@ -411,7 +411,7 @@ class RealESRGAN:
         return r.q
 
     def enhance16(self, img: np.ndarray, value_range=None, display=None, valid=None, nodata=None, fill_radius: int = 32, extra=None,
-                  extra_range=None, extra_weights=None):
+                  extra_range=None, extra_weights=None, indices=None):
         """HxWx3 uint16 (channel order as given) -> 4Hx4Wx3 uint16, in the source's units: the 16-bit door of the native library
         (upstream RealESRGANer's max_range = 65535 branch; the reference has none).  value_range (lo, hi), None = (0, 65535): the
         net sees (clip(v, lo, hi) - lo) / (hi - lo), the output is lo + rint(clip(y, 0, 1) * (hi - lo)).  Same whole / tiled
@@ -425,7 +425,12 @@ class RealESRGAN:
         (native.Engine.carry_band_u16: guided upsampling, then block means that reproduce the band), behind the door and in front of
         the display rendering, under the call's mask.  The carried 4Hx4Wxk array comes back as one more, last, return value.
         extra_range: one (lo, hi) or one per band; None: each band's own min and max over the valid pixels.  extra_weights: the
-        three guide weights in the channel order of `img` (None: 1, 1, 1).  last_extra: the ranges, eps and inexact blocks per band."""
+        three guide weights in the channel order of `img` (None: 1, 1, 1).  last_extra: the ranges, eps and inexact blocks per band.
+        indices: normalised-difference indices on the output grid, a list of {"a", "b", "offset", "L", "K", "lut",
+        "zones", "zone_scale", "Z"} with a and b either ("img", channel of `img`) -- read from the output's device copy -- or
+        ("extra", i) -- the i-th carried band; lut (uint8 [65536][4]) and zones (uint16 labels, with zone_scale and Z) may be None.
+        Under the call's mask.  One more, last, return value: per index {"index" int16 [4H, 4W], "hist", "undefined"} and, with a
+        lut / zones, "rgba" / "zonal" (native.Engine.index_nd_u16)."""
         if self.scale != 4 or getattr(self.model, "arch", "rrdb") != "rrdb":
             raise ValueError(f"enhance16 is built for the x4 RRDB models, not {self.model_name}")
         if img.ndim != 3 or img.shape[2] != 3:
@@ -437,10 +442,13 @@ class RealESRGAN:
             raise ValueError(f"value_range {value_range}: need 0 <= lo < hi <= 65535")
         valid, out_nodata = self._mask_of(img, valid, nodata, fill_radius)
         plan = None if extra is None else self._extra_plan(img, extra, extra_range, extra_weights, valid, out_nodata)
+        iplan = None if indices is None else self._index_plan(indices, 0 if extra is None else np.asarray(extra).shape[2])
         if display is None:
             with self._engine.chain_lock:
                 out16 = self._door(img, valid, fill_radius, out_nodata, lo=lo, hi=hi)
-                return out16 if plan is None else (out16, self._carry_extra(plan))
+                carried = None if plan is None else self._carry_extra(plan)
+                res = (out16,) + (() if plan is None else (carried,)) + (() if iplan is None else (self._run_indices(iplan, out16, carried, valid),))
+                return res[0] if len(res) == 1 else res
         from s2sr.display import Stretch, render_u16
         stretch = Stretch.of(display)
         if nodata is not None and stretch.nodata is None:
@@ -450,7 +458,57 @@ class RealESRGAN:
             out16 = self._door(img, valid, fill_radius, out_nodata, lo=lo, hi=hi)
             carried = None if plan is None else self._carry_extra(plan)      # (it leaves the device copy as the door left it)
             disp, info = render_u16(None, stretch, self._engine, shape=out16.shape[:2])
-        return (out16, disp, info) if plan is None else (out16, disp, info, carried)
+            found = None if iplan is None else self._run_indices(iplan, out16, carried, valid)      # (behind the rendering: see there)
+        return (out16, disp, info) + (() if plan is None else (carried,)) + (() if iplan is None else (found,))
+
+    @staticmethod
+    def _index_plan(indices, k: int) -> list:
+        """The index records of a call, checked before the door runs."""
+        from s2sr import index as X
+        plan = []
+        for d in indices:
+            for side in ("a", "b"):
+                kind, c = d[side]
+                if kind not in ("img", "extra") or not 0 <= int(c) < (3 if kind == "img" else k):
+                    raise ValueError(f"indices: {side} = {d[side]!r} names neither a channel of the image nor one of the {k} carried band(s)")
+            if d["a"] == d["b"]:
+                raise ValueError(f"indices: a and b are both {d['a']!r}")
+            X._int(d.get("offset", 0), 0, 65535, "offset"), X._int(d.get("L", 0), 0, 65535, "L"), X._int(d.get("K", 10000), 1, X.K_MAX, "K")
+            plan.append(dict(d))
+        return plan
+
+    def _run_indices(self, plan, out16, carried, valid):
+        """Inside the chain lock, behind the door, the carried bands and the display rendering.  An image channel is read from the
+        output's device copy, which the engine takes as plane a only: an index whose b is an image channel runs with the planes
+        exchanged -- that negates every defined value exactly -- through the mirrored LUT, and its raster,
+        histogram and zonal sums are mirrored back here.  Indices of two carried bands upload both planes over the device copy,
+        so they run last."""
+        found = [None] * len(plan)
+        order = sorted(range(len(plan)), key=lambda i: plan[i]["a"][0] == "extra" and plan[i]["b"][0] == "extra")
+        for i in order:
+            d = plan[i]
+            (ka, ca), (kb, cb) = d["a"], d["b"]
+            flip = kb == "img" and ka == "extra"
+            if flip:
+                (ka, ca), (kb, cb) = (kb, cb), (ka, ca)
+            lut = d.get("lut")
+            if flip and lut is not None:
+                lut = np.concatenate([lut[:1], lut[:0:-1]])            # entry (-v) + 32768 = 65536 - (v + 32768)
+            zones = d.get("zones")
+            want = ("index", "hist") + (("rgba",) if lut is not None else ()) + (("zonal",) if zones is not None else ())
+            a = None if ka == "img" else np.ascontiguousarray(carried[..., ca])
+            b = np.ascontiguousarray(out16[..., cb]) if kb == "img" else np.ascontiguousarray(carried[..., cb])
+            r = self._engine.index_nd_u16(a, b, ca=ca if ka == "img" else 0, cb=0, offset=d.get("offset", 0), L=d.get("L", 0), K=d.get("K", 10000),
+                                          valid=valid, valid_scale=4, zones=zones, zone_scale=d.get("zone_scale", 1), Z=d.get("Z", 0), lut=lut,
+                                          want=want)
+            r = {k: (np.array(v) if isinstance(v, np.ndarray) else v) for k, v in r.items()}       # (out of the pinned pool, which the next call reuses)
+            if flip:
+                r["index"] = np.negative(r["index"])                    # int16: -(-32768) is -32768, nodata stays
+                r["hist"] = np.ascontiguousarray(r["hist"][::-1])
+                if "zonal" in r:
+                    r["zonal"][:, 1] *= -1
+            found[i] = r
+        return found
 
     @staticmethod
     def _extra_plan(img, extra, extra_range, extra_weights, valid, fill):

@@ -49,6 +49,8 @@ class WowRequest(BaseModel):         # main.py:200-208
     consistency: Optional[str] = None   # not in the reference: "exact" or "smooth" -- block means reproduce the input pixels
     extra_bands: Optional[Union[str, List[int]]] = None   # not in the reference: "all" or band numbers from 4 on, carried to the SR grid; 16-bit jobs only
     transparent_tiles: bool = False  # not in the reference: the tile pyramid shows the map through the job's nodata pixels; with nodata only
+    indices: Optional[List[Union[str, dict]]] = None   # not in the reference: spectral indices on the SR grid (s2sr/index.py); 16-bit jobs only
+    index_offset: int = 0            # ... and the DN offset of the definitions that name none (Sentinel-2 L2A baseline 04.00 and later: 1000)
 
 
 class SRResponse(BaseModel):         # main.py:230-235
@@ -197,11 +199,12 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
         tifs = sorted(source_dir.glob("*.tif"), key=lambda x: x.stat().st_mtime, reverse=True)
         return tifs[0] if tifs else None
 
-    def _default_tiler(sr_tif, tiles_dir, stretch=None, mask=None):
+    def _default_tiler(sr_tif, tiles_dir, stretch=None, mask=None, ramp=None):
         from app.tiling import process_raster_to_tiles
         process_raster_to_tiles(input_path=sr_tif, tiles_dir=tiles_dir, min_zoom=tile_min_zoom,
                                 max_zoom=min(tile_max_zoom + 2, 20),          # "Higher zoom for SR" (main.py:276)
                                 **({"stretch": stretch} if stretch is not None else {}),
+                                **({"ramp": ramp} if ramp is not None else {}),
                                 **({"valid": mask[0], "valid_scale": mask[1], "nodata": mask[2]} if mask is not None else {}))
 
     def _tile(result, sub, stretch=None, mask=None):
@@ -215,6 +218,10 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             else:
                 run(Path(sr_tif), tiles_dir)
             result["tiles_dir"] = str(tiles_dir)
+            # a job with indices: the default tiler once more per index, its raster through its colour ramp, into <tiles dir>_<name>
+            for e in (result.get("sr_metadata", {}).get("indices") or []) if tiler is None else []:
+                _default_tiler(Path(e["files"]["tif"]), data_dir / f"{sub}_{e['name']}", ramp=[tuple(st) for st in e["ramp"]])
+                result.setdefault("index_tiles", {})[e["name"]] = str(data_dir / f"{sub}_{e['name']}")
 
     def _check_consistency(value):                                           # an unknown mode is a 400, before a job exists
         try:
@@ -237,7 +244,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
 
     def run_wow_job(job_id, input_file, output_dir, enhance_crops, auto_fetch=True, max_age_days=30,
                     max_cloud_cover=30.0, force_fetch=False, model="realesrgan_x4", seam_blend=False, bit_depth=8,
-                    display=None, nodata=None, fill_radius=32, consistency=None, extra_bands=None, transparent_tiles=False):   # main.py:290-368
+                    display=None, nodata=None, fill_radius=32, consistency=None, extra_bands=None, transparent_tiles=False, indices=None,
+                    index_offset=0):   # main.py:290-368
         try:
             if input_file is None and auto_fetch:
                 _set(job_id, status="fetching",
@@ -262,6 +270,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                 extra["consistency"] = consistency
             if extra_bands is not None:
                 extra["extra_bands"] = extra_bands
+            if indices is not None:
+                extra.update(indices=indices, index_offset=index_offset)
             result = process_wow_sr(input_tif=input_file, output_dir=output_dir, enhance_crops=enhance_crops, model=model, **extra)
             _set(job_id, status="tiling", message="Generating tiles from WOW SR image...")
             # a 16-bit job's tiles show the rendering of its PNG: the job's stretch with the limits it found
@@ -359,6 +369,20 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                 select_bands(request.extra_bands, count)
             except ValueError as e:
                 raise HTTPException(status_code=400, detail=str(e))
+        if request.indices is not None:
+            if request.bit_depth != 16:
+                raise HTTPException(status_code=400, detail="indices are computed on the 16-bit path: pass bit_depth=16")
+            try:
+                from s2sr.index import resolve
+                count = None
+                if input_file is not None:
+                    from s2sr import rasterio_lite as rio
+                    count = rio.read_bands_raw(input_file)[0].shape[2]
+                resolve(request.indices, request.index_offset, count)
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
+        elif request.index_offset != 0:
+            raise HTTPException(status_code=400, detail="index_offset belongs to indices: pass indices")
         job_id = f"wow_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
         output_dir = data_dir / "wow" / job_id
         output_dir.mkdir(parents=True, exist_ok=True)
@@ -377,7 +401,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                                   **({"nodata": request.nodata, "fill_radius": request.fill_radius} if request.nodata is not None else {}),
                                   **({"consistency": request.consistency} if request.consistency is not None else {}),
                                   **({"extra_bands": request.extra_bands} if request.extra_bands is not None else {}),
-                                  **({"transparent_tiles": True} if request.transparent_tiles else {}))
+                                  **({"transparent_tiles": True} if request.transparent_tiles else {}),
+                                  **({"indices": request.indices, "index_offset": request.index_offset} if request.indices is not None else {}))
         msg = (f"WOW SR started: {input_file.name} -> Real-ESRGAN x4 + Enhanced" if input_file else
                f"WOW SR started: auto-fetching best image (last {request.max_age_days}d, cloud <={request.max_cloud_cover}%)")
         return SRResponse(job_id=job_id, status="queued", message=msg)

@@ -171,6 +171,23 @@ def _mask_of(arr: np.ndarray, tags: dict, path, nodata, valid, valid_scale: int)
     return mask_from_value(raw, value), 1, value
 
 
+def _ramp_source(arr: np.ndarray, ramp, path, stretch, nodata, valid):
+    """A single-band int16 index raster through a colour ramp -> (rgb uint8 [H, W, 3], the mask of the masked warp:
+    the rendering's alpha, scale 1).  ramp: a name of s2sr.index.RAMPS (its values at K = 10000), a list of (value, r, g, b) stops,
+    or a ready LUT uint8 [65536][4].  Rendered on the device (native.Engine.index_render_i16); nodata (-32768) comes out 0, 0, 0, 0."""
+    from s2sr import index as xi
+    if stretch is not None or nodata is not None or valid is not None:
+        raise ValueError("ramp renders an index raster, whose nodata is its own -32768: stretch, nodata and valid do not go with it")
+    if arr.dtype != np.int16 or arr.shape[2] != 1:
+        raise ValueError(f"{path}: ramp needs a single-band int16 raster, got {arr.shape[2]} band(s) of {arr.dtype}")
+    lut = ramp if isinstance(ramp, np.ndarray) else xi.ramp_lut(xi.ramp_for(ramp))
+    eng, lock = _engine_and_lock()
+    with lock:
+        rgba = np.array(eng.index_render_i16(np.ascontiguousarray(arr[..., 0]), lut))      # (out of the pinned pool, which the warp reuses)
+    rgb = np.ascontiguousarray(rgba[..., :3])
+    return rgb, native.warp_mask(rgb.shape, rgba[..., 3], 1)
+
+
 def _u8_nodata(value) -> Optional[int]:
     """What the 8-bit <stem>_3857.tif holds in its alpha-0 pixels and declares in GDAL_NODATA: the value where a byte can hold it,
     0 otherwise (a 16-bit product's value above 255 under a display stretch); None: no value known, the file as ever."""
@@ -287,17 +304,22 @@ def _cut_pyramid(rgba: np.ndarray, place: geo.Placement, output_dir: Path, min_z
 
 
 def generate_xyz_tiles(input_path: Path, output_dir: Path, min_zoom: int = 10, max_zoom: int = 16, tile_size: int = 256,
-                       resampling: str = "average", nodata=None, valid=None, valid_scale: int = 1) -> Path:
+                       resampling: str = "average", nodata=None, valid=None, valid_scale: int = 1, ramp=None) -> Path:
     """z/x/y.png (XYZ row order, RGBA) for every tile of zooms min..max that holds data.  nodata / valid / valid_scale: the pixels
-    the pyramid leaves transparent (see _mask_of)."""
+    the pyramid leaves transparent (see _mask_of).  ramp: a single-band int16 index raster through a colour ramp,
+    transparent over its nodata (see _ramp_source)."""
     _check_tile_args(tile_size, resampling)
     _check_mask_args(nodata, valid, valid_scale)
     input_path, output_dir = Path(input_path), Path(output_dir)
     arr, tags, place, crs = _read(input_path)
     if crs.epsg != 3857:
         raise ValueError(f"{input_path}: {crs}, tiles are cut from an EPSG:3857 raster (reproject_to_web_mercator first)")
-    mask, vs, _value = _mask_of(arr, tags, input_path, nodata, valid, valid_scale)
-    rgba = _masked_rgba(arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2), mask, vs)
+    if ramp is not None:
+        rgb, mask = _ramp_source(arr, ramp, input_path, None, nodata, valid)
+        rgba = _masked_rgba(rgb, mask, 1)
+    else:
+        mask, vs, _value = _mask_of(arr, tags, input_path, nodata, valid, valid_scale)
+        rgba = _masked_rgba(arr[..., :3] if arr.shape[2] >= 3 else np.repeat(arr[..., :1], 3, axis=2), mask, vs)
     _cut_pyramid(rgba, place, output_dir, min_zoom, max_zoom, resampling=resampling)
     logger.info("Tile generation complete: %s", output_dir)
     return output_dir
@@ -315,13 +337,15 @@ def create_tileset_metadata(tiles_dir: Path, bounds_4326: list, min_zoom: int, m
 
 def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 10, max_zoom: int = 16, resampling: str = "average",
                             tile_template: str = "/tiles/{z}/{x}/{y}.png", stretch=None, nodata=None, valid=None,
-                            valid_scale: int = 1) -> dict:
+                            valid_scale: int = 1, ramp=None) -> dict:
     """Check the CRS, reproject if needed, cut the pyramid, write tileset.json.  stretch (uint16 rasters; ignored for uint8): the
     8-bit image is the raster's display rendering instead of the global min-max, see _rgb_u8.
     nodata (None, an integer, or "tag") / valid, valid_scale (the caller's own mask, which wins; see _mask_of): the pyramid is
     transparent over the pixels that were never measured -- a raster that needs reprojecting goes through the
     masked warp, one that is EPSG:3857 already gets alpha 255 x mask and RGB 0 where invalid; with a value known <stem>_3857.tif
-    carries the GDAL_NODATA tag and holds the value in every alpha-0 pixel.  Without them every file is what it always was."""
+    carries the GDAL_NODATA tag and holds the value in every alpha-0 pixel.  Without them every file is what it always was.
+    ramp (see _ramp_source): the raster is a single-band int16 index; it is rendered through the colour ramp on the
+    device, the rendering's alpha is the mask of the masked warp, and the pyramid is cut as for any nodata-transparent raster."""
     import time
     _check_tile_args(256, resampling)
     _check_mask_args(nodata, valid, valid_scale)
@@ -329,7 +353,11 @@ def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 1
     LAST_STATS.clear()
     t0 = time.perf_counter()
     arr, tags, place, crs = _read(input_path)
-    mask, vs, value = _mask_of(arr, tags, input_path, nodata, valid, valid_scale)
+    if ramp is not None:
+        rgb, mask = _ramp_source(arr, ramp, input_path, stretch, nodata, valid)
+        vs, value = 1, None
+    else:
+        mask, vs, value = _mask_of(arr, tags, input_path, nodata, valid, valid_scale)
     h, w, b = arr.shape
     west, south, east, north = place.bounds(w, h)
     t = np.linspace(0.0, 1.0, 21)
@@ -337,7 +365,8 @@ def process_raster_to_tiles(input_path: Path, tiles_dir: Path, min_zoom: int = 1
     ey = np.concatenate([np.full(21, north), north - (north - south) * t, np.full(21, south), south + (north - south) * t])
     lon, lat = crs.to_lonlat(ex, ey)
     bounds_4326 = [float(lon.min()), float(lat.min()), float(lon.max()), float(lat.max())]
-    rgb = _rgb_u8(arr, stretch)
+    if ramp is None:
+        rgb = _rgb_u8(arr, stretch)
     t1 = time.perf_counter()
     LAST_STATS["read"] = t1 - t0
     side, err = None, []

@@ -70,7 +70,7 @@ def input_mask(input_path: Path, nodata, bit_depth: int = 8) -> np.ndarray:
 
 def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend: bool = False, display=None,
                     enhance_crops: bool = False, nodata=None, fill_radius: int = 32, consistency=None, extra_bands=None,
-                    extra_weights=None) -> Tuple[Path, dict]:
+                    extra_weights=None, indices=None, index_offset: int = 0, zones=None) -> Tuple[Path, dict]:
     """bit_depth=16 of apply_wow_sr: a uint16 GeoTIFF read raw, value_range = the image's own (min, max) -- the reference's
     min-max (wow_sr.py:67-73) minus its quantisation to 8 bits -- the net fed BGR as ever (:85,94), RealESRGAN.enhance16, RGB back,
     a uint16 GeoTIFF out.  Without `display`: no PNG (the encoder is 8-bit) and no crop-visibility post-process (OpenCV's 8-bit
@@ -82,7 +82,15 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     extra_bands ("all" or band numbers from 4 on): those bands of the file are carried to the output grid against the
     super-resolved image (RealESRGAN.enhance16(extra=...)), each with its own min-max over the valid pixels as its range, and the
     GeoTIFF holds 3 + k bands: RGB as without the option, then the carried bands in the order given.  extra_weights: the guide
-    weights in R, G, B terms (None: 1, 1, 1)."""
+    weights in R, G, B terms (None: 1, 1, 1).
+    indices, index_offset, zones (s2sr/index.py): spectral indices on the output grid -- a list of preset names
+    ("ndvi", "ndwi", "ndre", "savi"), presets with their bands named ({"preset": "ndre", "nir": 4, "rededge": 5}) or definitions
+    ({"name", "a", "b", "offset", "L", "K"}; a, b: 1-based bands of the file).  Bands 1-3 are read from the job's final uint16
+    product on the device (behind the consistency pass), bands from 4 on are carried for the index whether or not extra_bands
+    lists them (only listed bands go into the product GeoTIFF), and the job's nodata mask is the index's.  index_offset: the DN
+    offset of a definition that names none.  Per index the job writes <stem>_<name>.tif (int16, GDAL_NODATA -32768) and
+    <stem>_<name>.png (its RGBA rendering through the index's colour ramp); zones (the path of a single-band uint8 / uint16 label
+    GeoTIFF on the input or the output grid, or such an array) adds a per-zone table.  The metadata gains "indices", and only then."""
     import dataclasses
 
     from s2sr import rasterio_lite as rio
@@ -92,15 +100,22 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     input_path = Path(input_path)
     print(f"\nWOW Super-Resolution ({model}, 16-bit)\n   Input: {input_path}")
     img, georef, valid, value = read_masked(input_path, nodata, 16)
-    extra = numbers = None
-    if extra_bands is not None:
+    extra = numbers = defs = None
+    if extra_bands is not None or indices is not None:
         from s2sr import bands as xb
         try:
             every, _ = rio.read_bands_raw(input_path)
         except ValueError as e:
-            raise ValueError(f"extra_bands needs a GeoTIFF whose bands share one uint16 layout: {e}") from e
-        numbers = xb.select_bands(extra_bands, every.shape[2])
-        extra = np.ascontiguousarray(every[:, :, [b - 1 for b in numbers]])
+            raise ValueError(f"{'extra_bands' if extra_bands is not None else 'indices'} needs a GeoTIFF whose bands share one uint16 layout: {e}") from e
+        listed = [] if extra_bands is None else xb.select_bands(extra_bands, every.shape[2])
+        numbers = list(listed)                                    # the carried bands: the listed ones, then what only an index reads
+        if indices is not None:
+            from s2sr import index as xi
+            defs = xi.resolve(indices, index_offset, every.shape[2])
+            numbers += [b for b in xi.carried_bands(defs) if b not in numbers]
+            label = None if zones is None else xi.check_zones(rio.read_bands_raw(zones)[0] if isinstance(zones, (str, Path)) else zones, img.shape[:2], 4)
+        if numbers:
+            extra = np.ascontiguousarray(every[:, :, [b - 1 for b in numbers]])
         del every
         w_rgb = xb.check_args(4, 0, 65535, xb.WEIGHTS if extra_weights is None else extra_weights)["weights"]
     from s2sr.nodata import valid_range
@@ -111,14 +126,26 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     display_rgb = info = carried = None
     if extra is not None:            # the device copy is BGR: the guide weights go in reversed
         mask_kw = dict(mask_kw, extra=extra, extra_weights=w_rgb[::-1])
+    found = None
+    if defs is not None:             # file band 1, 2, 3 is channel 2, 1, 0 of the device copy; a band from 4 on is one of the carried
+        side = lambda b: ("img", 3 - b) if b <= 3 else ("extra", numbers.index(b))
+        ramps = [xi.ramp_for(xi.DEFAULT_RAMP.get(d["preset"], "diverging"), d["K"]) for d in defs]
+        mask_kw = dict(mask_kw, indices=[dict(a=side(d["a"]), b=side(d["b"]), offset=d["offset"], L=d["L"], K=d["K"], lut=xi.ramp_lut(r),
+                                              **({} if label is None else {"zones": label[0], "zone_scale": label[1], "Z": label[2]}))
+                                         for d, r in zip(defs, ramps)])
     if stretch is None:
         out_bgr = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), **mask_kw)
+        if defs is not None:
+            *out_bgr, found = out_bgr
+            out_bgr = out_bgr[0] if len(out_bgr) == 1 else tuple(out_bgr)
         if extra is not None:
             out_bgr, carried = out_bgr
     else:
         # the device copy is BGR like the net's input: explicit per-band limits go in reversed, the info's come back reversed
         bgr = stretch if stretch.limits is None else dataclasses.replace(stretch, limits=stretch.limits[::-1])
         out_bgr, disp_bgr, info, *rest = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), display=bgr, **mask_kw)
+        if defs is not None:
+            found = rest.pop()
         carried = rest[0] if rest else None
         display_rgb = np.ascontiguousarray(disp_bgr[:, :, ::-1])
         info = dict(info, limits=info["limits"][::-1])
@@ -132,6 +159,10 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
     del esrgan
     final_output = Path(output_path).with_suffix(".tif")
     final_output.parent.mkdir(parents=True, exist_ok=True)
+    if carried is not None and defs is not None:                  # only the listed bands go into the product
+        carried = carried[..., :len(listed)] if listed else None
+        carried_rec = None if carried is None else {k: (v[:len(listed)] if k in ("ranges", "eps", "inexact") else v) for k, v in carried_rec.items()}
+        numbers = listed
     if carried is None:
         rio.write_geotiff_rgb16(final_output, output_rgb, georef.scaled(scale), **({} if valid is None else {"nodata": value}))
     else:
@@ -167,11 +198,21 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
         metadata["consistency"] = metadata_block(consistency, inexact)
     if carried_rec is not None:
         metadata["extra_bands"] = xb.metadata_block(numbers, carried_rec["ranges"], w_rgb, carried_rec["r"], carried_rec["eps"], carried_rec["inexact"])
+    if defs is not None:
+        out_geo = georef.scaled(scale)
+        metadata["indices"] = []
+        for d, ramp, r in zip(defs, ramps, found):
+            tif = final_output.with_name(f"{final_output.stem}_{d['name']}.tif")
+            rio.write_geotiff_i16(tif, r["index"], out_geo, nodata=xi.NODATA)
+            rio.write_png(tif.with_suffix(".png"), r["rgba"])
+            stats = xi.stats_from_hist(r["hist"], d["K"], pixel_size=out_geo.pixel_size)
+            metadata["indices"].append(xi.metadata_entry(d, r["undefined"], stats, ramp, {"tif": str(tif), "png": str(tif.with_suffix(".png"))},
+                                                         None if label is None else xi.zonal_table(r["zonal"], d["K"])))
     return final_output, metadata
 
 
 def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=None, fill_radius: int = 32, consistency=None,
-                     extra_bands=None, extra_weights=None) -> None:
+                     extra_bands=None, extra_weights=None, indices=None, index_offset: int = 0, zones=None) -> None:
     from s2sr.consistency import check_args as check_consistency
     from s2sr.nodata import check_args
     check_args(nodata, fill_radius)
@@ -189,6 +230,13 @@ def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=N
         xb.check_args(4, 0, 65535, xb.WEIGHTS if extra_weights is None else extra_weights)
     elif extra_weights is not None:
         raise ValueError("extra_weights are the guide weights of extra_bands: pass extra_bands")
+    if indices is not None:
+        from s2sr import index as xi
+        if bit_depth != 16:
+            raise ValueError("indices are computed on the 16-bit path: pass bit_depth=16 (an 8-bit job has no uint16 product to take them from)")
+        xi.resolve(indices, index_offset)          # what can be refused without the file: presets, names, bands, K, L, offsets
+    elif zones is not None or index_offset != 0:
+        raise ValueError("zones and index_offset belong to indices: pass indices")
     if display is not None:
         if bit_depth != 16:
             raise ValueError("display is the 8-bit rendering of a 16-bit job: pass bit_depth=16 (an 8-bit job's image is its display image)")
@@ -201,7 +249,8 @@ def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=N
 
 def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True,
                  model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None, nodata=None,
-                 fill_radius: int = 32, consistency=None, extra_bands=None, extra_weights=None) -> Tuple[Path, dict]:
+                 fill_radius: int = 32, consistency=None, extra_bands=None, extra_weights=None, indices=None, index_offset: int = 0,
+                 zones=None) -> Tuple[Path, dict]:
     """Reference wow_sr.py:28-184 -- same outputs (GeoTIFF and/or PNG) and metadata dict.  bit_depth=16 (not in the reference): a
     uint16 GeoTIFF goes through the net without the 8-bit squeeze and comes back as a uint16 GeoTIFF (_apply_wow_sr16).
     display (bit_depth=16 only; a s2sr.display.Stretch or a dict of its fields): the job also writes the PNG, from the output's
@@ -219,13 +268,15 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
     changes radiometry on purpose, so the written 8-bit image is consistent only up to it.
     extra_bands, extra_weights (bit_depth=16 only; not in the reference): see _apply_wow_sr16.  The GeoTIFF gains
     the carried bands behind R, G, B and the metadata "extra_bands": {"bands", "ranges", "weights_rgb", "r", "eps", "gain_limit",
-    "inexact_blocks"}, and only then."""
+    "inexact_blocks"}, and only then.
+    indices, index_offset, zones (bit_depth=16 only; not in the reference): see _apply_wow_sr16.  Two files per index
+    next to the GeoTIFF and "indices" in the metadata, and only then."""
     from s2sr import rasterio_lite as rio
 
-    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency, extra_bands, extra_weights)
+    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency, extra_bands, extra_weights, indices, index_offset, zones)
     if bit_depth == 16:
         return _apply_wow_sr16(input_path, output_path, model, seam_blend, display, enhance_crops, nodata, fill_radius, consistency,
-                               extra_bands, extra_weights)
+                               extra_bands, extra_weights, **({} if indices is None else {"indices": indices, "index_offset": index_offset, "zones": zones}))
 
     model_display = {"realesrgan_x4": "Real-ESRGAN x4",
                      "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)",
@@ -304,11 +355,14 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
 
 def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True,
                    model: str = "realesrgan_x4", bit_depth: int = 8, seam_blend: bool = False, display=None, nodata=None,
-                   fill_radius: int = 32, consistency=None, extra_bands=None, extra_weights=None) -> dict:
+                   fill_radius: int = 32, consistency=None, extra_bands=None, extra_weights=None, indices=None, index_offset: int = 0,
+                   zones=None) -> dict:
     """Reference wow_sr.py:212-266 -- file naming, metadata JSON and result dict schema.  bit_depth=16: see apply_wow_sr (no PNG:
     "sr_png" is None -- unless `display` is given: the PNG is the output's display rendering).  seam_blend, nodata, fill_radius,
-    consistency, extra_bands, extra_weights: see apply_wow_sr."""
-    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency, extra_bands, extra_weights)   # before anything is created
+    consistency, extra_bands, extra_weights, indices, index_offset, zones: see apply_wow_sr; "outputs" gains "indices": {name: {"tif",
+    "png"}} with indices, and only then."""
+    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency, extra_bands, extra_weights, indices, index_offset,
+                     zones)   # before anything is created
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
@@ -323,6 +377,8 @@ def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True
         blend["extra_bands"] = extra_bands
         if extra_weights is not None:
             blend["extra_weights"] = extra_weights
+    if indices is not None:
+        blend.update(indices=indices, index_offset=index_offset, zones=zones)
     if bit_depth == 16:
         if display is not None:
             blend["display"] = display
@@ -338,6 +394,8 @@ def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True
                     "sr_png": str(png) if png is not None and png.exists() else None},
         "sr_metadata": sr_metadata,
     }
+    if indices is not None:
+        result["outputs"]["indices"] = {e["name"]: dict(e["files"]) for e in sr_metadata.get("indices", [])}
     with open(output_dir / f"{base_name}_wow_sr_metadata.json", "w") as f:
         json.dump(result, f, indent=2)
     return result

@@ -1,4 +1,4 @@
-// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_display.hip, engine_bands.hip, engine_debug.hip): the handle behind
+// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_display.hip, engine_bands.hip, engine_index.hip, engine_debug.hip): the handle behind
 // the C ABI of include/s2sr.h, the types it is made of, and the helpers that more than one of those files uses.  What a single
 // file uses stays static or anonymous in that file.
 #pragma once
@@ -20,12 +20,13 @@ enum Slot : int {
     SL_SRC = 0,   // 0 and 1: a call's source and its result: the upload and the image / tiles / level that leave.  Along a chain of
     SL_DST,       //   pyramid or display calls the roles swap: the source is where the call before kept its result, the result other() of it
     SL_MID,       // what lies between: gathered windows (the untiled image's tiles), the 16-bit batch's quantised tiles, the resample
-                  //   intermediate, the PNG writer's statistics, the band s2sr_carry_band_u16 carries
-    SL_TABLES,    // tables and plans: paste / blend tables, warp grid, footprint and tap tables, PNG plans, display histogram + LUT
+                  //   intermediate, the PNG writer's statistics, the band s2sr_carry_band_u16 carries, plane b of s2sr_index_nd_u16
+    SL_TABLES,    // tables and plans: paste / blend tables, warp grid, footprint and tap tables, PNG plans, display histogram + LUT, an index pass's LUT, counter,
+                  //   histogram and zonal sums
     SL_CHUNK,     // a chunk's tile outputs, the unbanded post-process's image, the PNG streams of even groups
     SL_PP,        // the post-process work area, where a banded run lives while it is open; the PNG streams of odd groups (the level the
                   //   writer reads is in 0 / 1, so while it runs 2 .. 5 are free)
-    SL_VALID,     // the device copy of a masked call's `valid` (nodata.hip; the masked warp of tiles.hip)
+    SL_VALID,     // the device copy of a masked call's `valid` (nodata.hip; the masked warp of tiles.hip); an index pass's `valid` and, behind it, its zone labels
     SL_CONS,      // a consistency pass's inexact counters (uint64[3], the first 256 bytes) and, in mode 2, its residual plane (consistency.hip);
                   //   a carried band's inexact counter (uint64, the first 256 bytes) and its coefficient planes A, C (bands.hip)
 };
@@ -82,11 +83,11 @@ struct ConvW {
 };
 
 // kernel families for the HIP-event statistics
-enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_DHIST, F_DAPPLY, F_NFILL, F_NMASK, F_CONS, F_BANDS, F_COUNT };
+enum Fam { F_PACK, F_FIRST, F_RDB14, F_RDB5, F_BODY, F_UP, F_HR, F_LAST, F_POST, F_MISC, F_CFIRST, F_CBODY, F_CLAST, F_DHIST, F_DAPPLY, F_NFILL, F_NMASK, F_CONS, F_BANDS, F_INDEX, F_COUNT };
 inline constexpr const char* kFamName[F_COUNT] = {"pack_u8",   "conv_first", "rdb_conv1-4", "rdb_conv5",   "conv_body",
                                  "conv_up",   "conv_hr",    "conv_last",   "postprocess", "misc",
                                  "compact_first", "compact_body", "compact_last", "display_hist", "display_apply",
-                                 "nodata_fill", "nodata_mask", "consistency", "bands"};
+                                 "nodata_fill", "nodata_mask", "consistency", "bands", "index"};
 
 inline constexpr int kRoleFam[kRoles] = {F_FIRST, F_RDB14, F_RDB5, F_RDB5, F_BODY, F_UP, F_UP, F_HR, F_LAST, F_CFIRST, F_CBODY, F_CLAST};   // by Role
 

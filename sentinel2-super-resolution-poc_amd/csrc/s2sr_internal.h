@@ -339,6 +339,17 @@ hipError_t launch_band_apply(const uint16_t* d_q, const uint16_t* d_band, const 
                              uint16_t* d_out, unsigned long long* d_cnt, int H, int W, int S, int by0, int by1, int lo, int hi, const int w[3],
                              int fill, hipStream_t st);
 
+// normalised-difference indices (index.hip): rows [y0, y1) of the index of channel ca of d_a ([H, W, ac], ac 1 or 3) and
+// channel cb of d_b.  d_valid [ceil(H / vs)][ceil(W / vs)] or null; d_zones likewise at zs, with d_zonal (uint64 [Z + 1][3], two's
+// complement sums, added to); d_lut uint8 [65536][4] (required with d_rgba); d_hist uint64 [2 K + 1] and d_undefined are added to.
+// Every output may be null.  Bases 16-byte aligned and readable up to the next multiple of 16 bytes; H W < 2^31.
+hipError_t launch_index_nd(const uint16_t* d_a, int ac, int ca, const uint16_t* d_b, int bc, int cb, int H, int W, int y0, int y1, int offset,
+                           int L, int K, const uint8_t* d_valid, int vs, const uint16_t* d_zones, int zs, int Z, const uint8_t* d_lut,
+                           int16_t* d_out, unsigned long long* d_hist, unsigned long long* d_zonal, uint8_t* d_rgba,
+                           unsigned long long* d_undefined, hipStream_t st);
+// rows [y0, y1) of an int16 index raster through the LUT: -32768 gives 0, 0, 0, 0
+hipError_t launch_index_render(const int16_t* d_idx, int H, int W, int y0, int y1, const uint8_t* d_lut, uint8_t* d_rgba, hipStream_t st);
+
 // XYZ tile pyramid (tiles.hip)
 hipError_t launch_warp_bilinear(const uint8_t* d_rgb, int H, int W, const float* d_grid, int gh, int gw, int step, int OH, int OW,
                                 uint8_t* d_out, hipStream_t st);

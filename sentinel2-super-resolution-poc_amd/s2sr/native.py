@@ -167,6 +167,9 @@ _PROTOS = {
     "s2sr_display_apply_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "s2sr_carry_band_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "s2sr_index_nd_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_int32, C.c_void_p,
+                                    C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
+    "s2sr_index_render_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "s2sr_enhance_job_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PPParams), C.c_void_p]),
     "s2sr_enhance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tile_process_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -922,6 +925,89 @@ class Engine:
                                                   int(r), int(eps), _ptr(valid) if valid is not None else None, int(fill), int(band_rows),
                                                   _ptr(out), _ptr(bad)), "s2sr_carry_band_u16")
         return out, int(bad[0])
+
+    # -- normalised-difference indices (include/s2sr.h; presets, ramps, statistics and argument checks: s2sr/index.py) --
+    @staticmethod
+    def _plane(p, what: str):
+        """a uint16 plane [H, W] or [H, W, c] -> (the contiguous array, H, W, c)"""
+        p = np.asarray(p)
+        if p.dtype != np.uint16:
+            raise TypeError(f"{what} takes uint16 planes, got {p.dtype}")
+        if p.ndim not in (2, 3):
+            raise ValueError(f"{what}: expected a plane [H, W] or [H, W, c], got shape {p.shape}")
+        p = np.ascontiguousarray(p)
+        return p, p.shape[0], p.shape[1], (p.shape[2] if p.ndim == 3 else 1)
+
+    @staticmethod
+    def _cells(m, H: int, W: int, scale: int, dtype, what: str) -> np.ndarray:
+        m = np.asarray(m)
+        scale = int(scale)
+        want = (-(-H // scale), -(-W // scale)) if scale >= 1 else None
+        if want is not None and m.shape != want:
+            raise ValueError(f"{what} must be [ceil(H / {scale}), ceil(W / {scale})] = {want}, got shape {m.shape}")
+        if dtype == np.uint8 and m.dtype != np.uint8:
+            m = m != 0
+        return np.ascontiguousarray(m, dtype=dtype)
+
+    @staticmethod
+    def _index_lut(lut, what: str) -> np.ndarray:
+        lut = np.ascontiguousarray(lut)
+        if lut.dtype != np.uint8 or lut.shape != (65536, 4):
+            raise ValueError(f"{what}: lut must be uint8 [65536][4], got {lut.dtype} {lut.shape}")
+        return lut
+
+    def index_nd_u16(self, a: Optional[np.ndarray], b: np.ndarray, ca: int = 0, cb: int = 0, offset: int = 0, L: int = 0, K: int = 10000,
+                     valid=None, valid_scale: int = 1, zones=None, zone_scale: int = 1, Z: int = 0, lut=None, band_rows: int = 0,
+                     want=("index",)) -> dict:
+        """v = round_half_away(K (a' - b') / (a' + b' + L)), a' = max(a - offset, 0), of channel ca of a and channel cb of b (uint16
+        [H, W] or [H, W, 3]); a None: channel ca of the H x W x 3 uint16 image the previous call on this engine left on the device,
+        which stays there.  `want` names the outputs: "index" (int16 [H, W], nodata -32768), "hist" (uint64 [2 K + 1]), "rgba"
+        (uint8 [H, W, 4] through lut, uint8 [65536][4]), "zonal" (int64 [Z + 1][3] over the uint16 labels `zones`).  Returns a dict
+        of those and "undefined" (the unmasked pixels whose denominator is zero).  No weights needed."""
+        what = "index_nd_u16"
+        b, H, W, bc = self._plane(b, what)
+        ac = 3
+        if a is not None:
+            a, Ha, Wa, ac = self._plane(a, what)
+            if (Ha, Wa) != (H, W):
+                raise ValueError(f"{what}: a is {Ha} x {Wa}, b is {H} x {W}")
+        want = set(want)
+        if not want <= {"index", "hist", "rgba", "zonal"}:
+            raise ValueError(f"{what}: outputs are index, hist, rgba, zonal; got {sorted(want)}")
+        if valid is not None:
+            valid = self._cells(valid, H, W, valid_scale, np.uint8, f"{what}: valid")
+        if zones is not None:
+            zones = self._cells(zones, H, W, zone_scale, np.uint16, f"{what}: zones")
+        if lut is not None:
+            lut = self._index_lut(lut, what)
+        K, Z = int(K), int(Z)
+        ok = H > 0 and W > 0
+        out = pinned_pool.empty((H, W), np.int16) if "index" in want and ok else None
+        rgba = pinned_pool.empty((H, W, 4), np.uint8) if "rgba" in want and ok else None
+        hist = np.zeros(2 * K + 1 if 1 <= K <= 16383 else 1, np.uint64) if "hist" in want else None
+        zonal = np.zeros((Z + 1 if 0 <= Z <= 65535 else 1, 3), np.int64) if "zonal" in want else None
+        undef = np.zeros(1, np.uint64)
+        p = lambda x: _ptr(x) if x is not None else None
+        self._check(self._lib.s2sr_index_nd_u16(self._h, p(a), ac, int(ca), _ptr(b), bc, int(cb), H, W, int(offset), int(L), K, p(valid),
+                                                int(valid_scale), p(zones), int(zone_scale), Z, p(lut), int(band_rows), p(out), p(hist), p(zonal),
+                                                p(rgba), _ptr(undef)), "s2sr_index_nd_u16")
+        res = {"undefined": int(undef[0])}
+        for k, v in (("index", out), ("hist", hist), ("rgba", rgba), ("zonal", zonal)):
+            if k in want:
+                res[k] = v
+        return res
+
+    def index_render_i16(self, idx: np.ndarray, lut: np.ndarray, band_rows: int = 0) -> np.ndarray:
+        """int16 [H, W] -> uint8 [H, W, 4] = lut[(uint16)(idx + 32768)], -32768 (nodata) -> 0, 0, 0, 0."""
+        idx = np.asarray(idx)
+        if idx.dtype != np.int16 or idx.ndim != 2:
+            raise TypeError(f"index_render_i16 takes an int16 raster [H, W], got {idx.dtype} {idx.shape}")
+        idx = np.ascontiguousarray(idx)
+        lut = self._index_lut(lut, "index_render_i16")
+        H, W = idx.shape
+        out = pinned_pool.empty((H, W, 4), np.uint8) if H > 0 and W > 0 else np.empty((1,), np.uint8)
+        self._check(self._lib.s2sr_index_render_i16(self._h, _ptr(idx), H, W, _ptr(lut), int(band_rows), _ptr(out)), "s2sr_index_render_i16")
+        return out
 
     # -- multi-GPU building blocks (device pointers) ------------------------------------------
     def cut_windows_u8_dev(self, d_img: int, H: int, W: int, tile: int, pad: int, first: int, count: int,

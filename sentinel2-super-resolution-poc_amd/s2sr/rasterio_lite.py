@@ -556,16 +556,32 @@ def write_geotiff_u16(path: Path, bands: np.ndarray, georef: GeoRef, nodata=None
     """uint16 [H, W, B], any B >= 1: the B-band sibling of `write_geotiff_rgb16` -- SamplesPerPixel B, chunky little-endian samples,
     LZW strips through the same native encoder, the same geo tags.  B = 3 IS write_geotiff_rgb16 (the same bytes).  B >= 4: RGB and
     B - 3 unspecified ExtraSamples; B = 1, 2: BlackIsZero (B = 2: one ExtraSample)."""
-    import struct
-
-    from . import hostpool, native
-
     bands = np.asarray(bands)
     if bands.ndim != 3 or bands.shape[2] < 1 or bands.dtype != np.uint16:
         raise ValueError(f"expected HxWxB uint16, got {bands.shape} {bands.dtype}")
     if bands.shape[2] == 3:
         return write_geotiff_rgb16(path, bands, georef, rows_per_strip, nodata)
-    bands = np.ascontiguousarray(bands.astype("<u2", copy=False))
+    _write_geotiff_16(path, bands, georef, nodata, rows_per_strip, 1)
+
+
+def write_geotiff_i16(path: Path, band: np.ndarray, georef: GeoRef, nodata=None, rows_per_strip: int = 64) -> None:
+    """int16 [H, W] or [H, W, B]: `write_geotiff_u16` with SampleFormat 2 (two's complement) -- the index rasters of app.wow_sr,
+    whose GDAL_NODATA is -32768.  `read_bands_raw` hands the samples back as int16."""
+    band = np.asarray(band)
+    if band.ndim == 2:
+        band = band[..., None]
+    if band.ndim != 3 or band.shape[2] < 1 or band.dtype != np.int16:
+        raise ValueError(f"expected HxW or HxWxB int16, got {band.shape} {band.dtype}")
+    _write_geotiff_16(path, band, georef, nodata, rows_per_strip, 2)
+
+
+def _write_geotiff_16(path: Path, bands: np.ndarray, georef: GeoRef, nodata, rows_per_strip: int, sample_format: int) -> None:
+    """the body of the two writers above: 16-bit chunky little-endian samples of SampleFormat 1 (unsigned) or 2 (signed)"""
+    import struct
+
+    from . import hostpool, native
+
+    bands = np.ascontiguousarray(bands.astype("<u2" if sample_format == 1 else "<i2", copy=False))
     h, w, nb = bands.shape
     strips = [(y, min(h, y + rows_per_strip)) for y in range(0, h, rows_per_strip)]
     offs, sizes, pos = [], [], 8
@@ -584,7 +600,7 @@ def write_geotiff_u16(path: Path, bands: np.ndarray, georef: GeoRef, nodata=None
                     raise ValueError("output exceeds the 4 GiB of a classic TIFF")
             colour = 3 if nb >= 4 else 1                               # samples the photometric interpretation accounts for
             ent = [(256, 4, (w,)), (257, 4, (h,)), (258, 3, (16,) * nb), (259, 3, (5,)), (262, 3, (2 if nb >= 4 else 1,)), (273, 4, tuple(offs)),
-                   (277, 3, (nb,)), (278, 4, (rows_per_strip,)), (279, 4, tuple(sizes)), (284, 3, (1,)), (339, 3, (1,) * nb)]
+                   (277, 3, (nb,)), (278, 4, (rows_per_strip,)), (279, 4, tuple(sizes)), (284, 3, (1,)), (339, 3, (sample_format,) * nb)]
             if nb > colour:
                 ent.append((338, 3, (0,) * (nb - colour)))             # ExtraSamples: unspecified data
             for tag, val in georef.tags.items():
