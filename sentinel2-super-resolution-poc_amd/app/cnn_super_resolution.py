@@ -20,7 +20,7 @@ import os
 import threading
 import urllib.request
 from pathlib import Path
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -284,6 +284,17 @@ def _resolve_device(device) -> torch.device:
     return dev if dev.index is not None else torch.device("cuda", 0)
 
 
+class Product16(NamedTuple):
+    """What RealESRGAN.product16 makes of one image; a part that was not asked for is None."""
+    out16: np.ndarray                        # uint16 [4H, 4W, 3], always
+    display: Optional[np.ndarray] = None     # display=: uint8 [4H, 4W, 3], the 8-bit rendering of out16
+    info: Optional[dict] = None              # display=: the stretch with the limits it found
+    carried: Optional[np.ndarray] = None     # extra=: uint16 [4H, 4W, k], the carried bands
+    carried_record: Optional[dict] = None    # extra=: their ranges, eps and inexact blocks, the weights and r (RealESRGAN.last_extra)
+    indices: Optional[list] = None           # indices=: one dict per index (native.Engine.index_nd_u16)
+    inexact_blocks: Optional[list] = None    # consistency: the blocks per band a clip kept off (RealESRGAN.last_inexact_blocks)
+
+
 class RealESRGAN:
     """Real-ESRGAN inference wrapper with the reference's interface (:161-280)."""
 
@@ -410,27 +421,28 @@ class RealESRGAN:
             self.last_inexact_blocks = [int(v) for v in r.inexact]
         return r.q
 
-    def enhance16(self, img: np.ndarray, value_range=None, display=None, valid=None, nodata=None, fill_radius: int = 32, extra=None,
-                  extra_range=None, extra_weights=None, indices=None):
-        """HxWx3 uint16 (channel order as given) -> 4Hx4Wx3 uint16, in the source's units: the 16-bit door of the native library
-        (upstream RealESRGANer's max_range = 65535 branch; the reference has none).  value_range (lo, hi), None = (0, 65535): the
-        net sees (clip(v, lo, hi) - lo) / (hi - lo), the output is lo + rint(clip(y, 0, 1) * (hi - lo)).  Same whole / tiled
-        switch and window plan as `enhance`.  The x4 RRDB models only (realesrgan_x4, realesrgan_anime).
-        display (a s2sr.display.Stretch or a dict of its fields): -> (out16, display_u8, info), the 8-bit display rendering of the
-        output (percentile stretch, s2sr/display.py) made from the output's device copy, without a second upload; per-band
-        limits are in the channel order of `img`.
+    def product16(self, img: np.ndarray, value_range=None, display=None, valid=None, nodata=None, fill_radius: int = 32, extra=None,
+                  extra_range=None, extra_weights=None, indices=None) -> "Product16":
+        """HxWx3 uint16 (channel order as given) -> Product16, whose out16 is 4Hx4Wx3 uint16 in the source's units: the 16-bit door
+        of the native library (upstream RealESRGANer's max_range = 65535 branch; the reference has none).  value_range (lo, hi),
+        None = (0, 65535): the net sees (clip(v, lo, hi) - lo) / (hi - lo), the output is lo + rint(clip(y, 0, 1) * (hi - lo)).
+        Same whole / tiled switch and window plan as `enhance`.  The x4 RRDB models only (realesrgan_x4, realesrgan_anime).
+        display (a s2sr.display.Stretch or a dict of its fields): .display and .info, the 8-bit display rendering of the output
+        (percentile stretch, s2sr/display.py) made from the output's device copy, without a second upload; per-band limits are in
+        the channel order of `img`.
         valid / nodata / fill_radius: as `enhance`; a display stretch that names no nodata of its own leaves the job's out of its
         statistics.
         extra (HxWxk uint16): bands the net never saw, carried to the output grid against the output's device copy
         (native.Engine.carry_band_u16: guided upsampling, then block means that reproduce the band), behind the door and in front of
-        the display rendering, under the call's mask.  The carried 4Hx4Wxk array comes back as one more, last, return value.
-        extra_range: one (lo, hi) or one per band; None: each band's own min and max over the valid pixels.  extra_weights: the
-        three guide weights in the channel order of `img` (None: 1, 1, 1).  last_extra: the ranges, eps and inexact blocks per band.
+        the display rendering, under the call's mask: .carried (4Hx4Wxk) and .carried_record (the ranges, eps and inexact blocks per
+        band; also kept as last_extra).  extra_range: one (lo, hi) or one per band; None: each band's own min and max over the
+        valid pixels.  extra_weights: the three guide weights in the channel order of `img` (None: 1, 1, 1).
         indices: normalised-difference indices on the output grid, a list of {"a", "b", "offset", "L", "K", "lut",
         "zones", "zone_scale", "Z"} with a and b either ("img", channel of `img`) -- read from the output's device copy -- or
         ("extra", i) -- the i-th carried band; lut (uint8 [65536][4]) and zones (uint16 labels, with zone_scale and Z) may be None.
-        Under the call's mask.  One more, last, return value: per index {"index" int16 [4H, 4W], "hist", "undefined"} and, with a
-        lut / zones, "rgba" / "zonal" (native.Engine.index_nd_u16)."""
+        Under the call's mask.  .indices: per index {"index" int16 [4H, 4W], "hist", "undefined"} and, with a lut / zones, "rgba" /
+        "zonal" (native.Engine.index_nd_u16).
+        .inexact_blocks: with consistency, the blocks per band a clip kept off (also kept as last_inexact_blocks)."""
         if self.scale != 4 or getattr(self.model, "arch", "rrdb") != "rrdb":
             raise ValueError(f"enhance16 is built for the x4 RRDB models, not {self.model_name}")
         if img.ndim != 3 or img.shape[2] != 3:
@@ -443,23 +455,46 @@ class RealESRGAN:
         valid, out_nodata = self._mask_of(img, valid, nodata, fill_radius)
         plan = None if extra is None else self._extra_plan(img, extra, extra_range, extra_weights, valid, out_nodata)
         iplan = None if indices is None else self._index_plan(indices, 0 if extra is None else np.asarray(extra).shape[2])
-        if display is None:
-            with self._engine.chain_lock:
-                out16 = self._door(img, valid, fill_radius, out_nodata, lo=lo, hi=hi)
-                carried = None if plan is None else self._carry_extra(plan)
-                res = (out16,) + (() if plan is None else (carried,)) + (() if iplan is None else (self._run_indices(iplan, out16, carried, valid),))
-                return res[0] if len(res) == 1 else res
-        from s2sr.display import Stretch, render_u16
-        stretch = Stretch.of(display)
-        if nodata is not None and stretch.nodata is None:
-            import dataclasses
-            stretch = dataclasses.replace(stretch, nodata=out_nodata)
-        with self._engine.chain_lock:        # the engine is shared by every job of the process: nothing between the door and the rendering
+        stretch = None
+        if display is not None:
+            from s2sr.display import Stretch, render_u16
+            stretch = Stretch.of(display)
+            if nodata is not None and stretch.nodata is None:
+                import dataclasses
+                stretch = dataclasses.replace(stretch, nodata=out_nodata)
+        disp = info = carried = record = found = None
+        with self._engine.chain_lock:        # the engine is shared by every job of the process: nothing between the door and its readers
             out16 = self._door(img, valid, fill_radius, out_nodata, lo=lo, hi=hi)
-            carried = None if plan is None else self._carry_extra(plan)      # (it leaves the device copy as the door left it)
-            disp, info = render_u16(None, stretch, self._engine, shape=out16.shape[:2])
-            found = None if iplan is None else self._run_indices(iplan, out16, carried, valid)      # (behind the rendering: see there)
-        return (out16, disp, info) + (() if plan is None else (carried,)) + (() if iplan is None else (found,))
+            if plan is not None:             # (it leaves the device copy as the door left it)
+                carried = self._carry_extra(plan)
+                record = self.last_extra
+            if stretch is not None:
+                disp, info = render_u16(None, stretch, self._engine, shape=out16.shape[:2])
+            if iplan is not None:            # (behind the rendering: see _run_indices)
+                found = self._run_indices(iplan, out16, carried, valid)
+            inexact = self.last_inexact_blocks if self._cmode else None
+        return Product16(out16, disp, info, carried, record, found, inexact)
+
+    def enhance16(self, img: np.ndarray, value_range=None, display=None, valid=None, nodata=None, fill_radius: int = 32, extra=None,
+                  extra_range=None, extra_weights=None, indices=None):
+        """`product16` (same arguments, see there) flattened into a bare array or a tuple of the parts that were asked for:
+
+        | display | extra | indices | returns                                   |
+        |---------|-------|---------|-------------------------------------------|
+        | -       | -     | -       | out16 (a bare array)                      |
+        | -       | yes   | -       | (out16, carried)                          |
+        | -       | -     | yes     | (out16, indices)                          |
+        | -       | yes   | yes     | (out16, carried, indices)                 |
+        | yes     | -     | -       | (out16, display, info)                    |
+        | yes     | yes   | -       | (out16, display, info, carried)           |
+        | yes     | -     | yes     | (out16, display, info, indices)           |
+        | yes     | yes   | yes     | (out16, display, info, carried, indices)  |
+
+        carried_record and inexact_blocks are not in the tuple: read last_extra and last_inexact_blocks, or call product16."""
+        p = self.product16(img, value_range, display, valid, nodata, fill_radius, extra, extra_range, extra_weights, indices)
+        res = (p.out16,) + (() if display is None else (p.display, p.info)) + (() if extra is None else (p.carried,)) + \
+              (() if indices is None else (p.indices,))
+        return res[0] if len(res) == 1 else res
 
     @staticmethod
     def _index_plan(indices, k: int) -> list:

@@ -12,6 +12,7 @@ from typing import Tuple
 import numpy as np
 
 from app.cnn_super_resolution import RealESRGAN
+from app.job_options import JobOptions
 from app.wow_sr import _pp_engine
 from s2sr import native
 
@@ -48,9 +49,10 @@ def apply_farm_sr(input_path: Path, output_path: Path, scale: int = 4, seam_blen
     consistency (not in the reference): None, "exact" or "smooth", see app.wow_sr.apply_wow_sr; the farm steps
     always follow the pass, so the metadata block says "applied_before": "post_process"."""
     from s2sr import rasterio_lite as rio
-    from s2sr.consistency import check_args as check_consistency, metadata_block
+    from s2sr.consistency import metadata_block
 
-    check_consistency(consistency)                                   # before anything is created
+    o = JobOptions(seam_blend=seam_blend, consistency=consistency)
+    o.check_option("consistency")                                    # before anything is created
 
     print(f"\nFarm Super-Resolution x{scale}\n   Input: {input_path}")
     input_path = Path(input_path)
@@ -61,8 +63,7 @@ def apply_farm_sr(input_path: Path, output_path: Path, scale: int = 4, seam_blen
     import os
     from app.cnn_super_resolution import thread_precision
     with thread_precision(os.environ.get("S2SR_FARM_PRECISION") or None):
-        esrgan = RealESRGAN(scale=scale, tile_size=256, **({"seam_blend": True} if seam_blend else {}),
-                            **({"consistency": consistency} if consistency is not None else {}))
+        esrgan = RealESRGAN(scale=scale, tile_size=256, **o.passed("RealESRGAN"))
         if hasattr(esrgan, "enhance_job"):      # RGB2BGR -> net -> BGR2RGB -> the three steps of :170-178, one native call
             final = esrgan.enhance_job(img, native.pp_farm())
         else:
@@ -103,8 +104,8 @@ def process_farm_sr(input_tif: Path, output_dir: Path, scale: int = 4, seam_blen
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
     sr_tif = output_dir / f"{base_name}_farm_sr_x{scale}.tif"
-    _, sr_metadata = apply_farm_sr(input_path=input_tif, output_path=sr_tif, scale=scale, **({"seam_blend": True} if seam_blend else {}),
-                                   **({"consistency": consistency} if consistency is not None else {}))
+    _, sr_metadata = apply_farm_sr(input_path=input_tif, output_path=sr_tif, scale=scale,
+                                   **JobOptions(seam_blend=seam_blend, consistency=consistency).passed("apply_farm_sr"))
     png = sr_tif.with_suffix(".png")
     result = {
         "timestamp": datetime.now().strftime("%Y%m%d_%H%M%S"),

@@ -23,6 +23,8 @@ from typing import Callable, List, Optional, Union
 from fastapi import BackgroundTasks, FastAPI, HTTPException, Request
 from pydantic import BaseModel
 
+from app.job_options import JobOptions
+
 MAX_UPLOAD_BYTES = 50 * 1024 * 1024          # main.py:68 (settings.max_upload_bytes default)
 
 
@@ -223,19 +225,23 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                 _default_tiler(Path(e["files"]["tif"]), data_dir / f"{sub}_{e['name']}", ramp=[tuple(st) for st in e["ramp"]])
                 result.setdefault("index_tiles", {})[e["name"]] = str(data_dir / f"{sub}_{e['name']}")
 
-    def _check_consistency(value):                                           # an unknown mode is a 400, before a job exists
+    def _refuse(detail):                                                     # a bad option is a 400, before a job exists
+        raise HTTPException(status_code=400, detail=detail)
+
+    def _checked(opts, name, band_count=None, prefix="", errors=ValueError):
+        """one option's own refusals (JobOptions.check_option) as a 400; band_count: a callable, so a file that cannot be read is
+        refused here too, and only when this option is reached"""
         try:
-            from s2sr.consistency import check_args
-            check_args(value)
-        except ValueError as e:
-            raise HTTPException(status_code=400, detail=str(e))
+            opts.check_option(name, None if band_count is None else band_count())
+        except errors as e:
+            _refuse(f"{prefix}{e}")
 
     def run_sr_job(job_id, input_file, scale, model, output_dir, seam_blend=False, consistency=None):          # main.py:247-287
         try:
             _set(job_id, status="processing", message=f"Applying {model.upper()} x{scale} super-resolution...")
             from app.farm_sr import process_farm_sr                          # `model` is ignored, as in the reference
-            result = process_farm_sr(input_tif=input_file, output_dir=output_dir, scale=scale, **({"seam_blend": True} if seam_blend else {}),
-                                     **({"consistency": consistency} if consistency is not None else {}))
+            result = process_farm_sr(input_tif=input_file, output_dir=output_dir, scale=scale,
+                                     **JobOptions(seam_blend=seam_blend, consistency=consistency).passed("process_farm_sr"))
             _set(job_id, status="tiling", message="Generating tiles from SR image...")
             _tile(result, "tiles_sr")
             _set(job_id, status="completed", message="Super-resolution complete!", result=result)
@@ -246,6 +252,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                     max_cloud_cover=30.0, force_fetch=False, model="realesrgan_x4", seam_blend=False, bit_depth=8,
                     display=None, nodata=None, fill_radius=32, consistency=None, extra_bands=None, transparent_tiles=False, indices=None,
                     index_offset=0):   # main.py:290-368
+        opts = JobOptions(seam_blend=seam_blend, bit_depth=bit_depth, display=display, nodata=nodata, fill_radius=fill_radius, consistency=consistency,
+                          extra_bands=extra_bands, transparent_tiles=transparent_tiles, indices=indices, index_offset=index_offset)
         try:
             if input_file is None and auto_fetch:
                 _set(job_id, status="fetching",
@@ -259,28 +267,15 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                              "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)"}.get(model, model)
             _set(job_id, status="processing", message=f"Stage 1/2: {model_display} (GAN upscaling)...")
             from app.wow_sr import process_wow_sr
-            extra = {"seam_blend": True} if seam_blend else {}
-            if bit_depth != 8:
-                extra["bit_depth"] = bit_depth
-            if display is not None:
-                extra["display"] = display
-            if nodata is not None:
-                extra.update(nodata=nodata, fill_radius=fill_radius)
-            if consistency is not None:
-                extra["consistency"] = consistency
-            if extra_bands is not None:
-                extra["extra_bands"] = extra_bands
-            if indices is not None:
-                extra.update(indices=indices, index_offset=index_offset)
-            result = process_wow_sr(input_tif=input_file, output_dir=output_dir, enhance_crops=enhance_crops, model=model, **extra)
+            result = process_wow_sr(input_tif=input_file, output_dir=output_dir, enhance_crops=enhance_crops, model=model, **opts.passed("process_wow_sr"))
             _set(job_id, status="tiling", message="Generating tiles from WOW SR image...")
             # a 16-bit job's tiles show the rendering of its PNG: the job's stretch with the limits it found
-            info = result.get("sr_metadata", {}).get("display") if display is not None else None
+            info = result.get("sr_metadata", {}).get("display") if opts.display is not None else None
             mask = None
-            if transparent_tiles and nodata is not None:
+            if opts.transparent_tiles and opts.nodata is not None:
                 # the job's own mask (input resolution; the warp reads it at the SR scale); the value is the one its GeoTIFF declares
                 from app.wow_sr import input_mask
-                mask = (input_mask(input_file, nodata, bit_depth), 4, "tag")
+                mask = (input_mask(input_file, opts.nodata, opts.bit_depth), 4, "tag")
             _tile(result, "tiles_wow", stretch=None if info is None else
                   {k: info[k] for k in ("p_lo", "p_hi", "linked", "gamma", "nodata", "limits")}, mask=mask)
             _set(job_id, status="completed", message="WOW Super-resolution complete!", result=result)
@@ -301,7 +296,8 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             raise HTTPException(status_code=400, detail="Scale must be 2, 3, or 4")
         if request.model not in ["edsr", "espcn", "lapsrn"]:
             raise HTTPException(status_code=400, detail="Model must be edsr, espcn, or lapsrn")
-        _check_consistency(request.consistency)
+        opts = JobOptions.from_request(request)
+        _checked(opts, "consistency")
         job_id = datetime.now().strftime("%Y%m%d_%H%M%S")
         output_dir = data_dir / "sr" / job_id
         output_dir.mkdir(parents=True, exist_ok=True)
@@ -309,9 +305,7 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             sr_jobs[job_id] = {"status": "queued", "message": "Job queued", "input_file": str(input_file),
                                "scale": request.scale, "model": request.model, "output_dir": str(output_dir),
                                "created_at": datetime.now().isoformat()}
-        background_tasks.add_task(run_sr_job, job_id, input_file, request.scale, request.model, output_dir,
-                                  **({"seam_blend": True} if request.seam_blend else {}),
-                                  **({"consistency": request.consistency} if request.consistency is not None else {}))
+        background_tasks.add_task(run_sr_job, job_id, input_file, request.scale, request.model, output_dir, **opts.passed("run_sr_job"))
         return SRResponse(job_id=job_id, status="queued", message=f"SR job started: {input_file.name} -> x{request.scale}")
 
     @app.get("/api/sr/{job_id}")                                             # main.py:437-443
@@ -338,51 +332,36 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
             if input_file is None:
                 raise HTTPException(status_code=404,
                                     detail="No GeoTIFF files found. Enable auto_fetch=true or run fetch first.")
-        if request.bit_depth not in (8, 16):
-            raise HTTPException(status_code=400, detail="bit_depth must be 8 or 16")
-        if request.display is not None:
-            if request.bit_depth != 16:
-                raise HTTPException(status_code=400, detail="display is the 8-bit rendering of a 16-bit job: pass bit_depth=16")
-            try:
-                from s2sr.display import Stretch
-                Stretch.of(request.display)
-            except (ValueError, TypeError) as e:
-                raise HTTPException(status_code=400, detail=f"display: {e}")
-        if request.nodata is not None:
-            try:
-                from s2sr.nodata import check_args
-                check_args(request.nodata, request.fill_radius)
-            except ValueError as e:
-                raise HTTPException(status_code=400, detail=str(e))
-        if request.transparent_tiles and request.nodata is None:
-            raise HTTPException(status_code=400, detail="transparent_tiles shows the map through the job's nodata pixels: pass nodata")
-        _check_consistency(request.consistency)
-        if request.extra_bands is not None:
-            if request.bit_depth != 16:
-                raise HTTPException(status_code=400, detail="extra_bands are carried on the 16-bit path: pass bit_depth=16")
-            try:
-                from s2sr.bands import select_bands
-                count = None
-                if input_file is not None:                                   # the file is at hand: its band count too
-                    from s2sr import rasterio_lite as rio
-                    count = rio.read_bands_raw(input_file)[0].shape[2]
-                select_bands(request.extra_bands, count)
-            except ValueError as e:
-                raise HTTPException(status_code=400, detail=str(e))
-        if request.indices is not None:
-            if request.bit_depth != 16:
-                raise HTTPException(status_code=400, detail="indices are computed on the 16-bit path: pass bit_depth=16")
-            try:
-                from s2sr.index import resolve
-                count = None
-                if input_file is not None:
-                    from s2sr import rasterio_lite as rio
-                    count = rio.read_bands_raw(input_file)[0].shape[2]
-                resolve(request.indices, request.index_offset, count)
-            except ValueError as e:
-                raise HTTPException(status_code=400, detail=str(e))
-        elif request.index_offset != 0:
-            raise HTTPException(status_code=400, detail="index_offset belongs to indices: pass indices")
+        # the refusals of JobOptions.check in the route's own order; where a text differs from the job functions', it is the route's
+        opts = JobOptions.from_request(request)
+        count = []
+
+        def band_count():                                                    # the file is at hand: its band count too, read once
+            if input_file is not None and not count:
+                from s2sr import rasterio_lite as rio
+                count.append(rio.read_bands_raw(input_file)[0].shape[2])
+            return count[0] if count else None
+        if opts.bit_depth not in (8, 16):
+            _refuse("bit_depth must be 8 or 16")
+        if opts.display is not None:
+            if opts.bit_depth != 16:
+                _refuse("display is the 8-bit rendering of a 16-bit job: pass bit_depth=16")
+            _checked(opts, "display", prefix="display: ", errors=(ValueError, TypeError))
+        if opts.nodata is not None:
+            _checked(opts, "nodata")
+        if opts.transparent_tiles and opts.nodata is None:
+            _refuse("transparent_tiles shows the map through the job's nodata pixels: pass nodata")
+        _checked(opts, "consistency")
+        if opts.extra_bands is not None:
+            if opts.bit_depth != 16:
+                _refuse("extra_bands are carried on the 16-bit path: pass bit_depth=16")
+            _checked(opts, "extra_bands", band_count)
+        if opts.indices is not None:
+            if opts.bit_depth != 16:
+                _refuse("indices are computed on the 16-bit path: pass bit_depth=16")
+            _checked(opts, "indices", band_count)
+        elif opts.index_offset != 0:
+            _refuse("index_offset belongs to indices: pass indices")
         job_id = f"wow_{datetime.now().strftime('%Y%m%d_%H%M%S')}"
         output_dir = data_dir / "wow" / job_id
         output_dir.mkdir(parents=True, exist_ok=True)
@@ -394,15 +373,7 @@ def create_app(data_dir: Path, source_dir: Optional[Path] = None, fetcher: Optio
                                "max_age_days": request.max_age_days, "max_cloud_cover": request.max_cloud_cover,
                                "output_dir": str(output_dir), "created_at": datetime.now().isoformat()}
         background_tasks.add_task(run_wow_job, job_id, input_file, output_dir, request.enhance_crops,
-                                  request.auto_fetch, request.max_age_days, request.max_cloud_cover, request.force_fetch,
-                                  **({"seam_blend": True} if request.seam_blend else {}),
-                                  **({"bit_depth": request.bit_depth} if request.bit_depth != 8 else {}),
-                                  **({"display": request.display} if request.display is not None else {}),
-                                  **({"nodata": request.nodata, "fill_radius": request.fill_radius} if request.nodata is not None else {}),
-                                  **({"consistency": request.consistency} if request.consistency is not None else {}),
-                                  **({"extra_bands": request.extra_bands} if request.extra_bands is not None else {}),
-                                  **({"transparent_tiles": True} if request.transparent_tiles else {}),
-                                  **({"indices": request.indices, "index_offset": request.index_offset} if request.indices is not None else {}))
+                                  request.auto_fetch, request.max_age_days, request.max_cloud_cover, request.force_fetch, **opts.passed("run_wow_job"))
         msg = (f"WOW SR started: {input_file.name} -> Real-ESRGAN x4 + Enhanced" if input_file else
                f"WOW SR started: auto-fetching best image (last {request.max_age_days}d, cloud <={request.max_cloud_cover}%)")
         return SRResponse(job_id=job_id, status="queued", message=msg)

@@ -11,6 +11,7 @@ from typing import Tuple
 import numpy as np
 
 from app.cnn_super_resolution import RealESRGAN
+from app.job_options import JobOptions
 from s2sr import native
 
 _PP_LOCK = threading.Lock()
@@ -33,6 +34,11 @@ def _enhance_for_crops(img: np.ndarray) -> np.ndarray:
     """CLAHE(2.5, 8x8) on L -> unsharp (sigma 1.2, 1.4/-0.4) -> saturation x1.2 on hue 36..84
     (reference wow_sr.py:187-209): HxWx3 uint8 RGB -> same, one fused GPU pass sequence."""
     return _pp_engine().postprocess_u8(img, native.pp_wow())
+
+
+def _alpha_of(valid, scale: int) -> dict:
+    """What a PNG writer gets of a nodata job's mask (a job without one: nothing, the call as ever)."""
+    return {} if valid is None else {"valid": valid, "valid_scale": scale}
 
 
 def _nodata_block(value, valid: np.ndarray, fill_radius: int) -> dict:
@@ -68,19 +74,17 @@ def input_mask(input_path: Path, nodata, bit_depth: int = 8) -> np.ndarray:
     return read_masked(input_path, nodata, bit_depth)[2]
 
 
-def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend: bool = False, display=None,
-                    enhance_crops: bool = False, nodata=None, fill_radius: int = 32, consistency=None, extra_bands=None,
-                    extra_weights=None, indices=None, index_offset: int = 0, zones=None) -> Tuple[Path, dict]:
-    """bit_depth=16 of apply_wow_sr: a uint16 GeoTIFF read raw, value_range = the image's own (min, max) -- the reference's
-    min-max (wow_sr.py:67-73) minus its quantisation to 8 bits -- the net fed BGR as ever (:85,94), RealESRGAN.enhance16, RGB back,
-    a uint16 GeoTIFF out.  Without `display`: no PNG (the encoder is 8-bit) and no crop-visibility post-process (OpenCV's 8-bit
+def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_crops: bool, o: JobOptions) -> Tuple[Path, dict]:
+    """bit_depth=16 of apply_wow_sr (o: the job's options, checked; its fields are named below): a uint16 GeoTIFF read raw,
+    value_range = the image's own (min, max) -- the reference's min-max (wow_sr.py:67-73) minus its quantisation to 8 bits -- the
+    net fed BGR as ever (:85,94), RealESRGAN.product16, RGB back, a uint16 GeoTIFF out.  Without `display`: no PNG (the encoder is 8-bit) and no crop-visibility post-process (OpenCV's 8-bit
     arithmetic).  With it (s2sr.display.Stretch or a dict of its fields): the output's display rendering, made on the device from
     the output's copy there, is written as the PNG, after the crop-visibility post-process when enhance_crops; the GeoTIFF stays raw.
     nodata (an integer, or "tag"): see apply_wow_sr; the value range is that of the valid pixels (s2sr.nodata.valid_range), the
     GeoTIFF declares the value, the PNG (with `display`) carries the mask as alpha, and the stretch leaves the value out of its
     statistics unless it names a nodata of its own.
     extra_bands ("all" or band numbers from 4 on): those bands of the file are carried to the output grid against the
-    super-resolved image (RealESRGAN.enhance16(extra=...)), each with its own min-max over the valid pixels as its range, and the
+    super-resolved image (RealESRGAN.product16(extra=...)), each with its own min-max over the valid pixels as its range, and the
     GeoTIFF holds 3 + k bands: RGB as without the option, then the carried bands in the order given.  extra_weights: the guide
     weights in R, G, B terms (None: 1, 1, 1).
     indices, index_offset, zones (s2sr/index.py): spectral indices on the output grid -- a list of preset names
@@ -95,67 +99,57 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
 
     from s2sr import rasterio_lite as rio
     from s2sr.display import Stretch
-    stretch = None if display is None else Stretch.of(display)
+    stretch = None if o.display is None else Stretch.of(o.display)
 
     input_path = Path(input_path)
     print(f"\nWOW Super-Resolution ({model}, 16-bit)\n   Input: {input_path}")
-    img, georef, valid, value = read_masked(input_path, nodata, 16)
+    img, georef, valid, value = read_masked(input_path, o.nodata, 16)
     extra = numbers = defs = None
-    if extra_bands is not None or indices is not None:
+    if o.extra_bands is not None or o.indices is not None:
         from s2sr import bands as xb
         try:
             every, _ = rio.read_bands_raw(input_path)
         except ValueError as e:
-            raise ValueError(f"{'extra_bands' if extra_bands is not None else 'indices'} needs a GeoTIFF whose bands share one uint16 layout: {e}") from e
-        listed = [] if extra_bands is None else xb.select_bands(extra_bands, every.shape[2])
+            raise ValueError(f"{'extra_bands' if o.extra_bands is not None else 'indices'} needs a GeoTIFF whose bands share one uint16 layout: {e}") from e
+        listed = [] if o.extra_bands is None else xb.select_bands(o.extra_bands, every.shape[2])
         numbers = list(listed)                                    # the carried bands: the listed ones, then what only an index reads
-        if indices is not None:
+        if o.indices is not None:
             from s2sr import index as xi
-            defs = xi.resolve(indices, index_offset, every.shape[2])
+            defs = xi.resolve(o.indices, o.index_offset, every.shape[2])
             numbers += [b for b in xi.carried_bands(defs) if b not in numbers]
-            label = None if zones is None else xi.check_zones(rio.read_bands_raw(zones)[0] if isinstance(zones, (str, Path)) else zones, img.shape[:2], 4)
+            label = None if o.zones is None else xi.check_zones(rio.read_bands_raw(o.zones)[0] if isinstance(o.zones, (str, Path)) else o.zones,
+                                                                 img.shape[:2], 4)
         if numbers:
             extra = np.ascontiguousarray(every[:, :, [b - 1 for b in numbers]])
         del every
-        w_rgb = xb.check_args(4, 0, 65535, xb.WEIGHTS if extra_weights is None else extra_weights)["weights"]
+        w_rgb = xb.check_args(4, 0, 65535, xb.WEIGHTS if o.extra_weights is None else o.extra_weights)["weights"]
     from s2sr.nodata import valid_range
     lo, hi = valid_range(img, valid)
-    mask_kw = {} if valid is None else {"valid": valid, "nodata": value, "fill_radius": fill_radius}
-    esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}),
-                        **({"consistency": consistency} if consistency is not None else {}))
-    display_rgb = info = carried = None
+    call = {} if valid is None else {"valid": valid, "nodata": value, "fill_radius": o.fill_radius}
+    tagged = {} if valid is None else {"nodata": value}                                  # what the GeoTIFF writers get
+    esrgan = RealESRGAN(model_name=model, tile_size=256, **o.passed("RealESRGAN"))
     if extra is not None:            # the device copy is BGR: the guide weights go in reversed
-        mask_kw = dict(mask_kw, extra=extra, extra_weights=w_rgb[::-1])
-    found = None
+        call.update(extra=extra, extra_weights=w_rgb[::-1])
     if defs is not None:             # file band 1, 2, 3 is channel 2, 1, 0 of the device copy; a band from 4 on is one of the carried
         side = lambda b: ("img", 3 - b) if b <= 3 else ("extra", numbers.index(b))
         ramps = [xi.ramp_for(xi.DEFAULT_RAMP.get(d["preset"], "diverging"), d["K"]) for d in defs]
-        mask_kw = dict(mask_kw, indices=[dict(a=side(d["a"]), b=side(d["b"]), offset=d["offset"], L=d["L"], K=d["K"], lut=xi.ramp_lut(r),
-                                              **({} if label is None else {"zones": label[0], "zone_scale": label[1], "Z": label[2]}))
-                                         for d, r in zip(defs, ramps)])
-    if stretch is None:
-        out_bgr = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), **mask_kw)
-        if defs is not None:
-            *out_bgr, found = out_bgr
-            out_bgr = out_bgr[0] if len(out_bgr) == 1 else tuple(out_bgr)
-        if extra is not None:
-            out_bgr, carried = out_bgr
-    else:
+        zoned = {} if label is None else {"zones": label[0], "zone_scale": label[1], "Z": label[2]}
+        call["indices"] = [dict(a=side(d["a"]), b=side(d["b"]), offset=d["offset"], L=d["L"], K=d["K"], lut=xi.ramp_lut(r), **zoned)
+                           for d, r in zip(defs, ramps)]
+    if stretch is not None:
         # the device copy is BGR like the net's input: explicit per-band limits go in reversed, the info's come back reversed
-        bgr = stretch if stretch.limits is None else dataclasses.replace(stretch, limits=stretch.limits[::-1])
-        out_bgr, disp_bgr, info, *rest = esrgan.enhance16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), display=bgr, **mask_kw)
-        if defs is not None:
-            found = rest.pop()
-        carried = rest[0] if rest else None
-        display_rgb = np.ascontiguousarray(disp_bgr[:, :, ::-1])
-        info = dict(info, limits=info["limits"][::-1])
+        call["display"] = stretch if stretch.limits is None else dataclasses.replace(stretch, limits=stretch.limits[::-1])
+    got = esrgan.product16(np.ascontiguousarray(img[:, :, ::-1]), value_range=(lo, hi), **call)
+    display_rgb, info, carried, carried_rec, found = None, None, got.carried, got.carried_record, got.indices
+    if stretch is not None:
+        display_rgb = np.ascontiguousarray(got.display[:, :, ::-1])
+        info = dict(got.info, limits=got.info["limits"][::-1])
         if enhance_crops:
             print("   Stage 2/2: Crop visibility enhancement (on the display image)...")
             display_rgb = _enhance_for_crops(display_rgb)
-    output_rgb = np.ascontiguousarray(out_bgr[:, :, ::-1])
+    output_rgb = np.ascontiguousarray(got.out16[:, :, ::-1])
     scale = esrgan.scale
-    inexact = None if consistency is None else esrgan.last_inexact_blocks[::-1]      # (the net's image is B, G, R)
-    carried_rec = esrgan.last_extra if carried is not None else None
+    inexact = None if o.consistency is None else got.inexact_blocks[::-1]      # (the net's image is B, G, R)
     del esrgan
     final_output = Path(output_path).with_suffix(".tif")
     final_output.parent.mkdir(parents=True, exist_ok=True)
@@ -164,12 +158,11 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
         carried_rec = None if carried is None else {k: (v[:len(listed)] if k in ("ranges", "eps", "inexact") else v) for k, v in carried_rec.items()}
         numbers = listed
     if carried is None:
-        rio.write_geotiff_rgb16(final_output, output_rgb, georef.scaled(scale), **({} if valid is None else {"nodata": value}))
+        rio.write_geotiff_rgb16(final_output, output_rgb, georef.scaled(scale), **tagged)
     else:
-        rio.write_geotiff_u16(final_output, np.concatenate([output_rgb, carried], axis=2), georef.scaled(scale),
-                              **({} if valid is None else {"nodata": value}))
+        rio.write_geotiff_u16(final_output, np.concatenate([output_rgb, carried], axis=2), georef.scaled(scale), **tagged)
     if display_rgb is not None:
-        rio.write_png(final_output.with_suffix(".png"), display_rgb, **({} if valid is None else {"valid": valid, "valid_scale": scale}))
+        rio.write_png(final_output.with_suffix(".png"), display_rgb, **_alpha_of(valid, scale))
     crops = display_rgb is not None and enhance_crops
     metadata = {
         "input_file": str(input_path),
@@ -187,15 +180,15 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
         "bit_depth": 16,
         "value_range": [lo, hi],
     }
-    if seam_blend:
+    if o.seam_blend:
         metadata["seam_blend"] = True
     if info is not None:
         metadata["display"] = info
     if valid is not None:
-        metadata["nodata"] = _nodata_block(value, valid, fill_radius)
-    if consistency is not None:      # the GeoTIFF is the consistent product; the display image and its crop step are renderings of it
+        metadata["nodata"] = _nodata_block(value, valid, o.fill_radius)
+    if o.consistency is not None:      # the GeoTIFF is the consistent product; the display image and its crop step are renderings of it
         from s2sr.consistency import metadata_block
-        metadata["consistency"] = metadata_block(consistency, inexact)
+        metadata["consistency"] = metadata_block(o.consistency, inexact)
     if carried_rec is not None:
         metadata["extra_bands"] = xb.metadata_block(numbers, carried_rec["ranges"], w_rgb, carried_rec["r"], carried_rec["eps"], carried_rec["inexact"])
     if defs is not None:
@@ -209,42 +202,6 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, seam_blend:
             metadata["indices"].append(xi.metadata_entry(d, r["undefined"], stats, ramp, {"tif": str(tif), "png": str(tif.with_suffix(".png"))},
                                                          None if label is None else xi.zonal_table(r["zonal"], d["K"])))
     return final_output, metadata
-
-
-def _check_bit_depth(bit_depth: int, enhance_crops: bool, display=None, nodata=None, fill_radius: int = 32, consistency=None,
-                     extra_bands=None, extra_weights=None, indices=None, index_offset: int = 0, zones=None) -> None:
-    from s2sr.consistency import check_args as check_consistency
-    from s2sr.nodata import check_args
-    check_args(nodata, fill_radius)
-    check_consistency(consistency)
-    if nodata is not None and nodata != "tag" and not 0 <= int(nodata) <= 65535:
-        # (compared with the bands as stored: an 8-bit job of a uint16 raster names the uint16 value)
-        raise ValueError(f"nodata {nodata!r}: an integer in 0..65535")
-    if bit_depth not in (8, 16):
-        raise ValueError(f"bit_depth {bit_depth!r}: 8 or 16")
-    if extra_bands is not None:
-        from s2sr import bands as xb
-        if bit_depth != 16:
-            raise ValueError("extra_bands are carried on the 16-bit path: pass bit_depth=16 (an 8-bit job has no uint16 image to guide them)")
-        xb.select_bands(extra_bands)               # what can be refused without the file: the form, numbers below 4, repeats
-        xb.check_args(4, 0, 65535, xb.WEIGHTS if extra_weights is None else extra_weights)
-    elif extra_weights is not None:
-        raise ValueError("extra_weights are the guide weights of extra_bands: pass extra_bands")
-    if indices is not None:
-        from s2sr import index as xi
-        if bit_depth != 16:
-            raise ValueError("indices are computed on the 16-bit path: pass bit_depth=16 (an 8-bit job has no uint16 product to take them from)")
-        xi.resolve(indices, index_offset)          # what can be refused without the file: presets, names, bands, K, L, offsets
-    elif zones is not None or index_offset != 0:
-        raise ValueError("zones and index_offset belong to indices: pass indices")
-    if display is not None:
-        if bit_depth != 16:
-            raise ValueError("display is the 8-bit rendering of a 16-bit job: pass bit_depth=16 (an 8-bit job's image is its display image)")
-        from s2sr.display import Stretch
-        Stretch.of(display)              # refuses a bad stretch here, before anything is created
-    elif bit_depth == 16 and enhance_crops:
-        raise ValueError("bit_depth=16 has no crop-visibility post-process (it is OpenCV's 8-bit arithmetic by definition): pass enhance_crops=False, "
-                         "or display=... to run it on the display image")
 
 
 def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True,
@@ -273,10 +230,11 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
     next to the GeoTIFF and "indices" in the metadata, and only then."""
     from s2sr import rasterio_lite as rio
 
-    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency, extra_bands, extra_weights, indices, index_offset, zones)
+    o = JobOptions(seam_blend=seam_blend, bit_depth=bit_depth, display=display, nodata=nodata, fill_radius=fill_radius, consistency=consistency,
+                   extra_bands=extra_bands, extra_weights=extra_weights, indices=indices, index_offset=index_offset, zones=zones)
+    o.check(enhance_crops)
     if bit_depth == 16:
-        return _apply_wow_sr16(input_path, output_path, model, seam_blend, display, enhance_crops, nodata, fill_radius, consistency,
-                               extra_bands, extra_weights, **({} if indices is None else {"indices": indices, "index_offset": index_offset, "zones": zones}))
+        return _apply_wow_sr16(input_path, output_path, model, enhance_crops, o)
 
     model_display = {"realesrgan_x4": "Real-ESRGAN x4",
                      "realesrgan_anime": "Real-ESRGAN Anime 6B (text/plates)",
@@ -297,8 +255,7 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
 
     pipeline_stages = []
     print(f"   Stage 1/2: {model_display} (GAN upscaling)...")
-    esrgan = RealESRGAN(model_name=model, tile_size=256, **({"seam_blend": True} if seam_blend else {}),
-                        **({"consistency": consistency} if consistency is not None else {}))
+    esrgan = RealESRGAN(model_name=model, tile_size=256, **o.passed("RealESRGAN"))
     # RGB2BGR -> enhance -> BGR2RGB -> _enhance_for_crops (:85-110) as ONE native call: the 16x image crosses PCIe once
     if enhance_crops:
         print("   Stage 2/2: Crop visibility enhancement...")
@@ -325,10 +282,10 @@ def apply_wow_sr(input_path: Path, output_path: Path, enhance_crops: bool = True
         final_output = output_path.with_suffix(".tif")
         # the two encoders side by side (both are thread pools over strips / bands of the same array)
         rio.write_outputs(output_rgb, output_png, final_output, georef.scaled(scale), remember=True,       # pixel size / scale (:128-135)
-                          **({} if valid is None else {"nodata": out_nodata, "valid": valid, "valid_scale": scale}))
+                          **dict({} if valid is None else {"nodata": out_nodata}, **_alpha_of(valid, scale)))
     else:
         final_output = output_png
-        rio.write_png(output_png, output_rgb, **({} if valid is None else {"valid": valid, "valid_scale": scale}))
+        rio.write_png(output_png, output_rgb, **_alpha_of(valid, scale))
 
     metadata = {
         "input_file": str(input_path),
@@ -361,32 +318,18 @@ def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True
     "sr_png" is None -- unless `display` is given: the PNG is the output's display rendering).  seam_blend, nodata, fill_radius,
     consistency, extra_bands, extra_weights, indices, index_offset, zones: see apply_wow_sr; "outputs" gains "indices": {name: {"tif",
     "png"}} with indices, and only then."""
-    _check_bit_depth(bit_depth, enhance_crops, display, nodata, fill_radius, consistency, extra_bands, extra_weights, indices, index_offset,
-                     zones)   # before anything is created
+    o = JobOptions(seam_blend=seam_blend, bit_depth=bit_depth, display=display, nodata=nodata, fill_radius=fill_radius, consistency=consistency,
+                   extra_bands=extra_bands, extra_weights=extra_weights, indices=indices, index_offset=index_offset, zones=zones)
+    o.check(enhance_crops)       # before anything is created
     output_dir = Path(output_dir)
     output_dir.mkdir(parents=True, exist_ok=True)
     base_name = Path(input_tif).stem
     wow_tif = output_dir / f"{base_name}_wow_sr.tif"
     png = wow_tif.with_suffix(".png")
-    blend = {"seam_blend": True} if seam_blend else {}   # (tests patch apply_wow_sr with the reference's signature)
-    if nodata is not None:
-        blend.update(nodata=nodata, fill_radius=fill_radius)
-    if consistency is not None:
-        blend["consistency"] = consistency
-    if extra_bands is not None:
-        blend["extra_bands"] = extra_bands
-        if extra_weights is not None:
-            blend["extra_weights"] = extra_weights
-    if indices is not None:
-        blend.update(indices=indices, index_offset=index_offset, zones=zones)
-    if bit_depth == 16:
-        if display is not None:
-            blend["display"] = display
-        _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model, bit_depth=16, **blend)
-        if display is None:
-            png = None   # (a PNG an earlier 8-bit job left under this name is not this job's output)
-    else:
-        _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model, **blend)
+    # (tests patch apply_wow_sr with the reference's signature: a plain job names nothing beyond it)
+    _, sr_metadata = apply_wow_sr(input_path=input_tif, output_path=wow_tif, enhance_crops=enhance_crops, model=model, **o.passed("apply_wow_sr"))
+    if bit_depth == 16 and display is None:
+        png = None   # (a PNG an earlier 8-bit job left under this name is not this job's output)
     result = {
         "timestamp": datetime.now().strftime("%Y%m%d_%H%M%S"),
         "input": str(input_tif),

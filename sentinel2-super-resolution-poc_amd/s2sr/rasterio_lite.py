@@ -380,32 +380,18 @@ def write_outputs(rgb: np.ndarray, png_path: Path, tif_path: Path, georef: "GeoR
         raise err[0]
 
 
-def write_geotiff_rgb(path: Path, rgb: np.ndarray, georef: GeoRef, rows_per_strip: int = 64, remember: bool = False, nodata=None) -> None:
-    """uint8 RGB, LZW compressed (compress="lzw", wow_sr.py:138-151) with the geo tags.  Classic
-    little-endian TIFF, chunky RGB strips; the strips are LZW-encoded by the native library on a
-    thread pool (the SR outputs are tens of megapixels; a single-threaded encoder is what a job would
-    otherwise wait for).  remember: the caller will not write to `rgb` again -- a view of it is kept for the stage that reads this
-    file right back (`recall_written`).  nodata (None: no tag, the file as ever): the value the GDAL_NODATA tag declares."""
+def _write_strips(path: Path, h: int, w: int, strip_bytes, georef: GeoRef, rows_per_strip: int, nodata, bits: int, samples: int,
+                  sample_format: int = 1) -> None:
+    """The body of every GeoTIFF writer below: a classic little-endian TIFF of chunky LZW strips (no predictor) with the geo tags.
+    strip_bytes((y0, y1)) -> the uint8 bytes of rows y0..y1, called on the host pool.  bits: per sample; samples: per pixel -- 3 and
+    more are RGB plus unspecified ExtraSamples, 1 and 2 BlackIsZero (2: one ExtraSample); sample_format: 1 unsigned, 2 two's
+    complement.  nodata (None: no tag): the value the GDAL_NODATA tag declares."""
     import os
     import struct
-    from concurrent.futures import ThreadPoolExecutor
 
-    from . import native
+    from . import hostpool, native
 
-    rgb = np.asarray(rgb)
-    if rgb.ndim != 3 or rgb.shape[2] not in (3, 4) or (rgb.shape[2] == 4 and remember):
-        raise ValueError(f"expected HxWx3 (or HxWx4, whose alpha is dropped), got {rgb.shape}")
-    h, w, c = rgb.shape
-    if c == 3:
-        rgb = np.ascontiguousarray(rgb, np.uint8)
-        strip_bytes = lambda s: rgb[s[0]:s[1]].reshape(-1)      # noqa: E731
-    else:
-        # an RGBA raster in hand (the tiler's warp result): its alpha is dropped strip by strip inside the pool -- a whole-image
-        # rgba[..., :3] copy in front of the encoder is one thread moving a gigabyte for a 16k x 16k raster (tools/job_big_probe.py)
-        rgb = rgb if rgb.dtype == np.uint8 else rgb.astype(np.uint8)
-        strip_bytes = lambda s: np.ascontiguousarray(rgb[s[0]:s[1], :, :3]).reshape(-1)      # noqa: E731
     strips = [(y, min(h, y + rows_per_strip)) for y in range(0, h, rows_per_strip)]
-    from . import hostpool
     # the strips go to the file as they come off the pool, in order (the offsets of a strip are known once its predecessors' sizes
     # are): the write loop runs under the encoding of the strips behind it instead of after all of it; the IFD follows the data, and
     # the header's pointer to it is patched in last
@@ -423,8 +409,12 @@ def write_geotiff_rgb(path: Path, rgb: np.ndarray, georef: GeoRef, rows_per_stri
                 pos += len(e) + (len(e) & 1)
                 if pos >= (1 << 32) - (1 << 20):
                     raise ValueError("output exceeds the 4 GiB of a classic TIFF")
-            ent = [(256, 4, (w,)), (257, 4, (h,)), (258, 3, (8, 8, 8)), (259, 3, (5,)), (262, 3, (2,)), (273, 4, tuple(offs)),
-                   (277, 3, (3,)), (278, 4, (rows_per_strip,)), (279, 4, tuple(sizes)), (284, 3, (1,)), (339, 3, (1, 1, 1))]
+            colour = 3 if samples >= 3 else 1                          # samples the photometric interpretation accounts for
+            ent = [(256, 4, (w,)), (257, 4, (h,)), (258, 3, (bits,) * samples), (259, 3, (5,)), (262, 3, (2 if colour == 3 else 1,)),
+                   (273, 4, tuple(offs)), (277, 3, (samples,)), (278, 4, (rows_per_strip,)), (279, 4, tuple(sizes)), (284, 3, (1,)),
+                   (339, 3, (sample_format,) * samples)]
+            if samples > colour:
+                ent.append((338, 3, (0,) * (samples - colour)))        # ExtraSamples: unspecified data
             for tag, val in georef.tags.items():
                 if tag == TAG_GEOKEYS:
                     ent.append((tag, 3, tuple(int(v) for v in val)))
@@ -463,78 +453,45 @@ def write_geotiff_rgb(path: Path, rgb: np.ndarray, georef: GeoRef, rows_per_stri
                 os.unlink(path)            # no half-written GeoTIFF stays behind a failed writer
             except OSError:
                 pass
+
+
+def write_geotiff_rgb(path: Path, rgb: np.ndarray, georef: GeoRef, rows_per_strip: int = 64, remember: bool = False, nodata=None) -> None:
+    """uint8 RGB, LZW compressed (compress="lzw", wow_sr.py:138-151) with the geo tags.  Classic
+    little-endian TIFF, chunky RGB strips; the strips are LZW-encoded by the native library on a
+    thread pool (the SR outputs are tens of megapixels; a single-threaded encoder is what a job would
+    otherwise wait for).  remember: the caller will not write to `rgb` again -- a view of it is kept for the stage that reads this
+    file right back (`recall_written`).  nodata (None: no tag, the file as ever): the value the GDAL_NODATA tag declares."""
+    rgb = np.asarray(rgb)
+    if rgb.ndim != 3 or rgb.shape[2] not in (3, 4) or (rgb.shape[2] == 4 and remember):
+        raise ValueError(f"expected HxWx3 (or HxWx4, whose alpha is dropped), got {rgb.shape}")
+    h, w, c = rgb.shape
+    if c == 3:
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        strip_bytes = lambda s: rgb[s[0]:s[1]].reshape(-1)      # noqa: E731
+    else:
+        # an RGBA raster in hand (the tiler's warp result): its alpha is dropped strip by strip inside the pool -- a whole-image
+        # rgba[..., :3] copy in front of the encoder is one thread moving a gigabyte for a 16k x 16k raster (tools/job_big_probe.py)
+        rgb = rgb if rgb.dtype == np.uint8 else rgb.astype(np.uint8)
+        strip_bytes = lambda s: np.ascontiguousarray(rgb[s[0]:s[1], :, :3]).reshape(-1)      # noqa: E731
+    _write_strips(path, h, w, strip_bytes, georef, rows_per_strip, nodata, bits=8, samples=3)
     if remember:
         _remember_written(path, rgb, georef, nodata)
 
 
+def _write_geotiff_16(path: Path, bands: np.ndarray, georef: GeoRef, nodata, rows_per_strip: int, sample_format: int) -> None:
+    """16-bit chunky little-endian samples [H, W, B] of SampleFormat 1 (uint16) or 2 (int16)"""
+    bands = np.ascontiguousarray(bands.astype("<u2" if sample_format == 1 else "<i2", copy=False))
+    _write_strips(path, bands.shape[0], bands.shape[1], lambda s: bands[s[0]:s[1]].reshape(-1).view(np.uint8), georef, rows_per_strip, nodata,
+                  bits=16, samples=bands.shape[2], sample_format=sample_format)
+
+
 def write_geotiff_rgb16(path: Path, rgb16: np.ndarray, georef: GeoRef, rows_per_strip: int = 64, nodata=None) -> None:
-    """uint16 RGB, the 16-bit sibling of `write_geotiff_rgb`: BitsPerSample 16,16,16, little-endian samples, LZW strips through
-    the same native encoder (no predictor), the same geo tags, classic little-endian TIFF with the IFD behind the data.  nodata:
-    as write_geotiff_rgb."""
-    import struct
-
-    from . import hostpool, native
-
+    """uint16 RGB, the 16-bit sibling of `write_geotiff_rgb`: BitsPerSample 16,16,16, little-endian samples, the same strips, geo
+    tags and nodata."""
     rgb16 = np.asarray(rgb16)
     if rgb16.ndim != 3 or rgb16.shape[2] != 3 or rgb16.dtype != np.uint16:
         raise ValueError(f"expected HxWx3 uint16, got {rgb16.shape} {rgb16.dtype}")
-    rgb16 = np.ascontiguousarray(rgb16.astype("<u2", copy=False))
-    h, w, _ = rgb16.shape
-    strips = [(y, min(h, y + rows_per_strip)) for y in range(0, h, rows_per_strip)]
-    offs, sizes, pos = [], [], 8
-    ok = False
-    try:
-        with open(path, "wb") as f:
-            f.write(b"II" + struct.pack("<HI", 42, 0))
-            for e in hostpool.pool().map(lambda s: native.tiff_lzw_encode(rgb16[s[0]:s[1]].reshape(-1).view(np.uint8)), strips):
-                offs.append(pos)
-                sizes.append(len(e))
-                f.write(e)
-                if len(e) & 1:
-                    f.write(b"\0")
-                pos += len(e) + (len(e) & 1)
-                if pos >= (1 << 32) - (1 << 20):
-                    raise ValueError("output exceeds the 4 GiB of a classic TIFF")
-            ent = [(256, 4, (w,)), (257, 4, (h,)), (258, 3, (16, 16, 16)), (259, 3, (5,)), (262, 3, (2,)), (273, 4, tuple(offs)),
-                   (277, 3, (3,)), (278, 4, (rows_per_strip,)), (279, 4, tuple(sizes)), (284, 3, (1,)), (339, 3, (1, 1, 1))]
-            for tag, val in georef.tags.items():
-                if tag == TAG_GEOKEYS:
-                    ent.append((tag, 3, tuple(int(v) for v in val)))
-                elif tag == TAG_GEOASCII:
-                    ent.append((tag, 2, val if isinstance(val, str) else str(val)))
-                else:
-                    ent.append((tag, 12, tuple(float(v) for v in val)))
-            if nodata is not None:
-                ent.append((TAG_GDAL_NODATA, 2, _nodata_text(nodata)))
-            ent.sort(key=lambda e: e[0])
-            fmt = {3: "H", 4: "I", 12: "d"}
-            ifd_off = pos
-            val_pos = ifd_off + 2 + 12 * len(ent) + 4
-            ifd, tail = b"", b""
-            for tag, typ, vals in ent:
-                if typ == 2:
-                    data = vals.encode("latin-1") + b"\0"
-                    cnt = len(data)
-                else:
-                    data = struct.pack("<" + fmt[typ] * len(vals), *vals)
-                    cnt = len(vals)
-                e = struct.pack("<HHI", tag, typ, cnt)
-                if len(data) <= 4:
-                    e += data.ljust(4, b"\0")
-                else:
-                    e += struct.pack("<I", val_pos + len(tail))
-                    tail += data + (b"\0" if len(data) & 1 else b"")
-                ifd += e
-            f.write(struct.pack("<H", len(ent)) + ifd + struct.pack("<I", 0) + tail)
-            f.seek(4)
-            f.write(struct.pack("<I", ifd_off))
-        ok = True
-    finally:
-        if not ok:
-            try:
-                os.unlink(path)            # no half-written GeoTIFF stays behind a failed writer
-            except OSError:
-                pass
+    _write_geotiff_16(path, rgb16, georef, nodata, rows_per_strip, 1)
 
 
 def read_bands_raw(path: Path) -> Tuple[np.ndarray, Optional[GeoRef]]:
@@ -559,8 +516,6 @@ def write_geotiff_u16(path: Path, bands: np.ndarray, georef: GeoRef, nodata=None
     bands = np.asarray(bands)
     if bands.ndim != 3 or bands.shape[2] < 1 or bands.dtype != np.uint16:
         raise ValueError(f"expected HxWxB uint16, got {bands.shape} {bands.dtype}")
-    if bands.shape[2] == 3:
-        return write_geotiff_rgb16(path, bands, georef, rows_per_strip, nodata)
     _write_geotiff_16(path, bands, georef, nodata, rows_per_strip, 1)
 
 
@@ -573,71 +528,3 @@ def write_geotiff_i16(path: Path, band: np.ndarray, georef: GeoRef, nodata=None,
     if band.ndim != 3 or band.shape[2] < 1 or band.dtype != np.int16:
         raise ValueError(f"expected HxW or HxWxB int16, got {band.shape} {band.dtype}")
     _write_geotiff_16(path, band, georef, nodata, rows_per_strip, 2)
-
-
-def _write_geotiff_16(path: Path, bands: np.ndarray, georef: GeoRef, nodata, rows_per_strip: int, sample_format: int) -> None:
-    """the body of the two writers above: 16-bit chunky little-endian samples of SampleFormat 1 (unsigned) or 2 (signed)"""
-    import struct
-
-    from . import hostpool, native
-
-    bands = np.ascontiguousarray(bands.astype("<u2" if sample_format == 1 else "<i2", copy=False))
-    h, w, nb = bands.shape
-    strips = [(y, min(h, y + rows_per_strip)) for y in range(0, h, rows_per_strip)]
-    offs, sizes, pos = [], [], 8
-    ok = False
-    try:
-        with open(path, "wb") as f:
-            f.write(b"II" + struct.pack("<HI", 42, 0))
-            for e in hostpool.pool().map(lambda s: native.tiff_lzw_encode(bands[s[0]:s[1]].reshape(-1).view(np.uint8)), strips):
-                offs.append(pos)
-                sizes.append(len(e))
-                f.write(e)
-                if len(e) & 1:
-                    f.write(b"\0")
-                pos += len(e) + (len(e) & 1)
-                if pos >= (1 << 32) - (1 << 20):
-                    raise ValueError("output exceeds the 4 GiB of a classic TIFF")
-            colour = 3 if nb >= 4 else 1                               # samples the photometric interpretation accounts for
-            ent = [(256, 4, (w,)), (257, 4, (h,)), (258, 3, (16,) * nb), (259, 3, (5,)), (262, 3, (2 if nb >= 4 else 1,)), (273, 4, tuple(offs)),
-                   (277, 3, (nb,)), (278, 4, (rows_per_strip,)), (279, 4, tuple(sizes)), (284, 3, (1,)), (339, 3, (sample_format,) * nb)]
-            if nb > colour:
-                ent.append((338, 3, (0,) * (nb - colour)))             # ExtraSamples: unspecified data
-            for tag, val in georef.tags.items():
-                if tag == TAG_GEOKEYS:
-                    ent.append((tag, 3, tuple(int(v) for v in val)))
-                elif tag == TAG_GEOASCII:
-                    ent.append((tag, 2, val if isinstance(val, str) else str(val)))
-                else:
-                    ent.append((tag, 12, tuple(float(v) for v in val)))
-            if nodata is not None:
-                ent.append((TAG_GDAL_NODATA, 2, _nodata_text(nodata)))
-            ent.sort(key=lambda e: e[0])
-            fmt = {3: "H", 4: "I", 12: "d"}
-            ifd_off = pos
-            val_pos = ifd_off + 2 + 12 * len(ent) + 4
-            ifd, tail = b"", b""
-            for tag, typ, vals in ent:
-                if typ == 2:
-                    data = vals.encode("latin-1") + b"\0"
-                    cnt = len(data)
-                else:
-                    data = struct.pack("<" + fmt[typ] * len(vals), *vals)
-                    cnt = len(vals)
-                e = struct.pack("<HHI", tag, typ, cnt)
-                if len(data) <= 4:
-                    e += data.ljust(4, b"\0")
-                else:
-                    e += struct.pack("<I", val_pos + len(tail))
-                    tail += data + (b"\0" if len(data) & 1 else b"")
-                ifd += e
-            f.write(struct.pack("<H", len(ent)) + ifd + struct.pack("<I", 0) + tail)
-            f.seek(4)
-            f.write(struct.pack("<I", ifd_off))
-        ok = True
-    finally:
-        if not ok:
-            try:
-                os.unlink(path)            # no half-written GeoTIFF stays behind a failed writer
-            except OSError:
-                pass

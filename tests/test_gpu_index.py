@@ -502,3 +502,62 @@ def test_enhance16_runs_every_pairing_of_planes(monkeypatch, tmp_path):
         e.enhance16(img, indices=[dict(a=("extra", 0), b=("img", 0))])                            # no carried band to name
     with pytest.raises(ValueError, match="indices"):
         e.enhance16(img, extra=extra, indices=[dict(a=("img", 3), b=("img", 0))])
+
+
+def _frozen(x):
+    """a call's result out of the pinned pool the next call reuses, arrays as (dtype, shape, bytes) so that == is byte equality"""
+    if isinstance(x, np.ndarray):
+        return (str(x.dtype), x.shape, x.tobytes())
+    if isinstance(x, dict):
+        return {k: _frozen(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_frozen(v) for v in x]
+    return x
+
+
+def test_enhance16_is_the_flattened_product16(monkeypatch, tmp_path):
+    """The form table of RealESRGAN.enhance16 over all eight combinations of display / extra / indices: the tuple's length and
+    order, every member byte-equal to the same field of product16 on the same arguments, out16 that of the plain call, and
+    last_extra / last_inexact_blocks the record's carried_record / inexact_blocks.  The index is image x carried with a LUT
+    wherever bands are carried; without `extra` such an index is refused (no carried band to name), so it is image x image there."""
+    import itertools
+
+    import app.cnn_super_resolution as m
+    monkeypatch.delenv("S2SR_PRECISION", raising=False)
+    _patch_weights(monkeypatch, tmp_path, {"realesrgan_anime": 6})
+    H, W = 20, 26
+    rng = np.random.default_rng(11)
+    img = rng.integers(100, 4000, (H, W, 3)).astype(np.uint16)
+    extra = rng.integers(100, 4000, (H, W, 2)).astype(np.uint16)
+    spec = [dict(a=("img", 1), b=("extra", 1), offset=500, L=0, K=10000, lut=xi.ramp_lut(xi.ramp_for("diverging")))]
+    asked = {"display": dict(p_lo=2.0, p_hi=98.0), "extra": extra, "indices": spec}
+    lone = [dict(spec[0], b=("img", 2))]            # without `extra` there is no carried band to name: the index reads two image channels
+    fields = {"display": ("display", "info"), "extra": ("carried",), "indices": ("indices",)}
+    assert m.Product16._fields == ("out16", "display", "info", "carried", "carried_record", "indices", "inexact_blocks")
+    for consistency in (None, "exact"):
+        e = m.RealESRGAN(model_name="realesrgan_anime", tile_size=256, **({} if consistency is None else {"consistency": consistency}))
+        plain = _frozen(e.enhance16(img, value_range=(100, 4000)))
+        assert plain[:2] == ("uint16", (4 * H, 4 * W, 3))                                      # a bare array
+        for on in itertools.product((False, True), repeat=3):
+            kw = {k: asked[k] for k, use in zip(("display", "extra", "indices"), on) if use}
+            if "indices" in kw and "extra" not in kw:
+                kw["indices"] = lone
+            order = ["out16"] + [f for k in ("display", "extra", "indices") if k in kw for f in fields[k]]
+            e.last_extra = None
+            got = e.enhance16(img, value_range=(100, 4000), **kw)
+            got = [_frozen(got)] if isinstance(got, np.ndarray) else _frozen(got)
+            seen_extra, seen_inexact = _frozen(e.last_extra), e.last_inexact_blocks
+            p = e.product16(img, value_range=(100, 4000), **kw)
+            rec = {f: _frozen(getattr(p, f)) for f in m.Product16._fields}
+            assert len(got) == len(order), (kw.keys(), len(got))
+            for f, member in zip(order, got):
+                assert member == rec[f], (sorted(kw), f)
+            assert got[0] == plain, sorted(kw)
+            assert [f for f in m.Product16._fields if rec[f] is None] == \
+                [f for f in m.Product16._fields if f not in order + ["carried_record"] * ("extra" in kw) + ["inexact_blocks"] * (consistency is not None)]
+            assert seen_extra == rec["carried_record"] == _frozen(e.last_extra)
+            assert seen_inexact == p.inexact_blocks == e.last_inexact_blocks and (consistency is None) == (p.inexact_blocks is None)
+            if "indices" in kw:
+                assert set(rec["indices"][0]) == {"index", "hist", "undefined", "rgba"}
+            if "display" in kw:
+                assert rec["display"][:2] == ("uint8", (4 * H, 4 * W, 3)) and isinstance(p.info, dict)
