@@ -439,6 +439,34 @@ int  s2sr_index_nd_u16(s2sr_handle* h, const uint16_t* a /* [H, W, ac] or NULL *
 int  s2sr_index_render_i16(s2sr_handle* h, const int16_t* idx /* [H, W] */, int32_t H, int32_t W, const uint8_t* lut /* [65536][4] */,
                            int32_t band_rows, uint8_t* rgba /* [H, W, 4] */);
 
+/* Polygons to zone labels: the label raster the `zones` of s2sr_index_nd_u16 takes, rasterised from features made
+ * of rings.  Integers throughout; no weights needed.
+ *   The label grid is H x W.  Coordinates are int32 in 1/256 of a label pixel, x along columns, y along rows, from the grid's
+ *   top-left corner, |x|, |y| <= 2^29 (every product below then fits int64); the centre of pixel (r, c) is
+ *   (cx, cy) = (256 c + 128, 256 r + 128).
+ *   A feature is a list of rings, a ring a closed list of at least 3 vertices (the edge last -> first is implied).  Holes, the
+ *   parts of a MultiPolygon and self-intersections need no special case, and winding does not matter:
+ *   an edge, its endpoints exchanged so that ya < yb (ya == yb: it never counts), counts for a centre iff
+ *     ya <= cy < yb  and  (cx - xa) (yb - ya) < (xb - xa) (cy - ya)
+ *   (the row test is half-open, the centre lies strictly left of the crossing), and a centre is inside a feature iff the count
+ *   over all edges of all its rings is odd.  Per row: with dy = yb - ya and N = (xb - xa) (cy - ya) + (xa - 128) dy the edge
+ *   toggles exactly the columns c < k, k = clamp(ceil(N / (256 dy)), 0, W).
+ *   Feature f carries label[f] in 1..Z; several may share one.  Where several features hold a centre the one latest in the list
+ *   wins (burn order); a pixel no feature holds is 0.
+ * xy: int32 [V][2] (x, y); ring_start: int32 [R + 1] into xy; feat_start: int32 [F + 1] into the rings (R = feat_start[F],
+ *   V = ring_start[R]); label: uint16 [F].
+ * out: uint16 [H, W].  area: uint64 [Z + 1] or NULL: the pixels per label, row 0 the unlabelled ones; its sum is H W.
+ * band_rows (0: the library's choice) sets the row bands the labels leave in; the result does not depend on it, nor on the number
+ *   of workgroups or on which stream runs first.
+ * The call requests scratch, so it voids whatever the call before it kept on the device (a uint16 image, a raster, a level), and it
+ *   keeps nothing itself: the labels go to the host, and s2sr_index_nd_u16 takes them from there.  A job calls it in front of the net.
+ * S2SR_E_INVALID with a text, before the device is touched: non-positive H or W, H W >= 2^31, F < 1, Z outside 1..65535, a label
+ * of 0 or above Z, start tables that are not non-decreasing from 0, a ring of fewer than 3 vertices, a coordinate outside +-2^29, a
+ * NULL table or out, band_rows < 0, and features that meet more than 2^31 - 1 tiles of 64 x 64 pixels in all.  The handle keeps working. */
+int  s2sr_zones_rasterize_u16(s2sr_handle* h, const int32_t* xy /* [V][2] */, const int32_t* ring_start /* [R + 1], into xy */,
+                              const int32_t* feat_start /* [F + 1], into the rings */, const uint16_t* label /* [F] */, int32_t F, int32_t Z,
+                              int32_t H, int32_t W, int32_t band_rows, uint16_t* out /* [H, W] */, uint64_t* area /* [Z + 1] or NULL */);
+
 /* Multi-GPU building blocks of _tile_process (cnn_super_resolution.py:244-278), device-resident:
  * cut windows [first, first+count) of the plan into d_tiles [count, wh, ww, 3] (wh/ww = the
  * plan's common window size), and paste ALL T windows' outputs d_tiles [T, 4wh, 4ww, 3] into

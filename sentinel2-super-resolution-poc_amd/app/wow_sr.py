@@ -94,7 +94,11 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
     lists them (only listed bands go into the product GeoTIFF), and the job's nodata mask is the index's.  index_offset: the DN
     offset of a definition that names none.  Per index the job writes <stem>_<name>.tif (int16, GDAL_NODATA -32768) and
     <stem>_<name>.png (its RGBA rendering through the index's colour ramp); zones (the path of a single-band uint8 / uint16 label
-    GeoTIFF on the input or the output grid, or such an array) adds a per-zone table.  The metadata gains "indices", and only then."""
+    GeoTIFF on the input or the output grid, or such an array) adds a per-zone table.  The metadata gains "indices", and only then.
+    zones may also be field polygons (s2sr/zones.py): a GeoJSON source -- the path of a .geojson / .json file, a parsed
+    FeatureCollection, Feature or geometry, or a list of those -- or {"geojson": source, "property": name}.  They are projected onto
+    the output grid, rasterised on the job's engine in front of the net, and the labels then travel as a caller's array does; the
+    job also writes <stem>_zones.tif (uint16, GDAL_NODATA 0, the product's georeference) and the metadata gains "zones", and only then."""
     import dataclasses
 
     from s2sr import rasterio_lite as rio
@@ -117,8 +121,10 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
             from s2sr import index as xi
             defs = xi.resolve(o.indices, o.index_offset, every.shape[2])
             numbers += [b for b in xi.carried_bands(defs) if b not in numbers]
-            label = None if o.zones is None else xi.check_zones(rio.read_bands_raw(o.zones)[0] if isinstance(o.zones, (str, Path)) else o.zones,
-                                                                 img.shape[:2], 4)
+            from s2sr import zones as xz
+            polygons = o.zones is not None and xz.is_geojson(o.zones)       # rasterised through the job's engine, below
+            label = None if o.zones is None or polygons else xi.check_zones(rio.read_bands_raw(o.zones)[0] if isinstance(o.zones, (str, Path)) else o.zones,
+                                                                             img.shape[:2], 4)
         if numbers:
             extra = np.ascontiguousarray(every[:, :, [b - 1 for b in numbers]])
         del every
@@ -130,6 +136,10 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
     esrgan = RealESRGAN(model_name=model, tile_size=256, **o.passed("RealESRGAN"))
     if extra is not None:            # the device copy is BGR: the guide weights go in reversed
         call.update(extra=extra, extra_weights=w_rgb[::-1])
+    burnt = None
+    if defs is not None and polygons:      # field polygons: labels on the output grid, in front of the net; they travel as a caller's array does
+        burnt = xz.rasterize(esrgan._engine, o.zones, georef, img.shape[:2], esrgan.scale)
+        label = (burnt["labels"], 1, burnt["Z"])
     if defs is not None:             # file band 1, 2, 3 is channel 2, 1, 0 of the device copy; a band from 4 on is one of the carried
         side = lambda b: ("img", 3 - b) if b <= 3 else ("extra", numbers.index(b))
         ramps = [xi.ramp_for(xi.DEFAULT_RAMP.get(d["preset"], "diverging"), d["K"]) for d in defs]
@@ -201,6 +211,11 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
             stats = xi.stats_from_hist(r["hist"], d["K"], pixel_size=out_geo.pixel_size)
             metadata["indices"].append(xi.metadata_entry(d, r["undefined"], stats, ramp, {"tif": str(tif), "png": str(tif.with_suffix(".png"))},
                                                          None if label is None else xi.zonal_table(r["zonal"], d["K"])))
+        if burnt is not None:
+            ztif = final_output.with_name(f"{final_output.stem}_zones.tif")
+            rio.write_geotiff_u16(ztif, burnt["labels"][..., None], out_geo, nodata=0)
+            metadata["zones"] = xz.metadata_block(burnt["source"], burnt["features"], burnt["table"], burnt["dropped"], burnt["grid"], 1, ztif,
+                                                  burnt["area"], out_geo.pixel_size)
     return final_output, metadata
 
 
@@ -339,6 +354,8 @@ def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True
     }
     if indices is not None:
         result["outputs"]["indices"] = {e["name"]: dict(e["files"]) for e in sr_metadata.get("indices", [])}
+    if "zones" in sr_metadata:           # field polygons were rasterised: the label raster the job wrote
+        result["outputs"]["zones_tif"] = sr_metadata["zones"]["file"]
     with open(output_dir / f"{base_name}_wow_sr_metadata.json", "w") as f:
         json.dump(result, f, indent=2)
     return result

@@ -1,4 +1,4 @@
-// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_display.hip, engine_bands.hip, engine_index.hip, engine_debug.hip): the handle behind
+// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_display.hip, engine_bands.hip, engine_index.hip, engine_zones.hip, engine_debug.hip): the handle behind
 // the C ABI of include/s2sr.h, the types it is made of, and the helpers that more than one of those files uses.  What a single
 // file uses stays static or anonymous in that file.
 #pragma once
@@ -18,11 +18,12 @@ namespace s2sr::engine {
 // (include/s2sr.h: scratch_peek, redzone_poke, the mask of poison_scratch).  THE table of what each holds, door family by family:
 enum Slot : int {
     SL_SRC = 0,   // 0 and 1: a call's source and its result: the upload and the image / tiles / level that leave.  Along a chain of
-    SL_DST,       //   pyramid or display calls the roles swap: the source is where the call before kept its result, the result other() of it
+    SL_DST,       //   pyramid or display calls the roles swap: the source is where the call before kept its result, the result other() of it;
+                  //   slot 1 also holds the label raster s2sr_zones_rasterize_u16 makes (kept by nobody: it leaves for the host in bands)
     SL_MID,       // what lies between: gathered windows (the untiled image's tiles), the 16-bit batch's quantised tiles, the resample
                   //   intermediate, the PNG writer's statistics, the band s2sr_carry_band_u16 carries, plane b of s2sr_index_nd_u16
     SL_TABLES,    // tables and plans: paste / blend tables, warp grid, footprint and tap tables, PNG plans, display histogram + LUT, an index pass's LUT, counter,
-                  //   histogram and zonal sums
+                  //   histogram and zonal sums; a zone rasterisation's xy, ring_start, feat_start, label, tile bins (starts, features) and area
     SL_CHUNK,     // a chunk's tile outputs, the unbanded post-process's image, the PNG streams of even groups
     SL_PP,        // the post-process work area, where a banded run lives while it is open; the PNG streams of odd groups (the level the
                   //   writer reads is in 0 / 1, so while it runs 2 .. 5 are free)

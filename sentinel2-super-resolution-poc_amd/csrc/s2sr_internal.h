@@ -350,6 +350,13 @@ hipError_t launch_index_nd(const uint16_t* d_a, int ac, int ca, const uint16_t* 
 // rows [y0, y1) of an int16 index raster through the LUT: -32768 gives 0, 0, 0, 0
 hipError_t launch_index_render(const int16_t* d_idx, int H, int W, int y0, int y1, const uint8_t* d_lut, uint8_t* d_rgba, hipStream_t st);
 
+// Polygon rasterisation to zone labels (zones.hip): rows [y0, y1) of the uint16 label raster d_out [H, W] (16-byte
+// aligned) from tables that zone_check_tables accepted and the bins zone_build_bins made of them (zone_bins.h), all on the device;
+// d_area (uint64 [Z + 1], or null) is added to.  Every pixel of the rows is stored exactly once.
+hipError_t launch_zones_rasterize(const int32_t* d_xy, const int32_t* d_ring_start, const int32_t* d_feat_start, const uint16_t* d_label,
+                                  const uint32_t* d_tile_start, const int32_t* d_tile_feat, int H, int W, int y0, int y1, uint16_t* d_out,
+                                  unsigned long long* d_area, hipStream_t st);
+
 // XYZ tile pyramid (tiles.hip)
 hipError_t launch_warp_bilinear(const uint8_t* d_rgb, int H, int W, const float* d_grid, int gh, int gw, int step, int OH, int OW,
                                 uint8_t* d_out, hipStream_t st);

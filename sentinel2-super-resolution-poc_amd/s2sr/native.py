@@ -170,6 +170,7 @@ _PROTOS = {
     "s2sr_index_nd_u16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_int32, C.c_void_p,
                                     C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
     "s2sr_index_render_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "s2sr_zones_rasterize_u16": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
     "s2sr_enhance_job_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PPParams), C.c_void_p]),
     "s2sr_enhance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tile_process_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -1008,6 +1009,41 @@ class Engine:
         out = pinned_pool.empty((H, W, 4), np.uint8) if H > 0 and W > 0 else np.empty((1,), np.uint8)
         self._check(self._lib.s2sr_index_render_i16(self._h, _ptr(idx), H, W, _ptr(lut), int(band_rows), _ptr(out)), "s2sr_index_render_i16")
         return out
+
+    def zones_rasterize_u16(self, xy, ring_start, feat_start, label, Z: int, shape, band_rows: int = 0, want_area: bool = True):
+        """Features made of rings -> (uint16 labels [H, W], uint64 area [Z + 1] or None) on the label grid shape = (H, W)
+        (include/s2sr.h s2sr_zones_rasterize_u16).  xy: int32 [V, 2] in 1/256 of a label pixel; ring_start: int32
+        [R + 1] into xy; feat_start: int32 [F + 1] into the rings; label: uint16 [F] in 1..Z.  The later feature wins a pixel two
+        features hold; 0 where none does.  The call voids whatever the call before it kept on the device.  No weights needed."""
+        what = "zones_rasterize_u16"
+        tabs = []
+        for name, t, dt in (("xy", xy, np.int32), ("ring_start", ring_start, np.int32), ("feat_start", feat_start, np.int32), ("label", label, np.uint16)):
+            t = np.asarray(t)
+            if t.dtype != dt:
+                raise TypeError(f"{what}: {name} must be {np.dtype(dt).name}, got {t.dtype}")
+            tabs.append(np.ascontiguousarray(t))
+        xy, ring_start, feat_start, label = tabs
+        if xy.ndim != 2 or xy.shape[1] != 2 or ring_start.ndim != 1 or feat_start.ndim != 1 or label.ndim != 1:
+            raise ValueError(f"{what}: xy is [V, 2], ring_start [R + 1], feat_start [F + 1], label [F]")
+        F = len(feat_start) - 1
+        if len(ring_start) < 1 or F < 0 or len(label) != F:
+            raise ValueError(f"{what}: {len(feat_start)} feature starts, {len(label)} labels and {len(ring_start)} ring starts do not fit together")
+        # what the library cannot know: the tables' lengths.  Every start must point inside the table it indexes
+        if F >= 0 and len(feat_start) and (feat_start.min(initial=0) < 0 or feat_start.max(initial=0) > len(ring_start) - 1):
+            raise ValueError(f"{what}: feat_start points outside the {len(ring_start) - 1} rings")
+        if ring_start.min(initial=0) < 0 or ring_start.max(initial=0) > len(xy):
+            raise ValueError(f"{what}: ring_start points outside the {len(xy)} vertices")
+        try:
+            H, W = (int(v) for v in shape)
+        except (TypeError, ValueError):
+            raise ValueError(f"{what}: shape is (H, W), got {shape!r}") from None
+        Z = int(Z)
+        ok = H > 0 and W > 0 and H * W < 2 ** 31
+        out = pinned_pool.empty((H, W), np.uint16) if ok else np.empty((1,), np.uint16)
+        area = np.zeros(Z + 1 if 0 <= Z <= 65535 else 1, np.uint64) if want_area else None
+        self._check(self._lib.s2sr_zones_rasterize_u16(self._h, _ptr(xy), _ptr(ring_start), _ptr(feat_start), _ptr(label), F, Z, H, W, int(band_rows),
+                                                       _ptr(out), _ptr(area) if area is not None else None), "s2sr_zones_rasterize_u16")
+        return out, area
 
     # -- multi-GPU building blocks (device pointers) ------------------------------------------
     def cut_windows_u8_dev(self, d_img: int, H: int, W: int, tile: int, pad: int, first: int, count: int,
