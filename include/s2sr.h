@@ -467,6 +467,63 @@ int  s2sr_zones_rasterize_u16(s2sr_handle* h, const int32_t* xy /* [V][2] */, co
                               const int32_t* feat_start /* [F + 1], into the rings */, const uint16_t* label /* [F] */, int32_t F, int32_t Z,
                               int32_t H, int32_t W, int32_t band_rows, uint16_t* out /* [H, W] */, uint64_t* area /* [Z + 1] or NULL */);
 
+/* Fields from the image: the inverse of s2sr_zones_rasterize_u16.  An index raster is thresholded, cleaned and
+ * split into connected components; the components are the zone labels.  Integers throughout; no weights needed.
+ *   idx: int16 [H, W], -32768 = nodata: the raster s2sr_index_nd_u16 writes.  H W < 2^31.
+ *   1. mask        m0 = idx != -32768 and lo <= idx <= hi          (lo <= hi, both in -32767..32767)
+ *   2. morphology  binary, the (2 r + 1) x (2 r + 1) square as the element (r_open, r_close in 0..8).  Erode is the AND, dilate the
+ *                  OR over the neighbours that lie INSIDE the image: out-of-image neighbours take no part, so a field at the
+ *                  raster's edge does not shrink.  open = dilate(erode(m0, r_open), r_open), close = erode(dilate(open, r_close),
+ *                  r_close), m = close and idx != -32768: a label never lies on a nodata pixel.  r = 0: the identity.
+ *   3. components  of m under conn (4 or 8).  A component's key is the smallest linear index y W + x among its pixels, its size its
+ *                  pixel count.  Components smaller than min_pixels (>= 1) become 0; the rest are numbered 1, 2, ... by ascending
+ *                  key; found is how many remain.  A component whose number exceeds Z (1..65535) is written as 0; found still
+ *                  counts it, so the caller can tell.
+ *   labels: uint16 [H, W].  fields: int64 [Z + 1][6] = pixels, key, x0, y0, x1, y1 (the bounding box, half-open); row 0 holds the
+ *   unlabelled pixel count and zeros; rows above min(found, Z) are zero; the pixels column sums to H W.
+ * Nothing depends on the order of atomics, on the row bands the rasters travel in, on the number of workgroups or on which stream
+ * runs first.
+ * The call requests scratch, so it voids whatever the call before it kept on the device (a uint16 image, a raster, a level), and it
+ *   keeps nothing itself: labels and fields go to the host, and s2sr_index_nd_u16 takes the labels from there.
+ * S2SR_E_INVALID with a text, before the device is touched: lo > hi or either outside -32767..32767, a radius outside 0..8, conn
+ * other than 4 or 8, min_pixels < 1, Z outside 1..65535, a NULL idx or labels, non-positive H or W, H W >= 2^31.  The handle keeps
+ * working. */
+int  s2sr_fields_segment_i16(s2sr_handle* h, const int16_t* idx /* [H, W] */, int32_t H, int32_t W, int32_t lo, int32_t hi, int32_t r_open,
+                             int32_t r_close, int32_t conn, int64_t min_pixels, int32_t Z, uint16_t* labels /* [H, W] */,
+                             int64_t* fields /* [Z + 1][6] or NULL */, uint64_t* found /* or NULL */);
+/* Labels to rings (host code: csrc/ring_trace.h): the polygons around the labels 1..Z of a uint16 raster, in pixel corners (pixel
+ * (r, c) covers x in [c, c + 1], y in [r, r + 1]).
+ *   The boundary of label l is the set of unit pixel edges between a pixel of l and anything else; the image border counts as
+ *   anything else.  Each edge is directed so that l's pixel lies on its left as seen on screen: exterior rings run counterclockwise
+ *   on a north-up map (RFC 7946), holes clockwise.  At a corner with two ways on the walk turns left: pixels of l that touch only
+ *   diagonally get rings of their own that touch.  By the same rule everything else is 8-connected, so a ring MAY TOUCH ITSELF at
+ *   a corner: two holes of one label that meet at a corner are ONE ring that passes through that corner twice, and a hole that
+ *   meets the outside at a corner is a notch of the exterior ring, which touches itself there.  No ring crosses itself or runs
+ *   along itself, every ring turns at every vertex, and under the even-odd rule of s2sr_zones_rasterize_u16 the rings of a label
+ *   burn back to exactly its pixels.  A caller that needs OGC-simple rings splits a ring at its repeated vertices.
+ *   Collinear vertices are dropped; a ring starts at its smallest (y, x) vertex (never a touching corner) and is not closed (the edge last -> first is implied, as s2sr_zones_rasterize_u16 takes it); rings are ordered by label,
+ *   then by start vertex.  Label 0 and labels above Z are not traced.
+ * counts: uint64 [2] = vertices, rings: always filled.  xy: int32 [xy_cap][2] (x, y); ring_start: int32 [ring_cap + 1] into xy;
+ * ring_label: uint16 [ring_cap].  The tables are written only if both capacities suffice (and none is NULL), so a caller sizes them
+ * with a first call at capacity 0.  S2SR_E_INVALID: a NULL labels or counts, non-positive H or W, H W >= 2^31, Z outside 1..65535,
+ * more than 2^31 - 1 vertices.  Touches no device. */
+int  s2sr_labels_trace_u16(s2sr_handle* h, const uint16_t* labels /* [H, W] */, int32_t H, int32_t W, int32_t Z, uint64_t xy_cap, uint64_t ring_cap,
+                           int32_t* xy, int32_t* ring_start, uint16_t* ring_label, uint64_t* counts /* [2] */);
+/* test hook: what the stages of the last s2sr_fields_segment_i16 on this handle took by HIP events.  The pass's launches share the
+ * statistics family "index"; with profiling on (s2sr_set_profiling(h, 1): every launch bracketed) each launch's event pair is also
+ * booked to its stage.  ms, launches: S2SR_FIELDS_STAGES entries, in the order of the S2SR_FIELDS_STAGE_* below; all zero when the
+ * last call ran with profiling off (with every_n > 1 only the sampled launches count).  Touches no device beyond reading event times. */
+#define S2SR_FIELDS_STAGES 8
+#define S2SR_FIELDS_STAGE_MASK 0      /* the mask, the morphology's passes, the nodata mask behind them */
+#define S2SR_FIELDS_STAGE_LOCAL 1     /* the tiles' union-find */
+#define S2SR_FIELDS_STAGE_BORDER 2    /* the unions across the tile lines */
+#define S2SR_FIELDS_STAGE_FLATTEN 3   /* parents to roots, sizes to roots */
+#define S2SR_FIELDS_STAGE_COUNT 4     /* numbering: the chunks' flags */
+#define S2SR_FIELDS_STAGE_SCAN 5      /* numbering: the one-workgroup scan of the chunk sums */
+#define S2SR_FIELDS_STAGE_APPLY 6     /* numbering: ranks to the roots, pixels and key to fields */
+#define S2SR_FIELDS_STAGE_LABELS 7    /* labels and boxes */
+int  s2sr_debug_fields_stage_ms(s2sr_handle* h, double* ms /* [S2SR_FIELDS_STAGES] */, int32_t* launches /* [S2SR_FIELDS_STAGES] */);
+
 /* Multi-GPU building blocks of _tile_process (cnn_super_resolution.py:244-278), device-resident:
  * cut windows [first, first+count) of the plan into d_tiles [count, wh, ww, 3] (wh/ww = the
  * plan's common window size), and paste ALL T windows' outputs d_tiles [T, 4wh, 4ww, 3] into

@@ -98,7 +98,10 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
     zones may also be field polygons (s2sr/zones.py): a GeoJSON source -- the path of a .geojson / .json file, a parsed
     FeatureCollection, Feature or geometry, or a list of those -- or {"geojson": source, "property": name}.  They are projected onto
     the output grid, rasterised on the job's engine in front of the net, and the labels then travel as a caller's array does; the
-    job also writes <stem>_zones.tif (uint16, GDAL_NODATA 0, the product's georeference) and the metadata gains "zones", and only then."""
+    job also writes <stem>_zones.tif (uint16, GDAL_NODATA 0, the product's georeference) and the metadata gains "zones", and only then.
+    zones may also be {"segment": {"index": name, "min": 0.3, "max": None, "open": 1, "close": 2, "connectivity": 4, "min_area_ha": 0.5}}
+    (s2sr/fields.py): the fields are the connected components of the thresholded, opened and closed raster of the named
+    index; the job writes <stem>_zones.tif as above and <stem>_fields.geojson (one Feature per field, lon / lat)."""
     import dataclasses
 
     from s2sr import rasterio_lite as rio
@@ -122,8 +125,10 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
             defs = xi.resolve(o.indices, o.index_offset, every.shape[2])
             numbers += [b for b in xi.carried_bands(defs) if b not in numbers]
             from s2sr import zones as xz
-            polygons = o.zones is not None and xz.is_geojson(o.zones)       # rasterised through the job's engine, below
-            label = None if o.zones is None or polygons else xi.check_zones(rio.read_bands_raw(o.zones)[0] if isinstance(o.zones, (str, Path)) else o.zones,
+            from s2sr import fields as xf
+            segmenting = xf.is_segment(o.zones)                            # fields from the job's own index raster, below
+            polygons = o.zones is not None and not segmenting and xz.is_geojson(o.zones)   # rasterised through the job's engine, below
+            label = None if o.zones is None or polygons or segmenting else xi.check_zones(rio.read_bands_raw(o.zones)[0] if isinstance(o.zones, (str, Path)) else o.zones,
                                                                              img.shape[:2], 4)
         if numbers:
             extra = np.ascontiguousarray(every[:, :, [b - 1 for b in numbers]])
@@ -136,7 +141,11 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
     esrgan = RealESRGAN(model_name=model, tile_size=256, **o.passed("RealESRGAN"))
     if extra is not None:            # the device copy is BGR: the guide weights go in reversed
         call.update(extra=extra, extra_weights=w_rgb[::-1])
-    burnt = None
+    burnt = seg = None
+    if defs is not None and segmenting:    # every refusal of the option before the net runs; the size in pixels of the output grid
+        xf.placement_of(None if georef is None else georef.scaled(esrgan.scale))      # the GeoJSON needs the raster's place
+        size = georef.scaled(esrgan.scale).pixel_size
+        seg = {"params": xf.resolve(o.zones, defs, None if size is None else abs(float(size[0]) * float(size[1])))}
     if defs is not None and polygons:      # field polygons: labels on the output grid, in front of the net; they travel as a caller's array does
         burnt = xz.rasterize(esrgan._engine, o.zones, georef, img.shape[:2], esrgan.scale)
         label = (burnt["labels"], 1, burnt["Z"])
@@ -160,6 +169,11 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
     output_rgb = np.ascontiguousarray(got.out16[:, :, ::-1])
     scale = esrgan.scale
     inexact = None if o.consistency is None else got.inexact_blocks[::-1]      # (the net's image is B, G, R)
+    if seg is not None:              # segment the named raster, then each index's per-zone sums from host arrays: the segment call voided the kept image
+        seg.update(xf.segment(esrgan._engine, found[seg["params"]["index"]]["index"], seg["params"]))
+        for d, r in zip(call["indices"], found):
+            r["zonal"] = xf.zonal(esrgan._engine, d, got.out16, carried, valid, seg["labels"], seg["found"])
+        label = (seg["labels"], 1, seg["found"])
     del esrgan
     final_output = Path(output_path).with_suffix(".tif")
     final_output.parent.mkdir(parents=True, exist_ok=True)
@@ -216,6 +230,13 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
             rio.write_geotiff_u16(ztif, burnt["labels"][..., None], out_geo, nodata=0)
             metadata["zones"] = xz.metadata_block(burnt["source"], burnt["features"], burnt["table"], burnt["dropped"], burnt["grid"], 1, ztif,
                                                   burnt["area"], out_geo.pixel_size)
+        if seg is not None:
+            ztif = final_output.with_name(f"{final_output.stem}_zones.tif")
+            rio.write_geotiff_u16(ztif, seg["labels"][..., None], out_geo, nodata=0)
+            tables = {e["name"]: e["zones"] for e in metadata["indices"]}
+            gj = xf.write_geojson(final_output.with_name(f"{final_output.stem}_fields.geojson"),
+                                  xf.to_geojson(xf.polygons(seg["rings"], seg["fields"]), out_geo, out_geo.pixel_size, tables))
+            metadata["zones"] = xf.metadata_block(seg["params"], seg["found"], seg["fields"], seg["labels"].shape, ztif, gj, out_geo.pixel_size)
     return final_output, metadata
 
 
@@ -356,6 +377,8 @@ def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True
         result["outputs"]["indices"] = {e["name"]: dict(e["files"]) for e in sr_metadata.get("indices", [])}
     if "zones" in sr_metadata:           # field polygons were rasterised: the label raster the job wrote
         result["outputs"]["zones_tif"] = sr_metadata["zones"]["file"]
+        if sr_metadata["zones"].get("geojson"):      # the fields were segmented from the image
+            result["outputs"]["fields_geojson"] = sr_metadata["zones"]["geojson"]
     with open(output_dir / f"{base_name}_wow_sr_metadata.json", "w") as f:
         json.dump(result, f, indent=2)
     return result

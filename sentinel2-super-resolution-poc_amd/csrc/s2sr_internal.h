@@ -357,6 +357,29 @@ hipError_t launch_zones_rasterize(const int32_t* d_xy, const int32_t* d_ring_sta
                                   const uint32_t* d_tile_start, const int32_t* d_tile_feat, int H, int W, int y0, int y1, uint16_t* d_out,
                                   unsigned long long* d_area, hipStream_t st);
 
+// Fields from the image (fields.hip), one launcher per stage, all on whole H x W planes (H W < 2^31):
+//   mask     d_mask = idx is data and lo <= idx <= hi; with and_into: d_mask &= idx is data
+//   morph    one erode (or dilate) pass of radius r in 1..8 along the rows (or, with column, the columns), d_src -> d_dst
+//   local    the 64 x 64 tiles' components: d_parent int32 = the global linear index of the local root, -1 for background; d_size
+//            uint32 = the local component's pixels at its local root, 0 elsewhere.  Every pixel of both planes is written.
+//   border   the unions across the tile lines; flatten: parent = root, the local counts added up at the roots
+//   count, scan, apply (the numbering)   d_sums uint32 [fields_chunks(H, W)] is scratch; *d_found the components of at least min_pixels; at the roots d_size
+//            becomes the rank (0: too small); rows 1 .. min(found, Z) of d_fields (uint64 [Z + 1][6], zeroed by the caller) get
+//            pixels, key and an empty box
+//   labels   d_labels uint16 = the rank of the pixel's root, 0 above Z; narrows the boxes and adds the unlabelled pixels to row 0
+hipError_t launch_fields_mask(const int16_t* d_idx, int H, int W, int lo, int hi, int and_into, uint8_t* d_mask, hipStream_t st);
+hipError_t launch_fields_morph(const uint8_t* d_src, uint8_t* d_dst, int H, int W, int r, int erode, int column, hipStream_t st);
+hipError_t launch_fields_local(const uint8_t* d_mask, int* d_parent, uint32_t* d_size, int H, int W, int conn, hipStream_t st);
+hipError_t launch_fields_border(int* d_parent, int H, int W, int conn, hipStream_t st);
+hipError_t launch_fields_flatten(int* d_parent, uint32_t* d_size, int H, int W, hipStream_t st);
+size_t fields_chunks(int H, int W);
+hipError_t launch_fields_count(const int* d_parent, const uint32_t* d_size, int H, int W, uint32_t min_pixels, uint32_t* d_sums, hipStream_t st);
+hipError_t launch_fields_scan(uint32_t* d_sums, int H, int W, unsigned long long* d_found, hipStream_t st);
+hipError_t launch_fields_apply(const int* d_parent, uint32_t* d_size, int H, int W, uint32_t min_pixels, uint32_t Z, const uint32_t* d_sums,
+                               unsigned long long* d_fields, hipStream_t st);
+hipError_t launch_fields_labels(const int* d_parent, const uint32_t* d_size, int H, int W, uint32_t Z, uint16_t* d_labels, unsigned long long* d_fields,
+                                hipStream_t st);
+
 // XYZ tile pyramid (tiles.hip)
 hipError_t launch_warp_bilinear(const uint8_t* d_rgb, int H, int W, const float* d_grid, int gh, int gw, int step, int OH, int OW,
                                 uint8_t* d_out, hipStream_t st);

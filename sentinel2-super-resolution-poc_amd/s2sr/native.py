@@ -171,6 +171,9 @@ _PROTOS = {
                                     C.c_int32, C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5),
     "s2sr_index_render_i16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "s2sr_zones_rasterize_u16": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
+    "s2sr_fields_segment_i16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.c_int64, C.c_int32] + [C.c_void_p] * 3),
+    "s2sr_labels_trace_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_uint64] * 2 + [C.c_void_p] * 4),
+    "s2sr_debug_fields_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "s2sr_enhance_job_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PPParams), C.c_void_p]),
     "s2sr_enhance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tile_process_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -253,6 +256,7 @@ _PROTOS = {
     "s2sr_debug_grid_cap_family": (C.c_char_p, [C.c_int32]),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
+FIELDS_STAGES = ("mask_morphology", "local", "border", "flatten", "count", "scan", "apply", "labels")   # S2SR_FIELDS_STAGE_*
 
 
 def _mapped_hip_runtimes() -> set:
@@ -1044,6 +1048,50 @@ class Engine:
         self._check(self._lib.s2sr_zones_rasterize_u16(self._h, _ptr(xy), _ptr(ring_start), _ptr(feat_start), _ptr(label), F, Z, H, W, int(band_rows),
                                                        _ptr(out), _ptr(area) if area is not None else None), "s2sr_zones_rasterize_u16")
         return out, area
+
+    def fields_segment_i16(self, idx, lo: int, hi: int, r_open: int = 0, r_close: int = 0, conn: int = 4, min_pixels: int = 1, Z: int = 65535):
+        """An int16 index raster [H, W] (nodata -32768) -> (uint16 labels [H, W], int64 fields [Z + 1][6] = pixels, key, x0, y0,
+        x1, y1, found) (include/s2sr.h s2sr_fields_segment_i16): the mask lo <= idx <= hi, opened and closed with
+        squares of radius r_open and r_close, split into components under conn (4 or 8); those of at least min_pixels pixels are
+        numbered 1, 2, ... by their first pixel.  The call voids whatever the call before it kept on the device.  No weights needed."""
+        idx = np.asarray(idx)
+        if idx.dtype != np.int16 or idx.ndim != 2:
+            raise TypeError(f"fields_segment_i16 takes an int16 raster [H, W], got {idx.dtype} {idx.shape}")
+        idx = np.ascontiguousarray(idx)
+        H, W = idx.shape
+        Z = int(Z)
+        ok = H > 0 and W > 0 and H * W < 2 ** 31
+        labels = pinned_pool.empty((H, W), np.uint16) if ok else np.empty((1,), np.uint16)
+        fields = np.zeros((Z + 1 if 0 <= Z <= 65535 else 1, 6), np.int64)
+        found = np.zeros(1, np.uint64)
+        self._check(self._lib.s2sr_fields_segment_i16(self._h, _ptr(idx), H, W, int(lo), int(hi), int(r_open), int(r_close), int(conn), int(min_pixels), Z,
+                                                      _ptr(labels), _ptr(fields), _ptr(found)), "s2sr_fields_segment_i16")
+        return labels, fields, int(found[0])
+
+    def fields_stage_ms(self) -> dict:
+        """What the stages of the last fields_segment_i16 took by HIP events, {stage: (ms, launches)} in the order of FIELDS_STAGES
+        (include/s2sr.h s2sr_debug_fields_stage_ms): zeros unless that call ran under set_profiling(1)."""
+        ms, n = np.zeros(len(FIELDS_STAGES), np.float64), np.zeros(len(FIELDS_STAGES), np.int32)
+        self._check(self._lib.s2sr_debug_fields_stage_ms(self._h, _ptr(ms), _ptr(n)), "s2sr_debug_fields_stage_ms")
+        return {name: (float(ms[k]), int(n[k])) for k, name in enumerate(FIELDS_STAGES)}
+
+    def labels_trace_u16(self, labels, Z: int):
+        """A uint16 label raster [H, W] -> (xy int32 [V, 2] in pixel corners, ring_start int32 [R + 1], ring_label uint16 [R]): the
+        rings around the labels 1..Z (include/s2sr.h s2sr_labels_trace_u16; csrc/ring_trace.h), exteriors counterclockwise on a
+        north-up map, holes clockwise, ordered by label and start vertex.  Host code; no weights needed."""
+        labels = np.asarray(labels)
+        if labels.dtype != np.uint16 or labels.ndim != 2:
+            raise TypeError(f"labels_trace_u16 takes a uint16 raster [H, W], got {labels.dtype} {labels.shape}")
+        labels = np.ascontiguousarray(labels)
+        H, W = labels.shape
+        counts = np.zeros(2, np.uint64)
+        self._check(self._lib.s2sr_labels_trace_u16(self._h, _ptr(labels), H, W, int(Z), 0, 0, None, None, None, _ptr(counts)), "s2sr_labels_trace_u16")
+        V, R = int(counts[0]), int(counts[1])
+        xy, ring_start, ring_label = np.zeros((V, 2), np.int32), np.zeros(R + 1, np.int32), np.zeros(R, np.uint16)
+        if R:
+            self._check(self._lib.s2sr_labels_trace_u16(self._h, _ptr(labels), H, W, int(Z), V, R, _ptr(xy), _ptr(ring_start), _ptr(ring_label),
+                                                        _ptr(counts)), "s2sr_labels_trace_u16")
+        return xy, ring_start, ring_label
 
     # -- multi-GPU building blocks (device pointers) ------------------------------------------
     def cut_windows_u8_dev(self, d_img: int, H: int, W: int, tile: int, pad: int, first: int, count: int,

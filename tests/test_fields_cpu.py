@@ -1,0 +1,381 @@
+"""Fields from the image without a GPU: the definition's model (tests/fields_model.py) on hand-made cases and against
+scipy, the host policy (s2sr/fields.py: every refusal of the option, polygons, GeoJSON, the metadata block), the ring tracer's round
+trip through the polygon model of 7.9, csrc/ring_trace.h under the address and undefined-behaviour sanitizers, the C ABI's
+declarations, and the job's refusals."""
+import json
+import re
+import shutil
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import fields_model as fm
+import zones_model as zm
+from s2sr import fields as xf
+from s2sr import geo, native
+from s2sr import rasterio_lite as rio
+
+REPO = Path(__file__).resolve().parent.parent
+HEADER = (REPO / "include" / "s2sr.h").read_text()
+N = fm.NODATA
+
+
+# ---- the model -----------------------------------------------------------------------------------------------------------------------------
+def test_the_model_on_hand_made_cases():
+    idx = np.array([[5, 5, 0, 5, N],
+                    [0, 5, 0, 0, 5],
+                    [5, 0, 5, 5, 5],
+                    [9, 0, N, 5, 0]], np.int16)
+    labels, fields, found = fm.segment(idx, 5, 5, conn=4, Z=6)
+    assert labels.tolist() == [[1, 1, 0, 2, 0],
+                               [0, 1, 0, 0, 3],
+                               [4, 0, 3, 3, 3],
+                               [0, 0, 0, 3, 0]] and found == 4
+    assert fields.tolist() == [[10, 0, 0, 0, 0, 0], [3, 0, 0, 0, 2, 2], [1, 3, 3, 0, 4, 1], [5, 9, 2, 1, 5, 4], [1, 10, 0, 2, 1, 3], [0] * 6, [0] * 6]
+    labels8, fields8, found8 = fm.segment(idx, 5, 5, conn=8, Z=6)
+    assert labels8.tolist() == [[1, 1, 0, 1, 0],
+                                [0, 1, 0, 0, 1],
+                                [1, 0, 1, 1, 1],
+                                [0, 0, 0, 1, 0]] and found8 == 1 and fields8[1].tolist() == [10, 0, 0, 0, 5, 4]      # (1, 1) meets (2, 0) and (2, 2) diagonally
+    # min_pixels drops the small ones and the numbering closes up; a Z below found writes the rest as 0 and found still counts them
+    labels, fields, found = fm.segment(idx, 5, 5, conn=4, min_pixels=3, Z=6)
+    assert found == 2 and labels.tolist() == [[1, 1, 0, 0, 0], [0, 1, 0, 0, 2], [0, 0, 2, 2, 2], [0, 0, 0, 2, 0]] and fields[0, 0] == 12
+    labels, fields, found = fm.segment(idx, 5, 5, conn=4, Z=2)
+    assert found == 4 and labels.max() == 2 and fields.shape == (3, 6) and fields[:, 0].tolist() == [16, 3, 1]
+    # the range is closed, nodata is never inside it
+    assert fm.mask(idx, -32767, 32767).sum() == 18 and fm.mask(idx, 6, 9).sum() == 1 and fm.mask(idx, 0, 0).sum() == 7
+
+
+def test_the_morphology_of_the_model():
+    m = np.zeros((7, 9), bool)
+    m[0:3, 0:4] = True                                             # a field in the corner
+    m[5, 7] = True                                                 # a speck
+    assert (fm.erode(m, 1) == np.pad(np.ones((2, 3), bool), ((0, 5), (0, 6)))).all()          # the raster's edge does not eat it
+    assert (fm.dilate(fm.erode(m, 1), 1)[0:3, 0:4]).all() and not fm.dilate(fm.erode(m, 1), 1)[5, 7]
+    assert (fm.erode(m, 0) == m).all() and (fm.dilate(m, 0) == m).all()
+    assert fm.erode(np.ones((3, 3), bool), 8).all() and not fm.dilate(np.zeros((3, 3), bool), 8).any()
+    hole = np.ones((7, 9), bool)
+    hole[3, 4] = False
+    assert fm.erode(fm.dilate(hole, 1), 1).all()                    # a close fills the pinhole
+    idx = fm.as_index(hole, nodata=~hole)
+    labels, fields, found = fm.segment(idx, 4000, 32767, r_close=1)
+    assert found == 1 and labels[3, 4] == 0 and fields[1].tolist() == [62, 0, 0, 0, 9, 7]      # but never a nodata pixel
+
+
+@pytest.mark.parametrize("conn", [4, 8])
+def test_the_model_against_scipy(conn):
+    ndi = pytest.importorskip("scipy.ndimage")
+    for (H, W) in ((37, 45), (64, 64), (65, 129)):
+        for name in ("noise", "spiral", "checker", "rings", "blobs"):
+            idx = fm.patterns(H, W)[name]
+            labels, fields, found = fm.segment(idx, 4000, 32767, conn=conn)
+            ref, n = ndi.label(fm.mask(idx, 4000, 32767), structure=np.ones((3, 3), int) if conn == 8 else None)
+            assert n == found
+            # up to renumbering by first pixel: scipy numbers in scan order of the first pixel too, but the test does not rely on it
+            first = {}
+            for v, l in zip(ref.ravel().tolist(), labels.ravel().tolist()):
+                if v:
+                    assert first.setdefault(v, l) == l and l > 0
+                else:
+                    assert l == 0
+            assert sorted(first.values()) == list(range(1, n + 1))
+            assert fields[1:n + 1, 0].tolist() == [int((labels == l).sum()) for l in range(1, n + 1)]
+
+
+# ---- the rings: round trip through the polygon model of 7.9 ---------------------------------------------------------------------------------
+def burn(xy, ring_start, ring_label, Z, H, W):
+    """every label's rings as one feature of zones_model, corners scaled to 1 / 256 pixel"""
+    feats = []
+    for l in sorted(set(ring_label.tolist())):
+        rings = [[(256 * int(x), 256 * int(y)) for x, y in xy[ring_start[k]:ring_start[k + 1]]] for k in np.flatnonzero(ring_label == l)]
+        feats.append((rings, l))
+    if not feats:
+        return np.zeros((H, W), np.uint16)
+    return zm.rasterize(feats, Z, H, W)[0]
+
+
+@pytest.mark.parametrize("name", sorted(fm.trace_rasters()))
+def test_traced_rings_burn_back_to_the_raster(name):
+    labels = fm.trace_rasters()[name]
+    Z = 9
+    xy, ring_start, ring_label = fm.trace(labels, Z)
+    want = np.where(labels <= Z, labels, 0).astype(np.uint16)
+    assert (burn(xy, ring_start, ring_label, Z, *labels.shape) == want).all()
+    for k in range(len(ring_label)):
+        ring = xy[ring_start[k]:ring_start[k + 1]]
+        assert len(ring) >= 4 and tuple(ring[0][::-1]) == min(tuple(v[::-1]) for v in ring.tolist())      # starts at its smallest (y, x)
+        nxt = np.roll(ring, -1, axis=0)
+        assert ((ring[:, 0] == nxt[:, 0]) != (ring[:, 1] == nxt[:, 1])).all()                              # axis-parallel edges
+        prv = np.roll(ring, 1, axis=0)
+        assert ((ring[:, 0] == nxt[:, 0]) != (ring[:, 0] == prv[:, 0])).all()                              # no collinear vertex
+    order = [(int(ring_label[k]), int(xy[ring_start[k]][1]), int(xy[ring_start[k]][0])) for k in range(len(ring_label))]
+    assert order == sorted(order)
+
+
+def test_rings_written_out():
+    t = fm.trace_rasters()
+    xy, rs, rl = fm.trace(t["one"], 9)
+    assert xy.tolist() == [[0, 0], [0, 1], [1, 1], [1, 0]] and rs.tolist() == [0, 4] and rl.tolist() == [1]      # counterclockwise on a north-up map
+    assert fm.ring_area2(xy) == -2
+    xy, rs, rl = fm.trace(t["hole"], 9)
+    assert rl.tolist() == [1, 1, 2, 3]
+    assert xy[rs[0]:rs[1]].tolist() == [[1, 1], [1, 8], [9, 8], [9, 1]] and xy[rs[1]:rs[2]].tolist() == [[3, 3], [7, 3], [7, 6], [3, 6]]      # the hole runs clockwise
+    assert fm.ring_area2(xy[rs[1]:rs[2]]) == 24 and xy[rs[3]:rs[4]].tolist() == [[10, 0], [10, 1], [11, 1], [11, 0]]
+    xy, rs, rl = fm.trace(t["diagonal"], 9)
+    assert rl.tolist() == [1] * 5 + [2] * 3                                           # a diagonal chain: five rings that touch
+    assert fm.trace(t["none"], 9)[1].tolist() == [0]
+    xy, rs, rl = fm.trace(t["pinch"], 9)
+    assert rl.tolist() == [4, 4] and 70 not in rl                                     # two holes that meet at a corner are one ring that touches itself
+    assert len(xy[rs[1]:rs[2]]) == 8 and xy[rs[1]:rs[2]].tolist().count([4, 4]) == 2
+
+
+def test_ring_trace_under_address_and_ub_sanitizers(tmp_path):
+    """csrc/ring_trace.h walks a caller's raster and sizes tables from what it finds: tests/native/ring_trace_main.cpp drives it on
+    exact-size heap blocks under ASan / UBSan, takes every result through the capacity protocol and prints the rings, which are the
+    model's: the hand-made rasters and the labels of the GPU tests' patterns."""
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = tmp_path / "ring_trace"
+    b = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                        "-I", str(REPO / "sentinel2-super-resolution-poc_amd" / "csrc"),
+                        str(REPO / "tests" / "native" / "ring_trace_main.cpp"), "-o", str(exe)], capture_output=True, text=True, timeout=300)
+    if b.returncode != 0 and "asan" in (b.stderr or "").lower() and "cannot find" in b.stderr:
+        pytest.skip("sanitizer runtime not installed")
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ok" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
+    cases = [(l, 9) for _, l in sorted(fm.trace_rasters().items())]
+    for name, kw in (("blobs", dict(r_open=1, r_close=1)), ("rings", dict(conn=8)), ("checker", dict(Z=40))):
+        cases.append((fm.segment(fm.patterns(37, 45)[name], 4000, 32767, **kw)[0], kw.get("Z", 65535)))
+    text = "\n".join(f"{l.shape[0]} {l.shape[1]} {Z} " + " ".join(str(v) for v in l.ravel().tolist()) for l, Z in cases)
+    (tmp_path / "cases.txt").write_text(f"{len(cases)}\n{text}\n")
+    r = subprocess.run([str(exe), str(tmp_path / "cases.txt")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-500:], r.stderr[-3000:])
+    lines = r.stdout.strip().split("\n")
+    at = 0
+    for i, (l, Z) in enumerate(cases):
+        xy, rs, rl = fm.trace(l, Z)
+        assert lines[at] == f"case {i} {len(xy)} {len(rl)}", lines[at]
+        for k in range(len(rl)):
+            assert lines[at + 1 + k] == f"{rl[k]}:" + "".join(f" {x} {y}" for x, y in xy[rs[k]:rs[k + 1]].tolist()), (i, k)
+        at += 1 + len(rl)
+    assert at == len(lines)
+
+
+# ---- s2sr/fields.py --------------------------------------------------------------------------------------------------------------------------
+DEFS = [{"name": "ndvi", "K": 10000}, {"name": "ndwi", "K": 5000}]
+GOOD = {"index": "ndvi", "min": 0.3, "max": None, "open": 1, "close": 2, "connectivity": 4, "min_area_ha": 0.5}
+
+
+def test_resolve_turns_index_units_into_integers():
+    p = xf.resolve({"segment": GOOD}, DEFS, 6.25)
+    assert p == {"index": 0, "name": "ndvi", "K": 10000, "lo": 3000, "hi": 32767, "r_open": 1, "r_close": 2, "conn": 4, "min_pixels": 800}
+    p = xf.resolve({"segment": {"index": "ndwi", "min": None, "max": -0.1, "min_pixels": 7, "connectivity": 8, "open": 0, "close": 8}}, DEFS, None)
+    assert p == {"index": 1, "name": "ndwi", "K": 5000, "lo": -32767, "hi": -500, "r_open": 0, "r_close": 8, "conn": 8, "min_pixels": 7}
+    assert xf.resolve({"segment": {"index": "ndvi", "min_area_ha": 0.001}}, DEFS, 100.0)["min_pixels"] == 1
+    assert xf.resolve({"segment": {"index": "ndvi", "min_area_ha": 0.0101}}, DEFS, 100.0)["min_pixels"] == 2           # ceil
+    d = xf.resolve({"segment": {"index": "ndvi", "min_pixels": 1}}, DEFS, None)                                    # the defaults
+    assert (d["lo"], d["hi"], d["r_open"], d["r_close"], d["conn"]) == (3000, 32767, 1, 2, 4)
+    assert xf.resolve({"segment": {"index": "ndvi", "min": -9.0, "max": 9.0, "min_pixels": 1}}, DEFS, None)["lo"] == -32767
+    assert xf.is_segment({"segment": {}}) and not xf.is_segment({"geojson": {}}) and not xf.is_segment("x.geojson") and not xf.is_segment(None)
+
+
+@pytest.mark.parametrize("change,text", [
+    ({"colour": 1}, "unknown key"), ({"index": "evi"}, "not among"), ({"index": None}, "index"), ({"min": 0.5, "max": 0.4}, "min 0.5 > max 0.4"),
+    ({"min": "0.3"}, "min"), ({"max": float("nan")}, "max"), ({"open": 9}, "open"), ({"open": -1}, "open"), ({"close": 9}, "close"),
+    ({"close": 1.5}, "close"), ({"connectivity": 6}, "connectivity"), ({"connectivity": "8"}, "connectivity"), ({"min_pixels": 5}, "exactly one"),
+    ({"min_area_ha": None}, "exactly one"), ({"min_area_ha": 0}, "min_area_ha"), ({"min_area_ha": -1.0}, "min_area_ha"),
+    ({"min_area_ha": None, "min_pixels": 0}, "min_pixels"), ({"min_area_ha": None, "min_pixels": 2.5}, "min_pixels")])
+def test_every_refusal_of_the_option(change, text):
+    with pytest.raises(ValueError, match=text):
+        xf.resolve({"segment": dict(GOOD, **change)}, DEFS, 6.25)
+
+
+def test_refusals_of_the_options_form():
+    for bad in ({"segment": GOOD, "property": "x"}, {"segment": [1]}, {"segment": None}, {"geojson": {}}):
+        with pytest.raises(ValueError):
+            xf.resolve(bad, DEFS, 6.25)
+    with pytest.raises(ValueError, match="pixel size"):
+        xf.resolve({"segment": GOOD}, DEFS, None)
+    with pytest.raises(ValueError, match="segment index 'ndvi' is not among"):
+        xf.resolve({"segment": GOOD}, [], 6.25)
+
+
+class _StubEngine:
+    """fields_segment_i16 answers `found` without a device; what s2sr.fields.segment makes of it"""
+    import threading
+    chain_lock = threading.RLock()
+
+    def __init__(self, found):
+        self.found, self.traced = found, 0
+
+    def fields_segment_i16(self, idx, lo, hi, **kw):
+        assert kw["Z"] == 65535
+        labels, fields, _ = fm.segment(idx, lo, hi, **kw)
+        return labels, fields, self.found
+
+    def labels_trace_u16(self, labels, Z):
+        self.traced += 1
+        return fm.trace(labels, Z)
+
+
+def test_segment_refuses_no_field_and_more_than_65535():
+    idx = fm.patterns(37, 45)["blobs"]
+    params = dict(xf.resolve({"segment": dict(GOOD, min_area_ha=None, min_pixels=3)}, DEFS, None), lo=4000)
+    want = fm.segment(idx, 4000, 32767, r_open=1, r_close=2, conn=4, min_pixels=3)
+    got = xf.segment(_StubEngine(want[2]), idx, params)
+    assert (got["labels"] == want[0]).all() and got["found"] == want[2] and got["fields"].shape == (want[2] + 1, 6) and len(got["rings"]) == 3
+    over = _StubEngine(65536)
+    with pytest.raises(ValueError, match="found 65536 fields.*65535.*raise the minimum area"):
+        xf.segment(over, idx, params)
+    none = _StubEngine(0)
+    with pytest.raises(ValueError, match="found no field"):
+        xf.segment(none, idx, params)
+    assert over.traced == none.traced == 0                          # refused before the rings are walked
+
+
+def georef(epsg, x0, y0, dx, dy):
+    return rio.GeoRef({rio.TAG_PIXEL_SCALE: (dx, dy, 0.0), rio.TAG_TIEPOINT: (0.0, 0.0, 0.0, x0, y0, 0.0),
+                       rio.TAG_GEOKEYS: (1, 1, 0, 3, 1024, 0, 1, 1, 1025, 0, 1, 1, 3072, 0, 1, epsg)})
+
+
+def known_raster():
+    """label 1: a frame with a hole that holds an island of label 1 and one of label 2; label 3: two parts"""
+    a = np.zeros((12, 14), np.uint16)
+    a[1:10, 1:10] = 1
+    a[3:8, 3:8] = 0
+    a[5, 5] = 1
+    a[4, 6] = 2
+    a[0, 12:14] = 3
+    a[11, 0:3] = 3
+    return a
+
+
+def fields_of(labels, Z):
+    f = np.zeros((Z + 1, 6), np.int64)
+    for l in range(1, Z + 1):
+        ys, xs = np.nonzero(labels == l)
+        f[l] = len(ys), (ys * labels.shape[1] + xs).min(), xs.min(), ys.min(), xs.max() + 1, ys.max() + 1
+    f[0, 0] = labels.size - f[1:, 0].sum()
+    return f
+
+
+def test_polygons_on_a_known_label_raster():
+    a = known_raster()
+    fields = fields_of(a, 3)
+    polys = xf.polygons(fm.trace(a, 3), fields)
+    assert [p["label"] for p in polys] == [1, 2, 3] and [p["pixels"] for p in polys] == [81 - 25 + 1, 1, 5]
+    assert polys[0]["bbox"] == [1, 1, 10, 10] and polys[2]["bbox"] == [0, 0, 14, 12]
+    frame, island = polys[0]["polygons"]                            # by start vertex: the frame (with its hole), then the island in the hole
+    assert [r.tolist() for r in frame] == [[[1, 1], [1, 10], [10, 10], [10, 1]], [[3, 3], [8, 3], [8, 8], [3, 8]]]
+    assert [r.tolist() for r in island] == [[[5, 5], [5, 6], [6, 6], [6, 5]]]
+    assert len(polys[1]["polygons"]) == 1 and len(polys[2]["polygons"]) == 2
+    assert [r.tolist() for r in polys[2]["polygons"][0]] == [[[12, 0], [12, 1], [14, 1], [14, 0]]]
+    # an island of the same label inside a hole of a frame inside a hole: every hole goes with the smallest exterior around it
+    b = np.zeros((13, 13), np.uint16)
+    b[0:13, 0:13] = 1
+    b[2:11, 2:11] = 0
+    b[4:9, 4:9] = 1
+    b[6, 6] = 0
+    polys = xf.polygons(fm.trace(b, 1), fields_of(b, 1))
+    outer, inner = polys[0]["polygons"]
+    assert [len(outer), len(inner)] == [2, 2] and inner[1].tolist() == [[6, 6], [7, 6], [7, 7], [6, 7]] and outer[1].tolist() == [[2, 2], [11, 2], [11, 11], [2, 11]]
+
+
+def test_to_geojson_on_a_known_label_raster():
+    a = known_raster()
+    x0, y0 = 600000.0, 5100000.0
+    g = georef(32633, x0, y0, 2.5, 2.5)
+    tables = {"ndvi": [{"zone": 0, "count": 9, "mean": 0.0, "std": 0.0}, {"zone": 1, "count": 57, "mean": 0.5, "std": 0.25},
+                       {"zone": 3, "count": 5, "mean": 0.75, "std": 0.125}]}
+    fc = xf.to_geojson(xf.polygons(fm.trace(a, 3), fields_of(a, 3)), g, (2.5, 2.5), tables)
+    assert fc["type"] == "FeatureCollection" and [f["id"] for f in fc["features"]] == [1, 2, 3]
+    f1, f2, f3 = fc["features"]
+    assert f1["geometry"]["type"] == "MultiPolygon" and f2["geometry"]["type"] == "Polygon" and f3["geometry"]["type"] == "MultiPolygon"
+    assert f1["properties"] == {"label": 1, "pixels": 57, "area_ha": 57 * (6.25 / 10000.0), "bbox": [1, 1, 10, 10], "ndvi": {"mean": 0.5, "std": 0.25}}
+    assert f2["properties"]["ndvi"] is None and f3["properties"]["ndvi"] == {"mean": 0.75, "std": 0.125}
+    assert json.loads(json.dumps(fc)) == fc
+    crs = geo.CRS(32633)
+    ring = f1["geometry"]["coordinates"][0][0]
+    assert ring[0] == ring[-1] and len(ring) == 5                   # closed
+    x, y = crs.from_lonlat(np.array([p[0] for p in ring]), np.array([p[1] for p in ring]))
+    assert np.abs(x - (x0 + 2.5 * np.array([1, 1, 10, 10, 1]))).max() < 1e-3 and np.abs(y - (y0 - 2.5 * np.array([1, 10, 10, 1, 1]))).max() < 1e-3
+    # RFC 7946: exteriors counterclockwise in lon / lat, holes clockwise
+    area2 = lambda r: sum(a[0] * b[1] - b[0] * a[1] for a, b in zip(r[:-1], r[1:]))
+    for f in fc["features"]:
+        polys = [f["geometry"]["coordinates"]] if f["geometry"]["type"] == "Polygon" else f["geometry"]["coordinates"]
+        for poly in polys:
+            assert area2(poly[0]) > 0 and all(area2(h) < 0 for h in poly[1:])
+    # the features burn back to the raster through the policy of 7.9
+    from s2sr import zones as xz
+    grid = xz.to_grid(xz.read(fc), g, a.shape, 1)
+    burnt = zm.rasterize(zm.from_tables(grid["xy"], grid["ring_start"], grid["feat_start"], [1, 2, 3]), 3, *a.shape)[0]
+    assert (burnt == a).all()
+    for bad in (None, rio.GeoRef({}), georef(2154, 1.0, 2.0, 10.0, 10.0)):
+        with pytest.raises(ValueError):
+            xf.to_geojson([], bad)
+
+
+def test_metadata_block():
+    a = known_raster()
+    params = xf.resolve({"segment": GOOD}, DEFS, 6.25)
+    block = xf.metadata_block(params, 3, fields_of(a, 3), a.shape, Path("out/x_zones.tif"), Path("out/x_fields.geojson"), (2.5, 2.5))
+    assert block["source"] == "segment" and block["found"] == 3 and block["grid"] == [12, 14] and block["zone_scale"] == 1
+    assert block["parameters"] == {"name": "ndvi", "K": 10000, "lo": 3000, "hi": 32767, "r_open": 1, "r_close": 2, "conn": 4, "min_pixels": 800}
+    assert block["labels"][0] == {"label": 1, "pixels": 57, "area_ha": 57 * (6.25 / 10000.0), "bbox": [1, 1, 10, 10]} and len(block["labels"]) == 3
+    assert block["file"] == "out/x_zones.tif" and block["geojson"] == "out/x_fields.geojson" and json.loads(json.dumps(block)) == block
+    assert xf.metadata_block(params, 3, fields_of(a, 3), a.shape, None, None, None)["labels"][2]["area_ha"] is None
+
+
+# ---- the C ABI and the job -------------------------------------------------------------------------------------------------------------------
+def test_the_entries_are_declared_and_refuse_a_null_handle():
+    for name, n in (("s2sr_fields_segment_i16", 14), ("s2sr_labels_trace_u16", 11), ("s2sr_debug_fields_stage_ms", 3)):
+        assert name in native.EXPORTED_SYMBOLS and re.search(rf"\b{name}\(", HEADER)
+        decl = re.search(rf"{name}\(([^;]*)\);", HEADER).group(1)
+        assert len([a for a in re.sub(r"/\*.*?\*/", "", decl).split(",") if a.strip()]) == len(native._PROTOS[name][1]) == n
+    lib = native.load_library()
+    assert lib.s2sr_fields_segment_i16(None, None, 1, 1, 0, 0, 0, 0, 4, 1, 1, None, None, None) == -1
+    assert lib.s2sr_labels_trace_u16(None, None, 1, 1, 1, 0, 0, None, None, None, None) == -1
+    assert lib.s2sr_debug_fields_stage_ms(None, None, None) == -1
+    stages = [int(v) for _, v in sorted(re.findall(r"#define S2SR_FIELDS_STAGE_(\w+) (\d+)", HEADER), key=lambda m: int(m[1]))]
+    assert stages == list(range(len(native.FIELDS_STAGES))) and int(re.search(r"#define S2SR_FIELDS_STAGES (\d+)", HEADER).group(1)) == len(stages) == 8
+    # the tracer's contract says what the code does: a ring may touch itself at a corner, and burns back exactly
+    for text in (HEADER[HEADER.index("Labels to rings"):HEADER.index("s2sr_labels_trace_u16(")],
+                 (REPO / "sentinel2-super-resolution-poc_amd" / "csrc" / "ring_trace.h").read_text()):
+        assert "MAY TOUCH ITSELF" in text and "no ring touches itself" not in text and "burn back to exactly" in text
+    text = HEADER[HEADER.index("Fields from the image"):HEADER.index("s2sr_fields_segment_i16(")]
+    assert "scratch" in text and "voids" in text and "keeps nothing" in text
+
+
+def test_the_tracer_through_the_library_needs_no_device():
+    """s2sr_labels_trace_u16 is host code behind a handle: without a GPU no handle can be made, so this runs the Python wrapper's
+    checks only"""
+    with pytest.raises(TypeError):
+        native.Engine.labels_trace_u16(None, np.zeros((2, 2), np.int16), 1)
+    with pytest.raises(TypeError):
+        native.Engine.fields_segment_i16(None, np.zeros((2, 2), np.uint16), 0, 1)
+
+
+def test_the_job_refuses_a_bad_segment_option_before_anything_is_created(tmp_path):
+    from app.job_options import JobOptions
+    from app.wow_sr import process_wow_sr
+    good = {"segment": GOOD}
+    JobOptions(bit_depth=16, indices=["ndvi"], zones=good).check(False, 4)
+    for bad, text in (({"segment": dict(GOOD, colour=1)}, "unknown key"), ({"segment": dict(GOOD, index="ndwi")}, "not among"),
+                      ({"segment": dict(GOOD, min=0.9, max=0.1)}, "min 0.9 > max 0.1"), ({"segment": dict(GOOD, open=9)}, "open"),
+                      ({"segment": dict(GOOD, connectivity=5)}, "connectivity"), ({"segment": dict(GOOD, min_pixels=3)}, "exactly one"),
+                      ({"segment": {"index": "ndvi"}}, "exactly one")):
+        with pytest.raises(ValueError, match=text):
+            JobOptions(bit_depth=16, indices=["ndvi"], zones=bad).check(False, 4)
+    with pytest.raises(ValueError, match="belong to indices"):
+        JobOptions(bit_depth=16, zones=good).check(False, 4)
+    # through the job: a 4-band GeoTIFF, refused before the output directory exists
+    rng = np.random.default_rng(1)
+    src = tmp_path / "scene4.tif"
+    rio.write_geotiff_u16(src, rng.integers(1000, 4000, size=(8, 8, 4)).astype(np.uint16), georef(32633, 600000.0, 5100000.0, 10.0, 10.0))
+    with pytest.raises(ValueError, match="not among"):
+        process_wow_sr(src, tmp_path / "out", enhance_crops=False, model="realesrgan_anime", bit_depth=16, indices=["ndvi"],
+                       zones={"segment": dict(GOOD, index="savi")})
+    assert not (tmp_path / "out").exists()
