@@ -47,8 +47,6 @@ void drop_graphs(s2sr_handle* h) {   // buffers or weights moved: every captured
     h->graphs.clear();
 }
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mos_px = 0) {
     Workspace& w = h->ws;
     const bool fp8 = h->cfg.precision == S2SR_PREC_FP8, hp = h->hp();
@@ -85,12 +83,12 @@ int ensure_workspace(s2sr_handle* h, int G, int H, int W, int mos_py = 0, int mo
     size_t off = 0;
     auto take = [&](size_t b) {
         size_t o = off;
-        off += align256(b);
+        off += up256(b);
         if (rz && b) { zoned.push_back({o, b}); off += rz; }
         return o;
     };
     auto zone_planes = [&]() -> int {
-        for (const Plane& p : zoned) HIPCHK(h, redzone_add_plane(w.base, w.base + p.off, p.bytes, align256(p.bytes) - p.bytes + rz));
+        for (const Plane& p : zoned) HIPCHK(h, redzone_add_plane(w.base, w.base + p.off, p.bytes, up256(p.bytes) - p.bytes + rz));
         return S2SR_OK;
     };
     if (h->compact()) {
@@ -1041,7 +1039,7 @@ static int load_weights_locked(s2sr_handle* h, const float* d_blob, size_t n_flo
         if (h->at[l.role] < 0) h->at[l.role] = (int)i;
         if (is_rdb(l.role)) {
             poff[i] = pool_bytes;
-            pool_bytes += align256(fp8 ? conv_wpack_bytes_f8(l.cin, l.cout) : conv_wpack_bytes(l.cin, l.cout));
+            pool_bytes += up256(fp8 ? conv_wpack_bytes_f8(l.cin, l.cout) : conv_wpack_bytes(l.cin, l.cout));
         }
     }
     // pool_b, per conv: [64 bias], compact: [64 bias | 64 slopes], built on the host (the last conv's rows are permuted)

@@ -671,7 +671,7 @@ static int enhance_locked(s2sr_handle* h, const s2sr_enhance_args& c) {
     const size_t win_in = (size_t)wh * ww * 3, win_out = win_in * scale * scale;      // samples per window, in and out
     const size_t row_b = (size_t)OW * 3 * esz;                                         // bytes of one output row
     // ---- staging.  SL_DST: the quantised image, then the fp32 image (the overwrite paste makes one of them per call)
-    const size_t f_off = over ? 0 : (opx * esz + 255) & ~(size_t)255;
+    const size_t f_off = over ? 0 : up256(opx * esz);
     const Slot tslot = over && !p.tiled ? SL_MID : SL_CHUNK;
     const size_t tile_b = over ? (size_t)nx * ny * win_out * (c.out_f32 ? 4 : 1) : (size_t)(p.max_rows + carry) * nx * win_out * sizeof(float);
     if ((rc = ensure_scratch(h, {{SL_SRC, ipx * esz}, {SL_DST, c.out_f32 ? f_off + opx * 4 : over ? opx : f_off},
@@ -920,9 +920,7 @@ static int consistency_impl(s2sr_handle* h, const void* sr, const void* img, int
     hipStream_t st = h->stream;
     int rc = ensure_scratch(h, {{SL_SRC, ipx * esz}, {SL_DST, row_b * OH}, {SL_CONS, cons_scratch_bytes(mode, H, W)}});
     if (rc) return rc;
-    size_t rows = band_rows > 0 ? (size_t)band_rows : ((size_t)32 << 20) / row_b;      // the library's choice: ~32 MB
-    if (rows < 1) rows = 1;
-    if (rows > (size_t)OH) rows = OH;
+    const size_t rows = band_of(band_rows, OH, row_b, (size_t)32 << 20);               // the library's choice: ~32 MB
     ConsRun cr;
     cr.mode = mode; cr.H = H; cr.W = W; cr.S = S; cr.u16 = u16;
     if (u16) { cr.lo = lo; cr.hi = hi; }

@@ -59,9 +59,7 @@ int carry_band_impl(s2sr_handle* h, const uint16_t* sr, const uint16_t* band, in
     HIPCHK(h, hipMemsetAsync(d_cnt, 0, kHead, st));
     HIPCHK(h, hipMemcpyAsync(d_band, band, px * 2, hipMemcpyHostToDevice, st));
     if (valid) HIPCHK(h, hipMemcpyAsync(d_valid, valid, px, hipMemcpyHostToDevice, st));
-    size_t rows = band_rows > 0 ? (size_t)band_rows : ((size_t)32 << 20) / grow_b;     // the library's choice: ~32 MB of guide
-    if (rows < 1) rows = 1;
-    if (rows > (size_t)OH) rows = OH;
+    const size_t rows = band_of(band_rows, OH, grow_b, (size_t)32 << 20);              // the library's choice: ~32 MB of guide
     int c_done = 0, a_done = 0;                               // input rows whose coefficients are there; block rows that have left
     for (size_t y0 = 0; y0 < (size_t)OH; y0 += rows) {
         const int y1 = (int)(y0 + rows < (size_t)OH ? y0 + rows : OH);

@@ -40,10 +40,8 @@ int plan_source(s2sr_handle* h, const char* who, const uint16_t* img, int H, int
         return fail(h, S2SR_E_INVALID, b);
     }
     // the library's choice: ~32 MB of samples per band (its upload hides the band before's kernel); never more than one launch counts
-    size_t rows = band_rows > 0 ? (size_t)band_rows : ((size_t)16 << 20) / s.row_s;
-    if (rows < 1) rows = 1;
+    size_t rows = band_of(band_rows, H, s.row_s, (size_t)16 << 20);                     // (counted in samples here)
     if (rows > kBandSamples / s.row_s) rows = kBandSamples / s.row_s;
-    if (rows > (size_t)H) rows = H;
     s.rows = (int)rows;
     s.nbands = (H + s.rows - 1) / s.rows;
     return S2SR_OK;
@@ -68,7 +66,7 @@ int display_hist_impl(s2sr_handle* h, const uint16_t* img, int H, int W, int nod
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
-    if ((rc = ensure_scratch(h, {{SL_SRC, (s.total * 2 + 255) & ~(size_t)255, img != nullptr}, {SL_TABLES, kHistBytes + kLutBytes}}))) return rc;
+    if ((rc = ensure_scratch(h, {{SL_SRC, up256(s.total * 2), img != nullptr}, {SL_TABLES, kHistBytes + kLutBytes}}))) return rc;
     if ((rc = ensure_group_events(h, 4))) return rc;
     const uint16_t* d_img = scratch<const uint16_t>(h, s.in.slot);
     unsigned long long* d_hist = scratch<unsigned long long>(h, SL_TABLES);
@@ -102,7 +100,7 @@ int display_apply_impl(s2sr_handle* h, const uint16_t* img, int H, int W, const 
     DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
     const Slot out_slot = other(s.in.slot);                   // the 8-bit image: the other of 0 / 1, as the pyramid calls do
-    if ((rc = ensure_scratch(h, {{SL_SRC, (s.total * 2 + 255) & ~(size_t)255, img != nullptr}, {out_slot, s.total}, {SL_TABLES, kHistBytes + kLutBytes}}))) return rc;
+    if ((rc = ensure_scratch(h, {{SL_SRC, up256(s.total * 2), img != nullptr}, {out_slot, s.total}, {SL_TABLES, kHistBytes + kLutBytes}}))) return rc;
     if ((rc = ensure_group_events(h, 4))) return rc;
     const uint16_t* d_img = scratch<const uint16_t>(h, s.in.slot);
     uint8_t* d_out = scratch<uint8_t>(h, out_slot);

@@ -12,7 +12,6 @@ using namespace s2sr::engine;
 
 namespace {
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 constexpr size_t kBandBytes = (size_t)64 << 20;                  // the rasters come and go in row bands of about this size
 
 int fields_impl(s2sr_handle* h, const int16_t* idx, int H, int W, int lo, int hi, int r_open, int r_close, int conn, int64_t min_pixels, int Z,
@@ -46,8 +45,7 @@ int fields_impl(s2sr_handle* h, const int16_t* idx, int H, int W, int lo, int hi
     uint32_t* d_sums = (uint32_t*)tab;
     unsigned long long* d_found = (unsigned long long*)(tab + o_found);
     unsigned long long* d_fields = (unsigned long long*)(tab + o_fields);
-    size_t rows = kBandBytes / row_i;
-    rows = rows < 1 ? 1 : rows > (size_t)H ? (size_t)H : rows;
+    const size_t rows = band_of(0, H, row_i, kBandBytes);
     for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
         const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
         HIPCHK(h, hipMemcpyAsync(d_idx + y0 * W, idx + y0 * W, (y1 - y0) * row_i, hipMemcpyHostToDevice, st));

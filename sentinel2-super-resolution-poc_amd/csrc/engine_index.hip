@@ -13,14 +13,7 @@ using namespace s2sr::engine;
 namespace {
 
 constexpr size_t kLutBytes = 65536 * 4;
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// the rows of one band: the caller's, or the library's choice of ~64 MB moved per band
-size_t band_of(int band_rows, int H, size_t row_bytes) {
-    size_t rows = band_rows > 0 ? (size_t)band_rows : ((size_t)64 << 20) / row_bytes;
-    if (rows < 1) rows = 1;
-    return rows > (size_t)H ? (size_t)H : rows;
-}
+constexpr size_t kBandBytes = (size_t)64 << 20;                  // the library's choice of what one band moves
 
 int index_nd_impl(s2sr_handle* h, const uint16_t* a, int ac, int ca, const uint16_t* b, int bc, int cb, int H, int W, int offset, int L, int K,
                   const uint8_t* valid, int vs, const uint16_t* zones, int zs, int Z, const uint8_t* lut, int band_rows, int16_t* out,
@@ -69,7 +62,7 @@ int index_nd_impl(s2sr_handle* h, const uint16_t* a, int ac, int ca, const uint1
     if (lut) HIPCHK(h, hipMemcpyAsync(d_lut, lut, kLutBytes, hipMemcpyHostToDevice, st));
     if (valid) HIPCHK(h, hipMemcpyAsync(d_valid, valid, vw * vh, hipMemcpyHostToDevice, st));
     if (zones) HIPCHK(h, hipMemcpyAsync(d_zones, zones, zw * zh * 2, hipMemcpyHostToDevice, st));
-    const size_t rows = band_of(band_rows, H, (a ? arow_b : 0) + brow_b + (out ? (size_t)W * 2 : 0) + (rgba ? (size_t)W * 4 : 0));
+    const size_t rows = band_of(band_rows, H, (a ? arow_b : 0) + brow_b + (out ? (size_t)W * 2 : 0) + (rgba ? (size_t)W * 4 : 0), kBandBytes);
     for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
         const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
         if (a) HIPCHK(h, hipMemcpyAsync((char*)d_a + y0 * arow_b, (const char*)a + y0 * arow_b, (y1 - y0) * arow_b, hipMemcpyHostToDevice, st));
@@ -108,7 +101,7 @@ int index_render_impl(s2sr_handle* h, const int16_t* idx, int H, int W, const ui
     uint8_t* d_rgba = scratch<uint8_t>(h, SL_DST);
     uint8_t* d_lut = scratch<uint8_t>(h, SL_TABLES);
     HIPCHK(h, hipMemcpyAsync(d_lut, lut, kLutBytes, hipMemcpyHostToDevice, st));
-    const size_t rows = band_of(band_rows, H, (size_t)W * 6);
+    const size_t rows = band_of(band_rows, H, (size_t)W * 6, kBandBytes);
     for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
         const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
         HIPCHK(h, hipMemcpyAsync(d_idx + y0 * W, idx + y0 * W, (y1 - y0) * W * 2, hipMemcpyHostToDevice, st));

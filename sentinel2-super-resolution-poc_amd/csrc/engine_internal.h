@@ -317,6 +317,14 @@ bool recover_stream(s2sr_handle* h);
         return rc_;                                  \
     } while (0)
 
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }   // the next multiple of 256: where the next table or plane starts
+// The rows of one band of a banded pass: the caller's band_rows, or the library's choice of budget_bytes moved per band (row_bytes:
+// what one row moves); at least 1, at most H.
+inline size_t band_of(int band_rows, size_t H, size_t row_bytes, size_t budget_bytes) {
+    const size_t rows = band_rows > 0 ? (size_t)band_rows : budget_bytes / row_bytes;
+    return rows < 1 ? 1 : rows > H ? H : rows;
+}
+
 constexpr size_t kTrashBytes = 8192;   // s2sr_handle::d_trash
 // Every device allocation the handle owns, each once: s2sr_destroy frees them, s2sr_debug_redzone_check counts the zoned ones.
 template <class F>

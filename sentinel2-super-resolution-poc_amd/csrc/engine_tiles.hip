@@ -239,7 +239,7 @@ static int tiles_write_png_locked(s2sr_handle* h, int32_t nx, int32_t ny, const 
     if ((rc = ensure_scratch(h, {{SL_MID, (size_t)n * tile_stats_b}, {SL_TABLES, png_plan_bytes(n)}}))) return rc;
     // the statistics come back into, and the plans go up from, ONE page-locked block kept on the handle (a z18 level: 40 MB down,
     // 27 MB up; as fresh pageable vectors each crossed PCIe through the runtime's staging and was page-faulted in first)
-    const size_t stats_b = ((size_t)n * tile_stats_b + 255) & ~(size_t)255, plan_b = png_plan_bytes(n);
+    const size_t stats_b = up256((size_t)n * tile_stats_b), plan_b = png_plan_bytes(n);
     if (h->host_arena_bytes < stats_b + plan_b) {
         if (h->host_arena) HIPCHK(h, host_free(h->host_arena));
         h->host_arena = nullptr; h->host_arena_bytes = 0;

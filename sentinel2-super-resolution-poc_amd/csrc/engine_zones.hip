@@ -12,8 +12,6 @@ using namespace s2sr::engine;
 
 namespace {
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 int zones_impl(s2sr_handle* h, const int32_t* xy, const int32_t* ring_start, const int32_t* feat_start, const uint16_t* label, int F, int Z, int H,
                int W, int band_rows, uint16_t* out, uint64_t* area) {
     if (!h) return S2SR_E_INVALID;
@@ -47,8 +45,7 @@ int zones_impl(s2sr_handle* h, const int32_t* xy, const int32_t* ring_start, con
     HIPCHK(h, hipMemcpyAsync(tab + o_start, bins.start.data(), (T + 1) * 4, hipMemcpyHostToDevice, st));
     if (nnz) HIPCHK(h, hipMemcpyAsync(tab + o_list, bins.feat.data(), nnz * 4, hipMemcpyHostToDevice, st));
     if (area) HIPCHK(h, hipMemsetAsync(d_area, 0, area_b, st));
-    size_t rows = band_rows > 0 ? (size_t)band_rows : ((size_t)64 << 20) / row_b;      // the caller's, or ~64 MB of labels per band
-    rows = rows < 1 ? 1 : rows > (size_t)H ? (size_t)H : rows;
+    const size_t rows = band_of(band_rows, H, row_b, (size_t)64 << 20);                // the caller's, or ~64 MB of labels per band
     for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
         const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
         {

@@ -12,6 +12,8 @@ units; valid an optional mask [H, W] (non-zero: valid); fill what invalid blocks
            g0 = floor((Abar I + Cbar + (den << 15)) / (den << 16)); g = clip(g0, lo, hi)
   exact    the consistency pass's exact step towards n p; invalid blocks = fill
   inexact  the valid blocks whose final sum differs from n p"""
+import functools
+
 import numpy as np
 
 import consistency_model as cm
@@ -130,3 +132,17 @@ def holes(H, W, seed):
         v[H - 2, W - 2] = 1
     v[0, 0] = 1
     return v
+
+
+@functools.lru_cache(maxsize=None)
+def case(H, W, S):
+    """(guide, band straying outside 1000..11000, mask): made once per shape and scale"""
+    q = scene(H, W, S, seed=5)
+    return q, stray_band(q, S, seed=6), holes(H, W, seed=7)
+
+
+@functools.lru_cache(maxsize=None)
+def modelled(H, W, S, lo, hi, w, r, eps, masked, fill=0):
+    """carry() on case(H, W, S): made once per parameter set"""
+    q, b, v = case(H, W, S)
+    return carry(q, b, S, lo, hi, w=w, r=r, eps=eps, valid=v if masked else None, fill=fill)

@@ -1,6 +1,8 @@
 """What the modules that run under a diagnostic mode share (red zones, poison, stall, grid cap; tests/test_gpu_redzones.py, _poison.py,
-_stall.py, _gridcap.py, and the nodata and consistency modules, which run under red zones): engines made and closed under a mode, the door
-table's baseline with every mode off, the byte-for-byte comparison and the red-zone verdict."""
+_stall.py, _gridcap.py, and the pass modules that run a case of their own under a mode): engines made and closed under a mode, the
+door table's baseline with every mode off, the two comparisons -- byte for byte against the baseline (same), sample for sample against
+a model with the first differing position (same_values) --, the red-zone verdict, and the grid cap in force with its counter
+(under, trips)."""
 import contextlib
 
 import numpy as np
@@ -82,6 +84,39 @@ def same(got, want, what):
         assert g.shape == w.shape and g.dtype == w.dtype, f"{what}: output {k} is {g.dtype} {g.shape}, the baseline {w.dtype} {w.shape}"
         differ = int((g.view(np.uint8) != w.view(np.uint8)).sum())
         assert differ == 0, f"{what}: {differ} of {g.nbytes} bytes of output {k} differ from the baseline"
+
+
+def same_values(got, want, what):
+    """sample for sample, dtype and shape included, against a model or another call; the message has the first differing position.
+    Tuples go member by member; a member for which `want` holds None has no model and is not judged."""
+    if isinstance(want, tuple):
+        assert isinstance(got, tuple) and len(got) == len(want), what
+        for k, (g, w) in enumerate(zip(got, want)):
+            if w is not None:
+                same_values(g, w, f"{what}, output {k}")
+        return
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} against {want.dtype} {want.shape}"
+    bad = np.argwhere(got != want)
+    assert len(bad) == 0, f"{what}: {len(bad)} samples differ, the first at {tuple(bad[0])}: {got[tuple(bad[0])]} against {want[tuple(bad[0])]}"
+
+
+@contextlib.contextmanager
+def under(cap):
+    """the grid cap in force and its counter at zero; afterwards the cap that was found"""
+    before = native.grid_cap_workgroups()
+    native.grid_cap(cap)
+    native.grid_cap_stats(reset=True)
+    try:
+        yield
+    finally:
+        native.grid_cap(before)
+
+
+def trips(*families):
+    """the largest trip count the grid-cap counter holds among these families (all: no argument), and the stats for the message"""
+    st = native.grid_cap_stats()
+    return max(t for f, (_, t) in st.items() if not families or f in families), st
 
 
 def clean(e, least=4, most=None):

@@ -1,10 +1,16 @@
 """The doors of the library as a table: id -> (engine config, fn(engine, inputs) -> arrays).  One entry is ONE call (or the short
-sequence that makes a door, such as base level + overview), on the smallest configs and shapes that take each route.  Three
+sequence that makes a door, such as base level + overview), on the smallest configs and shapes that take each route.  Four
 modules judge every entry, each under one diagnostic mode of the library: tests/test_gpu_redzones.py (no store outside a buffer),
-tests/test_gpu_poison.py (no load of bytes nobody wrote) and tests/test_gpu_stall.py (no dependence on which stream runs first);
-tests/diag.py holds what they share.  `inputs` lets a judge ask for the same call, with the same geometry, on a saturated input
-(Inputs(dirty=True): all 255 / 65535 / 1.0).  Importing this file builds the table and touches no device
-(tests/test_doors_cpu.py; tests/golden/doors_idents.txt lists the identifiers).
+tests/test_gpu_poison.py (no load of bytes nobody wrote), tests/test_gpu_stall.py (no dependence on which stream runs first) and
+section (c) of tests/test_gpu_gridcap.py (no dependence on the number of workgroups); tests/diag.py holds what they share.
+`inputs` lets a judge ask for the same call, with the same geometry, on a saturated input (Inputs(dirty=True): all 255 / 65535 /
+32767 / 1.0).  Importing this file builds the table and touches no device: inputs and models are made inside the door functions, once
+per case (tests/test_doors_cpu.py; tests/golden/doors_idents.txt lists the identifiers).
+
+The raster passes (carried band, index, zones, fields, masked warp) are rows like any other.  The four judges compare with
+diag.baseline, not with a model, so MODELS holds for each of these rows what the numpy model of its pass says, and the pass's own
+module (tests/test_gpu_bands.py, _index, _zones, _fields, _tiles_nodata) holds the baseline to it: every mode reaches the model
+through the baseline, as it does for the older doors through the parity modules.
 
 x2plus refuses odd tile sizes (pixel_unshuffle by 2), so its net doors run the listed shapes as the trunk grid: tiles of
 2 th x 2 tw.  The 16-bit doors exist on the x4 RRDB nets only."""
@@ -14,7 +20,13 @@ from pathlib import Path
 import numpy as np
 import torch
 
+import bands_model as bm
+import display_model as dm
+import fields_model as fm
+import index_model as im
 import resample_model as rm
+import warp_masked_model as wm
+import zones_model as zm
 from s2sr import geo, native, tiles
 
 HP, F16, FP8 = native.PREC_F16_HP, native.PREC_F16, native.PREC_FP8
@@ -46,6 +58,15 @@ class Inputs:
         if self.dirty:
             return np.full(shape, 65535, np.uint16)
         return np.random.default_rng(seed).integers(0, 65536, shape).astype(np.uint16)
+
+    def i16(self, shape, seed):
+        if self.dirty:
+            return np.full(shape, 32767, np.int16)
+        return np.random.default_rng(seed).integers(-32768, 32768, shape).astype(np.int16)
+
+    def like(self, a):
+        """`a` itself (a case's pixel data), or the saturated array of its type and shape"""
+        return getattr(self, {"uint8": "u8", "uint16": "u16", "int16": "i16"}[a.dtype.name])(a.shape, 0) if self.dirty else a
 
     def green(self, shape, seed):
         """the post-process tests' image: green at least 90, so the vegetation stage has pixels to work on"""
@@ -417,9 +438,137 @@ def _pyramid_doors():
     door("tiles_write_png-small_groups_5x4", "x4_hp")(lambda e, X: _pngs(e, X, png_level_5x4, no_path=(7,), small_groups=True))
 
 
+# ---- raster passes -------------------------------------------------------------------------------------------------------------------
+# Under Inputs(dirty=True) a row keeps its geometry -- shapes, masks, zone grids, polygon tables, LUTs, parameters -- and saturates
+# the pixel data only.  A counter comes back as a one-element array, a result dict as a tuple in a fixed order: diag.same views bytes.
+MODELS = {}                      # ident -> () -> what the numpy model says the row returns; None for an output that has no model
+
+
+def raster_door(ident, model):
+    MODELS[ident] = model
+    return door(ident, "x4_hp")
+
+
+def _n(x):
+    return np.array([x], np.uint64)
+
+
+def _carry(e, X, S, rows, chain=False):
+    q, b, v = bm.case(37, 45, S)
+    kw = dict(lo=1000, hi=11000, r=4, eps=5, valid=v, fill=9, band_rows=rows)
+    if not chain:
+        got, n = e.carry_band_u16(X.like(b), S, sr=X.like(q), **kw)
+        return got, _n(n)
+    with e.chain_lock:                                   # the same call, then again from the guide it kept on the device
+        got, n = e.carry_band_u16(X.like(b), S, sr=X.like(q), **kw)
+        got = np.array(got)
+        kept, m = e.carry_band_u16(X.like(b), S, sr=None, **kw)
+    return got, _n(n), kept, _n(m)
+
+
+def _carry_model(S, twice=False):
+    want, bad = bm.modelled(37, 45, S, 1000, 11000, (1, 1, 1), 4, 5, True, 9)
+    return (want, _n(bad)) * (2 if twice else 1)
+
+
+def _index_case(H, W, zs, Z):
+    """tests/test_gpu_index.py's call: channel 1 against a plane, offset 1000, the mask at scale 4, zones, the LUT, every output"""
+    A, B, grids, lut = im.case(H, W)
+    kw = dict(ca=1, offset=1000, valid=grids["valid", 4], valid_scale=4, zones=grids["zones", zs, Z], zone_scale=zs, Z=Z, lut=lut, want=im.OUTPUTS)
+    return A, im.plane(B, 1, 0), kw
+
+
+def _index_tuple(r):
+    return tuple(np.array(r[k]) for k in im.OUTPUTS) + (_n(r["undefined"]),)
+
+
+def _index(e, X, H, W, zs, Z, rows, kept=False):
+    A, b, kw = _index_case(H, W, zs, Z)
+    if not kept:
+        return _index_tuple(e.index_nd_u16(X.like(A), X.like(b), band_rows=rows, **kw))
+    with e.chain_lock:                                   # the display pass leaves A on the device as the kept image
+        hist = np.array(e.display_hist_u16(X.like(A)))
+        return (hist,) + _index_tuple(e.index_nd_u16(None, X.like(b), band_rows=rows, **kw))
+
+
+def _index_model(H, W, zs, Z, kept=False):
+    A, b, kw = _index_case(H, W, zs, Z)
+    want = im.model(A[..., 1], b, 1000, 0, 10000, kw["valid"], 4, kw["zones"], zs, Z, kw["lut"])
+    return ((dm.hist(A),) if kept else ()) + _index_tuple(want)
+
+
+def _render_input(X, H, W):
+    idx = X.i16((H, W), 1000 * H + W)
+    if not X.dirty:
+        idx[::5] = im.NODATA
+    return idx
+
+
+def _zones(e, H, W, kind, **kw):
+    tabs, Z, _, _ = zm.case(H, W, kind)
+    labels, area = e.zones_rasterize_u16(*tabs, Z, (H, W), **kw)          # no pixel data: the saturated call is the call
+    return labels if area is None else (labels, area)
+
+
+def _fields(e, X, H, W, name, **kw):
+    labels, fields, found = e.fields_segment_i16(X.like(fm.raster(H, W, name)), fm.LO, fm.HI, **kw)
+    return labels, fields, _n(found)
+
+
+def _fields_model(H, W, name, **kw):
+    labels, fields, found = fm.case(H, W, name, **kw)
+    return labels, fields, _n(found)
+
+
+def _masked_warp(e, X, then_base=False):
+    """the 150 x 211 / vs = 4 case, and the base level cut from the raster it keeps: the hand-over under the modes"""
+    rgb, valid, vs, plan, _ = wm.case(32633, "coarse")
+    raster = wm.warp(e, X.like(rgb), valid, vs, plan)
+    if not then_base:
+        return raster
+    raster = np.array(raster)
+    lv = tiles.plan_levels(plan.placement.bounds(plan.out_w, plan.out_h), 15, 15)[0]
+    return raster, e.tiles_base_u8(raster.shape[:2], *tiles.plan_base(lv, plan.placement, plan.out_w, plan.out_h), on_device=True)
+
+
+def _raster_doors():
+    # the carried band at 37 x 45, masked: in bands of 2 S + 1 guide rows, the S = 4 chain from the kept copy, and S = 4 whole (9
+    # tiles in one launch: the only one of these that a cap of 8 makes smaller)
+    for S in (2, 4):
+        raster_door(f"carry_band_u16-x{S}-bands", lambda S=S: _carry_model(S))(lambda e, X, S=S: _carry(e, X, S, 2 * S + 1))
+    raster_door("carry_band_u16-x4-bands-kept_chain", lambda: _carry_model(4, twice=True))(lambda e, X: _carry(e, X, 4, 9, chain=True))
+    raster_door("carry_band_u16-x4-whole", lambda: _carry_model(4))(lambda e, X: _carry(e, X, 4, 0))
+    # the index: the ragged shape in bands of 5 rows with zones at scale 1, Z = 65535; 255 x 257 (65535 pixels: 8 workgroups' worth,
+    # a ragged last group) whole with zones at scale 4, Z = 7; from the kept copy; the rendering of a raster that exists
+    for H, W, zs, Z, rows, tag in ((37, 45, 1, 65535, 5, "37x45-bands5"), (255, 257, 4, 7, 0, "255x257")):
+        raster_door(f"index_nd_u16-{tag}", lambda a=(H, W, zs, Z): _index_model(*a))(lambda e, X, a=(H, W, zs, Z, rows): _index(e, X, *a))
+        raster_door(f"index_render_i16-{tag}", lambda a=(H, W): im.render(_render_input(Inputs(), *a), im.case(*a)[3]))(
+            lambda e, X, a=(H, W), r=rows: e.index_render_i16(_render_input(X, *a), im.case(*a)[3], band_rows=r))
+    raster_door("index_nd_u16-37x45-bands5-kept", lambda: _index_model(37, 45, 1, 65535, kept=True))(
+        lambda e, X: _index(e, X, 37, 45, 1, 65535, 5, kept=True))
+    # zones: the scene in bands, on 4 x 5 tiles and on one pixel, the ring of 1000 vertices, and labels without area
+    for H, W, kind, kw, tag in ((37, 45, "scene", dict(band_rows=5), "37x45-bands5"), (255, 257, "scene", {}, "255x257"), (1, 1, "scene", {}, "1x1"),
+                                (255, 257, "star", {}, "255x257")):
+        raster_door(f"zones_rasterize_u16-{kind}-{tag}", lambda a=(H, W, kind): zm.case(*a)[2:])(lambda e, X, a=(H, W, kind), kw=kw: _zones(e, *a, **kw))
+    raster_door("zones_rasterize_u16-scene-37x45-no_area", lambda: zm.case(37, 45)[2])(lambda e, X: _zones(e, 37, 45, "scene", want_area=False))
+    # fields: one component through all 3 x 4 tiles, the morphology, one pixel, and more fields than Z
+    for H, W, name, kw in ((130, 197, "spiral", dict(conn=4)), (65, 129, "blobs", dict(r_open=1, r_close=2, conn=8, min_pixels=3)), (1, 1, "ones", {}),
+                           (63, 65, "noise", dict(conn=8, Z=5))):
+        raster_door(f"fields_segment_i16-{H}x{W}-{name}", lambda a=(H, W, name), kw=kw: _fields_model(*a, **kw))(
+            lambda e, X, a=(H, W, name), kw=kw: _fields(e, X, *a, **kw))
+    raster_door("warp_bilinear_masked_u8", lambda: wm.case(32633, "coarse")[4])(lambda e, X: _masked_warp(e, X))
+    raster_door("warp_bilinear_masked_u8-then-base", lambda: (wm.case(32633, "coarse")[4], None))(lambda e, X: _masked_warp(e, X, then_base=True))
+
+
+def owned(prefix):
+    """the raster rows of one pass, for the module that holds their baselines to the model"""
+    return [i for i in MODELS if i.startswith(prefix)]
+
+
 _net_doors()
 _image_doors()
 _block_doors()
 _postprocess_doors()
 _display_doors()
 _pyramid_doors()
+_raster_doors()

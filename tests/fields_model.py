@@ -1,6 +1,7 @@
 """The fields pass restated from its definition (include/s2sr.h: s2sr_fields_segment_i16, s2sr_labels_trace_u16), not
 from the kernels: the mask, the morphology by shifted ANDs and ORs, the components by a plain flood fill, the numbering, the fields
 table, and the ring tracer's rule edge by edge.  Also the rasters the CPU and GPU tests share."""
+import functools
 from collections import deque
 
 import numpy as np
@@ -210,3 +211,33 @@ def trace_rasters():
     rng = np.random.default_rng(5)
     out["random"] = rng.integers(0, 4, (13, 17)).astype(np.uint16)
     return out
+
+
+# ---- the inputs of the GPU tests -------------------------------------------------------------------------------------------------------
+LO, HI = 4000, 32767
+
+
+@functools.lru_cache(maxsize=None)
+def _patterns(H, W):
+    out = patterns(H, W)
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+def raster(H, W, name):
+    return _patterns(H, W)[name]
+
+
+_CASES = {}
+
+
+def case(H, W, name, **kw):
+    """segment() of raster(H, W, name) in LO..HI -> (labels, fields, found): made once per raster and parameter set"""
+    key = (H, W, name, tuple(sorted(kw.items())))
+    if key not in _CASES:
+        labels, fields, found = segment(raster(H, W, name), LO, HI, **kw)
+        labels.setflags(write=False)
+        fields.setflags(write=False)
+        _CASES[key] = labels, fields, found
+    return _CASES[key]

@@ -4,6 +4,7 @@ s2sr_create reads every switch ONCE.  So a cached default-configuration engine i
 test has put into the environment (a cached handle never carries a test's setting), and a test of a switch creates its own
 handle after setting it (fresh) and checks that the handle took it (s2sr_debug_get_config).
 tests/test_abi_cpu.py holds SWITCHES to the getenv calls of s2sr_create."""
+import contextlib
 import os
 
 from s2sr import native
@@ -53,3 +54,16 @@ def fresh(monkeypatch, env, num_block, precision, scale=4, arch="rrdb", group=0,
     e = native.Engine(num_block=num_block, precision=precision, group=group, scale=scale, arch=arch)
     e.load_state_dict(sd if sd is not None else state_dict(num_block, scale, arch, **sd_kw))
     return e
+
+
+@contextlib.contextmanager
+def bare(num_block=1, **kw):
+    """An engine without weights, for the passes that need none (kw: precision=...), made with every diagnostic mode off and closed
+    at the end.  (diag imports this module, so it is imported here.)"""
+    import diag
+    with diag.modes_off():
+        e = native.Engine(num_block=num_block, **kw)
+        try:
+            yield e
+        finally:
+            e.close()

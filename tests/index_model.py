@@ -5,6 +5,8 @@ hold the kernels to this byte for byte; s2sr/index.py's policy is compared with 
   a' = max(a - offset, 0), b' = max(b - offset, 0), n = a' - b', d = a' + b' + L
   v  = sign(n) floor((2 |n| K + d) / (2 d)) for d > 0, -32768 for d == 0 or a pixel whose mask cell is 0
 """
+import functools
+
 import numpy as np
 
 NODATA = -32768
@@ -118,3 +120,39 @@ def moments(h, K):
         c, v = int(c), i - K
         n, s, s2 = n + c, s + c * v, s2 + c * v * v
     return n, s, s2
+
+
+# ---- the inputs of the GPU tests -------------------------------------------------------------------------------------------------------
+OUTPUTS = ("index", "hist", "rgba", "zonal")
+
+
+@functools.lru_cache(maxsize=None)
+def case(H, W):
+    """(A [H, W, 3], B [H, W, 3], masks and zone grids at scales 1 and 4, the LUT): made once per shape.  The top third of the
+    planes lies in 900..1199, so an offset of 1000 takes the d == 0 path there."""
+    from s2sr import index as xi
+    rng = np.random.default_rng(1000 * H + W)
+    A, B = (rng.integers(0, 65536, (H, W, 3)).astype(np.uint16) for _ in range(2))
+    top = -(-H // 3)
+    A[:top], B[:top] = (rng.integers(900, 1200, (top, W, 3)).astype(np.uint16) for _ in range(2))
+    grids = {}
+    for s in (1, 4):
+        gh, gw = -(-H // s), -(-W // s)
+        grids["valid", s] = (rng.random((gh, gw)) > 0.25).astype(np.uint8)
+        for Z in (1, 7, 65535):
+            pool = np.array([0, 1] if Z == 1 else list(range(8)) + [9] if Z == 7 else [0, 1, 300, 65535], np.uint16)   # 9 > Z = 7: counts as 0
+            lab = pool[rng.integers(0, len(pool), (gh, gw))]
+            lab[: gh // 2, : gw // 2] = pool[-1] if Z != 7 else 7       # a field: neighbouring lanes share a label
+            grids["zones", s, Z] = lab
+    return A, B, grids, xi.ramp_lut(xi.ramp_for("vegetation"))
+
+
+def plane(P3, c, ch):
+    """the image as the entry takes it: one channel as a plane of its own (c == 1), or the three-channel image"""
+    return np.ascontiguousarray(P3[..., ch]) if c == 1 else P3
+
+
+def model(a, b, offset, L, K, valid, vs, zones, zs, Z, lut):
+    """every output of s2sr_index_nd_u16 as the dict Engine.index_nd_u16 returns"""
+    v, und = index(a, b, offset, L, K, valid, vs)
+    return {"index": v, "undefined": und, "hist": hist(v, K), "rgba": render(v, lut), "zonal": None if zones is None else zonal(v, zones, zs, Z)}

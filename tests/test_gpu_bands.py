@@ -1,12 +1,15 @@
 """Carrying an extra band to the SR grid on the GPU (include/s2sr.h: s2sr_carry_band_u16; csrc/bands.hip): byte for
-byte against tests/bands_model.py, the independence of band_rows, the chain behind the 16-bit door's kept image, and the entry under
-red zones, poison and stalls."""
+byte against tests/bands_model.py, the independence of band_rows, the chain behind the 16-bit door's kept image and every refusal.
+The entry under red zones, poison, stalls and capped grids: its rows of tests/doors.py, whose baselines this module holds to the model."""
 import numpy as np
 import pytest
 
 import bands_model as bm
 import diag
+import doors
 import gpu_engines
+from bands_model import case, modelled
+from diag import same_values as same
 from s2sr import native
 
 pytestmark = pytest.mark.gpu
@@ -20,42 +23,8 @@ WEIGHTS = [(1, 1, 1), (0, 0, 1)]
 
 @pytest.fixture(scope="module")
 def bare():
-    """the entry needs no weights"""
-    with diag.modes_off():
-        e = native.Engine(num_block=1, precision=HP)
-        try:
-            yield e
-        finally:
-            e.close()
-
-
-_CASES = {}
-
-
-def case(H, W, S):
-    """(guide, band straying outside 1000..11000, mask): made once per shape and scale"""
-    if (H, W, S) not in _CASES:
-        q = bm.scene(H, W, S, seed=5)
-        _CASES[H, W, S] = q, bm.stray_band(q, S, seed=6), bm.holes(H, W, seed=7)
-    return _CASES[H, W, S]
-
-
-_MODEL = {}
-
-
-def modelled(H, W, S, lo, hi, w, r, eps, masked, fill=0):
-    key = (H, W, S, lo, hi, w, r, eps, masked, fill)
-    if key not in _MODEL:
-        q, b, v = case(H, W, S)
-        _MODEL[key] = bm.carry(q, b, S, lo, hi, w=w, r=r, eps=eps, valid=v if masked else None, fill=fill)
-    return _MODEL[key]
-
-
-def same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} against {want.dtype} {want.shape}"
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} samples differ, the first at {tuple(bad[0])}: {got[tuple(bad[0])]} against {want[tuple(bad[0])]}"
+    with gpu_engines.bare(precision=HP) as e:                    # the entry needs no weights
+        yield e
 
 
 @pytest.mark.parametrize("S", [2, 4])
@@ -166,40 +135,11 @@ def test_every_refusal_leaves_the_engine_answering(bare):
     same(bare.carry_band_u16(b, S)[0], want, "after the refusal of sr=None")
 
 
-@pytest.mark.parametrize("S", [2, 4])
-def test_under_red_zones_and_poison(S):
-    """the ragged shape, masked and in bands: the modes-off bytes, zones clean"""
-    H, W = 37, 45
-    q, b, v = case(H, W, S)
-    want, bad = modelled(H, W, S, 1000, 11000, (1, 1, 1), 4, 5, True, fill=9)
-    kw = dict(sr=q, lo=1000, hi=11000, r=4, eps=5, valid=v, fill=9, band_rows=2 * S + 1)
-    with diag.engines_under(native.redzone_bytes, native.redzone, diag.Z) as get:
-        e = get("x4_hp")
-        got, n = e.carry_band_u16(b, S, **kw)
-        same(got, want, "under red zones")
-        assert n == bad
-        got, n = e.carry_band_u16(b, S, **dict(kw, sr=None))
-        same(got, want, "under red zones, from the kept copy")
-        diag.clean(e)
-    for pattern in (1, 2):
-        with diag.engines_under(native.poison_pattern, native.poison, pattern) as get:
-            e = get("x4_hp")
-            got, n = e.carry_band_u16(b, S, **kw)
-            same(got, want, f"fresh under poison pattern {pattern}")
-            assert n == bad
-            e.poison_scratch()
-            got, n = e.carry_band_u16(b, S, **kw)
-            same(got, want, f"behind poison_scratch, pattern {pattern}")
-            assert n == bad
-            for mode in (1, 2):                                          # stalled streams: the compute side, the copy side
-                e.poison_scratch()
-                native.delay(mode, 1200)
-                try:
-                    got, n = e.carry_band_u16(b, S, **kw)
-                finally:
-                    native.delay(0)
-                same(got, want, f"under stall mode {mode}, pattern {pattern}")
-                assert n == bad
+@pytest.mark.parametrize("ident", doors.owned("carry_band_u16"))
+def test_the_door_table_s_baseline_is_the_model(ident):
+    """tests/doors.py's rows of this pass: the red-zone, poison, stall and grid-cap matrices hold every mode to diag.baseline, and
+    this holds the baseline to the model, sample for sample"""
+    same(diag.baseline(ident), doors.MODELS[ident](), ident)
 
 
 def test_the_pass_has_a_kernel_family(bare):

@@ -1,7 +1,9 @@
 """Fields from the image on the GPU (include/s2sr.h: s2sr_fields_segment_i16, s2sr_labels_trace_u16; csrc/fields.hip):
 labels, fields and found byte for byte against tests/fields_model.py on shapes that cross the 64 x 64 tile lines and patterns chosen
-to break a union-find; every parameter; the independence of the number of workgroups; the entry under red zones, poison and stalls;
-every refusal, the void rule, the round trip through the ring tracer and the polygon rasteriser, and the job that segments its own NDVI.
+to break a union-find; every parameter; the independence of the number of workgroups (caps 1 and 3, with the launch and trip
+arithmetic); every refusal, the void rule, the round trip through the ring tracer and the polygon rasteriser, and the job that segments
+its own NDVI.  The entry under red zones, poison, stalls and cap 8: its rows of tests/doors.py, whose baselines this module holds to
+the model.
 
 The pass's capped launches are counted in the grid-cap family "display", as the index and zones passes' are."""
 import json
@@ -10,9 +12,12 @@ import numpy as np
 import pytest
 
 import diag
+import doors
 import fields_model as fm
 import gpu_engines
 import zones_model as zm
+from diag import same_values as same
+from fields_model import HI, LO, case, raster
 from s2sr import native
 
 pytestmark = pytest.mark.gpu
@@ -22,47 +27,12 @@ HP = native.PREC_F16_HP
 SHAPES = [(1, 1), (1, 130), (63, 65), (64, 64), (65, 129), (130, 197)]
 PATTERNS = ("spiral", "checker", "comb", "rings", "noise", "ones", "zeros", "stripes", "blobs")
 GRID_FAMILY = "display"
-LO, HI = 4000, 32767
 
 
 @pytest.fixture(scope="module")
 def bare():
-    """the entry needs no weights"""
-    with diag.modes_off():
-        e = native.Engine(num_block=1, precision=HP)
-        try:
-            yield e
-        finally:
-            e.close()
-
-
-_RASTERS, _CASES = {}, {}
-
-
-def raster(H, W, name):
-    if (H, W) not in _RASTERS:
-        _RASTERS[H, W] = fm.patterns(H, W)
-        for v in _RASTERS[H, W].values():
-            v.setflags(write=False)
-    return _RASTERS[H, W][name]
-
-
-def case(H, W, name, **kw):
-    """the model's (labels, fields, found): made once per raster and parameter set"""
-    key = (H, W, name, tuple(sorted(kw.items())))
-    if key not in _CASES:
-        labels, fields, found = fm.segment(raster(H, W, name), LO, HI, **kw)
-        labels.setflags(write=False)
-        fields.setflags(write=False)
-        _CASES[key] = labels, fields, found
-    return _CASES[key]
-
-
-def same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} against {want.dtype} {want.shape}"
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} samples differ, the first at {tuple(bad[0])}: {got[tuple(bad[0])]} against {want[tuple(bad[0])]}"
+    with gpu_engines.bare(precision=HP) as e:                    # the entry needs no weights
+        yield e
 
 
 def check(e, H, W, name, **kw):
@@ -123,14 +93,9 @@ def test_under_capped_grids(bare, cap):
     """the same bytes with every workgroup on several trips: 130 x 197 pixels are 3 x 4 tiles, 26 numbering chunks"""
     H, W = 130, 197
     for name, kw in (("spiral", dict(conn=4)), ("noise", dict(conn=8, min_pixels=2)), ("blobs", dict(r_open=1, r_close=2, conn=4))):
-        before = native.grid_cap_workgroups()
-        native.grid_cap(cap)
-        native.grid_cap_stats(reset=True)
-        try:
+        with diag.under(cap):
             check(bare, H, W, name, **kw)
             launches, trips = native.grid_cap_stats()[GRID_FAMILY]
-        finally:
-            native.grid_cap(before)
         # mask, local, border, flatten, count, apply, labels (and the morphology's 8 passes and the nodata mask where it runs)
         assert launches == (7 + 9 if "r_open" in kw else 7), (name, launches)
         assert trips == -(-101 // cap), (name, trips)           # the most trips are the flatten pass's: 25610 pixels, 256 a workgroup
@@ -235,29 +200,11 @@ def test_the_call_voids_the_kept_image():
     assert found == want[2] and found > 0 and z[1:, 0].tolist() == fields[1:found + 1, 0].tolist()
 
 
-def test_under_red_zones_poison_and_stalls():
-    """the modes-off bytes with zones clean, on fresh memory and behind poison_scratch, with either side stalled"""
-    runs = ((130, 197, "spiral", dict(conn=4)), (65, 129, "blobs", dict(r_open=1, r_close=2, conn=8, min_pixels=3)), (1, 1, "ones", {}),
-            (63, 65, "noise", dict(conn=8, Z=5)))
-    with diag.engines_under(native.redzone_bytes, native.redzone, diag.Z) as get:
-        e = get("x4_hp")
-        for H, W, name, kw in runs:
-            check(e, H, W, name, **kw)
-        diag.clean(e)
-    for pattern in (1, 2):
-        with diag.engines_under(native.poison_pattern, native.poison, pattern) as get:
-            e = get("x4_hp")
-            check(e, *runs[1][:3], **runs[1][3])                                          # fresh
-            for H, W, name, kw in runs:
-                e.poison_scratch()
-                check(e, H, W, name, **kw)
-            for mode in (1, 2):                                      # stalled streams: the compute side, the copy side
-                e.poison_scratch()
-                native.delay(mode, 1200)
-                try:
-                    check(e, *runs[1][:3], **runs[1][3])
-                finally:
-                    native.delay(0)
+@pytest.mark.parametrize("ident", doors.owned("fields_segment_i16"))
+def test_the_door_table_s_baseline_is_the_model(ident):
+    """tests/doors.py's rows of this pass: the red-zone, poison, stall and grid-cap matrices hold every mode to diag.baseline, and
+    this holds the baseline to the model, sample for sample"""
+    same(diag.baseline(ident), doors.MODELS[ident](), ident)
 
 
 def _tables(labels, Z, engine):

@@ -10,7 +10,7 @@ every comparison is byte for byte, against the same call with the cap off (whose
 numpy model of the pass.
   (a) the conv kernels alone through debug_conv_trunk / debug_conv, cap 8 (the smallest grid the tile schedulers take);
   (b) every stored layer of a 1-block net (the taps of the in-situ modules) and the output in three sightings, cap 8;
-  (c) the door table of tests/doors.py on engines made under cap 8, against diag.baseline;
+  (c) the door table of tests/doors.py, the raster passes' rows included, on engines made under cap 8, against diag.baseline;
   (d) the tile-loop passes and the byte movers against their models under caps 1 and 3 (a stride that is no power of two, a
       ragged last trip);
   (e) the controls: off means off, a cap above every grid counts nothing, refused values change nothing, launches where a
@@ -19,7 +19,6 @@ The precondition of every case is read from the library's counter (native.grid_c
 the largest ceil(work items / workgroups) among them, per launcher family.  A case that relies on the second trip asserts it ran.
 The cap is read when a launch is enqueued and a captured graph keeps its grids, so the engines are made, and capture, under the cap.
 Nothing here can fault where the library is wrong: a cap changes how many workgroups share the same in-bounds work."""
-import contextlib
 import functools
 import math
 import tempfile
@@ -36,7 +35,7 @@ import display_model as dm
 import doors
 import gpu_engines
 import nodata_model as nm
-from diag import baseline, keep, same
+from diag import baseline, keep, same, same_values, trips, under
 from doors import CONFIGS, DOORS, NET_SHAPES, Inputs
 from s2sr import native
 
@@ -65,31 +64,6 @@ def _e4m3_vals(rng, shape, exp):
     b = np.where((b & 0x7F) == 0x7F, 0, b).astype(np.uint8)                 # no NaN codes
     v = torch.from_numpy(b).view(torch.float8_e4m3fn).float().numpy()
     return (np.clip(v, -8.0, 8.0) * 2.0 ** -exp).astype(np.float32)
-
-
-def same_values(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} against {want.dtype} {want.shape}"
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} samples differ from the model, the first at {tuple(bad[0])}: {got[tuple(bad[0])]} against {want[tuple(bad[0])]}"
-
-
-@contextlib.contextmanager
-def under(cap):
-    """the cap in force and the counter at zero; afterwards the cap the module found"""
-    before = native.grid_cap_workgroups()
-    native.grid_cap(cap)
-    native.grid_cap_stats(reset=True)
-    try:
-        yield
-    finally:
-        native.grid_cap(before)
-
-
-def trips(*families):
-    """the largest trip count the counter holds among these families (all: no argument), and the stats for the message"""
-    st = native.grid_cap_stats()
-    return max(t for f, (_, t) in st.items() if not families or f in families), st
 
 
 def same_bytes(got, want, what):
@@ -301,11 +275,17 @@ def test_door_under_the_cap(capped, ident):
 
 
 def test_the_door_table_ran_capped(capped):
-    """the precondition of (c): on an engine made under the cap, one door of each kind counts capped launches in its families"""
+    """The precondition of (c): on an engine made under the cap, one door of each kind counts capped launches in its families.
+    Of the raster passes: the carried band whole (9 tiles in one launch; in bands of 2 S + 1 guide rows no launch has more than 6,
+    which a cap of 8 leaves alone), the index pass's rendering, the zones and the fields pass at 255 x 257 and 130 x 197 (32 blocks,
+    20 and 12 tiles; index_nd_u16 itself takes 1024 lanes of 8 pixels a workgroup, so its 65535 pixels are 8 workgroups' worth and
+    cap 8 changes nothing there: caps 1 and 3 judge it in tests/test_gpu_index.py), and the masked warp."""
     for ident, fams in (("x4_hp-ragged_2x37x53-forward_batch_u8", ("conv", "trunk_f16", "pack")), ("x4_fp8-ragged_2x37x53-forward_batch_u8", ("trunk_f8",)),
                         ("x4_hp-banded-consistent_u8-smooth", ("consistency",)), ("x4_hp-banded-masked_u8", ("nodata",)),
                         ("postprocess_batch_u8_dev-67x101-wow", ("postprocess",)), ("display_apply_u16-255x257-bands0", ("display",)),
-                        ("tiles_base_u8", ("tiles",)), ("tiles_resample_u8-lanczos", ("resample",))):
+                        ("tiles_base_u8", ("tiles",)), ("tiles_resample_u8-lanczos", ("resample",)), ("carry_band_u16-x4-whole", ("bands",)),
+                        ("index_render_i16-255x257", ("display",)), ("zones_rasterize_u16-scene-255x257", ("display",)),
+                        ("fields_segment_i16-130x197-spiral", ("display",)), ("warp_bilinear_masked_u8", ("tiles",))):
         name, fn = DOORS[ident]
         e = diag.new_engine(name)                               # a fresh engine: no graph from an earlier test stands in for the launches
         try:

@@ -1,6 +1,7 @@
 """Spectral indices on the GPU (include/s2sr.h: s2sr_index_nd_u16, s2sr_index_render_i16; csrc/index.hip): byte for
 byte against tests/index_model.py, the independence of band_rows, the chain behind the 16-bit door's kept image, every refusal,
-the entries under red zones, poison, stalls and capped grids, and the job with its two files per index and its map tiles.
+the launch and trip arithmetic under caps 1 and 3, and the job with its two files per index and its map tiles.  The entries under red
+zones, poison, stalls and cap 8: their rows of tests/doors.py, whose baselines this module holds to the model.
 
 The pass's capped launches are counted in the grid-cap family "display" (the launcher families are a closed list that
 tests/test_gridcap_cpu.py spells out; DESIGN.md 7.8 says why the pass shares one)."""
@@ -10,8 +11,11 @@ import numpy as np
 import pytest
 
 import diag
+import doors
 import gpu_engines
 import index_model as im
+from diag import same_values as same
+from index_model import case, model, plane
 from s2sr import index as xi
 from s2sr import native
 
@@ -27,53 +31,8 @@ GRID_FAMILY = "display"
 
 @pytest.fixture(scope="module")
 def bare():
-    """the entries need no weights"""
-    with diag.modes_off():
-        e = native.Engine(num_block=1, precision=HP)
-        try:
-            yield e
-        finally:
-            e.close()
-
-
-_CASES = {}
-
-
-def case(H, W):
-    """(A [H, W, 3], B [H, W, 3], masks and zone grids at scales 1 and 4, the LUT): made once per shape.  The top third of the
-    planes lies in 900..1199, so an offset of 1000 takes the d == 0 path there."""
-    if (H, W) not in _CASES:
-        rng = np.random.default_rng(1000 * H + W)
-        A, B = (rng.integers(0, 65536, (H, W, 3)).astype(np.uint16) for _ in range(2))
-        top = -(-H // 3)
-        A[:top], B[:top] = (rng.integers(900, 1200, (top, W, 3)).astype(np.uint16) for _ in range(2))
-        grids = {}
-        for s in (1, 4):
-            gh, gw = -(-H // s), -(-W // s)
-            grids["valid", s] = (rng.random((gh, gw)) > 0.25).astype(np.uint8)
-            for Z in (1, 7, 65535):
-                pool = np.array([0, 1] if Z == 1 else list(range(8)) + [9] if Z == 7 else [0, 1, 300, 65535], np.uint16)   # 9 > Z = 7: counts as 0
-                lab = pool[rng.integers(0, len(pool), (gh, gw))]
-                lab[: gh // 2, : gw // 2] = pool[-1] if Z != 7 else 7       # a field: neighbouring lanes share a label
-                grids["zones", s, Z] = lab
-        _CASES[H, W] = A, B, grids, xi.ramp_lut(xi.ramp_for("vegetation"))
-    return _CASES[H, W]
-
-
-def plane(P3, c, ch):
-    return np.ascontiguousarray(P3[..., ch]) if c == 1 else P3
-
-
-def model(a, b, offset, L, K, valid, vs, zones, zs, Z, lut):
-    v, und = im.index(a, b, offset, L, K, valid, vs)
-    return {"index": v, "undefined": und, "hist": im.hist(v, K), "rgba": im.render(v, lut), "zonal": None if zones is None else im.zonal(v, zones, zs, Z)}
-
-
-def same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} against {want.dtype} {want.shape}"
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} samples differ, the first at {tuple(bad[0])}: {got[tuple(bad[0])]} against {want[tuple(bad[0])]}"
+    with gpu_engines.bare(precision=HP) as e:                    # the entries need no weights
+        yield e
 
 
 def same_result(got, want, what):
@@ -288,40 +247,11 @@ def test_every_refusal_returns_minus_one_and_leaves_the_next_call_intact(bare):
     same_result(bare.index_nd_u16(A, b1, **good), want, "after the Python refusals")
 
 
-def test_under_red_zones_poison_and_stalls():
-    """the ragged shape, masked, with zones and in bands: the modes-off bytes, zones clean"""
-    H, W = 37, 45
-    A, B, grids, lut = case(H, W)
-    b1 = plane(B, 1, 0)
-    kw = dict(ca=1, offset=1000, valid=grids["valid", 4], valid_scale=4, zones=grids["zones", 1, 65535], zone_scale=1, Z=65535, lut=lut,
-              band_rows=5, want=("index", "hist", "rgba", "zonal"))
-    want = model(A[..., 1], b1, 1000, 0, 10000, grids["valid", 4], 4, grids["zones", 1, 65535], 1, 65535, lut)
-    with diag.engines_under(native.redzone_bytes, native.redzone, diag.Z) as get:
-        e = get("x4_hp")
-        same_result(e.index_nd_u16(A, b1, **kw), want, "under red zones")
-        same(e.index_render_i16(want["index"], lut, band_rows=5), want["rgba"], "render under red zones")
-        with e.chain_lock:
-            e.display_hist_u16(A)                                    # leaves A on the device as the kept image
-            same_result(e.index_nd_u16(None, b1, **kw), want, "under red zones, from the kept copy")
-        diag.clean(e)
-    for pattern in (1, 2):
-        with diag.engines_under(native.poison_pattern, native.poison, pattern) as get:
-            e = get("x4_hp")
-            same_result(e.index_nd_u16(A, b1, **kw), want, f"fresh under poison pattern {pattern}")
-            e.poison_scratch()
-            same_result(e.index_nd_u16(A, b1, **kw), want, f"behind poison_scratch, pattern {pattern}")
-            e.poison_scratch()
-            same(e.index_render_i16(want["index"], lut, band_rows=5), want["rgba"], f"render behind poison_scratch, pattern {pattern}")
-            for mode in (1, 2):                                      # stalled streams: the compute side, the copy side
-                e.poison_scratch()
-                native.delay(mode, 1200)
-                try:
-                    got = keep(e.index_nd_u16(A, b1, **kw))
-                    ren = np.array(e.index_render_i16(want["index"], lut, band_rows=5))
-                finally:
-                    native.delay(0)
-                same_result(got, want, f"under stall mode {mode}, pattern {pattern}")
-                same(ren, want["rgba"], f"render under stall mode {mode}, pattern {pattern}")
+@pytest.mark.parametrize("ident", doors.owned("index_"))
+def test_the_door_table_s_baseline_is_the_model(ident):
+    """tests/doors.py's rows of this pass: the red-zone, poison, stall and grid-cap matrices hold every mode to diag.baseline, and
+    this holds the baseline to the model, sample for sample"""
+    same(diag.baseline(ident), doors.MODELS[ident](), ident)
 
 
 @pytest.mark.parametrize("cap", [1, 3])
@@ -334,16 +264,11 @@ def test_under_capped_grids(bare, cap):
         zones, zs, Z = (None, 1, 0) if zn is None else (grids["zones", zn[0], zn[1]], zn[0], zn[1])
         kw = dict(ca=0, offset=1000, valid=grids["valid", 4], valid_scale=4, zones=zones, zone_scale=zs, Z=Z, lut=lut, want=outs)
         want = model(A[..., 0], b1, 1000, 0, 10000, grids["valid", 4], 4, zones, zs, Z, lut)
-        before = native.grid_cap_workgroups()
-        native.grid_cap(cap)
-        native.grid_cap_stats(reset=True)
-        try:
+        with diag.under(cap):
             got = keep(bare.index_nd_u16(A, b1, **kw))
             launches, trips = native.grid_cap_stats()[GRID_FAMILY]
             ren = np.array(bare.index_render_i16(want["index"], lut))
             launches2, trips2 = native.grid_cap_stats()[GRID_FAMILY]
-        finally:
-            native.grid_cap(before)
         same_result(got, want, f"cap {cap}, outputs {outs}")
         same(ren, want["rgba"], f"render under cap {cap}")
         items = -(-(-(-H * W // 8)) // 1024)

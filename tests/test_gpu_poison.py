@@ -47,6 +47,32 @@ its index and offset tables: each is uploaded in full, on the stream of the kern
     emitting one; the stream buffer is memset before the atomicOr emit.
   engine_display.hip display_hist_impl SRC, TABLES: image uploaded band by band ahead of its kernel; histogram memset.
   engine_display.hip display_apply_impl SRC, SRC / DST, TABLES: as above; the LUT uploaded whole.
+  engine_tiles.hip s2sr_warp_bilinear_masked_u8 SRC, DST, TABLES, VALID: raster, node grid and mask uploaded whole, on the kernel's stream,
+    before it is queued; the mask index is y / vs, x / vs of a clamped tap, so at most ceil(H / vs) - 1, ceil(W / vs) - 1; every output
+    pixel is written.
+  The raster passes run on the handle's stream alone, uploads included, so "before the kernel is queued" is the order of the calls:
+  engine_bands.hip carry_band_impl SRC (the guide; from the kept copy: the slot that holds it), the other of SRC / DST (the carried plane),
+    MID (the band), VALID (the mask), CONS (the inexact counter, then C and A).  None holds an index.  The counter is memset, band and
+    mask are uploaded whole before the loop, a band of guide rows ahead of the coefficient launch whose windows end inside it
+    (coeffs_end), and the rows of A and C an apply launch reads are written by the coefficient launches before it (apply_end trails by a row).
+  engine_index.hip index_nd_impl SRC (image a, or the kept copy where it lies), the other of SRC / DST (the index plane, the RGBA behind
+    it), MID (plane b), VALID (the mask, the zone grid behind it), TABLES (the LUT, the undefined counter, histogram, zonal sums).
+    Index-like: the zone grid (a label picks the row of the zonal sums; one above Z counts as 0) and the LUT (entered by the value,
+    never read as an index).  Counter, histogram and sums are memset in one piece; LUT, mask and zone grid are uploaded whole before
+    the first band's kernel; each band of a and b ahead of the kernel that reads it.
+  engine_index.hip index_render_impl SRC (the index raster), DST (the RGBA), TABLES (the LUT, uploaded whole before the first band); the
+    raster goes up band by band ahead of its kernel.
+  engine_zones.hip zones_impl DST (the labels), TABLES (xy, ring_start, feat_start, label, the tile bins' start table and feature lists,
+    area).  All but xy and area are index-like: starts into the rings, the vertices and the lists, feature numbers, labels as rows of
+    area.  The host checks them against one another (zone_check_tables, zone_check_bins) and copies each whole before the first launch;
+    area is memset; the feature lists are left out only where they are empty, and then every bin's range is empty too.
+  engine_fields.hip fields_impl SRC (the index raster), DST (the labels), MID and CHUNK (the two mask planes), PP (the union-find
+    parents), CONS (the sizes, which become the ranks), TABLES (the chunk sums, found, the fields table).  Index-like: the parents
+    (followed as pointers), the ranks (rows of the fields table; above Z: 0) and the chunk sums (the ranks' offsets).  The raster is
+    uploaded whole before the first kernel; the first mask launch writes every pixel of its plane and reads none, every morphology pass
+    writes its whole destination from a whole source; the local pass writes the parent and the size of EVERY pixel before the border
+    and flatten passes follow one; the count pass writes every chunk's sum before the scan reads them, and the scan writes found; the
+    fields table is memset before the apply pass writes a row.
   engine_debug.hip s2sr_debug_mfma_ceiling MID, TABLES and s2sr_debug_rdb_persistent MID, TABLES, CHUNK: measuring prototypes, not doors; their
     buffers hold operands whose values do not matter and flags they memset themselves; no index is read from them.
 """
@@ -107,7 +133,7 @@ def test_dirty_predecessor(poisoned, ident):
 def test_the_saturated_inputs_keep_type_and_shape():
     """what (c) relies on: the dirty call has the judged call's geometry"""
     for shape in ((2, 3, 4, 3), (5, 7, 3)):
-        for kind in ("u8", "u16", "green"):
+        for kind in ("u8", "u16", "i16", "green"):
             a, b = getattr(Inputs(), kind)(shape, 1), getattr(Inputs(True), kind)(shape, 1)
             assert a.shape == b.shape and a.dtype == b.dtype and (b == np.iinfo(b.dtype).max).all() and not (a == b).all()
 

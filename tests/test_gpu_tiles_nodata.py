@@ -1,13 +1,10 @@
 """The nodata-transparent tile pyramid on the GPU: the masked warp (csrc/tiles.hip warp_bilinear_masked_kernel
 through s2sr_warp_bilinear_masked_u8) against its numpy model byte for byte, the pyramid chained on the raster it keeps, the tiler
-and one /api/wow job, and the new door once under each diagnostic mode.  No tolerance anywhere: every comparison is of bytes.
+and one /api/wow job, and the door under caps 1 and 3.  No tolerance anywhere: every comparison is of bytes.  The door under red zones,
+poison, stalls and cap 8: its two rows of tests/doors.py, whose baselines this module holds to the model (what the door reads is in the
+list of tests/test_gpu_poison.py).
 
-Each figure is printed before it is judged (pytest -s).  The model's outputs are computed once per case and shared.
-
-What the door reads (the list of tests/test_gpu_poison.py, continued): engine_tiles.hip s2sr_warp_bilinear_masked_u8 SRC, DST, TABLES,
-VALID: raster, node grid and mask uploaded whole, on the kernel's stream, before it is queued; the mask index is y / vs, x / vs of a
-clamped tap, so at most ceil(H / vs) - 1, ceil(W / vs) - 1; every output pixel is written."""
-import functools
+Each figure is printed before it is judged (pytest -s).  The model's outputs are computed once per case and shared."""
 import json
 
 import numpy as np
@@ -16,40 +13,24 @@ import torch
 from PIL import Image
 
 import diag
+import doors
 import warp_masked_model as wm
-from diag import Z, clean, keep, same
+from diag import keep, same
 from doors import Inputs
 from s2sr import geo, native, tiles
+from warp_masked_model import H, W
+from warp_masked_model import case as _case
+from warp_masked_model import warp as _warp
 from s2sr import rasterio_lite as rio
 from tiff_fixture import write_tiff
 
 pytestmark = pytest.mark.gpu
-
-H, W = 150, 211
-
 
 @pytest.fixture(scope="module")
 def eng():
     e = native.Engine(num_block=1)
     yield e
     e.close()
-
-
-@functools.lru_cache(maxsize=None)
-def _case(epsg, kind):
-    """(rgb, valid, vs, plan, the model's raster) of one scene and mask"""
-    origin = dict(wm.SCENES)[epsg]
-    rgb, plan = wm.scene(H, W, seed=epsg), wm.plan_for(epsg, origin)
-    valid, vs = {"mixed": (wm.mask_mixed(H, W), 1), "coarse": (wm.mask_coarse(H, W, 4), 4), "none": (np.zeros((H, W), np.uint8), 1),
-                 "thirds": (wm.mask_coarse(H, W, 3, seed=4), 3),                   # no power of two: the cell index by division
-                 "every3": (np.ones((50, 71), np.uint8), 3),
-                 "every": (np.ones((38, 53), np.uint8), 4)}[kind]
-    want = wm.warp_bilinear_masked(rgb, valid, vs, plan.grid, plan.step, plan.out_h, plan.out_w)
-    return rgb, valid, vs, plan, want
-
-
-def _warp(e, rgb, valid, vs, plan):
-    return e.warp_bilinear_u8(rgb, plan.grid, plan.step, plan.out_h, plan.out_w, valid=valid, valid_scale=vs)
 
 
 def _differ(got, want):
@@ -395,113 +376,28 @@ def test_http_wow_job_with_transparent_tiles(monkeypatch, tmp_path):
         assert not t[t[..., 3] == 0].any()
 
 
-# ---- the new door under the four diagnostic modes ----------------------------------------------------------------------------------------
-def _door_masked_warp(e, X):
-    """the 150 x 211 / vs = 4 case (a saturated raster for the dirty predecessor: same geometry, same mask)"""
-    rgb, valid, vs, plan, _ = _case(32633, "coarse")
-    return _warp(e, np.full_like(rgb, 255) if X.dirty else rgb, valid, vs, plan)
+# ---- the door's rows of tests/doors.py -------------------------------------------------------------------------------------------------------
+MASKED_WARP = doors.owned("warp_bilinear_masked_u8")
 
 
-def _door_chain(e, X):
-    """... and the base level cut from the raster it keeps: the hand-over under the modes"""
-    raster = keep(_door_masked_warp(e, X))
-    plan = _case(32633, "coarse")[3]
-    lv = tiles.plan_levels(plan.placement.bounds(plan.out_w, plan.out_h), 15, 15)[0]
-    return raster, e.tiles_base_u8(raster.shape[:2], *tiles.plan_base(lv, plan.placement, plan.out_w, plan.out_h), on_device=True)
-
-
-NODATA_DOORS = {"warp_bilinear_masked_u8": ("x4_hp", _door_masked_warp), "warp_bilinear_masked_u8-then-base": ("x4_hp", _door_chain)}
-_BASE = {}
-
-
-def _baseline(ident):
-    """the door on a fresh engine with every mode off: computed once; the warp's half is the model's raster"""
-    if ident not in _BASE:
-        with diag.modes_off():
-            e = diag.new_engine(NODATA_DOORS[ident][0])
-            try:
-                _BASE[ident] = keep(NODATA_DOORS[ident][1](e, Inputs()))
-            finally:
-                e.close()
-        first = _BASE[ident][0] if isinstance(_BASE[ident], tuple) else _BASE[ident]
-        assert np.array_equal(first, _case(32633, "coarse")[4])
-    return _BASE[ident]
-
-
-@pytest.mark.parametrize("ident", list(NODATA_DOORS))
-def test_door_under_red_zones(ident):
-    with diag.engines_under(native.redzone_bytes, native.redzone, Z) as zoned:
-        e = zoned(NODATA_DOORS[ident][0])
-        same(keep(NODATA_DOORS[ident][1](e, Inputs())), _baseline(ident), f"{ident}, with red zones")
-        clean(e)
-
-
-@pytest.mark.parametrize("ident", list(NODATA_DOORS))
-def test_door_under_poison(ident):
-    """fresh under both patterns; poison_scratch() in front of a sighting; behind the same call on a saturated raster"""
-    name, fn = NODATA_DOORS[ident]
-    want = _baseline(ident)
-    with diag.engines_under(native.poison_pattern, native.poison) as poisoned:
-        for pattern in (1, 2):
-            e = poisoned(name, pattern)
-            native.poison(pattern)
-            same(keep(fn(e, Inputs())), want, f"{ident}, on an engine created under pattern {pattern}")
-            torch.cuda.synchronize()
-            e.poison_scratch()
-            same(keep(fn(e, Inputs())), want, f"{ident}, behind poison_scratch, pattern {pattern}")
-        native.poison(0)
-        fn(e, Inputs(dirty=True))
-        same(keep(fn(e, Inputs())), want, f"{ident}, behind the same call on a saturated raster")
-
-
-STALL_USEC = 1200                # tests/test_gpu_stall.py's figure (profiles/stall_sensitivity.txt)
-
-
-@pytest.mark.parametrize("mode", [1, 2])
-@pytest.mark.parametrize("ident", list(NODATA_DOORS))
-def test_door_under_stalls(ident, mode):
-    """The compute side stalled (mode 1) and the copy side (mode 2), the call made from a side stream, behind the same call on a
-    saturated raster and with the scratch poisoned: the procedure of tests/test_gpu_stall.py's door matrix, without its probe of
-    which streams share a hardware queue (the door runs on the handle's own stream and copies on it too)."""
-    name, fn = NODATA_DOORS[ident]
-    want = _baseline(ident)
-    before, dropped = native.delay_mode(), native.delay_dropped()
-    with diag.engines_under(native.poison_pattern, native.poison) as made:
-        e = made(name, 2)
-        side = torch.cuda.Stream()
-        native.poison(0)
-        with torch.cuda.stream(side):
-            fn(e, Inputs(dirty=True))
-        native.poison(2)
-        torch.cuda.synchronize()
-        e.poison_scratch()
-        native.delay(mode, STALL_USEC)
-        try:
-            with torch.cuda.stream(side):
-                got = keep(fn(e, Inputs()))
-        finally:
-            native.delay(0)
-            native.delay_drop(dropped)
-            native.delay(*before)
-        same(got, want, f"{ident}, stall mode {mode}")
+@pytest.mark.parametrize("ident", MASKED_WARP)
+def test_the_door_table_s_baseline_is_the_model(ident):
+    """the red-zone, poison, stall and grid-cap matrices hold every mode to diag.baseline, and this holds the baseline's raster to the
+    model, sample for sample (the base level behind it is the pyramid modules' to judge)"""
+    diag.same_values(diag.baseline(ident), doors.MODELS[ident](), ident)
 
 
 @pytest.mark.parametrize("cap", [1, 3])
-@pytest.mark.parametrize("ident", list(NODATA_DOORS))
+@pytest.mark.parametrize("ident", MASKED_WARP)
 def test_door_under_the_grid_cap(ident, cap):
     """the raster has some 32 k pixels: 128 blocks of 256 threads on 1 and on 3 workgroups, a ragged last trip"""
-    name, fn = NODATA_DOORS[ident]
-    want = _baseline(ident)
-    before = native.grid_cap_workgroups()
+    name, fn = doors.DOORS[ident]
+    want = diag.baseline(ident)
     with diag.engines_under(native.grid_cap_workgroups, native.grid_cap, cap) as capped:
         e = capped(name)
-        native.grid_cap(cap)
-        native.grid_cap_stats(reset=True)
-        try:
+        with diag.under(cap):
             got = keep(fn(e, Inputs()))
             st = native.grid_cap_stats()
-        finally:
-            native.grid_cap(before)
     print(f"{ident}, cap {cap}: tiles {st['tiles']}")
     assert st["tiles"][0] >= 1 and st["tiles"][1] >= 3, st
     same(got, want, f"{ident}, cap {cap}")

@@ -1,6 +1,7 @@
 """Field polygons as zones on the GPU (include/s2sr.h: s2sr_zones_rasterize_u16; csrc/zones.hip): labels and area byte
-for byte against tests/zones_model.py, the independence of band_rows and of the number of workgroups, every refusal, the void rule,
-the entry under red zones, poison and stalls, and the job that takes a GeoJSON file as its `zones`.
+for byte against tests/zones_model.py, the independence of band_rows and of the number of workgroups (caps 1 and 3, with the launch
+and trip arithmetic), every refusal, the void rule, and the job that takes a GeoJSON file as its `zones`.  The entry under red zones,
+poison, stalls and cap 8: its rows of tests/doors.py, whose baselines this module holds to the model.
 
 The pass's capped launches are counted in the grid-cap family "display", as the index pass's are (the launcher families are a closed
 list that tests/test_gridcap_cpu.py spells out)."""
@@ -10,8 +11,11 @@ import numpy as np
 import pytest
 
 import diag
+import doors
 import gpu_engines
 import zones_model as zm
+from diag import same_values as same
+from zones_model import case
 from s2sr import geo, native
 from s2sr import zones as xz
 
@@ -25,34 +29,8 @@ GRID_FAMILY = "display"
 
 @pytest.fixture(scope="module")
 def bare():
-    """the entry needs no weights"""
-    with diag.modes_off():
-        e = native.Engine(num_block=1, precision=HP)
-        try:
-            yield e
-        finally:
-            e.close()
-
-
-_CASES = {}
-
-
-def case(H, W, kind="scene"):
-    """(the tables, Z, the model's labels, the model's area): made once per shape and kind"""
-    if (H, W, kind) not in _CASES:
-        feats, Z = zm.scene(H, W) if kind == "scene" else zm.unit_squares() if kind == "squares" else zm.star(H, W)
-        labels, area = zm.rasterize(feats, Z, H, W)
-        labels.setflags(write=False)
-        area.setflags(write=False)
-        _CASES[H, W, kind] = zm.tables(feats), Z, labels, area
-    return _CASES[H, W, kind]
-
-
-def same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.dtype} {got.shape} against {want.dtype} {want.shape}"
-    bad = np.argwhere(got != want)
-    assert len(bad) == 0, f"{what}: {len(bad)} samples differ, the first at {tuple(bad[0])}: {got[tuple(bad[0])]} against {want[tuple(bad[0])]}"
+    with gpu_engines.bare(precision=HP) as e:                    # the entry needs no weights
+        yield e
 
 
 def run(e, H, W, kind="scene", **kw):
@@ -99,17 +77,12 @@ def test_under_capped_grids(bare, cap):
     """the same bytes, and the trips are what ceil(items / cap) says: 255 x 257 pixels are 4 x 5 tiles"""
     H, W = 255, 257
     for kind in ("scene", "star"):
-        before = native.grid_cap_workgroups()
-        native.grid_cap(cap)
-        native.grid_cap_stats(reset=True)
-        try:
+        with diag.under(cap):
             got, got_area, labels, area = run(bare, H, W, kind)
             launches, trips = native.grid_cap_stats()[GRID_FAMILY]
             native.grid_cap_stats(reset=True)
             got2, area2, _, _ = run(bare, H, W, kind, band_rows=100)                       # bands of 100, 100, 55 rows: 2, 3 and 1 tile rows
             launches2, trips2 = native.grid_cap_stats()[GRID_FAMILY]
-        finally:
-            native.grid_cap(before)
         same(got, labels, f"cap {cap}, {kind}: labels")
         same(got_area, area, f"cap {cap}, {kind}: area")
         same(got2, labels, f"cap {cap}, {kind}, in bands: labels")
@@ -185,34 +158,11 @@ def test_the_call_voids_the_kept_image():
     assert int(z[:, 0].sum()) > 0
 
 
-def test_under_red_zones_poison_and_stalls():
-    """the ragged shape in bands and the 4 x 5 tiles: the modes-off bytes, zones clean"""
-    with diag.engines_under(native.redzone_bytes, native.redzone, diag.Z) as get:
-        e = get("x4_hp")
-        for H, W, kw in ((37, 45, dict(band_rows=5)), (255, 257, {}), (1, 1, {})):
-            got, got_area, labels, area = run(e, H, W, **kw)
-            same(got, labels, f"{H} x {W} under red zones: labels")
-            same(got_area, area, f"{H} x {W} under red zones: area")
-        diag.clean(e)
-    for pattern in (1, 2):
-        with diag.engines_under(native.poison_pattern, native.poison, pattern) as get:
-            e = get("x4_hp")
-            got, got_area, labels, area = run(e, 37, 45, band_rows=5)
-            same(got, labels, f"fresh under poison pattern {pattern}: labels")
-            same(got_area, area, f"fresh under poison pattern {pattern}: area")
-            e.poison_scratch()
-            got, got_area, labels, area = run(e, 255, 257, "star")
-            same(got, labels, f"behind poison_scratch, pattern {pattern}: labels")
-            same(got_area, area, f"behind poison_scratch, pattern {pattern}: area")
-            for mode in (1, 2):                                      # stalled streams: the compute side, the copy side
-                e.poison_scratch()
-                native.delay(mode, 1200)
-                try:
-                    got, got_area, labels, area = run(e, 37, 45, band_rows=5)
-                finally:
-                    native.delay(0)
-                same(got, labels, f"under stall mode {mode}, pattern {pattern}: labels")
-                same(got_area, area, f"under stall mode {mode}, pattern {pattern}: area")
+@pytest.mark.parametrize("ident", doors.owned("zones_rasterize_u16"))
+def test_the_door_table_s_baseline_is_the_model(ident):
+    """tests/doors.py's rows of this pass: the red-zone, poison, stall and grid-cap matrices hold every mode to diag.baseline, and
+    this holds the baseline to the model, sample for sample"""
+    same(diag.baseline(ident), doors.MODELS[ident](), ident)
 
 
 # ---- the job -------------------------------------------------------------------------------------------------------------------------------------

@@ -13,6 +13,8 @@ the all-valid test ties the two).  Then
 every float32 operation rounded on its own.  An invalid tap's weight enters as +0: x + 0 = x and 0 * p = 0 exactly for the
 non-negative finite values here, so "summed over the valid taps" and "summed over all four with the invalid weights zeroed" are
 the same numbers."""
+import functools
+
 import numpy as np
 
 from s2sr import geo, tiles
@@ -143,3 +145,25 @@ def warp_bilinear_masked(rgb, valid, vs, grid, step, out_h, out_w):
         out[..., k] = np.where(plain | mixed, _add(val, f32(0.5)).astype(np.int64), 0)
     out[..., 3] = np.where(plain | mixed, 255, 0)
     return out
+
+
+# ---- the cases of the GPU tests: 150 x 211 scenes under six masks ------------------------------------------------------------------------
+H, W = 150, 211
+
+
+@functools.lru_cache(maxsize=None)
+def case(epsg, kind):
+    """(rgb, valid, vs, plan, the model's raster) of one scene and mask"""
+    origin = dict(SCENES)[epsg]
+    rgb, plan = scene(H, W, seed=epsg), plan_for(epsg, origin)
+    valid, vs = {"mixed": (mask_mixed(H, W), 1), "coarse": (mask_coarse(H, W, 4), 4), "none": (np.zeros((H, W), np.uint8), 1),
+                 "thirds": (mask_coarse(H, W, 3, seed=4), 3),                   # no power of two: the cell index by division
+                 "every3": (np.ones((50, 71), np.uint8), 3),
+                 "every": (np.ones((38, 53), np.uint8), 4)}[kind]
+    want = warp_bilinear_masked(rgb, valid, vs, plan.grid, plan.step, plan.out_h, plan.out_w)
+    return rgb, valid, vs, plan, want
+
+
+def warp(e, rgb, valid, vs, plan):
+    """the entry on a case"""
+    return e.warp_bilinear_u8(rgb, plan.grid, plan.step, plan.out_h, plan.out_w, valid=valid, valid_scale=vs)

@@ -8,6 +8,8 @@ bins (csrc/zone_bins.h), and the scenes the CPU and GPU tests share.
   a centre is inside a feature iff the count over all edges of all its rings is odd; the latest feature of the list wins.
 
 A feature here is (rings, label); a ring is a list of (x, y) vertices, the edge last -> first implied."""
+import functools
+
 import numpy as np
 
 SUB = 256
@@ -216,3 +218,13 @@ def star(H, W, n=1000):
         rad = 0.62 if k & 1 else 0.35
         ring.append((int(round(w / 2 + rad * w * np.cos(a))), int(round(h / 2 + rad * h * np.sin(a)))))
     return [([ring], 3)], 3
+
+
+@functools.lru_cache(maxsize=None)
+def case(H, W, kind="scene"):
+    """(the tables, Z, the model's labels, the model's area) of scene / unit_squares ("squares") / star: made once per shape and kind"""
+    feats, Z = scene(H, W) if kind == "scene" else unit_squares() if kind == "squares" else star(H, W)
+    labels, area = rasterize(feats, Z, H, W)
+    labels.setflags(write=False)
+    area.setflags(write=False)
+    return tables(feats), Z, labels, area
