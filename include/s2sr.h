@@ -524,6 +524,56 @@ int  s2sr_labels_trace_u16(s2sr_handle* h, const uint16_t* labels /* [H, W] */, 
 #define S2SR_FIELDS_STAGE_LABELS 7    /* labels and boxes */
 int  s2sr_debug_fields_stage_ms(s2sr_handle* h, double* ms /* [S2SR_FIELDS_STAGES] */, int32_t* launches /* [S2SR_FIELDS_STAGES] */);
 
+/* Management zones: integer k-means inside every field.  The pixels of each label of a uint16 raster are split
+ * into k classes by their values in D index rasters; the classes are ranked by the first raster, so zone 1 is the lowest.  Integers
+ * throughout; no weights needed.
+ *   feat: int16 [D][H][W], -32768 = nodata, D in 1..4 (the rasters s2sr_index_nd_u16 writes).  labels: uint16 [H][W], 0 = no field,
+ *   1..Z (Z in 1..65535), a label above Z counts as 0.  H W < 2^31.  k in 2..8, iters in 1..64, min_per_zone >= 1, smooth in 0..4.
+ *   1. members     a pixel is a member of field l if its label is l in 1..Z and none of its D values is -32768.  Every other pixel
+ *                  gets zone 0 and is counted nowhere.
+ *   2. statistics  per field the member count n_l and per feature the member minimum lo_d and maximum hi_d.  A field with
+ *                  n_l < k min_per_zone is SKIPPED: its pixels get zone 0, its status is 1, its table and centre rows are zero.
+ *   3. start       c[j][d] = lo_d + ((2 j + 1) (hi_d - lo_d)) / (2 k), j = 0..k-1: on the diagonal of the field's bounding box.
+ *   4. iteration   each member goes to the j with the smallest sum_d (v_d - c[j][d])^2 (exact: a term is below 2^32, the sum below
+ *                  2^35), a tie to the smallest j.  Per (field, j) the count n and the sums s_d are taken in int64.  A cluster
+ *                  with n > 0 gets the centre sign(s_d) ((2 |s_d| + n) / (2 n)): rounded half away from zero.  An empty cluster
+ *                  keeps its centre.
+ *   5. the run     iters iterations.  An iteration that changes no centre of any field is a fixed point; the library stops there,
+ *                  because the bytes are the same.  iterations is the number of the first such iteration, counted from 1, or iters
+ *                  if none came: a defined output.
+ *   6. zones       the members are assigned once more to the final centres.  A field's clusters are ranked by (c[j][0], j)
+ *                  ascending; the zone id is 1 + rank.  An empty cluster keeps its rank: a zone id may have no pixel.  A field
+ *                  whose values are all equal ends with every member in zone 1.
+ *   7. smoothing   smooth Jacobi passes, each reading the previous raster.  For a pixel of zone > 0 the zone ids are counted among
+ *                  the at most 9 pixels of its 3 x 3 neighbourhood that lie inside the image, carry the same label and have
+ *                  zone > 0 (itself included).  The new zone is the id with the most votes; the pixel keeps its own id if that is
+ *                  among the tied, otherwise it takes the smallest tied id.  Zone 0 stays 0.
+ *   zone: uint8 [H][W].  table: int64 [Z + 1][k][1 + 2 D], row [l][z - 1] = the pixels of zone z of field l in the FINAL raster
+ *   (after smoothing), then per feature the sum of v_d and the sum of v_d^2 (pixels, s_0, q_0, s_1, q_1, ...); row 0 and the rows of
+ *   skipped or absent fields are zero.  centres: int32 [Z + 1][k][D], the final centres in zone order, zero for skipped or absent
+ *   fields.  status: uint8 [Z + 1]: 0 absent (no member), 1 skipped, 2 zoned.  iterations: see 5.
+ *   band_rows: the rows per band the rasters travel and the pixel passes run in (0: the library's choice).
+ * Nothing depends on the order of atomics, on the row bands or on the number of workgroups: every sum is an integer add, every
+ * statistic an integer minimum or maximum.
+ * The call requests scratch, so it voids whatever the call before it kept on the device (a uint16 image, a raster, a level), and it
+ *   keeps nothing itself.
+ * S2SR_E_INVALID with a text, before the device is touched: D outside 1..4, k outside 2..8, iters outside 1..64, smooth outside
+ * 0..4, Z outside 1..65535, min_per_zone < 1, a NULL feat, labels or zone, non-positive H or W, H W >= 2^31, band_rows < 0.  The
+ * handle keeps working. */
+int  s2sr_zones_kmeans_i16(s2sr_handle* h, const int16_t* feat /* [D][H][W] */, int32_t D, int32_t H, int32_t W,
+                           const uint16_t* labels /* [H][W] */, int32_t Z, int32_t k, int32_t iters, int64_t min_per_zone, int32_t smooth,
+                           int32_t band_rows, uint8_t* zone /* [H][W] */, int64_t* table /* [Z+1][k][1+2D] or NULL */,
+                           int32_t* centres /* [Z+1][k][D] or NULL */, uint8_t* status /* [Z+1] or NULL */, uint32_t* iterations /* or NULL */);
+/* test hook: what the stages of the last s2sr_zones_kmeans_i16 on this handle took by HIP events, as s2sr_debug_fields_stage_ms
+ * does for the segmentation: S2SR_MZONES_STAGES entries in the order below, all zero when the last call ran with profiling off. */
+#define S2SR_MZONES_STAGES 5
+#define S2SR_MZONES_STATISTICS 0      /* the tables cleared, the statistics band by band, status and the start centres */
+#define S2SR_MZONES_ITERATIONS 1      /* assign-and-accumulate and the centre update, once per iteration run */
+#define S2SR_MZONES_ASSIGN 2          /* the rank map and the final assignment */
+#define S2SR_MZONES_SMOOTHING 3       /* the mode filter's passes */
+#define S2SR_MZONES_TABLE 4           /* the sums of the final raster */
+int  s2sr_debug_mzones_stage_ms(s2sr_handle* h, double* ms /* [S2SR_MZONES_STAGES] */, int32_t* launches /* [S2SR_MZONES_STAGES] */);
+
 /* Multi-GPU building blocks of _tile_process (cnn_super_resolution.py:244-278), device-resident:
  * cut windows [first, first+count) of the plan into d_tiles [count, wh, ww, 3] (wh/ww = the
  * plan's common window size), and paste ALL T windows' outputs d_tiles [T, 4wh, 4ww, 3] into

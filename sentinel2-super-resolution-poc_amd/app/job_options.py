@@ -14,7 +14,8 @@ else: the refusals (`check`), the keywords each call seam passes on (`passed`), 
 | extra_weights     | None    | the guide weights of extra_bands in R, G, B terms                                         | both are given      |
 | indices           | None    | 16-bit jobs: spectral indices on the SR grid (s2sr/index.py)               | given               |
 | index_offset      | 0       | the DN offset of the index definitions that name none                                     | indices are given   |
-| zones             | None    | a label raster (path or array), field polygons or {"segment": ...} for per-zone tables    | indices are given   |
+| zones             | None    | a label raster (path or array), field polygons or {"segment": ...} for per-zone tables;   | indices are given   |
+|                   |         | {"manage": ..., "fields": one of those} adds management zones (s2sr/mzones.py)            |                     |
 | transparent_tiles | False   | the tile pyramid shows the map through the job's nodata pixels            | true                |
 
 A callee with the reference's signature (tests patch such stand-ins in) must keep working for a job that asks for nothing: an option
@@ -123,9 +124,15 @@ class JobOptions:
                 raise ValueError("indices are computed on the 16-bit path: pass bit_depth=16 (an 8-bit job has no uint16 product to take them from)")
             self.check_option("indices", band_count)
             from s2sr import fields as xf
-            if xf.is_segment(self.zones):      # (that its index is among the job's: s2sr.fields.resolve, with the definitions at hand)
+            from s2sr import mzones as xm
+            zones = self.zones
+            if xm.is_manage(zones):            # management zones: its own refusals, then `fields` as the value it is
                 from s2sr.index import resolve
-                xf.check_index(xf.check_option(self.zones), resolve(self.indices, self.index_offset, band_count))
+                xm.check_index(xm.check_option(zones), resolve(self.indices, self.index_offset, band_count))
+                zones = zones["fields"]
+            if xf.is_segment(zones):           # (that its index is among the job's: s2sr.fields.resolve, with the definitions at hand)
+                from s2sr.index import resolve
+                xf.check_index(xf.check_option(zones), resolve(self.indices, self.index_offset, band_count))
         elif self.zones is not None or self.index_offset != 0:
             raise ValueError("zones and index_offset belong to indices: pass indices")
         if self.display is not None:

@@ -101,12 +101,22 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
     job also writes <stem>_zones.tif (uint16, GDAL_NODATA 0, the product's georeference) and the metadata gains "zones", and only then.
     zones may also be {"segment": {"index": name, "min": 0.3, "max": None, "open": 1, "close": 2, "connectivity": 4, "min_area_ha": 0.5}}
     (s2sr/fields.py): the fields are the connected components of the thresholded, opened and closed raster of the named
-    index; the job writes <stem>_zones.tif as above and <stem>_fields.geojson (one Feature per field, lon / lat)."""
+    index; the job writes <stem>_zones.tif as above and <stem>_fields.geojson (one Feature per field, lon / lat).
+    zones may also be {"manage": {"index": name or names, "k": 3, "iterations": 32, "min_per_zone": 10, "smooth": 1, "polygons": True},
+    "fields": any of the values above} (DESIGN.md 7.11; s2sr/mzones.py): `fields` is handled exactly as that value is without "manage";
+    the pixels of every field are then split into k zones by the named index rasters (integer k-means on the job's engine), and the job
+    writes <stem>_mzones.tif (uint8, GDAL_NODATA 0, the product's georeference), with polygons <stem>_mzones.geojson (one Feature per
+    field and zone), and metadata["zones"]["management"]."""
     import dataclasses
 
     from s2sr import rasterio_lite as rio
     from s2sr.display import Stretch
     stretch = None if o.display is None else Stretch.of(o.display)
+    from s2sr import mzones as xm
+    manage = None
+    if xm.is_manage(o.zones):          # management zones (DESIGN.md 7.11): from here on `zones` is the value of "fields", handled as ever
+        manage = {"option": o.zones}
+        o = dataclasses.replace(o, zones=o.zones["fields"])
 
     input_path = Path(input_path)
     print(f"\nWOW Super-Resolution ({model}, 16-bit)\n   Input: {input_path}")
@@ -142,6 +152,10 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
     if extra is not None:            # the device copy is BGR: the guide weights go in reversed
         call.update(extra=extra, extra_weights=w_rgb[::-1])
     burnt = seg = None
+    if manage is not None:             # its refusals before the net runs; the GeoJSON needs the raster's place
+        manage["params"] = xm.resolve(manage["option"], defs)
+        if manage["params"]["polygons"]:
+            xf.placement_of(None if georef is None else georef.scaled(esrgan.scale))
     if defs is not None and segmenting:    # every refusal of the option before the net runs; the size in pixels of the output grid
         xf.placement_of(None if georef is None else georef.scaled(esrgan.scale))      # the GeoJSON needs the raster's place
         size = georef.scaled(esrgan.scale).pixel_size
@@ -174,6 +188,14 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
         for d, r in zip(call["indices"], found):
             r["zonal"] = xf.zonal(esrgan._engine, d, got.out16, carried, valid, seg["labels"], seg["found"])
         label = (seg["labels"], 1, seg["found"])
+    if manage is not None:           # k-means inside every field on the named index rasters (host arrays: the call voids the kept image)
+        mz_labels = np.asarray(label[0]) if label[1] == 1 else \
+            np.repeat(np.repeat(np.asarray(label[0]), label[1], axis=0), label[1], axis=1)[:got.out16.shape[0], :got.out16.shape[1]]
+        mz_labels = np.ascontiguousarray(mz_labels.astype(np.uint16))
+        params = manage["params"]
+        manage["result"] = xm.run(esrgan._engine, [found[i]["index"] for i in params["indices"]], mz_labels, label[2], params)
+        if params["polygons"]:
+            manage["rings"] = xm.trace(esrgan._engine, manage["result"]["zone"], mz_labels, label[2], params["k"])
     del esrgan
     final_output = Path(output_path).with_suffix(".tif")
     final_output.parent.mkdir(parents=True, exist_ok=True)
@@ -237,6 +259,14 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
             gj = xf.write_geojson(final_output.with_name(f"{final_output.stem}_fields.geojson"),
                                   xf.to_geojson(xf.polygons(seg["rings"], seg["fields"]), out_geo, out_geo.pixel_size, tables))
             metadata["zones"] = xf.metadata_block(seg["params"], seg["found"], seg["fields"], seg["labels"].shape, ztif, gj, out_geo.pixel_size)
+        if manage is not None:
+            mtif = final_output.with_name(f"{final_output.stem}_mzones.tif")
+            rio.write_geotiff_u8(mtif, manage["result"]["zone"][..., None], out_geo, nodata=0)
+            rows = xm.zone_rows(manage["result"]["table"], manage["result"]["status"], manage["params"], out_geo.pixel_size)
+            mgj = None
+            if manage["params"]["polygons"]:
+                mgj = xm.write_geojson(final_output.with_name(f"{final_output.stem}_mzones.geojson"), xm.to_geojson(manage["rings"], rows, out_geo))
+            metadata.setdefault("zones", {})["management"] = xm.metadata_block(manage["params"], manage["result"], rows, mtif, mgj)
     return final_output, metadata
 
 
@@ -375,10 +405,14 @@ def process_wow_sr(input_tif: Path, output_dir: Path, enhance_crops: bool = True
     }
     if indices is not None:
         result["outputs"]["indices"] = {e["name"]: dict(e["files"]) for e in sr_metadata.get("indices", [])}
-    if "zones" in sr_metadata:           # field polygons were rasterised: the label raster the job wrote
+    if "file" in sr_metadata.get("zones", {}):       # field polygons were rasterised: the label raster the job wrote
         result["outputs"]["zones_tif"] = sr_metadata["zones"]["file"]
         if sr_metadata["zones"].get("geojson"):      # the fields were segmented from the image
             result["outputs"]["fields_geojson"] = sr_metadata["zones"]["geojson"]
+    if "management" in sr_metadata.get("zones", {}):      # management zones inside the fields
+        result["outputs"]["management_tif"] = sr_metadata["zones"]["management"]["file"]
+        if sr_metadata["zones"]["management"].get("geojson"):
+            result["outputs"]["management_geojson"] = sr_metadata["zones"]["management"]["geojson"]
     with open(output_dir / f"{base_name}_wow_sr_metadata.json", "w") as f:
         json.dump(result, f, indent=2)
     return result

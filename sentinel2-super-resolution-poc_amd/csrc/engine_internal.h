@@ -1,4 +1,4 @@
-// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_display.hip, engine_bands.hip, engine_index.hip, engine_zones.hip, engine_fields.hip, engine_debug.hip): the handle behind
+// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_display.hip, engine_bands.hip, engine_index.hip, engine_zones.hip, engine_fields.hip, engine_mzones.hip, engine_debug.hip): the handle behind
 // the C ABI of include/s2sr.h, the types it is made of, and the helpers that more than one of those files uses.  What a single
 // file uses stays static or anonymous in that file.
 #pragma once
@@ -20,14 +20,17 @@ enum Slot : int {
     SL_SRC = 0,   // 0 and 1: a call's source and its result: the upload and the image / tiles / level that leave.  Along a chain of
     SL_DST,       //   pyramid or display calls the roles swap: the source is where the call before kept its result, the result other() of it;
                   //   slot 1 also holds the label raster s2sr_zones_rasterize_u16 makes (kept by nobody: it leaves for the host in bands);
-                  //   s2sr_fields_segment_i16: slot 0 the int16 index raster, slot 1 the uint16 labels
+                  //   s2sr_fields_segment_i16: slot 0 the int16 index raster, slot 1 the uint16 labels;
+                  //   s2sr_zones_kmeans_i16: slot 0 the D int16 index rasters, slot 1 the uint16 labels
     SL_MID,       // what lies between: gathered windows (the untiled image's tiles), the 16-bit batch's quantised tiles, the resample
                   //   intermediate, the PNG writer's statistics, the band s2sr_carry_band_u16 carries, plane b of s2sr_index_nd_u16,
-                  //   one of the two uint8 mask planes of s2sr_fields_segment_i16 (the morphology passes ping-pong between this one and SL_CHUNK)
+                  //   one of the two uint8 mask planes of s2sr_fields_segment_i16 (the morphology passes ping-pong between this one and SL_CHUNK),
+                  //   one of the two uint8 zone rasters of s2sr_zones_kmeans_i16 (the mode filter ping-pongs between this one and SL_CHUNK)
     SL_TABLES,    // tables and plans: paste / blend tables, warp grid, footprint and tap tables, PNG plans, display histogram + LUT, an index pass's LUT, counter,
                   //   histogram and zonal sums; a zone rasterisation's xy, ring_start, feat_start, label, tile bins (starts, features) and area;
-                  //   a segmentation's chunk sums (uint32 per 1024 pixels), found (uint64) and fields (uint64 [Z + 1][6])
-    SL_CHUNK,     // a chunk's tile outputs, the unbanded post-process's image, the PNG streams of even groups; a segmentation's other mask plane
+                  //   a segmentation's chunk sums (uint32 per 1024 pixels), found (uint64) and fields (uint64 [Z + 1][6]);
+                  //   a k-means' per-field count, minima, maxima, status, rank map, centres, ranked centres, changed flag and sums / table
+    SL_CHUNK,     // a chunk's tile outputs, the unbanded post-process's image, the PNG streams of even groups; a segmentation's other mask plane; a k-means' other zone raster
     SL_PP,        // the post-process work area, where a banded run lives while it is open; the PNG streams of odd groups (the level the
                   //   writer reads is in 0 / 1, so while it runs 2 .. 5 are free); a segmentation's parent plane (int32 per pixel: the local root,
                   //   then the root; -1 background)
@@ -290,6 +293,9 @@ struct s2sr_handle {
     // s2sr_fields_segment_i16 with profiling on: the event time and the bracketed launches of the last call, stage by stage (S2SR_FIELDS_STAGE_*)
     double fields_stage_ms[S2SR_FIELDS_STAGES] = {};
     int32_t fields_stage_launches[S2SR_FIELDS_STAGES] = {};
+    // s2sr_zones_kmeans_i16 with profiling on: the same, by S2SR_MZONES_* stage
+    double mzones_stage_ms[S2SR_MZONES_STAGES] = {};
+    int32_t mzones_stage_launches[S2SR_MZONES_STAGES] = {};
     s2sr::engine::TrunkTap* ttap = nullptr;     // s2sr_debug_trunk_taps' batch is running (run_net taps the trunk at its RDB boundaries); null otherwise
     s2sr::engine::CompactTap* ctap = nullptr;   // s2sr_debug_compact_taps' batch is running
 };

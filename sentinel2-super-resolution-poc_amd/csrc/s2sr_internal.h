@@ -380,6 +380,30 @@ hipError_t launch_fields_apply(const int* d_parent, uint32_t* d_size, int H, int
 hipError_t launch_fields_labels(const int* d_parent, const uint32_t* d_size, int H, int W, uint32_t Z, uint16_t* d_labels, unsigned long long* d_fields,
                                 hipStream_t st);
 
+// Management zones (mzones.hip), one launcher per step.  d_feat: int16 [D][H][W] (D in 1..4), d_labels: uint16 [H][W],
+// H W < 2^31, Z in 1..65535, k in 2..8; the pixel passes take the rows [y0, y1) of the image.  The tables, Z + 1 rows each:
+//   d_cnt uint32, d_lo / d_hi int32 [D]       the members and their minimum / maximum per feature (clear, then stats band by band)
+//   d_status uint8                            0 absent, 1 skipped (fewer than `least` = k min_per_zone members), 2 zoned
+//   d_centres int32 [k][D]                    start writes them, update moves them
+//   d_acc uint64 [k][1 + D]                   n, s_d of one iteration: zero before the first accumulate, left at zero by update;
+//                                             with d_zone (the table pass) [k][1 + 2 D]: n, then s_d, q_d per feature, zeroed by the caller
+//   d_zone_of uint8 [k], d_ranked int32 [k][D]   rank: the zone id of cluster j, and the centres in zone order
+//   *d_changed                                update ORs 1 into it when a centre moved
+// accumulate without d_zone assigns each member to its nearest centre; with d_zone the cluster is the raster's id - 1.
+// assign writes every pixel of its rows of d_zone; mode is one Jacobi pass of the 3 x 3 filter, d_src the whole previous raster.
+hipError_t launch_mzones_clear(uint32_t* d_cnt, int* d_lo, int* d_hi, int Z, int D, hipStream_t st);
+hipError_t launch_mzones_stats(const int16_t* d_feat, int D, int H, int W, int y0, int y1, const uint16_t* d_labels, int Z, uint32_t* d_cnt, int* d_lo,
+                               int* d_hi, hipStream_t st);
+hipError_t launch_mzones_start(const uint32_t* d_cnt, const int* d_lo, const int* d_hi, int Z, int k, int D, long long least, uint8_t* d_status,
+                               int* d_centres, hipStream_t st);
+hipError_t launch_mzones_accumulate(const int16_t* d_feat, int D, int H, int W, int y0, int y1, const uint16_t* d_labels, int Z, int k,
+                                    const int* d_centres, const uint8_t* d_status, const uint8_t* d_zone, unsigned long long* d_acc, hipStream_t st);
+hipError_t launch_mzones_update(unsigned long long* d_acc, int Z, int k, int D, const uint8_t* d_status, int* d_centres, uint32_t* d_changed, hipStream_t st);
+hipError_t launch_mzones_rank(const int* d_centres, int Z, int k, int D, const uint8_t* d_status, uint8_t* d_zone_of, int* d_ranked, hipStream_t st);
+hipError_t launch_mzones_assign(const int16_t* d_feat, int D, int H, int W, int y0, int y1, const uint16_t* d_labels, int Z, int k, const int* d_centres,
+                                const uint8_t* d_status, const uint8_t* d_zone_of, uint8_t* d_zone, hipStream_t st);
+hipError_t launch_mzones_mode(const uint8_t* d_src, const uint16_t* d_labels, int H, int W, int y0, int y1, int k, uint8_t* d_dst, hipStream_t st);
+
 // XYZ tile pyramid (tiles.hip)
 hipError_t launch_warp_bilinear(const uint8_t* d_rgb, int H, int W, const float* d_grid, int gh, int gw, int step, int OH, int OW,
                                 uint8_t* d_out, hipStream_t st);

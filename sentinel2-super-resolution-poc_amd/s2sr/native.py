@@ -174,6 +174,9 @@ _PROTOS = {
     "s2sr_fields_segment_i16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.c_int64, C.c_int32] + [C.c_void_p] * 3),
     "s2sr_labels_trace_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_uint64] * 2 + [C.c_void_p] * 4),
     "s2sr_debug_fields_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s2sr_zones_kmeans_i16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] + [C.c_int32] * 3 + [C.c_int64] + [C.c_int32] * 2 +
+                              [C.c_void_p] * 5),
+    "s2sr_debug_mzones_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "s2sr_enhance_job_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PPParams), C.c_void_p]),
     "s2sr_enhance_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "s2sr_tile_process_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
@@ -257,6 +260,7 @@ _PROTOS = {
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 FIELDS_STAGES = ("mask_morphology", "local", "border", "flatten", "count", "scan", "apply", "labels")   # S2SR_FIELDS_STAGE_*
+MZONES_STAGES = ("statistics", "iterations", "assign", "smoothing", "table")                            # S2SR_MZONES_*
 
 
 def _mapped_hip_runtimes() -> set:
@@ -1074,6 +1078,39 @@ class Engine:
         ms, n = np.zeros(len(FIELDS_STAGES), np.float64), np.zeros(len(FIELDS_STAGES), np.int32)
         self._check(self._lib.s2sr_debug_fields_stage_ms(self._h, _ptr(ms), _ptr(n)), "s2sr_debug_fields_stage_ms")
         return {name: (float(ms[k]), int(n[k])) for k, name in enumerate(FIELDS_STAGES)}
+
+    def zones_kmeans_i16(self, feats, labels, Z: int, k: int = 3, iters: int = 32, min_per_zone: int = 10, smooth: int = 0, band_rows: int = 0) -> dict:
+        """Integer k-means inside every field (include/s2sr.h s2sr_zones_kmeans_i16).  feats: int16 [D, H, W] (or
+        [H, W]: one raster), nodata -32768; labels: uint16 [H, W], 0 = no field, above Z = no field.  Returns {"zone": uint8 [H, W]
+        (0: no zone; 1 the lowest class of the first raster), "table": int64 [Z + 1, k, 1 + 2 D] = pixels, then sum and sum of
+        squares per raster, "centres": int32 [Z + 1, k, D] in zone order, "status": uint8 [Z + 1] (0 absent, 1 skipped, 2 zoned),
+        "iterations": int}.  The call voids whatever the call before it kept on the device.  No weights needed."""
+        feats, labels = np.asarray(feats), np.asarray(labels)
+        if feats.dtype == np.int16 and feats.ndim == 2:
+            feats = feats[None]
+        if feats.dtype != np.int16 or feats.ndim != 3:
+            raise TypeError(f"zones_kmeans_i16 takes int16 rasters [D, H, W], got {feats.dtype} {feats.shape}")
+        if labels.dtype != np.uint16 or labels.ndim != 2 or labels.shape != feats.shape[1:]:
+            raise TypeError(f"zones_kmeans_i16 takes uint16 labels {feats.shape[1:]}, got {labels.dtype} {labels.shape}")
+        feats, labels = np.ascontiguousarray(feats), np.ascontiguousarray(labels)
+        D, H, W = feats.shape
+        Z, k = int(Z), int(k)
+        ok = H > 0 and W > 0 and H * W < 2 ** 31
+        rows, kk, dd = (Z + 1 if 0 <= Z <= 65535 else 1), (k if 2 <= k <= 8 else 1), (D if 1 <= D <= 4 else 1)
+        zone = pinned_pool.empty((H, W), np.uint8) if ok else np.empty((1,), np.uint8)
+        table, centres = np.zeros((rows, kk, 1 + 2 * dd), np.int64), np.zeros((rows, kk, dd), np.int32)
+        status, iterations = np.zeros(rows, np.uint8), np.zeros(1, np.uint32)
+        self._check(self._lib.s2sr_zones_kmeans_i16(self._h, _ptr(feats), D, H, W, _ptr(labels), Z, k, int(iters), int(min_per_zone), int(smooth),
+                                                    int(band_rows), _ptr(zone), _ptr(table), _ptr(centres), _ptr(status), _ptr(iterations)),
+                    "s2sr_zones_kmeans_i16")
+        return {"zone": zone, "table": table, "centres": centres, "status": status, "iterations": int(iterations[0])}
+
+    def mzones_stage_ms(self) -> dict:
+        """What the stages of the last zones_kmeans_i16 took by HIP events, {stage: (ms, launches)} in the order of MZONES_STAGES
+        (include/s2sr.h s2sr_debug_mzones_stage_ms): zeros unless that call ran under set_profiling(1)."""
+        ms, n = np.zeros(len(MZONES_STAGES), np.float64), np.zeros(len(MZONES_STAGES), np.int32)
+        self._check(self._lib.s2sr_debug_mzones_stage_ms(self._h, _ptr(ms), _ptr(n)), "s2sr_debug_mzones_stage_ms")
+        return {name: (float(ms[k]), int(n[k])) for k, name in enumerate(MZONES_STAGES)}
 
     def labels_trace_u16(self, labels, Z: int):
         """A uint16 label raster [H, W] -> (xy int32 [V, 2] in pixel corners, ring_start int32 [R + 1], ring_label uint16 [R]): the

@@ -528,3 +528,16 @@ def write_geotiff_i16(path: Path, band: np.ndarray, georef: GeoRef, nodata=None,
     if band.ndim != 3 or band.shape[2] < 1 or band.dtype != np.int16:
         raise ValueError(f"expected HxW or HxWxB int16, got {band.shape} {band.dtype}")
     _write_geotiff_16(path, band, georef, nodata, rows_per_strip, 2)
+
+
+def write_geotiff_u8(path: Path, band: np.ndarray, georef: GeoRef, nodata=None, rows_per_strip: int = 64) -> None:
+    """uint8 [H, W] or [H, W, B]: the 8-bit sibling of `write_geotiff_u16` -- the same strips, geo tags and nodata; B = 1 is
+    BlackIsZero: the management-zone raster of app.wow_sr, whose GDAL_NODATA is 0.  `read_bands_raw` hands the samples back as uint8."""
+    band = np.asarray(band)
+    if band.ndim == 2:
+        band = band[..., None]
+    if band.ndim != 3 or band.shape[2] < 1 or band.dtype != np.uint8:
+        raise ValueError(f"expected HxW or HxWxB uint8, got {band.shape} {band.dtype}")
+    band = np.ascontiguousarray(band)
+    _write_strips(path, band.shape[0], band.shape[1], lambda s: band[s[0]:s[1]].reshape(-1), georef, rows_per_strip, nodata, bits=8,
+                  samples=band.shape[2])
