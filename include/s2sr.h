@@ -524,6 +524,65 @@ int  s2sr_labels_trace_u16(s2sr_handle* h, const uint16_t* labels /* [H, W] */, 
 #define S2SR_FIELDS_STAGE_LABELS 7    /* labels and boxes */
 int  s2sr_debug_fields_stage_ms(s2sr_handle* h, double* ms /* [S2SR_FIELDS_STAGES] */, int32_t* launches /* [S2SR_FIELDS_STAGES] */);
 
+/* Touching fields split: s2sr_fields_segment_i16 with the blobs of several parcels cut apart.  Two vegetated
+ * parcels with no bare pixel between them, or joined by a bridge the close built, are one component of the mask; here every
+ * component is split around the cores of its distance transform, optionally after field boundaries found as a gradient ridge of
+ * the index were taken out.  Integers throughout, order-free; no weights needed.  All arguments up to Z are s2sr_fields_segment_i16's.
+ *   1. mask      m: steps 1 and 2 of s2sr_fields_segment_i16, unchanged.
+ *   2. interior  I = m when edge == 0.  Otherwise, for every pixel p that is not nodata: B(p) is the sum over the (2 edge_r + 1)^2 box
+ *                around p of idx[q], where a q outside the image or a nodata q contributes idx[p] instead; gx and gy are the
+ *                unnormalised 3 x 3 Sobel sums of B, where a neighbour outside the image or a nodata neighbour contributes B(p); p is
+ *                an edge pixel iff gx^2 + gy^2 > (8 n T)^2 with n = (2 edge_r + 1)^2 and T = edge, in index units (of 1 / K) per
+ *                pixel.  int64 arithmetic: everything stays below 2^50.  I = m minus the edge pixels.
+ *   3. distance  for p in I, D2(p) = min(255^2, min |p - q|^2 over the pixels q of the image that are not in I); elsewhere D2 = 0: the
+ *                exact squared Euclidean distance, capped.  Pixels beyond the image take no part, as in the morphology: a field on
+ *                the raster's edge does not thin out there.
+ *   4. cores     take the components of I under conn; Dmax2 is the largest D2 in a component.  A pixel of I is a core pixel iff
+ *                Dmax2 < core_px^2 (the whole component is then one core), or else iff D2 >= core_px^2 and
+ *                1000000 D2 >= core_q^2 Dmax2.  Every component of I therefore holds a core.
+ *   5. markers   the components of the core pixels under conn.  A marker's key is its smallest linear index y W + x.
+ *   6. growth inside I         every pixel of I goes to the marker with the smallest pair (number of conn-steps of the shortest path
+ *                inside I, marker key).
+ *   7. growth over the edges   every pixel of m \ I goes to the owner with the smallest pair (steps of the shortest path that runs
+ *                through m \ I and starts on any pixel of I, marker key of that pixel's owner); a pixel of I from which several
+ *                paths start counts with its own owner.  A pixel of m \ I that no such path reaches gets label 0.
+ *   8. fields    a field is the set of pixels of one owner.  Its key is the smallest linear index among ITS pixels (not the
+ *                marker's).  Size, min_pixels, numbering by ascending key, Z, found and the fields table are exactly as in step 3 of
+ *                s2sr_fields_segment_i16.
+ *   labels, fields, found: as s2sr_fields_segment_i16.  dist2: uint16 [H, W] or NULL, receives D2.  cores: uint8 [H, W] or NULL,
+ *   receives 1 on core pixels and 0 elsewhere.
+ * split == NULL gives the bytes of s2sr_fields_segment_i16 (dist2 and cores are then left alone); so does {core_q 1, core_px 0,
+ * edge 0}, because every pixel of m is then a core.  Nothing depends on the order of atomics, on the row bands the rasters travel in,
+ * on the number of workgroups or on which stream runs first.
+ * The call requests scratch, so it voids whatever the call before it kept on the device, and it keeps nothing itself.
+ * S2SR_E_INVALID with a text, before the device is touched: every refusal of s2sr_fields_segment_i16, core_q outside 1..1000,
+ * core_px outside 0..255, edge outside 0..32767, edge_r outside 0..4.  The handle keeps working. */
+typedef struct s2sr_fields_split {
+    int32_t core_q;    /* 1..1000: a core pixel lies at >= core_q / 1000 of its interior component's largest distance */
+    int32_t core_px;   /* 0..255: and at >= core_px pixels from the interior's outside */
+    int32_t edge;      /* 0: no edge test; 1..32767: T, index units (of 1 / K) per pixel */
+    int32_t edge_r;    /* 0..4: radius of the box sum in front of the Sobel */
+} s2sr_fields_split;
+int  s2sr_fields_split_i16(s2sr_handle* h, const int16_t* idx /* [H, W] */, int32_t H, int32_t W, int32_t lo, int32_t hi, int32_t r_open,
+                           int32_t r_close, int32_t conn, int64_t min_pixels, int32_t Z,
+                           const s2sr_fields_split* split /* NULL: exactly s2sr_fields_segment_i16 */, uint16_t* labels /* [H, W] */,
+                           int64_t* fields /* [Z + 1][6] or NULL */, uint64_t* found /* or NULL */, uint16_t* dist2 /* [H, W] or NULL */,
+                           uint8_t* cores /* [H, W] or NULL */);
+/* test hook: what the stages of the last s2sr_fields_split_i16 with a split on this handle took by HIP events, as
+ * s2sr_debug_fields_stage_ms does for the plain segmentation (which keeps its own hook): S2SR_FSPLIT_STAGES entries in the order
+ * below, all zero when the last call ran with profiling off.  rounds: int32 [2], the launches the growth inside I and the growth
+ * over the edge pixels took until one changed nothing (the last one included; 0 for a growth that did not run), filled always. */
+#define S2SR_FSPLIT_STAGES 7
+#define S2SR_FSPLIT_EDGE 0            /* the mask and its morphology, the edge test: the interior */
+#define S2SR_FSPLIT_DISTANCE 1        /* the column pass and the row pass */
+#define S2SR_FSPLIT_CORES 2           /* components of the interior, maxima, the core test, components of the cores, the seeds */
+#define S2SR_FSPLIT_GROW_INTERIOR 3   /* the rounds of the growth inside I */
+#define S2SR_FSPLIT_GROW_EDGES 4      /* the restart and the rounds of the growth over the edge pixels */
+#define S2SR_FSPLIT_REMAP 5           /* field keys, parents and sizes */
+#define S2SR_FSPLIT_NUMBERING 6       /* count, scan, apply, labels */
+int  s2sr_debug_fields_split_stage_ms(s2sr_handle* h, double* ms /* [S2SR_FSPLIT_STAGES] */, int32_t* launches /* [S2SR_FSPLIT_STAGES] */,
+                                      int32_t* rounds /* [2] */);
+
 /* Management zones: integer k-means inside every field.  The pixels of each label of a uint16 raster are split
  * into k classes by their values in D index rasters; the classes are ranked by the first raster, so zone 1 is the lowest.  Integers
  * throughout; no weights needed.

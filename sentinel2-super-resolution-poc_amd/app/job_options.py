@@ -16,6 +16,7 @@ else: the refusals (`check`), the keywords each call seam passes on (`passed`), 
 | index_offset      | 0       | the DN offset of the index definitions that name none                                     | indices are given   |
 | zones             | None    | a label raster (path or array), field polygons or {"segment": ...} for per-zone tables;   | indices are given   |
 |                   |         | {"manage": ..., "fields": one of those} adds management zones (s2sr/mzones.py)            |                     |
+|                   |         | "split" inside "segment" cuts touching fields apart (s2sr/fields.py)      |                     |
 | transparent_tiles | False   | the tile pyramid shows the map through the job's nodata pixels            | true                |
 
 A callee with the reference's signature (tests patch such stand-ins in) must keep working for a job that asks for nothing: an option

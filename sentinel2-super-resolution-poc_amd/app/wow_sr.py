@@ -102,6 +102,9 @@ def _apply_wow_sr16(input_path: Path, output_path: Path, model: str, enhance_cro
     zones may also be {"segment": {"index": name, "min": 0.3, "max": None, "open": 1, "close": 2, "connectivity": 4, "min_area_ha": 0.5}}
     (s2sr/fields.py): the fields are the connected components of the thresholded, opened and closed raster of the named
     index; the job writes <stem>_zones.tif as above and <stem>_fields.geojson (one Feature per field, lon / lat).
+    With "split": True or {"core": 0.5, "core_px": 2, "edge": None, "edge_smooth": 1} inside "segment"  touching fields
+    are cut apart around the cores of their distance transform, optionally along gradient ridges of the index; the files are the same
+    files, and metadata["zones"]["parameters"] gains "split", and only then.
     zones may also be {"manage": {"index": name or names, "k": 3, "iterations": 32, "min_per_zone": 10, "smooth": 1, "polygons": True},
     "fields": any of the values above} (DESIGN.md 7.11; s2sr/mzones.py): `fields` is handled exactly as that value is without "manage";
     the pixels of every field are then split into k zones by the named index rasters (integer k-means on the job's engine), and the job

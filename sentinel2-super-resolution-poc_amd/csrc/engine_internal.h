@@ -1,4 +1,4 @@
-// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_display.hip, engine_bands.hip, engine_index.hip, engine_zones.hip, engine_fields.hip, engine_mzones.hip, engine_debug.hip): the handle behind
+// Internal to the engine's translation units (engine.hip, engine_aoi.hip, engine_tiles.hip, engine_display.hip, engine_bands.hip, engine_index.hip, engine_zones.hip, engine_fields.hip, engine_fields_split.hip, engine_mzones.hip, engine_debug.hip): the handle behind
 // the C ABI of include/s2sr.h, the types it is made of, and the helpers that more than one of those files uses.  What a single
 // file uses stays static or anonymous in that file.
 #pragma once
@@ -21,23 +21,28 @@ enum Slot : int {
     SL_DST,       //   pyramid or display calls the roles swap: the source is where the call before kept its result, the result other() of it;
                   //   slot 1 also holds the label raster s2sr_zones_rasterize_u16 makes (kept by nobody: it leaves for the host in bands);
                   //   s2sr_fields_segment_i16: slot 0 the int16 index raster, slot 1 the uint16 labels;
-                  //   s2sr_zones_kmeans_i16: slot 0 the D int16 index rasters, slot 1 the uint16 labels
+                  //   s2sr_zones_kmeans_i16: slot 0 the D int16 index rasters, slot 1 the uint16 labels;
+                  //   s2sr_fields_split_i16: as s2sr_fields_segment_i16; until the labels are written slot 1 holds the uint16 distance plane D2
     SL_MID,       // what lies between: gathered windows (the untiled image's tiles), the 16-bit batch's quantised tiles, the resample
                   //   intermediate, the PNG writer's statistics, the band s2sr_carry_band_u16 carries, plane b of s2sr_index_nd_u16,
                   //   one of the two uint8 mask planes of s2sr_fields_segment_i16 (the morphology passes ping-pong between this one and SL_CHUNK),
-                  //   one of the two uint8 zone rasters of s2sr_zones_kmeans_i16 (the mode filter ping-pongs between this one and SL_CHUNK)
+                  //   one of the two uint8 zone rasters of s2sr_zones_kmeans_i16 (the mode filter ping-pongs between this one and SL_CHUNK);
+                  //   s2sr_fields_split_i16: of this one and SL_CHUNK, one ends as the mask m and the other takes the interior I
     SL_TABLES,    // tables and plans: paste / blend tables, warp grid, footprint and tap tables, PNG plans, display histogram + LUT, an index pass's LUT, counter,
                   //   histogram and zonal sums; a zone rasterisation's xy, ring_start, feat_start, label, tile bins (starts, features) and area;
                   //   a segmentation's chunk sums (uint32 per 1024 pixels), found (uint64) and fields (uint64 [Z + 1][6]);
-                  //   a k-means' per-field count, minima, maxima, status, rank map, centres, ranked centres, changed flag and sums / table
+                  //   a k-means' per-field count, minima, maxima, status, rank map, centres, ranked centres, changed flag and sums / table;
+                  //   a split's tables are a segmentation's with the growth's changed counter (uint32) and two planes of tile marks (uint8 per 64 x 64 tile) between found and fields
     SL_CHUNK,     // a chunk's tile outputs, the unbanded post-process's image, the PNG streams of even groups; a segmentation's other mask plane; a k-means' other zone raster
     SL_PP,        // the post-process work area, where a banded run lives while it is open; the PNG streams of odd groups (the level the
                   //   writer reads is in 0 / 1, so while it runs 2 .. 5 are free); a segmentation's parent plane (int32 per pixel: the local root,
-                  //   then the root; -1 background)
-    SL_VALID,     // the device copy of a masked call's `valid` (nodata.hip; the masked warp of tiles.hip); an index pass's `valid` and, behind it, its zone labels
+                  //   then the root; -1 background); a split's growth words (uint64 per pixel: steps << 32 | owner key, all ones = unreached)
+    SL_VALID,     // the device copy of a masked call's `valid` (nodata.hip; the masked warp of tiles.hip); an index pass's `valid` and, behind it, its zone labels;
+                  //   a split's vertical distances g (uint8 per pixel) and, behind the distance pass, its core plane (uint8)
     SL_CONS,      // a consistency pass's inexact counters (uint64[3], the first 256 bytes) and, in mode 2, its residual plane (consistency.hip);
                   //   a carried band's inexact counter (uint64, the first 256 bytes) and its coefficient planes A, C (bands.hip);
-                  //   a segmentation's size plane (uint32 per pixel: a local component's pixels at its local root, the sum at the root, then the root's rank)
+                  //   a segmentation's size plane (uint32 per pixel: a local component's pixels at its local root, the sum at the root, then the root's rank);
+                  //   a split's parent plane (int32 per pixel) and, behind it, its size plane (also the components' largest D2 and the owners' keys)
 };
 static_assert(SL_CONS + 1 == slots::kSlots, "one enumerator per slot");
 inline Slot other(Slot s) { return s == SL_DST ? SL_SRC : SL_DST; }            // of the 0 / 1 pair
@@ -296,6 +301,10 @@ struct s2sr_handle {
     // s2sr_zones_kmeans_i16 with profiling on: the same, by S2SR_MZONES_* stage
     double mzones_stage_ms[S2SR_MZONES_STAGES] = {};
     int32_t mzones_stage_launches[S2SR_MZONES_STAGES] = {};
+    // s2sr_fields_split_i16 with profiling on: the same, by S2SR_FSPLIT_* stage; and the rounds its two growths took (always)
+    double fsplit_stage_ms[S2SR_FSPLIT_STAGES] = {};
+    int32_t fsplit_stage_launches[S2SR_FSPLIT_STAGES] = {};
+    int32_t fsplit_rounds[2] = {};
     s2sr::engine::TrunkTap* ttap = nullptr;     // s2sr_debug_trunk_taps' batch is running (run_net taps the trunk at its RDB boundaries); null otherwise
     s2sr::engine::CompactTap* ctap = nullptr;   // s2sr_debug_compact_taps' batch is running
 };

@@ -380,6 +380,30 @@ hipError_t launch_fields_apply(const int* d_parent, uint32_t* d_size, int H, int
 hipError_t launch_fields_labels(const int* d_parent, const uint32_t* d_size, int H, int W, uint32_t Z, uint16_t* d_labels, unsigned long long* d_fields,
                                 hipStream_t st);
 
+// Touching fields split (fields_split.hip), one launcher per step, all on whole H x W planes (H W < 2^31):
+//   edge      d_interior = d_m minus the edge pixels (edge in 1..32767, edge_r in 0..4); d_interior is another plane than d_m
+//   distance  d_g uint8 = the vertical distance to the nearest pixel outside the interior, capped at 255 (scratch); d_d2 uint16 =
+//             the squared Euclidean distance to it, capped at 255^2, 0 outside the interior.  Every pixel of both is written.
+//   cores     d_parent: the roots of the interior's components (launch_fields_local, _border, _flatten); d_dmax uint32 per pixel is
+//             scratch (cleared here; a component's largest D2 at its root); d_cores uint8 = 1 on core pixels
+//   seed      d_word uint64 per pixel = the marker's key (d_parent: the roots of the cores' components), all ones elsewhere
+//   grow      one round: a pixel of d_a that is not in d_b (null: none is) takes the least of its word and its neighbours' plus one
+//             step; *d_changed (cleared by the caller) counts the tiles that stored something; such a tile marks itself and its eight
+//             neighbours in d_dirty_out (uint8 [fsplit_tiles(H, W)], cleared by the caller), and a tile that d_dirty_in (the round
+//             before's; null: the first round) does not mark is passed over.  restart: every reached pixel to step 0
+//   remap     d_parent = the smallest linear index of the pixel's owner's pixels (-1: no owner), d_size = the pixels at that index:
+//             what launch_fields_count, _scan, _apply and _labels take
+hipError_t launch_fsplit_edge(const int16_t* d_idx, const uint8_t* d_m, uint8_t* d_interior, int H, int W, int edge, int edge_r, hipStream_t st);
+hipError_t launch_fsplit_distance(const uint8_t* d_interior, uint8_t* d_g, uint16_t* d_d2, int H, int W, hipStream_t st);
+hipError_t launch_fsplit_cores(const int* d_parent, const uint16_t* d_d2, uint32_t* d_dmax, uint8_t* d_cores, int H, int W, int core_q, int core_px,
+                               hipStream_t st);
+hipError_t launch_fsplit_seed(const int* d_parent, unsigned long long* d_word, int H, int W, hipStream_t st);
+hipError_t launch_fsplit_restart(unsigned long long* d_word, int H, int W, hipStream_t st);
+size_t fsplit_tiles(int H, int W);
+hipError_t launch_fsplit_grow(const uint8_t* d_a, const uint8_t* d_b, unsigned long long* d_word, int H, int W, int conn, uint32_t* d_changed,
+                              const uint8_t* d_dirty_in, uint8_t* d_dirty_out, hipStream_t st);
+hipError_t launch_fsplit_remap(const unsigned long long* d_word, int* d_parent, uint32_t* d_size, int H, int W, hipStream_t st);
+
 // Management zones (mzones.hip), one launcher per step.  d_feat: int16 [D][H][W] (D in 1..4), d_labels: uint16 [H][W],
 // H W < 2^31, Z in 1..65535, k in 2..8; the pixel passes take the rows [y0, y1) of the image.  The tables, Z + 1 rows each:
 //   d_cnt uint32, d_lo / d_hi int32 [D]       the members and their minimum / maximum per feature (clear, then stats band by band)

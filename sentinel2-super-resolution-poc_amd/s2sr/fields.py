@@ -7,7 +7,14 @@ A job's `zones` option takes, besides a label raster and field polygons (s2sr/zo
   {"segment": {"index": "ndvi", "min": 0.3, "max": None, "open": 1, "close": 2, "connectivity": 4, "min_area_ha": 0.5}}
 index names one of the job's indices; min / max are in index units (None: no bound on that side); open / close are the radii of the
 morphological open and close in output pixels (0..8); min_pixels may be given instead of min_area_ha, one of the two must be.
-Defaults: min 0.3, max None, open 1, close 2, connectivity 4.  What these defaults do on real scenes is unmeasured."""
+Defaults: min 0.3, max None, open 1, close 2, connectivity 4.  What these defaults do on real scenes is unmeasured.
+
+One more key cuts touching fields apart (native.Engine.fields_split_i16):
+  "split": True | {"core": 0.5, "core_px": 2, "edge": None, "edge_smooth": 1}
+core in (0, 1]: a core pixel lies at least that fraction of its blob's largest distance from the blob's outside, and at least
+core_px pixels (0..255); edge: a gradient of the index, in index units per output pixel, above which a pixel is a field boundary
+(None: no such test); edge_smooth: the radius of the box sum in front of the gradient (0..4).  True takes these defaults.  Without
+the key nothing changes, byte for byte."""
 from __future__ import annotations
 
 import json
@@ -19,7 +26,9 @@ import numpy as np
 from . import geo
 
 MAX_LABELS = 65535
-KEYS = ("index", "min", "max", "open", "close", "connectivity", "min_area_ha", "min_pixels")
+KEYS = ("index", "min", "max", "open", "close", "connectivity", "min_area_ha", "min_pixels", "split")
+SPLIT_KEYS = ("core", "core_px", "edge", "edge_smooth")
+SPLIT_DEFAULTS = {"core": 0.5, "core_px": 2, "edge": None, "edge_smooth": 1}
 DEFAULTS = {"min": 0.3, "max": None, "open": 1, "close": 2, "connectivity": 4}
 LIMIT = 32767                     # the index values a bound may name: -32768 is nodata
 
@@ -27,6 +36,30 @@ LIMIT = 32767                     # the index values a bound may name: -32768 is
 def is_segment(value) -> bool:
     """whether a job's `zones` value is the segment form"""
     return isinstance(value, dict) and "segment" in value
+
+
+def check_split(value) -> dict:
+    """the "split" value of a segment option -> its fields with the defaults filled in; ValueError: neither True nor a dict, an
+    unknown key, core outside (0, 1], core_px outside 0..255, a non-positive or non-finite edge, edge_smooth outside 0..4"""
+    if value is True:
+        return dict(SPLIT_DEFAULTS)
+    if not isinstance(value, dict):
+        raise ValueError(f"zones: segment split {value!r}: True, or a dict of {', '.join(SPLIT_KEYS)}")
+    unknown = set(value) - set(SPLIT_KEYS)
+    if unknown:
+        raise ValueError(f"zones: segment split has unknown key(s) {sorted(unknown)}; known are {', '.join(SPLIT_KEYS)}")
+    p = dict(SPLIT_DEFAULTS, **value)
+    if isinstance(p["core"], bool) or not isinstance(p["core"], (int, float)) or not math.isfinite(p["core"]) or not 0 < p["core"] <= 1:
+        raise ValueError(f"zones: segment split core {p['core']!r}: a fraction in (0, 1]")
+    if round(1000 * p["core"]) < 1:
+        raise ValueError(f"zones: segment split core {p['core']!r}: below a thousandth")
+    if isinstance(p["core_px"], bool) or not isinstance(p["core_px"], int) or not 0 <= p["core_px"] <= 255:
+        raise ValueError(f"zones: segment split core_px {p['core_px']!r}: an integer in 0..255 pixels")
+    if p["edge"] is not None and (isinstance(p["edge"], bool) or not isinstance(p["edge"], (int, float)) or not math.isfinite(p["edge"]) or p["edge"] <= 0):
+        raise ValueError(f"zones: segment split edge {p['edge']!r}: a positive number of index units per pixel, or None")
+    if isinstance(p["edge_smooth"], bool) or not isinstance(p["edge_smooth"], int) or not 0 <= p["edge_smooth"] <= 4:
+        raise ValueError(f"zones: segment split edge_smooth {p['edge_smooth']!r}: a radius in 0..4 pixels")
+    return p
 
 
 def check_option(option) -> dict:
@@ -62,6 +95,8 @@ def check_option(option) -> dict:
         raise ValueError(f"zones: segment min_area_ha {area!r}: a positive number of hectares")
     if pixels is not None and (isinstance(pixels, bool) or not isinstance(pixels, int) or pixels < 1):
         raise ValueError(f"zones: segment min_pixels {pixels!r}: an integer >= 1")
+    if "split" in p:
+        p["split"] = check_split(p["split"])
     return p
 
 
@@ -76,7 +111,8 @@ def check_index(p, index_defs) -> int:
 def resolve(option, index_defs, pixel_area_m2) -> dict:
     """A job's segment option -> the integers of the device pass: {"index" (its place in index_defs), "name", "K", "lo", "hi", "r_open",
     "r_close", "conn", "min_pixels"} with lo = round(K min), hi = round(K max), both kept inside -32767..32767, and min_pixels =
-    ceil(10000 min_area_ha / pixel_area_m2).  index_defs: s2sr.index.resolve's list.  ValueError: check_option's, an index that is
+    ceil(10000 min_area_ha / pixel_area_m2); only when the option has "split", also "split": {"core_q": round(1000 core), "core_px",
+    "edge": 0 or round(K edge) kept inside 1..32767, "edge_r"}.  index_defs: s2sr.index.resolve's list.  ValueError: check_option's, an index that is
     not among the job's, min_area_ha for a raster without a pixel size."""
     p = check_option(option)
     at = check_index(p, index_defs)
@@ -91,17 +127,26 @@ def resolve(option, index_defs, pixel_area_m2) -> dict:
         if pixel_area_m2 is None or not pixel_area_m2 > 0:
             raise ValueError("zones: segment min_area_ha needs a raster with a pixel size; pass min_pixels")
         min_pixels = max(1, math.ceil(10000.0 * float(p["min_area_ha"]) / float(pixel_area_m2)))
-    return {"index": at, "name": p["index"], "K": K, "lo": lo, "hi": hi, "r_open": p["open"], "r_close": p["close"], "conn": p["connectivity"],
-            "min_pixels": min_pixels}
+    out = {"index": at, "name": p["index"], "K": K, "lo": lo, "hi": hi, "r_open": p["open"], "r_close": p["close"], "conn": p["connectivity"],
+           "min_pixels": min_pixels}
+    if "split" in p:
+        sp = p["split"]
+        out["split"] = {"core_q": int(round(1000 * sp["core"])), "core_px": sp["core_px"],
+                        "edge": 0 if sp["edge"] is None else max(1, min(LIMIT, int(round(K * sp["edge"])))), "edge_r": sp["edge_smooth"]}
+    return out
 
 
 def segment(engine, idx, params) -> dict:
     """An int16 index raster through `engine` (native.Engine) with resolve()'s params -> {"labels" uint16 [H, W], "fields" int64
     [found + 1][6], "found", "rings": (xy, ring_start, ring_label)}.  The labels are a copy of the engine's own: they outlive its
-    next call.  ValueError: no field found, more than 65535 fields."""
+    next call.  With "split" among the params the fields are native.Engine.fields_split_i16's.  ValueError: no field found, more
+    than 65535 fields."""
+    kw = dict(r_open=params["r_open"], r_close=params["r_close"], conn=params["conn"], min_pixels=params["min_pixels"], Z=MAX_LABELS)
     with engine.chain_lock:          # the call voids what the engine kept: not between another job's door and its readers
-        labels, fields, found = engine.fields_segment_i16(idx, params["lo"], params["hi"], r_open=params["r_open"], r_close=params["r_close"],
-                                                          conn=params["conn"], min_pixels=params["min_pixels"], Z=MAX_LABELS)
+        if "split" in params:        # touching fields cut apart (DESIGN.md 7.12)
+            labels, fields, found = engine.fields_split_i16(idx, params["lo"], params["hi"], split=params["split"], **kw)
+        else:
+            labels, fields, found = engine.fields_segment_i16(idx, params["lo"], params["hi"], **kw)
         labels = np.array(labels)
     if found < 1:
         raise ValueError(f"zones: segment found no field of at least {params['min_pixels']} pixels with {params['name']} in "
@@ -208,11 +253,11 @@ def to_geojson(polys, georef, pixel_size=None, tables=None) -> dict:
 
 def metadata_block(params, found: int, fields, grid, file, geojson, pixel_size) -> dict:
     """the "zones" block of a job that segmented its fields.  params: resolve()'s; fields: int64 [found + 1][6]; pixel_size: the
-    output pixel's (x, y) in metres (or None: no hectares)."""
+    output pixel's (x, y) in metres (or None: no hectares).  "parameters" carries "split" only when the params do."""
     ha = None if pixel_size is None else abs(float(pixel_size[0]) * float(pixel_size[1])) / 10000.0
     rows = [{"label": l, "pixels": int(fields[l][0]), "area_ha": None if ha is None else int(fields[l][0]) * ha, "bbox": [int(v) for v in fields[l][2:6]]}
             for l in range(1, len(fields))]
-    return {"source": "segment", "parameters": {k: params[k] for k in ("name", "K", "lo", "hi", "r_open", "r_close", "conn", "min_pixels")},
+    return {"source": "segment", "parameters": {k: params[k] for k in ("name", "K", "lo", "hi", "r_open", "r_close", "conn", "min_pixels", "split") if k in params},
             "found": int(found), "unlabelled": int(fields[0][0]), "labels": rows, "grid": [int(grid[0]), int(grid[1])], "zone_scale": 1,
             "file": None if file is None else str(file), "geojson": None if geojson is None else str(geojson)}
 

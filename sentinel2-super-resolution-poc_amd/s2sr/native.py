@@ -174,6 +174,8 @@ _PROTOS = {
     "s2sr_fields_segment_i16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.c_int64, C.c_int32] + [C.c_void_p] * 3),
     "s2sr_labels_trace_u16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_uint64] * 2 + [C.c_void_p] * 4),
     "s2sr_debug_fields_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "s2sr_fields_split_i16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 7 + [C.c_int64, C.c_int32] + [C.c_void_p] * 6),
+    "s2sr_debug_fields_split_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "s2sr_zones_kmeans_i16": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p] + [C.c_int32] * 3 + [C.c_int64] + [C.c_int32] * 2 +
                               [C.c_void_p] * 5),
     "s2sr_debug_mzones_stage_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -261,6 +263,7 @@ _PROTOS = {
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 FIELDS_STAGES = ("mask_morphology", "local", "border", "flatten", "count", "scan", "apply", "labels")   # S2SR_FIELDS_STAGE_*
 MZONES_STAGES = ("statistics", "iterations", "assign", "smoothing", "table")                            # S2SR_MZONES_*
+FSPLIT_STAGES = ("edge", "distance", "cores", "grow_interior", "grow_edges", "remap", "numbering")      # S2SR_FSPLIT_*
 
 
 def _mapped_hip_runtimes() -> set:
@@ -1078,6 +1081,50 @@ class Engine:
         ms, n = np.zeros(len(FIELDS_STAGES), np.float64), np.zeros(len(FIELDS_STAGES), np.int32)
         self._check(self._lib.s2sr_debug_fields_stage_ms(self._h, _ptr(ms), _ptr(n)), "s2sr_debug_fields_stage_ms")
         return {name: (float(ms[k]), int(n[k])) for k, name in enumerate(FIELDS_STAGES)}
+
+    def fields_split_i16(self, idx, lo: int, hi: int, r_open: int = 0, r_close: int = 0, conn: int = 4, min_pixels: int = 1, Z: int = 65535,
+                         split=None, want=()):
+        """fields_segment_i16 with touching fields cut apart (include/s2sr.h s2sr_fields_split_i16).  split: None (the
+        bytes of fields_segment_i16) or {"core_q": 1..1000, "core_px": 0..255, "edge": 0..32767, "edge_r": 0..4} (defaults 500, 2, 0,
+        1).  Returns (labels, fields, found) and, with want=("dist2", "cores") or one of them, those planes behind them in that
+        order: uint16 [H, W] squared distances capped at 255^2, uint8 [H, W] core pixels (zeros without a split).  The call voids
+        whatever the call before it kept on the device.  No weights needed."""
+        idx = np.asarray(idx)
+        if idx.dtype != np.int16 or idx.ndim != 2:
+            raise TypeError(f"fields_split_i16 takes an int16 raster [H, W], got {idx.dtype} {idx.shape}")
+        unknown = set(want) - {"dist2", "cores"}
+        if unknown:
+            raise ValueError(f"fields_split_i16: unknown output(s) {sorted(unknown)}; known are dist2, cores")
+        idx = np.ascontiguousarray(idx)
+        H, W = idx.shape
+        Z = int(Z)
+        ok = H > 0 and W > 0 and H * W < 2 ** 31
+        labels = pinned_pool.empty((H, W), np.uint16) if ok else np.empty((1,), np.uint16)
+        fields = np.zeros((Z + 1 if 0 <= Z <= 65535 else 1, 6), np.int64)
+        found = np.zeros(1, np.uint64)
+        rec = None
+        if split is not None:
+            unknown = set(split) - {"core_q", "core_px", "edge", "edge_r"}
+            if unknown:
+                raise ValueError(f"fields_split_i16: split has unknown key(s) {sorted(unknown)}; known are core_q, core_px, edge, edge_r")
+            rec = np.array([split.get("core_q", 500), split.get("core_px", 2), split.get("edge", 0), split.get("edge_r", 1)], np.int32)
+        dist2 = np.zeros((H, W), np.uint16) if "dist2" in want else None
+        cores = np.zeros((H, W), np.uint8) if "cores" in want else None
+        self._check(self._lib.s2sr_fields_split_i16(self._h, _ptr(idx), H, W, int(lo), int(hi), int(r_open), int(r_close), int(conn), int(min_pixels), Z,
+                                                    _ptr(rec) if rec is not None else None, _ptr(labels), _ptr(fields), _ptr(found),
+                                                    _ptr(dist2) if dist2 is not None else None, _ptr(cores) if cores is not None else None),
+                    "s2sr_fields_split_i16")
+        return (labels, fields, int(found[0])) + tuple(v for v in (dist2, cores) if v is not None)
+
+    def fields_split_stage_ms(self) -> dict:
+        """What the stages of the last fields_split_i16 with a split took by HIP events, {stage: (ms, launches)} in the order of
+        FSPLIT_STAGES, and under "rounds" the launches its two growths took (include/s2sr.h s2sr_debug_fields_split_stage_ms): the
+        times are zeros unless that call ran under set_profiling(1)."""
+        ms, n, rounds = np.zeros(len(FSPLIT_STAGES), np.float64), np.zeros(len(FSPLIT_STAGES), np.int32), np.zeros(2, np.int32)
+        self._check(self._lib.s2sr_debug_fields_split_stage_ms(self._h, _ptr(ms), _ptr(n), _ptr(rounds)), "s2sr_debug_fields_split_stage_ms")
+        out = {name: (float(ms[k]), int(n[k])) for k, name in enumerate(FSPLIT_STAGES)}
+        out["rounds"] = (int(rounds[0]), int(rounds[1]))
+        return out
 
     def zones_kmeans_i16(self, feats, labels, Z: int, k: int = 3, iters: int = 32, min_per_zone: int = 10, smooth: int = 0, band_rows: int = 0) -> dict:
         """Integer k-means inside every field (include/s2sr.h s2sr_zones_kmeans_i16).  feats: int16 [D, H, W] (or
