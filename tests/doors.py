@@ -7,10 +7,15 @@ section (c) of tests/test_gpu_gridcap.py (no dependence on the number of workgro
 32767 / 1.0).  Importing this file builds the table and touches no device: inputs and models are made inside the door functions, once
 per case (tests/test_doors_cpu.py; tests/golden/doors_idents.txt lists the identifiers).
 
-The raster passes (carried band, index, zones, fields, masked warp) are rows like any other.  The four judges compare with
-diag.baseline, not with a model, so MODELS holds for each of these rows what the numpy model of its pass says, and the pass's own
-module (tests/test_gpu_bands.py, _index, _zones, _fields, _tiles_nodata) holds the baseline to it: every mode reaches the model
-through the baseline, as it does for the older doors through the parity modules.
+The raster passes (carried band, index, zones, fields, management zones, the split, masked warp) are rows like any other.  The four
+judges compare with diag.baseline, not with a model, so MODELS holds for each of these rows what the numpy model of its pass says,
+and the pass's own module (tests/test_gpu_bands.py, _index, _zones, _fields, _mzones, _fields_split, _tiles_nodata) holds the baseline
+to it: every mode reaches the model through the baseline, as it does for the older doors through the parity modules.
+
+Every raster a job hands to the zone, field, management-zone and split passes lives on the SR grid, 4 x (or 2 x) the input's width: W
+% 8 == 0 from an even input width, W % 8 == 4 (W % 4 == 2 at x2) from an odd one.  The kernels of these four passes pick their
+load and store widths by exactly that, so WIDTHS names the shapes that the pass modules add to their own, and each pass has rows at 65
+x 128 and 37 x 180 here: the red zones then watch the 16- and 8-byte stores at a ragged tile, poison the wide loads.
 
 x2plus refuses odd tile sizes (pixel_unshuffle by 2), so its net doors run the listed shapes as the trunk grid: tiles of
 2 th x 2 tw.  The 16-bit doors exist on the x4 RRDB nets only."""
@@ -23,7 +28,9 @@ import torch
 import bands_model as bm
 import display_model as dm
 import fields_model as fm
+import fields_split_model as sm
 import index_model as im
+import mzones_model as mm
 import resample_model as rm
 import warp_masked_model as wm
 import zones_model as zm
@@ -41,6 +48,9 @@ BANDED, CHUNKED = (100, 90, 16, 2), (53, 200, 16, 3)          # tests/test_gpu_u
 IMAGES = {"banded": BANDED, "chunked": CHUNKED, "short_ramps": (39, 39, 16, 3), "untiled": (28, 36, 256, 10), "one_pixel": (1, 1, 256, 10)}
 FULL, SUB = (0, 65535), (1000, 11000)
 FILL = 0x5A                      # what a caller-owned output buffer holds before the call, on both sides of a comparison
+# the widths of the SR grid: one vector group; a tile line between vector groups and a ragged bottom tile; three tile columns and a
+# ragged one of a single group; W % 8 == 4 twice (4 x 45 and 4 x 17: groups of 8 and a tail of 4); W % 4 == 2, the x2 grid of 39
+WIDTHS = [(5, 8), (65, 128), (33, 200), (37, 180), (1, 68), (39, 78)]
 
 
 class Inputs:
@@ -520,6 +530,52 @@ def _fields_model(H, W, name, **kw):
     return labels, fields, _n(found)
 
 
+MZ_KEYS = ("zone", "table", "centres", "status")
+# management zones: tag -> (H, W, features, layout, parameters).  Two cases at 65 x 129 (one raster and two, smoothing 1 and 2); 130
+# x 197 on one field with k 8 in bands of 7 rows and whole (whole: 20 tiles of 64 x 32, which a cap of 8 makes smaller; in bands of 7
+# rows no launch has more than 4); one pixel; W % 8 == 0 with D 4 and k 8, and W % 8 == 4 in bands of 5 rows
+MZ_ROWS = {"65x129-noise-grid16": (65, 129, "noise", "grid16", dict(smooth=1)),
+           "65x129-nodata_ramp-stripes-k5": (65, 129, ("nodata", "ramp"), "stripes", dict(k=5, min_per_zone=1, smooth=2)),
+           "130x197-planted_nodata-one-k8-bands7": (130, 197, ("planted", "nodata"), "one", dict(k=8, smooth=2, band_rows=7)),
+           "130x197-planted_nodata-one-k8": (130, 197, ("planted", "nodata"), "one", dict(k=8, smooth=2)),
+           "1x1-noise-one": (1, 1, "noise", "one", dict(k=2, min_per_zone=1)),
+           "65x128-d4-grid16-k8": (65, 128, ("planted", "noise", "nodata", "extremes"), "grid16", dict(k=8, min_per_zone=1, smooth=1)),
+           "37x180-noise_nodata-grid16-bands5": (37, 180, ("noise", "nodata"), "grid16", dict(smooth=2, min_per_zone=3, band_rows=5))}
+EDGE, MORPH = {"edge": 150, "edge_r": 1}, dict(r_open=1, r_close=2)          # tests/test_gpu_fields_split.py
+# the split: tag -> (H, W, raster, split, parameters).  Three cases at 65 x 129 (edge test, morphology, corridor); 130 x 197 (12
+# growth tiles and 101 per-pixel blocks: a second trip under a cap of 8); one pixel; W % 8 == 0 and W % 8 == 4
+SPLIT_ROWS = {"65x129-blobs-edge-morph": (65, 129, "blobs", EDGE, dict(conn=4, **MORPH)),
+              "65x129-parcels-edge_r0": (65, 129, "parcels", {"edge": 150, "edge_r": 0}, dict(conn=8)),
+              "65x129-snake-plain": (65, 129, "snake", {}, dict(conn=4)),
+              "130x197-blobs-edge": (130, 197, "blobs", EDGE, dict(conn=8)),
+              "1x1-ones": (1, 1, "ones", {}, {}),
+              "65x128-blobs-edge-morph": (65, 128, "blobs", EDGE, dict(conn=8, min_pixels=3, **MORPH)),
+              "37x180-blobs-edge": (37, 180, "blobs", EDGE, dict(conn=4))}
+
+
+def _mzones_tuple(r):
+    return tuple(np.array(r[k]) for k in MZ_KEYS) + (_n(r["iterations"]),)
+
+
+def _mzones(e, X, H, W, features, lay, kw):
+    feats, labels, Z = mm.inputs(H, W, features, lay)              # the labels are geometry: they stay under the saturated features
+    return _mzones_tuple(e.zones_kmeans_i16(X.like(feats), labels, Z, **kw))
+
+
+def _mzones_model(H, W, features, lay, kw):
+    return _mzones_tuple(mm.case(H, W, features, lay, **{k: v for k, v in kw.items() if k != "band_rows"}))
+
+
+def _split(e, X, H, W, name, split, kw):
+    labels, fields, found, dist2, cores = e.fields_split_i16(X.like(sm.raster(H, W, name)), fm.LO, fm.HI, split=split, want=("dist2", "cores"), **kw)
+    return labels, fields, _n(found), dist2, cores
+
+
+def _split_model(H, W, name, split, kw):
+    r = sm.case(H, W, name, split=split, **kw)
+    return r["labels"], r["fields"], _n(r["found"]), r["dist2"], r["cores"]
+
+
 def _masked_warp(e, X, then_base=False):
     """the 150 x 211 / vs = 4 case, and the base level cut from the raster it keeps: the hand-over under the modes"""
     rgb, valid, vs, plan, _ = wm.case(32633, "coarse")
@@ -547,15 +603,23 @@ def _raster_doors():
     raster_door("index_nd_u16-37x45-bands5-kept", lambda: _index_model(37, 45, 1, 65535, kept=True))(
         lambda e, X: _index(e, X, 37, 45, 1, 65535, 5, kept=True))
     # zones: the scene in bands, on 4 x 5 tiles and on one pixel, the ring of 1000 vertices, and labels without area
+    # (and at the widths of the SR grid: 16-byte stores across a tile line, 8-byte stores with a row tail of 4, scalar stores at x2)
     for H, W, kind, kw, tag in ((37, 45, "scene", dict(band_rows=5), "37x45-bands5"), (255, 257, "scene", {}, "255x257"), (1, 1, "scene", {}, "1x1"),
-                                (255, 257, "star", {}, "255x257")):
+                                (255, 257, "star", {}, "255x257"), (65, 128, "scene", {}, "65x128"), (37, 180, "scene", dict(band_rows=5), "37x180-bands5"),
+                                (39, 78, "scene", {}, "39x78")):
         raster_door(f"zones_rasterize_u16-{kind}-{tag}", lambda a=(H, W, kind): zm.case(*a)[2:])(lambda e, X, a=(H, W, kind), kw=kw: _zones(e, *a, **kw))
     raster_door("zones_rasterize_u16-scene-37x45-no_area", lambda: zm.case(37, 45)[2])(lambda e, X: _zones(e, 37, 45, "scene", want_area=False))
     # fields: one component through all 3 x 4 tiles, the morphology, one pixel, and more fields than Z
+    # (and the morphology at the widths of the SR grid: 8-byte masks and 16-byte labels, and the scalar forms at W % 8 == 4)
     for H, W, name, kw in ((130, 197, "spiral", dict(conn=4)), (65, 129, "blobs", dict(r_open=1, r_close=2, conn=8, min_pixels=3)), (1, 1, "ones", {}),
-                           (63, 65, "noise", dict(conn=8, Z=5))):
+                           (63, 65, "noise", dict(conn=8, Z=5)), (65, 128, "blobs", dict(r_open=1, r_close=2, conn=8, min_pixels=3)),
+                           (37, 180, "blobs", dict(r_open=1, r_close=1, conn=4))):
         raster_door(f"fields_segment_i16-{H}x{W}-{name}", lambda a=(H, W, name), kw=kw: _fields_model(*a, **kw))(
             lambda e, X, a=(H, W, name), kw=kw: _fields(e, X, *a, **kw))
+    for tag, row in MZ_ROWS.items():
+        raster_door(f"zones_kmeans_i16-{tag}", lambda row=row: _mzones_model(*row))(lambda e, X, row=row: _mzones(e, X, *row))
+    for tag, row in SPLIT_ROWS.items():
+        raster_door(f"fields_split_i16-{tag}", lambda row=row: _split_model(*row))(lambda e, X, row=row: _split(e, X, *row))
     raster_door("warp_bilinear_masked_u8", lambda: wm.case(32633, "coarse")[4])(lambda e, X: _masked_warp(e, X))
     raster_door("warp_bilinear_masked_u8-then-base", lambda: (wm.case(32633, "coarse")[4], None))(lambda e, X: _masked_warp(e, X, then_base=True))
 

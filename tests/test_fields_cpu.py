@@ -67,7 +67,7 @@ def test_the_morphology_of_the_model():
 @pytest.mark.parametrize("conn", [4, 8])
 def test_the_model_against_scipy(conn):
     ndi = pytest.importorskip("scipy.ndimage")
-    for (H, W) in ((37, 45), (64, 64), (65, 129)):
+    for (H, W) in ((37, 45), (64, 64), (65, 129), (65, 128), (37, 180)):
         for name in ("noise", "spiral", "checker", "rings", "blobs"):
             idx = fm.patterns(H, W)[name]
             labels, fields, found = fm.segment(idx, 4000, 32767, conn=conn)
@@ -82,6 +82,19 @@ def test_the_model_against_scipy(conn):
                     assert l == 0
             assert sorted(first.values()) == list(range(1, n + 1))
             assert fields[1:n + 1, 0].tolist() == [int((labels == l).sum()) for l in range(1, n + 1)]
+
+
+def test_the_rasters_are_real_cases_at_the_widths_of_the_sr_grid():
+    """tests/doors.py WIDTHS, which tests/test_gpu_fields.py segments: at least two fields on the rasters with the most of them, under
+    both connectivities and behind the morphology.  5 x 8 and 1 x 68 are left out: a single vector group and a single row are there
+    for the addresses, and hold one blob."""
+    import doors
+    for H, W in doors.WIDTHS:
+        if (H, W) in ((5, 8), (1, 68)):
+            continue
+        for name in ("blobs", "noise"):
+            for kw in (dict(conn=4), dict(conn=8), dict(r_open=1, r_close=2, conn=8, min_pixels=3)):
+                assert fm.case(H, W, name, **kw)[2] >= 2, (H, W, name, kw)
 
 
 # ---- the rings: round trip through the polygon model of 7.9 ---------------------------------------------------------------------------------

@@ -23,7 +23,7 @@ PATTERNS = ("spiral", "checker", "comb", "rings", "noise", "ones", "zeros", "str
 # ---- the model -----------------------------------------------------------------------------------------------------------------------------
 def test_the_distance_against_scipy():
     ndi = pytest.importorskip("scipy.ndimage")
-    for H, W in ((37, 45), (65, 129)):
+    for H, W in ((37, 45), (65, 129), (65, 128), (37, 180)):
         for name in PATTERNS:
             for kw in ({}, dict(r_open=1, r_close=2)):
                 I = fm.cleaned(fm.patterns(H, W)[name], LO, HI, **kw)
@@ -76,7 +76,7 @@ def test_the_gradient_on_hand_made_cases():
 
 @pytest.mark.parametrize("conn", [4, 8])
 def test_the_degenerate_parameters_and_none_are_the_plain_segmentation(conn):
-    for H, W in ((37, 45), (65, 129)):
+    for H, W in ((37, 45), (65, 129), (65, 128), (37, 180)):
         for name in PATTERNS:
             for kw in (dict(conn=conn), dict(conn=conn, r_open=1, r_close=2, min_pixels=3, Z=9)):
                 idx = fm.patterns(H, W)[name]
@@ -86,6 +86,19 @@ def test_the_degenerate_parameters_and_none_are_the_plain_segmentation(conn):
                     assert (got["labels"] == labels).all() and (got["fields"] == fields).all() and got["found"] == found, (H, W, name, kw, split)
                     if split is not None:
                         assert (got["cores"] == fm.cleaned(idx, LO, HI, kw.get("r_open", 0), kw.get("r_close", 0))).all()
+
+
+def test_the_rasters_are_real_cases_at_the_widths_of_the_sr_grid():
+    """tests/doors.py WIDTHS, which tests/test_gpu_fields_split.py splits: at least two fields on blobs, parcels and noise with
+    the edge test, and on the blobs behind the morphology.  5 x 8 and 1 x 68 are left out: a single vector group and a single row are there for
+    the addresses, and hold one blob."""
+    import doors
+    for H, W in doors.WIDTHS:
+        if (H, W) in ((5, 8), (1, 68)):
+            continue
+        for name in ("blobs", "parcels", "noise"):
+            assert sm.case(H, W, name, split={"edge": 150, "edge_r": 1}, conn=4)["found"] >= 2, (H, W, name)
+        assert sm.case(H, W, "blobs", split={}, conn=8, r_open=1, r_close=2)["found"] >= 2, (H, W)
 
 
 def test_the_parcels_come_out_as_planted():

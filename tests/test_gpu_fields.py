@@ -24,7 +24,8 @@ pytestmark = pytest.mark.gpu
 
 HP = native.PREC_F16_HP
 # one pixel, one row across two tile lines, one short of / one past a tile, exactly one tile, 2 x 3 and 3 x 4 tiles with ragged edges
-SHAPES = [(1, 1), (1, 130), (63, 65), (64, 64), (65, 129), (130, 197)]
+# (and the widths of the SR grid, tests/doors.py WIDTHS: at W % 8 == 0 the mask, morphology and label kernels move 8 and 16 bytes a lane)
+SHAPES = [(1, 1), (1, 130), (63, 65), (64, 64), (65, 129), (130, 197)] + doors.WIDTHS
 PATTERNS = ("spiral", "checker", "comb", "rings", "noise", "ones", "zeros", "stripes", "blobs")
 GRID_FAMILY = "display"
 
@@ -61,9 +62,10 @@ def test_byte_for_byte_against_the_model(bare, H, W):
         assert found["noise", 4] > found["noise", 8] > 10 and found["rings", 4] > 5
 
 
-@pytest.mark.parametrize("H,W", [(65, 129), (130, 197)])
+@pytest.mark.parametrize("H,W", [(65, 129), (130, 197), (65, 128)])
 def test_every_parameter(bare, H, W):
-    """min_pixels of 1 and above, a Z below found (found still counts them), radii 0, 1, 2 and 8 on fields that touch every edge"""
+    """min_pixels of 1 and above, a Z below found (found still counts them), radii 0, 1, 2 and 8 on fields that touch every edge
+    (65 x 128: the same in 8-byte masks and 16-byte labels, a tile line between two vector groups)"""
     for name in ("noise", "blobs"):
         for conn in (4, 8):
             for min_pixels in (2, 7, 400):
@@ -82,7 +84,7 @@ def test_every_parameter(bare, H, W):
 
 
 def test_radii_on_the_small_shapes(bare):
-    for H, W in ((1, 1), (1, 130), (63, 65), (64, 64)):
+    for H, W in ((1, 1), (1, 130), (63, 65), (64, 64), (5, 8), (65, 128), (1, 68)):
         for r_open, r_close in ((1, 1), (2, 8), (8, 2)):
             for name in ("blobs", "ones", "stripes"):
                 check(bare, H, W, name, r_open=r_open, r_close=r_close, conn=8)

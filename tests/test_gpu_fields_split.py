@@ -3,16 +3,18 @@ found, dist2 and cores byte for byte against tests/fields_split_model.py on shap
 that break a union-find and on the rasters made for the split (dumbbell, parcels, snake, edge-only), under both connectivities, with
 and without morphology and edge test; a 300 x 600 rectangle whose distance reaches the cap; every parameter at its limits; NULL and
 the degenerate parameters against s2sr_fields_segment_i16 on the device; the independence of the number of workgroups (caps 1 and
-3); red zones and poison with a dirty predecessor; every refusal, the void rule, the stage hook, and the job that splits its own NDVI.
+3); every refusal, the void rule, the stage hook, and the job that splits its own NDVI.  The shapes include the widths of the SR grid
+(doors.WIDTHS: at W % 8 == 0 the mask, morphology and label kernels the entry shares with the fields pass move 8 and 16 bytes a lane).
+The entry under red zones, poison, stalls and cap 8: its rows of tests/doors.py, whose baselines this module holds to the model.
 
-The entry is not in the door table (tests/doors.py) yet; its capped launches are counted in the grid-cap family "display"."""
-import contextlib
+The pass's capped launches are counted in the grid-cap family "display"."""
 import json
 
 import numpy as np
 import pytest
 
 import diag
+import doors
 import fields_model as fm
 import fields_split_model as sm
 import gpu_engines
@@ -23,7 +25,7 @@ from s2sr import native
 pytestmark = pytest.mark.gpu
 
 HP = native.PREC_F16_HP
-SHAPES = [(1, 1), (1, 130), (63, 65), (64, 64), (65, 129), (130, 197)]
+SHAPES = [(1, 1), (1, 130), (63, 65), (64, 64), (65, 129), (130, 197)] + doors.WIDTHS
 PATTERNS = ("spiral", "checker", "comb", "rings", "noise", "ones", "zeros", "stripes", "blobs") + sm.NEW
 GRID_FAMILY = "display"
 PLAIN = {}                                                        # the defaults: core 0.5, 2 pixels, no edge test
@@ -97,8 +99,9 @@ def test_the_distance_reaches_its_cap_through_the_halo(bare):
     assert want["dist2"].max() == 255 * 255 and want["dist2"][270, 290] == 250 * 250 + 10 * 10 and want["dist2"][299, 300] == 255 * 255 and want["dist2"][150, 20] == 1
 
 
-@pytest.mark.parametrize("H,W", [(65, 129)])
+@pytest.mark.parametrize("H,W", [(65, 129), (65, 128)])
 def test_every_parameter_at_its_limits(bare, H, W):
+    """(65 x 128: the same on the vector path of the kernels shared with the fields pass)"""
     for name in ("blobs", "parcels", "noise"):
         for conn in (4, 8):
             for split in ({"core_q": 1}, {"core_q": 1000}, {"core_px": 0}, {"core_px": 255}, {"core_q": 1000, "core_px": 255, "edge": 1, "edge_r": 4},
@@ -142,34 +145,11 @@ def test_under_capped_grids(bare, cap):
     assert native.grid_cap_stats()[GRID_FAMILY] == (0, 0)                                  # off means off
 
 
-@contextlib.contextmanager
-def zones_and_poison(pattern):
-    zone, before = native.redzone_bytes(), native.poison_pattern()
-    native.redzone(diag.Z), native.poison(pattern)
-    try:
-        yield
-    finally:
-        native.redzone(zone), native.poison(before)
-
-
-@pytest.mark.parametrize("pattern", [1, 2])
-def test_under_red_zones_and_poison_with_a_dirty_predecessor(pattern):
-    """an engine allocated under red zones and poison: fresh, behind poison_scratch, and behind the same call on a raster that
-    fills every plane, the bytes are the model's and no zone is damaged"""
-    H, W = 65, 129
-    cases = (("blobs", EDGE, dict(conn=4, **MORPH)), ("parcels", {"edge": 150, "edge_r": 0}, dict(conn=8)), ("snake", PLAIN, dict(conn=4)))
-    with zones_and_poison(pattern):
-        e = native.Engine(num_block=1, precision=HP)
-        try:
-            for name, split, kw in cases:
-                check(e, H, W, name, split, **kw)
-                e.poison_scratch()
-                check(e, H, W, name, split, **kw)
-                e.fields_split_i16(np.full((H, W), 32767, np.int16), LO, HI, split=EDGE, **kw)           # the dirty predecessor
-                check(e, H, W, name, split, **kw)
-            diag.clean(e, least=3)
-        finally:
-            e.close()
+@pytest.mark.parametrize("ident", doors.owned("fields_split_i16"))
+def test_the_door_table_s_baseline_is_the_model(ident):
+    """tests/doors.py's rows of this pass: the red-zone, poison, stall and grid-cap matrices hold every mode to diag.baseline, and
+    this holds the baseline to the model, sample for sample"""
+    same(diag.baseline(ident), doors.MODELS[ident](), ident)
 
 
 def test_stage_times_by_events_and_the_rounds(bare):

@@ -279,13 +279,16 @@ def test_the_door_table_ran_capped(capped):
     Of the raster passes: the carried band whole (9 tiles in one launch; in bands of 2 S + 1 guide rows no launch has more than 6,
     which a cap of 8 leaves alone), the index pass's rendering, the zones and the fields pass at 255 x 257 and 130 x 197 (32 blocks,
     20 and 12 tiles; index_nd_u16 itself takes 1024 lanes of 8 pixels a workgroup, so its 65535 pixels are 8 workgroups' worth and
-    cap 8 changes nothing there: caps 1 and 3 judge it in tests/test_gpu_index.py), and the masked warp."""
+    cap 8 changes nothing there: caps 1 and 3 judge it in tests/test_gpu_index.py), management zones and the split at 130 x 197
+    (20 tiles of 64 x 32 whole -- in bands of 7 rows no launch has more than 4 --, and 12 growth tiles and 101 per-pixel blocks),
+    and the masked warp."""
     for ident, fams in (("x4_hp-ragged_2x37x53-forward_batch_u8", ("conv", "trunk_f16", "pack")), ("x4_fp8-ragged_2x37x53-forward_batch_u8", ("trunk_f8",)),
                         ("x4_hp-banded-consistent_u8-smooth", ("consistency",)), ("x4_hp-banded-masked_u8", ("nodata",)),
                         ("postprocess_batch_u8_dev-67x101-wow", ("postprocess",)), ("display_apply_u16-255x257-bands0", ("display",)),
                         ("tiles_base_u8", ("tiles",)), ("tiles_resample_u8-lanczos", ("resample",)), ("carry_band_u16-x4-whole", ("bands",)),
                         ("index_render_i16-255x257", ("display",)), ("zones_rasterize_u16-scene-255x257", ("display",)),
-                        ("fields_segment_i16-130x197-spiral", ("display",)), ("warp_bilinear_masked_u8", ("tiles",))):
+                        ("fields_segment_i16-130x197-spiral", ("display",)), ("zones_kmeans_i16-130x197-planted_nodata-one-k8", ("display",)),
+                        ("fields_split_i16-130x197-blobs-edge", ("display",)), ("warp_bilinear_masked_u8", ("tiles",))):
         name, fn = DOORS[ident]
         e = diag.new_engine(name)                               # a fresh engine: no graph from an earlier test stands in for the launches
         try:

@@ -1,17 +1,19 @@
 """Management zones on the GPU (include/s2sr.h: s2sr_zones_kmeans_i16; csrc/mzones.hip): zone, table, centres,
 status and iterations byte for byte against tests/mzones_model.py on shapes that cross the 64 x 32 tile lines, for every pair of
-feature pattern and label layout; every parameter; the independence of the row bands and of the number of workgroups (caps 1 and 3,
-with the launch and trip arithmetic); the entry under red zones and poison with a dirty predecessor; every refusal, the void rule,
-the round trip through the segmentation, the ring tracer and the polygon rasteriser, and one whole job against the model.
+feature pattern and label layout, and at the widths of the SR grid (doors.WIDTHS: W % 8 == 0 takes the 16-byte loads of labels and
+features and the 8-byte loads and stores of zones, every other width the scalar forms); every parameter; the independence of the row
+bands and of the number of workgroups (caps 1 and 3, with the launch and trip arithmetic); every refusal, the void rule, the round
+trip through the segmentation, the ring tracer and the polygon rasteriser, and one whole job against the model.  The entry under red
+zones, poison, stalls and cap 8: its rows of tests/doors.py, whose baselines this module holds to the model.
 
 The pass's capped launches are counted in the grid-cap family "display", as the index, zones and fields passes' are."""
-import contextlib
 import json
 
 import numpy as np
 import pytest
 
 import diag
+import doors
 import fields_model as fm
 import gpu_engines
 import mzones_model as mm
@@ -22,7 +24,8 @@ pytestmark = pytest.mark.gpu
 
 HP = native.PREC_F16_HP
 # one pixel, one row across two tile lines, one short of / one past a tile, exactly one tile column, 3 x 3 and 5 x 4 tiles with ragged edges
-SHAPES = [(1, 1), (1, 130), (63, 65), (64, 64), (65, 129), (130, 197)]
+# (and the widths of the SR grid: tests/doors.py WIDTHS)
+SHAPES = [(1, 1), (1, 130), (63, 65), (64, 64), (65, 129), (130, 197)] + doors.WIDTHS
 GRID_FAMILY = "display"
 KEYS = ("zone", "table", "centres", "status")
 
@@ -60,8 +63,9 @@ def test_byte_for_byte_against_the_model(bare, H, W):
     assert zoned >= (1 if H * W >= 6 else 0)
 
 
-@pytest.mark.parametrize("H,W", [(65, 129), (130, 197)])
+@pytest.mark.parametrize("H,W", [(65, 129), (130, 197), (65, 128)])
 def test_every_parameter(bare, H, W):
+    """(65 x 128: every parameter on the vector path -- k 8, D 4, smooth 4 and Z below the largest label among them)"""
     for k in (2, 3, 8):
         for lay in ("grid16", "stripes", "one"):
             check(bare, H, W, "noise", lay, k=k, smooth=1)
@@ -88,68 +92,47 @@ def test_every_parameter(bare, H, W):
 
 
 def test_the_bytes_do_not_depend_on_the_row_bands(bare):
-    for H, W in ((65, 129), (130, 197)):
+    """(65 x 128: every band starts on a multiple of 8 bytes of every plane and is read and written in vectors; 37 x 180: no vectors)"""
+    for H, W in ((65, 129), (130, 197), (65, 128), (37, 180)):
         for band_rows in (0, 1, 7):
             check(bare, H, W, ("noise", "nodata"), "grid16", band_rows=band_rows, smooth=2, min_per_zone=3)
             check(bare, H, W, "ramp", "stripes", band_rows=band_rows, smooth=1, k=4)
 
 
-def launches_and_trips(cap, Z, k, iterations, smooth):
-    """130 x 197: 5 x 4 tiles of 64 x 32 for the passes with sums, 13 blocks of 256 groups of 8 pixels for the final assignment and
-    for a pass of the mode filter, and the tables' blocks of 256 fields or cells; a launch is counted where the cap made its grid
-    smaller"""
+def launches_and_trips(H, W, cap, Z, k, iterations, smooth):
+    """Tiles of 64 x 32 for the passes with sums (130 x 197: 5 x 4), blocks of 256 groups of 8 pixels for the final assignment and for
+    a pass of the mode filter (130 x 197: 13), and the tables' blocks of 256 fields or cells; a launch is counted where the cap made
+    its grid smaller"""
     blocks = lambda n: -(-n // 256)
-    cells = blocks((Z + 1) * k)
-    grids = [blocks(Z + 1), 20, cells] + [20, cells] * iterations + [cells, 13] + [13] * smooth + [20]
+    cells, tiles, groups = blocks((Z + 1) * k), -(-H // 32) * -(-W // 64), blocks(H * -(-W // 8))
+    grids = [blocks(Z + 1), tiles, cells] + [tiles, cells] * iterations + [cells, groups] + [groups] * smooth + [tiles]
     counted = [g for g in grids if g > cap]
     return len(counted), max(-(-g // cap) for g in counted)
 
 
 @pytest.mark.parametrize("cap", [1, 3])
 def test_under_capped_grids(bare, cap):
-    """the same bytes with every workgroup on several trips"""
-    H, W = 130, 197
-    for features, lay, kw in (("noise", "grid16", dict(smooth=1)), (("planted", "nodata"), "one", dict(k=8, smooth=2)),
-                              ("ramp", "stripes", dict(min_per_zone=1))):
-        with diag.under(cap):
-            want = check(bare, H, W, features, lay, **kw)
-            launches, trips = native.grid_cap_stats()[GRID_FAMILY]
-        Z = mm.layout(H, W, lay)[1]
-        assert (launches, trips) == launches_and_trips(cap, Z, kw.get("k", 3), want["iterations"], kw.get("smooth", 0)), (features, lay)
+    """the same bytes with every workgroup on several trips: 130 x 197, and 65 x 128 and 37 x 180 (6 tiles and 5 and 4 blocks of
+    groups: two trips at the least under either cap, on the vector path and beside it)"""
+    for H, W in ((130, 197), (65, 128), (37, 180)):
+        for features, lay, kw in (("noise", "grid16", dict(smooth=1)), (("planted", "nodata"), "one", dict(k=8, smooth=2)),
+                                  ("ramp", "stripes", dict(min_per_zone=1))):
+            with diag.under(cap):
+                want = check(bare, H, W, features, lay, **kw)
+                launches, trips = native.grid_cap_stats()[GRID_FAMILY]
+            Z = mm.layout(H, W, lay)[1]
+            arithmetic = launches_and_trips(H, W, cap, Z, kw.get("k", 3), want["iterations"], kw.get("smooth", 0))
+            assert (launches, trips) == arithmetic and trips >= 2, (H, W, features, lay)
     native.grid_cap_stats(reset=True)
-    check(bare, H, W, "noise", "grid16", smooth=1)
+    check(bare, 130, 197, "noise", "grid16", smooth=1)
     assert native.grid_cap_stats()[GRID_FAMILY] == (0, 0)                                  # off means off
 
 
-@contextlib.contextmanager
-def zones_and_poison(pattern):
-    zone, before = native.redzone_bytes(), native.poison_pattern()
-    native.redzone(diag.Z), native.poison(pattern)
-    try:
-        yield
-    finally:
-        native.redzone(zone), native.poison(before)
-
-
-@pytest.mark.parametrize("pattern", [1, 2])
-def test_under_red_zones_and_poison_with_a_dirty_predecessor(pattern):
-    """an engine allocated under red zones and poison: fresh, behind poison_scratch, and behind the same call on saturated inputs,
-    the bytes are the model's and no zone is damaged"""
-    H, W = 65, 129
-    cases = (("noise", "grid16", dict(smooth=1)), (("nodata", "ramp"), "stripes", dict(k=5, min_per_zone=1, smooth=2)))
-    with zones_and_poison(pattern):
-        e = native.Engine(num_block=1, precision=HP)
-        try:
-            for features, lay, kw in cases:
-                check(e, H, W, features, lay, **kw)
-                e.poison_scratch()
-                check(e, H, W, features, lay, **kw)
-                feats, labels, Z = mm.inputs(H, W, features, lay)
-                e.zones_kmeans_i16(np.full_like(feats, 32767), np.full_like(labels, Z), Z, **kw)          # the dirty predecessor
-                check(e, H, W, features, lay, **kw)
-            diag.clean(e, least=3)
-        finally:
-            e.close()
+@pytest.mark.parametrize("ident", doors.owned("zones_kmeans_i16"))
+def test_the_door_table_s_baseline_is_the_model(ident):
+    """tests/doors.py's rows of this pass: the red-zone, poison, stall and grid-cap matrices hold every mode to diag.baseline, and
+    this holds the baseline to the model, sample for sample"""
+    same(diag.baseline(ident), doors.MODELS[ident](), ident)
 
 
 def test_stage_times_by_events(bare):

@@ -73,6 +73,30 @@ its index and offset tables: each is uploaded in full, on the stream of the kern
     writes its whole destination from a whole source; the local pass writes the parent and the size of EVERY pixel before the border
     and flatten passes follow one; the count pass writes every chunk's sum before the scan reads them, and the scan writes found; the
     fields table is memset before the apply pass writes a row.
+  engine_mzones.hip mzones_impl SRC (the D feature planes), DST (the labels), MID and CHUNK (the two zone planes), TABLES (cnt, lo, hi,
+    status, zone_of, centres, ranked, changed, and acc: the iterations' sums, then the table).  Index-like: the labels (a label picks
+    the row of every table; one above Z counts as 0 in every kernel that reads it), status (says whether a field's centres are
+    fetched), zone_of (the cluster's byte in the raster, which the table pass reads back as a cluster number after checking it
+    against 1..k) and the centres (compared, never followed).  Labels and features go up band by band, each band ahead of the
+    statistics launch that reads it, and every later pass runs behind the last band.  cnt, lo and hi are written whole by the clear
+    kernel; the start kernel writes status for EVERY row (row 0 as absent) and all k D centres of every row before an accumulate or
+    update launch reads one; changed is memset in front of every iteration, acc once in front of the first (the update kernel puts
+    back the zeros it took) and again in front of the table pass; the rank kernel writes zone_of and ranked for every (row, cluster)
+    before the assignment reads zone_of; the assignment writes every group of its plane, a mode pass its whole destination from a
+    whole source, and the table pass reads the plane the last of them wrote.
+  engine_fields_split.hip split_impl SRC (the index raster), DST (the distance plane, later the labels), MID and CHUNK (the mask planes
+    and the interior), VALID (the vertical distances, later the cores), PP (the growth words), CONS (the parents; behind them one
+    plane that holds sizes, then the components' largest distances, then the keys, then sizes again), TABLES (the chunk sums, found,
+    the changed counter, two planes of tile marks, the fields table).  Index-like: the parents (followed as pointers, and rows of the
+    largest distances), the growth words (the low half is the owner: fsplit_parent_kernel reads key[] there), the key plane (what
+    becomes the parent), the tile marks (which tiles a round visits), the ranks and chunk sums as in fields_impl.  The mask, morphology,
+    local, border, flatten, count, scan, apply and label launches are fields_impl's, in its order.  The edge kernel writes every pixel
+    of the interior, the column pass every pixel of the vertical distances and the row pass every pixel of the distance plane before
+    the cores read it; the plane behind the parents is memset in front of the maxima (0), the keys (all ones) and the sizes (0); the
+    core kernel writes every pixel; the seed kernel writes EVERY word (unreached: all ones) behind the second components pass, and
+    an owner is a root that pass wrote; every owner's key is written by the key kernel before the parent kernel reads it; a round
+    memsets the marks it writes and reads the plane the round before wrote, the first round of either growth reads none; changed is
+    memset per round; the fields table is memset before the first kernel.
   engine_debug.hip s2sr_debug_mfma_ceiling MID, TABLES and s2sr_debug_rdb_persistent MID, TABLES, CHUNK: measuring prototypes, not doors; their
     buffers hold operands whose values do not matter and flags they memset themselves; no index is read from them.
 """

@@ -23,7 +23,9 @@ pytestmark = pytest.mark.gpu
 
 HP = native.PREC_F16_HP
 # the ragged shape, one pixel, a sliver, exactly one tile, one row and one column more than whole tiles, and 4 x 5 tiles with ragged edges
-SHAPES = [(37, 45), (1, 1), (3, 70), (64, 64), (65, 129), (255, 257)]
+# (and the widths of the SR grid, tests/doors.py WIDTHS: 16-byte stores at W % 8 == 0, 8-byte stores with a row tail of 4 at W % 8 == 4;
+# 3 x 68 beside 1 x 68, whose single row changes its label between pairs of pixels only: exchanged halves of a store leave it as it is)
+SHAPES = [(37, 45), (1, 1), (3, 70), (64, 64), (65, 129), (255, 257)] + doors.WIDTHS + [(3, 68)]
 GRID_FAMILY = "display"
 
 
@@ -64,7 +66,7 @@ def test_many_features_in_one_tile_and_many_edges_in_one_ring(bare):
     assert 150 < int((case(65, 129, "squares")[2] > 0).sum()) < 300                       # some squares repeat a pixel
 
 
-@pytest.mark.parametrize("H,W", [(37, 45), (65, 129)])
+@pytest.mark.parametrize("H,W", [(37, 45), (65, 129), (65, 128), (37, 180), (39, 78)])
 def test_band_rows_do_not_change_a_byte(bare, H, W):
     for rows in (0, 1, 3, H - 1):
         got, got_area, labels, area = run(bare, H, W, band_rows=rows)

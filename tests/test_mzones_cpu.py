@@ -51,6 +51,16 @@ def test_the_model_against_the_reference_s_clustering(mix):
         assert (rank[got] + 1 == ours).all() and (ours == cls.ravel() + 1).all(), (mix, n)
 
 
+def test_the_cases_are_real_at_the_widths_of_the_sr_grid():
+    """tests/doors.py WIDTHS, which tests/test_gpu_mzones.py zones: at every shape a zoned field (status 2) and more than one zone id
+    in the raster, for one raster and for two, on the grid of fields and on the layout that changes its label inside every group"""
+    import doors
+    for H, W in doors.WIDTHS:
+        for features, lay in (("noise", "grid16"), (("noise", "ramp"), "stripes"), ("planted", "one")):
+            r = mm.case(H, W, features, lay, min_per_zone=2, smooth=1)
+            assert (r["status"] == 2).any() and len(np.unique(r["zone"][r["zone"] > 0])) > 1, (H, W, features, lay)
+
+
 def test_a_constant_field_ends_in_zone_one():
     r = mm.kmeans(np.full((6, 7), 321, np.int16), np.ones((6, 7), np.uint16), 1, k=4, min_per_zone=1, smooth=2)
     assert (r["zone"] == 1).all() and r["iterations"] == 1 and r["centres"][1].tolist() == [[321]] * 4

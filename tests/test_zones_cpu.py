@@ -19,7 +19,7 @@ from s2sr import zones as xz
 
 REPO = Path(__file__).resolve().parent.parent
 HEADER = (REPO / "include" / "s2sr.h").read_text()
-SHAPES = [(37, 45), (1, 1), (3, 70), (64, 64), (65, 129), (255, 257)]
+SHAPES = [(37, 45), (1, 1), (3, 70), (64, 64), (65, 129), (255, 257), (65, 128), (37, 180)]
 
 
 # ---- the model -----------------------------------------------------------------------------------------------------------------------------
@@ -56,6 +56,20 @@ def test_the_row_form_is_the_pixel_form(H, W):
         assert np.array_equal(zm.inside_rows(rings, H, W), zm.inside_pixels(rings, H, W))
     a, b = zm.rasterize(feats, Z, H, W), zm.rasterize(feats, Z, H, W, inside=zm.inside_rows)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and int(a[1].sum()) == H * W
+
+
+def test_the_scene_is_a_real_case_at_the_widths_of_the_sr_grid():
+    """tests/doors.py WIDTHS, which tests/test_gpu_zones.py rasterises: at least two labels at every shape, and where W % 8 == 4 a
+    row whose last group of 4 pixels -- the 8-byte store of the row tail -- holds a label; with more than one row, a tail whose two
+    pairs differ and a full group of 8 whose first two pairs differ (every border in the single row of 1 x 68 falls between pairs)"""
+    import doors
+    for H, W in doors.WIDTHS + [(3, 68)]:                          # (3 x 68: what the GPU module runs beside 1 x 68 for that reason)
+        labels = zm.case(H, W)[2]
+        assert len(np.unique(labels[labels > 0])) >= 2, (H, W)
+        if W % 8 == 4:
+            tail = labels[:, W - 4:]
+            full = labels[:, :W - 4].reshape(H, -1, 8)
+            assert tail.any() and (H == 1 or ((tail[:, :2] != tail[:, 2:]).any() and (full[..., :2] != full[..., 2:4]).any())), (H, W)
 
 
 def test_windings_holes_and_bow_ties():
