@@ -582,6 +582,13 @@ hipError_t copy_blocking(s2sr_handle* h, void* dst, const void* src, size_t byte
     hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, h->stream);
     return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
 }
+hipError_t copy_rows(s2sr_handle*, void* dst, const void* src, size_t H, size_t row_bytes, size_t rows, hipMemcpyKind kind, hipStream_t st) {
+    for (const RowBand b : row_bands(H, rows)) {
+        const hipError_t e = hipMemcpyAsync((char*)dst + b.y0 * row_bytes, (const char*)src + b.y0 * row_bytes, b.rows() * row_bytes, kind, st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 hipError_t fill_blocking(s2sr_handle* h, void* dst, int value, size_t bytes) {
     hipError_t e = hipMemsetAsync(dst, value, bytes, h->stream);
     return e != hipSuccess ? e : hipStreamSynchronize(h->stream);

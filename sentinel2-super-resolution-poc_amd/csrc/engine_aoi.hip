@@ -929,10 +929,10 @@ static int consistency_impl(s2sr_handle* h, const void* sr, const void* img, int
     if ((rc = cons_begin(h, st, cr))) return rc;
     uint8_t* d_img = scratch<uint8_t>(h, SL_DST);
     int left = 0;                                                                       // rows that have left
-    for (size_t y0 = 0; y0 < (size_t)OH; y0 += rows) {
-        const int y1 = (int)(y0 + rows < (size_t)OH ? y0 + rows : OH);
-        HIPCHK(h, hipMemcpyAsync(d_img + y0 * row_b, (const uint8_t*)sr + y0 * row_b, (y1 - y0) * row_b, hipMemcpyHostToDevice, st));
-        const int oe = cons_out_end(mode, S, H, y1, y1 == OH);
+    for (const RowBand b : row_bands(OH, rows)) {
+        const int y1 = (int)b.y1;
+        HIPCHK(h, hipMemcpyAsync(d_img + b.y0 * row_b, (const uint8_t*)sr + b.y0 * row_b, b.rows() * row_b, hipMemcpyHostToDevice, st));
+        const int oe = cons_out_end(mode, S, H, y1, b.last);
         if ((rc = cons_advance(h, st, cr, y1, oe))) return rc;
         if (oe > left) HIPCHK(h, hipMemcpyAsync((uint8_t*)out + (size_t)left * row_b, d_img + (size_t)left * row_b, (size_t)(oe - left) * row_b, hipMemcpyDeviceToHost, st));
         if (oe > left) left = oe;

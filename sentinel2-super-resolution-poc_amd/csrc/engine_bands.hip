@@ -61,17 +61,16 @@ int carry_band_impl(s2sr_handle* h, const uint16_t* sr, const uint16_t* band, in
     if (valid) HIPCHK(h, hipMemcpyAsync(d_valid, valid, px, hipMemcpyHostToDevice, st));
     const size_t rows = band_of(band_rows, OH, grow_b, (size_t)32 << 20);              // the library's choice: ~32 MB of guide
     int c_done = 0, a_done = 0;                               // input rows whose coefficients are there; block rows that have left
-    for (size_t y0 = 0; y0 < (size_t)OH; y0 += rows) {
-        const int y1 = (int)(y0 + rows < (size_t)OH ? y0 + rows : OH);
-        const bool last = y1 == OH;
-        if (sr) HIPCHK(h, hipMemcpyAsync((char*)d_q + y0 * grow_b, (const char*)sr + y0 * grow_b, (y1 - y0) * grow_b, hipMemcpyHostToDevice, st));
-        const int ce = coeffs_end(S, H, r, y1, last);
+    for (const RowBand gb : row_bands(OH, rows)) {
+        const int y1 = (int)gb.y1;
+        if (sr) HIPCHK(h, hipMemcpyAsync((char*)d_q + gb.y0 * grow_b, (const char*)sr + gb.y0 * grow_b, gb.rows() * grow_b, hipMemcpyHostToDevice, st));
+        const int ce = coeffs_end(S, H, r, y1, gb.last);
         if (ce > c_done) {
             Scope sc(h, st, F_BANDS, 0.0, (double)(ce - c_done) * W * (S * S * 6.0 + 2.0 + 12.0));
             HIPCHK(h, launch_band_coeffs(d_q, d_band, d_valid, d_A, d_C, H, W, S, c_done, ce, lo, hi, wt, r, (long long)eps, st));
             c_done = ce;
         }
-        const int ae = apply_end(H, c_done, last);
+        const int ae = apply_end(H, c_done, gb.last);
         if (ae > a_done) {
             {
                 Scope sc(h, st, F_BANDS, 0.0, (double)(ae - a_done) * W * (S * S * 8.0 + 2.0 + 12.0));

@@ -10,15 +10,11 @@
 using namespace s2sr;
 using namespace s2sr::engine;
 
-namespace {
+// ---- the stages shared with the split (engine_internal.h).  A Scope's bytes: what the launch must move, not what its atomics and gathers add.
+namespace s2sr::engine {
 
-constexpr size_t kBandBytes = (size_t)64 << 20;                  // the rasters come and go in row bands of about this size
-
-int fields_impl(s2sr_handle* h, const int16_t* idx, int H, int W, int lo, int hi, int r_open, int r_close, int conn, int64_t min_pixels, int Z,
-                uint16_t* labels, int64_t* fields, uint64_t* found) {
-    if (!h) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    const char* what = "s2sr_fields_segment_i16: ";
+int fields_check_args(s2sr_handle* h, const char* what, const void* idx, const void* labels, int H, int W, int lo, int hi, int r_open, int r_close,
+                      int conn, int64_t min_pixels, int Z) {
     if (!idx || !labels) return fail(h, S2SR_E_INVALID, std::string(what) + "idx and labels are required");
     if (H <= 0 || W <= 0 || (long long)H * W > 0x7fffffffLL) return fail(h, S2SR_E_INVALID, std::string(what) + "H and W must be positive and H W < 2^31");
     if (lo < -32767 || hi > 32767 || lo > hi) return fail(h, S2SR_E_INVALID, std::string(what) + "lo <= hi, both in -32767..32767");
@@ -26,15 +22,107 @@ int fields_impl(s2sr_handle* h, const int16_t* idx, int H, int W, int lo, int hi
     if (conn != 4 && conn != 8) return fail(h, S2SR_E_INVALID, std::string(what) + "conn must be 4 or 8");
     if (min_pixels < 1) return fail(h, S2SR_E_INVALID, std::string(what) + "min_pixels must be >= 1");
     if (Z < 1 || Z > 65535) return fail(h, S2SR_E_INVALID, std::string(what) + "Z must be in 1..65535");
+    return S2SR_OK;
+}
+
+FieldsPlan fields_plan(int H, int W, int64_t min_pixels, int Z, size_t between) {
+    FieldsPlan p;
+    p.minpx = min_pixels > 0x80000000LL ? 0x80000000u : (uint32_t)min_pixels;       // beyond H W nothing is a field
+    p.o_found = up256(fields_chunks(H, W) * 4), p.o_between = p.o_found + 256, p.o_fields = p.o_between + between;
+    p.fields_b = ((size_t)Z + 1) * 6 * 8, p.bytes = p.o_fields + up256(p.fields_b);
+    return p;
+}
+
+int fields_mask(s2sr_handle* h, hipStream_t st, const int16_t* d_idx, uint8_t* const d_m[2], int H, int W, int lo, int hi, int r_open, int r_close,
+                int* cur) {
+    const double px = (double)H * W;
+    int c = 0;                                                   // the plane that holds the mask so far
+    {
+        Scope sc(h, st, F_INDEX, 0.0, px * 3);                   // the index in, a plane out
+        HIPCHK(h, launch_fields_mask(d_idx, H, W, lo, hi, 0, d_m[c], st));
+    }
+    // open = dilate(erode), close = erode(dilate): each a row pass and a column pass
+    const int steps[4][2] = {{r_open, 1}, {r_open, 0}, {r_close, 0}, {r_close, 1}};                // radius, erode
+    for (const auto& s : steps) {
+        if (!s[0]) continue;
+        for (int column = 0; column < 2; ++column) {
+            Scope sc(h, st, F_INDEX, 0.0, px * 2);               // a plane in, a plane out (a column pass reads its rows from cache)
+            HIPCHK(h, launch_fields_morph(d_m[c], d_m[c ^ 1], H, W, s[0], s[1], column, st));
+            c ^= 1;
+        }
+    }
+    if (r_open || r_close) {                                     // a close may have bridged nodata
+        Scope sc(h, st, F_INDEX, 0.0, px * 4);                   // the index and the plane in, the plane out
+        HIPCHK(h, launch_fields_mask(d_idx, H, W, -32767, 32767, 1, d_m[c], st));
+    }
+    *cur = c;
+    return S2SR_OK;
+}
+
+int fields_components(s2sr_handle* h, hipStream_t st, const uint8_t* plane, int* d_parent, uint32_t* d_size, int H, int W, int conn, StageMarks* book) {
+    const double px = (double)H * W;
+    {
+        Scope sc(h, st, F_INDEX, 0.0, px * 9);                   // a plane in, parents and sizes out
+        HIPCHK(h, launch_fields_local(plane, d_parent, d_size, H, W, conn, st));
+    }
+    if (book) book->next();
+    {
+        const double lines = (double)((H + 63) / 64 - 1) * W + (double)((W + 63) / 64 - 1) * H;
+        Scope sc(h, st, F_INDEX, 0.0, lines * 8);                // a border pixel's parent and its neighbour's; the walks come on top
+        HIPCHK(h, launch_fields_border(d_parent, H, W, conn, st));
+    }
+    if (book) book->next();
+    {
+        Scope sc(h, st, F_INDEX, 0.0, px * 12);                  // parents in and out, sizes in
+        HIPCHK(h, launch_fields_flatten(d_parent, d_size, H, W, st));
+    }
+    if (book) book->next();
+    return S2SR_OK;
+}
+
+int fields_numbering(s2sr_handle* h, hipStream_t st, int* d_parent, uint32_t* d_size, int H, int W, uint32_t minpx, int Z, uint32_t* d_sums,
+                     unsigned long long* d_found, unsigned long long* d_fields, uint16_t* d_labels, StageMarks* book) {
+    const double px = (double)H * W, chunks = (double)fields_chunks(H, W);
+    {
+        Scope sc(h, st, F_INDEX, 0.0, px * 4 + chunks * 4);      // parents in (sizes at the roots only), the sums out
+        HIPCHK(h, launch_fields_count(d_parent, d_size, H, W, minpx, d_sums, st));
+    }
+    if (book) book->next();
+    {
+        Scope sc(h, st, F_INDEX, 0.0, chunks * 8);
+        HIPCHK(h, launch_fields_scan(d_sums, H, W, d_found, st));
+    }
+    if (book) book->next();
+    {
+        Scope sc(h, st, F_INDEX, 0.0, px * 4 + chunks * 4);
+        HIPCHK(h, launch_fields_apply(d_parent, d_size, H, W, minpx, (uint32_t)Z, d_sums, d_fields, st));
+    }
+    if (book) book->next();
+    {
+        Scope sc(h, st, F_INDEX, 0.0, px * 6);                   // parents in, labels out (ranks at the roots only)
+        HIPCHK(h, launch_fields_labels(d_parent, d_size, H, W, (uint32_t)Z, d_labels, d_fields, st));
+    }
+    if (book) book->next();
+    return S2SR_OK;
+}
+
+}  // namespace s2sr::engine
+
+namespace {
+
+int fields_impl(s2sr_handle* h, const int16_t* idx, int H, int W, int lo, int hi, int r_open, int r_close, int conn, int64_t min_pixels, int Z,
+                uint16_t* labels, int64_t* fields, uint64_t* found) {
+    if (!h) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    int rc = fields_check_args(h, "s2sr_fields_segment_i16: ", idx, labels, H, W, lo, hi, r_open, r_close, conn, min_pixels, Z);
+    if (rc) return rc;
     const size_t N = (size_t)H * W, row_i = (size_t)W * 2;
-    const uint32_t minpx = min_pixels > 0x80000000LL ? 0x80000000u : (uint32_t)min_pixels;       // beyond H W nothing is a field
-    // SL_TABLES: the chunk sums, found, fields
-    const size_t o_found = up256(fields_chunks(H, W) * 4), o_fields = o_found + 256, fields_b = ((size_t)Z + 1) * 6 * 8;
+    const FieldsPlan p = fields_plan(H, W, min_pixels, Z);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DOOR_ENTER(h, h->stream);
     hipStream_t st = h->stream;
-    int rc = ensure_scratch(h, {{SL_SRC, up256(N * 2)}, {SL_DST, up256(N * 2)}, {SL_MID, up256(N)}, {SL_CHUNK, up256(N)}, {SL_PP, up256(N * 4)},
-                                {SL_CONS, up256(N * 4)}, {SL_TABLES, o_fields + up256(fields_b)}});
+    rc = ensure_scratch(h, {{SL_SRC, up256(N * 2)}, {SL_DST, up256(N * 2)}, {SL_MID, up256(N)}, {SL_CHUNK, up256(N)}, {SL_PP, up256(N * 4)},
+                            {SL_CONS, up256(N * 4)}, {SL_TABLES, p.bytes}});
     if (rc) return rc;
     int16_t* d_idx = scratch<int16_t>(h, SL_SRC);
     uint16_t* d_labels = scratch<uint16_t>(h, SL_DST);
@@ -43,94 +131,22 @@ int fields_impl(s2sr_handle* h, const int16_t* idx, int H, int W, int lo, int hi
     uint32_t* d_size = scratch<uint32_t>(h, SL_CONS);
     char* tab = scratch<char>(h, SL_TABLES);
     uint32_t* d_sums = (uint32_t*)tab;
-    unsigned long long* d_found = (unsigned long long*)(tab + o_found);
-    unsigned long long* d_fields = (unsigned long long*)(tab + o_fields);
-    const size_t rows = band_of(0, H, row_i, kBandBytes);
-    for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
-        const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
-        HIPCHK(h, hipMemcpyAsync(d_idx + y0 * W, idx + y0 * W, (y1 - y0) * row_i, hipMemcpyHostToDevice, st));
-    }
-    HIPCHK(h, hipMemsetAsync(d_fields, 0, fields_b, st));
-    const double px = (double)N, chunks = (double)fields_chunks(H, W);
-    // The bytes of a Scope are what the launch must move, not what its atomics and gathers add.  With profiling on every launch's
-    // event pair is also booked to its stage (s2sr_debug_fields_stage_ms): [from, to) of h->evs per stage.
-    size_t mark[S2SR_FIELDS_STAGES + 1];
-    int stage = 0;
-    mark[0] = h->evs.size();
-    int cur = 0;                                                 // the plane that holds the mask so far
-    {
-        Scope sc(h, st, F_INDEX, 0.0, px * 3);                   // the index in, a plane out
-        HIPCHK(h, launch_fields_mask(d_idx, H, W, lo, hi, 0, d_m[cur], st));
-    }
-    // open = dilate(erode), close = erode(dilate): each a row pass and a column pass
-    const int steps[4][2] = {{r_open, 1}, {r_open, 0}, {r_close, 0}, {r_close, 1}};                // radius, erode
-    for (const auto& s : steps) {
-        if (!s[0]) continue;
-        for (int column = 0; column < 2; ++column) {
-            Scope sc(h, st, F_INDEX, 0.0, px * 2);               // a plane in, a plane out (a column pass reads its rows from cache)
-            HIPCHK(h, launch_fields_morph(d_m[cur], d_m[cur ^ 1], H, W, s[0], s[1], column, st));
-            cur ^= 1;
-        }
-    }
-    if (r_open || r_close) {                                     // a close may have bridged nodata
-        Scope sc(h, st, F_INDEX, 0.0, px * 4);                   // the index and the plane in, the plane out
-        HIPCHK(h, launch_fields_mask(d_idx, H, W, -32767, 32767, 1, d_m[cur], st));
-    }
-    mark[++stage] = h->evs.size();                               // S2SR_FIELDS_STAGE_MASK ends
-    {
-        Scope sc(h, st, F_INDEX, 0.0, px * 9);                   // a plane in, parents and sizes out
-        HIPCHK(h, launch_fields_local(d_m[cur], d_parent, d_size, H, W, conn, st));
-    }
-    mark[++stage] = h->evs.size();
-    {
-        const double lines = (double)((H + 63) / 64 - 1) * W + (double)((W + 63) / 64 - 1) * H;
-        Scope sc(h, st, F_INDEX, 0.0, lines * 8);                // a border pixel's parent and its neighbour's; the walks come on top
-        HIPCHK(h, launch_fields_border(d_parent, H, W, conn, st));
-    }
-    mark[++stage] = h->evs.size();
-    {
-        Scope sc(h, st, F_INDEX, 0.0, px * 12);                  // parents in and out, sizes in
-        HIPCHK(h, launch_fields_flatten(d_parent, d_size, H, W, st));
-    }
-    mark[++stage] = h->evs.size();
-    {
-        Scope sc(h, st, F_INDEX, 0.0, px * 4 + chunks * 4);      // parents in (sizes at the roots only), the sums out
-        HIPCHK(h, launch_fields_count(d_parent, d_size, H, W, minpx, d_sums, st));
-    }
-    mark[++stage] = h->evs.size();
-    {
-        Scope sc(h, st, F_INDEX, 0.0, chunks * 8);
-        HIPCHK(h, launch_fields_scan(d_sums, H, W, d_found, st));
-    }
-    mark[++stage] = h->evs.size();
-    {
-        Scope sc(h, st, F_INDEX, 0.0, px * 4 + chunks * 4);
-        HIPCHK(h, launch_fields_apply(d_parent, d_size, H, W, minpx, (uint32_t)Z, d_sums, d_fields, st));
-    }
-    mark[++stage] = h->evs.size();
-    {
-        Scope sc(h, st, F_INDEX, 0.0, px * 6);                   // parents in, labels out (ranks at the roots only)
-        HIPCHK(h, launch_fields_labels(d_parent, d_size, H, W, (uint32_t)Z, d_labels, d_fields, st));
-    }
-    mark[++stage] = h->evs.size();
-    for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
-        const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
-        HIPCHK(h, hipMemcpyAsync(labels + y0 * W, d_labels + y0 * W, (y1 - y0) * row_i, hipMemcpyDeviceToHost, st));
-    }
-    if (fields) HIPCHK(h, hipMemcpyAsync(fields, d_fields, fields_b, hipMemcpyDeviceToHost, st));
+    unsigned long long* d_found = (unsigned long long*)(tab + p.o_found);
+    unsigned long long* d_fields = (unsigned long long*)(tab + p.o_fields);
+    const size_t rows = band_of(0, H, row_i, kRasterBandBytes);
+    HIPCHK(h, copy_rows(h, d_idx, idx, H, row_i, rows, hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipMemsetAsync(d_fields, 0, p.fields_b, st));
+    StageMarks book(h);                                          // every launch is booked to its stage (s2sr_debug_fields_stage_ms)
+    int cur = 0;
+    if ((rc = fields_mask(h, st, d_idx, d_m, H, W, lo, hi, r_open, r_close, &cur))) return rc;
+    book.next();                                                 // S2SR_FIELDS_STAGE_MASK ends
+    if ((rc = fields_components(h, st, d_m[cur], d_parent, d_size, H, W, conn, &book))) return rc;
+    if ((rc = fields_numbering(h, st, d_parent, d_size, H, W, p.minpx, Z, d_sums, d_found, d_fields, d_labels, &book))) return rc;
+    HIPCHK(h, copy_rows(h, labels, d_labels, H, row_i, rows, hipMemcpyDeviceToHost, st));
+    if (fields) HIPCHK(h, hipMemcpyAsync(fields, d_fields, p.fields_b, hipMemcpyDeviceToHost, st));
     if (found) HIPCHK(h, hipMemcpyAsync(found, d_found, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
-    for (int k = 0; k < S2SR_FIELDS_STAGES; ++k) {               // (the events stay where they are: the family's statistics read them later)
-        h->fields_stage_ms[k] = 0.0;
-        h->fields_stage_launches[k] = 0;
-        for (size_t i = mark[k]; i < mark[k + 1] && i < h->evs.size(); ++i) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, h->evs[i].e0, h->evs[i].e1) != hipSuccess) continue;
-            h->fields_stage_ms[k] += ms;
-            h->fields_stage_launches[k] += h->evs[i].n;
-        }
-    }
-    return S2SR_OK;
+    return book.close(h->fields_stages);
 }
 
 int trace_impl(s2sr_handle* h, const uint16_t* labels, int H, int W, int Z, uint64_t xy_cap, uint64_t ring_cap, int32_t* xy, int32_t* ring_start,
@@ -155,14 +171,7 @@ int s2sr_fields_segment_i16(s2sr_handle* h, const int16_t* idx, int32_t H, int32
 }
 
 int s2sr_debug_fields_stage_ms(s2sr_handle* h, double* ms, int32_t* launches) {
-    if (!h) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!ms || !launches) return fail(h, S2SR_E_INVALID, "s2sr_debug_fields_stage_ms: ms and launches are required");
-    for (int k = 0; k < S2SR_FIELDS_STAGES; ++k) {
-        ms[k] = h->fields_stage_ms[k];
-        launches[k] = h->fields_stage_launches[k];
-    }
-    return S2SR_OK;
+    return stage_times_out(h, &s2sr_handle::fields_stages, ms && launches, "s2sr_debug_fields_stage_ms: ms and launches are required", ms, launches);
 }
 
 int s2sr_labels_trace_u16(s2sr_handle* h, const uint16_t* labels, int32_t H, int32_t W, int32_t Z, uint64_t xy_cap, uint64_t ring_cap, int32_t* xy,

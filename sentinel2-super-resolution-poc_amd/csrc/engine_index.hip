@@ -13,7 +13,6 @@ using namespace s2sr::engine;
 namespace {
 
 constexpr size_t kLutBytes = 65536 * 4;
-constexpr size_t kBandBytes = (size_t)64 << 20;                  // the library's choice of what one band moves
 
 int index_nd_impl(s2sr_handle* h, const uint16_t* a, int ac, int ca, const uint16_t* b, int bc, int cb, int H, int W, int offset, int L, int K,
                   const uint8_t* valid, int vs, const uint16_t* zones, int zs, int Z, const uint8_t* lut, int band_rows, int16_t* out,
@@ -62,18 +61,17 @@ int index_nd_impl(s2sr_handle* h, const uint16_t* a, int ac, int ca, const uint1
     if (lut) HIPCHK(h, hipMemcpyAsync(d_lut, lut, kLutBytes, hipMemcpyHostToDevice, st));
     if (valid) HIPCHK(h, hipMemcpyAsync(d_valid, valid, vw * vh, hipMemcpyHostToDevice, st));
     if (zones) HIPCHK(h, hipMemcpyAsync(d_zones, zones, zw * zh * 2, hipMemcpyHostToDevice, st));
-    const size_t rows = band_of(band_rows, H, (a ? arow_b : 0) + brow_b + (out ? (size_t)W * 2 : 0) + (rgba ? (size_t)W * 4 : 0), kBandBytes);
-    for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
-        const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
-        if (a) HIPCHK(h, hipMemcpyAsync((char*)d_a + y0 * arow_b, (const char*)a + y0 * arow_b, (y1 - y0) * arow_b, hipMemcpyHostToDevice, st));
-        HIPCHK(h, hipMemcpyAsync((char*)d_b + y0 * brow_b, (const char*)b + y0 * brow_b, (y1 - y0) * brow_b, hipMemcpyHostToDevice, st));
+    const size_t rows = band_of(band_rows, H, (a ? arow_b : 0) + brow_b + (out ? (size_t)W * 2 : 0) + (rgba ? (size_t)W * 4 : 0), kRasterBandBytes);
+    for (const RowBand band : row_bands(H, rows)) {
+        if (a) HIPCHK(h, hipMemcpyAsync((char*)d_a + band.y0 * arow_b, (const char*)a + band.y0 * arow_b, band.rows() * arow_b, hipMemcpyHostToDevice, st));
+        HIPCHK(h, hipMemcpyAsync((char*)d_b + band.y0 * brow_b, (const char*)b + band.y0 * brow_b, band.rows() * brow_b, hipMemcpyHostToDevice, st));
         {
-            Scope sc(h, st, F_INDEX, 0.0, (double)(y1 - y0) * W * (4.0 + (out ? 2.0 : 0.0) + (rgba ? 4.0 : 0.0)));
-            HIPCHK(h, launch_index_nd(d_a, ac, ca, d_b, bc, cb, H, W, (int)y0, (int)y1, offset, L, K, d_valid, vs, d_zones, zs, Z, d_lut, d_out,
+            Scope sc(h, st, F_INDEX, 0.0, (double)band.rows() * W * (4.0 + (out ? 2.0 : 0.0) + (rgba ? 4.0 : 0.0)));
+            HIPCHK(h, launch_index_nd(d_a, ac, ca, d_b, bc, cb, H, W, (int)band.y0, (int)band.y1, offset, L, K, d_valid, vs, d_zones, zs, Z, d_lut, d_out,
                                       d_hist, d_zonal, d_rgba, d_undef, st));
         }
-        if (out) HIPCHK(h, hipMemcpyAsync(out + y0 * W, d_out + y0 * W, (y1 - y0) * W * 2, hipMemcpyDeviceToHost, st));
-        if (rgba) HIPCHK(h, hipMemcpyAsync(rgba + y0 * W * 4, d_rgba + y0 * W * 4, (y1 - y0) * W * 4, hipMemcpyDeviceToHost, st));
+        if (out) HIPCHK(h, hipMemcpyAsync(out + band.y0 * W, d_out + band.y0 * W, band.rows() * W * 2, hipMemcpyDeviceToHost, st));
+        if (rgba) HIPCHK(h, hipMemcpyAsync(rgba + band.y0 * W * 4, d_rgba + band.y0 * W * 4, band.rows() * W * 4, hipMemcpyDeviceToHost, st));
     }
     unsigned long long n = 0;
     HIPCHK(h, hipMemcpyAsync(&n, d_undef, sizeof n, hipMemcpyDeviceToHost, st));
@@ -101,15 +99,14 @@ int index_render_impl(s2sr_handle* h, const int16_t* idx, int H, int W, const ui
     uint8_t* d_rgba = scratch<uint8_t>(h, SL_DST);
     uint8_t* d_lut = scratch<uint8_t>(h, SL_TABLES);
     HIPCHK(h, hipMemcpyAsync(d_lut, lut, kLutBytes, hipMemcpyHostToDevice, st));
-    const size_t rows = band_of(band_rows, H, (size_t)W * 6, kBandBytes);
-    for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
-        const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
-        HIPCHK(h, hipMemcpyAsync(d_idx + y0 * W, idx + y0 * W, (y1 - y0) * W * 2, hipMemcpyHostToDevice, st));
+    const size_t rows = band_of(band_rows, H, (size_t)W * 6, kRasterBandBytes);
+    for (const RowBand band : row_bands(H, rows)) {
+        HIPCHK(h, hipMemcpyAsync(d_idx + band.y0 * W, idx + band.y0 * W, band.rows() * W * 2, hipMemcpyHostToDevice, st));
         {
-            Scope sc(h, st, F_INDEX, 0.0, (double)(y1 - y0) * W * 6.0);
-            HIPCHK(h, launch_index_render(d_idx, H, W, (int)y0, (int)y1, d_lut, d_rgba, st));
+            Scope sc(h, st, F_INDEX, 0.0, (double)band.rows() * W * 6.0);
+            HIPCHK(h, launch_index_render(d_idx, H, W, (int)band.y0, (int)band.y1, d_lut, d_rgba, st));
         }
-        HIPCHK(h, hipMemcpyAsync(rgba + y0 * W * 4, d_rgba + y0 * W * 4, (y1 - y0) * W * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(rgba + band.y0 * W * 4, d_rgba + band.y0 * W * 4, band.rows() * W * 4, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(h, hipStreamSynchronize(st));
     return S2SR_OK;

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "row_bands.h"
 #include "s2sr_internal.h"
 #include "scratch.h"
 
@@ -202,6 +203,10 @@ struct CompactTap {
     s2sr_debug_compact_fields* t = nullptr;
 };
 
+// What the N stages of a raster pass's last profiled call took (StageMarks::close writes it, stage_times_out reads it)
+template <int N>
+struct StageTimes { double ms[N] = {}; int32_t launches[N] = {}; };
+
 }  // namespace s2sr::engine
 
 // A device buffer added to this struct is also added to for_each_device_buffer below.
@@ -295,15 +300,12 @@ struct s2sr_handle {
     // where the last run_net left the trunk output conv_body reads (it differs between the fp16 and the fp8 trunk);
     // read by s2sr_debug_forward_taps only
     struct TrunkRec { const char* hi = nullptr; uint64_t hi_img = 0; const char* lo = nullptr; uint64_t lo_img = 0; int lo_exp = -1; } trunk_rec;
-    // s2sr_fields_segment_i16 with profiling on: the event time and the bracketed launches of the last call, stage by stage (S2SR_FIELDS_STAGE_*)
-    double fields_stage_ms[S2SR_FIELDS_STAGES] = {};
-    int32_t fields_stage_launches[S2SR_FIELDS_STAGES] = {};
-    // s2sr_zones_kmeans_i16 with profiling on: the same, by S2SR_MZONES_* stage
-    double mzones_stage_ms[S2SR_MZONES_STAGES] = {};
-    int32_t mzones_stage_launches[S2SR_MZONES_STAGES] = {};
-    // s2sr_fields_split_i16 with profiling on: the same, by S2SR_FSPLIT_* stage; and the rounds its two growths took (always)
-    double fsplit_stage_ms[S2SR_FSPLIT_STAGES] = {};
-    int32_t fsplit_stage_launches[S2SR_FSPLIT_STAGES] = {};
+    // The last s2sr_fields_segment_i16, s2sr_zones_kmeans_i16 and s2sr_fields_split_i16 with profiling on: the event time and the
+    // bracketed launches, stage by stage (S2SR_FIELDS_STAGE_*, S2SR_MZONES_*, S2SR_FSPLIT_*; written by StageMarks::close); and the
+    // rounds the split's two growths took (always)
+    s2sr::engine::StageTimes<S2SR_FIELDS_STAGES> fields_stages;
+    s2sr::engine::StageTimes<S2SR_MZONES_STAGES> mzones_stages;
+    s2sr::engine::StageTimes<S2SR_FSPLIT_STAGES> fsplit_stages;
     int32_t fsplit_rounds[2] = {};
     s2sr::engine::TrunkTap* ttap = nullptr;     // s2sr_debug_trunk_taps' batch is running (run_net taps the trunk at its RDB boundaries); null otherwise
     s2sr::engine::CompactTap* ctap = nullptr;   // s2sr_debug_compact_taps' batch is running
@@ -333,12 +335,7 @@ bool recover_stream(s2sr_handle* h);
     } while (0)
 
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }   // the next multiple of 256: where the next table or plane starts
-// The rows of one band of a banded pass: the caller's band_rows, or the library's choice of budget_bytes moved per band (row_bytes:
-// what one row moves); at least 1, at most H.
-inline size_t band_of(int band_rows, size_t H, size_t row_bytes, size_t budget_bytes) {
-    const size_t rows = band_rows > 0 ? (size_t)band_rows : budget_bytes / row_bytes;
-    return rows < 1 ? 1 : rows > H ? H : rows;
-}
+constexpr size_t kRasterBandBytes = (size_t)64 << 20;   // the raster passes' rasters come and go in row bands of about this size (band_of: row_bands.h)
 
 constexpr size_t kTrashBytes = 8192;   // s2sr_handle::d_trash
 // Every device allocation the handle owns, each once: s2sr_destroy frees them, s2sr_debug_redzone_check counts the zoned ones.
@@ -374,6 +371,8 @@ struct KeptInput {
 };
 hipError_t copy_blocking(s2sr_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
 hipError_t fill_blocking(s2sr_handle* h, void* dst, int value, size_t bytes);
+// H rows of row_bytes each from src to dst in bands of `rows` rows, queued on st: a raster comes in or leaves
+hipError_t copy_rows(s2sr_handle* h, void* dst, const void* src, size_t H, size_t row_bytes, size_t rows, hipMemcpyKind kind, hipStream_t st);
 
 // the plane decoders of the test hooks
 typedef _Float16 hf16;
@@ -463,6 +462,50 @@ struct Scope {   // brackets one launch with events when profiling is on
     }
 };
 
+// The stage book of one call of a raster pass.  With profiling on every launch's event pair (Scope) is also booked to the stage it
+// belongs to: [from, to) of h->evs per stage.  next() ends a stage; close(), at the call's successful end only, writes what each
+// stage took to the handle, so a call that fails midway leaves the times of the call before.  The events stay where they are: the
+// family's statistics read them later.  An unprofiled call records no event and leaves zeros.
+constexpr int kMaxStages = 8;
+struct StageMarks {
+    s2sr_handle* h;
+    int stage = 0;
+    size_t mark[kMaxStages + 1];
+    explicit StageMarks(s2sr_handle* h_) : h(h_) { mark[0] = h->evs.size(); }
+    void next() { if (stage++ < kMaxStages) mark[stage] = h->evs.size(); }   // one too many is counted, not stored: close refuses
+    template <int N>
+    int close(StageTimes<N>& t) {
+        static_assert(N <= kMaxStages, "a book of more stages needs a larger kMaxStages");
+        if (stage != N) return fail(h, S2SR_E_HIP, "stage book: " + std::to_string(stage) + " stages were ended where the pass has " + std::to_string(N));
+        for (int k = 0; k < N; ++k) {
+            t.ms[k] = 0.0;
+            t.launches[k] = 0;
+            for (size_t i = mark[k]; i < mark[k + 1] && i < h->evs.size(); ++i) {
+                float ms = 0.f;
+                if (hipEventElapsedTime(&ms, h->evs[i].e0, h->evs[i].e1) != hipSuccess) continue;
+                t.ms[k] += ms;
+                t.launches[k] += h->evs[i].n;
+            }
+        }
+        return S2SR_OK;
+    }
+};
+// The body of the s2sr_debug_*_stage_ms hooks: the book of the last call copied out under the lock.  given: every array the hook
+// requires is there (`refusal` otherwise); rounds: the split's hook also hands out fsplit_rounds.
+template <int N>
+int stage_times_out(s2sr_handle* h, StageTimes<N> s2sr_handle::*book, bool given, const char* refusal, double* ms, int32_t* launches,
+                    int32_t* rounds = nullptr) {
+    if (!h) return S2SR_E_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!given) return fail(h, S2SR_E_INVALID, refusal);
+    for (int k = 0; k < N; ++k) {
+        ms[k] = (h->*book).ms[k];
+        launches[k] = (h->*book).launches[k];
+    }
+    if (rounds) rounds[0] = h->fsplit_rounds[0], rounds[1] = h->fsplit_rounds[1];
+    return S2SR_OK;
+}
+
 int group_size(const s2sr_handle* h, int B, int H, int W);
 int group_windows(const s2sr_handle* h, const Mosaic& mo, int T, int th, int tw);
 void mosaic_remainder(int rem, int kx, int ky, int* rkx, int* rky);
@@ -484,5 +527,22 @@ struct WindowJob {
     std::vector<int32_t> rects, rm, cm;
 };
 int plan_window_job(int PH, int PW, int tile, int pad, int scale, bool tiled, WindowJob& job);
+
+// ---- engine_fields.hip: the stages s2sr_fields_segment_i16 and s2sr_fields_split_i16 (engine_fields_split.hip) share
+// The refusals of both doors, in order, under the door's own prefix `what`; S2SR_OK when none applies.
+int fields_check_args(s2sr_handle* h, const char* what, const void* idx, const void* labels, int H, int W, int lo, int hi, int r_open, int r_close,
+                      int conn, int64_t min_pixels, int Z);
+// min_pixels as the kernels take it, and SL_TABLES: the chunk sums, found (at o_found), `between` bytes of the door's own (at
+// o_between; a multiple of 256), the fields table (fields_b bytes at o_fields); bytes: the slot's request.
+struct FieldsPlan { uint32_t minpx; size_t o_found, o_between, o_fields, fields_b, bytes; };
+FieldsPlan fields_plan(int H, int W, int64_t min_pixels, int Z, size_t between = 0);
+// The index -> the mask: lo..hi, opened and closed, nodata taken out again behind a morphology.  *cur: the plane of d_m that holds it.
+int fields_mask(s2sr_handle* h, hipStream_t st, const int16_t* d_idx, uint8_t* const d_m[2], int H, int W, int lo, int hi, int r_open, int r_close,
+                int* cur);
+// A plane's connected components (local, border, flatten: parent = the root) and the numbering (count, scan, apply, labels).
+// book: the plain segmentation ends a stage behind every launch; the split books them in groups and passes none.
+int fields_components(s2sr_handle* h, hipStream_t st, const uint8_t* plane, int* d_parent, uint32_t* d_size, int H, int W, int conn, StageMarks* book);
+int fields_numbering(s2sr_handle* h, hipStream_t st, int* d_parent, uint32_t* d_size, int H, int W, uint32_t minpx, int Z, uint32_t* d_sums,
+                     unsigned long long* d_found, unsigned long long* d_fields, uint16_t* d_labels, StageMarks* book);
 
 }  // namespace s2sr::engine

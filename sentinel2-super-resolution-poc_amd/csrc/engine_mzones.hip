@@ -11,8 +11,6 @@ using namespace s2sr::engine;
 
 namespace {
 
-constexpr size_t kBandBytes = (size_t)64 << 20;                  // the rasters come and go in row bands of about this size
-
 int mzones_impl(s2sr_handle* h, const int16_t* feat, int D, int H, int W, const uint16_t* labels, int Z, int k, int iters, int64_t min_per_zone,
                 int smooth, int band_rows, uint8_t* zone, int64_t* table, int32_t* centres, uint8_t* status, uint32_t* iterations) {
     if (!h) return S2SR_E_INVALID;
@@ -53,37 +51,33 @@ int mzones_impl(s2sr_handle* h, const int16_t* feat, int D, int H, int W, const 
     unsigned long long* d_acc = (unsigned long long*)(tab + o_acc);
     // the bands the rasters travel in, the statistics pass behind each; and the bands of the passes that run on the whole raster,
     // which are the caller's or one
-    const size_t rows = band_of(band_rows, H, (size_t)W * (2 * D + 2), kBandBytes);
+    const size_t rows = band_of(band_rows, H, (size_t)W * (2 * D + 2), kRasterBandBytes);
     const size_t prows = band_rows > 0 ? band_of(band_rows, H, 1, 1) : (size_t)H;
     const double cells = (double)(F * k);
-    size_t mark[S2SR_MZONES_STAGES + 1];
-    int stage = 0;
-    mark[0] = h->evs.size();
+    StageMarks book(h);                                          // every launch is booked to its stage (s2sr_debug_mzones_stage_ms)
     HIPCHK(h, hipMemsetAsync(d_acc, 0, acc_b, st));
     {
         Scope sc(h, st, F_INDEX, 0.0, (double)F * (4 + 8 * D));
         HIPCHK(h, launch_mzones_clear(d_cnt, d_lo, d_hi, Z, D, st));
     }
-    for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
-        const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
-        HIPCHK(h, hipMemcpyAsync(d_labels + y0 * W, labels + y0 * W, (y1 - y0) * W * 2, hipMemcpyHostToDevice, st));
+    for (const RowBand b : row_bands(H, rows)) {
+        HIPCHK(h, hipMemcpyAsync(d_labels + b.y0 * W, labels + b.y0 * W, b.rows() * W * 2, hipMemcpyHostToDevice, st));
         for (int d = 0; d < D; ++d)
-            HIPCHK(h, hipMemcpyAsync(d_feat + d * N + y0 * W, feat + d * N + y0 * W, (y1 - y0) * W * 2, hipMemcpyHostToDevice, st));
-        Scope sc(h, st, F_INDEX, 0.0, (double)(y1 - y0) * W * (2 * D + 2));
-        HIPCHK(h, launch_mzones_stats(d_feat, D, H, W, (int)y0, (int)y1, d_labels, Z, d_cnt, d_lo, d_hi, st));
+            HIPCHK(h, hipMemcpyAsync(d_feat + d * N + b.y0 * W, feat + d * N + b.y0 * W, b.rows() * W * 2, hipMemcpyHostToDevice, st));
+        Scope sc(h, st, F_INDEX, 0.0, (double)b.rows() * W * (2 * D + 2));
+        HIPCHK(h, launch_mzones_stats(d_feat, D, H, W, (int)b.y0, (int)b.y1, d_labels, Z, d_cnt, d_lo, d_hi, st));
     }
     {
         Scope sc(h, st, F_INDEX, 0.0, cells * (1 + 4 * D));
         HIPCHK(h, launch_mzones_start(d_cnt, d_lo, d_hi, Z, k, D, least, d_status, d_centres, st));
     }
-    mark[++stage] = h->evs.size();                               // S2SR_MZONES_STATISTICS ends
+    book.next();                                                 // S2SR_MZONES_STATISTICS ends
     uint32_t ran = (uint32_t)iters;
     for (int t = 1; t <= iters; ++t) {
         HIPCHK(h, hipMemsetAsync(d_changed, 0, 4, st));
-        for (size_t y0 = 0; y0 < (size_t)H; y0 += prows) {
-            const size_t y1 = y0 + prows < (size_t)H ? y0 + prows : H;
-            Scope sc(h, st, F_INDEX, 0.0, (double)(y1 - y0) * W * (2 * D + 2));   // labels and features in; the sums leave through atomics
-            HIPCHK(h, launch_mzones_accumulate(d_feat, D, H, W, (int)y0, (int)y1, d_labels, Z, k, d_centres, d_status, nullptr, d_acc, st));
+        for (const RowBand b : row_bands(H, prows)) {
+            Scope sc(h, st, F_INDEX, 0.0, (double)b.rows() * W * (2 * D + 2));   // labels and features in; the sums leave through atomics
+            HIPCHK(h, launch_mzones_accumulate(d_feat, D, H, W, (int)b.y0, (int)b.y1, d_labels, Z, k, d_centres, d_status, nullptr, d_acc, st));
         }
         {
             Scope sc(h, st, F_INDEX, 0.0, cells * (1 + D) * 16);
@@ -97,56 +91,40 @@ int mzones_impl(s2sr_handle* h, const int16_t* feat, int D, int H, int W, const 
             break;
         }
     }
-    mark[++stage] = h->evs.size();
+    book.next();
     {
         Scope sc(h, st, F_INDEX, 0.0, cells * (2 + 8 * D));
         HIPCHK(h, launch_mzones_rank(d_centres, Z, k, D, d_status, d_zone_of, d_ranked, st));
     }
-    for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
-        const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
-        Scope sc(h, st, F_INDEX, 0.0, (double)(y1 - y0) * W * (2 * D + 3));
-        HIPCHK(h, launch_mzones_assign(d_feat, D, H, W, (int)y0, (int)y1, d_labels, Z, k, d_centres, d_status, d_zone_of, d_z[0], st));
+    for (const RowBand b : row_bands(H, rows)) {
+        Scope sc(h, st, F_INDEX, 0.0, (double)b.rows() * W * (2 * D + 3));
+        HIPCHK(h, launch_mzones_assign(d_feat, D, H, W, (int)b.y0, (int)b.y1, d_labels, Z, k, d_centres, d_status, d_zone_of, d_z[0], st));
     }
-    mark[++stage] = h->evs.size();
+    book.next();
     int cur = 0;                                                 // the plane that holds the raster so far
     for (int s = 0; s < smooth; ++s) {
-        for (size_t y0 = 0; y0 < (size_t)H; y0 += prows) {
-            const size_t y1 = y0 + prows < (size_t)H ? y0 + prows : H;
-            Scope sc(h, st, F_INDEX, 0.0, (double)(y1 - y0) * W * 4);                 // a plane and the labels in (the neighbours from cache), a plane out
-            HIPCHK(h, launch_mzones_mode(d_z[cur], d_labels, H, W, (int)y0, (int)y1, k, d_z[cur ^ 1], st));
+        for (const RowBand b : row_bands(H, prows)) {
+            Scope sc(h, st, F_INDEX, 0.0, (double)b.rows() * W * 4);                 // a plane and the labels in (the neighbours from cache), a plane out
+            HIPCHK(h, launch_mzones_mode(d_z[cur], d_labels, H, W, (int)b.y0, (int)b.y1, k, d_z[cur ^ 1], st));
         }
         cur ^= 1;
     }
-    mark[++stage] = h->evs.size();
+    book.next();
     if (table) {
         HIPCHK(h, hipMemsetAsync(d_acc, 0, table_b, st));
-        for (size_t y0 = 0; y0 < (size_t)H; y0 += prows) {
-            const size_t y1 = y0 + prows < (size_t)H ? y0 + prows : H;
-            Scope sc(h, st, F_INDEX, 0.0, (double)(y1 - y0) * W * (2 * D + 3));
-            HIPCHK(h, launch_mzones_accumulate(d_feat, D, H, W, (int)y0, (int)y1, d_labels, Z, k, nullptr, nullptr, d_z[cur], d_acc, st));
+        for (const RowBand b : row_bands(H, prows)) {
+            Scope sc(h, st, F_INDEX, 0.0, (double)b.rows() * W * (2 * D + 3));
+            HIPCHK(h, launch_mzones_accumulate(d_feat, D, H, W, (int)b.y0, (int)b.y1, d_labels, Z, k, nullptr, nullptr, d_z[cur], d_acc, st));
         }
     }
-    mark[++stage] = h->evs.size();
-    for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
-        const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
-        HIPCHK(h, hipMemcpyAsync(zone + y0 * W, d_z[cur] + y0 * W, (y1 - y0) * W, hipMemcpyDeviceToHost, st));
-    }
+    book.next();
+    HIPCHK(h, copy_rows(h, zone, d_z[cur], H, W, rows, hipMemcpyDeviceToHost, st));
     if (table) HIPCHK(h, hipMemcpyAsync(table, d_acc, table_b, hipMemcpyDeviceToHost, st));
     if (centres) HIPCHK(h, hipMemcpyAsync(centres, d_ranked, F * k * D * 4, hipMemcpyDeviceToHost, st));
     if (status) HIPCHK(h, hipMemcpyAsync(status, d_status, F, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));
     if (iterations) *iterations = ran;
-    for (int s = 0; s < S2SR_MZONES_STAGES; ++s) {               // (the events stay where they are: the family's statistics read them later)
-        h->mzones_stage_ms[s] = 0.0;
-        h->mzones_stage_launches[s] = 0;
-        for (size_t i = mark[s]; i < mark[s + 1] && i < h->evs.size(); ++i) {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, h->evs[i].e0, h->evs[i].e1) != hipSuccess) continue;
-            h->mzones_stage_ms[s] += ms;
-            h->mzones_stage_launches[s] += h->evs[i].n;
-        }
-    }
-    return S2SR_OK;
+    return book.close(h->mzones_stages);
 }
 
 }  // namespace
@@ -160,14 +138,7 @@ int s2sr_zones_kmeans_i16(s2sr_handle* h, const int16_t* feat, int32_t D, int32_
 }
 
 int s2sr_debug_mzones_stage_ms(s2sr_handle* h, double* ms, int32_t* launches) {
-    if (!h) return S2SR_E_INVALID;
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (!ms || !launches) return fail(h, S2SR_E_INVALID, "s2sr_debug_mzones_stage_ms: ms and launches are required");
-    for (int s = 0; s < S2SR_MZONES_STAGES; ++s) {
-        ms[s] = h->mzones_stage_ms[s];
-        launches[s] = h->mzones_stage_launches[s];
-    }
-    return S2SR_OK;
+    return stage_times_out(h, &s2sr_handle::mzones_stages, ms && launches, "s2sr_debug_mzones_stage_ms: ms and launches are required", ms, launches);
 }
 
 }  // extern "C"

@@ -45,16 +45,15 @@ int zones_impl(s2sr_handle* h, const int32_t* xy, const int32_t* ring_start, con
     HIPCHK(h, hipMemcpyAsync(tab + o_start, bins.start.data(), (T + 1) * 4, hipMemcpyHostToDevice, st));
     if (nnz) HIPCHK(h, hipMemcpyAsync(tab + o_list, bins.feat.data(), nnz * 4, hipMemcpyHostToDevice, st));
     if (area) HIPCHK(h, hipMemsetAsync(d_area, 0, area_b, st));
-    const size_t rows = band_of(band_rows, H, row_b, (size_t)64 << 20);                // the caller's, or ~64 MB of labels per band
-    for (size_t y0 = 0; y0 < (size_t)H; y0 += rows) {
-        const size_t y1 = y0 + rows < (size_t)H ? y0 + rows : H;
+    const size_t rows = band_of(band_rows, H, row_b, kRasterBandBytes);                // the caller's, or ~64 MB of labels per band
+    for (const RowBand b : row_bands(H, rows)) {
         {
-            Scope sc(h, st, F_INDEX, 0.0, (double)(y1 - y0) * row_b);
+            Scope sc(h, st, F_INDEX, 0.0, (double)b.rows() * row_b);
             HIPCHK(h, launch_zones_rasterize((const int32_t*)tab, (const int32_t*)(tab + o_ring), (const int32_t*)(tab + o_feat),
                                              (const uint16_t*)(tab + o_label), (const uint32_t*)(tab + o_start), (const int32_t*)(tab + o_list), H, W,
-                                             (int)y0, (int)y1, d_out, d_area, st));
+                                             (int)b.y0, (int)b.y1, d_out, d_area, st));
         }
-        HIPCHK(h, hipMemcpyAsync(out + y0 * W, d_out + y0 * W, (y1 - y0) * row_b, hipMemcpyDeviceToHost, st));
+        HIPCHK(h, hipMemcpyAsync(out + b.y0 * W, d_out + b.y0 * W, b.rows() * row_b, hipMemcpyDeviceToHost, st));
     }
     if (area) HIPCHK(h, hipMemcpyAsync(area, d_area, ((size_t)Z + 1) * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(h, hipStreamSynchronize(st));

@@ -1075,12 +1075,16 @@ class Engine:
                                                       _ptr(labels), _ptr(fields), _ptr(found)), "s2sr_fields_segment_i16")
         return labels, fields, int(found[0])
 
+    def _stage_ms(self, hook: str, stages, *more) -> dict:
+        """{stage: (ms, launches)} from one of the s2sr_debug_*_stage_ms hooks; more: what the hook takes behind ms and launches"""
+        ms, n = np.zeros(len(stages), np.float64), np.zeros(len(stages), np.int32)
+        self._check(getattr(self._lib, hook)(self._h, _ptr(ms), _ptr(n), *more), hook)
+        return {name: (float(ms[k]), int(n[k])) for k, name in enumerate(stages)}
+
     def fields_stage_ms(self) -> dict:
         """What the stages of the last fields_segment_i16 took by HIP events, {stage: (ms, launches)} in the order of FIELDS_STAGES
         (include/s2sr.h s2sr_debug_fields_stage_ms): zeros unless that call ran under set_profiling(1)."""
-        ms, n = np.zeros(len(FIELDS_STAGES), np.float64), np.zeros(len(FIELDS_STAGES), np.int32)
-        self._check(self._lib.s2sr_debug_fields_stage_ms(self._h, _ptr(ms), _ptr(n)), "s2sr_debug_fields_stage_ms")
-        return {name: (float(ms[k]), int(n[k])) for k, name in enumerate(FIELDS_STAGES)}
+        return self._stage_ms("s2sr_debug_fields_stage_ms", FIELDS_STAGES)
 
     def fields_split_i16(self, idx, lo: int, hi: int, r_open: int = 0, r_close: int = 0, conn: int = 4, min_pixels: int = 1, Z: int = 65535,
                          split=None, want=()):
@@ -1120,9 +1124,8 @@ class Engine:
         """What the stages of the last fields_split_i16 with a split took by HIP events, {stage: (ms, launches)} in the order of
         FSPLIT_STAGES, and under "rounds" the launches its two growths took (include/s2sr.h s2sr_debug_fields_split_stage_ms): the
         times are zeros unless that call ran under set_profiling(1)."""
-        ms, n, rounds = np.zeros(len(FSPLIT_STAGES), np.float64), np.zeros(len(FSPLIT_STAGES), np.int32), np.zeros(2, np.int32)
-        self._check(self._lib.s2sr_debug_fields_split_stage_ms(self._h, _ptr(ms), _ptr(n), _ptr(rounds)), "s2sr_debug_fields_split_stage_ms")
-        out = {name: (float(ms[k]), int(n[k])) for k, name in enumerate(FSPLIT_STAGES)}
+        rounds = np.zeros(2, np.int32)
+        out = self._stage_ms("s2sr_debug_fields_split_stage_ms", FSPLIT_STAGES, _ptr(rounds))
         out["rounds"] = (int(rounds[0]), int(rounds[1]))
         return out
 
@@ -1155,9 +1158,7 @@ class Engine:
     def mzones_stage_ms(self) -> dict:
         """What the stages of the last zones_kmeans_i16 took by HIP events, {stage: (ms, launches)} in the order of MZONES_STAGES
         (include/s2sr.h s2sr_debug_mzones_stage_ms): zeros unless that call ran under set_profiling(1)."""
-        ms, n = np.zeros(len(MZONES_STAGES), np.float64), np.zeros(len(MZONES_STAGES), np.int32)
-        self._check(self._lib.s2sr_debug_mzones_stage_ms(self._h, _ptr(ms), _ptr(n)), "s2sr_debug_mzones_stage_ms")
-        return {name: (float(ms[k]), int(n[k])) for k, name in enumerate(MZONES_STAGES)}
+        return self._stage_ms("s2sr_debug_mzones_stage_ms", MZONES_STAGES)
 
     def labels_trace_u16(self, labels, Z: int):
         """A uint16 label raster [H, W] -> (xy int32 [V, 2] in pixel corners, ring_start int32 [R + 1], ring_label uint16 [R]): the

@@ -90,7 +90,8 @@ its index and offset tables: each is uploaded in full, on the stream of the kern
     the changed counter, two planes of tile marks, the fields table).  Index-like: the parents (followed as pointers, and rows of the
     largest distances), the growth words (the low half is the owner: fsplit_parent_kernel reads key[] there), the key plane (what
     becomes the parent), the tile marks (which tiles a round visits), the ranks and chunk sums as in fields_impl.  The mask, morphology,
-    local, border, flatten, count, scan, apply and label launches are fields_impl's, in its order.  The edge kernel writes every pixel
+    local, border, flatten, count, scan, apply and label launches are the stages it shares with fields_impl (engine_fields.hip
+    fields_mask, fields_components, fields_numbering; the tables are laid out by fields_plan), in its order.  The edge kernel writes every pixel
     of the interior, the column pass every pixel of the vertical distances and the row pass every pixel of the distance plane before
     the cores read it; the plane behind the parents is memset in front of the maxima (0), the keys (all ones) and the sizes (0); the
     core kernel writes every pixel; the seed kernel writes EVERY word (unreached: all ones) behind the second components pass, and
