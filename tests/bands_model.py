@@ -104,6 +104,40 @@ def scene(H, W, S, seed=0):
     return np.clip(np.stack(chans, -1), 0, 65535).astype(np.uint16)
 
 
+SATURATED = ("blocks", "half", "noise", "full")
+SATURATED_BANDS = ("mean", "inverse", "full", "steep")
+
+
+@functools.lru_cache(maxsize=None)
+def saturated_scene(H, W, S, name):
+    """a uint16 guide [S H, S W, 3] of 0 and 65535 alone: "blocks" alternates per input pixel, "half" is a half plane whose edge cuts
+    a column of blocks, "noise" draws every sample of every channel, "full" is all 65535"""
+    yy, xx = np.mgrid[0:H * S, 0:W * S]
+    if name == "blocks":
+        on = (yy // S + xx // S) % 2 == 0
+    elif name == "half":
+        on = xx >= (W * S) // 2 + 1
+    elif name == "noise":
+        on = np.random.default_rng(17 * H + W + 3 * S).integers(0, 2, (H * S, W * S, 3)) != 0
+    elif name == "full":
+        on = np.ones((H * S, W * S), bool)
+    else:
+        raise KeyError(name)
+    q = np.where(on if on.ndim == 3 else on[..., None].repeat(3, 2), 65535, 0).astype(np.uint16)
+    q.setflags(write=False)
+    return q
+
+
+@functools.lru_cache(maxsize=None)
+def saturated_band(H, W, S, name, band):
+    """a band for saturated_scene(H, W, S, name): the block mean of the guide under weights (1, 1, 1), 65535 minus it, all 65535, or
+    ("steep") three times the block mean's distance from mid-range, clipped: a gain of 3 where the guide has grey block means"""
+    G = block_mean(guide(saturated_scene(H, W, S, name), (1, 1, 1)), S)
+    b = {"mean": G, "inverse": 65535 - G, "full": np.full_like(G, 65535), "steep": np.clip(3 * G - 65535, 0, 65535)}[band].astype(np.uint16)
+    b.setflags(write=False)
+    return b
+
+
 def affine_band(q, S, alpha, beta, w=(1, 1, 1)):
     """(the band: the rounded block mean of alpha I + beta, the truth alpha I + beta on the output grid as float)"""
     t = alpha * guide(q, w).astype(np.float64) + beta

@@ -213,6 +213,22 @@ def trace_rasters():
     return out
 
 
+# ---- the numbering's geometry --------------------------------------------------------------------------------------------------------------
+CHUNK, TURN = 1024, 256                                            # csrc/fields.hip: kChunk pixels a chunk; the scan walks 256 chunks a turn
+
+
+def scan_reach(keys, H, W):
+    """Where the keys of the numbered fields fall in the numbering scan (csrc/fields.hip fields_scan_kernel): the number of chunks and
+    of turns, the turns that hold a key, the keys in the last chunk of the first turn and in the first of the second, and the carry
+    each turn starts with (the fields numbered before it)."""
+    keys = np.sort(np.asarray(keys, np.int64))
+    chunks = -(-H * W // CHUNK)
+    turns = -(-chunks // TURN)
+    turn = keys // (TURN * CHUNK)
+    return {"chunks": chunks, "turns": turns, "met": sorted(set(turn.tolist())), "in255": int((keys // CHUNK == TURN - 1).sum()),
+            "in256": int((keys // CHUNK == TURN).sum()), "carry": [int((turn < t).sum()) for t in range(turns)]}
+
+
 # ---- the inputs of the GPU tests -------------------------------------------------------------------------------------------------------
 LO, HI = 4000, 32767
 

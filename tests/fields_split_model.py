@@ -240,9 +240,58 @@ def case(H, W, name, split=None, **kw):
     return _CASES[key]
 
 
-def notched(H=300, W=600):
-    """a solid rectangle wider than 510 pixels over every row, with one notch cut in from the top: D2 reaches the cap in its middle"""
+def notched(H=300, W=600, both=False):
+    """a solid rectangle wider than 510 pixels over every row, with one notch cut in from the top: D2 reaches the cap in its middle;
+    both: a second notch from the bottom, so that pixels also find their nearest outside pixel below them"""
     m = np.zeros((H, W), bool)
     m[:, 20:W - 20] = True
     m[0:21, 300:303] = False
+    if both:
+        m[H - 21:H, 296:299] = False
     return fm.as_index(m)
+
+
+SATURATED = (-32767, 32767)                                        # lo, hi of the saturated rasters: every pixel is in the mask
+SATURATED_SPLITS = ({"edge": 32767, "edge_r": 4}, {"edge": 1, "edge_r": 4}, {"edge": 32767, "edge_r": 0}, {"edge": 16000, "edge_r": 2})
+
+
+def saturated(H, W, cell):
+    """+32767 and -32767 in a checkerboard of cell x cell pixels: the box sums of the edge test reach +-(2 r + 1)^2 * 32767 where a
+    window lies inside a cell, and the Sobel sums of them their largest differences"""
+    yy, xx = np.mgrid[0:H, 0:W]
+    return np.where((yy // cell + xx // cell) % 2 == 0, 32767, -32767).astype(np.int16)
+
+
+_SATURATED = {}
+
+
+def saturated_case(H, W, cell, split, **kw):
+    """split() of saturated(H, W, cell) in SATURATED: made once per raster and parameter set, read-only"""
+    key = (H, W, cell, tuple(sorted(split.items())), tuple(sorted(kw.items())))
+    if key not in _SATURATED:
+        out = globals()["split"](saturated(H, W, cell), *SATURATED, split=split, **kw)
+        for v in out.values():
+            if isinstance(v, np.ndarray):
+                v.setflags(write=False)
+        _SATURATED[key] = out
+    return _SATURATED[key]
+
+
+# ---- the distance's geometry (csrc/fields_split.hip: kBand rows a thread of the column pass, kSeg pixels a workgroup of the row pass) -------
+BAND, SEG = 256, 256
+
+
+def band_reach(I, dist2, band=1):
+    """On the rows [ya, yb) of one band of the column pass: the pixels of I at the cap and below it; among the latter those whose D2
+    exceeds the squared distance to the row before the band (above) or to the row behind it (below), so that no pixel of the band's
+    own rows straight above or below them is the nearest one; and those for which the band's rows alone give a larger distance
+    (other): their nearest outside pixel lies in another band, whichever way one looks."""
+    H = dist2.shape[0]
+    ya, yb = band * BAND, min((band + 1) * BAND, H)
+    d = dist2[ya:yb].astype(np.int64)
+    rows = np.arange(ya, yb)[:, None]
+    open_ = (d > 0) & (d < CAP * CAP)
+    alone = distance2(np.asarray(I)[ya:yb])
+    return {"rows": (ya, yb), "capped": int((d == CAP * CAP).sum()), "uncapped": int(open_.sum()),
+            "above": int((open_ & (d > (rows - ya + 1) ** 2)).sum()), "below": int((open_ & (d > (yb - rows) ** 2)).sum()),
+            "other": int((open_ & (alone > d)).sum())}

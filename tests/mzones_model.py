@@ -12,6 +12,9 @@ NOISE = 300
 MIXES = {"thirds": (1 / 3, 1 / 3, 1 / 3), "60-30-10": (0.6, 0.3, 0.1), "10-10-80": (0.1, 0.1, 0.8), "5-90-5": (0.05, 0.9, 0.05)}
 FEATURES = ("planted", "noise", "constant", "ramp", "nodata", "extremes")
 LAYOUTS = ("one", "grid16", "stripes", "checker", "above", "zeros")
+# the saturated rasters and the layout of tests/test_gpu_limits.py: +32767 in the upper half of the rows and -32767 in the lower, its
+# negative and its half (floor); rows [H / 4, 3 H / 4) as a second field.  They are in no list above: the lists' loops stay what they are.
+HALVES = ("halves", "-halves", "halves/2")
 
 
 # ---- the definition --------------------------------------------------------------------------------------------------------------------
@@ -126,8 +129,13 @@ def planted(shape, mix="thirds", seed=0, D=1):
 @functools.lru_cache(maxsize=None)
 def raster(H, W, name):
     """one int16 feature raster [H, W]"""
-    rng = np.random.default_rng(1000 * H + 10 * W + FEATURES.index(name))
     y, x = np.mgrid[0:H, 0:W]
+    if name in HALVES:                                             # -32768 is nodata: it does not appear
+        f = np.where(y < (H + 1) // 2, 32767, -32767)
+        a = (f, -f, f // 2)[HALVES.index(name)].astype(np.int16)
+        a.setflags(write=False)
+        return a
+    rng = np.random.default_rng(1000 * H + 10 * W + FEATURES.index(name))
     if name == "planted":
         a = planted((H, W), "60-30-10", seed=H * 1000 + W)[0][0] if H * W >= 3 else np.full((H, W), 5000)
     elif name == "noise":
@@ -165,12 +173,32 @@ def layout(H, W, name):
         a = grid * 3
     elif name == "zeros":
         a = np.zeros((H, W))
+    elif name == "middle":                                         # a label change at H / 4 and at 3 H / 4, in every column
+        a = 1 + ((y >= H // 4) & (y < 3 * H // 4))
+    elif name == "late":                                           # the same, the first change 96 rows (3 tiles) later
+        a = 1 + ((y >= H // 4 + 96) & (y < 3 * H // 4))
     else:
         raise KeyError(name)
     a = a.astype(np.uint16)
     a.setflags(write=False)
     Z = max(1, int(a.max()) // 2) if name == "above" else max(1, int(a.max()))
     return a, Z
+
+
+# ---- the walk's geometry (csrc/mzones.hip) -----------------------------------------------------------------------------------------------
+TILE_W, TILE_H, WAVE_PIXELS = 64, 32, 512                          # a tile; the pixels of a tile that one wave takes (8 rows of 64)
+MOST_BLOCKS, PENDING = 2048, 65000                                 # kMostBlocks; the pixels a wave's int32 pending sums may hold
+
+
+def pending_reach(H, W, cap=None):
+    """One column of tiles (W <= 64) of a raster whose rows change value at H / 2: the workgroups, the longest run of tiles of one
+    workgroup inside one half, the pixels a wave meets on it, and the magnitude its sum of +-32767 would reach without the flush"""
+    assert W <= TILE_W
+    ntiles = -(-H // TILE_H)
+    grid = min(ntiles, MOST_BLOCKS if cap is None else cap)
+    per = -(-ntiles // grid)
+    run_tiles = min(ntiles // 2, per)
+    return {"ntiles": ntiles, "grid": grid, "run_tiles": run_tiles, "pixels": run_tiles * WAVE_PIXELS, "sum": run_tiles * WAVE_PIXELS * 32767}
 
 
 def inputs(H, W, features, lay):
